@@ -6,6 +6,12 @@
 (fresh child processes, before this process makes any GPU call); under torchrun (WORLD_SIZE set) it is
 one of the ranks.  Rank 0 prints ONE JSON line (contract in the task statement).
 
+A plain run sets up, warms up, times the K steps and prints the line: `value` / `ms_per_step` are those K steps.  `--full`
+adds everything else the benchmark measures, all outside the timed region: two profiled steps for the per-kernel times of
+the non-sweep kernels, the longer second run, the inputs-resident / configs[4] / other-precision legs, the stand-alone GEMM
+roofline, the fp64 parity step, the RCCL bucket probe and the CPU baseline.  `--dump-outputs DIR` writes what the last timed
+step computed (loss, per-utterance CTC loss and rewards, parameters after the update, gradients) as float32 DIR/<name>.npy.
+
 Workloads:
   headline  configs[2]+[1]: CTC + REINFORCE step, greedy (self-critical) baseline, lengths = T
   bucketed  configs[4]   : the reference's own reward hypothesis (prefix beam search, beam 16,
@@ -467,6 +473,31 @@ def allreduce_probe(trainer, dev, reps=10):
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def step_outputs(trainer, loss):
+    """What a caller of the timed path holds after its last step, copied to the host as float32: the loss, the per-utterance
+    CTC loss and rewards (trainer.last_stats), the parameters after the update and the gradients of the step (the flat
+    buffers without their leading flag words)."""
+    from policy_gradient_asr_amd.train_step import FLAG_PAD
+    nll, r_s, r_g = trainer.last_stats
+    arrays = {"loss": loss, "nll": nll, "reward_sampled": r_s, "reward_greedy": r_g,
+              "params": trainer.flat[FLAG_PAD:], "grads": trainer.gflat[FLAG_PAD:]}
+    return {k: v.detach().to(torch.float32).cpu().numpy() for k, v in arrays.items()}
+
+
+def dump_outputs(dirname, arrays):
+    """DIR/<name>.npy for every array; refuses more than DUMP_LIMIT_BYTES in all."""
+    import numpy as np
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise ValueError(f"outputs of {total} bytes exceed the dump limit of {DUMP_LIMIT_BYTES}")
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), np.asarray(a, dtype=np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -476,13 +507,20 @@ def main():
     ap.add_argument("--event-every", type=int, default=4, help="HIP-event timing of the sweeps and phases on every n-th timed step")
     ap.add_argument("--h2d", choices=("prefetch", "serial", "dma_prefetch", "dma_serial", "resident"), default="prefetch",
                     help="how each step's batch reaches HBM inside the timed region (resident: not at all, diagnostic)")
-    ap.add_argument("--long-steps", type=int, default=200, help="second, longer timed region after the headline one (0 = off)")
+    ap.add_argument("--long-steps", type=int, default=200, help="with --full: second, longer timed region after the headline one (0 = off)")
     ap.add_argument("--precision", choices=("f32", "bf16x3"), default="f32",
                     help="arithmetic of the timed step: f32 = the reference's (fp32-faithful six-product kernels), bf16x3 = the faster mode within 1e-3")
     ap.add_argument("--no-extra-legs", action="store_true", help="skip the configs[4] and other-precision legs that follow the headline")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-parity", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run the profiled steps, the extra legs, the GEMM roofline, the parity step and the "
+                         "CPU baseline (the --no-* / --long-steps options select among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as float32 DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus))
@@ -611,14 +649,19 @@ def main():
         print(f"[bench] timed region: {dt_local:.3f} s for {args.steps} steps", file=sys.stderr, flush=True)
     phases = hipops.profile_phases(step_marks)
     prof = hipops.profile_collect()
-    # the other instrumented kernels (GEMMs, beam search) are timed in two extra steps OUTSIDE the timed region
-    hipops.profile_reset(True)
-    for _ in range(2):
-        one_step()
-    extra = {k: (v[0] * n_sampled / 2.0, v[1] * n_sampled / 2.0) for k, v in hipops.profile_collect().items() if k not in prof}
-    prof.update(extra)
+    # taken before anything else steps the trainer: what the last TIMED step left
+    outputs = step_outputs(trainer, loss) if (args.dump_outputs and rank == 0) else None
+    if args.full:
+        # the other instrumented kernels (GEMMs, beam search) are timed in two extra steps OUTSIDE the timed region
+        hipops.profile_reset(True)
+        for _ in range(2):
+            one_step()
+        extra = {k: (v[0] * n_sampled / 2.0, v[1] * n_sampled / 2.0) for k, v in hipops.profile_collect().items() if k not in prof}
+        prof.update(extra)
     hipops.profile_reset(False)
     hipops.lstm_assert_no_timeouts()      # every rank: a timed-out sweep would make the number meaningless
+    if outputs is not None:
+        dump_outputs(args.dump_outputs, outputs)
 
     def timed_leg(fd, steps, warm, name=""):
         """ms per step (max over ranks) of `steps` steps fed by `fd`, barrier-bracketed like the headline region."""
@@ -641,19 +684,19 @@ def main():
 
     # ---- legs that follow the headline region (all outside it; every rank runs them: they contain collectives) ----
     long_run = None
-    if args.long_steps > 0:
+    if args.full and args.long_steps > 0:
         lms = timed_leg(feeder, args.long_steps, 0, "long_run")
         long_run = {"steps": args.long_steps, "ms_per_step": lms, "value": B_PER_GPU * world / (lms * 1e-3),
                     "note": "same workload and feeder as the headline region, timed again over a longer run"}
     resident_leg = None
-    if not bucketed and not args.no_extra_legs and args.h2d != "resident":
+    if args.full and not bucketed and not args.no_extra_legs and args.h2d != "resident":
         # the same step with its inputs ALREADY in HBM (no staging copy in the step): what the PCIe-inclusive headline costs
         rms = timed_leg(BatchFeeder(host, dev, "resident", trainer), 100, 5, "inputs_resident")
         resident_leg = {"ms_per_step": rms, "utt_per_s": B_PER_GPU * world / (rms * 1e-3), "steps": 100, "warmup": 5,
                         "note": "inputs resident in HBM before the timed region; the headline `value` stages every step's batch from pinned "
                                 "host memory inside the timed region (model.py:227-230's .to(device) is part of the reference's step)"}
     bucketed_leg = None
-    if not bucketed and not args.no_extra_legs:
+    if args.full and not bucketed and not args.no_extra_legs:
         # configs[4] in the same driver-run line: the reference's reward hypothesis (prefix beam search, beam 16) on
         # length-bucketed batches U[T/2,T], measured after the headline with the same model and trainer
         pool = bucketed_pool(rank, world, n_batches=8, seed=0)
@@ -668,7 +711,7 @@ def main():
                                     "U[500,1000] in length-bucketed batches balanced by frames, B=32/GPU, train mode, Adam, H2D inside"}
     precision_variants, parity_batch = None, None
     other = "bf16x3" if args.precision == "f32" else "f32"
-    if world == 1 and not bucketed and not args.no_extra_legs:
+    if args.full and world == 1 and not bucketed and not args.no_extra_legs:
         # the same step in the OTHER precision mode, outside the headline region (f32 = the reference's own arithmetic, torch fp32;
         # bf16x3 = two planes / three products, within north_star's 1e-3 bar)
         head_ms = (long_run or {}).get("ms_per_step", dt_local / args.steps * 1e3)
@@ -695,7 +738,7 @@ def main():
             per_rank_ms = [float(g.item()) / args.steps * 1e3 for g in gathered]
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
-        if not rehearse:
+        if args.full and not rehearse:
             ar = allreduce_probe(trainer, dev)
     if rank == 0:
         ms = dt / args.steps * 1e3
@@ -752,7 +795,7 @@ def main():
                                  "binds; floor_frac = the measured hand-off floor of this chip (0.5 us for the 16-way all-gather, "
                                  "tools/allgather.hip) / the per-step time: the fraction that says how close the chain is to its bound; "
                                  "frac is kept for continuity.  The MFMA-bound kernels of the step have their fractions in roofline_gemm"},
-            "roofline_gemm": gemm_probe(args.precision) if (world == 1 and not args.no_extra_legs) else None,
+            "roofline_gemm": gemm_probe(args.precision) if (args.full and world == 1 and not args.no_extra_legs) else None,
             "roofline_step": {"algorithmic_tflops": step_tf, "gflop_per_step_per_gpu": gflop_step_gpu,
                               "frac_vs_bf16_peak_over_products": step_tf / peak, "frac_vs_fp32_mfma_peak_157.3": step_tf / FP32_MFMA_PEAK_TF,
                               "note": "whole-step dense contraction flops (SURVEY §8d: 28.65 GFLOP per 1000-frame utterance) per GPU / ms_per_step"},
@@ -770,7 +813,7 @@ def main():
             out["inputs_resident"] = resident_leg
         if bucketed_leg is not None:
             out["bucketed"] = bucketed_leg
-        if world == 1 and not args.no_parity:
+        if args.full and world == 1 and not args.no_parity:
             with hipops.precision(args.precision):
                 out["max_rel_err_vs_fp64"] = parity_vs_fp64(model, trainer, parity_batch if parity_batch is not None else [t.to(dev) for t in host[0]])
         if precision_variants is not None:
@@ -778,7 +821,7 @@ def main():
                 precision_variants[args.precision]["max_rel_err_vs_fp64"] = {k: out["max_rel_err_vs_fp64"][k] for k in
                                                                          ("loss", "param_grads_maxnorm", "param_grads_maxnorm_tensor", "param_grads_frobenius")}
             out["precision_variants"] = precision_variants
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline()
         sys.stdout.flush()
         os.write(real_stdout, (json.dumps(out) + "\n").encode())

@@ -81,7 +81,7 @@ def test_roofline_record_counts_launches_per_sampled_step():
 
 
 def test_committed_bench_line_keeps_the_contract():
-    """profiles/r05_bench.json is one line of `python bench.py` on an MI355X (default precision f32): the driver's contract fields, the
+    """profiles/r05_bench.json is one line of `python bench.py --full` on an MI355X (default precision f32): the driver's contract fields, the
     roofline (latency-bound sweep with its hand-off floor), the MFMA-bound kernels' roofline_gemm, the CPU baseline and the round's extra
     legs are all there and consistent with each other; profiles/r05_bench_bf16x3.json is the same command with --precision bf16x3."""
     import json
@@ -125,3 +125,40 @@ def test_committed_bench_line_keeps_the_contract():
     assert reh["n_gpus"] == 2 and reh["rccl_world_size"] == 2 and "NOT a scaling number" in reh["collective_backend"]
     for leg in ("long_run", "inputs_resident", "bucketed"):
         assert reh[leg]["ms_per_step"] > 0
+
+
+def test_dump_outputs_writes_float32_npy_within_the_limit(tmp_path):
+    """--dump-outputs: one float32 DIR/<name>.npy per array, and nothing at all when the arrays exceed the 64 MB limit."""
+    import numpy as np
+    import pytest
+    arrays = {"loss": np.array(1.5, dtype=np.float32), "params": np.arange(10, dtype=np.float64)}
+    bench.dump_outputs(str(tmp_path / "out"), arrays)
+    assert sorted(os.listdir(tmp_path / "out")) == ["loss.npy", "params.npy"]
+    p = np.load(tmp_path / "out" / "params.npy")
+    assert p.dtype == np.float32 and p.tolist() == list(range(10)) and float(np.load(tmp_path / "out" / "loss.npy")) == 1.5
+    with pytest.raises(ValueError):
+        bench.dump_outputs(str(tmp_path / "big"), {"x": np.zeros(bench.DUMP_LIMIT_BYTES // 4 + 1, dtype=np.float32)})
+    assert not (tmp_path / "big").exists()
+
+
+def test_step_outputs_are_what_the_caller_of_a_step_holds():
+    """The loss, the per-utterance statistics of trainer.last_stats, and the parameters / gradients without the flag words."""
+    from policy_gradient_asr_amd.train_step import FLAG_PAD
+
+    class Trainer:
+        last_stats = (torch.tensor([1.0, 2.0]), torch.tensor([-0.5, -0.25]), torch.tensor([-0.75, 0.0]))
+        flat = torch.arange(FLAG_PAD + 5, dtype=torch.float32)
+        gflat = -torch.arange(FLAG_PAD + 5, dtype=torch.float32)
+
+    out = bench.step_outputs(Trainer(), torch.tensor(3.25))
+    assert sorted(out) == ["grads", "loss", "nll", "params", "reward_greedy", "reward_sampled"]
+    assert all(a.dtype.name == "float32" for a in out.values())
+    assert float(out["loss"]) == 3.25 and out["nll"].tolist() == [1.0, 2.0] and out["reward_sampled"].tolist() == [-0.5, -0.25]
+    assert out["params"].tolist() == list(range(FLAG_PAD, FLAG_PAD + 5)) and out["grads"].tolist() == [-v for v in range(FLAG_PAD, FLAG_PAD + 5)]
+
+
+def test_full_and_dump_outputs_are_options_and_steps_must_be_positive():
+    h = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=300)
+    assert h.returncode == 0 and "--full" in h.stdout and "--dump-outputs" in h.stdout
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 2 and "--steps must be at least 1" in r.stderr

@@ -2,7 +2,7 @@
 # like ab_env.sh but tolerant of extra stdout lines (RCCL's banner)
 for i in 1 2; do
   for e in "$@"; do
-    env $e timeout -k 10 100 python bench.py --no-cpu-baseline --no-parity 2>/dev/null | python -c "
+    env $e timeout -k 10 100 python bench.py --full --no-cpu-baseline --no-parity 2>/dev/null | python -c "
 import sys,json
 for line in sys.stdin:
     if line.startswith('{'):

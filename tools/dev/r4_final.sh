@@ -3,8 +3,8 @@
 R=${GRAFT_REPO_ROOT:-$(pwd)}; O=$R/gpurun_out/r4; mkdir -p $O; cd $R
 timeout -k 10 900 python3 -m pytest tests -m gpu -x -q > $O/full2.log 2>&1; echo "pytest rc=$?" >> $O/full2.log; tail -n 4 $O/full2.log
 timeout -k 10 200 python3 -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; echo "smoke rc=$?"; tail -n 2 $O/smoke.log
-timeout -k 10 400 python3 bench.py > $O/bench_f32.json 2> $O/bench_f32.err; echo "bench f32 rc=$?"
-timeout -k 10 400 python3 bench.py --precision bf16x3 --no-cpu-baseline > $O/bench_bf16x3.json 2> $O/bench_bf16x3.err; echo "bench bf16x3 rc=$?"
+timeout -k 10 400 python3 bench.py --full > $O/bench_f32.json 2> $O/bench_f32.err; echo "bench f32 rc=$?"
+timeout -k 10 400 python3 bench.py --full --precision bf16x3 --no-cpu-baseline > $O/bench_bf16x3.json 2> $O/bench_bf16x3.err; echo "bench bf16x3 rc=$?"
 python3 -c "
 import json
 for f in ('bench_f32','bench_bf16x3'):
