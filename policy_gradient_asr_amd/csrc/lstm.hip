@@ -225,6 +225,15 @@ __device__ __forceinline__ unsigned or4(u32x4 v) { return (v.x | v.y) | (v.z | v
 __device__ __forceinline__ unsigned bad4(u32x4 v, unsigned want) {
     return (((v.x ^ want) | (v.y ^ want)) | ((v.z ^ want) | (v.w ^ want))) & 0x00010001u;
 }
+// the same before the mask, two words per instruction: v_bitop3_b32 0x7e = (a ^ c) | (b ^ c) with c = want (wave-uniform, an SGPR).
+// The compiler does not form it by itself: for the three-plane forward poll (24 words per lane) it emitted one v_xor_b32 per word and
+// v_or3_b32 over those, ~33 VALU between the operand loads and the loop's exit branch; this is 12 + 6
+__device__ __forceinline__ unsigned xo2(unsigned a, unsigned b, unsigned want) {
+    unsigned r;
+    asm("v_bitop3_b32 %0, %1, %2, %3 bitop3:0x7e" : "=v"(r) : "v"(a), "v"(b), "s"(want));
+    return r;
+}
+__device__ __forceinline__ unsigned xo4(u32x4 v, unsigned want) { return xo2(v.x, v.y, want) | xo2(v.z, v.w, want); }
 
 // Every polling attempt starts with this: the exchange buffers are written by OTHER workgroups, which the
 // compiler cannot see.  Without it the (side-effect free) buffer loads may legally be hoisted out of the
@@ -595,6 +604,10 @@ __device__ __forceinline__ void dma16(const void* gsrc, void* lds_base) {
 // 4 x 16 x NP x 16 B and used 1/NP of each, 64 line requests per wave and step with two planes, 144 with three; the exchange is
 // request-bound, and stamps put the three-plane poll at 1259 cycles against 760.  Plane-major, an instruction reads 8
 // full lines: 32 / 48 requests.  PGASR_FWD_XLAYOUT=0 builds the old layout for A/B.)
+// Measured and NOT kept (NOTES.md 0.01): three planes exchanged as ONE fp32 word per value (16 KiB polled, 32 requests per wave and
+// step), split into the planes by each consuming wave in its MFMA gaps.  With the epoch tag in the mantissa LSB the planes, and so the
+// step's results, change; with a lossless word the split that re-forms the producer's tagged planes exactly costs 128 VALU per wave
+// and step, and the sweep was 1.34 ms against 1.28.
 // Measured and NOT kept (round 3, commit "second forward-sweep structure" in the history): the polled h_{t-1} itself through
 // LDS instead of the partial tiles -- every wave copies its validated k-quarter into an LDS image, one barrier, every wave
 // reads the whole 16 KB and multiplies all 256 k into its OWN 16 gate rows, so that the 16 x 16 MFMA output hands each lane
@@ -787,8 +800,11 @@ __global__ __launch_bounds__(LSTM_THREADS) void lstm_fwd_kernel(LstmArgs a) {
                 issue_loads();            // the operand loads ARE the poll
                 SpinGuard sg;
                 while (true) {
-                    unsigned bad = (bad4(vp[0][0], want) | bad4(vp[0][1], want)) | (bad4(vp[1][0], want) | bad4(vp[1][1], want));
-                    if constexpr (NP == 3) bad |= bad4(vp[0][2], want) | bad4(vp[1][2], want);
+                    unsigned bad;
+                    if constexpr (NP == 3)
+                        bad = (((xo4(vp[0][0], want) | xo4(vp[0][1], want)) | (xo4(vp[1][0], want) | xo4(vp[1][1], want))) |
+                               (xo4(vp[0][2], want) | xo4(vp[1][2], want))) & 0x00010001u;
+                    else bad = (bad4(vp[0][0], want) | bad4(vp[0][1], want)) | (bad4(vp[1][0], want) | bad4(vp[1][1], want));
                     if (!__any(bad != 0)) break;
 #ifdef PGASR_LSTM_DIAG
                     if (a.diag & 12) break;

@@ -1,5 +1,5 @@
 """When does the LAST fed backward sweep of an f32 train step wait, and when were its row tiles ready?  (development aid, round 5)
-Needs the diagnostic library (make -C policy_gradient_asr_amd/csrc lstmdiag; PGASR_HIP_LIB=.../libpgasr_hip_diag.so).  One step after a
+Needs the diagnostic library (make -C policy_gradient_asr_amd/csrc lstmdiag; PGASR_HIP_LIB=.../libpgasr_hip_lstmdiag.so).  One step after a
 warm-up; prints, per cluster of the layer-0 backward sweep, the steps at which member 0's loader found the staging ring late (step, us
 waited, us since the loader's first request) and, for the feed GEMM of that sweep, when each of the first row tiles of either direction was
 counted complete (us since the same origin)."""

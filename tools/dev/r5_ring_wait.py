@@ -1,5 +1,5 @@
 """What does the loader waves' wait for the staging ring cost, and are the helpers late?  (development aid, round 5; needs the diagnostic
-library: PGASR_HIP_LIB=.../libpgasr_hip_diag.so, built with -DPGASR_LSTM_DIAG.)  Runs headline train steps, then reads the counters the last
+library: PGASR_HIP_LIB=.../libpgasr_hip_lstmdiag.so, built with -DPGASR_LSTM_DIAG.)  Runs headline train steps, then reads the counters the last
 forward sweep (layer 3) and the last backward sweep (layer 1: fed + streamed) left in their workspaces' start-up words:
   loader of member 5 / member 0:  waits whose first poll found the slot not ready, retries, cycles in ring_wait, steps
   helper 0:                       cycles waiting for its turn (back-pressure), for the feed's tiles, moving a step's rows; steps; lead when ready"""
