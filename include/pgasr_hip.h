@@ -105,6 +105,44 @@ int pgasr_pg_step_coefs(const int32_t* paths, const int32_t* input_lengths, cons
                         float lam, float inv_global_batch, float* coef, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * A12  multi-sample REINFORCE ("greedy reward, self-critical, or batch mean").  K = 1..PGASR_MAX_SAMPLES sampled
+ * paths pi_k per utterance, rewards R_k = -ED(y, collapse(pi_k)) / max(L,1), and per sample a baseline b_k:
+ *   PGASR_BASELINE_HYPOTHESIS:     b_k = R_hyp, the reward of one greedy or beam hypothesis;
+ *   PGASR_BASELINE_LEAVE_ONE_OUT:  b_k = (S - R_k) / (K-1), S = sum_j R_j in j order, fp32 (K >= 2; needs no decode).
+ *   pg_coef[k,b] = lam * inv_global_batch / K * (R_k - b_k)
+ *   objective    = sum_b [ nll_b utt_scale_b - sum_k pg_coef[k,b] sum_{t<T_b} log p(pi_k[t,b]) ]
+ *   d(logits)    = utt_scale_b (softmax - occupancy) + sum_k pg_coef[k,b] (softmax - onehot(pi_k[t,b])), the K terms in k order.
+ * K = 1 with the hypothesis baseline is the single-sample objective above (pgasr_pg_rewards, pgasr_ctc_grad_from_lattice).
+ * K < 1 or K > PGASR_MAX_SAMPLES: PGASR_ERR_INVALID_ARG.
+ *
+ * pgasr_frame_sample_multi: pgasr_frame_argmax_sample with K draws per frame from one softmax; draw k uses Philox word 0 of
+ *   counter (t*ctr_stride+ctr_base+b, offset, 0, k) (third word 1 beyond the global batch, as there), so draw 0 is
+ *   pgasr_frame_argmax_sample's sample bit for bit.  sample_paths (K,T,B) int32; greedy_path (T,B) or NULL.
+ * pgasr_ctc_grad_from_lattice_multi: pgasr_ctc_grad_from_lattice's gradient pass with pg_paths (K,T,B) and pg_coef (K,B).
+ * pgasr_pg_rewards_multi: dist = [hypothesis row (HYPOTHESIS only), sample 0, .., sample K-1] x B edit distances (pgasr_edit_distance);
+ *   R_baseline (B) = b_k averaged over k in k order (= R_hyp for HYPOTHESIS), R_sample (K,B), pg_coef (K,B), utt_scale (B) as
+ *   pgasr_pg_rewards'.
+ * pgasr_pg_loss_value_multi: terms[b] = nll[b]*utt_scale[b] - sum_k pg_coef[k,b] * sum_{t<input_lengths[b]} log_probs[t,b,paths[k,t,b]];
+ *   each path's sum in pgasr_pg_loss_value's fixed order, the K products added in k order.  Deterministic.
+ * ---------------------------------------------------------------------------------------- */
+#define PGASR_MAX_SAMPLES 16
+#define PGASR_BASELINE_HYPOTHESIS 0
+#define PGASR_BASELINE_LEAVE_ONE_OUT 1
+int pgasr_frame_sample_multi(const float* scores, int T, int B, int V, int K,
+                             uint64_t seed, uint32_t offset, int ctr_stride, int ctr_base,
+                             int32_t* greedy_path, int32_t* sample_paths, void* stream);
+int pgasr_ctc_grad_from_lattice_multi(const float* log_probs, const int32_t* input_lengths,
+                                      const int32_t* target_lengths, int T, int B, int V, int Lmax, int blank,
+                                      const float* utt_scale, int K, const float* pg_coef, const int32_t* pg_paths,
+                                      float* grad_logits, void* workspace, size_t workspace_bytes, void* stream);
+int pgasr_pg_rewards_multi(const int32_t* dist, const int32_t* target_lengths, int B, int K, int baseline,
+                           float lam, float inv_global_batch, float* R_baseline, float* R_sample, float* pg_coef,
+                           float* utt_scale, void* stream);
+int pgasr_pg_loss_value_multi(const float* log_probs, const int32_t* paths, int K, const int32_t* input_lengths,
+                              const float* nll, const float* utt_scale, const float* pg_coef,
+                              int T, int B, int V, float* terms, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * A4  the CTC head as one kernel (model.py:52-55 as the build's Seq2Seq uses it): logits = x W^T + bias, log_probs = log_softmax.
  *   x (rows, K) fp32 with row stride ldx, W (V, K) row-major, bias (V) or NULL; logits / log_probs (rows, V), either may be NULL.
  *   Exact fp32 arithmetic (v_mfma_f32_32x32x2_f32) in every precision mode; one pass over x.  V <= 32, K % 64 == 0, K <= 1024.

@@ -367,6 +367,72 @@ __global__ __launch_bounds__(256) void ctc_grad_kernel(
     if (lane < V) grad[o + lane] = g;
 }
 
+// The CTC part of one (t,b) row's gradient, utt_scale_b * (softmax - occupancy) in this lane (0 when no alignment exists);
+// lpv / sm = this lane's log-prob / probability.  ctc_grad_kernel's own lines, for ctc_grad_multi_kernel: that kernel keeps
+// them inline (calling this helper changes its register allocation, and its code is to stay as measured).
+__device__ __forceinline__ float ctc_grad_row(float lpv, float sm, int lane, int t, int b, int T, int V, int Lb, int Smax, int blank,
+                                              CtcWs ws, const float* __restrict__ utt_scale) {
+    float g = 0.f;
+    const double nll = ws.nll64[b];
+    if (nll != INFINITY) {
+        const int S = 2 * Lb + 1;
+        const float* al = ws.alpha + ((size_t)b * T + t) * ws.SP;
+        const float* be = ws.beta + ((size_t)b * T + t) * ws.SP;
+        // log occupancy of state s = (alpha offset + beta offset) + [row maxima + nll - log p]: the bracket is O(10)
+        const double cst = ws.amax[(size_t)b * T + t] + ws.bmax[(size_t)b * T + t] + nll;
+        // blank occupancy: even states, all lanes, fixed butterfly order
+        const float lpb = __shfl(lpv, blank, 64);
+        const float cb = (float)(cst - (double)lpb);
+        float accb = 0.f;
+        for (int s = 2 * lane; s < S; s += 128)
+            accb += __expf((al[s] + be[s]) + cb);
+        accb = wave_sum(accb);
+        float occ = accb;
+        if (lane < V && lane != blank) {
+            const int32_t* lo = ws.lab_off + (size_t)b * (V + 1);
+            const int32_t* ls = ws.lab_states + (size_t)b * Smax;
+            float acc = 0.f;
+            const float cl = (float)(cst - (double)lpv);
+            for (int i = lo[lane]; i < lo[lane + 1]; ++i) {
+                const int s = ls[i];
+                acc += __expf((al[s] + be[s]) + cl);
+            }
+            occ = acc;
+        }
+        const float sc = utt_scale ? utt_scale[b] : 1.f;
+        g = sc * (sm - occ);
+    }
+    return g;
+}
+
+// Multi-sample REINFORCE (pgasr_ctc_grad_from_lattice_multi): the CTC part above, then the K terms
+// pg_coef[k,b] * (softmax - onehot(pg_paths[k,t,b])) added in k order.  One wave per (t,b), one pass over the gradient;
+// K = 1 is ctc_grad_kernel's per-utterance expression.
+__global__ __launch_bounds__(256) void ctc_grad_multi_kernel(
+    const float* __restrict__ lp, const int32_t* __restrict__ in_len, const int32_t* __restrict__ tg_len,
+    int T, int B, int V, int Lmax, int Smax, int blank, CtcWs ws,
+    const float* __restrict__ utt_scale, int K, const float* __restrict__ pg_coef,
+    const int32_t* __restrict__ pg_paths, float* __restrict__ grad) {
+    const int lane = threadIdx.x & 63;
+    const long long w = (long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (w >= (long long)T * B) return;
+    const int t = (int)(w / B), b = (int)(w % B);
+    int Tb = in_len[b]; Tb = Tb < 0 ? 0 : (Tb > T ? T : Tb);
+    int Lb = tg_len[b]; Lb = Lb < 0 ? 0 : (Lb > Lmax ? Lmax : Lb);
+    const size_t o = ((size_t)t * B + b) * V;
+    if (t >= Tb) { if (lane < V) grad[o + lane] = 0.f; return; }
+
+    const float lpv = (lane < V) ? lp[o + lane] : 0.f;
+    const float sm = (lane < V) ? __expf(lpv) : 0.f;
+    float g = ctc_grad_row(lpv, sm, lane, t, b, T, V, Lb, Smax, blank, ws, utt_scale);
+    const size_t TB = (size_t)T * B;
+    for (int k = 0; k < K; ++k) {
+        const int pk = pg_paths[k * TB + (size_t)t * B + b];
+        g += pg_coef[(size_t)k * B + b] * (sm - (lane == pk ? 1.f : 0.f));
+    }
+    if (lane < V) grad[o + lane] = g;
+}
+
 }  // namespace
 
 extern "C" size_t pgasr_ctc_workspace_bytes(int T, int B, int V, int Lmax) {
@@ -435,6 +501,29 @@ extern "C" int pgasr_ctc_grad_from_lattice(const float* log_probs, const int32_t
     PGASR_LAUNCH_KERNEL(ctc_grad_kernel, dim3(blocks), dim3(64 * wpb), 0, (hipStream_t)stream,
                        log_probs, input_lengths, target_lengths, T, B, V,
                        Lmax > 0 ? Lmax : 1, Smax, blank, ws, utt_scale, pg_coef, pg_path, pg_coef_per_frame ? 1 : 0, grad_logits);
+    PGASR_CHECK_LAUNCH();
+    return PGASR_OK;
+}
+
+// pgasr_ctc_grad_from_lattice with K sampled paths per utterance (multi-sample REINFORCE): pg_paths (K,T,B), pg_coef (K,B).
+extern "C" int pgasr_ctc_grad_from_lattice_multi(const float* log_probs, const int32_t* input_lengths,
+                                                 const int32_t* target_lengths, int T, int B, int V, int Lmax, int blank,
+                                                 const float* utt_scale, int K, const float* pg_coef, const int32_t* pg_paths,
+                                                 float* grad_logits, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!log_probs || !input_lengths || !target_lengths || !grad_logits || !pg_coef || !pg_paths) return PGASR_ERR_INVALID_ARG;
+    if (T <= 0 || B <= 0 || V <= 0 || Lmax < 0 || blank < 0 || blank >= V) return PGASR_ERR_INVALID_ARG;
+    if (K < 1 || K > PGASR_MAX_SAMPLES) return PGASR_ERR_INVALID_ARG;
+    const int Smax = 2 * Lmax + 1;
+    if (Smax > CTC_SMAX || V > CTC_VMAX) return PGASR_ERR_UNSUPPORTED;
+    CtcWs ws;
+    const size_t need = ctc_ws_layout(T, B, V, Smax, &ws, (char*)workspace);
+    if (!workspace || workspace_bytes < need) return PGASR_ERR_WORKSPACE;
+    const long long waves = (long long)T * B;
+    const int wpb = 4;
+    const unsigned blocks = (unsigned)((waves + wpb - 1) / wpb);
+    PGASR_LAUNCH_KERNEL(ctc_grad_multi_kernel, dim3(blocks), dim3(64 * wpb), 0, (hipStream_t)stream,
+                       log_probs, input_lengths, target_lengths, T, B, V,
+                       Lmax > 0 ? Lmax : 1, Smax, blank, ws, utt_scale, K, pg_coef, pg_paths, grad_logits);
     PGASR_CHECK_LAUNCH();
     return PGASR_OK;
 }

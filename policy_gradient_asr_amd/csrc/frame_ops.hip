@@ -53,6 +53,49 @@ __global__ __launch_bounds__(256) void frame_argmax_sample_kernel(
     }
 }
 
+// K draws per (t,b) row from ONE exp + prefix sum (multi-sample REINFORCE, pgasr_frame_sample_multi).  One wave per row as above;
+// lane j < K runs the Philox block of draw j (counter word 3 = j), so the K blocks cost one; each draw is then resolved by a ballot
+// against the same cdf.  Draw 0's counter, u, threshold and ballot are those of frame_argmax_sample_kernel: its sample bit for bit.
+__global__ __launch_bounds__(256) void frame_sample_multi_kernel(
+    const float* __restrict__ scores, long long rows, int B, int V, int K, uint32_t k0, uint32_t k1,
+    uint32_t offset, int ctr_stride, int ctr_base, int32_t* __restrict__ greedy, int32_t* __restrict__ samples) {
+    const int lane = threadIdx.x & 63;
+    const long long r = (long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (r >= rows) return;
+    const float x = (lane < V) ? scores[r * V + lane] : -INFINITY;
+    float bv = x; int bi = (lane < V) ? lane : 0x7fffffff;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(bv, o, 64);
+        const int oi = __shfl_xor(bi, o, 64);
+        if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
+    }
+    if (greedy && lane == 0) greedy[r] = bi;
+    const float e = (lane < V) ? __expf(x - bv) : 0.f;
+    float c = e;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const float up = __shfl_up(c, o, 64);
+        if (lane >= o) c += up;
+    }
+    const float total = __shfl(c, 63, 64);
+    const int bg_ = ctr_base + (int)(r % B);
+    const bool outside = bg_ >= ctr_stride;
+    const long long ctr = outside ? (long long)r : (r / B) * (long long)ctr_stride + bg_;
+    uint32_t rnd[4];
+    philox4x32_10((uint32_t)ctr, offset, outside ? 1u : 0u, (uint32_t)lane, k0, k1, rnd);
+    const float u = (float)(rnd[0] >> 8) * (1.0f / 16777216.0f);
+    int mine = 0;
+    for (int j = 0; j < K; ++j) {
+        const float thr = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(u), j)) * total;
+        const unsigned long long m = __ballot(lane < V && c <= thr);
+        int k = __popcll(m);
+        if (k > V - 1) k = V - 1;
+        if (lane == j) mine = k;
+    }
+    if (lane < K) samples[(size_t)lane * rows + r] = mine;
+}
+
 // one workgroup per (path set p, utterance b); ballot-compaction over frames
 __global__ __launch_bounds__(256) void ctc_collapse_kernel(
     const int32_t* __restrict__ paths, const int32_t* __restrict__ lengths, int T, int B, int blank,
@@ -138,6 +181,72 @@ __global__ __launch_bounds__(256) void pg_rewards_kernel(const int32_t* __restri
     R_g[b] = rg; R_s[b] = rs;
     coef[b] = (lam * inv_bg) * (rs - rg);
     utt_scale[b] = inv_bg / Lf;
+}
+
+// Multi-sample rewards (pgasr_pg_rewards_multi): dist = [hypothesis row (baseline 0 only), sample 0, .., sample K-1] x B.
+//   R_k = -ED_k / max(L,1);  b_k = R_hyp (baseline 0) or (S - R_k) / (K-1) with S = sum_j R_j in j order (baseline 1, leave one out);
+//   coef_k = lam/(Bg K) (R_k - b_k);  R_b = b_k averaged over k (in k order);  utt_scale = 1 / (Bg max(L,1)).
+// With K = 1 and baseline 0 every output is pg_rewards_kernel's bit for bit.
+__global__ __launch_bounds__(256) void pg_rewards_multi_kernel(const int32_t* __restrict__ dist, const int32_t* __restrict__ tg_len,
+                                                               int B, int K, int loo, float lam, float inv_bg, float* __restrict__ R_b,
+                                                               float* __restrict__ R_s, float* __restrict__ coef,
+                                                               float* __restrict__ utt_scale) {
+    const int b = blockIdx.x * 256 + threadIdx.x;
+    if (b >= B) return;
+    const int L = tg_len[b];
+    const float Lf = (float)(L > 1 ? L : 1);
+    const float scale = (lam * inv_bg) / (float)K;
+    const int32_t* ds = dist + (loo ? 0 : B);
+    if (!loo) {
+        const float rg = -(float)dist[b] / Lf;
+        for (int k = 0; k < K; ++k) {
+            const float rs = -(float)ds[(size_t)k * B + b] / Lf;
+            R_s[(size_t)k * B + b] = rs;
+            coef[(size_t)k * B + b] = scale * (rs - rg);
+        }
+        R_b[b] = rg;
+    } else {
+        float S = 0.f;
+        for (int k = 0; k < K; ++k) S += -(float)ds[(size_t)k * B + b] / Lf;
+        float bsum = 0.f;
+        for (int k = 0; k < K; ++k) {
+            const float rs = -(float)ds[(size_t)k * B + b] / Lf;
+            const float bk = (S - rs) / (float)(K - 1);
+            R_s[(size_t)k * B + b] = rs;
+            coef[(size_t)k * B + b] = scale * (rs - bk);
+            bsum += bk;
+        }
+        R_b[b] = bsum / (float)K;
+    }
+    utt_scale[b] = inv_bg / Lf;
+}
+
+// Value of the multi-sample objective per utterance: nll_b * utt_scale_b - sum_k coef[k,b] * sum_{t < T_b} log p(paths[k,t,b]).
+// One workgroup per utterance; per path the fixed-order reduction of pg_loss_value_kernel, the K products added in k order
+// (deterministic).
+__global__ __launch_bounds__(256) void pg_loss_value_multi_kernel(const float* __restrict__ lp, const int32_t* __restrict__ paths, int K,
+                                                                  const int32_t* __restrict__ in_len, const float* __restrict__ nll,
+                                                                  const float* __restrict__ utt_scale, const float* __restrict__ coef,
+                                                                  int T, int B, int V, float* __restrict__ terms) {
+    __shared__ float red[256];
+    const int b = blockIdx.x;
+    const int Tb = min(in_len[b], T);
+    float acc = 0.f;
+    for (int k = 0; k < K; ++k) {
+        const int32_t* path = paths + (size_t)k * T * B;
+        float s = 0.f;
+        for (int t = threadIdx.x; t < Tb; t += 256)
+            s += lp[((size_t)t * B + b) * V + path[(size_t)t * B + b]];
+        red[threadIdx.x] = s;
+        __syncthreads();
+        for (int o = 128; o > 0; o >>= 1) {
+            if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+            __syncthreads();
+        }
+        acc += coef[(size_t)k * B + b] * red[0];
+        __syncthreads();          // red[0] read by every thread before the next path overwrites it
+    }
+    if (threadIdx.x == 0) terms[b] = nll[b] * utt_scale[b] - acc;
 }
 
 // Value of the objective per utterance: nll_b * utt_scale_b - coef_b * sum_{t < T_b} log p(path[t,b]).
@@ -318,6 +427,49 @@ extern "C" int pgasr_pg_step_coefs(const int32_t* paths, const int32_t* input_le
     PGASR_LAUNCH_KERNEL(pg_step_coef_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream,
                        paths, input_lengths, prefix_dist, prefix_stride, token_lengths, target_lengths, T, B, blank, lam,
                        inv_global_batch, coef);
+    PGASR_CHECK_LAUNCH();
+    return PGASR_OK;
+}
+
+// ---- multi-sample REINFORCE (K sampled paths per utterance) ----
+extern "C" int pgasr_frame_sample_multi(const float* scores, int T, int B, int V, int K,
+                                        uint64_t seed, uint32_t offset, int ctr_stride, int ctr_base,
+                                        int32_t* greedy_path, int32_t* sample_paths, void* stream) {
+    if (!scores || !sample_paths || T <= 0 || B <= 0 || V <= 0) return PGASR_ERR_INVALID_ARG;
+    if (K < 1 || K > PGASR_MAX_SAMPLES) return PGASR_ERR_INVALID_ARG;
+    if (ctr_stride == 0) ctr_stride = B;
+    if (ctr_stride <= 0 || ctr_base < 0 || ctr_base >= ctr_stride) return PGASR_ERR_INVALID_ARG;
+    if (V > 64) return PGASR_ERR_UNSUPPORTED;
+    const long long rows = (long long)T * B;
+    const unsigned blocks = (unsigned)((rows + 3) / 4);
+    PGASR_LAUNCH_KERNEL(frame_sample_multi_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream,
+                       scores, rows, B, V, K, (uint32_t)(seed & 0xffffffffu), (uint32_t)(seed >> 32), offset,
+                       ctr_stride, ctr_base, greedy_path, sample_paths);
+    PGASR_CHECK_LAUNCH();
+    return PGASR_OK;
+}
+
+extern "C" int pgasr_pg_rewards_multi(const int32_t* dist, const int32_t* target_lengths, int B, int K, int baseline,
+                                      float lam, float inv_global_batch, float* R_baseline, float* R_sample, float* pg_coef,
+                                      float* utt_scale, void* stream) {
+    if (!dist || !target_lengths || !R_baseline || !R_sample || !pg_coef || !utt_scale || B <= 0) return PGASR_ERR_INVALID_ARG;
+    if (K < 1 || K > PGASR_MAX_SAMPLES) return PGASR_ERR_INVALID_ARG;
+    if (baseline != PGASR_BASELINE_HYPOTHESIS && baseline != PGASR_BASELINE_LEAVE_ONE_OUT) return PGASR_ERR_INVALID_ARG;
+    if (baseline == PGASR_BASELINE_LEAVE_ONE_OUT && K < 2) return PGASR_ERR_INVALID_ARG;
+    PGASR_LAUNCH_KERNEL(pg_rewards_multi_kernel, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream,
+                       dist, target_lengths, B, K, baseline == PGASR_BASELINE_LEAVE_ONE_OUT ? 1 : 0, lam, inv_global_batch,
+                       R_baseline, R_sample, pg_coef, utt_scale);
+    PGASR_CHECK_LAUNCH();
+    return PGASR_OK;
+}
+
+extern "C" int pgasr_pg_loss_value_multi(const float* log_probs, const int32_t* paths, int K, const int32_t* input_lengths,
+                                         const float* nll, const float* utt_scale, const float* pg_coef,
+                                         int T, int B, int V, float* terms, void* stream) {
+    if (!log_probs || !paths || !pg_coef || !input_lengths || !nll || !utt_scale || !terms) return PGASR_ERR_INVALID_ARG;
+    if (T <= 0 || B <= 0 || V <= 0 || K < 1 || K > PGASR_MAX_SAMPLES) return PGASR_ERR_INVALID_ARG;
+    PGASR_LAUNCH_KERNEL(pg_loss_value_multi_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream,
+                       log_probs, paths, K, input_lengths, nll, utt_scale, pg_coef, T, B, V, terms);
     PGASR_CHECK_LAUNCH();
     return PGASR_OK;
 }

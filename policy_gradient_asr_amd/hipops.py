@@ -216,6 +216,63 @@ def pg_loss_value(log_probs, path, input_lengths, nll, utt_scale, pg_coef):
     return terms
 
 
+# ---- multi-sample REINFORCE (include/pgasr_hip.h: K sampled paths per utterance, hypothesis or leave-one-out baseline) ----
+MAX_SAMPLES = 16                 # PGASR_MAX_SAMPLES
+BASELINES = {"hypothesis": 0, "leave_one_out": 1}
+
+
+def ctc_grad_from_lattice_multi(log_probs, input_lengths, target_lengths, handle, utt_scale, pg_coef, pg_paths):
+    """``ctc_grad_from_lattice`` with K sampled paths: pg_paths (K,T,B) int32, pg_coef (K,B) fp32; the K REINFORCE terms are
+    added in k order after the CTC part, in the same pass."""
+    lib = _lib.load()
+    ws, Lmax, blank = handle
+    T, B, V = log_probs.shape
+    _req(utt_scale, torch.float32, "utt_scale"); _req(pg_coef, torch.float32, "pg_coef"); _req(pg_paths, torch.int32, "pg_paths")
+    K = pg_paths.shape[0]
+    if pg_paths.dim() != 3 or tuple(pg_paths.shape[1:]) != (T, B) or tuple(pg_coef.shape) != (K, B):
+        raise _lib.PgasrError(f"ctc_grad_from_lattice_multi wants pg_paths (K,{T},{B}) and pg_coef (K,{B})")
+    grad = torch.empty_like(log_probs)
+    st = lib.pgasr_ctc_grad_from_lattice_multi(_p(log_probs), _p(input_lengths), _p(target_lengths), T, B, V, Lmax, blank,
+                                               _p(utt_scale), K, _p(pg_coef), _p(pg_paths), _p(grad), _p(ws), ws.numel(), _stream())
+    _lib.check(st, "pgasr_ctc_grad_from_lattice_multi")
+    return grad
+
+
+def pg_rewards_multi(dist, target_lengths, num_samples, lam, inv_global_batch, baseline="hypothesis"):
+    """dist ((H+K)*B,) int32: [hypothesis row (H = 1, baseline "hypothesis" only), sample 0, .., sample K-1] x B ->
+    (R_baseline (B), R_sample (K,B), pg_coef (K,B), utt_scale (B)) fp32."""
+    lib = _lib.load()
+    _req(dist, torch.int32, "dist"); _req(target_lengths, torch.int32, "target_lengths")
+    if baseline not in BASELINES:
+        raise ValueError(f"baseline must be one of {sorted(BASELINES)}")
+    B, K = target_lengths.numel(), int(num_samples)
+    H = 1 if baseline == "hypothesis" else 0
+    if dist.numel() != (H + K) * B:
+        raise _lib.PgasrError(f"pg_rewards_multi wants {(H + K)} x B distances")
+    out = torch.empty(2 * K + 2, B, dtype=torch.float32, device=dist.device)
+    R_b, R_s, coef, utt_scale = out[0], out[1:K + 1], out[K + 1:2 * K + 1], out[2 * K + 1]
+    st = lib.pgasr_pg_rewards_multi(_p(dist), _p(target_lengths), B, K, BASELINES[baseline], float(lam), float(inv_global_batch),
+                                    R_b.data_ptr(), R_s.data_ptr(), coef.data_ptr(), utt_scale.data_ptr(), _stream())
+    _lib.check(st, "pgasr_pg_rewards_multi")
+    return R_b, R_s, coef, utt_scale
+
+
+def pg_loss_value_multi(log_probs, paths, input_lengths, nll, utt_scale, pg_coef):
+    """Per-utterance value of the multi-sample objective, paths (K,T,B), pg_coef (K,B); sum() it for the loss."""
+    lib = _lib.load()
+    T, B, V = log_probs.shape
+    _req(log_probs, torch.float32, "log_probs"); _req(paths, torch.int32, "paths"); _req(nll, torch.float32, "nll")
+    _req(utt_scale, torch.float32, "utt_scale"); _req(pg_coef, torch.float32, "pg_coef")
+    K = paths.shape[0]
+    if paths.dim() != 3 or tuple(paths.shape[1:]) != (T, B) or tuple(pg_coef.shape) != (K, B):
+        raise _lib.PgasrError(f"pg_loss_value_multi wants paths (K,{T},{B}) and pg_coef (K,{B})")
+    terms = torch.empty(B, dtype=torch.float32, device=log_probs.device)
+    st = lib.pgasr_pg_loss_value_multi(_p(log_probs), _p(paths), K, _p(input_lengths), _p(nll), _p(utt_scale), _p(pg_coef),
+                                       T, B, V, _p(terms), _stream())
+    _lib.check(st, "pgasr_pg_loss_value_multi")
+    return terms
+
+
 FUSED_HEAD = _os_environ_get("PGASR_FUSED_HEAD", "1") != "0"
 
 
@@ -264,6 +321,28 @@ def frame_argmax_sample(scores, seed=0, offset=0, want_greedy=True, want_sample=
     st = lib.pgasr_frame_argmax_sample(_p(scores), T, B, V, int(seed) & (2 ** 64 - 1), int(offset) & 0xFFFFFFFF,
                                        int(batch_stride), int(batch_offset), _p(g), _p(s), _stream())
     _lib.check(st, "pgasr_frame_argmax_sample")
+    return g, s
+
+
+def frame_sample_multi(scores, num_samples, seed=0, offset=0, want_greedy=False, batch_stride=0, batch_offset=0, out=None):
+    """K draws per frame (include/pgasr_hip.h, pgasr_frame_sample_multi): returns (greedy (T,B) or None, samples (K,T,B)) int32.
+    Draw 0 is ``frame_argmax_sample``'s sample; batch_stride / batch_offset as there.  out = (greedy or None, samples) to
+    write into (contiguous int32)."""
+    lib = _lib.load()
+    _req(scores, torch.float32, "scores")
+    T, B, V = scores.shape
+    K = int(num_samples)
+    if out is not None:
+        g, s = out
+        _req(g, torch.int32, "out greedy"); _req(s, torch.int32, "out samples")
+        if tuple(s.shape) != (K, T, B) or (g is not None and tuple(g.shape) != (T, B)):
+            raise _lib.PgasrError(f"frame_sample_multi: out tensors must be ({T},{B}) and ({K},{T},{B}) int32")
+    else:
+        g = torch.empty(T, B, dtype=torch.int32, device=scores.device) if want_greedy else None
+        s = torch.empty(K, T, B, dtype=torch.int32, device=scores.device)
+    st = lib.pgasr_frame_sample_multi(_p(scores), T, B, V, K, int(seed) & (2 ** 64 - 1), int(offset) & 0xFFFFFFFF,
+                                      int(batch_stride), int(batch_offset), _p(g), _p(s), _stream())
+    _lib.check(st, "pgasr_frame_sample_multi")
     return g, s
 
 

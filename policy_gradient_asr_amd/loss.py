@@ -44,7 +44,17 @@ class PGCTCLossFn(torch.autograd.Function):
     characters that start at frames >= t (c(t) = characters started before t), for the sampled path and -- the baseline -- for the
     greedy path at the same frame (``pgasr_pg_step_coefs``); frame 0 carries the utterance coefficient.  Greedy baseline only (a
     beam hypothesis has no frame alignment).
-    Returns (loss, stats) where stats = (nll (B), R_s (B), R_g (B)) detached."""
+    ``num_samples = K > 1`` or ``baseline = "leave_one_out"`` (multi-sample REINFORCE, include/pgasr_hip.h): K paths pi_k per
+    utterance, draw k of frame t from Philox counter (t*Bg + b_global, offset, 0, k) -- draw 0 is the single-sample draw --, rewards
+    R_k = -ED(y_b, collapse(pi_k)) / max(L_b,1) and per sample a baseline b_k:
+      "hypothesis" (default): R_g, the reward of the greedy or beam hypothesis as above;
+      "leave_one_out": (S - R_k) / (K-1) with S = sum_j R_j in j order, fp32 (K >= 2; the greedy argmax and the beam search are skipped).
+        loss = sum_b [ nll_b / (Bg max(L_b,1))  -  sum_k lam / (Bg K) (R_k - b_k) sum_{t<T_b} log p(pi_k,t,b) ]
+    and d(logits) adds the K REINFORCE terms in k order after the CTC part.  K = 1 with the hypothesis baseline is the objective
+    above, on its own code path.  per_step takes K = 1 only.  The baseline of an utterance uses that utterance's samples alone, so
+    data-parallel ranks exchange nothing for it.
+    Returns (loss, stats) where stats = (nll (B), R_s (B), R_g (B)) detached; with K > 1, (nll (B), R_s (K,B), R_b (B)) where
+    R_b is the baseline averaged over k (R_g for "hypothesis")."""
 
     _lattice_streams = {}      # one side stream per calling stream
     # The trainer seeds loss.backward() with ITS OWN tensor of value 1 and registers that tensor's address here: only when
@@ -55,10 +65,12 @@ class PGCTCLossFn(torch.autograd.Function):
     unit_hits = 0              # how often the shortcut was taken (tests)
     @staticmethod
     def forward(ctx, logits, in_len, targets, tg_len, lam, seed, offset, global_batch, blank, beam=0, sample_base=-1, per_step=False,
-                log_probs=None):
+                log_probs=None, num_samples=1, baseline="hypothesis"):
         T, B, V = logits.shape
         if per_step and beam > 0:
             raise ValueError("per-step rewards need the frame-aligned greedy baseline (beam = 0)")
+        _check_samples(num_samples, baseline, per_step)
+        num_samples = int(num_samples)
         dev = logits.device
         # log-probs the head kernel already produced for exactly this tensor (model.Seq2Seq.logits), else one pass over the logits
         lp = log_probs
@@ -73,6 +85,9 @@ class PGCTCLossFn(torch.autograd.Function):
         PGCTCLossFn._lattice_streams[main.cuda_stream] = side
         # sample_base >= 0: this shard's first utterance in the GLOBAL batch -- the draws are then addressed globally
         lay = {"batch_stride": int(global_batch), "batch_offset": int(sample_base)} if sample_base >= 0 else {}
+        if num_samples != 1 or baseline != "hypothesis":
+            return PGCTCLossFn._forward_multi(ctx, lp, in_len, targets, tg_len, lam, seed, offset, global_batch, blank, beam, lay,
+                                              main, side, num_samples, baseline)
         side.wait_stream(main)
         with torch.cuda.stream(side):
             if beam > 0:
@@ -106,17 +121,70 @@ class PGCTCLossFn(torch.autograd.Function):
         return loss, nll, R_s, R_g
 
     @staticmethod
+    def _forward_multi(ctx, lp, in_len, targets, tg_len, lam, seed, offset, global_batch, blank, beam, lay, main, side, K, baseline):
+        """K sampled paths per utterance: the single-sample section's stream structure with the multi-sample kernels."""
+        T, B, V = lp.shape
+        dev = lp.device
+        loo = baseline == "leave_one_out"
+        P = K + (0 if loo else 1)          # path sets that are collapsed and scored: [hypothesis,] sample 0 .. K-1
+        side.wait_stream(main)
+        with torch.cuda.stream(side):
+            if loo:
+                # the baseline comes from the other samples: no greedy argmax, no beam search
+                _, samples = hipops.frame_sample_multi(lp, K, seed=seed, offset=offset, **lay)
+                tokens, tok_len = hipops.ctc_collapse(samples, in_len, blank=blank)
+            elif beam > 0:
+                _, samples = hipops.frame_sample_multi(lp, K, seed=seed, offset=offset, **lay)
+                tokens = torch.zeros(P, B, T, dtype=torch.int32, device=dev)
+                tok_len = torch.empty(P, B, dtype=torch.int32, device=dev)
+                hipops.ctc_beam_search(lp, in_len, beam=beam, blank=blank, collapse=True, out=(tokens[0], tok_len[0]))
+                hipops.ctc_collapse(samples, in_len, blank=blank, out=(tokens[1:], tok_len[1:]))
+            else:
+                paths = torch.empty(P, T, B, dtype=torch.int32, device=dev)          # greedy path, then the K samples
+                hipops.frame_sample_multi(lp, K, seed=seed, offset=offset, out=(paths[0], paths[1:]), **lay)
+                samples = paths[1:]
+                tokens, tok_len = hipops.ctc_collapse(paths, in_len, blank=blank)
+            dist = hipops.edit_distance(targets.repeat(P, 1), tg_len.repeat(P), tokens.view(P * B, T), tok_len.view(P * B))
+            R_b, R_s, coef, utt_scale = hipops.pg_rewards_multi(dist, tg_len, K, lam, 1.0 / float(global_batch), baseline=baseline)
+        nll, lattice = hipops.ctc_lattice(lp, targets, in_len, tg_len, blank=blank)
+        main.wait_stream(side)
+        for t_ in (samples, R_b, R_s, coef, utt_scale):
+            streams.hold(t_, main)
+        grad = hipops.ctc_grad_from_lattice_multi(lp, in_len, tg_len, lattice, utt_scale, coef, samples)
+        loss = hipops.pg_loss_value_multi(lp, samples, in_len, nll, utt_scale, coef).sum()
+        ctx.save_for_backward(grad)
+        ctx.mark_non_differentiable(nll, R_s, R_b)
+        ctx.set_materialize_grads(False)
+        return loss, nll, R_s, R_b
+
+    @staticmethod
     def backward(ctx, g, *unused):
         (grad,) = ctx.saved_tensors
         if PGCTCLossFn.unit_seed_ptr is not None and g.data_ptr() == PGCTCLossFn.unit_seed_ptr and g.numel() == 1:
             PGCTCLossFn.unit_hits += 1
-            return (grad,) + (None,) * 12
-        return (grad * g,) + (None,) * 12
+            return (grad,) + (None,) * 14
+        return (grad * g,) + (None,) * 14
+
+
+def _check_samples(num_samples, baseline, per_step=False):
+    """The multi-sample arguments of pg_ctc_loss / PolicyGradientTrainer, checked where the caller can read the reason."""
+    if baseline not in hipops.BASELINES:
+        raise ValueError(f"baseline must be one of {sorted(hipops.BASELINES)} (got {baseline!r})")
+    if isinstance(num_samples, bool) or int(num_samples) != num_samples:
+        raise ValueError(f"num_samples must be an integer (got {num_samples!r})")
+    if not 1 <= num_samples <= hipops.MAX_SAMPLES:
+        raise ValueError(f"num_samples {num_samples} outside 1 .. {hipops.MAX_SAMPLES}: the multi-sample kernels take at most "
+                         f"{hipops.MAX_SAMPLES} paths per utterance")
+    if baseline == "leave_one_out" and num_samples < 2:
+        raise ValueError("the leave-one-out baseline needs num_samples >= 2 (the other samples' rewards)")
+    if per_step and num_samples > 1:
+        raise ValueError("per-step rewards take one sampled path (num_samples = 1)")
 
 
 def pg_ctc_loss(logits, in_len, targets, tg_len, lam=1.0, seed=0, offset=0, global_batch=None, blank=0, beam=0, sample_base=-1,
-                per_step=False, log_probs=None):
+                per_step=False, log_probs=None, num_samples=1, baseline="hypothesis"):
     """beam > 0: the baseline reward comes from the prefix-beam-search hypothesis of that width (see PGCTCLossFn).
+    num_samples / baseline: multi-sample REINFORCE (see PGCTCLossFn); with num_samples > 1 the third returned tensor is R_s (K,B).
     sample_base >= 0 (data parallel): index of this shard's first utterance in the global batch; the sampled paths are
     then those of the single-process global batch with the same seed.
     log_probs: log_softmax(logits) if the caller already has it (the head kernel's by-product, ``logits.log_probs`` of
@@ -128,7 +196,8 @@ def pg_ctc_loss(logits, in_len, targets, tg_len, lam=1.0, seed=0, offset=0, glob
         if log_probs is not None and getattr(logits, "log_probs_version", None) != logits._version:
             log_probs = None
     return PGCTCLossFn.apply(logits, in_len, targets, tg_len, float(lam), int(seed), int(offset),
-                             int(global_batch or B), int(blank), int(beam), int(sample_base), bool(per_step), log_probs)
+                             int(global_batch or B), int(blank), int(beam), int(sample_base), bool(per_step), log_probs,
+                             num_samples, baseline)
 
 
 class CTCLoss(nn.Module):

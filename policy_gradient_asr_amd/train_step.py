@@ -245,13 +245,19 @@ class PolicyGradientTrainer(DataParallelStep):
     identity with the single-process run does not hold."""
 
     def __init__(self, model, lr=5e-4, lam=1.0, seed=0, blank=0, world_size=1, process_group=None, rank=0,
-                 reward_decoder="greedy", beam_size=16, precision=None, reward_mode="utterance"):
+                 reward_decoder="greedy", beam_size=16, precision=None, reward_mode="utterance", num_samples=1,
+                 reward_baseline="hypothesis"):
         """reward_mode: "utterance" (default) -- one reward R = -ED / |y| per utterance, the sum of the reference's per-step rewards
         (policy_grad.py:10-15) up to a constant the baseline removes; "per_step" -- the per-step rewards themselves, as rewards-to-go
         per frame against the greedy path's reward-to-go at the same frame (loss.PGCTCLossFn; greedy baseline only).
         reward_decoder: which hypothesis the self-critical baseline reward comes from -- "greedy" (best path) or
         "beam": the reference's own reward definition (policy_grad.py:6-8: prefix beam search -> collapse_fn ->
-        edit distance), decoded on the device with ``beam_size`` (BASELINE config 5: 16; the reference passes 5)."""
+        edit distance), decoded on the device with ``beam_size`` (BASELINE config 5: 16; the reference passes 5).
+        num_samples: sampled paths per utterance (1 .. MAX_SAMPLES; multi-sample REINFORCE, loss.PGCTCLossFn).
+        reward_baseline: "hypothesis" (default) -- every sample's reward against the reward_decoder hypothesis'; "leave_one_out" --
+        against the mean reward of the utterance's other samples (num_samples >= 2; no greedy or beam decode runs).
+        ``last_stats`` stays (nll, R_s, R_b), each (B,): R_s averaged over the samples, R_b the baseline averaged over them;
+        ``last_sample_rewards`` holds every sample's reward, (num_samples, B)."""
         super().__init__(model, lr=lr, world_size=world_size, process_group=process_group, precision=precision)
         if reward_decoder not in ("greedy", "beam"):
             raise ValueError("reward_decoder must be 'greedy' or 'beam'")
@@ -260,6 +266,8 @@ class PolicyGradientTrainer(DataParallelStep):
         if reward_mode == "per_step" and reward_decoder != "greedy":
             raise ValueError("per-step rewards need the frame-aligned greedy baseline (reward_decoder='greedy')")
         self.reward_decoder, self.beam_size, self.reward_mode = reward_decoder, int(beam_size), reward_mode
+        self._check_samples(num_samples, reward_baseline)
+        self.num_samples, self.reward_baseline = int(num_samples), reward_baseline
         self.lam = lam
         # ONE sampling seed for all ranks: a rank addresses its draws by GLOBAL utterance index (contiguous shards: rank *
         # local batch), so N ranks sample exactly the paths of one process holding the whole batch -- the N-rank REINFORCE
@@ -271,6 +279,7 @@ class PolicyGradientTrainer(DataParallelStep):
         self.blank = blank
         self._one = None
         self.last_stats = None
+        self.last_sample_rewards = None
         self.overlap_weight_grads = True
         # A batch whose size the fast orders do not take (feed-ahead: B <= 32; streamed weight gradients: B % 16 == 0 in "f32", B % 32
         # == 0 in "bf16x3") is padded with EMPTY utterances (no frames, no target) up to the next such size: the last, ragged batch of an
@@ -288,6 +297,14 @@ class PolicyGradientTrainer(DataParallelStep):
 
     MAX_LOCAL_BATCH = 128      # pgasr_lstm_layer_fwd/bwd: at most 16 clusters of 16 utterances are co-resident
     MAX_VOCAB = 64             # CTC lattice / frame kernels: one wave per (t, b) row
+    MAX_SAMPLES = 16           # multi-sample kernels: sampled paths per utterance (PGASR_MAX_SAMPLES)
+
+    def _check_samples(self, num_samples, reward_baseline):
+        """num_samples in 1 .. MAX_SAMPLES, a known baseline, leave_one_out with >= 2 samples, per_step with one."""
+        from .loss import _check_samples
+        if reward_baseline not in ("hypothesis", "leave_one_out"):
+            raise ValueError("reward_baseline must be 'hypothesis' or 'leave_one_out'")
+        _check_samples(num_samples, reward_baseline, self.reward_mode == "per_step")
 
     def _check_limits(self, x, targets):
         """The kernels' compiled-in limits, stated where the caller can read them (otherwise the first symptom is a
@@ -302,6 +319,7 @@ class PolicyGradientTrainer(DataParallelStep):
             raise ValueError(f"alphabet of {vocab} symbols > {self.MAX_VOCAB}: the CTC / sampling kernels hold one frame's scores in one wave")
         if self.reward_decoder == "beam" and self.beam_size > 128:
             raise ValueError("beam_size > 128 is not supported by pgasr_ctc_beam_search")
+        self._check_samples(self.num_samples, self.reward_baseline)
 
     def staging_stream(self):
         """The stream on which the NEXT batch is to be staged into HBM once ``step()`` has returned (model.py:227-230's
@@ -384,6 +402,11 @@ class PolicyGradientTrainer(DataParallelStep):
                                           offset=self.nstep + 1, global_batch=global_batch, blank=self.blank,
                                           beam=self.beam_size if self.reward_decoder == "beam" else 0,
                                           sample_base=self.rank * real_b if (self.world > 1 or padded) else -1,
-                                          per_step=self.reward_mode == "per_step")
+                                          per_step=self.reward_mode == "per_step", num_samples=self.num_samples,
+                                          baseline=self.reward_baseline)
+        R_all = R_s if R_s.dim() == 2 else R_s.view(1, -1)       # (K,B): every sample's reward
+        if R_s.dim() == 2:
+            R_s = R_s.mean(dim=0)
+        self.last_sample_rewards = R_all[:, :real_b] if padded else R_all
         self.last_stats = (nll[:real_b], R_s[:real_b], R_g[:real_b]) if padded else (nll, R_s, R_g)
         return loss
