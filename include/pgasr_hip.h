@@ -40,7 +40,9 @@ typedef enum pgasr_status {
 /* 4 (round 3): pgasr_adam_step(guards, applied), pgasr_lstm_pack_weights(planes), the feed phases, and the streamed order:
  * pgasr_lstm_wgrad_slabs, pgasr_lstm_layer_bwd_streamed, pgasr_lstm_wgrads_streamed(+_workspace_bytes), pgasr_stream_gate_sum.
  * 7 (round 5): pgasr_stream_gate_report, pgasr_lstm_cell_f32, pgasr_gemm_x6w_feed_phase_f32 / _head_items; the sampler's counters for
- * utterances beyond the global batch. */
+ * utterances beyond the global batch.  Added since without a version change: the multi-sample entries (pgasr_frame_sample_multi,
+ * pgasr_ctc_grad_from_lattice_multi, pgasr_pg_rewards_multi, pgasr_pg_loss_value_multi) and the word-reward entries (pgasr_word_ids,
+ * pgasr_pg_rewards_multi_ex). */
 #define PGASR_ABI_VERSION 7
 
 int pgasr_abi_version(void);
@@ -141,6 +143,31 @@ int pgasr_pg_rewards_multi(const int32_t* dist, const int32_t* target_lengths, i
 int pgasr_pg_loss_value_multi(const float* log_probs, const int32_t* paths, int K, const int32_t* input_lengths,
                               const float* nll, const float* utt_scale, const float* pg_coef,
                               int T, int B, int V, float* terms, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * A11  word-level (WER) reward, opt-in: R = -WED(y, yhat) / W(y), where a word is a run of tokens between delimiters -- exactly
+ * Python's str.split(" ") on the decoded string (n delimiters give n + 1 words, empty words included; an empty row is one empty
+ * word) --, WED the Levenshtein distance over the two word lists and W(y) >= 1 the reference's word count.
+ * pgasr_word_ids: N pairs in pgasr_edit_distance's layout (ref (N,ref_stride) with ref_len (N), hyp (N,hyp_stride) with hyp_len
+ *   (N)) and the delimiter token d >= 0 ->
+ *     ref_ids (N, ref_stride+1), hyp_ids (N, hyp_stride+1): per word, 1 + the index of its first occurrence in the pair's
+ *       (ref words ++ hyp words) -- two words of one pair get the same id iff their tokens are equal (confirmed on the tokens);
+ *       entries past the word count are not written;
+ *     ref_words (N), hyp_words (N): the word counts.
+ *   WED = pgasr_edit_distance(ref_ids, ref_words, ref_stride+1, hyp_ids, hyp_words, hyp_stride+1, ...).  One launch, deterministic,
+ *   no workspace.  N <= 0 or d < 0: PGASR_ERR_INVALID_ARG; a stride above PGASR_WORD_MAX_STRIDE: PGASR_ERR_UNSUPPORTED (the id rows
+ *   must stay within pgasr_edit_distance's 4095).
+ * pgasr_pg_rewards_multi_ex: pgasr_pg_rewards_multi with R normalised by max(reward_lengths, 1) (e.g. the word counts) and utt_scale
+ *   by max(target_lengths, 1) (the character counts of the CTC term).  reward_lengths == target_lengths gives
+ *   pgasr_pg_rewards_multi's bits, and with K = 1 and the hypothesis baseline pgasr_pg_rewards'.
+ * ---------------------------------------------------------------------------------------- */
+#define PGASR_WORD_MAX_STRIDE 4094
+int pgasr_word_ids(const int32_t* ref, const int32_t* ref_len, int ref_stride,
+                   const int32_t* hyp, const int32_t* hyp_len, int hyp_stride, int N, int delimiter,
+                   int32_t* ref_ids, int32_t* ref_words, int32_t* hyp_ids, int32_t* hyp_words, void* stream);
+int pgasr_pg_rewards_multi_ex(const int32_t* dist, const int32_t* reward_lengths, const int32_t* target_lengths, int B, int K,
+                              int baseline, float lam, float inv_global_batch, float* R_baseline, float* R_sample,
+                              float* pg_coef, float* utt_scale, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * A4  the CTC head as one kernel (model.py:52-55 as the build's Seq2Seq uses it): logits = x W^T + bias, log_probs = log_softmax.

@@ -238,22 +238,33 @@ def ctc_grad_from_lattice_multi(log_probs, input_lengths, target_lengths, handle
     return grad
 
 
-def pg_rewards_multi(dist, target_lengths, num_samples, lam, inv_global_batch, baseline="hypothesis"):
+def pg_rewards_multi(dist, target_lengths, num_samples, lam, inv_global_batch, baseline="hypothesis", reward_lengths=None):
     """dist ((H+K)*B,) int32: [hypothesis row (H = 1, baseline "hypothesis" only), sample 0, .., sample K-1] x B ->
-    (R_baseline (B), R_sample (K,B), pg_coef (K,B), utt_scale (B)) fp32."""
+    (R_baseline (B), R_sample (K,B), pg_coef (K,B), utt_scale (B)) fp32.
+    reward_lengths (B,) int32: normalise the rewards by these (the word counts of the word-level reward) instead of target_lengths,
+    which keep normalising utt_scale (pgasr_pg_rewards_multi_ex)."""
     lib = _lib.load()
     _req(dist, torch.int32, "dist"); _req(target_lengths, torch.int32, "target_lengths")
+    _req(reward_lengths, torch.int32, "reward_lengths")
     if baseline not in BASELINES:
         raise ValueError(f"baseline must be one of {sorted(BASELINES)}")
     B, K = target_lengths.numel(), int(num_samples)
     H = 1 if baseline == "hypothesis" else 0
     if dist.numel() != (H + K) * B:
         raise _lib.PgasrError(f"pg_rewards_multi wants {(H + K)} x B distances")
+    if reward_lengths is not None and reward_lengths.numel() != B:
+        raise _lib.PgasrError(f"pg_rewards_multi wants reward_lengths of {B} utterances")
     out = torch.empty(2 * K + 2, B, dtype=torch.float32, device=dist.device)
     R_b, R_s, coef, utt_scale = out[0], out[1:K + 1], out[K + 1:2 * K + 1], out[2 * K + 1]
-    st = lib.pgasr_pg_rewards_multi(_p(dist), _p(target_lengths), B, K, BASELINES[baseline], float(lam), float(inv_global_batch),
-                                    R_b.data_ptr(), R_s.data_ptr(), coef.data_ptr(), utt_scale.data_ptr(), _stream())
-    _lib.check(st, "pgasr_pg_rewards_multi")
+    if reward_lengths is None:
+        st = lib.pgasr_pg_rewards_multi(_p(dist), _p(target_lengths), B, K, BASELINES[baseline], float(lam), float(inv_global_batch),
+                                        R_b.data_ptr(), R_s.data_ptr(), coef.data_ptr(), utt_scale.data_ptr(), _stream())
+        _lib.check(st, "pgasr_pg_rewards_multi")
+    else:
+        st = lib.pgasr_pg_rewards_multi_ex(_p(dist), _p(reward_lengths), _p(target_lengths), B, K, BASELINES[baseline], float(lam),
+                                           float(inv_global_batch), R_b.data_ptr(), R_s.data_ptr(), coef.data_ptr(),
+                                           utt_scale.data_ptr(), _stream())
+        _lib.check(st, "pgasr_pg_rewards_multi_ex")
     return R_b, R_s, coef, utt_scale
 
 
@@ -394,6 +405,35 @@ def edit_distance(ref, ref_len, hyp, hyp_len, want_prefix=False):
                                  N, _p(dist), _p(prefix), _stream())
     _lib.check(st, "pgasr_edit_distance")
     return (dist, prefix) if want_prefix else dist
+
+
+WORD_MAX_STRIDE = 4094           # PGASR_WORD_MAX_STRIDE
+
+
+def word_ids(ref, ref_len, hyp, hyp_len, delimiter):
+    """Words = the runs between ``delimiter`` tokens (str.split(" ") on the decoded rows).  ref (N,R), hyp (N,Hy) int32 ->
+    (ref_ids (N,R+1), ref_words (N,), hyp_ids (N,Hy+1), hyp_words (N,)) int32: per word 1 + the index of its first occurrence in
+    the pair's ref words ++ hyp words (entries past a row's word count are not written), and the word counts."""
+    lib = _lib.load()
+    _req(ref, torch.int32, "ref"); _req(hyp, torch.int32, "hyp")
+    _req(ref_len, torch.int32, "ref_len"); _req(hyp_len, torch.int32, "hyp_len")
+    N, R = ref.shape
+    Hy = hyp.shape[1]
+    dev = ref.device
+    ref_ids = torch.empty(N, R + 1, dtype=torch.int32, device=dev)
+    hyp_ids = torch.empty(N, Hy + 1, dtype=torch.int32, device=dev)
+    counts = torch.empty(2, N, dtype=torch.int32, device=dev)
+    st = lib.pgasr_word_ids(_p(ref) if R else 0, _p(ref_len), R, _p(hyp) if Hy else 0, _p(hyp_len), Hy, N, int(delimiter),
+                            _p(ref_ids), counts[0].data_ptr(), _p(hyp_ids), counts[1].data_ptr(), _stream())
+    _lib.check(st, "pgasr_word_ids")
+    return ref_ids, counts[0], hyp_ids, counts[1]
+
+
+def word_edit_distance(ref, ref_len, hyp, hyp_len, delimiter):
+    """Word-level Levenshtein distance of N token-row pairs: ``word_ids`` then ``edit_distance`` on the id rows.
+    Returns (dist (N,), ref_words (N,), hyp_words (N,)) int32."""
+    ref_ids, ref_words, hyp_ids, hyp_words = word_ids(ref, ref_len, hyp, hyp_len, delimiter)
+    return edit_distance(ref_ids, ref_words, hyp_ids, hyp_words), ref_words, hyp_words
 
 
 def reinforce_grad(scores, path, coef, lengths, out=None, accumulate=False):

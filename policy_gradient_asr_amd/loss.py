@@ -53,6 +53,11 @@ class PGCTCLossFn(torch.autograd.Function):
     and d(logits) adds the K REINFORCE terms in k order after the CTC part.  K = 1 with the hypothesis baseline is the objective
     above, on its own code path.  per_step takes K = 1 only.  The baseline of an utterance uses that utterance's samples alone, so
     data-parallel ranks exchange nothing for it.
+    ``reward_unit = "word"`` (opt-in): every reward above -- sample, hypothesis and the leave-one-out baselines -- is the word-level
+    R = -WED(y, yhat) / W(y), words being the runs between ``word_delimiter`` tokens exactly as str.split(" ") cuts the decoded string
+    (n delimiters give n + 1 words, empty ones included), WED the Levenshtein distance over the word lists and W(y) >= 1 the target's
+    word count; the word step (pgasr_word_ids) runs on the side stream between collapse and edit distance.  The CTC term keeps
+    utt_scale = 1 / (Bg max(L_chars,1)).  Not with per_step (character-level only).
     Returns (loss, stats) where stats = (nll (B), R_s (B), R_g (B)) detached; with K > 1, (nll (B), R_s (K,B), R_b (B)) where
     R_b is the baseline averaged over k (R_g for "hypothesis")."""
 
@@ -65,11 +70,16 @@ class PGCTCLossFn(torch.autograd.Function):
     unit_hits = 0              # how often the shortcut was taken (tests)
     @staticmethod
     def forward(ctx, logits, in_len, targets, tg_len, lam, seed, offset, global_batch, blank, beam=0, sample_base=-1, per_step=False,
-                log_probs=None, num_samples=1, baseline="hypothesis"):
+                log_probs=None, num_samples=1, baseline="hypothesis", reward_unit="char", word_delimiter=None):
         T, B, V = logits.shape
         if per_step and beam > 0:
             raise ValueError("per-step rewards need the frame-aligned greedy baseline (beam = 0)")
         _check_samples(num_samples, baseline, per_step)
+        _check_unit(reward_unit, word_delimiter, per_step, blank=blank, vocab=V)
+        word = reward_unit == "word"
+        if word and max(T, targets.shape[1] if targets.dim() == 2 else 0) > hipops.WORD_MAX_STRIDE:
+            raise ValueError(f"the word-level reward takes at most {hipops.WORD_MAX_STRIDE} frames and target symbols per utterance "
+                             f"(pgasr_word_ids); got T = {T}")
         num_samples = int(num_samples)
         dev = logits.device
         # log-probs the head kernel already produced for exactly this tensor (model.Seq2Seq.logits), else one pass over the logits
@@ -85,9 +95,10 @@ class PGCTCLossFn(torch.autograd.Function):
         PGCTCLossFn._lattice_streams[main.cuda_stream] = side
         # sample_base >= 0: this shard's first utterance in the GLOBAL batch -- the draws are then addressed globally
         lay = {"batch_stride": int(global_batch), "batch_offset": int(sample_base)} if sample_base >= 0 else {}
+        wd = word_delimiter if word else None
         if num_samples != 1 or baseline != "hypothesis":
             return PGCTCLossFn._forward_multi(ctx, lp, in_len, targets, tg_len, lam, seed, offset, global_batch, blank, beam, lay,
-                                              main, side, num_samples, baseline)
+                                              main, side, num_samples, baseline, wd)
         side.wait_stream(main)
         with torch.cuda.stream(side):
             if beam > 0:
@@ -104,9 +115,16 @@ class PGCTCLossFn(torch.autograd.Function):
             if per_step:
                 dist, prefix = hipops.edit_distance(targets.repeat(2, 1), tg_len.repeat(2), tokens.view(2 * B, T), tok_len.view(2 * B),
                                                     want_prefix=True)
+            elif wd is not None:
+                # word-level reward: R = -WED / W(y), the CTC term's utt_scale stays on the character counts
+                dist, n_words = _word_distances(targets, tg_len, tokens, tok_len, 2, wd)
+                R_g, R_s, coef, utt_scale = hipops.pg_rewards_multi(dist, tg_len, 1, lam, 1.0 / float(global_batch),
+                                                                    reward_lengths=n_words)
+                R_s, coef = R_s[0], coef[0]
             else:
                 dist = hipops.edit_distance(targets.repeat(2, 1), tg_len.repeat(2), tokens.view(2 * B, T), tok_len.view(2 * B))
-            R_g, R_s, coef, utt_scale = hipops.pg_rewards(dist, tg_len, lam, 1.0 / float(global_batch))
+            if wd is None:
+                R_g, R_s, coef, utt_scale = hipops.pg_rewards(dist, tg_len, lam, 1.0 / float(global_batch))
             if per_step:
                 coef = hipops.pg_step_coefs(paths, in_len, prefix, tok_len.view(2 * B), tg_len, lam, 1.0 / float(global_batch), blank=blank)
         nll, lattice = hipops.ctc_lattice(lp, targets, in_len, tg_len, blank=blank)
@@ -121,7 +139,8 @@ class PGCTCLossFn(torch.autograd.Function):
         return loss, nll, R_s, R_g
 
     @staticmethod
-    def _forward_multi(ctx, lp, in_len, targets, tg_len, lam, seed, offset, global_batch, blank, beam, lay, main, side, K, baseline):
+    def _forward_multi(ctx, lp, in_len, targets, tg_len, lam, seed, offset, global_batch, blank, beam, lay, main, side, K, baseline,
+                       word_delimiter=None):
         """K sampled paths per utterance: the single-sample section's stream structure with the multi-sample kernels."""
         T, B, V = lp.shape
         dev = lp.device
@@ -144,8 +163,13 @@ class PGCTCLossFn(torch.autograd.Function):
                 hipops.frame_sample_multi(lp, K, seed=seed, offset=offset, out=(paths[0], paths[1:]), **lay)
                 samples = paths[1:]
                 tokens, tok_len = hipops.ctc_collapse(paths, in_len, blank=blank)
-            dist = hipops.edit_distance(targets.repeat(P, 1), tg_len.repeat(P), tokens.view(P * B, T), tok_len.view(P * B))
-            R_b, R_s, coef, utt_scale = hipops.pg_rewards_multi(dist, tg_len, K, lam, 1.0 / float(global_batch), baseline=baseline)
+            if word_delimiter is None:
+                dist = hipops.edit_distance(targets.repeat(P, 1), tg_len.repeat(P), tokens.view(P * B, T), tok_len.view(P * B))
+                n_words = None
+            else:
+                dist, n_words = _word_distances(targets, tg_len, tokens, tok_len, P, word_delimiter)
+            R_b, R_s, coef, utt_scale = hipops.pg_rewards_multi(dist, tg_len, K, lam, 1.0 / float(global_batch), baseline=baseline,
+                                                                reward_lengths=n_words)
         nll, lattice = hipops.ctc_lattice(lp, targets, in_len, tg_len, blank=blank)
         main.wait_stream(side)
         for t_ in (samples, R_b, R_s, coef, utt_scale):
@@ -162,8 +186,37 @@ class PGCTCLossFn(torch.autograd.Function):
         (grad,) = ctx.saved_tensors
         if PGCTCLossFn.unit_seed_ptr is not None and g.data_ptr() == PGCTCLossFn.unit_seed_ptr and g.numel() == 1:
             PGCTCLossFn.unit_hits += 1
-            return (grad,) + (None,) * 14
-        return (grad * g,) + (None,) * 14
+            return (grad,) + (None,) * 16
+        return (grad * g,) + (None,) * 16
+
+
+REWARD_UNITS = ("char", "word")
+
+
+def _word_distances(targets, tg_len, tokens, tok_len, P, delimiter):
+    """Word edit distances of the P x B (target, collapsed path) pairs and the targets' word counts (B,), both int32."""
+    B, T = tokens.shape[1], tokens.shape[2]
+    dist, ref_words, _ = hipops.word_edit_distance(targets.repeat(P, 1), tg_len.repeat(P), tokens.view(P * B, T),
+                                                   tok_len.view(P * B), delimiter)
+    return dist, ref_words[:B]
+
+
+def _check_unit(reward_unit, word_delimiter, per_step=False, blank=None, vocab=None):
+    """The word-reward arguments of pg_ctc_loss / PolicyGradientTrainer, checked before any kernel runs."""
+    if reward_unit not in REWARD_UNITS:
+        raise ValueError(f"reward_unit must be one of {REWARD_UNITS} (got {reward_unit!r})")
+    if reward_unit != "word":
+        return
+    if word_delimiter is None:
+        raise ValueError("reward_unit='word' needs word_delimiter, the token id of the alphabet's ' ' symbol")
+    if isinstance(word_delimiter, bool) or int(word_delimiter) != word_delimiter or word_delimiter < 0:
+        raise ValueError(f"word_delimiter must be a token id >= 0 (got {word_delimiter!r})")
+    if blank is not None and word_delimiter == blank:
+        raise ValueError(f"word_delimiter {word_delimiter} is the CTC blank: a collapsed path never holds it")
+    if vocab is not None and word_delimiter >= vocab:
+        raise ValueError(f"word_delimiter {word_delimiter} is outside the alphabet of {vocab} symbols")
+    if per_step:
+        raise ValueError("per-step rewards are character-level: reward_mode='per_step' does not take reward_unit='word'")
 
 
 def _check_samples(num_samples, baseline, per_step=False):
@@ -182,9 +235,11 @@ def _check_samples(num_samples, baseline, per_step=False):
 
 
 def pg_ctc_loss(logits, in_len, targets, tg_len, lam=1.0, seed=0, offset=0, global_batch=None, blank=0, beam=0, sample_base=-1,
-                per_step=False, log_probs=None, num_samples=1, baseline="hypothesis"):
+                per_step=False, log_probs=None, num_samples=1, baseline="hypothesis", reward_unit="char", word_delimiter=None):
     """beam > 0: the baseline reward comes from the prefix-beam-search hypothesis of that width (see PGCTCLossFn).
     num_samples / baseline: multi-sample REINFORCE (see PGCTCLossFn); with num_samples > 1 the third returned tensor is R_s (K,B).
+    reward_unit: "char" (default) or "word" -- the word-level reward R = -WED / W(y) with words split at the token
+    ``word_delimiter`` (see PGCTCLossFn); not with per_step.
     sample_base >= 0 (data parallel): index of this shard's first utterance in the global batch; the sampled paths are
     then those of the single-process global batch with the same seed.
     log_probs: log_softmax(logits) if the caller already has it (the head kernel's by-product, ``logits.log_probs`` of
@@ -197,7 +252,7 @@ def pg_ctc_loss(logits, in_len, targets, tg_len, lam=1.0, seed=0, offset=0, glob
             log_probs = None
     return PGCTCLossFn.apply(logits, in_len, targets, tg_len, float(lam), int(seed), int(offset),
                              int(global_batch or B), int(blank), int(beam), int(sample_base), bool(per_step), log_probs,
-                             num_samples, baseline)
+                             num_samples, baseline, reward_unit, word_delimiter)
 
 
 class CTCLoss(nn.Module):

@@ -54,6 +54,16 @@ def evaluate(s1, s2):
     return cer, wer
 
 
+def edit_counts(targets, tg_len, tokens, tok_len, delimiter):
+    """What ``evaluate`` computes for a whole batch of token rows, without the division and without a host round trip:
+    targets (B,L) / tokens (B,T) int32 on the GPU with their lengths, words split at the token ``delimiter`` (the alphabet's " ").
+    Returns (character distance, character length, word distance, word count), each (B,) int32 on the device; CER = cd / cl and
+    WER = wd / wc as evaluate() gives them on the decoded strings."""
+    cd = hipops.edit_distance(targets, tg_len, tokens, tok_len)
+    wd, wc, _ = hipops.word_edit_distance(targets, tg_len, tokens, tok_len, delimiter)
+    return cd, tg_len, wd, wc
+
+
 def save_predictions(target, predicted, model_path):
     """predicted.txt with one 'target|prediction' line per utterance (metrics.py:33-37)."""
     path = os.path.join(model_path, "predicted.txt")

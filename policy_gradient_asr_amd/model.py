@@ -209,7 +209,7 @@ def _check_features(features, n_feats, dataset):
 
 def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset=None, dev_dataset=None,
           n_feats=120, lam=1.0, lr=5e-4, resume=True, log_every=10, seed=0, bucket_by_length=True, features="mfcc",
-          precision="f32", num_samples=1, reward_baseline="hypothesis"):
+          precision="f32", num_samples=1, reward_baseline="hypothesis", reward_unit="char"):
     """Epoch loop of model.py:186-274 on the MI355X path: per-epoch train loss -> train_loss.npy,
     validation CTC loss -> val_losses.npy, model_best.pth / model_last.pth (state_dicts, reference
     names), plus checkpoint_last.pth (model + Adam moments + epoch) from which ``resume`` restarts
@@ -221,7 +221,9 @@ def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset
     precision: "f32" (default: the reference's torch-fp32 arithmetic, model.py:38-44) or "bf16x3" (opt-in, ~20 % faster,
     within 1e-3 on loss and gradients) -- hipops.PRECISION_MODES.
     num_samples / reward_baseline: sampled paths per utterance and the baseline their rewards are scored against ("hypothesis":
-    the greedy path's reward; "leave_one_out": the mean reward of the other samples, num_samples >= 2) -- PolicyGradientTrainer."""
+    the greedy path's reward; "leave_one_out": the mean reward of the other samples, num_samples >= 2) -- PolicyGradientTrainer.
+    reward_unit: "char" (default) or "word" -- the word-level reward -WED / W(y), words split at the alphabet's " " symbol (which
+    alphabet.txt must then hold)."""
     import os
     import numpy as np
     import torch.utils.data as tud
@@ -232,7 +234,13 @@ def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset
     from .train_step import PolicyGradientTrainer
 
     print("Num epochs:", num_epochs, "Batch size:", batch_size)
-    alphabet, char2ind = _read_alphabet(os.path.join(corpus_path, "alphabet.txt"))
+    alphabet_path = os.path.join(corpus_path, "alphabet.txt")
+    alphabet, char2ind = _read_alphabet(alphabet_path)
+    word_delimiter = None
+    if reward_unit == "word":
+        if " " not in char2ind:
+            raise ValueError(f"reward_unit='word' splits words at the alphabet's ' ' symbol, and {alphabet_path} has none")
+        word_delimiter = char2ind[" "]
     dev = torch.device("cuda", device if isinstance(device, int) else 0) if not isinstance(device, torch.device) else device
     os.makedirs(model_path, exist_ok=True)
     collate_custom = functools.partial(_collate, device=dev, features=features)
@@ -247,7 +255,7 @@ def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset
     model = model.to(dev)
     _check_features(features, n_feats, train_dataset)
     trainer = PolicyGradientTrainer(model, lr=lr, lam=lam, seed=seed, precision=precision, num_samples=num_samples,
-                                    reward_baseline=reward_baseline)
+                                    reward_baseline=reward_baseline, reward_unit=reward_unit, word_delimiter=word_delimiter)
     losses, val_losses, best, start_epoch = [], [], 9999999.0, 1
     ckpt = os.path.join(model_path, "checkpoint_last.pth")
     if resume and os.path.exists(ckpt):
@@ -261,7 +269,8 @@ def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset
         # epoch's masks and differs from an uninterrupted one
         model.encoder._drop_calls = st.get("drop_calls", 0)
         model.encoder.dropout_seed = st.get("dropout_seed", model.encoder.dropout_seed)
-        for k, want in (("lr", lr), ("lam", lam), ("num_samples", num_samples), ("reward_baseline", reward_baseline)):
+        for k, want in (("lr", lr), ("lam", lam), ("num_samples", num_samples), ("reward_baseline", reward_baseline),
+                        ("reward_unit", reward_unit)):
             if k in st and st[k] != want:
                 print("Warning: resuming with {}={} but the checkpoint was written with {}".format(k, want, st[k]))
         losses, val_losses, best, start_epoch = st["losses"], st["val_losses"], st["best"], st["epoch"] + 1
@@ -317,7 +326,8 @@ def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset
                     "applied_steps": trainer.applied_steps(),
                     "losses": losses, "val_losses": val_losses, "best": best, "epoch": epoch,
                     "drop_calls": model.encoder._drop_calls, "dropout_seed": model.encoder.dropout_seed,
-                    "lr": lr, "lam": lam, "num_samples": num_samples, "reward_baseline": reward_baseline}, ckpt)
+                    "lr": lr, "lam": lam, "num_samples": num_samples, "reward_baseline": reward_baseline,
+                    "reward_unit": reward_unit}, ckpt)
     return losses, val_losses
 
 

@@ -246,7 +246,7 @@ class PolicyGradientTrainer(DataParallelStep):
 
     def __init__(self, model, lr=5e-4, lam=1.0, seed=0, blank=0, world_size=1, process_group=None, rank=0,
                  reward_decoder="greedy", beam_size=16, precision=None, reward_mode="utterance", num_samples=1,
-                 reward_baseline="hypothesis"):
+                 reward_baseline="hypothesis", reward_unit="char", word_delimiter=None):
         """reward_mode: "utterance" (default) -- one reward R = -ED / |y| per utterance, the sum of the reference's per-step rewards
         (policy_grad.py:10-15) up to a constant the baseline removes; "per_step" -- the per-step rewards themselves, as rewards-to-go
         per frame against the greedy path's reward-to-go at the same frame (loss.PGCTCLossFn; greedy baseline only).
@@ -257,7 +257,10 @@ class PolicyGradientTrainer(DataParallelStep):
         reward_baseline: "hypothesis" (default) -- every sample's reward against the reward_decoder hypothesis'; "leave_one_out" --
         against the mean reward of the utterance's other samples (num_samples >= 2; no greedy or beam decode runs).
         ``last_stats`` stays (nll, R_s, R_b), each (B,): R_s averaged over the samples, R_b the baseline averaged over them;
-        ``last_sample_rewards`` holds every sample's reward, (num_samples, B)."""
+        ``last_sample_rewards`` holds every sample's reward, (num_samples, B).
+        reward_unit: "char" (default) -- R = -ED / |y| over characters; "word" -- R = -WED / W(y) over words, split at the token
+        ``word_delimiter`` (the alphabet's " "; not the blank) like str.split(" "), for every sample and baseline reward (the CTC term
+        stays normalised by the character count; not with reward_mode="per_step"; T <= MAX_WORD_FRAMES)."""
         super().__init__(model, lr=lr, world_size=world_size, process_group=process_group, precision=precision)
         if reward_decoder not in ("greedy", "beam"):
             raise ValueError("reward_decoder must be 'greedy' or 'beam'")
@@ -268,6 +271,8 @@ class PolicyGradientTrainer(DataParallelStep):
         self.reward_decoder, self.beam_size, self.reward_mode = reward_decoder, int(beam_size), reward_mode
         self._check_samples(num_samples, reward_baseline)
         self.num_samples, self.reward_baseline = int(num_samples), reward_baseline
+        self._check_unit(reward_unit, word_delimiter, blank)
+        self.reward_unit, self.word_delimiter = reward_unit, (None if word_delimiter is None else int(word_delimiter))
         self.lam = lam
         # ONE sampling seed for all ranks: a rank addresses its draws by GLOBAL utterance index (contiguous shards: rank *
         # local batch), so N ranks sample exactly the paths of one process holding the whole batch -- the N-rank REINFORCE
@@ -298,6 +303,13 @@ class PolicyGradientTrainer(DataParallelStep):
     MAX_LOCAL_BATCH = 128      # pgasr_lstm_layer_fwd/bwd: at most 16 clusters of 16 utterances are co-resident
     MAX_VOCAB = 64             # CTC lattice / frame kernels: one wave per (t, b) row
     MAX_SAMPLES = 16           # multi-sample kernels: sampled paths per utterance (PGASR_MAX_SAMPLES)
+    MAX_WORD_FRAMES = 4094     # word-level reward: token rows of at most PGASR_WORD_MAX_STRIDE (frames, target symbols)
+
+    def _check_unit(self, reward_unit, word_delimiter, blank):
+        """A known reward unit; "word" with a delimiter in [0, V) that is not the blank, and not with per-step rewards."""
+        from .loss import _check_unit
+        vocab = getattr(getattr(self.model, "head", None), "out_features", None)
+        _check_unit(reward_unit, word_delimiter, self.reward_mode == "per_step", blank=blank, vocab=vocab)
 
     def _check_samples(self, num_samples, reward_baseline):
         """num_samples in 1 .. MAX_SAMPLES, a known baseline, leave_one_out with >= 2 samples, per_step with one."""
@@ -320,6 +332,10 @@ class PolicyGradientTrainer(DataParallelStep):
         if self.reward_decoder == "beam" and self.beam_size > 128:
             raise ValueError("beam_size > 128 is not supported by pgasr_ctc_beam_search")
         self._check_samples(self.num_samples, self.reward_baseline)
+        self._check_unit(self.reward_unit, self.word_delimiter, self.blank)
+        if self.reward_unit == "word" and max(x.shape[2], targets.shape[1]) > self.MAX_WORD_FRAMES:
+            raise ValueError(f"T = {x.shape[2]} frames (targets of {targets.shape[1]} symbols): the word-level reward takes token rows of at "
+                             f"most {self.MAX_WORD_FRAMES} (pgasr_word_ids)")
 
     def staging_stream(self):
         """The stream on which the NEXT batch is to be staged into HBM once ``step()`` has returned (model.py:227-230's
@@ -403,7 +419,8 @@ class PolicyGradientTrainer(DataParallelStep):
                                           beam=self.beam_size if self.reward_decoder == "beam" else 0,
                                           sample_base=self.rank * real_b if (self.world > 1 or padded) else -1,
                                           per_step=self.reward_mode == "per_step", num_samples=self.num_samples,
-                                          baseline=self.reward_baseline)
+                                          baseline=self.reward_baseline, reward_unit=self.reward_unit,
+                                          word_delimiter=self.word_delimiter)
         R_all = R_s if R_s.dim() == 2 else R_s.view(1, -1)       # (K,B): every sample's reward
         if R_s.dim() == 2:
             R_s = R_s.mean(dim=0)
