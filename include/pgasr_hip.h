@@ -41,8 +41,9 @@ typedef enum pgasr_status {
  * pgasr_lstm_wgrad_slabs, pgasr_lstm_layer_bwd_streamed, pgasr_lstm_wgrads_streamed(+_workspace_bytes), pgasr_stream_gate_sum.
  * 7 (round 5): pgasr_stream_gate_report, pgasr_lstm_cell_f32, pgasr_gemm_x6w_feed_phase_f32 / _head_items; the sampler's counters for
  * utterances beyond the global batch.  Added since without a version change: the multi-sample entries (pgasr_frame_sample_multi,
- * pgasr_ctc_grad_from_lattice_multi, pgasr_pg_rewards_multi, pgasr_pg_loss_value_multi) and the word-reward entries (pgasr_word_ids,
- * pgasr_pg_rewards_multi_ex). */
+ * pgasr_ctc_grad_from_lattice_multi, pgasr_pg_rewards_multi, pgasr_pg_loss_value_multi), the word-reward entries (pgasr_word_ids,
+ * pgasr_pg_rewards_multi_ex) and the gradient-clipping entries (pgasr_grad_norm_ws_bytes, pgasr_grad_norm_clip,
+ * pgasr_adam_step_clipped). */
 #define PGASR_ABI_VERSION 7
 
 int pgasr_abi_version(void);
@@ -573,6 +574,32 @@ int pgasr_stream_copy(const void* src, void* dst, unsigned long long bytes, int 
 int pgasr_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, unsigned long long n,
                     int step, float lr, float beta1, float beta2, float eps, float weight_decay,
                     const int32_t* guard0, const int32_t* guard1, int32_t* applied, void* stream);
+/* Gradient clipping by global norm (torch.nn.utils.clip_grad_norm_) and a non-finite guard, on the device (csrc/optim.hip).
+ * The clip state is PGASR_CLIP_STATE_BYTES of device memory, 16-byte aligned, zeroed once by its owner:
+ *   float norm; float scale; int32 nonfinite; int32 pad; int32 n_clipped; int32 n_nonfinite; int32 pad2[2];
+ * pgasr_grad_norm_clip(grad, n, max_norm, ws, ws_bytes, state, stream): over the n fp32 words of grad (16-byte aligned)
+ *   norm      = sqrt(sum g^2), squares and sums in fp64 (the square of an fp32 is exact there), rounded to fp32 once;
+ *   scale     = min(1, max_norm / (norm + 1e-6f)) in fp32 -- clip_grad_norm_'s arithmetic; exactly 1.0f when nothing is clipped;
+ *   nonfinite = 1 iff the sum is not finite, i.e. some element is inf or NaN; scale is then 0;
+ *   n_nonfinite += nonfinite; n_clipped += (scale < 1 and the sum is finite) -- running counts, kept on the device.
+ *   max_norm must be > 0; +inf is allowed and means "measure and guard, never scale".
+ *   The result is a function of (grad, n) only: a grid derived from n, fixed orders inside a lane, a wave and a workgroup (no
+ *   floating-point atomics), one fp64 partial per workgroup parked in ws, and a second one-wave launch that adds the partials in a
+ *   fixed order (stream order is its only synchronisation: ws needs no initialisation and holds nothing between calls).  The same
+ *   gradient gives the same 32 bits of norm and scale, run to run and rank to rank.
+ *   ws: pgasr_grad_norm_ws_bytes(n) bytes (at most 8 KB), 8-byte aligned.
+ *   n == 0, a null or misaligned pointer, max_norm not > 0 (NaN included) or ws_bytes too small: PGASR_ERR_INVALID_ARG, nothing launched.
+ * pgasr_adam_step_clipped: pgasr_adam_step with g := state.scale * g (rounded on its own: scale == 1.0f gives pgasr_adam_step's bits)
+ *   and state.nonfinite != 0 as one more guard -- the update is skipped, parameters and moments untouched, applied not advanced.
+ *   clip_state: a state pgasr_grad_norm_clip has written on the same stream (null or misaligned: PGASR_ERR_INVALID_ARG). */
+#define PGASR_CLIP_STATE_BYTES 32
+size_t pgasr_grad_norm_ws_bytes(unsigned long long n);
+int pgasr_grad_norm_clip(const float* grad, unsigned long long n, float max_norm, void* ws, size_t ws_bytes,
+                         void* state, void* stream);
+int pgasr_adam_step_clipped(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, unsigned long long n,
+                            int step, float lr, float beta1, float beta2, float eps, float weight_decay,
+                            const int32_t* guard0, const int32_t* guard1, int32_t* applied, const void* clip_state,
+                            void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * N3  feature front end (data.py:44-79): MFCC(40) + delta + delta-delta of torchaudio's defaults

@@ -61,6 +61,10 @@ SIGNATURES = {
     "pgasr_stream_copy": (C.c_int, [c_ptr, c_ptr, C.c_ulonglong, C.c_int, c_ptr]),
     "pgasr_adam_step": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, C.c_ulonglong, C.c_int, C.c_float, C.c_float,
                                   C.c_float, C.c_float, C.c_float, c_i32p, c_i32p, c_i32p, c_ptr]),
+    "pgasr_adam_step_clipped": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, C.c_ulonglong, C.c_int, C.c_float, C.c_float,
+                                          C.c_float, C.c_float, C.c_float, c_i32p, c_i32p, c_i32p, c_ptr, c_ptr]),
+    "pgasr_grad_norm_ws_bytes": (C.c_size_t, [C.c_ulonglong]),
+    "pgasr_grad_norm_clip": (C.c_int, [c_f32p, C.c_ulonglong, C.c_float, c_ptr, C.c_size_t, c_ptr, c_ptr]),
     "pgasr_gemm_workspace_bytes": (C.c_size_t, [C.c_int] * 5),
     "pgasr_gemm_f32": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
                                  c_f32p, C.c_int, C.c_longlong, c_f32p, C.c_int, C.c_longlong,

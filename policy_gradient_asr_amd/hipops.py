@@ -1018,12 +1018,48 @@ def stream_copy(dst, src, workgroups=8):
     return dst
 
 
+CLIP_STATE_WORDS = 8    # PGASR_CLIP_STATE_BYTES / 4: norm, scale (fp32); nonfinite, pad, n_clipped, n_nonfinite (int32); 2 spare
+
+
+def clip_state(device):
+    """A zeroed clip state for ``grad_norm_clip`` / ``adam_step(clip_state=...)``: fp32 (8,); ``state[0]`` is the norm, ``state[1]`` the
+    scale, ``clip_state_counts`` reads the integer words."""
+    return torch.zeros(CLIP_STATE_WORDS, dtype=torch.float32, device=device)
+
+
+def clip_state_counts(state):
+    """(nonfinite, n_clipped, n_nonfinite) of a clip state (synchronises)."""
+    w = state.view(torch.int32).tolist()
+    return w[2], w[4], w[5]
+
+
+def grad_norm_clip(grad, max_norm, state=None):
+    """Global L2 norm of the flat fp32 gradient ``grad`` and what clip_grad_norm_ derives from it (``pgasr_grad_norm_clip``): writes
+    norm, scale = min(1, max_norm / (norm + 1e-6)) and the non-finite flag into ``state`` (``clip_state``; a new one when None) and
+    advances its counts.  Nothing is scaled here: ``adam_step(clip_state=state)`` applies the scale.  Returns the state."""
+    lib = _lib.load()
+    _req(grad, torch.float32, "grad")
+    if state is None:
+        state = clip_state(grad.device)
+    _req(state, torch.float32, "state")
+    if state.numel() != CLIP_STATE_WORDS:
+        raise _lib.PgasrError(f"grad_norm_clip: state must hold {CLIP_STATE_WORDS} words (hipops.clip_state)")
+    n = grad.numel()
+    nbytes = lib.pgasr_grad_norm_ws_bytes(n)
+    ws = _workspace(nbytes, grad.device, "grad_norm")
+    with _timed("grad_norm_kernel"):
+        _lib.check(lib.pgasr_grad_norm_clip(_p(grad), n, float(max_norm), _p(ws), nbytes, _p(state), _stream()), "pgasr_grad_norm_clip")
+    return state
+
+
 def adam_step(param, grad, exp_avg, exp_avg_sq, step, lr=5e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, guards=(),
-              applied=None):
+              applied=None, clip_state=None):
     """guards: up to two device addresses of int32 words (``lstm_error_words``, or the word of the gradient buffer that
     carried the error flag through the all-reduce); the update is skipped while one is set.
     applied: int32 (2,) GPU tensor, zeroed once: the count of updates really applied lives there (bias correction then
-    ignores skipped calls); ``step`` stays the 1-based count of calls."""
+    ignores skipped calls); ``step`` stays the 1-based count of calls.
+    clip_state: a state ``grad_norm_clip`` has written for this gradient on the current stream: the gradient enters as
+    scale * g, and a non-finite gradient skips the update like a set guard (``pgasr_adam_step_clipped``)."""
     lib = _lib.load()
     for t, nm in ((param, "param"), (grad, "grad"), (exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq")):
         _req(t, torch.float32, nm)
@@ -1031,6 +1067,14 @@ def adam_step(param, grad, exp_avg, exp_avg_sq, step, lr=5e-4, betas=(0.9, 0.999
     if applied is not None and applied.numel() != 2:
         raise _lib.PgasrError("adam_step: applied must hold two int32 words")
     g = list(guards)[:2] + [0, 0]
+    if clip_state is not None:
+        _req(clip_state, torch.float32, "clip_state")
+        if clip_state.numel() != CLIP_STATE_WORDS:
+            raise _lib.PgasrError(f"adam_step: clip_state must hold {CLIP_STATE_WORDS} words (hipops.clip_state)")
+        _lib.check(lib.pgasr_adam_step_clipped(_p(param), _p(grad), _p(exp_avg), _p(exp_avg_sq), param.numel(), int(step),
+                                               float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay),
+                                               g[0], g[1], _p(applied), _p(clip_state), _stream()), "pgasr_adam_step_clipped")
+        return
     _lib.check(lib.pgasr_adam_step(_p(param), _p(grad), _p(exp_avg), _p(exp_avg_sq), param.numel(), int(step),
                                    float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay),
                                    g[0], g[1], _p(applied), _stream()), "pgasr_adam_step")

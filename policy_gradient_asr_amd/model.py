@@ -209,7 +209,7 @@ def _check_features(features, n_feats, dataset):
 
 def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset=None, dev_dataset=None,
           n_feats=120, lam=1.0, lr=5e-4, resume=True, log_every=10, seed=0, bucket_by_length=True, features="mfcc",
-          precision="f32", num_samples=1, reward_baseline="hypothesis", reward_unit="char"):
+          precision="f32", num_samples=1, reward_baseline="hypothesis", reward_unit="char", max_grad_norm=None):
     """Epoch loop of model.py:186-274 on the MI355X path: per-epoch train loss -> train_loss.npy,
     validation CTC loss -> val_losses.npy, model_best.pth / model_last.pth (state_dicts, reference
     names), plus checkpoint_last.pth (model + Adam moments + epoch) from which ``resume`` restarts
@@ -223,7 +223,10 @@ def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset
     num_samples / reward_baseline: sampled paths per utterance and the baseline their rewards are scored against ("hypothesis":
     the greedy path's reward; "leave_one_out": the mean reward of the other samples, num_samples >= 2) -- PolicyGradientTrainer.
     reward_unit: "char" (default) or "word" -- the word-level reward -WED / W(y), words split at the alphabet's " " symbol (which
-    alphabet.txt must then hold)."""
+    alphabet.txt must then hold).
+    max_grad_norm: None (default) or a bound > 0 on the global L2 norm of a step's gradient, clipped on the device inside the step
+    (clip_grad_norm_ between backward and the update; a step whose gradient holds an inf / NaN is skipped) -- PolicyGradientTrainer.
+    The log lines then carry the last gradient norm, and the end of an epoch the counts of clipped and skipped steps."""
     import os
     import numpy as np
     import torch.utils.data as tud
@@ -255,7 +258,8 @@ def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset
     model = model.to(dev)
     _check_features(features, n_feats, train_dataset)
     trainer = PolicyGradientTrainer(model, lr=lr, lam=lam, seed=seed, precision=precision, num_samples=num_samples,
-                                    reward_baseline=reward_baseline, reward_unit=reward_unit, word_delimiter=word_delimiter)
+                                    reward_baseline=reward_baseline, reward_unit=reward_unit, word_delimiter=word_delimiter,
+                                    max_grad_norm=max_grad_norm)
     losses, val_losses, best, start_epoch = [], [], 9999999.0, 1
     ckpt = os.path.join(model_path, "checkpoint_last.pth")
     if resume and os.path.exists(ckpt):
@@ -270,7 +274,7 @@ def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset
         model.encoder._drop_calls = st.get("drop_calls", 0)
         model.encoder.dropout_seed = st.get("dropout_seed", model.encoder.dropout_seed)
         for k, want in (("lr", lr), ("lam", lam), ("num_samples", num_samples), ("reward_baseline", reward_baseline),
-                        ("reward_unit", reward_unit)):
+                        ("reward_unit", reward_unit), ("max_grad_norm", max_grad_norm)):
             if k in st and st[k] != want:
                 print("Warning: resuming with {}={} but the checkpoint was written with {}".format(k, want, st[k]))
         losses, val_losses, best, start_epoch = st["losses"], st["val_losses"], st["best"], st["epoch"] + 1
@@ -293,12 +297,17 @@ def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset
             if log_every and step % log_every == 0:
                 val = float(loss)                      # the host synchronises here anyway: check the sweeps' error words
                 hipops.lstm_assert_no_timeouts()       # (until then the guarded Adam has skipped every invalid update)
-                print("Step {}/{}. Loss: {:>4f}".format(step, len(loader), val))
+                if max_grad_norm is None:
+                    print("Step {}/{}. Loss: {:>4f}".format(step, len(loader), val))
+                else:
+                    print("Step {}/{}. Loss: {:>4f} Grad norm: {:>4f}".format(step, len(loader), val, float(trainer.last_grad_norm)))
         losses.append(float(acc) / max(len(loader), 1))
         hipops.lstm_assert_no_timeouts()          # .. and before anything of this epoch is written to disk
         streams.release()                         # the host has synchronised: nothing of the last step needs keeping alive
         np.save(os.path.join(model_path, "train_loss.npy"), np.array(losses))
         print("Epoch:{}/{} Training loss:{:>4f}".format(epoch, num_epochs, losses[-1]))
+        if max_grad_norm is not None:
+            print("Epoch:{}/{} Clipped steps: {} Skipped (non-finite gradient): {}".format(epoch, num_epochs, *trainer.clip_counts()))
 
         curr = losses[-1]
         if dev_dataset is not None:                                 # validation (model.py:246-268)
@@ -327,7 +336,7 @@ def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset
                     "losses": losses, "val_losses": val_losses, "best": best, "epoch": epoch,
                     "drop_calls": model.encoder._drop_calls, "dropout_seed": model.encoder.dropout_seed,
                     "lr": lr, "lam": lam, "num_samples": num_samples, "reward_baseline": reward_baseline,
-                    "reward_unit": reward_unit}, ckpt)
+                    "reward_unit": reward_unit, "max_grad_norm": max_grad_norm}, ckpt)
     return losses, val_losses
 
 

@@ -67,16 +67,36 @@ def balance_by_frames(lengths, world):
     return out
 
 
+def check_max_grad_norm(max_grad_norm):
+    """None (no clipping), or a real number > 0 (``float("inf")``: measure and guard, never scale) -> None or float."""
+    if max_grad_norm is None:
+        return None
+    import numbers
+    if isinstance(max_grad_norm, bool) or not isinstance(max_grad_norm, numbers.Real):
+        raise ValueError(f"max_grad_norm must be None or a real number > 0 (got {max_grad_norm!r})")
+    v = float(max_grad_norm)
+    if not v > 0:        # <= 0 and NaN
+        raise ValueError(f"max_grad_norm must be None or a real number > 0 (got {max_grad_norm!r})")
+    return v
+
+
 class DataParallelStep:
-    """zero_grad -> forward_loss -> backward -> all-reduce(sum) -> Adam, on flat buffers.
+    """zero_grad -> forward_loss -> backward -> all-reduce(sum) -> [clip by global norm] -> Adam, on flat buffers.
     Subclasses provide ``forward_loss(batch, global_batch) -> scalar loss`` already divided by the
     GLOBAL batch size, so the summed gradient is the global-batch gradient."""
 
-    def __init__(self, model, lr=5e-4, world_size=1, process_group=None, precision=None):
+    def __init__(self, model, lr=5e-4, world_size=1, process_group=None, precision=None, max_grad_norm=None):
         """precision: "f32" (the library default: the reference's arithmetic, torch fp32 -- every big product as six bf16 MFMA terms
         of three-plane operands, exact to 2^-24: three-plane sweeps, six-product W_ih projections / input and weight gradients,
         gemm_x6.hip; the small products on the exact fp32 MFMA) or "bf16x3" (opt-in: 3-term products of two-plane operands, within
-        the 1e-3 bar, ~20 % faster) -- hipops.PRECISION_MODES; None = whatever mode is set when a step runs."""
+        the 1e-3 bar, ~20 % faster) -- hipops.PRECISION_MODES; None = whatever mode is set when a step runs.
+        max_grad_norm: None (default: the step as it always was) or a bound > 0 on the L2 norm of the REDUCED gradient
+        (torch.nn.utils.clip_grad_norm_ between backward and the update: g := g * min(1, max / (norm + 1e-6))), measured over
+        gflat[FLAG_PAD:] after the last all-reduce -- the same numbers on every rank, so replicas stay bit-identical -- and applied
+        inside the Adam kernel; a gradient that holds an inf or NaN skips the update on every rank (parameters and moments untouched,
+        not counted by ``applied_steps``).  float("inf") measures and guards without ever scaling.  No host synchronisation:
+        ``last_grad_norm`` / ``clip_counts()`` read the result."""
+        self.max_grad_norm = check_max_grad_norm(max_grad_norm)
         if precision is not None:
             from . import hipops
             if precision not in hipops.PRECISION_MODES:
@@ -98,6 +118,16 @@ class DataParallelStep:
         else:   # CPU is only the gloo plumbing test: torch's Adam
             self.opt = torch.optim.Adam([self.flat_param], lr=lr)
             self.applied_cpu = 0
+        # clipping: the device-resident state of pgasr_grad_norm_clip (norm, scale, non-finite flag, counts); on the CPU plumbing
+        # path a 0-d tensor and two host counts
+        self.clip_state = None
+        self.last_grad_norm = None          # 0-d tensor: the pre-clip norm of the last step's reduced gradient (reading it synchronises)
+        self._clip_counts_cpu = [0, 0]
+        if self.max_grad_norm is not None and self.flat.is_cuda:
+            from . import hipops
+            self.clip_state = hipops.clip_state(self.flat.device)
+            self.last_grad_norm = self.clip_state[0]
+            self._clip_grad = self.gflat[FLAG_PAD:]     # what the norm is taken over: not the flag word and its pad
         self.nstep = 0                      # CALLS of step() (seeds the sampler / dropout offsets); see applied_steps()
         self.collective = self.world > 1    # tests set this on a 1-rank group to exercise the plumbing
         self._early = None                  # (split, work) of an all-reduce issued during backward
@@ -164,6 +194,15 @@ class DataParallelStep:
             return self.applied_cpu
         return int(self.applied[self.nstep & 1].item())
 
+    def clip_counts(self):
+        """(steps whose gradient was scaled down, steps skipped for a non-finite gradient) so far (synchronises); (0, 0)
+        without ``max_grad_norm``."""
+        if self.clip_state is None:
+            return tuple(self._clip_counts_cpu)
+        from . import hipops
+        _, n_clipped, n_nonfinite = hipops.clip_state_counts(self.clip_state)
+        return n_clipped, n_nonfinite
+
     def set_applied_steps(self, n):
         """Checkpoint resume: the bias correction continues from ``n`` applied updates."""
         if self.opt is not None:
@@ -222,13 +261,33 @@ class DataParallelStep:
             # the update is skipped on the device -- on every rank, since the guard is the reduced flag -- and does not
             # count for the bias correction; the host raises at its next check (hipops.lstm_assert_no_timeouts)
             guards = [self.gflat.data_ptr()] if self.collective else hipops.lstm_error_words(self.flat.device)
+            if self.clip_state is not None:
+                # both buckets are in: the norm of the reduced gradient (not of the flag word and its pad), on the critical
+                # stream between the last all-reduce and Adam, which reads scale and the non-finite flag from the state
+                hipops.grad_norm_clip(self._clip_grad, self.max_grad_norm, self.clip_state)
             hipops.adam_step(self.flat, self.gflat, self.exp_avg, self.exp_avg_sq, self.nstep, lr=self.lr,
-                             guards=guards, applied=self.applied)
-        elif self.collective and float(self.gflat[0]) > 0:
-            pass                                # CPU plumbing (gloo tests): same rule, checked on the host
+                             guards=guards, applied=self.applied, clip_state=self.clip_state)
         else:
-            self.opt.step()
-            self.applied_cpu += 1
+            # CPU plumbing (gloo tests): the same rules, checked on the host
+            flagged = self.collective and float(self.gflat[0]) > 0
+            scale = 1.0
+            if self.max_grad_norm is not None:
+                norm = self.gflat[FLAG_PAD:].double().norm().float()
+                self.last_grad_norm = norm
+                if not bool(torch.isfinite(norm)):
+                    self._clip_counts_cpu[1] += 1
+                    flagged = True
+                else:
+                    scale = float(torch.clamp(self.max_grad_norm / (norm + 1e-6), max=1.0))
+                    self._clip_counts_cpu[0] += scale < 1.0
+            if not flagged:
+                if scale < 1.0:         # Adam sees scale * g; gflat keeps the unclipped gradient, as on the device
+                    self.flat_param.grad = self.gflat * scale
+                    self.opt.step()
+                    self.flat_param.grad = self.gflat
+                else:
+                    self.opt.step()
+                self.applied_cpu += 1
         return loss.detach()
 
 
@@ -246,7 +305,7 @@ class PolicyGradientTrainer(DataParallelStep):
 
     def __init__(self, model, lr=5e-4, lam=1.0, seed=0, blank=0, world_size=1, process_group=None, rank=0,
                  reward_decoder="greedy", beam_size=16, precision=None, reward_mode="utterance", num_samples=1,
-                 reward_baseline="hypothesis", reward_unit="char", word_delimiter=None):
+                 reward_baseline="hypothesis", reward_unit="char", word_delimiter=None, max_grad_norm=None):
         """reward_mode: "utterance" (default) -- one reward R = -ED / |y| per utterance, the sum of the reference's per-step rewards
         (policy_grad.py:10-15) up to a constant the baseline removes; "per_step" -- the per-step rewards themselves, as rewards-to-go
         per frame against the greedy path's reward-to-go at the same frame (loss.PGCTCLossFn; greedy baseline only).
@@ -260,8 +319,11 @@ class PolicyGradientTrainer(DataParallelStep):
         ``last_sample_rewards`` holds every sample's reward, (num_samples, B).
         reward_unit: "char" (default) -- R = -ED / |y| over characters; "word" -- R = -WED / W(y) over words, split at the token
         ``word_delimiter`` (the alphabet's " "; not the blank) like str.split(" "), for every sample and baseline reward (the CTC term
-        stays normalised by the character count; not with reward_mode="per_step"; T <= MAX_WORD_FRAMES)."""
-        super().__init__(model, lr=lr, world_size=world_size, process_group=process_group, precision=precision)
+        stays normalised by the character count; not with reward_mode="per_step"; T <= MAX_WORD_FRAMES).
+        max_grad_norm: clip the reduced gradient to this global L2 norm inside the step and skip non-finite gradients
+        (DataParallelStep; None = off); ``last_grad_norm`` and ``clip_counts()`` report."""
+        super().__init__(model, lr=lr, world_size=world_size, process_group=process_group, precision=precision,
+                         max_grad_norm=max_grad_norm)
         if reward_decoder not in ("greedy", "beam"):
             raise ValueError("reward_decoder must be 'greedy' or 'beam'")
         if reward_mode not in ("utterance", "per_step"):
