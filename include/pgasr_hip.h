@@ -42,8 +42,8 @@ typedef enum pgasr_status {
  * 7 (round 5): pgasr_stream_gate_report, pgasr_lstm_cell_f32, pgasr_gemm_x6w_feed_phase_f32 / _head_items; the sampler's counters for
  * utterances beyond the global batch.  Added since without a version change: the multi-sample entries (pgasr_frame_sample_multi,
  * pgasr_ctc_grad_from_lattice_multi, pgasr_pg_rewards_multi, pgasr_pg_loss_value_multi), the word-reward entries (pgasr_word_ids,
- * pgasr_pg_rewards_multi_ex) and the gradient-clipping entries (pgasr_grad_norm_ws_bytes, pgasr_grad_norm_clip,
- * pgasr_adam_step_clipped). */
+ * pgasr_pg_rewards_multi_ex), the gradient-clipping entries (pgasr_grad_norm_ws_bytes, pgasr_grad_norm_clip,
+ * pgasr_adam_step_clipped) and the id-addressed samplers (pgasr_frame_argmax_sample_ids, pgasr_frame_sample_multi_ids). */
 #define PGASR_ABI_VERSION 7
 
 int pgasr_abi_version(void);
@@ -193,6 +193,22 @@ int pgasr_head_logsoftmax(const float* x, long long rows, int K, int ldx, const 
 int pgasr_frame_argmax_sample(const float* scores, int T, int B, int V,
                               uint64_t seed, uint32_t offset, int ctr_stride, int ctr_base,
                               int32_t* greedy_path, int32_t* sample_path, void* stream);
+
+/* The two samplers with the draws addressed by an explicit global utterance index per row instead of ctr_base + b (gradient
+ * accumulation over micro-batches, shards that are not contiguous slices of the global batch).  utt_ids (B) int32 on the device.
+ *   0 <= utt_ids[b] < ctr_stride: row b draws from Philox counter (t*ctr_stride + utt_ids[b], offset, 0, k);
+ *   utt_ids[b] < 0 or >= ctr_stride: the row lies beyond the global batch (a padded, empty utterance) and draws from the disjoint
+ *     domain (t*B + b, offset, 1, k) of the entry points above.
+ * With utt_ids[b] = ctr_base + b the outputs are those of pgasr_frame_argmax_sample / pgasr_frame_sample_multi bit for bit (one kernel
+ * body serves both).  Checked before any launch: utt_ids NULL or ctr_stride < 1 (there is no "0 means B" here): PGASR_ERR_INVALID_ARG;
+ * K outside 1 .. PGASR_MAX_SAMPLES: PGASR_ERR_INVALID_ARG; V > 64: PGASR_ERR_UNSUPPORTED; (long long)T * ctr_stride > 2^32:
+ * PGASR_ERR_UNSUPPORTED (counter word 0 is 32 bits; the entry points above truncate silently). */
+int pgasr_frame_argmax_sample_ids(const float* scores, int T, int B, int V, uint64_t seed, uint32_t offset,
+                                  int ctr_stride, const int32_t* utt_ids,
+                                  int32_t* greedy_path, int32_t* sample_path, void* stream);
+int pgasr_frame_sample_multi_ids(const float* scores, int T, int B, int V, int K, uint64_t seed, uint32_t offset,
+                                 int ctr_stride, const int32_t* utt_ids,
+                                 int32_t* greedy_path, int32_t* sample_paths, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * A9  CTC collapse of frame paths: drop repeats, then drop blank, per utterance, for frames

@@ -38,6 +38,10 @@ SIGNATURES = {
                                             c_i32p, c_i32p, c_ptr]),
     "pgasr_frame_sample_multi": (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint32, C.c_int, C.c_int,
                                            c_i32p, c_i32p, c_ptr]),
+    "pgasr_frame_argmax_sample_ids": (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint32, C.c_int, c_i32p,
+                                                c_i32p, c_i32p, c_ptr]),
+    "pgasr_frame_sample_multi_ids": (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint32, C.c_int, c_i32p,
+                                               c_i32p, c_i32p, c_ptr]),
     "pgasr_ctc_grad_from_lattice_multi": (C.c_int, [c_f32p, c_i32p, c_i32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                                     c_f32p, C.c_int, c_f32p, c_i32p, c_f32p, c_ptr, C.c_size_t, c_ptr]),
     "pgasr_pg_rewards_multi": (C.c_int, [c_i32p, c_i32p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, c_f32p, c_f32p, c_f32p,

@@ -10,7 +10,8 @@ namespace {
 // one wave per (t,b) row
 __global__ __launch_bounds__(256) void frame_argmax_sample_kernel(
     const float* __restrict__ scores, long long rows, int B, int V, uint32_t k0, uint32_t k1,
-    uint32_t offset, int ctr_stride, int ctr_base, int32_t* __restrict__ greedy, int32_t* __restrict__ sample) {
+    uint32_t offset, int ctr_stride, int ctr_base, const int32_t* __restrict__ utt_ids, int32_t* __restrict__ greedy,
+    int32_t* __restrict__ sample) {
     const int lane = threadIdx.x & 63;
     const long long r = (long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     if (r >= rows) return;
@@ -39,8 +40,10 @@ __global__ __launch_bounds__(256) void frame_argmax_sample_kernel(
         // base = this rank's first utterance, N ranks draw exactly what one process holding the whole batch draws
         // utterances BEYOND the global batch (ctr_base + b >= ctr_stride: the empty utterances a ragged batch is padded with) draw from
         // a disjoint counter domain (third counter word 1), so their addresses never coincide with a real utterance's
-        const int bg_ = ctr_base + (int)(r % B);
-        const bool outside = bg_ >= ctr_stride;
+        // utt_ids != NULL (the _ids entry points): the global index of row b is utt_ids[b] instead of ctr_base + b -- one 4-byte load
+        // per row, the same for every lane; an id that is negative or >= ctr_stride lies beyond the global batch (base + b is >= 0)
+        const int bg_ = utt_ids ? utt_ids[r % B] : ctr_base + (int)(r % B);
+        const bool outside = (unsigned)bg_ >= (unsigned)ctr_stride;
         const long long ctr = outside ? (long long)r : (r / B) * (long long)ctr_stride + bg_;
         philox4x32_10((uint32_t)ctr, offset, outside ? 1u : 0u, 0u, k0, k1, rnd);
         const float u = (float)(rnd[0] >> 8) * (1.0f / 16777216.0f);
@@ -58,7 +61,8 @@ __global__ __launch_bounds__(256) void frame_argmax_sample_kernel(
 // against the same cdf.  Draw 0's counter, u, threshold and ballot are those of frame_argmax_sample_kernel: its sample bit for bit.
 __global__ __launch_bounds__(256) void frame_sample_multi_kernel(
     const float* __restrict__ scores, long long rows, int B, int V, int K, uint32_t k0, uint32_t k1,
-    uint32_t offset, int ctr_stride, int ctr_base, int32_t* __restrict__ greedy, int32_t* __restrict__ samples) {
+    uint32_t offset, int ctr_stride, int ctr_base, const int32_t* __restrict__ utt_ids, int32_t* __restrict__ greedy,
+    int32_t* __restrict__ samples) {
     const int lane = threadIdx.x & 63;
     const long long r = (long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     if (r >= rows) return;
@@ -79,8 +83,8 @@ __global__ __launch_bounds__(256) void frame_sample_multi_kernel(
         if (lane >= o) c += up;
     }
     const float total = __shfl(c, 63, 64);
-    const int bg_ = ctr_base + (int)(r % B);
-    const bool outside = bg_ >= ctr_stride;
+    const int bg_ = utt_ids ? utt_ids[r % B] : ctr_base + (int)(r % B);     // as in frame_argmax_sample_kernel
+    const bool outside = (unsigned)bg_ >= (unsigned)ctr_stride;
     const long long ctr = outside ? (long long)r : (r / B) * (long long)ctr_stride + bg_;
     uint32_t rnd[4];
     philox4x32_10((uint32_t)ctr, offset, outside ? 1u : 0u, (uint32_t)lane, k0, k1, rnd);
@@ -324,6 +328,22 @@ extern "C" int pgasr_log_softmax_rows(const float* logits, long long rows, int V
     return PGASR_OK;
 }
 
+namespace {
+// counter word 0 is 32 bits: t * ctr_stride + id must fit (the _ids entry points check it; the older ones truncate silently)
+inline bool counter_fits(int T, int ctr_stride) { return (long long)T * ctr_stride <= (1ll << 32); }
+
+int launch_frame_argmax_sample(const float* scores, int T, int B, int V, uint64_t seed, uint32_t offset, int ctr_stride, int ctr_base,
+                               const int32_t* utt_ids, int32_t* greedy_path, int32_t* sample_path, void* stream) {
+    const long long rows = (long long)T * B;
+    const unsigned blocks = (unsigned)((rows + 3) / 4);
+    PGASR_LAUNCH_KERNEL(frame_argmax_sample_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream,
+                       scores, rows, B, V, (uint32_t)(seed & 0xffffffffu), (uint32_t)(seed >> 32), offset,
+                       ctr_stride, ctr_base, utt_ids, greedy_path, sample_path);
+    PGASR_CHECK_LAUNCH();
+    return PGASR_OK;
+}
+}  // namespace
+
 extern "C" int pgasr_frame_argmax_sample(const float* scores, int T, int B, int V,
                                          uint64_t seed, uint32_t offset, int ctr_stride, int ctr_base,
                                          int32_t* greedy_path, int32_t* sample_path, void* stream) {
@@ -332,13 +352,17 @@ extern "C" int pgasr_frame_argmax_sample(const float* scores, int T, int B, int 
     if (ctr_stride <= 0 || ctr_base < 0 || ctr_base >= ctr_stride) return PGASR_ERR_INVALID_ARG;
     if (V > 64) return PGASR_ERR_UNSUPPORTED;
     if (!greedy_path && !sample_path) return PGASR_OK;
-    const long long rows = (long long)T * B;
-    const unsigned blocks = (unsigned)((rows + 3) / 4);
-    PGASR_LAUNCH_KERNEL(frame_argmax_sample_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream,
-                       scores, rows, B, V, (uint32_t)(seed & 0xffffffffu), (uint32_t)(seed >> 32), offset,
-                       ctr_stride, ctr_base, greedy_path, sample_path);
-    PGASR_CHECK_LAUNCH();
-    return PGASR_OK;
+    return launch_frame_argmax_sample(scores, T, B, V, seed, offset, ctr_stride, ctr_base, nullptr, greedy_path, sample_path, stream);
+}
+
+// pgasr_frame_argmax_sample with the draws of row b addressed by utt_ids[b] (device, (B) int32) instead of ctr_base + b
+extern "C" int pgasr_frame_argmax_sample_ids(const float* scores, int T, int B, int V, uint64_t seed, uint32_t offset,
+                                             int ctr_stride, const int32_t* utt_ids,
+                                             int32_t* greedy_path, int32_t* sample_path, void* stream) {
+    if (!scores || !utt_ids || T <= 0 || B <= 0 || V <= 0 || ctr_stride < 1) return PGASR_ERR_INVALID_ARG;
+    if (V > 64 || !counter_fits(T, ctr_stride)) return PGASR_ERR_UNSUPPORTED;
+    if (!greedy_path && !sample_path) return PGASR_OK;
+    return launch_frame_argmax_sample(scores, T, B, V, seed, offset, ctr_stride, 0, utt_ids, greedy_path, sample_path, stream);
 }
 
 namespace {
@@ -432,6 +456,19 @@ extern "C" int pgasr_pg_step_coefs(const int32_t* paths, const int32_t* input_le
 }
 
 // ---- multi-sample REINFORCE (K sampled paths per utterance) ----
+namespace {
+int launch_frame_sample_multi(const float* scores, int T, int B, int V, int K, uint64_t seed, uint32_t offset, int ctr_stride,
+                              int ctr_base, const int32_t* utt_ids, int32_t* greedy_path, int32_t* sample_paths, void* stream) {
+    const long long rows = (long long)T * B;
+    const unsigned blocks = (unsigned)((rows + 3) / 4);
+    PGASR_LAUNCH_KERNEL(frame_sample_multi_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream,
+                       scores, rows, B, V, K, (uint32_t)(seed & 0xffffffffu), (uint32_t)(seed >> 32), offset,
+                       ctr_stride, ctr_base, utt_ids, greedy_path, sample_paths);
+    PGASR_CHECK_LAUNCH();
+    return PGASR_OK;
+}
+}  // namespace
+
 extern "C" int pgasr_frame_sample_multi(const float* scores, int T, int B, int V, int K,
                                         uint64_t seed, uint32_t offset, int ctr_stride, int ctr_base,
                                         int32_t* greedy_path, int32_t* sample_paths, void* stream) {
@@ -440,13 +477,16 @@ extern "C" int pgasr_frame_sample_multi(const float* scores, int T, int B, int V
     if (ctr_stride == 0) ctr_stride = B;
     if (ctr_stride <= 0 || ctr_base < 0 || ctr_base >= ctr_stride) return PGASR_ERR_INVALID_ARG;
     if (V > 64) return PGASR_ERR_UNSUPPORTED;
-    const long long rows = (long long)T * B;
-    const unsigned blocks = (unsigned)((rows + 3) / 4);
-    PGASR_LAUNCH_KERNEL(frame_sample_multi_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream,
-                       scores, rows, B, V, K, (uint32_t)(seed & 0xffffffffu), (uint32_t)(seed >> 32), offset,
-                       ctr_stride, ctr_base, greedy_path, sample_paths);
-    PGASR_CHECK_LAUNCH();
-    return PGASR_OK;
+    return launch_frame_sample_multi(scores, T, B, V, K, seed, offset, ctr_stride, ctr_base, nullptr, greedy_path, sample_paths, stream);
+}
+
+extern "C" int pgasr_frame_sample_multi_ids(const float* scores, int T, int B, int V, int K, uint64_t seed, uint32_t offset,
+                                            int ctr_stride, const int32_t* utt_ids,
+                                            int32_t* greedy_path, int32_t* sample_paths, void* stream) {
+    if (!scores || !sample_paths || !utt_ids || T <= 0 || B <= 0 || V <= 0 || ctr_stride < 1) return PGASR_ERR_INVALID_ARG;
+    if (K < 1 || K > PGASR_MAX_SAMPLES) return PGASR_ERR_INVALID_ARG;
+    if (V > 64 || !counter_fits(T, ctr_stride)) return PGASR_ERR_UNSUPPORTED;
+    return launch_frame_sample_multi(scores, T, B, V, K, seed, offset, ctr_stride, 0, utt_ids, greedy_path, sample_paths, stream);
 }
 
 extern "C" int pgasr_pg_rewards_multi(const int32_t* dist, const int32_t* target_lengths, int B, int K, int baseline,

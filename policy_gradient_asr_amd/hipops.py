@@ -321,28 +321,51 @@ def pg_step_coefs(paths, input_lengths, prefix_dist, token_lengths, target_lengt
     return coef
 
 
-def frame_argmax_sample(scores, seed=0, offset=0, want_greedy=True, want_sample=True, batch_stride=0, batch_offset=0):
+def _check_utt_ids(utt_ids, B, T, batch_stride, device, what):
+    """The id form's arguments: (B) int32 on the scores' device, a global batch >= 1 whose counters fit Philox word 0."""
+    _req(utt_ids, torch.int32, "utt_ids")
+    if utt_ids.dim() != 1 or utt_ids.numel() != B or utt_ids.device != device:
+        raise _lib.PgasrError(f"{what}: utt_ids must be ({B},) int32 on {device}")
+    if int(batch_stride) < 1:
+        raise ValueError(f"{what}: utt_ids needs batch_stride, the global batch (>= 1)")
+    if T * int(batch_stride) > 2 ** 32:
+        raise ValueError(f"{what}: T * batch_stride = {T} * {int(batch_stride)} > 2^32: the sampler's counter word is 32 bits")
+
+
+def frame_argmax_sample(scores, seed=0, offset=0, want_greedy=True, want_sample=True, batch_stride=0, batch_offset=0, utt_ids=None):
     """batch_stride / batch_offset: the GLOBAL batch and this shard's first utterance in it (data parallel: N ranks with
-    one seed then draw what one process holding the whole batch draws); 0 / 0 = the local batch is the whole batch."""
+    one seed then draw what one process holding the whole batch draws); 0 / 0 = the local batch is the whole batch.
+    utt_ids (B) int32 on the device, with batch_stride: row b's global index instead of batch_offset + b (an id < 0 or >=
+    batch_stride: a row beyond the global batch; pgasr_frame_argmax_sample_ids)."""
     lib = _lib.load()
     _req(scores, torch.float32, "scores")
     T, B, V = scores.shape
+    if utt_ids is not None:
+        _check_utt_ids(utt_ids, B, T, batch_stride, scores.device, "frame_argmax_sample")
     g = torch.empty(T, B, dtype=torch.int32, device=scores.device) if want_greedy else None
     s = torch.empty(T, B, dtype=torch.int32, device=scores.device) if want_sample else None
+    if utt_ids is not None:
+        st = lib.pgasr_frame_argmax_sample_ids(_p(scores), T, B, V, int(seed) & (2 ** 64 - 1), int(offset) & 0xFFFFFFFF,
+                                               int(batch_stride), _p(utt_ids), _p(g), _p(s), _stream())
+        _lib.check(st, "pgasr_frame_argmax_sample_ids")
+        return g, s
     st = lib.pgasr_frame_argmax_sample(_p(scores), T, B, V, int(seed) & (2 ** 64 - 1), int(offset) & 0xFFFFFFFF,
                                        int(batch_stride), int(batch_offset), _p(g), _p(s), _stream())
     _lib.check(st, "pgasr_frame_argmax_sample")
     return g, s
 
 
-def frame_sample_multi(scores, num_samples, seed=0, offset=0, want_greedy=False, batch_stride=0, batch_offset=0, out=None):
+def frame_sample_multi(scores, num_samples, seed=0, offset=0, want_greedy=False, batch_stride=0, batch_offset=0, out=None,
+                       utt_ids=None):
     """K draws per frame (include/pgasr_hip.h, pgasr_frame_sample_multi): returns (greedy (T,B) or None, samples (K,T,B)) int32.
-    Draw 0 is ``frame_argmax_sample``'s sample; batch_stride / batch_offset as there.  out = (greedy or None, samples) to
+    Draw 0 is ``frame_argmax_sample``'s sample; batch_stride / batch_offset / utt_ids as there.  out = (greedy or None, samples) to
     write into (contiguous int32)."""
     lib = _lib.load()
     _req(scores, torch.float32, "scores")
     T, B, V = scores.shape
     K = int(num_samples)
+    if utt_ids is not None:
+        _check_utt_ids(utt_ids, B, T, batch_stride, scores.device, "frame_sample_multi")
     if out is not None:
         g, s = out
         _req(g, torch.int32, "out greedy"); _req(s, torch.int32, "out samples")
@@ -351,6 +374,11 @@ def frame_sample_multi(scores, num_samples, seed=0, offset=0, want_greedy=False,
     else:
         g = torch.empty(T, B, dtype=torch.int32, device=scores.device) if want_greedy else None
         s = torch.empty(K, T, B, dtype=torch.int32, device=scores.device)
+    if utt_ids is not None:
+        st = lib.pgasr_frame_sample_multi_ids(_p(scores), T, B, V, K, int(seed) & (2 ** 64 - 1), int(offset) & 0xFFFFFFFF,
+                                              int(batch_stride), _p(utt_ids), _p(g), _p(s), _stream())
+        _lib.check(st, "pgasr_frame_sample_multi_ids")
+        return g, s
     st = lib.pgasr_frame_sample_multi(_p(scores), T, B, V, K, int(seed) & (2 ** 64 - 1), int(offset) & 0xFFFFFFFF,
                                       int(batch_stride), int(batch_offset), _p(g), _p(s), _stream())
     _lib.check(st, "pgasr_frame_sample_multi")

@@ -70,8 +70,10 @@ class PGCTCLossFn(torch.autograd.Function):
     unit_hits = 0              # how often the shortcut was taken (tests)
     @staticmethod
     def forward(ctx, logits, in_len, targets, tg_len, lam, seed, offset, global_batch, blank, beam=0, sample_base=-1, per_step=False,
-                log_probs=None, num_samples=1, baseline="hypothesis", reward_unit="char", word_delimiter=None):
+                log_probs=None, num_samples=1, baseline="hypothesis", reward_unit="char", word_delimiter=None, sample_ids=None):
         T, B, V = logits.shape
+        if sample_ids is not None and sample_base >= 0:
+            raise ValueError("sample_ids and sample_base >= 0 are two addressings of the same draws: give one")
         if per_step and beam > 0:
             raise ValueError("per-step rewards need the frame-aligned greedy baseline (beam = 0)")
         _check_samples(num_samples, baseline, per_step)
@@ -94,7 +96,11 @@ class PGCTCLossFn(torch.autograd.Function):
         side = PGCTCLossFn._lattice_streams.setdefault(main.cuda_stream, None) or streams.side_stream("loss_section")
         PGCTCLossFn._lattice_streams[main.cuda_stream] = side
         # sample_base >= 0: this shard's first utterance in the GLOBAL batch -- the draws are then addressed globally
-        lay = {"batch_stride": int(global_batch), "batch_offset": int(sample_base)} if sample_base >= 0 else {}
+        # sample_ids: the global index of every row instead (micro-batches of an accumulated step, shards that are not contiguous)
+        if sample_ids is not None:
+            lay = {"batch_stride": int(global_batch), "utt_ids": sample_ids}
+        else:
+            lay = {"batch_stride": int(global_batch), "batch_offset": int(sample_base)} if sample_base >= 0 else {}
         wd = word_delimiter if word else None
         if num_samples != 1 or baseline != "hypothesis":
             return PGCTCLossFn._forward_multi(ctx, lp, in_len, targets, tg_len, lam, seed, offset, global_batch, blank, beam, lay,
@@ -186,8 +192,8 @@ class PGCTCLossFn(torch.autograd.Function):
         (grad,) = ctx.saved_tensors
         if PGCTCLossFn.unit_seed_ptr is not None and g.data_ptr() == PGCTCLossFn.unit_seed_ptr and g.numel() == 1:
             PGCTCLossFn.unit_hits += 1
-            return (grad,) + (None,) * 16
-        return (grad * g,) + (None,) * 16
+            return (grad,) + (None,) * 17
+        return (grad * g,) + (None,) * 17
 
 
 REWARD_UNITS = ("char", "word")
@@ -235,16 +241,22 @@ def _check_samples(num_samples, baseline, per_step=False):
 
 
 def pg_ctc_loss(logits, in_len, targets, tg_len, lam=1.0, seed=0, offset=0, global_batch=None, blank=0, beam=0, sample_base=-1,
-                per_step=False, log_probs=None, num_samples=1, baseline="hypothesis", reward_unit="char", word_delimiter=None):
+                per_step=False, log_probs=None, num_samples=1, baseline="hypothesis", reward_unit="char", word_delimiter=None,
+                sample_ids=None):
     """beam > 0: the baseline reward comes from the prefix-beam-search hypothesis of that width (see PGCTCLossFn).
     num_samples / baseline: multi-sample REINFORCE (see PGCTCLossFn); with num_samples > 1 the third returned tensor is R_s (K,B).
     reward_unit: "char" (default) or "word" -- the word-level reward R = -WED / W(y) with words split at the token
     ``word_delimiter`` (see PGCTCLossFn); not with per_step.
     sample_base >= 0 (data parallel): index of this shard's first utterance in the global batch; the sampled paths are
     then those of the single-process global batch with the same seed.
+    sample_ids (B) int32 on the device, instead of sample_base >= 0: the index of EVERY row in the global batch (``global_batch`` is
+    the stride) -- for shards or micro-batches that are not contiguous slices of it; an id < 0 marks a row beyond the global batch
+    (a padded, empty utterance).
     log_probs: log_softmax(logits) if the caller already has it (the head kernel's by-product, ``logits.log_probs`` of
     Seq2Seq.logits -- picked up from that attribute when not given)."""
     B = logits.shape[1]
+    if sample_ids is not None and int(sample_base) >= 0:
+        raise ValueError("sample_ids and sample_base >= 0 are two addressings of the same draws: give one")
     if log_probs is None:
         # the by-product is valid only for the tensor as the head kernel wrote it: any in-place edit since bumps _version
         log_probs = getattr(logits, "log_probs", None)
@@ -252,7 +264,7 @@ def pg_ctc_loss(logits, in_len, targets, tg_len, lam=1.0, seed=0, offset=0, glob
             log_probs = None
     return PGCTCLossFn.apply(logits, in_len, targets, tg_len, float(lam), int(seed), int(offset),
                              int(global_batch or B), int(blank), int(beam), int(sample_base), bool(per_step), log_probs,
-                             num_samples, baseline, reward_unit, word_delimiter)
+                             num_samples, baseline, reward_unit, word_delimiter, sample_ids)
 
 
 class CTCLoss(nn.Module):

@@ -209,7 +209,8 @@ def _check_features(features, n_feats, dataset):
 
 def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset=None, dev_dataset=None,
           n_feats=120, lam=1.0, lr=5e-4, resume=True, log_every=10, seed=0, bucket_by_length=True, features="mfcc",
-          precision="f32", num_samples=1, reward_baseline="hypothesis", reward_unit="char", max_grad_norm=None):
+          precision="f32", num_samples=1, reward_baseline="hypothesis", reward_unit="char", max_grad_norm=None,
+          accumulate_steps=1):
     """Epoch loop of model.py:186-274 on the MI355X path: per-epoch train loss -> train_loss.npy,
     validation CTC loss -> val_losses.npy, model_best.pth / model_last.pth (state_dicts, reference
     names), plus checkpoint_last.pth (model + Adam moments + epoch) from which ``resume`` restarts
@@ -226,7 +227,11 @@ def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset
     alphabet.txt must then hold).
     max_grad_norm: None (default) or a bound > 0 on the global L2 norm of a step's gradient, clipped on the device inside the step
     (clip_grad_norm_ between backward and the update; a step whose gradient holds an inf / NaN is skipped) -- PolicyGradientTrainer.
-    The log lines then carry the last gradient norm, and the end of an epoch the counts of clipped and skipped steps."""
+    The log lines then carry the last gradient norm, and the end of an epoch the counts of clipped and skipped steps.
+    accumulate_steps: 1 (default: one optimizer step per loader batch, as always) or n > 1 -- n consecutive loader batches are the
+    micro-batches of ONE optimizer step (PolicyGradientTrainer.step_accumulated: the batch of an update is n x batch_size; the last
+    group of an epoch may be shorter).  The log lines and the epoch mean then count optimizer steps.  Each loader batch keeps its
+    own padded length, so the update is that of the n batches' summed loss, not of one batch padded to a common length."""
     import os
     import numpy as np
     import torch.utils.data as tud
@@ -236,6 +241,9 @@ def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset
     from .loss import pg_ctc_loss
     from .train_step import PolicyGradientTrainer
 
+    if isinstance(accumulate_steps, bool) or int(accumulate_steps) != accumulate_steps or accumulate_steps < 1:
+        raise ValueError(f"accumulate_steps must be an integer >= 1 (got {accumulate_steps!r})")
+    accumulate_steps = int(accumulate_steps)
     print("Num epochs:", num_epochs, "Batch size:", batch_size)
     alphabet_path = os.path.join(corpus_path, "alphabet.txt")
     alphabet, char2ind = _read_alphabet(alphabet_path)
@@ -274,7 +282,8 @@ def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset
         model.encoder._drop_calls = st.get("drop_calls", 0)
         model.encoder.dropout_seed = st.get("dropout_seed", model.encoder.dropout_seed)
         for k, want in (("lr", lr), ("lam", lam), ("num_samples", num_samples), ("reward_baseline", reward_baseline),
-                        ("reward_unit", reward_unit), ("max_grad_norm", max_grad_norm)):
+                        ("reward_unit", reward_unit), ("max_grad_norm", max_grad_norm),
+                        ("accumulate_steps", accumulate_steps)):
             if k in st and st[k] != want:
                 print("Warning: resuming with {}={} but the checkpoint was written with {}".format(k, want, st[k]))
         losses, val_losses, best, start_epoch = st["losses"], st["val_losses"], st["best"], st["epoch"] + 1
@@ -291,17 +300,27 @@ def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset
         else:
             loader = tud.DataLoader(train_dataset, batch_size=batch_size, shuffle=True, collate_fn=collate_custom)
         acc = torch.zeros((), device=dev)
-        for step, batch in enumerate(loader, 1):
-            loss = trainer.step(*_to_device(batch, dev))
+        n_steps = -(-len(loader) // accumulate_steps)          # optimizer steps of this epoch
+        step, group = 0, []
+        for n_batch, batch in enumerate(loader, 1):
+            if accumulate_steps == 1:
+                loss = trainer.step(*_to_device(batch, dev))
+            else:
+                group.append(_to_device(batch, dev))
+                if len(group) < accumulate_steps and n_batch < len(loader):
+                    continue
+                loss = trainer.step_accumulated(group)
+                group = []
+            step += 1
             acc += loss
             if log_every and step % log_every == 0:
                 val = float(loss)                      # the host synchronises here anyway: check the sweeps' error words
                 hipops.lstm_assert_no_timeouts()       # (until then the guarded Adam has skipped every invalid update)
                 if max_grad_norm is None:
-                    print("Step {}/{}. Loss: {:>4f}".format(step, len(loader), val))
+                    print("Step {}/{}. Loss: {:>4f}".format(step, n_steps, val))
                 else:
-                    print("Step {}/{}. Loss: {:>4f} Grad norm: {:>4f}".format(step, len(loader), val, float(trainer.last_grad_norm)))
-        losses.append(float(acc) / max(len(loader), 1))
+                    print("Step {}/{}. Loss: {:>4f} Grad norm: {:>4f}".format(step, n_steps, val, float(trainer.last_grad_norm)))
+        losses.append(float(acc) / max(step, 1))
         hipops.lstm_assert_no_timeouts()          # .. and before anything of this epoch is written to disk
         streams.release()                         # the host has synchronised: nothing of the last step needs keeping alive
         np.save(os.path.join(model_path, "train_loss.npy"), np.array(losses))
@@ -336,7 +355,7 @@ def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset
                     "losses": losses, "val_losses": val_losses, "best": best, "epoch": epoch,
                     "drop_calls": model.encoder._drop_calls, "dropout_seed": model.encoder.dropout_seed,
                     "lr": lr, "lam": lam, "num_samples": num_samples, "reward_baseline": reward_baseline,
-                    "reward_unit": reward_unit, "max_grad_norm": max_grad_norm}, ckpt)
+                    "reward_unit": reward_unit, "max_grad_norm": max_grad_norm, "accumulate_steps": accumulate_steps}, ckpt)
     return losses, val_losses
 
 

@@ -80,6 +80,55 @@ def check_max_grad_norm(max_grad_norm):
     return v
 
 
+def default_utt_ids(sizes, rank, world):
+    """The ids an accumulated step gives its rows when the caller names none: row b of micro-batch j (``sizes[j]`` real utterances
+    per rank) on ``rank`` is utterance ``world * off_j + rank * sizes[j] + b`` of the global batch, ``off_j = sum(sizes[:j])`` --
+    micro-batch j is a contiguous slice of the global batch, sharded contiguously over the ranks.  Over all ranks and micro-batches
+    the ids are a bijection onto [0, world * sum(sizes)).  Returns one list of ints per micro-batch."""
+    out, off = [], 0
+    for n in sizes:
+        base = world * off + rank * n
+        out.append(list(range(base, base + n)))
+        off += n
+    return out
+
+
+def check_utt_ids(utt_ids, sizes, world):
+    """``utt_ids`` of an accumulated step: one host sequence of integers per micro-batch, ``sizes[j]`` of them for micro-batch j,
+    pairwise distinct over the whole step and each in [0, world * sum(sizes)).  Returns them as lists of int."""
+    import numbers
+    if isinstance(utt_ids, torch.Tensor) or not hasattr(utt_ids, "__len__"):
+        raise ValueError("utt_ids must be a sequence of host integer sequences, one per micro-batch")
+    if len(utt_ids) != len(sizes):
+        raise ValueError(f"utt_ids names {len(utt_ids)} micro-batches, the step has {len(sizes)}")
+    total = world * sum(sizes)
+    seen, out = set(), []
+    for j, (ids, n) in enumerate(zip(utt_ids, sizes)):
+        ids = ids.tolist() if isinstance(ids, torch.Tensor) else list(ids)
+        if len(ids) != n:
+            raise ValueError(f"utt_ids[{j}] holds {len(ids)} ids for a micro-batch of {n} utterances")
+        for i in ids:
+            if isinstance(i, bool) or not isinstance(i, numbers.Integral):
+                raise ValueError(f"utt_ids[{j}]: {i!r} is not an integer")
+            if not 0 <= i < total:
+                raise ValueError(f"utt_ids[{j}]: id {i} outside [0, {total}) = world x the step's utterances per rank")
+            if i in seen:
+                raise ValueError(f"utt_ids[{j}]: id {i} occurs twice in one step (two utterances would share their sampler counters)")
+            seen.add(i)
+        out.append([int(i) for i in ids])
+    return out
+
+
+class MicroBatch:
+    """What ``forward_loss`` may want to know about the micro-batch it is running (``DataParallelStep._micro``; None outside
+    an accumulated step): its index, how many the step has, the real utterances per rank in the micro-batches before it, and
+    the caller's ids for its rows (a list of int, or None for the default rule)."""
+    __slots__ = ("index", "count", "offset", "ids")
+
+    def __init__(self, index, count, offset, ids):
+        self.index, self.count, self.offset, self.ids = index, count, offset, ids
+
+
 class DataParallelStep:
     """zero_grad -> forward_loss -> backward -> all-reduce(sum) -> [clip by global norm] -> Adam, on flat buffers.
     Subclasses provide ``forward_loss(batch, global_batch) -> scalar loss`` already divided by the
@@ -131,6 +180,8 @@ class DataParallelStep:
         self.nstep = 0                      # CALLS of step() (seeds the sampler / dropout offsets); see applied_steps()
         self.collective = self.world > 1    # tests set this on a 1-rank group to exercise the plumbing
         self._early = None                  # (split, work) of an all-reduce issued during backward
+        self._micro = None                  # the running micro-batch of an accumulated step (MicroBatch), else None
+        self._hold_collectives = False      # True while a micro-batch that is not the step's last runs: nothing is exchanged
         if self.world > 1:
             dist.broadcast(self.flat, src=0, group=self.pg)   # identical replicas
 
@@ -147,8 +198,8 @@ class DataParallelStep:
         """Start the all-reduce of gflat[split:] now (its gradients are complete on the CURRENT stream) and leave
         gflat[:split] to ``reduce_rest``: two buckets, the first one hidden under what is left of backward.
         Every rank must call it at the same point of its step (collectives are matched by order)."""
-        if not self.collective or self._early is not None:
-            return
+        if not self.collective or self._early is not None or self._hold_collectives:
+            return          # (an accumulated step exchanges around its LAST micro-batch only)
         # The blocking form on purpose: issued under the weight-gradient side stream it makes only THAT stream wait for the
         # collective (the caller's stream joins the side stream before Adam anyway).  With async_op=True the whole step ran
         # 9.0 -> 12.6 ms on a 1-rank RCCL group -- every phase slower, forward sweeps of the next step included, host enqueue
@@ -213,17 +264,53 @@ class DataParallelStep:
     def backward(self, loss):
         loss.backward()
 
-    def step(self, *batch):
+    def step(self, *batch, utt_ids=None):
+        """One optimizer step on one batch.  utt_ids: None, or one host integer per row -- the row's index in the GLOBAL batch
+        (world x B utterances), for shards that are not contiguous slices of it (``balance_by_frames``); see ``step_accumulated``."""
+        if utt_ids is not None:
+            return self.step_accumulated([batch], utt_ids=[utt_ids])
         return self._locked(self._step, batch)
 
-    def compute_gradients(self, *batch):
+    def compute_gradients(self, *batch, utt_ids=None):
         """The step WITHOUT its exchange and update: zero_grad -> forward_loss -> backward in the step's own orders (fed sweeps,
         streamed weight gradients, side streams), gradients left in ``gflat`` (the parameters' ``.grad`` views), every side stream
-        joined.  Returns the detached local loss.  What the full-size parity tests compare with the oracle; also the hook for a
-        caller that accumulates micro-batches itself."""
+        joined.  Returns the detached local loss.  What the full-size parity tests compare with the oracle.  Every call zeroes
+        ``gflat`` and draws with the same sampler offset: to accumulate micro-batches use ``accumulate_gradients`` /
+        ``step_accumulated``.  utt_ids as in ``step``."""
+        if utt_ids is not None:
+            return self.accumulate_gradients([batch], utt_ids=[utt_ids])
         return self._locked(self._gradients, batch).detach()
 
-    def _locked(self, fn, batch):
+    def step_accumulated(self, micro_batches, utt_ids=None):
+        """ONE optimizer step over a sequence of micro-batches, each the tuple that ``step()`` takes: the batch a step sees is then
+        bounded by time, not by what one call takes.
+          - ``gflat`` is zeroed once; every micro-batch runs forward_loss -> backward in the step's own orders and adds to it.
+          - Every micro-batch's loss is normalised by global_batch = world x (the sum of the micro-batches' real utterances), so
+            the accumulated gradient IS the global batch's gradient: no rescaling pass follows.
+          - Collectives are issued around the LAST micro-batch only (the early bucket during its backward, the rest after it).
+          - The error flag, the global-norm clip (if any) and the Adam update run once, after the last micro-batch, on the
+            accumulated and reduced gradient; ``nstep``, Adam's bias correction and ``applied_steps()`` advance by one.
+          - The step lock is held across the whole call; tensors a micro-batch keeps alive across streams are released when the
+            next one begins, so the peak memory is that of the largest micro-batch plus the flat buffers.
+        Returns the sum of the micro-batches' detached losses (the global-batch loss of this rank; added on the device).
+        utt_ids: None, or one sequence of host integers per micro-batch: the index of every row in the global batch of
+        world x sum(B_j) utterances -- pairwise distinct, checked on the host (ValueError).  A trainer that samples addresses its
+        draws by them.  None: ``default_utt_ids``.
+        world > 1: every rank must pass the same number of micro-batches with the same sizes (the normalisation and the order
+        of the collectives assume it; a rank cannot see the others' sizes, so only an empty sequence or an empty micro-batch
+        raises ValueError here).
+        The identity with ONE process that holds the whole global batch holds for micro-batches padded to one common T: the
+        encoder's instance norm runs over the whole padded (F, T) plane, so an utterance's activations depend on the T its
+        batch is padded to.  Micro-batches of different T (a bucketing loader's) are valid training, but their sum is not the
+        gradient of any single padded batch."""
+        return self._locked(self._step_accumulated, (micro_batches, utt_ids))
+
+    def accumulate_gradients(self, micro_batches, utt_ids=None):
+        """``step_accumulated`` WITHOUT its exchange and update, as ``compute_gradients`` is to ``step``: the accumulated local
+        gradient is left in ``gflat``, every side stream joined.  Returns the summed detached local loss."""
+        return self._locked(self._accumulate, (micro_batches, utt_ids), hold_last=True)
+
+    def _locked(self, fn, batch, **kw):
         from . import streams
         # every side stream of the step is joined into the calling stream by the time backward() returns, so tensors that
         # cross streams are kept alive until the next step begins instead of being handed to record_stream (streams.hold)
@@ -235,8 +322,8 @@ class DataParallelStep:
                 if self.precision is not None and self.flat.is_cuda:
                     from . import hipops
                     with hipops.precision(self.precision):
-                        return fn(*batch)
-                return fn(*batch)
+                        return fn(*batch, **kw)
+                return fn(*batch, **kw)
         finally:
             _step_lock.release()
 
@@ -247,8 +334,53 @@ class DataParallelStep:
         self.backward(loss)
         return loss
 
+    def _check_micro_batches(self, micro_batches, utt_ids):
+        """-> (list of batch tuples, their sizes, ids per micro-batch or Nones); ValueError on what cannot be one step."""
+        if isinstance(micro_batches, torch.Tensor) or not hasattr(micro_batches, "__len__"):
+            raise ValueError("micro_batches must be a sequence of batches, each the tuple that step() takes")
+        mbs = [tuple(mb) for mb in micro_batches]
+        if not mbs:
+            raise ValueError("step_accumulated needs at least one micro-batch")
+        for j, mb in enumerate(mbs):
+            if not mb or not isinstance(mb[0], torch.Tensor) or mb[0].dim() < 1 or mb[0].shape[0] < 1:
+                raise ValueError(f"micro-batch {j} is empty: every rank must pass the same micro-batch sizes, each >= 1")
+        sizes = [mb[0].shape[0] for mb in mbs]
+        ids = check_utt_ids(utt_ids, sizes, self.world) if utt_ids is not None else [None] * len(mbs)
+        return mbs, sizes, ids
+
+    def _accumulate(self, micro_batches, utt_ids, hold_last=False):
+        """gflat := the sum of the micro-batches' gradients of the global-batch loss.  hold_last: the last micro-batch exchanges
+        nothing either (accumulate_gradients)."""
+        from . import streams
+        mbs, sizes, ids = self._check_micro_batches(micro_batches, utt_ids)
+        global_batch = self.world * sum(sizes)
+        self.gflat.zero_()
+        total, off = None, 0
+        try:
+            for j, mb in enumerate(mbs):
+                if j:
+                    streams.release()       # backward() joined every side stream: as between two steps
+                self._micro = MicroBatch(j, len(mbs), off, ids[j])
+                self._hold_collectives = hold_last or j + 1 < len(mbs)
+                loss = self.forward_loss(mb, global_batch)
+                self.backward(loss)
+                loss = loss.detach()
+                total = loss if total is None else total + loss
+                del loss
+                off += sizes[j]
+        finally:
+            self._micro = None
+            self._hold_collectives = False
+        return total
+
+    def _step_accumulated(self, micro_batches, utt_ids):
+        return self._finish(self._accumulate(micro_batches, utt_ids))
+
     def _step(self, *batch):
-        loss = self._gradients(*batch)
+        return self._finish(self._gradients(*batch))
+
+    def _finish(self, loss):
+        """The once-per-step tail: error flag -> the rest of the exchange -> [clip] -> Adam, on the reduced gradient in gflat."""
         if self.collective:
             # the error flag travels with the last gradient bucket (word 0, see FLAG_PAD): SUM > 0 on every rank iff any
             # rank's gradients are invalid
@@ -298,10 +430,15 @@ class PolicyGradientTrainer(DataParallelStep):
     ONE trainer steps at a time per process: the overlap / stream / held-tensor state of the host layer (functional.grad_overlap,
     streams) is process-global and guarded by a step lock -- a second trainer may step between the steps of the first, a concurrent
     ``step()`` raises RuntimeError.
-    Data parallel: ranks are expected to hold CONTIGUOUS shards of the global batch (``shard_slice``): the sampler addresses its draws by
-    global utterance index ``rank * local_B + b``, which makes N ranks sample exactly what one process holding the whole batch samples.
-    With ``balance_by_frames`` shards (variable lengths, configs[4]) the draws are still distinct and the training valid, but that
-    identity with the single-process run does not hold."""
+    Data parallel: the sampler addresses its draws by global utterance index, which makes N ranks sample exactly what one process
+    holding the whole batch samples.  By default a rank's rows are taken for a CONTIGUOUS shard of the global batch
+    (``shard_slice``): row b is utterance ``rank * local_B + b``.  Shards that are not contiguous (``balance_by_frames``: variable
+    lengths, configs[4]) name their rows' global indices with ``utt_ids`` -- ``step(..., utt_ids=parts[rank])`` -- and keep the
+    identity.
+    ``step_accumulated(micro_batches, utt_ids=None)`` is one optimizer step over several such batches (DataParallelStep): every
+    micro-batch samples with the same offset ``nstep + 1`` and distinct ids -- by default ``default_utt_ids``, micro-batch j a contiguous
+    slice of the global batch --, and ``last_stats`` / ``last_sample_rewards`` hold the micro-batches' statistics concatenated in call
+    order (real rows only)."""
 
     def __init__(self, model, lr=5e-4, lam=1.0, seed=0, blank=0, world_size=1, process_group=None, rank=0,
                  reward_decoder="greedy", beam_size=16, precision=None, reward_mode="utterance", num_samples=1,
@@ -432,7 +569,8 @@ class PolicyGradientTrainer(DataParallelStep):
         from .functional import grad_overlap
         from .loss import PGCTCLossFn
         grad_overlap.enabled = self.overlap_weight_grads
-        early = self.collective and self.early_reduce and self.overlap_weight_grads and self.upper_split is not None
+        early = (self.collective and self.early_reduce and self.overlap_weight_grads and self.upper_split is not None
+                 and not self._hold_collectives)       # an accumulated step exchanges around its last micro-batch only
         grad_overlap.upper_grads_hook = self._upper_grads_issued if early else None
         if self._one is None or self._one.device != loss.device:
             self._one = torch.ones((), dtype=loss.dtype, device=loss.device)
@@ -476,16 +614,55 @@ class PolicyGradientTrainer(DataParallelStep):
             tg_len = tmask.sum(dim=1).to(torch.int32).contiguous()
             tg = targets.to(torch.int32).contiguous()
         logits, in_len = self.model.logits(x, fmask, in_len)
+        sample_base, sample_ids = self._sample_addressing(real_b, x.shape[0], x.device)
         loss, nll, R_s, R_g = pg_ctc_loss(logits, in_len, tg, tg_len, lam=self.lam, seed=self.seed,
                                           offset=self.nstep + 1, global_batch=global_batch, blank=self.blank,
                                           beam=self.beam_size if self.reward_decoder == "beam" else 0,
-                                          sample_base=self.rank * real_b if (self.world > 1 or padded) else -1,
+                                          sample_base=sample_base,
                                           per_step=self.reward_mode == "per_step", num_samples=self.num_samples,
                                           baseline=self.reward_baseline, reward_unit=self.reward_unit,
-                                          word_delimiter=self.word_delimiter)
+                                          word_delimiter=self.word_delimiter, sample_ids=sample_ids)
         R_all = R_s if R_s.dim() == 2 else R_s.view(1, -1)       # (K,B): every sample's reward
         if R_s.dim() == 2:
             R_s = R_s.mean(dim=0)
         self.last_sample_rewards = R_all[:, :real_b] if padded else R_all
         self.last_stats = (nll[:real_b], R_s[:real_b], R_g[:real_b]) if padded else (nll, R_s, R_g)
+        if self._micro is not None and self._micro.count > 1:
+            self._micro_stats.append((self.last_stats, self.last_sample_rewards))
+        return loss
+
+    def _sample_addressing(self, real_b, padded_b, device):
+        """(sample_base, sample_ids) of the running batch for pg_ctc_loss: how the sampler addresses its rows' draws.
+        No ids from the caller: the rows are utterances base .. base + real_b - 1 of the global batch, base = world * (real
+        utterances per rank in the micro-batches before this one) + rank * real_b (``default_utt_ids``), passed as ``sample_base``
+        -- no id tensor, no copy, nothing at all (-1) for a lone batch on one rank.  The id form is taken where the caller names
+        ids (uploaded from pinned memory, no synchronisation) and where base + b would hand a PADDED row the counters of a real
+        utterance of the next rank or micro-batch (world > 1, or more than one micro-batch): padded rows then carry id -1
+        (the ids are built on the device).  A padded lone batch on one rank keeps ``sample_base``: base + b >= the global batch
+        there, which the sampler already treats as beyond it."""
+        mb = self._micro
+        n_micro = mb.count if mb is not None else 1
+        padded = padded_b != real_b
+        if mb is not None and mb.ids is not None:
+            host = torch.tensor(mb.ids + [-1] * (padded_b - real_b), dtype=torch.int32)
+            if device.type == "cuda":
+                host = host.pin_memory()
+            return -1, host.to(device, non_blocking=True)
+        base = self.world * (mb.offset if mb is not None else 0) + self.rank * real_b
+        if padded and (self.world > 1 or n_micro > 1):
+            ids = torch.arange(base, base + padded_b, dtype=torch.int32, device=device)
+            ids[real_b:] = -1
+            return -1, ids
+        return (base if (self.world > 1 or padded or n_micro > 1) else -1), None
+
+    def _accumulate(self, micro_batches, utt_ids, hold_last=False):
+        self._micro_stats = []
+        try:
+            loss = super()._accumulate(micro_batches, utt_ids, hold_last=hold_last)
+            if len(self._micro_stats) > 1:
+                # the micro-batches' statistics in call order, real rows only
+                self.last_stats = tuple(torch.cat([st[i] for st, _ in self._micro_stats]) for i in range(3))
+                self.last_sample_rewards = torch.cat([r for _, r in self._micro_stats], dim=1)
+        finally:
+            self._micro_stats = []
         return loss
