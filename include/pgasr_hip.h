@@ -43,7 +43,9 @@ typedef enum pgasr_status {
  * utterances beyond the global batch.  Added since without a version change: the multi-sample entries (pgasr_frame_sample_multi,
  * pgasr_ctc_grad_from_lattice_multi, pgasr_pg_rewards_multi, pgasr_pg_loss_value_multi), the word-reward entries (pgasr_word_ids,
  * pgasr_pg_rewards_multi_ex), the gradient-clipping entries (pgasr_grad_norm_ws_bytes, pgasr_grad_norm_clip,
- * pgasr_adam_step_clipped) and the id-addressed samplers (pgasr_frame_argmax_sample_ids, pgasr_frame_sample_multi_ids). */
+ * pgasr_adam_step_clipped), the id-addressed samplers (pgasr_frame_argmax_sample_ids, pgasr_frame_sample_multi_ids) and the
+ * sequence-level score function (pgasr_ctc_hyp_workspace_bytes, pgasr_ctc_hyp_lattice, pgasr_ctc_grad_from_lattices_seq,
+ * pgasr_pg_loss_value_seq). */
 #define PGASR_ABI_VERSION 7
 
 int pgasr_abi_version(void);
@@ -144,6 +146,44 @@ int pgasr_pg_rewards_multi(const int32_t* dist, const int32_t* target_lengths, i
 int pgasr_pg_loss_value_multi(const float* log_probs, const int32_t* paths, int K, const int32_t* input_lengths,
                               const float* nll, const float* utt_scale, const float* pg_coef,
                               int T, int B, int V, float* terms, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * A12  sequence-level REINFORCE (sampled expected risk / MWER; opt-in beside the path-level score function above).  The reward of
+ * sample k depends on its HYPOTHESIS y_k = collapse(pi_k) alone, so the score function log p(pi_k | x) may be replaced by the CTC
+ * likelihood of the hypothesis, log p(y_k | x) = -nll(y_k) summed over all its alignments: the same expectation, no larger variance.
+ * With K sampled paths, hyp_tokens (K,B,hyp_stride) / hyp_len (K,B) exactly as pgasr_ctc_collapse leaves them, pg_coef (K,B),
+ * utt_scale (B) as above and a length cap Lh:
+ *     seq(k,b)  :=  hyp_len[k,b] <= Lh
+ *     objective =  sum_b [ nll_b utt_scale_b
+ *                          + sum_k pg_coef[k,b] * ( seq(k,b) ?  nll(y_k,b | x_b)  :  -sum_{t<T_b} log p(pi_k[t,b]) ) ]
+ *     d(logits) =  utt_scale_b (softmax - occ_target)
+ *                  + sum_k pg_coef[k,b] * ( seq(k,b) ? (softmax - occ_{y_k}) : (softmax - onehot(pi_k[t,b])) ),  the K terms in k order
+ * occ_y = posterior occupancy of y's CTC lattice over the utterance's own T_b frames.  A hypothesis longer than the cap keeps the
+ * path-level term (the choice depends on y alone: the mixture stays unbiased); a hypothesis nll of +inf contributes nothing.
+ *
+ * pgasr_ctc_hyp_workspace_bytes: the K*B hypothesis lattices, 2 * K*B*T * roundup64(2*Lh+1) * 4 bytes plus per-pair tables (row
+ *   maxima, nll, label lists); 0 for arguments the entry points below reject.
+ * pgasr_ctc_hyp_lattice: alpha / beta / label lists of the pairs (k,b) with hyp_len <= Lh, every pair over log-prob row b of the one
+ *   (T,B,V) tensor and frames t < input_lengths[b]; pgasr_ctc_loss_grad's lattice numerics, run-to-run reproducible.  hyp_nll (K,B):
+ *   nll(y_k,b | x_b), 0 for a skipped pair.  hyp_stride >= max(Lh, 1).
+ * pgasr_ctc_grad_from_lattices_seq: the gradient above in one pass over the target lattice in `workspace` (pgasr_ctc_loss_grad with
+ *   grad_logits = NULL, same T, B, V, Lmax) and the hypothesis lattices in `hyp_workspace` (same T, B, V, K, Lh).
+ * pgasr_pg_loss_value_seq: terms[b] of the objective; path sums in pgasr_pg_loss_value's fixed order, the K products in k order.
+ * K outside 1..PGASR_MAX_SAMPLES, Lh < 0, null pointers: PGASR_ERR_INVALID_ARG.  2*Lh+1 > 2048 or V > 64: PGASR_ERR_UNSUPPORTED.
+ * ---------------------------------------------------------------------------------------- */
+size_t pgasr_ctc_hyp_workspace_bytes(int T, int B, int V, int K, int Lh);
+int pgasr_ctc_hyp_lattice(const float* log_probs, const int32_t* hyp_tokens, int hyp_stride, const int32_t* hyp_len,
+                          const int32_t* input_lengths, int T, int B, int V, int K, int Lh, int blank,
+                          float* hyp_nll, void* hyp_workspace, size_t hyp_workspace_bytes, void* stream);
+int pgasr_ctc_grad_from_lattices_seq(const float* log_probs, const int32_t* input_lengths, const int32_t* target_lengths,
+                                     int T, int B, int V, int Lmax, int blank, const float* utt_scale,
+                                     int K, const float* pg_coef, const int32_t* pg_paths, const int32_t* hyp_len, int Lh,
+                                     float* grad_logits, void* workspace, size_t workspace_bytes,
+                                     void* hyp_workspace, size_t hyp_workspace_bytes, void* stream);
+int pgasr_pg_loss_value_seq(const float* log_probs, const int32_t* paths, int K, const int32_t* input_lengths,
+                            const float* nll, const float* utt_scale, const float* pg_coef,
+                            const float* hyp_nll, const int32_t* hyp_len, int Lh,
+                            int T, int B, int V, float* terms, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * A11  word-level (WER) reward, opt-in: R = -WED(y, yhat) / W(y), where a word is a run of tokens between delimiters -- exactly

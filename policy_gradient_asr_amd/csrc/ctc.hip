@@ -433,6 +433,267 @@ __global__ __launch_bounds__(256) void ctc_grad_multi_kernel(
     if (lane < V) grad[o + lane] = g;
 }
 
+
+// ---- sequence-level REINFORCE (pgasr_ctc_hyp_lattice, pgasr_ctc_grad_from_lattices_seq, pgasr_pg_loss_value_seq) ----
+// The score function of sample k is the CTC likelihood of its HYPOTHESIS y_k = collapse(pi_k), not of the sampled frame path:
+//   loss      = sum_b [ nll_b utt_scale_b + sum_k pg_coef[k,b] * ( seq(k,b) ? nll(y_k,b | x_b) : -sum_{t<T_b} log p(pi_k[t,b]) ) ]
+//   d(logits) = utt_scale_b (softmax - occ_target)
+//               + sum_k pg_coef[k,b] * ( seq(k,b) ? (softmax - occ_{y_k}) : (softmax - onehot(pi_k[t,b])) )         in k order
+// with seq(k,b) := |y_k,b| <= Lh (a longer hypothesis keeps the path-level term: the choice depends on y alone, so the mixture is
+// unbiased).  occ_y = posterior occupancy of y's lattice over the utterance's own T_b frames; a hypothesis whose nll is +inf
+// contributes nothing, as for targets.  The K*B hypothesis lattices live in a workspace of their own, a CtcWs for the "batch" of
+// pairs p = k*B + b with Smax = 2*Lh+1; every pair reads log-prob row b of the ONE (T,B,V) tensor.
+//
+// The lattice body below is ctc_lattice_body's recursion, storer wave and numerics with the row buffers handed in (the kernel
+// owns one LDS block for whichever states-per-thread variant the pair's REAL length selects) and the pair's rows addressed by
+// the caller.  A copy, not a new template parameter of ctc_lattice_body: the measured kernels above stay as compiled.
+template <int NSPT, int ROLE>
+__device__ __forceinline__ void ctc_hyp_lattice_body(
+    const float* __restrict__ lpb,      // log_probs + b*V: frame t of this utterance at lpb + t*fstride
+    size_t fstride, const int32_t* __restrict__ tgt, int Tb, int Lb, int V, int blank,
+    float* __restrict__ out, int SP, double* __restrict__ outmax, double* __restrict__ nll64, float* __restrict__ nll_out,
+    double* __restrict__ rows) {
+    constexpr int role = ROLE;
+    const int tid = threadIdx.x;
+    const int S = 2 * Lb + 1;
+    // row buffers: position p = s + 2, two guard cells of -inf on each side
+    constexpr int ROW = NSPT * CTC_THREADS + 4;
+    auto row = [&](int i) { return rows + i * ROW; };      // the two row buffers
+    const bool storer = tid >= CTC_THREADS;       // wave 4 copies each finished row from LDS to the lattice (see ctc_lattice_body)
+    for (int i = tid; i < 2 * ROW; i += CTC_THREADS + 64) rows[i] = -INFINITY;
+
+    int lab[NSPT];
+    bool skip[NSPT];   // alpha: may come from s-2 ; beta: may go to s+2
+#pragma unroll
+    for (int j = 0; j < NSPT; ++j) {
+        const int s = storer ? S : tid + j * CTC_THREADS;
+        lab[j] = blank; skip[j] = false;
+        if (s < S && (s & 1)) lab[j] = tgt[s >> 1];
+        if (role == 0) {
+            if (s < S && (s & 1) && s >= 3) skip[j] = (tgt[s >> 1] != tgt[(s >> 1) - 1]);
+        } else {
+            if (s + 2 < S && (s & 1)) skip[j] = (tgt[(s >> 1) + 1] != tgt[s >> 1]);
+        }
+        if (lab[j] < 0 || lab[j] >= V) lab[j] = blank;  // defensive: never index outside the row
+    }
+    __syncthreads();
+
+    double m_ref = 0.0;          // the storer's current reference (refreshed every 4th row)
+    auto store_row = [&](const double* rc, int t_row, bool refresh) {
+        constexpr int NG = NSPT * 4;
+        const int ls = tid - CTC_THREADS;
+        const int ng = (S + 63) >> 6;           // 64-state groups that hold states (wave-uniform)
+        double v[NG];
+#pragma unroll
+        for (int i = 0; i < NG; ++i) v[i] = rc[ls + 64 * i + 2];
+        if (refresh) {
+            double ml = -INFINITY;
+#pragma unroll
+            for (int i = 0; i < NG; ++i) ml = fmax(ml, v[i]);
+            const double mw = (double)wave_max_f32_all((float)ml);
+            m_ref = (mw == -INFINITY) ? 0.0 : mw;
+        }
+        const double m = m_ref;
+        float* o = out + (size_t)t_row * SP + ls;
+#pragma unroll
+        for (int i = 0; i < NG; ++i)
+            if (i < ng) o[64 * i] = (float)(v[i] - m);
+        if (ls == 0) outmax[t_row] = m;
+    };
+    if (Tb == 0) {
+        if (role == 0 && tid == 0) {
+            const double v = (Lb == 0) ? 0.0 : INFINITY;
+            *nll64 = v; *nll_out = (float)v;
+        }
+        return;
+    }
+
+    const int t0 = (role == 0) ? 0 : Tb - 1;
+    const int dt = (role == 0) ? 1 : -1;
+    {
+        const float* lpt = lpb + (size_t)t0 * fstride;
+#pragma unroll
+        for (int j = 0; j < NSPT; ++j) {
+            const int s = storer ? S : tid + j * CTC_THREADS;
+            if (s < S) {
+                double v = -INFINITY;
+                if (role == 0) { if (s <= 1) v = (double)lpt[lab[j]]; }
+                else           { if (s >= S - 2) v = (double)lpt[lab[j]]; }
+                row(0)[s + 2] = v;
+            }
+        }
+    }
+    int cur = 0;
+    // LDS-only barrier: __syncthreads() would also drain vmcnt (the storer's stores, the emission prefetch)
+#define ROW_BARRIER() do { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_s_barrier(); \
+                           asm volatile("" ::: "memory"); } while (0)
+    if (storer) {
+        for (int k = 1; k < Tb; ++k) {
+            ROW_BARRIER();
+            store_row(row(cur), t0 + (k - 1) * dt, ((k - 1) & 3) == 0);
+            cur ^= 1;
+        }
+    } else {
+        float lpn[NSPT];
+#pragma unroll
+        for (int j = 0; j < NSPT; ++j) lpn[j] = 0.f;
+        if (Tb > 1) {
+            const float* lpt = lpb + (size_t)(t0 + dt) * fstride;
+#pragma unroll
+            for (int j = 0; j < NSPT; ++j) lpn[j] = lpt[lab[j]];
+        }
+        for (int k = 1; k < Tb; ++k) {
+            const int t = t0 + k * dt;
+            float lpc[NSPT];
+#pragma unroll
+            for (int j = 0; j < NSPT; ++j) lpc[j] = lpn[j];
+            if (k + 1 < Tb) {  // prefetch the next frame's emissions: off the dependent chain
+                const float* lpt = lpb + (size_t)(t + dt) * fstride;
+#pragma unroll
+                for (int j = 0; j < NSPT; ++j) lpn[j] = lpt[lab[j]];
+            }
+            ROW_BARRIER();
+            const double* rc = row(cur);
+            double* rn = row(cur ^ 1);
+#pragma unroll
+            for (int j = 0; j < NSPT; ++j) {
+                const int s = tid + j * CTC_THREADS;
+                const int p = s + 2;
+                const double a0 = rc[p];
+                const double a1 = rc[role == 0 ? p - 1 : p + 1];
+                const double a2r = rc[role == 0 ? p - 2 : p + 2];
+                const double a2 = skip[j] ? a2r : -INFINITY;
+                const double v = lse3(a0, a1, a2) + (double)lpc[j];
+                rn[p] = (s < S) ? v : -INFINITY;
+            }
+            cur ^= 1;
+        }
+    }
+#undef ROW_BARRIER
+    {                    // the last frame's row (the only one when Tb == 1)
+        __syncthreads();
+        if (storer) store_row(row(cur), t0 + (Tb - 1) * dt, ((Tb - 1) & 3) == 0);
+    }
+    if (role == 0) {
+        __syncthreads();
+        if (tid == 0) {
+            const double* rc = row(cur);
+            const double ll = lse3(rc[S - 1 + 2], (S > 1) ? rc[S - 2 + 2] : -INFINITY, -INFINITY);
+            *nll64 = -ll;
+            *nll_out = (float)(-ll);
+        }
+    }
+}
+
+// grid (K*B, 3): pair p = k*B + b; y = 0 alpha, y = 1 beta, y = 2 the label -> states lists.  NMAX = the states-per-thread variant
+// that holds 2*Lh+1 states; a pair whose own 2*len+1 fits a smaller variant runs that one (a uniform branch per workgroup, read
+// from hyp_len on the device: no host synchronisation), so hypotheses near the target length do not pay for the cap.
+template <int NMAX>
+__global__ __launch_bounds__(CTC_THREADS + 64) void ctc_hyp_lattice_kernel(
+    const float* __restrict__ lp, const int32_t* __restrict__ hyp, int hyp_stride, const int32_t* __restrict__ hyp_len,
+    const int32_t* __restrict__ in_len, int T, int B, int V, int Lh, int Smax, int blank, CtcWs ws, float* __restrict__ hyp_nll) {
+    __shared__ double rows[2 * (NMAX * CTC_THREADS + 4)];
+    const int p = blockIdx.x, b = p % B, role = blockIdx.y;
+    const int len = hyp_len[p];
+    if (len > Lh) {            // path-scored sample: no lattice; its nll reads 0
+        if (role == 0 && threadIdx.x == 0) { ws.nll64[p] = 0.0; hyp_nll[p] = 0.f; }
+        return;
+    }
+    if (role == 2) { ctc_labels_body(hyp, hyp_len, V, hyp_stride, Smax, blank, ws); return; }
+    const int Lb = len < 0 ? 0 : len;
+    int Tb = in_len[b]; Tb = Tb < 0 ? 0 : (Tb > T ? T : Tb);
+    const int S = 2 * Lb + 1;
+    const float* lpb = lp + (size_t)b * V;
+    const size_t fstride = (size_t)B * V;
+    const int32_t* tgt = hyp + (size_t)p * hyp_stride;
+    float* out = (role == 0 ? ws.alpha : ws.beta) + (size_t)p * T * ws.SP;
+    double* outmax = (role == 0 ? ws.amax : ws.bmax) + (size_t)p * T;
+#define PGASR_HYP_BODY(N) do { \
+        if (role == 0) ctc_hyp_lattice_body<N, 0>(lpb, fstride, tgt, Tb, Lb, V, blank, out, ws.SP, outmax, ws.nll64 + p, hyp_nll + p, rows); \
+        else           ctc_hyp_lattice_body<N, 1>(lpb, fstride, tgt, Tb, Lb, V, blank, out, ws.SP, outmax, ws.nll64 + p, hyp_nll + p, rows); \
+    } while (0)
+    if constexpr (NMAX == 1) {
+        PGASR_HYP_BODY(1);
+    } else if constexpr (NMAX == 2) {
+        if (S <= CTC_THREADS) PGASR_HYP_BODY(1); else PGASR_HYP_BODY(2);
+    } else if constexpr (NMAX == 4) {
+        if (S <= CTC_THREADS) PGASR_HYP_BODY(1); else if (S <= 2 * CTC_THREADS) PGASR_HYP_BODY(2); else PGASR_HYP_BODY(4);
+    } else {
+        if (S <= CTC_THREADS) PGASR_HYP_BODY(1); else if (S <= 2 * CTC_THREADS) PGASR_HYP_BODY(2);
+        else if (S <= 4 * CTC_THREADS) PGASR_HYP_BODY(4); else PGASR_HYP_BODY(8);
+    }
+#undef PGASR_HYP_BODY
+}
+
+// One wave per (t,b), one pass, one write: the target part, then sample k = 0..K-1 in k order -- the sequence term from lattice
+// (k,b) where hyp_len[k,b] <= Lh (ctc_grad_row over the hypothesis workspace, scale pg_coef[k,b]), else ctc_grad_multi_kernel's path term.
+__global__ __launch_bounds__(256) void ctc_grad_seq_kernel(
+    const float* __restrict__ lp, const int32_t* __restrict__ in_len, const int32_t* __restrict__ tg_len,
+    int T, int B, int V, int Lmax, int Smax, int blank, CtcWs ws,
+    const float* __restrict__ utt_scale, int K, const float* __restrict__ pg_coef,
+    const int32_t* __restrict__ pg_paths, const int32_t* __restrict__ hyp_len, int Lh, int Smax_h, CtcWs hws,
+    float* __restrict__ grad) {
+    const int lane = threadIdx.x & 63;
+    const long long w = (long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (w >= (long long)T * B) return;
+    const int t = (int)(w / B), b = (int)(w % B);
+    int Tb = in_len[b]; Tb = Tb < 0 ? 0 : (Tb > T ? T : Tb);
+    int Lb = tg_len[b]; Lb = Lb < 0 ? 0 : (Lb > Lmax ? Lmax : Lb);
+    const size_t o = ((size_t)t * B + b) * V;
+    if (t >= Tb) { if (lane < V) grad[o + lane] = 0.f; return; }
+
+    const float lpv = (lane < V) ? lp[o + lane] : 0.f;
+    const float sm = (lane < V) ? __expf(lpv) : 0.f;
+    float g = ctc_grad_row(lpv, sm, lane, t, b, T, V, Lb, Smax, blank, ws, utt_scale);
+    const size_t TB = (size_t)T * B;
+    for (int k = 0; k < K; ++k) {
+        const int p = k * B + b;
+        const int len = hyp_len[p];
+        if (len <= Lh) {
+            // pair p's lattice; the per-pair scale is pg_coef[p]
+            g += ctc_grad_row(lpv, sm, lane, t, p, T, V, len < 0 ? 0 : len, Smax_h, blank, hws, pg_coef);
+        } else {
+            const int pk = pg_paths[k * TB + (size_t)t * B + b];
+            g += pg_coef[p] * (sm - (lane == pk ? 1.f : 0.f));
+        }
+    }
+    if (lane < V) grad[o + lane] = g;
+}
+
+// terms[b] = nll_b utt_scale_b + sum_k coef[k,b] * ( hyp_len[k,b] <= Lh ? hyp_nll[k,b] : -sum_{t<T_b} log p(paths[k,t,b]) ): the path
+// sums in pg_loss_value_kernel's fixed order, the K products added in k order; a +inf hypothesis nll adds nothing.
+__global__ __launch_bounds__(256) void pg_loss_value_seq_kernel(const float* __restrict__ lp, const int32_t* __restrict__ paths, int K,
+                                                                const int32_t* __restrict__ in_len, const float* __restrict__ nll,
+                                                                const float* __restrict__ utt_scale, const float* __restrict__ coef,
+                                                                const float* __restrict__ hyp_nll, const int32_t* __restrict__ hyp_len,
+                                                                int Lh, int T, int B, int V, float* __restrict__ terms) {
+    __shared__ float red[256];
+    const int b = blockIdx.x;
+    const int Tb = min(in_len[b], T);
+    float acc = 0.f;
+    for (int k = 0; k < K; ++k) {
+        const size_t p = (size_t)k * B + b;
+        if (hyp_len[p] <= Lh) {               // uniform over the workgroup
+            const float hn = hyp_nll[p];
+            if (hn != INFINITY) acc -= coef[p] * hn;
+            continue;
+        }
+        const int32_t* path = paths + (size_t)k * T * B;
+        float s = 0.f;
+        for (int t = threadIdx.x; t < Tb; t += 256)
+            s += lp[((size_t)t * B + b) * V + path[(size_t)t * B + b]];
+        red[threadIdx.x] = s;
+        __syncthreads();
+        for (int o = 128; o > 0; o >>= 1) {
+            if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+            __syncthreads();
+        }
+        acc += coef[p] * red[0];
+        __syncthreads();          // red[0] read by every thread before the next path overwrites it
+    }
+    if (threadIdx.x == 0) terms[b] = nll[b] * utt_scale[b] - acc;
+}
+
 }  // namespace
 
 extern "C" size_t pgasr_ctc_workspace_bytes(int T, int B, int V, int Lmax) {
@@ -524,6 +785,83 @@ extern "C" int pgasr_ctc_grad_from_lattice_multi(const float* log_probs, const i
     PGASR_LAUNCH_KERNEL(ctc_grad_multi_kernel, dim3(blocks), dim3(64 * wpb), 0, (hipStream_t)stream,
                        log_probs, input_lengths, target_lengths, T, B, V,
                        Lmax > 0 ? Lmax : 1, Smax, blank, ws, utt_scale, K, pg_coef, pg_paths, grad_logits);
+    PGASR_CHECK_LAUNCH();
+    return PGASR_OK;
+}
+
+// ---- sequence-level REINFORCE: the K*B hypothesis lattices and the passes over K+1 lattices (see the kernels' comment) ----
+static int ctc_hyp_args_ok(int T, int B, int V, int K, int Lh) {
+    if (T <= 0 || B <= 0 || V <= 0 || Lh < 0) return PGASR_ERR_INVALID_ARG;
+    if (K < 1 || K > PGASR_MAX_SAMPLES) return PGASR_ERR_INVALID_ARG;
+    if (2 * (long long)Lh + 1 > CTC_SMAX || V > CTC_VMAX) return PGASR_ERR_UNSUPPORTED;
+    if ((long long)K * B > 0x7fffffffLL / 4) return PGASR_ERR_UNSUPPORTED;
+    return PGASR_OK;
+}
+
+extern "C" size_t pgasr_ctc_hyp_workspace_bytes(int T, int B, int V, int K, int Lh) {
+    if (ctc_hyp_args_ok(T, B, V, K, Lh) != PGASR_OK) return 0;
+    return ctc_ws_layout(T, K * B, V, 2 * Lh + 1, nullptr, nullptr);
+}
+
+extern "C" int pgasr_ctc_hyp_lattice(const float* log_probs, const int32_t* hyp_tokens, int hyp_stride, const int32_t* hyp_len,
+                                     const int32_t* input_lengths, int T, int B, int V, int K, int Lh, int blank,
+                                     float* hyp_nll, void* hyp_workspace, size_t hyp_workspace_bytes, void* stream) {
+    if (!log_probs || !hyp_tokens || !hyp_len || !input_lengths || !hyp_nll) return PGASR_ERR_INVALID_ARG;
+    if (blank < 0 || blank >= V || hyp_stride < 1 || hyp_stride < Lh) return PGASR_ERR_INVALID_ARG;
+    const int ok = ctc_hyp_args_ok(T, B, V, K, Lh);
+    if (ok != PGASR_OK) return ok;
+    const int Smax = 2 * Lh + 1;
+    CtcWs ws;
+    const size_t need = ctc_ws_layout(T, K * B, V, Smax, &ws, (char*)hyp_workspace);
+    if (!hyp_workspace || hyp_workspace_bytes < need) return PGASR_ERR_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+#define PGASR_HYP_LATTICE(NMAX) PGASR_LAUNCH_KERNEL(ctc_hyp_lattice_kernel<NMAX>, dim3(K * B, 3), dim3(CTC_THREADS + 64), 0, st, \
+                        log_probs, hyp_tokens, hyp_stride, hyp_len, input_lengths, T, B, V, Lh, Smax, blank, ws, hyp_nll)
+    if (Smax <= CTC_THREADS) PGASR_HYP_LATTICE(1);
+    else if (Smax <= 2 * CTC_THREADS) PGASR_HYP_LATTICE(2);
+    else if (Smax <= 4 * CTC_THREADS) PGASR_HYP_LATTICE(4);
+    else PGASR_HYP_LATTICE(8);
+#undef PGASR_HYP_LATTICE
+    PGASR_CHECK_LAUNCH();
+    return PGASR_OK;
+}
+
+extern "C" int pgasr_ctc_grad_from_lattices_seq(const float* log_probs, const int32_t* input_lengths, const int32_t* target_lengths,
+                                                int T, int B, int V, int Lmax, int blank, const float* utt_scale,
+                                                int K, const float* pg_coef, const int32_t* pg_paths, const int32_t* hyp_len, int Lh,
+                                                float* grad_logits, void* workspace, size_t workspace_bytes,
+                                                void* hyp_workspace, size_t hyp_workspace_bytes, void* stream) {
+    if (!log_probs || !input_lengths || !target_lengths || !grad_logits || !pg_coef || !pg_paths || !hyp_len) return PGASR_ERR_INVALID_ARG;
+    if (Lmax < 0 || blank < 0 || blank >= V) return PGASR_ERR_INVALID_ARG;
+    const int ok = ctc_hyp_args_ok(T, B, V, K, Lh);
+    if (ok != PGASR_OK) return ok;
+    const int Smax = 2 * Lmax + 1, Smax_h = 2 * Lh + 1;
+    if (Smax > CTC_SMAX) return PGASR_ERR_UNSUPPORTED;
+    CtcWs ws, hws;
+    const size_t need = ctc_ws_layout(T, B, V, Smax, &ws, (char*)workspace);
+    if (!workspace || workspace_bytes < need) return PGASR_ERR_WORKSPACE;
+    const size_t need_h = ctc_ws_layout(T, K * B, V, Smax_h, &hws, (char*)hyp_workspace);
+    if (!hyp_workspace || hyp_workspace_bytes < need_h) return PGASR_ERR_WORKSPACE;
+    const long long waves = (long long)T * B;
+    const int wpb = 4;
+    const unsigned blocks = (unsigned)((waves + wpb - 1) / wpb);
+    PGASR_LAUNCH_KERNEL(ctc_grad_seq_kernel, dim3(blocks), dim3(64 * wpb), 0, (hipStream_t)stream,
+                       log_probs, input_lengths, target_lengths, T, B, V,
+                       Lmax > 0 ? Lmax : 1, Smax, blank, ws, utt_scale, K, pg_coef, pg_paths, hyp_len, Lh, Smax_h, hws, grad_logits);
+    PGASR_CHECK_LAUNCH();
+    return PGASR_OK;
+}
+
+extern "C" int pgasr_pg_loss_value_seq(const float* log_probs, const int32_t* paths, int K, const int32_t* input_lengths,
+                                       const float* nll, const float* utt_scale, const float* pg_coef,
+                                       const float* hyp_nll, const int32_t* hyp_len, int Lh,
+                                       int T, int B, int V, float* terms, void* stream) {
+    if (!log_probs || !paths || !input_lengths || !nll || !utt_scale || !pg_coef || !hyp_nll || !hyp_len || !terms)
+        return PGASR_ERR_INVALID_ARG;
+    if (T <= 0 || B <= 0 || V <= 0 || Lh < 0) return PGASR_ERR_INVALID_ARG;
+    if (K < 1 || K > PGASR_MAX_SAMPLES) return PGASR_ERR_INVALID_ARG;
+    PGASR_LAUNCH_KERNEL(pg_loss_value_seq_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream,
+                       log_probs, paths, K, input_lengths, nll, utt_scale, pg_coef, hyp_nll, hyp_len, Lh, T, B, V, terms);
     PGASR_CHECK_LAUNCH();
     return PGASR_OK;
 }

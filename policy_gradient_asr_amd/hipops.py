@@ -284,6 +284,82 @@ def pg_loss_value_multi(log_probs, paths, input_lengths, nll, utt_scale, pg_coef
     return terms
 
 
+# ---- sequence-level REINFORCE (include/pgasr_hip.h: the score function of a sample is the CTC likelihood of its hypothesis) ----
+SCORE_FUNCTIONS = ("path", "sequence")
+MAX_HYP_LEN = 1023               # the lattice's 2L+1 <= 2048 states
+
+
+def hyp_len_cap(T, max_hyp_len=None):
+    """Lh = min(T, MAX_HYP_LEN, max_hyp_len if given): hypotheses of at most Lh tokens are sequence-scored."""
+    return min(int(T), MAX_HYP_LEN) if max_hyp_len is None else min(int(T), MAX_HYP_LEN, int(max_hyp_len))
+
+
+def ctc_hyp_workspace_bytes(T, B, V, K, Lh):
+    """Bytes of the K*B hypothesis lattices: 2 * K*B*T * roundup64(2*Lh+1) * 4 plus the per-pair tables."""
+    return int(_lib.load().pgasr_ctc_hyp_workspace_bytes(T, B, V, K, Lh))
+
+
+def ctc_hyp_lattice(log_probs, hyp_tokens, hyp_len, input_lengths, Lh, blank=0):
+    """The CTC lattices of the K sampled hypotheses of every utterance over the SAME log-prob rows: log_probs (T,B,V),
+    hyp_tokens (K,B,stride) / hyp_len (K,B) int32 as ``ctc_collapse`` returns them.  Pairs with hyp_len > Lh are skipped.
+    Returns (hyp_nll (K,B) fp32 -- 0 for a skipped pair --, handle); the handle goes to ``ctc_grad_from_lattices_seq``.
+    The lattices live in a cached workspace of ``ctc_hyp_workspace_bytes(T, B, V, K, Lh)`` bytes (tag "ctc_hyp")."""
+    lib = _lib.load()
+    _req(log_probs, torch.float32, "log_probs"); _req(hyp_tokens, torch.int32, "hyp_tokens")
+    _req(hyp_len, torch.int32, "hyp_len"); _req(input_lengths, torch.int32, "input_lengths")
+    T, B, V = log_probs.shape
+    if hyp_tokens.dim() != 3 or hyp_tokens.shape[1] != B or tuple(hyp_len.shape) != (hyp_tokens.shape[0], B):
+        raise _lib.PgasrError(f"ctc_hyp_lattice wants hyp_tokens (K,{B},stride) and hyp_len (K,{B})")
+    K, stride, Lh = hyp_tokens.shape[0], hyp_tokens.shape[2], int(Lh)
+    nbytes = lib.pgasr_ctc_hyp_workspace_bytes(T, B, V, K, Lh)
+    ws = _workspace(nbytes, log_probs.device, "ctc_hyp")
+    hyp_nll = torch.empty(K, B, dtype=torch.float32, device=log_probs.device)
+    with _timed("ctc_hyp_lattice_kernel"):
+        st = lib.pgasr_ctc_hyp_lattice(_p(log_probs), _p(hyp_tokens), stride, _p(hyp_len), _p(input_lengths), T, B, V, K, Lh, blank,
+                                       _p(hyp_nll), _p(ws), ws.numel(), _stream())
+    _lib.check(st, "pgasr_ctc_hyp_lattice")
+    return hyp_nll, (ws, K, Lh)
+
+
+def ctc_grad_from_lattices_seq(log_probs, input_lengths, target_lengths, handle, hyp_handle, utt_scale, pg_coef, pg_paths, hyp_len):
+    """One gradient pass over the target lattice (``ctc_lattice``'s handle) and the K*B hypothesis lattices (``ctc_hyp_lattice``'s):
+    utt_scale (softmax - occ_target) + sum_k pg_coef[k,b] * (hyp_len[k,b] <= Lh ? softmax - occ_hyp : softmax - onehot(pg_paths[k,t,b])),
+    the K terms in k order.  pg_paths (K,T,B) int32, pg_coef (K,B) fp32, hyp_len (K,B) int32."""
+    lib = _lib.load()
+    ws, Lmax, blank = handle
+    hws, K, Lh = hyp_handle
+    T, B, V = log_probs.shape
+    _req(utt_scale, torch.float32, "utt_scale"); _req(pg_coef, torch.float32, "pg_coef"); _req(pg_paths, torch.int32, "pg_paths")
+    _req(hyp_len, torch.int32, "hyp_len")
+    if tuple(pg_paths.shape) != (K, T, B) or tuple(pg_coef.shape) != (K, B) or tuple(hyp_len.shape) != (K, B):
+        raise _lib.PgasrError(f"ctc_grad_from_lattices_seq wants pg_paths ({K},{T},{B}), pg_coef and hyp_len ({K},{B})")
+    grad = torch.empty_like(log_probs)
+    with _timed("ctc_grad_seq_kernel"):
+        st = lib.pgasr_ctc_grad_from_lattices_seq(_p(log_probs), _p(input_lengths), _p(target_lengths), T, B, V, Lmax, blank,
+                                                  _p(utt_scale), K, _p(pg_coef), _p(pg_paths), _p(hyp_len), Lh, _p(grad),
+                                                  _p(ws), ws.numel(), _p(hws), hws.numel(), _stream())
+    _lib.check(st, "pgasr_ctc_grad_from_lattices_seq")
+    return grad
+
+
+def pg_loss_value_seq(log_probs, paths, input_lengths, nll, utt_scale, pg_coef, hyp_nll, hyp_len, Lh):
+    """Per-utterance value of the sequence-level objective: nll_b utt_scale_b + sum_k pg_coef[k,b] * (hyp_len[k,b] <= Lh ?
+    hyp_nll[k,b] : -sum_t log p(paths[k,t,b])); sum() it for the loss."""
+    lib = _lib.load()
+    T, B, V = log_probs.shape
+    _req(log_probs, torch.float32, "log_probs"); _req(paths, torch.int32, "paths"); _req(nll, torch.float32, "nll")
+    _req(utt_scale, torch.float32, "utt_scale"); _req(pg_coef, torch.float32, "pg_coef")
+    _req(hyp_nll, torch.float32, "hyp_nll"); _req(hyp_len, torch.int32, "hyp_len")
+    K = paths.shape[0]
+    if paths.dim() != 3 or tuple(paths.shape[1:]) != (T, B) or any(tuple(t_.shape) != (K, B) for t_ in (pg_coef, hyp_nll, hyp_len)):
+        raise _lib.PgasrError(f"pg_loss_value_seq wants paths (K,{T},{B}) and pg_coef, hyp_nll, hyp_len (K,{B})")
+    terms = torch.empty(B, dtype=torch.float32, device=log_probs.device)
+    st = lib.pgasr_pg_loss_value_seq(_p(log_probs), _p(paths), K, _p(input_lengths), _p(nll), _p(utt_scale), _p(pg_coef),
+                                     _p(hyp_nll), _p(hyp_len), int(Lh), T, B, V, _p(terms), _stream())
+    _lib.check(st, "pgasr_pg_loss_value_seq")
+    return terms
+
+
 FUSED_HEAD = _os_environ_get("PGASR_FUSED_HEAD", "1") != "0"
 
 

@@ -58,6 +58,24 @@ class PGCTCLossFn(torch.autograd.Function):
     (n delimiters give n + 1 words, empty ones included), WED the Levenshtein distance over the word lists and W(y) >= 1 the target's
     word count; the word step (pgasr_word_ids) runs on the side stream between collapse and edit distance.  The CTC term keeps
     utt_scale = 1 / (Bg max(L_chars,1)).  Not with per_step (character-level only).
+    ``score_function = "sequence"`` (opt-in; the default "path" is everything above, launch for launch): the reward depends on the
+    HYPOTHESIS y_k = collapse(pi_k) alone, so the score function of sample k becomes the CTC likelihood of its hypothesis,
+    log p(y_k | x) = -nll(y_k) summed over all its alignments, instead of log p(pi_k | x) -- the same expectation (E[grad log p(pi|x) |
+    y] = grad log p(y|x)), no larger variance (sampled expected risk / MWER).  With rewards, baselines, pg_coef[k,b] = lam / (Bg K)
+    (R_k - b_k) and utt_scale_b = 1 / (Bg max(L_b,1)) exactly as above (any num_samples, either baseline, greedy or beam hypothesis,
+    char or word reward) and a length cap Lh = min(T, 1023, max_hyp_len if given):
+        seq(k,b)  :=  |y_k,b| <= Lh
+        loss      =  sum_b [ nll_b utt_scale_b
+                             + sum_k pg_coef[k,b] * ( seq(k,b) ?  nll(y_k,b | x_b)  :  -sum_{t<T_b} log p(pi_k[t,b]) ) ]
+        d(logits) =  utt_scale_b (softmax - occ_target)
+                     + sum_k pg_coef[k,b] * ( seq(k,b) ?  (softmax - occ_{y_k})  :  (softmax - onehot(pi_k[t,b])) )     in k order
+    occ_y is the CTC posterior occupancy of y's lattice over the utterance's own T_b frames.  A hypothesis longer than the cap keeps
+    the path-level term: the choice depends on y alone, so the mixture is still unbiased and a long sample never fails; a hypothesis
+    nll of +inf contributes nothing, as for targets.  The hypothesis lattices take 2 * K*B*T * roundup64(2*Lh+1) * 4 bytes of cached
+    workspace (B = 32, T = 1000, K = 4: 2.1 GB at Lh = 1000, 0.46 GB with max_hyp_len = 200; hipops.ctc_hyp_workspace_bytes).  Always
+    the multi-sample section (K = 1 included); not with per_step (frame-aligned coefficients have no sequence form).
+    ``PGCTCLossFn.last_sequence_scored``: (K,B) bool on the device, which samples of the last call took the sequence term (None after
+    a "path" call).
     Returns (loss, stats) where stats = (nll (B), R_s (B), R_g (B)) detached; with K > 1, (nll (B), R_s (K,B), R_b (B)) where
     R_b is the baseline averaged over k (R_g for "hypothesis")."""
 
@@ -68,10 +86,14 @@ class PGCTCLossFn(torch.autograd.Function):
     # trainer -- takes grad * g.
     unit_seed_ptr = None
     unit_hits = 0              # how often the shortcut was taken (tests)
+    last_sequence_scored = None    # (K,B) bool: the samples of the last score_function="sequence" call that were sequence-scored
     @staticmethod
     def forward(ctx, logits, in_len, targets, tg_len, lam, seed, offset, global_batch, blank, beam=0, sample_base=-1, per_step=False,
-                log_probs=None, num_samples=1, baseline="hypothesis", reward_unit="char", word_delimiter=None, sample_ids=None):
+                log_probs=None, num_samples=1, baseline="hypothesis", reward_unit="char", word_delimiter=None, sample_ids=None,
+                score_function="path", max_hyp_len=None):
         T, B, V = logits.shape
+        _check_score(score_function, max_hyp_len, per_step)
+        PGCTCLossFn.last_sequence_scored = None
         if sample_ids is not None and sample_base >= 0:
             raise ValueError("sample_ids and sample_base >= 0 are two addressings of the same draws: give one")
         if per_step and beam > 0:
@@ -102,9 +124,10 @@ class PGCTCLossFn(torch.autograd.Function):
         else:
             lay = {"batch_stride": int(global_batch), "batch_offset": int(sample_base)} if sample_base >= 0 else {}
         wd = word_delimiter if word else None
-        if num_samples != 1 or baseline != "hypothesis":
+        if num_samples != 1 or baseline != "hypothesis" or score_function == "sequence":
             return PGCTCLossFn._forward_multi(ctx, lp, in_len, targets, tg_len, lam, seed, offset, global_batch, blank, beam, lay,
-                                              main, side, num_samples, baseline, wd)
+                                              main, side, num_samples, baseline, wd,
+                                              hipops.hyp_len_cap(T, max_hyp_len) if score_function == "sequence" else None)
         side.wait_stream(main)
         with torch.cuda.stream(side):
             if beam > 0:
@@ -146,8 +169,10 @@ class PGCTCLossFn(torch.autograd.Function):
 
     @staticmethod
     def _forward_multi(ctx, lp, in_len, targets, tg_len, lam, seed, offset, global_batch, blank, beam, lay, main, side, K, baseline,
-                       word_delimiter=None):
-        """K sampled paths per utterance: the single-sample section's stream structure with the multi-sample kernels."""
+                       word_delimiter=None, Lh=None):
+        """K sampled paths per utterance: the single-sample section's stream structure with the multi-sample kernels.
+        Lh (score_function="sequence"): the hypothesis-length cap; the K*B hypothesis lattices follow the collapse on the side stream
+        (no third stream) and the gradient pass runs over K+1 lattices."""
         T, B, V = lp.shape
         dev = lp.device
         loo = baseline == "leave_one_out"
@@ -169,6 +194,10 @@ class PGCTCLossFn(torch.autograd.Function):
                 hipops.frame_sample_multi(lp, K, seed=seed, offset=offset, out=(paths[0], paths[1:]), **lay)
                 samples = paths[1:]
                 tokens, tok_len = hipops.ctc_collapse(paths, in_len, blank=blank)
+            if Lh is not None:
+                hyp_len = tok_len[P - K:]                     # the K samples' rows (row 0 may be the baseline hypothesis)
+                hyp_nll, hyp_lattice = hipops.ctc_hyp_lattice(lp, tokens[P - K:], hyp_len, in_len, Lh, blank=blank)
+                PGCTCLossFn.last_sequence_scored = scored = hyp_len <= Lh
             if word_delimiter is None:
                 dist = hipops.edit_distance(targets.repeat(P, 1), tg_len.repeat(P), tokens.view(P * B, T), tok_len.view(P * B))
                 n_words = None
@@ -180,8 +209,14 @@ class PGCTCLossFn(torch.autograd.Function):
         main.wait_stream(side)
         for t_ in (samples, R_b, R_s, coef, utt_scale):
             streams.hold(t_, main)
-        grad = hipops.ctc_grad_from_lattice_multi(lp, in_len, tg_len, lattice, utt_scale, coef, samples)
-        loss = hipops.pg_loss_value_multi(lp, samples, in_len, nll, utt_scale, coef).sum()
+        if Lh is not None:
+            for t_ in (tok_len, hyp_nll, scored):
+                streams.hold(t_, main)
+            grad = hipops.ctc_grad_from_lattices_seq(lp, in_len, tg_len, lattice, hyp_lattice, utt_scale, coef, samples, hyp_len)
+            loss = hipops.pg_loss_value_seq(lp, samples, in_len, nll, utt_scale, coef, hyp_nll, hyp_len, Lh).sum()
+        else:
+            grad = hipops.ctc_grad_from_lattice_multi(lp, in_len, tg_len, lattice, utt_scale, coef, samples)
+            loss = hipops.pg_loss_value_multi(lp, samples, in_len, nll, utt_scale, coef).sum()
         ctx.save_for_backward(grad)
         ctx.mark_non_differentiable(nll, R_s, R_b)
         ctx.set_materialize_grads(False)
@@ -192,8 +227,8 @@ class PGCTCLossFn(torch.autograd.Function):
         (grad,) = ctx.saved_tensors
         if PGCTCLossFn.unit_seed_ptr is not None and g.data_ptr() == PGCTCLossFn.unit_seed_ptr and g.numel() == 1:
             PGCTCLossFn.unit_hits += 1
-            return (grad,) + (None,) * 17
-        return (grad * g,) + (None,) * 17
+            return (grad,) + (None,) * 19
+        return (grad * g,) + (None,) * 19
 
 
 REWARD_UNITS = ("char", "word")
@@ -225,6 +260,21 @@ def _check_unit(reward_unit, word_delimiter, per_step=False, blank=None, vocab=N
         raise ValueError("per-step rewards are character-level: reward_mode='per_step' does not take reward_unit='word'")
 
 
+def _check_score(score_function, max_hyp_len, per_step=False):
+    """The score-function arguments of pg_ctc_loss / PolicyGradientTrainer, checked before any kernel runs."""
+    if score_function not in hipops.SCORE_FUNCTIONS:
+        raise ValueError(f"score_function must be one of {hipops.SCORE_FUNCTIONS} (got {score_function!r})")
+    if max_hyp_len is not None:
+        import numbers
+        if isinstance(max_hyp_len, bool) or not isinstance(max_hyp_len, numbers.Integral) or max_hyp_len < 0:
+            raise ValueError(f"max_hyp_len must be None or an integer >= 0 (got {max_hyp_len!r})")
+        if score_function != "sequence":
+            raise ValueError("max_hyp_len caps the hypotheses that score_function='sequence' scores: it has no meaning with 'path'")
+    if score_function == "sequence" and per_step:
+        raise ValueError("per-step rewards have frame-aligned coefficients, which have no sequence form: score_function='sequence' "
+                         "does not take reward_mode='per_step'")
+
+
 def _check_samples(num_samples, baseline, per_step=False):
     """The multi-sample arguments of pg_ctc_loss / PolicyGradientTrainer, checked where the caller can read the reason."""
     if baseline not in hipops.BASELINES:
@@ -242,7 +292,7 @@ def _check_samples(num_samples, baseline, per_step=False):
 
 def pg_ctc_loss(logits, in_len, targets, tg_len, lam=1.0, seed=0, offset=0, global_batch=None, blank=0, beam=0, sample_base=-1,
                 per_step=False, log_probs=None, num_samples=1, baseline="hypothesis", reward_unit="char", word_delimiter=None,
-                sample_ids=None):
+                sample_ids=None, score_function="path", max_hyp_len=None):
     """beam > 0: the baseline reward comes from the prefix-beam-search hypothesis of that width (see PGCTCLossFn).
     num_samples / baseline: multi-sample REINFORCE (see PGCTCLossFn); with num_samples > 1 the third returned tensor is R_s (K,B).
     reward_unit: "char" (default) or "word" -- the word-level reward R = -WED / W(y) with words split at the token
@@ -252,11 +302,14 @@ def pg_ctc_loss(logits, in_len, targets, tg_len, lam=1.0, seed=0, offset=0, glob
     sample_ids (B) int32 on the device, instead of sample_base >= 0: the index of EVERY row in the global batch (``global_batch`` is
     the stride) -- for shards or micro-batches that are not contiguous slices of it; an id < 0 marks a row beyond the global batch
     (a padded, empty utterance).
+    score_function: "path" (default) or "sequence" -- score every sample by the CTC likelihood of its collapsed hypothesis instead of
+    its frame path (see PGCTCLossFn); max_hyp_len caps the hypotheses so scored (None: min(T, 1023)), longer ones keep the path term.
     log_probs: log_softmax(logits) if the caller already has it (the head kernel's by-product, ``logits.log_probs`` of
     Seq2Seq.logits -- picked up from that attribute when not given)."""
     B = logits.shape[1]
     if sample_ids is not None and int(sample_base) >= 0:
         raise ValueError("sample_ids and sample_base >= 0 are two addressings of the same draws: give one")
+    _check_score(score_function, max_hyp_len, per_step)
     if log_probs is None:
         # the by-product is valid only for the tensor as the head kernel wrote it: any in-place edit since bumps _version
         log_probs = getattr(logits, "log_probs", None)
@@ -264,7 +317,8 @@ def pg_ctc_loss(logits, in_len, targets, tg_len, lam=1.0, seed=0, offset=0, glob
             log_probs = None
     return PGCTCLossFn.apply(logits, in_len, targets, tg_len, float(lam), int(seed), int(offset),
                              int(global_batch or B), int(blank), int(beam), int(sample_base), bool(per_step), log_probs,
-                             num_samples, baseline, reward_unit, word_delimiter, sample_ids)
+                             num_samples, baseline, reward_unit, word_delimiter, sample_ids, score_function,
+                             None if max_hyp_len is None else int(max_hyp_len))
 
 
 class CTCLoss(nn.Module):

@@ -438,11 +438,12 @@ class PolicyGradientTrainer(DataParallelStep):
     ``step_accumulated(micro_batches, utt_ids=None)`` is one optimizer step over several such batches (DataParallelStep): every
     micro-batch samples with the same offset ``nstep + 1`` and distinct ids -- by default ``default_utt_ids``, micro-batch j a contiguous
     slice of the global batch --, and ``last_stats`` / ``last_sample_rewards`` hold the micro-batches' statistics concatenated in call
-    order (real rows only)."""
+    order (real rows only), and so does ``last_sequence_scored``."""
 
     def __init__(self, model, lr=5e-4, lam=1.0, seed=0, blank=0, world_size=1, process_group=None, rank=0,
                  reward_decoder="greedy", beam_size=16, precision=None, reward_mode="utterance", num_samples=1,
-                 reward_baseline="hypothesis", reward_unit="char", word_delimiter=None, max_grad_norm=None):
+                 reward_baseline="hypothesis", reward_unit="char", word_delimiter=None, max_grad_norm=None,
+                 score_function="path", max_hyp_len=None):
         """reward_mode: "utterance" (default) -- one reward R = -ED / |y| per utterance, the sum of the reference's per-step rewards
         (policy_grad.py:10-15) up to a constant the baseline removes; "per_step" -- the per-step rewards themselves, as rewards-to-go
         per frame against the greedy path's reward-to-go at the same frame (loss.PGCTCLossFn; greedy baseline only).
@@ -458,7 +459,13 @@ class PolicyGradientTrainer(DataParallelStep):
         ``word_delimiter`` (the alphabet's " "; not the blank) like str.split(" "), for every sample and baseline reward (the CTC term
         stays normalised by the character count; not with reward_mode="per_step"; T <= MAX_WORD_FRAMES).
         max_grad_norm: clip the reduced gradient to this global L2 norm inside the step and skip non-finite gradients
-        (DataParallelStep; None = off); ``last_grad_norm`` and ``clip_counts()`` report."""
+        (DataParallelStep; None = off); ``last_grad_norm`` and ``clip_counts()`` report.
+        score_function: "path" (default) -- the REINFORCE term scores a sample by its frame path, log p(pi_k | x); "sequence" -- by
+        the CTC likelihood of its collapsed hypothesis, log p(y_k | x) over all alignments: the same expected gradient with no larger
+        variance (loss.PGCTCLossFn; any num_samples, baseline, reward_decoder and reward_unit; not with reward_mode="per_step").
+        max_hyp_len ("sequence" only): hypotheses of more tokens keep the path-level term; None = min(T, MAX_HYP_LEN).  It bounds the
+        hypothesis-lattice workspace, 2 * K*B*T * roundup64(2*Lh+1) * 4 bytes.  ``last_sequence_scored``: (num_samples, B) bool on the
+        device, which samples took the sequence term in the last step (None with "path"); reading it synchronises."""
         super().__init__(model, lr=lr, world_size=world_size, process_group=process_group, precision=precision,
                          max_grad_norm=max_grad_norm)
         if reward_decoder not in ("greedy", "beam"):
@@ -472,6 +479,9 @@ class PolicyGradientTrainer(DataParallelStep):
         self.num_samples, self.reward_baseline = int(num_samples), reward_baseline
         self._check_unit(reward_unit, word_delimiter, blank)
         self.reward_unit, self.word_delimiter = reward_unit, (None if word_delimiter is None else int(word_delimiter))
+        self._check_score(score_function, max_hyp_len)
+        self.score_function, self.max_hyp_len = score_function, (None if max_hyp_len is None else int(max_hyp_len))
+        self.last_sequence_scored = None
         self.lam = lam
         # ONE sampling seed for all ranks: a rank addresses its draws by GLOBAL utterance index (contiguous shards: rank *
         # local batch), so N ranks sample exactly the paths of one process holding the whole batch -- the N-rank REINFORCE
@@ -503,6 +513,12 @@ class PolicyGradientTrainer(DataParallelStep):
     MAX_VOCAB = 64             # CTC lattice / frame kernels: one wave per (t, b) row
     MAX_SAMPLES = 16           # multi-sample kernels: sampled paths per utterance (PGASR_MAX_SAMPLES)
     MAX_WORD_FRAMES = 4094     # word-level reward: token rows of at most PGASR_WORD_MAX_STRIDE (frames, target symbols)
+    MAX_HYP_LEN = 1023         # sequence-level score: hypotheses of at most this many tokens (2L+1 <= 2048 lattice states)
+
+    def _check_score(self, score_function, max_hyp_len):
+        """A known score function; max_hyp_len a non-negative integer and only with "sequence"; "sequence" not with per-step rewards."""
+        from .loss import _check_score
+        _check_score(score_function, max_hyp_len, self.reward_mode == "per_step")
 
     def _check_unit(self, reward_unit, word_delimiter, blank):
         """A known reward unit; "word" with a delimiter in [0, V) that is not the blank, and not with per-step rewards."""
@@ -532,6 +548,7 @@ class PolicyGradientTrainer(DataParallelStep):
             raise ValueError("beam_size > 128 is not supported by pgasr_ctc_beam_search")
         self._check_samples(self.num_samples, self.reward_baseline)
         self._check_unit(self.reward_unit, self.word_delimiter, self.blank)
+        self._check_score(self.score_function, self.max_hyp_len)
         if self.reward_unit == "word" and max(x.shape[2], targets.shape[1]) > self.MAX_WORD_FRAMES:
             raise ValueError(f"T = {x.shape[2]} frames (targets of {targets.shape[1]} symbols): the word-level reward takes token rows of at "
                              f"most {self.MAX_WORD_FRAMES} (pgasr_word_ids)")
@@ -599,7 +616,7 @@ class PolicyGradientTrainer(DataParallelStep):
         return grow(x), grow(targets), grow(fmask), grow(tmask)
 
     def forward_loss(self, batch, global_batch):
-        from .loss import pg_ctc_loss
+        from .loss import PGCTCLossFn, pg_ctc_loss
         x, targets, fmask, tmask = batch
         from . import hipops
         self._check_limits(x, targets)
@@ -621,14 +638,17 @@ class PolicyGradientTrainer(DataParallelStep):
                                           sample_base=sample_base,
                                           per_step=self.reward_mode == "per_step", num_samples=self.num_samples,
                                           baseline=self.reward_baseline, reward_unit=self.reward_unit,
-                                          word_delimiter=self.word_delimiter, sample_ids=sample_ids)
+                                          word_delimiter=self.word_delimiter, sample_ids=sample_ids,
+                                          score_function=self.score_function, max_hyp_len=self.max_hyp_len)
+        scored = PGCTCLossFn.last_sequence_scored                # (K,B) bool, None with score_function="path"
+        self.last_sequence_scored = scored[:, :real_b] if (padded and scored is not None) else scored
         R_all = R_s if R_s.dim() == 2 else R_s.view(1, -1)       # (K,B): every sample's reward
         if R_s.dim() == 2:
             R_s = R_s.mean(dim=0)
         self.last_sample_rewards = R_all[:, :real_b] if padded else R_all
         self.last_stats = (nll[:real_b], R_s[:real_b], R_g[:real_b]) if padded else (nll, R_s, R_g)
         if self._micro is not None and self._micro.count > 1:
-            self._micro_stats.append((self.last_stats, self.last_sample_rewards))
+            self._micro_stats.append((self.last_stats, self.last_sample_rewards, self.last_sequence_scored))
         return loss
 
     def _sample_addressing(self, real_b, padded_b, device):
@@ -661,8 +681,10 @@ class PolicyGradientTrainer(DataParallelStep):
             loss = super()._accumulate(micro_batches, utt_ids, hold_last=hold_last)
             if len(self._micro_stats) > 1:
                 # the micro-batches' statistics in call order, real rows only
-                self.last_stats = tuple(torch.cat([st[i] for st, _ in self._micro_stats]) for i in range(3))
-                self.last_sample_rewards = torch.cat([r for _, r in self._micro_stats], dim=1)
+                self.last_stats = tuple(torch.cat([st[i] for st, _, _ in self._micro_stats]) for i in range(3))
+                self.last_sample_rewards = torch.cat([r for _, r, _ in self._micro_stats], dim=1)
+                if self.score_function == "sequence":
+                    self.last_sequence_scored = torch.cat([q for _, _, q in self._micro_stats], dim=1)
         finally:
             self._micro_stats = []
         return loss
