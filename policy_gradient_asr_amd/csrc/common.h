@@ -44,6 +44,28 @@ __device__ __forceinline__ float wave_max(float v) {
     return v;
 }
 
+// ---- sum_{t < Tb} log p(path[t,b]) of utterance b over a 256-thread workgroup (the three pg_loss_value kernels) ----
+// Thread i adds frames i, i + 256, .. in t order, then a halving tree over red[256]: a fixed order, so the sum is reproducible.
+// frame_coef (T,B): each term is first multiplied by its frame's coefficient; nullptr: plain sum.  Every thread returns the
+// sum, and the closing barrier lets the caller overwrite red at once.
+__device__ __forceinline__ float block_path_logprob_sum(const float* __restrict__ lp, const int32_t* __restrict__ path,
+                                                        const float* __restrict__ frame_coef, int Tb, int b, int B, int V, float* red) {
+    float s = 0.f;
+    for (int t = threadIdx.x; t < Tb; t += 256) {
+        const float v = lp[((size_t)t * B + b) * V + path[(size_t)t * B + b]];
+        s += frame_coef ? frame_coef[(size_t)t * B + b] * v : v;
+    }
+    red[threadIdx.x] = s;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+        __syncthreads();
+    }
+    const float r = red[0];
+    __syncthreads();
+    return r;
+}
+
 // ---- Philox4x32-10 (Salmon et al. 2011); same constants as oracle/decode_ref.py ----
 __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,
                                               uint32_t k0, uint32_t k1, uint32_t out[4]) {

@@ -137,30 +137,35 @@ __device__ __forceinline__ void ctc_labels_body(const int32_t* __restrict__ targ
         }
 }
 
+// LDS-only barrier: __syncthreads() would also drain vmcnt (the storer's stores, the emission prefetch)
+#define ROW_BARRIER() do { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_s_barrier(); \
+                           asm volatile("" ::: "memory"); } while (0)
+
+// The alpha (ROLE 0) or beta (ROLE 1) sweep of ONE label sequence over one utterance's frames: the body of both
+// ctc_lattice_kernel (the targets) and ctc_hyp_lattice_kernel (the sampled hypotheses).  The caller resolves everything that
+// depends on how its lattices are addressed: lpb = log_probs + b*V (frame t of the utterance at lpb + t*fstride), tgt / Tb / Lb
+// the label row and the clamped lengths, out / outmax this lattice's alpha or beta rows [T][SP] and row references [T],
+// nll64 / nll_out where ROLE 0 leaves the sequence's nll, rows the kernel's LDS block of 2 * (NSPT * CTC_THREADS + 4) doubles.
 // NSPT = states per thread, a compile-time constant: the common case S <= 256 (L <= 127) runs with no per-state
 // loop or bound checks on the T-step chain (measured 492 -> see DESIGN.md at T=1000, S=201).
 template <int NSPT, int ROLE>
 __device__ __forceinline__ void ctc_lattice_body(
-    const float* __restrict__ lp, const int32_t* __restrict__ targets,
-    const int32_t* __restrict__ in_len, const int32_t* __restrict__ tg_len,
-    int T, int B, int V, int Lmax, int Smax, int blank, CtcWs ws, float* __restrict__ nll_out) {
-    const int b = blockIdx.x;
+    const float* __restrict__ lpb, size_t fstride, const int32_t* __restrict__ tgt, int Tb, int Lb, int V, int blank,
+    float* __restrict__ out, int SP, double* __restrict__ outmax, double* __restrict__ nll64, float* __restrict__ nll_out,
+    double* __restrict__ rows) {
     constexpr int role = ROLE;          // compile-time: the frame loop carries no direction test
     const int tid = threadIdx.x;
-    int Tb = in_len[b]; Tb = Tb < 0 ? 0 : (Tb > T ? T : Tb);
-    int Lb = tg_len[b]; Lb = Lb < 0 ? 0 : (Lb > Lmax ? Lmax : Lb);
     const int S = 2 * Lb + 1;
-    const int32_t* tgt = targets + (size_t)b * Lmax;
 
     // row buffers: position p = s + 2, two guard cells of -inf on each side
     constexpr int ROW = NSPT * CTC_THREADS + 4;
-    __shared__ double row[2][ROW];
+    auto row = [&](int i) { return rows + i * ROW; };      // the two row buffers
     // Wave 4 is the STORER: it copies each finished row from LDS to the alpha/beta array.  With the store in the
     // compute threads the chain waited every step for the store's write acknowledgement: hipcc must use vmcnt(0)
     // for the emission prefetch as soon as a store is also outstanding (loads and stores retire out of order
     // with respect to each other) -- 391 us against 492 us before the NSPT template, see DESIGN.md.
     const bool storer = tid >= CTC_THREADS;
-    for (int i = tid; i < 2 * ROW; i += CTC_THREADS + 64) (&row[0][0])[i] = -INFINITY;
+    for (int i = tid; i < 2 * ROW; i += CTC_THREADS + 64) rows[i] = -INFINITY;
 
     // per-thread state descriptors
     int lab[NSPT];
@@ -179,8 +184,6 @@ __device__ __forceinline__ void ctc_lattice_body(
     }
     __syncthreads();
 
-    float* out = (role == 0 ? ws.alpha : ws.beta) + (size_t)b * T * ws.SP;
-    double* outmax = (role == 0 ? ws.amax : ws.bmax) + (size_t)b * T;
     // the storer wave's row write: maximum over the row (fixed butterfly order), then fp32 offsets
     double m_ref = 0.0;          // the storer's current reference (refreshed every 4th row)
     auto store_row = [&](const double* rc, int t_row, bool refresh) {
@@ -205,7 +208,7 @@ __device__ __forceinline__ void ctc_lattice_body(
             m_ref = (mw == -INFINITY) ? 0.0 : mw;
         }
         const double m = m_ref;
-        float* o = out + (size_t)t_row * ws.SP + ls;
+        float* o = out + (size_t)t_row * SP + ls;
 #pragma unroll
         for (int i = 0; i < NG; ++i)
             if (i < ng) o[64 * i] = (float)(v[i] - m);
@@ -214,7 +217,7 @@ __device__ __forceinline__ void ctc_lattice_body(
     if (Tb == 0) {
         if (role == 0 && tid == 0) {
             const double v = (Lb == 0) ? 0.0 : INFINITY;
-            ws.nll64[b] = v; nll_out[b] = (float)v;
+            *nll64 = v; *nll_out = (float)v;
         }
         return;
     }
@@ -224,7 +227,7 @@ __device__ __forceinline__ void ctc_lattice_body(
 
     // frame t0
     {
-        const float* lpt = lp + ((size_t)t0 * B + b) * V;
+        const float* lpt = lpb + (size_t)t0 * fstride;
 #pragma unroll
         for (int j = 0; j < NSPT; ++j) {
             const int s = storer ? S : tid + j * CTC_THREADS;
@@ -232,19 +235,16 @@ __device__ __forceinline__ void ctc_lattice_body(
                 double v = -INFINITY;
                 if (role == 0) { if (s <= 1) v = (double)lpt[lab[j]]; }
                 else           { if (s >= S - 2) v = (double)lpt[lab[j]]; }
-                row[0][s + 2] = v;
+                row(0)[s + 2] = v;
             }
         }
     }
     int cur = 0;
-    // LDS-only barrier: __syncthreads() would also drain vmcnt (the storer's stores, the emission prefetch)
-#define ROW_BARRIER() do { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_s_barrier(); \
-                           asm volatile("" ::: "memory"); } while (0)
     if (storer) {
         // its own loop (same number of barriers): nothing in this path ever waits for a store
         for (int k = 1; k < Tb; ++k) {
             ROW_BARRIER();
-            store_row(row[cur], t0 + (k - 1) * dt, ((k - 1) & 3) == 0);      // row[cur] = frame t0 + (k-1)*dt, stable until the next barrier
+            store_row(row(cur), t0 + (k - 1) * dt, ((k - 1) & 3) == 0);      // row(cur) = frame t0 + (k-1)*dt, stable until the next barrier
             cur ^= 1;
         }
     } else {
@@ -252,7 +252,7 @@ __device__ __forceinline__ void ctc_lattice_body(
 #pragma unroll
         for (int j = 0; j < NSPT; ++j) lpn[j] = 0.f;
         if (Tb > 1) {
-            const float* lpt = lp + ((size_t)(t0 + dt) * B + b) * V;
+            const float* lpt = lpb + (size_t)(t0 + dt) * fstride;
 #pragma unroll
             for (int j = 0; j < NSPT; ++j) lpn[j] = lpt[lab[j]];
         }
@@ -262,13 +262,13 @@ __device__ __forceinline__ void ctc_lattice_body(
 #pragma unroll
             for (int j = 0; j < NSPT; ++j) lpc[j] = lpn[j];
             if (k + 1 < Tb) {  // prefetch the next frame's emissions: off the dependent chain
-                const float* lpt = lp + ((size_t)(t + dt) * B + b) * V;
+                const float* lpt = lpb + (size_t)(t + dt) * fstride;
 #pragma unroll
                 for (int j = 0; j < NSPT; ++j) lpn[j] = lpt[lab[j]];
             }
             ROW_BARRIER();
-            const double* rc = row[cur];
-            double* rn = row[cur ^ 1];
+            const double* rc = row(cur);
+            double* rn = row(cur ^ 1);
 #pragma unroll
             for (int j = 0; j < NSPT; ++j) {
                 // no test on the chain: all three neighbours are read (guard cells on both sides), a state that may not
@@ -285,91 +285,48 @@ __device__ __forceinline__ void ctc_lattice_body(
             cur ^= 1;
         }
     }
-#undef ROW_BARRIER
     {                    // the last frame's row (the only one when Tb == 1)
         __syncthreads();
-        if (storer) store_row(row[cur], t0 + (Tb - 1) * dt, ((Tb - 1) & 3) == 0);
+        if (storer) store_row(row(cur), t0 + (Tb - 1) * dt, ((Tb - 1) & 3) == 0);
     }
     if (role == 0) {
         __syncthreads();
         if (tid == 0) {
-            const double* rc = row[cur];
+            const double* rc = row(cur);
             const double ll = lse3(rc[S - 1 + 2], (S > 1) ? rc[S - 2 + 2] : -INFINITY, -INFINITY);
-            ws.nll64[b] = -ll;
-            nll_out[b] = (float)(-ll);
+            *nll64 = -ll;
+            *nll_out = (float)(-ll);
         }
     }
 }
+#undef ROW_BARRIER
 
+// grid (B,3): y = 0 alpha, y = 1 beta, y = 2 the label -> states lists; one LDS block serves whichever sweep the workgroup runs
 template <int NSPT>
 __global__ __launch_bounds__(CTC_THREADS + 64) void ctc_lattice_kernel(
     const float* __restrict__ lp, const int32_t* __restrict__ targets,
     const int32_t* __restrict__ in_len, const int32_t* __restrict__ tg_len,
     int T, int B, int V, int Lmax, int Smax, int blank, CtcWs ws, float* __restrict__ nll_out, int role_base) {
+    __shared__ double rows[2 * (NSPT * CTC_THREADS + 4)];
+    const int b = blockIdx.x;
     const int role = blockIdx.y + role_base;      // one uniform branch per workgroup, none per frame
-    if (role == 0) ctc_lattice_body<NSPT, 0>(lp, targets, in_len, tg_len, T, B, V, Lmax, Smax, blank, ws, nll_out);
-    else if (role == 1) ctc_lattice_body<NSPT, 1>(lp, targets, in_len, tg_len, T, B, V, Lmax, Smax, blank, ws, nll_out);
-    else ctc_labels_body(targets, tg_len, V, Lmax, Smax, blank, ws);
-}
-
-
-// one wave per (t,b)
-__global__ __launch_bounds__(256) void ctc_grad_kernel(
-    const float* __restrict__ lp, const int32_t* __restrict__ in_len, const int32_t* __restrict__ tg_len,
-    int T, int B, int V, int Lmax, int Smax, int blank, CtcWs ws,
-    const float* __restrict__ utt_scale, const float* __restrict__ pg_coef,
-    const int32_t* __restrict__ pg_path, int coef_per_frame, float* __restrict__ grad) {
-    const int lane = threadIdx.x & 63;
-    const long long w = (long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    if (w >= (long long)T * B) return;
-    const int t = (int)(w / B), b = (int)(w % B);
+    if (role >= 2) { ctc_labels_body(targets, tg_len, V, Lmax, Smax, blank, ws); return; }
     int Tb = in_len[b]; Tb = Tb < 0 ? 0 : (Tb > T ? T : Tb);
     int Lb = tg_len[b]; Lb = Lb < 0 ? 0 : (Lb > Lmax ? Lmax : Lb);
-    const size_t o = ((size_t)t * B + b) * V;
-    if (t >= Tb) { if (lane < V) grad[o + lane] = 0.f; return; }
-
-    const float lpv = (lane < V) ? lp[o + lane] : 0.f;
-    const float sm = (lane < V) ? __expf(lpv) : 0.f;
-    float g = 0.f;
-    const double nll = ws.nll64[b];
-    if (nll != INFINITY) {
-        const int S = 2 * Lb + 1;
-        const float* al = ws.alpha + ((size_t)b * T + t) * ws.SP;
-        const float* be = ws.beta + ((size_t)b * T + t) * ws.SP;
-        // log occupancy of state s = (alpha offset + beta offset) + [row maxima + nll - log p]: the bracket is O(10)
-        const double cst = ws.amax[(size_t)b * T + t] + ws.bmax[(size_t)b * T + t] + nll;
-        // blank occupancy: even states, all lanes, fixed butterfly order
-        const float lpb = __shfl(lpv, blank, 64);
-        const float cb = (float)(cst - (double)lpb);
-        float accb = 0.f;
-        for (int s = 2 * lane; s < S; s += 128)
-            accb += __expf((al[s] + be[s]) + cb);
-        accb = wave_sum(accb);
-        float occ = accb;
-        if (lane < V && lane != blank) {
-            const int32_t* lo = ws.lab_off + (size_t)b * (V + 1);
-            const int32_t* ls = ws.lab_states + (size_t)b * Smax;
-            float acc = 0.f;
-            const float cl = (float)(cst - (double)lpv);
-            for (int i = lo[lane]; i < lo[lane + 1]; ++i) {
-                const int s = ls[i];
-                acc += __expf((al[s] + be[s]) + cl);
-            }
-            occ = acc;
-        }
-        const float sc = utt_scale ? utt_scale[b] : 1.f;
-        g = sc * (sm - occ);
-    }
-    if (pg_coef != nullptr && pg_path != nullptr) {
-        const int k = pg_path[(size_t)t * B + b];
-        g += pg_coef[coef_per_frame ? (size_t)t * B + b : (size_t)b] * (sm - (lane == k ? 1.f : 0.f));
-    }
-    if (lane < V) grad[o + lane] = g;
+    const float* lpb = lp + (size_t)b * V;
+    const size_t fstride = (size_t)B * V;
+    const int32_t* tgt = targets + (size_t)b * Lmax;
+    float* out = (role == 0 ? ws.alpha : ws.beta) + (size_t)b * T * ws.SP;
+    double* outmax = (role == 0 ? ws.amax : ws.bmax) + (size_t)b * T;
+    if (role == 0) ctc_lattice_body<NSPT, 0>(lpb, fstride, tgt, Tb, Lb, V, blank, out, ws.SP, outmax, ws.nll64 + b, nll_out + b, rows);
+    else           ctc_lattice_body<NSPT, 1>(lpb, fstride, tgt, Tb, Lb, V, blank, out, ws.SP, outmax, ws.nll64 + b, nll_out + b, rows);
 }
 
 // The CTC part of one (t,b) row's gradient, utt_scale_b * (softmax - occupancy) in this lane (0 when no alignment exists);
-// lpv / sm = this lane's log-prob / probability.  ctc_grad_kernel's own lines, for ctc_grad_multi_kernel: that kernel keeps
-// them inline (calling this helper changes its register allocation, and its code is to stay as measured).
+// lpv / sm = this lane's log-prob / probability.  The one occupancy routine of the three gradient kernels below: b names the
+// lattice in ws, so ctc_grad_seq_kernel calls it once more per sequence-scored hypothesis with the pair index and its workspace.
+// (ctc_grad_kernel once kept these lines inline: stand-alone at B = 32, T = 1000 that form ran 31.2 us against 31.8 us with the
+// call, and the step cannot tell them apart -- trace means 67.6 / 72.1 us inline, 71.3 us with the call; NOTES.md 0.07.)
 __device__ __forceinline__ float ctc_grad_row(float lpv, float sm, int lane, int t, int b, int T, int V, int Lb, int Smax, int blank,
                                               CtcWs ws, const float* __restrict__ utt_scale) {
     float g = 0.f;
@@ -403,6 +360,31 @@ __device__ __forceinline__ float ctc_grad_row(float lpv, float sm, int lane, int
         g = sc * (sm - occ);
     }
     return g;
+}
+
+// one wave per (t,b)
+__global__ __launch_bounds__(256) void ctc_grad_kernel(
+    const float* __restrict__ lp, const int32_t* __restrict__ in_len, const int32_t* __restrict__ tg_len,
+    int T, int B, int V, int Lmax, int Smax, int blank, CtcWs ws,
+    const float* __restrict__ utt_scale, const float* __restrict__ pg_coef,
+    const int32_t* __restrict__ pg_path, int coef_per_frame, float* __restrict__ grad) {
+    const int lane = threadIdx.x & 63;
+    const long long w = (long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (w >= (long long)T * B) return;
+    const int t = (int)(w / B), b = (int)(w % B);
+    int Tb = in_len[b]; Tb = Tb < 0 ? 0 : (Tb > T ? T : Tb);
+    int Lb = tg_len[b]; Lb = Lb < 0 ? 0 : (Lb > Lmax ? Lmax : Lb);
+    const size_t o = ((size_t)t * B + b) * V;
+    if (t >= Tb) { if (lane < V) grad[o + lane] = 0.f; return; }
+
+    const float lpv = (lane < V) ? lp[o + lane] : 0.f;
+    const float sm = (lane < V) ? __expf(lpv) : 0.f;
+    float g = ctc_grad_row(lpv, sm, lane, t, b, T, V, Lb, Smax, blank, ws, utt_scale);
+    if (pg_coef != nullptr && pg_path != nullptr) {
+        const int k = pg_path[(size_t)t * B + b];
+        g += pg_coef[coef_per_frame ? (size_t)t * B + b : (size_t)b] * (sm - (lane == k ? 1.f : 0.f));
+    }
+    if (lane < V) grad[o + lane] = g;
 }
 
 // Multi-sample REINFORCE (pgasr_ctc_grad_from_lattice_multi): the CTC part above, then the K terms
@@ -444,147 +426,9 @@ __global__ __launch_bounds__(256) void ctc_grad_multi_kernel(
 // contributes nothing, as for targets.  The K*B hypothesis lattices live in a workspace of their own, a CtcWs for the "batch" of
 // pairs p = k*B + b with Smax = 2*Lh+1; every pair reads log-prob row b of the ONE (T,B,V) tensor.
 //
-// The lattice body below is ctc_lattice_body's recursion, storer wave and numerics with the row buffers handed in (the kernel
-// owns one LDS block for whichever states-per-thread variant the pair's REAL length selects) and the pair's rows addressed by
-// the caller.  A copy, not a new template parameter of ctc_lattice_body: the measured kernels above stay as compiled.
-template <int NSPT, int ROLE>
-__device__ __forceinline__ void ctc_hyp_lattice_body(
-    const float* __restrict__ lpb,      // log_probs + b*V: frame t of this utterance at lpb + t*fstride
-    size_t fstride, const int32_t* __restrict__ tgt, int Tb, int Lb, int V, int blank,
-    float* __restrict__ out, int SP, double* __restrict__ outmax, double* __restrict__ nll64, float* __restrict__ nll_out,
-    double* __restrict__ rows) {
-    constexpr int role = ROLE;
-    const int tid = threadIdx.x;
-    const int S = 2 * Lb + 1;
-    // row buffers: position p = s + 2, two guard cells of -inf on each side
-    constexpr int ROW = NSPT * CTC_THREADS + 4;
-    auto row = [&](int i) { return rows + i * ROW; };      // the two row buffers
-    const bool storer = tid >= CTC_THREADS;       // wave 4 copies each finished row from LDS to the lattice (see ctc_lattice_body)
-    for (int i = tid; i < 2 * ROW; i += CTC_THREADS + 64) rows[i] = -INFINITY;
-
-    int lab[NSPT];
-    bool skip[NSPT];   // alpha: may come from s-2 ; beta: may go to s+2
-#pragma unroll
-    for (int j = 0; j < NSPT; ++j) {
-        const int s = storer ? S : tid + j * CTC_THREADS;
-        lab[j] = blank; skip[j] = false;
-        if (s < S && (s & 1)) lab[j] = tgt[s >> 1];
-        if (role == 0) {
-            if (s < S && (s & 1) && s >= 3) skip[j] = (tgt[s >> 1] != tgt[(s >> 1) - 1]);
-        } else {
-            if (s + 2 < S && (s & 1)) skip[j] = (tgt[(s >> 1) + 1] != tgt[s >> 1]);
-        }
-        if (lab[j] < 0 || lab[j] >= V) lab[j] = blank;  // defensive: never index outside the row
-    }
-    __syncthreads();
-
-    double m_ref = 0.0;          // the storer's current reference (refreshed every 4th row)
-    auto store_row = [&](const double* rc, int t_row, bool refresh) {
-        constexpr int NG = NSPT * 4;
-        const int ls = tid - CTC_THREADS;
-        const int ng = (S + 63) >> 6;           // 64-state groups that hold states (wave-uniform)
-        double v[NG];
-#pragma unroll
-        for (int i = 0; i < NG; ++i) v[i] = rc[ls + 64 * i + 2];
-        if (refresh) {
-            double ml = -INFINITY;
-#pragma unroll
-            for (int i = 0; i < NG; ++i) ml = fmax(ml, v[i]);
-            const double mw = (double)wave_max_f32_all((float)ml);
-            m_ref = (mw == -INFINITY) ? 0.0 : mw;
-        }
-        const double m = m_ref;
-        float* o = out + (size_t)t_row * SP + ls;
-#pragma unroll
-        for (int i = 0; i < NG; ++i)
-            if (i < ng) o[64 * i] = (float)(v[i] - m);
-        if (ls == 0) outmax[t_row] = m;
-    };
-    if (Tb == 0) {
-        if (role == 0 && tid == 0) {
-            const double v = (Lb == 0) ? 0.0 : INFINITY;
-            *nll64 = v; *nll_out = (float)v;
-        }
-        return;
-    }
-
-    const int t0 = (role == 0) ? 0 : Tb - 1;
-    const int dt = (role == 0) ? 1 : -1;
-    {
-        const float* lpt = lpb + (size_t)t0 * fstride;
-#pragma unroll
-        for (int j = 0; j < NSPT; ++j) {
-            const int s = storer ? S : tid + j * CTC_THREADS;
-            if (s < S) {
-                double v = -INFINITY;
-                if (role == 0) { if (s <= 1) v = (double)lpt[lab[j]]; }
-                else           { if (s >= S - 2) v = (double)lpt[lab[j]]; }
-                row(0)[s + 2] = v;
-            }
-        }
-    }
-    int cur = 0;
-    // LDS-only barrier: __syncthreads() would also drain vmcnt (the storer's stores, the emission prefetch)
-#define ROW_BARRIER() do { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_s_barrier(); \
-                           asm volatile("" ::: "memory"); } while (0)
-    if (storer) {
-        for (int k = 1; k < Tb; ++k) {
-            ROW_BARRIER();
-            store_row(row(cur), t0 + (k - 1) * dt, ((k - 1) & 3) == 0);
-            cur ^= 1;
-        }
-    } else {
-        float lpn[NSPT];
-#pragma unroll
-        for (int j = 0; j < NSPT; ++j) lpn[j] = 0.f;
-        if (Tb > 1) {
-            const float* lpt = lpb + (size_t)(t0 + dt) * fstride;
-#pragma unroll
-            for (int j = 0; j < NSPT; ++j) lpn[j] = lpt[lab[j]];
-        }
-        for (int k = 1; k < Tb; ++k) {
-            const int t = t0 + k * dt;
-            float lpc[NSPT];
-#pragma unroll
-            for (int j = 0; j < NSPT; ++j) lpc[j] = lpn[j];
-            if (k + 1 < Tb) {  // prefetch the next frame's emissions: off the dependent chain
-                const float* lpt = lpb + (size_t)(t + dt) * fstride;
-#pragma unroll
-                for (int j = 0; j < NSPT; ++j) lpn[j] = lpt[lab[j]];
-            }
-            ROW_BARRIER();
-            const double* rc = row(cur);
-            double* rn = row(cur ^ 1);
-#pragma unroll
-            for (int j = 0; j < NSPT; ++j) {
-                const int s = tid + j * CTC_THREADS;
-                const int p = s + 2;
-                const double a0 = rc[p];
-                const double a1 = rc[role == 0 ? p - 1 : p + 1];
-                const double a2r = rc[role == 0 ? p - 2 : p + 2];
-                const double a2 = skip[j] ? a2r : -INFINITY;
-                const double v = lse3(a0, a1, a2) + (double)lpc[j];
-                rn[p] = (s < S) ? v : -INFINITY;
-            }
-            cur ^= 1;
-        }
-    }
-#undef ROW_BARRIER
-    {                    // the last frame's row (the only one when Tb == 1)
-        __syncthreads();
-        if (storer) store_row(row(cur), t0 + (Tb - 1) * dt, ((Tb - 1) & 3) == 0);
-    }
-    if (role == 0) {
-        __syncthreads();
-        if (tid == 0) {
-            const double* rc = row(cur);
-            const double ll = lse3(rc[S - 1 + 2], (S > 1) ? rc[S - 2 + 2] : -INFINITY, -INFINITY);
-            *nll64 = -ll;
-            *nll_out = (float)(-ll);
-        }
-    }
-}
-
+// ctc_hyp_lattice_kernel runs ctc_lattice_body on them: it owns one LDS block for whichever states-per-thread variant the
+// pair's REAL length selects and addresses the pair's rows.
+//
 // grid (K*B, 3): pair p = k*B + b; y = 0 alpha, y = 1 beta, y = 2 the label -> states lists.  NMAX = the states-per-thread variant
 // that holds 2*Lh+1 states; a pair whose own 2*len+1 fits a smaller variant runs that one (a uniform branch per workgroup, read
 // from hyp_len on the device: no host synchronisation), so hypotheses near the target length do not pay for the cap.
@@ -609,8 +453,8 @@ __global__ __launch_bounds__(CTC_THREADS + 64) void ctc_hyp_lattice_kernel(
     float* out = (role == 0 ? ws.alpha : ws.beta) + (size_t)p * T * ws.SP;
     double* outmax = (role == 0 ? ws.amax : ws.bmax) + (size_t)p * T;
 #define PGASR_HYP_BODY(N) do { \
-        if (role == 0) ctc_hyp_lattice_body<N, 0>(lpb, fstride, tgt, Tb, Lb, V, blank, out, ws.SP, outmax, ws.nll64 + p, hyp_nll + p, rows); \
-        else           ctc_hyp_lattice_body<N, 1>(lpb, fstride, tgt, Tb, Lb, V, blank, out, ws.SP, outmax, ws.nll64 + p, hyp_nll + p, rows); \
+        if (role == 0) ctc_lattice_body<N, 0>(lpb, fstride, tgt, Tb, Lb, V, blank, out, ws.SP, outmax, ws.nll64 + p, hyp_nll + p, rows); \
+        else           ctc_lattice_body<N, 1>(lpb, fstride, tgt, Tb, Lb, V, blank, out, ws.SP, outmax, ws.nll64 + p, hyp_nll + p, rows); \
     } while (0)
     if constexpr (NMAX == 1) {
         PGASR_HYP_BODY(1);
@@ -661,7 +505,7 @@ __global__ __launch_bounds__(256) void ctc_grad_seq_kernel(
 }
 
 // terms[b] = nll_b utt_scale_b + sum_k coef[k,b] * ( hyp_len[k,b] <= Lh ? hyp_nll[k,b] : -sum_{t<T_b} log p(paths[k,t,b]) ): the path
-// sums in pg_loss_value_kernel's fixed order, the K products added in k order; a +inf hypothesis nll adds nothing.
+// sums in block_path_logprob_sum's fixed order, the K products added in k order; a +inf hypothesis nll adds nothing.
 __global__ __launch_bounds__(256) void pg_loss_value_seq_kernel(const float* __restrict__ lp, const int32_t* __restrict__ paths, int K,
                                                                 const int32_t* __restrict__ in_len, const float* __restrict__ nll,
                                                                 const float* __restrict__ utt_scale, const float* __restrict__ coef,
@@ -678,20 +522,44 @@ __global__ __launch_bounds__(256) void pg_loss_value_seq_kernel(const float* __r
             if (hn != INFINITY) acc -= coef[p] * hn;
             continue;
         }
-        const int32_t* path = paths + (size_t)k * T * B;
-        float s = 0.f;
-        for (int t = threadIdx.x; t < Tb; t += 256)
-            s += lp[((size_t)t * B + b) * V + path[(size_t)t * B + b]];
-        red[threadIdx.x] = s;
-        __syncthreads();
-        for (int o = 128; o > 0; o >>= 1) {
-            if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-            __syncthreads();
-        }
-        acc += coef[p] * red[0];
-        __syncthreads();          // red[0] read by every thread before the next path overwrites it
+        acc += coef[p] * block_path_logprob_sum(lp, paths + (size_t)k * T * B, nullptr, Tb, b, B, V, red);
     }
     if (threadIdx.x == 0) terms[b] = nll[b] * utt_scale[b] - acc;
+}
+
+// ---- what the entry points below share: argument checks, workspace binding, the gradient passes' launch ----
+static int ctc_args_ok(int T, int B, int V, int Lmax, int blank) {
+    if (T <= 0 || B <= 0 || V <= 0 || Lmax < 0 || blank < 0 || blank >= V) return PGASR_ERR_INVALID_ARG;
+    if (2 * (long long)Lmax + 1 > CTC_SMAX || V > CTC_VMAX) return PGASR_ERR_UNSUPPORTED;
+    return PGASR_OK;
+}
+
+static int ctc_hyp_args_ok(int T, int B, int V, int K, int Lh) {
+    if (T <= 0 || B <= 0 || V <= 0 || Lh < 0) return PGASR_ERR_INVALID_ARG;
+    if (K < 1 || K > PGASR_MAX_SAMPLES) return PGASR_ERR_INVALID_ARG;
+    if (2 * (long long)Lh + 1 > CTC_SMAX || V > CTC_VMAX) return PGASR_ERR_UNSUPPORTED;
+    if ((long long)K * B > 0x7fffffffLL / 4) return PGASR_ERR_UNSUPPORTED;
+    return PGASR_OK;
+}
+
+// lays *ws out over the caller's workspace of N lattices; false when that is missing or too small
+static bool ctc_ws_bind(int T, int N, int V, int Smax, CtcWs* ws, void* workspace, size_t workspace_bytes) {
+    const size_t need = ctc_ws_layout(T, N, V, Smax, ws, (char*)workspace);
+    return workspace && workspace_bytes >= need;
+}
+
+// A gradient pass: one wave per (t,b) row, four rows per workgroup.  Every gradient kernel starts with the same arguments up to
+// utt_scale; `tail` is what follows them.
+template <class Kernel, class... Tail>
+static int ctc_launch_grad(Kernel kernel, const float* log_probs, const int32_t* input_lengths, const int32_t* target_lengths,
+                           int T, int B, int V, int Lmax, int blank, const CtcWs& ws, const float* utt_scale, void* stream, Tail... tail) {
+    const long long waves = (long long)T * B;
+    const int wpb = 4;
+    const unsigned blocks = (unsigned)((waves + wpb - 1) / wpb);
+    PGASR_LAUNCH_KERNEL(kernel, dim3(blocks), dim3(64 * wpb), 0, (hipStream_t)stream,
+                       log_probs, input_lengths, target_lengths, T, B, V, Lmax > 0 ? Lmax : 1, 2 * Lmax + 1, blank, ws, utt_scale, tail...);
+    PGASR_CHECK_LAUNCH();
+    return PGASR_OK;
 }
 
 }  // namespace
@@ -708,13 +576,12 @@ extern "C" int pgasr_ctc_loss_grad(const float* log_probs, const int32_t* target
                                    float* nll, float* grad_logits,
                                    void* workspace, size_t workspace_bytes, void* stream) {
     if (!log_probs || !targets || !input_lengths || !target_lengths || !nll) return PGASR_ERR_INVALID_ARG;
-    if (T <= 0 || B <= 0 || V <= 0 || Lmax < 0 || blank < 0 || blank >= V) return PGASR_ERR_INVALID_ARG;
     if ((pg_coef == nullptr) != (pg_path == nullptr)) return PGASR_ERR_INVALID_ARG;
+    const int ok = ctc_args_ok(T, B, V, Lmax, blank);
+    if (ok != PGASR_OK) return ok;
     const int Smax = 2 * Lmax + 1;
-    if (Smax > CTC_SMAX || V > CTC_VMAX) return PGASR_ERR_UNSUPPORTED;
     CtcWs ws;
-    const size_t need = ctc_ws_layout(T, B, V, Smax, &ws, (char*)workspace);
-    if (!workspace || workspace_bytes < need) return PGASR_ERR_WORKSPACE;
+    if (!ctc_ws_bind(T, B, V, Smax, &ws, workspace, workspace_bytes)) return PGASR_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     // Lmax == 0 still needs a valid targets row pointer; Lmax>=1 is the caller's job.
     // (a single-wave register-resident variant was measured SLOWER: 850 us vs 492 us at S=201 --
@@ -727,16 +594,9 @@ extern "C" int pgasr_ctc_loss_grad(const float* log_probs, const int32_t* target
     else PGASR_LATTICE(8);
 #undef PGASR_LATTICE
     PGASR_CHECK_LAUNCH();
-    if (grad_logits) {
-        const long long waves = (long long)T * B;
-        const int wpb = 4;
-        const unsigned blocks = (unsigned)((waves + wpb - 1) / wpb);
-        PGASR_LAUNCH_KERNEL(ctc_grad_kernel, dim3(blocks), dim3(64 * wpb), 0, st,
-                           log_probs, input_lengths, target_lengths, T, B, V,
-                           Lmax > 0 ? Lmax : 1, Smax, blank, ws, utt_scale, pg_coef, pg_path, 0, grad_logits);
-        PGASR_CHECK_LAUNCH();
-    }
-    return PGASR_OK;
+    if (!grad_logits) return PGASR_OK;
+    return ctc_launch_grad(ctc_grad_kernel, log_probs, input_lengths, target_lengths, T, B, V, Lmax, blank, ws, utt_scale, stream,
+                           pg_coef, pg_path, 0, grad_logits);
 }
 
 // Second half of pgasr_ctc_loss_grad on its own: the gradient pass over a lattice that an earlier
@@ -749,21 +609,13 @@ extern "C" int pgasr_ctc_grad_from_lattice(const float* log_probs, const int32_t
                                            int pg_coef_per_frame, float* grad_logits, void* workspace, size_t workspace_bytes,
                                            void* stream) {
     if (!log_probs || !input_lengths || !target_lengths || !grad_logits) return PGASR_ERR_INVALID_ARG;
-    if (T <= 0 || B <= 0 || V <= 0 || Lmax < 0 || blank < 0 || blank >= V) return PGASR_ERR_INVALID_ARG;
     if ((pg_coef == nullptr) != (pg_path == nullptr)) return PGASR_ERR_INVALID_ARG;
-    const int Smax = 2 * Lmax + 1;
-    if (Smax > CTC_SMAX || V > CTC_VMAX) return PGASR_ERR_UNSUPPORTED;
+    const int ok = ctc_args_ok(T, B, V, Lmax, blank);
+    if (ok != PGASR_OK) return ok;
     CtcWs ws;
-    const size_t need = ctc_ws_layout(T, B, V, Smax, &ws, (char*)workspace);
-    if (!workspace || workspace_bytes < need) return PGASR_ERR_WORKSPACE;
-    const long long waves = (long long)T * B;
-    const int wpb = 4;
-    const unsigned blocks = (unsigned)((waves + wpb - 1) / wpb);
-    PGASR_LAUNCH_KERNEL(ctc_grad_kernel, dim3(blocks), dim3(64 * wpb), 0, (hipStream_t)stream,
-                       log_probs, input_lengths, target_lengths, T, B, V,
-                       Lmax > 0 ? Lmax : 1, Smax, blank, ws, utt_scale, pg_coef, pg_path, pg_coef_per_frame ? 1 : 0, grad_logits);
-    PGASR_CHECK_LAUNCH();
-    return PGASR_OK;
+    if (!ctc_ws_bind(T, B, V, 2 * Lmax + 1, &ws, workspace, workspace_bytes)) return PGASR_ERR_WORKSPACE;
+    return ctc_launch_grad(ctc_grad_kernel, log_probs, input_lengths, target_lengths, T, B, V, Lmax, blank, ws, utt_scale, stream,
+                           pg_coef, pg_path, pg_coef_per_frame ? 1 : 0, grad_logits);
 }
 
 // pgasr_ctc_grad_from_lattice with K sampled paths per utterance (multi-sample REINFORCE): pg_paths (K,T,B), pg_coef (K,B).
@@ -772,32 +624,16 @@ extern "C" int pgasr_ctc_grad_from_lattice_multi(const float* log_probs, const i
                                                  const float* utt_scale, int K, const float* pg_coef, const int32_t* pg_paths,
                                                  float* grad_logits, void* workspace, size_t workspace_bytes, void* stream) {
     if (!log_probs || !input_lengths || !target_lengths || !grad_logits || !pg_coef || !pg_paths) return PGASR_ERR_INVALID_ARG;
-    if (T <= 0 || B <= 0 || V <= 0 || Lmax < 0 || blank < 0 || blank >= V) return PGASR_ERR_INVALID_ARG;
     if (K < 1 || K > PGASR_MAX_SAMPLES) return PGASR_ERR_INVALID_ARG;
-    const int Smax = 2 * Lmax + 1;
-    if (Smax > CTC_SMAX || V > CTC_VMAX) return PGASR_ERR_UNSUPPORTED;
+    const int ok = ctc_args_ok(T, B, V, Lmax, blank);
+    if (ok != PGASR_OK) return ok;
     CtcWs ws;
-    const size_t need = ctc_ws_layout(T, B, V, Smax, &ws, (char*)workspace);
-    if (!workspace || workspace_bytes < need) return PGASR_ERR_WORKSPACE;
-    const long long waves = (long long)T * B;
-    const int wpb = 4;
-    const unsigned blocks = (unsigned)((waves + wpb - 1) / wpb);
-    PGASR_LAUNCH_KERNEL(ctc_grad_multi_kernel, dim3(blocks), dim3(64 * wpb), 0, (hipStream_t)stream,
-                       log_probs, input_lengths, target_lengths, T, B, V,
-                       Lmax > 0 ? Lmax : 1, Smax, blank, ws, utt_scale, K, pg_coef, pg_paths, grad_logits);
-    PGASR_CHECK_LAUNCH();
-    return PGASR_OK;
+    if (!ctc_ws_bind(T, B, V, 2 * Lmax + 1, &ws, workspace, workspace_bytes)) return PGASR_ERR_WORKSPACE;
+    return ctc_launch_grad(ctc_grad_multi_kernel, log_probs, input_lengths, target_lengths, T, B, V, Lmax, blank, ws, utt_scale, stream,
+                           K, pg_coef, pg_paths, grad_logits);
 }
 
 // ---- sequence-level REINFORCE: the K*B hypothesis lattices and the passes over K+1 lattices (see the kernels' comment) ----
-static int ctc_hyp_args_ok(int T, int B, int V, int K, int Lh) {
-    if (T <= 0 || B <= 0 || V <= 0 || Lh < 0) return PGASR_ERR_INVALID_ARG;
-    if (K < 1 || K > PGASR_MAX_SAMPLES) return PGASR_ERR_INVALID_ARG;
-    if (2 * (long long)Lh + 1 > CTC_SMAX || V > CTC_VMAX) return PGASR_ERR_UNSUPPORTED;
-    if ((long long)K * B > 0x7fffffffLL / 4) return PGASR_ERR_UNSUPPORTED;
-    return PGASR_OK;
-}
-
 extern "C" size_t pgasr_ctc_hyp_workspace_bytes(int T, int B, int V, int K, int Lh) {
     if (ctc_hyp_args_ok(T, B, V, K, Lh) != PGASR_OK) return 0;
     return ctc_ws_layout(T, K * B, V, 2 * Lh + 1, nullptr, nullptr);
@@ -812,8 +648,7 @@ extern "C" int pgasr_ctc_hyp_lattice(const float* log_probs, const int32_t* hyp_
     if (ok != PGASR_OK) return ok;
     const int Smax = 2 * Lh + 1;
     CtcWs ws;
-    const size_t need = ctc_ws_layout(T, K * B, V, Smax, &ws, (char*)hyp_workspace);
-    if (!hyp_workspace || hyp_workspace_bytes < need) return PGASR_ERR_WORKSPACE;
+    if (!ctc_ws_bind(T, K * B, V, Smax, &ws, hyp_workspace, hyp_workspace_bytes)) return PGASR_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
 #define PGASR_HYP_LATTICE(NMAX) PGASR_LAUNCH_KERNEL(ctc_hyp_lattice_kernel<NMAX>, dim3(K * B, 3), dim3(CTC_THREADS + 64), 0, st, \
                         log_probs, hyp_tokens, hyp_stride, hyp_len, input_lengths, T, B, V, Lh, Smax, blank, ws, hyp_nll)
@@ -833,23 +668,15 @@ extern "C" int pgasr_ctc_grad_from_lattices_seq(const float* log_probs, const in
                                                 void* hyp_workspace, size_t hyp_workspace_bytes, void* stream) {
     if (!log_probs || !input_lengths || !target_lengths || !grad_logits || !pg_coef || !pg_paths || !hyp_len) return PGASR_ERR_INVALID_ARG;
     if (Lmax < 0 || blank < 0 || blank >= V) return PGASR_ERR_INVALID_ARG;
-    const int ok = ctc_hyp_args_ok(T, B, V, K, Lh);
+    int ok = ctc_hyp_args_ok(T, B, V, K, Lh);
+    if (ok == PGASR_OK) ok = ctc_args_ok(T, B, V, Lmax, blank);
     if (ok != PGASR_OK) return ok;
-    const int Smax = 2 * Lmax + 1, Smax_h = 2 * Lh + 1;
-    if (Smax > CTC_SMAX) return PGASR_ERR_UNSUPPORTED;
+    const int Smax_h = 2 * Lh + 1;
     CtcWs ws, hws;
-    const size_t need = ctc_ws_layout(T, B, V, Smax, &ws, (char*)workspace);
-    if (!workspace || workspace_bytes < need) return PGASR_ERR_WORKSPACE;
-    const size_t need_h = ctc_ws_layout(T, K * B, V, Smax_h, &hws, (char*)hyp_workspace);
-    if (!hyp_workspace || hyp_workspace_bytes < need_h) return PGASR_ERR_WORKSPACE;
-    const long long waves = (long long)T * B;
-    const int wpb = 4;
-    const unsigned blocks = (unsigned)((waves + wpb - 1) / wpb);
-    PGASR_LAUNCH_KERNEL(ctc_grad_seq_kernel, dim3(blocks), dim3(64 * wpb), 0, (hipStream_t)stream,
-                       log_probs, input_lengths, target_lengths, T, B, V,
-                       Lmax > 0 ? Lmax : 1, Smax, blank, ws, utt_scale, K, pg_coef, pg_paths, hyp_len, Lh, Smax_h, hws, grad_logits);
-    PGASR_CHECK_LAUNCH();
-    return PGASR_OK;
+    if (!ctc_ws_bind(T, B, V, 2 * Lmax + 1, &ws, workspace, workspace_bytes)) return PGASR_ERR_WORKSPACE;
+    if (!ctc_ws_bind(T, K * B, V, Smax_h, &hws, hyp_workspace, hyp_workspace_bytes)) return PGASR_ERR_WORKSPACE;
+    return ctc_launch_grad(ctc_grad_seq_kernel, log_probs, input_lengths, target_lengths, T, B, V, Lmax, blank, ws, utt_scale, stream,
+                           K, pg_coef, pg_paths, hyp_len, Lh, Smax_h, hws, grad_logits);
 }
 
 extern "C" int pgasr_pg_loss_value_seq(const float* log_probs, const int32_t* paths, int K, const int32_t* input_lengths,

@@ -226,7 +226,7 @@ __global__ __launch_bounds__(256) void pg_rewards_multi_kernel(const int32_t* __
 }
 
 // Value of the multi-sample objective per utterance: nll_b * utt_scale_b - sum_k coef[k,b] * sum_{t < T_b} log p(paths[k,t,b]).
-// One workgroup per utterance; per path the fixed-order reduction of pg_loss_value_kernel, the K products added in k order
+// One workgroup per utterance; per path the fixed-order reduction of block_path_logprob_sum, the K products added in k order
 // (deterministic).
 __global__ __launch_bounds__(256) void pg_loss_value_multi_kernel(const float* __restrict__ lp, const int32_t* __restrict__ paths, int K,
                                                                   const int32_t* __restrict__ in_len, const float* __restrict__ nll,
@@ -236,20 +236,8 @@ __global__ __launch_bounds__(256) void pg_loss_value_multi_kernel(const float* _
     const int b = blockIdx.x;
     const int Tb = min(in_len[b], T);
     float acc = 0.f;
-    for (int k = 0; k < K; ++k) {
-        const int32_t* path = paths + (size_t)k * T * B;
-        float s = 0.f;
-        for (int t = threadIdx.x; t < Tb; t += 256)
-            s += lp[((size_t)t * B + b) * V + path[(size_t)t * B + b]];
-        red[threadIdx.x] = s;
-        __syncthreads();
-        for (int o = 128; o > 0; o >>= 1) {
-            if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-            __syncthreads();
-        }
-        acc += coef[(size_t)k * B + b] * red[0];
-        __syncthreads();          // red[0] read by every thread before the next path overwrites it
-    }
+    for (int k = 0; k < K; ++k)
+        acc += coef[(size_t)k * B + b] * block_path_logprob_sum(lp, paths + (size_t)k * T * B, nullptr, Tb, b, B, V, red);
     if (threadIdx.x == 0) terms[b] = nll[b] * utt_scale[b] - acc;
 }
 
@@ -263,20 +251,9 @@ __global__ __launch_bounds__(256) void pg_loss_value_kernel(const float* __restr
     __shared__ float red[256];
     const int b = blockIdx.x;
     const int Tb = min(in_len[b], T);
-    float s = 0.f;
-    if (path && coef)
-        for (int t = threadIdx.x; t < Tb; t += 256) {
-            const int k = path[(size_t)t * B + b];
-            const float v = lp[((size_t)t * B + b) * V + k];
-            s += coef_per_frame ? coef[(size_t)t * B + b] * v : v;
-        }
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) terms[b] = nll[b] * utt_scale[b] - (coef ? (coef_per_frame ? red[0] : coef[b] * red[0]) : 0.f);
+    // per-frame coefficients weigh the terms inside the sum, a per-utterance one the sum
+    const float s = (path && coef) ? block_path_logprob_sum(lp, path, coef_per_frame ? coef : nullptr, Tb, b, B, V, red) : 0.f;
+    if (threadIdx.x == 0) terms[b] = nll[b] * utt_scale[b] - (coef ? (coef_per_frame ? s : coef[b] * s) : 0.f);
 }
 
 // Per-frame REINFORCE coefficients from the per-step rewards of policy_grad.py:10-15 (reward_mode "per_step").

@@ -98,7 +98,7 @@ class _timed:
         self.name = name
 
     def __enter__(self):
-        self.on = _prof_on and (_prof_only is None or self.name.startswith(_prof_only))
+        self.on = _prof_on and self.name is not None and (_prof_only is None or self.name.startswith(_prof_only))
         if self.on:
             self.e0 = torch.cuda.Event(enable_timing=True); self.e1 = torch.cuda.Event(enable_timing=True)
             self.e0.record()
@@ -122,10 +122,8 @@ def _workspace(nbytes, device, tag):
     return buf
 
 
-def ctc_loss_grad(log_probs, targets, input_lengths, target_lengths, blank=0, utt_scale=None,
-                  pg_coef=None, pg_path=None, need_grad=True):
-    """log_probs (T,B,V) fp32; targets (B,Lmax) int32; lengths int32.
-    Returns (nll (B,), grad_logits (T,B,V) or None)."""
+def _ctc_call(log_probs, targets, input_lengths, target_lengths, blank, utt_scale=None, pg_coef=None, pg_path=None, need_grad=False):
+    """``pgasr_ctc_loss_grad`` for ``ctc_loss_grad`` and ``ctc_lattice``: (nll, grad or None, lattice handle)."""
     lib = _lib.load()
     _req(log_probs, torch.float32, "log_probs")
     T, B, V = log_probs.shape
@@ -144,27 +142,21 @@ def ctc_loss_grad(log_probs, targets, input_lengths, target_lengths, blank=0, ut
                                  T, B, V, Lmax, blank, _p(utt_scale), _p(pg_coef), _p(pg_path),
                                  _p(nll), _p(grad), _p(ws), ws.numel(), _stream())
     _lib.check(st, "pgasr_ctc_loss_grad")
-    return nll, grad
+    return nll, grad, (ws, Lmax, blank)
+
+
+def ctc_loss_grad(log_probs, targets, input_lengths, target_lengths, blank=0, utt_scale=None,
+                  pg_coef=None, pg_path=None, need_grad=True):
+    """log_probs (T,B,V) fp32; targets (B,Lmax) int32; lengths int32.
+    Returns (nll (B,), grad_logits (T,B,V) or None)."""
+    return _ctc_call(log_probs, targets, input_lengths, target_lengths, blank, utt_scale, pg_coef, pg_path, need_grad)[:2]
 
 
 def ctc_lattice(log_probs, targets, input_lengths, target_lengths, blank=0):
     """First half of ``ctc_loss_grad``: alpha/beta lattice only.  Returns (nll (B,), handle); the handle goes to
     ``ctc_grad_from_lattice`` (which may run on another stream once this one's work is ordered before it)."""
-    lib = _lib.load()
-    _req(log_probs, torch.float32, "log_probs")
-    T, B, V = log_probs.shape
-    _req(targets, torch.int32, "targets"); _req(input_lengths, torch.int32, "input_lengths")
-    _req(target_lengths, torch.int32, "target_lengths")
-    Lmax = targets.shape[1] if targets.dim() == 2 else 0
-    if Lmax == 0:
-        targets = torch.zeros(B, 1, dtype=torch.int32, device=log_probs.device)
-    nbytes = lib.pgasr_ctc_workspace_bytes(T, B, V, Lmax)
-    ws = _workspace(nbytes, log_probs.device, "ctc")
-    nll = torch.empty(B, dtype=torch.float32, device=log_probs.device)
-    st = lib.pgasr_ctc_loss_grad(_p(log_probs), _p(targets), _p(input_lengths), _p(target_lengths),
-                                 T, B, V, Lmax, blank, None, None, None, _p(nll), None, _p(ws), ws.numel(), _stream())
-    _lib.check(st, "pgasr_ctc_loss_grad")
-    return nll, (ws, Lmax, blank)
+    nll, _, handle = _ctc_call(log_probs, targets, input_lengths, target_lengths, blank)
+    return nll, handle
 
 
 def _coef_per_frame(pg_coef, T, B):
@@ -176,17 +168,41 @@ def _coef_per_frame(pg_coef, T, B):
     return 1
 
 
-def ctc_grad_from_lattice(log_probs, input_lengths, target_lengths, handle, utt_scale=None, pg_coef=None, pg_path=None):
+def _grad_pass(entry, log_probs, input_lengths, target_lengths, handle, utt_scale, pg_coef, paths, paths_name, mid, ws_tail=(),
+               label=None):
+    """The three ``ctc_grad_from_lattice*`` wrappers: entry(log-probs, lengths, shapes, blank, utt_scale, *mid, grad, workspace,
+    *ws_tail, stream) into a fresh (T,B,V) gradient.  mid: what the entry point takes between utt_scale and grad_logits, tensors
+    as tensors; label: the launch's ``_timed`` name."""
     lib = _lib.load()
     ws, Lmax, blank = handle
     T, B, V = log_probs.shape
-    _req(utt_scale, torch.float32, "utt_scale"); _req(pg_coef, torch.float32, "pg_coef"); _req(pg_path, torch.int32, "pg_path")
+    _req(utt_scale, torch.float32, "utt_scale"); _req(pg_coef, torch.float32, "pg_coef"); _req(paths, torch.int32, paths_name)
     grad = torch.empty_like(log_probs)
-    st = lib.pgasr_ctc_grad_from_lattice(_p(log_probs), _p(input_lengths), _p(target_lengths), T, B, V, Lmax, blank,
-                                         _p(utt_scale), _p(pg_coef), _p(pg_path), _coef_per_frame(pg_coef, T, B), _p(grad), _p(ws),
-                                         ws.numel(), _stream())
-    _lib.check(st, "pgasr_ctc_grad_from_lattice")
+    with _timed(label):
+        st = getattr(lib, entry)(_p(log_probs), _p(input_lengths), _p(target_lengths), T, B, V, Lmax, blank, _p(utt_scale),
+                                 *(a if isinstance(a, int) else _p(a) for a in mid), _p(grad), _p(ws), ws.numel(), *ws_tail, _stream())
+    _lib.check(st, entry)
     return grad
+
+
+def _loss_value(entry, log_probs, paths, paths_name, input_lengths, nll, utt_scale, pg_coef, K=(), mid=(), tail=()):
+    """The three ``pg_loss_value*`` wrappers: entry(log_probs, paths, *K, input_lengths, nll, utt_scale, pg_coef, *mid, T, B, V,
+    *tail, terms, stream) -> terms (B,) fp32."""
+    lib = _lib.load()
+    T, B, V = log_probs.shape
+    _req(log_probs, torch.float32, "log_probs"); _req(paths, torch.int32, paths_name); _req(nll, torch.float32, "nll")
+    _req(utt_scale, torch.float32, "utt_scale"); _req(pg_coef, torch.float32, "pg_coef")
+    terms = torch.empty(B, dtype=torch.float32, device=log_probs.device)
+    st = getattr(lib, entry)(_p(log_probs), _p(paths), *K, _p(input_lengths), _p(nll), _p(utt_scale), _p(pg_coef), *mid,
+                             T, B, V, *tail, _p(terms), _stream())
+    _lib.check(st, entry)
+    return terms
+
+
+def ctc_grad_from_lattice(log_probs, input_lengths, target_lengths, handle, utt_scale=None, pg_coef=None, pg_path=None):
+    T, B, _ = log_probs.shape
+    return _grad_pass("pgasr_ctc_grad_from_lattice", log_probs, input_lengths, target_lengths, handle, utt_scale, pg_coef, pg_path,
+                      "pg_path", (pg_coef, pg_path, _coef_per_frame(pg_coef, T, B)))
 
 
 def pg_rewards(dist, target_lengths, lam, inv_global_batch):
@@ -205,15 +221,9 @@ def pg_rewards(dist, target_lengths, lam, inv_global_batch):
 
 def pg_loss_value(log_probs, path, input_lengths, nll, utt_scale, pg_coef):
     """Per-utterance value of the objective (see include/pgasr_hip.h); sum() it for the loss."""
-    lib = _lib.load()
-    T, B, V = log_probs.shape
-    _req(log_probs, torch.float32, "log_probs"); _req(path, torch.int32, "path"); _req(nll, torch.float32, "nll")
-    _req(utt_scale, torch.float32, "utt_scale"); _req(pg_coef, torch.float32, "pg_coef")
-    terms = torch.empty(B, dtype=torch.float32, device=log_probs.device)
-    st = lib.pgasr_pg_loss_value(_p(log_probs), _p(path), _p(input_lengths), _p(nll), _p(utt_scale), _p(pg_coef),
-                                 T, B, V, _coef_per_frame(pg_coef, T, B), _p(terms), _stream())
-    _lib.check(st, "pgasr_pg_loss_value")
-    return terms
+    T, B, _ = log_probs.shape
+    return _loss_value("pgasr_pg_loss_value", log_probs, path, "path", input_lengths, nll, utt_scale, pg_coef,
+                       tail=(_coef_per_frame(pg_coef, T, B),))
 
 
 # ---- multi-sample REINFORCE (include/pgasr_hip.h: K sampled paths per utterance, hypothesis or leave-one-out baseline) ----
@@ -224,18 +234,12 @@ BASELINES = {"hypothesis": 0, "leave_one_out": 1}
 def ctc_grad_from_lattice_multi(log_probs, input_lengths, target_lengths, handle, utt_scale, pg_coef, pg_paths):
     """``ctc_grad_from_lattice`` with K sampled paths: pg_paths (K,T,B) int32, pg_coef (K,B) fp32; the K REINFORCE terms are
     added in k order after the CTC part, in the same pass."""
-    lib = _lib.load()
-    ws, Lmax, blank = handle
-    T, B, V = log_probs.shape
-    _req(utt_scale, torch.float32, "utt_scale"); _req(pg_coef, torch.float32, "pg_coef"); _req(pg_paths, torch.int32, "pg_paths")
+    T, B, _ = log_probs.shape
     K = pg_paths.shape[0]
     if pg_paths.dim() != 3 or tuple(pg_paths.shape[1:]) != (T, B) or tuple(pg_coef.shape) != (K, B):
         raise _lib.PgasrError(f"ctc_grad_from_lattice_multi wants pg_paths (K,{T},{B}) and pg_coef (K,{B})")
-    grad = torch.empty_like(log_probs)
-    st = lib.pgasr_ctc_grad_from_lattice_multi(_p(log_probs), _p(input_lengths), _p(target_lengths), T, B, V, Lmax, blank,
-                                               _p(utt_scale), K, _p(pg_coef), _p(pg_paths), _p(grad), _p(ws), ws.numel(), _stream())
-    _lib.check(st, "pgasr_ctc_grad_from_lattice_multi")
-    return grad
+    return _grad_pass("pgasr_ctc_grad_from_lattice_multi", log_probs, input_lengths, target_lengths, handle, utt_scale, pg_coef,
+                      pg_paths, "pg_paths", (K, pg_coef, pg_paths))
 
 
 def pg_rewards_multi(dist, target_lengths, num_samples, lam, inv_global_batch, baseline="hypothesis", reward_lengths=None):
@@ -270,18 +274,11 @@ def pg_rewards_multi(dist, target_lengths, num_samples, lam, inv_global_batch, b
 
 def pg_loss_value_multi(log_probs, paths, input_lengths, nll, utt_scale, pg_coef):
     """Per-utterance value of the multi-sample objective, paths (K,T,B), pg_coef (K,B); sum() it for the loss."""
-    lib = _lib.load()
-    T, B, V = log_probs.shape
-    _req(log_probs, torch.float32, "log_probs"); _req(paths, torch.int32, "paths"); _req(nll, torch.float32, "nll")
-    _req(utt_scale, torch.float32, "utt_scale"); _req(pg_coef, torch.float32, "pg_coef")
+    T, B, _ = log_probs.shape
     K = paths.shape[0]
     if paths.dim() != 3 or tuple(paths.shape[1:]) != (T, B) or tuple(pg_coef.shape) != (K, B):
         raise _lib.PgasrError(f"pg_loss_value_multi wants paths (K,{T},{B}) and pg_coef (K,{B})")
-    terms = torch.empty(B, dtype=torch.float32, device=log_probs.device)
-    st = lib.pgasr_pg_loss_value_multi(_p(log_probs), _p(paths), K, _p(input_lengths), _p(nll), _p(utt_scale), _p(pg_coef),
-                                       T, B, V, _p(terms), _stream())
-    _lib.check(st, "pgasr_pg_loss_value_multi")
-    return terms
+    return _loss_value("pgasr_pg_loss_value_multi", log_probs, paths, "paths", input_lengths, nll, utt_scale, pg_coef, K=(K,))
 
 
 # ---- sequence-level REINFORCE (include/pgasr_hip.h: the score function of a sample is the CTC likelihood of its hypothesis) ----
@@ -325,39 +322,26 @@ def ctc_grad_from_lattices_seq(log_probs, input_lengths, target_lengths, handle,
     """One gradient pass over the target lattice (``ctc_lattice``'s handle) and the K*B hypothesis lattices (``ctc_hyp_lattice``'s):
     utt_scale (softmax - occ_target) + sum_k pg_coef[k,b] * (hyp_len[k,b] <= Lh ? softmax - occ_hyp : softmax - onehot(pg_paths[k,t,b])),
     the K terms in k order.  pg_paths (K,T,B) int32, pg_coef (K,B) fp32, hyp_len (K,B) int32."""
-    lib = _lib.load()
-    ws, Lmax, blank = handle
     hws, K, Lh = hyp_handle
-    T, B, V = log_probs.shape
-    _req(utt_scale, torch.float32, "utt_scale"); _req(pg_coef, torch.float32, "pg_coef"); _req(pg_paths, torch.int32, "pg_paths")
+    T, B, _ = log_probs.shape
     _req(hyp_len, torch.int32, "hyp_len")
     if tuple(pg_paths.shape) != (K, T, B) or tuple(pg_coef.shape) != (K, B) or tuple(hyp_len.shape) != (K, B):
         raise _lib.PgasrError(f"ctc_grad_from_lattices_seq wants pg_paths ({K},{T},{B}), pg_coef and hyp_len ({K},{B})")
-    grad = torch.empty_like(log_probs)
-    with _timed("ctc_grad_seq_kernel"):
-        st = lib.pgasr_ctc_grad_from_lattices_seq(_p(log_probs), _p(input_lengths), _p(target_lengths), T, B, V, Lmax, blank,
-                                                  _p(utt_scale), K, _p(pg_coef), _p(pg_paths), _p(hyp_len), Lh, _p(grad),
-                                                  _p(ws), ws.numel(), _p(hws), hws.numel(), _stream())
-    _lib.check(st, "pgasr_ctc_grad_from_lattices_seq")
-    return grad
+    return _grad_pass("pgasr_ctc_grad_from_lattices_seq", log_probs, input_lengths, target_lengths, handle, utt_scale, pg_coef,
+                      pg_paths, "pg_paths", (K, pg_coef, pg_paths, hyp_len, Lh), ws_tail=(_p(hws), hws.numel()),
+                      label="ctc_grad_seq_kernel")
 
 
 def pg_loss_value_seq(log_probs, paths, input_lengths, nll, utt_scale, pg_coef, hyp_nll, hyp_len, Lh):
     """Per-utterance value of the sequence-level objective: nll_b utt_scale_b + sum_k pg_coef[k,b] * (hyp_len[k,b] <= Lh ?
     hyp_nll[k,b] : -sum_t log p(paths[k,t,b])); sum() it for the loss."""
-    lib = _lib.load()
-    T, B, V = log_probs.shape
-    _req(log_probs, torch.float32, "log_probs"); _req(paths, torch.int32, "paths"); _req(nll, torch.float32, "nll")
-    _req(utt_scale, torch.float32, "utt_scale"); _req(pg_coef, torch.float32, "pg_coef")
+    T, B, _ = log_probs.shape
     _req(hyp_nll, torch.float32, "hyp_nll"); _req(hyp_len, torch.int32, "hyp_len")
     K = paths.shape[0]
     if paths.dim() != 3 or tuple(paths.shape[1:]) != (T, B) or any(tuple(t_.shape) != (K, B) for t_ in (pg_coef, hyp_nll, hyp_len)):
         raise _lib.PgasrError(f"pg_loss_value_seq wants paths (K,{T},{B}) and pg_coef, hyp_nll, hyp_len (K,{B})")
-    terms = torch.empty(B, dtype=torch.float32, device=log_probs.device)
-    st = lib.pgasr_pg_loss_value_seq(_p(log_probs), _p(paths), K, _p(input_lengths), _p(nll), _p(utt_scale), _p(pg_coef),
-                                     _p(hyp_nll), _p(hyp_len), int(Lh), T, B, V, _p(terms), _stream())
-    _lib.check(st, "pgasr_pg_loss_value_seq")
-    return terms
+    return _loss_value("pgasr_pg_loss_value_seq", log_probs, paths, "paths", input_lengths, nll, utt_scale, pg_coef, K=(K,),
+                       mid=(_p(hyp_nll), _p(hyp_len), int(Lh)))
 
 
 FUSED_HEAD = _os_environ_get("PGASR_FUSED_HEAD", "1") != "0"

@@ -5,6 +5,9 @@ including its quirk that a falsy ignore_index (None or 0) ignores nothing.  ``PG
 the spec'd objective the reference lacks: CTC + lambda * REINFORCE with a
 self-critical (greedy) baseline, computed by the HIP kernels in one fused gradient pass.
 """
+import dataclasses
+import numbers
+
 import torch
 import torch.nn as nn
 
@@ -51,7 +54,7 @@ class PGCTCLossFn(torch.autograd.Function):
       "leave_one_out": (S - R_k) / (K-1) with S = sum_j R_j in j order, fp32 (K >= 2; the greedy argmax and the beam search are skipped).
         loss = sum_b [ nll_b / (Bg max(L_b,1))  -  sum_k lam / (Bg K) (R_k - b_k) sum_{t<T_b} log p(pi_k,t,b) ]
     and d(logits) adds the K REINFORCE terms in k order after the CTC part.  K = 1 with the hypothesis baseline is the objective
-    above, on its own code path.  per_step takes K = 1 only.  The baseline of an utterance uses that utterance's samples alone, so
+    above, on the single-path kernels.  per_step takes K = 1 only.  The baseline of an utterance uses that utterance's samples alone, so
     data-parallel ranks exchange nothing for it.
     ``reward_unit = "word"`` (opt-in): every reward above -- sample, hypothesis and the leave-one-out baselines -- is the word-level
     R = -WED(y, yhat) / W(y), words being the runs between ``word_delimiter`` tokens exactly as str.split(" ") cuts the decoded string
@@ -73,7 +76,7 @@ class PGCTCLossFn(torch.autograd.Function):
     the path-level term: the choice depends on y alone, so the mixture is still unbiased and a long sample never fails; a hypothesis
     nll of +inf contributes nothing, as for targets.  The hypothesis lattices take 2 * K*B*T * roundup64(2*Lh+1) * 4 bytes of cached
     workspace (B = 32, T = 1000, K = 4: 2.1 GB at Lh = 1000, 0.46 GB with max_hyp_len = 200; hipops.ctc_hyp_workspace_bytes).  Always
-    the multi-sample section (K = 1 included); not with per_step (frame-aligned coefficients have no sequence form).
+    the multi-sample kernels (K = 1 included); not with per_step (frame-aligned coefficients have no sequence form).
     ``PGCTCLossFn.last_sequence_scored``: (K,B) bool on the device, which samples of the last call took the sequence term (None after
     a "path" call).
     Returns (loss, stats) where stats = (nll (B), R_s (B), R_g (B)) detached; with K > 1, (nll (B), R_s (K,B), R_b (B)) where
@@ -88,138 +91,100 @@ class PGCTCLossFn(torch.autograd.Function):
     unit_hits = 0              # how often the shortcut was taken (tests)
     last_sequence_scored = None    # (K,B) bool: the samples of the last score_function="sequence" call that were sequence-scored
     @staticmethod
-    def forward(ctx, logits, in_len, targets, tg_len, lam, seed, offset, global_batch, blank, beam=0, sample_base=-1, per_step=False,
-                log_probs=None, num_samples=1, baseline="hypothesis", reward_unit="char", word_delimiter=None, sample_ids=None,
-                score_function="path", max_hyp_len=None):
+    def forward(ctx, logits, in_len, targets, tg_len, log_probs, sample_ids, opt):
+        """opt: the ``PGOptions`` of the call, checked by ``pg_ctc_loss``."""
         T, B, V = logits.shape
-        _check_score(score_function, max_hyp_len, per_step)
         PGCTCLossFn.last_sequence_scored = None
-        if sample_ids is not None and sample_base >= 0:
-            raise ValueError("sample_ids and sample_base >= 0 are two addressings of the same draws: give one")
-        if per_step and beam > 0:
-            raise ValueError("per-step rewards need the frame-aligned greedy baseline (beam = 0)")
-        _check_samples(num_samples, baseline, per_step)
-        _check_unit(reward_unit, word_delimiter, per_step, blank=blank, vocab=V)
-        word = reward_unit == "word"
-        if word and max(T, targets.shape[1] if targets.dim() == 2 else 0) > hipops.WORD_MAX_STRIDE:
-            raise ValueError(f"the word-level reward takes at most {hipops.WORD_MAX_STRIDE} frames and target symbols per utterance "
-                             f"(pgasr_word_ids); got T = {T}")
-        num_samples = int(num_samples)
+        K, beam, blank = opt.num_samples, opt.beam, opt.blank
+        loo = opt.baseline == "leave_one_out"
+        wd = opt.word_delimiter if opt.reward_unit == "word" else None
+        Lh = hipops.hyp_len_cap(T, opt.max_hyp_len) if opt.score_function == "sequence" else None     # the hypothesis-length cap
+        # Kernel family: the single-path kernels (per_step's (T,B) coefficients included) for the one configuration they were
+        # written for, the multi-sample kernels -- K = 1 included -- for every other, their _seq pair when Lh is set.
+        single = K == 1 and not loo and Lh is None
+        greedy_row = not loo and beam == 0      # the greedy path is sampled along and collapsed as row 0
+        P = K + (0 if loo else 1)               # path sets that are collapsed and scored: [hypothesis,] sample 0 .. K-1
+        inv_gb = 1.0 / float(opt.global_batch)
         dev = logits.device
         # log-probs the head kernel already produced for exactly this tensor (model.Seq2Seq.logits), else one pass over the logits
         lp = log_probs
         if lp is None or lp.shape != logits.shape or not lp.is_contiguous():
             lp = hipops.log_softmax_rows(logits.contiguous())
         # The alpha/beta lattice (96 workgroups, a serial chain of T frames, ~0.27 ms at T=1000) is the long pole of this
-        # section and stays on the CALLING stream; sampling, collapse, (beam search,) edit distance and the reward
-        # arithmetic (~0.13 ms with the greedy baseline) run beside it on a side stream and are joined before the gradient
-        # pass.  (Round 1 had it the other way round: two cross-stream hops then sat on the critical chain.)
+        # section and stays on the CALLING stream; sampling, collapse, (beam search,) (the K*B hypothesis lattices,) edit
+        # distance and the reward arithmetic (~0.13 ms with the greedy baseline) run beside it on a side stream -- no third
+        # stream -- and are joined before the gradient pass.  (Round 1 had it the other way round: two cross-stream hops then
+        # sat on the critical chain.)
         main = torch.cuda.current_stream()
         side = PGCTCLossFn._lattice_streams.setdefault(main.cuda_stream, None) or streams.side_stream("loss_section")
         PGCTCLossFn._lattice_streams[main.cuda_stream] = side
         # sample_base >= 0: this shard's first utterance in the GLOBAL batch -- the draws are then addressed globally
         # sample_ids: the global index of every row instead (micro-batches of an accumulated step, shards that are not contiguous)
         if sample_ids is not None:
-            lay = {"batch_stride": int(global_batch), "utt_ids": sample_ids}
+            lay = {"batch_stride": opt.global_batch, "utt_ids": sample_ids}
         else:
-            lay = {"batch_stride": int(global_batch), "batch_offset": int(sample_base)} if sample_base >= 0 else {}
-        wd = word_delimiter if word else None
-        if num_samples != 1 or baseline != "hypothesis" or score_function == "sequence":
-            return PGCTCLossFn._forward_multi(ctx, lp, in_len, targets, tg_len, lam, seed, offset, global_batch, blank, beam, lay,
-                                              main, side, num_samples, baseline, wd,
-                                              hipops.hyp_len_cap(T, max_hyp_len) if score_function == "sequence" else None)
+            lay = {"batch_stride": opt.global_batch, "batch_offset": opt.sample_base} if opt.sample_base >= 0 else {}
         side.wait_stream(main)
         with torch.cuda.stream(side):
-            if beam > 0:
-                # baseline hypothesis = prefix beam search + collapse_fn (policy_grad.py:6-8), rows [0] of the pair buffers
-                _, sample = hipops.frame_argmax_sample(lp, seed=seed, offset=offset, want_greedy=False, **lay)
-                tokens = torch.zeros(2, B, T, dtype=torch.int32, device=dev)
-                tok_len = torch.empty(2, B, dtype=torch.int32, device=dev)
-                hipops.ctc_beam_search(lp, in_len, beam=beam, blank=blank, collapse=True, out=(tokens[0], tok_len[0]))
-                hipops.ctc_collapse(sample[None], in_len, blank=blank, out=(tokens[1:], tok_len[1:]))
+            # samples (K,T,B); paths = what one collapse takes: [greedy,] samples
+            if single:
+                greedy, sample = hipops.frame_argmax_sample(lp, seed=opt.seed, offset=opt.offset, want_greedy=greedy_row, **lay)
+                samples = sample[None]
+                paths = torch.stack((greedy, sample), dim=0) if greedy_row else samples
+            elif greedy_row:
+                paths = torch.empty(P, T, B, dtype=torch.int32, device=dev)
+                hipops.frame_sample_multi(lp, K, seed=opt.seed, offset=opt.offset, out=(paths[0], paths[1:]), **lay)
+                samples = paths[1:]
             else:
-                greedy, sample = hipops.frame_argmax_sample(lp, seed=seed, offset=offset, **lay)
-                paths = torch.stack((greedy, sample), dim=0)                          # (2,T,B)
-                tokens, tok_len = hipops.ctc_collapse(paths, in_len, blank=blank)     # (2,B,T), (2,B)
-            if per_step:
-                dist, prefix = hipops.edit_distance(targets.repeat(2, 1), tg_len.repeat(2), tokens.view(2 * B, T), tok_len.view(2 * B),
-                                                    want_prefix=True)
-            elif wd is not None:
-                # word-level reward: R = -WED / W(y), the CTC term's utt_scale stays on the character counts
-                dist, n_words = _word_distances(targets, tg_len, tokens, tok_len, 2, wd)
-                R_g, R_s, coef, utt_scale = hipops.pg_rewards_multi(dist, tg_len, 1, lam, 1.0 / float(global_batch),
-                                                                    reward_lengths=n_words)
-                R_s, coef = R_s[0], coef[0]
-            else:
-                dist = hipops.edit_distance(targets.repeat(2, 1), tg_len.repeat(2), tokens.view(2 * B, T), tok_len.view(2 * B))
-            if wd is None:
-                R_g, R_s, coef, utt_scale = hipops.pg_rewards(dist, tg_len, lam, 1.0 / float(global_batch))
-            if per_step:
-                coef = hipops.pg_step_coefs(paths, in_len, prefix, tok_len.view(2 * B), tg_len, lam, 1.0 / float(global_batch), blank=blank)
-        nll, lattice = hipops.ctc_lattice(lp, targets, in_len, tg_len, blank=blank)
-        main.wait_stream(side)
-        for t_ in (sample, R_g, R_s, coef, utt_scale):
-            streams.hold(t_, main)
-        grad = hipops.ctc_grad_from_lattice(lp, in_len, tg_len, lattice, utt_scale=utt_scale, pg_coef=coef, pg_path=sample)
-        loss = hipops.pg_loss_value(lp, sample, in_len, nll, utt_scale, coef).sum()
-        ctx.save_for_backward(grad)
-        ctx.mark_non_differentiable(nll, R_s, R_g)
-        ctx.set_materialize_grads(False)        # no zero-filled gradients for the three statistics
-        return loss, nll, R_s, R_g
-
-    @staticmethod
-    def _forward_multi(ctx, lp, in_len, targets, tg_len, lam, seed, offset, global_batch, blank, beam, lay, main, side, K, baseline,
-                       word_delimiter=None, Lh=None):
-        """K sampled paths per utterance: the single-sample section's stream structure with the multi-sample kernels.
-        Lh (score_function="sequence"): the hypothesis-length cap; the K*B hypothesis lattices follow the collapse on the side stream
-        (no third stream) and the gradient pass runs over K+1 lattices."""
-        T, B, V = lp.shape
-        dev = lp.device
-        loo = baseline == "leave_one_out"
-        P = K + (0 if loo else 1)          # path sets that are collapsed and scored: [hypothesis,] sample 0 .. K-1
-        side.wait_stream(main)
-        with torch.cuda.stream(side):
-            if loo:
-                # the baseline comes from the other samples: no greedy argmax, no beam search
-                _, samples = hipops.frame_sample_multi(lp, K, seed=seed, offset=offset, **lay)
-                tokens, tok_len = hipops.ctc_collapse(samples, in_len, blank=blank)
-            elif beam > 0:
-                _, samples = hipops.frame_sample_multi(lp, K, seed=seed, offset=offset, **lay)
+                # leave-one-out: the baseline comes from the other samples, no greedy argmax and no beam search
+                _, samples = hipops.frame_sample_multi(lp, K, seed=opt.seed, offset=opt.offset, **lay)
+                paths = samples
+            if beam > 0 and not loo:
+                # baseline hypothesis = prefix beam search + collapse_fn (policy_grad.py:6-8), row 0 of the token buffers
                 tokens = torch.zeros(P, B, T, dtype=torch.int32, device=dev)
                 tok_len = torch.empty(P, B, dtype=torch.int32, device=dev)
                 hipops.ctc_beam_search(lp, in_len, beam=beam, blank=blank, collapse=True, out=(tokens[0], tok_len[0]))
                 hipops.ctc_collapse(samples, in_len, blank=blank, out=(tokens[1:], tok_len[1:]))
             else:
-                paths = torch.empty(P, T, B, dtype=torch.int32, device=dev)          # greedy path, then the K samples
-                hipops.frame_sample_multi(lp, K, seed=seed, offset=offset, out=(paths[0], paths[1:]), **lay)
-                samples = paths[1:]
-                tokens, tok_len = hipops.ctc_collapse(paths, in_len, blank=blank)
+                tokens, tok_len = hipops.ctc_collapse(paths, in_len, blank=blank)     # (P,B,T), (P,B)
             if Lh is not None:
                 hyp_len = tok_len[P - K:]                     # the K samples' rows (row 0 may be the baseline hypothesis)
                 hyp_nll, hyp_lattice = hipops.ctc_hyp_lattice(lp, tokens[P - K:], hyp_len, in_len, Lh, blank=blank)
                 PGCTCLossFn.last_sequence_scored = scored = hyp_len <= Lh
-            if word_delimiter is None:
-                dist = hipops.edit_distance(targets.repeat(P, 1), tg_len.repeat(P), tokens.view(P * B, T), tok_len.view(P * B))
-                n_words = None
+            n_words = prefix = None
+            if wd is not None:
+                # word-level reward: R = -WED / W(y), the CTC term's utt_scale stays on the character counts
+                dist, n_words = _word_distances(targets, tg_len, tokens, tok_len, P, wd)
             else:
-                dist, n_words = _word_distances(targets, tg_len, tokens, tok_len, P, word_delimiter)
-            R_b, R_s, coef, utt_scale = hipops.pg_rewards_multi(dist, tg_len, K, lam, 1.0 / float(global_batch), baseline=baseline,
-                                                                reward_lengths=n_words)
+                dist = hipops.edit_distance(targets.repeat(P, 1), tg_len.repeat(P), tokens.view(P * B, T), tok_len.view(P * B),
+                                            want_prefix=opt.per_step)
+                if opt.per_step:
+                    dist, prefix = dist
+            if single and wd is None:
+                R_b, R_s, coef, utt_scale = hipops.pg_rewards(dist, tg_len, opt.lam, inv_gb)
+            else:
+                R_b, R_s, coef, utt_scale = hipops.pg_rewards_multi(dist, tg_len, K, opt.lam, inv_gb, baseline=opt.baseline,
+                                                                    reward_lengths=n_words)
+                if single:
+                    R_s, coef = R_s[0], coef[0]
+            if opt.per_step:
+                coef = hipops.pg_step_coefs(paths, in_len, prefix, tok_len.view(2 * B), tg_len, opt.lam, inv_gb, blank=blank)
         nll, lattice = hipops.ctc_lattice(lp, targets, in_len, tg_len, blank=blank)
         main.wait_stream(side)
-        for t_ in (samples, R_b, R_s, coef, utt_scale):
+        for t_ in (samples, R_b, R_s, coef, utt_scale) + ((tok_len, hyp_nll, scored) if Lh is not None else ()):
             streams.hold(t_, main)
-        if Lh is not None:
-            for t_ in (tok_len, hyp_nll, scored):
-                streams.hold(t_, main)
-            grad = hipops.ctc_grad_from_lattices_seq(lp, in_len, tg_len, lattice, hyp_lattice, utt_scale, coef, samples, hyp_len)
-            loss = hipops.pg_loss_value_seq(lp, samples, in_len, nll, utt_scale, coef, hyp_nll, hyp_len, Lh).sum()
-        else:
+        if single:
+            grad = hipops.ctc_grad_from_lattice(lp, in_len, tg_len, lattice, utt_scale=utt_scale, pg_coef=coef, pg_path=sample)
+            loss = hipops.pg_loss_value(lp, sample, in_len, nll, utt_scale, coef).sum()
+        elif Lh is None:
             grad = hipops.ctc_grad_from_lattice_multi(lp, in_len, tg_len, lattice, utt_scale, coef, samples)
             loss = hipops.pg_loss_value_multi(lp, samples, in_len, nll, utt_scale, coef).sum()
+        else:
+            grad = hipops.ctc_grad_from_lattices_seq(lp, in_len, tg_len, lattice, hyp_lattice, utt_scale, coef, samples, hyp_len)
+            loss = hipops.pg_loss_value_seq(lp, samples, in_len, nll, utt_scale, coef, hyp_nll, hyp_len, Lh).sum()
         ctx.save_for_backward(grad)
         ctx.mark_non_differentiable(nll, R_s, R_b)
-        ctx.set_materialize_grads(False)
+        ctx.set_materialize_grads(False)        # no zero-filled gradients for the three statistics
         return loss, nll, R_s, R_b
 
     @staticmethod
@@ -227,8 +192,9 @@ class PGCTCLossFn(torch.autograd.Function):
         (grad,) = ctx.saved_tensors
         if PGCTCLossFn.unit_seed_ptr is not None and g.data_ptr() == PGCTCLossFn.unit_seed_ptr and g.numel() == 1:
             PGCTCLossFn.unit_hits += 1
-            return (grad,) + (None,) * 19
-        return (grad * g,) + (None,) * 19
+        else:
+            grad = grad * g
+        return (grad,) + (None,) * (len(ctx.needs_input_grad) - 1)      # the logits' gradient; no other input has one
 
 
 REWARD_UNITS = ("char", "word")
@@ -242,8 +208,44 @@ def _word_distances(targets, tg_len, tokens, tok_len, P, delimiter):
     return dist, ref_words[:B]
 
 
+@dataclasses.dataclass(frozen=True)
+class PGOptions:
+    """Everything of a ``pg_ctc_loss`` call that is not a tensor: ONE input of ``PGCTCLossFn`` beside the tensors."""
+    lam: float = 1.0
+    seed: int = 0
+    offset: int = 0
+    global_batch: int = 1
+    blank: int = 0
+    beam: int = 0
+    sample_base: int = -1
+    per_step: bool = False
+    num_samples: int = 1
+    baseline: str = "hypothesis"
+    reward_unit: str = "char"
+    word_delimiter: object = None
+    score_function: str = "path"
+    max_hyp_len: object = None
+
+
+def check_options(opt, vocab=None, frames=None, symbols=None, sample_ids=None):
+    """The one check of a ``PGOptions`` -- by ``pg_ctc_loss`` per call, by ``PolicyGradientTrainer`` at construction and before
+    every step --, made before any kernel runs and where the caller can read the reason.  vocab, frames (T) and symbols (the
+    targets' row length) are checked against where they are known.  Returns the options with their integers as ints."""
+    _check_score(opt.score_function, opt.max_hyp_len, opt.per_step)
+    if sample_ids is not None and opt.sample_base >= 0:
+        raise ValueError("sample_ids and sample_base >= 0 are two addressings of the same draws: give one")
+    if opt.per_step and opt.beam > 0:
+        raise ValueError("per-step rewards need the frame-aligned greedy baseline (beam = 0)")
+    _check_samples(opt.num_samples, opt.baseline, opt.per_step)
+    _check_unit(opt.reward_unit, opt.word_delimiter, opt.per_step, blank=opt.blank, vocab=vocab)
+    if opt.reward_unit == "word" and frames is not None and max(frames, symbols or 0) > hipops.WORD_MAX_STRIDE:
+        raise ValueError(f"the word-level reward takes at most {hipops.WORD_MAX_STRIDE} frames and target symbols per utterance "
+                         f"(pgasr_word_ids); got T = {frames}")
+    return dataclasses.replace(opt, num_samples=int(opt.num_samples),
+                               max_hyp_len=None if opt.max_hyp_len is None else int(opt.max_hyp_len))
+
+
 def _check_unit(reward_unit, word_delimiter, per_step=False, blank=None, vocab=None):
-    """The word-reward arguments of pg_ctc_loss / PolicyGradientTrainer, checked before any kernel runs."""
     if reward_unit not in REWARD_UNITS:
         raise ValueError(f"reward_unit must be one of {REWARD_UNITS} (got {reward_unit!r})")
     if reward_unit != "word":
@@ -261,11 +263,9 @@ def _check_unit(reward_unit, word_delimiter, per_step=False, blank=None, vocab=N
 
 
 def _check_score(score_function, max_hyp_len, per_step=False):
-    """The score-function arguments of pg_ctc_loss / PolicyGradientTrainer, checked before any kernel runs."""
     if score_function not in hipops.SCORE_FUNCTIONS:
         raise ValueError(f"score_function must be one of {hipops.SCORE_FUNCTIONS} (got {score_function!r})")
     if max_hyp_len is not None:
-        import numbers
         if isinstance(max_hyp_len, bool) or not isinstance(max_hyp_len, numbers.Integral) or max_hyp_len < 0:
             raise ValueError(f"max_hyp_len must be None or an integer >= 0 (got {max_hyp_len!r})")
         if score_function != "sequence":
@@ -276,7 +276,6 @@ def _check_score(score_function, max_hyp_len, per_step=False):
 
 
 def _check_samples(num_samples, baseline, per_step=False):
-    """The multi-sample arguments of pg_ctc_loss / PolicyGradientTrainer, checked where the caller can read the reason."""
     if baseline not in hipops.BASELINES:
         raise ValueError(f"baseline must be one of {sorted(hipops.BASELINES)} (got {baseline!r})")
     if isinstance(num_samples, bool) or int(num_samples) != num_samples:
@@ -306,19 +305,18 @@ def pg_ctc_loss(logits, in_len, targets, tg_len, lam=1.0, seed=0, offset=0, glob
     its frame path (see PGCTCLossFn); max_hyp_len caps the hypotheses so scored (None: min(T, 1023)), longer ones keep the path term.
     log_probs: log_softmax(logits) if the caller already has it (the head kernel's by-product, ``logits.log_probs`` of
     Seq2Seq.logits -- picked up from that attribute when not given)."""
-    B = logits.shape[1]
-    if sample_ids is not None and int(sample_base) >= 0:
-        raise ValueError("sample_ids and sample_base >= 0 are two addressings of the same draws: give one")
-    _check_score(score_function, max_hyp_len, per_step)
+    T, B, V = logits.shape
+    opt = check_options(PGOptions(lam=float(lam), seed=int(seed), offset=int(offset), global_batch=int(global_batch or B),
+                                  blank=int(blank), beam=int(beam), sample_base=int(sample_base), per_step=bool(per_step),
+                                  num_samples=num_samples, baseline=baseline, reward_unit=reward_unit, word_delimiter=word_delimiter,
+                                  score_function=score_function, max_hyp_len=max_hyp_len),
+                        vocab=V, frames=T, symbols=targets.shape[1] if targets.dim() == 2 else 0, sample_ids=sample_ids)
     if log_probs is None:
         # the by-product is valid only for the tensor as the head kernel wrote it: any in-place edit since bumps _version
         log_probs = getattr(logits, "log_probs", None)
         if log_probs is not None and getattr(logits, "log_probs_version", None) != logits._version:
             log_probs = None
-    return PGCTCLossFn.apply(logits, in_len, targets, tg_len, float(lam), int(seed), int(offset),
-                             int(global_batch or B), int(blank), int(beam), int(sample_base), bool(per_step), log_probs,
-                             num_samples, baseline, reward_unit, word_delimiter, sample_ids, score_function,
-                             None if max_hyp_len is None else int(max_hyp_len))
+    return PGCTCLossFn.apply(logits, in_len, targets, tg_len, log_probs, sample_ids, opt)
 
 
 class CTCLoss(nn.Module):

@@ -475,12 +475,13 @@ class PolicyGradientTrainer(DataParallelStep):
         if reward_mode == "per_step" and reward_decoder != "greedy":
             raise ValueError("per-step rewards need the frame-aligned greedy baseline (reward_decoder='greedy')")
         self.reward_decoder, self.beam_size, self.reward_mode = reward_decoder, int(beam_size), reward_mode
-        self._check_samples(num_samples, reward_baseline)
-        self.num_samples, self.reward_baseline = int(num_samples), reward_baseline
-        self._check_unit(reward_unit, word_delimiter, blank)
-        self.reward_unit, self.word_delimiter = reward_unit, (None if word_delimiter is None else int(word_delimiter))
-        self._check_score(score_function, max_hyp_len)
-        self.score_function, self.max_hyp_len = score_function, (None if max_hyp_len is None else int(max_hyp_len))
+        self.blank = blank
+        self.num_samples, self.reward_baseline = num_samples, reward_baseline
+        self.reward_unit, self.word_delimiter = reward_unit, word_delimiter
+        self.score_function, self.max_hyp_len = score_function, max_hyp_len
+        opt = self._checked_options()
+        self.num_samples, self.max_hyp_len = opt.num_samples, opt.max_hyp_len
+        self.word_delimiter = None if word_delimiter is None else int(word_delimiter)
         self.last_sequence_scored = None
         self.lam = lam
         # ONE sampling seed for all ranks: a rank addresses its draws by GLOBAL utterance index (contiguous shards: rank *
@@ -490,7 +491,6 @@ class PolicyGradientTrainer(DataParallelStep):
         self.rank = rank
         if hasattr(model, "encoder"):
             model.encoder.dropout_seed = 0x5EED + 104729 * rank
-        self.blank = blank
         self._one = None
         self.last_stats = None
         self.last_sample_rewards = None
@@ -515,23 +515,14 @@ class PolicyGradientTrainer(DataParallelStep):
     MAX_WORD_FRAMES = 4094     # word-level reward: token rows of at most PGASR_WORD_MAX_STRIDE (frames, target symbols)
     MAX_HYP_LEN = 1023         # sequence-level score: hypotheses of at most this many tokens (2L+1 <= 2048 lattice states)
 
-    def _check_score(self, score_function, max_hyp_len):
-        """A known score function; max_hyp_len a non-negative integer and only with "sequence"; "sequence" not with per-step rewards."""
-        from .loss import _check_score
-        _check_score(score_function, max_hyp_len, self.reward_mode == "per_step")
-
-    def _check_unit(self, reward_unit, word_delimiter, blank):
-        """A known reward unit; "word" with a delimiter in [0, V) that is not the blank, and not with per-step rewards."""
-        from .loss import _check_unit
+    def _checked_options(self, frames=None, symbols=None):
+        """This trainer's loss settings as they stand now, through the loss's own check (loss.check_options)."""
+        from .loss import PGOptions, check_options
         vocab = getattr(getattr(self.model, "head", None), "out_features", None)
-        _check_unit(reward_unit, word_delimiter, self.reward_mode == "per_step", blank=blank, vocab=vocab)
-
-    def _check_samples(self, num_samples, reward_baseline):
-        """num_samples in 1 .. MAX_SAMPLES, a known baseline, leave_one_out with >= 2 samples, per_step with one."""
-        from .loss import _check_samples
-        if reward_baseline not in ("hypothesis", "leave_one_out"):
-            raise ValueError("reward_baseline must be 'hypothesis' or 'leave_one_out'")
-        _check_samples(num_samples, reward_baseline, self.reward_mode == "per_step")
+        opt = PGOptions(blank=self.blank, per_step=self.reward_mode == "per_step", num_samples=self.num_samples,
+                        baseline=self.reward_baseline, reward_unit=self.reward_unit, word_delimiter=self.word_delimiter,
+                        score_function=self.score_function, max_hyp_len=self.max_hyp_len)
+        return check_options(opt, vocab=vocab, frames=frames, symbols=symbols)
 
     def _check_limits(self, x, targets):
         """The kernels' compiled-in limits, stated where the caller can read them (otherwise the first symptom is a
@@ -546,12 +537,7 @@ class PolicyGradientTrainer(DataParallelStep):
             raise ValueError(f"alphabet of {vocab} symbols > {self.MAX_VOCAB}: the CTC / sampling kernels hold one frame's scores in one wave")
         if self.reward_decoder == "beam" and self.beam_size > 128:
             raise ValueError("beam_size > 128 is not supported by pgasr_ctc_beam_search")
-        self._check_samples(self.num_samples, self.reward_baseline)
-        self._check_unit(self.reward_unit, self.word_delimiter, self.blank)
-        self._check_score(self.score_function, self.max_hyp_len)
-        if self.reward_unit == "word" and max(x.shape[2], targets.shape[1]) > self.MAX_WORD_FRAMES:
-            raise ValueError(f"T = {x.shape[2]} frames (targets of {targets.shape[1]} symbols): the word-level reward takes token rows of at "
-                             f"most {self.MAX_WORD_FRAMES} (pgasr_word_ids)")
+        self._checked_options(frames=x.shape[2], symbols=targets.shape[1])
 
     def staging_stream(self):
         """The stream on which the NEXT batch is to be staged into HBM once ``step()`` has returned (model.py:227-230's
