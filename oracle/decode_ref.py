@@ -212,6 +212,37 @@ def sampler_uniforms(T, B, seed, offset=0):
     return ((x0 >> np.uint32(8)).astype(np.float64) * (1.0 / 16777216.0)).reshape(T, B)
 
 
+def dropout_threshold(p):
+    """The uint32 a Philox word is compared with: min(2^32 - 1, float32(p) * 2^32), truncated.  p goes through float32 as it
+    does on the C ABI (0.3 -> 1288490240, not 1288490188); the product of a float32 and 2^32 is exact in float64."""
+    p32 = float(np.float32(p))
+    if not 0.0 <= p32 < 1.0:
+        raise ValueError("dropout probability must be in [0, 1) as a float32")
+    return int(min(4294967295.0, p32 * 4294967296.0))
+
+
+def dropout_scale(p):
+    """What a kept element is multiplied by: the float32 value 1 / (1 - float32(p))."""
+    return np.float32(1.0) / (np.float32(1.0) - np.float32(p))
+
+
+def dropout_keep_mask(n, p, seed, offset):
+    """Keep-mask of inverted dropout over a flat tensor of n elements (spec; model.py:42,45,51 fix only the rates): element i belongs
+    to quad q = i >> 2; the Philox4x32-10 counter is (q lo32, q hi32, offset, 0), the key (seed lo32, seed hi32); element i is kept
+    iff word (i & 3) >= dropout_threshold(p).  Returns a bool array of length n."""
+    n = int(n)
+    nq = (n + 3) // 4
+    q = np.arange(nq, dtype=np.uint64)
+    c0 = (q & _M32).astype(np.uint32)
+    c1 = (q >> np.uint64(32)).astype(np.uint32)
+    c2 = np.full(nq, int(offset) & 0xFFFFFFFF, dtype=np.uint32)
+    c3 = np.zeros(nq, dtype=np.uint32)
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    words = philox4x32_10(c0, c1, c2, c3, seed & 0xFFFFFFFF, seed >> 32)
+    keep = np.stack(words, axis=1) >= np.uint32(dropout_threshold(p))           # (nq, 4): word j of quad q is element 4 q + j
+    return keep.reshape(-1)[:n]
+
+
 def sample_paths(logits, seed, offset=0):
     """Inverse-CDF sample of softmax(logits[t,b,:]) per frame, float64.
     Returns (paths (T,B) int64, cdf (T,B,V) float64, u (T,B))."""

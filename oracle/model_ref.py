@@ -100,9 +100,12 @@ def blstm_layer_packed_equivalent(x, lengths, w):
     return torch.cat(outs, dim=2)
 
 
-def encoder_forward_torch(p, x, mask, packed=True, leaky_side=None, return_pre=False, fast_packed=False):
-    """p: dict of tensors; x (B,F,T); mask (B,T) 1/0 -> (B,T,512).
-    Eval mode (no dropout).  model.py:47-56.
+def encoder_forward_torch(p, x, mask, packed=True, leaky_side=None, return_pre=False, fast_packed=False, dropout_masks=None):
+    """p: dict of tensors; x (B,F,T); mask (B,T) 1/0 -> (B,T,512).  model.py:47-56.
+    dropout_masks = None: eval mode (no dropout).  Train mode: a triple of multiplicative (B,T,512) tensors, ALREADY scaled (0 or
+    1/(1-p)), applied after leaky_relu (nn.Dropout(), model.py:45,51), after BLSTM layer 0 and after BLSTM layer 1 on the
+    concatenated directions (nn.LSTM(dropout=0.3), model.py:42) -- not after layer 2.  The caller draws them (torch's own generator
+    in tests/test_oracle_cpu.py, decode_ref.dropout_keep_mask in the device tests); the BLSTM then runs layer by layer.
     fast_packed (with packed): the packed semantics through ``blstm_layer_packed_equivalent`` (full-size ragged batches).
     leaky_side (B,T,512) bool: which side of leaky_relu (model.py:50) each pre-activation is put on, instead of its own
     sign -- a DISCRETE choice, like an arg-max: a full-size parity test that shares the discrete choices of the device
@@ -113,6 +116,9 @@ def encoder_forward_torch(p, x, mask, packed=True, leaky_side=None, return_pre=F
     pre = F.linear(h, p["input_layer.weight"], p["input_layer.bias"])
     h = F.leaky_relu(pre) if leaky_side is None else torch.where(leaky_side, pre, 0.01 * pre)
     lengths = mask.sum(dim=1).to(torch.int64).cpu()
+    if dropout_masks is not None:
+        out = _blstm_layerwise_with_dropout(p, h, lengths, packed, fast_packed, dropout_masks)
+        return (out, pre) if return_pre else out
     lstm = torch.nn.LSTM(D_IN, H, N_LAYERS, bidirectional=True, batch_first=True).to(x.dtype)
     lstm.eval()
     # run the module with OUR tensors as its parameters so gradients flow back to ``p``
@@ -129,6 +135,54 @@ def encoder_forward_torch(p, x, mask, packed=True, leaky_side=None, return_pre=F
     else:
         out, _ = torch.func.functional_call(lstm, sd, (h,))
     return (out, pre) if return_pre else out
+
+
+def _blstm_layerwise_with_dropout(p, h, lengths, packed, fast_packed, dropout_masks):
+    """The three BLSTM layers one at a time (each in the form ``encoder_forward_torch`` would run all three in), with the input
+    mask on h and the inter-layer masks on the outputs of layers 0 and 1.  h (B,T,512)."""
+    if len(dropout_masks) != N_LAYERS:
+        raise ValueError("dropout_masks: (input mask, after layer 0, after layer 1)")
+    T = h.shape[1]
+    out = h * dropout_masks[0].to(h.dtype)
+    names = [f"{k}_l0{sfx}" for sfx in ("", "_reverse") for k in ("weight_ih", "weight_hh", "bias_ih", "bias_hh")]
+    for l in range(N_LAYERS):
+        w = [p[f"blstm.{k}_l{l}{sfx}"] for sfx in ("", "_reverse") for k in ("weight_ih", "weight_hh", "bias_ih", "bias_hh")]
+        if packed and fast_packed:
+            out = blstm_layer_packed_equivalent(out, lengths, w)
+        else:
+            layer = torch.nn.LSTM(out.shape[2], H, 1, bidirectional=True, batch_first=True).to(h.dtype)
+            layer.eval()
+            if packed:
+                pk = pack_padded_sequence(out, lengths, enforce_sorted=False, batch_first=True)
+                out, _ = torch.func.functional_call(layer, dict(zip(names, w)), (pk,))
+                out, _ = pad_packed_sequence(out, total_length=T, batch_first=True)
+            else:
+                out, _ = torch.func.functional_call(layer, dict(zip(names, w)), (out,))
+        if l + 1 < N_LAYERS:
+            out = out * dropout_masks[l + 1].to(h.dtype)
+    return out
+
+
+def torch_generator_dropout_masks(B, T, lengths=None, dtype=torch.float32, p_in=0.5, p_layer=0.3):
+    """The three scaled masks torch's CPU kernels draw from the GLOBAL generator for one train-mode forward of model.py:50-55, in the
+    order they draw them -- call right after the ``torch.manual_seed`` the forward under comparison started from.
+      lengths given (the reference's call: nn.Dropout, then nn.LSTM on a PackedSequence): F.dropout(ones(B,T,512), p_in), then per
+        inter-layer dropout F.dropout(ones(sum(lengths), 512), p_layer) over the packed data, laid back on (B,T,512).
+      lengths None (nn.LSTM alone on a dense batch): no input mask (ones); each inter-layer draw is time-major, (T,B,512).
+    Checked against torch itself in tests/test_oracle_cpu.py."""
+    from torch.nn.utils.rnn import PackedSequence
+    if lengths is None:
+        layer = [F.dropout(torch.ones(T, B, 2 * H, dtype=dtype), p_layer, True).transpose(0, 1) for _ in range(N_LAYERS - 1)]
+        return [torch.ones(B, T, D_IN, dtype=dtype)] + layer
+    m_in = F.dropout(torch.ones(B, T, D_IN, dtype=dtype), p_in, True)
+    pk = pack_padded_sequence(torch.zeros(B, T, 1), torch.as_tensor(lengths).cpu(), enforce_sorted=False, batch_first=True)
+    layer = []
+    for _ in range(N_LAYERS - 1):
+        d = F.dropout(torch.ones(int(pk.batch_sizes.sum()), 2 * H, dtype=dtype), p_layer, True)
+        m, _ = pad_packed_sequence(PackedSequence(d, pk.batch_sizes, pk.sorted_indices, pk.unsorted_indices),
+                                   total_length=T, batch_first=True)
+        layer.append(m)
+    return [m_in] + layer
 
 
 def head_forward_torch(p, enc_out):

@@ -11,7 +11,7 @@ functions returned for them.  No reference source travels.
   metrics.edit_dist / evaluate                 (metrics.py:4,23)
   loss.customNLLLoss                           (loss.py:5)
   policy_grad.reward                           (policy_grad.py:4)  -- raises as written
-  model.Encoder                                (model.py:34)
+  model.Encoder                                (model.py:34)  -- eval mode, and train mode with its dropout masks
 
 model.py imports torchaudio / torchsummary (and data.py imports cvutils), none of
 which is installed here and none of which the Encoder touches; SURVEY.md §8c
@@ -246,6 +246,45 @@ def gen_encoder():
     return {"n_cases": 3, "n_params": int(n_params), "param_seed": 0, "load_state_dict": str(missing)}
 
 
+def gen_encoder_train():
+    """model.Encoder in .train() (model.py:45,51: nn.Dropout(); model.py:42: nn.LSTM(dropout=0.3)) on small ragged cases, run right
+    after torch.manual_seed(seed); the three keep masks are what torch's generator draws after the same manual_seed in the order the
+    forward draws them (oracle/model_ref.torch_generator_dropout_masks, pinned against torch in tests/test_oracle_cpu.py), stored
+    bit-packed -> encoder_train_cases.npz.  Parameters: model_ref.init_params(seed 0), as gen_encoder."""
+    _placeholders()
+    import model as ref_model  # noqa: E402
+    from oracle import model_ref
+
+    p = model_ref.init_params(n_feats=120, vocab=29, seed=0)
+    enc = ref_model.Encoder()
+    enc.load_state_dict({k: v for k, v in p.items() if not k.startswith("head.")}, strict=True)
+    enc.train()
+    cases = {"param_seed": np.array([0]), "p": np.array([enc.drop.p, enc.blstm.dropout, enc.blstm.dropout])}
+    specs = [(2, 10, [10, 6]), (3, 8, [3, 8, 1])]
+    for cid, (B, T, lens) in enumerate(specs):
+        g = torch.Generator().manual_seed(600 + cid)
+        x = torch.randn(B, 120, T, generator=g)
+        mask = torch.zeros(B, T)
+        for b, n in enumerate(lens):
+            mask[b, :n] = 1
+            x[b, :, n:] = 0
+        torch.manual_seed(700 + cid)
+        with torch.no_grad():
+            y = enc(x, mask)
+        torch.manual_seed(700 + cid)
+        masks = model_ref.torch_generator_dropout_masks(B, T, lens)
+        for m, pp in zip(masks, cases["p"]):       # every kept element carries the one scale 1/(1-p)
+            assert set(np.unique(m.numpy()).tolist()) <= {0.0, float(np.float32(1.0 / (1.0 - pp)))}
+        cases[f"x{cid}"] = x.numpy()
+        cases[f"mask{cid}"] = mask.numpy()
+        cases[f"keep{cid}"] = np.packbits(torch.stack(masks).numpy() != 0)
+        cases[f"y{cid}"] = y.numpy()
+    cases["n_cases"] = np.array([len(specs)])
+    np.savez_compressed(os.path.join(HERE, "encoder_train_cases.npz"), **cases)
+    return {"n_cases": len(specs), "param_seed": 0, "manual_seeds": [700 + c for c in range(len(specs))],
+            "p": [float(v) for v in cases["p"]], "shapes_BT_lens": [[B, T, lens] for B, T, lens in specs]}
+
+
 def main():
     meta = {
         "generator": "tests/golden/make_golden.py",
@@ -255,11 +294,12 @@ def main():
         "custom_nll": gen_nll(),
         "reward_defect": gen_reward_defect(),
         "encoder": gen_encoder(),
+        "encoder_train": gen_encoder_train(),
         "attention": gen_attention(),
     }
     with open(os.path.join(HERE, "reference_vectors.json"), "w") as fo:
         json.dump(meta, fo, indent=0)
-    print("beam cases:", len(meta["beam"]), " encoder:", meta["encoder"])
+    print("beam cases:", len(meta["beam"]), " encoder:", meta["encoder"], " encoder (train mode):", meta["encoder_train"])
 
 
 if __name__ == "__main__":

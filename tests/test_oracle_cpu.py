@@ -325,3 +325,153 @@ def test_step_rewards_and_reward_to_go_properties():
         # frames before the first character all carry the whole reward; frames after the last start carry none
         first = next((t for t, k in enumerate(path) if k != 0), T)
         assert np.all(G[:first + 1] == G[0])
+
+
+# --------------------------------------------------------------------------- #
+# train mode: the dropout mask and its placement
+# --------------------------------------------------------------------------- #
+def test_dropout_threshold_and_scale_go_through_float32():
+    """p crosses the C ABI as a float: 0.3 is 0.300000011920929 there, and the threshold is that value times 2^32 -- 1288490240,
+    not the 1288490188 of the double 0.3 (they differ on ~0.2 elements of a headline tensor: no device test could tell)."""
+    assert decode_ref.dropout_threshold(0.3) == 1288490240 != int(0.3 * 2 ** 32) == 1288490188
+    assert decode_ref.dropout_threshold(0.5) == 2 ** 31
+    assert decode_ref.dropout_threshold(0.0) == 0
+    assert decode_ref.dropout_keep_mask(1001, 0.0, 5, 1).all()                      # every word >= 0
+    assert decode_ref.dropout_threshold(np.nextafter(np.float32(1), np.float32(0))) == 4294967040
+    assert decode_ref.dropout_scale(0.3) == np.float32(1.0) / np.float32(0.7) and decode_ref.dropout_scale(0.3).dtype == np.float32
+    assert decode_ref.dropout_scale(0.5) == 2.0 and decode_ref.dropout_scale(0.0) == 1.0
+    for bad in (1.0, -0.1, 1.5):
+        with pytest.raises(ValueError):
+            decode_ref.dropout_threshold(bad)
+
+
+def test_dropout_keep_mask_is_the_philox_word_comparison():
+    """Element i is word (i & 3) of Philox(counter (i >> 2 lo, i >> 2 hi, offset, 0), key (seed lo, seed hi)) compared with the
+    threshold: hand-picked elements with a key high word and the largest offset; prefixes; every argument matters; the rate."""
+    seed, offset, p = (7 << 32) + 0x1234, 2 ** 32 - 1, 0.3
+    mask = decode_ref.dropout_keep_mask(1003, p, seed, offset)
+    assert mask.dtype == np.bool_ and mask.shape == (1003,)
+    for i in (0, 1, 2, 3, 4, 7, 501, 1000, 1002):
+        one = lambda v: np.array([v], dtype=np.uint32)
+        words = decode_ref.philox4x32_10(one(i >> 2), one(0), one(offset), one(0), seed & 0xFFFFFFFF, seed >> 32)
+        assert bool(mask[i]) == (int(words[i & 3][0]) >= 1288490240), i
+    # prefix property (the tail quad of a length that is no multiple of 4 is the head of the full quad)
+    for m in (1, 2, 3, 5, 998, 1001):
+        np.testing.assert_array_equal(decode_ref.dropout_keep_mask(m, p, seed, offset), mask[:m])
+    # offset, key low word, key high word: each one changes the mask; the seed is taken modulo 2^64, the offset modulo 2^32
+    for other in ((seed, offset - 1), (seed + 1, offset), (seed + (1 << 32), offset), (seed & 0xFFFFFFFF, offset)):
+        assert not np.array_equal(decode_ref.dropout_keep_mask(1003, p, *other), mask), other
+    np.testing.assert_array_equal(decode_ref.dropout_keep_mask(1003, p, seed + (1 << 64), offset + (1 << 32)), mask)
+    # keep rate within 4 binomial sigma of 1 - float32(p)
+    n = 10 ** 6
+    for pp, sd, off in ((0.3, 0x5EED, 1), (0.5, 2 ** 64 - 1, 3)):
+        rate = decode_ref.dropout_keep_mask(n, pp, sd, off).mean()
+        q = 1.0 - decode_ref.dropout_threshold(pp) / 2.0 ** 32
+        assert abs(rate - q) < 4 * np.sqrt(q * (1 - q) / n), (pp, rate)
+
+
+def _ragged_case(B, T, lens, seed, dtype=torch.float64, F_=120):
+    g = torch.Generator().manual_seed(seed)
+    x = torch.randn(B, F_, T, generator=g, dtype=dtype)
+    mask = torch.zeros(B, T)
+    for b, n in enumerate(lens):
+        mask[b, :n] = 1; x[b, :, n:] = 0
+    dy = torch.randn(B, T, 512, generator=g, dtype=dtype)
+    return x, mask, dy
+
+
+def _torch_train_mode_encoder(p, x, mask, dense, seed):
+    """torch's own train-mode modules on our parameters: [nn.Dropout ->] nn.LSTM(3 layers, bidirectional, dropout=0.3) [on a
+    PackedSequence], drawing from the global generator after manual_seed(seed).  ``dense``: nn.LSTM alone on the padded batch."""
+    from torch.nn.utils.rnn import pack_padded_sequence, pad_packed_sequence
+    h = torch.nn.functional.leaky_relu(torch.nn.functional.linear(model_ref.instance_norm(x).transpose(1, 2),
+                                                                  p["input_layer.weight"], p["input_layer.bias"]))
+    lstm = torch.nn.LSTM(512, 256, 3, dropout=0.3, bidirectional=True, batch_first=True).to(x.dtype).train()
+    sd = {k[len("blstm."):]: v for k, v in p.items() if k.startswith("blstm.")}
+    torch.manual_seed(seed)
+    if dense:
+        out, _ = torch.func.functional_call(lstm, sd, (h,))
+        return out
+    h = torch.nn.Dropout().train()(h)
+    pk = pack_padded_sequence(h, mask.sum(1).long(), enforce_sorted=False, batch_first=True)
+    out, _ = torch.func.functional_call(lstm, sd, (pk,))
+    out, _ = pad_packed_sequence(out, total_length=x.shape[2], batch_first=True)
+    return out
+
+
+@pytest.mark.parametrize("dtype", [torch.float64, torch.float32])
+@pytest.mark.parametrize("dense", [True, False])
+def test_train_mode_oracle_equals_torch_train_mode(dense, dtype):
+    """encoder_forward_torch(dropout_masks=...) puts its masks where torch's own train-mode modules put theirs and scales like them:
+    with the masks torch's generator draws (model_ref.torch_generator_dropout_masks) the layer-wise oracle reproduces torch's
+    train-mode output and every parameter gradient -- a dense batch through nn.LSTM alone (time-major draws), a ragged one through
+    nn.Dropout -> pack_padded_sequence -> nn.LSTM as model.py:50-55 -- on every oracle path, at the bound of
+    test_fast_packed_oracle_equals_packed_sequence_path (fp64; fp32 at its own rounding)."""
+    B, T = 4, 19
+    lens = [T] * B if dense else [19, 1, 12, 7]
+    x, mask, dy = _ragged_case(B, T, lens, 17, dtype)
+    p0 = {k: v.to(dtype) for k, v in model_ref.init_params(n_feats=120, vocab=29, seed=0).items() if not k.startswith("head.")}
+    pr = {k: v.clone().requires_grad_(True) for k, v in p0.items()}
+    want = _torch_train_mode_encoder(pr, x, mask, dense, seed=123)
+    want.backward(dy)
+    torch.manual_seed(123)
+    masks = model_ref.torch_generator_dropout_masks(B, T, None if dense else lens, dtype=dtype)
+    assert all(m.shape == (B, T, 512) for m in masks) and 0.6 < float((masks[1] != 0)[mask.bool()].double().mean()) < 0.8
+    paths = [dict(packed=True), dict(packed=True, fast_packed=True)] + ([dict(packed=False)] if dense else [])
+    ro, ao, rg, ag = (1e-12, 1e-13, 1e-9, 1e-12) if dtype == torch.float64 else (1e-5, 1e-6, 1e-4, 1e-5)
+    for kw in paths:
+        pq = {k: v.clone().requires_grad_(True) for k, v in p0.items()}
+        got = model_ref.encoder_forward_torch(pq, x, mask, dropout_masks=masks, **kw)
+        got.backward(dy)
+        np.testing.assert_allclose(got.detach().numpy(), want.detach().numpy(), rtol=ro, atol=ao, err_msg=str(kw))
+        for k in pr:
+            np.testing.assert_allclose(pq[k].grad.numpy(), pr[k].grad.numpy(), rtol=rg, atol=ag, err_msg=f"{kw} {k}")
+    # the masks matter: the eval-mode oracle is far away, and a mask moved one layer down is too
+    with torch.no_grad():
+        ev = model_ref.encoder_forward_torch(p0, x, mask)
+        swapped = model_ref.encoder_forward_torch(p0, x, mask, dropout_masks=[masks[0], masks[2], masks[1]])
+    assert float((ev - want.detach()).abs().max()) > 1e-2 and float((swapped - want.detach()).abs().max()) > 1e-2
+
+
+def test_oracle_without_masks_is_the_eval_mode_oracle_bit_for_bit():
+    """dropout_masks=None takes the branches it always took; masks of ones give the same VALUES through the layer-wise form."""
+    x, mask, _ = _ragged_case(3, 14, [14, 5, 9], 3, torch.float32)
+    p = model_ref.init_params(n_feats=120, vocab=29, seed=0)
+    ones = [torch.ones(3, 14, 512)] * 3
+    with torch.no_grad():
+        for kw in (dict(), dict(fast_packed=True)):
+            a = model_ref.encoder_forward_torch(p, x, mask, **kw)
+            b = model_ref.encoder_forward_torch(p, x, mask, dropout_masks=None, **kw)
+            c = model_ref.encoder_forward_torch(p, x, mask, dropout_masks=ones, **kw)
+            assert torch.equal(a, b)
+            np.testing.assert_allclose(c.numpy(), a.numpy(), rtol=1e-5, atol=1e-6)
+    with pytest.raises(ValueError):
+        model_ref.encoder_forward_torch(p, x, mask, dropout_masks=ones[:2])
+
+
+def test_train_mode_encoder_matches_reference(golden_dir):
+    """The reference's own Encoder in .train() (tests/golden/make_golden.py: gen_encoder_train) against the oracle with the three
+    keep masks the fixture recorded (bit-packed; scaled here by 1/(1-p): 2 and float32(1/0.7)), ragged lengths, both oracle paths,
+    at test_encoder_matches_reference's bound."""
+    z = np.load(os.path.join(golden_dir, "encoder_train_cases.npz"))
+    p = model_ref.init_params(n_feats=120, vocab=29, seed=int(z["param_seed"][0]))
+    n = int(z["n_cases"][0])
+    assert n >= 2 and list(z["p"]) == [0.5, 0.3, 0.3]
+    for cid in range(n):
+        x = torch.from_numpy(z[f"x{cid}"]); mask = torch.from_numpy(z[f"mask{cid}"])
+        B, _, T = x.shape
+        lens = mask.sum(1).int().tolist()
+        assert len(set(lens)) > 1                                   # ragged
+        keep = np.unpackbits(z[f"keep{cid}"])[:3 * B * T * 512].reshape(3, B, T, 512).astype(bool)
+        masks = [torch.from_numpy(keep[i].astype(np.float32) * decode_ref.dropout_scale(pp)) for i, pp in enumerate(z["p"])]
+        for i, pp in enumerate(z["p"]):
+            valid = keep[i][mask.bool().numpy()]
+            assert abs(valid.mean() - (1 - pp)) < 5 * np.sqrt(pp * (1 - pp) / valid.size)
+        for kw in (dict(), dict(fast_packed=True)):
+            with torch.no_grad():
+                y = model_ref.encoder_forward_torch(p, x, mask, dropout_masks=masks, **kw).numpy()
+                y_eval = model_ref.encoder_forward_torch(p, x, mask, **kw).numpy()
+            np.testing.assert_allclose(y, z[f"y{cid}"], rtol=1e-5, atol=1e-6)
+            assert np.abs(y_eval - z[f"y{cid}"]).max() > 1e-2          # the fixture IS a train-mode output
+            for b, nb in enumerate(lens):
+                assert np.all(y[b, nb:] == 0)
