@@ -605,6 +605,33 @@ int pgasr_ctc_beam_search(const void* log_probs, int is_f64, long long stride_t,
                           void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * A7-LM  The same search fused with a character n-gram language model (Hannun/Maas, arXiv:1408.2873; the place the reference
+ * marks at its extension step, CTCdecoder.py:90-96).  Arguments of pgasr_ctc_beam_search, the same workspace function, plus:
+ *   lm_table: dense fp32 device table of natural-log probabilities of shape (V,)*lm_order, C order:
+ *             lm_table[c_1, .., c_{n-1}, s] = ln p(s | c_1 .. c_{n-1}), c_{n-1} the most recent symbol.  blank never occurs inside a
+ *             prefix and serves as the start pad: the context of a prefix shorter than n-1 is left-padded with blank.  The column
+ *             s == blank is never read.  Every entry that can be read must be finite (the caller's duty; the Python layer checks it).
+ *   lm_order: n >= 1;  V^n <= 2^25 entries (128 MiB: order 5 at V = 29, order 4 at V = 64), beyond that PGASR_ERR_UNSUPPORTED --
+ *             a table is never truncated.
+ *   lm_alpha, lm_beta: every term that enters a prefix by an extension with a non-blank s gets
+ *             w = lm_alpha * (double)lm_table[ctx(prefix), s] + lm_beta  added -- (p_b + p) + w, (p_nb + p) + w -- also where the
+ *             extension merges into a prefix already in the beam.  The blank update and the repeat branch that keeps the prefix
+ *             (CTCdecoder.py:103-106) are unchanged; there is no end-of-sentence term.  Candidate order, first-touch ties and the
+ *             stable descending sort are those of pgasr_ctc_beam_search; the ranking key logsumexp(p_b, p_nb) includes the bonuses.
+ *   out_score = -logsumexp(p_blank, p_nonblank) of the best entry: with a language model a FUSED score, not a negative log-likelihood.
+ *   lm_table == NULL and lm_order == 0: exactly pgasr_ctc_beam_search (the same kernels, the single-wave dispatch included).
+ *   With a table every call takes the workgroup-per-utterance kernel (the single-wave kernel has no LM term); the LM arithmetic is
+ *   fp64 for fp32 and fp64 log_probs alike; lm_alpha = lm_beta = 0 gives the no-LM result of that kernel bit for bit.
+ *   Checked before any HIP call: lm_order < 0, lm_order > 0 with a NULL table, a table with lm_order == 0, non-finite weights
+ *   -> PGASR_ERR_INVALID_ARG; the size cap -> PGASR_ERR_UNSUPPORTED.
+ * ---------------------------------------------------------------------------------------- */
+int pgasr_ctc_beam_search_lm(const void* log_probs, int is_f64, long long stride_t, long long stride_b,
+                             const int32_t* lengths, int T, int B, int V, int beam, int blank, int flags,
+                             int32_t* out_tokens, int32_t* out_len, double* out_score,
+                             void* workspace, size_t workspace_bytes, void* stream,
+                             const float* lm_table, int lm_order, double lm_alpha, double lm_beta);
+
+/* ------------------------------------------------------------------------------------------
  * Elementwise pieces of the train step.
  * pgasr_dropout: inverted dropout y = keep ? x/(1-p) : 0 (nn.Dropout, model.py:45,51 p=0.5; LSTM
  *   inter-layer dropout model.py:42 p=0.3).  keep is a pure function of (seed, offset, element

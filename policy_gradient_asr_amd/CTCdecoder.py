@@ -19,15 +19,30 @@ def _device(device=None):
 BEAM_KMAX = 128      # csrc/beam.hip
 
 
+_UNSET = object()      # "use the decoder's own value" (None is a value: no language model)
+
+
 class CTCDecoder:
-    def __init__(self, alphabet, device=None):
+    def __init__(self, alphabet, device=None, lm=None, lm_alpha=0.0, lm_beta=0.0):
+        """lm: None (default: the acoustic search of the reference) or a ``lm.CharNgramLM``; every extension of a prefix by a
+        non-blank symbol s then gets ``lm_alpha * ln p_lm(s | last order-1 symbols) + lm_beta`` added (Hannun/Maas,
+        arXiv:1408.2873 -- the place CTCdecoder.py:90-96 marks for an LM score).  ``decode`` / ``decode_batch`` use these values
+        unless a call overrides them."""
         self.alphabet = alphabet
         self.NEG_INF = -float("inf")
         self.device = device
+        self.lm, self.lm_alpha, self.lm_beta = lm, float(lm_alpha), float(lm_beta)
 
-    def decode(self, probs, beam_size=100, blank=0):
+    def _lm_args(self, lm, lm_alpha, lm_beta):
+        return {"lm": self.lm if lm is _UNSET else lm,
+                "lm_alpha": self.lm_alpha if lm_alpha is None else float(lm_alpha),
+                "lm_beta": self.lm_beta if lm_beta is None else float(lm_beta)}
+
+    def decode(self, probs, beam_size=100, blank=0, lm=_UNSET, lm_alpha=None, lm_beta=None):
         """probs: (time x output dim) array of PROBABILITIES (CTCdecoder.py:41-53).
-        Returns (label tuple, negative log-likelihood of that prefix).
+        Returns (label tuple, negative log-likelihood of that prefix).  With a language model (the decoder's, or ``lm`` /
+        ``lm_alpha`` / ``lm_beta`` given here; ``lm=None`` switches it off for this call) the second value is the FUSED score
+        -logsumexp(p_blank, p_nonblank) with the LM bonuses in it, not a negative log-likelihood.
         Limits of the device search (the reference has none): beam_size <= 128 and at most 64 output symbols --
         a larger request raises instead of silently searching a narrower beam."""
         dev = _device(self.device)
@@ -40,14 +55,17 @@ class CTCDecoder:
         lp = torch.from_numpy(np.ascontiguousarray(logp)).to(dev).view(T, 1, V)
         if int(beam_size) > BEAM_KMAX:
             raise ValueError(f"beam_size {beam_size} exceeds the device search's limit of {BEAM_KMAX}")
-        tokens, tl, score = hipops.ctc_beam_search(lp, None, beam=int(beam_size), blank=int(blank))
+        tokens, tl, score = hipops.ctc_beam_search(lp, None, beam=int(beam_size), blank=int(blank),
+                                                   **self._lm_args(lm, lm_alpha, lm_beta))
         n = int(tl[0].item())
         return tuple(int(x) for x in tokens[0, :n].tolist()), float(score[0].item())
 
-    def decode_batch(self, log_probs, lengths=None, beam_size=5, blank=0):
+    def decode_batch(self, log_probs, lengths=None, beam_size=5, blank=0, lm=_UNSET, lm_alpha=None, lm_beta=None):
         """Device-side batched form: log_probs (T,B,V) GPU tensor of natural-log probabilities.
-        Returns (tokens (B,T) int32, lengths (B) int32, nll (B) float64) without a host sync."""
-        return hipops.ctc_beam_search(log_probs, lengths, beam=int(beam_size), blank=int(blank))
+        Returns (tokens (B,T) int32, lengths (B) int32, nll (B) float64) without a host sync.  With a language model (see
+        ``decode``) the third value is the fused score, not a negative log-likelihood."""
+        return hipops.ctc_beam_search(log_probs, lengths, beam=int(beam_size), blank=int(blank),
+                                      **self._lm_args(lm, lm_alpha, lm_beta))
 
 
 def collapse_fn(preds):

@@ -14,6 +14,7 @@
 // Scores are fp64 (log-sum-exp exactly as CTCdecoder.py:31-39: max, sum of exps in argument order,
 // log); this is integer/latency work, not MFMA work.
 #include "common.h"
+#include <cmath>
 #include <type_traits>
 
 namespace {
@@ -86,11 +87,36 @@ __device__ __forceinline__ bool item_less(const SortItem& a, const SortItem& b) 
     return a.key < b.key || (a.key == b.key && a.time < b.time);
 }
 
-template <typename TIn, bool FAST>
+// Language-model fusion (LM = true; Hannun/Maas arXiv:1408.2873, the reference's "*NB* this would be a good place to include an LM
+// score" at the extension step): a dense fp32 table of natural-log probabilities, table[c_1 .. c_{n-1}, s] = ln p(s | c_1 .. c_{n-1}),
+// c_{n-1} the most recent symbol, contexts shorter than n-1 left-padded with blank.  Every term that enters a prefix by an extension with a
+// non-blank s (:90-96) gets  w = alpha * (double)table[ctx(prefix), s] + beta  added: (p_b + p) + w, (p_nb + p) + w.  The blank update
+// (:78-82) and the repeat branch that keeps the prefix (:103-106) are unchanged.
+//   * an entry carries ctx = index of its last n-1 symbols (stay: inherited; extension by s: (ctx V + s) mod V^(n-1)) and lmi = the
+//     table index ctx(parent prefix) V + last of its own last emission.  The merged term of entry j's stay candidate, "extension of
+//     parent i by last(j)", uses parent i's context -- a function of the prefix alone, so its table word IS table[lmi_j], known without
+//     waiting for pidx;
+//   * candidate (j, s) reads table[ctx_j V + s]: consecutive candidates of one entry read consecutive words.  The loads of a thread's
+//     first BEAM_LM_PRE candidates and of the entries' own words are issued at the top of the frame (ctx is known as soon as the new
+//     beam is written) and parked in the thread's own, not yet written sort items until the candidate loop, so they are in flight
+//     beside the frame's log-probs and waited for once; candidates beyond BEAM_LM_PRE * 256 load in place;
+//   * w is computed in fp64 without contraction (__dmul_rn, __dadd_rn) in the exact and the fast instantiation alike.
+// The arguments are an empty struct for LM = false: those instantiations carry none of this.
+constexpr int BEAM_LM_PRE = 4;
+constexpr long long BEAM_LM_MAX_ENTRIES = 1ll << 25;      // V^n <= 2^25 words (128 MiB): order 5 at V = 29, order 4 at V = 64
+template <bool LM> struct BeamLm {};
+template <> struct BeamLm<true> {
+    const float* table;      // V^n words
+    int ctx_mod;             // V^(n-1)
+    int ctx0;                // the all-blank context (the root's)
+    double alpha, beta;
+};
+
+template <typename TIn, bool FAST, bool LM>
 __global__ __launch_bounds__(BEAM_THREADS) void beam_search_kernel(
     const TIn* __restrict__ lp, long long stride_t, long long stride_b, const int32_t* __restrict__ lengths,
     int T, int V, int K, int blank, int collapse, BeamWs ws, int32_t* __restrict__ out_tokens, int32_t* __restrict__ out_len,
-    double* __restrict__ out_score) {
+    double* __restrict__ out_score, const BeamLm<LM> lm) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int b = blockIdx.x, tid = threadIdx.x;
     int Tb = lengths ? lengths[b] : T; Tb = Tb < 0 ? 0 : (Tb > T ? T : Tb);
@@ -108,7 +134,10 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_search_kernel(
     int* par = last + 2 * K;                   // [2][K]
     int* pidx = par + 2 * K;                   // [K]
     int* s_ctl = pidx + K;                     // [4]: nb, node counter
-    short* cb = reinterpret_cast<short*>(s_ctl + 4);       // [K][V] child-in-beam table
+    int* ctx = s_ctl + 4;                      // LM only: [2][K] context index
+    int* lmi = ctx + 2 * K;                    // LM only: [2][K] table index of the entry's own last emission
+    float* ptv = reinterpret_cast<float*>(lmi + 2 * K);    // LM only: [K] table[lmi] of the current beam
+    short* cb = reinterpret_cast<short*>(LM ? s_ctl + 4 + 5 * K : s_ctl + 4);       // [K][V] child-in-beam table
 #define s_nb s_ctl[0]
 #define s_nodes s_ctl[1]
 
@@ -120,6 +149,7 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_search_kernel(
         s_nb = 1; s_nodes = 1;
         id[0] = 0; last[0] = -1; par[0] = -1; pb[0] = 0.0; pnb[0] = -INFINITY;
         nodes[0] = 0xFFFFFFFFu;
+        if constexpr (LM) { ctx[0] = lm.ctx0; lmi[0] = 0; }      // the root has no emission of its own: lmi is never used (last < 0)
     }
     __syncthreads();
     int cur = 0;
@@ -127,12 +157,31 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_search_kernel(
         const int nb = s_nb;
         const int* cid = id + cur * K; const int* clast = last + cur * K; const int* cpar = par + cur * K;
         const double* cpb = pb + cur * K; const double* cpnb = pnb + cur * K;
+        [[maybe_unused]] const int* cctx = ctx + cur * K;
+        [[maybe_unused]] float lmv[BEAM_LM_PRE], lmp = 0.0f;
+        if constexpr (LM) {      // issue the gathers first: nothing below depends on them until the candidate loop
+#pragma unroll
+            for (int k = 0; k < BEAM_LM_PRE; ++k) {
+                const int c = tid + k * BEAM_THREADS;
+                lmv[k] = 0.0f;
+                if (c < nb * V) { const int j = c / V, s = c % V; if (s != blank) lmv[k] = lm.table[cctx[j] * V + s]; }
+            }
+            if (tid < nb && last[cur * K + tid] >= 0) lmp = lm.table[lmi[cur * K + tid]];
+        }
         if (tid < V) frame[tid] = (double)lp[(long long)t * stride_t + (long long)b * stride_b + tid];
         for (int i = tid; i < nb * V; i += BEAM_THREADS) cb[i] = -1;
         if (tid < nb) {
             int f = -1;
             for (int i = 0; i < nb; ++i) if (cid[i] == cpar[tid]) f = i;
             pidx[tid] = f;
+        }
+        if constexpr (LM) {      // park them: items[c] is this thread's own word until it writes candidate c
+#pragma unroll
+            for (int k = 0; k < BEAM_LM_PRE; ++k) {
+                const int c = tid + k * BEAM_THREADS;
+                if (c < P) items[c].cand = __float_as_uint(lmv[k]);
+            }
+            if (tid < nb) ptv[tid] = lmp;
         }
         __syncthreads();
         if (tid < nb && pidx[tid] >= 0) cb[pidx[tid] * V + clast[tid]] = (short)tid;
@@ -158,6 +207,10 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_search_kernel(
                         const double own = cpnb[j] + pl;                              // repeat branch (:103-106)
                         if (i >= 0) {
                             double e1 = cpb[i] + pl, e2 = cpnb[i] + pl;               // extension of parent i by lj (:90-96)
+                            if constexpr (LM) {
+                                const double w = __dadd_rn(__dmul_rn(lm.alpha, (double)ptv[j]), lm.beta);
+                                e1 += w; e2 += w;
+                            }
                             const bool rep = (clast[i] == lj);
                             if (i < j) {
                                 npnb = rep ? lse2x<FAST>(npnb, e1) : lse3x<FAST>(npnb, e1, e2);
@@ -178,6 +231,12 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_search_kernel(
                     alive = false;          // merged into an existing entry's stay candidate
                 } else {
                     const double ps = frame[s];
+                    if constexpr (LM) {
+                        const float tv = (c < BEAM_LM_PRE * BEAM_THREADS) ? __uint_as_float(items[c].cand) : lm.table[cctx[j] * V + s];
+                        const double w = __dadd_rn(__dmul_rn(lm.alpha, (double)tv), lm.beta);
+                        const double eb = (cpb[j] + ps) + w, en = (cpnb[j] + ps) + w;
+                        npnb = (s != clast[j]) ? lse3x<FAST>(-INFINITY, eb, en) : lse2x<FAST>(-INFINITY, eb);
+                    } else
                     npnb = (s != clast[j]) ? lse3x<FAST>(-INFINITY, cpb[j] + ps, cpnb[j] + ps) : lse2x<FAST>(-INFINITY, cpb[j] + ps);
                     time = (unsigned)(s * nb + j);
                 }
@@ -222,6 +281,11 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_search_kernel(
             if (it.cand != 0xFFFFFFFFu) {
                 const int c = (int)it.cand, j = c / V, s = c % V;
                 nbpb[tid] = c_pb[c]; nbpnb[tid] = c_pnb[c];
+                if constexpr (LM) {
+                    const int e = cctx[j] * V + s;
+                    ctx[nxt * K + tid] = (s == blank) ? cctx[j] : e % lm.ctx_mod;
+                    lmi[nxt * K + tid] = (s == blank) ? lmi[cur * K + j] : e;
+                }
                 if (s == blank) { nid[tid] = cid[j]; nlast[tid] = clast[j]; npar[tid] = cpar[j]; }
                 else {
                     // canonical node for (id[j], s): look up, else create
@@ -273,13 +337,14 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_search_kernel(
 #undef s_nb
 #undef s_nodes
 
-inline size_t beam_lds_bytes(int K, int V) {
+inline size_t beam_lds_bytes(int K, int V, bool lm) {
     int P = 1; while (P < K * V) P <<= 1;
     size_t n = (size_t)P * sizeof(SortItem);
     n += (size_t)2 * K * V * sizeof(double);          // c_pb, c_pnb
     n += (size_t)4 * K * sizeof(double);              // pb, pnb double-buffered
     n += (size_t)BEAM_VMAX * sizeof(double);          // frame
     n += (size_t)(6 * K + K + 4) * sizeof(int);       // id,last,par (x2), pidx, control words
+    if (lm) n += (size_t)(5 * K) * sizeof(int);       // ctx, lmi (x2), ptv
     n += (size_t)K * V * sizeof(short);               // cb
     return (n + 15) / 16 * 16;
 }
@@ -757,13 +822,30 @@ extern "C" size_t pgasr_beam_workspace_bytes(int T, int B, int V, int beam) {
     return beam_ws_layout(T, B, beam, nullptr, nullptr);
 }
 
-extern "C" int pgasr_ctc_beam_search(const void* log_probs, int is_f64, long long stride_t, long long stride_b,
-                                     const int32_t* lengths, int T, int B, int V, int beam, int blank, int flags,
-                                     int32_t* out_tokens, int32_t* out_len, double* out_score,
-                                     void* workspace, size_t workspace_bytes, void* stream) {
+namespace {
+int beam_search_impl(const void* log_probs, int is_f64, long long stride_t, long long stride_b,
+                     const int32_t* lengths, int T, int B, int V, int beam, int blank, int flags,
+                     int32_t* out_tokens, int32_t* out_len, double* out_score,
+                     void* workspace, size_t workspace_bytes, void* stream,
+                     const float* lm_table, int lm_order, double lm_alpha, double lm_beta) {
     if (!log_probs || !out_tokens || !out_len || !out_score) return PGASR_ERR_INVALID_ARG;
     if (T <= 0 || B <= 0 || V <= 0 || beam <= 0 || blank < 0 || blank >= V) return PGASR_ERR_INVALID_ARG;
     if (V > BEAM_VMAX || beam > BEAM_KMAX) return PGASR_ERR_UNSUPPORTED;
+    // the language model's arguments, before any HIP call
+    if (lm_order < 0 || (lm_order > 0) != (lm_table != nullptr)) return PGASR_ERR_INVALID_ARG;
+    const bool with_lm = lm_order > 0;
+    BeamLm<true> lm{};
+    if (with_lm) {
+        if (!std::isfinite(lm_alpha) || !std::isfinite(lm_beta)) return PGASR_ERR_INVALID_ARG;
+        long long entries = 1, ctx_mod = 1, ctx0 = 0;
+        for (int k = 0; k < lm_order; ++k) {
+            if (k == lm_order - 1) ctx_mod = entries;
+            entries *= V;
+            if (entries > BEAM_LM_MAX_ENTRIES) return PGASR_ERR_UNSUPPORTED;      // refused, never truncated
+        }
+        for (int k = 0; k < lm_order - 1; ++k) ctx0 = ctx0 * V + blank;
+        lm.table = lm_table; lm.ctx_mod = (int)ctx_mod; lm.ctx0 = (int)ctx0; lm.alpha = lm_alpha; lm.beta = lm_beta;
+    }
     BeamWs ws;
     const size_t need = beam_ws_layout(T, B, beam, &ws, (char*)workspace);
     if (!workspace || workspace_bytes < need) return PGASR_ERR_WORKSPACE;
@@ -774,7 +856,7 @@ extern "C" int pgasr_ctc_beam_search(const void* log_probs, int is_f64, long lon
 #else
     const int collapse = flags & 1;
 #endif
-    if (!is_f64 && !(flags & 2) && beam <= sb::K_MAX && V <= sb::V_MAX && (long long)T * beam <= sb::MAX_NODES && T <= sb::MAX_TOKENS) {
+    if (!with_lm && !is_f64 && !(flags & 2) && beam <= sb::K_MAX && V <= sb::V_MAX && (long long)T * beam <= sb::MAX_NODES && T <= sb::MAX_TOKENS) {
         // training path: one wave per utterance, trie and candidate lists in LDS, no workspace traffic; 8 symbols per lane up to V = 32
         // (the English alphabet of the headline), 16 up to V = 64 (round 5: CommonVoice's larger alphabets stay on this kernel)
         auto kern = V <= 32 ? &sb::beam_small_kernel<8> : &sb::beam_small_kernel<16>;
@@ -786,17 +868,40 @@ extern "C" int pgasr_ctc_beam_search(const void* log_probs, int is_f64, long lon
         return PGASR_OK;
     }
     if (hipMemsetAsync(ws.table, 0, (size_t)B * ws.H * sizeof(unsigned long long), st) != hipSuccess) return PGASR_ERR_LAUNCH;
-    const size_t lds = beam_lds_bytes(beam, V);
+    const size_t lds = beam_lds_bytes(beam, V, with_lm);
     if (lds > 160 * 1024) return PGASR_ERR_UNSUPPORTED;
-    if (is_f64) {   // exact path: fp64 transcendentals (drop-in CTCDecoder.decode)
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&beam_search_kernel<double, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        PGASR_LAUNCH_KERNEL((beam_search_kernel<double, false>), dim3(B), dim3(BEAM_THREADS), lds, st, (const double*)log_probs,
-                           stride_t, stride_b, lengths, T, V, beam, blank, collapse, ws, out_tokens, out_len, out_score);
-    } else {        // fp32 device log-probs: fast transcendentals
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&beam_search_kernel<float, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        PGASR_LAUNCH_KERNEL((beam_search_kernel<float, true>), dim3(B), dim3(BEAM_THREADS), lds, st, (const float*)log_probs,
-                           stride_t, stride_b, lengths, T, V, beam, blank, collapse, ws, out_tokens, out_len, out_score);
+    // is_f64: exact path, fp64 transcendentals (drop-in CTCDecoder.decode); fp32 device log-probs: fast transcendentals
+#define BEAM_LAUNCH(TIN, FAST, LMB, LMARG)                                                                                        \
+    {                                                                                                                             \
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&beam_search_kernel<TIN, FAST, LMB>),                             \
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                          \
+        PGASR_LAUNCH_KERNEL((beam_search_kernel<TIN, FAST, LMB>), dim3(B), dim3(BEAM_THREADS), lds, st, (const TIN*)log_probs,    \
+                           stride_t, stride_b, lengths, T, V, beam, blank, collapse, ws, out_tokens, out_len, out_score, LMARG);  \
     }
+    if (with_lm) {      // with a language model every call takes this kernel (the single-wave kernel has no LM term)
+        if (is_f64) BEAM_LAUNCH(double, false, true, lm) else BEAM_LAUNCH(float, true, true, lm)
+    } else {
+        if (is_f64) BEAM_LAUNCH(double, false, false, BeamLm<false>{}) else BEAM_LAUNCH(float, true, false, BeamLm<false>{})
+    }
+#undef BEAM_LAUNCH
     PGASR_CHECK_LAUNCH();
     return PGASR_OK;
+}
+}  // namespace
+
+extern "C" int pgasr_ctc_beam_search(const void* log_probs, int is_f64, long long stride_t, long long stride_b,
+                                     const int32_t* lengths, int T, int B, int V, int beam, int blank, int flags,
+                                     int32_t* out_tokens, int32_t* out_len, double* out_score,
+                                     void* workspace, size_t workspace_bytes, void* stream) {
+    return beam_search_impl(log_probs, is_f64, stride_t, stride_b, lengths, T, B, V, beam, blank, flags, out_tokens, out_len, out_score,
+                            workspace, workspace_bytes, stream, nullptr, 0, 0.0, 0.0);
+}
+
+extern "C" int pgasr_ctc_beam_search_lm(const void* log_probs, int is_f64, long long stride_t, long long stride_b,
+                                        const int32_t* lengths, int T, int B, int V, int beam, int blank, int flags,
+                                        int32_t* out_tokens, int32_t* out_len, double* out_score,
+                                        void* workspace, size_t workspace_bytes, void* stream,
+                                        const float* lm_table, int lm_order, double lm_alpha, double lm_beta) {
+    return beam_search_impl(log_probs, is_f64, stride_t, stride_b, lengths, T, B, V, beam, blank, flags, out_tokens, out_len, out_score,
+                            workspace, workspace_bytes, stream, lm_table, lm_order, lm_alpha, lm_beta);
 }

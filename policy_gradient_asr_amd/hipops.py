@@ -1043,12 +1043,17 @@ def lstm_cell(gh, xp, c, h, h_out=None):
 # ------------------------------------------------------------------------------------------
 # prefix beam search
 # ------------------------------------------------------------------------------------------
-def ctc_beam_search(log_probs, lengths=None, beam=5, blank=0, collapse=False, out=None, generic=False):
+def ctc_beam_search(log_probs, lengths=None, beam=5, blank=0, collapse=False, out=None, generic=False,
+                    lm=None, lm_alpha=0.0, lm_beta=0.0):
     """log_probs (T,B,V) fp32 or fp64 natural-log probabilities on the GPU.
     Returns (tokens (B,T) int32, token_lengths (B) int32, score (B) float64 = -log p).
     collapse: the returned tokens have gone through collapse_fn (adjacent duplicates removed, CTCdecoder.py:119-131),
     the form policy_grad.py:8 scores.  out = (tokens, token_lengths) to write into (tokens zero-filled).
-    generic: never take the single-wave small-beam kernel (testing)."""
+    generic: never take the single-wave small-beam kernel (testing).
+    lm: None (default: the acoustic search, the kernels and bits it always had) or a ``lm.CharNgramLM`` over the same V symbols and
+    blank: every extension by a non-blank s gets ``lm_alpha * ln p_lm(s | context) + lm_beta`` added (pgasr_ctc_beam_search_lm in
+    include/pgasr_hip.h).  The returned score is then a FUSED score, not a negative log-likelihood.  With an LM every call takes the
+    workgroup-per-utterance kernel."""
     lib = _lib.load()
     if not log_probs.is_cuda or log_probs.dtype not in (torch.float32, torch.float64):
         raise _lib.PgasrError("log_probs must be a float32/float64 GPU tensor")
@@ -1056,6 +1061,11 @@ def ctc_beam_search(log_probs, lengths=None, beam=5, blank=0, collapse=False, ou
         raise _lib.PgasrError("log_probs must be contiguous in its last dimension")
     T, B, V = log_probs.shape
     _req(lengths, torch.int32, "lengths")
+    lm_table, lm_order = None, 0
+    if lm is not None:
+        if lm.vocab != V or lm.blank != int(blank):
+            raise ValueError(f"the LM is over {lm.vocab} symbols with blank {lm.blank}; the search has {V} symbols and blank {int(blank)}")
+        lm_table, lm_order = lm.device_table(log_probs.device), lm.order
     nbytes = lib.pgasr_beam_workspace_bytes(T, B, V, beam)
     ws = _workspace(nbytes, log_probs.device, "beam")
     if out is not None:
@@ -1068,10 +1078,12 @@ def ctc_beam_search(log_probs, lengths=None, beam=5, blank=0, collapse=False, ou
         tl = torch.empty(B, dtype=torch.int32, device=log_probs.device)
     score = torch.empty(B, dtype=torch.float64, device=log_probs.device)
     with _timed("beam_search"):
-        st = lib.pgasr_ctc_beam_search(_p(log_probs), int(log_probs.dtype == torch.float64), log_probs.stride(0),
-                                       log_probs.stride(1), _p(lengths), T, B, V, int(beam), int(blank), int(bool(collapse)) | (2 if generic else 0),
-                                       _p(tokens), _p(tl), _p(score), _p(ws), ws.numel(), _stream())
-    _lib.check(st, "pgasr_ctc_beam_search")
+        # one entry point for both: without a table it IS pgasr_ctc_beam_search
+        st = lib.pgasr_ctc_beam_search_lm(_p(log_probs), int(log_probs.dtype == torch.float64), log_probs.stride(0),
+                                          log_probs.stride(1), _p(lengths), T, B, V, int(beam), int(blank), int(bool(collapse)) | (2 if generic else 0),
+                                          _p(tokens), _p(tl), _p(score), _p(ws), ws.numel(), _stream(),
+                                          _p(lm_table), lm_order, float(lm_alpha), float(lm_beta))
+    _lib.check(st, "pgasr_ctc_beam_search_lm")
     return tokens, tl, score
 
 

@@ -365,16 +365,19 @@ def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset
 
 
 def predict(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=None, maxlent=None, device_id=0,
-            test_dataset=None, n_feats=120, beam_size=5, features="mfcc"):
+            test_dataset=None, n_feats=120, beam_size=5, features="mfcc", lm_path=None, lm_alpha=0.0, lm_beta=0.0):
     """model.py:277-339: load model_best.pth, forward, beam=5 prefix search (device side, batched),
     collapse_fn, CER/WER, predicted.txt.  Frames are cut by the FEATURE mask (the reference cuts the
     time axis by the target mask, model.py:322 -- a listed defect).  Returns (CER, WER).
     features: the front end for items that carry waveforms, as in ``train`` ("mfcc": n_feats=120, "logmel80": n_feats=80);
-    the features stay on the device."""
+    the features stay on the device.
+    lm_path: None (default) or an ``lm.npz`` written by ``build_lm`` / ``CharNgramLM.save``: the beam search then adds
+    lm_alpha * ln p_lm(s | context) + lm_beta to every extension by a character s (CTCDecoder)."""
     import os
     import functools
     import torch.utils.data as tud
     from .CTCdecoder import CTCDecoder, collapse_fn
+    from .lm import CharNgramLM
     from .data import Data
     from .data import collate_custom as _collate
     from .metrics import evaluate, save_predictions
@@ -390,7 +393,8 @@ def predict(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=N
     _check_features(features, n_feats, test_dataset)
     collate_custom = functools.partial(_collate, device=dev, features=features)
     loader = tud.DataLoader(test_dataset, batch_size=batch_size, shuffle=False, collate_fn=collate_custom)
-    decoder = CTCDecoder(alphabet)
+    lm = CharNgramLM.load(lm_path) if lm_path is not None else None
+    decoder = CTCDecoder(alphabet, lm=lm, lm_alpha=lm_alpha, lm_beta=lm_beta)
     targets, predicted, tot_cer, tot_wer, n = [], [], 0.0, 0.0, 0
     print("Total number of examples: ", len(test_dataset))
     with torch.no_grad():
@@ -411,3 +415,19 @@ def predict(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=N
     cer, wer = tot_cer / max(n, 1), tot_wer / max(n, 1)
     print("CER: {:>4f} WER: {:>4f}".format(cer, wer))
     return cer, wer
+
+
+def build_lm(corpus_path, order=3, out_path=None, train_dataset=None):
+    """Character n-gram LM (lm.CharNgramLM, interpolated Witten-Bell) from the transcripts that Data(train.tsv) yields, over the
+    symbols of <corpus_path>/alphabet.txt (``<pad>`` = blank = 0); saved to ``out_path`` (default <corpus_path>/lm.npz) for
+    ``predict(lm_path=...)``.  ``train_dataset``: any Dataset whose items carry "trans", instead of train.tsv.  Returns the LM."""
+    import os
+    from .data import Data
+    from .lm import CharNgramLM
+    _, char2ind = _read_alphabet(os.path.join(corpus_path, "alphabet.txt"))
+    if train_dataset is None:
+        train_dataset = Data(os.path.join(corpus_path, "train.tsv"), os.path.join(corpus_path, "clips"), char2ind)
+    lines = [train_dataset[i]["trans"] for i in range(len(train_dataset))]
+    lm = CharNgramLM.from_text(lines, char2ind, order=order, blank=0)
+    lm.save(out_path if out_path is not None else os.path.join(corpus_path, "lm.npz"))
+    return lm
