@@ -45,7 +45,8 @@ typedef enum pgasr_status {
  * pgasr_pg_rewards_multi_ex), the gradient-clipping entries (pgasr_grad_norm_ws_bytes, pgasr_grad_norm_clip,
  * pgasr_adam_step_clipped), the id-addressed samplers (pgasr_frame_argmax_sample_ids, pgasr_frame_sample_multi_ids) and the
  * sequence-level score function (pgasr_ctc_hyp_workspace_bytes, pgasr_ctc_hyp_lattice, pgasr_ctc_grad_from_lattices_seq,
- * pgasr_pg_loss_value_seq). */
+ * pgasr_pg_loss_value_seq) and the entropy regularisation (pgasr_frame_entropy, pgasr_ctc_grad_from_lattice_ent,
+ * pgasr_ctc_grad_from_lattice_multi_ent, pgasr_ctc_grad_from_lattices_seq_ent). */
 #define PGASR_ABI_VERSION 7
 
 int pgasr_abi_version(void);
@@ -184,6 +185,45 @@ int pgasr_pg_loss_value_seq(const float* log_probs, const int32_t* paths, int K,
                             const float* nll, const float* utt_scale, const float* pg_coef,
                             const float* hyp_nll, const int32_t* hyp_len, int Lh,
                             int T, int B, int V, float* terms, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * A12  entropy regularisation of the frame policy (opt-in; the exploration side of the REINFORCE objectives above).  With
+ * beta >= 0, T_b = input_lengths[b] clamped to [0, T] and H[t,b] = -sum_v p_v ln p_v in nats (p = exp(log_probs[t,b,:]), 0 ln 0 := 0):
+ *     ent_mean[b]  = (1 / max(T_b,1)) sum_{t<T_b} H[t,b]            the utterance's MEAN frame entropy; 0 for an empty utterance
+ *     ent_scale[b] = beta * inv_global_batch / max(T_b,1)
+ *     objective   += -sum_b beta * inv_global_batch * ent_mean[b]   =  -sum_b ent_scale[b] sum_{t<T_b} H[t,b]
+ *     d(logits)[t,b,v] += ent_scale[b] * p_v * (ln p_v + H[t,b])    for t < T_b, 0 beyond
+ * The bonus is a mean over the utterance's own frames, so beta is in loss units per nat per frame and does not grow with T.  It
+ * depends on the log-probs and lengths alone: not on targets, rewards, samples or the score function, and an utterance whose target
+ * nll is +inf still gets it.
+ *
+ * pgasr_frame_entropy: both vectors in one launch, no host round trip (as pgasr_pg_rewards leaves utt_scale).  One workgroup per
+ *   utterance; the sums over v (wave butterfly) and over t (16 strided partial sums in fp64, added in order) have a fixed order, so
+ *   the result is run-to-run reproducible.  -inf entries and symbols whose p underflows add exactly 0.  beta = 0 is the monitoring
+ *   call (ent_scale = 0).  V <= 64 (else PGASR_ERR_UNSUPPORTED), any T; beta < 0 or NaN, inv_global_batch <= 0, null pointers:
+ *   PGASR_ERR_INVALID_ARG.
+ * pgasr_ctc_grad_from_lattice_ent / _multi_ent / pgasr_ctc_grad_from_lattices_seq_ent: the three gradient passes above with the
+ *   entropy term added in the same pass, after the REINFORCE terms: one wave sum per row and one fma per lane.  ent_scale (B) sits
+ *   before grad_logits; every other argument is the entry's without the suffix.  ent_scale = NULL runs that entry's own kernel (the
+ *   same bits); lanes >= V and symbols with p = 0 contribute exactly 0.
+ * ---------------------------------------------------------------------------------------- */
+int pgasr_frame_entropy(const float* log_probs, const int32_t* input_lengths, int T, int B, int V,
+                        float beta, float inv_global_batch, float* ent_mean, float* ent_scale, void* stream);
+int pgasr_ctc_grad_from_lattice_ent(const float* log_probs, const int32_t* input_lengths,
+                                    const int32_t* target_lengths, int T, int B, int V, int Lmax, int blank,
+                                    const float* utt_scale, const float* pg_coef, const int32_t* pg_path,
+                                    int pg_coef_per_frame, const float* ent_scale, float* grad_logits,
+                                    void* workspace, size_t workspace_bytes, void* stream);
+int pgasr_ctc_grad_from_lattice_multi_ent(const float* log_probs, const int32_t* input_lengths,
+                                          const int32_t* target_lengths, int T, int B, int V, int Lmax, int blank,
+                                          const float* utt_scale, int K, const float* pg_coef, const int32_t* pg_paths,
+                                          const float* ent_scale, float* grad_logits, void* workspace, size_t workspace_bytes,
+                                          void* stream);
+int pgasr_ctc_grad_from_lattices_seq_ent(const float* log_probs, const int32_t* input_lengths, const int32_t* target_lengths,
+                                         int T, int B, int V, int Lmax, int blank, const float* utt_scale,
+                                         int K, const float* pg_coef, const int32_t* pg_paths, const int32_t* hyp_len, int Lh,
+                                         const float* ent_scale, float* grad_logits, void* workspace, size_t workspace_bytes,
+                                         void* hyp_workspace, size_t hyp_workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * A11  word-level (WER) reward, opt-in: R = -WED(y, yhat) / W(y), where a word is a run of tokens between delimiters -- exactly

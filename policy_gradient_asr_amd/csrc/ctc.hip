@@ -362,12 +362,70 @@ __device__ __forceinline__ float ctc_grad_row(float lpv, float sm, int lane, int
     return g;
 }
 
+// ---- entropy regularisation of the frame policy (pgasr_frame_entropy and the *_ent gradient entries) ----
+// H_{t,b} = -sum_v p_v ln p_v (nats) of row (t,b), from the row's log p and p as the gradient kernels hold them: one lane per symbol,
+// lanes >= V with p = 0.  A symbol with p = 0 (ln p = -inf, or an exp that underflowed) adds exactly 0: no 0 * -inf.  One wave_sum in
+// its fixed butterfly order; every lane returns p ln p of its own symbol and the row's H.
+__device__ __forceinline__ float row_entropy(float lpv, float sm, float* plp) {
+    *plp = sm > 0.f ? sm * lpv : 0.f;
+    return -wave_sum(*plp);
+}
+
+// d(-ent_scale_b H_{t,b}) / d(logits) = ent_scale_b p (ln p + H), in the pass that writes the row: one wave_sum, one fma per lane.
+// The three gradient kernels are templated <bool ENT, class... Ent>: the ENT instantiation takes ONE more argument after grad,
+// `const float* ent_scale` (B), and adds this term last; the ENT = false instantiation has the argument list -- and the kernarg
+// layout, implicit arguments included -- it had before the term existed.  (An empty struct in that place moved the implicit
+// arguments by 8 bytes.)
+__device__ __forceinline__ float ctc_entropy_grad(float lpv, float sm, int b, const float* __restrict__ ent_scale) {
+    float plp;
+    const float H = row_entropy(lpv, sm, &plp);
+    return sm > 0.f ? ent_scale[b] * fmaf(sm, H, plp) : 0.f;
+}
+
+// ent_mean[b] = (1 / max(T_b,1)) sum_{t<T_b} H_{t,b} and ent_scale[b] = beta * inv_global_batch / max(T_b,1).  One workgroup of
+// ENT_WAVES waves per utterance: wave w adds the entropies of frames w, w + ENT_WAVES, .. in t order (fp64 carries), wave 0 lane 0 adds
+// the ENT_WAVES partial sums in w order -- a fixed order over v and t, so two calls give the same bits.
+constexpr int ENT_WAVES = 16;
+__global__ __launch_bounds__(64 * ENT_WAVES) void frame_entropy_kernel(
+    const float* __restrict__ lp, const int32_t* __restrict__ in_len, int T, int B, int V, float beta, float inv_gb,
+    float* __restrict__ ent_mean, float* __restrict__ ent_scale) {
+    __shared__ double part[ENT_WAVES];
+    const int b = blockIdx.x, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    int Tb = in_len[b]; Tb = Tb < 0 ? 0 : (Tb > T ? T : Tb);
+    double acc = 0.0;
+    // four of the wave's frames per trip: their loads are in flight together, their entropies added in t order
+    for (int t0 = w; t0 < Tb; t0 += 4 * ENT_WAVES) {
+        float lpv[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int t = t0 + i * ENT_WAVES;
+            lpv[i] = (lane < V && t < Tb) ? lp[((size_t)t * B + b) * V + lane] : -INFINITY;
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            float plp;
+            acc += (double)row_entropy(lpv[i], __expf(lpv[i]), &plp);      // a frame >= T_b reads as p = 0 everywhere: H = 0
+        }
+    }
+    if (lane == 0) part[w] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double s = 0.0;
+        for (int i = 0; i < ENT_WAVES; ++i) s += part[i];
+        const float n = (float)(Tb > 0 ? Tb : 1);
+        ent_mean[b] = (float)(s / (double)n);
+        ent_scale[b] = beta * inv_gb / n;
+    }
+}
+
 // one wave per (t,b)
+template <bool ENT, class... Ent>
 __global__ __launch_bounds__(256) void ctc_grad_kernel(
     const float* __restrict__ lp, const int32_t* __restrict__ in_len, const int32_t* __restrict__ tg_len,
     int T, int B, int V, int Lmax, int Smax, int blank, CtcWs ws,
     const float* __restrict__ utt_scale, const float* __restrict__ pg_coef,
-    const int32_t* __restrict__ pg_path, int coef_per_frame, float* __restrict__ grad) {
+    const int32_t* __restrict__ pg_path, int coef_per_frame, float* __restrict__ grad, Ent... ent_scale) {
+    static_assert(sizeof...(Ent) == (ENT ? 1 : 0), "ent_scale iff ENT");
     const int lane = threadIdx.x & 63;
     const long long w = (long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     if (w >= (long long)T * B) return;
@@ -384,17 +442,20 @@ __global__ __launch_bounds__(256) void ctc_grad_kernel(
         const int k = pg_path[(size_t)t * B + b];
         g += pg_coef[coef_per_frame ? (size_t)t * B + b : (size_t)b] * (sm - (lane == k ? 1.f : 0.f));
     }
+    if constexpr (ENT) g += ctc_entropy_grad(lpv, sm, b, ent_scale...);
     if (lane < V) grad[o + lane] = g;
 }
 
 // Multi-sample REINFORCE (pgasr_ctc_grad_from_lattice_multi): the CTC part above, then the K terms
 // pg_coef[k,b] * (softmax - onehot(pg_paths[k,t,b])) added in k order.  One wave per (t,b), one pass over the gradient;
 // K = 1 is ctc_grad_kernel's per-utterance expression.
+template <bool ENT, class... Ent>
 __global__ __launch_bounds__(256) void ctc_grad_multi_kernel(
     const float* __restrict__ lp, const int32_t* __restrict__ in_len, const int32_t* __restrict__ tg_len,
     int T, int B, int V, int Lmax, int Smax, int blank, CtcWs ws,
     const float* __restrict__ utt_scale, int K, const float* __restrict__ pg_coef,
-    const int32_t* __restrict__ pg_paths, float* __restrict__ grad) {
+    const int32_t* __restrict__ pg_paths, float* __restrict__ grad, Ent... ent_scale) {
+    static_assert(sizeof...(Ent) == (ENT ? 1 : 0), "ent_scale iff ENT");
     const int lane = threadIdx.x & 63;
     const long long w = (long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     if (w >= (long long)T * B) return;
@@ -412,6 +473,7 @@ __global__ __launch_bounds__(256) void ctc_grad_multi_kernel(
         const int pk = pg_paths[k * TB + (size_t)t * B + b];
         g += pg_coef[(size_t)k * B + b] * (sm - (lane == pk ? 1.f : 0.f));
     }
+    if constexpr (ENT) g += ctc_entropy_grad(lpv, sm, b, ent_scale...);
     if (lane < V) grad[o + lane] = g;
 }
 
@@ -471,12 +533,14 @@ __global__ __launch_bounds__(CTC_THREADS + 64) void ctc_hyp_lattice_kernel(
 
 // One wave per (t,b), one pass, one write: the target part, then sample k = 0..K-1 in k order -- the sequence term from lattice
 // (k,b) where hyp_len[k,b] <= Lh (ctc_grad_row over the hypothesis workspace, scale pg_coef[k,b]), else ctc_grad_multi_kernel's path term.
+template <bool ENT, class... Ent>
 __global__ __launch_bounds__(256) void ctc_grad_seq_kernel(
     const float* __restrict__ lp, const int32_t* __restrict__ in_len, const int32_t* __restrict__ tg_len,
     int T, int B, int V, int Lmax, int Smax, int blank, CtcWs ws,
     const float* __restrict__ utt_scale, int K, const float* __restrict__ pg_coef,
     const int32_t* __restrict__ pg_paths, const int32_t* __restrict__ hyp_len, int Lh, int Smax_h, CtcWs hws,
-    float* __restrict__ grad) {
+    float* __restrict__ grad, Ent... ent_scale) {
+    static_assert(sizeof...(Ent) == (ENT ? 1 : 0), "ent_scale iff ENT");
     const int lane = threadIdx.x & 63;
     const long long w = (long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     if (w >= (long long)T * B) return;
@@ -501,6 +565,7 @@ __global__ __launch_bounds__(256) void ctc_grad_seq_kernel(
             g += pg_coef[p] * (sm - (lane == pk ? 1.f : 0.f));
         }
     }
+    if constexpr (ENT) g += ctc_entropy_grad(lpv, sm, b, ent_scale...);
     if (lane < V) grad[o + lane] = g;
 }
 
@@ -595,7 +660,7 @@ extern "C" int pgasr_ctc_loss_grad(const float* log_probs, const int32_t* target
 #undef PGASR_LATTICE
     PGASR_CHECK_LAUNCH();
     if (!grad_logits) return PGASR_OK;
-    return ctc_launch_grad(ctc_grad_kernel, log_probs, input_lengths, target_lengths, T, B, V, Lmax, blank, ws, utt_scale, stream,
+    return ctc_launch_grad(ctc_grad_kernel<false>, log_probs, input_lengths, target_lengths, T, B, V, Lmax, blank, ws, utt_scale, stream,
                            pg_coef, pg_path, 0, grad_logits);
 }
 
@@ -608,13 +673,26 @@ extern "C" int pgasr_ctc_grad_from_lattice(const float* log_probs, const int32_t
                                            const float* utt_scale, const float* pg_coef, const int32_t* pg_path,
                                            int pg_coef_per_frame, float* grad_logits, void* workspace, size_t workspace_bytes,
                                            void* stream) {
+    return pgasr_ctc_grad_from_lattice_ent(log_probs, input_lengths, target_lengths, T, B, V, Lmax, blank, utt_scale, pg_coef, pg_path,
+                                           pg_coef_per_frame, nullptr, grad_logits, workspace, workspace_bytes, stream);
+}
+
+// ... with the entropy term: ent_scale NULL launches the kernel of the entry above, else its ENT instantiation
+extern "C" int pgasr_ctc_grad_from_lattice_ent(const float* log_probs, const int32_t* input_lengths,
+                                               const int32_t* target_lengths, int T, int B, int V, int Lmax, int blank,
+                                               const float* utt_scale, const float* pg_coef, const int32_t* pg_path,
+                                               int pg_coef_per_frame, const float* ent_scale, float* grad_logits,
+                                               void* workspace, size_t workspace_bytes, void* stream) {
     if (!log_probs || !input_lengths || !target_lengths || !grad_logits) return PGASR_ERR_INVALID_ARG;
     if ((pg_coef == nullptr) != (pg_path == nullptr)) return PGASR_ERR_INVALID_ARG;
     const int ok = ctc_args_ok(T, B, V, Lmax, blank);
     if (ok != PGASR_OK) return ok;
     CtcWs ws;
     if (!ctc_ws_bind(T, B, V, 2 * Lmax + 1, &ws, workspace, workspace_bytes)) return PGASR_ERR_WORKSPACE;
-    return ctc_launch_grad(ctc_grad_kernel, log_probs, input_lengths, target_lengths, T, B, V, Lmax, blank, ws, utt_scale, stream,
+    if (ent_scale)
+        return ctc_launch_grad(ctc_grad_kernel<true, const float*>, log_probs, input_lengths, target_lengths, T, B, V, Lmax, blank, ws, utt_scale, stream,
+                               pg_coef, pg_path, pg_coef_per_frame ? 1 : 0, grad_logits, ent_scale);
+    return ctc_launch_grad(ctc_grad_kernel<false>, log_probs, input_lengths, target_lengths, T, B, V, Lmax, blank, ws, utt_scale, stream,
                            pg_coef, pg_path, pg_coef_per_frame ? 1 : 0, grad_logits);
 }
 
@@ -623,14 +701,38 @@ extern "C" int pgasr_ctc_grad_from_lattice_multi(const float* log_probs, const i
                                                  const int32_t* target_lengths, int T, int B, int V, int Lmax, int blank,
                                                  const float* utt_scale, int K, const float* pg_coef, const int32_t* pg_paths,
                                                  float* grad_logits, void* workspace, size_t workspace_bytes, void* stream) {
+    return pgasr_ctc_grad_from_lattice_multi_ent(log_probs, input_lengths, target_lengths, T, B, V, Lmax, blank, utt_scale, K, pg_coef,
+                                                 pg_paths, nullptr, grad_logits, workspace, workspace_bytes, stream);
+}
+
+extern "C" int pgasr_ctc_grad_from_lattice_multi_ent(const float* log_probs, const int32_t* input_lengths,
+                                                     const int32_t* target_lengths, int T, int B, int V, int Lmax, int blank,
+                                                     const float* utt_scale, int K, const float* pg_coef, const int32_t* pg_paths,
+                                                     const float* ent_scale, float* grad_logits, void* workspace,
+                                                     size_t workspace_bytes, void* stream) {
     if (!log_probs || !input_lengths || !target_lengths || !grad_logits || !pg_coef || !pg_paths) return PGASR_ERR_INVALID_ARG;
     if (K < 1 || K > PGASR_MAX_SAMPLES) return PGASR_ERR_INVALID_ARG;
     const int ok = ctc_args_ok(T, B, V, Lmax, blank);
     if (ok != PGASR_OK) return ok;
     CtcWs ws;
     if (!ctc_ws_bind(T, B, V, 2 * Lmax + 1, &ws, workspace, workspace_bytes)) return PGASR_ERR_WORKSPACE;
-    return ctc_launch_grad(ctc_grad_multi_kernel, log_probs, input_lengths, target_lengths, T, B, V, Lmax, blank, ws, utt_scale, stream,
-                           K, pg_coef, pg_paths, grad_logits);
+    if (ent_scale)
+        return ctc_launch_grad(ctc_grad_multi_kernel<true, const float*>, log_probs, input_lengths, target_lengths, T, B, V, Lmax, blank, ws, utt_scale,
+                               stream, K, pg_coef, pg_paths, grad_logits, ent_scale);
+    return ctc_launch_grad(ctc_grad_multi_kernel<false>, log_probs, input_lengths, target_lengths, T, B, V, Lmax, blank, ws, utt_scale,
+                           stream, K, pg_coef, pg_paths, grad_logits);
+}
+
+// ---- the frame policy's entropy: ent_mean (B) for monitoring and the loss value, ent_scale (B) for the *_ent gradient passes ----
+extern "C" int pgasr_frame_entropy(const float* log_probs, const int32_t* input_lengths, int T, int B, int V,
+                                   float beta, float inv_global_batch, float* ent_mean, float* ent_scale, void* stream) {
+    if (!log_probs || !input_lengths || !ent_mean || !ent_scale) return PGASR_ERR_INVALID_ARG;
+    if (T <= 0 || B <= 0 || V <= 0 || !(beta >= 0.f) || !(inv_global_batch > 0.f)) return PGASR_ERR_INVALID_ARG;
+    if (V > CTC_VMAX) return PGASR_ERR_UNSUPPORTED;
+    PGASR_LAUNCH_KERNEL(frame_entropy_kernel, dim3(B), dim3(64 * ENT_WAVES), 0, (hipStream_t)stream,
+                       log_probs, input_lengths, T, B, V, beta, inv_global_batch, ent_mean, ent_scale);
+    PGASR_CHECK_LAUNCH();
+    return PGASR_OK;
 }
 
 // ---- sequence-level REINFORCE: the K*B hypothesis lattices and the passes over K+1 lattices (see the kernels' comment) ----
@@ -666,6 +768,16 @@ extern "C" int pgasr_ctc_grad_from_lattices_seq(const float* log_probs, const in
                                                 int K, const float* pg_coef, const int32_t* pg_paths, const int32_t* hyp_len, int Lh,
                                                 float* grad_logits, void* workspace, size_t workspace_bytes,
                                                 void* hyp_workspace, size_t hyp_workspace_bytes, void* stream) {
+    return pgasr_ctc_grad_from_lattices_seq_ent(log_probs, input_lengths, target_lengths, T, B, V, Lmax, blank, utt_scale, K, pg_coef,
+                                                pg_paths, hyp_len, Lh, nullptr, grad_logits, workspace, workspace_bytes,
+                                                hyp_workspace, hyp_workspace_bytes, stream);
+}
+
+extern "C" int pgasr_ctc_grad_from_lattices_seq_ent(const float* log_probs, const int32_t* input_lengths, const int32_t* target_lengths,
+                                                    int T, int B, int V, int Lmax, int blank, const float* utt_scale,
+                                                    int K, const float* pg_coef, const int32_t* pg_paths, const int32_t* hyp_len, int Lh,
+                                                    const float* ent_scale, float* grad_logits, void* workspace, size_t workspace_bytes,
+                                                    void* hyp_workspace, size_t hyp_workspace_bytes, void* stream) {
     if (!log_probs || !input_lengths || !target_lengths || !grad_logits || !pg_coef || !pg_paths || !hyp_len) return PGASR_ERR_INVALID_ARG;
     if (Lmax < 0 || blank < 0 || blank >= V) return PGASR_ERR_INVALID_ARG;
     int ok = ctc_hyp_args_ok(T, B, V, K, Lh);
@@ -675,8 +787,11 @@ extern "C" int pgasr_ctc_grad_from_lattices_seq(const float* log_probs, const in
     CtcWs ws, hws;
     if (!ctc_ws_bind(T, B, V, 2 * Lmax + 1, &ws, workspace, workspace_bytes)) return PGASR_ERR_WORKSPACE;
     if (!ctc_ws_bind(T, K * B, V, Smax_h, &hws, hyp_workspace, hyp_workspace_bytes)) return PGASR_ERR_WORKSPACE;
-    return ctc_launch_grad(ctc_grad_seq_kernel, log_probs, input_lengths, target_lengths, T, B, V, Lmax, blank, ws, utt_scale, stream,
-                           K, pg_coef, pg_paths, hyp_len, Lh, Smax_h, hws, grad_logits);
+    if (ent_scale)
+        return ctc_launch_grad(ctc_grad_seq_kernel<true, const float*>, log_probs, input_lengths, target_lengths, T, B, V, Lmax, blank, ws, utt_scale,
+                               stream, K, pg_coef, pg_paths, hyp_len, Lh, Smax_h, hws, grad_logits, ent_scale);
+    return ctc_launch_grad(ctc_grad_seq_kernel<false>, log_probs, input_lengths, target_lengths, T, B, V, Lmax, blank, ws, utt_scale,
+                           stream, K, pg_coef, pg_paths, hyp_len, Lh, Smax_h, hws, grad_logits);
 }
 
 extern "C" int pgasr_pg_loss_value_seq(const float* log_probs, const int32_t* paths, int K, const int32_t* input_lengths,

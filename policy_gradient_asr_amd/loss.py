@@ -79,6 +79,19 @@ class PGCTCLossFn(torch.autograd.Function):
     the multi-sample kernels (K = 1 included); not with per_step (frame-aligned coefficients have no sequence form).
     ``PGCTCLossFn.last_sequence_scored``: (K,B) bool on the device, which samples of the last call took the sequence term (None after
     a "path" call).
+    ``entropy_weight = beta > 0`` (opt-in; 0, the default, is every objective above launch for launch and bit for bit): entropy
+    regularisation of the frame policy, the exploration side -- nothing above keeps the per-frame distributions from collapsing to
+    one-hot rows, after which every sample is the greedy path, R_k - b_k = 0 and the REINFORCE term is silent.  With
+    H_{t,b} = -sum_v p_v ln p_v (nats, 0 ln 0 := 0) and ent_scale_b = beta / (Bg max(T_b,1)):
+        loss      += -sum_b ent_scale_b sum_{t<T_b} H_{t,b}
+        d(logits) += ent_scale_b p_v (ln p_v + H_{t,b})     for t < T_b, 0 beyond
+    The bonus is the utterance's MEAN frame entropy, so beta is in loss units per nat per frame and does not grow with T.  It does
+    not depend on targets, rewards, samples or the score function (any other option, per_step included, takes it), an utterance whose
+    target nll is +inf still gets it, an empty utterance adds nothing, and nothing in it is sampled, so shards and micro-batches need
+    no addressing for it.  ``pgasr_frame_entropy`` runs on the side stream beside the lattice; the gradient passes add the term in the
+    pass that writes d(logits) (their ``_ent`` entries).  ``PGCTCLossFn.last_entropy``: (B,) mean frame entropy per utterance of the
+    last call, detached, on the device (None after a call with weight 0); ``metrics.frame_entropy`` is the same kernel for monitoring.
+    A KL penalty towards a frozen reference policy would be the same kernel with a second log-prob tensor (not built).
     Returns (loss, stats) where stats = (nll (B), R_s (B), R_g (B)) detached; with K > 1, (nll (B), R_s (K,B), R_b (B)) where
     R_b is the baseline averaged over k (R_g for "hypothesis")."""
 
@@ -90,12 +103,15 @@ class PGCTCLossFn(torch.autograd.Function):
     unit_seed_ptr = None
     unit_hits = 0              # how often the shortcut was taken (tests)
     last_sequence_scored = None    # (K,B) bool: the samples of the last score_function="sequence" call that were sequence-scored
+    last_entropy = None            # (B,) fp32: mean frame entropy per utterance of the last entropy_weight > 0 call
     @staticmethod
     def forward(ctx, logits, in_len, targets, tg_len, log_probs, sample_ids, opt):
         """opt: the ``PGOptions`` of the call, checked by ``pg_ctc_loss``."""
         T, B, V = logits.shape
-        PGCTCLossFn.last_sequence_scored = None
+        PGCTCLossFn.last_sequence_scored = PGCTCLossFn.last_entropy = None
         K, beam, blank = opt.num_samples, opt.beam, opt.blank
+        beta = opt.entropy_weight
+        ent_mean = ent_scale = None
         loo = opt.baseline == "leave_one_out"
         wd = opt.word_delimiter if opt.reward_unit == "word" else None
         Lh = hipops.hyp_len_cap(T, opt.max_hyp_len) if opt.score_function == "sequence" else None     # the hypothesis-length cap
@@ -126,6 +142,10 @@ class PGCTCLossFn(torch.autograd.Function):
             lay = {"batch_stride": opt.global_batch, "batch_offset": opt.sample_base} if opt.sample_base >= 0 else {}
         side.wait_stream(main)
         with torch.cuda.stream(side):
+            if beta > 0:
+                # the policy's entropy needs the log-probs alone: first on the side stream, under the lattice
+                ent_mean, ent_scale = hipops.frame_entropy(lp, in_len, beta, inv_gb)
+                PGCTCLossFn.last_entropy = ent_mean
             # samples (K,T,B); paths = what one collapse takes: [greedy,] samples
             if single:
                 greedy, sample = hipops.frame_argmax_sample(lp, seed=opt.seed, offset=opt.offset, want_greedy=greedy_row, **lay)
@@ -171,17 +191,22 @@ class PGCTCLossFn(torch.autograd.Function):
                 coef = hipops.pg_step_coefs(paths, in_len, prefix, tok_len.view(2 * B), tg_len, opt.lam, inv_gb, blank=blank)
         nll, lattice = hipops.ctc_lattice(lp, targets, in_len, tg_len, blank=blank)
         main.wait_stream(side)
-        for t_ in (samples, R_b, R_s, coef, utt_scale) + ((tok_len, hyp_nll, scored) if Lh is not None else ()):
+        for t_ in ((samples, R_b, R_s, coef, utt_scale) + ((tok_len, hyp_nll, scored) if Lh is not None else ())
+                   + ((ent_mean, ent_scale) if beta > 0 else ())):
             streams.hold(t_, main)
+        ent = {"ent_scale": ent_scale} if beta > 0 else {}        # weight 0: the calls as they were
         if single:
-            grad = hipops.ctc_grad_from_lattice(lp, in_len, tg_len, lattice, utt_scale=utt_scale, pg_coef=coef, pg_path=sample)
-            loss = hipops.pg_loss_value(lp, sample, in_len, nll, utt_scale, coef).sum()
+            grad = hipops.ctc_grad_from_lattice(lp, in_len, tg_len, lattice, utt_scale=utt_scale, pg_coef=coef, pg_path=sample, **ent)
+            terms = hipops.pg_loss_value(lp, sample, in_len, nll, utt_scale, coef)
         elif Lh is None:
-            grad = hipops.ctc_grad_from_lattice_multi(lp, in_len, tg_len, lattice, utt_scale, coef, samples)
-            loss = hipops.pg_loss_value_multi(lp, samples, in_len, nll, utt_scale, coef).sum()
+            grad = hipops.ctc_grad_from_lattice_multi(lp, in_len, tg_len, lattice, utt_scale, coef, samples, **ent)
+            terms = hipops.pg_loss_value_multi(lp, samples, in_len, nll, utt_scale, coef)
         else:
-            grad = hipops.ctc_grad_from_lattices_seq(lp, in_len, tg_len, lattice, hyp_lattice, utt_scale, coef, samples, hyp_len)
-            loss = hipops.pg_loss_value_seq(lp, samples, in_len, nll, utt_scale, coef, hyp_nll, hyp_len, Lh).sum()
+            grad = hipops.ctc_grad_from_lattices_seq(lp, in_len, tg_len, lattice, hyp_lattice, utt_scale, coef, samples, hyp_len, **ent)
+            terms = hipops.pg_loss_value_seq(lp, samples, in_len, nll, utt_scale, coef, hyp_nll, hyp_len, Lh)
+        if beta > 0:
+            terms = torch.sub(terms, ent_mean, alpha=beta * inv_gb)      # - beta / Bg * (mean frame entropy), on the device
+        loss = terms.sum()
         ctx.save_for_backward(grad)
         ctx.mark_non_differentiable(nll, R_s, R_b)
         ctx.set_materialize_grads(False)        # no zero-filled gradients for the three statistics
@@ -225,6 +250,7 @@ class PGOptions:
     word_delimiter: object = None
     score_function: str = "path"
     max_hyp_len: object = None
+    entropy_weight: float = 0.0
 
 
 def check_options(opt, vocab=None, frames=None, symbols=None, sample_ids=None):
@@ -242,7 +268,19 @@ def check_options(opt, vocab=None, frames=None, symbols=None, sample_ids=None):
         raise ValueError(f"the word-level reward takes at most {hipops.WORD_MAX_STRIDE} frames and target symbols per utterance "
                          f"(pgasr_word_ids); got T = {frames}")
     return dataclasses.replace(opt, num_samples=int(opt.num_samples),
-                               max_hyp_len=None if opt.max_hyp_len is None else int(opt.max_hyp_len))
+                               max_hyp_len=None if opt.max_hyp_len is None else int(opt.max_hyp_len),
+                               entropy_weight=check_entropy_weight(opt.entropy_weight))
+
+
+def check_entropy_weight(entropy_weight):
+    """The weight of the entropy bonus, in loss units per nat per frame: a finite real number >= 0 -> float."""
+    if isinstance(entropy_weight, bool) or not isinstance(entropy_weight, numbers.Real):
+        raise ValueError(f"entropy_weight must be a real number >= 0 (got {entropy_weight!r})")
+    v = float(entropy_weight)
+    if not (v >= 0.0 and v != float("inf")):        # negative, NaN, inf
+        raise ValueError(f"entropy_weight must be finite and >= 0: it weighs the mean frame entropy, in loss units per nat per frame "
+                         f"(got {entropy_weight!r})")
+    return v
 
 
 def _check_unit(reward_unit, word_delimiter, per_step=False, blank=None, vocab=None):
@@ -291,7 +329,7 @@ def _check_samples(num_samples, baseline, per_step=False):
 
 def pg_ctc_loss(logits, in_len, targets, tg_len, lam=1.0, seed=0, offset=0, global_batch=None, blank=0, beam=0, sample_base=-1,
                 per_step=False, log_probs=None, num_samples=1, baseline="hypothesis", reward_unit="char", word_delimiter=None,
-                sample_ids=None, score_function="path", max_hyp_len=None):
+                sample_ids=None, score_function="path", max_hyp_len=None, entropy_weight=0.0):
     """beam > 0: the baseline reward comes from the prefix-beam-search hypothesis of that width (see PGCTCLossFn).
     num_samples / baseline: multi-sample REINFORCE (see PGCTCLossFn); with num_samples > 1 the third returned tensor is R_s (K,B).
     reward_unit: "char" (default) or "word" -- the word-level reward R = -WED / W(y) with words split at the token
@@ -303,13 +341,16 @@ def pg_ctc_loss(logits, in_len, targets, tg_len, lam=1.0, seed=0, offset=0, glob
     (a padded, empty utterance).
     score_function: "path" (default) or "sequence" -- score every sample by the CTC likelihood of its collapsed hypothesis instead of
     its frame path (see PGCTCLossFn); max_hyp_len caps the hypotheses so scored (None: min(T, 1023)), longer ones keep the path term.
+    entropy_weight: beta >= 0, the weight of the entropy bonus on the frame policy -- the loss gains -beta / Bg times every utterance's
+    MEAN frame entropy, so beta is in loss units per nat per frame and does not grow with T (see PGCTCLossFn); 0 (default): off, the
+    call as it was.  With every other option.
     log_probs: log_softmax(logits) if the caller already has it (the head kernel's by-product, ``logits.log_probs`` of
     Seq2Seq.logits -- picked up from that attribute when not given)."""
     T, B, V = logits.shape
     opt = check_options(PGOptions(lam=float(lam), seed=int(seed), offset=int(offset), global_batch=int(global_batch or B),
                                   blank=int(blank), beam=int(beam), sample_base=int(sample_base), per_step=bool(per_step),
                                   num_samples=num_samples, baseline=baseline, reward_unit=reward_unit, word_delimiter=word_delimiter,
-                                  score_function=score_function, max_hyp_len=max_hyp_len),
+                                  score_function=score_function, max_hyp_len=max_hyp_len, entropy_weight=entropy_weight),
                         vocab=V, frames=T, symbols=targets.shape[1] if targets.dim() == 2 else 0, sample_ids=sample_ids)
     if log_probs is None:
         # the by-product is valid only for the tensor as the head kernel wrote it: any in-place edit since bumps _version

@@ -64,6 +64,14 @@ def edit_counts(targets, tg_len, tokens, tok_len, delimiter):
     return cd, tg_len, wd, wc
 
 
+def frame_entropy(log_probs, in_len):
+    """Mean frame entropy of the policy per utterance: log_probs (T,B,V) fp32 log-softmax outputs and in_len (B) int32 on the GPU ->
+    (B,) fp32 on the device, the mean over each utterance's own frames of H = -sum_v p ln p in nats (0 for an empty utterance;
+    ln V for a uniform policy, 0 for a collapsed one).  The kernel of the trainer's ``entropy_weight`` term with weight 0
+    (hipops.frame_entropy): lets ``predict`` or validation code watch for collapse without training.  No host round trip."""
+    return hipops.frame_entropy(log_probs, in_len, 0.0, 1.0)[0]
+
+
 def save_predictions(target, predicted, model_path):
     """predicted.txt with one 'target|prediction' line per utterance (metrics.py:33-37)."""
     path = os.path.join(model_path, "predicted.txt")

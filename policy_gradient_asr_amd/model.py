@@ -210,7 +210,7 @@ def _check_features(features, n_feats, dataset):
 def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset=None, dev_dataset=None,
           n_feats=120, lam=1.0, lr=5e-4, resume=True, log_every=10, seed=0, bucket_by_length=True, features="mfcc",
           precision="f32", num_samples=1, reward_baseline="hypothesis", reward_unit="char", max_grad_norm=None,
-          accumulate_steps=1, score_function="path", max_hyp_len=None):
+          accumulate_steps=1, score_function="path", max_hyp_len=None, entropy_weight=0.0):
     """Epoch loop of model.py:186-274 on the MI355X path: per-epoch train loss -> train_loss.npy,
     validation CTC loss -> val_losses.npy, model_best.pth / model_last.pth (state_dicts, reference
     names), plus checkpoint_last.pth (model + Adam moments + epoch) from which ``resume`` restarts
@@ -228,6 +228,9 @@ def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset
     score_function: "path" (default) or "sequence" -- score every sample by the CTC likelihood of its collapsed hypothesis instead of
     its frame path (same expected gradient, lower variance); max_hyp_len caps the hypotheses so scored (None: every one of at most
     min(T, 1023) tokens; longer ones keep the path-level term) and with it the lattice workspace -- PolicyGradientTrainer.
+    entropy_weight: 0 (default: off) or beta > 0 -- entropy regularisation of the frame policy against collapse: the loss gains
+    -beta / batch times every utterance's MEAN frame entropy (nats), so beta is in loss units per nat per frame and does not grow with
+    T -- PolicyGradientTrainer.  The log lines then carry the batch-mean entropy.
     max_grad_norm: None (default) or a bound > 0 on the global L2 norm of a step's gradient, clipped on the device inside the step
     (clip_grad_norm_ between backward and the update; a step whose gradient holds an inf / NaN is skipped) -- PolicyGradientTrainer.
     The log lines then carry the last gradient norm, and the end of an epoch the counts of clipped and skipped steps.
@@ -270,7 +273,8 @@ def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset
     _check_features(features, n_feats, train_dataset)
     trainer = PolicyGradientTrainer(model, lr=lr, lam=lam, seed=seed, precision=precision, num_samples=num_samples,
                                     reward_baseline=reward_baseline, reward_unit=reward_unit, word_delimiter=word_delimiter,
-                                    max_grad_norm=max_grad_norm, score_function=score_function, max_hyp_len=max_hyp_len)
+                                    max_grad_norm=max_grad_norm, score_function=score_function, max_hyp_len=max_hyp_len,
+                                    entropy_weight=entropy_weight)
     losses, val_losses, best, start_epoch = [], [], 9999999.0, 1
     ckpt = os.path.join(model_path, "checkpoint_last.pth")
     if resume and os.path.exists(ckpt):
@@ -287,7 +291,7 @@ def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset
         for k, want in (("lr", lr), ("lam", lam), ("num_samples", num_samples), ("reward_baseline", reward_baseline),
                         ("reward_unit", reward_unit), ("max_grad_norm", max_grad_norm),
                         ("accumulate_steps", accumulate_steps), ("score_function", score_function),
-                        ("max_hyp_len", max_hyp_len)):
+                        ("max_hyp_len", max_hyp_len), ("entropy_weight", entropy_weight)):
             if k in st and st[k] != want:
                 print("Warning: resuming with {}={} but the checkpoint was written with {}".format(k, want, st[k]))
         losses, val_losses, best, start_epoch = st["losses"], st["val_losses"], st["best"], st["epoch"] + 1
@@ -320,10 +324,12 @@ def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset
             if log_every and step % log_every == 0:
                 val = float(loss)                      # the host synchronises here anyway: check the sweeps' error words
                 hipops.lstm_assert_no_timeouts()       # (until then the guarded Adam has skipped every invalid update)
-                if max_grad_norm is None:
-                    print("Step {}/{}. Loss: {:>4f}".format(step, n_steps, val))
-                else:
-                    print("Step {}/{}. Loss: {:>4f} Grad norm: {:>4f}".format(step, n_steps, val, float(trainer.last_grad_norm)))
+                line = "Step {}/{}. Loss: {:>4f}".format(step, n_steps, val)
+                if max_grad_norm is not None:
+                    line += " Grad norm: {:>4f}".format(float(trainer.last_grad_norm))
+                if trainer.entropy_weight > 0:
+                    line += " Entropy: {:>4f}".format(float(trainer.last_entropy.mean()))
+                print(line)
         losses.append(float(acc) / max(step, 1))
         hipops.lstm_assert_no_timeouts()          # .. and before anything of this epoch is written to disk
         streams.release()                         # the host has synchronised: nothing of the last step needs keeping alive
@@ -360,7 +366,7 @@ def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset
                     "drop_calls": model.encoder._drop_calls, "dropout_seed": model.encoder.dropout_seed,
                     "lr": lr, "lam": lam, "num_samples": num_samples, "reward_baseline": reward_baseline,
                     "reward_unit": reward_unit, "max_grad_norm": max_grad_norm, "accumulate_steps": accumulate_steps,
-                    "score_function": score_function, "max_hyp_len": max_hyp_len}, ckpt)
+                    "score_function": score_function, "max_hyp_len": max_hyp_len, "entropy_weight": trainer.entropy_weight}, ckpt)
     return losses, val_losses
 
 

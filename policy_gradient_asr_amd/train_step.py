@@ -438,12 +438,12 @@ class PolicyGradientTrainer(DataParallelStep):
     ``step_accumulated(micro_batches, utt_ids=None)`` is one optimizer step over several such batches (DataParallelStep): every
     micro-batch samples with the same offset ``nstep + 1`` and distinct ids -- by default ``default_utt_ids``, micro-batch j a contiguous
     slice of the global batch --, and ``last_stats`` / ``last_sample_rewards`` hold the micro-batches' statistics concatenated in call
-    order (real rows only), and so does ``last_sequence_scored``."""
+    order (real rows only), and so do ``last_sequence_scored`` and ``last_entropy``."""
 
     def __init__(self, model, lr=5e-4, lam=1.0, seed=0, blank=0, world_size=1, process_group=None, rank=0,
                  reward_decoder="greedy", beam_size=16, precision=None, reward_mode="utterance", num_samples=1,
                  reward_baseline="hypothesis", reward_unit="char", word_delimiter=None, max_grad_norm=None,
-                 score_function="path", max_hyp_len=None):
+                 score_function="path", max_hyp_len=None, entropy_weight=0.0):
         """reward_mode: "utterance" (default) -- one reward R = -ED / |y| per utterance, the sum of the reference's per-step rewards
         (policy_grad.py:10-15) up to a constant the baseline removes; "per_step" -- the per-step rewards themselves, as rewards-to-go
         per frame against the greedy path's reward-to-go at the same frame (loss.PGCTCLossFn; greedy baseline only).
@@ -465,7 +465,12 @@ class PolicyGradientTrainer(DataParallelStep):
         variance (loss.PGCTCLossFn; any num_samples, baseline, reward_decoder and reward_unit; not with reward_mode="per_step").
         max_hyp_len ("sequence" only): hypotheses of more tokens keep the path-level term; None = min(T, MAX_HYP_LEN).  It bounds the
         hypothesis-lattice workspace, 2 * K*B*T * roundup64(2*Lh+1) * 4 bytes.  ``last_sequence_scored``: (num_samples, B) bool on the
-        device, which samples took the sequence term in the last step (None with "path"); reading it synchronises."""
+        device, which samples took the sequence term in the last step (None with "path"); reading it synchronises.
+        entropy_weight: beta >= 0 (default 0: off, the step as it was), entropy regularisation of the frame policy against collapse:
+        the loss gains -beta / global_batch times every utterance's MEAN frame entropy (nats), so beta is in loss units per nat per
+        frame and does not grow with T (loss.PGCTCLossFn; with every other setting, reward_mode="per_step" included).
+        ``last_entropy``: (B,) mean frame entropy of the last step's real utterances, on the device (None with weight 0); nothing
+        synchronises until it is read."""
         super().__init__(model, lr=lr, world_size=world_size, process_group=process_group, precision=precision,
                          max_grad_norm=max_grad_norm)
         if reward_decoder not in ("greedy", "beam"):
@@ -479,8 +484,10 @@ class PolicyGradientTrainer(DataParallelStep):
         self.num_samples, self.reward_baseline = num_samples, reward_baseline
         self.reward_unit, self.word_delimiter = reward_unit, word_delimiter
         self.score_function, self.max_hyp_len = score_function, max_hyp_len
+        self.entropy_weight = entropy_weight
         opt = self._checked_options()
-        self.num_samples, self.max_hyp_len = opt.num_samples, opt.max_hyp_len
+        self.num_samples, self.max_hyp_len, self.entropy_weight = opt.num_samples, opt.max_hyp_len, opt.entropy_weight
+        self.last_entropy = None
         self.word_delimiter = None if word_delimiter is None else int(word_delimiter)
         self.last_sequence_scored = None
         self.lam = lam
@@ -521,7 +528,7 @@ class PolicyGradientTrainer(DataParallelStep):
         vocab = getattr(getattr(self.model, "head", None), "out_features", None)
         opt = PGOptions(blank=self.blank, per_step=self.reward_mode == "per_step", num_samples=self.num_samples,
                         baseline=self.reward_baseline, reward_unit=self.reward_unit, word_delimiter=self.word_delimiter,
-                        score_function=self.score_function, max_hyp_len=self.max_hyp_len)
+                        score_function=self.score_function, max_hyp_len=self.max_hyp_len, entropy_weight=self.entropy_weight)
         return check_options(opt, vocab=vocab, frames=frames, symbols=symbols)
 
     def _check_limits(self, x, targets):
@@ -625,16 +632,19 @@ class PolicyGradientTrainer(DataParallelStep):
                                           per_step=self.reward_mode == "per_step", num_samples=self.num_samples,
                                           baseline=self.reward_baseline, reward_unit=self.reward_unit,
                                           word_delimiter=self.word_delimiter, sample_ids=sample_ids,
-                                          score_function=self.score_function, max_hyp_len=self.max_hyp_len)
+                                          score_function=self.score_function, max_hyp_len=self.max_hyp_len,
+                                          entropy_weight=self.entropy_weight)
         scored = PGCTCLossFn.last_sequence_scored                # (K,B) bool, None with score_function="path"
         self.last_sequence_scored = scored[:, :real_b] if (padded and scored is not None) else scored
+        ent = PGCTCLossFn.last_entropy                           # (B,) mean frame entropy, None with entropy_weight = 0
+        self.last_entropy = ent[:real_b] if (padded and ent is not None) else ent
         R_all = R_s if R_s.dim() == 2 else R_s.view(1, -1)       # (K,B): every sample's reward
         if R_s.dim() == 2:
             R_s = R_s.mean(dim=0)
         self.last_sample_rewards = R_all[:, :real_b] if padded else R_all
         self.last_stats = (nll[:real_b], R_s[:real_b], R_g[:real_b]) if padded else (nll, R_s, R_g)
         if self._micro is not None and self._micro.count > 1:
-            self._micro_stats.append((self.last_stats, self.last_sample_rewards, self.last_sequence_scored))
+            self._micro_stats.append((self.last_stats, self.last_sample_rewards, self.last_sequence_scored, self.last_entropy))
         return loss
 
     def _sample_addressing(self, real_b, padded_b, device):
@@ -667,10 +677,12 @@ class PolicyGradientTrainer(DataParallelStep):
             loss = super()._accumulate(micro_batches, utt_ids, hold_last=hold_last)
             if len(self._micro_stats) > 1:
                 # the micro-batches' statistics in call order, real rows only
-                self.last_stats = tuple(torch.cat([st[i] for st, _, _ in self._micro_stats]) for i in range(3))
-                self.last_sample_rewards = torch.cat([r for _, r, _ in self._micro_stats], dim=1)
+                self.last_stats = tuple(torch.cat([st[i] for st, _, _, _ in self._micro_stats]) for i in range(3))
+                self.last_sample_rewards = torch.cat([r for _, r, _, _ in self._micro_stats], dim=1)
                 if self.score_function == "sequence":
-                    self.last_sequence_scored = torch.cat([q for _, _, q in self._micro_stats], dim=1)
+                    self.last_sequence_scored = torch.cat([q for _, _, q, _ in self._micro_stats], dim=1)
+                if self.entropy_weight > 0:
+                    self.last_entropy = torch.cat([e for _, _, _, e in self._micro_stats])
         finally:
             self._micro_stats = []
         return loss
