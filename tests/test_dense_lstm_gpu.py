@@ -7,6 +7,7 @@ import pytest
 import torch
 
 from oracle import model_ref
+from pg_harness import rel_err
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -15,11 +16,6 @@ DEV = "cuda:0"
 def _lib_load():
     from policy_gradient_asr_amd import _lib
     return _lib.load()
-
-
-def rel_err(a, b):
-    a = np.asarray(a, dtype=np.float64); b = np.asarray(b, dtype=np.float64)
-    return np.abs(a - b).max() / (np.abs(b).max() + 1e-30)
 
 
 @pytest.mark.parametrize("tA,tB,M,N,K", [

@@ -1,7 +1,7 @@
 """Entropy regularisation of the frame policy (entropy_weight) on a GPU-less host: the new entry points are exported and bound with
 the header's argument counts, the ABI stays 7, the C entries reject what they cannot take before touching a pointer, the host layer
 checks the weight where the caller can read the reason and takes it with every other option, and the fp64 statement the GPU tests
-are held to (tests/entropy_ref.py) is the derivative autograd takes."""
+are held to (oracle/pg_ref.py) is the derivative autograd takes."""
 import ctypes
 import os
 import re
@@ -9,7 +9,7 @@ import re
 import numpy as np
 import pytest
 
-import entropy_ref
+from oracle import pg_ref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "pgasr_hip.h")
@@ -128,7 +128,7 @@ def test_trainer_checks_the_weight_and_takes_it_with_every_mode():
 
 
 def test_the_fp64_statement_is_the_derivative_autograd_takes():
-    """entropy_ref against torch autograd in fp64 on ragged lengths (0 and T included), a row with two -inf entries and a one-hot
+    """pg_ref's entropy term against torch autograd in fp64 on ragged lengths (0 and T included), a row with two -inf entries and a one-hot
     row: value, gradient, zero rows beyond T_b, rows that sum to 0."""
     import torch
     T, B, V, beta, inv_gb = 9, 4, 6, 2.0, 0.25
@@ -146,12 +146,12 @@ def test_the_fp64_statement_is_the_derivative_autograd_takes():
     term = -(beta * inv_gb * ((H * mask).sum(0) / n)).sum()
     term.backward()
     lpn = lp.detach().numpy()
-    mean, scale = entropy_ref.entropy_stats(lpn, in_len, beta, inv_gb)
+    mean, scale = pg_ref.entropy_stats(lpn, in_len, beta, inv_gb)
     np.testing.assert_allclose(mean, ((H * mask).sum(0) / n).detach().numpy(), rtol=1e-14, atol=1e-15)
     np.testing.assert_allclose(scale, beta * inv_gb / np.maximum(in_len, 1), rtol=1e-15)
-    assert mean[1] == 0.0 and entropy_ref.row_entropy(lpn)[2, 2] == 0.0
-    assert abs(entropy_ref.entropy_loss(lpn, in_len, beta, inv_gb) - float(term.detach())) < 1e-14
-    want = entropy_ref.entropy_grad(lpn, in_len, scale)
+    assert mean[1] == 0.0 and pg_ref.row_entropy(lpn)[2, 2] == 0.0
+    assert abs(pg_ref.entropy_loss(lpn, in_len, beta, inv_gb) - float(term.detach())) < 1e-14
+    want = pg_ref.entropy_grad(lpn, in_len, scale)
     got = torch.nan_to_num(zz.grad, nan=0.0).numpy()          # autograd leaves nan at the -inf logits themselves
     finite = np.isfinite(z.numpy())
     np.testing.assert_allclose(want[finite], got[finite], rtol=1e-12, atol=1e-15)
@@ -160,5 +160,5 @@ def test_the_fp64_statement_is_the_derivative_autograd_takes():
     assert np.abs(want.sum(axis=2)).max() < 1e-15
     # uniform rows: H = ln V, no gradient
     u = np.full((3, 2, 5), -np.log(5.0))
-    np.testing.assert_allclose(entropy_ref.row_entropy(u), np.log(5.0), rtol=1e-15)
-    assert np.abs(entropy_ref.entropy_grad(u, [3, 3], [1.0, 1.0])).max() < 1e-15
+    np.testing.assert_allclose(pg_ref.row_entropy(u), np.log(5.0), rtol=1e-15)
+    assert np.abs(pg_ref.entropy_grad(u, [3, 3], [1.0, 1.0])).max() < 1e-15

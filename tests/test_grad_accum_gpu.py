@@ -5,32 +5,11 @@ import numpy as np
 import pytest
 import torch
 
-from oracle import decode_ref
-from test_train_step_gpu import _make
+from oracle import pg_ref
+from pg_harness import (ACC_F as F, ACC_L as L, ACC_T as T, ACC_V as V, DEV, _batch, _lens, _rows, _slices, _trainer, make_batch,
+                        rel_err, tiny_corpus)
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-F, T, V, L = 80, 60, 29, 6
-
-
-def rel_err(a, b):
-    a = np.asarray(a, dtype=np.float64); b = np.asarray(b, dtype=np.float64)
-    return np.abs(a - b).max() / (np.abs(b).max() + 1e-30)
-
-
-def id_uniforms(T_, ids, K, seed, offset, stride):
-    """u[k,t,b]: Philox word 0 of counter (t*stride + ids[b], offset, 0, k), 24 high bits * 2^-24."""
-    ids = np.asarray(ids, dtype=np.uint64)
-    t, i = np.meshgrid(np.arange(T_, dtype=np.uint64), ids, indexing="ij")
-    c0 = ((t * np.uint64(stride) + i) & np.uint64(0xFFFFFFFF)).astype(np.uint32).ravel()
-    c1 = np.full(c0.size, offset & 0xFFFFFFFF, dtype=np.uint32)
-    z = np.zeros(c0.size, dtype=np.uint32)
-    u = np.empty((K, T_, ids.size))
-    for k in range(K):
-        x0, _, _, _ = decode_ref.philox4x32_10(c0, c1, z, np.full(c0.size, k, dtype=np.uint32), seed & 0xFFFFFFFF,
-                                               (seed >> 32) & 0xFFFFFFFF)
-        u[k] = ((x0 >> np.uint32(8)).astype(np.float64) * (1.0 / 16777216.0)).reshape(T_, ids.size)
-    return u
 
 
 @pytest.mark.parametrize("V_", [29, 64])
@@ -72,11 +51,7 @@ def test_id_samplers_vs_philox_oracle(V_):
         assert torch.equal(hipops.frame_sample_multi(x, K, seed=seed, offset=offset, batch_stride=5, utt_ids=oid)[1], oldk)
     assert not torch.equal(old1[:, 5:], s1w[:, 5:])            # .. which is another domain than the ids 5 .. 7
     # the oracle's Philox on counters t * stride + id
-    lg = xp.double().cpu().numpy()
-    e = np.exp(lg - lg.max(axis=2, keepdims=True))
-    cdf = np.cumsum(e, axis=2) / e.sum(axis=2, keepdims=True)
-    u = id_uniforms(T_, perm, K, seed, offset, B)
-    want = np.minimum((cdf[None] <= u[..., None]).sum(axis=3), V_ - 1)
+    want, cdf, u = pg_ref.sample_paths(xp.double().cpu().numpy(), K, seed, offset, ids=perm, stride=B)
     got = s_ids.cpu().numpy()
     bad = got != want
     near = (np.abs(cdf[None] - u[..., None]) < 1e-6).any(axis=3)
@@ -91,38 +66,6 @@ def test_id_samplers_vs_philox_oracle(V_):
 
 
 # ---- the accumulated step against the whole batch, through the real trainer ----
-def _lens(B):
-    return [T - (3 * b) % 17 for b in range(B)], [max(1, L - b % 4) for b in range(B)]
-
-
-def _batch(B, seed=8):
-    lens, tlens = _lens(B)
-    return tuple(v.to(DEV) for v in _make(B, F, T, V, L, lens, tlens, seed)), lens
-
-
-def _trainer(precision="f32", train=False, **kw):
-    from policy_gradient_asr_amd.model import Seq2Seq, weights
-    from policy_gradient_asr_amd.train_step import PolicyGradientTrainer
-    torch.manual_seed(0)
-    m = Seq2Seq(V, n_feats=F); m.apply(weights); m = m.to(DEV)
-    m = m.train() if train else m.eval()
-    kw.setdefault("seed", 4)
-    return PolicyGradientTrainer(m, lam=1.0, precision=precision, **kw)
-
-
-def _rows(batch, idx):
-    idx = torch.as_tensor(idx, device=DEV)
-    return tuple(t.index_select(0, idx).contiguous() for t in batch)
-
-
-def _slices(sizes):
-    out, o = [], 0
-    for n in sizes:
-        out.append(list(range(o, o + n)))
-        o += n
-    return out
-
-
 def _balanced_parts(B):
     from policy_gradient_asr_amd.train_step import balance_by_frames
     return balance_by_frames(_lens(B)[0], 2)
@@ -216,7 +159,7 @@ def test_one_optimizer_step_and_one_clip():
 def test_peak_memory_does_not_grow_with_the_number_of_micro_batches():
     T_ = 200
     lens, tlens = [T_ - (3 * b) % 17 for b in range(64)], [max(1, L - b % 4) for b in range(64)]
-    batch = tuple(v.to(DEV) for v in _make(64, F, T_, V, L, lens, tlens, 8))
+    batch = tuple(v.to(DEV) for v in make_batch(64, F, T_, V, L, lens, tlens, 8))
     mbs = [_rows(batch, p) for p in _slices((16,) * 4)]
     one_mb = sum(t.numel() * t.element_size() for t in mbs[0])
     tr = _trainer(lr=1e-4)
@@ -275,13 +218,8 @@ def test_default_path_is_unchanged(B):
 
 
 def test_model_train_accumulate_steps(tmp_path, capsys):
-    from policy_gradient_asr_amd.data import SyntheticSpeech
     from policy_gradient_asr_amd.model import train
-    corpus = tmp_path / "corpus"; out = tmp_path / "run"
-    corpus.mkdir()
-    (corpus / "alphabet.txt").write_text("a\nb\nc\nd\n \n")
-    char2ind = {"<pad>": 0, "a": 1, "b": 2, "c": 3, "d": 4, " ": 5}
-    ds = SyntheticSpeech(48, char2ind, n_feats=20, seed=1)       # 3 loader batches of 16 per epoch: groups of 2 and 1
+    corpus, out, ds = tiny_corpus(tmp_path, 48)                  # 3 loader batches of 16 per epoch: groups of 2 and 1
     kw = dict(train_dataset=ds, n_feats=20, lam=0.0, lr=3e-3, log_every=0)
     l1, _ = train(str(corpus), str(out), 2, 16, 0, accumulate_steps=2, **kw)
     st = torch.load(out / "checkpoint_last.pth", map_location="cpu")

@@ -11,6 +11,7 @@ import pytest
 import torch
 
 from policy_gradient_asr_amd.train_step import FLAG_PAD, PolicyGradientTrainer
+from pg_harness import make_batch
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -173,24 +174,11 @@ def test_clipped_adam_skips_a_non_finite_gradient():
 
 
 # ---- the trainer ----
-def _make(B, F, T, V, L, lens, tlens, seed):
-    g = torch.Generator().manual_seed(seed)
-    x = torch.randn(B, F, T, generator=g)
-    fmask = torch.zeros(B, T)
-    for b, n in enumerate(lens):
-        fmask[b, :n] = 1; x[b, :, n:] = 0
-    targets = torch.randint(1, V, (B, L), generator=g)
-    tmask = torch.zeros(B, L, dtype=torch.int64)
-    for b, n in enumerate(tlens):
-        tmask[b, :n] = 1; targets[b, n:] = 0
-    return x, targets, fmask, tmask
-
-
 def _trainer_and_batch(max_grad_norm, precision, cls=PolicyGradientTrainer, B=20, T=60):
     """The mid-size train-mode trainer of tests/test_train_step_gpu.py (_trainer_and_batch), with a precision and a bound."""
     from policy_gradient_asr_amd.model import Seq2Seq, weights
     F, V, L = 80, 29, 6
-    x, targets, fmask, tmask = _make(B, F, T, V, L, [T] * (B // 2) + [T - 19] * (B - B // 2), [6] * B, 3)
+    x, targets, fmask, tmask = make_batch(B, F, T, V, L, [T] * (B // 2) + [T - 19] * (B - B // 2), [6] * B, 3)
     torch.manual_seed(0)
     m = Seq2Seq(V, n_feats=F); m.apply(weights); m = m.to(DEV).train()
     tr = cls(m, lr=1e-3, lam=1.0, seed=5, precision=precision, max_grad_norm=max_grad_norm)

@@ -5,38 +5,11 @@ import numpy as np
 import pytest
 import torch
 
-from oracle import ctc_ref, decode_ref, model_ref
-from test_grad_accum_gpu import _batch, _rows, _slices, _trainer
-from test_multisample_pg_gpu import _lattice_case, baselines, multi_sample_paths, rel_err
-from test_train_step_gpu import _make
-from test_word_reward_gpu import D, _spaced_batch, split_words
+from oracle import ctc_ref
+from pg_harness import (D, DEV, _batch, _rows, _slices, _trainer, fused_grad_ref, lattice_case, rel_err, sampled_case,
+                        shards_vs_whole, tiny_corpus, trainer_step_vs_oracle)
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-
-
-def _sampled_case(T, B, V, K, seed=44, philox=11, offset=4, in_len=None, blank_path=None):
-    """_lattice_case's logits and targets, K paths per utterance from the device sampler, their collapsed hypotheses.
-    blank_path = (k, b): that sample is replaced by the all-blank path (an empty hypothesis)."""
-    from policy_gradient_asr_amd import hipops
-    logits, targets, il, tg_len = _lattice_case(T, B, V, 14, seed)
-    if in_len is not None:
-        il = torch.tensor(in_len, dtype=torch.int32)
-    lp = hipops.log_softmax_rows(logits.float().to(DEV))
-    _, paths = hipops.frame_sample_multi(lp, K, seed=philox, offset=offset)
-    if blank_path is not None:
-        paths[blank_path[0], :, blank_path[1]] = 0
-    ild = il.to(DEV)
-    tokens, tok_len = hipops.ctc_collapse(paths, ild)
-    torch.cuda.synchronize()
-    # the device's collapse is the oracle's
-    pn, tn, ln = paths.cpu().numpy(), tokens.cpu().numpy(), tok_len.cpu().numpy()
-    for k in range(K):
-        for b in range(B):
-            want = decode_ref.collapse_path(pn[k, :int(il[b]), b])
-            assert list(tn[k, b, :ln[k, b]]) == list(want)
-    return dict(lp=lp, lg=lp.double().cpu().numpy(), targets=targets, in_len=il, tg_len=tg_len, paths=paths, tokens=tokens,
-                tok_len=tok_len, T=T, B=B, V=V, K=K)
 
 
 def _hyp_nll_ref(c):
@@ -61,7 +34,7 @@ def test_hypothesis_nll_vs_fp64(name, T, B, V, K):
     in_len = [T - 37 * (b % 4) for b in range(B)]
     if name != "long":
         in_len[4] = 0
-    c = _sampled_case(T, B, V, K, in_len=in_len, blank_path=(1, 2) if name != "long" else None)
+    c = sampled_case(T, B, V, K, in_len=in_len, blank_path=(1, 2) if name != "long" else None)
     Lh = hipops.hyp_len_cap(T)
     ln = c["tok_len"].cpu().numpy()
     if name == "long":
@@ -93,28 +66,13 @@ def _fused(c, coef, scale, Lh):
     return nll, hyp_nll, grad
 
 
-def _fused_ref(c, coef, scale, Lh):
-    """fp64: the target part, then per sample the hypothesis' CTC gradient (sequence-scored) or the path term."""
-    lg, il = c["lg"], c["in_len"].numpy()
-    _, g_ctc = ctc_ref.ctc_loss_and_grad(lg, c["targets"].numpy(), il, c["tg_len"].numpy())
-    want = g_ctc * scale.double().numpy()[None, :, None]
-    tn, ln, pn = c["tokens"].cpu().numpy(), c["tok_len"].cpu().numpy(), c["paths"].cpu().numpy()
-    for k in range(c["K"]):
-        seq = ln[k] <= Lh
-        ck = coef[k].double().numpy()
-        _, g_k = ctc_ref.ctc_loss_and_grad(lg, tn[k], il, np.where(seq, ln[k], 0))
-        want = want + g_k * (ck * seq)[None, :, None]
-        want = want + decode_ref.reinforce_grad(lg, pn[k], ck * ~seq, il)
-    return want
-
-
 @pytest.mark.parametrize("cap", ["all", "median", "zero"])
 @pytest.mark.parametrize("K", [1, 4, 16])
 def test_fused_gradient_vs_fp64(K, cap):
     """Random pg_coef of both signs; Lh = T (all sequence-scored), the median collapsed length (mixed) and 0 (only the empty
     hypothesis).  Max-norm relative error < 1e-5, test_multi_path_ctc_grad_vs_fp64's bound."""
     T, B, V = 160, 6, 29
-    c = _sampled_case(T, B, V, K, blank_path=(0, 1))
+    c = sampled_case(T, B, V, K, blank_path=(0, 1))
     ln = c["tok_len"].cpu().numpy()
     Lh = {"all": T, "median": int(np.median(ln)), "zero": 0}[cap]
     share = float((ln <= Lh).mean())
@@ -130,7 +88,7 @@ def test_fused_gradient_vs_fp64(K, cap):
     assert (coef > 0).any() and (coef < 0).any()
     scale = torch.rand(B, generator=g) + 0.5
     _, _, grad = _fused(c, coef, scale, Lh)
-    err = rel_err(grad.cpu().numpy(), _fused_ref(c, coef, scale, Lh))
+    err = rel_err(grad.cpu().numpy(), fused_grad_ref(c, coef, scale, Lh))
     print(f"[fused grad] K={K} cap={cap}: rel err {err:.2e}")
     assert err < 1e-5
     _, _, again = _fused(c, coef, scale, Lh)
@@ -142,7 +100,7 @@ def test_fused_gradient_is_the_existing_kernels_on_an_expanded_batch():
     fp64, plus the target part."""
     from policy_gradient_asr_amd import hipops
     T, B, V, K = 160, 6, 29, 4
-    c = _sampled_case(T, B, V, K, blank_path=(0, 1))
+    c = sampled_case(T, B, V, K, blank_path=(0, 1))
     g = torch.Generator().manual_seed(9)
     coef = torch.randn(K, B, generator=g) * 0.1
     scale = torch.rand(B, generator=g) + 0.5
@@ -166,7 +124,7 @@ def test_loss_value_vs_fp64_and_reproducible():
     value): < 1e-6 relative; the same with the hypothesis nll from the fp64 lattice: the nll's own bar, 1e-5.  Mixed cap."""
     from policy_gradient_asr_amd import hipops
     T, B, V, K = 160, 6, 29, 4
-    c = _sampled_case(T, B, V, K, blank_path=(0, 1))
+    c = sampled_case(T, B, V, K, blank_path=(0, 1))
     ln = c["tok_len"].cpu().numpy()
     Lh = int(np.median(ln))
     g = torch.Generator().manual_seed(2)
@@ -210,90 +168,16 @@ def _seq_step_vs_oracle(reward_baseline, beam, K, word=False, seed=51):
     """One lambda = 1 trainer step (f32 mode, score_function="sequence") against the torch-CPU model in FP64 on the same weights, as
     test_multisample_pg_gpu._multi_step_vs_oracle: rewards exact (rtol 1e-6), loss within 1e-5, every parameter gradient within
     1e-4 (max norm).  The oracle collapses its own sampled paths and takes the hypotheses' gradients from ctc_ref."""
-    from policy_gradient_asr_amd import hipops
-    from policy_gradient_asr_amd.model import Seq2Seq
-    from policy_gradient_asr_amd.train_step import PolicyGradientTrainer
-    B, F, T, V = 4, 80, 120, 29
-    if word:
-        L, lens, tlens = 16, [120, 90, 120, 64], [16, 11, 14, 7]
-        x, targets, fmask, tmask = _spaced_batch(B, F, T, V, L, lens, tlens, seed)
-    else:
-        L, lens, tlens = 12, [120, 90, 120, 64], [12, 9, 12, 5]
-        x, targets, fmask, tmask = _make(B, F, T, V, L, lens, tlens, seed)
-    p = model_ref.init_params(n_feats=F, vocab=V, seed=seed + 1)
-    pr = {k: v.double().requires_grad_(True) for k, v in p.items()}
-    m = Seq2Seq(V, n_feats=F)
-    m.load_state_dict({("encoder." + k if not k.startswith("head.") else k): v for k, v in p.items()}, strict=True)
-    m = m.to(DEV).eval()
-    kw = dict(reward_unit="word", word_delimiter=D) if word else {}
-    tr = PolicyGradientTrainer(m, lam=1.0, seed=3, reward_decoder="beam" if beam else "greedy", beam_size=beam or 16,
-                               precision="f32", num_samples=K, reward_baseline=reward_baseline, score_function="sequence", **kw)
-    loss = tr.compute_gradients(x.to(DEV), targets.to(DEV), fmask.to(DEV), tmask.to(DEV))
-    nll, R_s, R_b = tr.last_stats
-    R_all = tr.last_sample_rewards
-    torch.cuda.synchronize()
-    hipops.lstm_assert_no_timeouts()
-    assert R_s.shape == (B,) and R_b.shape == (B,) and R_all.shape == (K, B)
+    unit = dict(reward_unit="word", word_delimiter=D) if word else {}
+    r = trainer_step_vs_oracle(dict(reward_decoder="beam" if beam else "greedy", beam_size=beam or 16, num_samples=K,
+                                    reward_baseline=reward_baseline, score_function="sequence", **unit),
+                               dict(num_samples=K, baseline=reward_baseline, beam=beam, score_function="sequence", **unit),
+                               word=word, seed=seed, label=f"[seq step] K={K} {reward_baseline} beam={beam} word={word}")
+    tr = r.trainer
+    assert all(s_.shape == (4,) for s_ in tr.last_stats) and tr.last_sample_rewards.shape == (K, 4)
     scored = tr.last_sequence_scored
-    assert scored.shape == (K, B) and scored.dtype == torch.bool and bool(scored.all())       # T <= 1023, no cap
-
-    enc = model_ref.encoder_forward_torch(pr, x.double(), fmask, packed=True)
-    logits_ref = model_ref.head_logits_torch(pr, enc)
-    lg = logits_ref.detach().numpy()
-    il, tl_, tg = np.array(lens), np.array(tlens), targets.numpy()
-    paths, _, _ = multi_sample_paths(lg, K, seed=3, offset=1)          # the trainer's first step samples with offset 1
-    lp64 = ctc_ref.log_softmax(lg, axis=2)
-    Lf = np.maximum(tl_, 1).astype(np.float64)
-
-    def reward(y, hyp, b):
-        if word:
-            wy = split_words(y)
-            return -decode_ref.edit_dist(wy, split_words(hyp))[0] / len(wy)
-        return -decode_ref.edit_dist(y, hyp)[0] / Lf[b]
-
-    R = np.zeros((K, B)); R_hyp = np.zeros(B)
-    hyps = [[None] * B for _ in range(K)]
-    for b in range(B):
-        y = [int(t) for t in tg[b][:tlens[b]]]
-        for k in range(K):
-            hyps[k][b] = [int(t) for t in decode_ref.collapse_path(paths[k, :lens[b], b])]
-            R[k, b] = reward(y, hyps[k][b], b)
-        if reward_baseline == "hypothesis":
-            if beam:
-                hyp, _ = decode_ref.prefix_beam_search(np.exp(lp64[:lens[b], b]), beam_size=beam)
-                hyp = [h for i, h in enumerate(hyp) if i == 0 or h != hyp[i - 1]]
-            else:
-                hyp = decode_ref.collapse_path(np.argmax(lg[:lens[b], b], axis=1))
-            R_hyp[b] = reward(y, [int(t) for t in hyp], b)
-    bk = baselines(R, R_hyp, reward_baseline)
-    coef = (R - bk) / (B * K)
-    assert np.abs(coef).max() > 0
-    nll_o, g_ctc = ctc_ref.ctc_loss_and_grad(lg, tg, il, tl_)
-    scale = 1.0 / (Lf * B)
-    w_loss = (nll_o * scale).sum()
-    w_grad = g_ctc * scale[None, :, None]
-    for k in range(K):
-        hl = np.array([len(h) for h in hyps[k]])
-        ht = np.zeros((B, T), dtype=np.int64)
-        for b in range(B):
-            ht[b, :hl[b]] = hyps[k][b]
-        nll_h, g_h = ctc_ref.ctc_loss_and_grad(lg, ht, il, hl)
-        w_loss += (coef[k] * nll_h).sum()
-        w_grad = w_grad + g_h * coef[k][None, :, None]
-    np.testing.assert_allclose(R_all.cpu().numpy(), R, rtol=1e-6)
-    np.testing.assert_allclose(R_s.cpu().numpy(), R.mean(axis=0), rtol=1e-6, atol=1e-7)
-    np.testing.assert_allclose(R_b.cpu().numpy(), bk.mean(axis=0), rtol=1e-6, atol=1e-7)
-    lerr = abs(float(loss) - w_loss) / abs(w_loss)
-    logits_ref.backward(torch.from_numpy(w_grad))
-    errs = {}
-    for k, v in m.named_parameters():
-        rk = k[len("encoder."):] if k.startswith("encoder.") else k
-        errs[rk] = rel_err(v.grad.cpu(), pr[rk].grad)
-    worst = max(errs, key=errs.get)
-    print(f"[seq step] K={K} {reward_baseline} beam={beam} word={word}: loss rel err {lerr:.2e}; "
-          f"worst parameter gradient {worst} {errs[worst]:.2e}")
-    assert lerr < 1e-5, (float(loss), w_loss)
-    assert errs[worst] < 1e-4, (worst, errs[worst])
+    assert scored.shape == (K, 4) and scored.dtype == torch.bool and bool(scored.all())       # T <= 1023, no cap
+    assert r.oracle.scored.all() and np.abs(r.oracle.coef).max() > 0
 
 
 @pytest.mark.parametrize("baseline,beam,K,word", [("hypothesis", 0, 4, False), ("leave_one_out", 0, 4, False),
@@ -309,39 +193,20 @@ def test_sequence_shards_sum_to_the_whole_batch(max_hyp_len):
     its max, as test_leave_one_out_shards_sum_to_the_whole_batch; with a cap that splits the samples too."""
     from policy_gradient_asr_amd.loss import PGCTCLossFn, pg_ctc_loss
     T, B, V, L, K = 150, 8, 29, 12, 4
-    logits, targets, in_len, tg_len = _lattice_case(T, B, V, L, 77)
-    lg = logits.float().to(DEV)
-    tg, il, tl = targets.to(DEV), in_len.to(DEV), tg_len.to(DEV)
     kw = dict(lam=1.0, seed=11, offset=4, num_samples=K, baseline="leave_one_out", score_function="sequence", max_hyp_len=max_hyp_len)
-    whole = lg.clone().requires_grad_(True)
-    loss, nll, R_s, R_b = pg_ctc_loss(whole, il, tg, tl, **kw)
-    scored = PGCTCLossFn.last_sequence_scored
-    loss.backward()
+    r = shards_vs_whole(kw, lattice_case(T, B, V, L, 77), extra=lambda: PGCTCLossFn.last_sequence_scored)
+    scored = r.extra_whole
     assert scored.shape == (K, B)
     if max_hyp_len is None:
         assert bool(scored.all())
     else:
         assert bool(scored.any()) and not bool(scored.all())
-    grads, total, parts = [], 0.0, []
-    for h in range(2):
-        sl = slice(4 * h, 4 * h + 4)
-        part = lg[:, sl].contiguous().requires_grad_(True)
-        l_h, _, Rs_h, _ = pg_ctc_loss(part, il[sl].contiguous(), tg[sl].contiguous(), tl[sl].contiguous(), global_batch=B,
-                                      sample_base=4 * h, **kw)
-        parts.append(PGCTCLossFn.last_sequence_scored)
-        l_h.backward()
-        grads.append(part.grad)
-        total += float(l_h.detach())
-        assert torch.equal(Rs_h, R_s[:, sl])
-    assert torch.equal(torch.cat(parts, dim=1), scored)
-    diff = (torch.cat(grads, dim=1) - whole.grad).abs().max()
-    assert float(diff) <= 1e-6 * float(whole.grad.abs().max()), float(diff)
-    assert abs(total - float(loss)) <= 1e-6 * abs(float(loss))
+    assert torch.equal(torch.cat(r.extra_parts, dim=1), scored)
     # the sequence-level gradient is another estimator than the path-level one, around the same CTC part
-    other = lg.clone().requires_grad_(True)
+    other = r.lg.clone().requires_grad_(True)
     kw_path = {k: v for k, v in kw.items() if k not in ("score_function", "max_hyp_len")}
-    pg_ctc_loss(other, il, tg, tl, **kw_path)[0].backward()
-    assert float((other.grad - whole.grad).abs().max()) > 1e-6 * float(whole.grad.abs().max())
+    pg_ctc_loss(other, r.il, r.tg, r.tl, **kw_path)[0].backward()
+    assert float((other.grad - r.grad).abs().max()) > 1e-6 * float(r.grad.abs().max())
 
 
 @pytest.mark.parametrize("sizes", [(16, 16), (16, 9, 7)])
@@ -376,7 +241,7 @@ def test_sequence_accumulated_step_is_the_whole_batch(sizes):
 def test_default_score_function_is_path_bit_for_bit():
     from policy_gradient_asr_amd.loss import PGCTCLossFn, pg_ctc_loss
     T, B, V, L = 150, 8, 29, 12
-    logits, targets, in_len, tg_len = _lattice_case(T, B, V, L, 78)
+    logits, targets, in_len, tg_len = lattice_case(T, B, V, L, 78)
     lg = logits.float().to(DEV)
     tg, il, tl = targets.to(DEV), in_len.to(DEV), tg_len.to(DEV)
     for extra in ({}, {"num_samples": 4, "baseline": "leave_one_out"}, {"beam": 8}):
@@ -402,13 +267,8 @@ def test_default_score_function_is_path_bit_for_bit():
 
 def test_train_driver_records_score_function(tmp_path, capsys):
     """model.train(score_function, max_hyp_len): trains with them, records them in the checkpoint, warns on a resume with others."""
-    from policy_gradient_asr_amd.data import SyntheticSpeech
     from policy_gradient_asr_amd.model import train
-    corpus = tmp_path / "corpus"; out = tmp_path / "run"
-    corpus.mkdir()
-    (corpus / "alphabet.txt").write_text("a\nb\nc\nd\n \n")
-    char2ind = {"<pad>": 0, "a": 1, "b": 2, "c": 3, "d": 4, " ": 5}
-    ds = SyntheticSpeech(32, char2ind, n_feats=20, seed=1)
+    corpus, out, ds = tiny_corpus(tmp_path)
     common = dict(train_dataset=ds, n_feats=20, lam=1.0, lr=3e-3, log_every=0, num_samples=4, reward_baseline="leave_one_out")
     l1, _ = train(str(corpus), str(out), 2, 16, 0, score_function="sequence", **common)
     assert len(l1) == 2 and all(np.isfinite(l1))

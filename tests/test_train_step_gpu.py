@@ -6,38 +6,10 @@ import numpy as np
 import pytest
 import torch
 
-from oracle import ctc_ref, decode_ref, model_ref
+from oracle import decode_ref, model_ref, pg_ref
+from pg_harness import DEV, load_params, make_batch, param_errs, rel_err
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-
-
-def rel_err(a, b):
-    a = np.asarray(a, dtype=np.float64); b = np.asarray(b, dtype=np.float64)
-    return np.abs(a - b).max() / (np.abs(b).max() + 1e-30)
-
-
-def oracle_objective(logits, in_len, targets, tg_len, lam, seed, offset, paths=None):
-    """float64 restatement of loss.PGCTCLossFn: returns loss, grad, R_s, R_g, paths."""
-    T, B, V = logits.shape
-    nll, g_ctc = ctc_ref.ctc_loss_and_grad(logits, targets, in_len, tg_len)
-    if paths is None:
-        paths, _, _ = decode_ref.sample_paths(logits, seed=seed, offset=offset)
-    greedy = decode_ref.greedy_decode(logits, in_len)
-    Lf = np.maximum(tg_len, 1).astype(np.float64)
-    R_s = np.zeros(B); R_g = np.zeros(B)
-    for b in range(B):
-        y = list(targets[b][:tg_len[b]])
-        R_s[b] = -decode_ref.edit_dist(y, decode_ref.collapse_path(paths[:in_len[b], b]))[0] / Lf[b]
-        R_g[b] = -decode_ref.edit_dist(y, greedy[b])[0] / Lf[b]
-    coef = lam * (R_s - R_g) / B
-    scale = 1.0 / (Lf * B)
-    lp = ctc_ref.log_softmax(logits, axis=2)
-    mask = np.arange(T)[:, None] < in_len[None, :]
-    lps = (np.take_along_axis(lp, paths[..., None], axis=2)[..., 0] * mask).sum(axis=0)
-    loss = (nll * scale).sum() - (coef * lps).sum()
-    grad = g_ctc * scale[None, :, None] + decode_ref.reinforce_grad(logits, paths, coef, in_len)
-    return loss, grad, R_s, R_g, paths
 
 
 @pytest.mark.parametrize("lam", [0.0, 1.0])
@@ -53,25 +25,11 @@ def test_pg_ctc_loss_vs_oracle(lam):
     lg = logits.to(DEV).requires_grad_(True)
     loss, nll, R_s, R_g = pg_ctc_loss(lg, in_len.to(DEV), targets.to(DEV), tg_len.to(DEV), lam=lam, seed=77, offset=5)
     loss.backward()
-    want_loss, want_grad, wRs, wRg, _ = oracle_objective(logits.double().numpy(), in_len.numpy(), targets.numpy(),
-                                                         tg_len.numpy(), lam, 77, 5)
-    np.testing.assert_allclose(R_g.cpu().numpy(), wRg, rtol=1e-6)
-    np.testing.assert_allclose(R_s.cpu().numpy(), wRs, rtol=1e-6)
-    assert abs(float(loss) - want_loss) / abs(want_loss) < 1e-4
-    assert rel_err(lg.grad.cpu(), want_grad) < 1e-3
-
-
-def oracle_step_coefs(logits, in_len, targets, tg_len, lam, paths):
-    """(T,B) per-frame coefficients of the "per_step" reward mode, from the oracle's character-by-character reward-to-go."""
-    T, B, V = logits.shape
-    greedy = np.argmax(logits, axis=2)
-    coef = np.zeros((T, B))
-    for b in range(B):
-        y = list(targets[b][:tg_len[b]])
-        Gs, _, _ = decode_ref.reward_to_go(paths[:in_len[b], b], y)
-        Gg, _, _ = decode_ref.reward_to_go(greedy[:in_len[b], b], y)
-        coef[:in_len[b], b] = lam * (Gs - Gg) / (max(int(tg_len[b]), 1) * B)
-    return coef
+    o = pg_ref.pg_objective(logits.double().numpy(), in_len.numpy(), targets.numpy(), tg_len.numpy(), lam=lam, seed=77, offset=5)
+    np.testing.assert_allclose(R_g.cpu().numpy(), o.R_hyp, rtol=1e-6)
+    np.testing.assert_allclose(R_s.cpu().numpy(), o.R[0], rtol=1e-6)
+    assert abs(float(loss) - o.loss) / abs(o.loss) < 1e-4
+    assert rel_err(lg.grad.cpu(), o.grad) < 1e-3
 
 
 @pytest.mark.parametrize("shape", [(200, 4, 29, 20), (70, 3, 7, 9), (1000, 32, 29, 100)])
@@ -95,8 +53,8 @@ def test_pg_ctc_loss_per_step_rewards_vs_oracle(shape):
     loss, nll, R_s, R_g = pg_ctc_loss(lg, in_len.to(DEV), targets.to(DEV), tg_len.to(DEV), lam=lam, seed=31, offset=2, per_step=True)
     loss.backward()
     ln, il, tn, tl = logits.double().numpy(), in_len.numpy(), targets.numpy(), tg_len.numpy()
-    paths, _, _ = decode_ref.sample_paths(ln, seed=31, offset=2)
-    coef = oracle_step_coefs(ln, il, tn, tl, lam, paths)
+    o = pg_ref.pg_objective(ln, il, tn, tl, lam=lam, seed=31, offset=2, per_step=True)
+    paths, coef = o.paths[0], o.coef
     # the device's coefficients, from the same pieces the loss uses
     lp = hipops.log_softmax_rows(logits.to(DEV))
     greedy_d, sample_d = hipops.frame_argmax_sample(lp, seed=31, offset=2)
@@ -110,16 +68,9 @@ def test_pg_ctc_loss_per_step_rewards_vs_oracle(shape):
     np.testing.assert_allclose(got[0].cpu().numpy(), coef_utt.cpu().numpy(), rtol=1e-6, atol=1e-9)      # frame 0 = the utterance coefficient
     assert float(got.abs().sum()) > 0
     # objective and gradient
-    nll_o, g_ctc = ctc_ref.ctc_loss_and_grad(ln, tn, il, tl)
-    scale = 1.0 / (np.maximum(tl, 1) * B)
-    lpo = ctc_ref.log_softmax(ln, axis=2)
-    picked = np.take_along_axis(lpo, paths[..., None], axis=2)[..., 0]
-    finite = np.isfinite(nll_o)
-    want_loss = (np.where(finite, nll_o, 0.0) * scale).sum() - (coef * picked).sum()
-    want_grad = g_ctc * scale[None, :, None] + decode_ref.reinforce_grad(ln, paths, coef, il)
-    if finite.all():
-        assert abs(float(loss) - want_loss) / abs(want_loss) < 1e-4
-    assert rel_err(lg.grad.cpu(), want_grad) < 1e-3
+    if np.isfinite(o.nll).all():                  # an infeasible target adds 0 to the oracle's loss
+        assert abs(float(loss) - o.loss) / abs(o.loss) < 1e-4
+    assert rel_err(lg.grad.cpu(), o.grad) < 1e-3
     with pytest.raises(ValueError):
         pg_ctc_loss(lg, in_len.to(DEV), targets.to(DEV), tg_len.to(DEV), lam=lam, beam=4, per_step=True)
 
@@ -129,7 +80,7 @@ def test_per_step_reward_mode_trains():
     from policy_gradient_asr_amd.model import Seq2Seq
     from policy_gradient_asr_amd.train_step import PolicyGradientTrainer
     B, F, T, V, L = 4, 80, 200, 29, 20
-    x, targets, fmask, tmask = _make(B, F, T, V, L, [200, 170, 200, 120], [20, 15, 20, 9], 5)
+    x, targets, fmask, tmask = make_batch(B, F, T, V, L, [200, 170, 200, 120], [20, 15, 20, 9], 5)
     grads = {}
     for mode in ("utterance", "per_step"):
         torch.manual_seed(0)
@@ -143,43 +94,28 @@ def test_per_step_reward_mode_trains():
         PolicyGradientTrainer(m, reward_mode="per_step", reward_decoder="beam")
 
 
-def _make(B, F, T, V, L, lens, tlens, seed):
-    g = torch.Generator().manual_seed(seed)
-    x = torch.randn(B, F, T, generator=g)
-    fmask = torch.zeros(B, T)
-    for b, n in enumerate(lens):
-        fmask[b, :n] = 1; x[b, :, n:] = 0
-    targets = torch.randint(1, V, (B, L), generator=g)
-    tmask = torch.zeros(B, L, dtype=torch.int64)
-    for b, n in enumerate(tlens):
-        tmask[b, :n] = 1; targets[b, n:] = 0
-    return x, targets, fmask, tmask
-
-
 def test_ctc_train_step_grads_vs_oracle_plumbing_config():
     """configs[0]: B=4,T=200,F=80,V=29 CTC-only step: loss and every parameter gradient."""
     from policy_gradient_asr_amd.model import Seq2Seq
     from policy_gradient_asr_amd.loss import pg_ctc_loss
     B, F, T, V, L = 4, 80, 200, 29, 20
     lens, tlens = [200, 170, 200, 120], [20, 15, 20, 9]
-    x, targets, fmask, tmask = _make(B, F, T, V, L, lens, tlens, 5)
+    x, targets, fmask, tmask = make_batch(B, F, T, V, L, lens, tlens, 5)
     p = model_ref.init_params(n_feats=F, vocab=V, seed=2)
     pr = {k: v.clone().requires_grad_(True) for k, v in p.items()}
     enc = model_ref.encoder_forward_torch(pr, x, fmask)
     lp = model_ref.head_forward_torch(pr, enc)
     ref = torch.nn.functional.ctc_loss(lp, targets, torch.tensor(lens), torch.tensor(tlens), blank=0, reduction="mean")
     ref.backward()
-    m = Seq2Seq(V, n_feats=F)
-    m.load_state_dict({("encoder." + k if not k.startswith("head.") else k): v for k, v in p.items()}, strict=True)
+    m = load_params(Seq2Seq(V, n_feats=F), p)
     m = m.to(DEV).eval()
     logits, in_len = m.logits(x.to(DEV), fmask.to(DEV))
     loss, nll, _, _ = pg_ctc_loss(logits, in_len, targets.to(torch.int32).to(DEV),
                                   torch.tensor(tlens, dtype=torch.int32, device=DEV), lam=0.0)
     loss.backward()
     assert abs(float(loss) - float(ref)) / abs(float(ref)) < 1e-3
-    for k, v in m.named_parameters():
-        rk = k[len("encoder."):] if k.startswith("encoder.") else k
-        assert rel_err(v.grad.cpu(), pr[rk].grad) < 1e-3, k
+    errs = param_errs(m, {k: v.grad for k, v in pr.items()})
+    assert max(errs.values()) < 1e-3, errs
 
 
 def test_f32_mode_ctc_step_vs_fp64_oracle():
@@ -191,7 +127,7 @@ def test_f32_mode_ctc_step_vs_fp64_oracle():
     from policy_gradient_asr_amd.loss import pg_ctc_loss
     B, F, T, V, L = 4, 80, 200, 29, 20
     lens, tlens = [200, 170, 200, 120], [20, 15, 20, 9]
-    x, targets, fmask, tmask = _make(B, F, T, V, L, lens, tlens, 5)
+    x, targets, fmask, tmask = make_batch(B, F, T, V, L, lens, tlens, 5)
     p = model_ref.init_params(n_feats=F, vocab=V, seed=2)
     pr = {k: v.double().requires_grad_(True) for k, v in p.items()}
     enc = model_ref.encoder_forward_torch(pr, x.double(), fmask)
@@ -200,8 +136,7 @@ def test_f32_mode_ctc_step_vs_fp64_oracle():
     ref.backward()
     res = {}
     for mode in ("f32", "bf16x3"):
-        m = Seq2Seq(V, n_feats=F)
-        m.load_state_dict({("encoder." + k if not k.startswith("head.") else k): v for k, v in p.items()}, strict=True)
+        m = load_params(Seq2Seq(V, n_feats=F), p)
         m = m.to(DEV).eval()
         with hipops.precision(mode):
             logits, in_len = m.logits(x.to(DEV), fmask.to(DEV))
@@ -227,7 +162,7 @@ def test_trainer_precision_modes_and_limits():
     from policy_gradient_asr_amd.model import Seq2Seq, weights
     from policy_gradient_asr_amd.train_step import PolicyGradientTrainer
     B, F, T, V, L = 4, 80, 64, 29, 6
-    x, targets, fmask, tmask = _make(B, F, T, V, L, [64, 50, 64, 33], [6, 5, 6, 3], 2)
+    x, targets, fmask, tmask = make_batch(B, F, T, V, L, [64, 50, 64, 33], [6, 5, 6, 3], 2)
     losses = {}
     for mode in ("bf16x3", "f32"):
         torch.manual_seed(0)
@@ -254,27 +189,25 @@ def test_pg_train_step_grads_vs_oracle_with_shared_paths():
     from policy_gradient_asr_amd.loss import pg_ctc_loss
     B, F, T, V, L = 4, 80, 120, 29, 12
     lens, tlens = [120, 90, 120, 64], [12, 9, 12, 5]
-    x, targets, fmask, tmask = _make(B, F, T, V, L, lens, tlens, 9)
+    x, targets, fmask, tmask = make_batch(B, F, T, V, L, lens, tlens, 9)
     p = model_ref.init_params(n_feats=F, vocab=V, seed=4)
     pr = {k: v.clone().requires_grad_(True) for k, v in p.items()}
     enc = model_ref.encoder_forward_torch(pr, x, fmask)
     logits_ref = model_ref.head_logits_torch(pr, enc)
-    m = Seq2Seq(V, n_feats=F)
-    m.load_state_dict({("encoder." + k if not k.startswith("head.") else k): v for k, v in p.items()}, strict=True)
+    m = load_params(Seq2Seq(V, n_feats=F), p)
     m = m.to(DEV).eval()
     logits, in_len = m.logits(x.to(DEV), fmask.to(DEV))
     loss, nll, R_s, R_g = pg_ctc_loss(logits, in_len, targets.to(torch.int32).to(DEV),
                                       torch.tensor(tlens, dtype=torch.int32, device=DEV), lam=1.0, seed=3, offset=1)
     loss.backward()
-    w_loss, w_grad, wRs, wRg, _ = oracle_objective(logits_ref.detach().double().numpy(), np.array(lens), targets.numpy(),
-                                                   np.array(tlens), 1.0, 3, 1)
-    np.testing.assert_allclose(R_g.cpu().numpy(), wRg, rtol=1e-6)
-    np.testing.assert_allclose(R_s.cpu().numpy(), wRs, rtol=1e-6)
-    assert abs(float(loss) - w_loss) / abs(w_loss) < 1e-3
-    logits_ref.backward(torch.from_numpy(w_grad).float())
-    for k, v in m.named_parameters():
-        rk = k[len("encoder."):] if k.startswith("encoder.") else k
-        assert rel_err(v.grad.cpu(), pr[rk].grad) < 1e-3, k
+    o = pg_ref.pg_objective(logits_ref.detach().double().numpy(), np.array(lens), targets.numpy(), np.array(tlens), lam=1.0, seed=3,
+                            offset=1)
+    np.testing.assert_allclose(R_g.cpu().numpy(), o.R_hyp, rtol=1e-6)
+    np.testing.assert_allclose(R_s.cpu().numpy(), o.R[0], rtol=1e-6)
+    assert abs(float(loss) - o.loss) / abs(o.loss) < 1e-3
+    logits_ref.backward(torch.from_numpy(o.grad).float())
+    errs = param_errs(m, {k: v.grad for k, v in pr.items()})
+    assert max(errs.values()) < 1e-3, errs
 
 
 def test_custom_nll_loss_dropin_vs_reference_golden(golden_dir):
@@ -337,13 +270,12 @@ def _pg_step_vs_oracle(B, F, T, V, L, lens, tlens, seed, beam=0, threads=None, s
     if threads:
         torch.set_num_threads(threads)
     import contextlib
-    x, targets, fmask, tmask = _make(B, F, T, V, L, lens, tlens, seed)
+    x, targets, fmask, tmask = make_batch(B, F, T, V, L, lens, tlens, seed)
     p = model_ref.init_params(n_feats=F, vocab=V, seed=seed + 1)
     odt = torch.float64 if mode is not None else torch.float32
     tol_loss, tol_grad = (1e-5, 1e-4) if mode == "f32" else (1e-3, 1e-3)
     pr = {k: v.to(odt).requires_grad_(True) for k, v in p.items()}
-    m = Seq2Seq(V, n_feats=F)
-    m.load_state_dict({("encoder." + k if not k.startswith("head.") else k): v for k, v in p.items()}, strict=True)
+    m = load_params(Seq2Seq(V, n_feats=F), p)
     m = m.to(DEV).eval()
     if train:
         assert mode is not None, "the train-mode comparison goes through the trainer"
@@ -447,35 +379,14 @@ def _pg_step_vs_oracle_body(m, p, pr, x, targets, fmask, tmask, B, F, T, V, L, l
             for b in sorted(range(B), key=lambda i: lens[i])[:beam_spot_checks]:
                 hyp, _ = decode_ref.prefix_beam_search(np.exp(lp_np[:lens[b], b]), beam_size=beam)
                 assert [h for i, h in enumerate(hyp) if i == 0 or h != hyp[i - 1]] == dev_hyp[b], b
-    Lf = np.maximum(tl_, 1).astype(np.float64)
-    wRs, wRb = np.zeros(B), np.zeros(B)
-    lp64 = ctc_ref.log_softmax(lg, axis=2)
-    for b in range(B):
-        y = list(tg[b][:tlens[b]])
-        wRs[b] = -decode_ref.edit_dist(y, decode_ref.collapse_path(paths[:lens[b], b]))[0] / Lf[b]
-        if beam and dev_hyp is not None:
-            hyp = dev_hyp[b]
-        elif beam:      # the reference's reward hypothesis (policy_grad.py:6-8): prefix beam search -> collapse_fn -> edit distance
-            hyp, _ = decode_ref.prefix_beam_search(np.exp(lp64[:lens[b], b]), beam_size=beam)
-            hyp = [h for i, h in enumerate(hyp) if i == 0 or h != hyp[i - 1]]
-        else:
-            hyp = decode_ref.collapse_path(greedy_frames[:lens[b], b])
-        wRb[b] = -decode_ref.edit_dist(y, hyp)[0] / Lf[b]
-    coef = lam * (wRs - wRb) / B
-    mask = np.arange(T)[:, None] < il[None, :]
-    lps = (np.take_along_axis(lp64, paths[..., None], axis=2)[..., 0] * mask).sum(axis=0)
-    nll_o, g_ctc = ctc_ref.ctc_loss_and_grad(lg, tg, il, tl_)
-    scale = 1.0 / (Lf * B)
-    w_loss = (nll_o * scale).sum() - (coef * lps).sum()
-    w_grad = g_ctc * scale[None, :, None] + decode_ref.reinforce_grad(lg, paths, coef, il)
+    # everything downstream of the choices: collapse, edit distance and rewards, the loss and d(logits)
+    o = pg_ref.pg_objective(lg, il, tg, tl_, lam=lam, beam=beam, paths=paths, greedy_frames=greedy_frames, hypotheses=dev_hyp)
+    wRs, wRb, w_loss, w_grad = o.R[0], o.R_hyp, o.loss, o.grad
     np.testing.assert_allclose(R_b.cpu().numpy(), wRb, rtol=1e-6)
     np.testing.assert_allclose(R_s.cpu().numpy(), wRs, rtol=1e-6)
     assert abs(float(loss) - w_loss) / abs(w_loss) < tol_loss, (float(loss), w_loss)
     logits_ref.backward(torch.from_numpy(w_grad).to(odt))
-    errs = {}
-    for k, v in m.named_parameters():
-        rk = k[len("encoder."):] if k.startswith("encoder.") else k
-        errs[rk] = rel_err(v.grad.cpu(), pr[rk].grad)
+    errs = param_errs(m, {k: v.grad for k, v in pr.items()})
     worst = max(errs, key=errs.get)
     print(f"[parity] {'train-mode (dropout on) ' if train else ''}mode {mode or hipops.get_precision()} oracle {str(odt)[6:]}: loss rel err {abs(float(loss) - w_loss) / abs(w_loss):.2e}; "
           f"worst parameter gradient {worst} {errs[worst]:.2e}; "
@@ -529,7 +440,7 @@ def test_trainer_with_beam_reward_runs_and_matches_loss_fn():
     from policy_gradient_asr_amd.model import Seq2Seq, weights
     from policy_gradient_asr_amd.train_step import PolicyGradientTrainer
     B, F, T, V, L = 8, 80, 90, 29, 9
-    x, targets, fmask, tmask = _make(B, F, T, V, L, [90, 90, 77, 60, 90, 45, 90, 81], [9, 9, 7, 6, 9, 4, 9, 8], 4)
+    x, targets, fmask, tmask = make_batch(B, F, T, V, L, [90, 90, 77, 60, 90, 45, 90, 81], [9, 9, 7, 6, 9, 4, 9, 8], 4)
     stats = {}
     for dec in ("greedy", "beam"):
         torch.manual_seed(0)
@@ -548,7 +459,7 @@ def test_trainer_steps_reduce_loss():
     from policy_gradient_asr_amd.train_step import PolicyGradientTrainer
     torch.manual_seed(0)
     B, F, T, V, L = 4, 80, 100, 29, 10
-    x, targets, fmask, tmask = _make(B, F, T, V, L, [100] * 4, [10] * 4, 1)
+    x, targets, fmask, tmask = make_batch(B, F, T, V, L, [100] * 4, [10] * 4, 1)
     m = Seq2Seq(V, n_feats=F); m.apply(weights); m = m.to(DEV).eval()
     tr = PolicyGradientTrainer(m, lr=2e-3, lam=0.0, seed=1)   # CTC-only: the loss value is monotone-ish
     losses = [float(tr.step(x.to(DEV), targets.to(DEV), fmask.to(DEV), tmask.to(DEV))) for _ in range(12)]
@@ -568,7 +479,7 @@ def test_ragged_batch_is_padded_with_empty_utterances(B, reward):
     from policy_gradient_asr_amd.train_step import PolicyGradientTrainer
     F, T, V, L = 80, 60, 29, 6
     lens = [T - (3 * b) % 17 for b in range(B)]
-    x, targets, fmask, tmask = _make(B, F, T, V, L, lens, [max(1, L - b % 4) for b in range(B)], 8)
+    x, targets, fmask, tmask = make_batch(B, F, T, V, L, lens, [max(1, L - b % 4) for b in range(B)], 8)
     batch = [v.to(DEV) for v in (x, targets, fmask, tmask)]
     res = {}
     for pad in (False, True):
@@ -733,7 +644,7 @@ def test_weight_grad_overlap_gives_identical_gradients():
     from policy_gradient_asr_amd.model import Seq2Seq, weights
     from policy_gradient_asr_amd.train_step import PolicyGradientTrainer
     B, F, T, V, L = 20, 80, 60, 29, 6
-    x, targets, fmask, tmask = _make(B, F, T, V, L, [60] * 10 + [41] * 10, [6] * 20, 3)
+    x, targets, fmask, tmask = make_batch(B, F, T, V, L, [60] * 10 + [41] * 10, [6] * 20, 3)
     grads = []
     for ov in (False, True):
         torch.manual_seed(0)
@@ -750,7 +661,7 @@ def _trainer_and_batch(seed=3, train=False, B=20, T=60):
     from policy_gradient_asr_amd.model import Seq2Seq, weights
     from policy_gradient_asr_amd.train_step import PolicyGradientTrainer
     F, V, L = 80, 29, 6
-    x, targets, fmask, tmask = _make(B, F, T, V, L, [T] * (B // 2) + [T - 19] * (B - B // 2), [6] * B, seed)
+    x, targets, fmask, tmask = make_batch(B, F, T, V, L, [T] * (B // 2) + [T - 19] * (B - B // 2), [6] * B, seed)
     torch.manual_seed(0)
     m = Seq2Seq(V, n_feats=F); m.apply(weights); m = m.to(DEV)
     m = m.train() if train else m.eval()
@@ -947,7 +858,7 @@ def test_train_mode_step_runs_with_dropout():
     from policy_gradient_asr_amd.train_step import PolicyGradientTrainer
     torch.manual_seed(0)
     B, F, T, V, L = 4, 80, 50, 29, 5
-    x, targets, fmask, tmask = _make(B, F, T, V, L, [50] * 4, [5] * 4, 2)
+    x, targets, fmask, tmask = make_batch(B, F, T, V, L, [50] * 4, [5] * 4, 2)
     m = Seq2Seq(V, n_feats=F); m.apply(weights); m = m.to(DEV).train()
     tr = PolicyGradientTrainer(m, lr=1e-3, lam=0.0, seed=1)
     l0 = float(tr.step(x.to(DEV), targets.to(DEV), fmask.to(DEV), tmask.to(DEV)))
@@ -974,8 +885,7 @@ def test_headline_size_loss_and_gradient_parity(mode):
     p = model_ref.init_params(n_feats=F, vocab=V, seed=0)
     pr = {k: v.double().requires_grad_(True) for k, v in p.items()}
     torch.set_num_threads(min(16, os.cpu_count() or 1))
-    m = Seq2Seq(V, n_feats=F)
-    m.load_state_dict({("encoder." + k if not k.startswith("head.") else k): v for k, v in p.items()}, strict=True)
+    m = load_params(Seq2Seq(V, n_feats=F), p)
     m = m.to(DEV).eval()
     # the one discrete choice of a CTC-only step: which side of leaky_relu (model.py:50) a pre-activation of the input layer falls on.  Two
     # evaluations that agree to 1e-7 still disagree on a handful of 16 M pre-activations that are zero to rounding, and each one scales a
@@ -1002,10 +912,7 @@ def test_headline_size_loss_and_gradient_parity(mode):
     with hipops.precision(mode), torch.no_grad():
         logits, in_len = m.logits(x.to(DEV), fmask.to(DEV))
     e_loss = abs(float(loss.detach()) - float(ref)) / abs(float(ref))
-    worst = 0.0
-    for k, v in m.named_parameters():
-        rk = k[len("encoder."):] if k.startswith("encoder.") else k
-        worst = max(worst, rel_err(v.grad.cpu(), pr[rk].grad))
+    worst = max(param_errs(m, {k: v.grad for k, v in pr.items()}).values())
     e_logits = rel_err(logits.detach().cpu(), logits_ref.detach())
     print(f"[parity] headline CTC step, mode {mode} vs fp64: loss {e_loss:.2e}, worst gradient (max norm) {worst:.2e}, logits {e_logits:.2e}")
     assert e_loss < tol_loss, e_loss
@@ -1025,7 +932,7 @@ def test_held_tensors_give_the_same_steps_as_record_stream_and_side_streams_are_
     from policy_gradient_asr_amd.model import Seq2Seq, weights
     from policy_gradient_asr_amd.train_step import PolicyGradientTrainer
     B, F, T, V, L = 32, 80, 64, 29, 6
-    x, targets, fmask, tmask = _make(B, F, T, V, L, [T] * B, [L] * B, 3)
+    x, targets, fmask, tmask = make_batch(B, F, T, V, L, [T] * B, [L] * B, 3)
     batch = [v.to(DEV) for v in (x, targets, fmask, tmask)]
     flats = {}
     for mode in (True, False):

@@ -5,13 +5,10 @@ import numpy as np
 import pytest
 import torch
 
-from oracle import ctc_ref, decode_ref, model_ref
-from test_multisample_pg_gpu import _lattice_case, baselines, multi_sample_paths
-from test_train_step_gpu import _make
+from oracle import decode_ref, pg_ref
+from pg_harness import D, DEV, spaced_batch, spaced_lattice_case, shards_vs_whole, tiny_corpus, trainer_step_vs_oracle
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-D = 28                                   # the delimiter of these cases: V = 29, ids 1..27 letters, 28 = " "
 CHARS = "abcdefghijklmnopqrstuvwxyz'"
 
 
@@ -19,16 +16,8 @@ def decode(seq):
     return "".join(" " if int(t) == D else CHARS[int(t) - 1] for t in seq)
 
 
-def split_words(seq, d=D):
-    """str.split(" ") on a token row: n delimiters give n + 1 words, empty words kept."""
-    words, cur = [], []
-    for t in seq:
-        if int(t) == d:
-            words.append(tuple(cur)); cur = []
-        else:
-            cur.append(int(t))
-    words.append(tuple(cur))
-    return words
+def split_words(seq):
+    return pg_ref.split_words(seq, D)
 
 
 def lev(a, b):
@@ -181,7 +170,7 @@ def test_rewards_with_word_normaliser_vs_numpy(mode):
     np.testing.assert_array_equal(R_s.cpu().numpy(), R)                             # R normalised by the word count
     np.testing.assert_allclose(coef.cpu().numpy(), scale * (R - bk), rtol=2e-7, atol=1e-12)
     R64 = -dist[H * B:].reshape(K, B) / n_words
-    b64 = baselines(R64, -dist[:B] / n_words if H else None, mode)
+    b64 = np.broadcast_to(-dist[:B] / n_words, R64.shape) if H else (R64.sum(axis=0, keepdims=True) - R64) / (K - 1)
     np.testing.assert_allclose(coef.cpu().numpy(), lam / (Bg * K) * (R64 - b64), rtol=1e-5, atol=1e-8)
     # utt_scale stays on the character counts: the bits of the character path
     _, _, _, us_c = hipops.pg_rewards_multi(d_, t_, K, lam, 1.0 / Bg, baseline=mode)
@@ -197,94 +186,17 @@ def test_rewards_with_word_normaliser_vs_numpy(mode):
         assert torch.equal(one[0], R_g) and torch.equal(one[1][0], R_s1) and torch.equal(one[2][0], c1) and torch.equal(one[3], u1)
 
 
-def _spaced_batch(B, F, T, V, L, lens, tlens, seed):
-    """_make's batch with about 18 % of the target symbols replaced by the delimiter."""
-    x, targets, fmask, tmask = _make(B, F, T, V, L, lens, tlens, seed)
-    g = torch.Generator().manual_seed(seed + 1000)
-    sp = (torch.rand(B, L, generator=g) < 0.18) & (tmask > 0)
-    targets[sp] = D
-    return x, targets, fmask, tmask
-
-
 def _word_step_vs_oracle(reward_baseline, beam, K, seed=61):
     """One lambda = 1 trainer step (f32 mode, reward_unit="word") against the torch-CPU model in FP64 on the same weights:
     rewards exact, loss within 1e-5, every parameter gradient within 1e-4 (max norm)."""
-    from policy_gradient_asr_amd import hipops
-    from policy_gradient_asr_amd.model import Seq2Seq
-    from policy_gradient_asr_amd.train_step import PolicyGradientTrainer
-    B, F, T, V, L = 4, 80, 120, 29, 16
-    lens, tlens = [120, 90, 120, 64], [16, 11, 14, 7]
-    x, targets, fmask, tmask = _spaced_batch(B, F, T, V, L, lens, tlens, seed)
-    p = model_ref.init_params(n_feats=F, vocab=V, seed=seed + 1)
-    pr = {k: v.double().requires_grad_(True) for k, v in p.items()}
-    m = Seq2Seq(V, n_feats=F)
-    m.load_state_dict({("encoder." + k if not k.startswith("head.") else k): v for k, v in p.items()}, strict=True)
-    m = m.to(DEV).eval()
-    tr = PolicyGradientTrainer(m, lam=1.0, seed=3, reward_decoder="beam" if beam else "greedy", beam_size=beam or 16,
-                               precision="f32", num_samples=K, reward_baseline=reward_baseline, reward_unit="word", word_delimiter=D)
-    loss = tr.compute_gradients(x.to(DEV), targets.to(DEV), fmask.to(DEV), tmask.to(DEV))
-    nll, R_s, R_b = tr.last_stats
-    R_all = tr.last_sample_rewards
-    torch.cuda.synchronize()
-    hipops.lstm_assert_no_timeouts()
-    assert R_s.shape == (B,) and R_b.shape == (B,) and R_all.shape == (K, B)
-
-    enc = model_ref.encoder_forward_torch(pr, x.double(), fmask, packed=True)
-    logits_ref = model_ref.head_logits_torch(pr, enc)
-    lg = logits_ref.detach().numpy()
-    il, tl_, tg = np.array(lens), np.array(tlens), targets.numpy()
-    paths, _, _ = multi_sample_paths(lg, K, seed=3, offset=1)          # the trainer's first step samples with offset 1
-    lp64 = ctc_ref.log_softmax(lg, axis=2)
-    Lf = np.maximum(tl_, 1).astype(np.float64)
-
-    def word_reward(y, hyp):
-        wy = split_words(y)
-        return -decode_ref.edit_dist(wy, split_words(hyp))[0] / len(wy)
-
-    R = np.zeros((K, B)); Rc = np.zeros((K, B)); R_hyp = np.zeros(B)
-    for b in range(B):
-        y = [int(t) for t in tg[b][:tlens[b]]]
-        for k in range(K):
-            hyp = decode_ref.collapse_path(paths[k, :lens[b], b])
-            R[k, b] = word_reward(y, hyp)
-            Rc[k, b] = -decode_ref.edit_dist(y, hyp)[0] / Lf[b]
-        if reward_baseline == "hypothesis":
-            if beam:
-                hyp, _ = decode_ref.prefix_beam_search(np.exp(lp64[:lens[b], b]), beam_size=beam)
-                hyp = [h for i, h in enumerate(hyp) if i == 0 or h != hyp[i - 1]]
-            else:
-                hyp = decode_ref.collapse_path(np.argmax(lg[:lens[b], b], axis=1))
-            R_hyp[b] = word_reward(y, hyp)
-    assert (np.abs(R - Rc) > 1e-6).any()          # the word rewards are not the character rewards
-    bk = baselines(R, R_hyp, reward_baseline)
-    coef = (R - bk) / (B * K)
-    mask = np.arange(T)[:, None] < il[None, :]
-    nll_o, g_ctc = ctc_ref.ctc_loss_and_grad(lg, tg, il, tl_)
-    scale = 1.0 / (Lf * B)                         # the CTC term stays on the character counts
-    w_loss = (nll_o * scale).sum()
-    w_grad = g_ctc * scale[None, :, None]
-    for k in range(K):
-        lps = (np.take_along_axis(lp64, paths[k][..., None], axis=2)[..., 0] * mask).sum(axis=0)
-        w_loss -= (coef[k] * lps).sum()
-        w_grad = w_grad + decode_ref.reinforce_grad(lg, paths[k], coef[k], il)
-    np.testing.assert_allclose(R_all.cpu().numpy(), R, rtol=1e-6)
-    np.testing.assert_allclose(R_s.cpu().numpy(), R.mean(axis=0), rtol=1e-6, atol=1e-7)
-    np.testing.assert_allclose(R_b.cpu().numpy(), bk.mean(axis=0), rtol=1e-6, atol=1e-7)
-    assert abs(float(loss) - w_loss) / abs(w_loss) < 1e-5, (float(loss), w_loss)
-    logits_ref.backward(torch.from_numpy(w_grad))
-    errs = {}
-    for k, v in m.named_parameters():
-        rk = k[len("encoder."):] if k.startswith("encoder.") else k
-        errs[rk] = rel_err(v.grad.cpu(), pr[rk].grad)
-    worst = max(errs, key=errs.get)
-    print(f"[word step] K={K} {reward_baseline} beam={beam}: loss rel err {abs(float(loss) - w_loss) / abs(w_loss):.2e}; "
-          f"worst parameter gradient {worst} {errs[worst]:.2e}")
-    assert errs[worst] < 1e-4, (worst, errs[worst])
-
-
-def rel_err(a, b):
-    a = np.asarray(a, dtype=np.float64); b = np.asarray(b, dtype=np.float64)
-    return np.abs(a - b).max() / (np.abs(b).max() + 1e-30)
+    r = trainer_step_vs_oracle(dict(reward_decoder="beam" if beam else "greedy", beam_size=beam or 16, num_samples=K,
+                                    reward_baseline=reward_baseline, reward_unit="word", word_delimiter=D),
+                               dict(num_samples=K, baseline=reward_baseline, beam=beam, reward_unit="word", word_delimiter=D),
+                               word=True, seed=seed, label=f"[word step] K={K} {reward_baseline} beam={beam}")
+    tr = r.trainer
+    assert all(s_.shape == (4,) for s_ in tr.last_stats) and tr.last_sample_rewards.shape == (K, 4)
+    chars = pg_ref.pg_objective(*r.args, **dict(r.kw, reward_unit="char", paths=r.oracle.paths, beam=0))
+    assert (np.abs(r.oracle.R - chars.R) > 1e-6).any()          # the word rewards are not the character rewards
 
 
 @pytest.mark.parametrize("baseline,beam,K", [("hypothesis", 0, 1), ("hypothesis", 16, 1), ("hypothesis", 0, 4),
@@ -293,40 +205,13 @@ def test_word_reward_step_vs_oracle(baseline, beam, K):
     _word_step_vs_oracle(baseline, beam, K)
 
 
-def _spaced_lattice_case(T, B, V, L, seed):
-    logits, targets, in_len, tg_len = _lattice_case(T, B, V, L, seed)
-    g = torch.Generator().manual_seed(seed + 1)
-    targets[torch.rand(B, L, generator=g) < 0.18] = D
-    return logits, targets, in_len, tg_len
-
-
 @pytest.mark.parametrize("K,baseline", [(1, "hypothesis"), (4, "leave_one_out")])
 def test_word_reward_shards_reproduce_the_whole_batch(K, baseline):
     """Two pg_ctc_loss calls on the halves of a batch (global_batch, sample_base set) give the whole batch's word rewards and logits
     gradient (the coefficients times the paths)."""
-    from policy_gradient_asr_amd.loss import pg_ctc_loss
     T, B, V, L = 150, 8, 29, 14
-    logits, targets, in_len, tg_len = _spaced_lattice_case(T, B, V, L, 78)
-    lg = logits.float().to(DEV)
-    tg, il, tl = targets.to(DEV), in_len.to(DEV), tg_len.to(DEV)
     kw = dict(lam=1.0, seed=11, offset=4, num_samples=K, baseline=baseline, reward_unit="word", word_delimiter=D)
-    whole = lg.clone().requires_grad_(True)
-    loss, nll, R_s, R_b = pg_ctc_loss(whole, il, tg, tl, **kw)
-    loss.backward()
-    grads, total = [], 0.0
-    for h in range(2):
-        sl = slice(4 * h, 4 * h + 4)
-        part = lg[:, sl].contiguous().requires_grad_(True)
-        l_h, _, Rs_h, Rb_h = pg_ctc_loss(part, il[sl].contiguous(), tg[sl].contiguous(), tl[sl].contiguous(), global_batch=B,
-                                         sample_base=4 * h, **kw)
-        l_h.backward()
-        grads.append(part.grad)
-        total += float(l_h.detach())
-        assert torch.equal(Rs_h, R_s[..., sl]) and torch.equal(Rb_h, R_b[sl])
-    diff = (torch.cat(grads, dim=1) - whole.grad).abs().max()
-    assert float(diff) <= 1e-6 * float(whole.grad.abs().max()), float(diff)
-    loss = float(loss.detach())
-    assert abs(total - loss) <= 1e-6 * abs(loss)
+    shards_vs_whole(kw, spaced_lattice_case(T, B, V, L, 78))
 
 
 def test_word_reward_ragged_batch():
@@ -337,7 +222,7 @@ def test_word_reward_ragged_batch():
     from policy_gradient_asr_amd.model import Seq2Seq, weights
     from policy_gradient_asr_amd.train_step import PolicyGradientTrainer
     T, B, V, L, P = 90, 5, 29, 12, 3
-    logits, targets, in_len, tg_len = _spaced_lattice_case(T, B, V, L, 5)
+    logits, targets, in_len, tg_len = spaced_lattice_case(T, B, V, L, 5)
     for K, baseline in ((1, "hypothesis"), (4, "leave_one_out")):
         kw = dict(lam=1.0, seed=2, offset=3, num_samples=K, baseline=baseline, reward_unit="word", word_delimiter=D)
         _, _, R_s, R_b = pg_ctc_loss(logits.float().to(DEV), in_len.to(DEV), targets.to(DEV), tg_len.to(DEV), **kw)
@@ -351,7 +236,7 @@ def test_word_reward_ragged_batch():
 
     F, T, L = 80, 60, 6
     lens = [T - (3 * b) % 17 for b in range(B)]
-    x, targets, fmask, tmask = _spaced_batch(B, F, T, V, L, lens, [max(1, L - b % 4) for b in range(B)], 8)
+    x, targets, fmask, tmask = spaced_batch(B, F, T, V, L, lens, [max(1, L - b % 4) for b in range(B)], 8)
     batch = [v.to(DEV) for v in (x, targets, fmask, tmask)]
     res = {}
     for pad in (False, True):
@@ -372,7 +257,7 @@ def test_default_reward_unit_is_char_bit_for_bit():
     from policy_gradient_asr_amd.model import Seq2Seq, weights
     from policy_gradient_asr_amd.train_step import PolicyGradientTrainer
     B, F, T, V, L = 16, 80, 80, 29, 10
-    x, targets, fmask, tmask = _spaced_batch(B, F, T, V, L, [T - b for b in range(B)], [L - b % 3 for b in range(B)], 12)
+    x, targets, fmask, tmask = spaced_batch(B, F, T, V, L, [T - b for b in range(B)], [L - b % 3 for b in range(B)], 12)
     batch = [v.to(DEV) for v in (x, targets, fmask, tmask)]
     out = []
     for kw in ({}, {"reward_unit": "char"}):
@@ -407,13 +292,8 @@ def test_word_reward_argument_checks():
 def test_train_driver_records_reward_unit(tmp_path, capsys):
     """model.train(reward_unit="word"): trains with the alphabet's " " as the delimiter, records the unit in the checkpoint, warns on
     a resume with another unit; an alphabet without " " is refused."""
-    from policy_gradient_asr_amd.data import SyntheticSpeech
     from policy_gradient_asr_amd.model import train
-    corpus = tmp_path / "corpus"; out = tmp_path / "run"
-    corpus.mkdir()
-    (corpus / "alphabet.txt").write_text("a\nb\nc\nd\n \n")
-    char2ind = {"<pad>": 0, "a": 1, "b": 2, "c": 3, "d": 4, " ": 5}
-    ds = SyntheticSpeech(32, char2ind, n_feats=20, seed=1)
+    corpus, out, ds = tiny_corpus(tmp_path)
     l1, _ = train(str(corpus), str(out), 2, 16, 0, train_dataset=ds, n_feats=20, lam=1.0, lr=3e-3, log_every=0, reward_unit="word")
     assert len(l1) == 2 and all(np.isfinite(l1))
     st = torch.load(out / "checkpoint_last.pth", map_location="cpu")
