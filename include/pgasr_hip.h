@@ -226,6 +226,36 @@ int pgasr_ctc_grad_from_lattices_seq_ent(const float* log_probs, const int32_t* 
                                          void* hyp_workspace, size_t hyp_workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * A5-VIT  CTC forced alignment (Viterbi): the best single alignment of a KNOWN label sequence, its score, and the frames each token
+ * occupies (csrc/align.hip).  Max-plus in fp64 with a fixed order: the outputs are bit-identical to tests/align_ref.py.
+ * log_probs (T,B,V) fp32 contiguous, natural log; tokens (B,Lmax) int32; T_b = input_lengths[b] clamped to [0,T], L_b =
+ * token_lengths[b] clamped to [0,Lmax].  States s = 0 .. 2 L_b: even states are blank, state 2i+1 is token i.  label(s) is blank or
+ * tok[i]; a label outside [0,V) is TREATED AS BLANK (defensive: valid labels are the caller's duty).
+ *     delta_0(0) = lp[0][blank], delta_0(1) = lp[0][tok_0], -inf elsewhere
+ *     delta_t(s) = max(c0, c1, c2) + (double)lp[t][label(s)],   c0 = delta_{t-1}(s), c1 = delta_{t-1}(s-1),
+ *                  c2 = delta_{t-1}(s-2) only for odd s >= 3 with tok[i] != tok[i-1]
+ *     backpointer: the smallest move wins a tie -- 1 only if c1 > c0, 2 only if c2 > max(c0, c1)
+ *     end state:   2 L_b, unless L_b > 0 and delta(2 L_b - 1) > delta(2 L_b)
+ * Outputs, row b (the value beyond the real lengths in parentheses):
+ *     score (B) fp64        -delta_{T_b-1}(end); +inf when no alignment exists; T_b = 0: 0 when L_b = 0, else +inf
+ *     frame_label (B,T)     label of the state occupied at each frame (-1)
+ *     frame_token (B,T)     i on a frame in state 2i+1, -1 on a blank frame (-1)                                  [may be NULL]
+ *     token_start/_end (B,Lmax)  first frame and one-past-last frame in state 2i+1 (-1)                          [may be NULL]
+ *     token_logp (B,Lmax) fp64   sum of (double)lp[t][label(2i+1)] over the token's frames, ascending t (0)       [may be NULL]
+ *   When score is +inf every per-frame and per-token value of that utterance is -1 / 0.
+ * pgasr_ctc_align_workspace_bytes: the backpointers, one byte per (b,t,state) with the states rounded up to 64, plus two small
+ *   tables; 0 for sizes the entry point rejects.  No GPU needed.
+ * Checked before any HIP call: null required pointers, T/B/V/Lmax <= 0, blank outside [0,V): PGASR_ERR_INVALID_ARG;
+ * 2*Lmax+1 > 2048: PGASR_ERR_UNSUPPORTED; workspace NULL or short: PGASR_ERR_WORKSPACE.  Any V, any T.  No host synchronisation.
+ * ---------------------------------------------------------------------------------------- */
+size_t pgasr_ctc_align_workspace_bytes(int T, int B, int Lmax);
+int pgasr_ctc_forced_align(const float* log_probs, const int32_t* tokens, const int32_t* input_lengths,
+                           const int32_t* token_lengths, int T, int B, int V, int Lmax, int blank,
+                           double* score, int32_t* frame_label, int32_t* frame_token,
+                           int32_t* token_start, int32_t* token_end, double* token_logp,
+                           void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * A11  word-level (WER) reward, opt-in: R = -WED(y, yhat) / W(y), where a word is a run of tokens between delimiters -- exactly
  * Python's str.split(" ") on the decoded string (n delimiters give n + 1 words, empty words included; an empty row is one empty
  * word) --, WED the Levenshtein distance over the two word lists and W(y) >= 1 the reference's word count.

@@ -68,6 +68,76 @@ class CTCDecoder:
                                       **self._lm_args(lm, lm_alpha, lm_beta))
 
 
+    def align_batch(self, log_probs, tokens, token_lengths, lengths=None, blank=0):
+        """Forced alignment on the device: log_probs (T,B,V) fp32 GPU tensor of natural-log probabilities, tokens (B,Lmax) /
+        token_lengths (B) int32 the transcripts (Lmax <= 1023).  Returns ``hipops.CTCAlignment`` (score, frame_label, frame_token,
+        token_start, token_end, token_logp) without a host sync: the best single alignment of each transcript (Viterbi), its
+        negative log-probability (+inf where the transcript does not fit the frames) and the frames each token occupies."""
+        T, B, _ = log_probs.shape
+        if lengths is None:
+            lengths = torch.full((B,), T, dtype=torch.int32, device=log_probs.device)
+        return hipops.ctc_forced_align(log_probs, tokens, lengths.to(torch.int32).contiguous(), token_lengths, blank=int(blank))
+
+    def align(self, probs, labels, blank=0):
+        """Single-utterance host form: probs (time x output dim) array of PROBABILITIES as ``decode`` takes them, labels a sequence
+        of symbol indices, each in range and not blank (else ValueError, before the device is touched).
+        Returns (frame_label tuple, [(start, end, mean_log_prob)] per label, score): the label of every frame on the best
+        alignment, each label's first and one-past-last frame with the mean log-probability of its frames, and the alignment's
+        negative log-probability.  When the labels do not fit the frames the score is +inf, the frame labels are -1 and every
+        span is (-1, -1, -inf)."""
+        probs = np.asarray(probs)
+        T, V = probs.shape
+        labels = [int(x) for x in labels]
+        blank = int(blank)
+        if not 0 <= blank < V:
+            raise ValueError(f"blank {blank} outside [0, {V})")
+        for i, x in enumerate(labels):
+            if not 0 <= x < V or x == blank:
+                raise ValueError(f"label {x} at position {i} is blank or outside [0, {V})")
+        if len(labels) > hipops.ALIGN_MAX_TOKENS:
+            raise ValueError(f"{len(labels)} labels exceed the device alignment's limit of {hipops.ALIGN_MAX_TOKENS}")
+        none = [(-1, -1, -float("inf"))] * len(labels)
+        if T == 0:
+            return tuple(), none, (0.0 if not labels else float("inf"))
+        dev = _device(self.device)
+        with np.errstate(divide="ignore"):
+            logp = np.log(probs.astype(np.float64)).astype(np.float32)
+        lp = torch.from_numpy(np.ascontiguousarray(logp)).to(dev).view(T, 1, V)
+        tok = torch.tensor([labels or [0]], dtype=torch.int32, device=dev)
+        tl = torch.tensor([len(labels)], dtype=torch.int32, device=dev)
+        a = self.align_batch(lp, tok, tl, blank=blank)
+        score = float(a.score[0].item())
+        if score == float("inf"):
+            return (-1,) * T, none, score
+        st, en, sm = a.token_start[0].tolist(), a.token_end[0].tolist(), a.token_logp[0].tolist()
+        spans = [(st[i], en[i], sm[i] / (en[i] - st[i])) for i in range(len(labels))]
+        return tuple(a.frame_label[0].tolist()), spans, score
+
+
+def word_spans(token_start, token_end, tokens, delimiter):
+    """Character spans -> word spans, pure host: token_start / token_end / tokens are equally long sequences (one utterance, real
+    length only), ``delimiter`` the token that separates words.  Words follow ``str.split(" ")`` as the word reward does: n
+    delimiters give n + 1 words, empty ones included.  Returns one (start, end) per word: the first frame of its first
+    character and the one-past-last frame of its last; (-1, -1) for an empty word or one with an unaligned character."""
+    token_start, token_end, tokens = list(token_start), list(token_end), list(tokens)
+    if not len(token_start) == len(token_end) == len(tokens):
+        raise ValueError("word_spans: token_start, token_end and tokens must be equally long")
+    words, cur = [], []
+    for i, k in enumerate(tokens):
+        if int(k) == int(delimiter):
+            words.append(cur); cur = []
+        else:
+            cur.append(i)
+    words.append(cur)
+    out = []
+    for w in words:
+        if not w or any(int(token_start[i]) < 0 or int(token_end[i]) < 0 for i in w):
+            out.append((-1, -1))
+        else:
+            out.append((int(token_start[w[0]]), int(token_end[w[-1]])))
+    return out
+
+
 def collapse_fn(preds):
     """Remove adjacent duplicate characters of an already-decoded string (CTCdecoder.py:119-131):
     'aabbcc' -> 'abc', '' -> ''.  Pure host string work."""

@@ -1,6 +1,7 @@
 """Tensor-level wrappers over the C ABI (one function per entry point of
 include/pgasr_hip.h).  torch is used for device memory and the current stream only.
 Every wrapper requires CUDA(HIP) tensors and raises otherwise -- no CPU fallback."""
+import collections
 import os
 
 import torch
@@ -506,6 +507,44 @@ def ctc_collapse(paths, lengths, blank=0, out=None):
     st = lib.pgasr_ctc_collapse(_p(paths), _p(lengths), P, T, B, blank, _p(tokens), _p(tl), _stream())
     _lib.check(st, "pgasr_ctc_collapse")
     return tokens, tl
+
+
+CTCAlignment = collections.namedtuple("CTCAlignment", "score frame_label frame_token token_start token_end token_logp")
+ALIGN_MAX_TOKENS = 1023      # csrc/align.hip: 2 * Lmax + 1 <= 2048 lattice states
+
+
+def ctc_forced_align(log_probs, tokens, input_lengths, token_lengths, blank=0, want_spans=True):
+    """The best single CTC alignment (Viterbi, fp64 max-plus) of tokens (B,Lmax) int32 to log_probs (T,B,V) fp32; lengths (B) int32.
+    Returns ``CTCAlignment`` of device tensors, no host synchronisation: score (B) fp64 = -log p of the best path (+inf: no
+    alignment), frame_label (B,T) int32 (-1 beyond the utterance), and with ``want_spans`` frame_token (B,T) int32 (token index,
+    -1 on blank frames), token_start / token_end (B,Lmax) int32 (first and one-past-last frame, -1 beyond the transcript),
+    token_logp (B,Lmax) fp64 (sum of the token's frame log-probs); else None in their places.  Labels must lie in [0,V) and differ
+    from blank: one that does not is aligned as a blank."""
+    lib = _lib.load()
+    _req(log_probs, torch.float32, "log_probs"); _req(tokens, torch.int32, "tokens")
+    _req(input_lengths, torch.int32, "input_lengths"); _req(token_lengths, torch.int32, "token_lengths")
+    if log_probs.dim() != 3:
+        raise _lib.PgasrError("ctc_forced_align wants log_probs (T,B,V)")
+    T, B, V = log_probs.shape
+    if tokens.dim() != 2 or tokens.shape[0] != B or tokens.shape[1] < 1 or input_lengths.numel() != B or token_lengths.numel() != B:
+        raise _lib.PgasrError(f"ctc_forced_align wants tokens ({B},Lmax >= 1) and lengths ({B})")
+    Lmax, dev = tokens.shape[1], log_probs.device
+    nbytes = lib.pgasr_ctc_align_workspace_bytes(T, B, Lmax)
+    ws = _workspace(nbytes, dev, "align")
+    score = torch.empty(B, dtype=torch.float64, device=dev)
+    frame_label = torch.empty(B, T, dtype=torch.int32, device=dev)
+    frame_token = token_start = token_end = token_logp = None
+    if want_spans:
+        frame_token = torch.empty(B, T, dtype=torch.int32, device=dev)
+        token_start = torch.empty(B, Lmax, dtype=torch.int32, device=dev)
+        token_end = torch.empty(B, Lmax, dtype=torch.int32, device=dev)
+        token_logp = torch.empty(B, Lmax, dtype=torch.float64, device=dev)
+    with _timed("ctc_forced_align"):
+        st = lib.pgasr_ctc_forced_align(_p(log_probs), _p(tokens), _p(input_lengths), _p(token_lengths), T, B, V, Lmax, int(blank),
+                                        _p(score), _p(frame_label), _p(frame_token), _p(token_start), _p(token_end), _p(token_logp),
+                                        _p(ws), ws.numel(), _stream())
+    _lib.check(st, "pgasr_ctc_forced_align")
+    return CTCAlignment(score, frame_label, frame_token, token_start, token_end, token_logp)
 
 
 def edit_distance(ref, ref_len, hyp, hyp_len, want_prefix=False):

@@ -423,6 +423,56 @@ def predict(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=N
     return cer, wer
 
 
+def align(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=None, maxlent=None, device_id=0,
+          test_dataset=None, n_feats=120, features="mfcc", out_path=None):
+    """Forced alignment of the REFERENCE transcripts: ``predict``'s loading and batching, then per batch forward, log-softmax and
+    ``CTCDecoder.align_batch`` (Viterbi on the device).  Writes ``out_path`` (default <model_path>/alignments.tsv), one line per
+    reference character: utterance index, character index, symbol, start frame, end frame (one past the last), mean log-prob of
+    its frames.  An utterance whose transcript does not fit its frames is written with spans -1 -1 and mean -inf, not dropped.
+    Returns the per-utterance scores (negative log-probability of the best alignment, +inf where there is none)."""
+    import os
+    import functools
+    import torch.utils.data as tud
+    from .CTCdecoder import CTCDecoder
+    from .data import Data
+    from .data import collate_custom as _collate
+
+    alphabet, char2ind = _read_alphabet(alphabet_path)
+    ind2char = {char2ind[k]: k for k in char2ind}
+    dev = torch.device("cuda", device_id)
+    model = Seq2Seq(alphabet_size=len(alphabet), n_feats=n_feats)
+    model.load_state_dict(torch.load(os.path.join(model_path, "model_best.pth"), map_location="cpu"))
+    model = model.to(dev).eval()
+    if test_dataset is None:
+        test_dataset = Data(test_path, aud_path, char2ind)
+    _check_features(features, n_feats, test_dataset)
+    collate_custom = functools.partial(_collate, device=dev, features=features)
+    loader = tud.DataLoader(test_dataset, batch_size=batch_size, shuffle=False, collate_fn=collate_custom)
+    decoder = CTCDecoder(alphabet)
+    scores, lines = [], []
+    with torch.no_grad():
+        for batch in loader:
+            x, t, fmask, tmask = _to_device(batch, dev)
+            logits, in_len = model.logits(x, fmask)
+            lp = Fh.LogSoftmaxFn.apply(logits).contiguous()
+            tl = tmask.sum(1).to(torch.int32).contiguous()
+            a = decoder.align_batch(lp, t.to(torch.int32).contiguous(), tl, in_len)
+            t, tl = t.cpu(), tl.cpu()
+            st, en, sm, sc = a.token_start.cpu(), a.token_end.cpu(), a.token_logp.cpu(), a.score.cpu()
+            for i in range(t.shape[0]):
+                u = len(scores)
+                scores.append(float(sc[i]))
+                for j in range(int(tl[i])):
+                    s0, s1 = int(st[i, j]), int(en[i, j])
+                    mean = float(sm[i, j]) / (s1 - s0) if s0 >= 0 else -float("inf")
+                    lines.append("{}\t{}\t{}\t{}\t{}\t{:.6f}\n".format(u, j, ind2char[int(t[i, j])], s0, s1, mean))
+    if out_path is None:
+        out_path = os.path.join(model_path, "alignments.tsv")
+    with open(out_path, "w") as fo:
+        fo.writelines(lines)
+    return scores
+
+
 def build_lm(corpus_path, order=3, out_path=None, train_dataset=None):
     """Character n-gram LM (lm.CharNgramLM, interpolated Witten-Bell) from the transcripts that Data(train.tsv) yields, over the
     symbols of <corpus_path>/alphabet.txt (``<pad>`` = blank = 0); saved to ``out_path`` (default <corpus_path>/lm.npz) for
