@@ -46,7 +46,8 @@ typedef enum pgasr_status {
  * pgasr_adam_step_clipped), the id-addressed samplers (pgasr_frame_argmax_sample_ids, pgasr_frame_sample_multi_ids) and the
  * sequence-level score function (pgasr_ctc_hyp_workspace_bytes, pgasr_ctc_hyp_lattice, pgasr_ctc_grad_from_lattices_seq,
  * pgasr_pg_loss_value_seq) and the entropy regularisation (pgasr_frame_entropy, pgasr_ctc_grad_from_lattice_ent,
- * pgasr_ctc_grad_from_lattice_multi_ent, pgasr_ctc_grad_from_lattices_seq_ent). */
+ * pgasr_ctc_grad_from_lattice_multi_ent, pgasr_ctc_grad_from_lattices_seq_ent), forced alignment (pgasr_ctc_forced_align) and
+ * SpecAugment masking (pgasr_spec_augment). */
 #define PGASR_ABI_VERSION 7
 
 int pgasr_abi_version(void);
@@ -700,6 +701,39 @@ int pgasr_ctc_beam_search_lm(const void* log_probs, int is_f64, long long stride
                              int32_t* out_tokens, int32_t* out_len, double* out_score,
                              void* workspace, size_t workspace_bytes, void* stream,
                              const float* lm_table, int lm_order, double lm_alpha, double lm_beta);
+
+/* ------------------------------------------------------------------------------------------
+ * A0-AUG  SpecAugment (Park et al., arXiv:1904.08779): time / frequency masking of a feature batch on the device.
+ *   x (B,F,T) fp32 contiguous, zero beyond each utterance's length; lengths (B) int32 (clamped to [0,T]); out (B,F,T), may equal x.
+ *   id_b = utt_ids[b] (utt_ids (B) int32 on the device), or batch_offset + b where utt_ids is NULL: the utterance's index in the
+ *   GLOBAL batch, so a rank, a shard or a micro-batch masks exactly what one process holding the whole batch masks.
+ *   Every mask interval of utterance b comes from ONE Philox4x32-10 block:
+ *        w = philox4x32_10(ctr = (id_b, offset, dom, m), key = (seed lo32, seed hi32)),   m = the mask's index,
+ *        dom = 2 for the n_freq frequency masks, 3 for the n_time time masks (the samplers use 0 and 1 in that word: one seed
+ *        serves both without overlap);
+ *        span = F, W = min(freq_width, F)                                                       (frequency mask)
+ *        span = len_b, W = min(time_width, len_b, (int)fmul_rn(time_ratio, (float)len_b))       (time mask: one fp32 multiply,
+ *                                                                                                then truncation)
+ *        width = ((w[0] >> 8) * (W + 1)) >> 24            uniform on 0 .. W
+ *        start = ((w[1] >> 8) * (span - width + 1)) >> 24  uniform on 0 .. span - width          (64-bit integers, no float)
+ *   out[b,f,t] = the fill value where t < len_b and (f lies in a frequency interval of b or t in a time interval of b), else
+ *   x[b,f,t]: frames t >= len_b are copied (the padding stays zero), and so is every row with len_b <= 0 or id_b < 0 (id_b < 0: a
+ *   padded, empty utterance; it has no intervals).  fill_mode PGASR_SPECAUG_FILL_ZERO: 0.0f; PGASR_SPECAUG_FILL_ROW_MEAN: the mean of
+ *   the ORIGINAL x[b,f,0:len_b] (masked frames included), summed in fp64 in a fixed order (two runs give the same bits), divided by
+ *   len_b in fp64, rounded to fp32.
+ *   masks: NULL, or (B, n_freq + n_time, 2) int32: (start, width) of every interval, frequency masks first (0, 0 where id_b < 0).
+ *   One launch, no workspace, no atomics, no host synchronisation; any B, F, T (16-byte accesses where T % 4 == 0 and x, out are
+ *   16-byte aligned).  Checked before any pointer is touched or anything is launched: x, lengths or out NULL, B / F / T < 1, a negative
+ *   count or width, time_ratio outside (0,1] or NaN, an unknown fill_mode: PGASR_ERR_INVALID_ARG; more than 8 masks of a kind:
+ *   PGASR_ERR_UNSUPPORTED.
+ * ---------------------------------------------------------------------------------------- */
+#define PGASR_SPECAUG_FILL_ROW_MEAN 0
+#define PGASR_SPECAUG_FILL_ZERO 1
+int pgasr_spec_augment(const float* x, const int32_t* lengths, const int32_t* utt_ids /* NULL: id = batch_offset + b */,
+                       int batch_offset, int B, int F, int T, int n_freq, int freq_width, int n_time, int time_width,
+                       float time_ratio, int fill_mode, unsigned long long seed, unsigned offset,
+                       float* out /* may equal x */, int32_t* masks /* NULL or (B, n_freq + n_time, 2): start, width */,
+                       void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Elementwise pieces of the train step.

@@ -118,6 +118,97 @@ class LogMel(_FrontEnd):
         return feat, fmask
 
 
+class SpecAugment:
+    """The SpecAugment policy (Park et al., arXiv:1904.08779): ``freq_masks`` bands of at most ``freq_width`` feature rows and
+    ``time_masks`` spans of at most min(``time_width``, ``time_ratio`` x the utterance's frames) frames are replaced by ``fill`` --
+    "row_mean" (default: the mean of the feature row over the utterance's real frames; the encoder's instance norm runs over the
+    whole plane afterwards, so such a cell carries no information) or "zero" (in dB-scaled log-mel the loudest possible cell).
+    Widths and positions are uniform draws, a function of (seed, offset, global utterance index) only (include/pgasr_hip.h,
+    A0-AUG): a rank, a shard or a micro-batch masks what one process holding the whole batch masks.  Limits: 0 <= masks of a kind
+    <= MAX_MASKS, widths >= 0, 0 < time_ratio <= 1 (None: 1.0).  Immutable; ``state()`` / ``from_state()`` for checkpoints.
+    ``aug(feat, lengths_or_fmask, seed, offset, utt_ids=None)`` masks a (B,F,T) fp32 batch on the device, out of place: lengths (B)
+    int32, or the front end's fmask (B,1,T) / (B,T); utt_ids: None (row b is utterance b), or one global index per row."""
+    MAX_MASKS = hipops.SPECAUG_MAX_MASKS
+    FILLS = tuple(hipops.SPECAUG_FILLS)
+    FIELDS = ("freq_masks", "freq_width", "time_masks", "time_width", "time_ratio", "fill")
+    __slots__ = FIELDS
+
+    def __init__(self, freq_masks=2, freq_width=27, time_masks=2, time_width=100, time_ratio=1.0, fill="row_mean"):
+        import ctypes
+        import numbers
+        set_ = lambda k, v: object.__setattr__(self, k, v)
+        for k, v in (("freq_masks", freq_masks), ("freq_width", freq_width), ("time_masks", time_masks), ("time_width", time_width)):
+            if isinstance(v, bool) or not isinstance(v, numbers.Integral):
+                raise TypeError(f"SpecAugment: {k} must be an integer (got {v!r})")
+            if v < 0:
+                raise ValueError(f"SpecAugment: {k} must be >= 0 (got {v})")
+            if k.endswith("masks") and v > self.MAX_MASKS:
+                raise ValueError(f"SpecAugment: {k} must be <= {self.MAX_MASKS} (got {v})")
+            if v > 2 ** 31 - 1:
+                raise ValueError(f"SpecAugment: {k} must be <= 2^31 - 1 (got {v})")
+            set_(k, int(v))
+        if time_ratio is None:
+            time_ratio = 1.0
+        if isinstance(time_ratio, bool) or not isinstance(time_ratio, numbers.Real):
+            raise TypeError(f"SpecAugment: time_ratio must be a real number or None (got {time_ratio!r})")
+        time_ratio = float(time_ratio)
+        if not (0.0 < ctypes.c_float(time_ratio).value and time_ratio <= 1.0):       # NaN included; it travels as fp32
+            raise ValueError(f"SpecAugment: time_ratio must lie in (0, 1] (got {time_ratio!r})")
+        set_("time_ratio", time_ratio)
+        if fill not in self.FILLS:
+            raise ValueError(f"SpecAugment: fill must be one of {self.FILLS} (got {fill!r})")
+        set_("fill", fill)
+
+    def __setattr__(self, k, v):
+        raise AttributeError("SpecAugment is immutable")
+
+    __delattr__ = __setattr__
+
+    def state(self):
+        return {k: getattr(self, k) for k in self.FIELDS}
+
+    @classmethod
+    def from_state(cls, state):
+        unknown = sorted(set(state) - set(cls.FIELDS))
+        if unknown:
+            raise ValueError(f"SpecAugment: unknown fields {unknown}")
+        return cls(**state)
+
+    @classmethod
+    def coerce(cls, value, what="spec_augment"):
+        """None, a SpecAugment or a dict of its fields -> None or a SpecAugment; anything else: TypeError."""
+        if value is None or isinstance(value, cls):
+            return value
+        if isinstance(value, dict):
+            return cls.from_state(value)
+        raise TypeError(f"{what} must be None, a features.SpecAugment or a dict of its fields (got {value!r})")
+
+    def __eq__(self, other):
+        return isinstance(other, SpecAugment) and self.state() == other.state()
+
+    def __hash__(self):
+        return hash(tuple(self.state().values()))
+
+    def __repr__(self):
+        return "SpecAugment({})".format(", ".join(f"{k}={getattr(self, k)!r}" for k in self.FIELDS))
+
+    def __call__(self, feat, lengths_or_fmask, seed, offset, utt_ids=None):
+        if not isinstance(feat, torch.Tensor) or not feat.is_cuda:
+            raise _lib.PgasrError("SpecAugment masks on the MI355X only; there is no CPU path")
+        dev = feat.device
+        lengths = lengths_or_fmask
+        if not isinstance(lengths, torch.Tensor):
+            lengths = torch.tensor(list(lengths), dtype=torch.int32)
+        if lengths.is_floating_point():          # a frame mask of 1 / 0
+            lengths = lengths.reshape(lengths.shape[0], -1).sum(dim=1)
+        lengths = lengths.to(device=dev, dtype=torch.int32).contiguous()
+        if utt_ids is not None:
+            if not isinstance(utt_ids, torch.Tensor):
+                utt_ids = torch.tensor(list(utt_ids), dtype=torch.int32)
+            utt_ids = utt_ids.to(device=dev, dtype=torch.int32).contiguous()
+        return hipops.spec_augment(feat, lengths, self, seed, offset, utt_ids=utt_ids)
+
+
 def read_wav(path):
     """PCM-16 / PCM-32 / float32 RIFF WAV -> (1-D float32 tensor in [-1,1), sample rate): the stand-in for
     ``torchaudio.load`` (data.py:53) where torchaudio is absent; first channel only, like ``.squeeze(0)`` on mono."""

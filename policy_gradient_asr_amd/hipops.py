@@ -490,6 +490,40 @@ def batch_prep(fmask, tmask, targets):
     return in_len, tg_len, tg32
 
 
+SPECAUG_FILLS = {"row_mean": 0, "zero": 1}      # PGASR_SPECAUG_FILL_*
+SPECAUG_MAX_MASKS = 8                           # csrc/specaug.hip: masks of a kind
+
+
+def spec_augment(x, lengths, policy, seed, offset, utt_ids=None, batch_offset=0, out=None, want_masks=False):
+    """SpecAugment masking of x (B,F,T) fp32 (include/pgasr_hip.h, A0-AUG): ``policy`` holds freq_masks, freq_width, time_masks,
+    time_width, time_ratio and fill (features.SpecAugment); lengths (B) int32 on the device.  The intervals are a function of
+    (seed, offset, the row's global utterance index): utt_ids (B) int32 on the device, or batch_offset + b.  Returns the masked
+    tensor -- a new one, ``out`` (contiguous fp32 of x's shape), or x itself with ``out=x`` -- and with ``want_masks`` also the
+    (B, freq_masks + time_masks, 2) int32 tensor of (start, width), frequency masks first.  No host synchronisation."""
+    lib = _lib.load()
+    _req(x, torch.float32, "x"); _req(lengths, torch.int32, "lengths"); _req(utt_ids, torch.int32, "utt_ids"); _req(out, torch.float32, "out")
+    if x.dim() != 3 or lengths.dim() != 1 or lengths.numel() != x.shape[0] or lengths.device != x.device:
+        raise _lib.PgasrError("spec_augment wants x (B,F,T) and lengths (B) on one device")
+    B, F, T = x.shape
+    if utt_ids is not None and (utt_ids.dim() != 1 or utt_ids.numel() != B or utt_ids.device != x.device):
+        raise _lib.PgasrError(f"spec_augment: utt_ids must be ({B},) int32 on {x.device}")
+    if out is None:
+        out = torch.empty_like(x)
+    elif tuple(out.shape) != (B, F, T) or out.device != x.device:
+        raise _lib.PgasrError(f"spec_augment: out must be ({B},{F},{T}) fp32 on {x.device}")
+    if policy.fill not in SPECAUG_FILLS:
+        raise ValueError(f"spec_augment: fill must be one of {sorted(SPECAUG_FILLS)} (got {policy.fill!r})")
+    nF, nT = int(policy.freq_masks), int(policy.time_masks)
+    ratio = 1.0 if policy.time_ratio is None else float(policy.time_ratio)
+    masks = torch.empty(B, nF + nT, 2, dtype=torch.int32, device=x.device) if want_masks else None
+    with _timed("spec_augment"):
+        st = lib.pgasr_spec_augment(_p(x), _p(lengths), _p(utt_ids), int(batch_offset), B, F, T, nF, int(policy.freq_width), nT,
+                                    int(policy.time_width), ratio, SPECAUG_FILLS[policy.fill], int(seed) & (2 ** 64 - 1),
+                                    int(offset) & 0xFFFFFFFF, _p(out), _p(masks), _stream())
+    _lib.check(st, "pgasr_spec_augment")
+    return (out, masks) if want_masks else out
+
+
 def ctc_collapse(paths, lengths, blank=0, out=None):
     """paths (P,T,B) int32 -> tokens (P,B,T) int32, token_lengths (P,B) int32.
     out = (tokens, token_lengths) to write into (contiguous, zero-filled tokens)."""
