@@ -46,8 +46,8 @@ typedef enum pgasr_status {
  * pgasr_adam_step_clipped), the id-addressed samplers (pgasr_frame_argmax_sample_ids, pgasr_frame_sample_multi_ids) and the
  * sequence-level score function (pgasr_ctc_hyp_workspace_bytes, pgasr_ctc_hyp_lattice, pgasr_ctc_grad_from_lattices_seq,
  * pgasr_pg_loss_value_seq) and the entropy regularisation (pgasr_frame_entropy, pgasr_ctc_grad_from_lattice_ent,
- * pgasr_ctc_grad_from_lattice_multi_ent, pgasr_ctc_grad_from_lattices_seq_ent), forced alignment (pgasr_ctc_forced_align) and
- * SpecAugment masking (pgasr_spec_augment). */
+ * pgasr_ctc_grad_from_lattice_multi_ent, pgasr_ctc_grad_from_lattices_seq_ent), forced alignment (pgasr_ctc_forced_align),
+ * SpecAugment masking (pgasr_spec_augment) and the N-best entries (pgasr_ctc_beam_search_nbest, pgasr_nbest_rescore). */
 #define PGASR_ABI_VERSION 7
 
 int pgasr_abi_version(void);
@@ -701,6 +701,55 @@ int pgasr_ctc_beam_search_lm(const void* log_probs, int is_f64, long long stride
                              int32_t* out_tokens, int32_t* out_len, double* out_score,
                              void* workspace, size_t workspace_bytes, void* stream,
                              const float* lm_table, int lm_order, double lm_alpha, double lm_beta);
+
+/* ------------------------------------------------------------------------------------------
+ * A7-NBEST  The same search returning the first `nbest` entries of its final beam instead of the best one: the reference's
+ * sorted(...)[:nbest] of the last frame (CTCdecoder.py:110-113) -- score descending, first touch among equals; the kernel's own sort,
+ * no second one.  One exception to "first touch", which a list exposes beyond rank 0: with blank != 0 an entry's unchanged ("stay")
+ * candidate and its own repeat extension can carry the same first-touch time, and where their scores are EXACTLY equal -- in
+ * practice two entries of probability zero -- the kernel may rank the stay first where the reference ranks the extension first.
+ * Arguments of pgasr_ctc_beam_search_lm (a NULL table with lm_order 0: the acoustic search), plus:
+ *   nbest:      rows to return, 1 <= nbest <= beam.
+ *   out_tokens: (nbest, B, tok_stride) int32, tok_stride >= T; out_len, out_score: (nbest, B); out_count: (B).  This is the
+ *               (K, B, stride) layout pgasr_ctc_hyp_lattice takes, so a list goes there without a copy.
+ *   count[b] = min(nbest, entries of utterance b's final beam).  Row r < count[b]: the prefix of rank r in out_tokens[r, b, :len],
+ *               zeros behind it, out_score[r, b] = -logsumexp(p_blank, p_nonblank) of that entry (+inf for an entry of probability
+ *               zero).  Rows r >= count[b]: length 0, score +inf, tokens zero.  lengths[b] == 0: count 1, the empty prefix, score -0.0.
+ *               The kernel writes every word of the four outputs: they need no initialisation.
+ *   flags bit 0: collapse_fn is applied to every hypothesis separately; rows that become equal strings are NOT merged and keep
+ *               their own scores.  Bit 1 is ignored: every call takes the workgroup-per-utterance kernel -- exact fp64 math for fp64
+ *               input, fp32 exp/log on differences for fp32 input, with or without a table.  Row 0 is therefore, bit for bit,
+ *               what pgasr_ctc_beam_search_lm returns from that kernel (flags bit 1 set, or a table given).
+ *   Every ancestor walk ends after lengths[b] steps at the latest, whatever the node store holds.
+ *   Checked before any HIP call, in this order: the search's argument checks, its limits and the LM's checks as in
+ *   pgasr_ctc_beam_search_lm; nbest < 1, nbest > beam, tok_stride < T, a NULL output -> PGASR_ERR_INVALID_ARG; then the
+ *   workspace (pgasr_beam_workspace_bytes) -> PGASR_ERR_WORKSPACE.  No host synchronisation.
+ * ---------------------------------------------------------------------------------------- */
+int pgasr_ctc_beam_search_nbest(const void* log_probs, int is_f64, long long stride_t, long long stride_b,
+                                const int32_t* lengths, int T, int B, int V, int beam, int blank, int flags,
+                                int nbest, int32_t* out_tokens, int tok_stride, int32_t* out_len, double* out_score,
+                                int32_t* out_count, void* workspace, size_t workspace_bytes, void* stream,
+                                const float* lm_table, int lm_order, double lm_alpha, double lm_beta);
+
+/* ------------------------------------------------------------------------------------------
+ * A7-RESCORE  Second pass over N-best lists: an n-gram LM score of every hypothesis, a weighted total and its rank.
+ *   tokens (N, B, tok_stride) int32, len (N, B), count (B): a list as pgasr_ctc_beam_search_nbest writes it (len is clamped to
+ *   [0, tok_stride], count to [0, N]); am (N, B) fp64: the caller's acoustic score, lower is better.
+ *   lm_table / lm_order: a table as pgasr_ctc_beam_search_lm takes it, or NULL / 0 (lm_logp = 0).  For n < count[b]:
+ *     lm_logp[n, b] = sum_i (double)lm_table[ctx(y_<i), y_i]   (the last lm_order-1 symbols, left-padded with blank; fp64 sum)
+ *     total[n, b]   = ((am_weight * am) + -(lm_alpha * lm_logp)) + -(lm_beta * len),  every product and sum rounded once.
+ *   A non-finite am, or a total that is not a number, gives total = +inf.  A symbol outside [0, V) gives lm_logp = -inf and
+ *   total = +inf (no table word is read for it).  Rows n >= count[b]: lm_logp = 0, total = +inf.
+ *   order (B, N) int32: order[b, :count[b]] = the stable ascending rank of total (ties keep the list's order), then the rows
+ *   n >= count[b] in index order.
+ *   N <= 128, V <= 64, V^lm_order <= 2^25 (else PGASR_ERR_UNSUPPORTED: a table is never truncated); NULL pointers, N < 1, B < 1,
+ *   tok_stride < 1, blank outside [0, V), a table without an order or the reverse, non-finite weights: PGASR_ERR_INVALID_ARG.
+ *   All checked before any HIP call.  One launch, one workgroup per utterance, no workspace, no host synchronisation.
+ * ---------------------------------------------------------------------------------------- */
+int pgasr_nbest_rescore(const int32_t* tokens, int tok_stride, const int32_t* len, const int32_t* count, const double* am,
+                        int N, int B, int V, int blank, const float* lm_table, int lm_order,
+                        double am_weight, double lm_alpha, double lm_beta,
+                        double* out_lm_logp, double* out_total, int32_t* out_order, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * A0-AUG  SpecAugment (Park et al., arXiv:1904.08779): time / frequency masking of a feature batch on the device.

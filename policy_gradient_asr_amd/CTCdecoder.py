@@ -1,7 +1,10 @@
 """Drop-in for the reference's CTCdecoder.py: ``CTCDecoder(alphabet).decode(probs, beam_size=100,
 blank=0) -> (tuple[int], float)`` and ``collapse_fn(str) -> str``, with the search itself running
 as a HIP kernel (csrc/beam.hip).  ``greedy_decode`` is the best-path decoder the reference lacks
-(SURVEY §8a A9)."""
+(SURVEY §8a A9).  Beyond the reference: ``nbest=N`` returns the first N entries of the final beam instead of the best one, and
+``CTCDecoder.rescore`` ranks such a list in a second pass (exact CTC likelihood and / or a stronger n-gram LM, csrc/nbest.hip)."""
+import collections
+
 import numpy as np
 import torch
 
@@ -21,6 +24,8 @@ BEAM_KMAX = 128      # csrc/beam.hip
 
 _UNSET = object()      # "use the decoder's own value" (None is a value: no language model)
 
+NBestRescored = collections.namedtuple("NBestRescored", "order total am lm_logp best_tokens best_len skipped")
+
 
 class CTCDecoder:
     def __init__(self, alphabet, device=None, lm=None, lm_alpha=0.0, lm_beta=0.0):
@@ -38,35 +43,84 @@ class CTCDecoder:
                 "lm_alpha": self.lm_alpha if lm_alpha is None else float(lm_alpha),
                 "lm_beta": self.lm_beta if lm_beta is None else float(lm_beta)}
 
-    def decode(self, probs, beam_size=100, blank=0, lm=_UNSET, lm_alpha=None, lm_beta=None):
+    def decode(self, probs, beam_size=100, blank=0, lm=_UNSET, lm_alpha=None, lm_beta=None, nbest=None):
         """probs: (time x output dim) array of PROBABILITIES (CTCdecoder.py:41-53).
         Returns (label tuple, negative log-likelihood of that prefix).  With a language model (the decoder's, or ``lm`` /
         ``lm_alpha`` / ``lm_beta`` given here; ``lm=None`` switches it off for this call) the second value is the FUSED score
         -logsumexp(p_blank, p_nonblank) with the LM bonuses in it, not a negative log-likelihood.
         Limits of the device search (the reference has none): beam_size <= 128 and at most 64 output symbols --
-        a larger request raises instead of silently searching a narrower beam."""
+        a larger request raises instead of silently searching a narrower beam.
+        nbest: None (default: the pair above) or N with 1 <= N <= beam_size: a list of (label tuple, score) pairs, the first
+        min(N, size of the final beam) entries of the final beam in the search's rank order (best first; equal scores in first-touch
+        order, like the reference's sorted(...)[:N])."""
         dev = _device(self.device)
         probs = np.asarray(probs)
         T, V = probs.shape
         if T == 0:
-            return tuple(), -0.0
+            return (tuple(), -0.0) if nbest is None else [(tuple(), -0.0)]
         with np.errstate(divide="ignore"):
             logp = np.log(probs.astype(np.float64))          # like CTCdecoder.py:55
         lp = torch.from_numpy(np.ascontiguousarray(logp)).to(dev).view(T, 1, V)
         if int(beam_size) > BEAM_KMAX:
             raise ValueError(f"beam_size {beam_size} exceeds the device search's limit of {BEAM_KMAX}")
+        if nbest is not None:
+            nb = hipops.ctc_beam_search_nbest(lp, None, beam=int(beam_size), nbest=int(nbest), blank=int(blank),
+                                              **self._lm_args(lm, lm_alpha, lm_beta))
+            tok, tl, sc = nb.tokens[:, 0].cpu(), nb.lengths[:, 0].tolist(), nb.score[:, 0].tolist()
+            return [(tuple(int(x) for x in tok[r, :tl[r]].tolist()), float(sc[r])) for r in range(int(nb.count[0].item()))]
         tokens, tl, score = hipops.ctc_beam_search(lp, None, beam=int(beam_size), blank=int(blank),
                                                    **self._lm_args(lm, lm_alpha, lm_beta))
         n = int(tl[0].item())
         return tuple(int(x) for x in tokens[0, :n].tolist()), float(score[0].item())
 
-    def decode_batch(self, log_probs, lengths=None, beam_size=5, blank=0, lm=_UNSET, lm_alpha=None, lm_beta=None):
+    def decode_batch(self, log_probs, lengths=None, beam_size=5, blank=0, lm=_UNSET, lm_alpha=None, lm_beta=None, nbest=None):
         """Device-side batched form: log_probs (T,B,V) GPU tensor of natural-log probabilities.
         Returns (tokens (B,T) int32, lengths (B) int32, nll (B) float64) without a host sync.  With a language model (see
-        ``decode``) the third value is the fused score, not a negative log-likelihood."""
+        ``decode``) the third value is the fused score, not a negative log-likelihood.
+        nbest: None (default: the triple above) or N with 1 <= N <= beam_size: ``hipops.CTCNBest`` (tokens (N,B,T), lengths (N,B),
+        score (N,B), count (B)), still without a host sync; see ``hipops.ctc_beam_search_nbest``."""
+        if nbest is not None:
+            return hipops.ctc_beam_search_nbest(log_probs, lengths, beam=int(beam_size), nbest=int(nbest), blank=int(blank),
+                                                **self._lm_args(lm, lm_alpha, lm_beta))
         return hipops.ctc_beam_search(log_probs, lengths, beam=int(beam_size), blank=int(blank),
                                       **self._lm_args(lm, lm_alpha, lm_beta))
 
+    def rescore(self, log_probs, lengths, nb, lm=_UNSET, lm_alpha=None, lm_beta=None, acoustic="ctc", am_weight=1.0, max_hyp_len=None,
+                blank=0):
+        """Second pass over an N-best list ``nb`` (``hipops.CTCNBest`` of ``decode_batch(..., nbest=N)`` on the same log_probs
+        (T,B,V) / lengths), N <= 128:  total = am_weight * am - lm_alpha * lm_logp - lm_beta * length, lower is better, with
+        lm_logp the hypothesis' log-probability under ``lm`` (the decoder's own unless given; None: no LM term).
+        acoustic="ctc" (default): am = -log p(y|x) over ALL alignments of the hypothesis (``hipops.ctc_hyp_lattice`` on fp32
+            log-probs), not the search's partial sum.  The lattices are sized by Lh = hyp_len_cap(T, max_hyp_len); with
+            max_hyp_len=None the longest hypothesis of the list is read from the device -- ONE host synchronisation, which keeps the
+            lattice workspace at the size the list needs instead of T.  Give max_hyp_len to avoid it.  A hypothesis longer than
+            Lh is not scored: it is marked in ``skipped`` and gets total = +inf.
+        acoustic="first_pass": am = nb.score, no synchronisation.  After a search fused with an LM that score already contains
+            the first pass' LM bonuses: the second LM is then added on top of them, not in their place.
+        Returns ``NBestRescored``: order (B,N) int32 -- per utterance the list's rows by ascending total, ties in first-pass order,
+        rows beyond count last --, total / am / lm_logp (N,B) float64, best_tokens (B,T) / best_len (B) int32 the row order[:, 0]
+        of every utterance, skipped (N,B) bool."""
+        if acoustic not in ("ctc", "first_pass"):
+            raise ValueError(f"acoustic must be 'ctc' or 'first_pass' (got {acoustic!r})")
+        T, B, V = log_probs.shape
+        N = nb.tokens.shape[0]
+        args = self._lm_args(lm, lm_alpha, lm_beta)
+        if acoustic == "ctc":
+            if lengths is None:
+                lengths = torch.full((B,), T, dtype=torch.int32, device=log_probs.device)
+            Lh = hipops.hyp_len_cap(T, int(nb.lengths.max().item()) if max_hyp_len is None else max_hyp_len)
+            skipped = nb.lengths > Lh
+            nll, _ = hipops.ctc_hyp_lattice(log_probs.float().contiguous(), nb.tokens, nb.lengths, lengths.to(torch.int32).contiguous(),
+                                            Lh, blank=int(blank))
+            am = torch.where(skipped, torch.full_like(nb.score, float("inf")), nll.double())
+        else:
+            skipped = torch.zeros_like(nb.lengths, dtype=torch.bool)
+            am = nb.score
+        order, total, lm_logp = hipops.nbest_rescore(nb.tokens, nb.lengths, nb.count, am.contiguous(), V, blank=int(blank), lm=args["lm"],
+                                                     am_weight=float(am_weight), lm_alpha=args["lm_alpha"], lm_beta=args["lm_beta"])
+        first = order[:, 0].long()
+        cols = torch.arange(B, device=order.device)
+        return NBestRescored(order, total, am, lm_logp, nb.tokens[first, cols].contiguous(), nb.lengths[first, cols].contiguous(), skipped)
 
     def align_batch(self, log_probs, tokens, token_lengths, lengths=None, blank=0):
         """Forced alignment on the device: log_probs (T,B,V) fp32 GPU tensor of natural-log probabilities, tokens (B,Lmax) /

@@ -112,11 +112,19 @@ template <> struct BeamLm<true> {
     double alpha, beta;
 };
 
-template <typename TIn, bool FAST, bool LM>
+// N-best emission (NBEST = true, pgasr_ctc_beam_search_nbest): the search is the same; only the result tail differs.  Its extra arguments ride
+// behind the language model's, so the kernels without it keep their argument list (and their code: NOTES.md 0.13).
+template <bool LM> struct BeamNbest : BeamLm<LM> {
+    int nbest;               // rows to write, 1 <= nbest <= K
+    int tok_stride;          // out_tokens is (nbest, B, tok_stride), tok_stride >= T
+    int32_t* out_count;      // (B) min(nbest, entries of the final beam)
+};
+
+template <typename TIn, bool FAST, bool LM, bool NBEST = false>
 __global__ __launch_bounds__(BEAM_THREADS) void beam_search_kernel(
     const TIn* __restrict__ lp, long long stride_t, long long stride_b, const int32_t* __restrict__ lengths,
     int T, int V, int K, int blank, int collapse, BeamWs ws, int32_t* __restrict__ out_tokens, int32_t* __restrict__ out_len,
-    double* __restrict__ out_score, const BeamLm<LM> lm) {
+    double* __restrict__ out_score, const typename std::conditional<NBEST, BeamNbest<LM>, BeamLm<LM>>::type lm) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int b = blockIdx.x, tid = threadIdx.x;
     int Tb = lengths ? lengths[b] : T; Tb = Tb < 0 ? 0 : (Tb > T ? T : Tb);
@@ -314,6 +322,43 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_search_kernel(
         }
         __syncthreads();
         cur = nxt;
+    }
+    if constexpr (NBEST) {
+        // ---- N-best result: the final beam is ranked (the last frame's sort IS sorted(...)[:N], CTCdecoder.py:110-113), so row r is entry r ----
+        // Thread r walks the ancestors of entry r: the chains are independent and run side by side, one chain's latency in all.  A walk ends at
+        // the root, after Tb steps (a prefix has at most one symbol per frame) or at an id outside the node store, whatever nodes[] holds.
+        // out_tokens (nbest, B, tok_stride), out_len / out_score (nbest, B): the (K, B, stride) layout of pgasr_ctc_hyp_lattice.
+        const int B = (int)gridDim.x, N = lm.nbest, S = lm.tok_stride;
+        const int count = N < s_nb ? N : s_nb;
+        int* hlen = pidx;                          // [K], free after the frame loop: the length each row was written with
+        if (tid < N) {                             // N <= K <= BEAM_KMAX < BEAM_THREADS
+            int n = 0;
+            double sc = INFINITY;                  // rows beyond count: length 0, score +inf, tokens zero
+            if (tid < count) {
+                int32_t* o = out_tokens + ((size_t)tid * B + b) * S;
+                const int head = id[cur * K + tid];
+                for (int v = head; v > 0 && v < ws.NN && n < Tb; v = (int)(nodes[v] >> 8)) ++n;
+                int v = head;
+                for (int k = n - 1; k >= 0; --k) { const unsigned w = nodes[v]; o[k] = (int32_t)(w & 0xFFu); v = (int)(w >> 8); }
+                if (collapse) {      // collapse_fn on this hypothesis alone: rows that become equal strings stay separate rows
+                    int w = 0;
+                    for (int i = 0; i < n; ++i) if (i == 0 || o[i] != o[i - 1]) { const int32_t x = o[i]; o[w++] = x; }
+                    n = w;
+                }
+                sc = -lse2x<FAST>(pb[cur * K + tid], pnb[cur * K + tid]);
+            }
+            hlen[tid] = n;
+            out_len[(size_t)tid * B + b] = n;
+            out_score[(size_t)tid * B + b] = sc;
+        }
+        if (tid == 0) lm.out_count[b] = count;
+        __threadfence_block();
+        __syncthreads();
+        for (int r = 0; r < N; ++r) {              // zero tails (and whole rows beyond count), coalesced
+            int32_t* o = out_tokens + ((size_t)r * B + b) * S;
+            for (int i = hlen[r] + tid; i < S; i += BEAM_THREADS) o[i] = 0;
+        }
+        return;
     }
     // ---- result: walk the best entry's ancestors ----
     if (tid == 0) {
@@ -823,6 +868,23 @@ extern "C" size_t pgasr_beam_workspace_bytes(int T, int B, int V, int beam) {
 }
 
 namespace {
+// the language model's arguments (no HIP call): PGASR_OK with *lm filled where lm_order > 0
+int beam_lm_args(int V, int blank, const float* lm_table, int lm_order, double lm_alpha, double lm_beta, BeamLm<true>* lm) {
+    if (lm_order < 0 || (lm_order > 0) != (lm_table != nullptr)) return PGASR_ERR_INVALID_ARG;
+    if (lm_order > 0) {
+        if (!std::isfinite(lm_alpha) || !std::isfinite(lm_beta)) return PGASR_ERR_INVALID_ARG;
+        long long entries = 1, ctx_mod = 1, ctx0 = 0;
+        for (int k = 0; k < lm_order; ++k) {
+            if (k == lm_order - 1) ctx_mod = entries;
+            entries *= V;
+            if (entries > BEAM_LM_MAX_ENTRIES) return PGASR_ERR_UNSUPPORTED;      // refused, never truncated
+        }
+        for (int k = 0; k < lm_order - 1; ++k) ctx0 = ctx0 * V + blank;
+        lm->table = lm_table; lm->ctx_mod = (int)ctx_mod; lm->ctx0 = (int)ctx0; lm->alpha = lm_alpha; lm->beta = lm_beta;
+    }
+    return PGASR_OK;
+}
+
 int beam_search_impl(const void* log_probs, int is_f64, long long stride_t, long long stride_b,
                      const int32_t* lengths, int T, int B, int V, int beam, int blank, int flags,
                      int32_t* out_tokens, int32_t* out_len, double* out_score,
@@ -832,20 +894,9 @@ int beam_search_impl(const void* log_probs, int is_f64, long long stride_t, long
     if (T <= 0 || B <= 0 || V <= 0 || beam <= 0 || blank < 0 || blank >= V) return PGASR_ERR_INVALID_ARG;
     if (V > BEAM_VMAX || beam > BEAM_KMAX) return PGASR_ERR_UNSUPPORTED;
     // the language model's arguments, before any HIP call
-    if (lm_order < 0 || (lm_order > 0) != (lm_table != nullptr)) return PGASR_ERR_INVALID_ARG;
-    const bool with_lm = lm_order > 0;
     BeamLm<true> lm{};
-    if (with_lm) {
-        if (!std::isfinite(lm_alpha) || !std::isfinite(lm_beta)) return PGASR_ERR_INVALID_ARG;
-        long long entries = 1, ctx_mod = 1, ctx0 = 0;
-        for (int k = 0; k < lm_order; ++k) {
-            if (k == lm_order - 1) ctx_mod = entries;
-            entries *= V;
-            if (entries > BEAM_LM_MAX_ENTRIES) return PGASR_ERR_UNSUPPORTED;      // refused, never truncated
-        }
-        for (int k = 0; k < lm_order - 1; ++k) ctx0 = ctx0 * V + blank;
-        lm.table = lm_table; lm.ctx_mod = (int)ctx_mod; lm.ctx0 = (int)ctx0; lm.alpha = lm_alpha; lm.beta = lm_beta;
-    }
+    if (const int st = beam_lm_args(V, blank, lm_table, lm_order, lm_alpha, lm_beta, &lm)) return st;
+    const bool with_lm = lm_order > 0;
     BeamWs ws;
     const size_t need = beam_ws_layout(T, B, beam, &ws, (char*)workspace);
     if (!workspace || workspace_bytes < need) return PGASR_ERR_WORKSPACE;
@@ -904,4 +955,51 @@ extern "C" int pgasr_ctc_beam_search_lm(const void* log_probs, int is_f64, long 
                                         const float* lm_table, int lm_order, double lm_alpha, double lm_beta) {
     return beam_search_impl(log_probs, is_f64, stride_t, stride_b, lengths, T, B, V, beam, blank, flags, out_tokens, out_len, out_score,
                             workspace, workspace_bytes, stream, lm_table, lm_order, lm_alpha, lm_beta);
+}
+
+// The N-best list of the final beam (include/pgasr_hip.h, A7-NBEST): always the workgroup-per-utterance kernel, NBEST = true.
+extern "C" int pgasr_ctc_beam_search_nbest(const void* log_probs, int is_f64, long long stride_t, long long stride_b,
+                                           const int32_t* lengths, int T, int B, int V, int beam, int blank, int flags,
+                                           int nbest, int32_t* out_tokens, int tok_stride, int32_t* out_len, double* out_score,
+                                           int32_t* out_count, void* workspace, size_t workspace_bytes, void* stream,
+                                           const float* lm_table, int lm_order, double lm_alpha, double lm_beta) {
+    // the search's own checks, in the order of pgasr_ctc_beam_search_lm
+    if (!log_probs || !out_tokens || !out_len || !out_score) return PGASR_ERR_INVALID_ARG;
+    if (T <= 0 || B <= 0 || V <= 0 || beam <= 0 || blank < 0 || blank >= V) return PGASR_ERR_INVALID_ARG;
+    if (V > BEAM_VMAX || beam > BEAM_KMAX) return PGASR_ERR_UNSUPPORTED;
+    BeamLm<true> lmb{};
+    if (const int st = beam_lm_args(V, blank, lm_table, lm_order, lm_alpha, lm_beta, &lmb)) return st;
+    // the list's
+    if (nbest < 1 || nbest > beam || tok_stride < T || !out_count) return PGASR_ERR_INVALID_ARG;
+    BeamWs ws;
+    const size_t need = beam_ws_layout(T, B, beam, &ws, (char*)workspace);
+    if (!workspace || workspace_bytes < need) return PGASR_ERR_WORKSPACE;
+    if ((long long)T * beam + 1 >= (1ll << 24)) return PGASR_ERR_UNSUPPORTED;
+    const bool with_lm = lm_order > 0;
+    const size_t lds = beam_lds_bytes(beam, V, with_lm);
+    if (lds > 160 * 1024) return PGASR_ERR_UNSUPPORTED;
+    hipStream_t st = (hipStream_t)stream;
+    if (hipMemsetAsync(ws.table, 0, (size_t)B * ws.H * sizeof(unsigned long long), st) != hipSuccess) return PGASR_ERR_LAUNCH;
+    const int collapse = flags & 1;
+    BeamNbest<true> nl{};
+    static_cast<BeamLm<true>&>(nl) = lmb;
+    nl.nbest = nbest; nl.tok_stride = tok_stride; nl.out_count = out_count;
+    BeamNbest<false> nn{};
+    nn.nbest = nbest; nn.tok_stride = tok_stride; nn.out_count = out_count;
+#define BEAM_NBEST_LAUNCH(TIN, FAST, LMB, ARG)                                                                                    \
+    {                                                                                                                             \
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&beam_search_kernel<TIN, FAST, LMB, true>),                       \
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                          \
+        PGASR_LAUNCH_KERNEL((beam_search_kernel<TIN, FAST, LMB, true>), dim3(B), dim3(BEAM_THREADS), lds, st,                     \
+                           (const TIN*)log_probs, stride_t, stride_b, lengths, T, V, beam, blank, collapse, ws, out_tokens,       \
+                           out_len, out_score, ARG);                                                                              \
+    }
+    if (with_lm) {
+        if (is_f64) BEAM_NBEST_LAUNCH(double, false, true, nl) else BEAM_NBEST_LAUNCH(float, true, true, nl)
+    } else {
+        if (is_f64) BEAM_NBEST_LAUNCH(double, false, false, nn) else BEAM_NBEST_LAUNCH(float, true, false, nn)
+    }
+#undef BEAM_NBEST_LAUNCH
+    PGASR_CHECK_LAUNCH();
+    return PGASR_OK;
 }

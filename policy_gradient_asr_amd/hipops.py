@@ -1188,6 +1188,78 @@ def ctc_beam_search(log_probs, lengths=None, beam=5, blank=0, collapse=False, ou
     return tokens, tl, score
 
 
+CTCNBest = collections.namedtuple("CTCNBest", "tokens lengths score count")
+NBEST_RESCORE_MAX = 128          # csrc/nbest.hip: hypotheses per utterance
+
+
+def _lm_table(lm, V, blank, device):
+    if lm is None:
+        return None, 0
+    if lm.vocab != V or lm.blank != int(blank):
+        raise ValueError(f"the LM is over {lm.vocab} symbols with blank {lm.blank}; the search has {V} symbols and blank {int(blank)}")
+    return lm.device_table(device), lm.order
+
+
+def ctc_beam_search_nbest(log_probs, lengths=None, beam=5, nbest=1, blank=0, collapse=False, lm=None, lm_alpha=0.0, lm_beta=0.0):
+    """The first ``nbest`` entries of the search's final beam (pgasr_ctc_beam_search_nbest): log_probs (T,B,V) fp32 or fp64 as
+    ``ctc_beam_search`` takes them, 1 <= nbest <= beam.  Returns ``CTCNBest`` of device tensors, no host synchronisation:
+    tokens (N,B,T) int32 (zero behind each hypothesis), lengths (N,B) int32, score (N,B) float64 = -logsumexp(p_blank, p_nonblank)
+    of the entry (a FUSED score with ``lm``), count (B) int32 = min(nbest, size of the final beam).  Rank order is the search's own:
+    score ascending (probability descending), first touch among equals (with blank != 0 two entries of exactly equal score -- in
+    practice of probability zero -- can swap against the reference: include/pgasr_hip.h, A7-NBEST).  Rows beyond count: length 0, score +inf, tokens zero.
+    collapse: collapse_fn on each hypothesis separately -- rows that become equal strings are NOT merged.
+    Every call takes the workgroup-per-utterance kernel (fp64 math for fp64 input, the fast path for fp32): row 0 is bit for bit
+    ``ctc_beam_search(generic=True)``, or ``ctc_beam_search(lm=...)`` with a language model.  (N,B,T) is the (K,B,stride) layout
+    ``ctc_hyp_lattice`` takes."""
+    lib = _lib.load()
+    if not log_probs.is_cuda or log_probs.dtype not in (torch.float32, torch.float64):
+        raise _lib.PgasrError("log_probs must be a float32/float64 GPU tensor")
+    if log_probs.stride(2) != 1:
+        raise _lib.PgasrError("log_probs must be contiguous in its last dimension")
+    T, B, V = log_probs.shape
+    _req(lengths, torch.int32, "lengths")
+    lm_table, lm_order = _lm_table(lm, V, blank, log_probs.device)
+    N, dev = int(nbest), log_probs.device
+    ws = _workspace(lib.pgasr_beam_workspace_bytes(T, B, V, int(beam)), dev, "beam")
+    tokens = torch.empty(max(N, 0), B, T, dtype=torch.int32, device=dev)      # the kernel writes every word
+    tl = torch.empty(max(N, 0), B, dtype=torch.int32, device=dev)
+    score = torch.empty(max(N, 0), B, dtype=torch.float64, device=dev)
+    count = torch.empty(B, dtype=torch.int32, device=dev)
+    with _timed("beam_search_nbest"):
+        st = lib.pgasr_ctc_beam_search_nbest(_p(log_probs), int(log_probs.dtype == torch.float64), log_probs.stride(0),
+                                             log_probs.stride(1), _p(lengths), T, B, V, int(beam), int(blank), int(bool(collapse)),
+                                             N, _p(tokens), T, _p(tl), _p(score), _p(count), _p(ws), ws.numel(), _stream(),
+                                             _p(lm_table), lm_order, float(lm_alpha), float(lm_beta))
+    _lib.check(st, "pgasr_ctc_beam_search_nbest")
+    return CTCNBest(tokens, tl, score, count)
+
+
+def nbest_rescore(tokens, lengths, count, am, vocab, blank=0, lm=None, am_weight=1.0, lm_alpha=0.0, lm_beta=0.0):
+    """Second pass over N-best lists (pgasr_nbest_rescore): tokens (N,B,stride) / lengths (N,B) / count (B) int32 as
+    ``ctc_beam_search_nbest`` returns them, am (N,B) float64 acoustic scores (lower is better), ``vocab`` the number of symbols.
+    Returns (order (B,N) int32, total (N,B) float64, lm_logp (N,B) float64), no host synchronisation:
+    lm_logp = the hypothesis' log-probability under ``lm`` (0 without one), total = am_weight * am - lm_alpha * lm_logp -
+    lm_beta * length (lower is better; +inf for a non-finite am and for rows beyond count), order[b] = the stable ascending
+    rank of total over the utterance's count hypotheses (ties keep the list's order), then the remaining rows.  N <= 128."""
+    lib = _lib.load()
+    _req(tokens, torch.int32, "tokens"); _req(lengths, torch.int32, "lengths"); _req(count, torch.int32, "count")
+    _req(am, torch.float64, "am")
+    if tokens.dim() != 3 or tuple(lengths.shape) != tuple(tokens.shape[:2]) or tuple(am.shape) != tuple(tokens.shape[:2]) \
+            or count.numel() != tokens.shape[1]:
+        raise _lib.PgasrError("nbest_rescore wants tokens (N,B,stride), lengths (N,B), am (N,B) and count (B)")
+    N, B, stride = tokens.shape
+    lm_table, lm_order = _lm_table(lm, int(vocab), blank, tokens.device)
+    order = torch.empty(B, N, dtype=torch.int32, device=tokens.device)
+    total = torch.empty(N, B, dtype=torch.float64, device=tokens.device)
+    lm_logp = torch.empty(N, B, dtype=torch.float64, device=tokens.device)
+    with _timed("nbest_rescore"):
+        st = lib.pgasr_nbest_rescore(_p(tokens), stride, _p(lengths), _p(count), _p(am), N, B, int(vocab), int(blank),
+                                     _p(lm_table), lm_order, float(am_weight), float(lm_alpha), float(lm_beta),
+                                     _p(lm_logp), _p(total), _p(order), _stream())
+    _lib.check(st, "pgasr_nbest_rescore")
+    return order, total, lm_logp
+
+
 # ------------------------------------------------------------------------------------------
 # dropout / Adam
 # ------------------------------------------------------------------------------------------

@@ -64,6 +64,23 @@ def edit_counts(targets, tg_len, tokens, tok_len, delimiter):
     return cd, tg_len, wd, wc
 
 
+def nbest_oracle(targets, tg_len, nb):
+    """The best the list could have done: targets (B,L) / tg_len (B) int32 on the GPU, ``nb`` a ``hipops.CTCNBest``.
+    Returns (min character edit distance over the utterance's count hypotheses (B) int32, the first rank that reaches it (B) int32),
+    on the device without a host round trip: one ``hipops.edit_distance`` launch over the N * B (target, hypothesis) pairs.
+    Oracle CER = distance / tg_len; a rank > 0 says the search had a better hypothesis than the one it ranked first."""
+    N, B, T = nb.tokens.shape
+    L = targets.shape[1]
+    ref = targets.unsqueeze(0).expand(N, B, L).reshape(N * B, L).contiguous()
+    ref_len = tg_len.unsqueeze(0).expand(N, B).reshape(N * B).contiguous()
+    dist = hipops.edit_distance(ref, ref_len, nb.tokens.reshape(N * B, T), nb.lengths.reshape(N * B)).view(N, B)
+    rows = torch.arange(N, dtype=torch.int32, device=dist.device).unsqueeze(1)
+    dist = torch.where(rows < nb.count.unsqueeze(0), dist, torch.full_like(dist, torch.iinfo(torch.int32).max))
+    best = dist.min(0).values
+    rank = torch.where(dist == best.unsqueeze(0), rows.expand(N, B), torch.full_like(dist, N)).min(0).values
+    return best, rank
+
+
 def frame_entropy(log_probs, in_len):
     """Mean frame entropy of the policy per utterance: log_probs (T,B,V) fp32 log-softmax outputs and in_len (B) int32 on the GPU ->
     (B,) fp32 on the device, the mean over each utterance's own frames of H = -sum_v p ln p in nats (0 for an empty utterance;

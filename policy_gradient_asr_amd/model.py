@@ -371,14 +371,24 @@ def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset
 
 
 def predict(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=None, maxlent=None, device_id=0,
-            test_dataset=None, n_feats=120, beam_size=5, features="mfcc", lm_path=None, lm_alpha=0.0, lm_beta=0.0):
+            test_dataset=None, n_feats=120, beam_size=5, features="mfcc", lm_path=None, lm_alpha=0.0, lm_beta=0.0,
+            nbest=1, rescore_lm_path=None, rescore_alpha=0.0, rescore_beta=0.0):
     """model.py:277-339: load model_best.pth, forward, beam=5 prefix search (device side, batched),
     collapse_fn, CER/WER, predicted.txt.  Frames are cut by the FEATURE mask (the reference cuts the
     time axis by the target mask, model.py:322 -- a listed defect).  Returns (CER, WER).
     features: the front end for items that carry waveforms, as in ``train`` ("mfcc": n_feats=120, "logmel80": n_feats=80);
     the features stay on the device.
     lm_path: None (default) or an ``lm.npz`` written by ``build_lm`` / ``CharNgramLM.save``: the beam search then adds
-    lm_alpha * ln p_lm(s | context) + lm_beta to every extension by a character s (CTCDecoder)."""
+    lm_alpha * ln p_lm(s | context) + lm_beta to every extension by a character s (CTCDecoder).
+    nbest: 1 (default: the calls above, nothing else) or N with 2 <= N <= beam_size: the search returns its N best hypotheses per
+    utterance (``decode_batch(nbest=N)``), all of them go to ``nbest.tsv`` in model_path -- utterance, rank, first-pass score, second-pass
+    total (empty when not rescored), collapsed text, tab-separated -- and the oracle CER (the best hypothesis of every list) is
+    printed beside the CER of the chosen one.  rescore_lm_path: None, or an ``lm.npz`` for a second pass over the lists
+    (``CTCDecoder.rescore`` with the exact CTC likelihood as acoustic score, total = nll - rescore_alpha * ln p_lm - rescore_beta *
+    length): the hypothesis with the lowest total is the one written to predicted.txt and scored.  Without it rank 0 is.
+    With nbest > 1 every list comes from the workgroup-per-utterance kernel: rank 0 is ``ctc_beam_search(generic=True)``'s result,
+    while nbest = 1 without an LM takes the single-wave fp32 kernel for beam_size <= 16.  The two agree to ~1e-7 relative in their
+    scores, so their hypotheses can differ only where two candidates are closer than that."""
     import os
     import functools
     import torch.utils.data as tud
@@ -386,8 +396,13 @@ def predict(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=N
     from .lm import CharNgramLM
     from .data import Data
     from .data import collate_custom as _collate
-    from .metrics import evaluate, save_predictions
+    from .metrics import edit_dist_batch, evaluate, save_predictions
 
+    nbest = int(nbest)
+    if nbest < 1 or nbest > int(beam_size):
+        raise ValueError(f"nbest must lie in [1, beam_size = {beam_size}] (got {nbest})")
+    if rescore_lm_path is not None and nbest < 2:
+        raise ValueError("rescoring needs a list: give nbest >= 2 with rescore_lm_path")
     alphabet, char2ind = _read_alphabet(alphabet_path)
     ind2char = {char2ind[k]: k for k in char2ind}
     dev = torch.device("cuda", device_id)
@@ -401,7 +416,9 @@ def predict(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=N
     loader = tud.DataLoader(test_dataset, batch_size=batch_size, shuffle=False, collate_fn=collate_custom)
     lm = CharNgramLM.load(lm_path) if lm_path is not None else None
     decoder = CTCDecoder(alphabet, lm=lm, lm_alpha=lm_alpha, lm_beta=lm_beta)
+    rescore_lm = CharNgramLM.load(rescore_lm_path) if rescore_lm_path is not None else None
     targets, predicted, tot_cer, tot_wer, n = [], [], 0.0, 0.0, 0
+    nbest_lines, tot_oracle = [], 0.0
     print("Total number of examples: ", len(test_dataset))
     with torch.no_grad():
         for step, batch in enumerate(loader, 1):
@@ -409,7 +426,30 @@ def predict(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=N
             x, t, fmask, tmask = _to_device(batch, dev)
             logits, in_len = model.logits(x, fmask)
             lp = Fh.LogSoftmaxFn.apply(logits)
-            tok, tl, _ = decoder.decode_batch(lp, in_len, beam_size=beam_size)
+            if nbest > 1:
+                nb = decoder.decode_batch(lp, in_len, beam_size=beam_size, nbest=nbest)
+                tok, tl, total = nb.tokens[0], nb.lengths[0], None
+                if rescore_lm is not None:
+                    rs = decoder.rescore(lp, in_len, nb, lm=rescore_lm, lm_alpha=rescore_alpha, lm_beta=rescore_beta)
+                    tok, tl, total = rs.best_tokens, rs.best_len, rs.total.cpu()
+                # every hypothesis through collapse_fn on the host (the list is copied once); the oracle is over these strings,
+                # one edit-distance launch per batch
+                ntok, nlen, nscore, ncount = nb.tokens.cpu(), nb.lengths.cpu(), nb.score.cpu(), nb.count.cpu()
+                t_h, tlen_h = t.cpu(), tmask.sum(1).cpu()
+                refs, hyps, owner = [], [], []
+                for i in range(ntok.shape[1]):
+                    target = "".join(ind2char[int(k)] for k in t_h[i][:int(tlen_h[i])])
+                    for r in range(int(ncount[i])):
+                        text = collapse_fn("".join(ind2char[int(k)] for k in ntok[r, i, :nlen[r, i]]))
+                        refs.append(target); hyps.append(text); owner.append(i)
+                        nbest_lines.append("{}\t{}\t{:.6f}\t{}\t{}\n".format(n + i, r, float(nscore[r, i]),
+                                                                          "" if total is None else "{:.6f}".format(float(total[r, i])), text))
+                best = {}
+                for i, d in zip(owner, edit_dist_batch(refs, hyps, device=dev)):
+                    best[i] = min(d, best.get(i, d))
+                tot_oracle += sum(d / max(int(tlen_h[i]), 1) for i, d in best.items())
+            else:
+                tok, tl, _ = decoder.decode_batch(lp, in_len, beam_size=beam_size)
             tok, tl, t, tmask = tok.cpu(), tl.cpu(), t.cpu(), tmask.cpu()
             for i in range(tok.shape[0]):
                 seq = collapse_fn("".join(ind2char[int(k)] for k in tok[i, :tl[i]]))
@@ -419,7 +459,12 @@ def predict(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=N
                 tot_cer += cer; tot_wer += wer; n += 1
     save_predictions(targets, predicted, model_path)
     cer, wer = tot_cer / max(n, 1), tot_wer / max(n, 1)
-    print("CER: {:>4f} WER: {:>4f}".format(cer, wer))
+    if nbest > 1:
+        with open(os.path.join(model_path, "nbest.tsv"), "w") as fo:
+            fo.writelines(nbest_lines)
+        print("CER: {:>4f} WER: {:>4f} Oracle CER ({}-best): {:>4f}".format(cer, wer, nbest, tot_oracle / max(n, 1)))
+    else:
+        print("CER: {:>4f} WER: {:>4f}".format(cer, wer))
     return cer, wer
 
 
