@@ -66,6 +66,9 @@ const char* pgasr_status_string(int status);
  *               utterances whose nll is +inf.  utt_scale may be NULL (= 1).
  *   If pg_coef and pg_path are non-NULL the REINFORCE term of pgasr_reinforce_grad is
  *   added in the same pass (A12):  + pg_coef[b] * (softmax - onehot(pg_path[t,b])).
+ *   log_probs may hold -inf (a symbol of probability exactly 0 at that frame, e.g. a masked vocabulary): such a symbol has
+ *   occupancy 0 and gradient entry 0 -- in this entry and in every gradient pass below -- and a target that needs it at every
+ *   frame has no alignment (nll = +inf, zero gradient).  Held to the fp64 oracle by tests/test_ctc_numerics_gpu.py.
  *   Limits: 2*Lmax+1 <= 2048, V <= 64.
  * ---------------------------------------------------------------------------------------- */
 size_t pgasr_ctc_workspace_bytes(int T, int B, int V, int Lmax);

@@ -84,7 +84,11 @@ def ctc_alpha_beta(lp, target, blank=0):
 def ctc_loss_and_grad(logits, targets, input_lengths, target_lengths, blank=0):
     """logits (T,B,V) any float; targets (B,Lmax) int (pad ignored);
     returns nll (B,) float64, grad (T,B,V) float64 = d sum_b nll_b / d logits,
-    zero for frames t >= input_lengths[b] (same as torch's ctc_loss backward)."""
+    zero for frames t >= input_lengths[b] (same as torch's ctc_loss backward).
+
+    A logit of -inf is a symbol of probability exactly 0 at that frame (a masked vocabulary).  No alignment passes through it,
+    so its occupancy is 0 and its gradient entry exp(lp) - 0 = 0: the limit of the expression below as the logit goes to -inf,
+    which itself reads exp(-inf + nll + inf) there.  An utterance without frames has nll 0 for an empty target, +inf otherwise."""
     logits = np.asarray(logits, dtype=np.float64)
     T, B, V = logits.shape
     lp_all = log_softmax(logits, axis=2)
@@ -93,6 +97,9 @@ def ctc_loss_and_grad(logits, targets, input_lengths, target_lengths, blank=0):
     for b in range(B):
         Tb = int(input_lengths[b])
         Lb = int(target_lengths[b])
+        if Tb == 0:
+            nll[b] = 0.0 if Lb == 0 else np.inf
+            continue
         lp = lp_all[:Tb, b]
         tgt = np.asarray(targets[b][:Lb], dtype=np.int64)
         alpha, beta, nll_b, ext = ctc_alpha_beta(lp, tgt, blank)
@@ -105,8 +112,9 @@ def ctc_loss_and_grad(logits, targets, input_lengths, target_lengths, blank=0):
         occ = np.full((Tb, V), NEG_INF)
         for s in range(len(ext)):
             occ[:, ext[s]] = _lse2(occ[:, ext[s]], ab[:, s])
-        with np.errstate(over="ignore"):
-            grad[:Tb, b] = np.exp(lp) - np.exp(occ + nll_b - lp)
+        with np.errstate(over="ignore", invalid="ignore"):
+            post = np.exp(occ + nll_b - lp)
+        grad[:Tb, b] = np.exp(lp) - np.where(np.isneginf(lp), 0.0, post)
     return nll, grad
 
 

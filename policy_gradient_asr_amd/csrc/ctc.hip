@@ -337,9 +337,12 @@ __device__ __forceinline__ float ctc_grad_row(float lpv, float sm, int lane, int
         const float* be = ws.beta + ((size_t)b * T + t) * ws.SP;
         // log occupancy of state s = (alpha offset + beta offset) + [row maxima + nll - log p]: the bracket is O(10)
         const double cst = ws.amax[(size_t)b * T + t] + ws.bmax[(size_t)b * T + t] + nll;
+        // A symbol of probability exactly 0 at this frame (log p = -inf, a masked vocabulary) has occupancy 0: every state that
+        // carries it holds alpha = beta = -inf, and the constant would read +inf -- -inf + inf = NaN, for the blank in all lanes
+        // through wave_sum.  A select on the constant: exp(-inf + 0) = 0.  A finite log p keeps its bits.
         // blank occupancy: even states, all lanes, fixed butterfly order
         const float lpb = __shfl(lpv, blank, 64);
-        const float cb = (float)(cst - (double)lpb);
+        const float cb = (lpb == -INFINITY) ? 0.f : (float)(cst - (double)lpb);
         float accb = 0.f;
         for (int s = 2 * lane; s < S; s += 128)
             accb += __expf((al[s] + be[s]) + cb);
@@ -349,7 +352,7 @@ __device__ __forceinline__ float ctc_grad_row(float lpv, float sm, int lane, int
             const int32_t* lo = ws.lab_off + (size_t)b * (V + 1);
             const int32_t* ls = ws.lab_states + (size_t)b * Smax;
             float acc = 0.f;
-            const float cl = (float)(cst - (double)lpv);
+            const float cl = (lpv == -INFINITY) ? 0.f : (float)(cst - (double)lpv);
             for (int i = lo[lane]; i < lo[lane + 1]; ++i) {
                 const int s = ls[i];
                 acc += __expf((al[s] + be[s]) + cl);
