@@ -47,7 +47,8 @@ typedef enum pgasr_status {
  * sequence-level score function (pgasr_ctc_hyp_workspace_bytes, pgasr_ctc_hyp_lattice, pgasr_ctc_grad_from_lattices_seq,
  * pgasr_pg_loss_value_seq) and the entropy regularisation (pgasr_frame_entropy, pgasr_ctc_grad_from_lattice_ent,
  * pgasr_ctc_grad_from_lattice_multi_ent, pgasr_ctc_grad_from_lattices_seq_ent), forced alignment (pgasr_ctc_forced_align),
- * SpecAugment masking (pgasr_spec_augment) and the N-best entries (pgasr_ctc_beam_search_nbest, pgasr_nbest_rescore). */
+ * SpecAugment masking (pgasr_spec_augment), the N-best entries (pgasr_ctc_beam_search_nbest, pgasr_nbest_rescore) and MWER training
+ * over them (pgasr_mwer_weights, pgasr_ctc_grad_from_lattices_nbest). */
 #define PGASR_ABI_VERSION 7
 
 int pgasr_abi_version(void);
@@ -720,9 +721,14 @@ int pgasr_ctc_beam_search_lm(const void* log_probs, int is_f64, long long stride
  *               zero).  Rows r >= count[b]: length 0, score +inf, tokens zero.  lengths[b] == 0: count 1, the empty prefix, score -0.0.
  *               The kernel writes every word of the four outputs: they need no initialisation.
  *   flags bit 0: collapse_fn is applied to every hypothesis separately; rows that become equal strings are NOT merged and keep
- *               their own scores.  Bit 1 is ignored: every call takes the workgroup-per-utterance kernel -- exact fp64 math for fp64
- *               input, fp32 exp/log on differences for fp32 input, with or without a table.  Row 0 is therefore, bit for bit,
- *               what pgasr_ctc_beam_search_lm returns from that kernel (flags bit 1 set, or a table given).
+ *               their own scores.  Bit 1 is ignored: without bit 3 every call takes the workgroup-per-utterance kernel -- exact fp64
+ *               math for fp64 input, fp32 exp/log on differences for fp32 input, with or without a table.  Row 0 is therefore, bit for
+ *               bit, what pgasr_ctc_beam_search_lm returns from that kernel (flags bit 1 set, or a table given).
+ *   flags bit 3 (value 8, "fast"): the call may take the single-wave kernel of the train step, exactly where the 1-best dispatch of
+ *               pgasr_ctc_beam_search would: no table, fp32 input, beam <= 16, V <= 64, T * beam <= 24576, T <= 4096.  Row 0 is
+ *               then, bit for bit, what pgasr_ctc_beam_search returns by default; the list is that kernel's final beam in its rank
+ *               order, lane r of the wave walking entry r's ancestors through the trie in LDS.  Outside those conditions the bit
+ *               changes nothing: the call is the call without it, launch for launch.  Every refusal below is the same with the bit.
  *   Every ancestor walk ends after lengths[b] steps at the latest, whatever the node store holds.
  *   Checked before any HIP call, in this order: the search's argument checks, its limits and the LM's checks as in
  *   pgasr_ctc_beam_search_lm; nbest < 1, nbest > beam, tok_stride < T, a NULL output -> PGASR_ERR_INVALID_ARG; then the
@@ -753,6 +759,44 @@ int pgasr_nbest_rescore(const int32_t* tokens, int tok_stride, const int32_t* le
                         int N, int B, int V, int blank, const float* lm_table, int lm_order,
                         double am_weight, double lm_alpha, double lm_beta,
                         double* out_lm_logp, double* out_total, int32_t* out_order, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * A13-MWER  Minimum word error rate training over the N-best list of the beam search (Prabhavalkar et al., arXiv:1712.01818): the
+ * model's probability renormalised over the N hypotheses the decoder returns, and the expected risk under that distribution.
+ * Nothing is sampled.  With a list as pgasr_ctc_beam_search_nbest writes it WITHOUT collapse (raw prefixes are distinct label
+ * sequences), hyp_nll (N,B) = the exact -log p(y_n | x) of pgasr_ctc_hyp_lattice (not the first-pass beam score, which lacks the
+ * pruned mass), dist (N,B) the (word) edit distances to the target and risk_len (B) the target's characters (or words):
+ *     valid(n,b) := n < count[b]  and  hyp_len[n,b] <= Lh  and  hyp_nll[n,b] finite
+ *     m_b        =  min over valid n of hyp_nll[n,b]
+ *     p[n,b]     =  exp(-(hyp_nll[n,b] - m_b)) / sum_valid exp(-(hyp_nll - m_b))              0 where not valid
+ *     r[n,b]     =  dist[n,b] / max(risk_len[b], 1)
+ *     rbar[b]    =  sum_n p[n,b] r[n,b]
+ *     coef[n,b]  =  -lam * inv_global_batch * p[n,b] * (r[n,b] - rbar[b])                     the factor of d nll_n / d logits
+ *     utt_scale[b] = inv_global_batch / max(target_lengths[b], 1)                             as pgasr_pg_rewards leaves it
+ *     terms[b]   =  nll[b] * utt_scale[b] + lam * inv_global_batch * rbar[b]                  the CTC part as pgasr_pg_loss_value forms it
+ *     objective  =  sum_b terms[b]
+ *     d(logits)  =  utt_scale_b (softmax - occ_target) + sum_n coef[n,b] (softmax - occ_{y_n}),  the N terms in n order
+ * sum_n coef[n,b] = 0.  No valid entry: p = coef = 0, rbar = 0.
+ *
+ * pgasr_mwer_weights: all six outputs (fp32; p, r, coef (N,B); utt_scale, rbar, terms (B)) in one launch, one thread per utterance,
+ *   fp64 arithmetic with the sums in n order: run-to-run reproducible, no host synchronisation.  N outside 1..PGASR_MAX_SAMPLES,
+ *   B < 1, Lh < 0, null pointers, lam or inv_global_batch not finite, inv_global_batch <= 0: PGASR_ERR_INVALID_ARG before any HIP call.
+ * pgasr_ctc_grad_from_lattices_nbest: pgasr_ctc_grad_from_lattices_seq without a path tensor (its kernel with the path branch
+ *   compiled out): the gradient above in one pass over the target lattice in `workspace` and the N*B hypothesis lattices in
+ *   `hyp_workspace` (pgasr_ctc_hyp_lattice with K = N, same T, B, V, Lh and the SAME hyp_len).  A pair with hyp_len > Lh has no
+ *   lattice and adds nothing; give pgasr_ctc_hyp_lattice and this entry a length of 0 for every pair that is over the cap or beyond
+ *   count, so that every lattice in the workspace is really computed (the empty hypothesis') and meets a coefficient of 0.
+ *   Checks and limits as pgasr_ctc_grad_from_lattices_seq, before any HIP call.
+ * ---------------------------------------------------------------------------------------- */
+int pgasr_mwer_weights(const int32_t* dist, const int32_t* risk_len, const int32_t* target_lengths, const float* hyp_nll,
+                       const int32_t* hyp_len, const int32_t* count, const float* nll, int N, int B, int Lh,
+                       float lam, float inv_global_batch, float* p, float* r, float* coef, float* utt_scale,
+                       float* rbar, float* terms, void* stream);
+int pgasr_ctc_grad_from_lattices_nbest(const float* log_probs, const int32_t* input_lengths, const int32_t* target_lengths,
+                                       int T, int B, int V, int Lmax, int blank, const float* utt_scale,
+                                       int N, const float* coef, const int32_t* hyp_len, int Lh,
+                                       float* grad_logits, void* workspace, size_t workspace_bytes,
+                                       void* hyp_workspace, size_t hyp_workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * A0-AUG  SpecAugment (Park et al., arXiv:1904.08779): time / frequency masking of a feature batch on the device.

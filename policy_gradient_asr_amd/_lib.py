@@ -88,6 +88,11 @@ SIGNATURES = {
                                               c_ptr, C.c_size_t, c_ptr, c_f32p, C.c_int, C.c_double, C.c_double]),
     "pgasr_nbest_rescore": (C.c_int, [c_i32p, C.c_int, c_i32p, c_i32p, c_ptr, C.c_int, C.c_int, C.c_int, C.c_int, c_f32p, C.c_int,
                                       C.c_double, C.c_double, C.c_double, c_ptr, c_ptr, c_i32p, c_ptr]),
+    "pgasr_mwer_weights": (C.c_int, [c_i32p, c_i32p, c_i32p, c_f32p, c_i32p, c_i32p, c_f32p, C.c_int, C.c_int, C.c_int,
+                                     C.c_float, C.c_float, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_ptr]),
+    "pgasr_ctc_grad_from_lattices_nbest": (C.c_int, [c_f32p, c_i32p, c_i32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_f32p,
+                                                     C.c_int, c_f32p, c_i32p, C.c_int, c_f32p, c_ptr, C.c_size_t,
+                                                     c_ptr, C.c_size_t, c_ptr]),
     "pgasr_dropout": (C.c_int, [c_f32p, c_f32p, C.c_ulonglong, C.c_float, C.c_uint64, C.c_uint32, c_f32p, C.c_float, c_ptr]),
     "pgasr_spec_augment": (C.c_int, [c_f32p, c_i32p, c_i32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                      C.c_float, C.c_int, C.c_ulonglong, C.c_uint, c_f32p, c_i32p, c_ptr]),

@@ -502,11 +502,20 @@ __device__ __forceinline__ unsigned wave_allmax(unsigned v) {
                       k[a] = ((unsigned long long)(sw_ ? yh_ : xh_) << 32) | (sw_ ? yl_ : xl_);                                    \
                       k[b] = ((unsigned long long)(sw_ ? xh_ : yh_) << 32) | (sw_ ? xl_ : yl_); }
 
-template <int SPL>
+// N-best tail (NBEST = true, the "fast" bit of pgasr_ctc_beam_search_nbest): the search is the same; the list's arguments take the
+// place of the last argument, so the NBEST = false instantiations -- what the train step runs -- keep their argument list and code.
+struct SmallNbest {
+    double* out_score;       // (nbest, B)
+    int32_t* out_count;      // (B) min(nbest, entries of the final beam)
+    int nbest;               // rows to write, 1 <= nbest <= K
+    int tok_stride;          // out_tokens is (nbest, B, tok_stride), tok_stride >= T
+};
+
+template <int SPL, bool NBEST = false>
 __global__ __launch_bounds__(64) void beam_small_kernel(
     const float* __restrict__ lp, long long stride_t, long long stride_b, const int32_t* __restrict__ lengths,
     int T, int V, int K, int blank, int collapse, int32_t* __restrict__ out_tokens, int32_t* __restrict__ out_len,
-    double* __restrict__ out_score) {
+    typename std::conditional<NBEST, const SmallNbest, double* __restrict__>::type out_score) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned* table = reinterpret_cast<unsigned*>(smem);
     static_assert(SPL == 8 || SPL == 16, "8 or 16 symbols per lane");
@@ -813,6 +822,48 @@ __global__ __launch_bounds__(64) void beam_small_kernel(
         nb = nnew;
     }
 
+    if constexpr (NBEST) {
+        // ---- result: the first nbest entries of the final beam.  Lane r < count of row 0 holds entry r (rank order) and walks its
+        // own ancestors through the table twice: once to count (with collapse, kept tokens only: a token is dropped when the one before
+        // it is the same), once to write back to front.  Every walk ends at the root, at an id outside the table or after T_b steps.
+        __syncthreads();
+        const int B = (int)gridDim.x, N = out_score.nbest, S = out_score.tok_stride;
+        const int count = N < nb ? N : nb;
+        const bool coll = (collapse & 1) != 0;
+        int mylen = 0;
+        if (lane < count) {
+            int32_t* o = out_tokens + ((size_t)lane * B + b) * S;
+            int kept = 0;
+            for (int pass = 0; pass < 2; ++pass) {
+                unsigned cur = id;
+                int pos = kept, pending = -1;          // pending: the token behind the one about to be read, not yet decided
+                for (int n = 0; cur != ROOT && cur < (unsigned)H && n < Tb; ++n) {
+                    const unsigned v = (table[cur] & KEYMASK) - 1u;
+                    const int tok = (int)(v & 255u);
+                    if (pending >= 0 && !(coll && pending == tok)) {
+                        if (pass == 0) ++kept; else o[--pos] = pending;
+                    }
+                    pending = tok;
+                    cur = v >> 8;
+                }
+                if (pending >= 0) {                    // the first token is always kept
+                    if (pass == 0) ++kept; else o[--pos] = pending;
+                }
+            }
+            mylen = kept;
+        }
+        if (lane < N) {                                // N <= K <= 16: row 0
+            out_len[(size_t)lane * B + b] = mylen;
+            out_score.out_score[(size_t)lane * B + b] = lane < count ? ((Tb > 0) ? -tot : -0.0) : (double)INFINITY;
+        }
+        if (lane == 0) out_score.out_count[b] = count;
+        for (int r = 0; r < N; ++r) {                  // zero tails (and whole rows beyond count), coalesced; disjoint from the tokens written above
+            int32_t* o = out_tokens + ((size_t)r * B + b) * S;
+            const int lr = __builtin_amdgcn_readlane(mylen, r);
+            for (int i = lr + lane; i < S; i += 64) o[i] = 0;
+        }
+        return;
+    } else {
     // ---- result: ancestors of the best entry, in order, optionally through collapse_fn ----
     __syncthreads();
     unsigned short* tmp = reinterpret_cast<unsigned short*>(frames);      // 8 KB = 4096 tokens: the dispatch admits T <= MAX_TOKENS only
@@ -847,6 +898,7 @@ __global__ __launch_bounds__(64) void beam_small_kernel(
 #ifdef PGASR_BEAM_DIAG
         if (getenv_cycles_) out_score[b] = (double)(clock64() - dg_c0_) / (double)(Tb > 0 ? Tb : 1);      // cycles per frame of this utterance
 #endif
+    }
     }
 }
 #undef SB_CE
@@ -957,7 +1009,8 @@ extern "C" int pgasr_ctc_beam_search_lm(const void* log_probs, int is_f64, long 
                             workspace, workspace_bytes, stream, lm_table, lm_order, lm_alpha, lm_beta);
 }
 
-// The N-best list of the final beam (include/pgasr_hip.h, A7-NBEST): always the workgroup-per-utterance kernel, NBEST = true.
+// The N-best list of the final beam (include/pgasr_hip.h, A7-NBEST): the workgroup-per-utterance kernel, NBEST = true; with flags bit 3
+// ("fast") the single-wave kernel's NBEST instantiation wherever the 1-best dispatch of beam_search_impl takes that kernel.
 extern "C" int pgasr_ctc_beam_search_nbest(const void* log_probs, int is_f64, long long stride_t, long long stride_b,
                                            const int32_t* lengths, int T, int B, int V, int beam, int blank, int flags,
                                            int nbest, int32_t* out_tokens, int tok_stride, int32_t* out_len, double* out_score,
@@ -979,8 +1032,18 @@ extern "C" int pgasr_ctc_beam_search_nbest(const void* log_probs, int is_f64, lo
     const size_t lds = beam_lds_bytes(beam, V, with_lm);
     if (lds > 160 * 1024) return PGASR_ERR_UNSUPPORTED;
     hipStream_t st = (hipStream_t)stream;
-    if (hipMemsetAsync(ws.table, 0, (size_t)B * ws.H * sizeof(unsigned long long), st) != hipSuccess) return PGASR_ERR_LAUNCH;
     const int collapse = flags & 1;
+    if ((flags & 8) && !with_lm && !is_f64 && beam <= sb::K_MAX && V <= sb::V_MAX && (long long)T * beam <= sb::MAX_NODES && T <= sb::MAX_TOKENS) {
+        auto kern = V <= 32 ? &sb::beam_small_kernel<8, true> : &sb::beam_small_kernel<16, true>;
+        const size_t lds_small = sb::lds_bytes(V <= 32 ? 8 : 16);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_small);
+        const sb::SmallNbest sn{out_score, out_count, nbest, tok_stride};
+        PGASR_LAUNCH_KERNEL(kern, dim3(B), dim3(64), lds_small, st, (const float*)log_probs, stride_t, stride_b,
+                           lengths, T, V, beam, blank, collapse, out_tokens, out_len, sn);
+        PGASR_CHECK_LAUNCH();
+        return PGASR_OK;
+    }
+    if (hipMemsetAsync(ws.table, 0, (size_t)B * ws.H * sizeof(unsigned long long), st) != hipSuccess) return PGASR_ERR_LAUNCH;
     BeamNbest<true> nl{};
     static_cast<BeamLm<true>&>(nl) = lmb;
     nl.nbest = nbest; nl.tok_stride = tok_stride; nl.out_count = out_count;

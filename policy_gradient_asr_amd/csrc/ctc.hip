@@ -536,7 +536,9 @@ __global__ __launch_bounds__(CTC_THREADS + 64) void ctc_hyp_lattice_kernel(
 
 // One wave per (t,b), one pass, one write: the target part, then sample k = 0..K-1 in k order -- the sequence term from lattice
 // (k,b) where hyp_len[k,b] <= Lh (ctc_grad_row over the hypothesis workspace, scale pg_coef[k,b]), else ctc_grad_multi_kernel's path term.
-template <bool ENT, class... Ent>
+// PATHS = false (pgasr_ctc_grad_from_lattices_nbest, MWER over N-best lists): there are no sampled paths -- the path branch is compiled
+// out, pg_paths is not read, and a pair with hyp_len > Lh adds nothing.  The PATHS = true instantiations are the code they were.
+template <bool ENT, bool PATHS, class... Ent>
 __global__ __launch_bounds__(256) void ctc_grad_seq_kernel(
     const float* __restrict__ lp, const int32_t* __restrict__ in_len, const int32_t* __restrict__ tg_len,
     int T, int B, int V, int Lmax, int Smax, int blank, CtcWs ws,
@@ -563,7 +565,7 @@ __global__ __launch_bounds__(256) void ctc_grad_seq_kernel(
         if (len <= Lh) {
             // pair p's lattice; the per-pair scale is pg_coef[p]
             g += ctc_grad_row(lpv, sm, lane, t, p, T, V, len < 0 ? 0 : len, Smax_h, blank, hws, pg_coef);
-        } else {
+        } else if constexpr (PATHS) {
             const int pk = pg_paths[k * TB + (size_t)t * B + b];
             g += pg_coef[p] * (sm - (lane == pk ? 1.f : 0.f));
         }
@@ -791,10 +793,31 @@ extern "C" int pgasr_ctc_grad_from_lattices_seq_ent(const float* log_probs, cons
     if (!ctc_ws_bind(T, B, V, 2 * Lmax + 1, &ws, workspace, workspace_bytes)) return PGASR_ERR_WORKSPACE;
     if (!ctc_ws_bind(T, K * B, V, Smax_h, &hws, hyp_workspace, hyp_workspace_bytes)) return PGASR_ERR_WORKSPACE;
     if (ent_scale)
-        return ctc_launch_grad(ctc_grad_seq_kernel<true, const float*>, log_probs, input_lengths, target_lengths, T, B, V, Lmax, blank, ws, utt_scale,
+        return ctc_launch_grad(ctc_grad_seq_kernel<true, true, const float*>, log_probs, input_lengths, target_lengths, T, B, V, Lmax, blank, ws, utt_scale,
                                stream, K, pg_coef, pg_paths, hyp_len, Lh, Smax_h, hws, grad_logits, ent_scale);
-    return ctc_launch_grad(ctc_grad_seq_kernel<false>, log_probs, input_lengths, target_lengths, T, B, V, Lmax, blank, ws, utt_scale,
+    return ctc_launch_grad(ctc_grad_seq_kernel<false, true>, log_probs, input_lengths, target_lengths, T, B, V, Lmax, blank, ws, utt_scale,
                            stream, K, pg_coef, pg_paths, hyp_len, Lh, Smax_h, hws, grad_logits);
+}
+
+// MWER over N-best lists: the sequence pass without a path tensor.  Every pair (n,b) adds coef[n,b] (softmax - occ_{y_n}) from its
+// hypothesis lattice, in n order, after the target part; hyp_len is what pgasr_ctc_hyp_lattice was given (0 for a pair that is not
+// in the list or over the cap, whose coefficient is 0 and whose lattice -- the empty hypothesis' -- was really computed).
+extern "C" int pgasr_ctc_grad_from_lattices_nbest(const float* log_probs, const int32_t* input_lengths, const int32_t* target_lengths,
+                                                  int T, int B, int V, int Lmax, int blank, const float* utt_scale,
+                                                  int N, const float* coef, const int32_t* hyp_len, int Lh,
+                                                  float* grad_logits, void* workspace, size_t workspace_bytes,
+                                                  void* hyp_workspace, size_t hyp_workspace_bytes, void* stream) {
+    if (!log_probs || !input_lengths || !target_lengths || !grad_logits || !coef || !hyp_len) return PGASR_ERR_INVALID_ARG;
+    if (Lmax < 0 || blank < 0 || blank >= V) return PGASR_ERR_INVALID_ARG;
+    int ok = ctc_hyp_args_ok(T, B, V, N, Lh);
+    if (ok == PGASR_OK) ok = ctc_args_ok(T, B, V, Lmax, blank);
+    if (ok != PGASR_OK) return ok;
+    const int Smax_h = 2 * Lh + 1;
+    CtcWs ws, hws;
+    if (!ctc_ws_bind(T, B, V, 2 * Lmax + 1, &ws, workspace, workspace_bytes)) return PGASR_ERR_WORKSPACE;
+    if (!ctc_ws_bind(T, N * B, V, Smax_h, &hws, hyp_workspace, hyp_workspace_bytes)) return PGASR_ERR_WORKSPACE;
+    return ctc_launch_grad(ctc_grad_seq_kernel<false, false>, log_probs, input_lengths, target_lengths, T, B, V, Lmax, blank, ws, utt_scale,
+                           stream, N, coef, (const int32_t*)nullptr, hyp_len, Lh, Smax_h, hws, grad_logits);
 }
 
 extern "C" int pgasr_pg_loss_value_seq(const float* log_probs, const int32_t* paths, int K, const int32_t* input_lengths,

@@ -96,7 +96,68 @@ __global__ __launch_bounds__(NR_THREADS) void nbest_rescore_kernel(
     }
 }
 
+// MWER over an N-best list (pgasr_mwer_weights; semantics in include/pgasr_hip.h, section A13-MWER): the posterior over the list's valid
+// entries from their exact CTC nll, the risks, the expected risk and the gradient coefficients.  One thread per utterance, fp64, the
+// sums in n order: two calls give the same bits.  N <= PGASR_MAX_SAMPLES entries, read three times; nothing here is worth a wave.
+__global__ __launch_bounds__(64) void mwer_weights_kernel(
+    const int32_t* __restrict__ dist, const int32_t* __restrict__ risk_len, const int32_t* __restrict__ tg_len,
+    const float* __restrict__ hyp_nll, const int32_t* __restrict__ hyp_len, const int32_t* __restrict__ count,
+    const float* __restrict__ nll, int N, int B, int Lh, double lam, double inv_gb,
+    float* __restrict__ p_out, float* __restrict__ r_out, float* __restrict__ coef, float* __restrict__ utt_scale,
+    float* __restrict__ rbar_out, float* __restrict__ terms) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const int cnt = count[b];
+    const int rl = risk_len[b];
+    const double den = (double)(rl > 1 ? rl : 1);
+    unsigned valid = 0u;
+    double m = INFINITY;
+    for (int n = 0; n < N; ++n) {
+        const size_t i = (size_t)n * B + b;
+        const float h = hyp_nll[i];
+        const bool ok = n < cnt && hyp_len[i] <= Lh && h == h && h != INFINITY && h != -INFINITY;
+        if (ok) { valid |= 1u << n; m = fmin(m, (double)h); }
+    }
+    double z = 0.0;
+    for (int n = 0; n < N; ++n)
+        if (valid >> n & 1u) z += exp(-((double)hyp_nll[(size_t)n * B + b] - m));
+    double rbar = 0.0;
+    for (int n = 0; n < N; ++n) {
+        const size_t i = (size_t)n * B + b;
+        const double p = (valid >> n & 1u) ? exp(-((double)hyp_nll[i] - m)) / z : 0.0;
+        const double r = (double)dist[i] / den;
+        rbar += p * r;
+        p_out[i] = (float)p;
+        r_out[i] = (float)r;
+    }
+    for (int n = 0; n < N; ++n) {
+        const size_t i = (size_t)n * B + b;
+        const double p = (valid >> n & 1u) ? exp(-((double)hyp_nll[i] - m)) / z : 0.0;
+        const double r = (double)dist[i] / den;
+        coef[i] = (valid >> n & 1u) ? (float)(-lam * inv_gb * p * (r - rbar)) : 0.f;
+    }
+    const int L = tg_len[b];
+    const float us = (float)inv_gb / (float)(L > 1 ? L : 1);      // as pgasr_pg_rewards leaves it
+    utt_scale[b] = us;
+    rbar_out[b] = (float)rbar;
+    terms[b] = (float)((double)(nll[b] * us) + lam * inv_gb * rbar);       // the CTC part as pgasr_pg_loss_value forms it: one fp32 product
+}
+
 }  // namespace
+
+extern "C" int pgasr_mwer_weights(const int32_t* dist, const int32_t* risk_len, const int32_t* target_lengths, const float* hyp_nll,
+                                  const int32_t* hyp_len, const int32_t* count, const float* nll, int N, int B, int Lh,
+                                  float lam, float inv_global_batch, float* p, float* r, float* coef, float* utt_scale,
+                                  float* rbar, float* terms, void* stream) {
+    if (!dist || !risk_len || !target_lengths || !hyp_nll || !hyp_len || !count || !nll) return PGASR_ERR_INVALID_ARG;
+    if (!p || !r || !coef || !utt_scale || !rbar || !terms) return PGASR_ERR_INVALID_ARG;
+    if (N < 1 || N > PGASR_MAX_SAMPLES || B <= 0 || Lh < 0) return PGASR_ERR_INVALID_ARG;
+    if (!std::isfinite(lam) || !std::isfinite(inv_global_batch) || !(inv_global_batch > 0.f)) return PGASR_ERR_INVALID_ARG;
+    PGASR_LAUNCH_KERNEL(mwer_weights_kernel, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, dist, risk_len, target_lengths,
+                       hyp_nll, hyp_len, count, nll, N, B, Lh, (double)lam, (double)inv_global_batch, p, r, coef, utt_scale, rbar, terms);
+    PGASR_CHECK_LAUNCH();
+    return PGASR_OK;
+}
 
 extern "C" int pgasr_nbest_rescore(const int32_t* tokens, int tok_stride, const int32_t* len, const int32_t* count, const double* am,
                                    int N, int B, int V, int blank, const float* lm_table, int lm_order,

@@ -1200,7 +1200,8 @@ def _lm_table(lm, V, blank, device):
     return lm.device_table(device), lm.order
 
 
-def ctc_beam_search_nbest(log_probs, lengths=None, beam=5, nbest=1, blank=0, collapse=False, lm=None, lm_alpha=0.0, lm_beta=0.0):
+def ctc_beam_search_nbest(log_probs, lengths=None, beam=5, nbest=1, blank=0, collapse=False, lm=None, lm_alpha=0.0, lm_beta=0.0,
+                          fast=False):
     """The first ``nbest`` entries of the search's final beam (pgasr_ctc_beam_search_nbest): log_probs (T,B,V) fp32 or fp64 as
     ``ctc_beam_search`` takes them, 1 <= nbest <= beam.  Returns ``CTCNBest`` of device tensors, no host synchronisation:
     tokens (N,B,T) int32 (zero behind each hypothesis), lengths (N,B) int32, score (N,B) float64 = -logsumexp(p_blank, p_nonblank)
@@ -1208,9 +1209,12 @@ def ctc_beam_search_nbest(log_probs, lengths=None, beam=5, nbest=1, blank=0, col
     score ascending (probability descending), first touch among equals (with blank != 0 two entries of exactly equal score -- in
     practice of probability zero -- can swap against the reference: include/pgasr_hip.h, A7-NBEST).  Rows beyond count: length 0, score +inf, tokens zero.
     collapse: collapse_fn on each hypothesis separately -- rows that become equal strings are NOT merged.
-    Every call takes the workgroup-per-utterance kernel (fp64 math for fp64 input, the fast path for fp32): row 0 is bit for bit
+    Without ``fast`` every call takes the workgroup-per-utterance kernel (fp64 math for fp64 input, the fast path for fp32): row 0 is bit for bit
     ``ctc_beam_search(generic=True)``, or ``ctc_beam_search(lm=...)`` with a language model.  (N,B,T) is the (K,B,stride) layout
-    ``ctc_hyp_lattice`` takes."""
+    ``ctc_hyp_lattice`` takes.
+    fast: the call may take the single-wave kernel of the train step, exactly where ``ctc_beam_search`` takes it by default (no LM,
+    fp32, beam <= 16, V <= 64, T * beam <= 24576, T <= 4096); row 0 is then bit for bit ``ctc_beam_search(...)``.  Anywhere else
+    the flag changes nothing."""
     lib = _lib.load()
     if not log_probs.is_cuda or log_probs.dtype not in (torch.float32, torch.float64):
         raise _lib.PgasrError("log_probs must be a float32/float64 GPU tensor")
@@ -1227,11 +1231,47 @@ def ctc_beam_search_nbest(log_probs, lengths=None, beam=5, nbest=1, blank=0, col
     count = torch.empty(B, dtype=torch.int32, device=dev)
     with _timed("beam_search_nbest"):
         st = lib.pgasr_ctc_beam_search_nbest(_p(log_probs), int(log_probs.dtype == torch.float64), log_probs.stride(0),
-                                             log_probs.stride(1), _p(lengths), T, B, V, int(beam), int(blank), int(bool(collapse)),
-                                             N, _p(tokens), T, _p(tl), _p(score), _p(count), _p(ws), ws.numel(), _stream(),
+                                             log_probs.stride(1), _p(lengths), T, B, V, int(beam), int(blank),
+                                             int(bool(collapse)) | (8 if fast else 0), N, _p(tokens), T, _p(tl), _p(score), _p(count), _p(ws), ws.numel(), _stream(),
                                              _p(lm_table), lm_order, float(lm_alpha), float(lm_beta))
     _lib.check(st, "pgasr_ctc_beam_search_nbest")
     return CTCNBest(tokens, tl, score, count)
+
+
+def mwer_weights(dist, risk_len, target_lengths, hyp_nll, hyp_len, count, nll, Lh, lam, inv_global_batch):
+    """Posterior, risks and gradient coefficients of MWER over an N-best list (pgasr_mwer_weights; include/pgasr_hip.h, A13-MWER):
+    dist (N,B) int32 (word) edit distances, risk_len (B) int32 what normalises them, target_lengths (B) int32, hyp_nll (N,B) fp32 the
+    exact CTC nll of every hypothesis, hyp_len (N,B) / count (B) int32 the list's, nll (B) fp32 the target's.
+    Returns (p (N,B), r (N,B), coef (N,B), utt_scale (B), rbar (B), terms (B)) fp32; one launch, no host synchronisation."""
+    lib = _lib.load()
+    _req(dist, torch.int32, "dist"); _req(risk_len, torch.int32, "risk_len"); _req(target_lengths, torch.int32, "target_lengths")
+    _req(hyp_nll, torch.float32, "hyp_nll"); _req(hyp_len, torch.int32, "hyp_len"); _req(count, torch.int32, "count")
+    _req(nll, torch.float32, "nll")
+    if hyp_nll.dim() != 2:
+        raise _lib.PgasrError("mwer_weights wants hyp_nll (N,B)")
+    N, B = hyp_nll.shape
+    if dist.numel() != N * B or tuple(hyp_len.shape) != (N, B) or any(t_.numel() != B for t_ in (risk_len, target_lengths, count, nll)):
+        raise _lib.PgasrError(f"mwer_weights wants dist, hyp_nll, hyp_len ({N},{B}) and risk_len, target_lengths, count, nll ({B},)")
+    out = torch.empty(3 * N + 3, B, dtype=torch.float32, device=hyp_nll.device)
+    p, r, coef, rest = out[:N], out[N:2 * N], out[2 * N:3 * N], out[3 * N:]
+    st = lib.pgasr_mwer_weights(_p(dist), _p(risk_len), _p(target_lengths), _p(hyp_nll), _p(hyp_len), _p(count), _p(nll), N, B, int(Lh),
+                                float(lam), float(inv_global_batch), p.data_ptr(), r.data_ptr(), coef.data_ptr(),
+                                rest[0].data_ptr(), rest[1].data_ptr(), rest[2].data_ptr(), _stream())
+    _lib.check(st, "pgasr_mwer_weights")
+    return p, r, coef, rest[0], rest[1], rest[2]
+
+
+def ctc_grad_from_lattices_nbest(log_probs, input_lengths, target_lengths, handle, hyp_handle, utt_scale, coef, hyp_len):
+    """``ctc_grad_from_lattices_seq`` without sampled paths (pgasr_ctc_grad_from_lattices_nbest): utt_scale (softmax - occ_target) +
+    sum_n coef[n,b] (softmax - occ_{y_n}) over the N*B hypothesis lattices of ``ctc_hyp_lattice``, the N terms in n order.  coef (N,B)
+    fp32; hyp_len (N,B) int32 is the tensor ``ctc_hyp_lattice`` was given."""
+    hws, N, Lh = hyp_handle
+    T, B, _ = log_probs.shape
+    _req(hyp_len, torch.int32, "hyp_len")
+    if tuple(coef.shape) != (N, B) or tuple(hyp_len.shape) != (N, B):
+        raise _lib.PgasrError(f"ctc_grad_from_lattices_nbest wants coef and hyp_len ({N},{B})")
+    return _grad_pass("pgasr_ctc_grad_from_lattices_nbest", log_probs, input_lengths, target_lengths, handle, utt_scale, coef,
+                      None, "paths", (N, coef, hyp_len, Lh), ws_tail=(_p(hws), hws.numel()), label="ctc_grad_nbest_kernel")
 
 
 def nbest_rescore(tokens, lengths, count, am, vocab, blank=0, lm=None, am_weight=1.0, lm_alpha=0.0, lm_beta=0.0):

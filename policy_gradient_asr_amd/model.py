@@ -210,7 +210,8 @@ def _check_features(features, n_feats, dataset):
 def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset=None, dev_dataset=None,
           n_feats=120, lam=1.0, lr=5e-4, resume=True, log_every=10, seed=0, bucket_by_length=True, features="mfcc",
           precision="f32", num_samples=1, reward_baseline="hypothesis", reward_unit="char", max_grad_norm=None,
-          accumulate_steps=1, score_function="path", max_hyp_len=None, entropy_weight=0.0):
+          accumulate_steps=1, score_function="path", max_hyp_len=None, entropy_weight=0.0, objective="reinforce", mwer_nbest=4,
+          mwer_beam=16):
     """Epoch loop of model.py:186-274 on the MI355X path: per-epoch train loss -> train_loss.npy,
     validation CTC loss -> val_losses.npy, model_best.pth / model_last.pth (state_dicts, reference
     names), plus checkpoint_last.pth (model + Adam moments + epoch) from which ``resume`` restarts
@@ -237,7 +238,11 @@ def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset
     accumulate_steps: 1 (default: one optimizer step per loader batch, as always) or n > 1 -- n consecutive loader batches are the
     micro-batches of ONE optimizer step (PolicyGradientTrainer.step_accumulated: the batch of an update is n x batch_size; the last
     group of an epoch may be shorter).  The log lines and the epoch mean then count optimizer steps.  Each loader batch keeps its
-    own padded length, so the update is that of the n batches' summed loss, not of one batch padded to a common length."""
+    own padded length, so the update is that of the n batches' summed loss, not of one batch padded to a common length.
+    objective: "reinforce" (default: the sampled objectives above, today's trainer with today's arguments) or "mwer" -- MWER over the
+    ``mwer_nbest`` best hypotheses of the width-``mwer_beam`` beam search (mwer.MWERTrainer: nothing is sampled, so num_samples,
+    reward_baseline, score_function and entropy_weight must keep their defaults; reward_unit chooses the char or word risk and
+    max_hyp_len caps the hypotheses in the list's posterior)."""
     import os
     import numpy as np
     import torch.utils.data as tud
@@ -250,6 +255,8 @@ def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset
     if isinstance(accumulate_steps, bool) or int(accumulate_steps) != accumulate_steps or accumulate_steps < 1:
         raise ValueError(f"accumulate_steps must be an integer >= 1 (got {accumulate_steps!r})")
     accumulate_steps = int(accumulate_steps)
+    if objective not in ("reinforce", "mwer"):
+        raise ValueError(f"objective must be 'reinforce' or 'mwer' (got {objective!r})")
     print("Num epochs:", num_epochs, "Batch size:", batch_size)
     alphabet_path = os.path.join(corpus_path, "alphabet.txt")
     alphabet, char2ind = _read_alphabet(alphabet_path)
@@ -271,10 +278,17 @@ def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset
     model.apply(weights)                                            # model.py:202
     model = model.to(dev)
     _check_features(features, n_feats, train_dataset)
-    trainer = PolicyGradientTrainer(model, lr=lr, lam=lam, seed=seed, precision=precision, num_samples=num_samples,
-                                    reward_baseline=reward_baseline, reward_unit=reward_unit, word_delimiter=word_delimiter,
-                                    max_grad_norm=max_grad_norm, score_function=score_function, max_hyp_len=max_hyp_len,
-                                    entropy_weight=entropy_weight)
+    if objective == "mwer":
+        from .mwer import MWERTrainer
+        trainer = MWERTrainer(model, lr=lr, lam=lam, seed=seed, precision=precision, max_grad_norm=max_grad_norm,
+                              beam_size=mwer_beam, nbest=mwer_nbest, risk_unit=reward_unit, word_delimiter=word_delimiter,
+                              max_hyp_len=max_hyp_len, num_samples=num_samples, reward_baseline=reward_baseline,
+                              score_function=score_function, entropy_weight=entropy_weight)
+    else:
+        trainer = PolicyGradientTrainer(model, lr=lr, lam=lam, seed=seed, precision=precision, num_samples=num_samples,
+                                        reward_baseline=reward_baseline, reward_unit=reward_unit, word_delimiter=word_delimiter,
+                                        max_grad_norm=max_grad_norm, score_function=score_function, max_hyp_len=max_hyp_len,
+                                        entropy_weight=entropy_weight)
     losses, val_losses, best, start_epoch = [], [], 9999999.0, 1
     ckpt = os.path.join(model_path, "checkpoint_last.pth")
     if resume and os.path.exists(ckpt):

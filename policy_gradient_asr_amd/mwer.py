@@ -1,0 +1,203 @@
+"""MWER training over the N-best list of the in-step beam search (Prabhavalkar et al., arXiv:1712.01818).
+
+The other standard form of expected-risk training beside the sampled objectives of ``loss.PGCTCLossFn``: the model's probability is
+renormalised over the N hypotheses the decoder actually returns, and the expected (word) edit distance under that distribution is
+minimised.  Nothing is sampled: no sampling variance, no sampler addressing.  The lists are the ones ``CTCDecoder.decode_batch(nbest=)``
+and ``rescore`` consume.  Semantics of the kernels: include/pgasr_hip.h, section A13-MWER.
+
+This module adds nothing to the code the default train step runs: ``train_step.py`` and ``loss.py`` do not know it.
+"""
+import dataclasses
+
+import torch
+
+from . import hipops
+from . import streams
+from .loss import PGCTCLossFn, _check_score, _check_unit, _word_distances
+from .train_step import PolicyGradientTrainer
+
+MAX_NBEST = hipops.MAX_SAMPLES       # PGASR_MAX_SAMPLES: entries per utterance the weights and gradient kernels take
+
+
+@dataclasses.dataclass(frozen=True)
+class MWEROptions:
+    """Everything of a ``mwer_ctc_loss`` call that is not a tensor."""
+    lam: float = 1.0
+    beam: int = 16
+    nbest: int = 4
+    global_batch: int = 1
+    blank: int = 0
+    risk_unit: str = "char"
+    word_delimiter: object = None
+    max_hyp_len: object = None
+
+
+def check_mwer_options(opt, vocab=None, frames=None, symbols=None):
+    """Made before any kernel runs.  Returns the options with their integers as ints."""
+    for name in ("beam", "nbest"):
+        v = getattr(opt, name)
+        if isinstance(v, bool) or int(v) != v:
+            raise ValueError(f"{name} must be an integer (got {v!r})")
+    if not 1 <= opt.nbest <= opt.beam:
+        raise ValueError(f"nbest {opt.nbest} outside 1 .. beam = {opt.beam}: the list is the head of the search's final beam")
+    if opt.nbest > MAX_NBEST:
+        raise ValueError(f"nbest {opt.nbest} > {MAX_NBEST}: the MWER kernels take at most {MAX_NBEST} hypotheses per utterance")
+    _check_unit(opt.risk_unit, opt.word_delimiter, blank=opt.blank, vocab=vocab)
+    _check_score("sequence", opt.max_hyp_len)
+    if opt.risk_unit == "word" and frames is not None and max(frames, symbols or 0) > hipops.WORD_MAX_STRIDE:
+        raise ValueError(f"the word-level risk takes at most {hipops.WORD_MAX_STRIDE} frames and target symbols per utterance "
+                         f"(pgasr_word_ids); got T = {frames}")
+    return dataclasses.replace(opt, beam=int(opt.beam), nbest=int(opt.nbest),
+                               max_hyp_len=None if opt.max_hyp_len is None else int(opt.max_hyp_len))
+
+
+class MWERLossFn(torch.autograd.Function):
+    """loss = sum_b [ nll_b / (Bg max(L_b,1))  +  lam / Bg * sum_n p[n,b] r[n,b] ]
+
+    over the first ``nbest`` entries y_n of the width-``beam`` prefix beam search's final beam (raw prefixes, no collapse_fn: distinct
+    label sequences, each with a well-defined CTC likelihood), with
+        valid(n,b) := n < count_b  and  |y_n| <= Lh  and  nll(y_n | x_b) finite           Lh = min(T, 1023, max_hyp_len if given)
+        p[n,b]     =  softmax over the valid n of -nll(y_n | x_b), the EXACT CTC likelihood (not the first-pass beam score)
+        r[n,b]     =  ED(y_b, y_n) / max(L_b,1), or WED / W(y_b) with risk_unit = "word"
+        d(logits)  =  utt_scale_b (softmax - occ_target) + sum_n coef[n,b] (softmax - occ_{y_n}),
+        coef[n,b]  =  -lam / Bg * p[n,b] (r[n,b] - rbar_b)
+    Stream layout of ``PGCTCLossFn``: the target lattice stays on the calling stream; N-best search, hypothesis lattices, (word) edit
+    distance and the weights run on its side stream and are joined before the one gradient pass.
+    ``MWERLossFn.last_nbest``: the ``CTCNBest`` of the last call; ``MWERLossFn.last_posterior``: p (N,B) fp32, 0 where not valid;
+    ``MWERLossFn.last_risk``: r (N,B) fp32.
+    Returns (loss, nll (B), expected_reward (B) = -rbar, top_reward (B) = -r[0]), the last three detached."""
+
+    last_nbest = None
+    last_posterior = None
+    last_risk = None           # r (N,B) fp32 of the last call
+
+    @staticmethod
+    def forward(ctx, logits, in_len, targets, tg_len, log_probs, opt):
+        T, B, V = logits.shape
+        N, blank = opt.nbest, opt.blank
+        wd = opt.word_delimiter if opt.risk_unit == "word" else None
+        Lh = hipops.hyp_len_cap(T, opt.max_hyp_len)
+        inv_gb = 1.0 / float(opt.global_batch)
+        lp = log_probs
+        if lp is None or lp.shape != logits.shape or not lp.is_contiguous():
+            lp = hipops.log_softmax_rows(logits.contiguous())
+        main = torch.cuda.current_stream()
+        side = PGCTCLossFn._lattice_streams.setdefault(main.cuda_stream, None) or streams.side_stream("loss_section")
+        PGCTCLossFn._lattice_streams[main.cuda_stream] = side
+        side.wait_stream(main)
+        with torch.cuda.stream(side):
+            nb = hipops.ctc_beam_search_nbest(lp, in_len, beam=opt.beam, nbest=N, blank=blank, collapse=False, fast=True)
+            # a hypothesis over the cap gets the EMPTY hypothesis' lattice (rows beyond count have length 0 already): every lattice
+            # the gradient pass reads was really computed, and meets a coefficient of 0
+            lat_len = torch.where(nb.lengths > Lh, torch.zeros_like(nb.lengths), nb.lengths)
+            hyp_nll, hyp_lattice = hipops.ctc_hyp_lattice(lp, nb.tokens, lat_len, in_len, Lh, blank=blank)
+            if wd is not None:
+                dist, risk_len = _word_distances(targets, tg_len, nb.tokens, nb.lengths, N, wd)
+            else:
+                dist = hipops.edit_distance(targets.repeat(N, 1), tg_len.repeat(N), nb.tokens.view(N * B, T), nb.lengths.view(N * B))
+                risk_len = tg_len
+        nll, lattice = hipops.ctc_lattice(lp, targets, in_len, tg_len, blank=blank)
+        with torch.cuda.stream(side):
+            side.wait_stream(main)                   # the weights form the loss terms from the target's nll
+            p, r, coef, utt_scale, rbar, terms = hipops.mwer_weights(dist, risk_len, tg_len, hyp_nll, nb.lengths, nb.count, nll, Lh,
+                                                                     opt.lam, inv_gb)
+        main.wait_stream(side)
+        for t_ in (nb.tokens, nb.lengths, nb.score, nb.count, lat_len, hyp_nll, dist, p, r, coef, utt_scale, rbar, terms):
+            streams.hold(t_, main)
+        MWERLossFn.last_nbest, MWERLossFn.last_posterior, MWERLossFn.last_risk = nb, p, r
+        grad = hipops.ctc_grad_from_lattices_nbest(lp, in_len, tg_len, lattice, hyp_lattice, utt_scale, coef, lat_len)
+        loss = terms.sum()
+        expected, top = -rbar, -r[0]
+        ctx.save_for_backward(grad)
+        ctx.mark_non_differentiable(nll, expected, top)
+        ctx.set_materialize_grads(False)
+        return loss, nll, expected, top
+
+    @staticmethod
+    def backward(ctx, g, *unused):
+        (grad,) = ctx.saved_tensors
+        # the trainer's backward registers its unit seed with PGCTCLossFn: the same shortcut, the same counter
+        if PGCTCLossFn.unit_seed_ptr is not None and g.data_ptr() == PGCTCLossFn.unit_seed_ptr and g.numel() == 1:
+            PGCTCLossFn.unit_hits += 1
+        else:
+            grad = grad * g
+        return (grad,) + (None,) * (len(ctx.needs_input_grad) - 1)
+
+
+def mwer_ctc_loss(logits, in_len, targets, tg_len, lam=1.0, beam=16, nbest=4, global_batch=None, blank=0, risk_unit="char",
+                  word_delimiter=None, max_hyp_len=None, log_probs=None):
+    """CTC + lam * MWER over the ``nbest`` best hypotheses of the width-``beam`` prefix beam search (see ``MWERLossFn``).
+    logits (T,B,V) fp32 on the GPU, in_len / tg_len (B) int32, targets (B,L) int32.  1 <= nbest <= beam, nbest <= 16.
+    risk_unit: "char" (default) -- r = ED / |y|; "word" -- r = WED / W(y), words split at the token ``word_delimiter``.
+    max_hyp_len: hypotheses of more tokens are left out of the list's posterior (None: min(T, 1023)); it bounds the hypothesis-lattice
+    workspace, 2 * nbest*B*T * roundup64(2*Lh+1) * 4 bytes.
+    log_probs: log_softmax(logits) if the caller already has it (picked up from ``logits.log_probs`` when not given).
+    Returns (loss, nll (B), expected_reward (B) = -rbar, top_reward (B) = -r[0])."""
+    if logits.dim() != 3:
+        raise ValueError("mwer_ctc_loss: logits (T,B,V)")
+    T, B, V = logits.shape
+    opt = check_mwer_options(MWEROptions(lam=float(lam), beam=beam, nbest=nbest, global_batch=int(global_batch or B), blank=int(blank),
+                                         risk_unit=risk_unit, word_delimiter=word_delimiter, max_hyp_len=max_hyp_len),
+                             vocab=V, frames=T, symbols=targets.shape[1] if targets.dim() == 2 else 0)
+    for name, t_ in (("logits", logits), ("in_len", in_len), ("targets", targets), ("tg_len", tg_len)):
+        if not t_.is_cuda:
+            raise hipops._lib.PgasrError(f"{name} must live on the GPU (got {t_.device}); there is no CPU path")
+    if log_probs is None:
+        log_probs = getattr(logits, "log_probs", None)
+        if log_probs is not None and getattr(logits, "log_probs_version", None) != logits._version:
+            log_probs = None
+    return MWERLossFn.apply(logits, in_len, targets, tg_len, log_probs, opt)
+
+
+class MWERTrainer(PolicyGradientTrainer):
+    """``PolicyGradientTrainer`` with the MWER objective: only ``forward_loss`` differs, so ``step``, ``compute_gradients``,
+    ``step_accumulated``, clipping, shards and RCCL work as in the parent.  Nothing is sampled, so ``utt_ids`` and the sampler's
+    addressing play no part: a shard or micro-batch contributes its own utterances' terms, normalised by the global batch.
+    ``last_stats`` = (nll, expected reward -rbar, top-hypothesis reward -r[0]), each (B,); ``last_sample_rewards`` = -r, (nbest, B);
+    ``last_posterior`` (nbest, B), 0 where an entry is not in the list's posterior."""
+
+    _FIXED = {"num_samples": 1, "reward_baseline": "hypothesis", "score_function": "path", "reward_mode": "utterance",
+              "reward_decoder": "greedy", "entropy_weight": 0.0}
+
+    def __init__(self, model, lr=5e-4, lam=1.0, seed=0, blank=0, world_size=1, process_group=None, rank=0, precision=None,
+                 max_grad_norm=None, beam_size=16, nbest=4, risk_unit="char", word_delimiter=None, max_hyp_len=None, **sampled):
+        for k, v in sampled.items():
+            if k not in self._FIXED:
+                raise TypeError(f"MWERTrainer got an unexpected keyword argument {k!r}")
+            if isinstance(v, bool) or v != self._FIXED[k]:
+                raise ValueError(f"MWERTrainer samples nothing: {k}={v!r} has no meaning here (an entropy bonus for MWER is not built)")
+        vocab = getattr(getattr(model, "head", None), "out_features", None)
+        opt = check_mwer_options(MWEROptions(blank=int(blank), beam=beam_size, nbest=nbest, risk_unit=risk_unit,
+                                             word_delimiter=word_delimiter, max_hyp_len=max_hyp_len), vocab=vocab)
+        super().__init__(model, lr=lr, lam=lam, seed=seed, blank=blank, world_size=world_size, process_group=process_group, rank=rank,
+                         precision=precision, max_grad_norm=max_grad_norm)
+        self.beam_size, self.nbest = opt.beam, opt.nbest
+        self.risk_unit, self.mwer_max_hyp_len = risk_unit, opt.max_hyp_len
+        self.risk_delimiter = None if word_delimiter is None else int(word_delimiter)
+        self.last_posterior = None
+
+    def forward_loss(self, batch, global_batch):
+        x, targets, fmask, tmask = batch
+        self._check_limits(x, targets)
+        real_b = x.shape[0]
+        x, targets, fmask, tmask = self._padded(x, targets, fmask, tmask)
+        padded = x.shape[0] != real_b
+        if (fmask.dtype == torch.float32 and tmask.dtype == torch.int64 and targets.dtype == torch.int64 and targets.dim() == 2
+                and targets.shape[1] > 0 and fmask.is_contiguous() and tmask.is_contiguous() and targets.is_contiguous()):
+            in_len, tg_len, tg = hipops.batch_prep(fmask, tmask, targets)
+        else:
+            in_len = None
+            tg_len = tmask.sum(dim=1).to(torch.int32).contiguous()
+            tg = targets.to(torch.int32).contiguous()
+        logits, in_len = self.model.logits(x, fmask, in_len)
+        loss, nll, expected, top = mwer_ctc_loss(logits, in_len, tg, tg_len, lam=self.lam, beam=self.beam_size, nbest=self.nbest,
+                                                 global_batch=global_batch, blank=self.blank, risk_unit=self.risk_unit,
+                                                 word_delimiter=self.risk_delimiter, max_hyp_len=self.mwer_max_hyp_len)
+        post = MWERLossFn.last_posterior
+        R_all = -MWERLossFn.last_risk                            # (N,B): every entry's reward
+        self.last_posterior = post[:, :real_b] if padded else post
+        self.last_sample_rewards = R_all[:, :real_b] if padded else R_all
+        self.last_stats = (nll[:real_b], expected[:real_b], top[:real_b]) if padded else (nll, expected, top)
+        if self._micro is not None and self._micro.count > 1:
+            self._micro_stats.append((self.last_stats, self.last_sample_rewards, None, None))
+        return loss
