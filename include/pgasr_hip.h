@@ -48,7 +48,8 @@ typedef enum pgasr_status {
  * pgasr_pg_loss_value_seq) and the entropy regularisation (pgasr_frame_entropy, pgasr_ctc_grad_from_lattice_ent,
  * pgasr_ctc_grad_from_lattice_multi_ent, pgasr_ctc_grad_from_lattices_seq_ent), forced alignment (pgasr_ctc_forced_align),
  * SpecAugment masking (pgasr_spec_augment), the N-best entries (pgasr_ctc_beam_search_nbest, pgasr_nbest_rescore) and MWER training
- * over them (pgasr_mwer_weights, pgasr_ctc_grad_from_lattices_nbest). */
+ * over them (pgasr_mwer_weights, pgasr_ctc_grad_from_lattices_nbest), and the KL penalty towards a frozen reference policy
+ * (pgasr_frame_kl, pgasr_ctc_grad_from_lattice_kl, pgasr_ctc_grad_from_lattice_multi_kl, pgasr_ctc_grad_from_lattices_seq_kl). */
 #define PGASR_ABI_VERSION 7
 
 int pgasr_abi_version(void);
@@ -229,6 +230,50 @@ int pgasr_ctc_grad_from_lattices_seq_ent(const float* log_probs, const int32_t* 
                                          int K, const float* pg_coef, const int32_t* pg_paths, const int32_t* hyp_len, int Lh,
                                          const float* ent_scale, float* grad_logits, void* workspace, size_t workspace_bytes,
                                          void* hyp_workspace, size_t hyp_workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * A12  KL penalty towards a frozen reference policy (opt-in; the anchor of an RL fine-tune of a pretrained model).  With gamma >= 0,
+ * p = exp(log_probs[t,b,:]) the trained policy, T_b = input_lengths[b] clamped to [0, T] and the reference's log-probs floored,
+ * lnq_v = max(ref_log_probs[t,b,v], PGASR_KL_LOG_FLOOR) -- just under ln 2^-149, so a zero reference probability costs a large finite
+ * penalty, never inf or NaN:
+ *     KL[t,b]     = sum_v p_v (ln p_v - lnq_v)                      nats; a symbol with p_v = 0 adds exactly 0 (no 0 * inf)
+ *     kl_mean[b]  = (1 / max(T_b,1)) sum_{t<T_b} KL[t,b]            0 for an empty utterance; NOT clamped at 0
+ *     kl_scale[b] = gamma * inv_global_batch / max(T_b,1)
+ *     objective  += sum_b gamma * inv_global_batch * kl_mean[b]
+ *     d(logits)[t,b,v] += kl_scale[b] * p_v * (ln p_v - lnq_v - KL[t,b])     for t < T_b, 0 beyond
+ * The reverse KL(p || q) of KL-regularised policy optimisation, as a mean over the utterance's own frames: gamma is in loss units per
+ * nat per frame, like beta above.  It depends on the two log-prob tensors and the lengths alone; nothing is sampled.
+ *
+ * pgasr_frame_kl: pgasr_frame_entropy's launch with a second row load -- one workgroup per utterance, fixed summation order over v
+ *   and t (fp64 carries), so two calls give equal bits; both vectors in one launch.  ref_log_probs == log_probs gives exactly 0.
+ *   gamma = 0 is the monitoring call (kl_scale = 0).  gamma < 0 or NaN, inv_global_batch <= 0, T, B or V <= 0, null pointers:
+ *   PGASR_ERR_INVALID_ARG; V > 64: PGASR_ERR_UNSUPPORTED; all checked before any pointer is touched.
+ * pgasr_ctc_grad_from_lattice_kl / _multi_kl / pgasr_ctc_grad_from_lattices_seq_kl: the _ent entries above with ref_log_probs
+ *   (T,B,V) and kl_scale (B) between ent_scale and grad_logits.  The KL term is added in the pass that writes the row, after the
+ *   REINFORCE terms and after the entropy term (ent_scale may be NULL: KL alone): a second row read, a second wave sum, one fma per
+ *   lane.  Both NULL runs exactly what the _ent entry runs for that ent_scale (the same bits); exactly one NULL is
+ *   PGASR_ERR_INVALID_ARG; every other check is the _ent entry's.
+ * ---------------------------------------------------------------------------------------- */
+#define PGASR_KL_LOG_FLOOR (-104.0f)
+int pgasr_frame_kl(const float* log_probs, const float* ref_log_probs, const int32_t* input_lengths, int T, int B, int V,
+                   float gamma, float inv_global_batch, float* kl_mean, float* kl_scale, void* stream);
+int pgasr_ctc_grad_from_lattice_kl(const float* log_probs, const int32_t* input_lengths,
+                                   const int32_t* target_lengths, int T, int B, int V, int Lmax, int blank,
+                                   const float* utt_scale, const float* pg_coef, const int32_t* pg_path,
+                                   int pg_coef_per_frame, const float* ent_scale, const float* ref_log_probs,
+                                   const float* kl_scale, float* grad_logits,
+                                   void* workspace, size_t workspace_bytes, void* stream);
+int pgasr_ctc_grad_from_lattice_multi_kl(const float* log_probs, const int32_t* input_lengths,
+                                         const int32_t* target_lengths, int T, int B, int V, int Lmax, int blank,
+                                         const float* utt_scale, int K, const float* pg_coef, const int32_t* pg_paths,
+                                         const float* ent_scale, const float* ref_log_probs, const float* kl_scale,
+                                         float* grad_logits, void* workspace, size_t workspace_bytes, void* stream);
+int pgasr_ctc_grad_from_lattices_seq_kl(const float* log_probs, const int32_t* input_lengths, const int32_t* target_lengths,
+                                        int T, int B, int V, int Lmax, int blank, const float* utt_scale,
+                                        int K, const float* pg_coef, const int32_t* pg_paths, const int32_t* hyp_len, int Lh,
+                                        const float* ent_scale, const float* ref_log_probs, const float* kl_scale,
+                                        float* grad_logits, void* workspace, size_t workspace_bytes,
+                                        void* hyp_workspace, size_t hyp_workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * A5-VIT  CTC forced alignment (Viterbi): the best single alignment of a KNOWN label sequence, its score, and the frames each token

@@ -67,6 +67,16 @@ SIGNATURES = {
     "pgasr_ctc_align_workspace_bytes": (C.c_size_t, [C.c_int] * 3),
     "pgasr_ctc_forced_align": (C.c_int, [c_f32p, c_i32p, c_i32p, c_i32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                          c_ptr, c_i32p, c_i32p, c_i32p, c_i32p, c_ptr, c_ptr, C.c_size_t, c_ptr]),
+    "pgasr_frame_kl": (C.c_int, [c_f32p, c_f32p, c_i32p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, c_f32p, c_f32p, c_ptr]),
+    "pgasr_ctc_grad_from_lattice_kl": (C.c_int, [c_f32p, c_i32p, c_i32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                 c_f32p, c_f32p, c_i32p, C.c_int, c_f32p, c_f32p, c_f32p, c_f32p, c_ptr, C.c_size_t,
+                                                 c_ptr]),
+    "pgasr_ctc_grad_from_lattice_multi_kl": (C.c_int, [c_f32p, c_i32p, c_i32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                       c_f32p, C.c_int, c_f32p, c_i32p, c_f32p, c_f32p, c_f32p, c_f32p, c_ptr,
+                                                       C.c_size_t, c_ptr]),
+    "pgasr_ctc_grad_from_lattices_seq_kl": (C.c_int, [c_f32p, c_i32p, c_i32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_f32p,
+                                                      C.c_int, c_f32p, c_i32p, c_i32p, C.c_int, c_f32p, c_f32p, c_f32p, c_f32p, c_ptr,
+                                                      C.c_size_t, c_ptr, C.c_size_t, c_ptr]),
     "pgasr_word_ids": (C.c_int, [c_i32p, c_i32p, C.c_int, c_i32p, c_i32p, C.c_int, C.c_int, C.c_int, c_i32p, c_i32p, c_i32p, c_i32p,
                                  c_ptr]),
     "pgasr_pg_rewards_multi_ex": (C.c_int, [c_i32p, c_i32p, c_i32p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, c_f32p, c_f32p,

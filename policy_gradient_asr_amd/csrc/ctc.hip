@@ -421,6 +421,80 @@ __global__ __launch_bounds__(64 * ENT_WAVES) void frame_entropy_kernel(
     }
 }
 
+// ---- KL penalty towards a frozen reference policy (pgasr_frame_kl and the *_kl gradient entries) ----
+// KL_{t,b} = sum_v p_v (ln p_v - lnq_v) (nats) of row (t,b): the reverse KL(p || q) of the trained policy p against the reference's
+// log-probs, lnq_v = max(ref_log_probs, PGASR_KL_LOG_FLOOR) -- a zero reference probability under a live policy symbol costs a large
+// finite penalty, never inf or NaN.  A symbol with p = 0 adds exactly 0 (no 0 * inf), and q = p gives exactly 0 in every lane.  One
+// wave_sum in its fixed butterfly order; every lane returns p (ln p - lnq) of its own symbol and the row's KL.
+constexpr float KL_LOG_FLOOR = PGASR_KL_LOG_FLOOR;
+__device__ __forceinline__ float row_kl(float lpv, float sm, float lqv, float* d) {
+    *d = sm > 0.f ? sm * (lpv - fmaxf(lqv, KL_LOG_FLOOR)) : 0.f;
+    return wave_sum(*d);
+}
+
+// The KL form of the three gradient kernels: their Ent pack holds three pointers, (ent_scale, ref_log_probs, kl_scale), with
+// ent_scale nullable (one uniform branch per row).  After the entropy term it adds
+// d(kl_scale_b KL_{t,b}) / d(logits) = kl_scale_b p (ln p - lnq - KL): a second row read, a second wave_sum, one fma per lane.  A lane
+// whose term is 0 leaves g as it is, sign of zero included, so a reference equal to the policy gives the bits of the pass without it.
+__device__ __forceinline__ float ctc_entropy_kl_grad(float g, float lpv, float sm, int lane, int V, int b, size_t o,
+                                                     const float* __restrict__ ent_scale, const float* __restrict__ ref_lp,
+                                                     const float* __restrict__ kl_scale) {
+    if (ent_scale != nullptr) g += ctc_entropy_grad(lpv, sm, b, ent_scale);
+    const float lqv = (lane < V) ? ref_lp[o + lane] : 0.f;
+    float d;
+    const float kl = row_kl(lpv, sm, lqv, &d);
+    const float term = kl_scale[b] * fmaf(-sm, kl, d);
+    return term != 0.f ? g + term : g;
+}
+
+// kl_mean[b] = (1 / max(T_b,1)) sum_{t<T_b} KL_{t,b} and kl_scale[b] = gamma * inv_global_batch / max(T_b,1): frame_entropy_kernel's
+// structure with a second row load -- one workgroup of ENT_WAVES waves per utterance, wave w adds the KLs of frames w, w + ENT_WAVES, ..
+// in t order (fp64 carries), wave 0 lane 0 adds the partial sums in w order, so two calls give the same bits.  Not clamped at 0.
+__global__ __launch_bounds__(64 * ENT_WAVES) void frame_kl_kernel(
+    const float* __restrict__ lp, const float* __restrict__ ref_lp, const int32_t* __restrict__ in_len, int T, int B, int V,
+    float gamma, float inv_gb, float* __restrict__ kl_mean, float* __restrict__ kl_scale) {
+    __shared__ double part[ENT_WAVES];
+    const int b = blockIdx.x, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    int Tb = in_len[b]; Tb = Tb < 0 ? 0 : (Tb > T ? T : Tb);
+    double acc = 0.0;
+    // four of the wave's frames per trip: their eight loads are in flight together, their KLs added in t order
+    for (int t0 = w; t0 < Tb; t0 += 4 * ENT_WAVES) {
+        float lpv[4], lqv[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int t = t0 + i * ENT_WAVES;
+            const bool live = lane < V && t < Tb;
+            const size_t o = ((size_t)t * B + b) * V + lane;
+            lpv[i] = live ? lp[o] : -INFINITY;
+            lqv[i] = live ? ref_lp[o] : 0.f;
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            float d;
+            acc += (double)row_kl(lpv[i], __expf(lpv[i]), lqv[i], &d);      // a frame >= T_b reads as p = 0 everywhere: KL = 0
+        }
+    }
+    if (lane == 0) part[w] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double s = 0.0;
+        for (int i = 0; i < ENT_WAVES; ++i) s += part[i];
+        const float n = (float)(Tb > 0 ? Tb : 1);
+        kl_mean[b] = (float)(s / (double)n);
+        kl_scale[b] = gamma * inv_gb / n;
+    }
+}
+
+// The tail of a gradient kernel's row: nothing (ENT = false), the entropy term (one pointer in the pack) or entropy and KL (three).
+template <bool ENT, class... Ent>
+__device__ __forceinline__ float ctc_grad_tail(float g, float lpv, float sm, int lane, int V, int b, size_t o, Ent... ent) {
+    static_assert(ENT ? (sizeof...(Ent) == 1 || sizeof...(Ent) == 3) : sizeof...(Ent) == 0,
+                  "no pointer, ent_scale, or (ent_scale, ref_log_probs, kl_scale)");
+    if constexpr (sizeof...(Ent) == 3) return ctc_entropy_kl_grad(g, lpv, sm, lane, V, b, o, ent...);
+    else if constexpr (ENT) return g + ctc_entropy_grad(lpv, sm, b, ent...);
+    else return g;
+}
+
 // one wave per (t,b)
 template <bool ENT, class... Ent>
 __global__ __launch_bounds__(256) void ctc_grad_kernel(
@@ -428,7 +502,6 @@ __global__ __launch_bounds__(256) void ctc_grad_kernel(
     int T, int B, int V, int Lmax, int Smax, int blank, CtcWs ws,
     const float* __restrict__ utt_scale, const float* __restrict__ pg_coef,
     const int32_t* __restrict__ pg_path, int coef_per_frame, float* __restrict__ grad, Ent... ent_scale) {
-    static_assert(sizeof...(Ent) == (ENT ? 1 : 0), "ent_scale iff ENT");
     const int lane = threadIdx.x & 63;
     const long long w = (long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     if (w >= (long long)T * B) return;
@@ -445,7 +518,7 @@ __global__ __launch_bounds__(256) void ctc_grad_kernel(
         const int k = pg_path[(size_t)t * B + b];
         g += pg_coef[coef_per_frame ? (size_t)t * B + b : (size_t)b] * (sm - (lane == k ? 1.f : 0.f));
     }
-    if constexpr (ENT) g += ctc_entropy_grad(lpv, sm, b, ent_scale...);
+    g = ctc_grad_tail<ENT>(g, lpv, sm, lane, V, b, o, ent_scale...);
     if (lane < V) grad[o + lane] = g;
 }
 
@@ -458,7 +531,6 @@ __global__ __launch_bounds__(256) void ctc_grad_multi_kernel(
     int T, int B, int V, int Lmax, int Smax, int blank, CtcWs ws,
     const float* __restrict__ utt_scale, int K, const float* __restrict__ pg_coef,
     const int32_t* __restrict__ pg_paths, float* __restrict__ grad, Ent... ent_scale) {
-    static_assert(sizeof...(Ent) == (ENT ? 1 : 0), "ent_scale iff ENT");
     const int lane = threadIdx.x & 63;
     const long long w = (long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     if (w >= (long long)T * B) return;
@@ -476,7 +548,7 @@ __global__ __launch_bounds__(256) void ctc_grad_multi_kernel(
         const int pk = pg_paths[k * TB + (size_t)t * B + b];
         g += pg_coef[(size_t)k * B + b] * (sm - (lane == pk ? 1.f : 0.f));
     }
-    if constexpr (ENT) g += ctc_entropy_grad(lpv, sm, b, ent_scale...);
+    g = ctc_grad_tail<ENT>(g, lpv, sm, lane, V, b, o, ent_scale...);
     if (lane < V) grad[o + lane] = g;
 }
 
@@ -545,7 +617,6 @@ __global__ __launch_bounds__(256) void ctc_grad_seq_kernel(
     const float* __restrict__ utt_scale, int K, const float* __restrict__ pg_coef,
     const int32_t* __restrict__ pg_paths, const int32_t* __restrict__ hyp_len, int Lh, int Smax_h, CtcWs hws,
     float* __restrict__ grad, Ent... ent_scale) {
-    static_assert(sizeof...(Ent) == (ENT ? 1 : 0), "ent_scale iff ENT");
     const int lane = threadIdx.x & 63;
     const long long w = (long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     if (w >= (long long)T * B) return;
@@ -570,7 +641,7 @@ __global__ __launch_bounds__(256) void ctc_grad_seq_kernel(
             g += pg_coef[p] * (sm - (lane == pk ? 1.f : 0.f));
         }
     }
-    if constexpr (ENT) g += ctc_entropy_grad(lpv, sm, b, ent_scale...);
+    g = ctc_grad_tail<ENT>(g, lpv, sm, lane, V, b, o, ent_scale...);
     if (lane < V) grad[o + lane] = g;
 }
 
@@ -688,12 +759,28 @@ extern "C" int pgasr_ctc_grad_from_lattice_ent(const float* log_probs, const int
                                                const float* utt_scale, const float* pg_coef, const int32_t* pg_path,
                                                int pg_coef_per_frame, const float* ent_scale, float* grad_logits,
                                                void* workspace, size_t workspace_bytes, void* stream) {
+    return pgasr_ctc_grad_from_lattice_kl(log_probs, input_lengths, target_lengths, T, B, V, Lmax, blank, utt_scale, pg_coef, pg_path,
+                                          pg_coef_per_frame, ent_scale, nullptr, nullptr, grad_logits, workspace, workspace_bytes, stream);
+}
+
+// ... and with the KL term: ref_log_probs and kl_scale both NULL launch what the entry above launched, else the three-pointer
+// instantiation (ent_scale may be NULL there)
+extern "C" int pgasr_ctc_grad_from_lattice_kl(const float* log_probs, const int32_t* input_lengths,
+                                              const int32_t* target_lengths, int T, int B, int V, int Lmax, int blank,
+                                              const float* utt_scale, const float* pg_coef, const int32_t* pg_path,
+                                              int pg_coef_per_frame, const float* ent_scale, const float* ref_log_probs,
+                                              const float* kl_scale, float* grad_logits,
+                                              void* workspace, size_t workspace_bytes, void* stream) {
     if (!log_probs || !input_lengths || !target_lengths || !grad_logits) return PGASR_ERR_INVALID_ARG;
+    if ((ref_log_probs == nullptr) != (kl_scale == nullptr)) return PGASR_ERR_INVALID_ARG;
     if ((pg_coef == nullptr) != (pg_path == nullptr)) return PGASR_ERR_INVALID_ARG;
     const int ok = ctc_args_ok(T, B, V, Lmax, blank);
     if (ok != PGASR_OK) return ok;
     CtcWs ws;
     if (!ctc_ws_bind(T, B, V, 2 * Lmax + 1, &ws, workspace, workspace_bytes)) return PGASR_ERR_WORKSPACE;
+    if (kl_scale)
+        return ctc_launch_grad(ctc_grad_kernel<true, const float*, const float*, const float*>, log_probs, input_lengths, target_lengths, T, B, V, Lmax,
+                               blank, ws, utt_scale, stream, pg_coef, pg_path, pg_coef_per_frame ? 1 : 0, grad_logits, ent_scale, ref_log_probs, kl_scale);
     if (ent_scale)
         return ctc_launch_grad(ctc_grad_kernel<true, const float*>, log_probs, input_lengths, target_lengths, T, B, V, Lmax, blank, ws, utt_scale, stream,
                                pg_coef, pg_path, pg_coef_per_frame ? 1 : 0, grad_logits, ent_scale);
@@ -715,12 +802,25 @@ extern "C" int pgasr_ctc_grad_from_lattice_multi_ent(const float* log_probs, con
                                                      const float* utt_scale, int K, const float* pg_coef, const int32_t* pg_paths,
                                                      const float* ent_scale, float* grad_logits, void* workspace,
                                                      size_t workspace_bytes, void* stream) {
+    return pgasr_ctc_grad_from_lattice_multi_kl(log_probs, input_lengths, target_lengths, T, B, V, Lmax, blank, utt_scale, K, pg_coef,
+                                                pg_paths, ent_scale, nullptr, nullptr, grad_logits, workspace, workspace_bytes, stream);
+}
+
+extern "C" int pgasr_ctc_grad_from_lattice_multi_kl(const float* log_probs, const int32_t* input_lengths,
+                                                    const int32_t* target_lengths, int T, int B, int V, int Lmax, int blank,
+                                                    const float* utt_scale, int K, const float* pg_coef, const int32_t* pg_paths,
+                                                    const float* ent_scale, const float* ref_log_probs, const float* kl_scale,
+                                                    float* grad_logits, void* workspace, size_t workspace_bytes, void* stream) {
     if (!log_probs || !input_lengths || !target_lengths || !grad_logits || !pg_coef || !pg_paths) return PGASR_ERR_INVALID_ARG;
+    if ((ref_log_probs == nullptr) != (kl_scale == nullptr)) return PGASR_ERR_INVALID_ARG;
     if (K < 1 || K > PGASR_MAX_SAMPLES) return PGASR_ERR_INVALID_ARG;
     const int ok = ctc_args_ok(T, B, V, Lmax, blank);
     if (ok != PGASR_OK) return ok;
     CtcWs ws;
     if (!ctc_ws_bind(T, B, V, 2 * Lmax + 1, &ws, workspace, workspace_bytes)) return PGASR_ERR_WORKSPACE;
+    if (kl_scale)
+        return ctc_launch_grad(ctc_grad_multi_kernel<true, const float*, const float*, const float*>, log_probs, input_lengths, target_lengths, T, B, V,
+                               Lmax, blank, ws, utt_scale, stream, K, pg_coef, pg_paths, grad_logits, ent_scale, ref_log_probs, kl_scale);
     if (ent_scale)
         return ctc_launch_grad(ctc_grad_multi_kernel<true, const float*>, log_probs, input_lengths, target_lengths, T, B, V, Lmax, blank, ws, utt_scale,
                                stream, K, pg_coef, pg_paths, grad_logits, ent_scale);
@@ -736,6 +836,18 @@ extern "C" int pgasr_frame_entropy(const float* log_probs, const int32_t* input_
     if (V > CTC_VMAX) return PGASR_ERR_UNSUPPORTED;
     PGASR_LAUNCH_KERNEL(frame_entropy_kernel, dim3(B), dim3(64 * ENT_WAVES), 0, (hipStream_t)stream,
                        log_probs, input_lengths, T, B, V, beta, inv_global_batch, ent_mean, ent_scale);
+    PGASR_CHECK_LAUNCH();
+    return PGASR_OK;
+}
+
+// ---- the KL of the frame policy from a frozen reference: kl_mean (B) for monitoring and the loss value, kl_scale (B) for the *_kl passes ----
+extern "C" int pgasr_frame_kl(const float* log_probs, const float* ref_log_probs, const int32_t* input_lengths, int T, int B, int V,
+                              float gamma, float inv_global_batch, float* kl_mean, float* kl_scale, void* stream) {
+    if (!log_probs || !ref_log_probs || !input_lengths || !kl_mean || !kl_scale) return PGASR_ERR_INVALID_ARG;
+    if (T <= 0 || B <= 0 || V <= 0 || !(gamma >= 0.f) || !(inv_global_batch > 0.f)) return PGASR_ERR_INVALID_ARG;
+    if (V > CTC_VMAX) return PGASR_ERR_UNSUPPORTED;
+    PGASR_LAUNCH_KERNEL(frame_kl_kernel, dim3(B), dim3(64 * ENT_WAVES), 0, (hipStream_t)stream,
+                       log_probs, ref_log_probs, input_lengths, T, B, V, gamma, inv_global_batch, kl_mean, kl_scale);
     PGASR_CHECK_LAUNCH();
     return PGASR_OK;
 }
@@ -783,7 +895,19 @@ extern "C" int pgasr_ctc_grad_from_lattices_seq_ent(const float* log_probs, cons
                                                     int K, const float* pg_coef, const int32_t* pg_paths, const int32_t* hyp_len, int Lh,
                                                     const float* ent_scale, float* grad_logits, void* workspace, size_t workspace_bytes,
                                                     void* hyp_workspace, size_t hyp_workspace_bytes, void* stream) {
+    return pgasr_ctc_grad_from_lattices_seq_kl(log_probs, input_lengths, target_lengths, T, B, V, Lmax, blank, utt_scale, K, pg_coef,
+                                               pg_paths, hyp_len, Lh, ent_scale, nullptr, nullptr, grad_logits, workspace, workspace_bytes,
+                                               hyp_workspace, hyp_workspace_bytes, stream);
+}
+
+extern "C" int pgasr_ctc_grad_from_lattices_seq_kl(const float* log_probs, const int32_t* input_lengths, const int32_t* target_lengths,
+                                                   int T, int B, int V, int Lmax, int blank, const float* utt_scale,
+                                                   int K, const float* pg_coef, const int32_t* pg_paths, const int32_t* hyp_len, int Lh,
+                                                   const float* ent_scale, const float* ref_log_probs, const float* kl_scale,
+                                                   float* grad_logits, void* workspace, size_t workspace_bytes,
+                                                   void* hyp_workspace, size_t hyp_workspace_bytes, void* stream) {
     if (!log_probs || !input_lengths || !target_lengths || !grad_logits || !pg_coef || !pg_paths || !hyp_len) return PGASR_ERR_INVALID_ARG;
+    if ((ref_log_probs == nullptr) != (kl_scale == nullptr)) return PGASR_ERR_INVALID_ARG;
     if (Lmax < 0 || blank < 0 || blank >= V) return PGASR_ERR_INVALID_ARG;
     int ok = ctc_hyp_args_ok(T, B, V, K, Lh);
     if (ok == PGASR_OK) ok = ctc_args_ok(T, B, V, Lmax, blank);
@@ -792,6 +916,10 @@ extern "C" int pgasr_ctc_grad_from_lattices_seq_ent(const float* log_probs, cons
     CtcWs ws, hws;
     if (!ctc_ws_bind(T, B, V, 2 * Lmax + 1, &ws, workspace, workspace_bytes)) return PGASR_ERR_WORKSPACE;
     if (!ctc_ws_bind(T, K * B, V, Smax_h, &hws, hyp_workspace, hyp_workspace_bytes)) return PGASR_ERR_WORKSPACE;
+    if (kl_scale)
+        return ctc_launch_grad(ctc_grad_seq_kernel<true, true, const float*, const float*, const float*>, log_probs, input_lengths, target_lengths, T, B,
+                               V, Lmax, blank, ws, utt_scale, stream, K, pg_coef, pg_paths, hyp_len, Lh, Smax_h, hws, grad_logits, ent_scale,
+                               ref_log_probs, kl_scale);
     if (ent_scale)
         return ctc_launch_grad(ctc_grad_seq_kernel<true, true, const float*>, log_probs, input_lengths, target_lengths, T, B, V, Lmax, blank, ws, utt_scale,
                                stream, K, pg_coef, pg_paths, hyp_len, Lh, Smax_h, hws, grad_logits, ent_scale);

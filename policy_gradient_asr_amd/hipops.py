@@ -170,12 +170,14 @@ def _coef_per_frame(pg_coef, T, B):
 
 
 def _grad_pass(entry, log_probs, input_lengths, target_lengths, handle, utt_scale, pg_coef, paths, paths_name, mid, ws_tail=(),
-               label=None, ent_scale=None):
+               label=None, ent_scale=None, ref_log_probs=None, kl_scale=None):
     """The three ``ctc_grad_from_lattice*`` wrappers: entry(log-probs, lengths, shapes, blank, utt_scale, *mid, grad, workspace,
     *ws_tail, stream) into a fresh (T,B,V) gradient.  mid: what the entry point takes between utt_scale and grad_logits, tensors
     as tensors; label: the launch's ``_timed`` name.
     ent_scale (B) fp32 (``frame_entropy``): the entry's ``_ent`` form, which takes it as the last of ``mid`` and adds the entropy
-    term ent_scale_b p (ln p + H) in the same pass.  None: the entry itself -- the same call as before the term existed."""
+    term ent_scale_b p (ln p + H) in the same pass.  None: the entry itself -- the same call as before the term existed.
+    ref_log_probs (T,B,V), kl_scale (B) fp32 (``frame_kl``), both or neither: the entry's ``_kl`` form, which takes them after
+    ent_scale (NULL when that is None) and adds kl_scale_b p (ln p - lnq - KL) after the entropy term.  Neither: the calls above."""
     lib = _lib.load()
     ws, Lmax, blank = handle
     T, B, V = log_probs.shape
@@ -185,6 +187,16 @@ def _grad_pass(entry, log_probs, input_lengths, target_lengths, handle, utt_scal
         if tuple(ent_scale.shape) != (B,):
             raise _lib.PgasrError(f"ent_scale must be ({B},); got {tuple(ent_scale.shape)}")
         entry, mid = entry + "_ent", tuple(mid) + (ent_scale,)
+    if ref_log_probs is not None or kl_scale is not None:
+        if ref_log_probs is None or kl_scale is None:
+            raise _lib.PgasrError("the KL term takes ref_log_probs and kl_scale together")
+        _req(ref_log_probs, torch.float32, "ref_log_probs"); _req(kl_scale, torch.float32, "kl_scale")
+        if ref_log_probs.shape != log_probs.shape or tuple(kl_scale.shape) != (B,):
+            raise _lib.PgasrError(f"ref_log_probs must be {tuple(log_probs.shape)} and kl_scale ({B},); got "
+                                  f"{tuple(ref_log_probs.shape)} and {tuple(kl_scale.shape)}")
+        # the _kl form takes (ent_scale or NULL, ref_log_probs, kl_scale) where the _ent form takes ent_scale
+        entry = (entry[:-4] if ent_scale is not None else entry) + "_kl"
+        mid = (tuple(mid) if ent_scale is not None else tuple(mid) + (None,)) + (ref_log_probs, kl_scale)
     grad = torch.empty_like(log_probs)
     with _timed(label):
         st = getattr(lib, entry)(_p(log_probs), _p(input_lengths), _p(target_lengths), T, B, V, Lmax, blank, _p(utt_scale),
@@ -208,11 +220,33 @@ def _loss_value(entry, log_probs, paths, paths_name, input_lengths, nll, utt_sca
 
 
 def ctc_grad_from_lattice(log_probs, input_lengths, target_lengths, handle, utt_scale=None, pg_coef=None, pg_path=None,
-                          ent_scale=None):
-    """ent_scale (B): add the entropy term of ``frame_entropy`` in the same pass (``_grad_pass``), here and in the two wrappers below."""
+                          ent_scale=None, ref_log_probs=None, kl_scale=None):
+    """ent_scale (B): add the entropy term of ``frame_entropy`` in the same pass (``_grad_pass``), here and in the two wrappers below.
+    ref_log_probs (T,B,V), kl_scale (B): add the KL term of ``frame_kl`` after it, likewise."""
     T, B, _ = log_probs.shape
     return _grad_pass("pgasr_ctc_grad_from_lattice", log_probs, input_lengths, target_lengths, handle, utt_scale, pg_coef, pg_path,
-                      "pg_path", (pg_coef, pg_path, _coef_per_frame(pg_coef, T, B)), ent_scale=ent_scale)
+                      "pg_path", (pg_coef, pg_path, _coef_per_frame(pg_coef, T, B)), ent_scale=ent_scale,
+                      ref_log_probs=ref_log_probs, kl_scale=kl_scale)
+
+
+def frame_kl(log_probs, ref_log_probs, input_lengths, kl_weight=0.0, inv_global_batch=1.0):
+    """The KL of the frame policy from a frozen reference policy (``pgasr_frame_kl``): log_probs, ref_log_probs (T,B,V) fp32,
+    input_lengths (B) int32 -> (kl_mean (B), kl_scale (B)) fp32 in one launch: kl_mean[b] = the MEAN over the utterance's own frames of
+    KL(p || q) = sum_v p (ln p - max(ln q, -104)) (nats; 0 for an empty utterance, not clamped at 0), kl_scale[b] =
+    kl_weight * inv_global_batch / max(T_b,1), what the gradient passes take as ``kl_scale``.  Deterministic; symbols with p = 0 add
+    exactly 0 and a zero reference probability costs the floor, never inf."""
+    lib = _lib.load()
+    _req(log_probs, torch.float32, "log_probs"); _req(ref_log_probs, torch.float32, "ref_log_probs")
+    _req(input_lengths, torch.int32, "input_lengths")
+    if log_probs.dim() != 3 or ref_log_probs.shape != log_probs.shape or input_lengths.numel() != log_probs.shape[1]:
+        raise _lib.PgasrError("frame_kl wants log_probs and ref_log_probs (T,B,V) and input_lengths (B,)")
+    T, B, V = log_probs.shape
+    out = torch.empty(2, B, dtype=torch.float32, device=log_probs.device)
+    with _timed("frame_kl_kernel"):
+        st = lib.pgasr_frame_kl(_p(log_probs), _p(ref_log_probs), _p(input_lengths), T, B, V, float(kl_weight),
+                                float(inv_global_batch), out[0].data_ptr(), out[1].data_ptr(), _stream())
+    _lib.check(st, "pgasr_frame_kl")
+    return out[0], out[1]
 
 
 def frame_entropy(log_probs, input_lengths, entropy_weight=0.0, inv_global_batch=1.0):
@@ -259,7 +293,8 @@ MAX_SAMPLES = 16                 # PGASR_MAX_SAMPLES
 BASELINES = {"hypothesis": 0, "leave_one_out": 1}
 
 
-def ctc_grad_from_lattice_multi(log_probs, input_lengths, target_lengths, handle, utt_scale, pg_coef, pg_paths, ent_scale=None):
+def ctc_grad_from_lattice_multi(log_probs, input_lengths, target_lengths, handle, utt_scale, pg_coef, pg_paths, ent_scale=None,
+                                ref_log_probs=None, kl_scale=None):
     """``ctc_grad_from_lattice`` with K sampled paths: pg_paths (K,T,B) int32, pg_coef (K,B) fp32; the K REINFORCE terms are
     added in k order after the CTC part, in the same pass."""
     T, B, _ = log_probs.shape
@@ -267,7 +302,8 @@ def ctc_grad_from_lattice_multi(log_probs, input_lengths, target_lengths, handle
     if pg_paths.dim() != 3 or tuple(pg_paths.shape[1:]) != (T, B) or tuple(pg_coef.shape) != (K, B):
         raise _lib.PgasrError(f"ctc_grad_from_lattice_multi wants pg_paths (K,{T},{B}) and pg_coef (K,{B})")
     return _grad_pass("pgasr_ctc_grad_from_lattice_multi", log_probs, input_lengths, target_lengths, handle, utt_scale, pg_coef,
-                      pg_paths, "pg_paths", (K, pg_coef, pg_paths), ent_scale=ent_scale)
+                      pg_paths, "pg_paths", (K, pg_coef, pg_paths), ent_scale=ent_scale, ref_log_probs=ref_log_probs,
+                      kl_scale=kl_scale)
 
 
 def pg_rewards_multi(dist, target_lengths, num_samples, lam, inv_global_batch, baseline="hypothesis", reward_lengths=None):
@@ -347,7 +383,7 @@ def ctc_hyp_lattice(log_probs, hyp_tokens, hyp_len, input_lengths, Lh, blank=0):
 
 
 def ctc_grad_from_lattices_seq(log_probs, input_lengths, target_lengths, handle, hyp_handle, utt_scale, pg_coef, pg_paths, hyp_len,
-                               ent_scale=None):
+                               ent_scale=None, ref_log_probs=None, kl_scale=None):
     """One gradient pass over the target lattice (``ctc_lattice``'s handle) and the K*B hypothesis lattices (``ctc_hyp_lattice``'s):
     utt_scale (softmax - occ_target) + sum_k pg_coef[k,b] * (hyp_len[k,b] <= Lh ? softmax - occ_hyp : softmax - onehot(pg_paths[k,t,b])),
     the K terms in k order.  pg_paths (K,T,B) int32, pg_coef (K,B) fp32, hyp_len (K,B) int32."""
@@ -358,7 +394,7 @@ def ctc_grad_from_lattices_seq(log_probs, input_lengths, target_lengths, handle,
         raise _lib.PgasrError(f"ctc_grad_from_lattices_seq wants pg_paths ({K},{T},{B}), pg_coef and hyp_len ({K},{B})")
     return _grad_pass("pgasr_ctc_grad_from_lattices_seq", log_probs, input_lengths, target_lengths, handle, utt_scale, pg_coef,
                       pg_paths, "pg_paths", (K, pg_coef, pg_paths, hyp_len, Lh), ws_tail=(_p(hws), hws.numel()),
-                      label="ctc_grad_seq_kernel", ent_scale=ent_scale)
+                      label="ctc_grad_seq_kernel", ent_scale=ent_scale, ref_log_probs=ref_log_probs, kl_scale=kl_scale)
 
 
 def pg_loss_value_seq(log_probs, paths, input_lengths, nll, utt_scale, pg_coef, hyp_nll, hyp_len, Lh):

@@ -91,7 +91,22 @@ class PGCTCLossFn(torch.autograd.Function):
     no addressing for it.  ``pgasr_frame_entropy`` runs on the side stream beside the lattice; the gradient passes add the term in the
     pass that writes d(logits) (their ``_ent`` entries).  ``PGCTCLossFn.last_entropy``: (B,) mean frame entropy per utterance of the
     last call, detached, on the device (None after a call with weight 0); ``metrics.frame_entropy`` is the same kernel for monitoring.
-    A KL penalty towards a frozen reference policy would be the same kernel with a second log-prob tensor (not built).
+    ``kl_weight = gamma > 0`` with ``ref_log_probs`` (opt-in; 0, the default, is every objective above launch for launch and bit for
+    bit, whether or not a reference tensor is given): a KL penalty towards a frozen reference policy q, the anchor of an RL
+    fine-tune of a pretrained model -- the ``lam`` mix holds the policy near the targets, not near the model it started from.  The
+    reverse KL(p || q) of KL-regularised policy optimisation, per frame, with lnq_v = max(ref_log_probs[t,b,v], -104) (just under
+    ln 2^-149: a zero reference probability costs a large finite penalty, never inf or NaN) and kl_scale_b = gamma / (Bg max(T_b,1)):
+        KL_{t,b}   = sum_v p_v (ln p_v - lnq_v)              nats; a symbol with p_v = 0 adds exactly 0
+        loss      += sum_b kl_scale_b sum_{t<T_b} KL_{t,b}
+        d(logits) += kl_scale_b p_v (ln p_v - lnq_v - KL_{t,b})     for t < T_b, 0 beyond
+    A mean over the utterance's own frames like the entropy bonus, so gamma is in loss units per nat per frame.  It depends on the
+    two log-prob tensors and the lengths alone: with every other option (per_step and entropy_weight included), nothing sampled, no
+    addressing for shards and micro-batches (slice ref_log_probs as the logits are sliced), and an utterance with an infeasible
+    target still gets it.  ref_log_probs is one more tensor input without a gradient: fp32, contiguous, detached, of the logits' shape
+    and device.  ``pgasr_frame_kl`` runs on the side stream after the entropy launch, under the lattice; the gradient passes add the
+    term after the entropy term in the pass that writes d(logits) (their ``_kl`` entries).  ``PGCTCLossFn.last_kl``: (B,) mean frame KL
+    per utterance of the last call, detached, on the device (None after a call with weight 0; not clamped at 0, it can read -1e-7
+    where the policies agree); ``metrics.frame_kl`` is the same kernel for monitoring.
     Returns (loss, stats) where stats = (nll (B), R_s (B), R_g (B)) detached; with K > 1, (nll (B), R_s (K,B), R_b (B)) where
     R_b is the baseline averaged over k (R_g for "hypothesis")."""
 
@@ -104,14 +119,15 @@ class PGCTCLossFn(torch.autograd.Function):
     unit_hits = 0              # how often the shortcut was taken (tests)
     last_sequence_scored = None    # (K,B) bool: the samples of the last score_function="sequence" call that were sequence-scored
     last_entropy = None            # (B,) fp32: mean frame entropy per utterance of the last entropy_weight > 0 call
+    last_kl = None                 # (B,) fp32: mean frame KL(p || reference) per utterance of the last kl_weight > 0 call
     @staticmethod
-    def forward(ctx, logits, in_len, targets, tg_len, log_probs, sample_ids, opt):
-        """opt: the ``PGOptions`` of the call, checked by ``pg_ctc_loss``."""
+    def forward(ctx, logits, in_len, targets, tg_len, log_probs, sample_ids, opt, ref_log_probs=None):
+        """opt: the ``PGOptions`` of the call, checked by ``pg_ctc_loss``; ref_log_probs: read only when opt.kl_weight > 0."""
         T, B, V = logits.shape
-        PGCTCLossFn.last_sequence_scored = PGCTCLossFn.last_entropy = None
+        PGCTCLossFn.last_sequence_scored = PGCTCLossFn.last_entropy = PGCTCLossFn.last_kl = None
         K, beam, blank = opt.num_samples, opt.beam, opt.blank
-        beta = opt.entropy_weight
-        ent_mean = ent_scale = None
+        beta, gamma = opt.entropy_weight, opt.kl_weight
+        ent_mean = ent_scale = kl_mean = kl_scale = None
         loo = opt.baseline == "leave_one_out"
         wd = opt.word_delimiter if opt.reward_unit == "word" else None
         Lh = hipops.hyp_len_cap(T, opt.max_hyp_len) if opt.score_function == "sequence" else None     # the hypothesis-length cap
@@ -146,6 +162,10 @@ class PGCTCLossFn(torch.autograd.Function):
                 # the policy's entropy needs the log-probs alone: first on the side stream, under the lattice
                 ent_mean, ent_scale = hipops.frame_entropy(lp, in_len, beta, inv_gb)
                 PGCTCLossFn.last_entropy = ent_mean
+            if gamma > 0:
+                # .. and so does the KL from the reference, whose log-probs the caller finished on the calling stream
+                kl_mean, kl_scale = hipops.frame_kl(lp, ref_log_probs, in_len, gamma, inv_gb)
+                PGCTCLossFn.last_kl = kl_mean
             # samples (K,T,B); paths = what one collapse takes: [greedy,] samples
             if single:
                 greedy, sample = hipops.frame_argmax_sample(lp, seed=opt.seed, offset=opt.offset, want_greedy=greedy_row, **lay)
@@ -192,9 +212,11 @@ class PGCTCLossFn(torch.autograd.Function):
         nll, lattice = hipops.ctc_lattice(lp, targets, in_len, tg_len, blank=blank)
         main.wait_stream(side)
         for t_ in ((samples, R_b, R_s, coef, utt_scale) + ((tok_len, hyp_nll, scored) if Lh is not None else ())
-                   + ((ent_mean, ent_scale) if beta > 0 else ())):
+                   + ((ent_mean, ent_scale) if beta > 0 else ()) + ((kl_mean, kl_scale, ref_log_probs) if gamma > 0 else ())):
             streams.hold(t_, main)
         ent = {"ent_scale": ent_scale} if beta > 0 else {}        # weight 0: the calls as they were
+        if gamma > 0:
+            ent.update(ref_log_probs=ref_log_probs, kl_scale=kl_scale)
         if single:
             grad = hipops.ctc_grad_from_lattice(lp, in_len, tg_len, lattice, utt_scale=utt_scale, pg_coef=coef, pg_path=sample, **ent)
             terms = hipops.pg_loss_value(lp, sample, in_len, nll, utt_scale, coef)
@@ -206,6 +228,8 @@ class PGCTCLossFn(torch.autograd.Function):
             terms = hipops.pg_loss_value_seq(lp, samples, in_len, nll, utt_scale, coef, hyp_nll, hyp_len, Lh)
         if beta > 0:
             terms = torch.sub(terms, ent_mean, alpha=beta * inv_gb)      # - beta / Bg * (mean frame entropy), on the device
+        if gamma > 0:
+            terms = torch.add(terms, kl_mean, alpha=gamma * inv_gb)      # + gamma / Bg * (mean frame KL), on the device
         loss = terms.sum()
         ctx.save_for_backward(grad)
         ctx.mark_non_differentiable(nll, R_s, R_b)
@@ -251,6 +275,7 @@ class PGOptions:
     score_function: str = "path"
     max_hyp_len: object = None
     entropy_weight: float = 0.0
+    kl_weight: float = 0.0
 
 
 def check_options(opt, vocab=None, frames=None, symbols=None, sample_ids=None):
@@ -269,7 +294,7 @@ def check_options(opt, vocab=None, frames=None, symbols=None, sample_ids=None):
                          f"(pgasr_word_ids); got T = {frames}")
     return dataclasses.replace(opt, num_samples=int(opt.num_samples),
                                max_hyp_len=None if opt.max_hyp_len is None else int(opt.max_hyp_len),
-                               entropy_weight=check_entropy_weight(opt.entropy_weight))
+                               entropy_weight=check_entropy_weight(opt.entropy_weight), kl_weight=check_kl_weight(opt.kl_weight))
 
 
 def check_entropy_weight(entropy_weight):
@@ -281,6 +306,33 @@ def check_entropy_weight(entropy_weight):
         raise ValueError(f"entropy_weight must be finite and >= 0: it weighs the mean frame entropy, in loss units per nat per frame "
                          f"(got {entropy_weight!r})")
     return v
+
+
+def check_kl_weight(kl_weight):
+    """The weight of the KL penalty towards the reference policy, in loss units per nat per frame: a finite real number >= 0 -> float."""
+    if isinstance(kl_weight, bool) or not isinstance(kl_weight, numbers.Real):
+        raise ValueError(f"kl_weight must be a real number >= 0 (got {kl_weight!r})")
+    v = float(kl_weight)
+    if not (v >= 0.0 and v != float("inf")):        # negative, NaN, inf
+        raise ValueError(f"kl_weight must be finite and >= 0: it weighs the mean frame KL from the reference policy, in loss units per "
+                         f"nat per frame (got {kl_weight!r})")
+    return v
+
+
+def _check_reference(ref_log_probs, logits):
+    """The reference log-probs of a kl_weight > 0 call, checked before any kernel runs."""
+    if ref_log_probs is None:
+        raise ValueError("kl_weight > 0 needs ref_log_probs, the frozen reference policy's log-probs for this batch")
+    if not isinstance(ref_log_probs, torch.Tensor) or ref_log_probs.dtype != torch.float32:
+        raise ValueError(f"ref_log_probs must be an fp32 tensor (got {getattr(ref_log_probs, 'dtype', type(ref_log_probs))})")
+    if ref_log_probs.shape != logits.shape:
+        raise ValueError(f"ref_log_probs must have the logits' shape {tuple(logits.shape)} (got {tuple(ref_log_probs.shape)})")
+    if ref_log_probs.device != logits.device:
+        raise ValueError(f"ref_log_probs must be on the logits' device {logits.device} (got {ref_log_probs.device})")
+    if not ref_log_probs.is_contiguous():
+        raise ValueError("ref_log_probs must be contiguous")
+    if ref_log_probs.requires_grad:
+        raise ValueError("ref_log_probs must be detached: the reference policy is frozen and the term has no gradient towards it")
 
 
 def _check_unit(reward_unit, word_delimiter, per_step=False, blank=None, vocab=None):
@@ -329,7 +381,7 @@ def _check_samples(num_samples, baseline, per_step=False):
 
 def pg_ctc_loss(logits, in_len, targets, tg_len, lam=1.0, seed=0, offset=0, global_batch=None, blank=0, beam=0, sample_base=-1,
                 per_step=False, log_probs=None, num_samples=1, baseline="hypothesis", reward_unit="char", word_delimiter=None,
-                sample_ids=None, score_function="path", max_hyp_len=None, entropy_weight=0.0):
+                sample_ids=None, score_function="path", max_hyp_len=None, entropy_weight=0.0, kl_weight=0.0, ref_log_probs=None):
     """beam > 0: the baseline reward comes from the prefix-beam-search hypothesis of that width (see PGCTCLossFn).
     num_samples / baseline: multi-sample REINFORCE (see PGCTCLossFn); with num_samples > 1 the third returned tensor is R_s (K,B).
     reward_unit: "char" (default) or "word" -- the word-level reward R = -WED / W(y) with words split at the token
@@ -344,19 +396,27 @@ def pg_ctc_loss(logits, in_len, targets, tg_len, lam=1.0, seed=0, offset=0, glob
     entropy_weight: beta >= 0, the weight of the entropy bonus on the frame policy -- the loss gains -beta / Bg times every utterance's
     MEAN frame entropy, so beta is in loss units per nat per frame and does not grow with T (see PGCTCLossFn); 0 (default): off, the
     call as it was.  With every other option.
+    kl_weight: gamma >= 0, the weight of the KL penalty towards a frozen reference policy whose log-probs for this batch are
+    ref_log_probs (T,B,V) fp32, contiguous, detached, on the logits' device -- the loss gains gamma / Bg times every utterance's MEAN
+    frame KL(p || q), so gamma is in loss units per nat per frame (see PGCTCLossFn).  With gamma > 0 the tensor is required; 0
+    (default): off, the tensor is ignored and the call is as it was, so a schedule may anneal gamma to 0.  With every other option.
     log_probs: log_softmax(logits) if the caller already has it (the head kernel's by-product, ``logits.log_probs`` of
     Seq2Seq.logits -- picked up from that attribute when not given)."""
     T, B, V = logits.shape
     opt = check_options(PGOptions(lam=float(lam), seed=int(seed), offset=int(offset), global_batch=int(global_batch or B),
                                   blank=int(blank), beam=int(beam), sample_base=int(sample_base), per_step=bool(per_step),
                                   num_samples=num_samples, baseline=baseline, reward_unit=reward_unit, word_delimiter=word_delimiter,
-                                  score_function=score_function, max_hyp_len=max_hyp_len, entropy_weight=entropy_weight),
+                                  score_function=score_function, max_hyp_len=max_hyp_len, entropy_weight=entropy_weight,
+                                  kl_weight=kl_weight),
                         vocab=V, frames=T, symbols=targets.shape[1] if targets.dim() == 2 else 0, sample_ids=sample_ids)
     if log_probs is None:
         # the by-product is valid only for the tensor as the head kernel wrote it: any in-place edit since bumps _version
         log_probs = getattr(logits, "log_probs", None)
         if log_probs is not None and getattr(logits, "log_probs_version", None) != logits._version:
             log_probs = None
+    if opt.kl_weight > 0:
+        _check_reference(ref_log_probs, logits)
+        return PGCTCLossFn.apply(logits, in_len, targets, tg_len, log_probs, sample_ids, opt, ref_log_probs)
     return PGCTCLossFn.apply(logits, in_len, targets, tg_len, log_probs, sample_ids, opt)
 
 

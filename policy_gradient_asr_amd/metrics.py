@@ -89,6 +89,14 @@ def frame_entropy(log_probs, in_len):
     return hipops.frame_entropy(log_probs, in_len, 0.0, 1.0)[0]
 
 
+def frame_kl(log_probs, ref_log_probs, in_len):
+    """Mean frame KL(p || q) of the policy from a reference policy per utterance: log_probs and ref_log_probs (T,B,V) fp32 log-softmax
+    outputs for the same batch and in_len (B) int32 on the GPU -> (B,) fp32 on the device, the mean over each utterance's own frames of
+    sum_v p (ln p - max(ln q, -104)) in nats (0 for an empty utterance and where the two agree).  The kernel of the trainer's
+    ``kl_weight`` term with weight 0 (hipops.frame_kl): how far a fine-tuned model has drifted from its start.  No host round trip."""
+    return hipops.frame_kl(log_probs, ref_log_probs, in_len, 0.0, 1.0)[0]
+
+
 def save_predictions(target, predicted, model_path):
     """predicted.txt with one 'target|prediction' line per utterance (metrics.py:33-37)."""
     path = os.path.join(model_path, "predicted.txt")

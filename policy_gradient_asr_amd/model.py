@@ -211,7 +211,7 @@ def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset
           n_feats=120, lam=1.0, lr=5e-4, resume=True, log_every=10, seed=0, bucket_by_length=True, features="mfcc",
           precision="f32", num_samples=1, reward_baseline="hypothesis", reward_unit="char", max_grad_norm=None,
           accumulate_steps=1, score_function="path", max_hyp_len=None, entropy_weight=0.0, objective="reinforce", mwer_nbest=4,
-          mwer_beam=16):
+          mwer_beam=16, init_from=None, kl_weight=0.0, kl_reference_path=None):
     """Epoch loop of model.py:186-274 on the MI355X path: per-epoch train loss -> train_loss.npy,
     validation CTC loss -> val_losses.npy, model_best.pth / model_last.pth (state_dicts, reference
     names), plus checkpoint_last.pth (model + Adam moments + epoch) from which ``resume`` restarts
@@ -232,6 +232,13 @@ def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset
     entropy_weight: 0 (default: off) or beta > 0 -- entropy regularisation of the frame policy against collapse: the loss gains
     -beta / batch times every utterance's MEAN frame entropy (nats), so beta is in loss units per nat per frame and does not grow with
     T -- PolicyGradientTrainer.  The log lines then carry the batch-mean entropy.
+    init_from: None (default) or the path of a state dict (a ``model_best.pth``, e.g. of a lam=0 CTC run) that the model starts from:
+    loaded after the ``weights`` init when no resume checkpoint is found -- the second stage of the two-stage recipe, CTC pretraining
+    followed by a policy-gradient fine-tune.
+    kl_weight: 0 (default: off) or gamma > 0 -- a KL penalty that anchors the fine-tune to a frozen reference policy: the loss gains
+    gamma / batch times every utterance's MEAN frame KL(policy || reference) in nats -- PolicyGradientTrainer.  The reference is a
+    second model loaded from ``kl_reference_path`` (default: ``init_from``; one of the two is required), also in a resumed run: never
+    from the checkpointed model, which has moved.  The log lines then carry the batch-mean KL.  Not with objective="mwer".
     max_grad_norm: None (default) or a bound > 0 on the global L2 norm of a step's gradient, clipped on the device inside the step
     (clip_grad_norm_ between backward and the update; a step whose gradient holds an inf / NaN is skipped) -- PolicyGradientTrainer.
     The log lines then carry the last gradient norm, and the end of an epoch the counts of clipped and skipped steps.
@@ -257,6 +264,14 @@ def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset
     accumulate_steps = int(accumulate_steps)
     if objective not in ("reinforce", "mwer"):
         raise ValueError(f"objective must be 'reinforce' or 'mwer' (got {objective!r})")
+    from .loss import check_kl_weight
+    kl_weight = check_kl_weight(kl_weight)
+    if kl_reference_path is None:
+        kl_reference_path = init_from
+    if kl_weight > 0 and kl_reference_path is None:
+        raise ValueError("kl_weight > 0 needs the frozen reference policy's weights: give kl_reference_path or init_from")
+    if kl_weight > 0 and objective == "mwer":
+        raise ValueError("objective='mwer' does not take kl_weight (the KL penalty belongs to the sampled objectives)")
     print("Num epochs:", num_epochs, "Batch size:", batch_size)
     alphabet_path = os.path.join(corpus_path, "alphabet.txt")
     alphabet, char2ind = _read_alphabet(alphabet_path)
@@ -285,13 +300,23 @@ def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset
                               max_hyp_len=max_hyp_len, num_samples=num_samples, reward_baseline=reward_baseline,
                               score_function=score_function, entropy_weight=entropy_weight)
     else:
+        kl = {}
+        if kl_weight > 0:
+            # the frozen reference is a model of its own, loaded from its path -- in a resumed run too
+            reference = Seq2Seq(alphabet_size=len(char2ind), n_feats=n_feats)
+            reference.load_state_dict(torch.load(kl_reference_path, map_location="cpu"))
+            kl = {"kl_weight": kl_weight, "kl_reference": reference.to(dev)}
         trainer = PolicyGradientTrainer(model, lr=lr, lam=lam, seed=seed, precision=precision, num_samples=num_samples,
                                         reward_baseline=reward_baseline, reward_unit=reward_unit, word_delimiter=word_delimiter,
                                         max_grad_norm=max_grad_norm, score_function=score_function, max_hyp_len=max_hyp_len,
-                                        entropy_weight=entropy_weight)
+                                        entropy_weight=entropy_weight, **kl)
     losses, val_losses, best, start_epoch = [], [], 9999999.0, 1
     ckpt = os.path.join(model_path, "checkpoint_last.pth")
-    if resume and os.path.exists(ckpt):
+    resuming = resume and os.path.exists(ckpt)
+    if init_from is not None and not resuming:
+        model.load_state_dict(torch.load(init_from, map_location=dev))      # in place: the trainer's flat buffer holds the parameters
+        print("Initialised from", init_from)
+    if resuming:
         st = torch.load(ckpt, map_location=dev)
         model.load_state_dict(st["model"])
         from .train_step import FLAG_PAD
@@ -305,7 +330,8 @@ def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset
         for k, want in (("lr", lr), ("lam", lam), ("num_samples", num_samples), ("reward_baseline", reward_baseline),
                         ("reward_unit", reward_unit), ("max_grad_norm", max_grad_norm),
                         ("accumulate_steps", accumulate_steps), ("score_function", score_function),
-                        ("max_hyp_len", max_hyp_len), ("entropy_weight", entropy_weight)):
+                        ("max_hyp_len", max_hyp_len), ("entropy_weight", entropy_weight), ("kl_weight", kl_weight),
+                        ("kl_reference_path", kl_reference_path)):
             if k in st and st[k] != want:
                 print("Warning: resuming with {}={} but the checkpoint was written with {}".format(k, want, st[k]))
         losses, val_losses, best, start_epoch = st["losses"], st["val_losses"], st["best"], st["epoch"] + 1
@@ -343,6 +369,8 @@ def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset
                     line += " Grad norm: {:>4f}".format(float(trainer.last_grad_norm))
                 if trainer.entropy_weight > 0:
                     line += " Entropy: {:>4f}".format(float(trainer.last_entropy.mean()))
+                if kl_weight > 0:
+                    line += " KL: {:>4f}".format(float(trainer.last_kl.mean()))
                 print(line)
         losses.append(float(acc) / max(step, 1))
         hipops.lstm_assert_no_timeouts()          # .. and before anything of this epoch is written to disk
@@ -380,7 +408,8 @@ def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset
                     "drop_calls": model.encoder._drop_calls, "dropout_seed": model.encoder.dropout_seed,
                     "lr": lr, "lam": lam, "num_samples": num_samples, "reward_baseline": reward_baseline,
                     "reward_unit": reward_unit, "max_grad_norm": max_grad_norm, "accumulate_steps": accumulate_steps,
-                    "score_function": score_function, "max_hyp_len": max_hyp_len, "entropy_weight": trainer.entropy_weight}, ckpt)
+                    "score_function": score_function, "max_hyp_len": max_hyp_len, "entropy_weight": trainer.entropy_weight,
+                    "kl_weight": kl_weight, "kl_reference_path": kl_reference_path}, ckpt)
     return losses, val_losses
 
 

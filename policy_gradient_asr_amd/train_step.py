@@ -7,6 +7,7 @@ optimizer is one Adam over the flat buffer.  Utterances are independent through 
 decode, reward and REINFORCE gradient, so the gradient all-reduce is the only collective; the loss
 is normalised by the GLOBAL batch so 1-GPU and N-GPU gradients agree to fp32 rounding.
 """
+import copy
 import os
 import threading
 
@@ -438,12 +439,12 @@ class PolicyGradientTrainer(DataParallelStep):
     ``step_accumulated(micro_batches, utt_ids=None)`` is one optimizer step over several such batches (DataParallelStep): every
     micro-batch samples with the same offset ``nstep + 1`` and distinct ids -- by default ``default_utt_ids``, micro-batch j a contiguous
     slice of the global batch --, and ``last_stats`` / ``last_sample_rewards`` hold the micro-batches' statistics concatenated in call
-    order (real rows only), and so do ``last_sequence_scored`` and ``last_entropy``."""
+    order (real rows only), and so do ``last_sequence_scored``, ``last_entropy`` and ``last_kl``."""
 
     def __init__(self, model, lr=5e-4, lam=1.0, seed=0, blank=0, world_size=1, process_group=None, rank=0,
                  reward_decoder="greedy", beam_size=16, precision=None, reward_mode="utterance", num_samples=1,
                  reward_baseline="hypothesis", reward_unit="char", word_delimiter=None, max_grad_norm=None,
-                 score_function="path", max_hyp_len=None, entropy_weight=0.0):
+                 score_function="path", max_hyp_len=None, entropy_weight=0.0, kl_weight=0.0, kl_reference=None):
         """reward_mode: "utterance" (default) -- one reward R = -ED / |y| per utterance, the sum of the reference's per-step rewards
         (policy_grad.py:10-15) up to a constant the baseline removes; "per_step" -- the per-step rewards themselves, as rewards-to-go
         per frame against the greedy path's reward-to-go at the same frame (loss.PGCTCLossFn; greedy baseline only).
@@ -470,7 +471,22 @@ class PolicyGradientTrainer(DataParallelStep):
         the loss gains -beta / global_batch times every utterance's MEAN frame entropy (nats), so beta is in loss units per nat per
         frame and does not grow with T (loss.PGCTCLossFn; with every other setting, reward_mode="per_step" included).
         ``last_entropy``: (B,) mean frame entropy of the last step's real utterances, on the device (None with weight 0); nothing
-        synchronises until it is read."""
+        synchronises until it is read.
+        kl_weight: gamma >= 0 (default 0: off, the step as it was -- no reference forward, no launch), a KL penalty towards the frozen
+        reference policy ``kl_reference``, the anchor of an RL fine-tune of a pretrained model: the loss gains gamma / global_batch
+        times every utterance's MEAN frame KL(p || q) in nats, so gamma is in loss units per nat per frame (loss.PGCTCLossFn; with every
+        other setting).  kl_reference: a module with ``Seq2Seq.logits`` and the model's alphabet, not the trained model and sharing no
+        parameter storage with it, or "initial" for a deep copy of ``model`` as it stands at construction; required when gamma > 0.
+        The trainer puts it in eval() with requires_grad_(False) and never updates it.  Every step its logits are computed on the
+        padded batch under no_grad, in the trainer's precision, on the calling stream and BEFORE the policy's forward (the two
+        models' sweeps never run beside each other), which costs one eval forward per step.  ``last_kl``: (B,) mean frame KL of the
+        last step's real utterances, on the device (None with weight 0)."""
+        from .loss import check_kl_weight
+        kl_weight = check_kl_weight(kl_weight)
+        if isinstance(kl_reference, str):
+            if kl_reference != "initial":
+                raise ValueError(f"kl_reference must be a module with Seq2Seq.logits or 'initial' (got {kl_reference!r})")
+            kl_reference = copy.deepcopy(model)          # before the parameters move into the trainer's flat buffer
         super().__init__(model, lr=lr, world_size=world_size, process_group=process_group, precision=precision,
                          max_grad_norm=max_grad_norm)
         if reward_decoder not in ("greedy", "beam"):
@@ -485,9 +501,13 @@ class PolicyGradientTrainer(DataParallelStep):
         self.reward_unit, self.word_delimiter = reward_unit, word_delimiter
         self.score_function, self.max_hyp_len = score_function, max_hyp_len
         self.entropy_weight = entropy_weight
+        self.kl_weight, self.kl_reference = kl_weight, None
         opt = self._checked_options()
         self.num_samples, self.max_hyp_len, self.entropy_weight = opt.num_samples, opt.max_hyp_len, opt.entropy_weight
-        self.last_entropy = None
+        self.last_entropy = self.last_kl = None
+        if kl_reference is not None:
+            self.kl_reference = self._frozen_reference(kl_reference)
+        self._check_kl_reference()
         self.word_delimiter = None if word_delimiter is None else int(word_delimiter)
         self.last_sequence_scored = None
         self.lam = lam
@@ -522,13 +542,57 @@ class PolicyGradientTrainer(DataParallelStep):
     MAX_WORD_FRAMES = 4094     # word-level reward: token rows of at most PGASR_WORD_MAX_STRIDE (frames, target symbols)
     MAX_HYP_LEN = 1023         # sequence-level score: hypotheses of at most this many tokens (2L+1 <= 2048 lattice states)
 
+    def _frozen_reference(self, ref):
+        """``ref`` as the frozen reference policy of the KL term: checked against the trained model, in eval mode, without gradients."""
+        if not callable(getattr(ref, "logits", None)) or not isinstance(ref, torch.nn.Module):
+            raise ValueError("kl_reference must be a module with Seq2Seq.logits(x, fmask, lengths), or 'initial'")
+        if ref is self.model:
+            raise ValueError("kl_reference is the trained model itself: the KL from a policy to itself is 0; pass a frozen copy "
+                             "(kl_reference='initial' deep-copies the model as it stands)")
+        own = {p.untyped_storage().data_ptr() for p in self.model.parameters()}
+        if any(p.untyped_storage().data_ptr() in own for p in ref.parameters()):
+            raise ValueError("kl_reference shares parameter storage with the trained model: the optimizer would move the reference")
+        vocab, ref_vocab = (getattr(getattr(m, "head", None), "out_features", None) for m in (self.model, ref))
+        if vocab != ref_vocab:
+            raise ValueError(f"kl_reference has an alphabet of {ref_vocab} symbols, the model one of {vocab}")
+        ref.eval()
+        ref.requires_grad_(False)
+        for p in ref.parameters():
+            p.grad = None
+        return ref
+
+    def _check_kl_reference(self):
+        if self.kl_weight > 0 and self.kl_reference is None:
+            raise ValueError("kl_weight > 0 needs kl_reference: the frozen reference policy (a module with Seq2Seq.logits, or 'initial')")
+
+    def _reference_log_probs(self, x, fmask, in_len):
+        """The frozen reference's log-probs (T,B,V) for the padded batch: its eval forward under no_grad on the calling stream, in the
+        precision of the running step, complete before the policy's forward starts.  It uses its own encoder's counters (eval mode
+        draws no dropout mask) and leaves grad_overlap as it found it: a feed stream it left unjoined is joined here."""
+        from . import hipops
+        from .functional import grad_overlap
+        key = grad_overlap._key()
+        unjoined = grad_overlap._feed_unjoined.get(key, False)
+        ref = self.kl_reference
+        if ref.training:
+            ref.eval()
+        with torch.no_grad():
+            z, _ = ref.logits(x, fmask, in_len)
+            lp = getattr(z, "log_probs", None)
+            if lp is None or getattr(z, "log_probs_version", None) != z._version or lp.shape != z.shape or not lp.is_contiguous():
+                lp = hipops.log_softmax_rows(z.contiguous())
+        if not unjoined and grad_overlap._feed_unjoined.pop(key, False):
+            torch.cuda.current_stream().wait_stream(grad_overlap.second_side_stream())
+        return lp.detach()
+
     def _checked_options(self, frames=None, symbols=None):
         """This trainer's loss settings as they stand now, through the loss's own check (loss.check_options)."""
         from .loss import PGOptions, check_options
         vocab = getattr(getattr(self.model, "head", None), "out_features", None)
         opt = PGOptions(blank=self.blank, per_step=self.reward_mode == "per_step", num_samples=self.num_samples,
                         baseline=self.reward_baseline, reward_unit=self.reward_unit, word_delimiter=self.word_delimiter,
-                        score_function=self.score_function, max_hyp_len=self.max_hyp_len, entropy_weight=self.entropy_weight)
+                        score_function=self.score_function, max_hyp_len=self.max_hyp_len, entropy_weight=self.entropy_weight,
+                        kl_weight=self.kl_weight)
         return check_options(opt, vocab=vocab, frames=frames, symbols=symbols)
 
     def _check_limits(self, x, targets):
@@ -545,6 +609,7 @@ class PolicyGradientTrainer(DataParallelStep):
         if self.reward_decoder == "beam" and self.beam_size > 128:
             raise ValueError("beam_size > 128 is not supported by pgasr_ctc_beam_search")
         self._checked_options(frames=x.shape[2], symbols=targets.shape[1])
+        self._check_kl_reference()
 
     def staging_stream(self):
         """The stream on which the NEXT batch is to be staged into HBM once ``step()`` has returned (model.py:227-230's
@@ -623,6 +688,10 @@ class PolicyGradientTrainer(DataParallelStep):
             in_len = None
             tg_len = tmask.sum(dim=1).to(torch.int32).contiguous()
             tg = targets.to(torch.int32).contiguous()
+        kl = {}
+        if self.kl_weight > 0:
+            # the frozen reference's sweep first, whole, then the policy's: weight 0 runs neither this forward nor the KL launch
+            kl = {"kl_weight": self.kl_weight, "ref_log_probs": self._reference_log_probs(x, fmask, in_len)}
         logits, in_len = self.model.logits(x, fmask, in_len)
         sample_base, sample_ids = self._sample_addressing(real_b, x.shape[0], x.device)
         loss, nll, R_s, R_g = pg_ctc_loss(logits, in_len, tg, tg_len, lam=self.lam, seed=self.seed,
@@ -633,18 +702,21 @@ class PolicyGradientTrainer(DataParallelStep):
                                           baseline=self.reward_baseline, reward_unit=self.reward_unit,
                                           word_delimiter=self.word_delimiter, sample_ids=sample_ids,
                                           score_function=self.score_function, max_hyp_len=self.max_hyp_len,
-                                          entropy_weight=self.entropy_weight)
+                                          entropy_weight=self.entropy_weight, **kl)
         scored = PGCTCLossFn.last_sequence_scored                # (K,B) bool, None with score_function="path"
         self.last_sequence_scored = scored[:, :real_b] if (padded and scored is not None) else scored
         ent = PGCTCLossFn.last_entropy                           # (B,) mean frame entropy, None with entropy_weight = 0
         self.last_entropy = ent[:real_b] if (padded and ent is not None) else ent
+        klm = PGCTCLossFn.last_kl                                # (B,) mean frame KL from the reference, None with kl_weight = 0
+        self.last_kl = klm[:real_b] if (padded and klm is not None) else klm
         R_all = R_s if R_s.dim() == 2 else R_s.view(1, -1)       # (K,B): every sample's reward
         if R_s.dim() == 2:
             R_s = R_s.mean(dim=0)
         self.last_sample_rewards = R_all[:, :real_b] if padded else R_all
         self.last_stats = (nll[:real_b], R_s[:real_b], R_g[:real_b]) if padded else (nll, R_s, R_g)
         if self._micro is not None and self._micro.count > 1:
-            self._micro_stats.append((self.last_stats, self.last_sample_rewards, self.last_sequence_scored, self.last_entropy))
+            self._micro_stats.append((self.last_stats, self.last_sample_rewards, self.last_sequence_scored, self.last_entropy,
+                                      self.last_kl))
         return loss
 
     def _sample_addressing(self, real_b, padded_b, device):
@@ -677,12 +749,14 @@ class PolicyGradientTrainer(DataParallelStep):
             loss = super()._accumulate(micro_batches, utt_ids, hold_last=hold_last)
             if len(self._micro_stats) > 1:
                 # the micro-batches' statistics in call order, real rows only
-                self.last_stats = tuple(torch.cat([st[i] for st, _, _, _ in self._micro_stats]) for i in range(3))
-                self.last_sample_rewards = torch.cat([r for _, r, _, _ in self._micro_stats], dim=1)
+                self.last_stats = tuple(torch.cat([m[0][i] for m in self._micro_stats]) for i in range(3))
+                self.last_sample_rewards = torch.cat([m[1] for m in self._micro_stats], dim=1)
                 if self.score_function == "sequence":
-                    self.last_sequence_scored = torch.cat([q for _, _, q, _ in self._micro_stats], dim=1)
+                    self.last_sequence_scored = torch.cat([m[2] for m in self._micro_stats], dim=1)
                 if self.entropy_weight > 0:
-                    self.last_entropy = torch.cat([e for _, _, _, e in self._micro_stats])
+                    self.last_entropy = torch.cat([m[3] for m in self._micro_stats])
+                if self.kl_weight > 0:
+                    self.last_kl = torch.cat([m[4] for m in self._micro_stats])
         finally:
             self._micro_stats = []
         return loss
