@@ -740,11 +740,24 @@ int pgasr_ctc_beam_search(const void* log_probs, int is_f64, long long stride_t,
  *             stable descending sort are those of pgasr_ctc_beam_search; the ranking key logsumexp(p_b, p_nb) includes the bonuses.
  *   out_score = -logsumexp(p_blank, p_nonblank) of the best entry: with a language model a FUSED score, not a negative log-likelihood.
  *   lm_table == NULL and lm_order == 0: exactly pgasr_ctc_beam_search (the same kernels, the single-wave dispatch included).
- *   With a table every call takes the workgroup-per-utterance kernel (the single-wave kernel has no LM term); the LM arithmetic is
+ *   With a table every call without flags bit 4 takes the workgroup-per-utterance kernel; the LM arithmetic is
  *   fp64 for fp32 and fp64 log_probs alike; lm_alpha = lm_beta = 0 gives the no-LM result of that kernel bit for bit.
+ *   flags bit 4 (value 16, "single-wave LM"), here and on pgasr_ctc_beam_search_nbest: with a table, the call takes the single-wave
+ *             kernel's LM instantiations (the same algebra on that kernel's lane layout: the table words of a frame are gathered at
+ *             its top, 8 or 16 consecutive words per lane, and parked in LDS for the winners) when ALL of these hold: a table is
+ *             given, fp32 log_probs, beam <= 16, V <= 64, T * beam <= 24576, T <= 4096 -- pgasr_beam_lm_single_wave_ok says so
+ *             beforehand.  The bit is an explicit choice and is not overridden by bit 1.  Scores agree with the workgroup kernel's to
+ *             ~1e-7 relative (both carry fp64 sums with fp32 exp/log on differences), hypotheses wherever no two candidates are
+ *             closer than that; lm_alpha = lm_beta = 0 gives the no-LM result of the single-wave kernel bit for bit.  Without a
+ *             table or outside those limits the bit changes nothing, and without the bit every call is what it was, bit for bit --
+ *             bit 3 of pgasr_ctc_beam_search_nbest with a table included, which stays on the workgroup kernel.  Every refusal is
+ *             the same with the bit.
  *   Checked before any HIP call: lm_order < 0, lm_order > 0 with a NULL table, a table with lm_order == 0, non-finite weights
  *   -> PGASR_ERR_INVALID_ARG; the size cap -> PGASR_ERR_UNSUPPORTED.
+ * pgasr_beam_lm_single_wave_ok: 1 where flags bit 4 takes the single-wave kernel for (T, V, beam, is_f64, lm_order) -- lm_order > 0 with
+ *   V^lm_order <= 2^25, is_f64 == 0 and the four limits above --, else 0.  Host only: no HIP call.
  * ---------------------------------------------------------------------------------------- */
+int pgasr_beam_lm_single_wave_ok(int T, int V, int beam, int is_f64, int lm_order);
 int pgasr_ctc_beam_search_lm(const void* log_probs, int is_f64, long long stride_t, long long stride_b,
                              const int32_t* lengths, int T, int B, int V, int beam, int blank, int flags,
                              int32_t* out_tokens, int32_t* out_len, double* out_score,
@@ -774,6 +787,9 @@ int pgasr_ctc_beam_search_lm(const void* log_probs, int is_f64, long long stride
  *               then, bit for bit, what pgasr_ctc_beam_search returns by default; the list is that kernel's final beam in its rank
  *               order, lane r of the wave walking entry r's ancestors through the trie in LDS.  Outside those conditions the bit
  *               changes nothing: the call is the call without it, launch for launch.  Every refusal below is the same with the bit.
+ *   flags bit 4 (value 16, "single-wave LM"): as on pgasr_ctc_beam_search_lm -- with a table and inside the limits there the list is
+ *               the final beam of the single-wave kernel's LM instantiation, and row 0 is, bit for bit, what pgasr_ctc_beam_search_lm
+ *               returns with bit 4.  Bit 3 is not needed for it and, alone, keeps a call with a table on the workgroup kernel.
  *   Every ancestor walk ends after lengths[b] steps at the latest, whatever the node store holds.
  *   Checked before any HIP call, in this order: the search's argument checks, its limits and the LM's checks as in
  *   pgasr_ctc_beam_search_lm; nbest < 1, nbest > beam, tok_stride < T, a NULL output -> PGASR_ERR_INVALID_ARG; then the

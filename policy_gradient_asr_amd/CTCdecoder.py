@@ -28,15 +28,19 @@ NBestRescored = collections.namedtuple("NBestRescored", "order total am lm_logp 
 
 
 class CTCDecoder:
-    def __init__(self, alphabet, device=None, lm=None, lm_alpha=0.0, lm_beta=0.0):
+    def __init__(self, alphabet, device=None, lm=None, lm_alpha=0.0, lm_beta=0.0, fast_lm=False):
         """lm: None (default: the acoustic search of the reference) or a ``lm.CharNgramLM``; every extension of a prefix by a
         non-blank symbol s then gets ``lm_alpha * ln p_lm(s | last order-1 symbols) + lm_beta`` added (Hannun/Maas,
         arXiv:1408.2873 -- the place CTCdecoder.py:90-96 marks for an LM score).  ``decode`` / ``decode_batch`` use these values
-        unless a call overrides them."""
+        unless a call overrides them.
+        fast_lm: ``decode_batch`` with an LM takes the single-wave kernel where its limits allow (``hipops.ctc_beam_search``:
+        fp32 log-probs, beam_size <= 16, at most 64 symbols, T * beam_size <= 24576, T <= 4096) instead of the several times slower
+        workgroup kernel; a call may override it.  ``decode`` is the fp64 drop-in and always takes the exact kernel."""
         self.alphabet = alphabet
         self.NEG_INF = -float("inf")
         self.device = device
         self.lm, self.lm_alpha, self.lm_beta = lm, float(lm_alpha), float(lm_beta)
+        self.fast_lm = bool(fast_lm)
 
     def _lm_args(self, lm, lm_alpha, lm_beta):
         return {"lm": self.lm if lm is _UNSET else lm,
@@ -73,16 +77,19 @@ class CTCDecoder:
         n = int(tl[0].item())
         return tuple(int(x) for x in tokens[0, :n].tolist()), float(score[0].item())
 
-    def decode_batch(self, log_probs, lengths=None, beam_size=5, blank=0, lm=_UNSET, lm_alpha=None, lm_beta=None, nbest=None):
+    def decode_batch(self, log_probs, lengths=None, beam_size=5, blank=0, lm=_UNSET, lm_alpha=None, lm_beta=None, fast_lm=None,
+                     nbest=None):
         """Device-side batched form: log_probs (T,B,V) GPU tensor of natural-log probabilities.
         Returns (tokens (B,T) int32, lengths (B) int32, nll (B) float64) without a host sync.  With a language model (see
         ``decode``) the third value is the fused score, not a negative log-likelihood.
         nbest: None (default: the triple above) or N with 1 <= N <= beam_size: ``hipops.CTCNBest`` (tokens (N,B,T), lengths (N,B),
-        score (N,B), count (B)), still without a host sync; see ``hipops.ctc_beam_search_nbest``."""
+        score (N,B), count (B)), still without a host sync; see ``hipops.ctc_beam_search_nbest``.
+        fast_lm: None (default: the decoder's own) or a bool -- with an LM, take the single-wave kernel where its limits allow."""
+        fast_lm = self.fast_lm if fast_lm is None else bool(fast_lm)
         if nbest is not None:
             return hipops.ctc_beam_search_nbest(log_probs, lengths, beam=int(beam_size), nbest=int(nbest), blank=int(blank),
-                                                **self._lm_args(lm, lm_alpha, lm_beta))
-        return hipops.ctc_beam_search(log_probs, lengths, beam=int(beam_size), blank=int(blank),
+                                                fast_lm=fast_lm, **self._lm_args(lm, lm_alpha, lm_beta))
+        return hipops.ctc_beam_search(log_probs, lengths, beam=int(beam_size), blank=int(blank), fast_lm=fast_lm,
                                       **self._lm_args(lm, lm_alpha, lm_beta))
 
     def rescore(self, log_probs, lengths, nb, lm=_UNSET, lm_alpha=None, lm_beta=None, acoustic="ctc", am_weight=1.0, max_hyp_len=None,

@@ -93,6 +93,7 @@ SIGNATURES = {
     "pgasr_ctc_beam_search_lm": (C.c_int, [c_ptr, C.c_int, C.c_longlong, C.c_longlong, c_i32p, C.c_int, C.c_int, C.c_int,
                                            C.c_int, C.c_int, C.c_int, c_i32p, c_i32p, c_ptr, c_ptr, C.c_size_t, c_ptr,
                                            c_f32p, C.c_int, C.c_double, C.c_double]),
+    "pgasr_beam_lm_single_wave_ok": (C.c_int, [C.c_int] * 5),
     "pgasr_ctc_beam_search_nbest": (C.c_int, [c_ptr, C.c_int, C.c_longlong, C.c_longlong, c_i32p, C.c_int, C.c_int, C.c_int,
                                               C.c_int, C.c_int, C.c_int, C.c_int, c_i32p, C.c_int, c_i32p, c_ptr, c_i32p,
                                               c_ptr, C.c_size_t, c_ptr, c_f32p, C.c_int, C.c_double, C.c_double]),

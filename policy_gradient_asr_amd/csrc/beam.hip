@@ -511,11 +511,37 @@ struct SmallNbest {
     int tok_stride;          // out_tokens is (nbest, B, tok_stride), tok_stride >= T
 };
 
-template <int SPL, bool NBEST = false>
+// Language-model fusion (LM = true, flags bit 4 of pgasr_ctc_beam_search_lm / _nbest): the algebra of beam_search_kernel<.., LM = true> above
+// (tests/beam_lm_ref.py states it in plain Python) on this kernel's lane layout.
+//   * an entry carries, replicated per row like pb / pnb / tot: ctx = the index of its last n-1 symbols (the root: ctx0) and lmp = the table
+//     word of its own last emission, table[ctx(parent prefix) V + last].  (The index of that word, the workgroup kernel's lmi, is only a
+//     temporary here: that kernel reloads the word every frame, this one keeps it.)
+//   * lane (q, j) gathers table[ctx_j V + SPL q + i], i < SPL -- consecutive words -- at the top of the frame, where j < nb, the symbol is
+//     < V and not blank; every other lane and slot loads nothing and uses 0.  ctx is checked against ctx_mod first, so every index is
+//     < ctx_mod V = V^n.  The loads are in flight beside the parent lookup and the stay candidate and are waited for once, at the keys.
+//   * w = __dadd_rn(__dmul_rn(alpha, (double)word), beta) as in the workgroup kernel: an extension scores (p + lp) + w, the merged term of the
+//     stay candidate (parent i extended by last(j)) gets w(lmp_j); the blank update and the repeat branch are unchanged.
+//   * the frame's words are parked in LDS (K_MAX x 4 SPL fp32 behind the trie's control words): winner r reads its word there as it reads
+//     its log-prob in `frames` -- no second gather on the dependent chain -- and sets lmp = that word, ctx = (ctx_parent V + s) % ctx_mod;
+//     a stay inherits both.
+// Keys, pop rounds, tied_last, the trie and both result tails are the LM = false code.  The arguments ride in the last parameter: with LM it
+// is a struct of the tail's own argument and BeamLm<true>; without, it is the type it always was (an empty struct behind it would still add
+// four bytes to the kernel-argument segment), so those instantiations keep their argument list, their LDS, their code and their descriptor.
+struct SmallLmScore { double* out_score; BeamLm<true> lm; };      // the 1-best tail's last argument with a language model
+struct SmallLmNbest : SmallNbest { BeamLm<true> lm; };           // the N-best tail's
+template <bool NBEST, bool LM> struct small_tail { using type = typename std::conditional<NBEST, const SmallNbest, double* __restrict__>::type; };
+template <> struct small_tail<false, true> { using type = const SmallLmScore; };
+template <> struct small_tail<true, true> { using type = const SmallLmNbest; };
+__device__ __forceinline__ double* small_score(double* p) { return p; }
+__device__ __forceinline__ double* small_score(const SmallLmScore& a) { return a.out_score; }
+constexpr size_t lds_lm(int spl) { return (size_t)K_MAX * (4 * spl) * 4; }
+constexpr size_t lds_bytes_lm(int spl) { return lds_bytes(spl) + lds_lm(spl); }      // 148.1 KB at SPL = 16
+
+template <int SPL, bool NBEST = false, bool LM = false>
 __global__ __launch_bounds__(64) void beam_small_kernel(
     const float* __restrict__ lp, long long stride_t, long long stride_b, const int32_t* __restrict__ lengths,
     int T, int V, int K, int blank, int collapse, int32_t* __restrict__ out_tokens, int32_t* __restrict__ out_len,
-    typename std::conditional<NBEST, const SmallNbest, double* __restrict__>::type out_score) {
+    typename small_tail<NBEST, LM>::type out_score) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned* table = reinterpret_cast<unsigned*>(smem);
     static_assert(SPL == 8 || SPL == 16, "8 or 16 symbols per lane");
@@ -525,6 +551,7 @@ __global__ __launch_bounds__(64) void beam_small_kernel(
     using mask_t = typename std::conditional<SPL == 8, unsigned, unsigned long long>::type;      // one bit per symbol
     float* frames = reinterpret_cast<float*>(smem + LDS_TABLE);
     mask_t* mm = reinterpret_cast<mask_t*>(smem + LDS_TABLE + lds_frames(SPL));
+    [[maybe_unused]] float* lmw = reinterpret_cast<float*>(smem + LDS_TABLE + lds_frames(SPL) + LDS_MM);      // LM only: [K_MAX][VM] table words of the frame
     const int b = blockIdx.x, lane = threadIdx.x, q = lane >> 4, j = lane & 15;
     int Tb = lengths ? lengths[b] : T; Tb = Tb < 0 ? 0 : (Tb > T ? T : Tb);
 
@@ -539,6 +566,9 @@ __global__ __launch_bounds__(64) void beam_small_kernel(
     unsigned id = (j == 0) ? ROOT : BAD_ID, par = NONE;
     int last = -1;
     int nb = 1, root_pos = 0;
+    [[maybe_unused]] int ctx = 0;             // LM only: context index of the entry's prefix
+    [[maybe_unused]] float lmp = 0.0f;        // LM only: table word of the entry's own last emission (unused while last < 0)
+    if constexpr (LM) ctx = out_score.lm.ctx0;
 
     const float* base = lp + (long long)b * stride_b;
     constexpr int FPI = 64 / VM, NPRE = CH / FPI;          // frames one wave instruction covers (2 / 1), instructions per chunk
@@ -565,6 +595,17 @@ __global__ __launch_bounds__(64) void beam_small_kernel(
             commit((t >> 5) & 1);
             issue(t + CH);
             __syncthreads();
+        }
+        [[maybe_unused]] float tv[SPL];
+        if constexpr (LM) {      // issue the gathers first: nothing depends on them until the keys
+            const BeamLm<true>& lm = out_score.lm;
+            const bool ok = (j < nb) && ((unsigned)ctx < (unsigned)lm.ctx_mod);      // ctx V + s < ctx_mod V = V^n <= 2^25
+            const float* row = lm.table + ((long long)(ok ? ctx : 0) * V + SPL * q);
+#pragma unroll
+            for (int i = 0; i < SPL; ++i) {
+                const int s = SPL * q + i;
+                tv[i] = (ok && s < V && s != blank) ? row[i] : 0.0f;
+            }
         }
         const float* fr = frames + ((t >> 5) & 1) * (CH * VM) + (t & (CH - 1)) * VM;
         float lpv[SPL];
@@ -596,7 +637,8 @@ __global__ __launch_bounds__(64) void beam_small_kernel(
         const bool has_last = last >= 0, has_par = pidx >= 0;
         const double dla = (double)lp_la;
         const double own = has_last ? pnb + dla : -INFINITY;                                    // repeat of the last symbol
-        const double ext = (has_last && has_par) ? ((last_i == last) ? pb_i : tot_i) + dla : -INFINITY;   // parent i extended by it
+        double ext = (has_last && has_par) ? ((last_i == last) ? pb_i : tot_i) + dla : -INFINITY;   // parent i extended by it
+        if constexpr (LM) ext += __dadd_rn(__dmul_rn(out_score.lm.alpha, (double)lmp), out_score.lm.beta);             // that extension's own table word (-inf stays -inf)
         const double npnb = lse2f(ext, own);
         const unsigned lbits = (unsigned)(has_last ? last : 0) << 5;
         const unsigned t_bl = ((unsigned)blank << 5) | ((unsigned)j << 1);
@@ -612,12 +654,18 @@ __global__ __launch_bounds__(64) void beam_small_kernel(
                                                  (unsigned)__builtin_amdgcn_readlane((int)(unsigned)tb0, 0));
         const double ref = (tot0 == -INFINITY) ? 0.0 : tot0;
         unsigned long long k[SPL];
+        if constexpr (LM) {      // park the frame's words for the winners: lane (q, j) owns row j's words SPL q .. SPL q + SPL - 1
+#pragma unroll
+            for (int c = 0; c < SPL / 4; ++c)
+                *reinterpret_cast<float4*>(lmw + j * VM + SPL * q + 4 * c) = make_float4(tv[4 * c], tv[4 * c + 1], tv[4 * c + 2], tv[4 * c + 3]);
+        }
 #pragma unroll
         for (int i = 0; i < SPL; ++i) {
             const int s = SPL * q + i;
             const bool is_bl = (s == blank);
             const bool alive = (j < nb) && (s < V) && (is_bl || !((mmask >> s) & (mask_t)1));
-            const double sx = ((s == last) ? pb : tot) + (double)lpv[i];
+            double sx = ((s == last) ? pb : tot) + (double)lpv[i];
+            if constexpr (LM) sx += __dadd_rn(__dmul_rn(out_score.lm.alpha, (double)tv[i]), out_score.lm.beta);
             const double sc = is_bl ? sstay : sx;
             const unsigned tk = is_bl ? tie : (((unsigned)s << 5) | ((unsigned)j << 1));
             const long long bits = __double_as_longlong(sc - ref);
@@ -774,6 +822,13 @@ __global__ __launch_bounds__(64) void beam_small_kernel(
         const unsigned g_id = (unsigned)__shfl((int)id, pj, 16), g_par = (unsigned)__shfl((int)par, pj, 16);
         const int g_last = __shfl(last, pj, 16);
         const float lps = fr[valid ? s : 0];
+        [[maybe_unused]] float g_word = 0.0f, g_lmp = 0.0f;
+        [[maybe_unused]] int g_ctx = 0;
+        if constexpr (LM) {
+            g_word = lmw[valid ? pj * VM + s : 0];      // pj < 16, s < VM: inside the K_MAX x VM words; parked before the rounds (DS operations of one wave execute in issue order)
+            g_lmp = __shfl(lmp, pj, 16);
+            g_ctx = __shfl(ctx, pj, 16);
+        }
 
         // beam-position bits of the outgoing entries are cleared before the incoming ones are set
         if (lane < nb && id != ROOT) atomicAnd(&table[id], KEYMASK);
@@ -811,14 +866,24 @@ __global__ __launch_bounds__(64) void beam_small_kernel(
         root_pos = rootm ? (__ffsll((long long)rootm) - 1) : -1;
 
         if (valid) {
-            if (stay) { pb = g_npb; pnb = g_npnb; tot = g_sstay; last = g_last; par = g_par; }
-            else {
+            if (stay) {
+                pb = g_npb; pnb = g_npnb; tot = g_sstay; last = g_last; par = g_par;
+                if constexpr (LM) { ctx = g_ctx; lmp = g_lmp; }
+            } else {
                 pb = -INFINITY;
                 pnb = ((s == g_last) ? g_pb : g_tot) + (double)lps;
+                if constexpr (LM) {      // the candidate's score as its key had it; its word becomes the entry's own
+                    pnb += __dadd_rn(__dmul_rn(out_score.lm.alpha, (double)g_word), out_score.lm.beta);
+                    lmp = g_word;
+                    ctx = (int)((unsigned)(g_ctx * V + s) % (unsigned)out_score.lm.ctx_mod);
+                }
                 tot = pnb; last = s; par = g_id;
             }
             id = n_id;
-        } else { pb = pnb = tot = -INFINITY; last = -1; par = NONE; id = BAD_ID; }
+        } else {
+            pb = pnb = tot = -INFINITY; last = -1; par = NONE; id = BAD_ID;
+            if constexpr (LM) { ctx = 0; lmp = 0.0f; }
+        }
         nb = nnew;
     }
 
@@ -894,9 +959,9 @@ __global__ __launch_bounds__(64) void beam_small_kernel(
     if (lane == 0) {
         out_len[b] = outn;
         const double t0 = __shfl(tot, 0, 64);
-        out_score[b] = (Tb > 0) ? -t0 : -0.0;
+        small_score(out_score)[b] = (Tb > 0) ? -t0 : -0.0;
 #ifdef PGASR_BEAM_DIAG
-        if (getenv_cycles_) out_score[b] = (double)(clock64() - dg_c0_) / (double)(Tb > 0 ? Tb : 1);      // cycles per frame of this utterance
+        if (getenv_cycles_) small_score(out_score)[b] = (double)(clock64() - dg_c0_) / (double)(Tb > 0 ? Tb : 1);      // cycles per frame of this utterance
 #endif
     }
     }
@@ -917,6 +982,15 @@ extern "C" int pgasr_diag_beam_counters(unsigned long long* out, int reset) {   
 extern "C" size_t pgasr_beam_workspace_bytes(int T, int B, int V, int beam) {
     if (T <= 0 || B <= 0 || V <= 0 || beam <= 0) return 0;
     return beam_ws_layout(T, B, beam, nullptr, nullptr);
+}
+
+// Which kernel flags bit 4 picks (include/pgasr_hip.h, A7-LM): 1 = the single-wave kernel's LM instantiations.  Host only, no HIP call.
+extern "C" int pgasr_beam_lm_single_wave_ok(int T, int V, int beam, int is_f64, int lm_order) {
+    if (T <= 0 || V <= 0 || beam <= 0 || lm_order <= 0 || is_f64) return 0;
+    if (beam > sb::K_MAX || V > sb::V_MAX || (long long)T * beam > sb::MAX_NODES || T > sb::MAX_TOKENS) return 0;
+    long long entries = 1;
+    for (int k = 0; k < lm_order; ++k) { entries *= V; if (entries > BEAM_LM_MAX_ENTRIES) return 0; }      // such a table is refused by the search itself
+    return 1;
 }
 
 namespace {
@@ -959,6 +1033,17 @@ int beam_search_impl(const void* log_probs, int is_f64, long long stride_t, long
 #else
     const int collapse = flags & 1;
 #endif
+    if (with_lm && (flags & 16) && pgasr_beam_lm_single_wave_ok(T, V, beam, is_f64, lm_order)) {
+        // flags bit 4: the single-wave kernel's LM instantiations (the same limits as below; the bit is the caller's explicit choice, so bit 1 is not consulted)
+        auto kern = V <= 32 ? &sb::beam_small_kernel<8, false, true> : &sb::beam_small_kernel<16, false, true>;
+        const size_t lds_small = sb::lds_bytes_lm(V <= 32 ? 8 : 16);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_small);
+        const sb::SmallLmScore sl{out_score, lm};
+        PGASR_LAUNCH_KERNEL(kern, dim3(B), dim3(64), lds_small, st, (const float*)log_probs, stride_t, stride_b,
+                           lengths, T, V, beam, blank, collapse, out_tokens, out_len, sl);
+        PGASR_CHECK_LAUNCH();
+        return PGASR_OK;
+    }
     if (!with_lm && !is_f64 && !(flags & 2) && beam <= sb::K_MAX && V <= sb::V_MAX && (long long)T * beam <= sb::MAX_NODES && T <= sb::MAX_TOKENS) {
         // training path: one wave per utterance, trie and candidate lists in LDS, no workspace traffic; 8 symbols per lane up to V = 32
         // (the English alphabet of the headline), 16 up to V = 64 (round 5: CommonVoice's larger alphabets stay on this kernel)
@@ -981,7 +1066,7 @@ int beam_search_impl(const void* log_probs, int is_f64, long long stride_t, long
         PGASR_LAUNCH_KERNEL((beam_search_kernel<TIN, FAST, LMB>), dim3(B), dim3(BEAM_THREADS), lds, st, (const TIN*)log_probs,    \
                            stride_t, stride_b, lengths, T, V, beam, blank, collapse, ws, out_tokens, out_len, out_score, LMARG);  \
     }
-    if (with_lm) {      // with a language model every call takes this kernel (the single-wave kernel has no LM term)
+    if (with_lm) {      // with a language model every call without flags bit 4 takes this kernel
         if (is_f64) BEAM_LAUNCH(double, false, true, lm) else BEAM_LAUNCH(float, true, true, lm)
     } else {
         if (is_f64) BEAM_LAUNCH(double, false, false, BeamLm<false>{}) else BEAM_LAUNCH(float, true, false, BeamLm<false>{})
@@ -1033,6 +1118,16 @@ extern "C" int pgasr_ctc_beam_search_nbest(const void* log_probs, int is_f64, lo
     if (lds > 160 * 1024) return PGASR_ERR_UNSUPPORTED;
     hipStream_t st = (hipStream_t)stream;
     const int collapse = flags & 1;
+    if (with_lm && (flags & 16) && pgasr_beam_lm_single_wave_ok(T, V, beam, is_f64, lm_order)) {      // flags bit 4, as in the 1-best dispatch
+        auto kern = V <= 32 ? &sb::beam_small_kernel<8, true, true> : &sb::beam_small_kernel<16, true, true>;
+        const size_t lds_small = sb::lds_bytes_lm(V <= 32 ? 8 : 16);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_small);
+        const sb::SmallLmNbest sn{{out_score, out_count, nbest, tok_stride}, lmb};
+        PGASR_LAUNCH_KERNEL(kern, dim3(B), dim3(64), lds_small, st, (const float*)log_probs, stride_t, stride_b,
+                           lengths, T, V, beam, blank, collapse, out_tokens, out_len, sn);
+        PGASR_CHECK_LAUNCH();
+        return PGASR_OK;
+    }
     if ((flags & 8) && !with_lm && !is_f64 && beam <= sb::K_MAX && V <= sb::V_MAX && (long long)T * beam <= sb::MAX_NODES && T <= sb::MAX_TOKENS) {
         auto kern = V <= 32 ? &sb::beam_small_kernel<8, true> : &sb::beam_small_kernel<16, true>;
         const size_t lds_small = sb::lds_bytes(V <= 32 ? 8 : 16);

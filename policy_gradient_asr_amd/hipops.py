@@ -1180,8 +1180,14 @@ def lstm_cell(gh, xp, c, h, h_out=None):
 # ------------------------------------------------------------------------------------------
 # prefix beam search
 # ------------------------------------------------------------------------------------------
+def beam_lm_single_wave_ok(T, V, beam, is_f64, lm_order):
+    """Whether ``fast_lm=True`` takes the single-wave kernel's LM instantiations for this shape (pgasr_beam_lm_single_wave_ok: a
+    table, fp32 log-probs, beam <= 16, V <= 64, T * beam <= 24576, T <= 4096).  Host only: no device is touched."""
+    return bool(_lib.load().pgasr_beam_lm_single_wave_ok(int(T), int(V), int(beam), int(bool(is_f64)), int(lm_order)))
+
+
 def ctc_beam_search(log_probs, lengths=None, beam=5, blank=0, collapse=False, out=None, generic=False,
-                    lm=None, lm_alpha=0.0, lm_beta=0.0):
+                    lm=None, lm_alpha=0.0, lm_beta=0.0, fast_lm=False):
     """log_probs (T,B,V) fp32 or fp64 natural-log probabilities on the GPU.
     Returns (tokens (B,T) int32, token_lengths (B) int32, score (B) float64 = -log p).
     collapse: the returned tokens have gone through collapse_fn (adjacent duplicates removed, CTCdecoder.py:119-131),
@@ -1190,7 +1196,11 @@ def ctc_beam_search(log_probs, lengths=None, beam=5, blank=0, collapse=False, ou
     lm: None (default: the acoustic search, the kernels and bits it always had) or a ``lm.CharNgramLM`` over the same V symbols and
     blank: every extension by a non-blank s gets ``lm_alpha * ln p_lm(s | context) + lm_beta`` added (pgasr_ctc_beam_search_lm in
     include/pgasr_hip.h).  The returned score is then a FUSED score, not a negative log-likelihood.  With an LM every call takes the
-    workgroup-per-utterance kernel."""
+    workgroup-per-utterance kernel, unless
+    fast_lm: the call takes the single-wave kernel with the LM term where ``beam_lm_single_wave_ok`` says so (an LM, fp32, beam <= 16,
+    V <= 64, T * beam <= 24576, T <= 4096): the same algebra, several times faster; its scores agree with the workgroup kernel's to
+    ~1e-7 relative, its hypotheses wherever no two candidates are closer than that.  Without an LM or outside those limits the flag
+    changes nothing."""
     lib = _lib.load()
     if not log_probs.is_cuda or log_probs.dtype not in (torch.float32, torch.float64):
         raise _lib.PgasrError("log_probs must be a float32/float64 GPU tensor")
@@ -1217,7 +1227,8 @@ def ctc_beam_search(log_probs, lengths=None, beam=5, blank=0, collapse=False, ou
     with _timed("beam_search"):
         # one entry point for both: without a table it IS pgasr_ctc_beam_search
         st = lib.pgasr_ctc_beam_search_lm(_p(log_probs), int(log_probs.dtype == torch.float64), log_probs.stride(0),
-                                          log_probs.stride(1), _p(lengths), T, B, V, int(beam), int(blank), int(bool(collapse)) | (2 if generic else 0),
+                                          log_probs.stride(1), _p(lengths), T, B, V, int(beam), int(blank),
+                                          int(bool(collapse)) | (2 if generic else 0) | (16 if fast_lm else 0),
                                           _p(tokens), _p(tl), _p(score), _p(ws), ws.numel(), _stream(),
                                           _p(lm_table), lm_order, float(lm_alpha), float(lm_beta))
     _lib.check(st, "pgasr_ctc_beam_search_lm")
@@ -1237,7 +1248,7 @@ def _lm_table(lm, V, blank, device):
 
 
 def ctc_beam_search_nbest(log_probs, lengths=None, beam=5, nbest=1, blank=0, collapse=False, lm=None, lm_alpha=0.0, lm_beta=0.0,
-                          fast=False):
+                          fast=False, fast_lm=False):
     """The first ``nbest`` entries of the search's final beam (pgasr_ctc_beam_search_nbest): log_probs (T,B,V) fp32 or fp64 as
     ``ctc_beam_search`` takes them, 1 <= nbest <= beam.  Returns ``CTCNBest`` of device tensors, no host synchronisation:
     tokens (N,B,T) int32 (zero behind each hypothesis), lengths (N,B) int32, score (N,B) float64 = -logsumexp(p_blank, p_nonblank)
@@ -1250,7 +1261,10 @@ def ctc_beam_search_nbest(log_probs, lengths=None, beam=5, nbest=1, blank=0, col
     ``ctc_hyp_lattice`` takes.
     fast: the call may take the single-wave kernel of the train step, exactly where ``ctc_beam_search`` takes it by default (no LM,
     fp32, beam <= 16, V <= 64, T * beam <= 24576, T <= 4096); row 0 is then bit for bit ``ctc_beam_search(...)``.  Anywhere else
-    the flag changes nothing."""
+    the flag changes nothing.
+    fast_lm: with ``lm``, the call takes the single-wave kernel's LM instantiations where ``beam_lm_single_wave_ok`` says so (the
+    limits of ``fast`` with a table); row 0 is then bit for bit ``ctc_beam_search(lm=..., fast_lm=True)``.  Without an LM or outside
+    the limits the flag changes nothing; ``fast`` without it keeps a call with an LM on the workgroup kernel."""
     lib = _lib.load()
     if not log_probs.is_cuda or log_probs.dtype not in (torch.float32, torch.float64):
         raise _lib.PgasrError("log_probs must be a float32/float64 GPU tensor")
@@ -1268,7 +1282,7 @@ def ctc_beam_search_nbest(log_probs, lengths=None, beam=5, nbest=1, blank=0, col
     with _timed("beam_search_nbest"):
         st = lib.pgasr_ctc_beam_search_nbest(_p(log_probs), int(log_probs.dtype == torch.float64), log_probs.stride(0),
                                              log_probs.stride(1), _p(lengths), T, B, V, int(beam), int(blank),
-                                             int(bool(collapse)) | (8 if fast else 0), N, _p(tokens), T, _p(tl), _p(score), _p(count), _p(ws), ws.numel(), _stream(),
+                                             int(bool(collapse)) | (8 if fast else 0) | (16 if fast_lm else 0), N, _p(tokens), T, _p(tl), _p(score), _p(count), _p(ws), ws.numel(), _stream(),
                                              _p(lm_table), lm_order, float(lm_alpha), float(lm_beta))
     _lib.check(st, "pgasr_ctc_beam_search_nbest")
     return CTCNBest(tokens, tl, score, count)

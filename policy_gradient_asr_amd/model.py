@@ -211,7 +211,8 @@ def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset
           n_feats=120, lam=1.0, lr=5e-4, resume=True, log_every=10, seed=0, bucket_by_length=True, features="mfcc",
           precision="f32", num_samples=1, reward_baseline="hypothesis", reward_unit="char", max_grad_norm=None,
           accumulate_steps=1, score_function="path", max_hyp_len=None, entropy_weight=0.0, objective="reinforce", mwer_nbest=4,
-          mwer_beam=16, init_from=None, kl_weight=0.0, kl_reference_path=None):
+          mwer_beam=16, init_from=None, kl_weight=0.0, kl_reference_path=None, mwer_lm_path=None, mwer_lm_alpha=0.0,
+          mwer_lm_beta=0.0):
     """Epoch loop of model.py:186-274 on the MI355X path: per-epoch train loss -> train_loss.npy,
     validation CTC loss -> val_losses.npy, model_best.pth / model_last.pth (state_dicts, reference
     names), plus checkpoint_last.pth (model + Adam moments + epoch) from which ``resume`` restarts
@@ -249,7 +250,10 @@ def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset
     objective: "reinforce" (default: the sampled objectives above, today's trainer with today's arguments) or "mwer" -- MWER over the
     ``mwer_nbest`` best hypotheses of the width-``mwer_beam`` beam search (mwer.MWERTrainer: nothing is sampled, so num_samples,
     reward_baseline, score_function and entropy_weight must keep their defaults; reward_unit chooses the char or word risk and
-    max_hyp_len caps the hypotheses in the list's posterior)."""
+    max_hyp_len caps the hypotheses in the list's posterior).
+    mwer_lm_path: None (default) or an ``lm.npz`` of ``build_lm``: with objective="mwer" the N-best lists come from the search fused
+    with that LM at weights mwer_lm_alpha / mwer_lm_beta (the ones ``predict(lm_path=, lm_alpha=, lm_beta=)`` will decode with), on the
+    single-wave kernel; the posterior over the list stays the exact CTC likelihood -- mwer.MWERTrainer."""
     import os
     import numpy as np
     import torch.utils.data as tud
@@ -270,6 +274,8 @@ def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset
         kl_reference_path = init_from
     if kl_weight > 0 and kl_reference_path is None:
         raise ValueError("kl_weight > 0 needs the frozen reference policy's weights: give kl_reference_path or init_from")
+    if mwer_lm_path is not None and objective != "mwer":
+        raise ValueError("mwer_lm_path belongs to objective='mwer' (the sampled objectives decode without an LM)")
     if kl_weight > 0 and objective == "mwer":
         raise ValueError("objective='mwer' does not take kl_weight (the KL penalty belongs to the sampled objectives)")
     print("Num epochs:", num_epochs, "Batch size:", batch_size)
@@ -295,10 +301,14 @@ def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset
     _check_features(features, n_feats, train_dataset)
     if objective == "mwer":
         from .mwer import MWERTrainer
+        mwer_lm = {}
+        if mwer_lm_path is not None:
+            from .lm import CharNgramLM
+            mwer_lm = {"lm": CharNgramLM.load(mwer_lm_path), "lm_alpha": mwer_lm_alpha, "lm_beta": mwer_lm_beta}
         trainer = MWERTrainer(model, lr=lr, lam=lam, seed=seed, precision=precision, max_grad_norm=max_grad_norm,
                               beam_size=mwer_beam, nbest=mwer_nbest, risk_unit=reward_unit, word_delimiter=word_delimiter,
                               max_hyp_len=max_hyp_len, num_samples=num_samples, reward_baseline=reward_baseline,
-                              score_function=score_function, entropy_weight=entropy_weight)
+                              score_function=score_function, entropy_weight=entropy_weight, **mwer_lm)
     else:
         kl = {}
         if kl_weight > 0:
@@ -415,7 +425,7 @@ def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset
 
 def predict(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=None, maxlent=None, device_id=0,
             test_dataset=None, n_feats=120, beam_size=5, features="mfcc", lm_path=None, lm_alpha=0.0, lm_beta=0.0,
-            nbest=1, rescore_lm_path=None, rescore_alpha=0.0, rescore_beta=0.0):
+            nbest=1, rescore_lm_path=None, rescore_alpha=0.0, rescore_beta=0.0, lm_fast=False):
     """model.py:277-339: load model_best.pth, forward, beam=5 prefix search (device side, batched),
     collapse_fn, CER/WER, predicted.txt.  Frames are cut by the FEATURE mask (the reference cuts the
     time axis by the target mask, model.py:322 -- a listed defect).  Returns (CER, WER).
@@ -423,6 +433,9 @@ def predict(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=N
     the features stay on the device.
     lm_path: None (default) or an ``lm.npz`` written by ``build_lm`` / ``CharNgramLM.save``: the beam search then adds
     lm_alpha * ln p_lm(s | context) + lm_beta to every extension by a character s (CTCDecoder).
+    lm_fast: False (default: with an LM every search takes the workgroup-per-utterance kernel) or True: the single-wave kernel with
+    the LM term where its limits allow (beam_size <= 16, at most 64 symbols, T * beam_size <= 24576, T <= 4096; CTCDecoder(fast_lm=)),
+    several times faster; scores agree to ~1e-7 relative, hypotheses wherever no two candidates are closer than that.
     nbest: 1 (default: the calls above, nothing else) or N with 2 <= N <= beam_size: the search returns its N best hypotheses per
     utterance (``decode_batch(nbest=N)``), all of them go to ``nbest.tsv`` in model_path -- utterance, rank, first-pass score, second-pass
     total (empty when not rescored), collapsed text, tab-separated -- and the oracle CER (the best hypothesis of every list) is
@@ -458,7 +471,7 @@ def predict(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=N
     collate_custom = functools.partial(_collate, device=dev, features=features)
     loader = tud.DataLoader(test_dataset, batch_size=batch_size, shuffle=False, collate_fn=collate_custom)
     lm = CharNgramLM.load(lm_path) if lm_path is not None else None
-    decoder = CTCDecoder(alphabet, lm=lm, lm_alpha=lm_alpha, lm_beta=lm_beta)
+    decoder = CTCDecoder(alphabet, lm=lm, lm_alpha=lm_alpha, lm_beta=lm_beta, fast_lm=bool(lm_fast))
     rescore_lm = CharNgramLM.load(rescore_lm_path) if rescore_lm_path is not None else None
     targets, predicted, tot_cer, tot_wer, n = [], [], 0.0, 0.0, 0
     nbest_lines, tot_oracle = [], 0.0

@@ -8,6 +8,7 @@ and ``rescore`` consume.  Semantics of the kernels: include/pgasr_hip.h, section
 This module adds nothing to the code the default train step runs: ``train_step.py`` and ``loss.py`` do not know it.
 """
 import dataclasses
+import math
 
 import torch
 
@@ -30,6 +31,9 @@ class MWEROptions:
     risk_unit: str = "char"
     word_delimiter: object = None
     max_hyp_len: object = None
+    lm: object = None              # a lm.CharNgramLM: the N-best list comes from the LM-fused search (the posterior does not change)
+    lm_alpha: float = 0.0
+    lm_beta: float = 0.0
 
 
 def check_mwer_options(opt, vocab=None, frames=None, symbols=None):
@@ -42,6 +46,13 @@ def check_mwer_options(opt, vocab=None, frames=None, symbols=None):
         raise ValueError(f"nbest {opt.nbest} outside 1 .. beam = {opt.beam}: the list is the head of the search's final beam")
     if opt.nbest > MAX_NBEST:
         raise ValueError(f"nbest {opt.nbest} > {MAX_NBEST}: the MWER kernels take at most {MAX_NBEST} hypotheses per utterance")
+    if opt.lm is not None:
+        if opt.lm.blank != int(opt.blank) or (vocab is not None and opt.lm.vocab != int(vocab)):
+            raise ValueError(f"the LM is over {opt.lm.vocab} symbols with blank {opt.lm.blank}; the search has "
+                             f"{'its own' if vocab is None else int(vocab)} symbols and blank {int(opt.blank)}")
+        for name in ("lm_alpha", "lm_beta"):
+            if not math.isfinite(float(getattr(opt, name))):
+                raise ValueError(f"{name} must be finite (got {getattr(opt, name)!r})")
     _check_unit(opt.risk_unit, opt.word_delimiter, blank=opt.blank, vocab=vocab)
     _check_score("sequence", opt.max_hyp_len)
     if opt.risk_unit == "word" and frames is not None and max(frames, symbols or 0) > hipops.WORD_MAX_STRIDE:
@@ -49,6 +60,11 @@ def check_mwer_options(opt, vocab=None, frames=None, symbols=None):
                          f"(pgasr_word_ids); got T = {frames}")
     return dataclasses.replace(opt, beam=int(opt.beam), nbest=int(opt.nbest),
                                max_hyp_len=None if opt.max_hyp_len is None else int(opt.max_hyp_len))
+
+
+def _lm_fields(lm, lm_alpha, lm_beta):
+    """The options' LM fields; without an LM the weights are not part of them, so the options are the ones of a call without these arguments."""
+    return {} if lm is None else {"lm": lm, "lm_alpha": float(lm_alpha), "lm_beta": float(lm_beta)}
 
 
 class MWERLossFn(torch.autograd.Function):
@@ -61,6 +77,9 @@ class MWERLossFn(torch.autograd.Function):
         r[n,b]     =  ED(y_b, y_n) / max(L_b,1), or WED / W(y_b) with risk_unit = "word"
         d(logits)  =  utt_scale_b (softmax - occ_target) + sum_n coef[n,b] (softmax - occ_{y_n}),
         coef[n,b]  =  -lam / Bg * p[n,b] (r[n,b] - rbar_b)
+    With ``opt.lm`` the list is the final beam of the LM-FUSED search (every extension by s gets lm_alpha * ln p_lm(s | context) + lm_beta,
+    ``ctc_beam_search_nbest(lm=, fast=True, fast_lm=True)``: the single-wave kernel with the LM term): the hypotheses the model is
+    decoded to at test time.  The LM only chooses which hypotheses are in the list; p, r and the gradient are formed as above.
     Stream layout of ``PGCTCLossFn``: the target lattice stays on the calling stream; N-best search, hypothesis lattices, (word) edit
     distance and the weights run on its side stream and are joined before the one gradient pass.
     ``MWERLossFn.last_nbest``: the ``CTCNBest`` of the last call; ``MWERLossFn.last_posterior``: p (N,B) fp32, 0 where not valid;
@@ -86,7 +105,8 @@ class MWERLossFn(torch.autograd.Function):
         PGCTCLossFn._lattice_streams[main.cuda_stream] = side
         side.wait_stream(main)
         with torch.cuda.stream(side):
-            nb = hipops.ctc_beam_search_nbest(lp, in_len, beam=opt.beam, nbest=N, blank=blank, collapse=False, fast=True)
+            fused = {} if opt.lm is None else {"lm": opt.lm, "lm_alpha": float(opt.lm_alpha), "lm_beta": float(opt.lm_beta), "fast_lm": True}
+            nb = hipops.ctc_beam_search_nbest(lp, in_len, beam=opt.beam, nbest=N, blank=blank, collapse=False, fast=True, **fused)
             # a hypothesis over the cap gets the EMPTY hypothesis' lattice (rows beyond count have length 0 already): every lattice
             # the gradient pass reads was really computed, and meets a coefficient of 0
             lat_len = torch.where(nb.lengths > Lh, torch.zeros_like(nb.lengths), nb.lengths)
@@ -132,12 +152,25 @@ def mwer_ctc_loss(logits, in_len, targets, tg_len, lam=1.0, beam=16, nbest=4, gl
     max_hyp_len: hypotheses of more tokens are left out of the list's posterior (None: min(T, 1023)); it bounds the hypothesis-lattice
     workspace, 2 * nbest*B*T * roundup64(2*Lh+1) * 4 bytes.
     log_probs: log_softmax(logits) if the caller already has it (picked up from ``logits.log_probs`` when not given).
-    Returns (loss, nll (B), expected_reward (B) = -rbar, top_reward (B) = -r[0])."""
+    Returns (loss, nll (B), expected_reward (B) = -rbar, top_reward (B) = -r[0]).  The list is the acoustic search's;
+    ``mwer_ctc_loss_lm`` takes it from the search fused with a language model."""
+    return mwer_ctc_loss_lm(logits, in_len, targets, tg_len, None, lam=lam, beam=beam, nbest=nbest, global_batch=global_batch, blank=blank,
+                            risk_unit=risk_unit, word_delimiter=word_delimiter, max_hyp_len=max_hyp_len, log_probs=log_probs)
+
+
+def mwer_ctc_loss_lm(logits, in_len, targets, tg_len, lm=None, lm_alpha=0.0, lm_beta=0.0, lam=1.0, beam=16, nbest=4, global_batch=None,
+                     blank=0, risk_unit="char", word_delimiter=None, max_hyp_len=None, log_probs=None):
+    """``mwer_ctc_loss`` over the N-best list of the LM-FUSED search: ``lm`` a ``lm.CharNgramLM`` over the same V symbols and blank, its
+    weights lm_alpha / lm_beta as ``CTCDecoder`` takes them (``MWERLossFn``; the list comes from the single-wave kernel's LM
+    instantiation where its limits allow).  The posterior over the list stays the exact CTC likelihood.  ``lm=None`` is
+    ``mwer_ctc_loss``: the options and the calls it always made.  (A function of its own because ``mwer_ctc_loss`` keeps its
+    parameter list.)"""
     if logits.dim() != 3:
         raise ValueError("mwer_ctc_loss: logits (T,B,V)")
     T, B, V = logits.shape
     opt = check_mwer_options(MWEROptions(lam=float(lam), beam=beam, nbest=nbest, global_batch=int(global_batch or B), blank=int(blank),
-                                         risk_unit=risk_unit, word_delimiter=word_delimiter, max_hyp_len=max_hyp_len),
+                                         risk_unit=risk_unit, word_delimiter=word_delimiter, max_hyp_len=max_hyp_len,
+                                         **_lm_fields(lm, lm_alpha, lm_beta)),
                              vocab=V, frames=T, symbols=targets.shape[1] if targets.dim() == 2 else 0)
     for name, t_ in (("logits", logits), ("in_len", in_len), ("targets", targets), ("tg_len", tg_len)):
         if not t_.is_cuda:
@@ -154,13 +187,16 @@ class MWERTrainer(PolicyGradientTrainer):
     ``step_accumulated``, clipping, shards and RCCL work as in the parent.  Nothing is sampled, so ``utt_ids`` and the sampler's
     addressing play no part: a shard or micro-batch contributes its own utterances' terms, normalised by the global batch.
     ``last_stats`` = (nll, expected reward -rbar, top-hypothesis reward -r[0]), each (B,); ``last_sample_rewards`` = -r, (nbest, B);
-    ``last_posterior`` (nbest, B), 0 where an entry is not in the list's posterior."""
+    ``last_posterior`` (nbest, B), 0 where an entry is not in the list's posterior.
+    lm / lm_alpha / lm_beta: None (default) or a ``lm.CharNgramLM`` and its weights -- the N-best lists then come from the LM-fused search
+    (the standard MWER setting, arXiv:1712.01818 section 3: train on the lists the model is decoded to); ``mwer_options`` holds the checked options."""
 
     _FIXED = {"num_samples": 1, "reward_baseline": "hypothesis", "score_function": "path", "reward_mode": "utterance",
               "reward_decoder": "greedy", "entropy_weight": 0.0}
 
     def __init__(self, model, lr=5e-4, lam=1.0, seed=0, blank=0, world_size=1, process_group=None, rank=0, precision=None,
-                 max_grad_norm=None, beam_size=16, nbest=4, risk_unit="char", word_delimiter=None, max_hyp_len=None, **sampled):
+                 max_grad_norm=None, beam_size=16, nbest=4, risk_unit="char", word_delimiter=None, max_hyp_len=None, lm=None, lm_alpha=0.0,
+                 lm_beta=0.0, **sampled):
         for k, v in sampled.items():
             if k not in self._FIXED:
                 raise TypeError(f"MWERTrainer got an unexpected keyword argument {k!r}")
@@ -168,12 +204,15 @@ class MWERTrainer(PolicyGradientTrainer):
                 raise ValueError(f"MWERTrainer samples nothing: {k}={v!r} has no meaning here (an entropy bonus for MWER is not built)")
         vocab = getattr(getattr(model, "head", None), "out_features", None)
         opt = check_mwer_options(MWEROptions(blank=int(blank), beam=beam_size, nbest=nbest, risk_unit=risk_unit,
-                                             word_delimiter=word_delimiter, max_hyp_len=max_hyp_len), vocab=vocab)
+                                             word_delimiter=word_delimiter, max_hyp_len=max_hyp_len,
+                                             **_lm_fields(lm, lm_alpha, lm_beta)), vocab=vocab)
         super().__init__(model, lr=lr, lam=lam, seed=seed, blank=blank, world_size=world_size, process_group=process_group, rank=rank,
                          precision=precision, max_grad_norm=max_grad_norm)
         self.beam_size, self.nbest = opt.beam, opt.nbest
         self.risk_unit, self.mwer_max_hyp_len = risk_unit, opt.max_hyp_len
         self.risk_delimiter = None if word_delimiter is None else int(word_delimiter)
+        self.mwer_lm, self.mwer_lm_alpha, self.mwer_lm_beta = opt.lm, opt.lm_alpha, opt.lm_beta
+        self.mwer_options = opt
         self.last_posterior = None
 
     def forward_loss(self, batch, global_batch):
@@ -190,9 +229,10 @@ class MWERTrainer(PolicyGradientTrainer):
             tg_len = tmask.sum(dim=1).to(torch.int32).contiguous()
             tg = targets.to(torch.int32).contiguous()
         logits, in_len = self.model.logits(x, fmask, in_len)
-        loss, nll, expected, top = mwer_ctc_loss(logits, in_len, tg, tg_len, lam=self.lam, beam=self.beam_size, nbest=self.nbest,
-                                                 global_batch=global_batch, blank=self.blank, risk_unit=self.risk_unit,
-                                                 word_delimiter=self.risk_delimiter, max_hyp_len=self.mwer_max_hyp_len)
+        loss, nll, expected, top = mwer_ctc_loss_lm(logits, in_len, tg, tg_len, lam=self.lam, beam=self.beam_size, nbest=self.nbest,
+                                                    global_batch=global_batch, blank=self.blank, risk_unit=self.risk_unit,
+                                                    word_delimiter=self.risk_delimiter, max_hyp_len=self.mwer_max_hyp_len,
+                                                    **_lm_fields(self.mwer_lm, self.mwer_lm_alpha, self.mwer_lm_beta))
         post = MWERLossFn.last_posterior
         R_all = -MWERLossFn.last_risk                            # (N,B): every entry's reward
         self.last_posterior = post[:, :real_b] if padded else post
