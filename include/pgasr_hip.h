@@ -711,7 +711,8 @@ int pgasr_lstm_layer_bwd_streamed(float* gates, const float* out, const float* c
  *   lengths (B) frames per utterance (NULL = T); beam <= 128, V <= 64, beam*V LDS-limited.
  *   out_tokens (B,T) best prefix, out_len (B), out_score (B) = -logsumexp(p_blank, p_nonblank)
  *   of that prefix (CTCdecoder.py:115-116).  Candidate order, prefix merging and the stable
- *   descending sort (ties -> first insertion) follow the reference exactly; scores are fp64.
+ *   descending sort (ties -> first insertion) follow the reference exactly (held on inputs whose exact ties decide the
+ *   output, for every kernel behind A7, A7-LM and A7-NBEST: tests/test_beam_ties_gpu.py); scores are fp64.
  *   flags bit 0: out_tokens / out_len are given AFTER collapse_fn (adjacent duplicate symbols removed,
  *   CTCdecoder.py:119-131) -- the string policy_grad.py:8 and model.py:326 score; bit 1: never take the
  *   single-wave kernel.  fp32 input with beam <= 16, V <= 64 (8 symbols per lane up to 32, 16 beyond) and T * beam <= 24576 (the reward hypothesis inside
