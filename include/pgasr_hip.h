@@ -49,7 +49,8 @@ typedef enum pgasr_status {
  * pgasr_ctc_grad_from_lattice_multi_ent, pgasr_ctc_grad_from_lattices_seq_ent), forced alignment (pgasr_ctc_forced_align),
  * SpecAugment masking (pgasr_spec_augment), the N-best entries (pgasr_ctc_beam_search_nbest, pgasr_nbest_rescore) and MWER training
  * over them (pgasr_mwer_weights, pgasr_ctc_grad_from_lattices_nbest), and the KL penalty towards a frozen reference policy
- * (pgasr_frame_kl, pgasr_ctc_grad_from_lattice_kl, pgasr_ctc_grad_from_lattice_multi_kl, pgasr_ctc_grad_from_lattices_seq_kl). */
+ * (pgasr_frame_kl, pgasr_ctc_grad_from_lattice_kl, pgasr_ctc_grad_from_lattice_multi_kl, pgasr_ctc_grad_from_lattices_seq_kl),
+ * and sample-rate conversion / speed perturbation (pgasr_resample). */
 #define PGASR_ABI_VERSION 7
 
 int pgasr_abi_version(void);
@@ -892,6 +893,37 @@ int pgasr_spec_augment(const float* x, const int32_t* lengths, const int32_t* ut
                        float time_ratio, int fill_mode, unsigned long long seed, unsigned offset,
                        float* out /* may equal x */, int32_t* masks /* NULL or (B, n_freq + n_time, 2): start, width */,
                        void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * A0-RS  Sample-rate conversion and speed perturbation (Ko et al., Interspeech 2015) of a waveform batch on the device: one
+ *   polyphase Hann-windowed sinc filter (the function of torchaudio's default "sinc_interp_hann" resampler, 6 zero crossings,
+ *   rolloff 0.99).  A conversion is a reduced ratio L / M = output rate / input rate; speed factor f = p / q is the ratio q / p.
+ *   Per ratio (all in fp64, h then rounded to fp32):
+ *        fc = 0.99 * min(1, L / M);  half = ceil(6 / fc);  W = 2 * half + 1 taps
+ *        base_j = (j * M) / L (integer),  frac_j = j * M / L - base_j                            for each phase j = 0 .. L-1
+ *        t = fc * ((k - half) - frac_j);  h[j][k] = fc * sinc(t) * cos(pi * t / 12)^2 if |t| < 6, else 0    (sinc(t) = sin(pi t) / (pi t))
+ *   wave (B, in_stride) fp32; n_in (B) int32 on the device, clamped to [0, in_stride]; out (B, out_stride) fp32, not wave.
+ *   Row b takes ratio r = ratio_idx[b] (ratio_idx (B) int32 on the device; NULL: every row takes ratio 0):
+ *        n_out[b] = ceil(n_in[b] * L / M)                                                        (64-bit integers)
+ *        out[b, i * L + j] = fp32( sum_{k = 0 .. W-1} fp64(h[j][k]) * fp64(wave[b, i * M + base_j - half + k]) )
+ *   summed in ascending k in an fp64 accumulator that starts at +0.0; a tap whose sample lies outside [0, n_in[b]) is skipped and
+ *   never read.  A product of two fp32 numbers is exact in fp64, so the result equals a numpy loop over k bit for bit, and two runs
+ *   give the same bits.  out[b, n] = 0.0f for n_out[b] <= n < out_stride.  Ratio 1/1 copies the bits of wave[b, 0:n_in[b]].  A row
+ *   with n_in[b] <= 0, or with ratio_idx[b] outside [0, n_ratios), is zeros and n_out[b] = 0.
+ *   ratio_desc: HOST memory, (n_ratios, 4) int32: L, M, W, and the offset in words of the ratio's h[L][W] in `tables` (device,
+ *   fp32); `bases` (device, int32) holds base_j of ratio 0, then of ratio 1, ..: L_r words each, with no gaps.
+ *   One launch, no workspace, no atomics, no host synchronisation: a workgroup stages the input span of a tile of consecutive
+ *   outputs in LDS (16-byte loads where in_stride % 4 == 0 and wave is 16-byte aligned) and the ratio's table beside it where
+ *   L * W <= 5632 words.  Checked before any device pointer is touched or anything is launched: a NULL pointer (ratio_idx excepted),
+ *   out == wave, B / in_stride / out_stride / n_ratios < 1: PGASR_ERR_INVALID_ARG; n_ratios > 8: PGASR_ERR_UNSUPPORTED; then per
+ *   descriptor L or M < 1 or gcd(L, M) != 1: PGASR_ERR_INVALID_ARG; L or M > 1024, or L / M outside [1/16, 16] (so W <= 195):
+ *   PGASR_ERR_UNSUPPORTED; a W that is not the W of L / M, or a negative offset: PGASR_ERR_INVALID_ARG; last, out_stride below
+ *   the largest ceil(in_stride * L / M) of the ratios: PGASR_ERR_INVALID_ARG.
+ * ---------------------------------------------------------------------------------------- */
+int pgasr_resample(const float* wave, int in_stride, const int32_t* n_in, int B,
+                   const int32_t* ratio_idx /* NULL: all 0 */, int n_ratios, const int32_t* ratio_desc /* host */,
+                   const float* tables, const int32_t* bases, float* out, int out_stride, int32_t* n_out /* written */,
+                   void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Elementwise pieces of the train step.

@@ -26,36 +26,55 @@ def pad_feats(feats):
 _front_end = {}
 
 
-def extract_feats(batch, device="cuda:0", features="mfcc", keep_on_device=False):
+def extract_feats(batch, device="cuda:0", features="mfcc", keep_on_device=False, target_rate=None, speed_perturb=None, seed=0,
+                  offset=0):
     """data.py:44-79: MFCC(40) + delta + delta-delta per utterance, zero padded to (B,120,Tmax) + (B,1,Tmax) masks.
     An item carries precomputed features ("feat", (F,T)), a waveform tensor ("wave"), or a path ("aud", read with
     torchaudio where it exists, else as RIFF WAV).  Waveforms go through the GPU front end: ``features`` = "mfcc"
     (features.MFCCDeltas, the reference's 120 features) or "logmel80" (features.LogMel(80): the benchmark's F = 80).
     keep_on_device: return the tensors where the front end left them (no host round trip on the way to the trainer);
-    default: on the CPU like the reference's collate output."""
+    default: on the CPU like the reference's collate output.
+    target_rate: None (default: every waveform is taken to be at the front end's 16 kHz, whatever its file says -- the reference's
+    behaviour) or the front end's rate, 16000: a waveform at another rate -- the file's, or the item's "rate" beside "wave" -- is
+    converted on the device first (features.Resample); an item without a rate is taken to be at the target.
+    speed_perturb: None or a features.SpeedPerturb: every waveform is resampled by the factor drawn for (seed, offset, the item's
+    "idx": its index in the corpus, which ``Indexed`` adds); with a rate conversion it is one pass over the samples."""
     if all("feat" in inst for inst in batch):
+        if speed_perturb is not None:
+            raise ValueError("speed perturbation resamples waveforms: these items carry precomputed features")
         feat, fmask = pad_feats([inst["feat"] for inst in batch])
         return (feat.to(device), fmask.to(device)) if keep_on_device else (feat, fmask)
     if any("feat" in inst for inst in batch):
         raise ValueError("a batch mixes precomputed features and waveforms")
     from .features import LogMel, MFCCDeltas, read_wav
-    waves = []
+    waves, rates = [], []
     for inst in batch:
         if "wave" in inst:
             waves.append(inst["wave"])
+            rates.append(inst.get("rate"))
             continue
         try:
             import torchaudio
-            waveform, _sr = torchaudio.load(inst["aud"])          # data.py:53
+            waveform, sr = torchaudio.load(inst["aud"])           # data.py:53
             waves.append(waveform[0])
         except ImportError:
-            waves.append(read_wav(inst["aud"])[0])
+            wave, sr = read_wav(inst["aud"])
+            waves.append(wave)
+        rates.append(int(sr))
     if features not in ("mfcc", "logmel80"):
         raise ValueError('features must be "mfcc" or "logmel80"')
     fe = _front_end.get((str(device), features))
     if fe is None:
         fe = _front_end[(str(device), features)] = MFCCDeltas(device) if features == "mfcc" else LogMel(80, device)
-    feat, fmask = fe(waves)
+    if target_rate is None and speed_perturb is None:
+        feat, fmask = fe(waves)
+    else:
+        speed = None
+        if speed_perturb is not None:
+            if any("idx" not in inst for inst in batch):
+                raise ValueError('speed perturbation draws by utterance id: every item needs an "idx" (wrap the dataset in data.Indexed)')
+            speed = speed_perturb.ratios([int(inst["idx"]) for inst in batch], seed, offset)
+        feat, fmask = fe(waves, rates=rates, target_rate=target_rate, speed=speed)
     return (feat, fmask) if keep_on_device else (feat.cpu(), fmask.cpu())
 
 
@@ -68,17 +87,34 @@ def encode_trans(batch):
     return out, (out > 0).to(torch.int64)
 
 
-def collate_custom(batch, device=None, features="mfcc"):
+def collate_custom(batch, device=None, features="mfcc", target_rate=None, speed_perturb=None, seed=0, offset=0):
     """data.py:107-116.  device = None: the reference's contract -- everything on the CPU.  device = a GPU: "feat" / "fmask" stay
     where the front end computed them and "trans" / "tmask" are put beside them, so ``PolicyGradientTrainer.step`` consumes the
-    batch without the features ever visiting the host (use ``functools.partial(collate_custom, device=...)`` as collate_fn)."""
+    batch without the features ever visiting the host (use ``functools.partial(collate_custom, device=...)`` as collate_fn).
+    target_rate / speed_perturb / seed / offset: sample-rate conversion and speed perturbation of waveform items (``extract_feats``)."""
+    aug = {"target_rate": target_rate, "speed_perturb": speed_perturb, "seed": seed, "offset": offset}
     if device is None:
-        feats, fmasks = extract_feats(batch, features=features)
+        feats, fmasks = extract_feats(batch, features=features, **aug)
         trans, tmasks = encode_trans(batch)
     else:
-        feats, fmasks = extract_feats(batch, device=device, features=features, keep_on_device=True)
+        feats, fmasks = extract_feats(batch, device=device, features=features, keep_on_device=True, **aug)
         trans, tmasks = (t.to(device) for t in encode_trans(batch))
     return {"feat": feats, "fmask": fmasks, "trans": trans, "tmask": tmasks}
+
+
+class Indexed(data.Dataset):
+    """A dataset whose items also carry "idx", their index in it: the utterance id speed perturbation draws by."""
+
+    def __init__(self, dataset):
+        self.dataset = dataset
+
+    def __len__(self):
+        return len(self.dataset)
+
+    def __getitem__(self, idx):
+        if torch.is_tensor(idx):
+            idx = idx.tolist()
+        return dict(self.dataset[idx], idx=int(idx))
 
 
 class Data(data.Dataset):

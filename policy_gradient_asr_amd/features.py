@@ -48,18 +48,30 @@ class _FrontEnd:
             raise _lib.PgasrError("the feature front end runs on the MI355X only; there is no CPU path")
         self.n_mels = int(n_mels)
         self.dft, self.fb, self.dct = _constants(self.device, self.n_mels)
+        self._resample = None
 
-    def mel_db(self, waves):
+    def mel_db(self, waves, rates=None, target_rate=None, speed=None):
+        """rates / target_rate: the items' sample rates and the rate the front end works at (16000) -- an item at another rate is
+        converted on the device first (Resample); speed: one resampling ratio (L, M) per item (SpeedPerturb.ratios), or None.  Both
+        on one item compose into one ratio and one pass.  All three None: no resampling code runs."""
         lib = _lib.load()
         dev = self.device
         B = len(waves)
-        ns = [int(w.numel()) for w in waves]
-        if min(ns) <= N_FFT // 2:
-            raise ValueError("reflect-centred framing needs more than n_fft/2 = 200 samples per utterance")
-        nmax = (max(ns) + 3) // 4 * 4
-        wave = torch.zeros(B, nmax, dtype=torch.float32, device=dev)
-        for i, w in enumerate(waves):
-            wave[i, :ns[i]] = w.reshape(-1).to(device=dev, dtype=torch.float32)
+        if (rates is None or target_rate is None) and speed is None:
+            ns = [int(w.numel()) for w in waves]
+            if min(ns) <= N_FFT // 2:
+                raise ValueError("reflect-centred framing needs more than n_fft/2 = 200 samples per utterance")
+            nmax = (max(ns) + 3) // 4 * 4
+            wave = torch.zeros(B, nmax, dtype=torch.float32, device=dev)
+            for i, w in enumerate(waves):
+                wave[i, :ns[i]] = w.reshape(-1).to(device=dev, dtype=torch.float32)
+        else:
+            if self._resample is None:
+                self._resample = Resample(dev)
+            wave, ns = self._resample.apply(waves, item_ratios(B, rates, target_rate, speed))
+            if min(ns) <= N_FFT // 2:
+                raise ValueError("reflect-centred framing needs more than n_fft/2 = 200 samples per utterance (after resampling)")
+            nmax = wave.stride(0)          # the row stride: the resampler's buffer may be wider than the longest result
         n_samples = torch.tensor(ns, dtype=torch.int32, device=dev)
         nf = [1 + n // HOP for n in ns]
         n_frames = torch.tensor(nf, dtype=torch.int32, device=dev)
@@ -80,15 +92,16 @@ class _FrontEnd:
 
 
 class MFCCDeltas(_FrontEnd):
-    """waves: list of 1-D float tensors (any device; moved to ``device``) -> (feat (B,120,Tmax), fmask (B,1,Tmax))."""
+    """waves: list of 1-D float tensors (any device; moved to ``device``) -> (feat (B,120,Tmax), fmask (B,1,Tmax)).
+    rates / target_rate / speed: optional resampling in front of the framing (``_FrontEnd.mel_db``)."""
 
     def __init__(self, device="cuda:0"):
         super().__init__(device, N_MELS)
 
-    def __call__(self, waves):
+    def __call__(self, waves, rates=None, target_rate=None, speed=None):
         lib = _lib.load()
         dev = self.device
-        mel, n_frames, B, Tmax = self.mel_db(waves)
+        mel, n_frames, B, Tmax = self.mel_db(waves, rates, target_rate, speed)
         rows = B * Tmax
         st = torch.cuda.current_stream().cuda_stream
         mfcc = torch.empty(rows, N_MFCC, dtype=torch.float32, device=dev)
@@ -108,9 +121,9 @@ class LogMel(_FrontEnd):
     def __init__(self, n_mels=80, device="cuda:0"):
         super().__init__(device, n_mels)
 
-    def __call__(self, waves):
+    def __call__(self, waves, rates=None, target_rate=None, speed=None):
         lib = _lib.load()
-        mel, n_frames, B, Tmax = self.mel_db(waves)
+        mel, n_frames, B, Tmax = self.mel_db(waves, rates, target_rate, speed)
         feat = torch.empty(B, self.n_mels, Tmax, dtype=torch.float32, device=self.device)
         fmask = torch.empty(B, 1, Tmax, dtype=torch.float32, device=self.device)
         _lib.check(lib.pgasr_feat_stack(mel.data_ptr(), n_frames.data_ptr(), B, Tmax, self.n_mels, feat.data_ptr(), fmask.data_ptr(),
@@ -207,6 +220,233 @@ class SpecAugment:
                 utt_ids = torch.tensor(list(utt_ids), dtype=torch.int32)
             utt_ids = utt_ids.to(device=dev, dtype=torch.int32).contiguous()
         return hipops.spec_augment(feat, lengths, self, seed, offset, utt_ids=utt_ids)
+
+
+RESAMPLE_ZEROS, RESAMPLE_ROLLOFF = 6, 0.99              # torchaudio's default sinc_interp_hann resampler
+RESAMPLE_MAX_LM, RESAMPLE_MAX_FACTOR, RESAMPLE_MAX_RATIOS = hipops.RESAMPLE_MAX_LM, hipops.RESAMPLE_MAX_FACTOR, hipops.RESAMPLE_MAX_RATIOS
+
+
+def reduce_ratio(L, M):
+    """(L, M) -> the reduced ratio as python ints; ValueError unless it lies within the kernel's limits (include/pgasr_hip.h, A0-RS)."""
+    L, M = int(L), int(M)
+    if L < 1 or M < 1:
+        raise ValueError(f"a resampling ratio needs L, M >= 1 (got {L}/{M})")
+    g = math.gcd(L, M)
+    L, M = L // g, M // g
+    if L > RESAMPLE_MAX_LM or M > RESAMPLE_MAX_LM or L > RESAMPLE_MAX_FACTOR * M or M > RESAMPLE_MAX_FACTOR * L:
+        raise ValueError(f"resampling ratio {L}/{M} is beyond the limits: L, M <= {RESAMPLE_MAX_LM} after reduction and "
+                         f"1/{RESAMPLE_MAX_FACTOR} <= L/M <= {RESAMPLE_MAX_FACTOR}")
+    return L, M
+
+
+_filters = {}
+
+
+def resample_filter(L, M):
+    """The polyphase Hann-windowed sinc filter of the reduced ratio L / M (A0-RS): (h (L, W) fp32, base (L,) int32, half), computed
+    in fp64 and rounded to fp32 once; cached per (L, M), the arrays are read-only."""
+    import numpy as np
+    L, M = int(L), int(M)
+    hit = _filters.get((L, M))
+    if hit is not None:
+        return hit
+    if reduce_ratio(L, M) != (L, M):
+        raise ValueError(f"resample_filter wants a reduced ratio (got {L}/{M})")
+    fc = RESAMPLE_ROLLOFF * (L / M if L < M else 1.0)
+    half = int(math.ceil(RESAMPLE_ZEROS / fc))
+    W = 2 * half + 1
+    j = np.arange(L, dtype=np.int64)
+    base = (j * M) // L
+    frac = (j * M).astype(np.float64) / np.float64(L) - base.astype(np.float64)
+    d = (np.arange(W, dtype=np.float64)[None, :] - half) - frac[:, None]
+    t = fc * d
+    pt = np.pi * t
+    sinc = np.where(t == 0.0, 1.0, np.sin(pt) / np.where(t == 0.0, 1.0, pt))
+    h = np.where(np.abs(t) < RESAMPLE_ZEROS, fc * sinc * np.cos(pt / (2.0 * RESAMPLE_ZEROS)) ** 2, 0.0).astype(np.float32)
+    base = base.astype(np.int32)
+    h.setflags(write=False); base.setflags(write=False)
+    _filters[(L, M)] = (h, base, half)
+    return _filters[(L, M)]
+
+
+def resample_length(n, L, M):
+    """Samples a ratio L / M makes of n: ceil(n * L / M), in python integers (no overflow)."""
+    n, L, M = int(n), int(L), int(M)
+    return (max(n, 0) * L + M - 1) // M
+
+
+class Resample:
+    """Sample-rate conversion on the device (hipops.resample, one polyphase windowed-sinc kernel):
+    ``Resample(device)(waves, rates, target_rate=16000)`` -> (wave (B, nmax) fp32 on the device, zero beyond each length; lengths, a
+    list of python ints).  waves: 1-D float tensors (any device); rates: one sample rate per item (None: the item is at the target).
+    An item already at the target is copied, not filtered.  ``apply(waves, ratios)`` takes one reduced (L, M) per item instead.
+    A batch with more than 8 distinct ratios is split into several launches.  Lengths are computed on the host: no synchronisation."""
+
+    def __init__(self, device="cuda:0"):
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise _lib.PgasrError("resampling runs on the MI355X only; there is no CPU path")
+
+    def __call__(self, waves, rates, target_rate=SAMPLE_RATE):
+        return self.apply(waves, item_ratios(len(waves), rates, target_rate, None))
+
+    def apply(self, waves, ratios):
+        dev = self.device
+        B = len(waves)
+        if len(ratios) != B:
+            raise ValueError(f"{B} waveforms but {len(ratios)} ratios")
+        ratios = [reduce_ratio(*r) for r in ratios]
+        distinct = sorted(set(ratios))
+        # a launch takes 8 ratios and contiguous rows: with more distinct ones the batch is laid out group by group (a stable sort:
+        # one group leaves the rows where they are)
+        groups = [distinct[k:k + RESAMPLE_MAX_RATIOS] for k in range(0, len(distinct), RESAMPLE_MAX_RATIOS)]
+        group_of = {r: g for g, rs in enumerate(groups) for r in rs}
+        order = sorted(range(B), key=lambda i: group_of[ratios[i]])
+        ns = [int(w.numel()) for w in waves]
+        lengths = [resample_length(n, *r) for n, r in zip(ns, ratios)]
+        in_stride = max((max(ns) + 3) // 4 * 4, 4)
+        nmax = max((max(lengths) + 3) // 4 * 4, 4)
+        wave = torch.zeros(B, in_stride, dtype=torch.float32, device=dev)
+        for row, i in enumerate(order):
+            wave[row, :ns[i]] = waves[i].reshape(-1).to(device=dev, dtype=torch.float32)
+        if distinct == [(1, 1)]:
+            return wave, lengths
+        # the kernel wants room for what the longest row would give at the batch's largest ratio; the result is the view of the
+        # first nmax columns
+        out_stride = (max(resample_length(in_stride, *r) for r in distinct) + 3) // 4 * 4
+        n_in = torch.tensor([ns[i] for i in order], dtype=torch.int32, device=dev)
+        out = torch.empty(B, out_stride, dtype=torch.float32, device=dev)
+        n_out = torch.empty(B, dtype=torch.int32, device=dev)
+        s = 0
+        for g, rs in enumerate(groups):
+            e = s + sum(1 for i in order if group_of[ratios[i]] == g)
+            idx = torch.tensor([rs.index(ratios[i]) for i in order[s:e]], dtype=torch.int32, device=dev)
+            hipops.resample(wave[s:e], n_in[s:e], rs, ratio_idx=idx, out=out[s:e], n_out=n_out[s:e])
+            s = e
+        if order != list(range(B)):
+            inv = [0] * B
+            for row, i in enumerate(order):
+                inv[i] = row
+            out = out[torch.tensor(inv, device=dev)]
+        return out[:, :nmax], lengths
+
+
+def item_ratios(B, rates, target_rate, speed):
+    """One reduced (L, M) per item: the rate conversion target_rate / rate (rate None, or target_rate None: none) composed with the
+    item's speed ratio ``speed[i]`` = (L, M) (None: none) into ONE ratio, so one pass does both."""
+    out = []
+    for i in range(B):
+        L, M = 1, 1
+        rate = rates[i] if (rates is not None and target_rate is not None) else None
+        if rate is not None:
+            if int(rate) != rate or int(target_rate) != target_rate or rate < 1 or target_rate < 1:
+                raise ValueError(f"sample rates must be positive integers (got {rate!r} -> {target_rate!r})")
+            L, M = int(target_rate), int(rate)
+        if speed is not None and speed[i] is not None:
+            L, M = L * int(speed[i][0]), M * int(speed[i][1])
+        out.append(reduce_ratio(L, M))
+    return out
+
+
+def _philox4x32_10(c, k):
+    """One Philox4x32-10 block (Salmon et al. 2011) in python integers: counter (c0..c3), key (k0, k1) -> four 32-bit words; the
+    constants of csrc/common.h."""
+    c0, c1, c2, c3 = (int(v) & 0xFFFFFFFF for v in c)
+    k0, k1 = (int(v) & 0xFFFFFFFF for v in k)
+    for _ in range(10):
+        p0, p1 = 0xD2511F53 * c0, 0xCD9E8D57 * c2
+        c0, c1, c2, c3 = (p1 >> 32) ^ c1 ^ k0, p1 & 0xFFFFFFFF, (p0 >> 32) ^ c3 ^ k1, p0 & 0xFFFFFFFF
+        k0, k1 = (k0 + 0x9E3779B9) & 0xFFFFFFFF, (k1 + 0xBB67AE85) & 0xFFFFFFFF
+    return c0, c1, c2, c3
+
+
+class SpeedPerturb:
+    """The speed-perturbation policy (Ko et al., Interspeech 2015): every utterance is resampled by one of ``factors`` (default 0.9,
+    1.0, 1.1), drawn uniformly, and the result is still called 16 kHz -- a factor f = p / q makes an utterance f times faster and 1 / f
+    times as long: the resampling ratio L / M = q / p.  Factors are given as floats (or Fractions, or (p, q) pairs) and stored as
+    reduced fractions; one that is no ratio within the kernel's limits (p, q <= 1024, 1/16 <= f <= 16) is refused.
+    The draw for the utterance with global index u is a function of (seed, offset, u) only:
+        idx = ((w0 >> 8) * len(factors)) >> 24,   w0 = word 0 of philox4x32_10(ctr = (u, offset, 4, 0), key = (seed lo32, seed hi32))
+    (counter word 2: the samplers hold 0 and 1, SpecAugment 2 and 3, so one seed serves all three) -- a rank, a shard or a micro-batch
+    perturbs what one process holding the whole batch perturbs.  It is drawn on the host, which needs the output lengths to size the
+    batch anyway.  Immutable; ``state()`` / ``from_state()`` for checkpoints.  ``ratios(utt_ids, seed, offset)`` -> one (L, M) per id."""
+    DOMAIN = 4
+    __slots__ = ("factors",)
+
+    def __init__(self, factors=(0.9, 1.0, 1.1)):
+        import fractions
+        import numbers
+        if isinstance(factors, (str, bytes, numbers.Number)):
+            raise TypeError(f"SpeedPerturb: factors must be a sequence of speed factors (got {factors!r})")
+        fr = []
+        for f in factors:
+            if isinstance(f, (tuple, list)) and len(f) == 2:
+                q = fractions.Fraction(int(f[0]), int(f[1])) if int(f[0]) > 0 and int(f[1]) > 0 else None
+            elif isinstance(f, bool) or not isinstance(f, (numbers.Real, fractions.Fraction)):
+                raise TypeError(f"SpeedPerturb: a factor must be a real number or a (p, q) pair (got {f!r})")
+            elif not (f > 0 and f < float("inf")):
+                q = None
+            else:
+                q = fractions.Fraction(f).limit_denominator(RESAMPLE_MAX_LM)
+                if abs(float(q) - float(f)) > 1e-9 * float(f):
+                    q = None
+            if q is None or q.numerator > RESAMPLE_MAX_LM or q.denominator > RESAMPLE_MAX_LM or \
+                    q > RESAMPLE_MAX_FACTOR or q * RESAMPLE_MAX_FACTOR < 1:
+                raise ValueError(f"SpeedPerturb: factor {f!r} is no ratio p/q within the limits p, q <= {RESAMPLE_MAX_LM}, "
+                                 f"1/{RESAMPLE_MAX_FACTOR} <= p/q <= {RESAMPLE_MAX_FACTOR}")
+            fr.append((q.numerator, q.denominator))
+        if not fr:
+            raise ValueError("SpeedPerturb: factors must not be empty")
+        object.__setattr__(self, "factors", tuple(fr))
+
+    def __setattr__(self, k, v):
+        raise AttributeError("SpeedPerturb is immutable")
+
+    __delattr__ = __setattr__
+
+    def state(self):
+        return {"factors": [list(f) for f in self.factors]}
+
+    @classmethod
+    def from_state(cls, state):
+        unknown = sorted(set(state) - {"factors"})
+        if unknown:
+            raise ValueError(f"SpeedPerturb: unknown fields {unknown}")
+        return cls(**state)
+
+    @classmethod
+    def coerce(cls, value, what="speed_perturb"):
+        """None, a SpeedPerturb, a dict of its state or a sequence of factors -> None or a SpeedPerturb; anything else: TypeError."""
+        if value is None or isinstance(value, cls):
+            return value
+        if isinstance(value, dict):
+            return cls.from_state(value)
+        if isinstance(value, (tuple, list)):
+            return cls(value)
+        raise TypeError(f"{what} must be None, a features.SpeedPerturb, a dict of its state or a sequence of factors (got {value!r})")
+
+    def __eq__(self, other):
+        return isinstance(other, SpeedPerturb) and self.factors == other.factors
+
+    def __hash__(self):
+        return hash(self.factors)
+
+    def __repr__(self):
+        return "SpeedPerturb(factors=({}))".format(", ".join(f"{p}/{q}" for p, q in self.factors))
+
+    def draw(self, utt_id, seed, offset):
+        """The index into ``factors`` of utterance ``utt_id``."""
+        seed = int(seed) & (2 ** 64 - 1)
+        w0 = _philox4x32_10((int(utt_id), int(offset), self.DOMAIN, 0), (seed & 0xFFFFFFFF, seed >> 32))[0]
+        return ((w0 >> 8) * len(self.factors)) >> 24
+
+    def ratios(self, utt_ids, seed, offset):
+        """One resampling ratio (L, M) = (q, p) per utterance id."""
+        out = []
+        for u in utt_ids:
+            p, q = self.factors[self.draw(u, seed, offset)]
+            out.append((q, p))
+        return out
 
 
 def read_wav(path):

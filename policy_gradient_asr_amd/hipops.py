@@ -560,6 +560,66 @@ def spec_augment(x, lengths, policy, seed, offset, utt_ids=None, batch_offset=0,
     return (out, masks) if want_masks else out
 
 
+RESAMPLE_MAX_LM, RESAMPLE_MAX_FACTOR, RESAMPLE_MAX_RATIOS = 1024, 16, 8      # csrc/resample.hip
+
+_resample_tables = {}
+
+
+def _resample_tables_for(ratios, device):
+    """(descriptors (n,4) int32 numpy, tables fp32, bases int32 on the device) of a tuple of reduced ratios; built once per device."""
+    import numpy as np
+    from .features import resample_filter
+    key = (str(device), ratios)
+    hit = _resample_tables.get(key)
+    if hit is None:
+        desc, hs, bs, off = [], [], [], 0
+        for L, M in ratios:
+            h, base, _ = resample_filter(L, M)
+            desc.append((L, M, h.shape[1], off))
+            pad = -h.size % 4                                  # every table starts on a 16-byte boundary
+            hs += [h.reshape(-1), np.zeros(pad, dtype=np.float32)]
+            bs.append(base)
+            off += h.size + pad
+        hit = _resample_tables[key] = (np.ascontiguousarray(np.array(desc, dtype=np.int32)),
+                                       torch.from_numpy(np.concatenate(hs)).to(device),
+                                       torch.from_numpy(np.concatenate(bs)).to(device))
+    return hit
+
+
+def resample(wave, n_in, ratios, ratio_idx=None, out=None, n_out=None):
+    """Sample-rate conversion of wave (B, in_stride) fp32 (include/pgasr_hip.h, A0-RS): row b, n_in[b] samples long (n_in (B) int32 on
+    the device), is resampled by ratios[ratio_idx[b]] = (L, M), output rate / input rate, reduced (ratio_idx (B) int32 on the device;
+    None: every row takes ratios[0]; at most 8 ratios).  Returns (out (B, out_stride) fp32, zero beyond each row's length, n_out (B)
+    int32 = ceil(n_in * L / M)); ``out``: a contiguous fp32 (B, out_stride) tensor with out_stride >= the length the largest ratio
+    gives in_stride samples (default: just that, rounded up to 4).  One launch, no host synchronisation."""
+    lib = _lib.load()
+    _req(wave, torch.float32, "wave"); _req(n_in, torch.int32, "n_in"); _req(ratio_idx, torch.int32, "ratio_idx")
+    _req(out, torch.float32, "out"); _req(n_out, torch.int32, "n_out")
+    if wave.dim() != 2 or n_in.dim() != 1 or n_in.numel() != wave.shape[0] or n_in.device != wave.device:
+        raise _lib.PgasrError("resample wants wave (B, in_stride) and n_in (B) on one device")
+    B, in_stride = wave.shape
+    ratios = tuple((int(L), int(M)) for L, M in ratios)
+    if not 1 <= len(ratios) <= RESAMPLE_MAX_RATIOS:
+        raise _lib.PgasrError(f"resample takes 1 .. {RESAMPLE_MAX_RATIOS} ratios per call (got {len(ratios)})")
+    if ratio_idx is not None and (ratio_idx.dim() != 1 or ratio_idx.numel() != B or ratio_idx.device != wave.device):
+        raise _lib.PgasrError(f"resample: ratio_idx must be ({B},) int32 on {wave.device}")
+    desc, tables, bases = _resample_tables_for(ratios, wave.device)
+    if out is None:
+        need = max((in_stride * L + M - 1) // M for L, M in ratios)
+        out = torch.empty(B, (need + 3) // 4 * 4, dtype=torch.float32, device=wave.device)
+    elif out.dim() != 2 or out.shape[0] != B or out.device != wave.device:
+        raise _lib.PgasrError(f"resample: out must be ({B}, out_stride) fp32 on {wave.device}")
+    if n_out is None:
+        n_out = torch.empty(B, dtype=torch.int32, device=wave.device)
+    elif n_out.dim() != 1 or n_out.numel() != B or n_out.device != wave.device:
+        raise _lib.PgasrError(f"resample: n_out must be ({B},) int32 on {wave.device}")
+    with _timed("resample"):
+        st = lib.pgasr_resample(_p(wave), in_stride, _p(n_in), B, _p(ratio_idx), len(ratios), desc.ctypes.data, _p(tables), _p(bases),
+                                _p(out), out.shape[1], _p(n_out), _stream())
+    _lib.check(st, "pgasr_resample")
+    return out, n_out
+
+
 def ctc_collapse(paths, lengths, blank=0, out=None):
     """paths (P,T,B) int32 -> tokens (P,B,T) int32, token_lengths (P,B) int32.
     out = (tokens, token_lengths) to write into (contiguous, zero-filled tokens)."""

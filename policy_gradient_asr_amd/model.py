@@ -212,7 +212,7 @@ def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset
           precision="f32", num_samples=1, reward_baseline="hypothesis", reward_unit="char", max_grad_norm=None,
           accumulate_steps=1, score_function="path", max_hyp_len=None, entropy_weight=0.0, objective="reinforce", mwer_nbest=4,
           mwer_beam=16, init_from=None, kl_weight=0.0, kl_reference_path=None, mwer_lm_path=None, mwer_lm_alpha=0.0,
-          mwer_lm_beta=0.0):
+          mwer_lm_beta=0.0, target_rate=None, speed_perturb=None):
     """Epoch loop of model.py:186-274 on the MI355X path: per-epoch train loss -> train_loss.npy,
     validation CTC loss -> val_losses.npy, model_best.pth / model_last.pth (state_dicts, reference
     names), plus checkpoint_last.pth (model + Adam moments + epoch) from which ``resume`` restarts
@@ -253,7 +253,14 @@ def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset
     max_hyp_len caps the hypotheses in the list's posterior).
     mwer_lm_path: None (default) or an ``lm.npz`` of ``build_lm``: with objective="mwer" the N-best lists come from the search fused
     with that LM at weights mwer_lm_alpha / mwer_lm_beta (the ones ``predict(lm_path=, lm_alpha=, lm_beta=)`` will decode with), on the
-    single-wave kernel; the posterior over the list stays the exact CTC likelihood -- mwer.MWERTrainer."""
+    single-wave kernel; the posterior over the list stays the exact CTC likelihood -- mwer.MWERTrainer.
+    target_rate: None (default: every waveform is taken to be at 16 kHz whatever its file says, as in the reference) or 16000: audio
+    at another rate (Common Voice clips are 48 or 32 kHz) is converted on the device in front of the framing (features.Resample);
+    validation batches too.
+    speed_perturb: None (default) or a features.SpeedPerturb (or its factors, e.g. (0.9, 1.0, 1.1)): every training waveform is
+    resampled by a factor drawn per (seed, epoch, utterance index) -- the dataset is then wrapped in data.Indexed, and the draws
+    change every epoch.  The length bucketing keeps using the UNPERTURBED lengths: a batch's utterances differ by at most the
+    extreme factors' ratio more than they would.  Validation is not perturbed."""
     import os
     import numpy as np
     import torch.utils.data as tud
@@ -288,7 +295,9 @@ def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset
         word_delimiter = char2ind[" "]
     dev = torch.device("cuda", device if isinstance(device, int) else 0) if not isinstance(device, torch.device) else device
     os.makedirs(model_path, exist_ok=True)
-    collate_custom = functools.partial(_collate, device=dev, features=features)
+    from .features import SpeedPerturb
+    speed_perturb = SpeedPerturb.coerce(speed_perturb)
+    collate_custom = functools.partial(_collate, device=dev, features=features, target_rate=target_rate)
     if train_dataset is None:
         train_dataset = Data(os.path.join(corpus_path, "train.tsv"), os.path.join(corpus_path, "clips"), char2ind)
     if dev_dataset is None and os.path.exists(os.path.join(corpus_path, "dev.tsv")):
@@ -341,7 +350,8 @@ def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset
                         ("reward_unit", reward_unit), ("max_grad_norm", max_grad_norm),
                         ("accumulate_steps", accumulate_steps), ("score_function", score_function),
                         ("max_hyp_len", max_hyp_len), ("entropy_weight", entropy_weight), ("kl_weight", kl_weight),
-                        ("kl_reference_path", kl_reference_path)):
+                        ("kl_reference_path", kl_reference_path), ("target_rate", target_rate),
+                        ("speed_perturb", None if speed_perturb is None else speed_perturb.state())):
             if k in st and st[k] != want:
                 print("Warning: resuming with {}={} but the checkpoint was written with {}".format(k, want, st[k]))
         losses, val_losses, best, start_epoch = st["losses"], st["val_losses"], st["best"], st["epoch"] + 1
@@ -351,12 +361,18 @@ def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset
     for epoch in range(start_epoch, num_epochs + 1):
         model.train()
         lens = dataset_lengths(train_dataset) if bucket_by_length else None
+        epoch_dataset, train_collate = train_dataset, collate_custom
+        if speed_perturb is not None:      # the draws are addressed by (seed, epoch, index in the corpus)
+            from .data import Indexed
+            epoch_dataset = Indexed(train_dataset)
+            train_collate = functools.partial(_collate, device=dev, features=features, target_rate=target_rate,
+                                              speed_perturb=speed_perturb, seed=seed, offset=epoch)
         if lens is not None:      # similar lengths per batch instead of model.py:221's shuffle=True
             sampler = LengthBucketSampler(lens, batch_size, seed=seed)
             sampler.set_epoch(epoch)
-            loader = tud.DataLoader(train_dataset, batch_sampler=sampler, collate_fn=collate_custom)
+            loader = tud.DataLoader(epoch_dataset, batch_sampler=sampler, collate_fn=train_collate)
         else:
-            loader = tud.DataLoader(train_dataset, batch_size=batch_size, shuffle=True, collate_fn=collate_custom)
+            loader = tud.DataLoader(epoch_dataset, batch_size=batch_size, shuffle=True, collate_fn=train_collate)
         acc = torch.zeros((), device=dev)
         n_steps = -(-len(loader) // accumulate_steps)          # optimizer steps of this epoch
         step, group = 0, []
@@ -419,18 +435,20 @@ def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset
                     "lr": lr, "lam": lam, "num_samples": num_samples, "reward_baseline": reward_baseline,
                     "reward_unit": reward_unit, "max_grad_norm": max_grad_norm, "accumulate_steps": accumulate_steps,
                     "score_function": score_function, "max_hyp_len": max_hyp_len, "entropy_weight": trainer.entropy_weight,
-                    "kl_weight": kl_weight, "kl_reference_path": kl_reference_path}, ckpt)
+                    "kl_weight": kl_weight, "kl_reference_path": kl_reference_path, "target_rate": target_rate,
+                    "speed_perturb": None if speed_perturb is None else speed_perturb.state()}, ckpt)
     return losses, val_losses
 
 
 def predict(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=None, maxlent=None, device_id=0,
             test_dataset=None, n_feats=120, beam_size=5, features="mfcc", lm_path=None, lm_alpha=0.0, lm_beta=0.0,
-            nbest=1, rescore_lm_path=None, rescore_alpha=0.0, rescore_beta=0.0, lm_fast=False):
+            nbest=1, rescore_lm_path=None, rescore_alpha=0.0, rescore_beta=0.0, lm_fast=False, target_rate=None):
     """model.py:277-339: load model_best.pth, forward, beam=5 prefix search (device side, batched),
     collapse_fn, CER/WER, predicted.txt.  Frames are cut by the FEATURE mask (the reference cuts the
     time axis by the target mask, model.py:322 -- a listed defect).  Returns (CER, WER).
     features: the front end for items that carry waveforms, as in ``train`` ("mfcc": n_feats=120, "logmel80": n_feats=80);
-    the features stay on the device.
+    the features stay on the device.  target_rate: None (default) or 16000 -- audio at another rate is converted on the device
+    first, as in ``train``.
     lm_path: None (default) or an ``lm.npz`` written by ``build_lm`` / ``CharNgramLM.save``: the beam search then adds
     lm_alpha * ln p_lm(s | context) + lm_beta to every extension by a character s (CTCDecoder).
     lm_fast: False (default: with an LM every search takes the workgroup-per-utterance kernel) or True: the single-wave kernel with
@@ -468,7 +486,7 @@ def predict(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=N
     if test_dataset is None:
         test_dataset = Data(test_path, aud_path, char2ind)
     _check_features(features, n_feats, test_dataset)
-    collate_custom = functools.partial(_collate, device=dev, features=features)
+    collate_custom = functools.partial(_collate, device=dev, features=features, target_rate=target_rate)
     loader = tud.DataLoader(test_dataset, batch_size=batch_size, shuffle=False, collate_fn=collate_custom)
     lm = CharNgramLM.load(lm_path) if lm_path is not None else None
     decoder = CTCDecoder(alphabet, lm=lm, lm_alpha=lm_alpha, lm_beta=lm_beta, fast_lm=bool(lm_fast))
@@ -525,12 +543,13 @@ def predict(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=N
 
 
 def align(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=None, maxlent=None, device_id=0,
-          test_dataset=None, n_feats=120, features="mfcc", out_path=None):
+          test_dataset=None, n_feats=120, features="mfcc", out_path=None, target_rate=None):
     """Forced alignment of the REFERENCE transcripts: ``predict``'s loading and batching, then per batch forward, log-softmax and
     ``CTCDecoder.align_batch`` (Viterbi on the device).  Writes ``out_path`` (default <model_path>/alignments.tsv), one line per
     reference character: utterance index, character index, symbol, start frame, end frame (one past the last), mean log-prob of
     its frames.  An utterance whose transcript does not fit its frames is written with spans -1 -1 and mean -inf, not dropped.
-    Returns the per-utterance scores (negative log-probability of the best alignment, +inf where there is none)."""
+    Returns the per-utterance scores (negative log-probability of the best alignment, +inf where there is none).
+    target_rate: as in ``predict``."""
     import os
     import functools
     import torch.utils.data as tud
@@ -547,7 +566,7 @@ def align(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=Non
     if test_dataset is None:
         test_dataset = Data(test_path, aud_path, char2ind)
     _check_features(features, n_feats, test_dataset)
-    collate_custom = functools.partial(_collate, device=dev, features=features)
+    collate_custom = functools.partial(_collate, device=dev, features=features, target_rate=target_rate)
     loader = tud.DataLoader(test_dataset, batch_size=batch_size, shuffle=False, collate_fn=collate_custom)
     decoder = CTCDecoder(alphabet)
     scores, lines = [], []
