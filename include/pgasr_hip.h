@@ -989,6 +989,15 @@ int pgasr_adam_step_clipped(float* param, const float* grad, float* exp_avg, flo
  *   pgasr_feat_db:      in place on mel (B, Tmax, n_mels)
  *   pgasr_feat_deltas_stack: mfcc (B, Tmax, n_mfcc) -> feat (B, 3*n_mfcc, Tmax) zero padded (the reference's
  *                       batch layout, data.py:71-79), fmask (B, 1, Tmax) (optional)
+ *   Preconditions the calls cannot check (the lengths live on the device): 200 < n_samples[b] <= wave_stride -- the reflect
+ *   index of a shorter utterance leaves its row (features._FrontEnd refuses it with a ValueError); 1 <= n_frames[b] <= Tmax.
+ *   Checked, PGASR_ERR_INVALID_ARG before any launch: null pointers (fmask alone may be NULL), B, Tmax, wave_stride, rows,
+ *   n_mels, n_mfcc, C <= 0, B or n_mfcc / C > 65535 in the two stacking calls (grid dimensions), B * Tmax > 2^31 - 1 in
+ *   pgasr_feat_frames, top_db not > 0 (NaN included).
+ *   Rows t >= n_frames[b] are never read: pgasr_feat_frames / _deltas_stack / _stack write zeros there whatever the input row
+ *   holds, pgasr_feat_db leaves them as they are and takes its maximum over the utterance's own n_frames[b] * n_mels cells.
+ *   A delta is (2 (x[t+2] - x[t-2]) + (x[t+1] - x[t-1])) / 10 with the indices clamped to [0, n_frames[b] - 1]: exactly 0 over
+ *   a constant stretch, so both deltas of a one-frame utterance are exactly 0.
  * ---------------------------------------------------------------------------------------- */
 int pgasr_feat_frames(const float* wave, const int32_t* n_samples, const int32_t* n_frames, int B,
                       long long wave_stride, int Tmax, float* frames, void* stream);

@@ -80,13 +80,15 @@ __global__ __launch_bounds__(256) void feat_deltas_kernel(const float* __restric
     }
     const float* x = mfcc + (size_t)b * Tmax * C + c;
     auto X = [&](int u) { u = u < 0 ? 0 : (u >= T ? T - 1 : u); return x[(size_t)u * C]; };
+    // the taps are paired as differences: where replicate padding (or a constant stretch) makes both ends of a pair the same value
+    // the delta is exactly 0, as in exact arithmetic -- summed tap by tap, -2x - x + x + 2x rounds to an ulp of x, not to 0
     auto D1 = [&](int u) {       // delta at the (clamped) frame u
         u = u < 0 ? 0 : (u >= T ? T - 1 : u);
-        return (-2.f * X(u - 2) - X(u - 1) + X(u + 1) + 2.f * X(u + 2)) / 10.f;
+        return (2.f * (X(u + 2) - X(u - 2)) + (X(u + 1) - X(u - 1))) / 10.f;
     };
     out[(size_t)c * Tmax + t] = x[(size_t)t * C];
     out[(size_t)(C + c) * Tmax + t] = D1(t);
-    out[(size_t)(2 * C + c) * Tmax + t] = (-2.f * D1(t - 2) - D1(t - 1) + D1(t + 1) + 2.f * D1(t + 2)) / 10.f;
+    out[(size_t)(2 * C + c) * Tmax + t] = (2.f * (D1(t + 2) - D1(t - 2)) + (D1(t + 1) - D1(t - 1))) / 10.f;
 }
 
 // x (B, Tmax, C) -> feat (B, C, Tmax) (time contiguous, 0 past the length), mask (B,1,Tmax): the layout step of a front end WITHOUT
@@ -113,6 +115,7 @@ extern "C" int pgasr_feat_stack(const float* x, const int32_t* n_frames, int B, 
 extern "C" int pgasr_feat_frames(const float* wave, const int32_t* n_samples, const int32_t* n_frames, int B,
                                  long long wave_stride, int Tmax, float* frames, void* stream) {
     if (!wave || !n_samples || !n_frames || !frames || B <= 0 || Tmax <= 0 || wave_stride <= 0) return PGASR_ERR_INVALID_ARG;
+    if ((long long)B * Tmax > 2147483647LL) return PGASR_ERR_INVALID_ARG;      // one workgroup per row: the grid's x limit
     PGASR_LAUNCH_KERNEL(feat_frames_kernel, dim3((unsigned)((long long)B * Tmax)), dim3(256), 0, (hipStream_t)stream,
                        wave, n_samples, n_frames, wave_stride, Tmax, frames);
     PGASR_CHECK_LAUNCH();

@@ -450,17 +450,24 @@ class SpeedPerturb:
 
 
 def read_wav(path):
-    """PCM-16 / PCM-32 / float32 RIFF WAV -> (1-D float32 tensor in [-1,1), sample rate): the stand-in for
-    ``torchaudio.load`` (data.py:53) where torchaudio is absent; first channel only, like ``.squeeze(0)`` on mono."""
+    """Integer PCM-16 / PCM-32 RIFF WAV -> (1-D float32 tensor, sample rate): the stand-in for ``torchaudio.load`` (data.py:53) where
+    torchaudio is absent; first channel only, like ``.squeeze(0)`` on mono.  A sample is its integer / 2^15 (2^31), rounded to fp32
+    once: PCM-16 lies in [-1, 1), PCM-32 in [-1, 1] (the largest integers round up to 1.0).  Anything else is refused with a
+    ValueError: 8- and 24-bit PCM, a file that is no RIFF WAV (an empty one included), and above all IEEE-float WAV (format tag 3),
+    whose 4-byte samples must never be taken for PCM-32."""
     import wave as _wave
     import numpy as np
-    with _wave.open(path, "rb") as f:
-        sr, nch, width, n = f.getframerate(), f.getnchannels(), f.getsampwidth(), f.getnframes()
-        raw = f.readframes(n)
+    try:
+        with _wave.open(path, "rb") as f:
+            sr, nch, width, n = f.getframerate(), f.getnchannels(), f.getsampwidth(), f.getnframes()
+            raw = f.readframes(n)
+    except (_wave.Error, EOFError) as e:       # the wave module reads integer PCM only: format tag 3 ends here, as "unknown format: 3"
+        raise ValueError(f"{path}: not an integer-PCM RIFF WAV file ({str(e) or 'file too short'}); IEEE-float (format tag 3) and "
+                         f"compressed WAV are not read -- convert to PCM-16 or PCM-32") from e
     if width == 2:
         x = np.frombuffer(raw, dtype="<i2").astype(np.float32) / 32768.0
     elif width == 4:
         x = np.frombuffer(raw, dtype="<i4").astype(np.float32) / 2147483648.0
     else:
-        raise ValueError(f"unsupported sample width {width}")
+        raise ValueError(f"{path}: unsupported sample width {width} bytes (PCM-16 and PCM-32 are read)")
     return torch.from_numpy(x.reshape(-1, nch)[:, 0].copy()), sr

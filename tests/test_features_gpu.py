@@ -3,6 +3,7 @@ import numpy as np
 import pytest
 import torch
 
+import features_f32_ref as f32
 from oracle import features_ref as fr
 
 pytestmark = pytest.mark.gpu
@@ -49,6 +50,52 @@ def test_logmel80_matches_oracle_and_stays_on_device(lengths):
     assert np.abs(got - want).max() < 2e-3, np.abs(got - want).max()
     for b, n in enumerate(lengths):
         assert np.all(got[b, :, 1 + n // 200:] == 0)
+
+
+def _front_end(kind):
+    from policy_gradient_asr_amd.features import LogMel, MFCCDeltas
+    return MFCCDeltas(DEV) if kind == "mfcc" else LogMel(80, DEV)
+
+
+@pytest.mark.parametrize("kind", f32.KINDS)
+@pytest.mark.parametrize("name", f32.CASES)
+def test_edge_inputs_match_oracle_to_what_fp32_can_hold(name, kind):
+    """Inputs the two-tone family never reaches (features_f32_ref.py lists them).  fp32 cannot hold 2e-3 dB on all of them, so the
+    bound per case is max(2e-3, 4 x floor): the floor is the error of the float32 numpy restatement of the chain against the same
+    oracle, recorded in features_f32_ref.FLOORS and re-measured by test_features_cpu.py; the 4 is for the device's GEMMs, which
+    accumulate in another order than the restatement."""
+    waves = f32.case(name)
+    feat, fmask = _front_end(kind)([torch.from_numpy(w) for w in waves])
+    want = f32.oracle(kind, waves)
+    got = feat.cpu().numpy()
+    assert got.shape == want.shape and tuple(fmask.shape) == (len(waves), 1, want.shape[2])
+    tol = f32.tolerance(name, kind)
+    err = float(np.abs(got - want).max())
+    print(f"{name} {kind}: device {err:.3e} dB, float32 floor {f32.FLOORS[name][f32.KINDS.index(kind)]:.3e} dB, bound {tol:.3e} dB")
+    assert err <= tol, (err, tol)
+    for b, w in enumerate(waves):
+        T = fr.n_frames(w.shape[0])
+        assert np.all(got[b, :, T:] == 0)
+        assert np.array_equal(fmask[b, 0].cpu().numpy(), (np.arange(want.shape[2]) < T).astype(np.float32))
+    if name == "loud_quiet" and kind == "logmel80":
+        # the same waveform 60 dB down: wherever neither cell is held by the absolute 1e-10 floor (-100 dB) the features are the
+        # loud ones minus 60 dB -- the top_db clamp moves with the utterance's own maximum; a floor shared across the batch does not.
+        # Each of the two device values is within tol of its oracle value, and the oracle's two differ by 60 dB to well within tol.
+        both = (want[0] > -100.0 + 1e-3) & (want[1] > -100.0 + 1e-3)
+        assert both.mean() > 0.9
+        assert np.abs((want[0] - want[1])[both] - 20.0 * np.log10(1e3)).max() < 1e-4
+        assert np.abs((got[0] - got[1])[both] - 60.0).max() <= 2.0 * tol
+
+
+def test_front_ends_refuse_utterances_of_200_samples_or_fewer():
+    """Reflect-centred framing needs more than n_fft / 2 samples: the kernel's reflect index would leave the row."""
+    for kind in f32.KINDS:
+        fe = _front_end(kind)
+        for ns in ([200], [1], [4000, 200], [0, 4000]):
+            with pytest.raises(ValueError, match="200 samples"):
+                fe([torch.zeros(n) for n in ns])
+        feat, _ = fe([torch.zeros(201)])
+        assert feat.shape[2] == 2
 
 
 def test_device_collate_feeds_the_trainer_without_a_host_copy():
