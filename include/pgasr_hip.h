@@ -50,7 +50,8 @@ typedef enum pgasr_status {
  * SpecAugment masking (pgasr_spec_augment), the N-best entries (pgasr_ctc_beam_search_nbest, pgasr_nbest_rescore) and MWER training
  * over them (pgasr_mwer_weights, pgasr_ctc_grad_from_lattices_nbest), and the KL penalty towards a frozen reference policy
  * (pgasr_frame_kl, pgasr_ctc_grad_from_lattice_kl, pgasr_ctc_grad_from_lattice_multi_kl, pgasr_ctc_grad_from_lattices_seq_kl),
- * and sample-rate conversion / speed perturbation (pgasr_resample). */
+ * sample-rate conversion / speed perturbation (pgasr_resample), and minimum-Bayes-risk decoding over N-best lists
+ * (pgasr_nbest_pair_dist, pgasr_mbr_select). */
 #define PGASR_ABI_VERSION 7
 
 int pgasr_abi_version(void);
@@ -822,6 +823,40 @@ int pgasr_nbest_rescore(const int32_t* tokens, int tok_stride, const int32_t* le
                         int N, int B, int V, int blank, const float* lm_table, int lm_order,
                         double am_weight, double lm_alpha, double lm_beta,
                         double* out_lm_logp, double* out_total, int32_t* out_order, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * A7-MBR  Minimum-Bayes-risk decoding over N-best lists (the inference-side counterpart of A13-MWER): the edit distances inside each
+ * list, and the hypothesis of least expected distance under the list's renormalised posterior.
+ * pgasr_nbest_pair_dist:
+ *   tokens (N, B, tok_stride) int32, len (N, B), count (B): a list as pgasr_ctc_beam_search_nbest writes it (len is clamped to
+ *   [0, tok_stride], count to [0, N]); nothing behind a hypothesis' length is read.  dist (B, N, N) int32; the kernel writes every
+ *   word of it.  For n, m < count[b] with len[n,b] <= Lmax and len[m,b] <= Lmax:
+ *     dist[b,n,m] = dist[b,m,n] = the Levenshtein distance of the two hypotheses (sub = ins = del = 1), 0 on the diagonal.
+ *   Every other entry is -1: a row beyond count, a hypothesis longer than Lmax -- its row, its column and its own diagonal.
+ *   A symbol outside [0, V) matches nothing, not even itself (the search never emits one): two equal rows holding one such
+ *   symbol are at distance 1.
+ *   Myers' bit-vector recurrence in blocks of 64 pattern positions, one lane per pair, each unordered pair once (csrc/mbr.hip).
+ *   Checked before any HIP call, in this order: N < 1, N > 128, V < 1, V > 64, Lmax outside [0, 1024] -> PGASR_ERR_UNSUPPORTED;
+ *   a NULL pointer, B < 1, tok_stride < 1 -> PGASR_ERR_INVALID_ARG.  One launch, no workspace, no host synchronisation.
+ * pgasr_mbr_select:
+ *   dist (B, N, N) int32 as above, or any caller-made matrix in that layout (word distances); score (N, B) fp64, lower is better
+ *   (the exact CTC -log p, the first-pass score or a rescored total); scale: the posterior temperature, finite and >= 0.
+ *     valid(n,b)      := n < count[b]  and  score[n,b] finite  and  dist[b,n,n] >= 0
+ *     m_b              = min over valid n of score[n,b]
+ *     w[n,b]           = exp(-(scale * (score[n,b] - m_b)))
+ *     posterior[n,b]   = w[n,b] / sum_valid w, the sum in n order                      0 where not valid
+ *     risk[n,b]        = sum over valid m of posterior[m,b] * dist[b,n,m], in m order  +inf where not valid
+ *     best[b]          = the first valid n of least risk                               0 when no n is valid
+ *   Every product and every sum is rounded once (no contraction into fused multiply-adds); scale = 0 gives the uniform posterior
+ *   over the valid rows.  posterior, risk (N, B) fp64, best (B) int32.  risk[best[b], b] is the expected number of errors of the
+ *   chosen hypothesis under the list's posterior.
+ *   Checked before any HIP call: N < 1 or N > 128 -> PGASR_ERR_UNSUPPORTED; a NULL pointer, B < 1, a scale that is negative or
+ *   not finite -> PGASR_ERR_INVALID_ARG.  One launch, one workgroup per utterance, fp64, no host synchronisation.
+ * ---------------------------------------------------------------------------------------- */
+int pgasr_nbest_pair_dist(const int32_t* tokens, int tok_stride, const int32_t* len, const int32_t* count,
+                          int N, int B, int V, int Lmax, int32_t* dist, void* stream);
+int pgasr_mbr_select(const int32_t* dist, const double* score, const int32_t* count, int N, int B, double scale,
+                     double* posterior, double* risk, int32_t* best, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * A13-MWER  Minimum word error rate training over the N-best list of the beam search (Prabhavalkar et al., arXiv:1712.01818): the

@@ -2,7 +2,9 @@
 blank=0) -> (tuple[int], float)`` and ``collapse_fn(str) -> str``, with the search itself running
 as a HIP kernel (csrc/beam.hip).  ``greedy_decode`` is the best-path decoder the reference lacks
 (SURVEY §8a A9).  Beyond the reference: ``nbest=N`` returns the first N entries of the final beam instead of the best one, and
-``CTCDecoder.rescore`` ranks such a list in a second pass (exact CTC likelihood and / or a stronger n-gram LM, csrc/nbest.hip)."""
+``CTCDecoder.rescore`` ranks such a list in a second pass (exact CTC likelihood and / or a stronger n-gram LM, csrc/nbest.hip);
+``CTCDecoder.mbr_decode`` returns the hypothesis of least expected edit distance under the list's posterior instead of the best-scored
+one (minimum-Bayes-risk decoding, csrc/mbr.hip)."""
 import collections
 
 import numpy as np
@@ -25,6 +27,7 @@ BEAM_KMAX = 128      # csrc/beam.hip
 _UNSET = object()      # "use the decoder's own value" (None is a value: no language model)
 
 NBestRescored = collections.namedtuple("NBestRescored", "order total am lm_logp best_tokens best_len skipped")
+MBRDecoded = collections.namedtuple("MBRDecoded", "tokens lengths best risk posterior dist nbest")
 
 
 class CTCDecoder:
@@ -128,6 +131,42 @@ class CTCDecoder:
         first = order[:, 0].long()
         cols = torch.arange(B, device=order.device)
         return NBestRescored(order, total, am, lm_logp, nb.tokens[first, cols].contiguous(), nb.lengths[first, cols].contiguous(), skipped)
+
+    def mbr_from_list(self, nb, score, vocab=None, risk_unit="char", word_delimiter=None, posterior_scale=1.0, max_hyp_len=None):
+        """Minimum-Bayes-risk choice over an N-best list the caller already holds: ``nb`` a ``hipops.CTCNBest`` (N <= 128), ``score``
+        (N,B) float64 with lower better (``rescore(...).total``, ``nb.score``, ...), ``vocab`` the number of symbols (default: the
+        alphabet's).  posterior = softmax(-posterior_scale * score) over the list's valid rows; the row of least expected edit
+        distance to the others under it is returned (the first among equals).
+        risk_unit: "char" (default: ``hipops.nbest_pair_distance`` on the bit-vector kernel) or "word" (words split at the token
+            ``word_delimiter``, the alphabet's " ", as str.split(" ") cuts them).
+        max_hyp_len: None reads the longest hypothesis from the device for risk_unit="char" (ONE host synchronisation); a number
+            avoids it, and a hypothesis longer than that takes no part (risk +inf, posterior 0).
+        Returns ``MBRDecoded``: tokens (B,T) / lengths (B) int32 the chosen row of every utterance, best (B) int32 its rank in the
+        list, risk (N,B) / posterior (N,B) float64, dist (B,N,N) int32 (-1 where a row takes no part), nbest = ``nb``.
+        risk[best[b], b] is the expected number of character (word) errors of the returned hypothesis: a confidence."""
+        if risk_unit not in ("char", "word"):
+            raise ValueError(f"risk_unit must be 'char' or 'word' (got {risk_unit!r})")
+        V = len(self.alphabet) if vocab is None else int(vocab)
+        dist = hipops.nbest_pair_distance(nb.tokens, nb.lengths, nb.count, V, max_hyp_len=max_hyp_len, unit=risk_unit,
+                                          delimiter=word_delimiter)
+        best, risk, posterior = hipops.mbr_select(dist, score.contiguous(), nb.count, scale=float(posterior_scale))
+        first = best.long()
+        cols = torch.arange(first.numel(), device=first.device)
+        return MBRDecoded(nb.tokens[first, cols].contiguous(), nb.lengths[first, cols].contiguous(), best, risk, posterior, dist, nb)
+
+    def mbr_decode(self, log_probs, lengths=None, beam_size=16, nbest=16, risk_unit="char", word_delimiter=None, acoustic="ctc",
+                   posterior_scale=1.0, lm=_UNSET, lm_alpha=None, lm_beta=None, am_weight=1.0, max_hyp_len=None, blank=0):
+        """Minimum-Bayes-risk decoding: the N-best search (``decode_batch(nbest=)``, with the decoder's first-pass LM if it has
+        one), the score of every hypothesis (``rescore(...).total`` with ``acoustic`` / ``lm`` / ``lm_alpha`` / ``lm_beta`` /
+        ``am_weight`` as ``rescore`` takes them: without an LM the exact CTC -log p, or the first-pass score), the distances inside
+        each list and the selection (``mbr_from_list``), in that order.  log_probs (T,B,V) GPU tensor, nbest <= beam_size, nbest <= 128.
+        Returns ``MBRDecoded``."""
+        T, B, V = log_probs.shape
+        nb = self.decode_batch(log_probs, lengths, beam_size=beam_size, blank=blank, nbest=int(nbest))
+        rs = self.rescore(log_probs, lengths, nb, lm=lm, lm_alpha=lm_alpha, lm_beta=lm_beta, acoustic=acoustic, am_weight=am_weight,
+                          max_hyp_len=max_hyp_len, blank=blank)
+        return self.mbr_from_list(nb, rs.total, vocab=V, risk_unit=risk_unit, word_delimiter=word_delimiter,
+                                  posterior_scale=posterior_scale, max_hyp_len=max_hyp_len)
 
     def align_batch(self, log_probs, tokens, token_lengths, lengths=None, blank=0):
         """Forced alignment on the device: log_probs (T,B,V) fp32 GPU tensor of natural-log probabilities, tokens (B,Lmax) /

@@ -99,6 +99,8 @@ SIGNATURES = {
                                               c_ptr, C.c_size_t, c_ptr, c_f32p, C.c_int, C.c_double, C.c_double]),
     "pgasr_nbest_rescore": (C.c_int, [c_i32p, C.c_int, c_i32p, c_i32p, c_ptr, C.c_int, C.c_int, C.c_int, C.c_int, c_f32p, C.c_int,
                                       C.c_double, C.c_double, C.c_double, c_ptr, c_ptr, c_i32p, c_ptr]),
+    "pgasr_nbest_pair_dist": (C.c_int, [c_i32p, C.c_int, c_i32p, c_i32p, C.c_int, C.c_int, C.c_int, C.c_int, c_i32p, c_ptr]),
+    "pgasr_mbr_select": (C.c_int, [c_i32p, c_ptr, c_i32p, C.c_int, C.c_int, C.c_double, c_ptr, c_ptr, c_i32p, c_ptr]),
     "pgasr_mwer_weights": (C.c_int, [c_i32p, c_i32p, c_i32p, c_f32p, c_i32p, c_i32p, c_f32p, C.c_int, C.c_int, C.c_int,
                                      C.c_float, C.c_float, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_ptr]),
     "pgasr_ctc_grad_from_lattices_nbest": (C.c_int, [c_f32p, c_i32p, c_i32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_f32p,

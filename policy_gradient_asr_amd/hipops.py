@@ -1410,6 +1410,126 @@ def nbest_rescore(tokens, lengths, count, am, vocab, blank=0, lm=None, am_weight
     return order, total, lm_logp
 
 
+PAIR_DIST_MAX_LEN = 1024         # csrc/mbr.hip: 16 blocks of 64 pattern positions
+PAIR_DIST_CHUNK_ELEMS = 1 << 24  # the composed path: int32 words of expanded rows per chunk of pairs (64 MB)
+# Where the composed path is the faster one (MI355X, tools/dev/mbr_cost.py, NOTES.md 0.20): few pairs of long hypotheses.  A lane of
+# the bit-vector kernel walks its pair alone, 1.3 - 1.7 ms at 930 symbols however few pairs there are; a wave per pair takes 0.97 /
+# 1.19 ms there for 192 / 896 pairs (B = 32, N = 4 / 8).  From 16 hypotheses per list, or at 232 symbols, the kernel wins at every
+# size measured.
+PAIR_DIST_COMPOSED_MAX_PAIRS = 1024
+PAIR_DIST_COMPOSED_MIN_LEN = 640
+
+
+def _pair_distance_composed(tokens, lengths, count, vocab, cap, unit, delimiter):
+    """The unordered pairs of every list through the wave-per-pair kernels (``edit_distance`` / ``word_edit_distance``), expanded in
+    chunks of at most PAIR_DIST_CHUNK_ELEMS words, scattered into (B,N,N) with pgasr_nbest_pair_dist's -1 convention."""
+    N, B, stride = tokens.shape
+    dev = tokens.device
+    S = max(1, min(stride, int(cap)))                       # a valid hypothesis has no token behind min(stride, cap)
+    ln = lengths.clamp(0, stride)
+    valid = (torch.arange(N, device=dev).view(N, 1) < count.clamp(0, N).view(1, B)) & (ln <= int(cap))       # (N,B)
+    ln = torch.where(valid, ln, torch.zeros_like(ln))
+    dist = torch.full((B, N, N), -1, dtype=torch.int32, device=dev)
+    diag = torch.arange(N, device=dev)
+    dist[:, diag, diag] = torch.where(valid.t(), 0, -1).to(torch.int32)
+    P = N * (N - 1) // 2
+    if P == 0:
+        return dist
+    iu = torch.triu_indices(N, N, offset=1, device=dev)      # (2,P): n < m
+    words_per_pair = (2 if unit == "char" else 4) * (S + 1)
+    step = max(1, PAIR_DIST_CHUNK_ELEMS // words_per_pair)
+    flat = dist.view(-1)
+    for q0 in range(0, B * P, step):
+        q = torch.arange(q0, min(q0 + step, B * P), device=dev)
+        b, pr = q // P, q % P
+        n, m = iu[0, pr], iu[1, pr]
+        ref, hyp = tokens[n, b, :S].contiguous(), tokens[m, b, :S].contiguous()
+        rl, hl = ln[n, b].contiguous(), ln[m, b].contiguous()
+        if unit == "char":
+            # pgasr_nbest_pair_dist's rule: a symbol outside [0, vocab) matches nothing, not even itself
+            ref = torch.where((ref >= 0) & (ref < int(vocab)), ref, torch.full_like(ref, -1))
+            hyp = torch.where((hyp >= 0) & (hyp < int(vocab)), hyp, torch.full_like(hyp, -2))
+            d = edit_distance(ref, rl, hyp, hl)
+        else:
+            d = word_edit_distance(ref, rl, hyp, hl, int(delimiter))[0]
+        d = torch.where(valid[n, b] & valid[m, b], d, torch.full_like(d, -1))
+        flat[(b * N + n) * N + m] = d
+        flat[(b * N + m) * N + n] = d
+    return dist
+
+
+def nbest_pair_distance(tokens, lengths, count, vocab, max_hyp_len=None, unit="char", delimiter=None):
+    """The edit distances inside each N-best list: tokens (N,B,stride) / lengths (N,B) / count (B) int32 as ``ctc_beam_search_nbest``
+    returns them, ``vocab`` the number of symbols.  Returns dist (B,N,N) int32: dist[b,n,m] = dist[b,m,n] = the Levenshtein distance of
+    hypotheses n and m of utterance b, 0 on the diagonal, and -1 wherever n or m lies beyond count[b] or is longer than the cap (its own
+    diagonal included).  N <= 128.
+    unit="char" (default): characters, by pgasr_nbest_pair_dist (Myers' bit-vector algorithm, one lane per pair, one launch; vocab <= 64);
+        a symbol outside [0, vocab) matches nothing, not even itself.  Lists whose cap exceeds 1024 take the composed path: the
+        unordered pairs expanded in bounded chunks through ``edit_distance`` (one wave per pair), the same result -- and so do
+        at most PAIR_DIST_COMPOSED_MAX_PAIRS pairs with a cap from PAIR_DIST_COMPOSED_MIN_LEN, where that path measured faster.
+    unit="word": words split at the token ``delimiter`` as str.split(" ") cuts them (``word_edit_distance`` on the composed path).
+    max_hyp_len: the cap.  None: the longest hypothesis of the lists, read from the device (ONE host synchronisation, as in
+        ``CTCDecoder.rescore``; unit="word" needs none) -- nothing is over it.  A number avoids the synchronisation."""
+    _lib.load()
+    _req(tokens, torch.int32, "tokens"); _req(lengths, torch.int32, "lengths"); _req(count, torch.int32, "count")
+    if tokens.dim() != 3 or tuple(lengths.shape) != tuple(tokens.shape[:2]) or count.numel() != tokens.shape[1]:
+        raise _lib.PgasrError("nbest_pair_distance wants tokens (N,B,stride), lengths (N,B) and count (B)")
+    if unit not in ("char", "word"):
+        raise ValueError(f"unit must be 'char' or 'word' (got {unit!r})")
+    if unit == "word" and (delimiter is None or int(delimiter) < 0):
+        raise ValueError("unit='word' needs delimiter, the token id of the alphabet's ' ' symbol")
+    N, B, stride = tokens.shape
+    if N < 1 or N > NBEST_RESCORE_MAX:
+        raise _lib.PgasrError(f"nbest_pair_distance takes 1 <= N <= {NBEST_RESCORE_MAX} hypotheses per utterance (got {N})")
+    if max_hyp_len is not None:
+        cap = int(max_hyp_len)
+        if cap < 0:
+            raise ValueError(f"max_hyp_len must be >= 0 (got {max_hyp_len})")
+    elif unit == "word":
+        cap = stride
+    else:
+        rows = torch.arange(N, device=tokens.device).view(N, 1) < count.view(1, B)
+        cap = int((lengths.clamp(0, stride) * rows).max().item())
+    few_and_long = B * N * (N - 1) // 2 <= PAIR_DIST_COMPOSED_MAX_PAIRS and cap >= PAIR_DIST_COMPOSED_MIN_LEN
+    if unit == "word" or cap > PAIR_DIST_MAX_LEN or few_and_long:
+        with _timed("nbest_pair_dist_composed"):
+            return _pair_distance_composed(tokens, lengths, count, vocab, cap, unit, delimiter)
+    return _pair_distance_kernel(tokens, lengths, count, vocab, cap)
+
+
+def _pair_distance_kernel(tokens, lengths, count, vocab, cap):
+    """pgasr_nbest_pair_dist itself: one launch, no host synchronisation; cap <= 1024, vocab <= 64."""
+    N, B, stride = tokens.shape
+    dist = torch.empty(B, N, N, dtype=torch.int32, device=tokens.device)      # the kernel writes every word
+    with _timed("nbest_pair_dist"):
+        st = _lib.load().pgasr_nbest_pair_dist(_p(tokens), stride, _p(lengths), _p(count), N, B, int(vocab), int(cap), _p(dist),
+                                               _stream())
+    _lib.check(st, "pgasr_nbest_pair_dist")
+    return dist
+
+
+def mbr_select(dist, score, count, scale=1.0):
+    """Minimum-Bayes-risk selection over N-best lists (pgasr_mbr_select; include/pgasr_hip.h, A7-MBR): dist (B,N,N) int32 as
+    ``nbest_pair_distance`` returns it (or any matrix in that layout), score (N,B) float64 with lower better, count (B) int32.
+    Returns (best (B) int32, risk (N,B) float64, posterior (N,B) float64), no host synchronisation: posterior = the softmax of
+    -scale * score over the valid rows (n < count, finite score, dist[b,n,n] >= 0; 0 elsewhere), risk[n] = sum_m posterior[m] *
+    dist[n,m] (+inf where not valid), best = the first row of least risk (0 when no row is valid).  scale = 0: a uniform posterior."""
+    lib = _lib.load()
+    _req(dist, torch.int32, "dist"); _req(score, torch.float64, "score"); _req(count, torch.int32, "count")
+    if dist.dim() != 3 or dist.shape[1] != dist.shape[2] or tuple(score.shape) != (dist.shape[1], dist.shape[0]) \
+            or count.numel() != dist.shape[0]:
+        raise _lib.PgasrError("mbr_select wants dist (B,N,N), score (N,B) and count (B)")
+    B, N, _ = dist.shape
+    dev = dist.device
+    out = torch.empty(2, N, B, dtype=torch.float64, device=dev)
+    best = torch.empty(B, dtype=torch.int32, device=dev)
+    with _timed("mbr_select"):
+        st = lib.pgasr_mbr_select(_p(dist), _p(score), _p(count), N, B, float(scale), out[1].data_ptr(), out[0].data_ptr(), _p(best),
+                                  _stream())
+    _lib.check(st, "pgasr_mbr_select")
+    return best, out[0], out[1]
+
+
 # ------------------------------------------------------------------------------------------
 # dropout / Adam
 # ------------------------------------------------------------------------------------------

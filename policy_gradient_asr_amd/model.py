@@ -442,7 +442,8 @@ def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset
 
 def predict(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=None, maxlent=None, device_id=0,
             test_dataset=None, n_feats=120, beam_size=5, features="mfcc", lm_path=None, lm_alpha=0.0, lm_beta=0.0,
-            nbest=1, rescore_lm_path=None, rescore_alpha=0.0, rescore_beta=0.0, lm_fast=False, target_rate=None):
+            nbest=1, rescore_lm_path=None, rescore_alpha=0.0, rescore_beta=0.0, lm_fast=False, target_rate=None,
+            mbr=False, mbr_unit="char", mbr_scale=1.0):
     """model.py:277-339: load model_best.pth, forward, beam=5 prefix search (device side, batched),
     collapse_fn, CER/WER, predicted.txt.  Frames are cut by the FEATURE mask (the reference cuts the
     time axis by the target mask, model.py:322 -- a listed defect).  Returns (CER, WER).
@@ -462,7 +463,13 @@ def predict(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=N
     length): the hypothesis with the lowest total is the one written to predicted.txt and scored.  Without it rank 0 is.
     With nbest > 1 every list comes from the workgroup-per-utterance kernel: rank 0 is ``ctc_beam_search(generic=True)``'s result,
     while nbest = 1 without an LM takes the single-wave fp32 kernel for beam_size <= 16.  The two agree to ~1e-7 relative in their
-    scores, so their hypotheses can differ only where two candidates are closer than that."""
+    scores, so their hypotheses can differ only where two candidates are closer than that.
+    mbr: False (default: everything above, nothing else) or True, with nbest >= 2: minimum-Bayes-risk decoding
+    (``CTCDecoder.mbr_from_list``).  The posterior over each list is softmax(-mbr_scale * score), score being the rescored total with
+    rescore_lm_path and the exact CTC likelihood without; the hypothesis of least expected character (mbr_unit="char") or word
+    (mbr_unit="word", words split at the alphabet's " ") edit distance to the rest of its list is the one written to predicted.txt
+    and scored, the CER / WER of the best-scored rows are printed beside its own, and ``mbr.tsv`` in model_path gets one line per
+    utterance: utterance, chosen rank, its expected errors, rank 0's expected errors, tab-separated."""
     import os
     import functools
     import torch.utils.data as tud
@@ -477,6 +484,10 @@ def predict(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=N
         raise ValueError(f"nbest must lie in [1, beam_size = {beam_size}] (got {nbest})")
     if rescore_lm_path is not None and nbest < 2:
         raise ValueError("rescoring needs a list: give nbest >= 2 with rescore_lm_path")
+    if mbr and nbest < 2:
+        raise ValueError("minimum-Bayes-risk decoding needs a list: give nbest >= 2 with mbr=True")
+    if mbr and mbr_unit not in ("char", "word"):
+        raise ValueError(f"mbr_unit must be 'char' or 'word' (got {mbr_unit!r})")
     alphabet, char2ind = _read_alphabet(alphabet_path)
     ind2char = {char2ind[k]: k for k in char2ind}
     dev = torch.device("cuda", device_id)
@@ -490,9 +501,12 @@ def predict(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=N
     loader = tud.DataLoader(test_dataset, batch_size=batch_size, shuffle=False, collate_fn=collate_custom)
     lm = CharNgramLM.load(lm_path) if lm_path is not None else None
     decoder = CTCDecoder(alphabet, lm=lm, lm_alpha=lm_alpha, lm_beta=lm_beta, fast_lm=bool(lm_fast))
+    if mbr and mbr_unit == "word" and " " not in char2ind:
+        raise ValueError("mbr_unit='word' needs an alphabet with the ' ' symbol")
     rescore_lm = CharNgramLM.load(rescore_lm_path) if rescore_lm_path is not None else None
     targets, predicted, tot_cer, tot_wer, n = [], [], 0.0, 0.0, 0
     nbest_lines, tot_oracle = [], 0.0
+    mbr_lines, map_cer, map_wer = [], 0.0, 0.0
     print("Total number of examples: ", len(test_dataset))
     with torch.no_grad():
         for step, batch in enumerate(loader, 1):
@@ -506,6 +520,15 @@ def predict(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=N
                 if rescore_lm is not None:
                     rs = decoder.rescore(lp, in_len, nb, lm=rescore_lm, lm_alpha=rescore_alpha, lm_beta=rescore_beta)
                     tok, tl, total = rs.best_tokens, rs.best_len, rs.total.cpu()
+                if mbr:
+                    score = rs.total if rescore_lm is not None else decoder.rescore(lp, in_len, nb, lm=None).total
+                    md = decoder.mbr_from_list(nb, score, vocab=lp.shape[2], risk_unit=mbr_unit, posterior_scale=mbr_scale,
+                                               word_delimiter=char2ind[" "] if mbr_unit == "word" else None)
+                    map_tok, map_tl, tok, tl = tok.cpu(), tl.cpu(), md.tokens, md.lengths
+                    mbest, mrisk = md.best.cpu(), md.risk.cpu()
+                    for i in range(mbest.shape[0]):
+                        mbr_lines.append("{}\t{}\t{:.6f}\t{:.6f}\n".format(n + i, int(mbest[i]), float(mrisk[int(mbest[i]), i]),
+                                                                          float(mrisk[0, i])))
                 # every hypothesis through collapse_fn on the host (the list is copied once); the oracle is over these strings,
                 # one edit-distance launch per batch
                 ntok, nlen, nscore, ncount = nb.tokens.cpu(), nb.lengths.cpu(), nb.score.cpu(), nb.count.cpu()
@@ -531,12 +554,21 @@ def predict(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=N
                 targets.append(target); predicted.append(seq)
                 cer, wer = evaluate(target, seq)
                 tot_cer += cer; tot_wer += wer; n += 1
+                if mbr:
+                    cer, wer = evaluate(target, collapse_fn("".join(ind2char[int(k)] for k in map_tok[i, :map_tl[i]])))
+                    map_cer += cer; map_wer += wer
     save_predictions(targets, predicted, model_path)
     cer, wer = tot_cer / max(n, 1), tot_wer / max(n, 1)
     if nbest > 1:
         with open(os.path.join(model_path, "nbest.tsv"), "w") as fo:
             fo.writelines(nbest_lines)
-        print("CER: {:>4f} WER: {:>4f} Oracle CER ({}-best): {:>4f}".format(cer, wer, nbest, tot_oracle / max(n, 1)))
+        if mbr:
+            with open(os.path.join(model_path, "mbr.tsv"), "w") as fo:
+                fo.writelines(mbr_lines)
+            print("MBR ({}) CER: {:>4f} WER: {:>4f} MAP CER: {:>4f} WER: {:>4f} Oracle CER ({}-best): {:>4f}".format(
+                mbr_unit, cer, wer, map_cer / max(n, 1), map_wer / max(n, 1), nbest, tot_oracle / max(n, 1)))
+        else:
+            print("CER: {:>4f} WER: {:>4f} Oracle CER ({}-best): {:>4f}".format(cer, wer, nbest, tot_oracle / max(n, 1)))
     else:
         print("CER: {:>4f} WER: {:>4f}".format(cer, wer))
     return cer, wer
