@@ -430,6 +430,12 @@ int pgasr_reinforce_grad(const float* scores, const int32_t* path, const float* 
  *   unmasked second launch picks up any leftovers.  Keeps a GEMM off the XCDs of a concurrent sweep; the
  *   result is complete and identical for any placement.
  *   workspace: always >= pgasr_gemm_workspace_bytes (>= 256: tile counter + partial slabs).
+ *   Leading dimensions (elements) are at least the row they stride: lda >= (transA ? M : K), ldb >= (transB ? K : N),
+ *   ldc >= N, else PGASR_ERR_INVALID_ARG; batch strides may be zero or negative.  Also PGASR_ERR_INVALID_ARG, all before any
+ *   launch: null A/B/C, a size, batch or splitk < 1, norm_operand outside 0..2 or without shift/scale, act outside 0..1,
+ *   precision outside 0..2, dact_y together with splitk > 1 or sum_batches.  Only rows < M and columns < N of each C[b] are
+ *   written; an output whose last 128-row tile would reach 4 GiB (ceil128(M) rows of ldc, or of N in a partial slab) keeps
+ *   64-bit addressing in the epilogue.
  * ---------------------------------------------------------------------------------------- */
 size_t pgasr_gemm_workspace_bytes(int M, int N, int batch, int splitk, int sum_batches);
 int pgasr_gemm_f32(int transA, int transB, int M, int N, int K, float alpha,
@@ -441,7 +447,6 @@ int pgasr_gemm_f32(int transA, int transB, int M, int N, int K, float alpha,
                    const float* dact_y, int norm_operand, const float* shift, const float* scale,
                    int precision, const unsigned* xcc_busy, void* workspace, size_t workspace_bytes, void* stream);
 
-/* column sums of X (rows x cols, leading dim ld) -> out (and out2 if non-NULL): bias gradients. */
 /* Activation x weight GEMM with the weight PRE-SPLIT into bf16 hi/lo planes (csrc/gemm_dma.hip):
  *   C[M,N] = A[M,K] * W[N,K]^T (+ bias[n]) (* (dact_y[m,n] > 0 ? 1 : slope))
  * Replaces the same torch calls as pgasr_gemm_f32 for the two big shapes of the path: the LSTM input
@@ -450,7 +455,8 @@ int pgasr_gemm_f32(int transA, int transB, int M, int N, int K, float alpha,
  * pgasr_split_bf16_planes: src (rows x cols fp32, leading dim ld) -> dense planes hi, lo of
  *   (rows x cols) bf16, or (cols x rows) when transpose != 0; x = hi + lo to ~2^-17 relative.
  * pgasr_gemm_x3w_f32 needs K % 32 == 0, N % 128 == 0, lda % 4 == 0 and 16-byte aligned A / planes, else
- *   PGASR_ERR_UNSUPPORTED (use pgasr_gemm_f32).  N % 256 == 0 takes the 256 x 256 tile (128 x 128 per wave, 4 waves).  dact_y (optional) has C's shape and leading dim. */
+ *   PGASR_ERR_UNSUPPORTED (use pgasr_gemm_f32), and so does ceil256(M)*ldc*4 >= 2^32 (whole 256-row tiles are addressed with
+ *   32-bit offsets).  N % 256 == 0 takes the 256 x 256 tile (128 x 128 per wave, 4 waves).  dact_y (optional) has C's shape and leading dim. */
 int pgasr_split_bf16_planes(const float* src, int rows, int cols, int ld, int transpose,
                             unsigned short* hi, unsigned short* lo, void* stream);
 int pgasr_gemm_x3w_f32(int M, int N, int K, const float* A, int lda, const unsigned short* Whi,
@@ -473,7 +479,7 @@ int pgasr_gemm_x3w_f32(int M, int N, int K, const float* A, int lda, const unsig
  * Call order on the host:
  * zero tiles_done -> pgasr_lstm_layer_fwd_fed (stream S) -> pgasr_stream_gate + this call (another stream that
  * waits for the zeroing).  order 0: rows in the order a forward sweep consumes them; 1: a backward sweep's (the
- * product is then the input gradient of the layer above, feeding pgasr_lstm_layer_bwd_fed).  Needs N % 256 == 0 on top of pgasr_gemm_x3w_f32's conditions and M*ldc*4 < 2^31. */
+ * product is then the input gradient of the layer above, feeding pgasr_lstm_layer_bwd_fed).  Needs N % 256 == 0 on top of pgasr_gemm_x3w_f32's conditions and ceil256(M)*ldc*4 < 2^31. */
 /* phase 0: the whole feed in one call (queue zeroed here, two persistent launches).  phase 1 (HEAD) + phase 2 (REST) split it:
  * phase 1 zeroes the queue and computes the first head_groups tile groups -- pgasr_gemm_x3w_feed_head_items(N, K, head_groups)
  * work items, one per workgroup, no XCD mask -- and is meant for the SWEEP'S OWN stream, in front of the sweep launch, so
@@ -570,6 +576,10 @@ int pgasr_attention_ctx(const float* dec, const float* enc, int NQ, int B, int T
  * Forward only, like the reference's decoder. */
 int pgasr_lstm_cell_f32(const float* gh, const float* xp, float* c, float* h, float* h_out, int B, int H, void* stream);
 
+/* Column sums of X (rows x cols, leading dim ld >= cols) -> out[cols] (and out2[cols] if non-NULL): the bias gradients.
+ * accumulate != 0 adds to out / out2.  Rows are summed in blocks of 512 (four interleaved chains each), the blocks in index order:
+ * deterministic.  Null X / out, rows or cols < 1, ld < cols: PGASR_ERR_INVALID_ARG; workspace NULL or below
+ * pgasr_colsum_workspace_bytes: PGASR_ERR_WORKSPACE; both before any launch. */
 size_t pgasr_colsum_workspace_bytes(int rows, int cols);
 int pgasr_colsum_f32(const float* X, int rows, int cols, int ld, float* out, float* out2, int accumulate,
                      void* workspace, size_t workspace_bytes, void* stream);

@@ -774,6 +774,8 @@ extern "C" int pgasr_gemm_f32(int transA, int transB, int M, int N, int K, float
     if (norm_operand < 0 || norm_operand > 2 || (norm_operand && (!shift || !scale))) return PGASR_ERR_INVALID_ARG;
     if (act < 0 || act > 1 || precision < 0 || precision > 2) return PGASR_ERR_INVALID_ARG;
     if ((splitk > 1 || sum_batches) && dact_y) return PGASR_ERR_INVALID_ARG;
+    // a leading dimension shorter than the row it strides makes rows overlap: never a layout, always a mistake
+    if (lda < (transA ? M : K) || ldb < (transB ? K : N) || ldc < N) return PGASR_ERR_INVALID_ARG;
     GemmArgs g;
     g.A = A; g.B = B; g.C = C; g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
     g.sA = strideA; g.sB = strideB; g.sC = strideC; g.batch = batch; g.splitk = splitk;
@@ -783,7 +785,11 @@ extern "C" int pgasr_gemm_f32(int transA, int transB, int M, int N, int K, float
     g.kper = kper;
     g.alpha = alpha; g.bias = bias; g.bias2 = bias2; g.act = act; g.slope = slope; g.accumulate = accumulate;
     g.dact_y = dact_y; g.norm_operand = norm_operand; g.shift = shift; g.scale = scale; g.partial = nullptr;
-    g.wide = (((size_t)(M - 1) * ldc + N) * 4 >= ((size_t)1 << 32) || (size_t)M * N * 4 >= ((size_t)1 << 32)) ? 1 : 0;
+    // The fast epilogue forms 32-bit byte offsets for EVERY row of the last 128-row tile and leaves rows >= M to the buffer
+    // range check: decided on M alone, the padded rows of a span just under 4 GiB wrap modulo 2^32 to offsets INSIDE the
+    // buffer and are stored.  So both terms (C's span, a partial slab) count the rows the tiles touch.
+    const size_t Mp = ((size_t)M + BM - 1) / BM * BM;
+    g.wide = (((Mp - 1) * ldc + N) * 4 >= ((size_t)1 << 32) || Mp * N * 4 >= ((size_t)1 << 32)) ? 1 : 0;
     return gemm_launch(g, transA, transB, sum_batches, precision, xcc_busy, workspace, workspace_bytes, (hipStream_t)stream);
 }
 

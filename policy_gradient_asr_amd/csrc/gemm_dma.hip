@@ -676,7 +676,9 @@ extern "C" int pgasr_gemm_x3w_f32(int M, int N, int K, const float* A, int lda, 
         return PGASR_ERR_UNSUPPORTED;
     const unsigned gy = (unsigned)((M + TM - 1) / TM);
     if (gy > 65535u) return PGASR_ERR_UNSUPPORTED;
-    if ((size_t)M * ldc * 4 >= ((size_t)1 << 32)) return PGASR_ERR_UNSUPPORTED;      // buffer-addressed epilogue (callers fall back to pgasr_gemm_f32)
+    // buffer-addressed epilogue (callers fall back to pgasr_gemm_f32): all three tile structures are 256 rows high and form 32-bit
+    // offsets for every row of the last tile, so the bound is on the PADDED row count (a padded row that wraps lands inside C)
+    if ((size_t)gy * TM * ldc * 4 >= ((size_t)1 << 32)) return PGASR_ERR_UNSUPPORTED;
     if (N % 256 == 0 && x3w_tile_mode(false) == 2 && (size_t)M * lda * 4 < ((size_t)1 << 32)) {
         PgasrX3cArgs a{A, Whi, Wlo, C, M, N, K, lda, ldc, bias, dact_y, slope, 0, nullptr, nullptr, nullptr, 0, 0, 0, 1, 0, nullptr, nullptr};
         return pgasr_internal_x3c_launch(a, (hipStream_t)stream);
@@ -719,7 +721,7 @@ extern "C" int pgasr_gemm_x3w_feed_f32(int M, int N, int K, const float* A, int 
     if (!workspace || workspace_bytes < 1024) return PGASR_ERR_WORKSPACE;
     if ((K % TK) || (N % (2 * TN)) || (lda & 3) || (((size_t)A) & 15) || (((size_t)Whi) & 15) || (((size_t)Wlo) & 15))
         return PGASR_ERR_UNSUPPORTED;
-    if ((size_t)M * ldc * 4 >= ((size_t)1 << 31)) return PGASR_ERR_UNSUPPORTED;      // buffer-addressed stores
+    if ((size_t)((M + TM - 1) / TM) * TM * ldc * 4 >= ((size_t)1 << 31)) return PGASR_ERR_UNSUPPORTED;      // buffer-addressed stores, whole 256-row tiles
     hipStream_t st = (hipStream_t)stream;
     if (pgasr_gemm_x3w_feed_col_tiles(N) == N / (2 * w256::TN) && x3w_tile_mode(true) == 2 && (size_t)M * lda * 4 < ((size_t)1 << 32)) {
         const int mt2 = (M + 255) / 256, nt2 = N / 256;

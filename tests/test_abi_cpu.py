@@ -117,5 +117,7 @@ def test_host_side_shape_rules():
     assert hipops.gemm_x3w_ok(2047 * 256, 2048, 512, planes=3)                  # 2047 tiles x 2048 x 4 B < 4 GiB
     assert not hipops.gemm_x3w_ok(2047 * 256 + 1, 2048, 512, planes=3)          # M itself is below the bound, its last tile's rows are not
     assert not hipops.gemm_x3w_ok(524287, 2048, 512, planes=3) and hipops.gemm_x3w_ok(524287, 256, 512, planes=3)
+    # the two-plane (bf16x3) LDS-DMA kernels: 256-row tiles and the same 32-bit epilogue offsets, so the same padded-row rule
+    assert hipops.gemm_x3w_ok(2047 * 256, 2048, 512, planes=2) and not hipops.gemm_x3w_ok(2047 * 256 + 1, 2048, 512, planes=2)
     assert hipops.lstm_wgrads_ok(200, 16, 512, 3) and not hipops.lstm_wgrads_ok(200, 16, 512, 2)
     assert hipops.lstm_wgrads_ok(200, 32, 512, 2) and not hipops.lstm_wgrads_ok(200, 24, 512, 3) and not hipops.lstm_wgrads_ok(1, 32, 512, 3)
