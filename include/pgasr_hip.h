@@ -51,7 +51,8 @@ typedef enum pgasr_status {
  * over them (pgasr_mwer_weights, pgasr_ctc_grad_from_lattices_nbest), and the KL penalty towards a frozen reference policy
  * (pgasr_frame_kl, pgasr_ctc_grad_from_lattice_kl, pgasr_ctc_grad_from_lattice_multi_kl, pgasr_ctc_grad_from_lattices_seq_kl),
  * sample-rate conversion / speed perturbation (pgasr_resample), and minimum-Bayes-risk decoding over N-best lists
- * (pgasr_nbest_pair_dist, pgasr_mbr_select). */
+ * (pgasr_nbest_pair_dist, pgasr_mbr_select), and waveform augmentation (pgasr_reverb_limits, pgasr_reverb, pgasr_wave_power,
+ * pgasr_wave_mix). */
 #define PGASR_ABI_VERSION 7
 
 int pgasr_abi_version(void);
@@ -969,6 +970,54 @@ int pgasr_resample(const float* wave, int in_stride, const int32_t* n_in, int B,
                    const int32_t* ratio_idx /* NULL: all 0 */, int n_ratios, const int32_t* ratio_desc /* host */,
                    const float* tables, const int32_t* bases, float* out, int out_stride, int32_t* n_out /* written */,
                    void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * A0-WA  Waveform augmentation on the device (csrc/wave_aug.hip; in numpy: tests/wave_aug_ref.py): convolution with a room impulse
+ *   response and additive noise at a drawn signal-to-noise ratio (the Kaldi / ESPnet "noise + RIR" recipe; Ko et al., ICASSP 2017).
+ *   Waveforms are fp32 rows (B, stride) with lengths n (B) int32 on the device, clamped to [0, stride]; every intermediate is fp64.
+ *   A product of two fp32 numbers is exact in fp64, so a fused multiply-add and a multiply followed by an add give the same bits.
+ *   Bit statements hold for finite samples and taps.  Each call is launches on `stream` only: no workspace, no atomics, no host
+ *   synchronisation, 16-byte accesses where the stride is a multiple of 4 and the bases are 16-byte aligned; two runs give the same bits.
+ *
+ * pgasr_reverb: rirs (n_rirs, rir_stride) fp32; row r has K = rir_len[r] taps (clamped to [0, min(rir_stride, max_taps)]) and its
+ *   direct path at d = rir_delay[r] (clamped to [0, K-1]): the first index of max |h|, found by whoever builds the bank.
+ *   With r = rir_idx[b] in [0, n_rirs), for 0 <= i < n_b:
+ *        out[b, i] = fp32( sum_{k = 0 .. K-1} fp64(h[k]) * fp64(wave[b, i + d - k]) )
+ *   summed in ascending k in an fp64 accumulator that starts at +0.0; a term whose sample index lies outside [0, n_b) is skipped and
+ *   the sample never read.  The output is as long as the input: out[b, i] = 0.0f for n_b <= i < stride.  A row with rir_idx[b]
+ *   outside [0, n_rirs) is copied bit for bit (zero beyond n_b).  out must not be wave (PGASR_ERR_INVALID_ARG, as are a NULL pointer
+ *   and B / stride / rir_stride / n_rirs < 1).  A workgroup computes a tile of `tile` outputs and stages `chunk` taps at a time:
+ *   pgasr_reverb_limits reports both and max_taps (>= 16000: one second at 16 kHz); any of its pointers may be NULL.
+ *
+ * pgasr_wave_power: power[b] = sum_{i < n_b} fp64(src[row_b, (start_b + i) mod period_b])^2, fp64, in a fixed order that depends on
+ *   n_b alone: the value does not depend on what else is in the batch.  src (src_rows, src_stride) fp32.  row NULL: row_b = b (then
+ *   src_rows >= B); period NULL: no wrap -- start must be NULL too, period_b = src_stride and n_b is clamped to it; else period_b is
+ *   clamped to src_stride, start_b is reduced mod period_b, and n_b may exceed period_b (the segment wraps, several times if need be).
+ *   0 where n_b <= 0, row_b lies outside [0, src_rows) or period_b < 1.  power: (B) fp64, written.
+ *
+ * pgasr_wave_mix: for i < n_b
+ *        out[b, i] = fp32( fp64(a_b) * fp64(wave[b, i]) + fp64(g_b) * fp64(noise[r_b, (s_b + i) mod m_b]) ),   0.0f for n_b <= i < stride,
+ *   r_b = noise_idx[b], m_b = noise_len[r_b] (clamped to noise_stride), s_b = noise_start[b] mod m_b (noise_start NULL: 0).  Where
+ *   g_b = 0 the noise is not read and the term is dropped: out = fp32(fp64(a_b) * fp64(wave)), with a_b = 1 the bits of the input.
+ *   A row takes no noise (g_b = 0) where noise is NULL, r_b lies outside [0, noise_rows), m_b < 1 or n_b < 1.
+ *   gains (B, 2) fp32 holds (a_b, g_b).  gains_given != 0: they are read (g_b still 0 for a row that takes no noise).  Else they
+ *   are formed from p_dry, p_wet, p_noise and amp (each (B) fp64; amp_b = 10^(-snr_b / 20), computed on the host) and written:
+ *        a_b = fp32( sqrt(p_dry / p_wet) )                     the dry signal's level, restored after the reverberation;
+ *                                                               1 where a power is 0 or the result is no finite positive fp32
+ *        g_b = fp32( amp_b * sqrt((fp64(a_b)^2 * p_wet) / p_noise) )    0 where a power or amp_b is 0, the row takes no noise, or the
+ *                                                               result is no finite positive fp32: never inf or NaN
+ *   every fp64 operation rounded once, in the order written.  The gains are fp32 so that a sum of squares whose last bits differ
+ *   does not change the output (the idiom of SpecAugment's row mean).  out may equal wave.
+ * ---------------------------------------------------------------------------------------- */
+int pgasr_reverb_limits(int* tile, int* chunk, int* max_taps);
+int pgasr_reverb(const float* wave, int stride, const int32_t* n, int B, const float* rirs, int rir_stride, int n_rirs,
+                 const int32_t* rir_len, const int32_t* rir_delay, const int32_t* rir_idx, float* out /* not wave */, void* stream);
+int pgasr_wave_power(const float* src, int src_stride, int src_rows, const int32_t* n, int B, const int32_t* row /* NULL: b */,
+                     const int32_t* start /* NULL: 0 */, const int32_t* period /* NULL: no wrap */, double* power, void* stream);
+int pgasr_wave_mix(const float* wave, int stride, const int32_t* n, int B, const double* p_dry, const double* p_wet,
+                   const double* p_noise, const double* amp, const float* noise /* NULL: none */, int noise_stride, int noise_rows,
+                   const int32_t* noise_len, const int32_t* noise_idx, const int32_t* noise_start, float* gains /* (B,2) */,
+                   int gains_given, float* out /* may equal wave */, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Elementwise pieces of the train step.

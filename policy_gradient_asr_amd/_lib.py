@@ -111,6 +111,11 @@ SIGNATURES = {
                                      C.c_float, C.c_int, C.c_ulonglong, C.c_uint, c_f32p, c_i32p, c_ptr]),
     "pgasr_resample": (C.c_int, [c_f32p, C.c_int, c_i32p, C.c_int, c_i32p, C.c_int, c_ptr, c_f32p, c_i32p, c_f32p, C.c_int, c_i32p,
                                  c_ptr]),
+    "pgasr_reverb_limits": (C.c_int, [C.POINTER(C.c_int)] * 3),
+    "pgasr_reverb": (C.c_int, [c_f32p, C.c_int, c_i32p, C.c_int, c_f32p, C.c_int, C.c_int, c_i32p, c_i32p, c_i32p, c_f32p, c_ptr]),
+    "pgasr_wave_power": (C.c_int, [c_f32p, C.c_int, C.c_int, c_i32p, C.c_int, c_i32p, c_i32p, c_i32p, c_ptr, c_ptr]),
+    "pgasr_wave_mix": (C.c_int, [c_f32p, C.c_int, c_i32p, C.c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_f32p, C.c_int, C.c_int,
+                                 c_i32p, c_i32p, c_i32p, c_f32p, C.c_int, c_f32p, c_ptr]),
     "pgasr_stream_copy": (C.c_int, [c_ptr, c_ptr, C.c_ulonglong, C.c_int, c_ptr]),
     "pgasr_adam_step": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, C.c_ulonglong, C.c_int, C.c_float, C.c_float,
                                   C.c_float, C.c_float, C.c_float, c_i32p, c_i32p, c_i32p, c_ptr]),

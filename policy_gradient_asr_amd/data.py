@@ -27,7 +27,7 @@ _front_end = {}
 
 
 def extract_feats(batch, device="cuda:0", features="mfcc", keep_on_device=False, target_rate=None, speed_perturb=None, seed=0,
-                  offset=0):
+                  offset=0, wave_augment=None):
     """data.py:44-79: MFCC(40) + delta + delta-delta per utterance, zero padded to (B,120,Tmax) + (B,1,Tmax) masks.
     An item carries precomputed features ("feat", (F,T)), a waveform tensor ("wave"), or a path ("aud", read with
     torchaudio where it exists, else as RIFF WAV).  Waveforms go through the GPU front end: ``features`` = "mfcc"
@@ -38,14 +38,23 @@ def extract_feats(batch, device="cuda:0", features="mfcc", keep_on_device=False,
     behaviour) or the front end's rate, 16000: a waveform at another rate -- the file's, or the item's "rate" beside "wave" -- is
     converted on the device first (features.Resample); an item without a rate is taken to be at the target.
     speed_perturb: None or a features.SpeedPerturb: every waveform is resampled by the factor drawn for (seed, offset, the item's
-    "idx": its index in the corpus, which ``Indexed`` adds); with a rate conversion it is one pass over the samples."""
+    "idx": its index in the corpus, which ``Indexed`` adds); with a rate conversion it is one pass over the samples.
+    wave_augment: None or a features.WaveAugment: noise and reverberation of every waveform, drawn for (seed, offset, the item's
+    "idx"), after the resampling and in front of the framing."""
     if all("feat" in inst for inst in batch):
         if speed_perturb is not None:
             raise ValueError("speed perturbation resamples waveforms: these items carry precomputed features")
+        if wave_augment is not None:
+            raise ValueError("noise and reverberation augment waveforms: these items carry precomputed features")
         feat, fmask = pad_feats([inst["feat"] for inst in batch])
         return (feat.to(device), fmask.to(device)) if keep_on_device else (feat, fmask)
     if any("feat" in inst for inst in batch):
         raise ValueError("a batch mixes precomputed features and waveforms")
+    wave_aug = None
+    if wave_augment is not None:
+        if any("idx" not in inst for inst in batch):
+            raise ValueError('noise and reverberation draw by utterance id: every item needs an "idx" (wrap the dataset in data.Indexed)')
+        wave_aug = wave_augment.bind([int(inst["idx"]) for inst in batch], seed, offset)
     from .features import LogMel, MFCCDeltas, read_wav
     waves, rates = [], []
     for inst in batch:
@@ -67,14 +76,17 @@ def extract_feats(batch, device="cuda:0", features="mfcc", keep_on_device=False,
     if fe is None:
         fe = _front_end[(str(device), features)] = MFCCDeltas(device) if features == "mfcc" else LogMel(80, device)
     if target_rate is None and speed_perturb is None:
-        feat, fmask = fe(waves)
+        feat, fmask = fe(waves) if wave_aug is None else fe(waves, wave_aug=wave_aug)
     else:
         speed = None
         if speed_perturb is not None:
             if any("idx" not in inst for inst in batch):
                 raise ValueError('speed perturbation draws by utterance id: every item needs an "idx" (wrap the dataset in data.Indexed)')
             speed = speed_perturb.ratios([int(inst["idx"]) for inst in batch], seed, offset)
-        feat, fmask = fe(waves, rates=rates, target_rate=target_rate, speed=speed)
+        if wave_aug is None:
+            feat, fmask = fe(waves, rates=rates, target_rate=target_rate, speed=speed)
+        else:
+            feat, fmask = fe(waves, rates=rates, target_rate=target_rate, speed=speed, wave_aug=wave_aug)
     return (feat, fmask) if keep_on_device else (feat.cpu(), fmask.cpu())
 
 
@@ -87,12 +99,15 @@ def encode_trans(batch):
     return out, (out > 0).to(torch.int64)
 
 
-def collate_custom(batch, device=None, features="mfcc", target_rate=None, speed_perturb=None, seed=0, offset=0):
+def collate_custom(batch, device=None, features="mfcc", target_rate=None, speed_perturb=None, seed=0, offset=0, wave_augment=None):
     """data.py:107-116.  device = None: the reference's contract -- everything on the CPU.  device = a GPU: "feat" / "fmask" stay
     where the front end computed them and "trans" / "tmask" are put beside them, so ``PolicyGradientTrainer.step`` consumes the
     batch without the features ever visiting the host (use ``functools.partial(collate_custom, device=...)`` as collate_fn).
-    target_rate / speed_perturb / seed / offset: sample-rate conversion and speed perturbation of waveform items (``extract_feats``)."""
+    target_rate / speed_perturb / wave_augment / seed / offset: sample-rate conversion, speed perturbation, noise and reverberation of
+    waveform items (``extract_feats``)."""
     aug = {"target_rate": target_rate, "speed_perturb": speed_perturb, "seed": seed, "offset": offset}
+    if wave_augment is not None:
+        aug["wave_augment"] = wave_augment
     if device is None:
         feats, fmasks = extract_feats(batch, features=features, **aug)
         trans, tmasks = encode_trans(batch)

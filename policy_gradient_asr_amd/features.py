@@ -50,10 +50,12 @@ class _FrontEnd:
         self.dft, self.fb, self.dct = _constants(self.device, self.n_mels)
         self._resample = None
 
-    def mel_db(self, waves, rates=None, target_rate=None, speed=None):
+    def mel_db(self, waves, rates=None, target_rate=None, speed=None, wave_aug=None):
         """rates / target_rate: the items' sample rates and the rate the front end works at (16000) -- an item at another rate is
         converted on the device first (Resample); speed: one resampling ratio (L, M) per item (SpeedPerturb.ratios), or None.  Both
-        on one item compose into one ratio and one pass.  All three None: no resampling code runs."""
+        on one item compose into one ratio and one pass.  All three None: no resampling code runs.
+        wave_aug: None, or a callable (wave (B, stride), n (B) int32) -> wave of the same shape (``WaveAugment.bind``): noise and
+        reverberation of the packed batch, after the resampling and in front of the framing.  None: no such code runs."""
         lib = _lib.load()
         dev = self.device
         B = len(waves)
@@ -73,6 +75,13 @@ class _FrontEnd:
                 raise ValueError("reflect-centred framing needs more than n_fft/2 = 200 samples per utterance (after resampling)")
             nmax = wave.stride(0)          # the row stride: the resampler's buffer may be wider than the longest result
         n_samples = torch.tensor(ns, dtype=torch.int32, device=dev)
+        if wave_aug is not None:
+            wave = wave.contiguous()       # the resampler's result may be a view of a wider buffer
+            nmax = wave.shape[1]
+            aug = wave_aug(wave, n_samples)
+            if tuple(aug.shape) != tuple(wave.shape) or aug.dtype != torch.float32 or not aug.is_contiguous():
+                raise ValueError("wave_aug must return a contiguous fp32 batch of the shape it was given")
+            wave = aug
         nf = [1 + n // HOP for n in ns]
         n_frames = torch.tensor(nf, dtype=torch.int32, device=dev)
         Tmax = max(nf)
@@ -93,15 +102,16 @@ class _FrontEnd:
 
 class MFCCDeltas(_FrontEnd):
     """waves: list of 1-D float tensors (any device; moved to ``device``) -> (feat (B,120,Tmax), fmask (B,1,Tmax)).
-    rates / target_rate / speed: optional resampling in front of the framing (``_FrontEnd.mel_db``)."""
+    rates / target_rate / speed: optional resampling in front of the framing; wave_aug: optional noise / reverberation behind it
+    (``_FrontEnd.mel_db``)."""
 
     def __init__(self, device="cuda:0"):
         super().__init__(device, N_MELS)
 
-    def __call__(self, waves, rates=None, target_rate=None, speed=None):
+    def __call__(self, waves, rates=None, target_rate=None, speed=None, wave_aug=None):
         lib = _lib.load()
         dev = self.device
-        mel, n_frames, B, Tmax = self.mel_db(waves, rates, target_rate, speed)
+        mel, n_frames, B, Tmax = self.mel_db(waves, rates, target_rate, speed, wave_aug)
         rows = B * Tmax
         st = torch.cuda.current_stream().cuda_stream
         mfcc = torch.empty(rows, N_MFCC, dtype=torch.float32, device=dev)
@@ -121,9 +131,9 @@ class LogMel(_FrontEnd):
     def __init__(self, n_mels=80, device="cuda:0"):
         super().__init__(device, n_mels)
 
-    def __call__(self, waves, rates=None, target_rate=None, speed=None):
+    def __call__(self, waves, rates=None, target_rate=None, speed=None, wave_aug=None):
         lib = _lib.load()
-        mel, n_frames, B, Tmax = self.mel_db(waves, rates, target_rate, speed)
+        mel, n_frames, B, Tmax = self.mel_db(waves, rates, target_rate, speed, wave_aug)
         feat = torch.empty(B, self.n_mels, Tmax, dtype=torch.float32, device=self.device)
         fmask = torch.empty(B, 1, Tmax, dtype=torch.float32, device=self.device)
         _lib.check(lib.pgasr_feat_stack(mel.data_ptr(), n_frames.data_ptr(), B, Tmax, self.n_mels, feat.data_ptr(), fmask.data_ptr(),
@@ -447,6 +457,224 @@ class SpeedPerturb:
             p, q = self.factors[self.draw(u, seed, offset)]
             out.append((q, p))
         return out
+
+
+REVERB_MAX_TAPS = hipops.REVERB_MAX_TAPS
+
+
+def _pack_bank(waves, rates, target_rate, device, what):
+    """Waveforms -> (wave (R, stride) fp32 on the device, lengths): packed once, brought to target_rate with ``Resample``."""
+    waves = list(waves)
+    if not waves:
+        raise ValueError(f"{what}: no waveforms")
+    if any(int(w.numel()) < 1 for w in waves):
+        raise ValueError(f"{what}: an empty waveform")
+    if rates is not None and len(rates) != len(waves):
+        raise ValueError(f"{what}: {len(waves)} waveforms but {len(rates)} rates")
+    wave, lengths = Resample(device)(waves, rates, target_rate)
+    return wave.contiguous(), [int(v) for v in lengths]
+
+
+class NoiseBank:
+    """Noise recordings for ``WaveAugment``, packed on the device once: ``NoiseBank(waves, rates=None, target_rate=16000, device=...)``;
+    waves: 1-D float tensors, rates: one sample rate per item (None: at the target).  ``wave`` (R, stride) fp32, ``lengths`` (python
+    ints), ``len_dev`` (R) int32.  A recording shorter than an utterance is repeated cyclically from the drawn start."""
+
+    def __init__(self, waves, rates=None, target_rate=SAMPLE_RATE, device="cuda:0"):
+        self.device = torch.device(device)
+        self.wave, self.lengths = _pack_bank(waves, rates, target_rate, self.device, "NoiseBank")
+        self.len_dev = torch.tensor(self.lengths, dtype=torch.int32, device=self.device)
+
+    def __len__(self):
+        return len(self.lengths)
+
+
+class RirBank:
+    """Room impulse responses for ``WaveAugment``, packed on the device once like ``NoiseBank``; each is cut to ``REVERB_MAX_TAPS``
+    taps, scaled to unit energy (fp64 sum of squares, one division per tap in fp64, rounded to fp32) and its direct path -- the first
+    index of max |h| -- is found here, on the host: ``wave`` (R, stride) fp32, ``lengths``, ``delays`` (python ints), ``len_dev``,
+    ``delay_dev`` (R) int32.  An all-zero response is refused."""
+
+    def __init__(self, waves, rates=None, target_rate=SAMPLE_RATE, device="cuda:0"):
+        import numpy as np
+        self.device = torch.device(device)
+        wave, lengths = _pack_bank(waves, rates, target_rate, self.device, "RirBank")
+        h = wave.cpu().numpy()[:, :REVERB_MAX_TAPS].copy()
+        self.lengths = [min(n, REVERB_MAX_TAPS) for n in lengths]
+        self.delays = []
+        for r, K in enumerate(self.lengths):
+            h[r, K:] = 0.0
+            e = float(np.sum(h[r, :K].astype(np.float64) ** 2))
+            if not (e > 0.0 and math.isfinite(e)):
+                raise ValueError(f"RirBank: impulse response {r} is all zero or not finite")
+            h[r, :K] = (h[r, :K].astype(np.float64) / math.sqrt(e)).astype(np.float32)
+            self.delays.append(int(np.argmax(np.abs(h[r, :K]))))
+        pad = -h.shape[1] % 4
+        if pad:
+            h = np.concatenate((h, np.zeros((h.shape[0], pad), dtype=np.float32)), axis=1)
+        self.wave = torch.from_numpy(np.ascontiguousarray(h)).to(self.device)
+        self.len_dev = torch.tensor(self.lengths, dtype=torch.int32, device=self.device)
+        self.delay_dev = torch.tensor(self.delays, dtype=torch.int32, device=self.device)
+
+    def __len__(self):
+        return len(self.lengths)
+
+
+class WaveAugment:
+    """Additive noise at a drawn signal-to-noise ratio and reverberation of waveforms on the device (the Kaldi / ESPnet "noise + RIR"
+    recipe; include/pgasr_hip.h, A0-WA): ``WaveAugment(noise=None, snr_db=(5.0, 20.0), noise_prob=1.0, rir=None, rir_prob=0.5)`` with a
+    ``NoiseBank`` and / or a ``RirBank`` (``draws`` needs only their ``lengths``).  A reverberated utterance is brought back to its dry
+    level; the noise -- a segment of one recording from a drawn start, repeated cyclically -- is scaled to the drawn SNR against it.
+    The draws of the utterance with global index u are a function of (seed, offset, u) only, made on the host from two Philox4x32-10
+    blocks, key = (seed lo32, seed hi32) (counter word 2: the samplers hold 0 and 1, SpecAugment 2 and 3, speed perturbation 4):
+        w = philox4x32_10(ctr = (u, offset, 5, 0)):  noise applies iff (w0 >> 8) < round(noise_prob * 2^24);  recording r = ((w1 >> 8) * Rn) >> 24;
+            snr = lo + (hi - lo) * (w2 >> 8) / 2^24 dB;  start = ((w3 >> 8) * m_r) >> 24,  m_r the recording's length
+        w = philox4x32_10(ctr = (u, offset, 6, 0)):  reverberation applies iff (w0 >> 8) < round(rir_prob * 2^24);  response ((w1 >> 8) * Rr) >> 24
+    so a rank, a shard or a micro-batch augments what one process holding the whole batch augments.  An id < 0 (padding) is never
+    augmented.  Immutable; ``state()`` for checkpoints (the policy and the banks' lengths).
+    ``aug.draws(ids, seed, offset)`` -> dict of host arrays; ``aug(wave, n, ids, seed, offset)`` -> the augmented (B, stride) batch."""
+    NOISE_DOMAIN, RIR_DOMAIN = 5, 6
+    FIELDS = ("noise", "snr_db", "noise_prob", "rir", "rir_prob")
+    __slots__ = FIELDS
+
+    def __init__(self, noise=None, snr_db=(5.0, 20.0), noise_prob=1.0, rir=None, rir_prob=0.5):
+        import numbers
+        set_ = lambda k, v: object.__setattr__(self, k, v)
+        for k, bank in (("noise", noise), ("rir", rir)):
+            if bank is not None:
+                lengths = getattr(bank, "lengths", None)
+                if not lengths or any(int(v) < 1 for v in lengths):
+                    raise ValueError(f"WaveAugment: {k} must be None or a bank with positive lengths")
+            set_(k, bank)
+        if noise is None and rir is None:
+            raise ValueError("WaveAugment needs a noise bank, an impulse-response bank or both")
+        if isinstance(snr_db, numbers.Real) and not isinstance(snr_db, bool):
+            snr_db = (snr_db, snr_db)
+        try:
+            lo, hi = (float(v) for v in snr_db)
+        except (TypeError, ValueError):
+            raise TypeError(f"WaveAugment: snr_db must be a number or a (low, high) pair in dB (got {snr_db!r})") from None
+        if not (math.isfinite(lo) and math.isfinite(hi) and lo <= hi and -200.0 <= lo and hi <= 200.0):
+            raise ValueError(f"WaveAugment: snr_db must be finite, low <= high, within +-200 dB (got {snr_db!r})")
+        set_("snr_db", (lo, hi))
+        for k, v in (("noise_prob", noise_prob), ("rir_prob", rir_prob)):
+            if isinstance(v, bool) or not isinstance(v, numbers.Real):
+                raise TypeError(f"WaveAugment: {k} must be a real number (got {v!r})")
+            if not 0.0 <= float(v) <= 1.0:
+                raise ValueError(f"WaveAugment: {k} must lie in [0, 1] (got {v!r})")
+            set_(k, float(v))
+
+    def __setattr__(self, k, v):
+        raise AttributeError("WaveAugment is immutable")
+
+    __delattr__ = __setattr__
+
+    def state(self):
+        return {"snr_db": list(self.snr_db), "noise_prob": self.noise_prob, "rir_prob": self.rir_prob,
+                "noise_lengths": None if self.noise is None else [int(v) for v in self.noise.lengths],
+                "rir_lengths": None if self.rir is None else [int(v) for v in self.rir.lengths]}
+
+    @classmethod
+    def coerce(cls, value, what="wave_augment"):
+        """None or a WaveAugment -> itself; anything else: TypeError (the banks live on the device: a dict cannot rebuild them)."""
+        if value is None or isinstance(value, cls):
+            return value
+        raise TypeError(f"{what} must be None or a features.WaveAugment (got {value!r})")
+
+    def __eq__(self, other):
+        return isinstance(other, WaveAugment) and self.state() == other.state() and self.noise is other.noise and self.rir is other.rir
+
+    def __hash__(self):
+        return hash((self.snr_db, self.noise_prob, self.rir_prob, id(self.noise), id(self.rir)))
+
+    def __repr__(self):
+        return "WaveAugment(noise={}, snr_db={}, noise_prob={}, rir={}, rir_prob={})".format(
+            None if self.noise is None else f"<{len(self.noise.lengths)} recordings>", self.snr_db, self.noise_prob,
+            None if self.rir is None else f"<{len(self.rir.lengths)} responses>", self.rir_prob)
+
+    @staticmethod
+    def _noise_from_words(w, prob, lengths, snr_db):
+        """(apply, recording, snr in dB, start) from one block's four words: integer arithmetic except the SNR."""
+        apply = (w[0] >> 8) < int(round(prob * (1 << 24)))
+        r = ((w[1] >> 8) * len(lengths)) >> 24
+        snr = snr_db[0] + (snr_db[1] - snr_db[0]) * (w[2] >> 8) / float(1 << 24)
+        start = ((w[3] >> 8) * int(lengths[r])) >> 24
+        return apply, r, snr, start
+
+    @staticmethod
+    def _rir_from_words(w, prob, n_rirs):
+        return (w[0] >> 8) < int(round(prob * (1 << 24))), ((w[1] >> 8) * n_rirs) >> 24
+
+    def draws(self, ids, seed, offset):
+        """Host arrays, one entry per id: noise_idx, noise_start, rir_idx (int32; -1 / 0 / -1 where nothing applies), snr_db and
+        amp = 10^(-snr / 20) (float64; 0 where no noise applies)."""
+        import numpy as np
+        seed = int(seed) & (2 ** 64 - 1)
+        key = (seed & 0xFFFFFFFF, seed >> 32)
+        ids = [int(u) for u in ids]
+        B = len(ids)
+        out = {"noise_idx": np.full(B, -1, dtype=np.int32), "noise_start": np.zeros(B, dtype=np.int32),
+               "rir_idx": np.full(B, -1, dtype=np.int32), "snr_db": np.zeros(B, dtype=np.float64), "amp": np.zeros(B, dtype=np.float64)}
+        for b, u in enumerate(ids):
+            if u < 0:
+                continue
+            if self.noise is not None:
+                w = _philox4x32_10((u, int(offset), self.NOISE_DOMAIN, 0), key)
+                apply, r, snr, start = self._noise_from_words(w, self.noise_prob, self.noise.lengths, self.snr_db)
+                if apply:
+                    out["noise_idx"][b], out["noise_start"][b], out["snr_db"][b] = r, start, snr
+                    out["amp"][b] = 10.0 ** (-snr / 20.0)
+            if self.rir is not None:
+                w = _philox4x32_10((u, int(offset), self.RIR_DOMAIN, 0), key)
+                apply, r = self._rir_from_words(w, self.rir_prob, len(self.rir.lengths))
+                if apply:
+                    out["rir_idx"][b] = r
+        return out
+
+    def bind(self, ids, seed, offset):
+        """The callable (wave, n) -> wave the front ends take as ``wave_aug``: this policy on these ids, in place where it can."""
+        ids = [int(u) for u in ids]
+        return lambda wave, n: self(wave, n, ids, seed, offset, out=wave)
+
+    def __call__(self, wave, n, ids, seed, offset, out=None, want_gains=False):
+        """wave (B, stride) fp32 on the device, zero or anything beyond each length; n: (B) int32 on the device (or python ints);
+        ids: one global utterance index per row (< 0: padding, copied).  Returns the augmented batch, zero beyond each length -- a new
+        tensor, or ``out`` (``out=wave``: in place where no row is reverberated) -- and with ``want_gains`` the (B, 2) fp32 gains too.
+        The chain -- reverberation, three powers, gains, mix -- runs on the current stream without a host synchronisation."""
+        if not isinstance(wave, torch.Tensor) or not wave.is_cuda:
+            raise _lib.PgasrError("WaveAugment runs on the MI355X only; there is no CPU path")
+        dev = wave.device
+        if not isinstance(n, torch.Tensor):
+            n = torch.tensor([int(v) for v in n], dtype=torch.int32)
+        n = n.to(device=dev, dtype=torch.int32).contiguous()
+        if isinstance(ids, torch.Tensor):
+            ids = ids.tolist()
+        d = self.draws(ids, seed, offset)
+        if len(d["rir_idx"]) != wave.shape[0]:
+            raise ValueError(f"{wave.shape[0]} waveforms but {len(d['rir_idx'])} ids")
+        # the draws travel in ONE pinned buffer and one asynchronous copy: amp (fp64) in front, then the three int32 rows
+        B = wave.shape[0]
+        host = torch.empty(5 * B, dtype=torch.int32, pin_memory=True)
+        hn = host.numpy()
+        hn[:2 * B].view("float64")[:] = d["amp"]
+        hn[2 * B:3 * B], hn[3 * B:4 * B], hn[4 * B:] = d["noise_idx"], d["noise_start"], d["rir_idx"]
+        up = host.to(dev, non_blocking=True)
+        amp, nidx, nstart, ridx = up[:2 * B].view(torch.float64), up[2 * B:3 * B], up[3 * B:4 * B], up[4 * B:]
+        p_dry = hipops.wave_power(wave, n)
+        if self.rir is not None and bool((d["rir_idx"] >= 0).any()):
+            wet = hipops.reverb(wave, n, self.rir.wave, self.rir.len_dev, self.rir.delay_dev, ridx,
+                                out=out if (out is not None and out is not wave) else None)
+            p_wet = hipops.wave_power(wet, n)
+            if out is None:
+                out = wet
+        else:
+            wet, p_wet = wave, p_dry
+        if self.noise is not None and bool((d["noise_idx"] >= 0).any()):
+            p_noise = hipops.wave_power(self.noise.wave, n, row=nidx, start=nstart, period=self.noise.len_dev[nidx.clamp(min=0).long()])
+            res, gains = hipops.wave_mix(wet, n, p_dry, p_wet, p_noise, amp, self.noise.wave, self.noise.len_dev, nidx, nstart, out=out)
+        else:
+            res, gains = hipops.wave_mix(wet, n, p_dry, p_wet, out=out)
+        return (res, gains) if want_gains else res
 
 
 def read_wav(path):

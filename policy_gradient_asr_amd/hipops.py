@@ -620,6 +620,118 @@ def resample(wave, n_in, ratios, ratio_idx=None, out=None, n_out=None):
     return out, n_out
 
 
+REVERB_TILE, REVERB_CHUNK, REVERB_MAX_TAPS = 2048, 512, 16384      # csrc/wave_aug.hip (pgasr_reverb_limits)
+
+
+def _rows_i32(t, B, device, what, name):
+    _req(t, torch.int32, name)
+    if t is not None and (t.dim() != 1 or t.numel() != B or t.device != device):
+        raise _lib.PgasrError(f"{what}: {name} must be ({B},) int32 on {device}")
+
+
+def reverb(wave, n, rirs, rir_len, rir_delay, rir_idx, out=None):
+    """Convolution of wave (B, stride) fp32 with room impulse responses (include/pgasr_hip.h, A0-WA): row b, n[b] samples long (n (B)
+    int32 on the device), is filtered with row rir_idx[b] of the bank rirs (R, rir_stride) fp32, rir_len (R) taps, direct path at
+    rir_delay (R) (all int32 on the device); a row with rir_idx[b] < 0 is copied.  The output is as long as the input and zero beyond
+    it.  ``out``: a contiguous fp32 tensor of wave's shape that shares no memory with it.  One launch, no host synchronisation."""
+    lib = _lib.load()
+    _req(wave, torch.float32, "wave"); _req(n, torch.int32, "n"); _req(rirs, torch.float32, "rirs"); _req(out, torch.float32, "out")
+    if wave.dim() != 2 or n.dim() != 1 or n.numel() != wave.shape[0] or n.device != wave.device:
+        raise _lib.PgasrError("reverb wants wave (B, stride) and n (B) on one device")
+    B, stride = wave.shape
+    if rirs.dim() != 2 or rirs.device != wave.device:
+        raise _lib.PgasrError(f"reverb: rirs must be (R, rir_stride) fp32 on {wave.device}")
+    R = rirs.shape[0]
+    _rows_i32(rir_len, R, wave.device, "reverb", "rir_len"); _rows_i32(rir_delay, R, wave.device, "reverb", "rir_delay")
+    _rows_i32(rir_idx, B, wave.device, "reverb", "rir_idx")
+    if rir_len is None or rir_delay is None or rir_idx is None:
+        raise _lib.PgasrError("reverb wants rir_len, rir_delay and rir_idx")
+    if out is None:
+        out = torch.empty_like(wave)
+    elif tuple(out.shape) != (B, stride) or out.device != wave.device:
+        raise _lib.PgasrError(f"reverb: out must be ({B}, {stride}) fp32 on {wave.device}")
+    if out.untyped_storage().data_ptr() == wave.untyped_storage().data_ptr():
+        lo, hi = sorted(((out.data_ptr(), out.numel()), (wave.data_ptr(), wave.numel())))
+        if lo[0] + 4 * lo[1] > hi[0]:
+            raise _lib.PgasrError("reverb: out must not alias wave")
+    with _timed("reverb"):
+        st = lib.pgasr_reverb(_p(wave), stride, _p(n), B, _p(rirs), rirs.shape[1], R, _p(rir_len), _p(rir_delay), _p(rir_idx), _p(out),
+                              _stream())
+    _lib.check(st, "pgasr_reverb")
+    return out
+
+
+def wave_power(src, n, row=None, start=None, period=None, out=None):
+    """power[b] = sum over i < n[b] of src[row[b], (start[b] + i) mod period[b]]^2 in fp64, in a fixed order (A0-WA): (B) fp64 on the
+    device.  src (rows, stride) fp32; n, row, start, period: (B) int32 on the device.  row None: row b; period None: no wrap (start
+    must be None too).  One launch, no host synchronisation."""
+    lib = _lib.load()
+    _req(src, torch.float32, "src"); _req(n, torch.int32, "n"); _req(out, torch.float64, "out")
+    if src.dim() != 2 or n.dim() != 1 or n.device != src.device:
+        raise _lib.PgasrError("wave_power wants src (rows, stride) and n (B) on one device")
+    B = n.numel()
+    for t, name in ((row, "row"), (start, "start"), (period, "period")):
+        _rows_i32(t, B, src.device, "wave_power", name)
+    if row is None and src.shape[0] < B:
+        raise _lib.PgasrError(f"wave_power: src has {src.shape[0]} rows for {B} lengths and no row index")
+    if start is not None and period is None:
+        raise _lib.PgasrError("wave_power: start needs a period")
+    if out is None:
+        out = torch.empty(B, dtype=torch.float64, device=src.device)
+    elif out.dim() != 1 or out.numel() != B or out.device != src.device:
+        raise _lib.PgasrError(f"wave_power: out must be ({B},) fp64 on {src.device}")
+    with _timed("wave_power"):
+        st = lib.pgasr_wave_power(_p(src), src.shape[1], src.shape[0], _p(n), B, _p(row), _p(start), _p(period), _p(out), _stream())
+    _lib.check(st, "pgasr_wave_power")
+    return out
+
+
+def wave_mix(wave, n, p_dry=None, p_wet=None, p_noise=None, amp=None, noise=None, noise_len=None, noise_idx=None, noise_start=None,
+             gains=None, out=None):
+    """out[b, i] = fp32(a_b wave[b, i] + g_b noise[noise_idx[b], (noise_start[b] + i) mod noise_len]) for i < n[b], zero beyond (A0-WA).
+    With ``gains`` (B, 2) fp32 = (a, g) given they are used as they are; else they are formed on the device from the powers p_dry,
+    p_wet, p_noise and amp = 10^(-snr / 20) (each (B) fp64 on the device): a restores the dry level after reverberation, g sets the
+    signal-to-noise ratio.  Returns (out, gains); ``out=wave`` mixes in place.  noise (Rn, noise_stride) fp32, noise_len (Rn),
+    noise_idx / noise_start (B) int32 on the device; a row with noise_idx < 0 takes no noise.  One launch, no host synchronisation."""
+    lib = _lib.load()
+    _req(wave, torch.float32, "wave"); _req(n, torch.int32, "n"); _req(noise, torch.float32, "noise"); _req(out, torch.float32, "out")
+    _req(gains, torch.float32, "gains")
+    if wave.dim() != 2 or n.dim() != 1 or n.numel() != wave.shape[0] or n.device != wave.device:
+        raise _lib.PgasrError("wave_mix wants wave (B, stride) and n (B) on one device")
+    B, stride = wave.shape
+    dev = wave.device
+    given = gains is not None
+    if given:
+        if tuple(gains.shape) != (B, 2) or gains.device != dev:
+            raise _lib.PgasrError(f"wave_mix: gains must be ({B}, 2) fp32 on {dev}")
+    else:
+        gains = torch.empty(B, 2, dtype=torch.float32, device=dev)
+        for t, name in ((p_dry, "p_dry"), (p_wet, "p_wet"), (p_noise, "p_noise"), (amp, "amp")):
+            _req(t, torch.float64, name)
+            if t is not None and (t.dim() != 1 or t.numel() != B or t.device != dev):
+                raise _lib.PgasrError(f"wave_mix: {name} must be ({B},) fp64 on {dev}")
+        if p_dry is None or p_wet is None or (noise is not None and (p_noise is None or amp is None)):
+            raise _lib.PgasrError("wave_mix wants gains, or p_dry and p_wet (with noise: p_noise and amp too)")
+    nstride = nrows = 0
+    if noise is not None:
+        if noise.dim() != 2 or noise.device != dev:
+            raise _lib.PgasrError(f"wave_mix: noise must be (Rn, noise_stride) fp32 on {dev}")
+        nrows, nstride = noise.shape
+        _rows_i32(noise_len, nrows, dev, "wave_mix", "noise_len"); _rows_i32(noise_idx, B, dev, "wave_mix", "noise_idx")
+        _rows_i32(noise_start, B, dev, "wave_mix", "noise_start")
+        if noise_len is None or noise_idx is None:
+            raise _lib.PgasrError("wave_mix: noise needs noise_len and noise_idx")
+    if out is None:
+        out = torch.empty_like(wave)
+    elif tuple(out.shape) != (B, stride) or out.device != dev:
+        raise _lib.PgasrError(f"wave_mix: out must be ({B}, {stride}) fp32 on {dev}")
+    with _timed("wave_mix"):
+        st = lib.pgasr_wave_mix(_p(wave), stride, _p(n), B, _p(p_dry), _p(p_wet), _p(p_noise), _p(amp), _p(noise), nstride, nrows,
+                                _p(noise_len), _p(noise_idx), _p(noise_start), _p(gains), 1 if given else 0, _p(out), _stream())
+    _lib.check(st, "pgasr_wave_mix")
+    return out, gains
+
+
 def ctc_collapse(paths, lengths, blank=0, out=None):
     """paths (P,T,B) int32 -> tokens (P,B,T) int32, token_lengths (P,B) int32.
     out = (tokens, token_lengths) to write into (contiguous, zero-filled tokens)."""

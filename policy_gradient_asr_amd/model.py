@@ -207,12 +207,43 @@ def _check_features(features, n_feats, dataset):
             raise ValueError(f"features='{features}' gives {FEATURE_DIMS[features]} features per frame but n_feats={n_feats}")
 
 
+def _read_wav_dir(path):
+    """Every *.wav of a directory, in sorted order -> (waveforms, sample rates)."""
+    import os
+    from .features import read_wav
+    names = sorted(f for f in os.listdir(path) if f.lower().endswith(".wav"))
+    if not names:
+        raise ValueError(f"{path}: no .wav files")
+    waves, rates = [], []
+    for f in names:
+        try:
+            import torchaudio
+            w, sr = torchaudio.load(os.path.join(path, f))
+            w = w[0]
+        except ImportError:
+            w, sr = read_wav(os.path.join(path, f))
+        waves.append(w)
+        rates.append(int(sr))
+    return waves, rates
+
+
+def _wave_augment(noise_dir, rir_dir, snr_db, noise_prob, rir_prob, device):
+    """None where both directories are None, else the features.WaveAugment over their files."""
+    if noise_dir is None and rir_dir is None:
+        return None
+    from .features import NoiseBank, RirBank, WaveAugment
+    noise = None if noise_dir is None else NoiseBank(*_read_wav_dir(noise_dir), device=device)
+    rir = None if rir_dir is None else RirBank(*_read_wav_dir(rir_dir), device=device)
+    return WaveAugment(noise=noise, snr_db=snr_db, noise_prob=noise_prob, rir=rir, rir_prob=rir_prob)
+
+
 def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset=None, dev_dataset=None,
           n_feats=120, lam=1.0, lr=5e-4, resume=True, log_every=10, seed=0, bucket_by_length=True, features="mfcc",
           precision="f32", num_samples=1, reward_baseline="hypothesis", reward_unit="char", max_grad_norm=None,
           accumulate_steps=1, score_function="path", max_hyp_len=None, entropy_weight=0.0, objective="reinforce", mwer_nbest=4,
           mwer_beam=16, init_from=None, kl_weight=0.0, kl_reference_path=None, mwer_lm_path=None, mwer_lm_alpha=0.0,
-          mwer_lm_beta=0.0, target_rate=None, speed_perturb=None):
+          mwer_lm_beta=0.0, target_rate=None, speed_perturb=None, noise_dir=None, rir_dir=None, snr_db=(5.0, 20.0), noise_prob=1.0,
+          rir_prob=0.5):
     """Epoch loop of model.py:186-274 on the MI355X path: per-epoch train loss -> train_loss.npy,
     validation CTC loss -> val_losses.npy, model_best.pth / model_last.pth (state_dicts, reference
     names), plus checkpoint_last.pth (model + Adam moments + epoch) from which ``resume`` restarts
@@ -260,7 +291,12 @@ def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset
     speed_perturb: None (default) or a features.SpeedPerturb (or its factors, e.g. (0.9, 1.0, 1.1)): every training waveform is
     resampled by a factor drawn per (seed, epoch, utterance index) -- the dataset is then wrapped in data.Indexed, and the draws
     change every epoch.  The length bucketing keeps using the UNPERTURBED lengths: a batch's utterances differ by at most the
-    extreme factors' ratio more than they would.  Validation is not perturbed."""
+    extreme factors' ratio more than they would.  Validation is not perturbed.
+    noise_dir / rir_dir: None (default) or a directory of WAV files (read with torchaudio where present, else features.read_wav):
+    noise recordings and room impulse responses, packed on the device once at 16 kHz (features.NoiseBank / RirBank).  Every training
+    waveform then takes noise with probability noise_prob at an SNR drawn uniformly from snr_db = (low, high) dB, and a reverberation
+    with probability rir_prob (features.WaveAugment), drawn per (seed, epoch, utterance index) behind the resampling and in front of
+    the framing.  Validation and ``predict`` are never augmented."""
     import os
     import numpy as np
     import torch.utils.data as tud
@@ -297,6 +333,7 @@ def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset
     os.makedirs(model_path, exist_ok=True)
     from .features import SpeedPerturb
     speed_perturb = SpeedPerturb.coerce(speed_perturb)
+    wave_augment = _wave_augment(noise_dir, rir_dir, snr_db, noise_prob, rir_prob, dev)
     collate_custom = functools.partial(_collate, device=dev, features=features, target_rate=target_rate)
     if train_dataset is None:
         train_dataset = Data(os.path.join(corpus_path, "train.tsv"), os.path.join(corpus_path, "clips"), char2ind)
@@ -351,7 +388,8 @@ def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset
                         ("accumulate_steps", accumulate_steps), ("score_function", score_function),
                         ("max_hyp_len", max_hyp_len), ("entropy_weight", entropy_weight), ("kl_weight", kl_weight),
                         ("kl_reference_path", kl_reference_path), ("target_rate", target_rate),
-                        ("speed_perturb", None if speed_perturb is None else speed_perturb.state())):
+                        ("speed_perturb", None if speed_perturb is None else speed_perturb.state()),
+                        ("wave_augment", None if wave_augment is None else wave_augment.state())):
             if k in st and st[k] != want:
                 print("Warning: resuming with {}={} but the checkpoint was written with {}".format(k, want, st[k]))
         losses, val_losses, best, start_epoch = st["losses"], st["val_losses"], st["best"], st["epoch"] + 1
@@ -362,11 +400,13 @@ def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset
         model.train()
         lens = dataset_lengths(train_dataset) if bucket_by_length else None
         epoch_dataset, train_collate = train_dataset, collate_custom
-        if speed_perturb is not None:      # the draws are addressed by (seed, epoch, index in the corpus)
+        if speed_perturb is not None or wave_augment is not None:      # the draws are addressed by (seed, epoch, index in the corpus)
             from .data import Indexed
             epoch_dataset = Indexed(train_dataset)
-            train_collate = functools.partial(_collate, device=dev, features=features, target_rate=target_rate,
-                                              speed_perturb=speed_perturb, seed=seed, offset=epoch)
+            draws = {"speed_perturb": speed_perturb, "seed": seed, "offset": epoch}
+            if wave_augment is not None:
+                draws["wave_augment"] = wave_augment
+            train_collate = functools.partial(_collate, device=dev, features=features, target_rate=target_rate, **draws)
         if lens is not None:      # similar lengths per batch instead of model.py:221's shuffle=True
             sampler = LengthBucketSampler(lens, batch_size, seed=seed)
             sampler.set_epoch(epoch)
@@ -436,7 +476,8 @@ def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset
                     "reward_unit": reward_unit, "max_grad_norm": max_grad_norm, "accumulate_steps": accumulate_steps,
                     "score_function": score_function, "max_hyp_len": max_hyp_len, "entropy_weight": trainer.entropy_weight,
                     "kl_weight": kl_weight, "kl_reference_path": kl_reference_path, "target_rate": target_rate,
-                    "speed_perturb": None if speed_perturb is None else speed_perturb.state()}, ckpt)
+                    "speed_perturb": None if speed_perturb is None else speed_perturb.state(),
+                    "wave_augment": None if wave_augment is None else wave_augment.state()}, ckpt)
     return losses, val_losses
 
 
