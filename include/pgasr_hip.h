@@ -870,6 +870,69 @@ int pgasr_mbr_select(const int32_t* dist, const double* score, const int32_t* co
                      double* posterior, double* risk, int32_t* best, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * A7-WORDLM  A back-off word n-gram language model (ARPA form, order 1 .. 5) over N-best lists: the log-probability of every
+ * hypothesis' word sequence, and a weighted total with its rank on top of an earlier pass' total (csrc/word_lm.hip; the host
+ * model, its packing and its own statement of the query: lm.WordNgramLM).
+ * The model.  A word is 1 .. 32 token ids in [0, 255], without the delimiter; word ids 0, 1, 2 are <s>, </s>, <unk> and have no
+ *   spelling.  Every stored n-gram has logp and, below the top order, bow (natural log, fp32).  With h the last order-1 words
+ *   (<s>-padded at the sentence start, a word outside the vocabulary replaced by <unk>):
+ *     score(w | h) = logp(h, w) if that n-gram is stored, else (bow(h) if h is stored else 0) + score(w | h without its oldest word),
+ *   ending at the unigram, which every vocabulary entry has.  Every fp32 is widened to fp64; one word's score starts from 0 and
+ *   adds the back-off weights from the longest context to the shortest, then the found logp; a sentence's word_logp is the sum
+ *   of its words' scores in word order, one addition per word, then the score of </s>.  An empty sentence scores score(</s> | <s>).
+ *   The words of a hypothesis are its maximal runs of tokens other than `delimiter` (str.split(): no empty words).
+ * pgasr_word_lm_tables: device pointers and sizes, a plain struct in HOST memory passed by pointer and read before the launch.
+ *   word_pool (pool_bytes) bytes, word_off (n_words + 1) int32: the spelling of word i is word_pool[word_off[i] .. word_off[i+1]).
+ *   word_slots (word_cap) int32: a word id or -1.  A word is looked up from slot hash_word(spelling) & (word_cap - 1) on, slot by
+ *     slot, until its spelling equals a slot's word byte for byte (found) or a slot is empty (not in the vocabulary): a hash match
+ *     alone never decides.  hash_word: FNV-1a over the bytes (offset 2166136261, prime 16777619), then h ^= h >> 16;
+ *     h *= 0x85EBCA6B; h ^= h >> 13; h *= 0xC2B2AE35; h ^= h >> 16, in wrapping 32 bits.
+ *   uni_logp, uni_bow (n_words) fp32: the unigrams at the word's id.  The entry index of a unigram is the word id.
+ *   ngram_slots (ngram_cap) x 16 bytes {int32 ctx, int32 word, float logp, float bow}, ctx = -1 in an empty slot: the n-grams of
+ *     all orders >= 2 in one table.  ctx is the entry index of the n-gram's context (all its words but the last); the entry index
+ *     of the n-gram in slot s is n_words + s.  Looked up from slot hash_ngram(ctx, word) & (ngram_cap - 1) on until both ctx and
+ *     word are equal or a slot is empty.  hash_ngram: x = ctx * 2^32 + word; x ^= x >> 30; x *= 0xBF58476D1CE4E5B9; x ^= x >> 27;
+ *     x *= 0x94D049BB133111EB; x ^= x >> 31, in wrapping 64 bits.
+ *   word_cap and ngram_cap are powers of two and at most half their slots are taken, so every probe ends.
+ * pgasr_nbest_word_lm_score:
+ *   tokens (N, B, tok_stride) int32, len (N, B), count (B): a list as pgasr_ctc_beam_search_nbest writes it (len is clamped to
+ *   [0, tok_stride], count to [0, N]); nothing behind a hypothesis' length is read.  For n < count[b]:
+ *     out_word_logp[n, b] fp64 = the sentence's word_logp,  out_n_words[n, b] int32 = its words (</s> not counted),
+ *     out_n_oov[n, b] int32 = its words outside the vocabulary.   Rows n >= count[b]: 0, 0, 0.
+ *   A word of more than 32 tokens, or with a token outside [0, 255], is outside the vocabulary without a look at the tables.  The
+ *   blank is not special here: no spelling holds it (the host model refuses one), so a word with a blank in it is not found.
+ *   Checked before any HIP call: tables NULL -> PGASR_ERR_INVALID_ARG; order outside 1 .. 5, N < 1, N > 128, tok_stride >
+ *   PGASR_WORD_LM_MAX_STRIDE, n_words > 2^22, ngram_cap > 2^25 (2^24 n-grams) -> PGASR_ERR_UNSUPPORTED; a NULL pointer, B < 1,
+ *   tok_stride < 1, n_words < 3, a capacity that is no power of two, more than word_cap / 2 spelled words, pool_bytes < 0 or above
+ *   32 bytes per spelled word -> PGASR_ERR_INVALID_ARG.  One launch, one workgroup per hypothesis, no workspace, no host
+ *   synchronisation.
+ * pgasr_nbest_combine_rank:
+ *   base, word_logp (N, B) fp64, n_words (N, B) int32, count (B).  For n < count[b]:
+ *     total[n, b] = (base + -(word_alpha * word_logp)) + -(word_beta * n_words),  every product and sum rounded once.
+ *   A non-finite base, or a total that is not a number, gives total = +inf; rows n >= count[b]: total = +inf.  order (B, N) int32 as
+ *   pgasr_nbest_rescore ranks: the stable ascending rank of total over the first count[b] rows (ties keep the list's order), then
+ *   the rows beyond count in index order.  word_alpha = word_beta = 0 returns base bit for bit where it is finite.
+ *   Checked before any HIP call: N < 1 or N > 128 -> PGASR_ERR_UNSUPPORTED; a NULL pointer, B < 1, a weight that is not finite ->
+ *   PGASR_ERR_INVALID_ARG.  One launch, one workgroup per utterance, no host synchronisation.
+ * ---------------------------------------------------------------------------------------- */
+#define PGASR_WORD_LM_MAX_STRIDE 4096
+typedef struct pgasr_word_lm_tables {
+    const unsigned char* word_pool;
+    const int32_t* word_off;
+    const int32_t* word_slots;
+    const float* uni_logp;
+    const float* uni_bow;
+    const void* ngram_slots;
+    int32_t order, n_words, word_cap, ngram_cap, pool_bytes, reserved;
+} pgasr_word_lm_tables;
+int pgasr_nbest_word_lm_score(const int32_t* tokens, int tok_stride, const int32_t* len, const int32_t* count,
+                              int N, int B, int delimiter, const pgasr_word_lm_tables* tables,
+                              double* out_word_logp, int32_t* out_n_words, int32_t* out_n_oov, void* stream);
+int pgasr_nbest_combine_rank(const double* base, const double* word_logp, const int32_t* n_words, const int32_t* count,
+                             int N, int B, double word_alpha, double word_beta, double* out_total, int32_t* out_order,
+                             void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * A13-MWER  Minimum word error rate training over the N-best list of the beam search (Prabhavalkar et al., arXiv:1712.01818): the
  * model's probability renormalised over the N hypotheses the decoder returns, and the expected risk under that distribution.
  * Nothing is sampled.  With a list as pgasr_ctc_beam_search_nbest writes it WITHOUT collapse (raw prefixes are distinct label

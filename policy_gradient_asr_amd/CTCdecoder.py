@@ -2,7 +2,8 @@
 blank=0) -> (tuple[int], float)`` and ``collapse_fn(str) -> str``, with the search itself running
 as a HIP kernel (csrc/beam.hip).  ``greedy_decode`` is the best-path decoder the reference lacks
 (SURVEY §8a A9).  Beyond the reference: ``nbest=N`` returns the first N entries of the final beam instead of the best one, and
-``CTCDecoder.rescore`` ranks such a list in a second pass (exact CTC likelihood and / or a stronger n-gram LM, csrc/nbest.hip);
+``CTCDecoder.rescore`` ranks such a list in a second pass (exact CTC likelihood and / or a stronger n-gram LM, csrc/nbest.hip; with
+``word_lm=`` a word n-gram LM on top, csrc/word_lm.hip);
 ``CTCDecoder.mbr_decode`` returns the hypothesis of least expected edit distance under the list's posterior instead of the best-scored
 one (minimum-Bayes-risk decoding, csrc/mbr.hip)."""
 import collections
@@ -27,6 +28,7 @@ BEAM_KMAX = 128      # csrc/beam.hip
 _UNSET = object()      # "use the decoder's own value" (None is a value: no language model)
 
 NBestRescored = collections.namedtuple("NBestRescored", "order total am lm_logp best_tokens best_len skipped")
+NBestRescoredWords = collections.namedtuple("NBestRescoredWords", NBestRescored._fields + ("word_logp", "n_words", "n_oov"))
 MBRDecoded = collections.namedtuple("MBRDecoded", "tokens lengths best risk posterior dist nbest")
 
 
@@ -95,8 +97,16 @@ class CTCDecoder:
         return hipops.ctc_beam_search(log_probs, lengths, beam=int(beam_size), blank=int(blank), fast_lm=fast_lm,
                                       **self._lm_args(lm, lm_alpha, lm_beta))
 
+    def _word_delimiter(self, word_delimiter):
+        if word_delimiter is not None:
+            return int(word_delimiter)
+        for i, sym in enumerate(self.alphabet):
+            if sym.replace("\n", "") == " ":
+                return i
+        raise ValueError("a word LM needs word_delimiter: the alphabet has no ' ' symbol")
+
     def rescore(self, log_probs, lengths, nb, lm=_UNSET, lm_alpha=None, lm_beta=None, acoustic="ctc", am_weight=1.0, max_hyp_len=None,
-                blank=0):
+                blank=0, word_lm=None, word_lm_alpha=0.0, word_lm_beta=0.0, word_delimiter=None):
         """Second pass over an N-best list ``nb`` (``hipops.CTCNBest`` of ``decode_batch(..., nbest=N)`` on the same log_probs
         (T,B,V) / lengths), N <= 128:  total = am_weight * am - lm_alpha * lm_logp - lm_beta * length, lower is better, with
         lm_logp the hypothesis' log-probability under ``lm`` (the decoder's own unless given; None: no LM term).
@@ -109,9 +119,21 @@ class CTCDecoder:
             the first pass' LM bonuses: the second LM is then added on top of them, not in their place.
         Returns ``NBestRescored``: order (B,N) int32 -- per utterance the list's rows by ascending total, ties in first-pass order,
         rows beyond count last --, total / am / lm_logp (N,B) float64, best_tokens (B,T) / best_len (B) int32 the row order[:, 0]
-        of every utterance, skipped (N,B) bool."""
+        of every utterance, skipped (N,B) bool.
+        word_lm: None (default: everything above, nothing else) or a ``lm.WordNgramLM``.  The pass above runs first and its total
+            is the base of a second launch: total = base - word_lm_alpha * word_logp - word_lm_beta * n_words, with word_logp the
+            log-probability of the hypothesis' words under ``word_lm`` (``hipops.nbest_word_lm_score``; words split at the token
+            ``word_delimiter``, default the alphabet's " " -- an alphabet without one raises).  Returns ``NBestRescoredWords``:
+            the seven fields above with order / total / best_* from the combined total, then word_logp (N,B) float64, n_words and
+            n_oov (N,B) int32.  No further host synchronisation.  word_lm_alpha = word_lm_beta = 0 leaves order and total as
+            they are without a word LM, bit for bit."""
         if acoustic not in ("ctc", "first_pass"):
             raise ValueError(f"acoustic must be 'ctc' or 'first_pass' (got {acoustic!r})")
+        if word_lm is not None:
+            delim = self._word_delimiter(word_delimiter)
+            if nb.tokens.shape[2] > hipops.WORD_LM_MAX_STRIDE:
+                raise ValueError(f"a word LM takes hypotheses of at most {hipops.WORD_LM_MAX_STRIDE} tokens (got rows of "
+                                 f"{nb.tokens.shape[2]})")
         T, B, V = log_probs.shape
         N = nb.tokens.shape[0]
         args = self._lm_args(lm, lm_alpha, lm_beta)
@@ -128,9 +150,16 @@ class CTCDecoder:
             am = nb.score
         order, total, lm_logp = hipops.nbest_rescore(nb.tokens, nb.lengths, nb.count, am.contiguous(), V, blank=int(blank), lm=args["lm"],
                                                      am_weight=float(am_weight), lm_alpha=args["lm_alpha"], lm_beta=args["lm_beta"])
+        if word_lm is not None:
+            word_logp, n_words, n_oov = hipops.nbest_word_lm_score(nb.tokens, nb.lengths, nb.count, word_lm, delim)
+            order, total = hipops.nbest_combine_rank(total, word_logp, n_words, nb.count, word_alpha=float(word_lm_alpha),
+                                                     word_beta=float(word_lm_beta))
         first = order[:, 0].long()
         cols = torch.arange(B, device=order.device)
-        return NBestRescored(order, total, am, lm_logp, nb.tokens[first, cols].contiguous(), nb.lengths[first, cols].contiguous(), skipped)
+        best = (nb.tokens[first, cols].contiguous(), nb.lengths[first, cols].contiguous())
+        if word_lm is not None:
+            return NBestRescoredWords(order, total, am, lm_logp, best[0], best[1], skipped, word_logp, n_words, n_oov)
+        return NBestRescored(order, total, am, lm_logp, best[0], best[1], skipped)
 
     def mbr_from_list(self, nb, score, vocab=None, risk_unit="char", word_delimiter=None, posterior_scale=1.0, max_hyp_len=None):
         """Minimum-Bayes-risk choice over an N-best list the caller already holds: ``nb`` a ``hipops.CTCNBest`` (N <= 128), ``score``
@@ -155,16 +184,19 @@ class CTCDecoder:
         return MBRDecoded(nb.tokens[first, cols].contiguous(), nb.lengths[first, cols].contiguous(), best, risk, posterior, dist, nb)
 
     def mbr_decode(self, log_probs, lengths=None, beam_size=16, nbest=16, risk_unit="char", word_delimiter=None, acoustic="ctc",
-                   posterior_scale=1.0, lm=_UNSET, lm_alpha=None, lm_beta=None, am_weight=1.0, max_hyp_len=None, blank=0):
+                   posterior_scale=1.0, lm=_UNSET, lm_alpha=None, lm_beta=None, am_weight=1.0, max_hyp_len=None, blank=0,
+                   word_lm=None, word_lm_alpha=0.0, word_lm_beta=0.0):
         """Minimum-Bayes-risk decoding: the N-best search (``decode_batch(nbest=)``, with the decoder's first-pass LM if it has
         one), the score of every hypothesis (``rescore(...).total`` with ``acoustic`` / ``lm`` / ``lm_alpha`` / ``lm_beta`` /
         ``am_weight`` as ``rescore`` takes them: without an LM the exact CTC -log p, or the first-pass score), the distances inside
         each list and the selection (``mbr_from_list``), in that order.  log_probs (T,B,V) GPU tensor, nbest <= beam_size, nbest <= 128.
-        Returns ``MBRDecoded``."""
+        word_lm / word_lm_alpha / word_lm_beta go to ``rescore`` (words split at ``word_delimiter``, as the word risk): the
+        posterior then comes from the totals with the word LM in them.  Returns ``MBRDecoded``."""
         T, B, V = log_probs.shape
         nb = self.decode_batch(log_probs, lengths, beam_size=beam_size, blank=blank, nbest=int(nbest))
         rs = self.rescore(log_probs, lengths, nb, lm=lm, lm_alpha=lm_alpha, lm_beta=lm_beta, acoustic=acoustic, am_weight=am_weight,
-                          max_hyp_len=max_hyp_len, blank=blank)
+                          max_hyp_len=max_hyp_len, blank=blank, word_lm=word_lm, word_lm_alpha=word_lm_alpha,
+                          word_lm_beta=word_lm_beta, word_delimiter=word_delimiter)
         return self.mbr_from_list(nb, rs.total, vocab=V, risk_unit=risk_unit, word_delimiter=word_delimiter,
                                   posterior_scale=posterior_scale, max_hyp_len=max_hyp_len)
 

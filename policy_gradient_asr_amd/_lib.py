@@ -101,6 +101,10 @@ SIGNATURES = {
                                       C.c_double, C.c_double, C.c_double, c_ptr, c_ptr, c_i32p, c_ptr]),
     "pgasr_nbest_pair_dist": (C.c_int, [c_i32p, C.c_int, c_i32p, c_i32p, C.c_int, C.c_int, C.c_int, C.c_int, c_i32p, c_ptr]),
     "pgasr_mbr_select": (C.c_int, [c_i32p, c_ptr, c_i32p, C.c_int, C.c_int, C.c_double, c_ptr, c_ptr, c_i32p, c_ptr]),
+    "pgasr_nbest_word_lm_score": (C.c_int, [c_i32p, C.c_int, c_i32p, c_i32p, C.c_int, C.c_int, C.c_int, c_ptr, c_ptr, c_i32p, c_i32p,
+                                            c_ptr]),
+    "pgasr_nbest_combine_rank": (C.c_int, [c_ptr, c_ptr, c_i32p, c_i32p, C.c_int, C.c_int, C.c_double, C.c_double, c_ptr, c_i32p,
+                                           c_ptr]),
     "pgasr_mwer_weights": (C.c_int, [c_i32p, c_i32p, c_i32p, c_f32p, c_i32p, c_i32p, c_f32p, C.c_int, C.c_int, C.c_int,
                                      C.c_float, C.c_float, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_ptr]),
     "pgasr_ctc_grad_from_lattices_nbest": (C.c_int, [c_f32p, c_i32p, c_i32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_f32p,
@@ -189,6 +193,13 @@ SIGNATURES = {
     "pgasr_gemm_x6w_feed_phase_f32": (C.c_int, [C.c_int, C.c_int, C.c_int, c_f32p, C.c_int, c_ptr, c_ptr, c_ptr, c_f32p, C.c_int,
                                                 c_f32p, c_ptr, c_ptr, C.c_int, C.c_int, c_ptr, c_ptr, C.c_size_t, c_ptr]),
 }
+
+
+class WordLMTables(C.Structure):
+    """pgasr_word_lm_tables (include/pgasr_hip.h, A7-WORDLM): device addresses and sizes, a host struct passed with C.byref."""
+    _fields_ = [("word_pool", C.c_void_p), ("word_off", C.c_void_p), ("word_slots", C.c_void_p), ("uni_logp", C.c_void_p),
+                ("uni_bow", C.c_void_p), ("ngram_slots", C.c_void_p), ("order", C.c_int32), ("n_words", C.c_int32),
+                ("word_cap", C.c_int32), ("ngram_cap", C.c_int32), ("pool_bytes", C.c_int32), ("reserved", C.c_int32)]
 
 
 class PgasrError(RuntimeError):

@@ -2,6 +2,7 @@
 include/pgasr_hip.h).  torch is used for device memory and the current stream only.
 Every wrapper requires CUDA(HIP) tensors and raises otherwise -- no CPU fallback."""
 import collections
+import ctypes
 import os
 
 import torch
@@ -1521,6 +1522,53 @@ def nbest_rescore(tokens, lengths, count, am, vocab, blank=0, lm=None, am_weight
                                      _p(lm_logp), _p(total), _p(order), _stream())
     _lib.check(st, "pgasr_nbest_rescore")
     return order, total, lm_logp
+
+
+WORD_LM_MAX_STRIDE = 4096        # csrc/word_lm.hip: the row of tokens, its words and their scores live in 64 KB of LDS
+
+
+def nbest_word_lm_score(tokens, lengths, count, word_lm, delimiter):
+    """A word n-gram LM over N-best lists (pgasr_nbest_word_lm_score; include/pgasr_hip.h, A7-WORDLM): tokens (N,B,stride) /
+    lengths (N,B) / count (B) int32 as ``ctc_beam_search_nbest`` returns them, ``word_lm`` a ``lm.WordNgramLM``, ``delimiter`` the
+    token id that separates words.  Returns (word_logp (N,B) float64, n_words (N,B) int32, n_oov (N,B) int32), no host
+    synchronisation: per hypothesis what ``word_lm.logp_sentence`` returns, bit for bit; zeros in the rows beyond count.
+    N <= 128, stride <= WORD_LM_MAX_STRIDE."""
+    lib = _lib.load()
+    _req(tokens, torch.int32, "tokens"); _req(lengths, torch.int32, "lengths"); _req(count, torch.int32, "count")
+    if tokens.dim() != 3 or tuple(lengths.shape) != tuple(tokens.shape[:2]) or count.numel() != tokens.shape[1]:
+        raise _lib.PgasrError("nbest_word_lm_score wants tokens (N,B,stride), lengths (N,B) and count (B)")
+    if not hasattr(word_lm, "device_tables"):
+        raise _lib.PgasrError("nbest_word_lm_score wants a lm.WordNgramLM")
+    N, B, stride = tokens.shape
+    tables = word_lm.device_tables(tokens.device)
+    out = torch.empty(2, N, B, dtype=torch.int32, device=tokens.device)
+    word_logp = torch.empty(N, B, dtype=torch.float64, device=tokens.device)
+    with _timed("nbest_word_lm_score"):
+        st = lib.pgasr_nbest_word_lm_score(_p(tokens), stride, _p(lengths), _p(count), N, B, int(delimiter), ctypes.byref(tables.struct),
+                                           _p(word_logp), out[0].data_ptr(), out[1].data_ptr(), _stream())
+    _lib.check(st, "pgasr_nbest_word_lm_score")
+    return word_logp, out[0], out[1]
+
+
+def nbest_combine_rank(base, word_logp, n_words, count, word_alpha=0.0, word_beta=0.0):
+    """A word LM's score on top of an earlier pass (pgasr_nbest_combine_rank): base, word_logp (N,B) float64, n_words (N,B) int32,
+    count (B) int32.  Returns (order (B,N) int32, total (N,B) float64), no host synchronisation:
+    total = base - word_alpha * word_logp - word_beta * n_words (lower is better; +inf for a non-finite base and for rows beyond
+    count), order as ``nbest_rescore`` ranks.  N <= 128."""
+    lib = _lib.load()
+    _req(base, torch.float64, "base"); _req(word_logp, torch.float64, "word_logp"); _req(n_words, torch.int32, "n_words")
+    _req(count, torch.int32, "count")
+    if base.dim() != 2 or tuple(word_logp.shape) != tuple(base.shape) or tuple(n_words.shape) != tuple(base.shape) \
+            or count.numel() != base.shape[1]:
+        raise _lib.PgasrError("nbest_combine_rank wants base, word_logp, n_words (N,B) and count (B)")
+    N, B = base.shape
+    order = torch.empty(B, N, dtype=torch.int32, device=base.device)
+    total = torch.empty(N, B, dtype=torch.float64, device=base.device)
+    with _timed("nbest_combine_rank"):
+        st = lib.pgasr_nbest_combine_rank(_p(base), _p(word_logp), _p(n_words), _p(count), N, B, float(word_alpha), float(word_beta),
+                                          _p(total), _p(order), _stream())
+    _lib.check(st, "pgasr_nbest_combine_rank")
+    return order, total
 
 
 PAIR_DIST_MAX_LEN = 1024         # csrc/mbr.hip: 16 blocks of 64 pattern positions

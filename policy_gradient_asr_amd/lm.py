@@ -4,7 +4,13 @@ An LM of order ``n >= 1`` over ``V`` symbols is a dense fp32 table of natural-lo
 ``table[c_1, .., c_{n-1}, s] = ln p(s | c_1 .. c_{n-1})`` with ``c_{n-1}`` the most recent symbol.  The blank index never occurs
 inside a prefix, so it serves as the start-of-sentence pad: the context of a prefix shorter than ``n-1`` is left-padded with
 ``blank``.  The column ``s == blank`` is never read and holds 0.  Building, saving and loading are host-side numpy work; the
-search reads the table on the device (``device_table``)."""
+search reads the table on the device (``device_table``).
+
+``WordNgramLM`` is the word-level model of the second pass: a back-off n-gram model (ARPA form, order <= 5) over words spelled in
+the acoustic alphabet, queried on the host by ``logp_sentence`` and on the device by csrc/word_lm.hip through ``device_tables``."""
+import collections
+import math
+
 import numpy as np
 
 MAX_ENTRIES = 1 << 25      # V**n words (128 MiB): order 5 at V = 29, order 4 at V = 64 -- csrc/beam.hip refuses more
@@ -120,4 +126,468 @@ class CharNgramLM:
         t = self._device_tables.get(device)
         if t is None:
             t = self._device_tables[device] = torch.from_numpy(self.table).to(device).contiguous()
+        return t
+
+
+# ------------------------------------------------------------------------------------------
+# Word n-gram model for second-pass rescoring (csrc/word_lm.hip; include/pgasr_hip.h, section A7-WORDLM)
+# ------------------------------------------------------------------------------------------
+MAX_WORD_LEN = 32          # tokens per vocabulary word: a longer word is OOV by definition
+MAX_WORD_ORDER = 5
+MAX_WORDS = 1 << 22        # vocabulary entries, the three reserved ones included
+MAX_NGRAMS = 1 << 24       # stored n-grams of all orders
+BOS, EOS, UNK = 0, 1, 2    # the reserved word ids: <s>, </s>, <unk> (no spelling)
+N_RESERVED = 3
+ARPA_RESERVED = ("<s>", "</s>", "<unk>")
+ARPA_NEVER = -99.0         # log10 p of an entry that is never predicted (<s>), ARPA's convention
+_LN10 = math.log(10.0)
+
+
+def hash_word(spellings):
+    """The integer hash of a word's spelling, as csrc/word_lm.hip computes it: FNV-1a over the token bytes, then murmur3's 32-bit
+    finaliser, all in wrapping uint32.  ``spellings``: a sequence of byte strings; returns a uint32 array."""
+    spellings = list(spellings)
+    n = len(spellings)
+    width = max([len(s) for s in spellings] + [1])
+    mat = np.zeros((n, width), dtype=np.uint32)
+    lens = np.zeros(n, dtype=np.int64)
+    for i, s in enumerate(spellings):
+        mat[i, :len(s)] = np.frombuffer(bytes(s), dtype=np.uint8)
+        lens[i] = len(s)
+    h = np.full(n, 2166136261, dtype=np.uint32)
+    for j in range(width):
+        live = j < lens
+        h = np.where(live, (h ^ mat[:, j]) * np.uint32(16777619), h)
+    h = h ^ (h >> np.uint32(16))
+    h = h * np.uint32(0x85EBCA6B)
+    h = h ^ (h >> np.uint32(13))
+    h = h * np.uint32(0xC2B2AE35)
+    h = h ^ (h >> np.uint32(16))
+    return h
+
+
+def hash_ngram(ctx, word):
+    """The integer hash of an n-gram's key (index of its context entry, word id), as csrc/word_lm.hip computes it: splitmix64's
+    finaliser of ctx * 2^32 + word in wrapping uint64.  Arrays in, a uint64 array out."""
+    x = (np.atleast_1d(np.asarray(ctx)).astype(np.uint64) << np.uint64(32)) | np.atleast_1d(np.asarray(word)).astype(np.uint64)
+    x = x ^ (x >> np.uint64(30))
+    x = x * np.uint64(0xBF58476D1CE4E5B9)
+    x = x ^ (x >> np.uint64(27))
+    x = x * np.uint64(0x94D049BB133111EB)
+    x = x ^ (x >> np.uint64(31))
+    return x
+
+
+def _table_size(n):
+    """The smallest power of two >= max(2, 2 n): a load factor of at most 0.5."""
+    cap = 2
+    while cap < 2 * n:
+        cap *= 2
+    return cap
+
+
+def _place(home, used):
+    """Linear probing, deterministic and vectorised: every item starts at its home slot; per round, among the items standing on the
+    same free slot the one of lowest index takes it and the others, like those standing on a taken slot, move one slot on.  An
+    item therefore only ever passes taken slots, which is what a probe that stops at the first empty slot needs.  ``used`` (bool
+    per slot) is updated in place; returns the slot of every item."""
+    cap = used.size
+    pos = np.full(home.size, -1, dtype=np.int64)
+    cur = home.astype(np.int64) & (cap - 1)
+    pending = np.arange(home.size)
+    while pending.size:
+        c = cur[pending]
+        free = ~used[c]
+        slots, first = np.unique(c[free], return_index=True)
+        pos[pending[free][first]] = slots
+        used[slots] = True
+        pending = pending[pos[pending] < 0]
+        cur[pending] = (cur[pending] + 1) & (cap - 1)
+    return pos
+
+
+WordLMDeviceTables = collections.namedtuple("WordLMDeviceTables", "struct tensors")
+
+
+class WordNgramLM:
+    """A back-off word n-gram model of order 1 <= n <= 5 in ARPA form.
+
+    A word is a non-empty tuple of at most MAX_WORD_LEN token ids of the acoustic alphabet (stored as bytes: ids <= 255), without
+    the delimiter and without the blank; ids 0, 1, 2 are <s>, </s>, <unk> and have no spelling.  Every stored n-gram has ``logp``
+    and, below the top order, ``bow`` (natural log, fp32).  With h the last n-1 words (<s>-padded at the sentence start, OOV words
+    replaced by <unk>):
+        score(w | h) = logp(h, w) if that n-gram is stored, else (bow(h) if h is stored else 0) + score(w | h without its oldest word)
+    ending at the unigram, which every vocabulary entry has.  The arithmetic is contractual (the device repeats it bit for bit):
+    every fp32 is widened to fp64; one word's score starts from 0 and adds the back-off weights from the longest context to the
+    shortest, then the found logp; a sentence's score is the sum of its words' scores in word order, then the score of </s>.
+
+    Arrays (canonical: words ordered by spelling, n-grams of an order by their word ids, so equal models have equal arrays):
+        word_pool uint8, word_off int32 (n_words + 1): the spelling of word i is word_pool[word_off[i] : word_off[i + 1]]
+        ngrams[k-1] (M_k, k) int32, logp[k-1] / bow[k-1] (M_k,) fp32 for k = 1 .. order; the unigram of word i is row i.
+    The context (all words but the last) of every stored n-gram must itself be stored, as in every ARPA file a toolkit writes."""
+
+    def __init__(self, word_pool, word_off, ngrams, logp, bow, blank=0, delimiter=-1):
+        order = len(ngrams)
+        if not 1 <= order <= MAX_WORD_ORDER or len(logp) != order or len(bow) != order:
+            raise ValueError(f"a word LM has order 1 .. {MAX_WORD_ORDER} with one n-gram, logp and bow array per order (got {order})")
+        self.word_pool = np.array(word_pool, dtype=np.uint8).reshape(-1)         # a copy: the caller's may be a read-only view of bytes
+        self.word_off = np.ascontiguousarray(np.asarray(word_off), dtype=np.int32).reshape(-1)
+        n_words = self.word_off.size - 1
+        if n_words < N_RESERVED:
+            raise ValueError("a word LM holds at least <s>, </s> and <unk>")
+        if n_words > MAX_WORDS:
+            raise ValueError(f"{n_words} words exceed the limit of 2**22; a model is never truncated")
+        lens = np.diff(self.word_off.astype(np.int64))
+        if self.word_off[0] != 0 or self.word_off[-1] != self.word_pool.size or (lens[:N_RESERVED] != 0).any() \
+                or (lens[N_RESERVED:] < 1).any() or (lens > MAX_WORD_LEN).any():
+            raise ValueError(f"every word but the three reserved ones has 1 .. {MAX_WORD_LEN} tokens, the reserved ones none")
+        self.blank, self.delimiter = int(blank), int(delimiter)
+        if (self.word_pool == self.blank).any() or (0 <= self.delimiter <= 255 and (self.word_pool == self.delimiter).any()):
+            raise ValueError("a word's spelling holds neither the blank nor the delimiter")
+        pool = self.word_pool.tobytes()
+        self.spellings = [pool[self.word_off[i]:self.word_off[i + 1]] for i in range(n_words)]
+        self._word_id = {s: i for i, s in enumerate(self.spellings) if i >= N_RESERVED}
+        if len(self._word_id) != n_words - N_RESERVED:
+            raise ValueError("two words of the vocabulary have the same spelling")
+        self.ngrams, self.logp, self.bow = [], [], []
+        for k in range(1, order + 1):
+            g = np.ascontiguousarray(np.asarray(ngrams[k - 1]), dtype=np.int32).reshape(-1, k)
+            lp = np.ascontiguousarray(np.asarray(logp[k - 1]), dtype=np.float32).reshape(-1)
+            bw = np.ascontiguousarray(np.asarray(bow[k - 1]), dtype=np.float32).reshape(-1)
+            if lp.size != g.shape[0] or bw.size != g.shape[0]:
+                raise ValueError(f"order {k}: n-grams, logp and bow differ in length")
+            if g.size and (g.min() < 0 or g.max() >= n_words):
+                raise ValueError(f"order {k}: a word id outside the vocabulary")
+            if not (np.isfinite(lp).all() and np.isfinite(bw).all()):
+                raise ValueError(f"order {k}: a non-finite logp or bow")
+            self.ngrams.append(g); self.logp.append(lp); self.bow.append(bw)
+        if sum(g.shape[0] for g in self.ngrams) > MAX_NGRAMS:
+            raise ValueError(f"{sum(g.shape[0] for g in self.ngrams)} n-grams exceed the limit of 2**24; a model is never truncated")
+        if self.ngrams[0].shape[0] != n_words or (self.ngrams[0][:, 0] != np.arange(n_words)).any():
+            raise ValueError("every vocabulary entry has a unigram, stored at its own id")
+        self.order, self.n_words = order, n_words
+        self.ctx_row = self._context_rows()
+        self._table = None
+        self._packed = None
+        self._device_tables = {}
+
+    def _context_rows(self):
+        """Per order k >= 2, the row at order k-1 of every n-gram's context.  Rows are in lexicographic order, so the key
+        (context row, last word) is ascending and a binary search finds it."""
+        rows = [np.arange(self.n_words, dtype=np.int64)]
+        keys = [np.arange(self.n_words, dtype=np.int64)]        # keys[j-1]: the ascending key of every row of order j
+        for k in range(2, self.order + 1):
+            g = self.ngrams[k - 1].astype(np.int64)
+            p = g[:, 0]                                          # the row at order j of the n-gram's first j words, j = 1 .. k-1
+            for j in range(2, k):
+                p = self._search(keys[j - 1], (p << 32) | g[:, j - 1], j)
+            key = (p << 32) | g[:, k - 1]
+            if key.size > 1 and (np.diff(key) <= 0).any():
+                raise ValueError(f"order {k}: the n-grams are not in ascending order of their word ids, or one is stored twice")
+            rows.append(p)
+            keys.append(key)
+        return rows
+
+    @staticmethod
+    def _search(keys, want, k):
+        if want.size == 0:
+            return want
+        if keys.size == 0:
+            raise ValueError(f"an n-gram's context is not stored at order {k}")
+        i = np.minimum(np.searchsorted(keys, want), keys.size - 1)
+        if (keys[i] != want).any():
+            raise ValueError(f"an n-gram's context is not stored at order {k}")
+        return i
+
+    # ---------------------------------------------------------------- construction
+    @classmethod
+    def _build(cls, grams, order, blank, delimiter):
+        """grams[k-1]: dict from tuples of k words -- a reserved id (int) or a spelling (bytes) each -- to (logp, bow) in natural
+        log.  Words are the spellings of the unigrams; arrays come out in canonical order."""
+        words = sorted(w[0] for w in grams[0] if not isinstance(w[0], int))
+        wid = {s: N_RESERVED + i for i, s in enumerate(words)}
+        wid.update({BOS: BOS, EOS: EOS, UNK: UNK})
+        off = np.zeros(N_RESERVED + len(words) + 1, dtype=np.int64)
+        off[N_RESERVED + 1:] = np.cumsum([len(s) for s in words])
+        pool = np.frombuffer(b"".join(words), dtype=np.uint8)
+        if off[-1] >= 2 ** 31:
+            raise ValueError("the spellings exceed 2**31 bytes")
+        ngrams, logp, bow = [], [], []
+        for k in range(1, order + 1):
+            items = grams[k - 1]
+            g = np.array([[wid[w] for w in key] for key in items], dtype=np.int32).reshape(-1, k)
+            vals = np.array(list(items.values()), dtype=np.float64).reshape(-1, 2)
+            idx = np.lexsort(tuple(g[:, j] for j in range(k - 1, -1, -1))) if g.shape[0] else np.zeros(0, dtype=np.int64)
+            ngrams.append(g[idx]); logp.append(vals[idx, 0].astype(np.float32)); bow.append(vals[idx, 1].astype(np.float32))
+        return cls(pool, off, ngrams, logp, bow, blank=blank, delimiter=delimiter)
+
+    @classmethod
+    def from_text(cls, lines, char2ind, order=3, min_count=1, delimiter=" ", blank=0):
+        """Interpolated Witten-Bell smoothing (as ``CharNgramLM``), written out in back-off form, in float64 on the host.  A line is
+        <s> w_1 .. w_m </s>, its words cut at ``delimiter`` as str.split() cuts them; an n-gram of order k is every window of k
+        of these whose last entry is not <s>.  With c the counts and N1+(h.) the number of distinct entries seen after h:
+            p_0(w)   = 1 / (words + 2)                                   uniform over the vocabulary, </s> and <unk>
+            p_k(w|h) = (c(hw) + N1+(h.) p_{k-1}(w|h')) / (c(h) + N1+(h.))  for a seen hw, h' = h without its oldest word
+            bow(h)   = ln(N1+(h.) / (c(h) + N1+(h.)))
+        p_{k-1}(w|h') being the back-off model of order k-1 itself.  Every vocabulary entry gets a unigram (c = 0 where unseen), so
+        <unk> always has a finite probability; <s> is never predicted (log10 p = -99).  Words seen fewer than ``min_count`` times
+        or longer than MAX_WORD_LEN count as <unk>.  A character outside the alphabet raises."""
+        order = int(order)
+        if not 1 <= order <= MAX_WORD_ORDER:
+            raise ValueError(f"a word LM has order 1 .. {MAX_WORD_ORDER} (got {order})")
+        if delimiter not in char2ind:
+            raise ValueError(f"the alphabet has no delimiter {delimiter!r}")
+        sents, freq = [], collections.Counter()
+        for ln in lines:
+            sent = []
+            for w in ln.rstrip("\n").split(delimiter):
+                if not w:
+                    continue
+                try:
+                    ids = [char2ind[c] for c in w]
+                except KeyError as e:
+                    raise ValueError(f"character {e.args[0]!r} is not in the alphabet") from None
+                if max(ids) > 255 or int(blank) in ids:
+                    raise ValueError("a word LM needs token ids <= 255 other than the blank")
+                sent.append(bytes(ids))
+            freq.update(sent)
+            sents.append(sent)
+        if not sents:
+            raise ValueError("from_text needs at least one line")
+        vocab = {w for w, c in freq.items() if c >= int(min_count) and len(w) <= MAX_WORD_LEN}
+        seqs = [[BOS] + [w if w in vocab else UNK for w in s] + [EOS] for s in sents]
+        p0 = 1.0 / (len(vocab) + 2)
+        counts = []                                              # counts[k-1][h][w]
+        for k in range(1, order + 1):
+            ck = collections.defaultdict(collections.Counter)
+            for s in seqs:
+                for i in range(max(1, k - 1), len(s)):
+                    ck[tuple(s[i - k + 1:i])][s[i]] += 1
+            counts.append(ck)
+        prob = [dict() for _ in range(order)]                    # prob[k-1][h + (w,)] = p_k(w | h)
+        bowp = [dict() for _ in range(order)]                    # bowp[k-1][h] = the back-off mass of the k-1 words h
+
+        def lower(k, h, w):                                      # the model of order k at (w | h), len(h) == k - 1
+            if k == 0:
+                return p0
+            p = prob[k - 1].get(h + (w,))
+            if p is not None:
+                return p
+            return bowp[k - 1].get(h, 1.0) * lower(k - 1, h[1:], w)
+
+        for k in range(1, order + 1):
+            for h, cw in counts[k - 1].items():
+                c, n1 = float(sum(cw.values())), float(len(cw))
+                bowp[k - 1][h] = n1 / (c + n1)
+                targets = list(cw) if k > 1 else sorted(vocab) + [EOS, UNK]
+                for w in targets:
+                    prob[k - 1][h + (w,)] = (cw.get(w, 0) + n1 * lower(k - 1, h[1:], w)) / (c + n1)
+        grams = []
+        for k in range(1, order + 1):
+            items = {}
+            for key, p in prob[k - 1].items():
+                b = bowp[k].get(key, 1.0) if k < order else 1.0
+                items[key] = (math.log(p), math.log(b))
+            if k == 1:
+                b = bowp[1].get((BOS,), 1.0) if order > 1 else 1.0
+                items[(BOS,)] = (ARPA_NEVER * _LN10, math.log(b))
+            grams.append(items)
+        return cls._build(grams, order, int(blank), int(char2ind[delimiter]))
+
+    @classmethod
+    def from_arpa(cls, path, char2ind, skip_unknown=False, blank=0, delimiter=" "):
+        """Read the standard ARPA text format (log10 -> ln).  A word is spelled through ``char2ind``; <s>, </s>, <unk> are the
+        reserved entries (added with log10 p = -99 and no back-off weight where the file lacks them).  An n-gram with a word that
+        cannot be spelled in the alphabet (a character outside it, more than MAX_WORD_LEN characters, or a word without a
+        unigram) raises, or is dropped with ``skip_unknown=True``: the decoder can never emit such a word."""
+        reserved = {name: i for i, name in enumerate(ARPA_RESERVED)}
+        grams, k, known = [], 0, {BOS, EOS, UNK}
+
+        def spell(w):
+            if w in reserved:
+                return reserved[w]
+            if not 1 <= len(w) <= MAX_WORD_LEN:
+                return None
+            ids = [char2ind.get(c, -1) for c in w]
+            if min(ids) < 0 or max(ids) > 255 or int(blank) in ids:
+                return None
+            return bytes(ids)
+
+        with open(path, "r") as fo:
+            for raw in fo:
+                ln = raw.strip()
+                if not ln or ln == "\\data\\" or ln.startswith("ngram "):
+                    continue
+                if ln == "\\end\\":
+                    break
+                if ln.startswith("\\") and ln.endswith("-grams:"):
+                    k = int(ln[1:-len("-grams:")])
+                    if k != len(grams) + 1 or k > MAX_WORD_ORDER:
+                        raise ValueError(f"{path}: the sections must be 1-grams .. n-grams in order, n <= {MAX_WORD_ORDER} (got {k})")
+                    grams.append({})
+                    continue
+                if k == 0:
+                    raise ValueError(f"{path}: {ln!r} stands before the first section")
+                f = ln.split()
+                if len(f) not in (k + 1, k + 2):
+                    raise ValueError(f"{path}: {ln!r} is no {k}-gram line")
+                key = tuple(spell(w) for w in f[1:k + 1])
+                if any(w is None for w in key) or (k > 1 and any(w not in known for w in key)):
+                    if skip_unknown:
+                        continue
+                    raise ValueError(f"{path}: {' '.join(f[1:k + 1])!r} holds a word that cannot be spelled in the alphabet")
+                if k == 1:
+                    known.add(key[0])
+                grams[k - 1][key] = (float(f[0]) * _LN10, float(f[k + 1]) * _LN10 if len(f) == k + 2 else 0.0)
+        if not grams:
+            raise ValueError(f"{path}: no n-gram section")
+        for r in (BOS, EOS, UNK):
+            grams[0].setdefault((r,), (ARPA_NEVER * _LN10, 0.0))
+        return cls._build(grams, len(grams), int(blank), int(char2ind.get(delimiter, -1)))
+
+    def to_arpa(self, path, ind2char):
+        """Write the standard ARPA text format (ln -> log10, 17 significant digits: ``from_arpa`` returns the same arrays)."""
+        names = list(ARPA_RESERVED) + ["".join(ind2char[int(t)] for t in s) for s in self.spellings[N_RESERVED:]]
+        with open(path, "w") as fo:
+            fo.write("\\data\\\n")
+            for k in range(1, self.order + 1):
+                fo.write(f"ngram {k}={self.ngrams[k - 1].shape[0]}\n")
+            for k in range(1, self.order + 1):
+                fo.write(f"\n\\{k}-grams:\n")
+                g, lp, bw = self.ngrams[k - 1], self.logp[k - 1].astype(np.float64) / _LN10, self.bow[k - 1].astype(np.float64) / _LN10
+                for i in range(g.shape[0]):
+                    text = " ".join(names[j] for j in g[i])
+                    fo.write(f"{float(lp[i])!r}\t{text}" + (f"\t{float(bw[i])!r}\n" if k < self.order else "\n"))
+            fo.write("\n\\end\\\n")
+
+    # ---------------------------------------------------------------- persistence
+    def save(self, path):
+        arrays = {"word_pool": self.word_pool, "word_off": self.word_off, "order": np.int64(self.order),
+                  "blank": np.int64(self.blank), "delimiter": np.int64(self.delimiter)}
+        for k in range(1, self.order + 1):
+            arrays[f"ngrams_{k}"], arrays[f"logp_{k}"], arrays[f"bow_{k}"] = self.ngrams[k - 1], self.logp[k - 1], self.bow[k - 1]
+        with open(path, "wb") as fo:
+            np.savez(fo, **arrays)
+
+    @classmethod
+    def load(cls, path):
+        with np.load(path, allow_pickle=False) as z:
+            ks = range(1, int(z["order"]) + 1)
+            return cls(z["word_pool"], z["word_off"], [z[f"ngrams_{k}"] for k in ks], [z[f"logp_{k}"] for k in ks],
+                       [z[f"bow_{k}"] for k in ks], blank=int(z["blank"]), delimiter=int(z["delimiter"]))
+
+    # ---------------------------------------------------------------- queries (the host's own statement)
+    def word_id(self, tokens):
+        """The id of the word spelled by ``tokens``, or UNK: a word longer than MAX_WORD_LEN, or with a token outside the byte
+        range, is in no vocabulary."""
+        tokens = [int(t) for t in tokens]
+        if not 1 <= len(tokens) <= MAX_WORD_LEN or min(tokens) < 0 or max(tokens) > 255:
+            return UNK
+        return self._word_id.get(bytes(tokens), UNK)
+
+    def _entries(self):
+        if self._table is None:
+            tab = {}
+            for k in range(1, self.order + 1):
+                g, lp, bw = self.ngrams[k - 1].tolist(), self.logp[k - 1].astype(np.float64).tolist(), \
+                    self.bow[k - 1].astype(np.float64).tolist()
+                for i, key in enumerate(g):
+                    tab[tuple(key)] = (lp[i], bw[i])
+            self._table = tab
+        return self._table
+
+    def score(self, context, w):
+        """ln p(w | context) by the back-off rule: ``context`` any sequence of earlier word ids, most recent last."""
+        tab = self._entries()
+        h = tuple(int(c) for c in context)[-(self.order - 1):] if self.order > 1 else ()
+        h = (BOS,) * (self.order - 1 - len(h)) + h
+        w, acc = int(w), 0.0
+        while True:
+            e = tab.get(h + (w,))
+            if e is not None:
+                return acc + e[0]
+            c = tab.get(h)
+            if c is not None:
+                acc = acc + c[1]
+            h = h[1:]
+
+    def split(self, token_ids, delimiter=None):
+        """The words of a sentence: the maximal runs of non-delimiter tokens, as str.split() cuts them."""
+        d = self.delimiter if delimiter is None else int(delimiter)
+        words, cur = [], []
+        for t in token_ids:
+            if int(t) == d:
+                if cur:
+                    words.append(tuple(cur))
+                cur = []
+            else:
+                cur.append(int(t))
+        if cur:
+            words.append(tuple(cur))
+        return words
+
+    def logp_sentence(self, token_ids, delimiter=None):
+        """(word_logp, n_words, n_oov) of a sentence of token ids: the fp64 sum of its words' scores in word order, then the score
+        of </s>; n_words does not count </s>; an empty sentence scores score(</s> | <s>)."""
+        ids = [self.word_id(w) for w in self.split(token_ids, delimiter)]
+        hist, total = [BOS] * (self.order - 1), 0.0
+        for w in ids + [EOS]:
+            total = total + self.score(hist, w)
+            hist.append(w)
+        return total, len(ids), sum(1 for w in ids if w == UNK)
+
+    # ---------------------------------------------------------------- the device's tables
+    def pack(self):
+        """The tables csrc/word_lm.hip reads, as numpy arrays (deterministic; both hash tables are open-addressed with linear
+        probing and at most half full):
+            word_slots (word_cap) int32: a word id or -1; a word is found from hash_word(spelling) & (word_cap - 1) on, and
+                confirmed on its spelling in word_pool / word_off.
+            uni_logp, uni_bow (n_words) fp32: the unigrams, at the word's id.  Entry index of a unigram: the word id.
+            ngram_slots (ngram_cap, 4) int32: (index of the context entry, word id, logp bits, bow bits), or ctx = -1 for an empty
+                slot; the n-grams of all orders >= 2 share the table.  Entry index of the n-gram in slot s: n_words + s.  An
+                n-gram is found from hash_ngram(ctx, word) & (ngram_cap - 1) on, and confirmed on the pair (ctx, word)."""
+        if self._packed is not None:
+            return self._packed
+        n_real = self.n_words - N_RESERVED
+        word_cap = _table_size(n_real)
+        word_slots = np.full(word_cap, -1, dtype=np.int32)
+        if n_real:
+            pos = _place(hash_word(self.spellings[N_RESERVED:]).astype(np.int64), np.zeros(word_cap, dtype=bool))
+            word_slots[pos] = np.arange(N_RESERVED, self.n_words, dtype=np.int32)
+        n_high = sum(g.shape[0] for g in self.ngrams[1:])
+        ngram_cap = _table_size(n_high)
+        slots = np.zeros((ngram_cap, 4), dtype=np.int32)
+        slots[:, 0] = -1
+        used = np.zeros(ngram_cap, dtype=bool)
+        entry = np.arange(self.n_words, dtype=np.int64)         # entry index of every row of the order below
+        for k in range(2, self.order + 1):
+            g = self.ngrams[k - 1]
+            ctx = entry[self.ctx_row[k - 1]] if g.shape[0] else np.zeros(0, dtype=np.int64)
+            pos = _place((hash_ngram(ctx, g[:, k - 1]) & np.uint64(ngram_cap - 1)).astype(np.int64), used)
+            slots[pos, 0] = ctx
+            slots[pos, 1] = g[:, k - 1]
+            slots[pos, 2] = self.logp[k - 1].view(np.int32)
+            slots[pos, 3] = self.bow[k - 1].view(np.int32)
+            entry = self.n_words + pos
+        self._packed = {"word_pool": self.word_pool if self.word_pool.size else np.zeros(1, dtype=np.uint8),
+                        "word_off": self.word_off, "word_slots": word_slots,
+                        "uni_logp": self.logp[0], "uni_bow": self.bow[0], "ngram_slots": slots}
+        return self._packed
+
+    def device_tables(self, device):
+        """The packed tables as tensors on ``device`` and the POD struct of their addresses that pgasr_nbest_word_lm_score takes
+        (made once per device; the tensors live as long as the model)."""
+        import torch
+        from . import _lib
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        t = self._device_tables.get(device)
+        if t is None:
+            p = self.pack()
+            tensors = {k: torch.from_numpy(np.ascontiguousarray(v)).to(device).contiguous() for k, v in p.items()}
+            st = _lib.WordLMTables(tensors["word_pool"].data_ptr(), tensors["word_off"].data_ptr(), tensors["word_slots"].data_ptr(),
+                                   tensors["uni_logp"].data_ptr(), tensors["uni_bow"].data_ptr(), tensors["ngram_slots"].data_ptr(),
+                                   self.order, self.n_words, p["word_slots"].size, p["ngram_slots"].shape[0], self.word_pool.size)
+            t = self._device_tables[device] = WordLMDeviceTables(st, tensors)
         return t

@@ -484,7 +484,7 @@ def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset
 def predict(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=None, maxlent=None, device_id=0,
             test_dataset=None, n_feats=120, beam_size=5, features="mfcc", lm_path=None, lm_alpha=0.0, lm_beta=0.0,
             nbest=1, rescore_lm_path=None, rescore_alpha=0.0, rescore_beta=0.0, lm_fast=False, target_rate=None,
-            mbr=False, mbr_unit="char", mbr_scale=1.0):
+            mbr=False, mbr_unit="char", mbr_scale=1.0, rescore_word_lm_path=None, rescore_word_alpha=0.0, rescore_word_beta=0.0):
     """model.py:277-339: load model_best.pth, forward, beam=5 prefix search (device side, batched),
     collapse_fn, CER/WER, predicted.txt.  Frames are cut by the FEATURE mask (the reference cuts the
     time axis by the target mask, model.py:322 -- a listed defect).  Returns (CER, WER).
@@ -510,12 +510,17 @@ def predict(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=N
     rescore_lm_path and the exact CTC likelihood without; the hypothesis of least expected character (mbr_unit="char") or word
     (mbr_unit="word", words split at the alphabet's " ") edit distance to the rest of its list is the one written to predicted.txt
     and scored, the CER / WER of the best-scored rows are printed beside its own, and ``mbr.tsv`` in model_path gets one line per
-    utterance: utterance, chosen rank, its expected errors, rank 0's expected errors, tab-separated."""
+    utterance: utterance, chosen rank, its expected errors, rank 0's expected errors, tab-separated.
+    rescore_word_lm_path: None (default: everything above, nothing else) or a ``word_lm.npz`` of ``build_word_lm`` /
+    ``WordNgramLM.save``, with nbest >= 2: the second pass also scores every hypothesis' words (split at the alphabet's " ") under
+    the word n-gram LM, total -= rescore_word_alpha * ln p_word + rescore_word_beta * words (``CTCDecoder.rescore(word_lm=)``), on top
+    of the exact CTC likelihood and, with rescore_lm_path, the character LM; with mbr=True the posterior comes from these totals.
+    ``nbest.tsv`` then has three more columns: word_logp, n_words, n_oov."""
     import os
     import functools
     import torch.utils.data as tud
     from .CTCdecoder import CTCDecoder, collapse_fn
-    from .lm import CharNgramLM
+    from .lm import CharNgramLM, WordNgramLM
     from .data import Data
     from .data import collate_custom as _collate
     from .metrics import edit_dist_batch, evaluate, save_predictions
@@ -525,6 +530,8 @@ def predict(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=N
         raise ValueError(f"nbest must lie in [1, beam_size = {beam_size}] (got {nbest})")
     if rescore_lm_path is not None and nbest < 2:
         raise ValueError("rescoring needs a list: give nbest >= 2 with rescore_lm_path")
+    if rescore_word_lm_path is not None and nbest < 2:
+        raise ValueError("rescoring needs a list: give nbest >= 2 with rescore_word_lm_path")
     if mbr and nbest < 2:
         raise ValueError("minimum-Bayes-risk decoding needs a list: give nbest >= 2 with mbr=True")
     if mbr and mbr_unit not in ("char", "word"):
@@ -545,6 +552,11 @@ def predict(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=N
     if mbr and mbr_unit == "word" and " " not in char2ind:
         raise ValueError("mbr_unit='word' needs an alphabet with the ' ' symbol")
     rescore_lm = CharNgramLM.load(rescore_lm_path) if rescore_lm_path is not None else None
+    if rescore_word_lm_path is not None and " " not in char2ind:
+        raise ValueError("rescore_word_lm_path needs an alphabet with the ' ' symbol")
+    word_lm = WordNgramLM.load(rescore_word_lm_path) if rescore_word_lm_path is not None else None
+    word_args = {} if word_lm is None else {"word_lm": word_lm, "word_lm_alpha": rescore_word_alpha, "word_lm_beta": rescore_word_beta,
+                                            "word_delimiter": char2ind[" "]}
     targets, predicted, tot_cer, tot_wer, n = [], [], 0.0, 0.0, 0
     nbest_lines, tot_oracle = [], 0.0
     mbr_lines, map_cer, map_wer = [], 0.0, 0.0
@@ -557,12 +569,15 @@ def predict(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=N
             lp = Fh.LogSoftmaxFn.apply(logits)
             if nbest > 1:
                 nb = decoder.decode_batch(lp, in_len, beam_size=beam_size, nbest=nbest)
-                tok, tl, total = nb.tokens[0], nb.lengths[0], None
-                if rescore_lm is not None:
-                    rs = decoder.rescore(lp, in_len, nb, lm=rescore_lm, lm_alpha=rescore_alpha, lm_beta=rescore_beta)
+                tok, tl, total, words = nb.tokens[0], nb.lengths[0], None, None
+                if rescore_lm is not None or word_lm is not None:
+                    rs = decoder.rescore(lp, in_len, nb, lm=rescore_lm, lm_alpha=rescore_alpha if rescore_lm is not None else 0.0,
+                                         lm_beta=rescore_beta if rescore_lm is not None else 0.0, **word_args)
                     tok, tl, total = rs.best_tokens, rs.best_len, rs.total.cpu()
+                    if word_lm is not None:
+                        words = (rs.word_logp.cpu(), rs.n_words.cpu(), rs.n_oov.cpu())
                 if mbr:
-                    score = rs.total if rescore_lm is not None else decoder.rescore(lp, in_len, nb, lm=None).total
+                    score = rs.total if total is not None else decoder.rescore(lp, in_len, nb, lm=None).total
                     md = decoder.mbr_from_list(nb, score, vocab=lp.shape[2], risk_unit=mbr_unit, posterior_scale=mbr_scale,
                                                word_delimiter=char2ind[" "] if mbr_unit == "word" else None)
                     map_tok, map_tl, tok, tl = tok.cpu(), tl.cpu(), md.tokens, md.lengths
@@ -580,8 +595,11 @@ def predict(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=N
                     for r in range(int(ncount[i])):
                         text = collapse_fn("".join(ind2char[int(k)] for k in ntok[r, i, :nlen[r, i]]))
                         refs.append(target); hyps.append(text); owner.append(i)
-                        nbest_lines.append("{}\t{}\t{:.6f}\t{}\t{}\n".format(n + i, r, float(nscore[r, i]),
-                                                                          "" if total is None else "{:.6f}".format(float(total[r, i])), text))
+                        extra = "" if words is None else "\t{:.6f}\t{}\t{}".format(float(words[0][r, i]), int(words[1][r, i]),
+                                                                                  int(words[2][r, i]))
+                        nbest_lines.append("{}\t{}\t{:.6f}\t{}\t{}{}\n".format(n + i, r, float(nscore[r, i]),
+                                                                            "" if total is None else "{:.6f}".format(float(total[r, i])),
+                                                                            text, extra))
                 best = {}
                 for i, d in zip(owner, edit_dist_batch(refs, hyps, device=dev)):
                     best[i] = min(d, best.get(i, d))
@@ -679,4 +697,22 @@ def build_lm(corpus_path, order=3, out_path=None, train_dataset=None):
     lines = [train_dataset[i]["trans"] for i in range(len(train_dataset))]
     lm = CharNgramLM.from_text(lines, char2ind, order=order, blank=0)
     lm.save(out_path if out_path is not None else os.path.join(corpus_path, "lm.npz"))
+    return lm
+
+
+def build_word_lm(corpus_path, order=3, min_count=1, out_path=None, train_dataset=None):
+    """Word n-gram LM (lm.WordNgramLM, interpolated Witten-Bell in back-off form) from the transcripts that Data(train.tsv) yields,
+    words split at " " and spelled in the symbols of <corpus_path>/alphabet.txt; saved to ``out_path`` (default
+    <corpus_path>/word_lm.npz, beside ``build_lm``'s lm.npz) for ``predict(rescore_word_lm_path=...)``.  Words seen fewer than
+    ``min_count`` times count as <unk>.  ``train_dataset``: any Dataset whose items carry "trans", instead of train.tsv.
+    Returns the LM."""
+    import os
+    from .data import Data
+    from .lm import WordNgramLM
+    _, char2ind = _read_alphabet(os.path.join(corpus_path, "alphabet.txt"))
+    if train_dataset is None:
+        train_dataset = Data(os.path.join(corpus_path, "train.tsv"), os.path.join(corpus_path, "clips"), char2ind)
+    lines = [train_dataset[i]["trans"] for i in range(len(train_dataset))]
+    lm = WordNgramLM.from_text(lines, char2ind, order=order, min_count=min_count, delimiter=" ", blank=0)
+    lm.save(out_path if out_path is not None else os.path.join(corpus_path, "word_lm.npz"))
     return lm
