@@ -52,7 +52,7 @@ typedef enum pgasr_status {
  * (pgasr_frame_kl, pgasr_ctc_grad_from_lattice_kl, pgasr_ctc_grad_from_lattice_multi_kl, pgasr_ctc_grad_from_lattices_seq_kl),
  * sample-rate conversion / speed perturbation (pgasr_resample), and minimum-Bayes-risk decoding over N-best lists
  * (pgasr_nbest_pair_dist, pgasr_mbr_select), and waveform augmentation (pgasr_reverb_limits, pgasr_reverb, pgasr_wave_power,
- * pgasr_wave_mix). */
+ * pgasr_wave_mix), and edit-operation alignment (pgasr_edit_ops_workspace_bytes, pgasr_edit_ops). */
 #define PGASR_ABI_VERSION 7
 
 int pgasr_abi_version(void);
@@ -396,6 +396,38 @@ int pgasr_ctc_collapse(const int32_t* paths, const int32_t* lengths, int P, int 
 int pgasr_edit_distance(const int32_t* ref, const int32_t* ref_len, int ref_stride,
                         const int32_t* hyp, const int32_t* hyp_len, int hyp_stride,
                         int N, int32_t* dist, int32_t* prefix_dist, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * A10-OPS  edit-operation alignment (csrc/editops.hip): WHICH edits make up the distance of A10 -- hits, substitutions, deletions
+ * and insertions per pair, the operation string, and a confusion matrix.  Inputs as for pgasr_edit_distance: int32 rows of
+ * arbitrary int32 symbols (word-id rows of pgasr_word_ids included), lengths clamped to [0, stride].
+ *   The alignment is contractual, because almost every pair has several optimal ones and S / D / I differ between them.  With
+ *   D[i][j] the Levenshtein matrix over reference prefix i and hypothesis prefix j, walk back from (n, m); at (i, j) take
+ *     the diagonal   if i, j > 0 and D[i-1][j-1] + (ref[i-1] != hyp[j-1]) == D[i][j],
+ *     else deletion  if i > 0 and D[i-1][j] + 1 == D[i][j]      (a reference symbol with no partner),
+ *     else insertion                                            (a hypothesis symbol with no partner).
+ *   The result does not depend on which sequence the kernel lays across its lanes.
+ *   counts (N,4) int32, required: hits, substitutions, deletions, insertions.  H + S + D = n, H + S + I = m, S + D + I = the distance.
+ *   ops (N, ref_stride + hyp_stride) int8 or NULL (counts only): the operations left to right, 0 = hit, 1 = substitution,
+ *     2 = deletion, 3 = insertion; every entry from n_ops[n] on is written as -1, so the buffer may be uninitialised.
+ *   n_ops (N) int32: the length of the string (H + S + D + I); required with ops, else optional.
+ *   confusion: NULL, or an int64 matrix (vocab+1) x (vocab+1), 1 <= vocab <= 64, that the kernel ADDS into: [r][h] every hit and
+ *     substitution, [r][vocab] deletions of r, [vocab][h] insertions of h.  An operation that involves a symbol outside
+ *     [0, vocab) is counted in counts and left out of the matrix.  Integer adds: the sums do not depend on their order.
+ *   workspace: pgasr_edit_ops_workspace_bytes(ref_stride, hyp_stride, N) bytes, 4-byte aligned: the 2-bit choice of every DP
+ *     cell, min(stride) rows of 64 * J cells, J = ceil((max(stride) + 1) / 64) rounded up to a power of two, a quarter byte each
+ *     (3 KB per pair at 100 x 100, 4 MB at 4095 x 4095).
+ *     The query is host-only and needs no GPU; it returns 0 for sizes the kernel refuses.
+ *   Checked before any HIP call, in this order: null ref_len / hyp_len / counts, N <= 0, a negative stride, a null row pointer
+ *   with a positive stride, ops without n_ops, confusion with vocab < 1 -> PGASR_ERR_INVALID_ARG; the longer stride above 4095,
+ *   confusion with vocab > 64 -> PGASR_ERR_UNSUPPORTED; a workspace that is NULL or too small -> PGASR_ERR_WORKSPACE.
+ *   One launch, one wave per pair, no host synchronisation.
+ * ---------------------------------------------------------------------------------------- */
+size_t pgasr_edit_ops_workspace_bytes(int ref_stride, int hyp_stride, int N);
+int pgasr_edit_ops(const int32_t* ref, const int32_t* ref_len, int ref_stride,
+                   const int32_t* hyp, const int32_t* hyp_len, int hyp_stride, int N,
+                   int32_t* counts, int8_t* ops, int32_t* n_ops, long long* confusion, int vocab,
+                   void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * A12  REINFORCE gradient on the logits:

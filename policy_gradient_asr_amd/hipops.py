@@ -834,6 +834,70 @@ def word_edit_distance(ref, ref_len, hyp, hyp_len, delimiter):
     return edit_distance(ref_ids, ref_words, hyp_ids, hyp_words), ref_words, hyp_words
 
 
+EditOps = collections.namedtuple("EditOps", "counts ops n_ops")
+WordEditOps = collections.namedtuple("WordEditOps", "counts ops n_ops ref_words hyp_words")
+EDIT_OPS_MAX_VOCAB = 64          # csrc/editops.hip: the confusion matrix
+
+
+def edit_ops_workspace_bytes(ref_stride, hyp_stride, N):
+    """Bytes of workspace one ``pgasr_edit_ops`` launch over N pairs of these strides needs (host only, no GPU)."""
+    return int(_lib.load().pgasr_edit_ops_workspace_bytes(int(ref_stride), int(hyp_stride), int(N)))
+
+
+def edit_ops(ref, ref_len, hyp, hyp_len, want_ops=True, confusion=None, vocab=None, max_workspace_bytes=256 << 20):
+    """The canonical optimal alignment of N (reference, hypothesis) pairs (include/pgasr_hip.h, A10-OPS): diagonal before deletion
+    before insertion on the walk back.  ref (N,R), hyp (N,Hy) int32 rows of arbitrary symbols with lengths (N) int32, on the GPU.
+    Returns ``EditOps`` of device tensors: counts (N,4) int32 = hits, substitutions, deletions, insertions; with ``want_ops`` ops
+    (N,R+Hy) int8 -- 0 hit, 1 substitution, 2 deletion, 3 insertion, left to right, -1 from n_ops on -- and n_ops (N) int32, else
+    None in their places.  confusion: None, or a (vocab+1, vocab+1) int64 device matrix the kernel ADDS into ([r][h] hits and
+    substitutions, [r][vocab] deletions, [vocab][h] insertions; symbols outside [0, vocab) are left out), vocab <= 64.
+    N is split into chunks so that no launch needs more than ``max_workspace_bytes`` of workspace (the cached "edit_ops" buffer);
+    a cap below one pair's workspace raises.  Current stream, no host synchronisation."""
+    lib = _lib.load()
+    _req(ref, torch.int32, "ref"); _req(hyp, torch.int32, "hyp")
+    _req(ref_len, torch.int32, "ref_len"); _req(hyp_len, torch.int32, "hyp_len")
+    if ref.dim() != 2 or hyp.dim() != 2 or hyp.shape[0] != ref.shape[0] or ref_len.numel() != ref.shape[0] or hyp_len.numel() != ref.shape[0]:
+        raise _lib.PgasrError("edit_ops wants ref (N,R), hyp (N,Hy) and lengths (N)")
+    N, R = ref.shape
+    Hy = hyp.shape[1]
+    dev = ref.device
+    if confusion is not None:
+        _req(confusion, torch.int64, "confusion")
+        if vocab is None or int(vocab) < 1 or tuple(confusion.shape) != (int(vocab) + 1, int(vocab) + 1):
+            raise _lib.PgasrError("edit_ops: confusion must be (vocab+1, vocab+1) int64 with vocab >= 1 given")
+    vocab = 0 if confusion is None else int(vocab)
+    counts = torch.empty(N, 4, dtype=torch.int32, device=dev)
+    ops = torch.empty(N, R + Hy, dtype=torch.int8, device=dev) if want_ops else None
+    n_ops = torch.empty(N, dtype=torch.int32, device=dev) if want_ops else None
+    if N == 0:
+        return EditOps(counts, ops, n_ops)
+    per_pair = int(lib.pgasr_edit_ops_workspace_bytes(R, Hy, 1))
+    if per_pair > int(max_workspace_bytes):
+        raise _lib.PgasrError(f"edit_ops: one pair of strides {R} / {Hy} needs {per_pair} bytes of workspace, above "
+                              f"max_workspace_bytes = {int(max_workspace_bytes)}")
+    chunk = N if per_pair == 0 else max(1, min(N, int(max_workspace_bytes) // per_pair))
+    nbytes = int(lib.pgasr_edit_ops_workspace_bytes(R, Hy, chunk))
+    ws = _workspace(nbytes, dev, "edit_ops")
+    with _timed("edit_ops"):
+        for a in range(0, N, chunk):
+            b = min(N, a + chunk)
+            st = lib.pgasr_edit_ops(ref[a:b].data_ptr() if R else 0, ref_len[a:b].data_ptr(), R,
+                                    hyp[a:b].data_ptr() if Hy else 0, hyp_len[a:b].data_ptr(), Hy, b - a,
+                                    counts[a:b].data_ptr(), ops[a:b].data_ptr() if want_ops and R + Hy else 0,
+                                    n_ops[a:b].data_ptr() if want_ops else 0, _p(confusion), vocab, _p(ws), ws.numel(), _stream())
+            _lib.check(st, "pgasr_edit_ops")
+    return EditOps(counts, ops, n_ops)
+
+
+def word_edit_ops(ref, ref_len, hyp, hyp_len, delimiter, want_ops=True, max_workspace_bytes=256 << 20):
+    """Word-level alignment of N token-row pairs: ``word_ids`` then ``edit_ops`` on the id rows (words are the runs between
+    ``delimiter`` tokens, as str.split(" ") cuts the decoded rows).  Returns ``WordEditOps``: counts (N,4), ops (N,R+Hy+2) / n_ops
+    as ``edit_ops`` gives them over words, and the word counts ref_words / hyp_words (N) int32."""
+    ref_ids, ref_words, hyp_ids, hyp_words = word_ids(ref, ref_len, hyp, hyp_len, delimiter)
+    eo = edit_ops(ref_ids, ref_words, hyp_ids, hyp_words, want_ops=want_ops, max_workspace_bytes=max_workspace_bytes)
+    return WordEditOps(eo.counts, eo.ops, eo.n_ops, ref_words, hyp_words)
+
+
 def reinforce_grad(scores, path, coef, lengths, out=None, accumulate=False):
     lib = _lib.load()
     _req(scores, torch.float32, "scores"); _req(path, torch.int32, "path")

@@ -1,5 +1,6 @@
 """Drop-in for the reference's metrics.py (edit_dist, evaluate, save_predictions) on the HIP
-Levenshtein kernel (csrc/editdist.hip)."""
+Levenshtein kernel (csrc/editdist.hip), and the error breakdown on the alignment kernel (csrc/editops.hip)."""
+import collections
 import os
 
 import torch
@@ -62,6 +63,195 @@ def edit_counts(targets, tg_len, tokens, tok_len, delimiter):
     cd = hipops.edit_distance(targets, tg_len, tokens, tok_len)
     wd, wc, _ = hipops.word_edit_distance(targets, tg_len, tokens, tok_len, delimiter)
     return cd, tg_len, wd, wc
+
+
+def error_counts(targets, tg_len, tokens, tok_len, delimiter):
+    """``edit_counts`` with the errors told apart: (character counts (B,4), word counts (B,4)) int32 on the device, columns hits,
+    substitutions, deletions, insertions of the canonical alignment (``hipops.edit_ops``: diagonal before deletion before insertion);
+    words split at the token ``delimiter``.  Per row S + D + I is the distance and H + S + D the reference length that
+    ``edit_counts`` returns.  No host round trip."""
+    cc = hipops.edit_ops(targets, tg_len, tokens, tok_len, want_ops=False).counts
+    wc = hipops.word_edit_ops(targets, tg_len, tokens, tok_len, delimiter, want_ops=False).counts
+    return cc, wc
+
+
+def _pad_rows(seqs, device):
+    n = len(seqs)
+    width = max(max((len(s) for s in seqs), default=0), 1)
+    rows = torch.zeros(n, width, dtype=torch.int32)
+    lens = torch.zeros(n, dtype=torch.int32)
+    for i, s in enumerate(seqs):
+        if len(s):
+            rows[i, :len(s)] = torch.tensor(s, dtype=torch.int32)
+        lens[i] = len(s)
+    return rows.to(device), lens.to(device)
+
+
+def edit_ops_batch(refs, hyps, device=None):
+    """The canonical alignments of many (reference, hypothesis) pairs in one launch, beside ``edit_dist_batch``: refs / hyps are lists
+    of sequences (str or list of tokens).  Returns per pair (hits, substitutions, deletions, insertions, ops), ops the list of
+    operations left to right: 0 hit, 1 substitution, 2 deletion, 3 insertion."""
+    dev = _device(device)
+    enc = [_encode([r, h]) for r, h in zip(refs, hyps)]
+    if not enc:
+        return []
+    ref, rl = _pad_rows([e[0] for e in enc], dev)
+    hyp, hl = _pad_rows([e[1] for e in enc], dev)
+    eo = hipops.edit_ops(ref, rl, hyp, hl)
+    counts, ops, n_ops = eo.counts.tolist(), eo.ops.cpu(), eo.n_ops.tolist()
+    return [(c[0], c[1], c[2], c[3], ops[i, :n_ops[i]].tolist()) for i, c in enumerate(counts)]
+
+
+OP_LETTERS = (" ", "S", "D", "I")
+
+
+def _aligned_lines(ref, hyp, ops, gap="*"):
+    """sclite-style REF / HYP / OPS columns of one alignment: every column as wide as its widest entry, a run of ``gap`` where a
+    side has no partner, substituted entries in upper case."""
+    cols, i, j = [], 0, 0
+    for o in ops:
+        if o in (0, 1):
+            a, b = str(ref[i]), str(hyp[j]); i += 1; j += 1
+            if o == 1:
+                a, b = a.upper(), b.upper()
+        elif o == 2:
+            a = str(ref[i]); i += 1; b = gap * max(len(a), 1)
+        else:
+            b = str(hyp[j]); j += 1; a = gap * max(len(b), 1)
+        wd = max(len(a), len(b), 1)
+        cols.append((a.ljust(wd), b.ljust(wd), OP_LETTERS[o].ljust(wd)))
+    return tuple(" ".join(c[k] for c in cols).rstrip() for k in range(3))
+
+
+class ErrorReport:
+    """Corpus-level error statistics of decoded strings: S / D / I totals for characters and words, the character confusion matrix
+    and the word confusions, the line every ASR toolkit prints.
+
+    alphabet: the symbols, index = token id (at most 64; a character outside it is scored but stays out of the matrix);
+    delimiter: the symbol words are split at (str.split(delimiter) of the strings, as ``evaluate`` does).
+    ``add(refs, hyps)`` aligns a batch on the device (``hipops.edit_ops`` / ``word_edit_ops``): totals and the character confusion
+    matrix accumulate there, nothing is copied back until ``summary`` / ``write``.  Word confusions are read off the word operation
+    paths on the host, because words have no bounded vocabulary."""
+
+    def __init__(self, alphabet, delimiter=" ", device=None):
+        self.symbols = [str(s) for s in alphabet]
+        self.vocab = len(self.symbols)
+        if not 1 <= self.vocab <= hipops.EDIT_OPS_MAX_VOCAB:
+            raise ValueError(f"ErrorReport: the alphabet must have 1 .. {hipops.EDIT_OPS_MAX_VOCAB} symbols (got {self.vocab})")
+        self.delimiter = delimiter
+        self.sym2id = {}
+        for i, s in enumerate(self.symbols):
+            self.sym2id.setdefault(s, i)
+        # words are cut at the delimiter's token; an alphabet without it has one word per string, cut at a token that never occurs
+        self.delim_id = self.sym2id.get(delimiter, 1 << 30)
+        self.device = _device(device)
+        self.confusion = torch.zeros(self.vocab + 1, self.vocab + 1, dtype=torch.int64, device=self.device)
+        self.char_totals = torch.zeros(4, dtype=torch.int64, device=self.device)
+        self.word_totals = torch.zeros(4, dtype=torch.int64, device=self.device)
+        self._batches = []
+        self._extra = {}
+
+    def _ids(self, s):
+        out = []
+        for ch in s:
+            k = self.sym2id.get(ch)
+            if k is None:                  # outside the alphabet: an id of its own beyond the matrix
+                k = self._extra.setdefault(ch, self.vocab + 1 + len(self._extra))
+            out.append(k)
+        return out
+
+    def add(self, refs, hyps):
+        """refs / hyps: equally long lists of strings (reference, hypothesis).  No host synchronisation."""
+        refs, hyps = list(refs), list(hyps)
+        if len(refs) != len(hyps):
+            raise ValueError("ErrorReport.add: as many hypotheses as references")
+        if not refs:
+            return
+        ref, rl = _pad_rows([self._ids(s) for s in refs], self.device)
+        hyp, hl = _pad_rows([self._ids(s) for s in hyps], self.device)
+        ch = hipops.edit_ops(ref, rl, hyp, hl, want_ops=True, confusion=self.confusion, vocab=self.vocab)
+        wd = hipops.word_edit_ops(ref, rl, hyp, hl, self.delim_id, want_ops=True)
+        self.char_totals += ch.counts.sum(0)
+        self.word_totals += wd.counts.sum(0)
+        self._batches.append((refs, hyps, ch, wd))
+
+    def utterances(self):
+        """Per utterance (ref, hyp, character counts, character ops, word counts, word ops), copied from the device."""
+        out = []
+        for refs, hyps, ch, wd in self._batches:
+            cc, co, cn = ch.counts.tolist(), ch.ops.cpu(), ch.n_ops.tolist()
+            wc, wo, wn = wd.counts.tolist(), wd.ops.cpu(), wd.n_ops.tolist()
+            for i in range(len(refs)):
+                out.append((refs[i], hyps[i], cc[i], co[i, :cn[i]].tolist(), wc[i], wo[i, :wn[i]].tolist()))
+        return out
+
+    def confusions(self):
+        """Every confusion as (kind, ref, hyp, count), kind in char_sub / char_del / char_ins / word_sub / word_del / word_ins, sorted
+        by falling count (ties: kind, ref, hyp)."""
+        rows = []
+        cm = self.confusion.cpu()
+        V = self.vocab
+        for r in range(V + 1):
+            for h in range(V + 1):
+                c = int(cm[r, h])
+                if c == 0 or r == h:
+                    continue
+                if h == V:
+                    rows.append(("char_del", self.symbols[r], "", c))
+                elif r == V:
+                    rows.append(("char_ins", "", self.symbols[h], c))
+                else:
+                    rows.append(("char_sub", self.symbols[r], self.symbols[h], c))
+        words = collections.Counter()
+        for ref, hyp, _, _, _, wops in self.utterances():
+            rw, hw, i, j = ref.split(self.delimiter), hyp.split(self.delimiter), 0, 0
+            for o in wops:
+                if o == 1:
+                    words[("word_sub", rw[i], hw[j])] += 1
+                elif o == 2:
+                    words[("word_del", rw[i], "")] += 1
+                elif o == 3:
+                    words[("word_ins", "", hw[j])] += 1
+                i += o != 3; j += o != 2
+        rows += [(k[0], k[1], k[2], c) for k, c in words.items()]
+        rows.sort(key=lambda x: (-x[3], x[0], x[1], x[2]))
+        return rows
+
+    def summary(self, top_k=10):
+        """Corpus-level rates, (S + D + I) / reference length, with their breakdown: {"utterances", "cer", "wer", "char": {"ref",
+        "hits", "sub", "del", "ins"}, "word": {...}, "top_confusions": the first top_k rows of ``confusions``}.  Synchronises."""
+        out = {"utterances": sum(len(b[0]) for b in self._batches)}
+        for name, tot in (("char", self.char_totals.tolist()), ("word", self.word_totals.tolist())):
+            h, s, d, i = (int(x) for x in tot)
+            out[name] = {"ref": h + s + d, "hits": h, "sub": s, "del": d, "ins": i}
+            out["cer" if name == "char" else "wer"] = (s + d + i) / max(h + s + d, 1)
+        out["top_confusions"] = self.confusions()[:int(top_k)]
+        return out
+
+    def totals_lines(self):
+        """The two corpus-level lines, e.g. ``%WER 12.32 [ 456 / 3700, 40 ins, 96 del, 320 sub ]``."""
+        s = self.summary(top_k=0)
+        return ["%{} {:.2f} [ {} / {}, {} ins, {} del, {} sub ]".format(
+            tag, 100.0 * s[rate], v["sub"] + v["del"] + v["ins"], v["ref"], v["ins"], v["del"], v["sub"])
+            for tag, rate, v in (("CER", "cer", s["char"]), ("WER", "wer", s["word"]))]
+
+    def write(self, directory):
+        """errors.txt: per utterance a header with its counts and a REF / HYP / OPS triple of padded, aligned lines over words
+        (sclite style: a run of * where a side has no partner, substituted words in upper case), then the two totals lines.
+        confusions.tsv: a header, then kind, ref, hyp, count per confusion, sorted by falling count."""
+        with open(os.path.join(directory, "errors.txt"), "w") as fo:
+            for k, (ref, hyp, cc, _, wc, wops) in enumerate(self.utterances()):
+                fo.write("utt {}  char H/S/D/I {} {} {} {}  word H/S/D/I {} {} {} {}\n".format(k, *cc, *wc))
+                lines = _aligned_lines(ref.split(self.delimiter), hyp.split(self.delimiter), wops)
+                for tag, line in zip(("REF", "HYP", "OPS"), lines):
+                    fo.write("{}: {}\n".format(tag, line))
+                fo.write("\n")
+            for line in self.totals_lines():
+                fo.write(line + "\n")
+        with open(os.path.join(directory, "confusions.tsv"), "w") as fo:
+            fo.write("kind\tref\thyp\tcount\n")
+            for kind, r, h, c in self.confusions():
+                fo.write("{}\t{}\t{}\t{}\n".format(kind, r, h, c))
 
 
 def nbest_oracle(targets, tg_len, nb):

@@ -484,7 +484,8 @@ def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset
 def predict(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=None, maxlent=None, device_id=0,
             test_dataset=None, n_feats=120, beam_size=5, features="mfcc", lm_path=None, lm_alpha=0.0, lm_beta=0.0,
             nbest=1, rescore_lm_path=None, rescore_alpha=0.0, rescore_beta=0.0, lm_fast=False, target_rate=None,
-            mbr=False, mbr_unit="char", mbr_scale=1.0, rescore_word_lm_path=None, rescore_word_alpha=0.0, rescore_word_beta=0.0):
+            mbr=False, mbr_unit="char", mbr_scale=1.0, rescore_word_lm_path=None, rescore_word_alpha=0.0, rescore_word_beta=0.0,
+            error_report=False):
     """model.py:277-339: load model_best.pth, forward, beam=5 prefix search (device side, batched),
     collapse_fn, CER/WER, predicted.txt.  Frames are cut by the FEATURE mask (the reference cuts the
     time axis by the target mask, model.py:322 -- a listed defect).  Returns (CER, WER).
@@ -515,7 +516,12 @@ def predict(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=N
     ``WordNgramLM.save``, with nbest >= 2: the second pass also scores every hypothesis' words (split at the alphabet's " ") under
     the word n-gram LM, total -= rescore_word_alpha * ln p_word + rescore_word_beta * words (``CTCDecoder.rescore(word_lm=)``), on top
     of the exact CTC likelihood and, with rescore_lm_path, the character LM; with mbr=True the posterior comes from these totals.
-    ``nbest.tsv`` then has three more columns: word_logp, n_words, n_oov."""
+    ``nbest.tsv`` then has three more columns: word_logp, n_words, n_oov.
+    error_report: False (default: everything above, nothing else) or True: the strings that are scored (reference, collapsed
+    hypothesis) are also aligned on the device (``metrics.ErrorReport``), ``errors.txt`` -- per utterance a REF / HYP / OPS triple of
+    aligned lines, then the totals -- and ``confusions.tsv`` -- kind, ref, hyp, count, sorted by count -- are written into model_path,
+    and one corpus-level line, (S + D + I) / reference length with the S / D / I breakdown for characters and words, is printed after
+    the line above.  The return value (the MEAN of the per-utterance rates) and every other output stay what they are."""
     import os
     import functools
     import torch.utils.data as tud
@@ -557,6 +563,10 @@ def predict(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=N
     word_lm = WordNgramLM.load(rescore_word_lm_path) if rescore_word_lm_path is not None else None
     word_args = {} if word_lm is None else {"word_lm": word_lm, "word_lm_alpha": rescore_word_alpha, "word_lm_beta": rescore_word_beta,
                                             "word_delimiter": char2ind[" "]}
+    report = None
+    if error_report:
+        from .metrics import ErrorReport
+        report = ErrorReport([a.replace("\n", "") for a in alphabet], " ", device=dev)
     targets, predicted, tot_cer, tot_wer, n = [], [], 0.0, 0.0, 0
     nbest_lines, tot_oracle = [], 0.0
     mbr_lines, map_cer, map_wer = [], 0.0, 0.0
@@ -616,6 +626,8 @@ def predict(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=N
                 if mbr:
                     cer, wer = evaluate(target, collapse_fn("".join(ind2char[int(k)] for k in map_tok[i, :map_tl[i]])))
                     map_cer += cer; map_wer += wer
+            if report is not None:
+                report.add(targets[-tok.shape[0]:], predicted[-tok.shape[0]:])
     save_predictions(targets, predicted, model_path)
     cer, wer = tot_cer / max(n, 1), tot_wer / max(n, 1)
     if nbest > 1:
@@ -630,6 +642,9 @@ def predict(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=N
             print("CER: {:>4f} WER: {:>4f} Oracle CER ({}-best): {:>4f}".format(cer, wer, nbest, tot_oracle / max(n, 1)))
     else:
         print("CER: {:>4f} WER: {:>4f}".format(cer, wer))
+    if report is not None:
+        report.write(model_path)
+        print("Corpus " + "  ".join(report.totals_lines()))
     return cer, wer
 
 
