@@ -52,7 +52,8 @@ typedef enum pgasr_status {
  * (pgasr_frame_kl, pgasr_ctc_grad_from_lattice_kl, pgasr_ctc_grad_from_lattice_multi_kl, pgasr_ctc_grad_from_lattices_seq_kl),
  * sample-rate conversion / speed perturbation (pgasr_resample), and minimum-Bayes-risk decoding over N-best lists
  * (pgasr_nbest_pair_dist, pgasr_mbr_select), and waveform augmentation (pgasr_reverb_limits, pgasr_reverb, pgasr_wave_power,
- * pgasr_wave_mix), and edit-operation alignment (pgasr_edit_ops_workspace_bytes, pgasr_edit_ops). */
+ * pgasr_wave_mix), and edit-operation alignment (pgasr_edit_ops_workspace_bytes, pgasr_edit_ops), and the wide-alphabet entries
+ * (pgasr_log_softmax_rows_wide, pgasr_frame_argmax_sample_wide, pgasr_ctc_loss_grad_wide, pgasr_ctc_grad_from_lattice_wide). */
 #define PGASR_ABI_VERSION 7
 
 int pgasr_abi_version(void);
@@ -1197,6 +1198,43 @@ int pgasr_feat_deltas_stack(const float* mfcc, const int32_t* n_frames, int B, i
 /* x (B x Tmax x C) -> feat (B x C x Tmax), 0 past n_frames[b], and fmask (B x 1 x Tmax): the layout of data.py:64-79 for a front
  * end without deltas -- the 80-band log-mel features (F = 80 of the benchmark; features.LogMel). */
 int pgasr_feat_stack(const float* x, const int32_t* n_frames, int B, int Tmax, int C, float* feat, float* fmask, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * A5-WIDE / A9-WIDE  alphabets of up to PGASR_MAX_VOCAB_WIDE = 1024 symbols (subword units): the four kernels that hold a (t,b)
+ * row of scores in one wave, for rows of 1 <= V <= 1024 fp32 values.  One wave per row as before, lane l holding the
+ * NV = ceil(V / 64) (rounded up to 1, 2, 4, 8 or 16) consecutive labels l*NV .. l*NV + NV - 1 in registers.  The entries above keep
+ * what they accept (V <= 64) and what they launch; these take any V in the range, V <= 64 included.  Every sum is taken in a fixed
+ * order: two calls give the same bits.  Checked before any HIP call: V <= 0, T, B or rows <= 0, a blank outside [0, V), a missing
+ * required pointer -> PGASR_ERR_INVALID_ARG; V > 1024, and for the CTC pair 2 * Lmax + 1 > 2048 -> PGASR_ERR_UNSUPPORTED.
+ *   pgasr_log_softmax_rows_wide: pgasr_log_softmax_rows.  Row maximum, exp of the differences and their sum in fp32.
+ *   pgasr_frame_argmax_sample_wide: pgasr_frame_argmax_sample and, with utt_ids != NULL, pgasr_frame_argmax_sample_ids (ctr_base is
+ *     then ignored, ctr_stride >= 1 is required and T * ctr_stride must fit counter word 0, else PGASR_ERR_UNSUPPORTED).  The
+ *     arg-max takes the first maximum.  The sample uses the same Philox counter, key and u, the domain for rows beyond the global
+ *     batch included: k = min(#{v : cdf_v <= u * total}, V - 1) with the inclusive cdf of exp(score - max) in label order (a
+ *     sequential prefix over the lane's labels on top of the wave scan of the lane totals; with V <= 64 the narrow kernel's cdf).
+ *   pgasr_ctc_loss_grad_wide, pgasr_ctc_grad_from_lattice_wide: pgasr_ctc_loss_grad and pgasr_ctc_grad_from_lattice, argument for
+ *     argument, on the same workspace (pgasr_ctc_workspace_bytes, same format: either pair may run the gradient pass over the
+ *     other's lattice).  The alpha / beta sweeps are the same kernel, so nll has the same bits; the label lists and the gradient
+ *     pass utt_scale_b (softmax - occupancy) + pg_coef (softmax - onehot(pg_path)) are kernels of their own.  A symbol of
+ *     probability exactly 0 has occupancy 0 and gradient entry 0, rows t >= input_lengths[b] are written as zeros, an utterance
+ *     without an alignment (nll = +inf) gets no CTC part.
+ * ---------------------------------------------------------------------------------------- */
+#define PGASR_MAX_VOCAB_WIDE 1024
+int pgasr_log_softmax_rows_wide(const float* logits, long long rows, int V, float* log_probs, void* stream);
+int pgasr_frame_argmax_sample_wide(const float* scores, int T, int B, int V, uint64_t seed, uint32_t offset,
+                                   int ctr_stride, int ctr_base, const int32_t* utt_ids /* may be NULL */,
+                                   int32_t* greedy_path /* may be NULL */, int32_t* sample_path /* may be NULL */, void* stream);
+int pgasr_ctc_loss_grad_wide(const float* log_probs, const int32_t* targets,
+                             const int32_t* input_lengths, const int32_t* target_lengths,
+                             int T, int B, int V, int Lmax, int blank,
+                             const float* utt_scale, const float* pg_coef, const int32_t* pg_path,
+                             float* nll, float* grad_logits,
+                             void* workspace, size_t workspace_bytes, void* stream);
+int pgasr_ctc_grad_from_lattice_wide(const float* log_probs, const int32_t* input_lengths,
+                                     const int32_t* target_lengths, int T, int B, int V, int Lmax, int blank,
+                                     const float* utt_scale, const float* pg_coef, const int32_t* pg_path,
+                                     int pg_coef_per_frame, float* grad_logits, void* workspace, size_t workspace_bytes,
+                                     void* stream);
 
 #ifdef __cplusplus
 }

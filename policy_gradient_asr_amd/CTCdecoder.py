@@ -25,6 +25,14 @@ def _device(device=None):
 BEAM_KMAX = 128      # csrc/beam.hip
 
 
+def _check_search_vocab(V):
+    """The beam searches hold one symbol per lane; wider rows have the best-path decoder only."""
+    if V > hipops.MAX_VOCAB_NARROW:
+        raise ValueError(f"the beam search takes at most {hipops.MAX_VOCAB_NARROW} output symbols (got {V}): decode a wider alphabet "
+                         f"greedily -- CTCdecoder.greedy_decode, model.predict(beam_size=0) -- which takes up to "
+                         f"{hipops.MAX_VOCAB_WIDE}")
+
+
 _UNSET = object()      # "use the decoder's own value" (None is a value: no language model)
 
 NBestRescored = collections.namedtuple("NBestRescored", "order total am lm_logp best_tokens best_len skipped")
@@ -65,6 +73,7 @@ class CTCDecoder:
         dev = _device(self.device)
         probs = np.asarray(probs)
         T, V = probs.shape
+        _check_search_vocab(V)
         if T == 0:
             return (tuple(), -0.0) if nbest is None else [(tuple(), -0.0)]
         with np.errstate(divide="ignore"):
@@ -91,6 +100,7 @@ class CTCDecoder:
         score (N,B), count (B)), still without a host sync; see ``hipops.ctc_beam_search_nbest``.
         fast_lm: None (default: the decoder's own) or a bool -- with an LM, take the single-wave kernel where its limits allow."""
         fast_lm = self.fast_lm if fast_lm is None else bool(fast_lm)
+        _check_search_vocab(log_probs.shape[-1])
         if nbest is not None:
             return hipops.ctc_beam_search_nbest(log_probs, lengths, beam=int(beam_size), nbest=int(nbest), blank=int(blank),
                                                 fast_lm=fast_lm, **self._lm_args(lm, lm_alpha, lm_beta))
@@ -283,7 +293,7 @@ def collapse_fn(preds):
 def greedy_decode(scores, lengths=None, blank=0):
     """Best-path decode on the device: scores (T,B,V) GPU tensor (logits or log-probs) ->
     (tokens (B,T) int32, token_lengths (B) int32): argmax per frame (first max wins), collapse
-    repeats, drop blank."""
+    repeats, drop blank.  Rows of up to hipops.MAX_VOCAB_WIDE = 1024 scores (above 64 the arg-max is the wide kernel)."""
     T, B, V = scores.shape
     if lengths is None:
         lengths = torch.full((B,), T, dtype=torch.int32, device=scores.device)

@@ -35,6 +35,7 @@
 // T=1000.  Sums over states are taken in a fixed order (wave butterfly, then list order), so
 // results are run-to-run reproducible.
 #include "common.h"
+#include "wide_rows.h"
 
 namespace {
 
@@ -703,6 +704,160 @@ static int ctc_launch_grad(Kernel kernel, const float* log_probs, const int32_t*
     return PGASR_OK;
 }
 
+// ---- alphabets of up to 1024 symbols (pgasr_ctc_loss_grad_wide, pgasr_ctc_grad_from_lattice_wide; header section A5-WIDE) ----
+// The lattice is V-agnostic (V only addresses a row): the wide entries launch ctc_lattice_kernel with grid (B,2) -- roles 0 and 1 --
+// and build the label -> states lists with the kernel below, in the workspace format of ctc_labels_body, for any V <= 1024.
+// One workgroup per utterance.  Counting the labels is integer work (LDS atomics: the counts do not depend on the order); the
+// offsets are a block scan over V + 1 counts; entry i of the target goes to slot lab_off[label] + #{j < i : target[j] == label},
+// so every list is in ascending s whatever order the threads run in.
+__global__ __launch_bounds__(256) void ctc_labels_wide_kernel(const int32_t* __restrict__ targets, const int32_t* __restrict__ tg_len,
+                                                              int V, int Lmax, int Smax, int blank, CtcWs ws) {
+    constexpr int CH = (PGASR_WIDE_VMAX + 1 + 255) / 256;      // counts per thread in the scan (5)
+    __shared__ int tg[CTC_SMAX / 2];                           // the target row, L <= 1023
+    __shared__ int cnt[256 * CH];                              // counts, then offsets
+    __shared__ int wtot[4];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    int Lb = tg_len[b]; Lb = Lb < 0 ? 0 : (Lb > Lmax ? Lmax : Lb);
+    if (Lb > CTC_SMAX / 2) Lb = CTC_SMAX / 2;                  // defensive: the entry points refuse 2 * Lmax + 1 > 2048
+    const int32_t* tgt = targets + (size_t)b * Lmax;
+    for (int i = tid; i < 256 * CH; i += 256) cnt[i] = 0;
+    for (int i = tid; i < Lb; i += 256) tg[i] = tgt[i];
+    __syncthreads();
+    for (int i = tid; i < Lb; i += 256) {
+        const int l = tg[i];
+        if (l != blank && (unsigned)l < (unsigned)V) atomicAdd(&cnt[l], 1);
+    }
+    __syncthreads();
+    // exclusive scan of cnt[0 .. V]: thread i owns entries i*CH .. i*CH + CH - 1
+    int loc[CH], sum = 0;
+#pragma unroll
+    for (int j = 0; j < CH; ++j) { loc[j] = cnt[tid * CH + j]; sum += loc[j]; }
+    int inc = sum;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int up = __shfl_up(inc, o, 64);
+        if (lane >= o) inc += up;
+    }
+    if (lane == 63) wtot[wid] = inc;
+    __syncthreads();
+    int run = inc - sum;
+    for (int w = 0; w < wid; ++w) run += wtot[w];
+#pragma unroll
+    for (int j = 0; j < CH; ++j) { cnt[tid * CH + j] = run; run += loc[j]; }
+    __syncthreads();
+    for (int v = tid; v <= V; v += 256) ws.lab_off[(size_t)b * (V + 1) + v] = cnt[v];
+    for (int i = tid; i < Lb; i += 256) {
+        const int l = tg[i];
+        if (l == blank || (unsigned)l >= (unsigned)V) continue;
+        int rank = 0;
+        for (int j = 0; j < i; ++j) rank += (tg[j] == l);
+        ws.lab_states[(size_t)b * Smax + cnt[l] + rank] = 2 * i + 1;
+    }
+}
+
+// The gradient pass for wide rows: one wave per (t,b), lane l holding labels l*NV .. l*NV + NV - 1 (wide_rows.h).
+//   grad = utt_scale_b (softmax - occupancy) [+ pg_coef (softmax - onehot(pg_path))],  zero rows at t >= T_b.
+// Occupancy is ctc_grad_row's walk with NV labels per lane: the lane reads lab_off[l*NV .. l*NV + NV] and adds up each of its
+// labels' lists in list order -- the order, the constants and the selects of ctc_grad_row, so a row of V <= 64 gets that routine's
+// sums -- and the blank's occupancy (even states) is its strided sum with one butterfly.  Fixed order, no atomics: the same bits
+// every run.  A symbol with log p = -inf has occupancy 0 and gradient entry 0, never NaN (the selects on the constant).  The
+// offsets are V + 1 more words per row, as many bytes as the row at V = 1024, but they are the utterance's 4 KB for all its T
+// rows and come from L2, not from HBM; walking the at most L target entries instead would need the targets, which
+// pgasr_ctc_grad_from_lattice's signature does not carry (NOTES.md).
+constexpr int CTC_WIDE_WPB = 4;      // waves (rows) per workgroup
+template <int NV>
+__global__ __launch_bounds__(64 * CTC_WIDE_WPB) void ctc_grad_wide_kernel(
+    const float* __restrict__ lp, const int32_t* __restrict__ in_len,
+    const int32_t* __restrict__ tg_len, int T, int B, int V, int vec, int Lmax, int Smax, int blank, CtcWs ws,
+    const float* __restrict__ utt_scale, const float* __restrict__ pg_coef,
+    const int32_t* __restrict__ pg_path, int coef_per_frame, float* __restrict__ grad) {
+    const int lane = threadIdx.x & 63;
+    const long long w = (long long)blockIdx.x * CTC_WIDE_WPB + (threadIdx.x >> 6);
+    if (w >= (long long)T * B) return;
+    const int t = (int)(w / B), b = (int)(w % B);
+    int Tb = in_len[b]; Tb = Tb < 0 ? 0 : (Tb > T ? T : Tb);
+    int Lb = tg_len[b]; Lb = Lb < 0 ? 0 : (Lb > Lmax ? Lmax : Lb);
+    const size_t o = ((size_t)t * B + b) * V;
+    const int v0 = lane * NV;
+    float g[NV];
+#pragma unroll
+    for (int i = 0; i < NV; ++i) g[i] = 0.f;
+    if (t >= Tb) {
+        wide_row_store<NV>(grad + o, V, lane, vec != 0, g);
+        return;
+    }
+    float lpv[NV], sm[NV];
+    wide_row_load<NV>(lp + o, V, lane, vec != 0, 0.f, lpv);
+#pragma unroll
+    for (int i = 0; i < NV; ++i) sm[i] = (v0 + i < V) ? __expf(lpv[i]) : 0.f;
+
+    const double nll = ws.nll64[b];
+    if (nll != INFINITY) {            // uniform over the wave
+        const int S = 2 * Lb + 1;
+        const float* al = ws.alpha + ((size_t)b * T + t) * ws.SP;
+        const float* be = ws.beta + ((size_t)b * T + t) * ws.SP;
+        const double cst = ws.amax[(size_t)b * T + t] + ws.bmax[(size_t)b * T + t] + nll;
+        const float lpb = lp[o + blank];
+        const float cb = (lpb == -INFINITY) ? 0.f : (float)(cst - (double)lpb);
+        float accb = 0.f;
+        for (int s = 2 * lane; s < S; s += 128)
+            accb += __expf((al[s] + be[s]) + cb);
+        accb = wave_sum(accb);
+        const int32_t* lo = ws.lab_off + (size_t)b * (V + 1);
+        const int32_t* ls = ws.lab_states + (size_t)b * Smax;
+        const float sc = utt_scale ? utt_scale[b] : 1.f;
+        int off[NV + 1];
+#pragma unroll
+        for (int i = 0; i <= NV; ++i) off[i] = (v0 + i <= V) ? lo[v0 + i] : 0;
+#pragma unroll
+        for (int i = 0; i < NV; ++i) {
+            const int v = v0 + i;
+            if (v < V) {
+                float occ = accb;
+                if (v != blank) {
+                    float acc = 0.f;
+                    const float cl = (lpv[i] == -INFINITY) ? 0.f : (float)(cst - (double)lpv[i]);
+                    for (int j = off[i]; j < off[i + 1]; ++j) {
+                        const int s = ls[j];
+                        acc += __expf((al[s] + be[s]) + cl);
+                    }
+                    occ = acc;
+                }
+                g[i] = sc * (sm[i] - occ);
+            }
+        }
+    }
+    if (pg_coef != nullptr && pg_path != nullptr) {
+        const int k = pg_path[(size_t)t * B + b];
+        const float c = pg_coef[coef_per_frame ? (size_t)t * B + b : (size_t)b];
+#pragma unroll
+        for (int i = 0; i < NV; ++i) g[i] += c * (sm[i] - (v0 + i == k ? 1.f : 0.f));
+    }
+    wide_row_store<NV>(grad + o, V, lane, vec != 0, g);
+}
+
+static int ctc_args_ok_wide(int T, int B, int V, int Lmax, int blank) {
+    if (T <= 0 || B <= 0 || V <= 0 || Lmax < 0 || blank < 0 || blank >= V) return PGASR_ERR_INVALID_ARG;
+    if (2 * (long long)Lmax + 1 > CTC_SMAX || V > PGASR_WIDE_VMAX) return PGASR_ERR_UNSUPPORTED;
+    return PGASR_OK;
+}
+
+static int ctc_launch_grad_wide(const float* log_probs, const int32_t* input_lengths,
+                                const int32_t* target_lengths, int T, int B, int V, int Lmax, int blank, const CtcWs& ws,
+                                const float* utt_scale, const float* pg_coef, const int32_t* pg_path, int coef_per_frame,
+                                float* grad_logits, void* stream) {
+    const long long waves = (long long)T * B;
+    const unsigned blocks = (unsigned)((waves + CTC_WIDE_WPB - 1) / CTC_WIDE_WPB);
+#define PGASR_CALL(NV) PGASR_LAUNCH_KERNEL(ctc_grad_wide_kernel<NV>, dim3(blocks), dim3(64 * CTC_WIDE_WPB), 0, (hipStream_t)stream,           \
+                                           log_probs, input_lengths, target_lengths, T, B, V,                                                  \
+                                           wide_vec_ok<NV>(log_probs, grad_logits, V) ? 1 : 0, Lmax > 0 ? Lmax : 1, 2 * Lmax + 1, blank, ws, \
+                                           utt_scale, pg_coef, pg_path, coef_per_frame, grad_logits)
+    PGASR_WIDE_DISPATCH(V, PGASR_CALL);
+#undef PGASR_CALL
+    PGASR_CHECK_LAUNCH();
+    return PGASR_OK;
+}
+
 }  // namespace
 
 extern "C" size_t pgasr_ctc_workspace_bytes(int T, int B, int V, int Lmax) {
@@ -960,4 +1115,50 @@ extern "C" int pgasr_pg_loss_value_seq(const float* log_probs, const int32_t* pa
                        log_probs, paths, K, input_lengths, nll, utt_scale, pg_coef, hyp_nll, hyp_len, Lh, T, B, V, terms);
     PGASR_CHECK_LAUNCH();
     return PGASR_OK;
+}
+
+// ---- A5-WIDE: pgasr_ctc_loss_grad / pgasr_ctc_grad_from_lattice for 1 <= V <= 1024 (same workspace, same lattice kernel) ----
+extern "C" int pgasr_ctc_loss_grad_wide(const float* log_probs, const int32_t* targets,
+                                        const int32_t* input_lengths, const int32_t* target_lengths,
+                                        int T, int B, int V, int Lmax, int blank,
+                                        const float* utt_scale, const float* pg_coef, const int32_t* pg_path,
+                                        float* nll, float* grad_logits,
+                                        void* workspace, size_t workspace_bytes, void* stream) {
+    if (!log_probs || !targets || !input_lengths || !target_lengths || !nll) return PGASR_ERR_INVALID_ARG;
+    if ((pg_coef == nullptr) != (pg_path == nullptr)) return PGASR_ERR_INVALID_ARG;
+    const int ok = ctc_args_ok_wide(T, B, V, Lmax, blank);
+    if (ok != PGASR_OK) return ok;
+    const int Smax = 2 * Lmax + 1;
+    CtcWs ws;
+    if (!ctc_ws_bind(T, B, V, Smax, &ws, workspace, workspace_bytes)) return PGASR_ERR_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    PGASR_LAUNCH_KERNEL(ctc_labels_wide_kernel, dim3(B), dim3(256), 0, st, targets, target_lengths, V, Lmax > 0 ? Lmax : 1, Smax, blank, ws);
+    PGASR_CHECK_LAUNCH();
+    // the sweeps alone: grid rows 0 and 1 of the lattice kernel, whose third row (the narrow label lists) is not launched
+#define PGASR_LATTICE(NSPT) PGASR_LAUNCH_KERNEL(ctc_lattice_kernel<NSPT>, dim3(B, 2), dim3(CTC_THREADS + 64), 0, st, \
+                        log_probs, targets, input_lengths, target_lengths, T, B, V, Lmax > 0 ? Lmax : 1, Smax, blank, ws, nll, 0)
+    if (Smax <= CTC_THREADS) PGASR_LATTICE(1);
+    else if (Smax <= 2 * CTC_THREADS) PGASR_LATTICE(2);
+    else if (Smax <= 4 * CTC_THREADS) PGASR_LATTICE(4);
+    else PGASR_LATTICE(8);
+#undef PGASR_LATTICE
+    PGASR_CHECK_LAUNCH();
+    if (!grad_logits) return PGASR_OK;
+    return ctc_launch_grad_wide(log_probs, input_lengths, target_lengths, T, B, V, Lmax, blank, ws, utt_scale, pg_coef, pg_path,
+                                0, grad_logits, stream);
+}
+
+extern "C" int pgasr_ctc_grad_from_lattice_wide(const float* log_probs, const int32_t* input_lengths,
+                                                const int32_t* target_lengths, int T, int B, int V, int Lmax, int blank,
+                                                const float* utt_scale, const float* pg_coef, const int32_t* pg_path,
+                                                int pg_coef_per_frame, float* grad_logits, void* workspace, size_t workspace_bytes,
+                                                void* stream) {
+    if (!log_probs || !input_lengths || !target_lengths || !grad_logits) return PGASR_ERR_INVALID_ARG;
+    if ((pg_coef == nullptr) != (pg_path == nullptr)) return PGASR_ERR_INVALID_ARG;
+    const int ok = ctc_args_ok_wide(T, B, V, Lmax, blank);
+    if (ok != PGASR_OK) return ok;
+    CtcWs ws;
+    if (!ctc_ws_bind(T, B, V, 2 * Lmax + 1, &ws, workspace, workspace_bytes)) return PGASR_ERR_WORKSPACE;
+    return ctc_launch_grad_wide(log_probs, input_lengths, target_lengths, T, B, V, Lmax, blank, ws, utt_scale, pg_coef, pg_path,
+                                pg_coef_per_frame ? 1 : 0, grad_logits, stream);
 }

@@ -90,30 +90,36 @@ def extract_feats(batch, device="cuda:0", features="mfcc", keep_on_device=False,
     return (feat, fmask) if keep_on_device else (feat.cpu(), fmask.cpu())
 
 
-def encode_trans(batch):
-    """char -> index with pad 0, mask = (id > 0) (data.py:82-104)."""
-    char2ind = batch[0]["charmap"]
-    enc = [torch.tensor([char2ind[c] for c in inst["trans"]], dtype=torch.int64) for inst in batch]
+def encode_trans(batch, units=None):
+    """char -> index with pad 0, mask = (id > 0) (data.py:82-104).  units: a ``units.SubwordUnits`` (given here, or carried by the
+    items as "units"): the transcripts are encoded by ``units.encode``, greedy longest match, instead of character by character."""
+    units = units if units is not None else batch[0].get("units")
+    if units is not None:
+        enc = [torch.tensor(units.encode(inst["trans"]), dtype=torch.int64) for inst in batch]
+    else:
+        char2ind = batch[0]["charmap"]
+        enc = [torch.tensor([char2ind[c] for c in inst["trans"]], dtype=torch.int64) for inst in batch]
     lmax = max(max((e.shape[0] for e in enc), default=1), 1)
     out = torch.stack([nn.functional.pad(e, (0, lmax - e.shape[0])) for e in enc])
     return out, (out > 0).to(torch.int64)
 
 
-def collate_custom(batch, device=None, features="mfcc", target_rate=None, speed_perturb=None, seed=0, offset=0, wave_augment=None):
+def collate_custom(batch, device=None, features="mfcc", target_rate=None, speed_perturb=None, seed=0, offset=0, wave_augment=None,
+                   units=None):
     """data.py:107-116.  device = None: the reference's contract -- everything on the CPU.  device = a GPU: "feat" / "fmask" stay
     where the front end computed them and "trans" / "tmask" are put beside them, so ``PolicyGradientTrainer.step`` consumes the
     batch without the features ever visiting the host (use ``functools.partial(collate_custom, device=...)`` as collate_fn).
     target_rate / speed_perturb / wave_augment / seed / offset: sample-rate conversion, speed perturbation, noise and reverberation of
-    waveform items (``extract_feats``)."""
+    waveform items (``extract_feats``).  units: subword units for the transcripts (``encode_trans``)."""
     aug = {"target_rate": target_rate, "speed_perturb": speed_perturb, "seed": seed, "offset": offset}
     if wave_augment is not None:
         aug["wave_augment"] = wave_augment
     if device is None:
         feats, fmasks = extract_feats(batch, features=features, **aug)
-        trans, tmasks = encode_trans(batch)
+        trans, tmasks = encode_trans(batch, units)
     else:
         feats, fmasks = extract_feats(batch, device=device, features=features, keep_on_device=True, **aug)
-        trans, tmasks = (t.to(device) for t in encode_trans(batch))
+        trans, tmasks = (t.to(device) for t in encode_trans(batch, units))
     return {"feat": feats, "fmask": fmasks, "trans": trans, "tmask": tmasks}
 
 
@@ -133,12 +139,15 @@ class Indexed(data.Dataset):
 
 
 class Data(data.Dataset):
-    """Data(csv_path, aud_path, char2ind) (data.py:118-132): CommonVoice TSV rows."""
+    """Data(csv_path, aud_path, char2ind) (data.py:118-132): CommonVoice TSV rows.
+    units: None, or a ``units.SubwordUnits`` whose ids are char2ind's: the items carry it and ``encode_trans`` encodes their
+    transcripts with it."""
 
-    def __init__(self, csv_path, aud_path, char2ind):
+    def __init__(self, csv_path, aud_path, char2ind, units=None):
         import pandas as pd
         self.df = pd.read_csv(csv_path, sep="\t")
         self.char2ind = char2ind
+        self.units = units
         self.fnames = [os.path.join(aud_path, f) for f in self.df["path"]]
         self.transcrpts = self.df["sentence"]
 
@@ -148,7 +157,10 @@ class Data(data.Dataset):
     def __getitem__(self, idx):
         if torch.is_tensor(idx):
             idx = idx.tolist()
-        return {"aud": self.fnames[idx], "trans": self.transcrpts[idx], "charmap": self.char2ind}
+        item = {"aud": self.fnames[idx], "trans": self.transcrpts[idx], "charmap": self.char2ind}
+        if self.units is not None:
+            item["units"] = self.units
+        return item
 
 
 class SyntheticSpeech(data.Dataset):

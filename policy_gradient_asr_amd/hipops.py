@@ -124,8 +124,25 @@ def _workspace(nbytes, device, tag):
     return buf
 
 
-def _ctc_call(log_probs, targets, input_lengths, target_lengths, blank, utt_scale=None, pg_coef=None, pg_path=None, need_grad=False):
-    """``pgasr_ctc_loss_grad`` for ``ctc_loss_grad`` and ``ctc_lattice``: (nll, grad or None, lattice handle)."""
+# ---- alphabets of 65 .. 1024 symbols (include/pgasr_hip.h, A5-WIDE / A9-WIDE) ----
+MAX_VOCAB_NARROW = 64            # one label per lane: every entry point without a _wide form
+MAX_VOCAB_WIDE = 1024            # PGASR_MAX_VOCAB_WIDE: log-softmax, arg-max / sample, CTC lattice and gradient pass
+
+
+def _wide(V, wide, what):
+    """Which entry a wrapper with a ``_wide`` form takes: by V (wide=None), or the caller's choice -- the wide kernels take V <= 64
+    too, which is how the tests compare the two."""
+    if wide is None:
+        wide = V > MAX_VOCAB_NARROW
+    if not wide and V > MAX_VOCAB_NARROW:
+        raise _lib.PgasrError(f"{what}: V = {V} > {MAX_VOCAB_NARROW} needs the wide entry")
+    return bool(wide)
+
+
+def _ctc_call(log_probs, targets, input_lengths, target_lengths, blank, utt_scale=None, pg_coef=None, pg_path=None, need_grad=False,
+              wide=None):
+    """``pgasr_ctc_loss_grad`` (V > 64: ``pgasr_ctc_loss_grad_wide``, the same arguments and workspace) for ``ctc_loss_grad`` and
+    ``ctc_lattice``: (nll, grad or None, lattice handle)."""
     lib = _lib.load()
     _req(log_probs, torch.float32, "log_probs")
     T, B, V = log_probs.shape
@@ -140,24 +157,25 @@ def _ctc_call(log_probs, targets, input_lengths, target_lengths, blank, utt_scal
     ws = _workspace(nbytes, log_probs.device, "ctc")
     nll = torch.empty(B, dtype=torch.float32, device=log_probs.device)
     grad = torch.empty_like(log_probs) if need_grad else None
-    st = lib.pgasr_ctc_loss_grad(_p(log_probs), _p(targets), _p(input_lengths), _p(target_lengths),
-                                 T, B, V, Lmax, blank, _p(utt_scale), _p(pg_coef), _p(pg_path),
-                                 _p(nll), _p(grad), _p(ws), ws.numel(), _stream())
-    _lib.check(st, "pgasr_ctc_loss_grad")
+    entry = "pgasr_ctc_loss_grad_wide" if _wide(V, wide, "ctc_loss_grad") else "pgasr_ctc_loss_grad"
+    st = getattr(lib, entry)(_p(log_probs), _p(targets), _p(input_lengths), _p(target_lengths),
+                             T, B, V, Lmax, blank, _p(utt_scale), _p(pg_coef), _p(pg_path),
+                             _p(nll), _p(grad), _p(ws), ws.numel(), _stream())
+    _lib.check(st, entry)
     return nll, grad, (ws, Lmax, blank)
 
 
 def ctc_loss_grad(log_probs, targets, input_lengths, target_lengths, blank=0, utt_scale=None,
-                  pg_coef=None, pg_path=None, need_grad=True):
-    """log_probs (T,B,V) fp32; targets (B,Lmax) int32; lengths int32.
-    Returns (nll (B,), grad_logits (T,B,V) or None)."""
-    return _ctc_call(log_probs, targets, input_lengths, target_lengths, blank, utt_scale, pg_coef, pg_path, need_grad)[:2]
+                  pg_coef=None, pg_path=None, need_grad=True, wide=None):
+    """log_probs (T,B,V) fp32, V <= MAX_VOCAB_WIDE; targets (B,Lmax) int32; lengths int32.
+    Returns (nll (B,), grad_logits (T,B,V) or None).  wide: None = the wide kernels when V > 64 (``_wide``)."""
+    return _ctc_call(log_probs, targets, input_lengths, target_lengths, blank, utt_scale, pg_coef, pg_path, need_grad, wide)[:2]
 
 
-def ctc_lattice(log_probs, targets, input_lengths, target_lengths, blank=0):
+def ctc_lattice(log_probs, targets, input_lengths, target_lengths, blank=0, wide=None):
     """First half of ``ctc_loss_grad``: alpha/beta lattice only.  Returns (nll (B,), handle); the handle goes to
     ``ctc_grad_from_lattice`` (which may run on another stream once this one's work is ordered before it)."""
-    nll, _, handle = _ctc_call(log_probs, targets, input_lengths, target_lengths, blank)
+    nll, _, handle = _ctc_call(log_probs, targets, input_lengths, target_lengths, blank, wide=wide)
     return nll, handle
 
 
@@ -221,10 +239,16 @@ def _loss_value(entry, log_probs, paths, paths_name, input_lengths, nll, utt_sca
 
 
 def ctc_grad_from_lattice(log_probs, input_lengths, target_lengths, handle, utt_scale=None, pg_coef=None, pg_path=None,
-                          ent_scale=None, ref_log_probs=None, kl_scale=None):
+                          ent_scale=None, ref_log_probs=None, kl_scale=None, wide=None):
     """ent_scale (B): add the entropy term of ``frame_entropy`` in the same pass (``_grad_pass``), here and in the two wrappers below.
-    ref_log_probs (T,B,V), kl_scale (B): add the KL term of ``frame_kl`` after it, likewise."""
-    T, B, _ = log_probs.shape
+    ref_log_probs (T,B,V), kl_scale (B): add the KL term of ``frame_kl`` after it, likewise.
+    V > 64 (or wide=True): ``pgasr_ctc_grad_from_lattice_wide``, which has no entropy or KL form."""
+    T, B, V = log_probs.shape
+    if _wide(V, wide, "ctc_grad_from_lattice"):
+        if ent_scale is not None or ref_log_probs is not None or kl_scale is not None:
+            raise _lib.PgasrError(f"ctc_grad_from_lattice: the entropy and KL terms take at most {MAX_VOCAB_NARROW} symbols (V = {V})")
+        return _grad_pass("pgasr_ctc_grad_from_lattice_wide", log_probs, input_lengths, target_lengths, handle, utt_scale, pg_coef,
+                          pg_path, "pg_path", (pg_coef, pg_path, _coef_per_frame(pg_coef, T, B)))
     return _grad_pass("pgasr_ctc_grad_from_lattice", log_probs, input_lengths, target_lengths, handle, utt_scale, pg_coef, pg_path,
                       "pg_path", (pg_coef, pg_path, _coef_per_frame(pg_coef, T, B)), ent_scale=ent_scale,
                       ref_log_probs=ref_log_probs, kl_scale=kl_scale)
@@ -458,11 +482,13 @@ def _check_utt_ids(utt_ids, B, T, batch_stride, device, what):
         raise ValueError(f"{what}: T * batch_stride = {T} * {int(batch_stride)} > 2^32: the sampler's counter word is 32 bits")
 
 
-def frame_argmax_sample(scores, seed=0, offset=0, want_greedy=True, want_sample=True, batch_stride=0, batch_offset=0, utt_ids=None):
+def frame_argmax_sample(scores, seed=0, offset=0, want_greedy=True, want_sample=True, batch_stride=0, batch_offset=0, utt_ids=None,
+                        wide=None):
     """batch_stride / batch_offset: the GLOBAL batch and this shard's first utterance in it (data parallel: N ranks with
     one seed then draw what one process holding the whole batch draws); 0 / 0 = the local batch is the whole batch.
     utt_ids (B) int32 on the device, with batch_stride: row b's global index instead of batch_offset + b (an id < 0 or >=
-    batch_stride: a row beyond the global batch; pgasr_frame_argmax_sample_ids)."""
+    batch_stride: a row beyond the global batch; pgasr_frame_argmax_sample_ids).
+    V > 64 (or wide=True): ``pgasr_frame_argmax_sample_wide``, one entry for both addressings, the same draws."""
     lib = _lib.load()
     _req(scores, torch.float32, "scores")
     T, B, V = scores.shape
@@ -470,6 +496,12 @@ def frame_argmax_sample(scores, seed=0, offset=0, want_greedy=True, want_sample=
         _check_utt_ids(utt_ids, B, T, batch_stride, scores.device, "frame_argmax_sample")
     g = torch.empty(T, B, dtype=torch.int32, device=scores.device) if want_greedy else None
     s = torch.empty(T, B, dtype=torch.int32, device=scores.device) if want_sample else None
+    if _wide(V, wide, "frame_argmax_sample"):
+        st = lib.pgasr_frame_argmax_sample_wide(_p(scores), T, B, V, int(seed) & (2 ** 64 - 1), int(offset) & 0xFFFFFFFF,
+                                                int(batch_stride), 0 if utt_ids is not None else int(batch_offset), _p(utt_ids),
+                                                _p(g), _p(s), _stream())
+        _lib.check(st, "pgasr_frame_argmax_sample_wide")
+        return g, s
     if utt_ids is not None:
         st = lib.pgasr_frame_argmax_sample_ids(_p(scores), T, B, V, int(seed) & (2 ** 64 - 1), int(offset) & 0xFFFFFFFF,
                                                int(batch_stride), _p(utt_ids), _p(g), _p(s), _stream())
@@ -1100,12 +1132,14 @@ def instnorm_stats(x, eps=1e-5):
     return mean, rstd
 
 
-def log_softmax_rows(logits):
+def log_softmax_rows(logits, wide=None):
+    """log_softmax over the last dimension, V <= MAX_VOCAB_WIDE; V > 64 (or wide=True): ``pgasr_log_softmax_rows_wide``."""
     lib = _lib.load()
     _req(logits, torch.float32, "logits")
     V = logits.shape[-1]
     out = torch.empty_like(logits)
-    _lib.check(lib.pgasr_log_softmax_rows(_p(logits), logits.numel() // V, V, _p(out), _stream()), "pgasr_log_softmax_rows")
+    entry = "pgasr_log_softmax_rows_wide" if _wide(V, wide, "log_softmax_rows") else "pgasr_log_softmax_rows"
+    _lib.check(getattr(lib, entry)(_p(logits), logits.numel() // V, V, _p(out), _stream()), entry)
     return out
 
 

@@ -278,10 +278,13 @@ class PGOptions:
     kl_weight: float = 0.0
 
 
-def check_options(opt, vocab=None, frames=None, symbols=None, sample_ids=None):
+def check_options(opt, vocab=None, frames=None, symbols=None, sample_ids=None, wide_check=True):
     """The one check of a ``PGOptions`` -- by ``pg_ctc_loss`` per call, by ``PolicyGradientTrainer`` at construction and before
     every step --, made before any kernel runs and where the caller can read the reason.  vocab, frames (T) and symbols (the
-    targets' row length) are checked against where they are known.  Returns the options with their integers as ints."""
+    targets' row length) are checked against where they are known.  Returns the options with their integers as ints.
+    An alphabet of 65 .. 1024 symbols (hipops.MAX_VOCAB_WIDE) takes the default objective alone -- CTC + single-sample REINFORCE
+    against the greedy hypothesis (``_check_wide``); wide_check=False leaves that rule to the caller (a trainer without
+    ``wide_alphabet`` refuses such a model itself)."""
     _check_score(opt.score_function, opt.max_hyp_len, opt.per_step)
     if sample_ids is not None and opt.sample_base >= 0:
         raise ValueError("sample_ids and sample_base >= 0 are two addressings of the same draws: give one")
@@ -292,9 +295,31 @@ def check_options(opt, vocab=None, frames=None, symbols=None, sample_ids=None):
     if opt.reward_unit == "word" and frames is not None and max(frames, symbols or 0) > hipops.WORD_MAX_STRIDE:
         raise ValueError(f"the word-level reward takes at most {hipops.WORD_MAX_STRIDE} frames and target symbols per utterance "
                          f"(pgasr_word_ids); got T = {frames}")
+    if wide_check and vocab is not None and vocab > hipops.MAX_VOCAB_NARROW:
+        _check_wide(opt, vocab)
     return dataclasses.replace(opt, num_samples=int(opt.num_samples),
                                max_hyp_len=None if opt.max_hyp_len is None else int(opt.max_hyp_len),
                                entropy_weight=check_entropy_weight(opt.entropy_weight), kl_weight=check_kl_weight(opt.kl_weight))
+
+
+def _check_wide(opt, vocab):
+    """An alphabet of more than 64 symbols: the wide kernels cover log-softmax, arg-max / sample, the CTC lattice and its gradient
+    pass with one sampled path -- the default objective.  Every other option runs kernels that hold one symbol per lane."""
+    if vocab > hipops.MAX_VOCAB_WIDE:
+        raise ValueError(f"alphabet of {vocab} symbols > {hipops.MAX_VOCAB_WIDE}: the wide kernels hold at most 16 symbols per lane")
+    entropy, kl = check_entropy_weight(opt.entropy_weight), check_kl_weight(opt.kl_weight)
+    for name, given, ok in (("baseline", opt.baseline, opt.baseline == "hypothesis"),
+                            ("num_samples", opt.num_samples, int(opt.num_samples) == 1),
+                            ("beam", opt.beam, opt.beam == 0),
+                            ("score_function", opt.score_function, opt.score_function == "path"),
+                            ("entropy_weight", opt.entropy_weight, entropy == 0.0),
+                            ("kl_weight", opt.kl_weight, kl == 0.0),
+                            ("reward_unit", opt.reward_unit, opt.reward_unit == "char"),
+                            ("per_step", opt.per_step, not opt.per_step)):
+        if not ok:
+            raise ValueError(f"{name}={given!r} takes an alphabet of at most {hipops.MAX_VOCAB_NARROW} symbols (got {vocab}): above the "
+                             f"64-symbol limit only the default objective runs -- num_samples=1, baseline='hypothesis', beam=0, "
+                             f"score_function='path', entropy_weight=0, kl_weight=0, reward_unit='char', no per-step rewards")
 
 
 def check_entropy_weight(entropy_weight):

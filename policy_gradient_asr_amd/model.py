@@ -243,7 +243,7 @@ def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset
           accumulate_steps=1, score_function="path", max_hyp_len=None, entropy_weight=0.0, objective="reinforce", mwer_nbest=4,
           mwer_beam=16, init_from=None, kl_weight=0.0, kl_reference_path=None, mwer_lm_path=None, mwer_lm_alpha=0.0,
           mwer_lm_beta=0.0, target_rate=None, speed_perturb=None, noise_dir=None, rir_dir=None, snr_db=(5.0, 20.0), noise_prob=1.0,
-          rir_prob=0.5):
+          rir_prob=0.5, units_path=None, wide_alphabet=None):
     """Epoch loop of model.py:186-274 on the MI355X path: per-epoch train loss -> train_loss.npy,
     validation CTC loss -> val_losses.npy, model_best.pth / model_last.pth (state_dicts, reference
     names), plus checkpoint_last.pth (model + Adam moments + epoch) from which ``resume`` restarts
@@ -296,7 +296,13 @@ def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset
     noise recordings and room impulse responses, packed on the device once at 16 kHz (features.NoiseBank / RirBank).  Every training
     waveform then takes noise with probability noise_prob at an SNR drawn uniformly from snr_db = (low, high) dB, and a reverberation
     with probability rir_prob (features.WaveAugment), drawn per (seed, epoch, utterance index) behind the resampling and in front of
-    the framing.  Validation and ``predict`` are never augmented."""
+    the framing.  Validation and ``predict`` are never augmented.
+    units_path: None (default: <corpus_path>/alphabet.txt, one character per symbol) or a units file of ``build_units`` /
+    ``units.SubwordUnits.save`` that stands in its place: the transcripts are encoded by greedy longest match over the units, the
+    output layer has one symbol per unit (and the blank), and the reward is the edit distance over units.
+    wide_alphabet: None (default: "more than 64 symbols") or a bool -- PolicyGradientTrainer(wide_alphabet=): up to 1024 symbols with
+    the default objective (num_samples=1, the greedy baseline, reward_unit="char", score_function="path", no entropy or KL term);
+    objective="mwer" does not take it."""
     import os
     import numpy as np
     import torch.utils.data as tud
@@ -322,8 +328,19 @@ def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset
     if kl_weight > 0 and objective == "mwer":
         raise ValueError("objective='mwer' does not take kl_weight (the KL penalty belongs to the sampled objectives)")
     print("Num epochs:", num_epochs, "Batch size:", batch_size)
-    alphabet_path = os.path.join(corpus_path, "alphabet.txt")
+    alphabet_path = os.path.join(corpus_path, "alphabet.txt") if units_path is None else units_path
     alphabet, char2ind = _read_alphabet(alphabet_path)
+    units = None
+    if units_path is not None:
+        from .units import SubwordUnits
+        units = SubwordUnits.load(units_path)
+        if units.unit2ind != {k: v for k, v in char2ind.items() if v > 0}:
+            raise ValueError(f"{units_path}: not a units file (one distinct, non-empty unit per line)")
+    if wide_alphabet is None:
+        wide_alphabet = len(char2ind) > hipops.MAX_VOCAB_NARROW
+    wide_alphabet = bool(wide_alphabet)
+    if wide_alphabet and objective == "mwer":
+        raise ValueError("objective='mwer' takes an alphabet of at most 64 symbols (the beam search's limit): not with wide_alphabet")
     word_delimiter = None
     if reward_unit == "word":
         if " " not in char2ind:
@@ -334,11 +351,12 @@ def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset
     from .features import SpeedPerturb
     speed_perturb = SpeedPerturb.coerce(speed_perturb)
     wave_augment = _wave_augment(noise_dir, rir_dir, snr_db, noise_prob, rir_prob, dev)
-    collate_custom = functools.partial(_collate, device=dev, features=features, target_rate=target_rate)
+    unit_args = {} if units is None else {"units": units}       # without a units file: the calls as they were
+    collate_custom = functools.partial(_collate, device=dev, features=features, target_rate=target_rate, **unit_args)
     if train_dataset is None:
-        train_dataset = Data(os.path.join(corpus_path, "train.tsv"), os.path.join(corpus_path, "clips"), char2ind)
+        train_dataset = Data(os.path.join(corpus_path, "train.tsv"), os.path.join(corpus_path, "clips"), char2ind, **unit_args)
     if dev_dataset is None and os.path.exists(os.path.join(corpus_path, "dev.tsv")):
-        dev_dataset = Data(os.path.join(corpus_path, "dev.tsv"), os.path.join(corpus_path, "clips"), char2ind)
+        dev_dataset = Data(os.path.join(corpus_path, "dev.tsv"), os.path.join(corpus_path, "clips"), char2ind, **unit_args)
 
     torch.manual_seed(seed)
     model = Seq2Seq(alphabet_size=len(char2ind), n_feats=n_feats)
@@ -365,7 +383,7 @@ def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset
         trainer = PolicyGradientTrainer(model, lr=lr, lam=lam, seed=seed, precision=precision, num_samples=num_samples,
                                         reward_baseline=reward_baseline, reward_unit=reward_unit, word_delimiter=word_delimiter,
                                         max_grad_norm=max_grad_norm, score_function=score_function, max_hyp_len=max_hyp_len,
-                                        entropy_weight=entropy_weight, **kl)
+                                        entropy_weight=entropy_weight, **kl, **({"wide_alphabet": True} if wide_alphabet else {}))
     losses, val_losses, best, start_epoch = [], [], 9999999.0, 1
     ckpt = os.path.join(model_path, "checkpoint_last.pth")
     resuming = resume and os.path.exists(ckpt)
@@ -388,6 +406,7 @@ def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset
                         ("accumulate_steps", accumulate_steps), ("score_function", score_function),
                         ("max_hyp_len", max_hyp_len), ("entropy_weight", entropy_weight), ("kl_weight", kl_weight),
                         ("kl_reference_path", kl_reference_path), ("target_rate", target_rate),
+                        ("units_path", units_path), ("wide_alphabet", wide_alphabet),
                         ("speed_perturb", None if speed_perturb is None else speed_perturb.state()),
                         ("wave_augment", None if wave_augment is None else wave_augment.state())):
             if k in st and st[k] != want:
@@ -406,7 +425,7 @@ def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset
             draws = {"speed_perturb": speed_perturb, "seed": seed, "offset": epoch}
             if wave_augment is not None:
                 draws["wave_augment"] = wave_augment
-            train_collate = functools.partial(_collate, device=dev, features=features, target_rate=target_rate, **draws)
+            train_collate = functools.partial(_collate, device=dev, features=features, target_rate=target_rate, **draws, **unit_args)
         if lens is not None:      # similar lengths per batch instead of model.py:221's shuffle=True
             sampler = LengthBucketSampler(lens, batch_size, seed=seed)
             sampler.set_epoch(epoch)
@@ -476,6 +495,7 @@ def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset
                     "reward_unit": reward_unit, "max_grad_norm": max_grad_norm, "accumulate_steps": accumulate_steps,
                     "score_function": score_function, "max_hyp_len": max_hyp_len, "entropy_weight": trainer.entropy_weight,
                     "kl_weight": kl_weight, "kl_reference_path": kl_reference_path, "target_rate": target_rate,
+                    "units_path": units_path, "wide_alphabet": wide_alphabet,
                     "speed_perturb": None if speed_perturb is None else speed_perturb.state(),
                     "wave_augment": None if wave_augment is None else wave_augment.state()}, ckpt)
     return losses, val_losses
@@ -485,7 +505,7 @@ def predict(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=N
             test_dataset=None, n_feats=120, beam_size=5, features="mfcc", lm_path=None, lm_alpha=0.0, lm_beta=0.0,
             nbest=1, rescore_lm_path=None, rescore_alpha=0.0, rescore_beta=0.0, lm_fast=False, target_rate=None,
             mbr=False, mbr_unit="char", mbr_scale=1.0, rescore_word_lm_path=None, rescore_word_alpha=0.0, rescore_word_beta=0.0,
-            error_report=False):
+            error_report=False, units_path=None):
     """model.py:277-339: load model_best.pth, forward, beam=5 prefix search (device side, batched),
     collapse_fn, CER/WER, predicted.txt.  Frames are cut by the FEATURE mask (the reference cuts the
     time axis by the target mask, model.py:322 -- a listed defect).  Returns (CER, WER).
@@ -521,18 +541,27 @@ def predict(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=N
     hypothesis) are also aligned on the device (``metrics.ErrorReport``), ``errors.txt`` -- per utterance a REF / HYP / OPS triple of
     aligned lines, then the totals -- and ``confusions.tsv`` -- kind, ref, hyp, count, sorted by count -- are written into model_path,
     and one corpus-level line, (S + D + I) / reference length with the S / D / I breakdown for characters and words, is printed after
-    the line above.  The return value (the MEAN of the per-utterance rates) and every other output stay what they are."""
+    the line above.  The return value (the MEAN of the per-utterance rates) and every other output stay what they are.
+    beam_size=0: greedy decoding -- arg-max per frame and CTC collapse on the device (``CTCdecoder.greedy_decode``), no search; the only
+    decoder for an alphabet of more than 64 symbols (up to 1024), where beam_size > 0 raises up front.  Not with nbest > 1 or an LM.
+    units_path: None (default) or a units file (``build_units``) that stands in place of ``alphabet_path``: the references are
+    encoded by greedy longest match, the hypotheses are the concatenated units (no ``collapse_fn``: a unit may end with the character the
+    next one starts with), and CER / WER are computed on the decoded strings as ever."""
     import os
     import functools
     import torch.utils.data as tud
-    from .CTCdecoder import CTCDecoder, collapse_fn
+    from .CTCdecoder import CTCDecoder, collapse_fn, greedy_decode
     from .lm import CharNgramLM, WordNgramLM
     from .data import Data
     from .data import collate_custom as _collate
     from .metrics import edit_dist_batch, evaluate, save_predictions
 
     nbest = int(nbest)
-    if nbest < 1 or nbest > int(beam_size):
+    greedy = int(beam_size) == 0
+    if greedy:
+        if nbest != 1 or lm_path is not None:
+            raise ValueError("beam_size=0 decodes greedily: it has no N-best list and no LM (nbest > 1 and lm_path need beam_size >= 1)")
+    elif nbest < 1 or nbest > int(beam_size):
         raise ValueError(f"nbest must lie in [1, beam_size = {beam_size}] (got {nbest})")
     if rescore_lm_path is not None and nbest < 2:
         raise ValueError("rescoring needs a list: give nbest >= 2 with rescore_lm_path")
@@ -542,16 +571,27 @@ def predict(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=N
         raise ValueError("minimum-Bayes-risk decoding needs a list: give nbest >= 2 with mbr=True")
     if mbr and mbr_unit not in ("char", "word"):
         raise ValueError(f"mbr_unit must be 'char' or 'word' (got {mbr_unit!r})")
+    if units_path is not None:
+        alphabet_path = units_path
     alphabet, char2ind = _read_alphabet(alphabet_path)
     ind2char = {char2ind[k]: k for k in char2ind}
+    unit_args = {}
+    if units_path is not None:
+        from .units import SubwordUnits
+        unit_args = {"units": SubwordUnits.load(units_path)}
+    if len(alphabet) > hipops.MAX_VOCAB_NARROW and not greedy:
+        raise ValueError(f"the beam search takes at most {hipops.MAX_VOCAB_NARROW} symbols and {alphabet_path} has {len(alphabet)}: "
+                         f"decode greedily with beam_size=0 (up to {hipops.MAX_VOCAB_WIDE} symbols)")
     dev = torch.device("cuda", device_id)
     model = Seq2Seq(alphabet_size=len(alphabet), n_feats=n_feats)
     model.load_state_dict(torch.load(os.path.join(model_path, "model_best.pth"), map_location="cpu"))
     model = model.to(dev).eval()
     if test_dataset is None:
-        test_dataset = Data(test_path, aud_path, char2ind)
+        test_dataset = Data(test_path, aud_path, char2ind, **unit_args)
     _check_features(features, n_feats, test_dataset)
-    collate_custom = functools.partial(_collate, device=dev, features=features, target_rate=target_rate)
+    collate_custom = functools.partial(_collate, device=dev, features=features, target_rate=target_rate, **unit_args)
+    # a units file: the device's collapse is the whole collapse -- collapse_fn would merge a unit's last character with the next unit's first
+    to_text = collapse_fn if units_path is None else (lambda text: text)
     loader = tud.DataLoader(test_dataset, batch_size=batch_size, shuffle=False, collate_fn=collate_custom)
     lm = CharNgramLM.load(lm_path) if lm_path is not None else None
     decoder = CTCDecoder(alphabet, lm=lm, lm_alpha=lm_alpha, lm_beta=lm_beta, fast_lm=bool(lm_fast))
@@ -614,11 +654,13 @@ def predict(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=N
                 for i, d in zip(owner, edit_dist_batch(refs, hyps, device=dev)):
                     best[i] = min(d, best.get(i, d))
                 tot_oracle += sum(d / max(int(tlen_h[i]), 1) for i, d in best.items())
+            elif greedy:
+                tok, tl = greedy_decode(lp, in_len)
             else:
                 tok, tl, _ = decoder.decode_batch(lp, in_len, beam_size=beam_size)
             tok, tl, t, tmask = tok.cpu(), tl.cpu(), t.cpu(), tmask.cpu()
             for i in range(tok.shape[0]):
-                seq = collapse_fn("".join(ind2char[int(k)] for k in tok[i, :tl[i]]))
+                seq = to_text("".join(ind2char[int(k)] for k in tok[i, :tl[i]]))
                 target = "".join(ind2char[int(k)] for k in t[i][:int(tmask[i].sum())])
                 targets.append(target); predicted.append(seq)
                 cer, wer = evaluate(target, seq)
@@ -697,6 +739,27 @@ def align(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=Non
     with open(out_path, "w") as fo:
         fo.writelines(lines)
     return scores
+
+
+def build_units(corpus_path, n_units, out_path=None, train_dataset=None):
+    """Learn ``n_units`` subword units by byte-pair encoding (``units.SubwordUnits.learn_bpe``) from the training transcripts -- the
+    "sentence" column of <corpus_path>/train.tsv, or the "trans" of ``train_dataset``'s items -- starting from the characters of
+    <corpus_path>/alphabet.txt, and write them to ``out_path`` (default <corpus_path>/units.txt) for ``train(units_path=)`` and
+    ``predict(units_path=)``.  The output layer then has n_units + 1 symbols (at most 1024).  Returns the ``SubwordUnits``."""
+    import os
+    from .units import SubwordUnits
+    _, char2ind = _read_alphabet(os.path.join(corpus_path, "alphabet.txt"))
+    base = [c for c, i in sorted(char2ind.items(), key=lambda kv: kv[1]) if i > 0]
+    if int(n_units) + 1 > hipops.MAX_VOCAB_WIDE:
+        raise ValueError(f"n_units = {n_units}: the output layer takes at most {hipops.MAX_VOCAB_WIDE} symbols, the blank included")
+    if train_dataset is not None:
+        lines = [train_dataset[i]["trans"] for i in range(len(train_dataset))]
+    else:
+        import pandas as pd
+        lines = [str(x) for x in pd.read_csv(os.path.join(corpus_path, "train.tsv"), sep="\t")["sentence"]]
+    units = SubwordUnits.learn_bpe(lines, n_units, alphabet=base)
+    units.save(out_path or os.path.join(corpus_path, "units.txt"))
+    return units
 
 
 def build_lm(corpus_path, order=3, out_path=None, train_dataset=None):

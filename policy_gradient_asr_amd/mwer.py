@@ -197,6 +197,9 @@ class MWERTrainer(PolicyGradientTrainer):
     def __init__(self, model, lr=5e-4, lam=1.0, seed=0, blank=0, world_size=1, process_group=None, rank=0, precision=None,
                  max_grad_norm=None, beam_size=16, nbest=4, risk_unit="char", word_delimiter=None, max_hyp_len=None, lm=None, lm_alpha=0.0,
                  lm_beta=0.0, **sampled):
+        if sampled.pop("wide_alphabet", False):
+            raise ValueError("MWERTrainer takes an alphabet of at most 64 symbols: the beam search and the N-best kernels hold one "
+                             "symbol per lane (wide_alphabet=True is PolicyGradientTrainer's default objective only)")
         for k, v in sampled.items():
             if k not in self._FIXED:
                 raise TypeError(f"MWERTrainer got an unexpected keyword argument {k!r}")

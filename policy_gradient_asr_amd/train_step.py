@@ -135,8 +135,10 @@ class DataParallelStep:
     Subclasses provide ``forward_loss(batch, global_batch) -> scalar loss`` already divided by the
     GLOBAL batch size, so the summed gradient is the global-batch gradient."""
 
-    def __init__(self, model, lr=5e-4, world_size=1, process_group=None, precision=None, max_grad_norm=None):
-        """precision: "f32" (the library default: the reference's arithmetic, torch fp32 -- every big product as six bf16 MFMA terms
+    def __init__(self, model, lr=5e-4, world_size=1, process_group=None, precision=None, max_grad_norm=None, wide_alphabet=False):
+        """wide_alphabet: False (default) -- an alphabet of more than 64 symbols is refused, as ever; True -- up to 1024 symbols
+        (hipops.MAX_VOCAB_WIDE) on the wide kernels, which run the default objective alone (loss.check_options).
+        precision: "f32" (the library default: the reference's arithmetic, torch fp32 -- every big product as six bf16 MFMA terms
         of three-plane operands, exact to 2^-24: three-plane sweeps, six-product W_ih projections / input and weight gradients,
         gemm_x6.hip; the small products on the exact fp32 MFMA) or "bf16x3" (opt-in: 3-term products of two-plane operands, within
         the 1e-3 bar, ~20 % faster) -- hipops.PRECISION_MODES; None = whatever mode is set when a step runs.
@@ -147,6 +149,7 @@ class DataParallelStep:
         not counted by ``applied_steps``).  float("inf") measures and guards without ever scaling.  No host synchronisation:
         ``last_grad_norm`` / ``clip_counts()`` read the result."""
         self.max_grad_norm = check_max_grad_norm(max_grad_norm)
+        self.wide_alphabet = bool(wide_alphabet)
         if precision is not None:
             from . import hipops
             if precision not in hipops.PRECISION_MODES:
@@ -444,8 +447,12 @@ class PolicyGradientTrainer(DataParallelStep):
     def __init__(self, model, lr=5e-4, lam=1.0, seed=0, blank=0, world_size=1, process_group=None, rank=0,
                  reward_decoder="greedy", beam_size=16, precision=None, reward_mode="utterance", num_samples=1,
                  reward_baseline="hypothesis", reward_unit="char", word_delimiter=None, max_grad_norm=None,
-                 score_function="path", max_hyp_len=None, entropy_weight=0.0, kl_weight=0.0, kl_reference=None):
-        """reward_mode: "utterance" (default) -- one reward R = -ED / |y| per utterance, the sum of the reference's per-step rewards
+                 score_function="path", max_hyp_len=None, entropy_weight=0.0, kl_weight=0.0, kl_reference=None, wide_alphabet=False):
+        """wide_alphabet: opt in to alphabets of 65 .. 1024 symbols (subword units).  MAX_VOCAB becomes 1024, and such a model takes
+        the default objective alone: reward_decoder="greedy", reward_mode="utterance", num_samples=1, reward_baseline="hypothesis",
+        reward_unit="char", score_function="path", entropy_weight=0, kl_weight=0 -- anything else raises here and before every
+        step (loss.check_options).  False (default): a model of more than 64 symbols is refused by ``step`` as ever.
+        reward_mode: "utterance" (default) -- one reward R = -ED / |y| per utterance, the sum of the reference's per-step rewards
         (policy_grad.py:10-15) up to a constant the baseline removes; "per_step" -- the per-step rewards themselves, as rewards-to-go
         per frame against the greedy path's reward-to-go at the same frame (loss.PGCTCLossFn; greedy baseline only).
         reward_decoder: which hypothesis the self-critical baseline reward comes from -- "greedy" (best path) or
@@ -488,7 +495,10 @@ class PolicyGradientTrainer(DataParallelStep):
                 raise ValueError(f"kl_reference must be a module with Seq2Seq.logits or 'initial' (got {kl_reference!r})")
             kl_reference = copy.deepcopy(model)          # before the parameters move into the trainer's flat buffer
         super().__init__(model, lr=lr, world_size=world_size, process_group=process_group, precision=precision,
-                         max_grad_norm=max_grad_norm)
+                         max_grad_norm=max_grad_norm, wide_alphabet=wide_alphabet)
+        if self.wide_alphabet:
+            from . import hipops
+            self.MAX_VOCAB = hipops.MAX_VOCAB_WIDE
         if reward_decoder not in ("greedy", "beam"):
             raise ValueError("reward_decoder must be 'greedy' or 'beam'")
         if reward_mode not in ("utterance", "per_step"):
@@ -590,10 +600,10 @@ class PolicyGradientTrainer(DataParallelStep):
         from .loss import PGOptions, check_options
         vocab = getattr(getattr(self.model, "head", None), "out_features", None)
         opt = PGOptions(blank=self.blank, per_step=self.reward_mode == "per_step", num_samples=self.num_samples,
-                        baseline=self.reward_baseline, reward_unit=self.reward_unit, word_delimiter=self.word_delimiter,
+                        beam=self.beam_size if self.reward_decoder == "beam" else 0, baseline=self.reward_baseline, reward_unit=self.reward_unit, word_delimiter=self.word_delimiter,
                         score_function=self.score_function, max_hyp_len=self.max_hyp_len, entropy_weight=self.entropy_weight,
                         kl_weight=self.kl_weight)
-        return check_options(opt, vocab=vocab, frames=frames, symbols=symbols)
+        return check_options(opt, vocab=vocab, frames=frames, symbols=symbols, wide_check=self.wide_alphabet)
 
     def _check_limits(self, x, targets):
         """The kernels' compiled-in limits, stated where the caller can read them (otherwise the first symptom is a
@@ -605,7 +615,8 @@ class PolicyGradientTrainer(DataParallelStep):
                              "clusters of 16 utterances resident on the chip; use more ranks or smaller batches")
         vocab = getattr(getattr(self.model, "head", None), "out_features", None)
         if vocab is not None and vocab > self.MAX_VOCAB:
-            raise ValueError(f"alphabet of {vocab} symbols > {self.MAX_VOCAB}: the CTC / sampling kernels hold one frame's scores in one wave")
+            raise ValueError(f"alphabet of {vocab} symbols > {self.MAX_VOCAB}: the CTC / sampling kernels hold one frame's scores in one wave"
+                             + ("" if self.wide_alphabet else "; wide_alphabet=True takes up to 1024 symbols with the default objective"))
         if self.reward_decoder == "beam" and self.beam_size > 128:
             raise ValueError("beam_size > 128 is not supported by pgasr_ctc_beam_search")
         self._checked_options(frames=x.shape[2], symbols=targets.shape[1])
