@@ -849,7 +849,44 @@ int pgasr_ctc_beam_search_nbest(const void* log_probs, int is_f64, long long str
                                 const float* lm_table, int lm_order, double lm_alpha, double lm_beta);
 
 /* ------------------------------------------------------------------------------------------
- * A7-RESCORE  Second pass over N-best lists: an n-gram LM score of every hypothesis, a weighted total and its rank.
+ * A7-WIDE  The same search over rows of up to 1024 symbols (subword units): the reference's CTCDecoder.decode (CTCdecoder.py:41-116)
+ * over all V symbols, no heuristic symbol pruning, returning the first `nbest` entries of the final beam in the layout and with the
+ * conventions of pgasr_ctc_beam_search_nbest (nbest = 1: the 1-best search).  A kernel of its own (csrc/beam_wide.hip): one
+ * workgroup of 256 threads per utterance, a beam x V bitmap for the merge test, the hash-consed trie with 10-bit symbols, and a
+ * top-`beam` SELECTION in place of the sort of all beam * V candidates -- a threshold (the beam-th largest of 2 * beam candidates that
+ * certainly exist), a list of the candidates at or above it (2048 items), a bitonic sort of that list; a frame whose list overflows
+ * takes a counting selection instead (radix passes over the 64-bit score image and the touch time with an LDS histogram, keys
+ * recomputed per pass, until exactly `beam` are kept).  Both rank by the same unique key (score image, touch time), so both return
+ * what the sort of everything would.
+ *   log_probs, strides, lengths, blank, out_tokens (nbest, B, tok_stride), out_len / out_score (nbest, B), out_count (B): as A7-NBEST.
+ *               Every word of the outputs is written; rows r >= count[b]: length 0, score +inf, tokens zero; lengths[b] == 0: count 1,
+ *               the empty prefix, score -0.0.  fp32 input: fp64 carries with fp32 exp/log on differences; fp64 input: exact fp64
+ *               math; both in the argument order of the A7 kernels, so that for V <= 64 every output word equals
+ *               pgasr_ctc_beam_search_nbest's (no table, flags bit 3 clear) bit for bit wherever no two candidates tie exactly.
+ *   Tie order: score descending, then first touch in the reference's loop nest (symbol-major, rank-minor; within one (symbol, entry)
+ *               iteration the extension is touched before the kept prefix).  The exception A7-NBEST documents (an entry's stay
+ *               candidate against its own repeat extension at exactly equal score) does NOT apply here: the touch time carries
+ *               one more bit that orders the two as the reference does.
+ *   flags bit 0: collapse_fn per hypothesis, as A7-NBEST.  Bit 5 (value 32): every frame takes the counting selection (the same
+ *               result bit for bit; for tests and measurements).  Any other bit: PGASR_ERR_INVALID_ARG.
+ *   out_counting_frames: (B) int32 or NULL: the number of frames of each utterance that took the counting selection.
+ *   Limits: 1 <= V <= 1024 (narrow rows are accepted), beam <= 128, 1 <= nbest <= beam, tok_stride >= T; node ids are 22 bits
+ *               (a trie node is parent << 10 | symbol in one word): T * beam + 1 >= 2^22 -> PGASR_ERR_UNSUPPORTED.
+ *   Every loop is bounded: hash probes by the table size, ancestor walks by lengths[b], radix passes by the key width (12).
+ *   Checked before any HIP call, in this order: NULL log_probs / out_tokens / out_len / out_score, T, B, V, beam <= 0, blank outside
+ *   [0, V) -> PGASR_ERR_INVALID_ARG; V > 1024 or beam > 128 -> PGASR_ERR_UNSUPPORTED; unknown flag bits, nbest < 1, nbest > beam,
+ *   tok_stride < T, NULL out_count -> PGASR_ERR_INVALID_ARG; the workspace (pgasr_beam_wide_workspace_bytes; 0 for T, B or
+ *   beam <= 0) -> PGASR_ERR_WORKSPACE; the node-id width -> PGASR_ERR_UNSUPPORTED.  No host synchronisation.
+ * ---------------------------------------------------------------------------------------- */
+size_t pgasr_beam_wide_workspace_bytes(int T, int B, int V, int beam);
+int pgasr_ctc_beam_search_wide(const void* log_probs, int is_f64, long long stride_t, long long stride_b,
+                               const int32_t* lengths, int T, int B, int V, int beam, int blank, int flags,
+                               int nbest, int32_t* out_tokens, int tok_stride, int32_t* out_len, double* out_score,
+                               int32_t* out_count, int32_t* out_counting_frames,
+                               void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * A7-RESCORE Second pass over N-best lists: an n-gram LM score of every hypothesis, a weighted total and its rank.
  *   tokens (N, B, tok_stride) int32, len (N, B), count (B): a list as pgasr_ctc_beam_search_nbest writes it (len is clamped to
  *   [0, tok_stride], count to [0, N]); am (N, B) fp64: the caller's acoustic score, lower is better.
  *   lm_table / lm_order: a table as pgasr_ctc_beam_search_lm takes it, or NULL / 0 (lm_logp = 0).  For n < count[b]:

@@ -41,19 +41,37 @@ MBRDecoded = collections.namedtuple("MBRDecoded", "tokens lengths best risk post
 
 
 class CTCDecoder:
-    def __init__(self, alphabet, device=None, lm=None, lm_alpha=0.0, lm_beta=0.0, fast_lm=False):
+    def __init__(self, alphabet, device=None, lm=None, lm_alpha=0.0, lm_beta=0.0, fast_lm=False, wide_search=False):
         """lm: None (default: the acoustic search of the reference) or a ``lm.CharNgramLM``; every extension of a prefix by a
         non-blank symbol s then gets ``lm_alpha * ln p_lm(s | last order-1 symbols) + lm_beta`` added (Hannun/Maas,
         arXiv:1408.2873 -- the place CTCdecoder.py:90-96 marks for an LM score).  ``decode`` / ``decode_batch`` use these values
         unless a call overrides them.
         fast_lm: ``decode_batch`` with an LM takes the single-wave kernel where its limits allow (``hipops.ctc_beam_search``:
         fp32 log-probs, beam_size <= 16, at most 64 symbols, T * beam_size <= 24576, T <= 4096) instead of the several times slower
-        workgroup kernel; a call may override it.  ``decode`` is the fp64 drop-in and always takes the exact kernel."""
+        workgroup kernel; a call may override it.  ``decode`` is the fp64 drop-in and always takes the exact kernel.
+        wide_search: opt in to the exact search over rows of 65 .. 1024 symbols (``hipops.ctc_beam_search_wide``, csrc/beam_wide.hip):
+        ``decode`` and ``decode_batch``, the ``nbest=`` forms included, then take that entry for rows of more than 64 symbols.  It has
+        no language-model fusion: such rows together with an LM raise.  Rows of at most 64 symbols make the calls they always made;
+        with the default False wider rows are refused as before."""
         self.alphabet = alphabet
         self.NEG_INF = -float("inf")
         self.device = device
         self.lm, self.lm_alpha, self.lm_beta = lm, float(lm_alpha), float(lm_beta)
         self.fast_lm = bool(fast_lm)
+        self.wide_search = bool(wide_search)
+
+    def _takes_wide(self, V, args):
+        """Whether rows of V symbols go to the wide search; refuses what neither search takes.  Touches no device."""
+        if V <= hipops.MAX_VOCAB_NARROW:
+            return False
+        if not self.wide_search:
+            _check_search_vocab(V)
+        if V > hipops.MAX_VOCAB_SEARCH_WIDE:
+            raise ValueError(f"the wide beam search takes at most {hipops.MAX_VOCAB_SEARCH_WIDE} output symbols (got {V})")
+        if args["lm"] is not None:
+            raise ValueError(f"lm: the wide beam search ({V} > {hipops.MAX_VOCAB_NARROW} symbols) has no language-model fusion; "
+                             f"search without one (lm=None)")
+        return True
 
     def _lm_args(self, lm, lm_alpha, lm_beta):
         return {"lm": self.lm if lm is _UNSET else lm,
@@ -65,15 +83,18 @@ class CTCDecoder:
         Returns (label tuple, negative log-likelihood of that prefix).  With a language model (the decoder's, or ``lm`` /
         ``lm_alpha`` / ``lm_beta`` given here; ``lm=None`` switches it off for this call) the second value is the FUSED score
         -logsumexp(p_blank, p_nonblank) with the LM bonuses in it, not a negative log-likelihood.
-        Limits of the device search (the reference has none): beam_size <= 128 and at most 64 output symbols --
-        a larger request raises instead of silently searching a narrower beam.
+        Limits of the device search (the reference has none): beam_size <= 128 and at most 64 output symbols (1024 with
+        ``wide_search=True`` and no language model) -- a larger request raises instead of silently searching a narrower beam.
         nbest: None (default: the pair above) or N with 1 <= N <= beam_size: a list of (label tuple, score) pairs, the first
         min(N, size of the final beam) entries of the final beam in the search's rank order (best first; equal scores in first-touch
         order, like the reference's sorted(...)[:N])."""
+        args = self._lm_args(lm, lm_alpha, lm_beta)
+        if self.wide_search:                                 # refused before a device is asked for
+            self._takes_wide(np.shape(probs)[-1], args)
         dev = _device(self.device)
         probs = np.asarray(probs)
         T, V = probs.shape
-        _check_search_vocab(V)
+        wide = self._takes_wide(V, args)
         if T == 0:
             return (tuple(), -0.0) if nbest is None else [(tuple(), -0.0)]
         with np.errstate(divide="ignore"):
@@ -82,12 +103,16 @@ class CTCDecoder:
         if int(beam_size) > BEAM_KMAX:
             raise ValueError(f"beam_size {beam_size} exceeds the device search's limit of {BEAM_KMAX}")
         if nbest is not None:
-            nb = hipops.ctc_beam_search_nbest(lp, None, beam=int(beam_size), nbest=int(nbest), blank=int(blank),
-                                              **self._lm_args(lm, lm_alpha, lm_beta))
+            if wide:
+                nb = hipops.ctc_beam_search_wide(lp, None, beam=int(beam_size), nbest=int(nbest), blank=int(blank))
+            else:
+                nb = hipops.ctc_beam_search_nbest(lp, None, beam=int(beam_size), nbest=int(nbest), blank=int(blank), **args)
             tok, tl, sc = nb.tokens[:, 0].cpu(), nb.lengths[:, 0].tolist(), nb.score[:, 0].tolist()
             return [(tuple(int(x) for x in tok[r, :tl[r]].tolist()), float(sc[r])) for r in range(int(nb.count[0].item()))]
-        tokens, tl, score = hipops.ctc_beam_search(lp, None, beam=int(beam_size), blank=int(blank),
-                                                   **self._lm_args(lm, lm_alpha, lm_beta))
+        if wide:
+            tokens, tl, score = hipops.ctc_beam_search_wide(lp, None, beam=int(beam_size), blank=int(blank))
+        else:
+            tokens, tl, score = hipops.ctc_beam_search(lp, None, beam=int(beam_size), blank=int(blank), **args)
         n = int(tl[0].item())
         return tuple(int(x) for x in tokens[0, :n].tolist()), float(score[0].item())
 
@@ -100,12 +125,14 @@ class CTCDecoder:
         score (N,B), count (B)), still without a host sync; see ``hipops.ctc_beam_search_nbest``.
         fast_lm: None (default: the decoder's own) or a bool -- with an LM, take the single-wave kernel where its limits allow."""
         fast_lm = self.fast_lm if fast_lm is None else bool(fast_lm)
-        _check_search_vocab(log_probs.shape[-1])
+        args = self._lm_args(lm, lm_alpha, lm_beta)
+        if self._takes_wide(log_probs.shape[-1], args):
+            return hipops.ctc_beam_search_wide(log_probs, lengths, beam=int(beam_size), blank=int(blank),
+                                               nbest=None if nbest is None else int(nbest))
         if nbest is not None:
             return hipops.ctc_beam_search_nbest(log_probs, lengths, beam=int(beam_size), nbest=int(nbest), blank=int(blank),
-                                                fast_lm=fast_lm, **self._lm_args(lm, lm_alpha, lm_beta))
-        return hipops.ctc_beam_search(log_probs, lengths, beam=int(beam_size), blank=int(blank), fast_lm=fast_lm,
-                                      **self._lm_args(lm, lm_alpha, lm_beta))
+                                                fast_lm=fast_lm, **args)
+        return hipops.ctc_beam_search(log_probs, lengths, beam=int(beam_size), blank=int(blank), fast_lm=fast_lm, **args)
 
     def _word_delimiter(self, word_delimiter):
         if word_delimiter is not None:

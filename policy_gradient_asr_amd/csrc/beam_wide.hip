@@ -1,0 +1,443 @@
+// Exact CTC prefix beam search for rows of up to 1024 symbols on gfx950 (CTCdecoder.py:41-116; include/pgasr_hip.h, A7-WIDE).
+//
+// The kernels of beam.hip lay one symbol per lane, pack a trie node as parent << 8 | symbol and SORT all beam * V candidates of a
+// frame: at V = 1024, beam = 128 that is 131072 candidates, which neither fit the LDS nor are worth sorting -- at most `beam` survive.
+// This kernel keeps that file's algebra (the same candidates, the same log-sum-exp calls in the same argument order, so the scores
+// are the same bits) and replaces the sort by a top-`beam` SELECTION that returns exactly what the sort would:
+//
+//   * one workgroup of 256 threads per utterance, frames a serial chain; the frame's V log-probs and the beam state (p_b, p_nb, node
+//     id, last symbol, parent id, the parent's position) live in LDS;
+//   * prefix identity is the hash-consed trie of beam.hip in the global workspace with 10-bit symbols (node = parent << 10 | symbol);
+//     only the winners of a frame insert nodes;
+//   * "the extension of entry i by s already sits in the beam" is bit (i, s) of a beam x V bitmap in LDS, rebuilt every frame; such an
+//     extension is no candidate of its own: its mass goes into that entry's stay candidate in the reference's update order;
+//   * every candidate has the unique rank key (score image, touch time): score image = the order-preserving u64 map of its fp64 total,
+//     touch time = 2 * (symbol * nb + rank) + (0: the extension touched first in that iteration of the reference's loop nest, 1: the
+//     kept prefix touched second) -- the position of the candidate's FIRST touch in the reference's dict, so (score descending, time
+//     ascending) is the reference's stable sort, the stay-against-own-repeat pair included;
+//   * selection: a threshold theta = the beam-th largest score image among 2 * nb candidates that certainly exist (every stay, every
+//     entry's extension by the frame's best symbol that is neither merged nor its own repeat) -- nothing below theta can enter the
+//     beam; all candidates >= theta are appended to an LDS list of WIDE_CAP items and sorted by the bitonic sort of beam.hip.  If the
+//     list overflows (or flags bit 5 forces it) a COUNTING selection finds the exact (score image, time) of rank beam - 1 by radix
+//     passes over the 96-bit key with an LDS histogram, most significant digit first, keys recomputed in every pass; the candidates
+//     at or above that cut -- exactly min(beam, all) by uniqueness of the key -- are then listed and sorted.  Both paths rank by the
+//     same key, so both are exact and equal.
+// Every loop is bounded by construction: hash probes by the table size, ancestor walks by lengths[b], radix passes by the key width.
+#include "common.h"
+#include <cmath>
+
+namespace {
+
+constexpr int WIDE_KMAX = 128;
+constexpr int WIDE_VMAX = 1024;
+constexpr int WIDE_THREADS = 256;
+constexpr int WIDE_CAP = 2048;                       // items of the candidate list: a frame with more candidates >= theta takes the counting selection
+constexpr int WIDE_SYM_BITS = 10;
+constexpr unsigned WIDE_SYM_MASK = (1u << WIDE_SYM_BITS) - 1u;
+constexpr long long WIDE_MAX_NODES = 1ll << 22;      // node ids are 22 bits: parent << 10 | symbol is one 32-bit word
+constexpr int WIDE_RADIX_PASSES = 12;                // 8 digits of the score image, 4 of the touch time
+constexpr unsigned WIDE_STAY = 0x80000000u;          // cand: WIDE_STAY | entry, else entry * V + symbol
+
+struct WideWs {
+    unsigned long long* table;   // [B][H] open addressing: (key + 1) << 32 | node id; 0 = empty
+    unsigned* nodes;             // [B][NN] parent << 10 | symbol; node 0 = root
+    int H, NN;
+};
+
+__host__ __device__ inline size_t wide_ws_layout(int T, int B, int beam, WideWs* ws, char* base) {
+    const long long nn = (long long)T * beam + 1;
+    long long H = 1024;
+    while (H < 2 * nn) H <<= 1;
+    size_t off = 0;
+    const size_t t_off = off; off += (size_t)B * (size_t)H * sizeof(unsigned long long);
+    off = (off + 255) / 256 * 256;
+    const size_t n_off = off; off += (size_t)B * (size_t)nn * sizeof(unsigned);
+    off = (off + 255) / 256 * 256;
+    if (ws) {
+        ws->table = (unsigned long long*)(base + t_off);
+        ws->nodes = (unsigned*)(base + n_off);
+        ws->H = (int)H; ws->NN = (int)nn;
+    }
+    return off;
+}
+
+// CTCdecoder.py:31-39 with 2 or 3 arguments, argument order preserved: restated from beam.hip (lse2 / lse3 / lse2x / lse3x) line for
+// line, so that both files give the same bits on the same inputs.  FAST (fp32 input): fp64 carries, fp32 exp/log on the differences.
+template <bool FAST> __device__ __forceinline__ double wlse2(double a, double b) {
+    const double m = fmax(a, b);
+    if (m == -INFINITY) return -INFINITY;
+    if (!FAST) return m + log(exp(a - m) + exp(b - m));
+    return m + (double)__logf(__expf((float)(a - m)) + __expf((float)(b - m)));
+}
+template <bool FAST> __device__ __forceinline__ double wlse3(double a, double b, double c) {
+    const double m = fmax(fmax(a, b), c);
+    if (m == -INFINITY) return -INFINITY;
+    if (!FAST) return m + log((exp(a - m) + exp(b - m)) + exp(c - m));
+    return m + (double)__logf((__expf((float)(a - m)) + __expf((float)(b - m))) + __expf((float)(c - m)));
+}
+
+// order-preserving map double -> u64 (ascending), as in beam.hip
+__device__ __forceinline__ unsigned long long wide_image(double x) {
+    const unsigned long long b = (unsigned long long)__double_as_longlong(x);
+    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+}
+
+struct WideItem { unsigned long long key; unsigned time; unsigned cand; };      // key = ~image(score): ascending sort = score descending
+
+__device__ __forceinline__ bool wide_less(const WideItem& a, const WideItem& b) {
+    return a.key < b.key || (a.key == b.key && a.time < b.time);
+}
+
+// p_nb of the extension of an entry (p_b, p_nb) by a symbol of log-prob ps (:90-96); rep: the symbol repeats the entry's last one
+template <bool FAST> __device__ __forceinline__ double wide_ext(double pbj, double pnbj, double ps, bool rep) {
+    return rep ? wlse2<FAST>(-INFINITY, pbj + ps) : wlse3<FAST>(-INFINITY, pbj + ps, pnbj + ps);
+}
+
+// LDS: fixed layout for the largest shape (all offsets multiples of 16)
+struct WideLds {
+    WideItem items[WIDE_CAP];                   // 32 KB candidate list
+    double frame[WIDE_VMAX];                    // the frame's log-probs
+    unsigned bitmap[WIDE_KMAX * (WIDE_VMAX / 32)];      // bit (i, s): the extension of entry i by s sits in the beam
+    unsigned long long tkeys[2 * WIDE_KMAX];    // the 2 * nb score images the threshold is formed from
+    double pb[2][WIDE_KMAX], pnb[2][WIDE_KMAX]; // beam state, double-buffered
+    double st_pb[WIDE_KMAX], st_pnb[WIDE_KMAX]; // the stay candidate of every entry
+    unsigned long long st_img[WIDE_KMAX];
+    int id[2][WIDE_KMAX], last[2][WIDE_KMAX], par[2][WIDE_KMAX];
+    int pidx[WIDE_KMAX];                        // position of the entry's parent in the beam, -1 if it is not there
+    unsigned st_time[WIDE_KMAX];
+    unsigned hist[256];
+    unsigned long long theta, cut_hi;
+    unsigned cut_lo;
+    int nb, nodes, total, done, need, counting;
+};
+
+template <typename TIn, bool FAST>
+__global__ __launch_bounds__(WIDE_THREADS) void beam_wide_kernel(
+    const TIn* __restrict__ lp, long long stride_t, long long stride_b, const int32_t* __restrict__ lengths,
+    int T, int V, int K, int blank, int collapse, int force_counting, WideWs ws, int nbest, int tok_stride,
+    int32_t* __restrict__ out_tokens, int32_t* __restrict__ out_len, double* __restrict__ out_score,
+    int32_t* __restrict__ out_count, int32_t* __restrict__ out_counting) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    WideLds& L = *reinterpret_cast<WideLds*>(smem);
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    int Tb = lengths ? lengths[b] : T; Tb = Tb < 0 ? 0 : (Tb > T ? T : Tb);
+    const int W = (V + 31) >> 5;                          // bitmap words per entry
+
+    unsigned long long* table = ws.table + (size_t)b * ws.H;
+    unsigned* nodes = ws.nodes + (size_t)b * ws.NN;
+    const unsigned hmask = (unsigned)ws.H - 1u;
+
+    if (tid == 0) {
+        L.nb = 1; L.nodes = 1; L.counting = 0;
+        L.id[0][0] = 0; L.last[0][0] = -1; L.par[0][0] = -1; L.pb[0][0] = 0.0; L.pnb[0][0] = -INFINITY;
+        nodes[0] = 0xFFFFFFFFu;
+    }
+    __syncthreads();
+    int cur = 0;
+    for (int t = 0; t < Tb; ++t) {
+        const int nb = L.nb;
+        const int* cid = L.id[cur]; const int* clast = L.last[cur]; const int* cpar = L.par[cur];
+        const double* cpb = L.pb[cur]; const double* cpnb = L.pnb[cur];
+
+        // ---- A: the frame, an empty bitmap, the parents' positions ----
+        for (int s = tid; s < V; s += WIDE_THREADS) L.frame[s] = (double)lp[(long long)t * stride_t + (long long)b * stride_b + s];
+        for (int i = tid; i < nb * W; i += WIDE_THREADS) L.bitmap[i] = 0u;
+        if (tid < nb) {
+            int f = -1;
+            for (int i = 0; i < nb; ++i) if (cid[i] == cpar[tid]) f = i;
+            L.pidx[tid] = f;
+        }
+        __syncthreads();
+        if (tid < nb && L.pidx[tid] >= 0) atomicOr(&L.bitmap[L.pidx[tid] * W + (clast[tid] >> 5)], 1u << (clast[tid] & 31));
+        __syncthreads();
+
+        // ---- B: stay candidates (:78-82, :90-96 merged, :103-106), as in beam.hip; the threshold's 2 * nb score images ----
+        if (tid < nb) {
+            const int j = tid;
+            const double fb = L.frame[blank];
+            const double npb = wlse3<FAST>(-INFINITY, cpb[j] + fb, cpnb[j] + fb);
+            double npnb = -INFINITY;
+            unsigned time = 2u * (unsigned)(blank * nb + j);
+            const int lj = clast[j];
+            if (lj >= 0 && lj != blank) {
+                const double pl = L.frame[lj];
+                const int i = L.pidx[j];
+                const double own = cpnb[j] + pl;                                  // repeat branch (:103-106): touched second in iteration (lj, j)
+                const unsigned t_own = 2u * (unsigned)(lj * nb + j) + 1u;
+                time = t_own < time ? t_own : time;
+                if (i >= 0) {
+                    const double e1 = cpb[i] + pl, e2 = cpnb[i] + pl;             // extension of parent i by lj (:90-96): touched first in iteration (lj, i)
+                    const bool rep = (clast[i] == lj);
+                    if (i < j) {
+                        npnb = rep ? wlse2<FAST>(npnb, e1) : wlse3<FAST>(npnb, e1, e2);
+                        npnb = wlse2<FAST>(npnb, own);
+                    } else {
+                        npnb = wlse2<FAST>(npnb, own);
+                        npnb = rep ? wlse2<FAST>(npnb, e1) : wlse3<FAST>(npnb, e1, e2);
+                    }
+                    const unsigned t_ext = 2u * (unsigned)(lj * nb + i);
+                    time = t_ext < time ? t_ext : time;
+                } else {
+                    npnb = wlse2<FAST>(npnb, own);
+                }
+            }
+            const unsigned long long img = wide_image(wlse2<FAST>(npb, npnb));
+            L.st_pb[j] = npb; L.st_pnb[j] = npnb; L.st_img[j] = img; L.st_time[j] = time;
+            L.tkeys[j] = img;
+        }
+        // wave w takes entries w, w + 4, ..: the best log-prob among the symbols that are a candidate of their own for this entry
+        for (int j = wave; j < nb; j += WIDE_THREADS / 64) {
+            double best = -INFINITY;
+            bool found = false;
+            const int lj = clast[j];
+            for (int s = lane; s < V; s += 64) {
+                if (s == blank || s == lj || ((L.bitmap[j * W + (s >> 5)] >> (s & 31)) & 1u)) continue;
+                const double v = L.frame[s];
+                best = found ? fmax(best, v) : v;
+                found = true;
+            }
+            const bool any = __ballot(found) != 0ull;
+            if (!found) best = -INFINITY;
+            for (int o = 32; o > 0; o >>= 1) best = fmax(best, __shfl_xor(best, o));
+            if (lane == 0)
+                L.tkeys[nb + j] = any ? wide_image(wlse2<FAST>(-INFINITY, wide_ext<FAST>(cpb[j], cpnb[j], best, false))) : 0ull;
+        }
+        for (int i = 2 * nb + tid; i < 2 * WIDE_KMAX; i += WIDE_THREADS) L.tkeys[i] = 0ull;       // 0 is below every real image
+        if (tid == 0) { L.total = 0; L.theta = 0ull; }
+        __syncthreads();
+
+        // ---- C: theta = the K-th largest of the 2 * nb images (0 if there are fewer than K): the slot whose value v has fewer than K
+        //      images above it and at least K at or above it ----
+        {
+            const unsigned long long mine = L.tkeys[tid];                         // 2 * WIDE_KMAX == WIDE_THREADS
+            int gt = 0, ge = 0;
+            for (int i = 0; i < 2 * WIDE_KMAX; ++i) { const unsigned long long x = L.tkeys[i]; gt += x > mine; ge += x >= mine; }
+            if (gt < K && K <= ge) L.theta = mine;                                // every such slot holds the same value
+        }
+        __syncthreads();
+
+        // every candidate of the frame, visited by all threads in step (the appends are wave-aggregated): f(valid, image, time, cand)
+        auto for_each_candidate = [&](auto&& f) {
+            for (int j = 0; j < nb; ++j) {
+                const double pbj = cpb[j], pnbj = cpnb[j];
+                const int lj = clast[j];
+                for (int s0 = 0; s0 < V; s0 += WIDE_THREADS) {
+                    const int s = s0 + tid;
+                    bool valid = s < V && s != blank;
+                    if (valid) valid = !((L.bitmap[j * W + (s >> 5)] >> (s & 31)) & 1u);
+                    unsigned long long img = 0ull;
+                    if (valid) img = wide_image(wlse2<FAST>(-INFINITY, wide_ext<FAST>(pbj, pnbj, L.frame[s], s == lj)));
+                    f(valid, img, 2u * (unsigned)(s * nb + j), (unsigned)(j * V + s));
+                }
+            }
+            const bool valid = tid < nb;
+            f(valid, valid ? L.st_img[tid] : 0ull, valid ? L.st_time[tid] : 0u, WIDE_STAY | (unsigned)tid);
+        };
+        // list every candidate at or above the cut (hi, lo) of the key (image, ~time)
+        auto collect = [&](unsigned long long chi, unsigned clo) {
+            for_each_candidate([&](bool valid, unsigned long long img, unsigned time, unsigned cand) {
+                const bool want = valid && (img > chi || (img == chi && ~time >= clo));
+                const unsigned long long m = __ballot(want);
+                if (m == 0ull) return;
+                const int leader = __ffsll((long long)m) - 1;
+                int base = 0;
+                if (lane == leader) base = atomicAdd(&L.total, __popcll(m));
+                base = __shfl(base, leader);
+                const int pos = base + __popcll(m & ((1ull << lane) - 1ull));
+                if (want && pos < WIDE_CAP) { WideItem it; it.key = ~img; it.time = time; it.cand = cand; L.items[pos] = it; }
+            });
+        };
+
+        bool counting = force_counting != 0;
+        if (!counting) {
+            collect(L.theta, 0u);
+            __syncthreads();
+            counting = L.total > WIDE_CAP;
+        }
+        if (counting) {
+            // ---- D: counting selection: the key of rank K - 1, digit by digit from the top ----
+            if (tid == 0) { L.cut_hi = 0ull; L.cut_lo = 0u; L.need = K; L.done = 0; L.counting += 1; }
+            for (int p = 0; p < WIDE_RADIX_PASSES; ++p) {
+                L.hist[tid] = 0u;                                                 // 256 bins, 256 threads
+                __syncthreads();
+                const unsigned long long phi = L.cut_hi;
+                const unsigned plo = L.cut_lo;
+                for_each_candidate([&](bool valid, unsigned long long img, unsigned time, unsigned) {
+                    const unsigned lo = ~time;
+                    bool match; unsigned d;
+                    if (p < 8) {
+                        match = (p == 0) || ((img >> (64 - 8 * p)) == (phi >> (64 - 8 * p)));
+                        d = (unsigned)(img >> (56 - 8 * p)) & 255u;
+                    } else {
+                        const int q = p - 8;
+                        match = (img == phi) && (q == 0 || (lo >> (32 - 8 * q)) == (plo >> (32 - 8 * q)));
+                        d = (lo >> (24 - 8 * q)) & 255u;
+                    }
+                    const bool in = valid && match;
+                    const unsigned long long m = __ballot(in);
+                    if (m == 0ull) return;
+                    const int leader = __ffsll((long long)m) - 1;
+                    const unsigned d0 = (unsigned)__shfl((int)d, leader);
+                    if (__ballot(in && d != d0) == 0ull) {                        // one bin for the whole wave (flat rows): one atomic
+                        if (lane == leader) atomicAdd(&L.hist[d0], (unsigned)__popcll(m));
+                    } else if (in) atomicAdd(&L.hist[d], 1u);
+                });
+                __syncthreads();
+                if (tid == 0) {
+                    const int need = L.need;
+                    int cum = 0, d = 255;
+                    for (; d >= 0; --d) { cum += (int)L.hist[d]; if (cum >= need) break; }
+                    if (d < 0) {                                                  // fewer than `need` candidates in all (first pass only): keep every one
+                        L.cut_hi = 0ull; L.cut_lo = 0u; L.done = 1;
+                    } else {
+                        if (p < 8) L.cut_hi = phi | ((unsigned long long)d << (56 - 8 * p));
+                        else L.cut_lo = plo | ((unsigned)d << (24 - 8 * (p - 8)));
+                        L.need = need - (cum - (int)L.hist[d]);
+                        if (cum == need) L.done = 1;                              // the whole bin is kept: the cut is the bin's lower edge
+                    }
+                }
+                __syncthreads();
+                if (L.done) break;
+            }
+            if (tid == 0) L.total = 0;
+            __syncthreads();
+            collect(L.cut_hi, L.cut_lo);
+            __syncthreads();
+        }
+        // ---- E: bitonic sort of the list (beam.hip's: element i belongs to thread i % 256, passes inside a wave need no barrier) ----
+        int total = L.total; total = total > WIDE_CAP ? WIDE_CAP : total;         // the counting selection lists at most K <= WIDE_CAP
+        int P = 2; while (P < total) P <<= 1;
+        for (int i = total + tid; i < P; i += WIDE_THREADS) { WideItem it; it.key = ~0ull; it.time = 0xFFFFFFFFu; it.cand = 0xFFFFFFFFu; L.items[i] = it; }
+        __syncthreads();
+        {
+            bool prev_cross = false;
+            for (int k2 = 2; k2 <= P; k2 <<= 1) {
+                for (int j2 = k2 >> 1; j2 > 0; j2 >>= 1) {
+                    const bool cross = j2 >= 64;
+                    if (cross || prev_cross) __syncthreads();
+                    for (int i = tid; i < P; i += WIDE_THREADS) {
+                        const int l = i ^ j2;
+                        if (l > i) {
+                            const WideItem x = L.items[i], y = L.items[l];
+                            const bool up = ((i & k2) == 0);
+                            if (wide_less(y, x) == up) { L.items[i] = y; L.items[l] = x; }
+                        }
+                    }
+                    prev_cross = cross;
+                }
+            }
+            __syncthreads();
+        }
+        // ---- F: new beam: the first min(K, total) items ----
+        const int nxt = cur ^ 1;
+        const int nnew = total < K ? total : K;
+        if (tid < nnew) {
+            const WideItem it = L.items[tid];
+            if (it.cand & WIDE_STAY) {
+                const int j = (int)(it.cand & ~WIDE_STAY);
+                L.pb[nxt][tid] = L.st_pb[j]; L.pnb[nxt][tid] = L.st_pnb[j];
+                L.id[nxt][tid] = cid[j]; L.last[nxt][tid] = clast[j]; L.par[nxt][tid] = cpar[j];
+            } else {
+                const int j = (int)it.cand / V, s = (int)it.cand - j * V;
+                L.pb[nxt][tid] = -INFINITY;
+                L.pnb[nxt][tid] = wide_ext<FAST>(cpb[j], cpnb[j], L.frame[s], s == clast[j]);
+                // canonical node for (id[j], s): look up, else create; at most H probes
+                const unsigned keyv = ((unsigned)cid[j] << WIDE_SYM_BITS) | (unsigned)s;
+                unsigned h = (keyv * 2654435761u) & hmask;
+                int node = -1;
+                bool placed = false;
+                for (int probe = 0; probe < ws.H && !placed; ++probe) {
+                    const unsigned long long slot = table[h];
+                    if (slot == 0ull) {
+                        if (node < 0) { node = atomicAdd(&L.nodes, 1); if (node < ws.NN) nodes[node] = keyv; }
+                        const unsigned long long want = ((unsigned long long)(keyv + 1u) << 32) | (unsigned)node;
+                        const unsigned long long old = atomicCAS(&table[h], 0ull, want);
+                        if (old == 0ull) placed = true;
+                        else if ((unsigned)(old >> 32) == keyv + 1u) { node = (int)(unsigned)old; placed = true; }
+                    } else if ((unsigned)(slot >> 32) == keyv + 1u) { node = (int)(unsigned)slot; placed = true; }
+                    h = (h + 1u) & hmask;
+                }
+                L.id[nxt][tid] = placed ? node : 0; L.last[nxt][tid] = s; L.par[nxt][tid] = cid[j];
+            }
+        }
+        if (tid == 0) L.nb = nnew;
+        __syncthreads();
+        cur = nxt;
+    }
+    // ---- result: the final beam is ranked, row r is entry r; thread r walks entry r's ancestors (at most Tb steps) ----
+    const int B = (int)gridDim.x, N = nbest, S = tok_stride;
+    const int count = N < L.nb ? N : L.nb;
+    int* hlen = L.pidx;
+    if (tid < N) {
+        int n = 0;
+        double sc = INFINITY;
+        if (tid < count) {
+            int32_t* o = out_tokens + ((size_t)tid * B + b) * S;
+            const int head = L.id[cur][tid];
+            for (int v = head; v > 0 && v < ws.NN && n < Tb; v = (int)(nodes[v] >> WIDE_SYM_BITS)) ++n;
+            int v = head;
+            for (int k = n - 1; k >= 0; --k) { const unsigned w = nodes[v]; o[k] = (int32_t)(w & WIDE_SYM_MASK); v = (int)(w >> WIDE_SYM_BITS); }
+            if (collapse) {
+                int w = 0;
+                for (int i = 0; i < n; ++i) if (i == 0 || o[i] != o[i - 1]) { const int32_t x = o[i]; o[w++] = x; }
+                n = w;
+            }
+            sc = -wlse2<FAST>(L.pb[cur][tid], L.pnb[cur][tid]);
+        }
+        hlen[tid] = n;
+        out_len[(size_t)tid * B + b] = n;
+        out_score[(size_t)tid * B + b] = sc;
+    }
+    if (tid == 0) {
+        out_count[b] = count;
+        if (out_counting) out_counting[b] = L.counting;
+    }
+    __threadfence_block();
+    __syncthreads();
+    for (int r = 0; r < N; ++r) {
+        int32_t* o = out_tokens + ((size_t)r * B + b) * S;
+        for (int i = hlen[r] + tid; i < S; i += WIDE_THREADS) o[i] = 0;
+    }
+}
+
+}  // namespace
+
+extern "C" size_t pgasr_beam_wide_workspace_bytes(int T, int B, int V, int beam) {
+    (void)V;
+    if (T <= 0 || B <= 0 || beam <= 0) return 0;
+    return wide_ws_layout(T, B, beam, nullptr, nullptr);
+}
+
+extern "C" int pgasr_ctc_beam_search_wide(const void* log_probs, int is_f64, long long stride_t, long long stride_b,
+                                          const int32_t* lengths, int T, int B, int V, int beam, int blank, int flags,
+                                          int nbest, int32_t* out_tokens, int tok_stride, int32_t* out_len, double* out_score,
+                                          int32_t* out_count, int32_t* out_counting_frames,
+                                          void* workspace, size_t workspace_bytes, void* stream) {
+    // the order and the status codes of pgasr_ctc_beam_search_nbest; nothing below touches HIP until every check has passed
+    if (!log_probs || !out_tokens || !out_len || !out_score) return PGASR_ERR_INVALID_ARG;
+    if (T <= 0 || B <= 0 || V <= 0 || beam <= 0 || blank < 0 || blank >= V) return PGASR_ERR_INVALID_ARG;
+    if (V > WIDE_VMAX || beam > WIDE_KMAX) return PGASR_ERR_UNSUPPORTED;
+    if (flags & ~(1 | 32)) return PGASR_ERR_INVALID_ARG;
+    if (nbest < 1 || nbest > beam || tok_stride < T || !out_count) return PGASR_ERR_INVALID_ARG;
+    WideWs ws;
+    const size_t need = wide_ws_layout(T, B, beam, &ws, (char*)workspace);
+    if (!workspace || workspace_bytes < need) return PGASR_ERR_WORKSPACE;
+    if ((long long)T * beam + 1 >= WIDE_MAX_NODES) return PGASR_ERR_UNSUPPORTED;
+    static_assert(2 * WIDE_KMAX == WIDE_THREADS, "one threshold slot and one histogram bin per thread");
+    static_assert(sizeof(WideLds) <= 160 * 1024, "LDS");
+    hipStream_t st = (hipStream_t)stream;
+    if (hipMemsetAsync(ws.table, 0, (size_t)B * ws.H * sizeof(unsigned long long), st) != hipSuccess) return PGASR_ERR_LAUNCH;
+    const size_t lds = (sizeof(WideLds) + 15) / 16 * 16;
+#define WIDE_LAUNCH(TIN, FAST)                                                                                                    \
+    {                                                                                                                             \
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&beam_wide_kernel<TIN, FAST>),                                    \
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                          \
+        PGASR_LAUNCH_KERNEL((beam_wide_kernel<TIN, FAST>), dim3(B), dim3(WIDE_THREADS), lds, st, (const TIN*)log_probs, stride_t, \
+                           stride_b, lengths, T, V, beam, blank, flags & 1, (flags & 32) ? 1 : 0, ws, nbest, tok_stride,          \
+                           out_tokens, out_len, out_score, out_count, out_counting_frames);                                       \
+    }
+    if (is_f64) WIDE_LAUNCH(double, false) else WIDE_LAUNCH(float, true)
+#undef WIDE_LAUNCH
+    PGASR_CHECK_LAUNCH();
+    return PGASR_OK;
+}

@@ -1560,6 +1560,43 @@ def ctc_beam_search_nbest(log_probs, lengths=None, beam=5, nbest=1, blank=0, col
     return CTCNBest(tokens, tl, score, count)
 
 
+MAX_VOCAB_SEARCH_WIDE = 1024     # csrc/beam_wide.hip: the exact prefix beam search over rows of up to 1024 symbols
+
+
+def ctc_beam_search_wide(log_probs, lengths=None, beam=5, nbest=None, blank=0, collapse=False, counting=False, stats=False):
+    """The exact prefix beam search over rows of up to MAX_VOCAB_SEARCH_WIDE = 1024 symbols (pgasr_ctc_beam_search_wide; narrower
+    rows are taken too): log_probs (T,B,V) fp32 or fp64 as ``ctc_beam_search`` takes them, beam <= 128, no language model.
+    nbest=None (default): the triple of ``ctc_beam_search`` -- tokens (B,T) int32, token_lengths (B) int32, score (B) float64.
+    nbest=N, 1 <= N <= beam: ``CTCNBest`` as ``ctc_beam_search_nbest`` returns it -- tokens (N,B,T), lengths (N,B), score (N,B),
+    count (B) --, rank order score ascending, first touch among equals, without the exception noted there.
+    No host synchronisation.  collapse: collapse_fn on each hypothesis separately.
+    counting: every frame takes the counting selection instead of the threshold list (the same result bit for bit; tests, timing).
+    stats: the counting-frames tensor (B) int32 -- frames of each utterance that took the counting selection -- is returned as one
+    more value behind the result."""
+    lib = _lib.load()
+    if not log_probs.is_cuda or log_probs.dtype not in (torch.float32, torch.float64):
+        raise _lib.PgasrError("log_probs must be a float32/float64 GPU tensor")
+    if log_probs.stride(2) != 1:
+        raise _lib.PgasrError("log_probs must be contiguous in its last dimension")
+    T, B, V = log_probs.shape
+    _req(lengths, torch.int32, "lengths")
+    N, dev = (1 if nbest is None else int(nbest)), log_probs.device
+    ws = _workspace(lib.pgasr_beam_wide_workspace_bytes(T, B, V, int(beam)), dev, "beam_wide")
+    tokens = torch.empty(max(N, 0), B, T, dtype=torch.int32, device=dev)      # the kernel writes every word
+    tl = torch.empty(max(N, 0), B, dtype=torch.int32, device=dev)
+    score = torch.empty(max(N, 0), B, dtype=torch.float64, device=dev)
+    count = torch.empty(B, dtype=torch.int32, device=dev)
+    frames = torch.empty(B, dtype=torch.int32, device=dev) if stats else None
+    with _timed("beam_search_wide"):
+        st = lib.pgasr_ctc_beam_search_wide(_p(log_probs), int(log_probs.dtype == torch.float64), log_probs.stride(0),
+                                            log_probs.stride(1), _p(lengths), T, B, V, int(beam), int(blank),
+                                            int(bool(collapse)) | (32 if counting else 0), N, _p(tokens), T, _p(tl), _p(score),
+                                            _p(count), _p(frames), _p(ws), ws.numel(), _stream())
+    _lib.check(st, "pgasr_ctc_beam_search_wide")
+    res = (tokens[0], tl[0], score[0]) if nbest is None else CTCNBest(tokens, tl, score, count)
+    return (res, frames) if stats else res
+
+
 def mwer_weights(dist, risk_len, target_lengths, hyp_nll, hyp_len, count, nll, Lh, lam, inv_global_batch):
     """Posterior, risks and gradient coefficients of MWER over an N-best list (pgasr_mwer_weights; include/pgasr_hip.h, A13-MWER):
     dist (N,B) int32 (word) edit distances, risk_len (B) int32 what normalises them, target_lengths (B) int32, hyp_nll (N,B) fp32 the

@@ -505,7 +505,7 @@ def predict(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=N
             test_dataset=None, n_feats=120, beam_size=5, features="mfcc", lm_path=None, lm_alpha=0.0, lm_beta=0.0,
             nbest=1, rescore_lm_path=None, rescore_alpha=0.0, rescore_beta=0.0, lm_fast=False, target_rate=None,
             mbr=False, mbr_unit="char", mbr_scale=1.0, rescore_word_lm_path=None, rescore_word_alpha=0.0, rescore_word_beta=0.0,
-            error_report=False, units_path=None):
+            error_report=False, units_path=None, wide_beam=False):
     """model.py:277-339: load model_best.pth, forward, beam=5 prefix search (device side, batched),
     collapse_fn, CER/WER, predicted.txt.  Frames are cut by the FEATURE mask (the reference cuts the
     time axis by the target mask, model.py:322 -- a listed defect).  Returns (CER, WER).
@@ -543,10 +543,17 @@ def predict(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=N
     and one corpus-level line, (S + D + I) / reference length with the S / D / I breakdown for characters and words, is printed after
     the line above.  The return value (the MEAN of the per-utterance rates) and every other output stay what they are.
     beam_size=0: greedy decoding -- arg-max per frame and CTC collapse on the device (``CTCdecoder.greedy_decode``), no search; the only
-    decoder for an alphabet of more than 64 symbols (up to 1024), where beam_size > 0 raises up front.  Not with nbest > 1 or an LM.
+    decoder for an alphabet of more than 64 symbols (up to 1024) without ``wide_beam``, where beam_size > 0 raises up front.  Not with
+    nbest > 1 or an LM.
     units_path: None (default) or a units file (``build_units``) that stands in place of ``alphabet_path``: the references are
     encoded by greedy longest match, the hypotheses are the concatenated units (no ``collapse_fn``: a unit may end with the character the
-    next one starts with), and CER / WER are computed on the decoded strings as ever."""
+    next one starts with), and CER / WER are computed on the decoded strings as ever.
+    wide_beam: False (default: everything above, nothing else) or True: an alphabet of more than 64 symbols (up to 1024) is searched
+    with beam_size > 0 by the exact wide prefix beam search (``CTCDecoder(wide_search=True)``, csrc/beam_wide.hip).  nbest=N then
+    writes ``nbest.tsv`` with the first-pass scores, and the oracle error rate over units (the best hypothesis of every list against
+    the encoded reference, ``metrics.nbest_oracle``) is printed beside CER / WER.  The wide search has no LM fusion and its lists no
+    second pass yet: lm_path, the rescore_* options, mbr and error_report raise for such an alphabet.  Alphabets of at most 64 symbols
+    are not affected by the flag."""
     import os
     import functools
     import torch.utils.data as tud
@@ -579,7 +586,15 @@ def predict(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=N
     if units_path is not None:
         from .units import SubwordUnits
         unit_args = {"units": SubwordUnits.load(units_path)}
-    if len(alphabet) > hipops.MAX_VOCAB_NARROW and not greedy:
+    wide = len(alphabet) > hipops.MAX_VOCAB_NARROW and not greedy and bool(wide_beam)
+    if wide:
+        for name, given in (("lm_path", lm_path is not None), ("rescore_lm_path", rescore_lm_path is not None),
+                            ("rescore_word_lm_path", rescore_word_lm_path is not None), ("mbr", bool(mbr)),
+                            ("error_report", bool(error_report))):
+            if given:
+                raise ValueError(f"{name}: not with the wide beam search ({len(alphabet)} > {hipops.MAX_VOCAB_NARROW} symbols), which "
+                                 f"has no LM fusion, no second pass over its lists and no error report yet")
+    if len(alphabet) > hipops.MAX_VOCAB_NARROW and not greedy and not wide:
         raise ValueError(f"the beam search takes at most {hipops.MAX_VOCAB_NARROW} symbols and {alphabet_path} has {len(alphabet)}: "
                          f"decode greedily with beam_size=0 (up to {hipops.MAX_VOCAB_WIDE} symbols)")
     dev = torch.device("cuda", device_id)
@@ -594,7 +609,8 @@ def predict(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=N
     to_text = collapse_fn if units_path is None else (lambda text: text)
     loader = tud.DataLoader(test_dataset, batch_size=batch_size, shuffle=False, collate_fn=collate_custom)
     lm = CharNgramLM.load(lm_path) if lm_path is not None else None
-    decoder = CTCDecoder(alphabet, lm=lm, lm_alpha=lm_alpha, lm_beta=lm_beta, fast_lm=bool(lm_fast))
+    decoder = CTCDecoder(alphabet, lm=lm, lm_alpha=lm_alpha, lm_beta=lm_beta, fast_lm=bool(lm_fast), wide_search=wide)
+    list_text = to_text if wide else collapse_fn      # a wide list holds units: their concatenation is the text
     if mbr and mbr_unit == "word" and " " not in char2ind:
         raise ValueError("mbr_unit='word' needs an alphabet with the ' ' symbol")
     rescore_lm = CharNgramLM.load(rescore_lm_path) if rescore_lm_path is not None else None
@@ -643,17 +659,22 @@ def predict(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=N
                 for i in range(ntok.shape[1]):
                     target = "".join(ind2char[int(k)] for k in t_h[i][:int(tlen_h[i])])
                     for r in range(int(ncount[i])):
-                        text = collapse_fn("".join(ind2char[int(k)] for k in ntok[r, i, :nlen[r, i]]))
+                        text = list_text("".join(ind2char[int(k)] for k in ntok[r, i, :nlen[r, i]]))
                         refs.append(target); hyps.append(text); owner.append(i)
                         extra = "" if words is None else "\t{:.6f}\t{}\t{}".format(float(words[0][r, i]), int(words[1][r, i]),
                                                                                   int(words[2][r, i]))
                         nbest_lines.append("{}\t{}\t{:.6f}\t{}\t{}{}\n".format(n + i, r, float(nscore[r, i]),
                                                                             "" if total is None else "{:.6f}".format(float(total[r, i])),
                                                                             text, extra))
-                best = {}
-                for i, d in zip(owner, edit_dist_batch(refs, hyps, device=dev)):
-                    best[i] = min(d, best.get(i, d))
-                tot_oracle += sum(d / max(int(tlen_h[i]), 1) for i, d in best.items())
+                if wide:      # over units: the lists against the encoded references, on the device
+                    from .metrics import nbest_oracle
+                    od, _ = nbest_oracle(t.to(torch.int32).contiguous(), tmask.sum(1).to(torch.int32).contiguous(), nb)
+                    tot_oracle += sum(int(d) / max(int(tlen_h[i]), 1) for i, d in enumerate(od.cpu().tolist()))
+                else:
+                    best = {}
+                    for i, d in zip(owner, edit_dist_batch(refs, hyps, device=dev)):
+                        best[i] = min(d, best.get(i, d))
+                    tot_oracle += sum(d / max(int(tlen_h[i]), 1) for i, d in best.items())
             elif greedy:
                 tok, tl = greedy_decode(lp, in_len)
             else:
@@ -680,6 +701,8 @@ def predict(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=N
                 fo.writelines(mbr_lines)
             print("MBR ({}) CER: {:>4f} WER: {:>4f} MAP CER: {:>4f} WER: {:>4f} Oracle CER ({}-best): {:>4f}".format(
                 mbr_unit, cer, wer, map_cer / max(n, 1), map_wer / max(n, 1), nbest, tot_oracle / max(n, 1)))
+        elif wide:
+            print("CER: {:>4f} WER: {:>4f} Oracle unit error rate ({}-best): {:>4f}".format(cer, wer, nbest, tot_oracle / max(n, 1)))
         else:
             print("CER: {:>4f} WER: {:>4f} Oracle CER ({}-best): {:>4f}".format(cer, wer, nbest, tot_oracle / max(n, 1)))
     else:
