@@ -1273,6 +1273,34 @@ int pgasr_ctc_grad_from_lattice_wide(const float* log_probs, const int32_t* inpu
                                      int pg_coef_per_frame, float* grad_logits, void* workspace, size_t workspace_bytes,
                                      void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * A12-SCORE  Lattice-free CTC scorer (csrc/hyp_score.hip): the exact -log p(y | x) of every hypothesis of an N-best list, one fp64
+ * number per hypothesis.  The forward sweep of pgasr_ctc_hyp_lattice alone, with its rows kept in LDS: no workspace, nothing
+ * written but the result, so none of the lattice's limits (K <= 16, V <= 64) and none of its 2*K*B*T*roundup64(2*Lh+1)*4 bytes.
+ *   log_probs (T,B,V) fp32; hyp_tokens (N,B,hyp_stride) / hyp_len (N,B) int32 as pgasr_ctc_beam_search_nbest and _wide write
+ *   them; count (B) int32, clamped to [0,N], or NULL: every row; input_lengths (B) int32.  out_nll (N,B) fp64, every word written.
+ *   With len = max(hyp_len[n,b], 0) and Tb = clamp(input_lengths[b], 0, T), in this order:
+ *     n >= count[b]                                     -> +inf, no work
+ *     len > Lh or len > hyp_stride                      -> +inf, no work (nothing behind len is ever read)
+ *     a token outside [0,V) or equal to blank           -> +inf (every gather index is brought into the row first: garbage tokens
+ *                                                          never cause a read outside log_probs)
+ *     Tb == 0                                           -> 0 for len == 0, +inf otherwise
+ *     else  -log sum_alignments prod_t p_t              the alpha recurrence of A5 over the 2*len+1 states, ending in the sum of
+ *                                                          alpha[S-1] and alpha[S-2]; +inf when no alignment exists (len +
+ *                                                          repeats > Tb, symbols of probability 0).
+ *   Arithmetic: the linear domain, every alpha an fp64 fraction with an int32 binary exponent of its own (nothing underflows; each
+ *   frame rounds a few times at 2^-53), exp(log_prob) in fp64, one fp64 log at the end: within 1e-9 relative of the log-domain
+ *   recurrence in fp64 (tests/hyp_score_ref.py), where pgasr_ctc_hyp_lattice's fp32 nll is within 1e-5.  A likelihood below
+ *   2^-(2^30) (an nll above 7.4e8 nats) reads +inf.
+ *   Never NaN for inputs that are finite or -inf.  No atomics: two calls give the same bits.  Every frame loop is bounded by Tb,
+ *   every state loop by 2*len+1.  One launch, one workgroup per (utterance, hypothesis), no host synchronisation.
+ *   Checked before any HIP call: a NULL pointer (count excepted), T, B, N or hyp_stride < 1, Lh < 0, V < 1, blank outside [0,V) ->
+ *   PGASR_ERR_INVALID_ARG; then V > 1024, N > 128, 2*Lh+1 > 2048 (or N*B >= 2^31) -> PGASR_ERR_UNSUPPORTED.
+ * ---------------------------------------------------------------------------------------- */
+int pgasr_ctc_hyp_score(const float* log_probs, const int32_t* hyp_tokens, int hyp_stride, const int32_t* hyp_len,
+                        const int32_t* count /* NULL: every row */, const int32_t* input_lengths,
+                        int T, int B, int V, int N, int Lh, int blank, double* out_nll, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2,7 +2,8 @@
 blank=0) -> (tuple[int], float)`` and ``collapse_fn(str) -> str``, with the search itself running
 as a HIP kernel (csrc/beam.hip).  ``greedy_decode`` is the best-path decoder the reference lacks
 (SURVEY §8a A9).  Beyond the reference: ``nbest=N`` returns the first N entries of the final beam instead of the best one, and
-``CTCDecoder.rescore`` ranks such a list in a second pass (exact CTC likelihood and / or a stronger n-gram LM, csrc/nbest.hip; with
+``CTCDecoder.rescore`` ranks such a list in a second pass (exact CTC likelihood and / or a stronger n-gram LM, csrc/nbest.hip; the
+likelihood of lists of more than 16 rows or more than 64 symbols from the lattice-free scorer, csrc/hyp_score.hip; with
 ``word_lm=`` a word n-gram LM on top, csrc/word_lm.hip);
 ``CTCDecoder.mbr_decode`` returns the hypothesis of least expected edit distance under the list's posterior instead of the best-scored
 one (minimum-Bayes-risk decoding, csrc/mbr.hip)."""
@@ -143,7 +144,7 @@ class CTCDecoder:
         raise ValueError("a word LM needs word_delimiter: the alphabet has no ' ' symbol")
 
     def rescore(self, log_probs, lengths, nb, lm=_UNSET, lm_alpha=None, lm_beta=None, acoustic="ctc", am_weight=1.0, max_hyp_len=None,
-                blank=0, word_lm=None, word_lm_alpha=0.0, word_lm_beta=0.0, word_delimiter=None):
+                blank=0, word_lm=None, word_lm_alpha=0.0, word_lm_beta=0.0, word_delimiter=None, scorer=None):
         """Second pass over an N-best list ``nb`` (``hipops.CTCNBest`` of ``decode_batch(..., nbest=N)`` on the same log_probs
         (T,B,V) / lengths), N <= 128:  total = am_weight * am - lm_alpha * lm_logp - lm_beta * length, lower is better, with
         lm_logp the hypothesis' log-probability under ``lm`` (the decoder's own unless given; None: no LM term).
@@ -163,30 +164,64 @@ class CTCDecoder:
             ``word_delimiter``, default the alphabet's " " -- an alphabet without one raises).  Returns ``NBestRescoredWords``:
             the seven fields above with order / total / best_* from the combined total, then word_logp (N,B) float64, n_words and
             n_oov (N,B) int32.  No further host synchronisation.  word_lm_alpha = word_lm_beta = 0 leaves order and total as
-            they are without a word LM, bit for bit."""
+            they are without a word LM, bit for bit.
+        scorer: what computes am for acoustic="ctc".  "lattice": ``hipops.ctc_hyp_lattice`` (fp32 nll, both sweeps of every pair in
+            a workspace; at most 64 symbols and N <= 16, else ValueError).  "forward": ``hipops.ctc_hyp_score`` (csrc/hyp_score.hip:
+            the forward sweep alone, fp64, no workspace; up to 1024 symbols, N <= 128), am = +inf where skipped.  None (default):
+            the lattice within its limits -- the call made before the forward scorer existed, the same bits in every field --, the
+            forward scorer beyond them.
+        Lists over more than 64 symbols (``CTCDecoder(wide_search=True)``): ``lm`` and ``word_lm`` must be None (ValueError naming
+            the option: a subword unit may span a space and the character tables hold 64 symbols); total = am_weight * am - lm_beta *
+            length and its rank come from ``hipops.nbest_combine_rank`` -- the formula above without an LM, with the same roundings --
+            and lm_logp is zeros."""
         if acoustic not in ("ctc", "first_pass"):
             raise ValueError(f"acoustic must be 'ctc' or 'first_pass' (got {acoustic!r})")
+        if scorer not in (None, "lattice", "forward"):
+            raise ValueError(f"scorer must be None, 'lattice' or 'forward' (got {scorer!r})")
+        T, B, V = log_probs.shape
+        N = nb.tokens.shape[0]
+        args = self._lm_args(lm, lm_alpha, lm_beta)
+        wide = V > hipops.MAX_VOCAB_NARROW
+        if wide:
+            for name, given in (("lm", args["lm"] is not None), ("word_lm", word_lm is not None)):
+                if given:
+                    raise ValueError(f"{name}: not over a list of {V} > {hipops.MAX_VOCAB_NARROW} symbols -- a subword unit may span a "
+                                     f"space and the n-gram tables hold characters; rescore such a list with {name}=None")
+        in_lattice_limits = not wide and N <= hipops.MAX_SAMPLES
+        if scorer == "lattice" and not in_lattice_limits:
+            raise ValueError(f"scorer='lattice' takes at most {hipops.MAX_VOCAB_NARROW} symbols and {hipops.MAX_SAMPLES} hypotheses per "
+                             f"utterance (got {V} and {N}): take scorer='forward'")
+        forward = scorer == "forward" or (scorer is None and not in_lattice_limits)
         if word_lm is not None:
             delim = self._word_delimiter(word_delimiter)
             if nb.tokens.shape[2] > hipops.WORD_LM_MAX_STRIDE:
                 raise ValueError(f"a word LM takes hypotheses of at most {hipops.WORD_LM_MAX_STRIDE} tokens (got rows of "
                                  f"{nb.tokens.shape[2]})")
-        T, B, V = log_probs.shape
-        N = nb.tokens.shape[0]
-        args = self._lm_args(lm, lm_alpha, lm_beta)
         if acoustic == "ctc":
             if lengths is None:
                 lengths = torch.full((B,), T, dtype=torch.int32, device=log_probs.device)
             Lh = hipops.hyp_len_cap(T, int(nb.lengths.max().item()) if max_hyp_len is None else max_hyp_len)
             skipped = nb.lengths > Lh
-            nll, _ = hipops.ctc_hyp_lattice(log_probs.float().contiguous(), nb.tokens, nb.lengths, lengths.to(torch.int32).contiguous(),
-                                            Lh, blank=int(blank))
-            am = torch.where(skipped, torch.full_like(nb.score, float("inf")), nll.double())
+            if forward:
+                am = hipops.ctc_hyp_score(log_probs.float().contiguous(), nb.tokens, nb.lengths, lengths.to(torch.int32).contiguous(),
+                                          Lh, count=nb.count, blank=int(blank))
+            else:
+                nll, _ = hipops.ctc_hyp_lattice(log_probs.float().contiguous(), nb.tokens, nb.lengths,
+                                                lengths.to(torch.int32).contiguous(), Lh, blank=int(blank))
+                am = torch.where(skipped, torch.full_like(nb.score, float("inf")), nll.double())
         else:
             skipped = torch.zeros_like(nb.lengths, dtype=torch.bool)
             am = nb.score
-        order, total, lm_logp = hipops.nbest_rescore(nb.tokens, nb.lengths, nb.count, am.contiguous(), V, blank=int(blank), lm=args["lm"],
-                                                     am_weight=float(am_weight), lm_alpha=args["lm_alpha"], lm_beta=args["lm_beta"])
+        if wide:
+            # pgasr_nbest_rescore's total without an LM, ((am_weight * am) + -0) + -(lm_beta * length), each rounded once
+            order, total = hipops.nbest_combine_rank((am * float(am_weight)).contiguous(), torch.zeros_like(am),
+                                                     nb.lengths.clamp(0, nb.tokens.shape[2]), nb.count, word_alpha=0.0,
+                                                     word_beta=args["lm_beta"])
+            lm_logp = torch.zeros_like(am)
+        else:
+            order, total, lm_logp = hipops.nbest_rescore(nb.tokens, nb.lengths, nb.count, am.contiguous(), V, blank=int(blank),
+                                                         lm=args["lm"], am_weight=float(am_weight), lm_alpha=args["lm_alpha"],
+                                                         lm_beta=args["lm_beta"])
         if word_lm is not None:
             word_logp, n_words, n_oov = hipops.nbest_word_lm_score(nb.tokens, nb.lengths, nb.count, word_lm, delim)
             order, total = hipops.nbest_combine_rank(total, word_logp, n_words, nb.count, word_alpha=float(word_lm_alpha),
@@ -203,13 +238,15 @@ class CTCDecoder:
         (N,B) float64 with lower better (``rescore(...).total``, ``nb.score``, ...), ``vocab`` the number of symbols (default: the
         alphabet's).  posterior = softmax(-posterior_scale * score) over the list's valid rows; the row of least expected edit
         distance to the others under it is returned (the first among equals).
-        risk_unit: "char" (default: ``hipops.nbest_pair_distance`` on the bit-vector kernel) or "word" (words split at the token
-            ``word_delimiter``, the alphabet's " ", as str.split(" ") cuts them).
+        risk_unit: "char" (default: the list's own units -- characters, or the subword units of a wide alphabet --,
+            ``hipops.nbest_pair_distance`` on the bit-vector kernel for at most 64 symbols and on the wave-per-pair kernels above) or
+            "word" (words split at the token ``word_delimiter``, the alphabet's " ", as str.split(" ") cuts them; at most 64
+            symbols, ValueError above: a subword unit may span a space).
         max_hyp_len: None reads the longest hypothesis from the device for risk_unit="char" (ONE host synchronisation); a number
             avoids it, and a hypothesis longer than that takes no part (risk +inf, posterior 0).
         Returns ``MBRDecoded``: tokens (B,T) / lengths (B) int32 the chosen row of every utterance, best (B) int32 its rank in the
         list, risk (N,B) / posterior (N,B) float64, dist (B,N,N) int32 (-1 where a row takes no part), nbest = ``nb``.
-        risk[best[b], b] is the expected number of character (word) errors of the returned hypothesis: a confidence."""
+        risk[best[b], b] is the expected number of unit (word) errors of the returned hypothesis: a confidence."""
         if risk_unit not in ("char", "word"):
             raise ValueError(f"risk_unit must be 'char' or 'word' (got {risk_unit!r})")
         V = len(self.alphabet) if vocab is None else int(vocab)

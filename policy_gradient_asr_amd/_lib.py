@@ -51,6 +51,8 @@ SIGNATURES = {
     "pgasr_ctc_hyp_workspace_bytes": (C.c_size_t, [C.c_int] * 5),
     "pgasr_ctc_hyp_lattice": (C.c_int, [c_f32p, c_i32p, C.c_int, c_i32p, c_i32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                         c_f32p, c_ptr, C.c_size_t, c_ptr]),
+    "pgasr_ctc_hyp_score": (C.c_int, [c_f32p, c_i32p, C.c_int, c_i32p, c_i32p, c_i32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                      C.c_int, c_ptr, c_ptr]),
     "pgasr_ctc_grad_from_lattices_seq": (C.c_int, [c_f32p, c_i32p, c_i32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_f32p,
                                                    C.c_int, c_f32p, c_i32p, c_i32p, C.c_int, c_f32p, c_ptr, C.c_size_t,
                                                    c_ptr, C.c_size_t, c_ptr]),

@@ -407,6 +407,30 @@ def ctc_hyp_lattice(log_probs, hyp_tokens, hyp_len, input_lengths, Lh, blank=0):
     return hyp_nll, (ws, K, Lh)
 
 
+def ctc_hyp_score(log_probs, hyp_tokens, hyp_len, input_lengths, Lh, count=None, blank=0):
+    """The exact CTC -log p(y|x) of every hypothesis of an N-best list, forward sweep only (pgasr_ctc_hyp_score; include/pgasr_hip.h,
+    A12-SCORE): log_probs (T,B,V) fp32 with V <= 1024, hyp_tokens (N,B,stride) / hyp_len (N,B) int32 as ``ctc_beam_search_nbest`` /
+    ``ctc_beam_search_wide`` return them, N <= 128, count (B) int32 or None (every row).  Returns nll (N,B) float64: +inf for a row
+    beyond count, a hypothesis longer than Lh (or than stride), a token that is the blank or outside [0,V), and where no alignment
+    exists.  No workspace, one launch, no host synchronisation; fp64 throughout (``ctc_hyp_lattice``'s nll is fp32)."""
+    lib = _lib.load()
+    _req(log_probs, torch.float32, "log_probs"); _req(hyp_tokens, torch.int32, "hyp_tokens")
+    _req(hyp_len, torch.int32, "hyp_len"); _req(input_lengths, torch.int32, "input_lengths"); _req(count, torch.int32, "count")
+    if log_probs.dim() != 3:
+        raise _lib.PgasrError("ctc_hyp_score wants log_probs (T,B,V)")
+    T, B, V = log_probs.shape
+    if hyp_tokens.dim() != 3 or hyp_tokens.shape[1] != B or tuple(hyp_len.shape) != (hyp_tokens.shape[0], B) \
+            or input_lengths.numel() != B or (count is not None and count.numel() != B):
+        raise _lib.PgasrError(f"ctc_hyp_score wants hyp_tokens (N,{B},stride), hyp_len (N,{B}), input_lengths ({B}) and count ({B})")
+    N, stride = hyp_tokens.shape[0], hyp_tokens.shape[2]
+    nll = torch.empty(N, B, dtype=torch.float64, device=log_probs.device)
+    with _timed("ctc_hyp_score_kernel"):
+        st = lib.pgasr_ctc_hyp_score(_p(log_probs), _p(hyp_tokens), stride, _p(hyp_len), _p(count), _p(input_lengths), T, B, V, N,
+                                     int(Lh), int(blank), _p(nll), _stream())
+    _lib.check(st, "pgasr_ctc_hyp_score")
+    return nll
+
+
 def ctc_grad_from_lattices_seq(log_probs, input_lengths, target_lengths, handle, hyp_handle, utt_scale, pg_coef, pg_paths, hyp_len,
                                ent_scale=None, ref_log_probs=None, kl_scale=None):
     """One gradient pass over the target lattice (``ctc_lattice``'s handle) and the K*B hypothesis lattices (``ctc_hyp_lattice``'s):
@@ -1759,11 +1783,13 @@ def nbest_pair_distance(tokens, lengths, count, vocab, max_hyp_len=None, unit="c
     returns them, ``vocab`` the number of symbols.  Returns dist (B,N,N) int32: dist[b,n,m] = dist[b,m,n] = the Levenshtein distance of
     hypotheses n and m of utterance b, 0 on the diagonal, and -1 wherever n or m lies beyond count[b] or is longer than the cap (its own
     diagonal included).  N <= 128.
-    unit="char" (default): characters, by pgasr_nbest_pair_dist (Myers' bit-vector algorithm, one lane per pair, one launch; vocab <= 64);
-        a symbol outside [0, vocab) matches nothing, not even itself.  Lists whose cap exceeds 1024 take the composed path: the
-        unordered pairs expanded in bounded chunks through ``edit_distance`` (one wave per pair), the same result -- and so do
-        at most PAIR_DIST_COMPOSED_MAX_PAIRS pairs with a cap from PAIR_DIST_COMPOSED_MIN_LEN, where that path measured faster.
-    unit="word": words split at the token ``delimiter`` as str.split(" ") cuts them (``word_edit_distance`` on the composed path).
+    unit="char" (default): the list's own units -- characters, or the subword units of a wide alphabet --, by pgasr_nbest_pair_dist
+        (Myers' bit-vector algorithm, one lane per pair, one launch; vocab <= 64); a symbol outside [0, vocab) matches nothing, not
+        even itself.  Lists whose cap exceeds 1024 take the composed path: the unordered pairs expanded in bounded chunks through
+        ``edit_distance`` (one wave per pair), the same result -- and so do at most PAIR_DIST_COMPOSED_MAX_PAIRS pairs with a cap
+        from PAIR_DIST_COMPOSED_MIN_LEN, where that path measured faster, and every list over more than 64 symbols (up to 1024).
+    unit="word": words split at the token ``delimiter`` as str.split(" ") cuts them (``word_edit_distance`` on the composed path);
+        vocab <= 64 only (ValueError above: a subword unit may span a space).
     max_hyp_len: the cap.  None: the longest hypothesis of the lists, read from the device (ONE host synchronisation, as in
         ``CTCDecoder.rescore``; unit="word" needs none) -- nothing is over it.  A number avoids the synchronisation."""
     _lib.load()
@@ -1774,6 +1800,10 @@ def nbest_pair_distance(tokens, lengths, count, vocab, max_hyp_len=None, unit="c
         raise ValueError(f"unit must be 'char' or 'word' (got {unit!r})")
     if unit == "word" and (delimiter is None or int(delimiter) < 0):
         raise ValueError("unit='word' needs delimiter, the token id of the alphabet's ' ' symbol")
+    wide = int(vocab) > MAX_VOCAB_NARROW
+    if wide and unit == "word":
+        raise ValueError(f"unit='word': not over {int(vocab)} > {MAX_VOCAB_NARROW} symbols -- a subword unit may span a space, so words "
+                         f"cannot be split at a delimiter token; take unit='char' (the units are the symbols)")
     N, B, stride = tokens.shape
     if N < 1 or N > NBEST_RESCORE_MAX:
         raise _lib.PgasrError(f"nbest_pair_distance takes 1 <= N <= {NBEST_RESCORE_MAX} hypotheses per utterance (got {N})")
@@ -1787,7 +1817,7 @@ def nbest_pair_distance(tokens, lengths, count, vocab, max_hyp_len=None, unit="c
         rows = torch.arange(N, device=tokens.device).view(N, 1) < count.view(1, B)
         cap = int((lengths.clamp(0, stride) * rows).max().item())
     few_and_long = B * N * (N - 1) // 2 <= PAIR_DIST_COMPOSED_MAX_PAIRS and cap >= PAIR_DIST_COMPOSED_MIN_LEN
-    if unit == "word" or cap > PAIR_DIST_MAX_LEN or few_and_long:
+    if unit == "word" or wide or cap > PAIR_DIST_MAX_LEN or few_and_long:
         with _timed("nbest_pair_dist_composed"):
             return _pair_distance_composed(tokens, lengths, count, vocab, cap, unit, delimiter)
     return _pair_distance_kernel(tokens, lengths, count, vocab, cap)

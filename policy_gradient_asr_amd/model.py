@@ -505,7 +505,7 @@ def predict(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=N
             test_dataset=None, n_feats=120, beam_size=5, features="mfcc", lm_path=None, lm_alpha=0.0, lm_beta=0.0,
             nbest=1, rescore_lm_path=None, rescore_alpha=0.0, rescore_beta=0.0, lm_fast=False, target_rate=None,
             mbr=False, mbr_unit="char", mbr_scale=1.0, rescore_word_lm_path=None, rescore_word_alpha=0.0, rescore_word_beta=0.0,
-            error_report=False, units_path=None, wide_beam=False):
+            error_report=False, units_path=None, wide_beam=False, wide_second_pass=False):
     """model.py:277-339: load model_best.pth, forward, beam=5 prefix search (device side, batched),
     collapse_fn, CER/WER, predicted.txt.  Frames are cut by the FEATURE mask (the reference cuts the
     time axis by the target mask, model.py:322 -- a listed defect).  Returns (CER, WER).
@@ -552,8 +552,14 @@ def predict(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=N
     with beam_size > 0 by the exact wide prefix beam search (``CTCDecoder(wide_search=True)``, csrc/beam_wide.hip).  nbest=N then
     writes ``nbest.tsv`` with the first-pass scores, and the oracle error rate over units (the best hypothesis of every list against
     the encoded reference, ``metrics.nbest_oracle``) is printed beside CER / WER.  The wide search has no LM fusion and its lists no
-    second pass yet: lm_path, the rescore_* options, mbr and error_report raise for such an alphabet.  Alphabets of at most 64 symbols
-    are not affected by the flag."""
+    second pass by default: lm_path, the rescore_* options, mbr and error_report raise for such an alphabet.  Alphabets of at most 64
+    symbols are not affected by the flag.
+    wide_second_pass: False (default: everything above, nothing else) or True, with wide_beam=True and nbest >= 2: every wide list is
+    re-ranked by the exact CTC likelihood of its hypotheses (``CTCDecoder.rescore`` on the forward scorer, csrc/hyp_score.hip), which
+    fills the total column of ``nbest.tsv``; the row of lowest total is the one written to predicted.txt and scored.  mbr=True is
+    then allowed with mbr_unit="char" -- the risk is counted in units -- and writes ``mbr.tsv``; mbr_unit="word" raises (a unit may
+    span a space), and so do lm_path, rescore_lm_path, rescore_word_lm_path and error_report, which stay refused for such an alphabet.
+    Alphabets of at most 64 symbols are not affected by the flag."""
     import os
     import functools
     import torch.utils.data as tud
@@ -587,7 +593,20 @@ def predict(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=N
         from .units import SubwordUnits
         unit_args = {"units": SubwordUnits.load(units_path)}
     wide = len(alphabet) > hipops.MAX_VOCAB_NARROW and not greedy and bool(wide_beam)
-    if wide:
+    second = wide and bool(wide_second_pass)
+    if second:
+        if nbest < 2:
+            raise ValueError("wide_second_pass re-ranks a list: give nbest >= 2 with it")
+        for name, given in (("lm_path", lm_path is not None), ("rescore_lm_path", rescore_lm_path is not None),
+                            ("rescore_word_lm_path", rescore_word_lm_path is not None), ("error_report", bool(error_report))):
+            if given:
+                raise ValueError(f"{name}: not with the wide beam search ({len(alphabet)} > {hipops.MAX_VOCAB_NARROW} symbols): its "
+                                 f"second pass is the exact CTC likelihood and minimum-Bayes-risk decoding over units, without "
+                                 f"language models or an error report")
+        if mbr and mbr_unit == "word":
+            raise ValueError(f"mbr_unit='word': not over {len(alphabet)} > {hipops.MAX_VOCAB_NARROW} symbols -- a subword unit may span "
+                             f"a space; take mbr_unit='char', which counts units")
+    elif wide:
         for name, given in (("lm_path", lm_path is not None), ("rescore_lm_path", rescore_lm_path is not None),
                             ("rescore_word_lm_path", rescore_word_lm_path is not None), ("mbr", bool(mbr)),
                             ("error_report", bool(error_report))):
@@ -636,7 +655,7 @@ def predict(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=N
             if nbest > 1:
                 nb = decoder.decode_batch(lp, in_len, beam_size=beam_size, nbest=nbest)
                 tok, tl, total, words = nb.tokens[0], nb.lengths[0], None, None
-                if rescore_lm is not None or word_lm is not None:
+                if rescore_lm is not None or word_lm is not None or second:
                     rs = decoder.rescore(lp, in_len, nb, lm=rescore_lm, lm_alpha=rescore_alpha if rescore_lm is not None else 0.0,
                                          lm_beta=rescore_beta if rescore_lm is not None else 0.0, **word_args)
                     tok, tl, total = rs.best_tokens, rs.best_len, rs.total.cpu()
@@ -687,7 +706,7 @@ def predict(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=N
                 cer, wer = evaluate(target, seq)
                 tot_cer += cer; tot_wer += wer; n += 1
                 if mbr:
-                    cer, wer = evaluate(target, collapse_fn("".join(ind2char[int(k)] for k in map_tok[i, :map_tl[i]])))
+                    cer, wer = evaluate(target, list_text("".join(ind2char[int(k)] for k in map_tok[i, :map_tl[i]])))
                     map_cer += cer; map_wer += wer
             if report is not None:
                 report.add(targets[-tok.shape[0]:], predicted[-tok.shape[0]:])
@@ -699,8 +718,9 @@ def predict(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=N
         if mbr:
             with open(os.path.join(model_path, "mbr.tsv"), "w") as fo:
                 fo.writelines(mbr_lines)
-            print("MBR ({}) CER: {:>4f} WER: {:>4f} MAP CER: {:>4f} WER: {:>4f} Oracle CER ({}-best): {:>4f}".format(
-                mbr_unit, cer, wer, map_cer / max(n, 1), map_wer / max(n, 1), nbest, tot_oracle / max(n, 1)))
+            print("MBR ({}) CER: {:>4f} WER: {:>4f} MAP CER: {:>4f} WER: {:>4f} Oracle {} ({}-best): {:>4f}".format(
+                "unit" if wide else mbr_unit, cer, wer, map_cer / max(n, 1), map_wer / max(n, 1),
+                "unit error rate" if wide else "CER", nbest, tot_oracle / max(n, 1)))
         elif wide:
             print("CER: {:>4f} WER: {:>4f} Oracle unit error rate ({}-best): {:>4f}".format(cer, wer, nbest, tot_oracle / max(n, 1)))
         else:
