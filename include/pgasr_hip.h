@@ -851,7 +851,8 @@ int pgasr_ctc_beam_search_nbest(const void* log_probs, int is_f64, long long str
 /* ------------------------------------------------------------------------------------------
  * A7-WIDE  The same search over rows of up to 1024 symbols (subword units): the reference's CTCDecoder.decode (CTCdecoder.py:41-116)
  * over all V symbols, no heuristic symbol pruning, returning the first `nbest` entries of the final beam in the layout and with the
- * conventions of pgasr_ctc_beam_search_nbest (nbest = 1: the 1-best search).  A kernel of its own (csrc/beam_wide.hip): one
+ * conventions of pgasr_ctc_beam_search_nbest (nbest = 1: the 1-best search).  A kernel of its own (csrc/beam_wide.hip; the score
+ * forms, the rank key, the trie and the result tail are the A7 workgroup kernel's, both from csrc/beam_core.h): one
  * workgroup of 256 threads per utterance, a beam x V bitmap for the merge test, the hash-consed trie with 10-bit symbols, and a
  * top-`beam` SELECTION in place of the sort of all beam * V candidates -- a threshold (the beam-th largest of 2 * beam candidates that
  * certainly exist), a list of the candidates at or above it (2048 items), a bitonic sort of that list; a frame whose list overflows

@@ -13,79 +13,22 @@
 //     is symbol-major / rank-minor (:68,:74).
 // Scores are fp64 (log-sum-exp exactly as CTCdecoder.py:31-39: max, sum of exps in argument order,
 // log); this is integer/latency work, not MFMA work.
+// The log-sum-exp forms, the rank key and its sort, the trie (workspace layout, find-or-create) and the N-best result tail are shared
+// with the wide search (beam_wide.hip) and live in beam_core.h; the single-wave kernel further down (namespace sb) uses none of them.
 #include "common.h"
+#include "beam_core.h"
 #include <cmath>
 #include <type_traits>
 
 namespace {
 
+using namespace beam_core;
+
 constexpr int BEAM_KMAX = 128;
 constexpr int BEAM_VMAX = 64;
 constexpr int BEAM_THREADS = 256;
-
-struct BeamWs {
-    unsigned long long* table;   // [B][H] open-addressing (key+1)<<32 | node id ; 0 = empty
-    unsigned* nodes;             // [B][NN] packed (parent << 8 | sym); node 0 = root
-    int H, NN;
-};
-
-__host__ __device__ inline size_t beam_ws_layout(int T, int B, int beam, BeamWs* ws, char* base) {
-    const long long nn = (long long)T * beam + 1;
-    int H = 1024;
-    while ((long long)H < 2 * nn) H <<= 1;
-    size_t off = 0;
-    const size_t t_off = off; off += (size_t)B * H * sizeof(unsigned long long);
-    off = (off + 255) / 256 * 256;
-    const size_t n_off = off; off += (size_t)B * nn * sizeof(unsigned);
-    off = (off + 255) / 256 * 256;
-    if (ws) {
-        ws->table = (unsigned long long*)(base + t_off);
-        ws->nodes = (unsigned*)(base + n_off);
-        ws->H = H; ws->NN = (int)nn;
-    }
-    return off;
-}
-
-// CTCdecoder.py:31-39 with 2 or 3 arguments (argument order preserved)
-__device__ __forceinline__ double lse2(double a, double b) {
-    const double m = fmax(a, b);
-    if (m == -INFINITY) return -INFINITY;
-    return m + log(exp(a - m) + exp(b - m));
-}
-__device__ __forceinline__ double lse3(double a, double b, double c) {
-    const double m = fmax(fmax(a, b), c);
-    if (m == -INFINITY) return -INFINITY;
-    return m + log((exp(a - m) + exp(b - m)) + exp(c - m));
-}
-
-// Fast variants (fp32 device log-probs, training-time rewards): fp64 carries, fp32 exp/log on the
-// differences to the maximum -- the software fp64 transcendentals dominate the exact path (28 ms
-// vs ~1/4 of that for T=1000, beam 16, 32 utterances).  Scores differ from the exact path by
-// ~1e-7 relative, so only exact score ties could rank differently.
-template <bool FAST> __device__ __forceinline__ double lse2x(double a, double b) {
-    if (!FAST) return lse2(a, b);
-    const double m = fmax(a, b);
-    if (m == -INFINITY) return -INFINITY;
-    return m + (double)__logf(__expf((float)(a - m)) + __expf((float)(b - m)));
-}
-template <bool FAST> __device__ __forceinline__ double lse3x(double a, double b, double c) {
-    if (!FAST) return lse3(a, b, c);
-    const double m = fmax(fmax(a, b), c);
-    if (m == -INFINITY) return -INFINITY;
-    return m + (double)__logf((__expf((float)(a - m)) + __expf((float)(b - m))) + __expf((float)(c - m)));
-}
-
-// order-preserving map double -> u64 (ascending)
-__device__ __forceinline__ unsigned long long ordered_key(double x) {
-    const unsigned long long b = (unsigned long long)__double_as_longlong(x);
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-
-struct SortItem { unsigned long long key; unsigned time; unsigned cand; };   // key = ~ordered(score): ascending sort = score descending
-
-__device__ __forceinline__ bool item_less(const SortItem& a, const SortItem& b) {
-    return a.key < b.key || (a.key == b.key && a.time < b.time);
-}
+constexpr int BEAM_SYM_BITS = 8;                      // a trie node is parent << 8 | symbol
+using BeamWs = TrieWs<BEAM_SYM_BITS>;
 
 // Language-model fusion (LM = true; Hannun/Maas arXiv:1408.2873, the reference's "*NB* this would be a good place to include an LM
 // score" at the extension step): a dense fp32 table of natural-log probabilities, table[c_1 .. c_{n-1}, s] = ln p(s | c_1 .. c_{n-1}),
@@ -151,7 +94,6 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_search_kernel(
 
     unsigned long long* table = ws.table + (size_t)b * ws.H;
     unsigned* nodes = ws.nodes + (size_t)b * ws.NN;
-    const unsigned hmask = (unsigned)ws.H - 1u;
 
     if (tid == 0) {
         s_nb = 1; s_nodes = 1;
@@ -257,29 +199,7 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_search_kernel(
             items[c] = it;
         }
         __syncthreads();
-        // ---- bitonic sort of P items ----
-        // Element i is handled by thread i % 256, so all elements of a 64-aligned group belong to one
-        // wave: a pass with partner distance j2 < 64 exchanges only inside a wave (LDS accesses of one
-        // wave are ordered) and needs a workgroup barrier only next to a cross-wave pass.
-        {
-            bool prev_cross = false;   // the candidate loop above ended with __syncthreads()
-            for (int k2 = 2; k2 <= P; k2 <<= 1) {
-                for (int j2 = k2 >> 1; j2 > 0; j2 >>= 1) {
-                    const bool cross = j2 >= 64;
-                    if (cross || prev_cross) __syncthreads();
-                    for (int i = tid; i < P; i += BEAM_THREADS) {
-                        const int l = i ^ j2;
-                        if (l > i) {
-                            const SortItem x = items[i], y = items[l];
-                            const bool up = ((i & k2) == 0);
-                            if (item_less(y, x) == up) { items[i] = y; items[l] = x; }
-                        }
-                    }
-                    prev_cross = cross;
-                }
-            }
-            __syncthreads();
-        }
+        bitonic_sort<BEAM_THREADS>(items, P, tid);
         // ---- new beam ----
         const int nxt = cur ^ 1;
         int* nid = id + nxt * K; int* nlast = last + nxt * K; int* npar = par + nxt * K;
@@ -297,21 +217,8 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_search_kernel(
                 if (s == blank) { nid[tid] = cid[j]; nlast[tid] = clast[j]; npar[tid] = cpar[j]; }
                 else {
                     // canonical node for (id[j], s): look up, else create
-                    const unsigned keyv = ((unsigned)cid[j] << 8) | (unsigned)s;
-                    unsigned h = (keyv * 2654435761u) & hmask;
-                    int node = -1;
-                    while (true) {
-                        const unsigned long long slot = table[h];
-                        if (slot == 0ull) {
-                            if (node < 0) { node = atomicAdd(&s_nodes, 1); nodes[node] = keyv; }
-                            const unsigned long long want = ((unsigned long long)(keyv + 1u) << 32) | (unsigned)node;
-                            const unsigned long long old = atomicCAS(&table[h], 0ull, want);
-                            if (old == 0ull) break;
-                            if ((unsigned)(old >> 32) == keyv + 1u) { node = (int)(unsigned)old; break; }   // cannot happen within a frame
-                        } else if ((unsigned)(slot >> 32) == keyv + 1u) { node = (int)(unsigned)slot; break; }
-                        h = (h + 1u) & hmask;
-                    }
-                    nid[tid] = node; nlast[tid] = s; npar[tid] = cid[j];
+                    nid[tid] = trie_find_or_create<BEAM_SYM_BITS>(table, nodes, ws.H, ws.NN, &s_nodes, cid[j], s);
+                    nlast[tid] = s; npar[tid] = cid[j];
                 }
             }
         }
@@ -324,51 +231,20 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_search_kernel(
         cur = nxt;
     }
     if constexpr (NBEST) {
-        // ---- N-best result: the final beam is ranked (the last frame's sort IS sorted(...)[:N], CTCdecoder.py:110-113), so row r is entry r ----
-        // Thread r walks the ancestors of entry r: the chains are independent and run side by side, one chain's latency in all.  A walk ends at
-        // the root, after Tb steps (a prefix has at most one symbol per frame) or at an id outside the node store, whatever nodes[] holds.
-        // out_tokens (nbest, B, tok_stride), out_len / out_score (nbest, B): the (K, B, stride) layout of pgasr_ctc_hyp_lattice.
-        const int B = (int)gridDim.x, N = lm.nbest, S = lm.tok_stride;
-        const int count = N < s_nb ? N : s_nb;
-        int* hlen = pidx;                          // [K], free after the frame loop: the length each row was written with
-        if (tid < N) {                             // N <= K <= BEAM_KMAX < BEAM_THREADS
-            int n = 0;
-            double sc = INFINITY;                  // rows beyond count: length 0, score +inf, tokens zero
-            if (tid < count) {
-                int32_t* o = out_tokens + ((size_t)tid * B + b) * S;
-                const int head = id[cur * K + tid];
-                for (int v = head; v > 0 && v < ws.NN && n < Tb; v = (int)(nodes[v] >> 8)) ++n;
-                int v = head;
-                for (int k = n - 1; k >= 0; --k) { const unsigned w = nodes[v]; o[k] = (int32_t)(w & 0xFFu); v = (int)(w >> 8); }
-                if (collapse) {      // collapse_fn on this hypothesis alone: rows that become equal strings stay separate rows
-                    int w = 0;
-                    for (int i = 0; i < n; ++i) if (i == 0 || o[i] != o[i - 1]) { const int32_t x = o[i]; o[w++] = x; }
-                    n = w;
-                }
-                sc = -lse2x<FAST>(pb[cur * K + tid], pnb[cur * K + tid]);
-            }
-            hlen[tid] = n;
-            out_len[(size_t)tid * B + b] = n;
-            out_score[(size_t)tid * B + b] = sc;
-        }
-        if (tid == 0) lm.out_count[b] = count;
-        __threadfence_block();
-        __syncthreads();
-        for (int r = 0; r < N; ++r) {              // zero tails (and whole rows beyond count), coalesced
-            int32_t* o = out_tokens + ((size_t)r * B + b) * S;
-            for (int i = hlen[r] + tid; i < S; i += BEAM_THREADS) o[i] = 0;
-        }
+        // ---- N-best result: row r is entry r of the final, ranked beam; pidx is free after the frame loop ----
+        nbest_tail<BEAM_SYM_BITS, BEAM_THREADS, FAST>(nodes, ws.NN, Tb, b, tid, lm.nbest, lm.tok_stride, collapse, s_nb, id + cur * K, pb + cur * K,
+                                                      pnb + cur * K, pidx, out_tokens, out_len, out_score, lm.out_count);
         return;
     }
     // ---- result: walk the best entry's ancestors ----
     if (tid == 0) {
         const int best = id[cur * K];
         int n = 0;
-        for (int v = best; v > 0; v = (int)(nodes[v] >> 8)) ++n;
+        for (int v = best; v > 0; v = (int)(nodes[v] >> BEAM_SYM_BITS)) ++n;
         out_len[b] = n;
         int32_t* o = out_tokens + (size_t)b * T;
         int k = n - 1;
-        for (int v = best; v > 0; v = (int)(nodes[v] >> 8)) o[k--] = (int32_t)(nodes[v] & 0xFFu);
+        for (int v = best; v > 0; v = (int)(nodes[v] >> BEAM_SYM_BITS)) o[k--] = (int32_t)(nodes[v] & BeamWs::SYM_MASK);
         if (collapse) {      // collapse_fn (CTCdecoder.py:119-131): adjacent duplicates removed
             int w = 0;
             for (int i = 0; i < n; ++i) if (i == 0 || o[i] != o[i - 1]) { const int32_t x = o[i]; o[w++] = x; }
@@ -981,7 +857,7 @@ extern "C" int pgasr_diag_beam_counters(unsigned long long* out, int reset) {   
 
 extern "C" size_t pgasr_beam_workspace_bytes(int T, int B, int V, int beam) {
     if (T <= 0 || B <= 0 || V <= 0 || beam <= 0) return 0;
-    return beam_ws_layout(T, B, beam, nullptr, nullptr);
+    return trie_ws_layout<BEAM_SYM_BITS>(T, B, beam, nullptr, nullptr);
 }
 
 // Which kernel flags bit 4 picks (include/pgasr_hip.h, A7-LM): 1 = the single-wave kernel's LM instantiations.  Host only, no HIP call.
@@ -1016,17 +892,13 @@ int beam_search_impl(const void* log_probs, int is_f64, long long stride_t, long
                      int32_t* out_tokens, int32_t* out_len, double* out_score,
                      void* workspace, size_t workspace_bytes, void* stream,
                      const float* lm_table, int lm_order, double lm_alpha, double lm_beta) {
-    if (!log_probs || !out_tokens || !out_len || !out_score) return PGASR_ERR_INVALID_ARG;
-    if (T <= 0 || B <= 0 || V <= 0 || beam <= 0 || blank < 0 || blank >= V) return PGASR_ERR_INVALID_ARG;
-    if (V > BEAM_VMAX || beam > BEAM_KMAX) return PGASR_ERR_UNSUPPORTED;
-    // the language model's arguments, before any HIP call
+    // the shared checks with the language model's arguments in their place, before any HIP call
     BeamLm<true> lm{};
-    if (const int st = beam_lm_args(V, blank, lm_table, lm_order, lm_alpha, lm_beta, &lm)) return st;
-    const bool with_lm = lm_order > 0;
     BeamWs ws;
-    const size_t need = beam_ws_layout(T, B, beam, &ws, (char*)workspace);
-    if (!workspace || workspace_bytes < need) return PGASR_ERR_WORKSPACE;
-    if ((long long)T * beam + 1 >= (1ll << 24)) return PGASR_ERR_UNSUPPORTED;
+    if (const int st = beam_check_args(log_probs, out_tokens, out_len, out_score, T, B, V, beam, blank, BEAM_VMAX, BEAM_KMAX,
+                                       [&] { return beam_lm_args(V, blank, lm_table, lm_order, lm_alpha, lm_beta, &lm); },
+                                       workspace, workspace_bytes, &ws)) return st;
+    const bool with_lm = lm_order > 0;
     hipStream_t st = (hipStream_t)stream;
 #ifdef PGASR_BEAM_DIAG
     const int collapse = (flags & 1) | ((flags & 4) ? 2 : 0);
@@ -1101,18 +973,15 @@ extern "C" int pgasr_ctc_beam_search_nbest(const void* log_probs, int is_f64, lo
                                            int nbest, int32_t* out_tokens, int tok_stride, int32_t* out_len, double* out_score,
                                            int32_t* out_count, void* workspace, size_t workspace_bytes, void* stream,
                                            const float* lm_table, int lm_order, double lm_alpha, double lm_beta) {
-    // the search's own checks, in the order of pgasr_ctc_beam_search_lm
-    if (!log_probs || !out_tokens || !out_len || !out_score) return PGASR_ERR_INVALID_ARG;
-    if (T <= 0 || B <= 0 || V <= 0 || beam <= 0 || blank < 0 || blank >= V) return PGASR_ERR_INVALID_ARG;
-    if (V > BEAM_VMAX || beam > BEAM_KMAX) return PGASR_ERR_UNSUPPORTED;
+    // the shared checks, in the order of pgasr_ctc_beam_search_lm, with the language model's and then the list's in their place
     BeamLm<true> lmb{};
-    if (const int st = beam_lm_args(V, blank, lm_table, lm_order, lm_alpha, lm_beta, &lmb)) return st;
-    // the list's
-    if (nbest < 1 || nbest > beam || tok_stride < T || !out_count) return PGASR_ERR_INVALID_ARG;
     BeamWs ws;
-    const size_t need = beam_ws_layout(T, B, beam, &ws, (char*)workspace);
-    if (!workspace || workspace_bytes < need) return PGASR_ERR_WORKSPACE;
-    if ((long long)T * beam + 1 >= (1ll << 24)) return PGASR_ERR_UNSUPPORTED;
+    if (const int st = beam_check_args(log_probs, out_tokens, out_len, out_score, T, B, V, beam, blank, BEAM_VMAX, BEAM_KMAX,
+                                       [&] {
+                                           if (const int s = beam_lm_args(V, blank, lm_table, lm_order, lm_alpha, lm_beta, &lmb)) return s;
+                                           return (nbest < 1 || nbest > beam || tok_stride < T || !out_count) ? (int)PGASR_ERR_INVALID_ARG : (int)PGASR_OK;
+                                       },
+                                       workspace, workspace_bytes, &ws)) return st;
     const bool with_lm = lm_order > 0;
     const size_t lds = beam_lds_bytes(beam, V, with_lm);
     if (lds > 160 * 1024) return PGASR_ERR_UNSUPPORTED;

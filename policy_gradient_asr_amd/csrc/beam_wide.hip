@@ -3,7 +3,9 @@
 // The kernels of beam.hip lay one symbol per lane, pack a trie node as parent << 8 | symbol and SORT all beam * V candidates of a
 // frame: at V = 1024, beam = 128 that is 131072 candidates, which neither fit the LDS nor are worth sorting -- at most `beam` survive.
 // This kernel keeps that file's algebra (the same candidates, the same log-sum-exp calls in the same argument order, so the scores
-// are the same bits) and replaces the sort by a top-`beam` SELECTION that returns exactly what the sort would:
+// are the same bits) and replaces the sort by a top-`beam` SELECTION that returns exactly what the sort would.  What the two have in
+// common is not restated here: the log-sum-exp forms, the rank key and its bitonic sort, the trie (workspace layout, find-or-create)
+// and the N-best result tail are those of beam_core.h, which both files include.
 //
 //   * one workgroup of 256 threads per utterance, frames a serial chain; the frame's V log-probs and the beam state (p_b, p_nb, node
 //     id, last symbol, parent id, the parent's position) live in LDS;
@@ -24,78 +26,30 @@
 //     same key, so both are exact and equal.
 // Every loop is bounded by construction: hash probes by the table size, ancestor walks by lengths[b], radix passes by the key width.
 #include "common.h"
+#include "beam_core.h"
 #include <cmath>
 
 namespace {
+
+using namespace beam_core;
 
 constexpr int WIDE_KMAX = 128;
 constexpr int WIDE_VMAX = 1024;
 constexpr int WIDE_THREADS = 256;
 constexpr int WIDE_CAP = 2048;                       // items of the candidate list: a frame with more candidates >= theta takes the counting selection
-constexpr int WIDE_SYM_BITS = 10;
-constexpr unsigned WIDE_SYM_MASK = (1u << WIDE_SYM_BITS) - 1u;
-constexpr long long WIDE_MAX_NODES = 1ll << 22;      // node ids are 22 bits: parent << 10 | symbol is one 32-bit word
+constexpr int WIDE_SYM_BITS = 10;                    // a trie node is parent << 10 | symbol, so node ids are 22 bits
+using WideWs = TrieWs<WIDE_SYM_BITS>;
 constexpr int WIDE_RADIX_PASSES = 12;                // 8 digits of the score image, 4 of the touch time
 constexpr unsigned WIDE_STAY = 0x80000000u;          // cand: WIDE_STAY | entry, else entry * V + symbol
 
-struct WideWs {
-    unsigned long long* table;   // [B][H] open addressing: (key + 1) << 32 | node id; 0 = empty
-    unsigned* nodes;             // [B][NN] parent << 10 | symbol; node 0 = root
-    int H, NN;
-};
-
-__host__ __device__ inline size_t wide_ws_layout(int T, int B, int beam, WideWs* ws, char* base) {
-    const long long nn = (long long)T * beam + 1;
-    long long H = 1024;
-    while (H < 2 * nn) H <<= 1;
-    size_t off = 0;
-    const size_t t_off = off; off += (size_t)B * (size_t)H * sizeof(unsigned long long);
-    off = (off + 255) / 256 * 256;
-    const size_t n_off = off; off += (size_t)B * (size_t)nn * sizeof(unsigned);
-    off = (off + 255) / 256 * 256;
-    if (ws) {
-        ws->table = (unsigned long long*)(base + t_off);
-        ws->nodes = (unsigned*)(base + n_off);
-        ws->H = (int)H; ws->NN = (int)nn;
-    }
-    return off;
-}
-
-// CTCdecoder.py:31-39 with 2 or 3 arguments, argument order preserved: restated from beam.hip (lse2 / lse3 / lse2x / lse3x) line for
-// line, so that both files give the same bits on the same inputs.  FAST (fp32 input): fp64 carries, fp32 exp/log on the differences.
-template <bool FAST> __device__ __forceinline__ double wlse2(double a, double b) {
-    const double m = fmax(a, b);
-    if (m == -INFINITY) return -INFINITY;
-    if (!FAST) return m + log(exp(a - m) + exp(b - m));
-    return m + (double)__logf(__expf((float)(a - m)) + __expf((float)(b - m)));
-}
-template <bool FAST> __device__ __forceinline__ double wlse3(double a, double b, double c) {
-    const double m = fmax(fmax(a, b), c);
-    if (m == -INFINITY) return -INFINITY;
-    if (!FAST) return m + log((exp(a - m) + exp(b - m)) + exp(c - m));
-    return m + (double)__logf((__expf((float)(a - m)) + __expf((float)(b - m))) + __expf((float)(c - m)));
-}
-
-// order-preserving map double -> u64 (ascending), as in beam.hip
-__device__ __forceinline__ unsigned long long wide_image(double x) {
-    const unsigned long long b = (unsigned long long)__double_as_longlong(x);
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-
-struct WideItem { unsigned long long key; unsigned time; unsigned cand; };      // key = ~image(score): ascending sort = score descending
-
-__device__ __forceinline__ bool wide_less(const WideItem& a, const WideItem& b) {
-    return a.key < b.key || (a.key == b.key && a.time < b.time);
-}
-
 // p_nb of the extension of an entry (p_b, p_nb) by a symbol of log-prob ps (:90-96); rep: the symbol repeats the entry's last one
 template <bool FAST> __device__ __forceinline__ double wide_ext(double pbj, double pnbj, double ps, bool rep) {
-    return rep ? wlse2<FAST>(-INFINITY, pbj + ps) : wlse3<FAST>(-INFINITY, pbj + ps, pnbj + ps);
+    return rep ? lse2x<FAST>(-INFINITY, pbj + ps) : lse3x<FAST>(-INFINITY, pbj + ps, pnbj + ps);
 }
 
 // LDS: fixed layout for the largest shape (all offsets multiples of 16)
 struct WideLds {
-    WideItem items[WIDE_CAP];                   // 32 KB candidate list
+    SortItem items[WIDE_CAP];                   // 32 KB candidate list
     double frame[WIDE_VMAX];                    // the frame's log-probs
     unsigned bitmap[WIDE_KMAX * (WIDE_VMAX / 32)];      // bit (i, s): the extension of entry i by s sits in the beam
     unsigned long long tkeys[2 * WIDE_KMAX];    // the 2 * nb score images the threshold is formed from
@@ -125,7 +79,6 @@ __global__ __launch_bounds__(WIDE_THREADS) void beam_wide_kernel(
 
     unsigned long long* table = ws.table + (size_t)b * ws.H;
     unsigned* nodes = ws.nodes + (size_t)b * ws.NN;
-    const unsigned hmask = (unsigned)ws.H - 1u;
 
     if (tid == 0) {
         L.nb = 1; L.nodes = 1; L.counting = 0;
@@ -155,7 +108,7 @@ __global__ __launch_bounds__(WIDE_THREADS) void beam_wide_kernel(
         if (tid < nb) {
             const int j = tid;
             const double fb = L.frame[blank];
-            const double npb = wlse3<FAST>(-INFINITY, cpb[j] + fb, cpnb[j] + fb);
+            const double npb = lse3x<FAST>(-INFINITY, cpb[j] + fb, cpnb[j] + fb);
             double npnb = -INFINITY;
             unsigned time = 2u * (unsigned)(blank * nb + j);
             const int lj = clast[j];
@@ -169,19 +122,19 @@ __global__ __launch_bounds__(WIDE_THREADS) void beam_wide_kernel(
                     const double e1 = cpb[i] + pl, e2 = cpnb[i] + pl;             // extension of parent i by lj (:90-96): touched first in iteration (lj, i)
                     const bool rep = (clast[i] == lj);
                     if (i < j) {
-                        npnb = rep ? wlse2<FAST>(npnb, e1) : wlse3<FAST>(npnb, e1, e2);
-                        npnb = wlse2<FAST>(npnb, own);
+                        npnb = rep ? lse2x<FAST>(npnb, e1) : lse3x<FAST>(npnb, e1, e2);
+                        npnb = lse2x<FAST>(npnb, own);
                     } else {
-                        npnb = wlse2<FAST>(npnb, own);
-                        npnb = rep ? wlse2<FAST>(npnb, e1) : wlse3<FAST>(npnb, e1, e2);
+                        npnb = lse2x<FAST>(npnb, own);
+                        npnb = rep ? lse2x<FAST>(npnb, e1) : lse3x<FAST>(npnb, e1, e2);
                     }
                     const unsigned t_ext = 2u * (unsigned)(lj * nb + i);
                     time = t_ext < time ? t_ext : time;
                 } else {
-                    npnb = wlse2<FAST>(npnb, own);
+                    npnb = lse2x<FAST>(npnb, own);
                 }
             }
-            const unsigned long long img = wide_image(wlse2<FAST>(npb, npnb));
+            const unsigned long long img = ordered_key(lse2x<FAST>(npb, npnb));
             L.st_pb[j] = npb; L.st_pnb[j] = npnb; L.st_img[j] = img; L.st_time[j] = time;
             L.tkeys[j] = img;
         }
@@ -200,7 +153,7 @@ __global__ __launch_bounds__(WIDE_THREADS) void beam_wide_kernel(
             if (!found) best = -INFINITY;
             for (int o = 32; o > 0; o >>= 1) best = fmax(best, __shfl_xor(best, o));
             if (lane == 0)
-                L.tkeys[nb + j] = any ? wide_image(wlse2<FAST>(-INFINITY, wide_ext<FAST>(cpb[j], cpnb[j], best, false))) : 0ull;
+                L.tkeys[nb + j] = any ? ordered_key(lse2x<FAST>(-INFINITY, wide_ext<FAST>(cpb[j], cpnb[j], best, false))) : 0ull;
         }
         for (int i = 2 * nb + tid; i < 2 * WIDE_KMAX; i += WIDE_THREADS) L.tkeys[i] = 0ull;       // 0 is below every real image
         if (tid == 0) { L.total = 0; L.theta = 0ull; }
@@ -226,7 +179,7 @@ __global__ __launch_bounds__(WIDE_THREADS) void beam_wide_kernel(
                     bool valid = s < V && s != blank;
                     if (valid) valid = !((L.bitmap[j * W + (s >> 5)] >> (s & 31)) & 1u);
                     unsigned long long img = 0ull;
-                    if (valid) img = wide_image(wlse2<FAST>(-INFINITY, wide_ext<FAST>(pbj, pnbj, L.frame[s], s == lj)));
+                    if (valid) img = ordered_key(lse2x<FAST>(-INFINITY, wide_ext<FAST>(pbj, pnbj, L.frame[s], s == lj)));
                     f(valid, img, 2u * (unsigned)(s * nb + j), (unsigned)(j * V + s));
                 }
             }
@@ -244,7 +197,7 @@ __global__ __launch_bounds__(WIDE_THREADS) void beam_wide_kernel(
                 if (lane == leader) base = atomicAdd(&L.total, __popcll(m));
                 base = __shfl(base, leader);
                 const int pos = base + __popcll(m & ((1ull << lane) - 1ull));
-                if (want && pos < WIDE_CAP) { WideItem it; it.key = ~img; it.time = time; it.cand = cand; L.items[pos] = it; }
+                if (want && pos < WIDE_CAP) { SortItem it; it.key = ~img; it.time = time; it.cand = cand; L.items[pos] = it; }
             });
         };
 
@@ -304,35 +257,17 @@ __global__ __launch_bounds__(WIDE_THREADS) void beam_wide_kernel(
             collect(L.cut_hi, L.cut_lo);
             __syncthreads();
         }
-        // ---- E: bitonic sort of the list (beam.hip's: element i belongs to thread i % 256, passes inside a wave need no barrier) ----
+        // ---- E: bitonic sort of the list ----
         int total = L.total; total = total > WIDE_CAP ? WIDE_CAP : total;         // the counting selection lists at most K <= WIDE_CAP
         int P = 2; while (P < total) P <<= 1;
-        for (int i = total + tid; i < P; i += WIDE_THREADS) { WideItem it; it.key = ~0ull; it.time = 0xFFFFFFFFu; it.cand = 0xFFFFFFFFu; L.items[i] = it; }
+        for (int i = total + tid; i < P; i += WIDE_THREADS) { SortItem it; it.key = ~0ull; it.time = 0xFFFFFFFFu; it.cand = 0xFFFFFFFFu; L.items[i] = it; }
         __syncthreads();
-        {
-            bool prev_cross = false;
-            for (int k2 = 2; k2 <= P; k2 <<= 1) {
-                for (int j2 = k2 >> 1; j2 > 0; j2 >>= 1) {
-                    const bool cross = j2 >= 64;
-                    if (cross || prev_cross) __syncthreads();
-                    for (int i = tid; i < P; i += WIDE_THREADS) {
-                        const int l = i ^ j2;
-                        if (l > i) {
-                            const WideItem x = L.items[i], y = L.items[l];
-                            const bool up = ((i & k2) == 0);
-                            if (wide_less(y, x) == up) { L.items[i] = y; L.items[l] = x; }
-                        }
-                    }
-                    prev_cross = cross;
-                }
-            }
-            __syncthreads();
-        }
+        bitonic_sort<WIDE_THREADS>(L.items, P, tid);
         // ---- F: new beam: the first min(K, total) items ----
         const int nxt = cur ^ 1;
         const int nnew = total < K ? total : K;
         if (tid < nnew) {
-            const WideItem it = L.items[tid];
+            const SortItem it = L.items[tid];
             if (it.cand & WIDE_STAY) {
                 const int j = (int)(it.cand & ~WIDE_STAY);
                 L.pb[nxt][tid] = L.st_pb[j]; L.pnb[nxt][tid] = L.st_pnb[j];
@@ -341,63 +276,19 @@ __global__ __launch_bounds__(WIDE_THREADS) void beam_wide_kernel(
                 const int j = (int)it.cand / V, s = (int)it.cand - j * V;
                 L.pb[nxt][tid] = -INFINITY;
                 L.pnb[nxt][tid] = wide_ext<FAST>(cpb[j], cpnb[j], L.frame[s], s == clast[j]);
-                // canonical node for (id[j], s): look up, else create; at most H probes
-                const unsigned keyv = ((unsigned)cid[j] << WIDE_SYM_BITS) | (unsigned)s;
-                unsigned h = (keyv * 2654435761u) & hmask;
-                int node = -1;
-                bool placed = false;
-                for (int probe = 0; probe < ws.H && !placed; ++probe) {
-                    const unsigned long long slot = table[h];
-                    if (slot == 0ull) {
-                        if (node < 0) { node = atomicAdd(&L.nodes, 1); if (node < ws.NN) nodes[node] = keyv; }
-                        const unsigned long long want = ((unsigned long long)(keyv + 1u) << 32) | (unsigned)node;
-                        const unsigned long long old = atomicCAS(&table[h], 0ull, want);
-                        if (old == 0ull) placed = true;
-                        else if ((unsigned)(old >> 32) == keyv + 1u) { node = (int)(unsigned)old; placed = true; }
-                    } else if ((unsigned)(slot >> 32) == keyv + 1u) { node = (int)(unsigned)slot; placed = true; }
-                    h = (h + 1u) & hmask;
-                }
-                L.id[nxt][tid] = placed ? node : 0; L.last[nxt][tid] = s; L.par[nxt][tid] = cid[j];
+                // canonical node for (id[j], s): look up, else create
+                L.id[nxt][tid] = trie_find_or_create<WIDE_SYM_BITS>(table, nodes, ws.H, ws.NN, &L.nodes, cid[j], s);
+                L.last[nxt][tid] = s; L.par[nxt][tid] = cid[j];
             }
         }
         if (tid == 0) L.nb = nnew;
         __syncthreads();
         cur = nxt;
     }
-    // ---- result: the final beam is ranked, row r is entry r; thread r walks entry r's ancestors (at most Tb steps) ----
-    const int B = (int)gridDim.x, N = nbest, S = tok_stride;
-    const int count = N < L.nb ? N : L.nb;
-    int* hlen = L.pidx;
-    if (tid < N) {
-        int n = 0;
-        double sc = INFINITY;
-        if (tid < count) {
-            int32_t* o = out_tokens + ((size_t)tid * B + b) * S;
-            const int head = L.id[cur][tid];
-            for (int v = head; v > 0 && v < ws.NN && n < Tb; v = (int)(nodes[v] >> WIDE_SYM_BITS)) ++n;
-            int v = head;
-            for (int k = n - 1; k >= 0; --k) { const unsigned w = nodes[v]; o[k] = (int32_t)(w & WIDE_SYM_MASK); v = (int)(w >> WIDE_SYM_BITS); }
-            if (collapse) {
-                int w = 0;
-                for (int i = 0; i < n; ++i) if (i == 0 || o[i] != o[i - 1]) { const int32_t x = o[i]; o[w++] = x; }
-                n = w;
-            }
-            sc = -wlse2<FAST>(L.pb[cur][tid], L.pnb[cur][tid]);
-        }
-        hlen[tid] = n;
-        out_len[(size_t)tid * B + b] = n;
-        out_score[(size_t)tid * B + b] = sc;
-    }
-    if (tid == 0) {
-        out_count[b] = count;
-        if (out_counting) out_counting[b] = L.counting;
-    }
-    __threadfence_block();
-    __syncthreads();
-    for (int r = 0; r < N; ++r) {
-        int32_t* o = out_tokens + ((size_t)r * B + b) * S;
-        for (int i = hlen[r] + tid; i < S; i += WIDE_THREADS) o[i] = 0;
-    }
+    // ---- result: row r is entry r of the final, ranked beam; L.pidx is free after the frame loop ----
+    nbest_tail<WIDE_SYM_BITS, WIDE_THREADS, FAST>(nodes, ws.NN, Tb, b, tid, nbest, tok_stride, collapse, L.nb, L.id[cur], L.pb[cur], L.pnb[cur],
+                                                  L.pidx, out_tokens, out_len, out_score, out_count);
+    if (tid == 0 && out_counting) out_counting[b] = L.counting;
 }
 
 }  // namespace
@@ -405,7 +296,7 @@ __global__ __launch_bounds__(WIDE_THREADS) void beam_wide_kernel(
 extern "C" size_t pgasr_beam_wide_workspace_bytes(int T, int B, int V, int beam) {
     (void)V;
     if (T <= 0 || B <= 0 || beam <= 0) return 0;
-    return wide_ws_layout(T, B, beam, nullptr, nullptr);
+    return trie_ws_layout<WIDE_SYM_BITS>(T, B, beam, nullptr, nullptr);
 }
 
 extern "C" int pgasr_ctc_beam_search_wide(const void* log_probs, int is_f64, long long stride_t, long long stride_b,
@@ -414,15 +305,13 @@ extern "C" int pgasr_ctc_beam_search_wide(const void* log_probs, int is_f64, lon
                                           int32_t* out_count, int32_t* out_counting_frames,
                                           void* workspace, size_t workspace_bytes, void* stream) {
     // the order and the status codes of pgasr_ctc_beam_search_nbest; nothing below touches HIP until every check has passed
-    if (!log_probs || !out_tokens || !out_len || !out_score) return PGASR_ERR_INVALID_ARG;
-    if (T <= 0 || B <= 0 || V <= 0 || beam <= 0 || blank < 0 || blank >= V) return PGASR_ERR_INVALID_ARG;
-    if (V > WIDE_VMAX || beam > WIDE_KMAX) return PGASR_ERR_UNSUPPORTED;
-    if (flags & ~(1 | 32)) return PGASR_ERR_INVALID_ARG;
-    if (nbest < 1 || nbest > beam || tok_stride < T || !out_count) return PGASR_ERR_INVALID_ARG;
     WideWs ws;
-    const size_t need = wide_ws_layout(T, B, beam, &ws, (char*)workspace);
-    if (!workspace || workspace_bytes < need) return PGASR_ERR_WORKSPACE;
-    if ((long long)T * beam + 1 >= WIDE_MAX_NODES) return PGASR_ERR_UNSUPPORTED;
+    if (const int st = beam_check_args(log_probs, out_tokens, out_len, out_score, T, B, V, beam, blank, WIDE_VMAX, WIDE_KMAX,
+                                       [&] {
+                                           const bool bad = (flags & ~(1 | 32)) || nbest < 1 || nbest > beam || tok_stride < T || !out_count;
+                                           return bad ? (int)PGASR_ERR_INVALID_ARG : (int)PGASR_OK;
+                                       },
+                                       workspace, workspace_bytes, &ws)) return st;
     static_assert(2 * WIDE_KMAX == WIDE_THREADS, "one threshold slot and one histogram bin per thread");
     static_assert(sizeof(WideLds) <= 160 * 1024, "LDS");
     hipStream_t st = (hipStream_t)stream;

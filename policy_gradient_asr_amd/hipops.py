@@ -1482,6 +1482,32 @@ def beam_lm_single_wave_ok(T, V, beam, is_f64, lm_order):
     return bool(_lib.load().pgasr_beam_lm_single_wave_ok(int(T), int(V), int(beam), int(bool(is_f64)), int(lm_order)))
 
 
+def _search_inputs(log_probs, lengths):
+    """The checks the three search wrappers share; returns (T, B, V)."""
+    if not log_probs.is_cuda or log_probs.dtype not in (torch.float32, torch.float64):
+        raise _lib.PgasrError("log_probs must be a float32/float64 GPU tensor")
+    if log_probs.stride(2) != 1:
+        raise _lib.PgasrError("log_probs must be contiguous in its last dimension")
+    T, B, V = log_probs.shape
+    _req(lengths, torch.int32, "lengths")
+    return T, B, V
+
+
+def _nbest_outputs(N, B, T, dev):
+    """tokens (N,B,T), lengths (N,B), score (N,B), count (B), uninitialised: the N-best kernels write every word."""
+    N = max(N, 0)
+    return (torch.empty(N, B, T, dtype=torch.int32, device=dev), torch.empty(N, B, dtype=torch.int32, device=dev),
+            torch.empty(N, B, dtype=torch.float64, device=dev), torch.empty(B, dtype=torch.int32, device=dev))
+
+
+def _lm_table(lm, V, blank, device):
+    if lm is None:
+        return None, 0
+    if lm.vocab != V or lm.blank != int(blank):
+        raise ValueError(f"the LM is over {lm.vocab} symbols with blank {lm.blank}; the search has {V} symbols and blank {int(blank)}")
+    return lm.device_table(device), lm.order
+
+
 def ctc_beam_search(log_probs, lengths=None, beam=5, blank=0, collapse=False, out=None, generic=False,
                     lm=None, lm_alpha=0.0, lm_beta=0.0, fast_lm=False):
     """log_probs (T,B,V) fp32 or fp64 natural-log probabilities on the GPU.
@@ -1498,17 +1524,8 @@ def ctc_beam_search(log_probs, lengths=None, beam=5, blank=0, collapse=False, ou
     ~1e-7 relative, its hypotheses wherever no two candidates are closer than that.  Without an LM or outside those limits the flag
     changes nothing."""
     lib = _lib.load()
-    if not log_probs.is_cuda or log_probs.dtype not in (torch.float32, torch.float64):
-        raise _lib.PgasrError("log_probs must be a float32/float64 GPU tensor")
-    if log_probs.stride(2) != 1:
-        raise _lib.PgasrError("log_probs must be contiguous in its last dimension")
-    T, B, V = log_probs.shape
-    _req(lengths, torch.int32, "lengths")
-    lm_table, lm_order = None, 0
-    if lm is not None:
-        if lm.vocab != V or lm.blank != int(blank):
-            raise ValueError(f"the LM is over {lm.vocab} symbols with blank {lm.blank}; the search has {V} symbols and blank {int(blank)}")
-        lm_table, lm_order = lm.device_table(log_probs.device), lm.order
+    T, B, V = _search_inputs(log_probs, lengths)
+    lm_table, lm_order = _lm_table(lm, V, blank, log_probs.device)
     nbytes = lib.pgasr_beam_workspace_bytes(T, B, V, beam)
     ws = _workspace(nbytes, log_probs.device, "beam")
     if out is not None:
@@ -1535,14 +1552,6 @@ CTCNBest = collections.namedtuple("CTCNBest", "tokens lengths score count")
 NBEST_RESCORE_MAX = 128          # csrc/nbest.hip: hypotheses per utterance
 
 
-def _lm_table(lm, V, blank, device):
-    if lm is None:
-        return None, 0
-    if lm.vocab != V or lm.blank != int(blank):
-        raise ValueError(f"the LM is over {lm.vocab} symbols with blank {lm.blank}; the search has {V} symbols and blank {int(blank)}")
-    return lm.device_table(device), lm.order
-
-
 def ctc_beam_search_nbest(log_probs, lengths=None, beam=5, nbest=1, blank=0, collapse=False, lm=None, lm_alpha=0.0, lm_beta=0.0,
                           fast=False, fast_lm=False):
     """The first ``nbest`` entries of the search's final beam (pgasr_ctc_beam_search_nbest): log_probs (T,B,V) fp32 or fp64 as
@@ -1562,19 +1571,11 @@ def ctc_beam_search_nbest(log_probs, lengths=None, beam=5, nbest=1, blank=0, col
     limits of ``fast`` with a table); row 0 is then bit for bit ``ctc_beam_search(lm=..., fast_lm=True)``.  Without an LM or outside
     the limits the flag changes nothing; ``fast`` without it keeps a call with an LM on the workgroup kernel."""
     lib = _lib.load()
-    if not log_probs.is_cuda or log_probs.dtype not in (torch.float32, torch.float64):
-        raise _lib.PgasrError("log_probs must be a float32/float64 GPU tensor")
-    if log_probs.stride(2) != 1:
-        raise _lib.PgasrError("log_probs must be contiguous in its last dimension")
-    T, B, V = log_probs.shape
-    _req(lengths, torch.int32, "lengths")
+    T, B, V = _search_inputs(log_probs, lengths)
     lm_table, lm_order = _lm_table(lm, V, blank, log_probs.device)
     N, dev = int(nbest), log_probs.device
     ws = _workspace(lib.pgasr_beam_workspace_bytes(T, B, V, int(beam)), dev, "beam")
-    tokens = torch.empty(max(N, 0), B, T, dtype=torch.int32, device=dev)      # the kernel writes every word
-    tl = torch.empty(max(N, 0), B, dtype=torch.int32, device=dev)
-    score = torch.empty(max(N, 0), B, dtype=torch.float64, device=dev)
-    count = torch.empty(B, dtype=torch.int32, device=dev)
+    tokens, tl, score, count = _nbest_outputs(N, B, T, dev)
     with _timed("beam_search_nbest"):
         st = lib.pgasr_ctc_beam_search_nbest(_p(log_probs), int(log_probs.dtype == torch.float64), log_probs.stride(0),
                                              log_probs.stride(1), _p(lengths), T, B, V, int(beam), int(blank),
@@ -1598,18 +1599,10 @@ def ctc_beam_search_wide(log_probs, lengths=None, beam=5, nbest=None, blank=0, c
     stats: the counting-frames tensor (B) int32 -- frames of each utterance that took the counting selection -- is returned as one
     more value behind the result."""
     lib = _lib.load()
-    if not log_probs.is_cuda or log_probs.dtype not in (torch.float32, torch.float64):
-        raise _lib.PgasrError("log_probs must be a float32/float64 GPU tensor")
-    if log_probs.stride(2) != 1:
-        raise _lib.PgasrError("log_probs must be contiguous in its last dimension")
-    T, B, V = log_probs.shape
-    _req(lengths, torch.int32, "lengths")
+    T, B, V = _search_inputs(log_probs, lengths)
     N, dev = (1 if nbest is None else int(nbest)), log_probs.device
     ws = _workspace(lib.pgasr_beam_wide_workspace_bytes(T, B, V, int(beam)), dev, "beam_wide")
-    tokens = torch.empty(max(N, 0), B, T, dtype=torch.int32, device=dev)      # the kernel writes every word
-    tl = torch.empty(max(N, 0), B, dtype=torch.int32, device=dev)
-    score = torch.empty(max(N, 0), B, dtype=torch.float64, device=dev)
-    count = torch.empty(B, dtype=torch.int32, device=dev)
+    tokens, tl, score, count = _nbest_outputs(N, B, T, dev)
     frames = torch.empty(B, dtype=torch.int32, device=dev) if stats else None
     with _timed("beam_search_wide"):
         st = lib.pgasr_ctc_beam_search_wide(_p(log_probs), int(log_probs.dtype == torch.float64), log_probs.stride(0),
