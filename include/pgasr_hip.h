@@ -887,6 +887,67 @@ int pgasr_ctc_beam_search_wide(const void* log_probs, int is_f64, long long stri
                                void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * A7-WIDE-LM  A back-off n-gram language model over the acoustic units themselves (order 1 .. 5, V <= 1024 symbols, sparse): fusion
+ * inside the A7-WIDE search, and the model's score of every hypothesis of an N-best list (csrc/beam_wide.hip, csrc/unit_lm.hip,
+ * csrc/unit_lm.h; the host model, its packing and its own statement of the query: lm.UnitNgramLM).
+ * The model.  blank never occurs inside a prefix: it is the start-of-sentence symbol, exactly one of it (ARPA's <s>).  The context of
+ *   a prefix y is the last order-1 symbols of (blank,) + y, shorter near the start.  Stored k-grams are (c_1 .. c_{k-1}, s), s != blank,
+ *   blank only as c_1; each has logp and, below the top order, bow (natural log, fp32).  Every one of the V-1 unigrams is stored, and
+ *   the context of every stored n-gram is stored.  The query lp32(h, s), contractual on the host and on the device:
+ *     acc = 0.0 (fp64); if (h, s) is stored: return (float)(acc + (double)logp[h, s]); else acc += (double)bow[h] where h is stored,
+ *     drop the oldest symbol of h, and again -- sums from the longest context to the shortest, one rounding to fp32 at the end.
+ * pgasr_unit_lm_tables: device pointers and sizes, a plain struct in HOST memory passed by pointer and read before the launch.
+ *   A STATE is a stored context: state 0 the empty one, then every stored k-gram with k < order (the unigram of symbol c, <s> = blank
+ *   included, is state 1 + c).  states (n_states) x 16 bytes {float bow, int32 back-off state, int32 first successor, int32 one past
+ *   the last}; the back-off state is the longest proper suffix of the context that is a state.  A SUCCESSOR is a stored n-gram listed
+ *   behind its context: succ (n_succ) x 16 bytes {int32 symbol, float logp, int32 next state, 0}, the successors of one state
+ *   consecutive and ascending in the symbol; state 0 lists all V-1 unigrams.  next state = the longest suffix of context + symbol, of
+ *   at most order-1 symbols, that is a state.  start = the state of the empty prefix: (blank,) from order 2 on.  Walking the back-off
+ *   states instead of dropping one symbol at a time is the same query: a context that is no state has no bow and, by closure, no
+ *   successor.
+ * pgasr_ctc_beam_search_wide_lm: pgasr_ctc_beam_search_wide with the model fused in, A7-LM's algebra word for word: every term that
+ *   enters a prefix by an extension with a non-blank s gets w = __dadd_rn(__dmul_rn(lm_alpha, (double)lp32(ctx(prefix), s)), lm_beta)
+ *   added -- (p_b + p) + w, (p_nb + p) + w --, also where the extension of parent i by last(j) merges into entry j's stay candidate
+ *   (with the parent's context); the blank update and the repeat branch that keeps the prefix are unchanged.  fp64 for fp32 and fp64
+ *   input alike.  Candidates, touch times, both selections, the trie and the result tail are A7-WIDE's; out_score is a FUSED score.
+ *   lm_alpha = lm_beta = 0 returns pgasr_ctc_beam_search_wide's words bit for bit; for V <= 64 and a model with a dense form every
+ *   output word equals pgasr_ctc_beam_search_nbest's with that table (flags bits 3 and 4 clear) wherever no two candidates tie.
+ *   Each beam entry owns a dense row of its state in the workspace (lp32(state, s) and the next state for every s; 2 * beam rows per
+ *   utterance; a staying entry keeps its row, an extension winner's row is filled from the successor lists of its back-off chain,
+ *   shortest context first), so a candidate costs one fp32 load.  Every loop is bounded: the chain by the order, a list by its length,
+ *   the rest as A7-WIDE.
+ *   Checked before any HIP call, in this order: A7-WIDE's checks up to and including the flags / nbest / tok_stride / out_count group;
+ *   then the model -- tables, states or succ NULL -> PGASR_ERR_INVALID_ARG; order outside 1 .. 5, vocab > 1024, n_succ > 2^24, n_states >
+ *   2^24 + 1 -> PGASR_ERR_UNSUPPORTED; vocab != V, blank != the call's, n_states < 1, n_succ < V - 1, start outside the states, a weight
+ *   that is not finite -> PGASR_ERR_INVALID_ARG --; then the trie's part of the workspace -> PGASR_ERR_WORKSPACE, the node-id width ->
+ *   PGASR_ERR_UNSUPPORTED, the whole workspace (pgasr_beam_wide_lm_workspace_bytes) -> PGASR_ERR_WORKSPACE.  No host synchronisation.
+ * pgasr_nbest_unit_lm_score:
+ *   tokens (N, B, tok_stride) int32, len (N, B), count (B): a list as pgasr_ctc_beam_search_nbest writes it (len is clamped to
+ *   [0, tok_stride], count to [0, N]); nothing behind a hypothesis' length is read.  For n < count[b]:
+ *     out_lm_logp[n, b] fp64 = sum_i (double)lp32(ctx(y_<i), y_i), one addition per token in index order; no end-of-sentence term.
+ *   A symbol outside [0, V) or equal to blank gives -inf (no table word is read for it).  Rows n >= count[b]: 0.  Totals and ranks:
+ *   pgasr_nbest_combine_rank with word_logp = out_lm_logp and n_words = len is A7-RESCORE's formula with the same roundings.
+ *   Checked before any HIP call, in this order: N < 1, N > 128, V > 1024 -> PGASR_ERR_UNSUPPORTED; a NULL pointer, B < 1,
+ *   tok_stride < 1, V < 1, blank outside [0, V) -> PGASR_ERR_INVALID_ARG; the model as above.  One launch, one thread per
+ *   hypothesis, no workspace, no host synchronisation.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct pgasr_unit_lm_tables {
+    const void* states;
+    const void* succ;
+    int32_t order, vocab, blank, n_states, n_succ, start;
+} pgasr_unit_lm_tables;
+size_t pgasr_beam_wide_lm_workspace_bytes(int T, int B, int V, int beam);
+int pgasr_ctc_beam_search_wide_lm(const void* log_probs, int is_f64, long long stride_t, long long stride_b,
+                                  const int32_t* lengths, int T, int B, int V, int beam, int blank, int flags,
+                                  int nbest, int32_t* out_tokens, int tok_stride, int32_t* out_len, double* out_score,
+                                  int32_t* out_count, int32_t* out_counting_frames,
+                                  void* workspace, size_t workspace_bytes, void* stream,
+                                  const pgasr_unit_lm_tables* tables, double lm_alpha, double lm_beta);
+int pgasr_nbest_unit_lm_score(const int32_t* tokens, int tok_stride, const int32_t* len, const int32_t* count,
+                              int N, int B, int V, int blank, const pgasr_unit_lm_tables* tables, double* out_lm_logp,
+                              void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * A7-RESCORE Second pass over N-best lists: an n-gram LM score of every hypothesis, a weighted total and its rank.
  *   tokens (N, B, tok_stride) int32, len (N, B), count (B): a list as pgasr_ctc_beam_search_nbest writes it (len is clamped to
  *   [0, tok_stride], count to [0, N]); am (N, B) fp64: the caller's acoustic score, lower is better.

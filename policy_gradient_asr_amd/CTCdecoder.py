@@ -4,7 +4,7 @@ as a HIP kernel (csrc/beam.hip).  ``greedy_decode`` is the best-path decoder the
 (SURVEY §8a A9).  Beyond the reference: ``nbest=N`` returns the first N entries of the final beam instead of the best one, and
 ``CTCDecoder.rescore`` ranks such a list in a second pass (exact CTC likelihood and / or a stronger n-gram LM, csrc/nbest.hip; the
 likelihood of lists of more than 16 rows or more than 64 symbols from the lattice-free scorer, csrc/hyp_score.hip; with
-``word_lm=`` a word n-gram LM on top, csrc/word_lm.hip);
+``word_lm=`` a word n-gram LM on top, csrc/word_lm.hip; with ``unit_lm=`` a back-off LM over the units themselves, csrc/unit_lm.hip);
 ``CTCDecoder.mbr_decode`` returns the hypothesis of least expected edit distance under the list's posterior instead of the best-scored
 one (minimum-Bayes-risk decoding, csrc/mbr.hip)."""
 import collections
@@ -38,11 +38,13 @@ _UNSET = object()      # "use the decoder's own value" (None is a value: no lang
 
 NBestRescored = collections.namedtuple("NBestRescored", "order total am lm_logp best_tokens best_len skipped")
 NBestRescoredWords = collections.namedtuple("NBestRescoredWords", NBestRescored._fields + ("word_logp", "n_words", "n_oov"))
+NBestRescoredUnits = collections.namedtuple("NBestRescoredUnits", NBestRescored._fields + ("unit_logp",))
+NBestRescoredWordsUnits = collections.namedtuple("NBestRescoredWordsUnits", NBestRescoredWords._fields + ("unit_logp",))
 MBRDecoded = collections.namedtuple("MBRDecoded", "tokens lengths best risk posterior dist nbest")
 
 
 class CTCDecoder:
-    def __init__(self, alphabet, device=None, lm=None, lm_alpha=0.0, lm_beta=0.0, fast_lm=False, wide_search=False):
+    def __init__(self, alphabet, device=None, lm=None, lm_alpha=0.0, lm_beta=0.0, fast_lm=False, wide_search=False, unit_lm=None):
         """lm: None (default: the acoustic search of the reference) or a ``lm.CharNgramLM``; every extension of a prefix by a
         non-blank symbol s then gets ``lm_alpha * ln p_lm(s | last order-1 symbols) + lm_beta`` added (Hannun/Maas,
         arXiv:1408.2873 -- the place CTCdecoder.py:90-96 marks for an LM score).  ``decode`` / ``decode_batch`` use these values
@@ -53,7 +55,16 @@ class CTCDecoder:
         wide_search: opt in to the exact search over rows of 65 .. 1024 symbols (``hipops.ctc_beam_search_wide``, csrc/beam_wide.hip):
         ``decode`` and ``decode_batch``, the ``nbest=`` forms included, then take that entry for rows of more than 64 symbols.  It has
         no language-model fusion: such rows together with an LM raise.  Rows of at most 64 symbols make the calls they always made;
-        with the default False wider rows are refused as before."""
+        with the default False wider rows are refused as before.
+        unit_lm: None or a ``lm.UnitNgramLM`` (a sparse back-off model over the units themselves, up to 1024 symbols), fused into the
+        wide search with ``lm_alpha`` / ``lm_beta`` as ``lm`` is into the narrow one (``hipops.ctc_beam_search_wide(unit_lm=)``).  It
+        needs ``wide_search=True`` and excludes ``lm``; rows of at most 64 symbols then take the wide entry too.  A model whose
+        vocabulary or blank differs from a call's raises."""
+        if unit_lm is not None and lm is not None:
+            raise ValueError("unit_lm: not together with lm -- one first-pass language model")
+        if unit_lm is not None and not wide_search:
+            raise ValueError("unit_lm: the model is fused into the wide search; give wide_search=True")
+        self.unit_lm = unit_lm
         self.alphabet = alphabet
         self.NEG_INF = -float("inf")
         self.device = device
@@ -61,8 +72,15 @@ class CTCDecoder:
         self.fast_lm = bool(fast_lm)
         self.wide_search = bool(wide_search)
 
-    def _takes_wide(self, V, args):
+    def _takes_wide(self, V, args, blank=0):
         """Whether rows of V symbols go to the wide search; refuses what neither search takes.  Touches no device."""
+        if self.unit_lm is not None:
+            if args["lm"] is not None:
+                raise ValueError("unit_lm: not together with lm -- one first-pass language model")
+            if V > hipops.MAX_VOCAB_SEARCH_WIDE:
+                raise ValueError(f"the wide beam search takes at most {hipops.MAX_VOCAB_SEARCH_WIDE} output symbols (got {V})")
+            hipops._unit_lm_check(self.unit_lm, V, blank)
+            return True
         if V <= hipops.MAX_VOCAB_NARROW:
             return False
         if not self.wide_search:
@@ -73,6 +91,12 @@ class CTCDecoder:
             raise ValueError(f"lm: the wide beam search ({V} > {hipops.MAX_VOCAB_NARROW} symbols) has no language-model fusion; "
                              f"search without one (lm=None)")
         return True
+
+    def _wide_lm(self, args):
+        """The language-model keywords of the wide entry."""
+        if self.unit_lm is None:
+            return {}
+        return {"unit_lm": self.unit_lm, "lm_alpha": args["lm_alpha"], "lm_beta": args["lm_beta"]}
 
     def _lm_args(self, lm, lm_alpha, lm_beta):
         return {"lm": self.lm if lm is _UNSET else lm,
@@ -85,17 +109,18 @@ class CTCDecoder:
         ``lm_alpha`` / ``lm_beta`` given here; ``lm=None`` switches it off for this call) the second value is the FUSED score
         -logsumexp(p_blank, p_nonblank) with the LM bonuses in it, not a negative log-likelihood.
         Limits of the device search (the reference has none): beam_size <= 128 and at most 64 output symbols (1024 with
-        ``wide_search=True`` and no language model) -- a larger request raises instead of silently searching a narrower beam.
+        ``wide_search=True``, where the language model is the decoder's ``unit_lm`` or none) -- a larger request raises instead of
+        silently searching a narrower beam.
         nbest: None (default: the pair above) or N with 1 <= N <= beam_size: a list of (label tuple, score) pairs, the first
         min(N, size of the final beam) entries of the final beam in the search's rank order (best first; equal scores in first-touch
         order, like the reference's sorted(...)[:N])."""
         args = self._lm_args(lm, lm_alpha, lm_beta)
         if self.wide_search:                                 # refused before a device is asked for
-            self._takes_wide(np.shape(probs)[-1], args)
+            self._takes_wide(np.shape(probs)[-1], args, blank)
         dev = _device(self.device)
         probs = np.asarray(probs)
         T, V = probs.shape
-        wide = self._takes_wide(V, args)
+        wide = self._takes_wide(V, args, blank)
         if T == 0:
             return (tuple(), -0.0) if nbest is None else [(tuple(), -0.0)]
         with np.errstate(divide="ignore"):
@@ -105,13 +130,13 @@ class CTCDecoder:
             raise ValueError(f"beam_size {beam_size} exceeds the device search's limit of {BEAM_KMAX}")
         if nbest is not None:
             if wide:
-                nb = hipops.ctc_beam_search_wide(lp, None, beam=int(beam_size), nbest=int(nbest), blank=int(blank))
+                nb = hipops.ctc_beam_search_wide(lp, None, beam=int(beam_size), nbest=int(nbest), blank=int(blank), **self._wide_lm(args))
             else:
                 nb = hipops.ctc_beam_search_nbest(lp, None, beam=int(beam_size), nbest=int(nbest), blank=int(blank), **args)
             tok, tl, sc = nb.tokens[:, 0].cpu(), nb.lengths[:, 0].tolist(), nb.score[:, 0].tolist()
             return [(tuple(int(x) for x in tok[r, :tl[r]].tolist()), float(sc[r])) for r in range(int(nb.count[0].item()))]
         if wide:
-            tokens, tl, score = hipops.ctc_beam_search_wide(lp, None, beam=int(beam_size), blank=int(blank))
+            tokens, tl, score = hipops.ctc_beam_search_wide(lp, None, beam=int(beam_size), blank=int(blank), **self._wide_lm(args))
         else:
             tokens, tl, score = hipops.ctc_beam_search(lp, None, beam=int(beam_size), blank=int(blank), **args)
         n = int(tl[0].item())
@@ -127,9 +152,9 @@ class CTCDecoder:
         fast_lm: None (default: the decoder's own) or a bool -- with an LM, take the single-wave kernel where its limits allow."""
         fast_lm = self.fast_lm if fast_lm is None else bool(fast_lm)
         args = self._lm_args(lm, lm_alpha, lm_beta)
-        if self._takes_wide(log_probs.shape[-1], args):
+        if self._takes_wide(log_probs.shape[-1], args, blank):
             return hipops.ctc_beam_search_wide(log_probs, lengths, beam=int(beam_size), blank=int(blank),
-                                               nbest=None if nbest is None else int(nbest))
+                                               nbest=None if nbest is None else int(nbest), **self._wide_lm(args))
         if nbest is not None:
             return hipops.ctc_beam_search_nbest(log_probs, lengths, beam=int(beam_size), nbest=int(nbest), blank=int(blank),
                                                 fast_lm=fast_lm, **args)
@@ -144,7 +169,8 @@ class CTCDecoder:
         raise ValueError("a word LM needs word_delimiter: the alphabet has no ' ' symbol")
 
     def rescore(self, log_probs, lengths, nb, lm=_UNSET, lm_alpha=None, lm_beta=None, acoustic="ctc", am_weight=1.0, max_hyp_len=None,
-                blank=0, word_lm=None, word_lm_alpha=0.0, word_lm_beta=0.0, word_delimiter=None, scorer=None):
+                blank=0, word_lm=None, word_lm_alpha=0.0, word_lm_beta=0.0, word_delimiter=None, scorer=None, unit_lm=None,
+                unit_lm_alpha=0.0, unit_lm_beta=0.0):
         """Second pass over an N-best list ``nb`` (``hipops.CTCNBest`` of ``decode_batch(..., nbest=N)`` on the same log_probs
         (T,B,V) / lengths), N <= 128:  total = am_weight * am - lm_alpha * lm_logp - lm_beta * length, lower is better, with
         lm_logp the hypothesis' log-probability under ``lm`` (the decoder's own unless given; None: no LM term).
@@ -173,7 +199,15 @@ class CTCDecoder:
         Lists over more than 64 symbols (``CTCDecoder(wide_search=True)``): ``lm`` and ``word_lm`` must be None (ValueError naming
             the option: a subword unit may span a space and the character tables hold 64 symbols); total = am_weight * am - lm_beta *
             length and its rank come from ``hipops.nbest_combine_rank`` -- the formula above without an LM, with the same roundings --
-            and lm_logp is zeros."""
+            and lm_logp is zeros.
+        unit_lm: None (default: everything above, nothing else) or a ``lm.UnitNgramLM`` over the list's V symbols and ``blank`` -- the
+            language model of wide lists, and of narrow ones alike.  The pass above runs first and its total is the base of one more
+            launch pair: total = base - unit_lm_alpha * unit_logp - unit_lm_beta * length, with unit_logp the hypothesis'
+            ``logp_sequence`` (``hipops.nbest_unit_lm_score``) and the roundings of the formula above
+            (``hipops.nbest_combine_rank``); a word LM, if any, comes on top of that.  The result carries one more field, unit_logp
+            (N,B) float64 (``NBestRescoredUnits`` / ``NBestRescoredWordsUnits``).  No further host synchronisation."""
+        if unit_lm is not None:
+            hipops._unit_lm_check(unit_lm, log_probs.shape[-1], blank)
         if acoustic not in ("ctc", "first_pass"):
             raise ValueError(f"acoustic must be 'ctc' or 'first_pass' (got {acoustic!r})")
         if scorer not in (None, "lattice", "forward"):
@@ -222,6 +256,10 @@ class CTCDecoder:
             order, total, lm_logp = hipops.nbest_rescore(nb.tokens, nb.lengths, nb.count, am.contiguous(), V, blank=int(blank),
                                                          lm=args["lm"], am_weight=float(am_weight), lm_alpha=args["lm_alpha"],
                                                          lm_beta=args["lm_beta"])
+        if unit_lm is not None:
+            unit_logp = hipops.nbest_unit_lm_score(nb.tokens, nb.lengths, nb.count, unit_lm)
+            order, total = hipops.nbest_combine_rank(total, unit_logp, nb.lengths.clamp(0, nb.tokens.shape[2]), nb.count,
+                                                     word_alpha=float(unit_lm_alpha), word_beta=float(unit_lm_beta))
         if word_lm is not None:
             word_logp, n_words, n_oov = hipops.nbest_word_lm_score(nb.tokens, nb.lengths, nb.count, word_lm, delim)
             order, total = hipops.nbest_combine_rank(total, word_logp, n_words, nb.count, word_alpha=float(word_lm_alpha),
@@ -230,8 +268,10 @@ class CTCDecoder:
         cols = torch.arange(B, device=order.device)
         best = (nb.tokens[first, cols].contiguous(), nb.lengths[first, cols].contiguous())
         if word_lm is not None:
-            return NBestRescoredWords(order, total, am, lm_logp, best[0], best[1], skipped, word_logp, n_words, n_oov)
-        return NBestRescored(order, total, am, lm_logp, best[0], best[1], skipped)
+            res = NBestRescoredWords(order, total, am, lm_logp, best[0], best[1], skipped, word_logp, n_words, n_oov)
+            return res if unit_lm is None else NBestRescoredWordsUnits(*res, unit_logp)
+        res = NBestRescored(order, total, am, lm_logp, best[0], best[1], skipped)
+        return res if unit_lm is None else NBestRescoredUnits(*res, unit_logp)
 
     def mbr_from_list(self, nb, score, vocab=None, risk_unit="char", word_delimiter=None, posterior_scale=1.0, max_hyp_len=None):
         """Minimum-Bayes-risk choice over an N-best list the caller already holds: ``nb`` a ``hipops.CTCNBest`` (N <= 128), ``score``
@@ -259,18 +299,20 @@ class CTCDecoder:
 
     def mbr_decode(self, log_probs, lengths=None, beam_size=16, nbest=16, risk_unit="char", word_delimiter=None, acoustic="ctc",
                    posterior_scale=1.0, lm=_UNSET, lm_alpha=None, lm_beta=None, am_weight=1.0, max_hyp_len=None, blank=0,
-                   word_lm=None, word_lm_alpha=0.0, word_lm_beta=0.0):
+                   word_lm=None, word_lm_alpha=0.0, word_lm_beta=0.0, unit_lm=None, unit_lm_alpha=0.0, unit_lm_beta=0.0):
         """Minimum-Bayes-risk decoding: the N-best search (``decode_batch(nbest=)``, with the decoder's first-pass LM if it has
         one), the score of every hypothesis (``rescore(...).total`` with ``acoustic`` / ``lm`` / ``lm_alpha`` / ``lm_beta`` /
         ``am_weight`` as ``rescore`` takes them: without an LM the exact CTC -log p, or the first-pass score), the distances inside
         each list and the selection (``mbr_from_list``), in that order.  log_probs (T,B,V) GPU tensor, nbest <= beam_size, nbest <= 128.
         word_lm / word_lm_alpha / word_lm_beta go to ``rescore`` (words split at ``word_delimiter``, as the word risk): the
-        posterior then comes from the totals with the word LM in them.  Returns ``MBRDecoded``."""
+        posterior then comes from the totals with the word LM in them; unit_lm / unit_lm_alpha / unit_lm_beta likewise (a
+        ``lm.UnitNgramLM`` in the second pass, wide lists included).  Returns ``MBRDecoded``."""
         T, B, V = log_probs.shape
         nb = self.decode_batch(log_probs, lengths, beam_size=beam_size, blank=blank, nbest=int(nbest))
         rs = self.rescore(log_probs, lengths, nb, lm=lm, lm_alpha=lm_alpha, lm_beta=lm_beta, acoustic=acoustic, am_weight=am_weight,
                           max_hyp_len=max_hyp_len, blank=blank, word_lm=word_lm, word_lm_alpha=word_lm_alpha,
-                          word_lm_beta=word_lm_beta, word_delimiter=word_delimiter)
+                          word_lm_beta=word_lm_beta, word_delimiter=word_delimiter, unit_lm=unit_lm, unit_lm_alpha=unit_lm_alpha,
+                          unit_lm_beta=unit_lm_beta)
         return self.mbr_from_list(nb, rs.total, vocab=V, risk_unit=risk_unit, word_delimiter=word_delimiter,
                                   posterior_scale=posterior_scale, max_hyp_len=max_hyp_len)
 

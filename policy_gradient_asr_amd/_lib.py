@@ -106,6 +106,12 @@ SIGNATURES = {
     "pgasr_ctc_beam_search_wide": (C.c_int, [c_ptr, C.c_int, C.c_longlong, C.c_longlong, c_i32p, C.c_int, C.c_int, C.c_int,
                                              C.c_int, C.c_int, C.c_int, C.c_int, c_i32p, C.c_int, c_i32p, c_ptr, c_i32p, c_i32p,
                                              c_ptr, C.c_size_t, c_ptr]),
+    "pgasr_beam_wide_lm_workspace_bytes": (C.c_size_t, [C.c_int] * 4),
+    "pgasr_ctc_beam_search_wide_lm": (C.c_int, [c_ptr, C.c_int, C.c_longlong, C.c_longlong, c_i32p, C.c_int, C.c_int, C.c_int,
+                                                C.c_int, C.c_int, C.c_int, C.c_int, c_i32p, C.c_int, c_i32p, c_ptr, c_i32p, c_i32p,
+                                                c_ptr, C.c_size_t, c_ptr, c_ptr, C.c_double, C.c_double]),
+    "pgasr_nbest_unit_lm_score": (C.c_int, [c_i32p, C.c_int, c_i32p, c_i32p, C.c_int, C.c_int, C.c_int, C.c_int, c_ptr, c_ptr,
+                                            c_ptr]),
     "pgasr_nbest_rescore": (C.c_int, [c_i32p, C.c_int, c_i32p, c_i32p, c_ptr, C.c_int, C.c_int, C.c_int, C.c_int, c_f32p, C.c_int,
                                       C.c_double, C.c_double, C.c_double, c_ptr, c_ptr, c_i32p, c_ptr]),
     "pgasr_nbest_pair_dist": (C.c_int, [c_i32p, C.c_int, c_i32p, c_i32p, C.c_int, C.c_int, C.c_int, C.c_int, c_i32p, c_ptr]),
@@ -216,6 +222,12 @@ class WordLMTables(C.Structure):
     _fields_ = [("word_pool", C.c_void_p), ("word_off", C.c_void_p), ("word_slots", C.c_void_p), ("uni_logp", C.c_void_p),
                 ("uni_bow", C.c_void_p), ("ngram_slots", C.c_void_p), ("order", C.c_int32), ("n_words", C.c_int32),
                 ("word_cap", C.c_int32), ("ngram_cap", C.c_int32), ("pool_bytes", C.c_int32), ("reserved", C.c_int32)]
+
+
+class UnitLMTables(C.Structure):
+    """pgasr_unit_lm_tables (include/pgasr_hip.h, A7-WIDE-LM): device addresses and sizes, a host struct passed with C.byref."""
+    _fields_ = [("states", C.c_void_p), ("succ", C.c_void_p), ("order", C.c_int32), ("vocab", C.c_int32), ("blank", C.c_int32),
+                ("n_states", C.c_int32), ("n_succ", C.c_int32), ("start", C.c_int32)]
 
 
 class PgasrError(RuntimeError):

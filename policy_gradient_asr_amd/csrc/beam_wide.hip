@@ -25,8 +25,10 @@
 //     at or above that cut -- exactly min(beam, all) by uniqueness of the key -- are then listed and sorted.  Both paths rank by the
 //     same key, so both are exact and equal.
 // Every loop is bounded by construction: hash probes by the table size, ancestor walks by lengths[b], radix passes by the key width.
+// With a back-off unit n-gram model (pgasr_ctc_beam_search_wide_lm) the same kernel fuses its scores in; see WideLm below.
 #include "common.h"
 #include "beam_core.h"
+#include "unit_lm.h"
 #include <cmath>
 
 namespace {
@@ -65,14 +67,65 @@ struct WideLds {
     int nb, nodes, total, done, need, counting;
 };
 
-template <typename TIn, bool FAST>
+// Fusion of a back-off unit n-gram model (LM = true, pgasr_ctc_beam_search_wide_lm; include/pgasr_hip.h, A7-WIDE-LM): A7-LM's algebra --
+// every term that enters a prefix by an extension with a non-blank s gets w = alpha * (double)lp32(ctx(prefix), s) + beta added, the
+// merged term of a stay candidate with its parent's context -- over the packed tables of lm.UnitNgramLM.  A back-off chain per candidate
+// would be a divergent pointer chase over up to 131072 candidates a frame, so every beam entry owns a dense ROW of its LM state in the
+// global workspace: lp[s] = lp32(state, s) and next[s] = the state after s, V words each.
+//   * 2 * K rows per utterance, reached through a per-entry slot: an entry that stays keeps its row; only a winner that is an extension
+//     takes a free one (the rows of the stay winners are marked, the e-th extension takes the e-th unmarked row);
+//   * the workgroup fills the new rows level by level: thread r walks its winner's back-off chain once (at most `order` states) and
+//     keeps the top-down prefix sums of the bows -- the contractual order --, then the states' successor lists are scattered over the
+//     rows as float32(sum + logp), the empty context (all V-1 unigrams, kept in LDS for the whole call) first, the longest context
+//     last, a barrier between levels; the lists are sorted by symbol, so the reads are coalesced;
+//   * a candidate then costs one fp32 load of an L2-resident row beside the frame's log-prob -- the words of entry j + 1 are loaded
+//     while entry j's candidates are scored --; a winner's new state is next[s].
+// The threshold's extension candidate of an entry is the one of largest frame[s] + w: a candidate that exists, its image with its own
+// w in it, so theta stays a valid lower bound.  The model's arguments are a parameter pack behind the kernel's own, empty without a model
+// (LM = false): those instantiations keep their argument list and carry none of this.
+constexpr int WIDE_LM_ORDER_MAX = 5;
+template <bool LM> struct WideLm {};
+template <> struct WideLm<true> {
+    const int4* states;      // (n_states) {bow bits, back-off state, first successor, one past the last}; state 0 = the empty context
+    const int4* succ;        // (n_succ) {symbol, logp bits, next state, 0}, a state's successors consecutive and ascending in the symbol
+    int n_states, n_succ, start, order;
+    float* rows;             // [B][2 K][2][V]: lp, then next (as int)
+    double alpha, beta;
+};
+struct WideLmLds {
+    double acc[WIDE_KMAX][WIDE_LM_ORDER_MAX];   // acc[r][p]: the bows of chain[r][0 .. p-1], summed in that order
+    int chain[WIDE_KMAX][WIDE_LM_ORDER_MAX];    // the back-off chain of winner r's state, the state itself first, state 0 last
+    int depth[WIDE_KMAX];
+    int st[2][WIDE_KMAX], row[2][WIDE_KMAX];    // an entry's LM state and the slot of its row
+    float own[2][WIDE_KMAX];                    // lp32(ctx(parent prefix), last): the word of the entry's own last emission
+    int isext[WIDE_KMAX];
+    int used[2 * WIDE_KMAX];
+    float uni_lp[WIDE_VMAX];                    // the successors of the empty context by symbol: every row starts from these
+    int uni_next[WIDE_VMAX];
+    unsigned long long freemask[WIDE_THREADS / 64], extmask[WIDE_THREADS / 64];
+};
+constexpr size_t WIDE_LM_LDS_OFFSET = (sizeof(WideLds) + 15) / 16 * 16;
+
+template <bool FAST> __device__ __forceinline__ double wide_ext_w(double pbj, double pnbj, double ps, bool rep, double w) {
+    const double eb = (pbj + ps) + w, en = (pnbj + ps) + w;
+    return rep ? lse2x<FAST>(-INFINITY, eb) : lse3x<FAST>(-INFINITY, eb, en);
+}
+
+// LmArg: nothing (the search of A7-WIDE: its argument list, and with it its code, is what it was without the model) or WideLm<true>
+__device__ __forceinline__ WideLm<false> wide_lm_of() { return {}; }
+__device__ __forceinline__ const WideLm<true>& wide_lm_of(const WideLm<true>& lm) { return lm; }
+
+template <typename TIn, bool FAST, typename... LmArg>
 __global__ __launch_bounds__(WIDE_THREADS) void beam_wide_kernel(
     const TIn* __restrict__ lp, long long stride_t, long long stride_b, const int32_t* __restrict__ lengths,
     int T, int V, int K, int blank, int collapse, int force_counting, WideWs ws, int nbest, int tok_stride,
     int32_t* __restrict__ out_tokens, int32_t* __restrict__ out_len, double* __restrict__ out_score,
-    int32_t* __restrict__ out_count, int32_t* __restrict__ out_counting) {
+    int32_t* __restrict__ out_count, int32_t* __restrict__ out_counting, const LmArg... lmarg) {
+    constexpr bool LM = sizeof...(LmArg) != 0;
+    [[maybe_unused]] const auto& lm = wide_lm_of(lmarg...);
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     WideLds& L = *reinterpret_cast<WideLds*>(smem);
+    [[maybe_unused]] WideLmLds& M = *reinterpret_cast<WideLmLds*>(smem + WIDE_LM_LDS_OFFSET);
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     int Tb = lengths ? lengths[b] : T; Tb = Tb < 0 ? 0 : (Tb > T ? T : Tb);
     const int W = (V + 31) >> 5;                          // bitmap words per entry
@@ -84,8 +137,89 @@ __global__ __launch_bounds__(WIDE_THREADS) void beam_wide_kernel(
         L.nb = 1; L.nodes = 1; L.counting = 0;
         L.id[0][0] = 0; L.last[0][0] = -1; L.par[0][0] = -1; L.pb[0][0] = 0.0; L.pnb[0][0] = -INFINITY;
         nodes[0] = 0xFFFFFFFFu;
+        if constexpr (LM) { M.st[0][0] = lm.start; M.own[0][0] = 0.0f; M.isext[0] = 1; }
     }
     __syncthreads();
+    [[maybe_unused]] float* lmrows = nullptr;
+    // the rows of the extension winners among the n entries of buffer `buf` (M.isext; M.st set, the stay winners' M.row set): take
+    // free slots, walk the chains, scatter the lists.  Called by every thread; ends with a barrier.
+    [[maybe_unused]] auto fill_rows = [&](int buf, int n) {
+        if constexpr (LM) {
+            M.used[tid] = 0;                                                      // 2 * WIDE_KMAX == WIDE_THREADS
+            __syncthreads();
+            const bool ext = tid < n && M.isext[tid];
+            if (tid < n && !ext) M.used[M.row[buf][tid]] = 1;
+            __syncthreads();
+            const unsigned long long fm = __ballot(tid < 2 * K && !M.used[tid]), em = __ballot(ext);
+            if (lane == 0) { M.freemask[wave] = fm; M.extmask[wave] = em; }
+            __syncthreads();
+            if (ext) {
+                int e = __popcll(M.extmask[wave] & ((1ull << lane) - 1ull));      // rank among the extension winners
+                for (int w = 0; w < wave; ++w) e += __popcll(M.extmask[w]);
+                int slot = 0;                                                     // the e-th free slot: at most K are marked, so one exists
+                for (int w = 0; w < WIDE_THREADS / 64; ++w) {
+                    unsigned long long m = M.freemask[w];
+                    const int c = __popcll(m);
+                    if (e >= c) { e -= c; continue; }
+                    for (int k = 0; k < e; ++k) m &= m - 1ull;
+                    slot = 64 * w + __ffsll((long long)m) - 1;
+                    break;
+                }
+                M.row[buf][tid] = slot;
+                int s = M.st[buf][tid];
+                s = (s < 0 || s >= lm.n_states) ? 0 : s;
+                double a = 0.0;
+                int d = 0;
+                for (; d < WIDE_LM_ORDER_MAX; ++d) {                              // top-down: the state itself, then ever shorter contexts
+                    if (d == WIDE_LM_ORDER_MAX - 1) s = 0;                        // a chain has at most `order` states; never walk past that
+                    M.chain[tid][d] = s; M.acc[tid][d] = a;
+                    if (s == 0) { ++d; break; }
+                    const int4 rec = lm.states[s];
+                    a = a + (double)__int_as_float(rec.x);
+                    s = (rec.y < 0 || rec.y >= lm.n_states) ? 0 : rec.y;
+                }
+                M.depth[tid] = d;
+            }
+            __syncthreads();
+            for (int r = wave; r < n; r += WIDE_THREADS / 64) {                   // the empty context: all V-1 unigrams, from LDS
+                if (!M.isext[r]) continue;
+                const double a = M.acc[r][M.depth[r] - 1];
+                float* rl = lmrows + (size_t)M.row[buf][r] * 2 * V;
+                int* rn = reinterpret_cast<int*>(rl + V);
+                for (int s = lane; s < V; s += 64) { rl[s] = (float)(a + (double)M.uni_lp[s]); rn[s] = M.uni_next[s]; }
+            }
+            __syncthreads();
+            for (int q = 1; q < lm.order; ++q) {                                  // level q above the empty context
+                for (int r = wave; r < n; r += WIDE_THREADS / 64) {
+                    if (!M.isext[r] || q >= M.depth[r]) continue;
+                    const int p = M.depth[r] - 1 - q;
+                    const int4 rec = lm.states[M.chain[r][p]];
+                    const double a = M.acc[r][p];
+                    const int lo = rec.z < 0 ? 0 : rec.z, hi = rec.w > lm.n_succ ? lm.n_succ : rec.w;
+                    float* rl = lmrows + (size_t)M.row[buf][r] * 2 * V;
+                    int* rn = reinterpret_cast<int*>(rl + V);
+                    for (int i = lo + lane; i < hi; i += 64) {
+                        const int4 e = lm.succ[i];
+                        if ((unsigned)e.x < (unsigned)V) { rl[e.x] = (float)(a + (double)__int_as_float(e.y)); rn[e.x] = e.z; }
+                    }
+                }
+                __syncthreads();
+            }
+        }
+    };
+    if constexpr (LM) {
+        lmrows = lm.rows + (size_t)b * 2 * K * 2 * V;
+        for (int s = tid; s < WIDE_VMAX; s += WIDE_THREADS) { M.uni_lp[s] = -INFINITY; M.uni_next[s] = 0; }
+        __syncthreads();
+        const int4 root = lm.states[0];
+        const int lo = root.z < 0 ? 0 : root.z, hi = root.w > lm.n_succ ? lm.n_succ : root.w;
+        for (int i = lo + tid; i < hi; i += WIDE_THREADS) {
+            const int4 e = lm.succ[i];
+            if ((unsigned)e.x < (unsigned)V) { M.uni_lp[e.x] = __int_as_float(e.y); M.uni_next[e.x] = e.z; }
+        }
+        __syncthreads();
+        fill_rows(0, 1);
+    }
     int cur = 0;
     for (int t = 0; t < Tb; ++t) {
         const int nb = L.nb;
@@ -119,7 +253,11 @@ __global__ __launch_bounds__(WIDE_THREADS) void beam_wide_kernel(
                 const unsigned t_own = 2u * (unsigned)(lj * nb + j) + 1u;
                 time = t_own < time ? t_own : time;
                 if (i >= 0) {
-                    const double e1 = cpb[i] + pl, e2 = cpnb[i] + pl;             // extension of parent i by lj (:90-96): touched first in iteration (lj, i)
+                    double e1 = cpb[i] + pl, e2 = cpnb[i] + pl;                   // extension of parent i by lj (:90-96): touched first in iteration (lj, i)
+                    if constexpr (LM) {                                           // with the parent's context: the entry's own word
+                        const double w = __dadd_rn(__dmul_rn(lm.alpha, (double)M.own[cur][j]), lm.beta);
+                        e1 += w; e2 += w;
+                    }
                     const bool rep = (clast[i] == lj);
                     if (i < j) {
                         npnb = rep ? lse2x<FAST>(npnb, e1) : lse3x<FAST>(npnb, e1, e2);
@@ -143,6 +281,30 @@ __global__ __launch_bounds__(WIDE_THREADS) void beam_wide_kernel(
             double best = -INFINITY;
             bool found = false;
             const int lj = clast[j];
+            if constexpr (LM) {      // the symbol of largest frame[s] + w (the lowest such s): that candidate's image, its w included
+                const float* rl = lmrows + (size_t)M.row[cur][j] * 2 * V;
+                int bs = -1;
+                for (int s = lane; s < V; s += 64) {
+                    if (s == blank || s == lj || ((L.bitmap[j * W + (s >> 5)] >> (s & 31)) & 1u)) continue;
+                    const double v = L.frame[s] + __dadd_rn(__dmul_rn(lm.alpha, (double)rl[s]), lm.beta);
+                    if (bs < 0 || v > best) { best = v; bs = s; }
+                }
+                if (bs < 0) best = -INFINITY;
+                const bool any = __ballot(bs >= 0) != 0ull;
+                double top = best;
+                for (int o = 32; o > 0; o >>= 1) top = fmax(top, __shfl_xor(top, o));
+                const unsigned long long who = __ballot(bs >= 0 && best == top);
+                const int s1 = __shfl(bs, who ? __ffsll((long long)who) - 1 : 0);
+                if (lane == 0) {
+                    unsigned long long img = 0ull;
+                    if (any && s1 >= 0) {                                         // s1 < 0: every sum is NaN or none compares equal -- no bound from this entry
+                        const double w = __dadd_rn(__dmul_rn(lm.alpha, (double)rl[s1]), lm.beta);
+                        img = ordered_key(lse2x<FAST>(-INFINITY, wide_ext_w<FAST>(cpb[j], cpnb[j], L.frame[s1], false, w)));
+                    }
+                    L.tkeys[nb + j] = img;
+                }
+                continue;
+            }
             for (int s = lane; s < V; s += 64) {
                 if (s == blank || s == lj || ((L.bitmap[j * W + (s >> 5)] >> (s & 31)) & 1u)) continue;
                 const double v = L.frame[s];
@@ -171,6 +333,37 @@ __global__ __launch_bounds__(WIDE_THREADS) void beam_wide_kernel(
 
         // every candidate of the frame, visited by all threads in step (the appends are wave-aggregated): f(valid, image, time, cand)
         auto for_each_candidate = [&](auto&& f) {
+            if constexpr (LM) {      // the same visits; entry j + 1's words are loaded while entry j's candidates are scored
+                constexpr int NV = WIDE_VMAX / WIDE_THREADS;
+                float wn[NV];
+                auto load_words = [&](int j) {
+                    const float* rl = lmrows + (size_t)M.row[cur][j] * 2 * V;
+#pragma unroll
+                    for (int k = 0; k < NV; ++k) { const int s = k * WIDE_THREADS + tid; wn[k] = s < V ? rl[s] : 0.0f; }
+                };
+                if (nb > 0) load_words(0);
+                for (int j = 0; j < nb; ++j) {
+                    const double pbj = cpb[j], pnbj = cpnb[j];
+                    const int lj = clast[j];
+                    float wc[NV];
+#pragma unroll
+                    for (int k = 0; k < NV; ++k) wc[k] = wn[k];
+                    if (j + 1 < nb) load_words(j + 1);
+#pragma unroll
+                    for (int k = 0; k < NV; ++k) {
+                        if (k * WIDE_THREADS >= V) break;
+                        const int s = k * WIDE_THREADS + tid;
+                        bool valid = s < V && s != blank;
+                        if (valid) valid = !((L.bitmap[j * W + (s >> 5)] >> (s & 31)) & 1u);
+                        unsigned long long img = 0ull;
+                        if (valid) {
+                            const double w = __dadd_rn(__dmul_rn(lm.alpha, (double)wc[k]), lm.beta);
+                            img = ordered_key(lse2x<FAST>(-INFINITY, wide_ext_w<FAST>(pbj, pnbj, L.frame[s], s == lj, w)));
+                        }
+                        f(valid, img, 2u * (unsigned)(s * nb + j), (unsigned)(j * V + s));
+                    }
+                }
+            } else
             for (int j = 0; j < nb; ++j) {
                 const double pbj = cpb[j], pnbj = cpnb[j];
                 const int lj = clast[j];
@@ -272,9 +465,17 @@ __global__ __launch_bounds__(WIDE_THREADS) void beam_wide_kernel(
                 const int j = (int)(it.cand & ~WIDE_STAY);
                 L.pb[nxt][tid] = L.st_pb[j]; L.pnb[nxt][tid] = L.st_pnb[j];
                 L.id[nxt][tid] = cid[j]; L.last[nxt][tid] = clast[j]; L.par[nxt][tid] = cpar[j];
+                if constexpr (LM) { M.st[nxt][tid] = M.st[cur][j]; M.row[nxt][tid] = M.row[cur][j]; M.own[nxt][tid] = M.own[cur][j]; M.isext[tid] = 0; }
             } else {
                 const int j = (int)it.cand / V, s = (int)it.cand - j * V;
                 L.pb[nxt][tid] = -INFINITY;
+                if constexpr (LM) {      // the candidate's score as its key had it; its word becomes the entry's own, next[s] its state
+                    const float* rl = lmrows + (size_t)M.row[cur][j] * 2 * V;
+                    const float word = rl[s];
+                    const double w = __dadd_rn(__dmul_rn(lm.alpha, (double)word), lm.beta);
+                    L.pnb[nxt][tid] = wide_ext_w<FAST>(cpb[j], cpnb[j], L.frame[s], s == clast[j], w);
+                    M.st[nxt][tid] = reinterpret_cast<const int*>(rl + V)[s]; M.own[nxt][tid] = word; M.isext[tid] = 1;
+                } else
                 L.pnb[nxt][tid] = wide_ext<FAST>(cpb[j], cpnb[j], L.frame[s], s == clast[j]);
                 // canonical node for (id[j], s): look up, else create
                 L.id[nxt][tid] = trie_find_or_create<WIDE_SYM_BITS>(table, nodes, ws.H, ws.NN, &L.nodes, cid[j], s);
@@ -283,12 +484,21 @@ __global__ __launch_bounds__(WIDE_THREADS) void beam_wide_kernel(
         }
         if (tid == 0) L.nb = nnew;
         __syncthreads();
+        if constexpr (LM) fill_rows(nxt, nnew);
         cur = nxt;
     }
     // ---- result: row r is entry r of the final, ranked beam; L.pidx is free after the frame loop ----
     nbest_tail<WIDE_SYM_BITS, WIDE_THREADS, FAST>(nodes, ws.NN, Tb, b, tid, nbest, tok_stride, collapse, L.nb, L.id[cur], L.pb[cur], L.pnb[cur],
                                                   L.pidx, out_tokens, out_len, out_score, out_count);
     if (tid == 0 && out_counting) out_counting[b] = L.counting;
+}
+
+// the row cache behind the trie in the workspace: [B][2 beam][2][V] words
+inline size_t wide_lm_ws_layout(int T, int B, int V, int beam, WideWs* ws, float** rows, char* base) {
+    size_t off = trie_ws_layout<WIDE_SYM_BITS>(T, B, beam, ws, base);
+    if (rows) *rows = (float*)(base + off);
+    off += (size_t)B * 2 * (size_t)beam * 2 * (size_t)V * sizeof(float);
+    return (off + 255) / 256 * 256;
 }
 
 }  // namespace
@@ -324,6 +534,51 @@ extern "C" int pgasr_ctc_beam_search_wide(const void* log_probs, int is_f64, lon
         PGASR_LAUNCH_KERNEL((beam_wide_kernel<TIN, FAST>), dim3(B), dim3(WIDE_THREADS), lds, st, (const TIN*)log_probs, stride_t, \
                            stride_b, lengths, T, V, beam, blank, flags & 1, (flags & 32) ? 1 : 0, ws, nbest, tok_stride,          \
                            out_tokens, out_len, out_score, out_count, out_counting_frames);                                       \
+    }
+    if (is_f64) WIDE_LAUNCH(double, false) else WIDE_LAUNCH(float, true)
+#undef WIDE_LAUNCH
+    PGASR_CHECK_LAUNCH();
+    return PGASR_OK;
+}
+
+extern "C" size_t pgasr_beam_wide_lm_workspace_bytes(int T, int B, int V, int beam) {
+    if (T <= 0 || B <= 0 || V <= 0 || beam <= 0) return 0;
+    return wide_lm_ws_layout(T, B, V, beam, nullptr, nullptr, nullptr);
+}
+
+extern "C" int pgasr_ctc_beam_search_wide_lm(const void* log_probs, int is_f64, long long stride_t, long long stride_b,
+                                             const int32_t* lengths, int T, int B, int V, int beam, int blank, int flags,
+                                             int nbest, int32_t* out_tokens, int tok_stride, int32_t* out_len, double* out_score,
+                                             int32_t* out_count, int32_t* out_counting_frames,
+                                             void* workspace, size_t workspace_bytes, void* stream,
+                                             const pgasr_unit_lm_tables* tables, double lm_alpha, double lm_beta) {
+    // pgasr_ctc_beam_search_wide's checks in its order, the model's where that entry checks its flags; nothing below touches HIP
+    // until every check has passed
+    WideWs ws;
+    if (const int st = beam_check_args(log_probs, out_tokens, out_len, out_score, T, B, V, beam, blank, WIDE_VMAX, WIDE_KMAX,
+                                       [&] {
+                                           const bool bad = (flags & ~(1 | 32)) || nbest < 1 || nbest > beam || tok_stride < T || !out_count;
+                                           if (bad) return (int)PGASR_ERR_INVALID_ARG;
+                                           return unit_lm::check_tables(tables, V, blank, lm_alpha, lm_beta);
+                                       },
+                                       workspace, workspace_bytes, &ws)) return st;
+    WideLm<true> lm;
+    if (workspace_bytes < wide_lm_ws_layout(T, B, V, beam, &ws, &lm.rows, (char*)workspace)) return PGASR_ERR_WORKSPACE;
+    lm.states = (const int4*)tables->states; lm.succ = (const int4*)tables->succ;
+    lm.n_states = tables->n_states; lm.n_succ = tables->n_succ; lm.start = tables->start; lm.order = tables->order;
+    lm.alpha = lm_alpha; lm.beta = lm_beta;
+    static_assert(WIDE_LM_LDS_OFFSET + sizeof(WideLmLds) <= 160 * 1024, "LDS");
+    hipStream_t st = (hipStream_t)stream;
+    if (hipMemsetAsync(ws.table, 0, (size_t)B * ws.H * sizeof(unsigned long long), st) != hipSuccess) return PGASR_ERR_LAUNCH;
+    const size_t lds = (WIDE_LM_LDS_OFFSET + sizeof(WideLmLds) + 15) / 16 * 16;
+#define WIDE_LAUNCH(TIN, FAST)                                                                                                    \
+    {                                                                                                                             \
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&beam_wide_kernel<TIN, FAST, WideLm<true>>),                      \
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                          \
+        PGASR_LAUNCH_KERNEL((beam_wide_kernel<TIN, FAST, WideLm<true>>), dim3(B), dim3(WIDE_THREADS), lds, st,                    \
+                           (const TIN*)log_probs,                                                                                 \
+                           stride_t, stride_b, lengths, T, V, beam, blank, flags & 1, (flags & 32) ? 1 : 0, ws, nbest, tok_stride, \
+                           out_tokens, out_len, out_score, out_count, out_counting_frames, lm);                                   \
     }
     if (is_f64) WIDE_LAUNCH(double, false) else WIDE_LAUNCH(float, true)
 #undef WIDE_LAUNCH

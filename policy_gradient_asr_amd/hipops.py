@@ -1588,7 +1588,17 @@ def ctc_beam_search_nbest(log_probs, lengths=None, beam=5, nbest=1, blank=0, col
 MAX_VOCAB_SEARCH_WIDE = 1024     # csrc/beam_wide.hip: the exact prefix beam search over rows of up to 1024 symbols
 
 
-def ctc_beam_search_wide(log_probs, lengths=None, beam=5, nbest=None, blank=0, collapse=False, counting=False, stats=False):
+def _unit_lm_check(unit_lm, V, blank):
+    """Refusals that need no device: the model's type, its vocabulary and its blank."""
+    if not hasattr(unit_lm, "device_tables") or not hasattr(unit_lm, "logp_sequence"):
+        raise ValueError("unit_lm: a lm.UnitNgramLM is wanted")
+    if unit_lm.vocab != V or unit_lm.blank != int(blank):
+        raise ValueError(f"unit_lm: the model is over {unit_lm.vocab} symbols with blank {unit_lm.blank}; the call has {V} symbols and "
+                         f"blank {int(blank)}")
+
+
+def ctc_beam_search_wide(log_probs, lengths=None, beam=5, nbest=None, blank=0, collapse=False, counting=False, stats=False,
+                         unit_lm=None, lm_alpha=0.0, lm_beta=0.0):
     """The exact prefix beam search over rows of up to MAX_VOCAB_SEARCH_WIDE = 1024 symbols (pgasr_ctc_beam_search_wide; narrower
     rows are taken too): log_probs (T,B,V) fp32 or fp64 as ``ctc_beam_search`` takes them, beam <= 128, no language model.
     nbest=None (default): the triple of ``ctc_beam_search`` -- tokens (B,T) int32, token_lengths (B) int32, score (B) float64.
@@ -1597,10 +1607,30 @@ def ctc_beam_search_wide(log_probs, lengths=None, beam=5, nbest=None, blank=0, c
     No host synchronisation.  collapse: collapse_fn on each hypothesis separately.
     counting: every frame takes the counting selection instead of the threshold list (the same result bit for bit; tests, timing).
     stats: the counting-frames tensor (B) int32 -- frames of each utterance that took the counting selection -- is returned as one
-    more value behind the result."""
+    more value behind the result.
+    unit_lm: None (default: the acoustic search, the kernels and bits it always had) or a ``lm.UnitNgramLM`` over the same V symbols
+    and blank: every extension by a non-blank s gets ``lm_alpha * ln p_lm(s | context) + lm_beta`` added (pgasr_ctc_beam_search_wide_lm;
+    include/pgasr_hip.h, A7-WIDE-LM) and the returned score is a FUSED score.  lm_alpha = lm_beta = 0 returns the words of the call
+    without a model."""
+    if unit_lm is not None:
+        _unit_lm_check(unit_lm, log_probs.shape[-1], blank)
     lib = _lib.load()
     T, B, V = _search_inputs(log_probs, lengths)
     N, dev = (1 if nbest is None else int(nbest)), log_probs.device
+    if unit_lm is not None:
+        tables = unit_lm.device_tables(dev)
+        ws = _workspace(lib.pgasr_beam_wide_lm_workspace_bytes(T, B, V, int(beam)), dev, "beam_wide")
+        tokens, tl, score, count = _nbest_outputs(N, B, T, dev)
+        frames = torch.empty(B, dtype=torch.int32, device=dev) if stats else None
+        with _timed("beam_search_wide_lm"):
+            st = lib.pgasr_ctc_beam_search_wide_lm(_p(log_probs), int(log_probs.dtype == torch.float64), log_probs.stride(0),
+                                                   log_probs.stride(1), _p(lengths), T, B, V, int(beam), int(blank),
+                                                   int(bool(collapse)) | (32 if counting else 0), N, _p(tokens), T, _p(tl), _p(score),
+                                                   _p(count), _p(frames), _p(ws), ws.numel(), _stream(), ctypes.byref(tables.struct),
+                                                   float(lm_alpha), float(lm_beta))
+        _lib.check(st, "pgasr_ctc_beam_search_wide_lm")
+        res = (tokens[0], tl[0], score[0]) if nbest is None else CTCNBest(tokens, tl, score, count)
+        return (res, frames) if stats else res
     ws = _workspace(lib.pgasr_beam_wide_workspace_bytes(T, B, V, int(beam)), dev, "beam_wide")
     tokens, tl, score, count = _nbest_outputs(N, B, T, dev)
     frames = torch.empty(B, dtype=torch.int32, device=dev) if stats else None
@@ -1700,6 +1730,26 @@ def nbest_word_lm_score(tokens, lengths, count, word_lm, delimiter):
                                            _p(word_logp), out[0].data_ptr(), out[1].data_ptr(), _stream())
     _lib.check(st, "pgasr_nbest_word_lm_score")
     return word_logp, out[0], out[1]
+
+
+def nbest_unit_lm_score(tokens, lengths, count, unit_lm):
+    """A back-off unit n-gram LM over N-best lists (pgasr_nbest_unit_lm_score; include/pgasr_hip.h, A7-WIDE-LM): tokens (N,B,stride) /
+    lengths (N,B) / count (B) int32 as the searches return them, ``unit_lm`` a ``lm.UnitNgramLM``.  Returns lm_logp (N,B) float64, no
+    host synchronisation: per hypothesis what ``unit_lm.logp_sequence`` returns, bit for bit; 0 in the rows beyond count, -inf for a
+    row holding the blank or a symbol outside the model's vocabulary.  N <= 128."""
+    _unit_lm_check(unit_lm, getattr(unit_lm, "vocab", 0), getattr(unit_lm, "blank", 0))
+    lib = _lib.load()
+    _req(tokens, torch.int32, "tokens"); _req(lengths, torch.int32, "lengths"); _req(count, torch.int32, "count")
+    if tokens.dim() != 3 or tuple(lengths.shape) != tuple(tokens.shape[:2]) or count.numel() != tokens.shape[1]:
+        raise _lib.PgasrError("nbest_unit_lm_score wants tokens (N,B,stride), lengths (N,B) and count (B)")
+    N, B, stride = tokens.shape
+    tables = unit_lm.device_tables(tokens.device)
+    lm_logp = torch.empty(N, B, dtype=torch.float64, device=tokens.device)
+    with _timed("nbest_unit_lm_score"):
+        st = lib.pgasr_nbest_unit_lm_score(_p(tokens), stride, _p(lengths), _p(count), N, B, unit_lm.vocab, unit_lm.blank,
+                                           ctypes.byref(tables.struct), _p(lm_logp), _stream())
+    _lib.check(st, "pgasr_nbest_unit_lm_score")
+    return lm_logp
 
 
 def nbest_combine_rank(base, word_logp, n_words, count, word_alpha=0.0, word_beta=0.0):

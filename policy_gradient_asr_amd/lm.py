@@ -7,7 +7,11 @@ inside a prefix, so it serves as the start-of-sentence pad: the context of a pre
 search reads the table on the device (``device_table``).
 
 ``WordNgramLM`` is the word-level model of the second pass: a back-off n-gram model (ARPA form, order <= 5) over words spelled in
-the acoustic alphabet, queried on the host by ``logp_sentence`` and on the device by csrc/word_lm.hip through ``device_tables``."""
+the acoustic alphabet, queried on the host by ``logp_sentence`` and on the device by csrc/word_lm.hip through ``device_tables``.
+
+``UnitNgramLM`` is the sparse model over the acoustic units themselves, for alphabets the dense table cannot hold (up to 1024
+symbols at order <= 5): a back-off n-gram model fused into the wide search (csrc/beam_wide.hip) and applied to N-best lists
+(csrc/unit_lm.hip) through ``device_tables``, queried on the host by ``logp`` / ``logp_sequence``."""
 import collections
 import math
 
@@ -590,4 +594,422 @@ class WordNgramLM:
                                    tensors["uni_logp"].data_ptr(), tensors["uni_bow"].data_ptr(), tensors["ngram_slots"].data_ptr(),
                                    self.order, self.n_words, p["word_slots"].size, p["ngram_slots"].shape[0], self.word_pool.size)
             t = self._device_tables[device] = WordLMDeviceTables(st, tensors)
+        return t
+
+
+# ------------------------------------------------------------------------------------------
+# Back-off n-gram model over the acoustic units themselves (csrc/beam_wide.hip with a model, csrc/unit_lm.hip; include/pgasr_hip.h,
+# section A7-WIDE-LM)
+# ------------------------------------------------------------------------------------------
+MAX_UNIT_VOCAB = 1024
+MAX_UNIT_ORDER = 5
+UnitLMDeviceTables = collections.namedtuple("UnitLMDeviceTables", "struct tensors")
+
+
+def _gram_keys(g, V):
+    """Rows of symbols -> their base-V number: ascending keys are lexicographic order (V**5 <= 2**50)."""
+    key = np.zeros(g.shape[0], dtype=np.int64)
+    for j in range(g.shape[1]):
+        key = key * V + g[:, j].astype(np.int64)
+    return key
+
+
+def _find_keys(keys, want):
+    """Index of every ``want`` in the ascending ``keys``, -1 where absent."""
+    if keys.size == 0 or want.size == 0:
+        return np.full(want.shape, -1, dtype=np.int64)
+    i = np.minimum(np.searchsorted(keys, want), keys.size - 1)
+    return np.where(keys[i] == want, i, -1)
+
+
+class UnitNgramLM:
+    """A back-off n-gram model of order 1 <= n <= 5 over the V <= 1024 ids of the acoustic alphabet (subword units or characters),
+    natural logs, fp32.  Unlike ``CharNgramLM`` it is sparse, so V = 1024 at order 5 is a model like any other.
+
+    The blank never occurs inside a prefix: it is the start-of-sentence symbol, exactly one of it (ARPA's <s>).  The context of a
+    prefix y is the last n-1 symbols of (blank,) + y -- shorter than n-1 near the start.  Stored k-grams are (c_1 .. c_{k-1}, s)
+    with s != blank; blank may stand only as c_1.  Every k-gram has ``logp`` and, below the top order, ``bow`` (0 where a file gives
+    none).  The unigram array has V rows, row = symbol: the row of the blank is <s> itself, whose logp is never read and whose bow
+    is the back-off weight of the context (blank,).  The context of every stored n-gram is itself stored.
+
+    The query is contractual (every device path returns its bits): acc = 0.0 in fp64, h = the context; if (h, s) is stored return
+    float32(acc + (double)logp[h, s]); else add (double)bow[h] where h is stored, drop the oldest symbol of h, and again.  The
+    sums run from the longest context to the shortest with ONE rounding to fp32, at the end.  ``logp_sequence`` is the fp64 sum in
+    index order of those fp32 values; there is no end-of-sentence term.
+
+    Arrays (canonical: the k-grams of an order in lexicographic order, so equal models have equal arrays):
+        ngrams[k-1] (M_k, k) int32, lp[k-1] / bw[k-1] (M_k,) fp32 (logp and bow) for k = 1 .. order; M_1 = V."""
+
+    def __init__(self, ngrams, logp, bow, vocab, blank=0):
+        order = len(ngrams)
+        if not 1 <= order <= MAX_UNIT_ORDER or len(logp) != order or len(bow) != order:
+            raise ValueError(f"a unit LM has order 1 .. {MAX_UNIT_ORDER} with one n-gram, logp and bow array per order (got {order})")
+        V, blank = int(vocab), int(blank)
+        if not 2 <= V <= MAX_UNIT_VOCAB:
+            raise ValueError(f"a unit LM is over 2 .. {MAX_UNIT_VOCAB} symbols, the blank included (got {V})")
+        if not 0 <= blank < V:
+            raise ValueError("blank must be a symbol of the vocabulary")
+        self.ngrams, self.lp, self.bw, self._keys = [], [], [], []
+        for k in range(1, order + 1):
+            g = np.ascontiguousarray(np.asarray(ngrams[k - 1]), dtype=np.int32).reshape(-1, k)
+            lp = np.ascontiguousarray(np.asarray(logp[k - 1]), dtype=np.float32).reshape(-1)
+            bw = np.ascontiguousarray(np.asarray(bow[k - 1]), dtype=np.float32).reshape(-1)
+            if lp.size != g.shape[0] or bw.size != g.shape[0]:
+                raise ValueError(f"order {k}: n-grams, logp and bow differ in length")
+            if g.size and (g.min() < 0 or g.max() >= V):
+                raise ValueError(f"order {k}: a symbol outside the vocabulary")
+            if k == 1:
+                if g.shape[0] != V or (g[:, 0] != np.arange(V)).any():
+                    raise ValueError("every symbol has a unigram, stored at its own id (the row of the blank is <s>): "
+                                     "a unigram is missing")
+                real = np.arange(V) != blank
+                if not (np.isfinite(lp[real]).all() and np.isfinite(bw).all()):
+                    raise ValueError("order 1: a non-finite logp or bow")
+            else:
+                if (g[:, 1:] == blank).any():
+                    raise ValueError(f"order {k}: the blank stands inside a context or is predicted; it may only be an n-gram's first symbol")
+                if not (np.isfinite(lp).all() and np.isfinite(bw).all()):
+                    raise ValueError(f"order {k}: a non-finite logp or bow")
+            key = _gram_keys(g, V)
+            if key.size > 1 and (np.diff(key) <= 0).any():
+                raise ValueError(f"order {k}: the n-grams are not in lexicographic order, or one is stored twice")
+            if k > 1 and (_find_keys(self._keys[k - 2], key // V) < 0).any():
+                raise ValueError(f"order {k}: an n-gram's context is not stored at order {k - 1}")
+            self.ngrams.append(g); self.lp.append(lp); self.bw.append(bw); self._keys.append(key)
+        if sum(g.shape[0] for g in self.ngrams) > MAX_NGRAMS:
+            raise ValueError(f"{sum(g.shape[0] for g in self.ngrams)} n-grams exceed the limit of 2**24; a model is never truncated")
+        self.order, self.vocab, self.blank = order, V, blank
+        self._table = None
+        self._packed = None
+        self._device_tables = {}
+
+    @property
+    def n_ngrams(self):
+        """Stored n-grams of all orders, <s> not counted."""
+        return sum(g.shape[0] for g in self.ngrams) - 1
+
+    # ---------------------------------------------------------------- construction
+    @classmethod
+    def _build(cls, grams, vocab, blank):
+        """grams[k-1]: dict from tuples of k symbols to (logp, bow) in natural log; arrays come out in canonical order."""
+        ngrams, logp, bow = [], [], []
+        for k in range(1, len(grams) + 1):
+            items = grams[k - 1]
+            g = np.array(list(items.keys()), dtype=np.int64).reshape(-1, k)
+            vals = np.array(list(items.values()), dtype=np.float64).reshape(-1, 2)
+            if g.size and (g.min() < 0 or g.max() >= int(vocab)):
+                raise ValueError(f"order {k}: a symbol outside the vocabulary")
+            idx = np.argsort(_gram_keys(g, int(vocab)), kind="stable")
+            ngrams.append(g[idx].astype(np.int32)); logp.append(vals[idx, 0].astype(np.float32)); bow.append(vals[idx, 1].astype(np.float32))
+        return cls(ngrams, logp, bow, vocab, blank=blank)
+
+    @staticmethod
+    def estimate(seqs_of_token_ids, vocab, order=3, blank=0, min_count=1):
+        """The fp64 estimate behind ``from_transcripts``: a list over k = 1 .. order of dicts {k-gram tuple: (ln p, ln bow)}.
+        Interpolated Witten-Bell smoothing written out in back-off form (the estimator of ``WordNgramLM.from_text`` and, context by
+        context, of ``CharNgramLM.from_transcripts``).  A transcript y is counted as (blank,) + y; a k-gram is every window of k of
+        these whose last entry is not the blank.  With c the counts and N1+(h.) the number of distinct symbols seen after h:
+            p_0(s)   = 1 / (V - 1)
+            p_k(s|h) = (c(hs) + N1+(h.) p_{k-1}(s|h')) / (c(h) + N1+(h.))   for a stored hs, h' = h without its oldest symbol
+            bow(h)   = ln(N1+(h.) / (c(h) + N1+(h.)))
+        Every one of the V-1 symbols gets a unigram (c = 0 where unseen).  A k-gram with k >= 2 seen fewer than ``min_count`` times
+        is not stored and takes no part in c and N1+: the model stays normalised."""
+        V, blank, order = int(vocab), int(blank), int(order)
+        if not 1 <= order <= MAX_UNIT_ORDER:
+            raise ValueError(f"a unit LM has order 1 .. {MAX_UNIT_ORDER} (got {order})")
+        if not 2 <= V <= MAX_UNIT_VOCAB:
+            raise ValueError(f"a unit LM is over 2 .. {MAX_UNIT_VOCAB} symbols, the blank included (got {V})")
+        if not 0 <= blank < V:
+            raise ValueError("blank must be a symbol of the vocabulary")
+        counts = [collections.defaultdict(collections.Counter) for _ in range(order)]      # counts[k-1][h][s]
+        for y in seqs_of_token_ids:
+            s = [blank] + [int(t) for t in y]
+            if any(t < 0 or t >= V or t == blank for t in s[1:]):
+                raise ValueError("transcripts must hold symbols of the vocabulary other than the blank")
+            for i in range(1, len(s)):
+                for k in range(1, min(order, i + 1) + 1):
+                    counts[k - 1][tuple(s[i - k + 1:i])][s[i]] += 1
+        for k in range(2, order + 1):
+            for h in list(counts[k - 1]):
+                kept = collections.Counter({w: c for w, c in counts[k - 1][h].items() if c >= int(min_count)})
+                if kept:
+                    counts[k - 1][h] = kept
+                else:
+                    del counts[k - 1][h]
+        p0 = 1.0 / (V - 1)
+        prob = [dict() for _ in range(order)]
+        bowp = [dict() for _ in range(order + 1)]
+
+        def lower(k, h, w):
+            if k == 0:
+                return p0
+            p = prob[k - 1].get(h + (w,))
+            if p is not None:
+                return p
+            return bowp[k - 1].get(h, 1.0) * lower(k - 1, h[1:], w)
+
+        symbols = [s for s in range(V) if s != blank]
+        for k in range(1, order + 1):
+            ctxs = counts[k - 1] if k > 1 else {(): counts[0].get((), collections.Counter())}
+            for h, cw in ctxs.items():
+                c, n1 = float(sum(cw.values())), float(len(cw))
+                if c == 0.0:                                         # no transcript at all: the uniform unigram
+                    for w in symbols:
+                        prob[0][(w,)] = p0
+                    continue
+                bowp[k - 1][h] = n1 / (c + n1)
+                for w in (list(cw) if k > 1 else symbols):
+                    prob[k - 1][h + (w,)] = (cw.get(w, 0) + n1 * lower(k - 1, h[1:], w)) / (c + n1)
+        grams = []
+        for k in range(1, order + 1):
+            items = {key: (math.log(p), math.log(bowp[k].get(key, 1.0)) if k < order else 0.0) for key, p in prob[k - 1].items()}
+            if k == 1:
+                items[(blank,)] = (ARPA_NEVER * _LN10, math.log(bowp[1].get((blank,), 1.0)) if order > 1 else 0.0)
+            grams.append(items)
+        return grams
+
+    @classmethod
+    def from_transcripts(cls, seqs_of_token_ids, vocab, order=3, blank=0, min_count=1):
+        """Sequences of token ids -> the model of ``estimate``, rounded to fp32."""
+        return cls._build(cls.estimate(seqs_of_token_ids, vocab, order=order, blank=blank, min_count=min_count), vocab, blank)
+
+    @classmethod
+    def from_text(cls, lines, units, order=3, blank=0, min_count=1):
+        """Lines of text -> token ids through ``units.encode`` (a ``SubwordUnits``: V = len(units), the blank is id 0)."""
+        return cls.from_transcripts([units.encode(ln.rstrip("\n")) for ln in lines], len(units), order=order, blank=blank,
+                                    min_count=min_count)
+
+    @classmethod
+    def from_arpa(cls, path, vocab, blank=0, names=None):
+        """Read the standard ARPA text format (log10 -> ln).  ``names``: the V symbols' spellings in the file (default: their
+        decimal ids; the entry of the blank is ignored); <s> is the blank.  Entries with </s> or <unk> are skipped: the model has
+        no end-of-sentence term and no unknown unit.  Any other name outside ``names`` raises."""
+        V, blank = int(vocab), int(blank)
+        names = [str(i) for i in range(V)] if names is None else [str(x) for x in names]
+        if len(names) != V:
+            raise ValueError(f"names must list the {V} symbols")
+        ids = {nm: i for i, nm in enumerate(names) if i != blank}
+        ids["<s>"] = blank
+        grams, k = [], 0
+        with open(path, "r") as fo:
+            for raw in fo:
+                ln = raw.strip()
+                if not ln or ln == "\\data\\" or ln.startswith("ngram "):
+                    continue
+                if ln == "\\end\\":
+                    break
+                if ln.startswith("\\") and ln.endswith("-grams:"):
+                    k = int(ln[1:-len("-grams:")])
+                    if k != len(grams) + 1 or k > MAX_UNIT_ORDER:
+                        raise ValueError(f"{path}: the sections must be 1-grams .. n-grams in order, n <= {MAX_UNIT_ORDER} (got {k})")
+                    grams.append({})
+                    continue
+                if k == 0:
+                    raise ValueError(f"{path}: {ln!r} stands before the first section")
+                f = ln.split()
+                if len(f) not in (k + 1, k + 2):
+                    raise ValueError(f"{path}: {ln!r} is no {k}-gram line")
+                if any(w in ("</s>", "<unk>") for w in f[1:k + 1]):
+                    continue
+                try:
+                    key = tuple(ids[w] for w in f[1:k + 1])
+                except KeyError as e:
+                    raise ValueError(f"{path}: {e.args[0]!r} is no symbol of the alphabet") from None
+                grams[k - 1][key] = (float(f[0]) * _LN10, float(f[k + 1]) * _LN10 if len(f) == k + 2 else 0.0)
+        if not grams:
+            raise ValueError(f"{path}: no n-gram section")
+        grams[0].setdefault((blank,), (ARPA_NEVER * _LN10, 0.0))
+        return cls._build(grams, V, blank)
+
+    def to_arpa(self, path, names=None):
+        """Write the standard ARPA text format (ln -> log10, 17 significant digits: ``from_arpa`` returns the same arrays)."""
+        names = [str(i) for i in range(self.vocab)] if names is None else [str(x) for x in names]
+        names = [("<s>" if i == self.blank else nm) for i, nm in enumerate(names)]
+        with open(path, "w") as fo:
+            fo.write("\\data\\\n")
+            for k in range(1, self.order + 1):
+                fo.write(f"ngram {k}={self.ngrams[k - 1].shape[0]}\n")
+            for k in range(1, self.order + 1):
+                fo.write(f"\n\\{k}-grams:\n")
+                g, lp, bw = self.ngrams[k - 1], self.lp[k - 1].astype(np.float64) / _LN10, self.bw[k - 1].astype(np.float64) / _LN10
+                for i in range(g.shape[0]):
+                    text = " ".join(names[j] for j in g[i])
+                    fo.write(f"{float(lp[i])!r}\t{text}" + (f"\t{float(bw[i])!r}\n" if k < self.order else "\n"))
+            fo.write("\n\\end\\\n")
+
+    # ---------------------------------------------------------------- persistence
+    def save(self, path):
+        arrays = {"order": np.int64(self.order), "vocab": np.int64(self.vocab), "blank": np.int64(self.blank)}
+        for k in range(1, self.order + 1):
+            arrays[f"ngrams_{k}"], arrays[f"logp_{k}"], arrays[f"bow_{k}"] = self.ngrams[k - 1], self.lp[k - 1], self.bw[k - 1]
+        with open(path, "wb") as fo:
+            np.savez(fo, **arrays)
+
+    @classmethod
+    def load(cls, path):
+        with np.load(path, allow_pickle=False) as z:
+            ks = range(1, int(z["order"]) + 1)
+            return cls([z[f"ngrams_{k}"] for k in ks], [z[f"logp_{k}"] for k in ks], [z[f"bow_{k}"] for k in ks],
+                       int(z["vocab"]), blank=int(z["blank"]))
+
+    # ---------------------------------------------------------------- queries (the host's own statement)
+    def _entries(self):
+        if self._table is None:
+            tab = {}
+            for k in range(1, self.order + 1):
+                g, lp, bw = self.ngrams[k - 1].tolist(), self.lp[k - 1].astype(np.float64).tolist(), \
+                    self.bw[k - 1].astype(np.float64).tolist()
+                top = k == self.order
+                for i, key in enumerate(g):
+                    tab[tuple(key)] = (lp[i], 0.0 if top else bw[i])
+            self._table = tab
+        return self._table
+
+    def context(self, prefix):
+        """The last order-1 symbols of (blank,) + prefix.  A prefix that holds the blank counts from its last blank on."""
+        y = [int(c) for c in prefix]
+        if self.blank in y:
+            y = y[len(y) - y[::-1].index(self.blank):]
+        h = [self.blank] + y
+        return tuple(h[max(0, len(h) - (self.order - 1)):]) if self.order > 1 else ()
+
+    def logp(self, context, s):
+        """ln p(s | context) by the contractual query, as a Python float holding an fp32 value.  ``context``: any sequence of
+        earlier symbols, most recent last (``context`` cuts it)."""
+        s = int(s)
+        if not 0 <= s < self.vocab or s == self.blank:
+            raise ValueError(f"symbol {s} is the blank or outside [0, {self.vocab})")
+        tab, h, acc = self._entries(), self.context(context), 0.0
+        while True:
+            e = tab.get(h + (s,))
+            if e is not None:
+                return float(np.float32(acc + e[0]))
+            c = tab.get(h) if h else None
+            if c is not None:
+                acc = acc + c[1]
+            h = h[1:]
+
+    def logp_sequence(self, tokens):
+        """The fp64 sum, in index order, of logp(tokens[:i], tokens[i]); 0.0 for no tokens."""
+        y, total = [int(t) for t in tokens], 0.0
+        for i, s in enumerate(y):
+            total = total + self.logp(y[max(0, i - self.order):i], s)
+        return total
+
+    # ---------------------------------------------------------------- the dense form
+    def to_dense(self):
+        """The equivalent ``CharNgramLM`` where V**order <= 2**25: table[ctx + (s,)] = logp(ctx from its last blank on, s), the
+        blank column 0 -- bit for bit what the query returns, so the dense kernels and their oracles apply."""
+        V, n = self.vocab, self.order
+        _check_size(V, n)
+        C = V ** (n - 1)
+        ctx = np.zeros((C, n - 1), dtype=np.int64)
+        rem = np.arange(C, dtype=np.int64)
+        for j in range(n - 2, -1, -1):
+            ctx[:, j] = rem % V
+            rem //= V
+        # eff[c]: symbols the query's context keeps -- from the last blank on, or all n-1 plus nothing (no blank: the oldest are cut)
+        isb = ctx == self.blank
+        lastb = np.where(isb.any(axis=1), (n - 2) - np.argmax(isb[:, ::-1], axis=1), -1) if n > 1 else np.full(C, -1)
+        eff = np.where(lastb >= 0, (n - 1) - lastb, n - 1)
+        table = np.zeros((C, V), dtype=np.float32)
+        done = np.zeros((C, V), dtype=bool)
+        acc = np.zeros(C, dtype=np.float64)
+        for k in range(n, 0, -1):                                 # k-grams: the context is the last k-1 symbols
+            if k == 1:
+                rows = np.zeros(C, dtype=np.int64)
+                live = np.ones(C, dtype=bool)
+            else:
+                live = eff >= k - 1
+                rows = _find_keys(self._keys[k - 2], _gram_keys(ctx[:, n - k:], V))
+                live &= rows >= 0
+            who = np.nonzero(live)[0]
+            if who.size == 0:
+                continue
+            if k == 1:
+                lo, hi = np.zeros(who.size, dtype=np.int64), np.full(who.size, V, dtype=np.int64)
+            else:
+                pk = self._keys[k - 1] // V
+                want = self._keys[k - 2][rows[who]]
+                lo, hi = np.searchsorted(pk, want, side="left"), np.searchsorted(pk, want, side="right")
+            cnt = hi - lo
+            c_of = np.repeat(who, cnt)
+            i_of = np.repeat(lo - np.concatenate([[0], np.cumsum(cnt)[:-1]]), cnt) + np.arange(int(cnt.sum()))
+            sym = self.ngrams[k - 1][i_of, k - 1].astype(np.int64)
+            val = (acc[c_of] + self.lp[k - 1][i_of].astype(np.float64)).astype(np.float32)
+            new = ~done[c_of, sym] & (sym != self.blank)
+            table[c_of[new], sym[new]] = val[new]
+            done[c_of[new], sym[new]] = True
+            if k > 1:
+                acc[who] = acc[who] + self.bw[k - 2][rows[who]].astype(np.float64)
+        table[:, self.blank] = 0.0
+        return CharNgramLM(table.reshape((V,) * n), n, self.blank)
+
+    # ---------------------------------------------------------------- the device's tables
+    def pack(self):
+        """The tables the kernels read, as numpy arrays (deterministic).  A STATE is a context the model stores: state 0 the empty
+        context, then every stored k-gram with k < order in canonical order (the unigram of symbol c is state 1 + c, <s> = the blank
+        included).  A SUCCESSOR is a stored n-gram, listed behind its context: the V-1 unigrams (blank left out) are the successors of
+        state 0, then the 2-grams, .., in canonical order, so one state's successors are consecutive and ascending in their symbol.
+            states (S, 4) int32: (bow bits, back-off state, first successor, one past the last).  The back-off state is the longest
+                proper suffix of the context that is a state (0 at the latest).
+            succ (M, 4) int32: (symbol, logp bits, next state, 0).  The next state is the longest suffix of context + symbol, of at
+                most order-1 symbols, that is a state: the n-gram itself below the top order.
+            start: the state of the empty prefix, (blank,) from order 2 on."""
+        if self._packed is not None:
+            return self._packed
+        V, n, blank = self.vocab, self.order, self.blank
+        sizes = [g.shape[0] for g in self.ngrams]
+        st_off = np.concatenate([[1], 1 + np.cumsum(sizes[:n - 1])]).astype(np.int64)       # st_off[k-1]: first state of the k-grams
+        S = int(st_off[-1]) if n > 1 else 1
+        su_off = np.concatenate([[0], np.cumsum([V - 1] + sizes[1:])]).astype(np.int64)     # su_off[k-1]: first successor of order k
+        M = int(su_off[-1])
+        states = np.zeros((S, 4), dtype=np.int32)
+        succ = np.zeros((M, 4), dtype=np.int32)
+
+        def longest_suffix(g, k, top):
+            """State of the longest suffix of the k-grams g with at most ``top`` symbols (0: none but the empty one)."""
+            out = np.zeros(g.shape[0], dtype=np.int64)
+            for j in range(1, min(top, k, n - 1) + 1):             # ascending: the longer suffix overwrites
+                r = _find_keys(self._keys[j - 1], _gram_keys(g[:, k - j:], V))
+                out = np.where(r >= 0, st_off[j - 1] + r, out)
+            return out
+
+        real = np.arange(V) != blank
+        states[0] = (0, 0, 0, V - 1)
+        succ[:V - 1, 0] = np.arange(V)[real]
+        succ[:V - 1, 1] = self.lp[0][real].view(np.int32)
+        succ[:V - 1, 2] = (1 + np.arange(V)[real]) if n > 1 else 0
+        for k in range(1, n + 1):
+            g = self.ngrams[k - 1].astype(np.int64)
+            if k < n:                                              # the k-grams as states
+                sl = slice(int(st_off[k - 1]), int(st_off[k - 1]) + sizes[k - 1])
+                states[sl, 0] = self.bw[k - 1].view(np.int32)
+                states[sl, 1] = longest_suffix(g, k, k - 1)
+                pk = self._keys[k] // V
+                states[sl, 2] = su_off[k] + np.searchsorted(pk, self._keys[k - 1], side="left")
+                states[sl, 3] = su_off[k] + np.searchsorted(pk, self._keys[k - 1], side="right")
+            if k >= 2:                                             # the k-grams as successors
+                sl = slice(int(su_off[k - 1]), int(su_off[k - 1]) + sizes[k - 1])
+                succ[sl, 0] = g[:, k - 1]
+                succ[sl, 1] = self.lp[k - 1].view(np.int32)
+                succ[sl, 2] = (st_off[k - 1] + np.arange(sizes[k - 1])) if k < n else longest_suffix(g, k, k - 1)
+        self._packed = {"states": states, "succ": succ, "start": int(1 + blank) if n > 1 else 0}
+        return self._packed
+
+    def device_tables(self, device):
+        """The packed tables as tensors on ``device`` and the POD struct of their addresses that the kernels take (made once per
+        device; the tensors live as long as the model)."""
+        import torch
+        from . import _lib
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        t = self._device_tables.get(device)
+        if t is None:
+            p = self.pack()
+            tensors = {k: torch.from_numpy(p[k]).to(device).contiguous() for k in ("states", "succ")}
+            st = _lib.UnitLMTables(tensors["states"].data_ptr(), tensors["succ"].data_ptr(), self.order, self.vocab, self.blank,
+                                   p["states"].shape[0], p["succ"].shape[0], p["start"])
+            t = self._device_tables[device] = UnitLMDeviceTables(st, tensors)
         return t

@@ -505,7 +505,8 @@ def predict(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=N
             test_dataset=None, n_feats=120, beam_size=5, features="mfcc", lm_path=None, lm_alpha=0.0, lm_beta=0.0,
             nbest=1, rescore_lm_path=None, rescore_alpha=0.0, rescore_beta=0.0, lm_fast=False, target_rate=None,
             mbr=False, mbr_unit="char", mbr_scale=1.0, rescore_word_lm_path=None, rescore_word_alpha=0.0, rescore_word_beta=0.0,
-            error_report=False, units_path=None, wide_beam=False, wide_second_pass=False):
+            error_report=False, units_path=None, wide_beam=False, wide_second_pass=False, unit_lm_path=None, unit_lm_alpha=0.0,
+            unit_lm_beta=0.0, rescore_unit_lm_path=None, rescore_unit_alpha=0.0, rescore_unit_beta=0.0):
     """model.py:277-339: load model_best.pth, forward, beam=5 prefix search (device side, batched),
     collapse_fn, CER/WER, predicted.txt.  Frames are cut by the FEATURE mask (the reference cuts the
     time axis by the target mask, model.py:322 -- a listed defect).  Returns (CER, WER).
@@ -559,12 +560,20 @@ def predict(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=N
     fills the total column of ``nbest.tsv``; the row of lowest total is the one written to predicted.txt and scored.  mbr=True is
     then allowed with mbr_unit="char" -- the risk is counted in units -- and writes ``mbr.tsv``; mbr_unit="word" raises (a unit may
     span a space), and so do lm_path, rescore_lm_path, rescore_word_lm_path and error_report, which stay refused for such an alphabet.
-    Alphabets of at most 64 symbols are not affected by the flag."""
+    Alphabets of at most 64 symbols are not affected by the flag.
+    unit_lm_path: None (default: everything above, nothing else) or a ``unit_lm.npz`` of ``build_unit_lm`` / ``UnitNgramLM.save``,
+    with wide_beam=True and beam_size > 0: the wide search adds unit_lm_alpha * ln p_lm(s | context) + unit_lm_beta to every
+    extension by a unit s (``CTCDecoder(wide_search=True, unit_lm=)``, a sparse back-off model over the units themselves); the
+    first-pass scores are then fused scores.  An alphabet of at most 64 symbols takes the wide entry with it too.
+    rescore_unit_lm_path: None (default: everything above, nothing else) or such a file, with nbest >= 2 (and wide_second_pass=True
+    for an alphabet of more than 64 symbols): the second pass also scores every hypothesis under the unit LM, total -=
+    rescore_unit_alpha * ln p_unit + rescore_unit_beta * length (``CTCDecoder.rescore(unit_lm=)``); with mbr=True the posterior comes
+    from these totals.  ``nbest.tsv`` then has one more column at its end: unit_logp."""
     import os
     import functools
     import torch.utils.data as tud
     from .CTCdecoder import CTCDecoder, collapse_fn, greedy_decode
-    from .lm import CharNgramLM, WordNgramLM
+    from .lm import CharNgramLM, UnitNgramLM, WordNgramLM
     from .data import Data
     from .data import collate_custom as _collate
     from .metrics import edit_dist_batch, evaluate, save_predictions
@@ -580,6 +589,12 @@ def predict(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=N
         raise ValueError("rescoring needs a list: give nbest >= 2 with rescore_lm_path")
     if rescore_word_lm_path is not None and nbest < 2:
         raise ValueError("rescoring needs a list: give nbest >= 2 with rescore_word_lm_path")
+    if rescore_unit_lm_path is not None and nbest < 2:
+        raise ValueError("rescoring needs a list: give nbest >= 2 with rescore_unit_lm_path")
+    if unit_lm_path is not None and (greedy or not wide_beam):
+        raise ValueError("unit_lm_path: the unit LM is fused into the wide beam search; give wide_beam=True and beam_size >= 1")
+    if unit_lm_path is not None and lm_path is not None:
+        raise ValueError("unit_lm_path: not together with lm_path -- one first-pass language model")
     if mbr and nbest < 2:
         raise ValueError("minimum-Bayes-risk decoding needs a list: give nbest >= 2 with mbr=True")
     if mbr and mbr_unit not in ("char", "word"):
@@ -609,7 +624,7 @@ def predict(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=N
     elif wide:
         for name, given in (("lm_path", lm_path is not None), ("rescore_lm_path", rescore_lm_path is not None),
                             ("rescore_word_lm_path", rescore_word_lm_path is not None), ("mbr", bool(mbr)),
-                            ("error_report", bool(error_report))):
+                            ("error_report", bool(error_report)), ("rescore_unit_lm_path", rescore_unit_lm_path is not None)):
             if given:
                 raise ValueError(f"{name}: not with the wide beam search ({len(alphabet)} > {hipops.MAX_VOCAB_NARROW} symbols), which "
                                  f"has no LM fusion, no second pass over its lists and no error report yet")
@@ -628,7 +643,21 @@ def predict(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=N
     to_text = collapse_fn if units_path is None else (lambda text: text)
     loader = tud.DataLoader(test_dataset, batch_size=batch_size, shuffle=False, collate_fn=collate_custom)
     lm = CharNgramLM.load(lm_path) if lm_path is not None else None
-    decoder = CTCDecoder(alphabet, lm=lm, lm_alpha=lm_alpha, lm_beta=lm_beta, fast_lm=bool(lm_fast), wide_search=wide)
+    unit_lm = rescore_unit_lm = None
+    for name, path in (("unit_lm_path", unit_lm_path), ("rescore_unit_lm_path", rescore_unit_lm_path)):
+        if path is not None:
+            m = UnitNgramLM.load(path)
+            if m.vocab != len(alphabet) or m.blank != 0:
+                raise ValueError(f"{name}: the model is over {m.vocab} symbols with blank {m.blank}; {alphabet_path} has "
+                                 f"{len(alphabet)} symbols and blank 0")
+            if name == "unit_lm_path":
+                unit_lm = m
+            else:
+                rescore_unit_lm = m
+    if unit_lm is not None:
+        decoder = CTCDecoder(alphabet, lm_alpha=unit_lm_alpha, lm_beta=unit_lm_beta, wide_search=True, unit_lm=unit_lm)
+    else:
+        decoder = CTCDecoder(alphabet, lm=lm, lm_alpha=lm_alpha, lm_beta=lm_beta, fast_lm=bool(lm_fast), wide_search=wide)
     list_text = to_text if wide else collapse_fn      # a wide list holds units: their concatenation is the text
     if mbr and mbr_unit == "word" and " " not in char2ind:
         raise ValueError("mbr_unit='word' needs an alphabet with the ' ' symbol")
@@ -638,6 +667,8 @@ def predict(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=N
     word_lm = WordNgramLM.load(rescore_word_lm_path) if rescore_word_lm_path is not None else None
     word_args = {} if word_lm is None else {"word_lm": word_lm, "word_lm_alpha": rescore_word_alpha, "word_lm_beta": rescore_word_beta,
                                             "word_delimiter": char2ind[" "]}
+    if rescore_unit_lm is not None:
+        word_args = dict(word_args, unit_lm=rescore_unit_lm, unit_lm_alpha=rescore_unit_alpha, unit_lm_beta=rescore_unit_beta)
     report = None
     if error_report:
         from .metrics import ErrorReport
@@ -654,13 +685,15 @@ def predict(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=N
             lp = Fh.LogSoftmaxFn.apply(logits)
             if nbest > 1:
                 nb = decoder.decode_batch(lp, in_len, beam_size=beam_size, nbest=nbest)
-                tok, tl, total, words = nb.tokens[0], nb.lengths[0], None, None
-                if rescore_lm is not None or word_lm is not None or second:
+                tok, tl, total, words, units_lp = nb.tokens[0], nb.lengths[0], None, None, None
+                if rescore_lm is not None or word_lm is not None or second or rescore_unit_lm is not None:
                     rs = decoder.rescore(lp, in_len, nb, lm=rescore_lm, lm_alpha=rescore_alpha if rescore_lm is not None else 0.0,
                                          lm_beta=rescore_beta if rescore_lm is not None else 0.0, **word_args)
                     tok, tl, total = rs.best_tokens, rs.best_len, rs.total.cpu()
                     if word_lm is not None:
                         words = (rs.word_logp.cpu(), rs.n_words.cpu(), rs.n_oov.cpu())
+                    if rescore_unit_lm is not None:
+                        units_lp = rs.unit_logp.cpu()
                 if mbr:
                     score = rs.total if total is not None else decoder.rescore(lp, in_len, nb, lm=None).total
                     md = decoder.mbr_from_list(nb, score, vocab=lp.shape[2], risk_unit=mbr_unit, posterior_scale=mbr_scale,
@@ -682,6 +715,8 @@ def predict(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=N
                         refs.append(target); hyps.append(text); owner.append(i)
                         extra = "" if words is None else "\t{:.6f}\t{}\t{}".format(float(words[0][r, i]), int(words[1][r, i]),
                                                                                   int(words[2][r, i]))
+                        if units_lp is not None:
+                            extra += "\t{:.6f}".format(float(units_lp[r, i]))
                         nbest_lines.append("{}\t{}\t{:.6f}\t{}\t{}{}\n".format(n + i, r, float(nscore[r, i]),
                                                                             "" if total is None else "{:.6f}".format(float(total[r, i])),
                                                                             text, extra))
@@ -836,4 +871,24 @@ def build_word_lm(corpus_path, order=3, min_count=1, out_path=None, train_datase
     lines = [train_dataset[i]["trans"] for i in range(len(train_dataset))]
     lm = WordNgramLM.from_text(lines, char2ind, order=order, min_count=min_count, delimiter=" ", blank=0)
     lm.save(out_path if out_path is not None else os.path.join(corpus_path, "word_lm.npz"))
+    return lm
+
+
+def build_unit_lm(corpus_path, units_path, order=3, min_count=1, out_path=None, train_dataset=None):
+    """Back-off n-gram LM over subword units (lm.UnitNgramLM, interpolated Witten-Bell in back-off form) from the training
+    transcripts -- the "sentence" column of <corpus_path>/train.tsv, or the "trans" of ``train_dataset``'s items -- encoded by the
+    units of ``units_path`` (``build_units``; blank = 0); saved to ``out_path`` (default <corpus_path>/unit_lm.npz) for
+    ``predict(unit_lm_path=...)`` and ``predict(rescore_unit_lm_path=...)``.  An n-gram of order >= 2 seen fewer than ``min_count``
+    times is not stored.  Returns the LM."""
+    import os
+    from .lm import UnitNgramLM
+    from .units import SubwordUnits
+    units = SubwordUnits.load(units_path)
+    if train_dataset is not None:
+        lines = [train_dataset[i]["trans"] for i in range(len(train_dataset))]
+    else:
+        import pandas as pd
+        lines = [str(x) for x in pd.read_csv(os.path.join(corpus_path, "train.tsv"), sep="\t")["sentence"]]
+    lm = UnitNgramLM.from_text(lines, units, order=order, blank=0, min_count=min_count)
+    lm.save(out_path if out_path is not None else os.path.join(corpus_path, "unit_lm.npz"))
     return lm
