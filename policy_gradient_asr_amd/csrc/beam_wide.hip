@@ -501,6 +501,45 @@ inline size_t wide_lm_ws_layout(int T, int B, int V, int beam, WideWs* ws, float
     return (off + 255) / 256 * 256;
 }
 
+static_assert(2 * WIDE_KMAX == WIDE_THREADS, "one threshold slot and one histogram bin per thread");
+static_assert(WIDE_LM_LDS_OFFSET + sizeof(WideLmLds) <= 160 * 1024, "LDS");
+
+// The host side of both entries.  The checks are pgasr_ctc_beam_search_nbest's in its order and with its status codes, lm_check()
+// (the model's) where that entry checks its flags, then the room for a model's row cache behind the trie; nothing touches HIP until
+// every check has passed.  Then the hash table is cleared and beam_wide_kernel<TIn, FAST, LmArg...> launched.  LmArg: nothing, or
+// the WideLm<true> that lm_check() fills in; its rows are set here.
+template <typename LmCheck, typename... LmArg>
+int wide_search(const void* log_probs, int is_f64, long long stride_t, long long stride_b, const int32_t* lengths, int T, int B, int V,
+                int beam, int blank, int flags, int nbest, int32_t* out_tokens, int tok_stride, int32_t* out_len, double* out_score,
+                int32_t* out_count, int32_t* out_counting_frames, void* workspace, size_t workspace_bytes, void* stream,
+                LmCheck&& lm_check, LmArg&... lm) {
+    constexpr bool LM = sizeof...(LmArg) != 0;
+    WideWs ws;
+    if (const int st = beam_check_args(log_probs, out_tokens, out_len, out_score, T, B, V, beam, blank, WIDE_VMAX, WIDE_KMAX,
+                                       [&] {
+                                           const bool bad = (flags & ~(1 | 32)) || nbest < 1 || nbest > beam || tok_stride < T || !out_count;
+                                           return bad ? (int)PGASR_ERR_INVALID_ARG : lm_check();
+                                       },
+                                       workspace, workspace_bytes, &ws)) return st;
+    if constexpr (LM)
+        if (workspace_bytes < wide_lm_ws_layout(T, B, V, beam, &ws, &lm.rows..., (char*)workspace)) return PGASR_ERR_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    if (hipMemsetAsync(ws.table, 0, (size_t)B * ws.H * sizeof(unsigned long long), st) != hipSuccess) return PGASR_ERR_LAUNCH;
+    constexpr size_t lds = ((LM ? WIDE_LM_LDS_OFFSET + sizeof(WideLmLds) : sizeof(WideLds)) + 15) / 16 * 16;
+#define WIDE_LAUNCH(TIN, FAST)                                                                                                    \
+    {                                                                                                                             \
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&beam_wide_kernel<TIN, FAST, LmArg...>),                          \
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                          \
+        PGASR_LAUNCH_KERNEL((beam_wide_kernel<TIN, FAST, LmArg...>), dim3(B), dim3(WIDE_THREADS), lds, st, (const TIN*)log_probs, \
+                           stride_t, stride_b, lengths, T, V, beam, blank, flags & 1, (flags & 32) ? 1 : 0, ws, nbest, tok_stride, \
+                           out_tokens, out_len, out_score, out_count, out_counting_frames, lm...);                                \
+    }
+    if (is_f64) WIDE_LAUNCH(double, false) else WIDE_LAUNCH(float, true)
+#undef WIDE_LAUNCH
+    PGASR_CHECK_LAUNCH();
+    return PGASR_OK;
+}
+
 }  // namespace
 
 extern "C" size_t pgasr_beam_wide_workspace_bytes(int T, int B, int V, int beam) {
@@ -514,31 +553,9 @@ extern "C" int pgasr_ctc_beam_search_wide(const void* log_probs, int is_f64, lon
                                           int nbest, int32_t* out_tokens, int tok_stride, int32_t* out_len, double* out_score,
                                           int32_t* out_count, int32_t* out_counting_frames,
                                           void* workspace, size_t workspace_bytes, void* stream) {
-    // the order and the status codes of pgasr_ctc_beam_search_nbest; nothing below touches HIP until every check has passed
-    WideWs ws;
-    if (const int st = beam_check_args(log_probs, out_tokens, out_len, out_score, T, B, V, beam, blank, WIDE_VMAX, WIDE_KMAX,
-                                       [&] {
-                                           const bool bad = (flags & ~(1 | 32)) || nbest < 1 || nbest > beam || tok_stride < T || !out_count;
-                                           return bad ? (int)PGASR_ERR_INVALID_ARG : (int)PGASR_OK;
-                                       },
-                                       workspace, workspace_bytes, &ws)) return st;
-    static_assert(2 * WIDE_KMAX == WIDE_THREADS, "one threshold slot and one histogram bin per thread");
-    static_assert(sizeof(WideLds) <= 160 * 1024, "LDS");
-    hipStream_t st = (hipStream_t)stream;
-    if (hipMemsetAsync(ws.table, 0, (size_t)B * ws.H * sizeof(unsigned long long), st) != hipSuccess) return PGASR_ERR_LAUNCH;
-    const size_t lds = (sizeof(WideLds) + 15) / 16 * 16;
-#define WIDE_LAUNCH(TIN, FAST)                                                                                                    \
-    {                                                                                                                             \
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&beam_wide_kernel<TIN, FAST>),                                    \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                          \
-        PGASR_LAUNCH_KERNEL((beam_wide_kernel<TIN, FAST>), dim3(B), dim3(WIDE_THREADS), lds, st, (const TIN*)log_probs, stride_t, \
-                           stride_b, lengths, T, V, beam, blank, flags & 1, (flags & 32) ? 1 : 0, ws, nbest, tok_stride,          \
-                           out_tokens, out_len, out_score, out_count, out_counting_frames);                                       \
-    }
-    if (is_f64) WIDE_LAUNCH(double, false) else WIDE_LAUNCH(float, true)
-#undef WIDE_LAUNCH
-    PGASR_CHECK_LAUNCH();
-    return PGASR_OK;
+    return wide_search(log_probs, is_f64, stride_t, stride_b, lengths, T, B, V, beam, blank, flags, nbest, out_tokens, tok_stride,
+                       out_len, out_score, out_count, out_counting_frames, workspace, workspace_bytes, stream,
+                       [] { return (int)PGASR_OK; });
 }
 
 extern "C" size_t pgasr_beam_wide_lm_workspace_bytes(int T, int B, int V, int beam) {
@@ -552,36 +569,16 @@ extern "C" int pgasr_ctc_beam_search_wide_lm(const void* log_probs, int is_f64, 
                                              int32_t* out_count, int32_t* out_counting_frames,
                                              void* workspace, size_t workspace_bytes, void* stream,
                                              const pgasr_unit_lm_tables* tables, double lm_alpha, double lm_beta) {
-    // pgasr_ctc_beam_search_wide's checks in its order, the model's where that entry checks its flags; nothing below touches HIP
-    // until every check has passed
-    WideWs ws;
-    if (const int st = beam_check_args(log_probs, out_tokens, out_len, out_score, T, B, V, beam, blank, WIDE_VMAX, WIDE_KMAX,
-                                       [&] {
-                                           const bool bad = (flags & ~(1 | 32)) || nbest < 1 || nbest > beam || tok_stride < T || !out_count;
-                                           if (bad) return (int)PGASR_ERR_INVALID_ARG;
-                                           return unit_lm::check_tables(tables, V, blank, lm_alpha, lm_beta);
-                                       },
-                                       workspace, workspace_bytes, &ws)) return st;
     WideLm<true> lm;
-    if (workspace_bytes < wide_lm_ws_layout(T, B, V, beam, &ws, &lm.rows, (char*)workspace)) return PGASR_ERR_WORKSPACE;
-    lm.states = (const int4*)tables->states; lm.succ = (const int4*)tables->succ;
-    lm.n_states = tables->n_states; lm.n_succ = tables->n_succ; lm.start = tables->start; lm.order = tables->order;
-    lm.alpha = lm_alpha; lm.beta = lm_beta;
-    static_assert(WIDE_LM_LDS_OFFSET + sizeof(WideLmLds) <= 160 * 1024, "LDS");
-    hipStream_t st = (hipStream_t)stream;
-    if (hipMemsetAsync(ws.table, 0, (size_t)B * ws.H * sizeof(unsigned long long), st) != hipSuccess) return PGASR_ERR_LAUNCH;
-    const size_t lds = (WIDE_LM_LDS_OFFSET + sizeof(WideLmLds) + 15) / 16 * 16;
-#define WIDE_LAUNCH(TIN, FAST)                                                                                                    \
-    {                                                                                                                             \
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&beam_wide_kernel<TIN, FAST, WideLm<true>>),                      \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                          \
-        PGASR_LAUNCH_KERNEL((beam_wide_kernel<TIN, FAST, WideLm<true>>), dim3(B), dim3(WIDE_THREADS), lds, st,                    \
-                           (const TIN*)log_probs,                                                                                 \
-                           stride_t, stride_b, lengths, T, V, beam, blank, flags & 1, (flags & 32) ? 1 : 0, ws, nbest, tok_stride, \
-                           out_tokens, out_len, out_score, out_count, out_counting_frames, lm);                                   \
-    }
-    if (is_f64) WIDE_LAUNCH(double, false) else WIDE_LAUNCH(float, true)
-#undef WIDE_LAUNCH
-    PGASR_CHECK_LAUNCH();
-    return PGASR_OK;
+    return wide_search(log_probs, is_f64, stride_t, stride_b, lengths, T, B, V, beam, blank, flags, nbest, out_tokens, tok_stride,
+                       out_len, out_score, out_count, out_counting_frames, workspace, workspace_bytes, stream,
+                       [&] {
+                           if (const int st = unit_lm::check_tables(tables, V, blank, lm_alpha, lm_beta)) return st;
+                           lm.states = (const int4*)tables->states; lm.succ = (const int4*)tables->succ;
+                           lm.n_states = tables->n_states; lm.n_succ = tables->n_succ; lm.start = tables->start; lm.order = tables->order;
+                           lm.alpha = lm_alpha; lm.beta = lm_beta;
+                           return (int)PGASR_OK;
+                       },
+                       lm);
 }
+

@@ -1617,29 +1617,19 @@ def ctc_beam_search_wide(log_probs, lengths=None, beam=5, nbest=None, blank=0, c
     lib = _lib.load()
     T, B, V = _search_inputs(log_probs, lengths)
     N, dev = (1 if nbest is None else int(nbest)), log_probs.device
-    if unit_lm is not None:
-        tables = unit_lm.device_tables(dev)
-        ws = _workspace(lib.pgasr_beam_wide_lm_workspace_bytes(T, B, V, int(beam)), dev, "beam_wide")
-        tokens, tl, score, count = _nbest_outputs(N, B, T, dev)
-        frames = torch.empty(B, dtype=torch.int32, device=dev) if stats else None
-        with _timed("beam_search_wide_lm"):
-            st = lib.pgasr_ctc_beam_search_wide_lm(_p(log_probs), int(log_probs.dtype == torch.float64), log_probs.stride(0),
-                                                   log_probs.stride(1), _p(lengths), T, B, V, int(beam), int(blank),
-                                                   int(bool(collapse)) | (32 if counting else 0), N, _p(tokens), T, _p(tl), _p(score),
-                                                   _p(count), _p(frames), _p(ws), ws.numel(), _stream(), ctypes.byref(tables.struct),
-                                                   float(lm_alpha), float(lm_beta))
-        _lib.check(st, "pgasr_ctc_beam_search_wide_lm")
-        res = (tokens[0], tl[0], score[0]) if nbest is None else CTCNBest(tokens, tl, score, count)
-        return (res, frames) if stats else res
-    ws = _workspace(lib.pgasr_beam_wide_workspace_bytes(T, B, V, int(beam)), dev, "beam_wide")
+    if unit_lm is None:
+        entry, label, ws_bytes, lm_args = "pgasr_ctc_beam_search_wide", "beam_search_wide", lib.pgasr_beam_wide_workspace_bytes, ()
+    else:
+        entry, label, ws_bytes = "pgasr_ctc_beam_search_wide_lm", "beam_search_wide_lm", lib.pgasr_beam_wide_lm_workspace_bytes
+        lm_args = (ctypes.byref(unit_lm.device_tables(dev).struct), float(lm_alpha), float(lm_beta))
+    ws = _workspace(ws_bytes(T, B, V, int(beam)), dev, "beam_wide")
     tokens, tl, score, count = _nbest_outputs(N, B, T, dev)
     frames = torch.empty(B, dtype=torch.int32, device=dev) if stats else None
-    with _timed("beam_search_wide"):
-        st = lib.pgasr_ctc_beam_search_wide(_p(log_probs), int(log_probs.dtype == torch.float64), log_probs.stride(0),
-                                            log_probs.stride(1), _p(lengths), T, B, V, int(beam), int(blank),
-                                            int(bool(collapse)) | (32 if counting else 0), N, _p(tokens), T, _p(tl), _p(score),
-                                            _p(count), _p(frames), _p(ws), ws.numel(), _stream())
-    _lib.check(st, "pgasr_ctc_beam_search_wide")
+    with _timed(label):
+        st = getattr(lib, entry)(_p(log_probs), int(log_probs.dtype == torch.float64), log_probs.stride(0), log_probs.stride(1),
+                                 _p(lengths), T, B, V, int(beam), int(blank), int(bool(collapse)) | (32 if counting else 0), N,
+                                 _p(tokens), T, _p(tl), _p(score), _p(count), _p(frames), _p(ws), ws.numel(), _stream(), *lm_args)
+    _lib.check(st, entry)
     res = (tokens[0], tl[0], score[0]) if nbest is None else CTCNBest(tokens, tl, score, count)
     return (res, frames) if stats else res
 

@@ -11,7 +11,13 @@ the acoustic alphabet, queried on the host by ``logp_sentence`` and on the devic
 
 ``UnitNgramLM`` is the sparse model over the acoustic units themselves, for alphabets the dense table cannot hold (up to 1024
 symbols at order <= 5): a back-off n-gram model fused into the wide search (csrc/beam_wide.hip) and applied to N-best lists
-(csrc/unit_lm.hip) through ``device_tables``, queried on the host by ``logp`` / ``logp_sequence``."""
+(csrc/unit_lm.hip) through ``device_tables``, queried on the host by ``logp`` / ``logp_sequence``.
+
+The two are the same ARPA-form model over different symbols, and what they share is stated once, in ``_BackoffNgramLM`` and the
+functions before it: the per-order arrays and their checks, the canonical order (``_sorted_arrays``), the ARPA reader and writer,
+the npz members, the Witten-Bell estimate in back-off form (``_witten_bell``), the dict of entries and the back-off walk.  The classes
+keep what a symbol is, how n-grams are counted, their own checks and their ``pack()`` layouts.  ``_on_device`` is the one "tensor
+once per device" rule of all three models."""
 import collections
 import math
 
@@ -27,6 +33,18 @@ def _check_size(V, order):
         raise ValueError("an LM needs at least one symbol beside the blank")
     if V ** int(order) > MAX_ENTRIES:
         raise ValueError(f"an order-{order} table over {V} symbols has {V ** int(order)} entries; the limit is 2**25")
+
+
+def _on_device(cache, device, make):
+    """``make(device)``, made once per device and kept in ``cache``; a bare "cuda" is the current device."""
+    import torch
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    t = cache.get(device)
+    if t is None:
+        t = cache[device] = make(device)
+    return t
 
 
 class CharNgramLM:
@@ -124,13 +142,7 @@ class CharNgramLM:
     def device_table(self, device):
         """The table as a contiguous fp32 tensor on ``device`` (made once per device)."""
         import torch
-        device = torch.device(device)
-        if device.type == "cuda" and device.index is None:
-            device = torch.device("cuda", torch.cuda.current_device())
-        t = self._device_tables.get(device)
-        if t is None:
-            t = self._device_tables[device] = torch.from_numpy(self.table).to(device).contiguous()
-        return t
+        return _on_device(self._device_tables, device, lambda dev: torch.from_numpy(self.table).to(dev).contiguous())
 
 
 # ------------------------------------------------------------------------------------------
@@ -210,10 +222,182 @@ def _place(home, used):
     return pos
 
 
+# ------------------------------------------------------------------------------------------
+# The back-off n-gram core: what WordNgramLM and UnitNgramLM both are, stated once
+# ------------------------------------------------------------------------------------------
+def _sorted_arrays(grams, ident=int):
+    """grams[k-1]: dict from tuples of k symbols to (logp, bow) in natural log; ``ident`` gives a symbol's id.  Returns (ngrams, logp,
+    bow) in canonical order: the k-grams of an order ascending in their ids, lexicographically; int32 and fp32."""
+    ngrams, logp, bow = [], [], []
+    for k, items in enumerate(grams, 1):
+        g = np.array([[ident(w) for w in key] for key in items], dtype=np.int32).reshape(-1, k)
+        vals = np.array(list(items.values()), dtype=np.float64).reshape(-1, 2)
+        idx = np.lexsort(tuple(g[:, j] for j in range(k - 1, -1, -1))) if g.shape[0] else np.zeros(0, dtype=np.int64)
+        ngrams.append(g[idx]); logp.append(vals[idx, 0].astype(np.float32)); bow.append(vals[idx, 1].astype(np.float32))
+    return ngrams, logp, bow
+
+
+def _witten_bell(counts, p0, unigrams, start):
+    """Interpolated Witten-Bell smoothing written out in back-off form, in float64: counts[k-1][h][w] = c(hw) for the k-1 symbols h
+    and k = 1 .. order -> a list over k of dicts {k-gram tuple: (ln p, ln bow)}.  With N1+(h.) the number of distinct w counted after h:
+        p_0(w)   = ``p0``
+        p_k(w|h) = (c(hw) + N1+(h.) p_{k-1}(w|h')) / (c(h) + N1+(h.))   for a counted hw, h' = h without its oldest symbol
+        bow(h)   = ln(N1+(h.) / (c(h) + N1+(h.)))                        0.0 where h was no context, and at the top order
+    p_{k-1}(w|h') being the back-off model of order k-1 itself.  Every symbol of ``unigrams`` gets a unigram (c = 0 where unseen);
+    ``start`` is never predicted (log10 p = -99) and carries the bow of the context (start,)."""
+    order = len(counts)
+    prob = [dict() for _ in range(order)]                    # prob[k-1][h + (w,)] = p_k(w | h)
+    bowp = [dict() for _ in range(order)]                    # bowp[k-1][h] = the back-off mass of the k-1 symbols h
+
+    def lower(k, h, w):                                      # the model of order k at (w | h), len(h) == k - 1
+        if k == 0:
+            return p0
+        p = prob[k - 1].get(h + (w,))
+        if p is not None:
+            return p
+        return bowp[k - 1].get(h, 1.0) * lower(k - 1, h[1:], w)
+
+    def ln_bow(k, key):
+        return math.log(bowp[k].get(key, 1.0)) if k < order else 0.0
+
+    for k in range(1, order + 1):
+        for h, cw in counts[k - 1].items():
+            c, n1 = float(sum(cw.values())), float(len(cw))
+            bowp[k - 1][h] = n1 / (c + n1)
+            for w in (list(cw) if k > 1 else unigrams):
+                prob[k - 1][h + (w,)] = (cw.get(w, 0) + n1 * lower(k - 1, h[1:], w)) / (c + n1)
+    grams = [{key: (math.log(p), ln_bow(k, key)) for key, p in prob[k - 1].items()} for k in range(1, order + 1)]
+    grams[0][(start,)] = (ARPA_NEVER * _LN10, ln_bow(1, (start,)))
+    return grams
+
+
+def _read_arpa(path, max_order, key_of):
+    """The sections of a standard ARPA text file as grams[k-1] = {key: (ln p, ln bow)} (log10 -> ln; 0.0 where a line gives no
+    bow).  ``key_of(k, names)`` turns the k names of a line into the model's key, returns None for a line the model skips, or
+    raises."""
+    grams, k = [], 0
+    with open(path, "r") as fo:
+        for raw in fo:
+            ln = raw.strip()
+            if not ln or ln == "\\data\\" or ln.startswith("ngram "):
+                continue
+            if ln == "\\end\\":
+                break
+            if ln.startswith("\\") and ln.endswith("-grams:"):
+                k = int(ln[1:-len("-grams:")])
+                if k != len(grams) + 1 or k > max_order:
+                    raise ValueError(f"{path}: the sections must be 1-grams .. n-grams in order, n <= {max_order} (got {k})")
+                grams.append({})
+                continue
+            if k == 0:
+                raise ValueError(f"{path}: {ln!r} stands before the first section")
+            f = ln.split()
+            if len(f) not in (k + 1, k + 2):
+                raise ValueError(f"{path}: {ln!r} is no {k}-gram line")
+            key = key_of(k, f[1:k + 1])
+            if key is not None:
+                grams[k - 1][key] = (float(f[0]) * _LN10, float(f[k + 1]) * _LN10 if len(f) == k + 2 else 0.0)
+    if not grams:
+        raise ValueError(f"{path}: no n-gram section")
+    return grams
+
+
+class _BackoffNgramLM:
+    """The arrays of an ARPA-form back-off model and everything that depends on them alone.  A subclass names itself (KIND, MAX_ORDER,
+    SYMBOL: the words of the error messages), runs its own checks between ``_canonical`` and ``_set_arrays`` and keeps the
+    arrays under the public names it likes; here they are ``ngrams``, ``_logp`` and ``_bow``."""
+    KIND = MAX_ORDER = SYMBOL = None
+
+    @classmethod
+    def _check_order(cls, order, *per_order):
+        """1 <= order <= MAX_ORDER, and every list of ``per_order`` has one entry per order."""
+        if not 1 <= order <= cls.MAX_ORDER or any(len(a) != order for a in per_order):
+            what = " with one n-gram, logp and bow array per order" if per_order else ""
+            raise ValueError(f"a {cls.KIND} LM has order 1 .. {cls.MAX_ORDER}{what} (got {order})")
+
+    @classmethod
+    def _canonical(cls, k, ngrams, logp, bow, n_symbols):
+        """The arrays of order k as (M, k) int32 and (M,) fp32, equally long, every id below ``n_symbols``."""
+        g = np.ascontiguousarray(np.asarray(ngrams[k - 1]), dtype=np.int32).reshape(-1, k)
+        lp = np.ascontiguousarray(np.asarray(logp[k - 1]), dtype=np.float32).reshape(-1)
+        bw = np.ascontiguousarray(np.asarray(bow[k - 1]), dtype=np.float32).reshape(-1)
+        if lp.size != g.shape[0] or bw.size != g.shape[0]:
+            raise ValueError(f"order {k}: n-grams, logp and bow differ in length")
+        if g.size and (g.min() < 0 or g.max() >= n_symbols):
+            raise ValueError(f"order {k}: a {cls.SYMBOL} outside the vocabulary")
+        return g, lp, bw
+
+    @staticmethod
+    def _check_finite(k, lp, bw):
+        if not (np.isfinite(lp).all() and np.isfinite(bw).all()):
+            raise ValueError(f"order {k}: a non-finite logp or bow")
+
+    def _set_arrays(self, per_order):
+        """per_order[k-1]: the (n-grams, logp, bow) of order k, checked."""
+        total = sum(g.shape[0] for g, _, _ in per_order)
+        if total > MAX_NGRAMS:
+            raise ValueError(f"{total} n-grams exceed the limit of 2**24; a model is never truncated")
+        self.ngrams, self._logp, self._bow = (list(a) for a in zip(*per_order))
+        self.order = len(per_order)
+        self._table = None
+        self._packed = None
+        self._device_tables = {}
+
+    def _write_arpa(self, path, names):
+        """The standard ARPA text format (ln -> log10, 17 significant digits: the readers return the same arrays)."""
+        with open(path, "w") as fo:
+            fo.write("\\data\\\n")
+            for k in range(1, self.order + 1):
+                fo.write(f"ngram {k}={self.ngrams[k - 1].shape[0]}\n")
+            for k in range(1, self.order + 1):
+                fo.write(f"\n\\{k}-grams:\n")
+                g, lp, bw = self.ngrams[k - 1], self._logp[k - 1].astype(np.float64) / _LN10, self._bow[k - 1].astype(np.float64) / _LN10
+                for i in range(g.shape[0]):
+                    text = " ".join(names[j] for j in g[i])
+                    fo.write(f"{float(lp[i])!r}\t{text}" + (f"\t{float(bw[i])!r}\n" if k < self.order else "\n"))
+            fo.write("\n\\end\\\n")
+
+    def _save(self, path, **own):
+        """The npz file: the model's ``own`` members in its own sequence ("order" among them), then ngrams_k, logp_k, bow_k for
+        k = 1 .. order."""
+        arrays = dict(own)
+        for k in range(1, self.order + 1):
+            arrays[f"ngrams_{k}"], arrays[f"logp_{k}"], arrays[f"bow_{k}"] = self.ngrams[k - 1], self._logp[k - 1], self._bow[k - 1]
+        with open(path, "wb") as fo:
+            np.savez(fo, **arrays)
+
+    @staticmethod
+    def _saved_arrays(z):
+        ks = range(1, int(z["order"]) + 1)
+        return [z[f"ngrams_{k}"] for k in ks], [z[f"logp_{k}"] for k in ks], [z[f"bow_{k}"] for k in ks]
+
+    def _entries(self):
+        """{n-gram tuple: (logp, bow)} over all orders, every fp32 widened to fp64 (made once)."""
+        if self._table is None:
+            tab = {}
+            for g, lp, bw in zip(self.ngrams, self._logp, self._bow):
+                tab.update(zip(map(tuple, g.tolist()), zip(lp.astype(np.float64).tolist(), bw.astype(np.float64).tolist())))
+            self._table = tab
+        return self._table
+
+    def _backoff(self, h, w):
+        """The contractual query in fp64: from 0.0, the bows of those of the contexts h, h[1:], .. that are stored, until one holds
+        (.., w); then its logp is added.  A context has at most order-1 symbols, so the bow of a top-order entry is never read."""
+        tab, acc = self._entries(), 0.0
+        while True:
+            e = tab.get(h + (w,))
+            if e is not None:
+                return acc + e[0]
+            c = tab.get(h)
+            if c is not None:
+                acc = acc + c[1]
+            h = h[1:]
+
+
 WordLMDeviceTables = collections.namedtuple("WordLMDeviceTables", "struct tensors")
 
 
-class WordNgramLM:
+class WordNgramLM(_BackoffNgramLM):
     """A back-off word n-gram model of order 1 <= n <= 5 in ARPA form.
 
     A word is a non-empty tuple of at most MAX_WORD_LEN token ids of the acoustic alphabet (stored as bytes: ids <= 255), without
@@ -230,10 +414,11 @@ class WordNgramLM:
         ngrams[k-1] (M_k, k) int32, logp[k-1] / bow[k-1] (M_k,) fp32 for k = 1 .. order; the unigram of word i is row i.
     The context (all words but the last) of every stored n-gram must itself be stored, as in every ARPA file a toolkit writes."""
 
+    KIND, MAX_ORDER, SYMBOL = "word", MAX_WORD_ORDER, "word id"
+
     def __init__(self, word_pool, word_off, ngrams, logp, bow, blank=0, delimiter=-1):
         order = len(ngrams)
-        if not 1 <= order <= MAX_WORD_ORDER or len(logp) != order or len(bow) != order:
-            raise ValueError(f"a word LM has order 1 .. {MAX_WORD_ORDER} with one n-gram, logp and bow array per order (got {order})")
+        self._check_order(order, logp, bow)
         self.word_pool = np.array(word_pool, dtype=np.uint8).reshape(-1)         # a copy: the caller's may be a read-only view of bytes
         self.word_off = np.ascontiguousarray(np.asarray(word_off), dtype=np.int32).reshape(-1)
         n_words = self.word_off.size - 1
@@ -253,27 +438,17 @@ class WordNgramLM:
         self._word_id = {s: i for i, s in enumerate(self.spellings) if i >= N_RESERVED}
         if len(self._word_id) != n_words - N_RESERVED:
             raise ValueError("two words of the vocabulary have the same spelling")
-        self.ngrams, self.logp, self.bow = [], [], []
+        per_order = []
         for k in range(1, order + 1):
-            g = np.ascontiguousarray(np.asarray(ngrams[k - 1]), dtype=np.int32).reshape(-1, k)
-            lp = np.ascontiguousarray(np.asarray(logp[k - 1]), dtype=np.float32).reshape(-1)
-            bw = np.ascontiguousarray(np.asarray(bow[k - 1]), dtype=np.float32).reshape(-1)
-            if lp.size != g.shape[0] or bw.size != g.shape[0]:
-                raise ValueError(f"order {k}: n-grams, logp and bow differ in length")
-            if g.size and (g.min() < 0 or g.max() >= n_words):
-                raise ValueError(f"order {k}: a word id outside the vocabulary")
-            if not (np.isfinite(lp).all() and np.isfinite(bw).all()):
-                raise ValueError(f"order {k}: a non-finite logp or bow")
-            self.ngrams.append(g); self.logp.append(lp); self.bow.append(bw)
-        if sum(g.shape[0] for g in self.ngrams) > MAX_NGRAMS:
-            raise ValueError(f"{sum(g.shape[0] for g in self.ngrams)} n-grams exceed the limit of 2**24; a model is never truncated")
+            g, lp, bw = self._canonical(k, ngrams, logp, bow, n_words)
+            self._check_finite(k, lp, bw)
+            per_order.append((g, lp, bw))
+        self._set_arrays(per_order)
+        self.logp, self.bow = self._logp, self._bow
         if self.ngrams[0].shape[0] != n_words or (self.ngrams[0][:, 0] != np.arange(n_words)).any():
             raise ValueError("every vocabulary entry has a unigram, stored at its own id")
-        self.order, self.n_words = order, n_words
+        self.n_words = n_words
         self.ctx_row = self._context_rows()
-        self._table = None
-        self._packed = None
-        self._device_tables = {}
 
     def _context_rows(self):
         """Per order k >= 2, the row at order k-1 of every n-gram's context.  Rows are in lexicographic order, so the key
@@ -316,29 +491,18 @@ class WordNgramLM:
         pool = np.frombuffer(b"".join(words), dtype=np.uint8)
         if off[-1] >= 2 ** 31:
             raise ValueError("the spellings exceed 2**31 bytes")
-        ngrams, logp, bow = [], [], []
-        for k in range(1, order + 1):
-            items = grams[k - 1]
-            g = np.array([[wid[w] for w in key] for key in items], dtype=np.int32).reshape(-1, k)
-            vals = np.array(list(items.values()), dtype=np.float64).reshape(-1, 2)
-            idx = np.lexsort(tuple(g[:, j] for j in range(k - 1, -1, -1))) if g.shape[0] else np.zeros(0, dtype=np.int64)
-            ngrams.append(g[idx]); logp.append(vals[idx, 0].astype(np.float32)); bow.append(vals[idx, 1].astype(np.float32))
-        return cls(pool, off, ngrams, logp, bow, blank=blank, delimiter=delimiter)
+        return cls(pool, off, *_sorted_arrays(grams[:order], wid.__getitem__), blank=blank, delimiter=delimiter)
 
     @classmethod
     def from_text(cls, lines, char2ind, order=3, min_count=1, delimiter=" ", blank=0):
-        """Interpolated Witten-Bell smoothing (as ``CharNgramLM``), written out in back-off form, in float64 on the host.  A line is
-        <s> w_1 .. w_m </s>, its words cut at ``delimiter`` as str.split() cuts them; an n-gram of order k is every window of k
-        of these whose last entry is not <s>.  With c the counts and N1+(h.) the number of distinct entries seen after h:
-            p_0(w)   = 1 / (words + 2)                                   uniform over the vocabulary, </s> and <unk>
-            p_k(w|h) = (c(hw) + N1+(h.) p_{k-1}(w|h')) / (c(h) + N1+(h.))  for a seen hw, h' = h without its oldest word
-            bow(h)   = ln(N1+(h.) / (c(h) + N1+(h.)))
-        p_{k-1}(w|h') being the back-off model of order k-1 itself.  Every vocabulary entry gets a unigram (c = 0 where unseen), so
-        <unk> always has a finite probability; <s> is never predicted (log10 p = -99).  Words seen fewer than ``min_count`` times
-        or longer than MAX_WORD_LEN count as <unk>.  A character outside the alphabet raises."""
+        """Interpolated Witten-Bell smoothing (as ``CharNgramLM``), written out in back-off form, in float64 on the host
+        (``_witten_bell``).  A line is <s> w_1 .. w_m </s>, its words cut at ``delimiter`` as str.split() cuts them; an n-gram of
+        order k is every window of k of these whose last entry is not <s>.  p_0(w) = 1 / (words + 2): uniform over the vocabulary,
+        </s> and <unk>.  Every vocabulary entry gets a unigram (c = 0 where unseen), so <unk> always has a finite probability; <s> is
+        never predicted (log10 p = -99).  Words seen fewer than ``min_count`` times or longer than MAX_WORD_LEN count as <unk>.  A
+        character outside the alphabet raises."""
         order = int(order)
-        if not 1 <= order <= MAX_WORD_ORDER:
-            raise ValueError(f"a word LM has order 1 .. {MAX_WORD_ORDER} (got {order})")
+        cls._check_order(order)
         if delimiter not in char2ind:
             raise ValueError(f"the alphabet has no delimiter {delimiter!r}")
         sents, freq = [], collections.Counter()
@@ -360,7 +524,6 @@ class WordNgramLM:
             raise ValueError("from_text needs at least one line")
         vocab = {w for w, c in freq.items() if c >= int(min_count) and len(w) <= MAX_WORD_LEN}
         seqs = [[BOS] + [w if w in vocab else UNK for w in s] + [EOS] for s in sents]
-        p0 = 1.0 / (len(vocab) + 2)
         counts = []                                              # counts[k-1][h][w]
         for k in range(1, order + 1):
             ck = collections.defaultdict(collections.Counter)
@@ -368,34 +531,7 @@ class WordNgramLM:
                 for i in range(max(1, k - 1), len(s)):
                     ck[tuple(s[i - k + 1:i])][s[i]] += 1
             counts.append(ck)
-        prob = [dict() for _ in range(order)]                    # prob[k-1][h + (w,)] = p_k(w | h)
-        bowp = [dict() for _ in range(order)]                    # bowp[k-1][h] = the back-off mass of the k-1 words h
-
-        def lower(k, h, w):                                      # the model of order k at (w | h), len(h) == k - 1
-            if k == 0:
-                return p0
-            p = prob[k - 1].get(h + (w,))
-            if p is not None:
-                return p
-            return bowp[k - 1].get(h, 1.0) * lower(k - 1, h[1:], w)
-
-        for k in range(1, order + 1):
-            for h, cw in counts[k - 1].items():
-                c, n1 = float(sum(cw.values())), float(len(cw))
-                bowp[k - 1][h] = n1 / (c + n1)
-                targets = list(cw) if k > 1 else sorted(vocab) + [EOS, UNK]
-                for w in targets:
-                    prob[k - 1][h + (w,)] = (cw.get(w, 0) + n1 * lower(k - 1, h[1:], w)) / (c + n1)
-        grams = []
-        for k in range(1, order + 1):
-            items = {}
-            for key, p in prob[k - 1].items():
-                b = bowp[k].get(key, 1.0) if k < order else 1.0
-                items[key] = (math.log(p), math.log(b))
-            if k == 1:
-                b = bowp[1].get((BOS,), 1.0) if order > 1 else 1.0
-                items[(BOS,)] = (ARPA_NEVER * _LN10, math.log(b))
-            grams.append(items)
+        grams = _witten_bell(counts, 1.0 / (len(vocab) + 2), sorted(vocab) + [EOS, UNK], BOS)
         return cls._build(grams, order, int(blank), int(char2ind[delimiter]))
 
     @classmethod
@@ -405,7 +541,7 @@ class WordNgramLM:
         cannot be spelled in the alphabet (a character outside it, more than MAX_WORD_LEN characters, or a word without a
         unigram) raises, or is dropped with ``skip_unknown=True``: the decoder can never emit such a word."""
         reserved = {name: i for i, name in enumerate(ARPA_RESERVED)}
-        grams, k, known = [], 0, {BOS, EOS, UNK}
+        known = {BOS, EOS, UNK}
 
         def spell(w):
             if w in reserved:
@@ -417,68 +553,34 @@ class WordNgramLM:
                 return None
             return bytes(ids)
 
-        with open(path, "r") as fo:
-            for raw in fo:
-                ln = raw.strip()
-                if not ln or ln == "\\data\\" or ln.startswith("ngram "):
-                    continue
-                if ln == "\\end\\":
-                    break
-                if ln.startswith("\\") and ln.endswith("-grams:"):
-                    k = int(ln[1:-len("-grams:")])
-                    if k != len(grams) + 1 or k > MAX_WORD_ORDER:
-                        raise ValueError(f"{path}: the sections must be 1-grams .. n-grams in order, n <= {MAX_WORD_ORDER} (got {k})")
-                    grams.append({})
-                    continue
-                if k == 0:
-                    raise ValueError(f"{path}: {ln!r} stands before the first section")
-                f = ln.split()
-                if len(f) not in (k + 1, k + 2):
-                    raise ValueError(f"{path}: {ln!r} is no {k}-gram line")
-                key = tuple(spell(w) for w in f[1:k + 1])
-                if any(w is None for w in key) or (k > 1 and any(w not in known for w in key)):
-                    if skip_unknown:
-                        continue
-                    raise ValueError(f"{path}: {' '.join(f[1:k + 1])!r} holds a word that cannot be spelled in the alphabet")
-                if k == 1:
-                    known.add(key[0])
-                grams[k - 1][key] = (float(f[0]) * _LN10, float(f[k + 1]) * _LN10 if len(f) == k + 2 else 0.0)
-        if not grams:
-            raise ValueError(f"{path}: no n-gram section")
+        def key_of(k, names):
+            key = tuple(spell(w) for w in names)
+            if any(w is None for w in key) or (k > 1 and any(w not in known for w in key)):
+                if skip_unknown:
+                    return None
+                raise ValueError(f"{path}: {' '.join(names)!r} holds a word that cannot be spelled in the alphabet")
+            if k == 1:
+                known.add(key[0])
+            return key
+
+        grams = _read_arpa(path, MAX_WORD_ORDER, key_of)
         for r in (BOS, EOS, UNK):
             grams[0].setdefault((r,), (ARPA_NEVER * _LN10, 0.0))
         return cls._build(grams, len(grams), int(blank), int(char2ind.get(delimiter, -1)))
 
     def to_arpa(self, path, ind2char):
         """Write the standard ARPA text format (ln -> log10, 17 significant digits: ``from_arpa`` returns the same arrays)."""
-        names = list(ARPA_RESERVED) + ["".join(ind2char[int(t)] for t in s) for s in self.spellings[N_RESERVED:]]
-        with open(path, "w") as fo:
-            fo.write("\\data\\\n")
-            for k in range(1, self.order + 1):
-                fo.write(f"ngram {k}={self.ngrams[k - 1].shape[0]}\n")
-            for k in range(1, self.order + 1):
-                fo.write(f"\n\\{k}-grams:\n")
-                g, lp, bw = self.ngrams[k - 1], self.logp[k - 1].astype(np.float64) / _LN10, self.bow[k - 1].astype(np.float64) / _LN10
-                for i in range(g.shape[0]):
-                    text = " ".join(names[j] for j in g[i])
-                    fo.write(f"{float(lp[i])!r}\t{text}" + (f"\t{float(bw[i])!r}\n" if k < self.order else "\n"))
-            fo.write("\n\\end\\\n")
+        self._write_arpa(path, list(ARPA_RESERVED) + ["".join(ind2char[int(t)] for t in s) for s in self.spellings[N_RESERVED:]])
 
     # ---------------------------------------------------------------- persistence
     def save(self, path):
-        arrays = {"word_pool": self.word_pool, "word_off": self.word_off, "order": np.int64(self.order),
-                  "blank": np.int64(self.blank), "delimiter": np.int64(self.delimiter)}
-        for k in range(1, self.order + 1):
-            arrays[f"ngrams_{k}"], arrays[f"logp_{k}"], arrays[f"bow_{k}"] = self.ngrams[k - 1], self.logp[k - 1], self.bow[k - 1]
-        with open(path, "wb") as fo:
-            np.savez(fo, **arrays)
+        self._save(path, word_pool=self.word_pool, word_off=self.word_off, order=np.int64(self.order), blank=np.int64(self.blank),
+                   delimiter=np.int64(self.delimiter))
 
     @classmethod
     def load(cls, path):
         with np.load(path, allow_pickle=False) as z:
-            ks = range(1, int(z["order"]) + 1)
-            return cls(z["word_pool"], z["word_off"], [z[f"ngrams_{k}"] for k in ks], [z[f"logp_{k}"] for k in ks],
-                       [z[f"bow_{k}"] for k in ks], blank=int(z["blank"]), delimiter=int(z["delimiter"]))
+            return cls(z["word_pool"], z["word_off"], *cls._saved_arrays(z), blank=int(z["blank"]), delimiter=int(z["delimiter"]))
 
     # ---------------------------------------------------------------- queries (the host's own statement)
     def word_id(self, tokens):
@@ -489,31 +591,10 @@ class WordNgramLM:
             return UNK
         return self._word_id.get(bytes(tokens), UNK)
 
-    def _entries(self):
-        if self._table is None:
-            tab = {}
-            for k in range(1, self.order + 1):
-                g, lp, bw = self.ngrams[k - 1].tolist(), self.logp[k - 1].astype(np.float64).tolist(), \
-                    self.bow[k - 1].astype(np.float64).tolist()
-                for i, key in enumerate(g):
-                    tab[tuple(key)] = (lp[i], bw[i])
-            self._table = tab
-        return self._table
-
     def score(self, context, w):
         """ln p(w | context) by the back-off rule: ``context`` any sequence of earlier word ids, most recent last."""
-        tab = self._entries()
         h = tuple(int(c) for c in context)[-(self.order - 1):] if self.order > 1 else ()
-        h = (BOS,) * (self.order - 1 - len(h)) + h
-        w, acc = int(w), 0.0
-        while True:
-            e = tab.get(h + (w,))
-            if e is not None:
-                return acc + e[0]
-            c = tab.get(h)
-            if c is not None:
-                acc = acc + c[1]
-            h = h[1:]
+        return self._backoff((BOS,) * (self.order - 1 - len(h)) + h, int(w))
 
     def split(self, token_ids, delimiter=None):
         """The words of a sentence: the maximal runs of non-delimiter tokens, as str.split() cuts them."""
@@ -583,18 +664,15 @@ class WordNgramLM:
         (made once per device; the tensors live as long as the model)."""
         import torch
         from . import _lib
-        device = torch.device(device)
-        if device.type == "cuda" and device.index is None:
-            device = torch.device("cuda", torch.cuda.current_device())
-        t = self._device_tables.get(device)
-        if t is None:
+
+        def make(device):
             p = self.pack()
             tensors = {k: torch.from_numpy(np.ascontiguousarray(v)).to(device).contiguous() for k, v in p.items()}
             st = _lib.WordLMTables(tensors["word_pool"].data_ptr(), tensors["word_off"].data_ptr(), tensors["word_slots"].data_ptr(),
                                    tensors["uni_logp"].data_ptr(), tensors["uni_bow"].data_ptr(), tensors["ngram_slots"].data_ptr(),
                                    self.order, self.n_words, p["word_slots"].size, p["ngram_slots"].shape[0], self.word_pool.size)
-            t = self._device_tables[device] = WordLMDeviceTables(st, tensors)
-        return t
+            return WordLMDeviceTables(st, tensors)
+        return _on_device(self._device_tables, device, make)
 
 
 # ------------------------------------------------------------------------------------------
@@ -622,7 +700,7 @@ def _find_keys(keys, want):
     return np.where(keys[i] == want, i, -1)
 
 
-class UnitNgramLM:
+class UnitNgramLM(_BackoffNgramLM):
     """A back-off n-gram model of order 1 <= n <= 5 over the V <= 1024 ids of the acoustic alphabet (subword units or characters),
     natural logs, fp32.  Unlike ``CharNgramLM`` it is sparse, so V = 1024 at order 5 is a model like any other.
 
@@ -640,48 +718,42 @@ class UnitNgramLM:
     Arrays (canonical: the k-grams of an order in lexicographic order, so equal models have equal arrays):
         ngrams[k-1] (M_k, k) int32, lp[k-1] / bw[k-1] (M_k,) fp32 (logp and bow) for k = 1 .. order; M_1 = V."""
 
+    KIND, MAX_ORDER, SYMBOL = "unit", MAX_UNIT_ORDER, "symbol"
+
     def __init__(self, ngrams, logp, bow, vocab, blank=0):
         order = len(ngrams)
-        if not 1 <= order <= MAX_UNIT_ORDER or len(logp) != order or len(bow) != order:
-            raise ValueError(f"a unit LM has order 1 .. {MAX_UNIT_ORDER} with one n-gram, logp and bow array per order (got {order})")
-        V, blank = int(vocab), int(blank)
-        if not 2 <= V <= MAX_UNIT_VOCAB:
-            raise ValueError(f"a unit LM is over 2 .. {MAX_UNIT_VOCAB} symbols, the blank included (got {V})")
-        if not 0 <= blank < V:
-            raise ValueError("blank must be a symbol of the vocabulary")
-        self.ngrams, self.lp, self.bw, self._keys = [], [], [], []
+        self._check_order(order, logp, bow)
+        V, blank = self._check_symbols(vocab, blank)
+        per_order, self._keys = [], []
         for k in range(1, order + 1):
-            g = np.ascontiguousarray(np.asarray(ngrams[k - 1]), dtype=np.int32).reshape(-1, k)
-            lp = np.ascontiguousarray(np.asarray(logp[k - 1]), dtype=np.float32).reshape(-1)
-            bw = np.ascontiguousarray(np.asarray(bow[k - 1]), dtype=np.float32).reshape(-1)
-            if lp.size != g.shape[0] or bw.size != g.shape[0]:
-                raise ValueError(f"order {k}: n-grams, logp and bow differ in length")
-            if g.size and (g.min() < 0 or g.max() >= V):
-                raise ValueError(f"order {k}: a symbol outside the vocabulary")
+            g, lp, bw = self._canonical(k, ngrams, logp, bow, V)
             if k == 1:
                 if g.shape[0] != V or (g[:, 0] != np.arange(V)).any():
                     raise ValueError("every symbol has a unigram, stored at its own id (the row of the blank is <s>): "
                                      "a unigram is missing")
-                real = np.arange(V) != blank
-                if not (np.isfinite(lp[real]).all() and np.isfinite(bw).all()):
-                    raise ValueError("order 1: a non-finite logp or bow")
+                self._check_finite(k, lp[np.arange(V) != blank], bw)       # the logp of <s> is never read
             else:
                 if (g[:, 1:] == blank).any():
                     raise ValueError(f"order {k}: the blank stands inside a context or is predicted; it may only be an n-gram's first symbol")
-                if not (np.isfinite(lp).all() and np.isfinite(bw).all()):
-                    raise ValueError(f"order {k}: a non-finite logp or bow")
+                self._check_finite(k, lp, bw)
             key = _gram_keys(g, V)
             if key.size > 1 and (np.diff(key) <= 0).any():
                 raise ValueError(f"order {k}: the n-grams are not in lexicographic order, or one is stored twice")
             if k > 1 and (_find_keys(self._keys[k - 2], key // V) < 0).any():
                 raise ValueError(f"order {k}: an n-gram's context is not stored at order {k - 1}")
-            self.ngrams.append(g); self.lp.append(lp); self.bw.append(bw); self._keys.append(key)
-        if sum(g.shape[0] for g in self.ngrams) > MAX_NGRAMS:
-            raise ValueError(f"{sum(g.shape[0] for g in self.ngrams)} n-grams exceed the limit of 2**24; a model is never truncated")
-        self.order, self.vocab, self.blank = order, V, blank
-        self._table = None
-        self._packed = None
-        self._device_tables = {}
+            per_order.append((g, lp, bw)); self._keys.append(key)
+        self._set_arrays(per_order)
+        self.lp, self.bw = self._logp, self._bow
+        self.vocab, self.blank = V, blank
+
+    @staticmethod
+    def _check_symbols(vocab, blank):
+        V, blank = int(vocab), int(blank)
+        if not 2 <= V <= MAX_UNIT_VOCAB:
+            raise ValueError(f"a unit LM is over 2 .. {MAX_UNIT_VOCAB} symbols, the blank included (got {V})")
+        if not 0 <= blank < V:
+            raise ValueError("blank must be a symbol of the vocabulary")
+        return V, blank
 
     @property
     def n_ngrams(self):
@@ -692,35 +764,19 @@ class UnitNgramLM:
     @classmethod
     def _build(cls, grams, vocab, blank):
         """grams[k-1]: dict from tuples of k symbols to (logp, bow) in natural log; arrays come out in canonical order."""
-        ngrams, logp, bow = [], [], []
-        for k in range(1, len(grams) + 1):
-            items = grams[k - 1]
-            g = np.array(list(items.keys()), dtype=np.int64).reshape(-1, k)
-            vals = np.array(list(items.values()), dtype=np.float64).reshape(-1, 2)
-            if g.size and (g.min() < 0 or g.max() >= int(vocab)):
-                raise ValueError(f"order {k}: a symbol outside the vocabulary")
-            idx = np.argsort(_gram_keys(g, int(vocab)), kind="stable")
-            ngrams.append(g[idx].astype(np.int32)); logp.append(vals[idx, 0].astype(np.float32)); bow.append(vals[idx, 1].astype(np.float32))
-        return cls(ngrams, logp, bow, vocab, blank=blank)
+        return cls(*_sorted_arrays(grams), vocab, blank=blank)
 
     @staticmethod
     def estimate(seqs_of_token_ids, vocab, order=3, blank=0, min_count=1):
         """The fp64 estimate behind ``from_transcripts``: a list over k = 1 .. order of dicts {k-gram tuple: (ln p, ln bow)}.
-        Interpolated Witten-Bell smoothing written out in back-off form (the estimator of ``WordNgramLM.from_text`` and, context by
-        context, of ``CharNgramLM.from_transcripts``).  A transcript y is counted as (blank,) + y; a k-gram is every window of k of
-        these whose last entry is not the blank.  With c the counts and N1+(h.) the number of distinct symbols seen after h:
-            p_0(s)   = 1 / (V - 1)
-            p_k(s|h) = (c(hs) + N1+(h.) p_{k-1}(s|h')) / (c(h) + N1+(h.))   for a stored hs, h' = h without its oldest symbol
-            bow(h)   = ln(N1+(h.) / (c(h) + N1+(h.)))
-        Every one of the V-1 symbols gets a unigram (c = 0 where unseen).  A k-gram with k >= 2 seen fewer than ``min_count`` times
-        is not stored and takes no part in c and N1+: the model stays normalised."""
+        ``_witten_bell``: the estimator of ``WordNgramLM.from_text`` and, context by context, of ``CharNgramLM.from_transcripts``.
+        A transcript y is counted as (blank,) + y; a k-gram is every window of k of these whose last entry is not the blank.
+        p_0(s) = 1 / (V - 1), and every one of the V-1 symbols gets a unigram (c = 0 where unseen; the uniform one where no token
+        was seen at all).  A k-gram with k >= 2 seen fewer than ``min_count`` times is not stored and takes no part in c and N1+:
+        the model stays normalised."""
         V, blank, order = int(vocab), int(blank), int(order)
-        if not 1 <= order <= MAX_UNIT_ORDER:
-            raise ValueError(f"a unit LM has order 1 .. {MAX_UNIT_ORDER} (got {order})")
-        if not 2 <= V <= MAX_UNIT_VOCAB:
-            raise ValueError(f"a unit LM is over 2 .. {MAX_UNIT_VOCAB} symbols, the blank included (got {V})")
-        if not 0 <= blank < V:
-            raise ValueError("blank must be a symbol of the vocabulary")
+        UnitNgramLM._check_order(order)
+        UnitNgramLM._check_symbols(V, blank)
         counts = [collections.defaultdict(collections.Counter) for _ in range(order)]      # counts[k-1][h][s]
         for y in seqs_of_token_ids:
             s = [blank] + [int(t) for t in y]
@@ -737,36 +793,12 @@ class UnitNgramLM:
                 else:
                     del counts[k - 1][h]
         p0 = 1.0 / (V - 1)
-        prob = [dict() for _ in range(order)]
-        bowp = [dict() for _ in range(order + 1)]
-
-        def lower(k, h, w):
-            if k == 0:
-                return p0
-            p = prob[k - 1].get(h + (w,))
-            if p is not None:
-                return p
-            return bowp[k - 1].get(h, 1.0) * lower(k - 1, h[1:], w)
-
         symbols = [s for s in range(V) if s != blank]
-        for k in range(1, order + 1):
-            ctxs = counts[k - 1] if k > 1 else {(): counts[0].get((), collections.Counter())}
-            for h, cw in ctxs.items():
-                c, n1 = float(sum(cw.values())), float(len(cw))
-                if c == 0.0:                                         # no transcript at all: the uniform unigram
-                    for w in symbols:
-                        prob[0][(w,)] = p0
-                    continue
-                bowp[k - 1][h] = n1 / (c + n1)
-                for w in (list(cw) if k > 1 else symbols):
-                    prob[k - 1][h + (w,)] = (cw.get(w, 0) + n1 * lower(k - 1, h[1:], w)) / (c + n1)
-        grams = []
-        for k in range(1, order + 1):
-            items = {key: (math.log(p), math.log(bowp[k].get(key, 1.0)) if k < order else 0.0) for key, p in prob[k - 1].items()}
-            if k == 1:
-                items[(blank,)] = (ARPA_NEVER * _LN10, math.log(bowp[1].get((blank,), 1.0)) if order > 1 else 0.0)
-            grams.append(items)
-        return grams
+        if not counts[0]:                                            # no token at all: the uniform unigram, nothing above it
+            uniform = {(w,): (math.log(p0), 0.0) for w in symbols}
+            uniform[(blank,)] = (ARPA_NEVER * _LN10, 0.0)
+            return [uniform] + [{} for _ in range(order - 1)]
+        return _witten_bell(counts, p0, symbols, blank)
 
     @classmethod
     def from_transcripts(cls, seqs_of_token_ids, vocab, order=3, blank=0, min_count=1):
@@ -790,81 +822,34 @@ class UnitNgramLM:
             raise ValueError(f"names must list the {V} symbols")
         ids = {nm: i for i, nm in enumerate(names) if i != blank}
         ids["<s>"] = blank
-        grams, k = [], 0
-        with open(path, "r") as fo:
-            for raw in fo:
-                ln = raw.strip()
-                if not ln or ln == "\\data\\" or ln.startswith("ngram "):
-                    continue
-                if ln == "\\end\\":
-                    break
-                if ln.startswith("\\") and ln.endswith("-grams:"):
-                    k = int(ln[1:-len("-grams:")])
-                    if k != len(grams) + 1 or k > MAX_UNIT_ORDER:
-                        raise ValueError(f"{path}: the sections must be 1-grams .. n-grams in order, n <= {MAX_UNIT_ORDER} (got {k})")
-                    grams.append({})
-                    continue
-                if k == 0:
-                    raise ValueError(f"{path}: {ln!r} stands before the first section")
-                f = ln.split()
-                if len(f) not in (k + 1, k + 2):
-                    raise ValueError(f"{path}: {ln!r} is no {k}-gram line")
-                if any(w in ("</s>", "<unk>") for w in f[1:k + 1]):
-                    continue
-                try:
-                    key = tuple(ids[w] for w in f[1:k + 1])
-                except KeyError as e:
-                    raise ValueError(f"{path}: {e.args[0]!r} is no symbol of the alphabet") from None
-                grams[k - 1][key] = (float(f[0]) * _LN10, float(f[k + 1]) * _LN10 if len(f) == k + 2 else 0.0)
-        if not grams:
-            raise ValueError(f"{path}: no n-gram section")
+
+        def key_of(k, words):
+            if any(w in ("</s>", "<unk>") for w in words):
+                return None
+            try:
+                return tuple(ids[w] for w in words)
+            except KeyError as e:
+                raise ValueError(f"{path}: {e.args[0]!r} is no symbol of the alphabet") from None
+
+        grams = _read_arpa(path, MAX_UNIT_ORDER, key_of)
         grams[0].setdefault((blank,), (ARPA_NEVER * _LN10, 0.0))
         return cls._build(grams, V, blank)
 
     def to_arpa(self, path, names=None):
         """Write the standard ARPA text format (ln -> log10, 17 significant digits: ``from_arpa`` returns the same arrays)."""
         names = [str(i) for i in range(self.vocab)] if names is None else [str(x) for x in names]
-        names = [("<s>" if i == self.blank else nm) for i, nm in enumerate(names)]
-        with open(path, "w") as fo:
-            fo.write("\\data\\\n")
-            for k in range(1, self.order + 1):
-                fo.write(f"ngram {k}={self.ngrams[k - 1].shape[0]}\n")
-            for k in range(1, self.order + 1):
-                fo.write(f"\n\\{k}-grams:\n")
-                g, lp, bw = self.ngrams[k - 1], self.lp[k - 1].astype(np.float64) / _LN10, self.bw[k - 1].astype(np.float64) / _LN10
-                for i in range(g.shape[0]):
-                    text = " ".join(names[j] for j in g[i])
-                    fo.write(f"{float(lp[i])!r}\t{text}" + (f"\t{float(bw[i])!r}\n" if k < self.order else "\n"))
-            fo.write("\n\\end\\\n")
+        self._write_arpa(path, [("<s>" if i == self.blank else nm) for i, nm in enumerate(names)])
 
     # ---------------------------------------------------------------- persistence
     def save(self, path):
-        arrays = {"order": np.int64(self.order), "vocab": np.int64(self.vocab), "blank": np.int64(self.blank)}
-        for k in range(1, self.order + 1):
-            arrays[f"ngrams_{k}"], arrays[f"logp_{k}"], arrays[f"bow_{k}"] = self.ngrams[k - 1], self.lp[k - 1], self.bw[k - 1]
-        with open(path, "wb") as fo:
-            np.savez(fo, **arrays)
+        self._save(path, order=np.int64(self.order), vocab=np.int64(self.vocab), blank=np.int64(self.blank))
 
     @classmethod
     def load(cls, path):
         with np.load(path, allow_pickle=False) as z:
-            ks = range(1, int(z["order"]) + 1)
-            return cls([z[f"ngrams_{k}"] for k in ks], [z[f"logp_{k}"] for k in ks], [z[f"bow_{k}"] for k in ks],
-                       int(z["vocab"]), blank=int(z["blank"]))
+            return cls(*cls._saved_arrays(z), int(z["vocab"]), blank=int(z["blank"]))
 
     # ---------------------------------------------------------------- queries (the host's own statement)
-    def _entries(self):
-        if self._table is None:
-            tab = {}
-            for k in range(1, self.order + 1):
-                g, lp, bw = self.ngrams[k - 1].tolist(), self.lp[k - 1].astype(np.float64).tolist(), \
-                    self.bw[k - 1].astype(np.float64).tolist()
-                top = k == self.order
-                for i, key in enumerate(g):
-                    tab[tuple(key)] = (lp[i], 0.0 if top else bw[i])
-            self._table = tab
-        return self._table
-
     def context(self, prefix):
         """The last order-1 symbols of (blank,) + prefix.  A prefix that holds the blank counts from its last blank on."""
         y = [int(c) for c in prefix]
@@ -879,15 +864,7 @@ class UnitNgramLM:
         s = int(s)
         if not 0 <= s < self.vocab or s == self.blank:
             raise ValueError(f"symbol {s} is the blank or outside [0, {self.vocab})")
-        tab, h, acc = self._entries(), self.context(context), 0.0
-        while True:
-            e = tab.get(h + (s,))
-            if e is not None:
-                return float(np.float32(acc + e[0]))
-            c = tab.get(h) if h else None
-            if c is not None:
-                acc = acc + c[1]
-            h = h[1:]
+        return float(np.float32(self._backoff(self.context(context), s)))
 
     def logp_sequence(self, tokens):
         """The fp64 sum, in index order, of logp(tokens[:i], tokens[i]); 0.0 for no tokens."""
@@ -1002,14 +979,11 @@ class UnitNgramLM:
         device; the tensors live as long as the model)."""
         import torch
         from . import _lib
-        device = torch.device(device)
-        if device.type == "cuda" and device.index is None:
-            device = torch.device("cuda", torch.cuda.current_device())
-        t = self._device_tables.get(device)
-        if t is None:
+
+        def make(device):
             p = self.pack()
             tensors = {k: torch.from_numpy(p[k]).to(device).contiguous() for k in ("states", "succ")}
             st = _lib.UnitLMTables(tensors["states"].data_ptr(), tensors["succ"].data_ptr(), self.order, self.vocab, self.blank,
                                    p["states"].shape[0], p["succ"].shape[0], p["start"])
-            t = self._device_tables[device] = UnitLMDeviceTables(st, tensors)
-        return t
+            return UnitLMDeviceTables(st, tensors)
+        return _on_device(self._device_tables, device, make)

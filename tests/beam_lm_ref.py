@@ -1,72 +1,20 @@
-"""Helper of the LM-fusion tests (not collected): a plain-Python fused prefix beam search written against
-oracle.decode_ref, the shared inputs of the CPU and GPU tests, and the shared list of GPU cases.
-
-The fused search is ``decode_ref.prefix_beam_search`` with ONE change: every term that enters a prefix by an extension with a
-non-blank s gets  w = alpha * float(table[ctx(prefix), s]) + beta  added -- (p_b + p) + w, (p_nb + p) + w.  The blank update
-and the repeat branch that keeps the prefix are unchanged.  ctx(prefix) = its last order-1 symbols, left-padded with blank."""
+"""Helper of the LM-fusion tests (not collected): the fused prefix beam search as the best entry of prefix_beam_ref's one loop
+(stated there: ``decode_ref.prefix_beam_search`` with  w = alpha * float(table[ctx(prefix), s]) + beta  on every extension), the
+shared inputs of the CPU and GPU tests, and the shared list of GPU cases."""
 import numpy as np
 
-from oracle.decode_ref import NEG_INF, _lse
+from prefix_beam_ref import nbest_prefix_beam_search
 
 
 def fused_prefix_beam_search(probs=None, table=None, order=0, alpha=0.0, beta=0.0, beam_size=100, blank=0, logp=None):
     """probs (T,V) probabilities (their numpy log is taken, like decode_ref) or logp (T,V) log-probabilities.
     table: None or an array of shape (V,)*order.  Returns (prefix tuple, score, gap): score = -lse(p_b, p_nb) of the best
     entry; gap = the smallest margin a ranking decision of this search had -- per frame the score of the last kept candidate
-    minus the first dropped one, at the end the best minus the second-best final entry (inf if there was no such decision)."""
-    if logp is None:
-        with np.errstate(divide="ignore"):
-            logp = np.log(probs)
-    T, V = logp.shape
-    alpha, beta = float(alpha), float(beta)
-
-    def bonus(prefix, s):
-        if table is None:
-            return 0.0
-        n1 = order - 1
-        tail = prefix[-n1:] if n1 else ()
-        ctx = (blank,) * (n1 - len(tail)) + tuple(tail)
-        return alpha * float(table[ctx + (s,)]) + beta
-
-    gap = float("inf")
-    beam = [((), 0.0, NEG_INF)]
-    for t in range(T):
-        tab = {}  # prefix -> [p_b, p_nb]; dict keeps first-touch order
-
-        def slot(key):
-            e = tab.get(key)
-            if e is None:
-                e = [NEG_INF, NEG_INF]
-                tab[key] = e
-            return e
-
-        for s in range(V):
-            p = logp[t, s]
-            for prefix, p_b, p_nb in beam:
-                if s == blank:
-                    e = slot(prefix)
-                    e[0] = _lse(e[0], p_b + p, p_nb + p)
-                    continue
-                last = prefix[-1] if prefix else None
-                w = bonus(prefix, s)
-                e = slot(prefix + (s,))
-                if s != last:
-                    e[1] = _lse(e[1], (p_b + p) + w, (p_nb + p) + w)
-                else:
-                    e[1] = _lse(e[1], (p_b + p) + w)
-                    e2 = slot(prefix)
-                    e2[1] = _lse(e2[1], p_nb + p)
-        ranked = sorted(tab.items(), key=lambda kv: _lse(kv[1][0], kv[1][1]), reverse=True)
-        if len(ranked) > beam_size:
-            kept, dropped = _lse(*ranked[beam_size - 1][1]), _lse(*ranked[beam_size][1])
-            if kept != NEG_INF:
-                gap = min(gap, kept - dropped)
-        ranked = ranked[:beam_size]
-        beam = [(k, v[0], v[1]) for k, v in ranked]
-    if len(beam) > 1 and _lse(beam[0][1], beam[0][2]) != NEG_INF:
-        gap = min(gap, _lse(beam[0][1], beam[0][2]) - _lse(beam[1][1], beam[1][2]))
-    best = beam[0]
-    return best[0], -_lse(best[1], best[2]), gap
+    minus the first dropped one, at the end the best minus the second-best final entry (inf if there was no such decision).
+    The loop is prefix_beam_ref's, asked for a list of one."""
+    hyps, gap = nbest_prefix_beam_search(probs=probs, table=table, order=order, alpha=alpha, beta=beta, beam_size=beam_size,
+                                         blank=blank, logp=logp, nbest=1)
+    return hyps[0][0], hyps[0][1], gap
 
 
 def random_table(V, order, blank, seed, scale=2.0):

@@ -10,8 +10,6 @@ import functools
 
 import numpy as np
 
-from oracle.decode_ref import NEG_INF, _lse
-
 import beam_lm_ref as R
 import beam_wide_cases as W
 import nbest_ref as NR
@@ -90,49 +88,9 @@ def random_unit_lm(V, order, blank, seed, n_ctx=40, n_succ=6, scale=2.0):
 
 
 def callable_search(logp, bonus, beam_size, blank, nbest):
-    """nbest_ref.nbest_prefix_beam_search's loop with the table lookup replaced by ``bonus(prefix, s)`` -- restated here because
-    that oracle takes a dense table and V = 1024 at order 3 has none.  Returns (hyps, gap) as it does."""
-    T, V = logp.shape
-    gap = float("inf")
-    beam = [((), 0.0, NEG_INF)]
-    for t in range(T):
-        tab = {}
-
-        def slot(key):
-            e = tab.get(key)
-            if e is None:
-                e = [NEG_INF, NEG_INF]
-                tab[key] = e
-            return e
-
-        for s in range(V):
-            p = logp[t, s]
-            for prefix, p_b, p_nb in beam:
-                if s == blank:
-                    e = slot(prefix)
-                    e[0] = _lse(e[0], p_b + p, p_nb + p)
-                    continue
-                last = prefix[-1] if prefix else None
-                w = bonus(prefix, s)
-                e = slot(prefix + (s,))
-                if s != last:
-                    e[1] = _lse(e[1], (p_b + p) + w, (p_nb + p) + w)
-                else:
-                    e[1] = _lse(e[1], (p_b + p) + w)
-                    e2 = slot(prefix)
-                    e2[1] = _lse(e2[1], p_nb + p)
-        ranked = sorted(tab.items(), key=lambda kv: _lse(kv[1][0], kv[1][1]), reverse=True)
-        if len(ranked) > beam_size:
-            kept, dropped = _lse(*ranked[beam_size - 1][1]), _lse(*ranked[beam_size][1])
-            if kept != NEG_INF:
-                gap = min(gap, kept - dropped)
-        ranked = ranked[:beam_size]
-        beam = [(k, v[0], v[1]) for k, v in ranked]
-    sc = [_lse(b[1], b[2]) for b in beam]
-    for r in range(min(nbest, len(beam))):
-        if r + 1 < len(beam) and sc[r] != NEG_INF:
-            gap = min(gap, sc[r] - sc[r + 1])
-    return [(b[0], -s) for b, s in zip(beam[:nbest], sc)], gap
+    """nbest_ref.nbest_prefix_beam_search with ``bonus(prefix, s)`` in place of the table lookup: V = 1024 at order 3 has no dense
+    table.  Returns (hyps, gap) as it does."""
+    return NR.nbest_prefix_beam_search(logp=logp, bonus=bonus, beam_size=beam_size, blank=blank, nbest=nbest)
 
 
 def dict_bonus(d, order, blank, alpha, beta):
@@ -151,7 +109,7 @@ def dict_bonus(d, order, blank, alpha, beta):
 
 def fused_search(d, model, logp, alpha, beta, beam_size, blank, nbest, form=None):
     """The fused search of one utterance: over the dense table of ``model.to_dense()`` through the existing oracle where V**order <=
-    2**25 (form "dense"), else the restated loop over the dict statement (form "callable"); ``form`` forces one."""
+    2**25 (form "dense"), else the same loop with the dict statement as its bonus (form "callable"); ``form`` forces one."""
     V, order = model.vocab, model.order
     if form is None:
         form = "dense" if V ** order <= DENSE_MAX else "callable"
