@@ -1336,6 +1336,45 @@ int pgasr_ctc_grad_from_lattice_wide(const float* log_probs, const int32_t* inpu
                                      void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * A12-WIDE  The multi-sample, entropy and KL objectives (A12) for rows of 1 <= V <= 1024 symbols: the four kernels of those
+ * objectives that hold one symbol per lane, on the rows of A5-WIDE / A9-WIDE (lane l holding NV consecutive labels).  Everything
+ * else the objectives run (collapse, edit distance, pgasr_pg_rewards_multi, pgasr_pg_loss_value_multi, the lattice) never looks at
+ * V.  The narrow entries keep what they accept (V <= 64) and what they launch.  Every sum is taken in a fixed order -- a lane's
+ * NV terms in label order, then one wave butterfly; frames in t order -- so two calls give the same bits, and with V <= 64 the
+ * operations are the narrow kernel's, one for one.  Checked before any HIP call, with the narrow twins' codes: a missing required
+ * pointer, T, B or V <= 0, K outside 1..PGASR_MAX_SAMPLES, a blank outside [0, V) -> PGASR_ERR_INVALID_ARG; V > 1024,
+ * 2 * Lmax + 1 > 2048 -> PGASR_ERR_UNSUPPORTED; a workspace that is missing or too small -> PGASR_ERR_WORKSPACE.
+ *   pgasr_frame_sample_multi_wide: pgasr_frame_sample_multi and, with utt_ids != NULL, pgasr_frame_sample_multi_ids (ctr_base is
+ *     then ignored, ctr_stride >= 1 is required and T * ctr_stride must fit counter word 0, else PGASR_ERR_UNSUPPORTED).  The
+ *     row's maximum, cdf and total are pgasr_frame_argmax_sample_wide's and are formed once; draw k uses Philox word 0 of counter
+ *     (t*ctr_stride + id, offset, 0 or 1, k), the same u and the same min(#{v : cdf_v <= u * total}, V - 1).  Draw 0 is
+ *     pgasr_frame_argmax_sample_wide's sample and greedy_path its arg-max, bit for bit.
+ *   pgasr_frame_entropy_wide, pgasr_frame_kl_wide: pgasr_frame_entropy and pgasr_frame_kl, argument for argument: one workgroup of
+ *     16 waves per utterance, frames added in t order with fp64 carries.  p = 0 adds exactly 0; the reference's log-probability is
+ *     floored at PGASR_KL_LOG_FLOOR; q = p gives exactly 0.
+ *   pgasr_ctc_grad_from_lattice_multi_wide: pgasr_ctc_grad_from_lattice_multi, _multi_ent and _multi_kl in one entry, on the
+ *     workspace of pgasr_ctc_loss_grad or pgasr_ctc_loss_grad_wide (same format: either lattice serves).  One wave per (t,b) row,
+ *     one write: the CTC part of pgasr_ctc_grad_from_lattice_wide, then pg_coef[k,b] (softmax - onehot(pg_paths[k,t,b])) in k
+ *     order, then ent_scale_b p (ln p + H) when ent_scale is given, then kl_scale_b p (ln p - lnq - KL) when ref_log_probs and
+ *     kl_scale are (both or neither, else PGASR_ERR_INVALID_ARG); a KL term of 0 leaves the entry as it is.  Rows t >=
+ *     input_lengths[b] are written as zeros, nll = +inf gives no CTC part, log p = -inf gives occupancy 0, gradient entry 0 and
+ *     entropy and KL terms 0, never NaN.  The pass without tails holds no code of them.
+ * ---------------------------------------------------------------------------------------- */
+int pgasr_frame_sample_multi_wide(const float* scores, int T, int B, int V, int K, uint64_t seed, uint32_t offset,
+                                  int ctr_stride, int ctr_base, const int32_t* utt_ids /* may be NULL */,
+                                  int32_t* greedy_path /* may be NULL */, int32_t* sample_paths /* (K,T,B) */, void* stream);
+int pgasr_frame_entropy_wide(const float* log_probs, const int32_t* input_lengths, int T, int B, int V,
+                             float beta, float inv_global_batch, float* ent_mean, float* ent_scale, void* stream);
+int pgasr_frame_kl_wide(const float* log_probs, const float* ref_log_probs, const int32_t* input_lengths, int T, int B, int V,
+                        float gamma, float inv_global_batch, float* kl_mean, float* kl_scale, void* stream);
+int pgasr_ctc_grad_from_lattice_multi_wide(const float* log_probs, const int32_t* input_lengths,
+                                           const int32_t* target_lengths, int T, int B, int V, int Lmax, int blank,
+                                           const float* utt_scale, int K, const float* pg_coef, const int32_t* pg_paths,
+                                           const float* ent_scale /* may be NULL */, const float* ref_log_probs /* may be NULL */,
+                                           const float* kl_scale /* may be NULL */, float* grad_logits,
+                                           void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * A12-SCORE  Lattice-free CTC scorer (csrc/hyp_score.hip): the exact -log p(y | x) of every hypothesis of an N-best list, one fp64
  * number per hypothesis.  The forward sweep of pgasr_ctc_hyp_lattice alone, with its rows kept in LDS: no workspace, nothing
  * written but the result, so none of the lattice's limits (K <= 16, V <= 64) and none of its 2*K*B*T*roundup64(2*Lh+1)*4 bytes.

@@ -858,6 +858,148 @@ static int ctc_launch_grad_wide(const float* log_probs, const int32_t* input_len
     return PGASR_OK;
 }
 
+// ---- the multi-sample gradient pass for wide rows, with the entropy and KL tails (pgasr_ctc_grad_from_lattice_multi_wide; A12-WIDE) ----
+// ctc_grad_multi_kernel with NV labels per lane: the CTC part of ctc_grad_wide_kernel, then the K terms
+// pg_coef[k,b] (softmax - onehot(pg_paths[k,t,b])) in k order, then ent_scale_b p (ln p + H), then kl_scale_b p (ln p - lnq - KL)
+// under ctc_entropy_kl_grad's rule that a zero term leaves g untouched.  H and KL add the lane's NV terms in label order before the
+// one wave_sum.  TAIL: 0 = none, 1 = entropy, 2 = entropy (nullable) and KL; the plain pass holds no code of the tails.  With NV = 1
+// every sum is ctc_grad_multi_kernel's, in its order.
+// The label offsets are read outer-first: lane l reads lab_off[v0] and lab_off[min(v0 + NV, V)], the bounds of the concatenated lists
+// of ALL its labels, and reads the NV - 1 offsets between them only when the two differ.  A lane none of whose labels occurs in the
+// target -- with L labels over V / NV groups, most lanes at V >= 256 -- does two loads where ctc_grad_wide_kernel does NV + 1, and
+// every label's (empty) sum is the 0 the walk would have given: the summation order is unchanged.
+template <int NV, int TAIL>
+__global__ __launch_bounds__(64 * CTC_WIDE_WPB) void ctc_grad_multi_wide_kernel(
+    const float* __restrict__ lp, const int32_t* __restrict__ in_len,
+    const int32_t* __restrict__ tg_len, int T, int B, int V, int vec, int Lmax, int Smax, int blank, CtcWs ws,
+    const float* __restrict__ utt_scale, int K, const float* __restrict__ pg_coef, const int32_t* __restrict__ pg_paths,
+    const float* __restrict__ ent_scale, const float* __restrict__ ref_lp, const float* __restrict__ kl_scale,
+    float* __restrict__ grad) {
+    const int lane = threadIdx.x & 63;
+    const long long w = (long long)blockIdx.x * CTC_WIDE_WPB + (threadIdx.x >> 6);
+    if (w >= (long long)T * B) return;
+    const int t = (int)(w / B), b = (int)(w % B);
+    int Tb = in_len[b]; Tb = Tb < 0 ? 0 : (Tb > T ? T : Tb);
+    int Lb = tg_len[b]; Lb = Lb < 0 ? 0 : (Lb > Lmax ? Lmax : Lb);
+    const size_t o = ((size_t)t * B + b) * V;
+    const int v0 = lane * NV;
+    float g[NV];
+#pragma unroll
+    for (int i = 0; i < NV; ++i) g[i] = 0.f;
+    if (t >= Tb) {
+        wide_row_store<NV>(grad + o, V, lane, vec != 0, g);
+        return;
+    }
+    float lpv[NV], sm[NV];
+    wide_row_load<NV>(lp + o, V, lane, vec != 0, 0.f, lpv);
+#pragma unroll
+    for (int i = 0; i < NV; ++i) sm[i] = (v0 + i < V) ? __expf(lpv[i]) : 0.f;
+
+    const double nll = ws.nll64[b];
+    if (nll != INFINITY) {            // uniform over the wave
+        const int S = 2 * Lb + 1;
+        const float* al = ws.alpha + ((size_t)b * T + t) * ws.SP;
+        const float* be = ws.beta + ((size_t)b * T + t) * ws.SP;
+        const double cst = ws.amax[(size_t)b * T + t] + ws.bmax[(size_t)b * T + t] + nll;
+        const float lpb = lp[o + blank];
+        const float cb = (lpb == -INFINITY) ? 0.f : (float)(cst - (double)lpb);
+        float accb = 0.f;
+        for (int s = 2 * lane; s < S; s += 128)
+            accb += __expf((al[s] + be[s]) + cb);
+        accb = wave_sum(accb);
+        const int32_t* lo = ws.lab_off + (size_t)b * (V + 1);
+        const int32_t* ls = ws.lab_states + (size_t)b * Smax;
+        const float sc = utt_scale ? utt_scale[b] : 1.f;
+        const int vend = (v0 + NV < V) ? v0 + NV : V;
+        const int lo0 = (v0 < V) ? lo[v0] : 0;
+        const int lo1 = (v0 < V) ? lo[vend] : 0;
+        int off[NV + 1];
+#pragma unroll
+        for (int i = 0; i <= NV; ++i) off[i] = lo0;                       // no label of this lane in the target: every list is empty
+        if (lo0 != lo1) {
+#pragma unroll
+            for (int i = 1; i < NV; ++i) off[i] = (v0 + i <= V) ? lo[v0 + i] : 0;
+            off[NV] = lo1;            // read by label v0 + NV - 1 alone, which exists only when vend = v0 + NV
+        }
+#pragma unroll
+        for (int i = 0; i < NV; ++i) {
+            const int v = v0 + i;
+            if (v < V) {
+                float occ = accb;
+                if (v != blank) {
+                    float acc = 0.f;
+                    const float cl = (lpv[i] == -INFINITY) ? 0.f : (float)(cst - (double)lpv[i]);
+                    for (int j = off[i]; j < off[i + 1]; ++j) {
+                        const int s = ls[j];
+                        acc += __expf((al[s] + be[s]) + cl);
+                    }
+                    occ = acc;
+                }
+                g[i] = sc * (sm[i] - occ);
+            }
+        }
+    }
+    const size_t TB = (size_t)T * B;
+    for (int k = 0; k < K; ++k) {
+        const int pk = pg_paths[k * TB + (size_t)t * B + b];
+        const float c = pg_coef[(size_t)k * B + b];
+#pragma unroll
+        for (int i = 0; i < NV; ++i) g[i] += c * (sm[i] - (v0 + i == pk ? 1.f : 0.f));
+    }
+    if constexpr (TAIL >= 1) {
+        if (TAIL == 1 || ent_scale != nullptr) {
+            float plp[NV], s = 0.f;
+#pragma unroll
+            for (int i = 0; i < NV; ++i) {
+                plp[i] = sm[i] > 0.f ? sm[i] * lpv[i] : 0.f;
+                s = (i == 0) ? plp[i] : s + plp[i];
+            }
+            const float H = -wave_sum(s);
+            const float es = ent_scale[b];
+#pragma unroll
+            for (int i = 0; i < NV; ++i) g[i] += sm[i] > 0.f ? es * fmaf(sm[i], H, plp[i]) : 0.f;
+        }
+    }
+    if constexpr (TAIL == 2) {
+        float d[NV];
+        wide_row_load<NV>(ref_lp + o, V, lane, vec != 0, 0.f, d);
+        float s = 0.f;
+#pragma unroll
+        for (int i = 0; i < NV; ++i) {
+            d[i] = sm[i] > 0.f ? sm[i] * (lpv[i] - fmaxf(d[i], KL_LOG_FLOOR)) : 0.f;
+            s = (i == 0) ? d[i] : s + d[i];
+        }
+        const float kl = wave_sum(s);
+        const float ks = kl_scale[b];
+#pragma unroll
+        for (int i = 0; i < NV; ++i) {
+            const float term = ks * fmaf(-sm[i], kl, d[i]);
+            g[i] = term != 0.f ? g[i] + term : g[i];
+        }
+    }
+    wide_row_store<NV>(grad + o, V, lane, vec != 0, g);
+}
+
+template <int TAIL>
+static int ctc_launch_grad_multi_wide(const float* log_probs, const int32_t* input_lengths, const int32_t* target_lengths, int T, int B,
+                                      int V, int Lmax, int blank, const CtcWs& ws, const float* utt_scale, int K, const float* pg_coef,
+                                      const int32_t* pg_paths, const float* ent_scale, const float* ref_log_probs,
+                                      const float* kl_scale, float* grad_logits, void* stream) {
+    const long long waves = (long long)T * B;
+    const unsigned blocks = (unsigned)((waves + CTC_WIDE_WPB - 1) / CTC_WIDE_WPB);
+    // one `vec` for the launch: the row loads of log_probs and ref_log_probs and the row store must all be aligned
+#define PGASR_CALL(NV) PGASR_LAUNCH_KERNEL((ctc_grad_multi_wide_kernel<NV, TAIL>), dim3(blocks), dim3(64 * CTC_WIDE_WPB), 0,                  \
+                                           (hipStream_t)stream, log_probs, input_lengths, target_lengths, T, B, V,                              \
+                                           (wide_vec_ok<NV>(log_probs, grad_logits, V) &&                                                       \
+                                            (TAIL < 2 || wide_vec_ok<NV>(ref_log_probs, ref_log_probs, V))) ? 1 : 0,                            \
+                                           Lmax > 0 ? Lmax : 1, 2 * Lmax + 1, blank, ws, utt_scale, K, pg_coef, pg_paths, ent_scale,            \
+                                           ref_log_probs, kl_scale, grad_logits)
+    PGASR_WIDE_DISPATCH(V, PGASR_CALL);
+#undef PGASR_CALL
+    PGASR_CHECK_LAUNCH();
+    return PGASR_OK;
+}
+
 }  // namespace
 
 extern "C" size_t pgasr_ctc_workspace_bytes(int T, int B, int V, int Lmax) {
@@ -1161,4 +1303,29 @@ extern "C" int pgasr_ctc_grad_from_lattice_wide(const float* log_probs, const in
     if (!ctc_ws_bind(T, B, V, 2 * Lmax + 1, &ws, workspace, workspace_bytes)) return PGASR_ERR_WORKSPACE;
     return ctc_launch_grad_wide(log_probs, input_lengths, target_lengths, T, B, V, Lmax, blank, ws, utt_scale, pg_coef, pg_path,
                                 pg_coef_per_frame ? 1 : 0, grad_logits, stream);
+}
+
+// ---- A12-WIDE: pgasr_ctc_grad_from_lattice_multi with its entropy and KL forms in one entry, for 1 <= V <= 1024 ----
+// ent_scale NULL and ref_log_probs / kl_scale NULL: the plain instantiation; ent_scale alone: the entropy one; ref_log_probs and
+// kl_scale (together): the one with both tails, ent_scale nullable there.
+extern "C" int pgasr_ctc_grad_from_lattice_multi_wide(const float* log_probs, const int32_t* input_lengths,
+                                                      const int32_t* target_lengths, int T, int B, int V, int Lmax, int blank,
+                                                      const float* utt_scale, int K, const float* pg_coef, const int32_t* pg_paths,
+                                                      const float* ent_scale, const float* ref_log_probs, const float* kl_scale,
+                                                      float* grad_logits, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!log_probs || !input_lengths || !target_lengths || !grad_logits || !pg_coef || !pg_paths) return PGASR_ERR_INVALID_ARG;
+    if ((ref_log_probs == nullptr) != (kl_scale == nullptr)) return PGASR_ERR_INVALID_ARG;
+    if (K < 1 || K > PGASR_MAX_SAMPLES) return PGASR_ERR_INVALID_ARG;
+    const int ok = ctc_args_ok_wide(T, B, V, Lmax, blank);
+    if (ok != PGASR_OK) return ok;
+    CtcWs ws;
+    if (!ctc_ws_bind(T, B, V, 2 * Lmax + 1, &ws, workspace, workspace_bytes)) return PGASR_ERR_WORKSPACE;
+    if (kl_scale)
+        return ctc_launch_grad_multi_wide<2>(log_probs, input_lengths, target_lengths, T, B, V, Lmax, blank, ws, utt_scale, K, pg_coef,
+                                             pg_paths, ent_scale, ref_log_probs, kl_scale, grad_logits, stream);
+    if (ent_scale)
+        return ctc_launch_grad_multi_wide<1>(log_probs, input_lengths, target_lengths, T, B, V, Lmax, blank, ws, utt_scale, K, pg_coef,
+                                             pg_paths, ent_scale, nullptr, nullptr, grad_logits, stream);
+    return ctc_launch_grad_multi_wide<0>(log_probs, input_lengths, target_lengths, T, B, V, Lmax, blank, ws, utt_scale, K, pg_coef,
+                                         pg_paths, nullptr, nullptr, nullptr, grad_logits, stream);
 }

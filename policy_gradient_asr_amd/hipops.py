@@ -124,9 +124,10 @@ def _workspace(nbytes, device, tag):
     return buf
 
 
-# ---- alphabets of 65 .. 1024 symbols (include/pgasr_hip.h, A5-WIDE / A9-WIDE) ----
+# ---- alphabets of 65 .. 1024 symbols (include/pgasr_hip.h, A5-WIDE / A9-WIDE / A12-WIDE) ----
 MAX_VOCAB_NARROW = 64            # one label per lane: every entry point without a _wide form
-MAX_VOCAB_WIDE = 1024            # PGASR_MAX_VOCAB_WIDE: log-softmax, arg-max / sample, CTC lattice and gradient pass
+MAX_VOCAB_WIDE = 1024            # PGASR_MAX_VOCAB_WIDE: log-softmax, arg-max / sample, CTC lattice and gradient pass; the K-draw
+                                 # sampler, the entropy and KL statistics and the multi-sample gradient pass with their tails
 
 
 def _wide(V, wide, what):
@@ -224,6 +225,34 @@ def _grad_pass(entry, log_probs, input_lengths, target_lengths, handle, utt_scal
     return grad
 
 
+def _grad_pass_multi_wide(log_probs, input_lengths, target_lengths, handle, utt_scale, pg_coef, pg_paths, ent_scale, ref_log_probs,
+                          kl_scale):
+    """``pgasr_ctc_grad_from_lattice_multi_wide`` with ``_grad_pass``'s checks of the optional terms."""
+    lib = _lib.load()
+    ws, Lmax, blank = handle
+    T, B, V = log_probs.shape
+    K = pg_paths.shape[0]
+    _req(log_probs, torch.float32, "log_probs")
+    _req(utt_scale, torch.float32, "utt_scale"); _req(pg_coef, torch.float32, "pg_coef"); _req(pg_paths, torch.int32, "pg_paths")
+    if ent_scale is not None:
+        _req(ent_scale, torch.float32, "ent_scale")
+        if tuple(ent_scale.shape) != (B,):
+            raise _lib.PgasrError(f"ent_scale must be ({B},); got {tuple(ent_scale.shape)}")
+    if ref_log_probs is not None or kl_scale is not None:
+        if ref_log_probs is None or kl_scale is None:
+            raise _lib.PgasrError("the KL term takes ref_log_probs and kl_scale together")
+        _req(ref_log_probs, torch.float32, "ref_log_probs"); _req(kl_scale, torch.float32, "kl_scale")
+        if ref_log_probs.shape != log_probs.shape or tuple(kl_scale.shape) != (B,):
+            raise _lib.PgasrError(f"ref_log_probs must be {tuple(log_probs.shape)} and kl_scale ({B},); got "
+                                  f"{tuple(ref_log_probs.shape)} and {tuple(kl_scale.shape)}")
+    grad = torch.empty_like(log_probs)
+    st = lib.pgasr_ctc_grad_from_lattice_multi_wide(_p(log_probs), _p(input_lengths), _p(target_lengths), T, B, V, Lmax, blank,
+                                                    _p(utt_scale), K, _p(pg_coef), _p(pg_paths), _p(ent_scale), _p(ref_log_probs),
+                                                    _p(kl_scale), _p(grad), _p(ws), ws.numel(), _stream())
+    _lib.check(st, "pgasr_ctc_grad_from_lattice_multi_wide")
+    return grad
+
+
 def _loss_value(entry, log_probs, paths, paths_name, input_lengths, nll, utt_scale, pg_coef, K=(), mid=(), tail=()):
     """The three ``pg_loss_value*`` wrappers: entry(log_probs, paths, *K, input_lengths, nll, utt_scale, pg_coef, *mid, T, B, V,
     *tail, terms, stream) -> terms (B,) fp32."""
@@ -246,7 +275,8 @@ def ctc_grad_from_lattice(log_probs, input_lengths, target_lengths, handle, utt_
     T, B, V = log_probs.shape
     if _wide(V, wide, "ctc_grad_from_lattice"):
         if ent_scale is not None or ref_log_probs is not None or kl_scale is not None:
-            raise _lib.PgasrError(f"ctc_grad_from_lattice: the entropy and KL terms take at most {MAX_VOCAB_NARROW} symbols (V = {V})")
+            raise _lib.PgasrError(f"ctc_grad_from_lattice: the entropy and KL terms take at most {MAX_VOCAB_NARROW} symbols (V = {V}); "
+                                  f"ctc_grad_from_lattice_multi has them for wide rows")
         return _grad_pass("pgasr_ctc_grad_from_lattice_wide", log_probs, input_lengths, target_lengths, handle, utt_scale, pg_coef,
                           pg_path, "pg_path", (pg_coef, pg_path, _coef_per_frame(pg_coef, T, B)))
     return _grad_pass("pgasr_ctc_grad_from_lattice", log_probs, input_lengths, target_lengths, handle, utt_scale, pg_coef, pg_path,
@@ -254,12 +284,13 @@ def ctc_grad_from_lattice(log_probs, input_lengths, target_lengths, handle, utt_
                       ref_log_probs=ref_log_probs, kl_scale=kl_scale)
 
 
-def frame_kl(log_probs, ref_log_probs, input_lengths, kl_weight=0.0, inv_global_batch=1.0):
+def frame_kl(log_probs, ref_log_probs, input_lengths, kl_weight=0.0, inv_global_batch=1.0, wide=None):
     """The KL of the frame policy from a frozen reference policy (``pgasr_frame_kl``): log_probs, ref_log_probs (T,B,V) fp32,
     input_lengths (B) int32 -> (kl_mean (B), kl_scale (B)) fp32 in one launch: kl_mean[b] = the MEAN over the utterance's own frames of
     KL(p || q) = sum_v p (ln p - max(ln q, -104)) (nats; 0 for an empty utterance, not clamped at 0), kl_scale[b] =
     kl_weight * inv_global_batch / max(T_b,1), what the gradient passes take as ``kl_scale``.  Deterministic; symbols with p = 0 add
-    exactly 0 and a zero reference probability costs the floor, never inf."""
+    exactly 0 and a zero reference probability costs the floor, never inf.
+    V > 64 (or wide=True): ``pgasr_frame_kl_wide``, the same arguments and sums."""
     lib = _lib.load()
     _req(log_probs, torch.float32, "log_probs"); _req(ref_log_probs, torch.float32, "ref_log_probs")
     _req(input_lengths, torch.int32, "input_lengths")
@@ -267,28 +298,31 @@ def frame_kl(log_probs, ref_log_probs, input_lengths, kl_weight=0.0, inv_global_
         raise _lib.PgasrError("frame_kl wants log_probs and ref_log_probs (T,B,V) and input_lengths (B,)")
     T, B, V = log_probs.shape
     out = torch.empty(2, B, dtype=torch.float32, device=log_probs.device)
+    entry = "pgasr_frame_kl_wide" if _wide(V, wide, "frame_kl") else "pgasr_frame_kl"
     with _timed("frame_kl_kernel"):
-        st = lib.pgasr_frame_kl(_p(log_probs), _p(ref_log_probs), _p(input_lengths), T, B, V, float(kl_weight),
-                                float(inv_global_batch), out[0].data_ptr(), out[1].data_ptr(), _stream())
-    _lib.check(st, "pgasr_frame_kl")
+        st = getattr(lib, entry)(_p(log_probs), _p(ref_log_probs), _p(input_lengths), T, B, V, float(kl_weight),
+                                 float(inv_global_batch), out[0].data_ptr(), out[1].data_ptr(), _stream())
+    _lib.check(st, entry)
     return out[0], out[1]
 
 
-def frame_entropy(log_probs, input_lengths, entropy_weight=0.0, inv_global_batch=1.0):
+def frame_entropy(log_probs, input_lengths, entropy_weight=0.0, inv_global_batch=1.0, wide=None):
     """The entropy of the frame policy (``pgasr_frame_entropy``): log_probs (T,B,V) fp32, input_lengths (B) int32 ->
     (ent_mean (B), ent_scale (B)) fp32 in one launch: ent_mean[b] = the MEAN over the utterance's own frames of
     H = -sum_v p ln p (nats; 0 for an empty utterance), ent_scale[b] = entropy_weight * inv_global_batch / max(T_b,1), what the
-    gradient passes take as ``ent_scale``.  Deterministic; -inf entries add exactly 0."""
+    gradient passes take as ``ent_scale``.  Deterministic; -inf entries add exactly 0.
+    V > 64 (or wide=True): ``pgasr_frame_entropy_wide``, the same arguments and sums."""
     lib = _lib.load()
     _req(log_probs, torch.float32, "log_probs"); _req(input_lengths, torch.int32, "input_lengths")
     if log_probs.dim() != 3 or input_lengths.numel() != log_probs.shape[1]:
         raise _lib.PgasrError("frame_entropy wants log_probs (T,B,V) and input_lengths (B,)")
     T, B, V = log_probs.shape
     out = torch.empty(2, B, dtype=torch.float32, device=log_probs.device)
+    entry = "pgasr_frame_entropy_wide" if _wide(V, wide, "frame_entropy") else "pgasr_frame_entropy"
     with _timed("frame_entropy_kernel"):
-        st = lib.pgasr_frame_entropy(_p(log_probs), _p(input_lengths), T, B, V, float(entropy_weight), float(inv_global_batch),
-                                     out[0].data_ptr(), out[1].data_ptr(), _stream())
-    _lib.check(st, "pgasr_frame_entropy")
+        st = getattr(lib, entry)(_p(log_probs), _p(input_lengths), T, B, V, float(entropy_weight), float(inv_global_batch),
+                                 out[0].data_ptr(), out[1].data_ptr(), _stream())
+    _lib.check(st, entry)
     return out[0], out[1]
 
 
@@ -319,13 +353,18 @@ BASELINES = {"hypothesis": 0, "leave_one_out": 1}
 
 
 def ctc_grad_from_lattice_multi(log_probs, input_lengths, target_lengths, handle, utt_scale, pg_coef, pg_paths, ent_scale=None,
-                                ref_log_probs=None, kl_scale=None):
+                                ref_log_probs=None, kl_scale=None, wide=None):
     """``ctc_grad_from_lattice`` with K sampled paths: pg_paths (K,T,B) int32, pg_coef (K,B) fp32; the K REINFORCE terms are
-    added in k order after the CTC part, in the same pass."""
-    T, B, _ = log_probs.shape
+    added in k order after the CTC part, in the same pass.
+    V > 64 (or wide=True): ``pgasr_ctc_grad_from_lattice_multi_wide``, ONE entry that takes ent_scale, ref_log_probs and kl_scale as
+    nullable pointers where the narrow family has three."""
+    T, B, V = log_probs.shape
     K = pg_paths.shape[0]
     if pg_paths.dim() != 3 or tuple(pg_paths.shape[1:]) != (T, B) or tuple(pg_coef.shape) != (K, B):
         raise _lib.PgasrError(f"ctc_grad_from_lattice_multi wants pg_paths (K,{T},{B}) and pg_coef (K,{B})")
+    if _wide(V, wide, "ctc_grad_from_lattice_multi"):
+        return _grad_pass_multi_wide(log_probs, input_lengths, target_lengths, handle, utt_scale, pg_coef, pg_paths, ent_scale,
+                                     ref_log_probs, kl_scale)
     return _grad_pass("pgasr_ctc_grad_from_lattice_multi", log_probs, input_lengths, target_lengths, handle, utt_scale, pg_coef,
                       pg_paths, "pg_paths", (K, pg_coef, pg_paths), ent_scale=ent_scale, ref_log_probs=ref_log_probs,
                       kl_scale=kl_scale)
@@ -538,10 +577,11 @@ def frame_argmax_sample(scores, seed=0, offset=0, want_greedy=True, want_sample=
 
 
 def frame_sample_multi(scores, num_samples, seed=0, offset=0, want_greedy=False, batch_stride=0, batch_offset=0, out=None,
-                       utt_ids=None):
+                       utt_ids=None, wide=None):
     """K draws per frame (include/pgasr_hip.h, pgasr_frame_sample_multi): returns (greedy (T,B) or None, samples (K,T,B)) int32.
     Draw 0 is ``frame_argmax_sample``'s sample; batch_stride / batch_offset / utt_ids as there.  out = (greedy or None, samples) to
-    write into (contiguous int32)."""
+    write into (contiguous int32).
+    V > 64 (or wide=True): ``pgasr_frame_sample_multi_wide``, one entry for both addressings, the same draws."""
     lib = _lib.load()
     _req(scores, torch.float32, "scores")
     T, B, V = scores.shape
@@ -556,6 +596,12 @@ def frame_sample_multi(scores, num_samples, seed=0, offset=0, want_greedy=False,
     else:
         g = torch.empty(T, B, dtype=torch.int32, device=scores.device) if want_greedy else None
         s = torch.empty(K, T, B, dtype=torch.int32, device=scores.device)
+    if _wide(V, wide, "frame_sample_multi"):
+        st = lib.pgasr_frame_sample_multi_wide(_p(scores), T, B, V, K, int(seed) & (2 ** 64 - 1), int(offset) & 0xFFFFFFFF,
+                                               int(batch_stride), 0 if utt_ids is not None else int(batch_offset), _p(utt_ids),
+                                               _p(g), _p(s), _stream())
+        _lib.check(st, "pgasr_frame_sample_multi_wide")
+        return g, s
     if utt_ids is not None:
         st = lib.pgasr_frame_sample_multi_ids(_p(scores), T, B, V, K, int(seed) & (2 ** 64 - 1), int(offset) & 0xFFFFFFFF,
                                               int(batch_stride), _p(utt_ids), _p(g), _p(s), _stream())

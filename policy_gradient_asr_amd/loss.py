@@ -134,6 +134,9 @@ class PGCTCLossFn(torch.autograd.Function):
         # Kernel family: the single-path kernels (per_step's (T,B) coefficients included) for the one configuration they were
         # written for, the multi-sample kernels -- K = 1 included -- for every other, their _seq pair when Lh is set.
         single = K == 1 and not loo and Lh is None
+        # Above 64 symbols the single-path gradient pass has no entropy or KL form: such a call samples, collapses and scores as a
+        # single-path call does and takes the multi-sample pass and loss value with K = 1 (samples = sample[None], coef[None]).
+        single_pass = single and not (V > hipops.MAX_VOCAB_NARROW and (beta > 0 or gamma > 0))
         greedy_row = not loo and beam == 0      # the greedy path is sampled along and collapsed as row 0
         P = K + (0 if loo else 1)               # path sets that are collapsed and scored: [hypothesis,] sample 0 .. K-1
         inv_gb = 1.0 / float(opt.global_batch)
@@ -217,9 +220,12 @@ class PGCTCLossFn(torch.autograd.Function):
         ent = {"ent_scale": ent_scale} if beta > 0 else {}        # weight 0: the calls as they were
         if gamma > 0:
             ent.update(ref_log_probs=ref_log_probs, kl_scale=kl_scale)
-        if single:
+        if single_pass:
             grad = hipops.ctc_grad_from_lattice(lp, in_len, tg_len, lattice, utt_scale=utt_scale, pg_coef=coef, pg_path=sample, **ent)
             terms = hipops.pg_loss_value(lp, sample, in_len, nll, utt_scale, coef)
+        elif single:
+            grad = hipops.ctc_grad_from_lattice_multi(lp, in_len, tg_len, lattice, utt_scale, coef[None], samples, **ent)
+            terms = hipops.pg_loss_value_multi(lp, samples, in_len, nll, utt_scale, coef[None])
         elif Lh is None:
             grad = hipops.ctc_grad_from_lattice_multi(lp, in_len, tg_len, lattice, utt_scale, coef, samples, **ent)
             terms = hipops.pg_loss_value_multi(lp, samples, in_len, nll, utt_scale, coef)
@@ -278,13 +284,14 @@ class PGOptions:
     kl_weight: float = 0.0
 
 
-def check_options(opt, vocab=None, frames=None, symbols=None, sample_ids=None, wide_check=True):
+def check_options(opt, vocab=None, frames=None, symbols=None, sample_ids=None, wide_check=True, wide_objectives=False):
     """The one check of a ``PGOptions`` -- by ``pg_ctc_loss`` per call, by ``PolicyGradientTrainer`` at construction and before
     every step --, made before any kernel runs and where the caller can read the reason.  vocab, frames (T) and symbols (the
     targets' row length) are checked against where they are known.  Returns the options with their integers as ints.
     An alphabet of 65 .. 1024 symbols (hipops.MAX_VOCAB_WIDE) takes the default objective alone -- CTC + single-sample REINFORCE
     against the greedy hypothesis (``_check_wide``); wide_check=False leaves that rule to the caller (a trainer without
-    ``wide_alphabet`` refuses such a model itself)."""
+    ``wide_alphabet`` refuses such a model itself).  wide_objectives=True (opt-in) admits the multi-sample, leave-one-out, entropy
+    and KL objectives for such an alphabet as well; at most 64 symbols it changes nothing."""
     _check_score(opt.score_function, opt.max_hyp_len, opt.per_step)
     if sample_ids is not None and opt.sample_base >= 0:
         raise ValueError("sample_ids and sample_base >= 0 are two addressings of the same draws: give one")
@@ -296,15 +303,21 @@ def check_options(opt, vocab=None, frames=None, symbols=None, sample_ids=None, w
         raise ValueError(f"the word-level reward takes at most {hipops.WORD_MAX_STRIDE} frames and target symbols per utterance "
                          f"(pgasr_word_ids); got T = {frames}")
     if wide_check and vocab is not None and vocab > hipops.MAX_VOCAB_NARROW:
-        _check_wide(opt, vocab)
+        _check_wide(opt, vocab, wide_objectives=bool(wide_objectives))
     return dataclasses.replace(opt, num_samples=int(opt.num_samples),
                                max_hyp_len=None if opt.max_hyp_len is None else int(opt.max_hyp_len),
                                entropy_weight=check_entropy_weight(opt.entropy_weight), kl_weight=check_kl_weight(opt.kl_weight))
 
 
-def _check_wide(opt, vocab):
+WIDE_OBJECTIVES = ("num_samples", "baseline", "entropy_weight", "kl_weight")      # what wide_objectives=True opens above 64 symbols
+
+
+def _check_wide(opt, vocab, wide_objectives=False):
     """An alphabet of more than 64 symbols: the wide kernels cover log-softmax, arg-max / sample, the CTC lattice and its gradient
-    pass with one sampled path -- the default objective.  Every other option runs kernels that hold one symbol per lane."""
+    pass with one sampled path -- the default objective.  Every other option runs kernels that hold one symbol per lane.
+    wide_objectives=True (opt-in): the K-draw sampler, the entropy and KL statistics and the multi-sample gradient pass have wide
+    forms too (include/pgasr_hip.h, A12-WIDE), so num_samples 1..16, either baseline, entropy_weight and kl_weight are admitted in
+    any combination; the beam reward search, the sequence score function, the word reward and per-step rewards stay refused."""
     if vocab > hipops.MAX_VOCAB_WIDE:
         raise ValueError(f"alphabet of {vocab} symbols > {hipops.MAX_VOCAB_WIDE}: the wide kernels hold at most 16 symbols per lane")
     entropy, kl = check_entropy_weight(opt.entropy_weight), check_kl_weight(opt.kl_weight)
@@ -316,6 +329,13 @@ def _check_wide(opt, vocab):
                             ("kl_weight", opt.kl_weight, kl == 0.0),
                             ("reward_unit", opt.reward_unit, opt.reward_unit == "char"),
                             ("per_step", opt.per_step, not opt.per_step)):
+        if ok or (wide_objectives and name in WIDE_OBJECTIVES):
+            continue
+        if wide_objectives:
+            raise ValueError(f"{name}={given!r} takes an alphabet of at most {hipops.MAX_VOCAB_NARROW} symbols (got {vocab}): above the "
+                             f"64-symbol limit wide_objectives=True opens num_samples 1..{hipops.MAX_SAMPLES}, "
+                             f"baseline='leave_one_out', entropy_weight and kl_weight, and nothing else -- beam=0, "
+                             f"score_function='path', reward_unit='char', no per-step rewards")
         if not ok:
             raise ValueError(f"{name}={given!r} takes an alphabet of at most {hipops.MAX_VOCAB_NARROW} symbols (got {vocab}): above the "
                              f"64-symbol limit only the default objective runs -- num_samples=1, baseline='hypothesis', beam=0, "
@@ -406,7 +426,8 @@ def _check_samples(num_samples, baseline, per_step=False):
 
 def pg_ctc_loss(logits, in_len, targets, tg_len, lam=1.0, seed=0, offset=0, global_batch=None, blank=0, beam=0, sample_base=-1,
                 per_step=False, log_probs=None, num_samples=1, baseline="hypothesis", reward_unit="char", word_delimiter=None,
-                sample_ids=None, score_function="path", max_hyp_len=None, entropy_weight=0.0, kl_weight=0.0, ref_log_probs=None):
+                sample_ids=None, score_function="path", max_hyp_len=None, entropy_weight=0.0, kl_weight=0.0, ref_log_probs=None,
+                wide_objectives=False):
     """beam > 0: the baseline reward comes from the prefix-beam-search hypothesis of that width (see PGCTCLossFn).
     num_samples / baseline: multi-sample REINFORCE (see PGCTCLossFn); with num_samples > 1 the third returned tensor is R_s (K,B).
     reward_unit: "char" (default) or "word" -- the word-level reward R = -WED / W(y) with words split at the token
@@ -425,6 +446,9 @@ def pg_ctc_loss(logits, in_len, targets, tg_len, lam=1.0, seed=0, offset=0, glob
     ref_log_probs (T,B,V) fp32, contiguous, detached, on the logits' device -- the loss gains gamma / Bg times every utterance's MEAN
     frame KL(p || q), so gamma is in loss units per nat per frame (see PGCTCLossFn).  With gamma > 0 the tensor is required; 0
     (default): off, the tensor is ignored and the call is as it was, so a schedule may anneal gamma to 0.  With every other option.
+    wide_objectives: opt-in for an alphabet of 65 .. 1024 symbols -- num_samples 1..16, either baseline, entropy_weight and kl_weight
+    then run there too, on the wide kernels of A12-WIDE (``_check_wide``); beam, score_function="sequence", reward_unit="word" and
+    per_step stay refused.  False (default) and at most 64 symbols: every call as it was.
     log_probs: log_softmax(logits) if the caller already has it (the head kernel's by-product, ``logits.log_probs`` of
     Seq2Seq.logits -- picked up from that attribute when not given)."""
     T, B, V = logits.shape
@@ -433,7 +457,8 @@ def pg_ctc_loss(logits, in_len, targets, tg_len, lam=1.0, seed=0, offset=0, glob
                                   num_samples=num_samples, baseline=baseline, reward_unit=reward_unit, word_delimiter=word_delimiter,
                                   score_function=score_function, max_hyp_len=max_hyp_len, entropy_weight=entropy_weight,
                                   kl_weight=kl_weight),
-                        vocab=V, frames=T, symbols=targets.shape[1] if targets.dim() == 2 else 0, sample_ids=sample_ids)
+                        vocab=V, frames=T, symbols=targets.shape[1] if targets.dim() == 2 else 0, sample_ids=sample_ids,
+                        wide_objectives=wide_objectives)
     if log_probs is None:
         # the by-product is valid only for the tensor as the head kernel wrote it: any in-place edit since bumps _version
         log_probs = getattr(logits, "log_probs", None)

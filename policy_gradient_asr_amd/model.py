@@ -243,7 +243,7 @@ def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset
           accumulate_steps=1, score_function="path", max_hyp_len=None, entropy_weight=0.0, objective="reinforce", mwer_nbest=4,
           mwer_beam=16, init_from=None, kl_weight=0.0, kl_reference_path=None, mwer_lm_path=None, mwer_lm_alpha=0.0,
           mwer_lm_beta=0.0, target_rate=None, speed_perturb=None, noise_dir=None, rir_dir=None, snr_db=(5.0, 20.0), noise_prob=1.0,
-          rir_prob=0.5, units_path=None, wide_alphabet=None):
+          rir_prob=0.5, units_path=None, wide_alphabet=None, wide_objectives=None):
     """Epoch loop of model.py:186-274 on the MI355X path: per-epoch train loss -> train_loss.npy,
     validation CTC loss -> val_losses.npy, model_best.pth / model_last.pth (state_dicts, reference
     names), plus checkpoint_last.pth (model + Adam moments + epoch) from which ``resume`` restarts
@@ -302,7 +302,11 @@ def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset
     output layer has one symbol per unit (and the blank), and the reward is the edit distance over units.
     wide_alphabet: None (default: "more than 64 symbols") or a bool -- PolicyGradientTrainer(wide_alphabet=): up to 1024 symbols with
     the default objective (num_samples=1, the greedy baseline, reward_unit="char", score_function="path", no entropy or KL term);
-    objective="mwer" does not take it."""
+    objective="mwer" does not take it.
+    wide_objectives: None / False (default: the line above) or True -- PolicyGradientTrainer(wide_objectives=True): with more than
+    64 symbols num_samples 1..16, either reward_baseline, entropy_weight and kl_weight (with init_from / kl_reference_path) run on
+    the wide kernels too; the word reward and score_function="sequence" stay refused there.  Needs wide_alphabet; kept in the
+    checkpoint beside it."""
     import os
     import numpy as np
     import torch.utils.data as tud
@@ -341,6 +345,9 @@ def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset
     wide_alphabet = bool(wide_alphabet)
     if wide_alphabet and objective == "mwer":
         raise ValueError("objective='mwer' takes an alphabet of at most 64 symbols (the beam search's limit): not with wide_alphabet")
+    wide_objectives = bool(wide_objectives)
+    if wide_objectives and not wide_alphabet:
+        raise ValueError("wide_objectives=True opens objectives for alphabets of more than 64 symbols: it needs wide_alphabet")
     word_delimiter = None
     if reward_unit == "word":
         if " " not in char2ind:
@@ -383,7 +390,8 @@ def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset
         trainer = PolicyGradientTrainer(model, lr=lr, lam=lam, seed=seed, precision=precision, num_samples=num_samples,
                                         reward_baseline=reward_baseline, reward_unit=reward_unit, word_delimiter=word_delimiter,
                                         max_grad_norm=max_grad_norm, score_function=score_function, max_hyp_len=max_hyp_len,
-                                        entropy_weight=entropy_weight, **kl, **({"wide_alphabet": True} if wide_alphabet else {}))
+                                        entropy_weight=entropy_weight, **kl, **({"wide_alphabet": True} if wide_alphabet else {}),
+                                        **({"wide_objectives": True} if wide_objectives else {}))
     losses, val_losses, best, start_epoch = [], [], 9999999.0, 1
     ckpt = os.path.join(model_path, "checkpoint_last.pth")
     resuming = resume and os.path.exists(ckpt)
@@ -406,7 +414,7 @@ def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset
                         ("accumulate_steps", accumulate_steps), ("score_function", score_function),
                         ("max_hyp_len", max_hyp_len), ("entropy_weight", entropy_weight), ("kl_weight", kl_weight),
                         ("kl_reference_path", kl_reference_path), ("target_rate", target_rate),
-                        ("units_path", units_path), ("wide_alphabet", wide_alphabet),
+                        ("units_path", units_path), ("wide_alphabet", wide_alphabet), ("wide_objectives", wide_objectives),
                         ("speed_perturb", None if speed_perturb is None else speed_perturb.state()),
                         ("wave_augment", None if wave_augment is None else wave_augment.state())):
             if k in st and st[k] != want:
@@ -495,7 +503,7 @@ def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset
                     "reward_unit": reward_unit, "max_grad_norm": max_grad_norm, "accumulate_steps": accumulate_steps,
                     "score_function": score_function, "max_hyp_len": max_hyp_len, "entropy_weight": trainer.entropy_weight,
                     "kl_weight": kl_weight, "kl_reference_path": kl_reference_path, "target_rate": target_rate,
-                    "units_path": units_path, "wide_alphabet": wide_alphabet,
+                    "units_path": units_path, "wide_alphabet": wide_alphabet, "wide_objectives": wide_objectives,
                     "speed_perturb": None if speed_perturb is None else speed_perturb.state(),
                     "wave_augment": None if wave_augment is None else wave_augment.state()}, ckpt)
     return losses, val_losses

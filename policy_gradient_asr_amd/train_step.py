@@ -447,11 +447,16 @@ class PolicyGradientTrainer(DataParallelStep):
     def __init__(self, model, lr=5e-4, lam=1.0, seed=0, blank=0, world_size=1, process_group=None, rank=0,
                  reward_decoder="greedy", beam_size=16, precision=None, reward_mode="utterance", num_samples=1,
                  reward_baseline="hypothesis", reward_unit="char", word_delimiter=None, max_grad_norm=None,
-                 score_function="path", max_hyp_len=None, entropy_weight=0.0, kl_weight=0.0, kl_reference=None, wide_alphabet=False):
+                 score_function="path", max_hyp_len=None, entropy_weight=0.0, kl_weight=0.0, kl_reference=None, wide_alphabet=False,
+                 wide_objectives=False):
         """wide_alphabet: opt in to alphabets of 65 .. 1024 symbols (subword units).  MAX_VOCAB becomes 1024, and such a model takes
         the default objective alone: reward_decoder="greedy", reward_mode="utterance", num_samples=1, reward_baseline="hypothesis",
         reward_unit="char", score_function="path", entropy_weight=0, kl_weight=0 -- anything else raises here and before every
         step (loss.check_options).  False (default): a model of more than 64 symbols is refused by ``step`` as ever.
+        wide_objectives: with wide_alphabet=True (else ValueError), opt in to num_samples 1 .. MAX_SAMPLES, either reward_baseline,
+        entropy_weight and kl_weight / kl_reference for such a model too, in any combination, on the wide kernels of A12-WIDE;
+        reward_decoder="beam", reward_mode="per_step", reward_unit="word" and score_function="sequence" stay refused there.  The
+        default objective keeps its launches and bits with or without it.
         reward_mode: "utterance" (default) -- one reward R = -ED / |y| per utterance, the sum of the reference's per-step rewards
         (policy_grad.py:10-15) up to a constant the baseline removes; "per_step" -- the per-step rewards themselves, as rewards-to-go
         per frame against the greedy path's reward-to-go at the same frame (loss.PGCTCLossFn; greedy baseline only).
@@ -499,6 +504,9 @@ class PolicyGradientTrainer(DataParallelStep):
         if self.wide_alphabet:
             from . import hipops
             self.MAX_VOCAB = hipops.MAX_VOCAB_WIDE
+        self.wide_objectives = bool(wide_objectives)
+        if self.wide_objectives and not self.wide_alphabet:
+            raise ValueError("wide_objectives=True opens objectives for alphabets of more than 64 symbols: it needs wide_alphabet=True")
         if reward_decoder not in ("greedy", "beam"):
             raise ValueError("reward_decoder must be 'greedy' or 'beam'")
         if reward_mode not in ("utterance", "per_step"):
@@ -603,7 +611,8 @@ class PolicyGradientTrainer(DataParallelStep):
                         beam=self.beam_size if self.reward_decoder == "beam" else 0, baseline=self.reward_baseline, reward_unit=self.reward_unit, word_delimiter=self.word_delimiter,
                         score_function=self.score_function, max_hyp_len=self.max_hyp_len, entropy_weight=self.entropy_weight,
                         kl_weight=self.kl_weight)
-        return check_options(opt, vocab=vocab, frames=frames, symbols=symbols, wide_check=self.wide_alphabet)
+        return check_options(opt, vocab=vocab, frames=frames, symbols=symbols, wide_check=self.wide_alphabet,
+                             wide_objectives=getattr(self, "wide_objectives", False))
 
     def _check_limits(self, x, targets):
         """The kernels' compiled-in limits, stated where the caller can read them (otherwise the first symptom is a
@@ -713,7 +722,8 @@ class PolicyGradientTrainer(DataParallelStep):
                                           baseline=self.reward_baseline, reward_unit=self.reward_unit,
                                           word_delimiter=self.word_delimiter, sample_ids=sample_ids,
                                           score_function=self.score_function, max_hyp_len=self.max_hyp_len,
-                                          entropy_weight=self.entropy_weight, **kl)
+                                          entropy_weight=self.entropy_weight, **kl,
+                                          **({"wide_objectives": True} if self.wide_objectives else {}))
         scored = PGCTCLossFn.last_sequence_scored                # (K,B) bool, None with score_function="path"
         self.last_sequence_scored = scored[:, :real_b] if (padded and scored is not None) else scored
         ent = PGCTCLossFn.last_entropy                           # (B,) mean frame entropy, None with entropy_weight = 0
