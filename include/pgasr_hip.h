@@ -1402,6 +1402,44 @@ int pgasr_ctc_hyp_score(const float* log_probs, const int32_t* hyp_tokens, int h
                         const int32_t* count /* NULL: every row */, const int32_t* input_lengths,
                         int T, int B, int V, int N, int Lh, int blank, double* out_nll, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * A13-WIDE  The sequence-level score function and MWER over N-best lists (A13-MWER) for rows of 1 <= V <= 1024 symbols: the two
+ * kernels of those objectives that hold one symbol per lane -- the label lists of the K*B hypothesis lattices and the gradient
+ * pass over K+1 lattices -- on the rows of A5-WIDE.  The sweeps are the narrow entry's kernel (the lattice never looks at V beyond
+ * addressing a row), so with V <= 64 hyp_nll and every alpha / beta word have pgasr_ctc_hyp_lattice's bits; collapse, edit
+ * distance, pgasr_mwer_weights, pgasr_pg_rewards_multi and pgasr_pg_loss_value_seq never look at V.  The narrow entries keep what
+ * they accept (V <= 64) and what they launch.
+ *   pgasr_ctc_hyp_workspace_bytes_wide: pgasr_ctc_hyp_workspace_bytes for V <= 1024 (the same layout; 0 where the arguments are
+ *     refused).
+ *   pgasr_ctc_hyp_lattice_wide: pgasr_ctc_hyp_lattice, argument for argument.  The label -> states lists of pair p = k*B + b are
+ *     built from row p of hyp_tokens and hyp_len[p] by integer counts, a scan over V + 1 counts and slot = offset + rank among
+ *     earlier equal tokens, so each list ascends in s.  A pair with hyp_len > Lh has no lattice; its nll reads 0.
+ *   pgasr_ctc_grad_from_lattices_seq_wide: pgasr_ctc_grad_from_lattices_seq, _seq_ent, _seq_kl and, with pg_paths == NULL,
+ *     pgasr_ctc_grad_from_lattices_nbest in one entry, on the workspaces of pgasr_ctc_loss_grad[_wide] and
+ *     pgasr_ctc_hyp_lattice[_wide] (same formats).  One wave per (t,b) row, one write: the target part of
+ *     pgasr_ctc_grad_from_lattice_multi_wide; then for k = 0 .. K-1 in k order pg_coef[k,b] (softmax - occ_{y_k}) from lattice (k,b)
+ *     where hyp_len[k,b] <= Lh, else pg_coef[k,b] (softmax - onehot(pg_paths[k,t,b])) -- nothing when pg_paths is NULL --; then
+ *     ent_scale_b p (ln p + H) when ent_scale is given; then kl_scale_b p (ln p - lnq - KL) when ref_log_probs and kl_scale are
+ *     (both or neither, else PGASR_ERR_INVALID_ARG).  The N-best form takes no tails (ent_scale or kl_scale with pg_paths == NULL
+ *     -> PGASR_ERR_INVALID_ARG).  Rows t >= input_lengths[b] are written as zeros, a lattice whose nll is +inf adds nothing,
+ *     log p = -inf gives occupancy 0 and gradient entry 0, never NaN.  Fixed summation order: the same bits every call, and with
+ *     V <= 64 the narrow kernels' sums in their order.
+ * Checked before any HIP call, with the narrow twins' codes: a missing required pointer, T, B or V <= 0, Lh < 0, K outside
+ * 1..PGASR_MAX_SAMPLES, a blank outside [0, V), hyp_stride < max(1, Lh) -> PGASR_ERR_INVALID_ARG; V > 1024, 2 * Lh + 1 > 2048,
+ * 2 * Lmax + 1 > 2048 -> PGASR_ERR_UNSUPPORTED; a workspace that is missing or too small -> PGASR_ERR_WORKSPACE.
+ * ---------------------------------------------------------------------------------------- */
+size_t pgasr_ctc_hyp_workspace_bytes_wide(int T, int B, int V, int K, int Lh);
+int pgasr_ctc_hyp_lattice_wide(const float* log_probs, const int32_t* hyp_tokens, int hyp_stride, const int32_t* hyp_len,
+                               const int32_t* input_lengths, int T, int B, int V, int K, int Lh, int blank,
+                               float* hyp_nll, void* hyp_workspace, size_t hyp_workspace_bytes, void* stream);
+int pgasr_ctc_grad_from_lattices_seq_wide(const float* log_probs, const int32_t* input_lengths, const int32_t* target_lengths,
+                                          int T, int B, int V, int Lmax, int blank, const float* utt_scale,
+                                          int K, const float* pg_coef, const int32_t* pg_paths /* NULL: the N-best form */,
+                                          const int32_t* hyp_len, int Lh, const float* ent_scale /* may be NULL */,
+                                          const float* ref_log_probs /* may be NULL */, const float* kl_scale /* may be NULL */,
+                                          float* grad_logits, void* workspace, size_t workspace_bytes,
+                                          void* hyp_workspace, size_t hyp_workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1000,6 +1000,233 @@ static int ctc_launch_grad_multi_wide(const float* log_probs, const int32_t* inp
     return PGASR_OK;
 }
 
+// ---- sequence-level REINFORCE and N-best MWER for wide rows (pgasr_ctc_hyp_lattice_wide, pgasr_ctc_grad_from_lattices_seq_wide; A13-WIDE) ----
+// The hypothesis lattices are V-agnostic like the target's: the wide entry launches ctc_hyp_lattice_kernel with grid (K*B, 2) -- the
+// sweeps alone -- and builds the label -> states lists of pair p = k*B + b with the kernel below: ctc_labels_wide_kernel's counts
+// (LDS atomics), block scan over V + 1 counts and slot = offset + rank among earlier equal tokens, over row p of hyp_tokens at
+// hyp_stride with the length hyp_len[p].  A pair with hyp_len > Lh has no lattice and no lists, as in the lattice roles.  A kernel
+// of its own beside ctc_labels_wide_kernel, whose text stays what it was.
+__global__ __launch_bounds__(256) void ctc_hyp_labels_wide_kernel(const int32_t* __restrict__ hyp, int hyp_stride,
+                                                                  const int32_t* __restrict__ hyp_len, int V, int Lh, int Smax, int blank,
+                                                                  CtcWs ws) {
+    constexpr int CH = (PGASR_WIDE_VMAX + 1 + 255) / 256;      // counts per thread in the scan (5)
+    __shared__ int tg[CTC_SMAX / 2];                           // the hypothesis row, L <= 1023
+    __shared__ int cnt[256 * CH];                              // counts, then offsets
+    __shared__ int wtot[4];
+    const int p = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int len = hyp_len[p];
+    if (len > Lh) return;                                      // path-scored sample: uniform over the workgroup
+    int Lb = len < 0 ? 0 : len;
+    if (Lb > hyp_stride) Lb = hyp_stride;                      // ctc_labels_body's clamp to the row
+    if (Lb > CTC_SMAX / 2) Lb = CTC_SMAX / 2;                  // defensive: the entry points refuse 2 * Lh + 1 > 2048
+    const int32_t* tgt = hyp + (size_t)p * hyp_stride;
+    for (int i = tid; i < 256 * CH; i += 256) cnt[i] = 0;
+    for (int i = tid; i < Lb; i += 256) tg[i] = tgt[i];
+    __syncthreads();
+    for (int i = tid; i < Lb; i += 256) {
+        const int l = tg[i];
+        if (l != blank && (unsigned)l < (unsigned)V) atomicAdd(&cnt[l], 1);
+    }
+    __syncthreads();
+    // exclusive scan of cnt[0 .. V]: thread i owns entries i*CH .. i*CH + CH - 1
+    int loc[CH], sum = 0;
+#pragma unroll
+    for (int j = 0; j < CH; ++j) { loc[j] = cnt[tid * CH + j]; sum += loc[j]; }
+    int inc = sum;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int up = __shfl_up(inc, o, 64);
+        if (lane >= o) inc += up;
+    }
+    if (lane == 63) wtot[wid] = inc;
+    __syncthreads();
+    int run = inc - sum;
+    for (int w = 0; w < wid; ++w) run += wtot[w];
+#pragma unroll
+    for (int j = 0; j < CH; ++j) { cnt[tid * CH + j] = run; run += loc[j]; }
+    __syncthreads();
+    for (int v = tid; v <= V; v += 256) ws.lab_off[(size_t)p * (V + 1) + v] = cnt[v];
+    for (int i = tid; i < Lb; i += 256) {
+        const int l = tg[i];
+        if (l == blank || (unsigned)l >= (unsigned)V) continue;
+        int rank = 0;
+        for (int j = 0; j < i; ++j) rank += (tg[j] == l);
+        ws.lab_states[(size_t)p * Smax + cnt[l] + rank] = 2 * i + 1;      // cnt[l] + rank < Lb <= Lh < Smax
+    }
+}
+
+// scale_n (softmax - occupancy) of lattice n of ws for one (t,b) row of NV labels per lane: ctc_grad_row with wide rows.  r[i] is
+// label v0 + i's value, 0 for every label when the lattice's nll is +inf (no alignment) and for labels past V.  The walk of
+// ctc_grad_multi_wide_kernel: the blank's strided sum and one butterfly, every label's list in list order, the selects that give a
+// log p = -inf occupancy 0, the label offsets read outer-first.  lpb = the row's log p(blank); scale NULL reads as 1.
+template <int NV>
+__device__ __forceinline__ void ctc_grad_row_wide(const float (&lpv)[NV], const float (&sm)[NV], float lpb, int lane, int t, int n, int T,
+                                                  int V, int Lb, int Smax, int blank, const CtcWs& ws, const float* __restrict__ scale,
+                                                  float (&r)[NV]) {
+    const int v0 = lane * NV;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) r[i] = 0.f;
+    const double nll = ws.nll64[n];
+    if (nll != INFINITY) {            // uniform over the wave
+        const int S = 2 * Lb + 1;
+        const float* al = ws.alpha + ((size_t)n * T + t) * ws.SP;
+        const float* be = ws.beta + ((size_t)n * T + t) * ws.SP;
+        const double cst = ws.amax[(size_t)n * T + t] + ws.bmax[(size_t)n * T + t] + nll;
+        const float cb = (lpb == -INFINITY) ? 0.f : (float)(cst - (double)lpb);
+        float accb = 0.f;
+        for (int s = 2 * lane; s < S; s += 128)
+            accb += __expf((al[s] + be[s]) + cb);
+        accb = wave_sum(accb);
+        const int32_t* lo = ws.lab_off + (size_t)n * (V + 1);
+        const int32_t* ls = ws.lab_states + (size_t)n * Smax;
+        const float sc = scale ? scale[n] : 1.f;
+        const int vend = (v0 + NV < V) ? v0 + NV : V;
+        const int lo0 = (v0 < V) ? lo[v0] : 0;
+        const int lo1 = (v0 < V) ? lo[vend] : 0;
+        int off[NV + 1];
+#pragma unroll
+        for (int i = 0; i <= NV; ++i) off[i] = lo0;                       // no label of this lane in the sequence: every list is empty
+        if (lo0 != lo1) {
+#pragma unroll
+            for (int i = 1; i < NV; ++i) off[i] = (v0 + i <= V) ? lo[v0 + i] : 0;
+            off[NV] = lo1;            // read by label v0 + NV - 1 alone, which exists only when vend = v0 + NV
+        }
+#pragma unroll
+        for (int i = 0; i < NV; ++i) {
+            const int v = v0 + i;
+            if (v < V) {
+                float occ = accb;
+                if (v != blank) {
+                    float acc = 0.f;
+                    const float cl = (lpv[i] == -INFINITY) ? 0.f : (float)(cst - (double)lpv[i]);
+                    for (int j = off[i]; j < off[i + 1]; ++j) {
+                        const int s = ls[j];
+                        acc += __expf((al[s] + be[s]) + cl);
+                    }
+                    occ = acc;
+                }
+                r[i] = sc * (sm[i] - occ);
+            }
+        }
+    }
+}
+
+// ctc_grad_seq_kernel with NV labels per lane: the target part, then pair (k,b) for k = 0 .. K-1 in k order -- the sequence term from
+// lattice (k,b) of the hypothesis workspace where hyp_len[k,b] <= Lh (scale pg_coef[k,b]), else, when PATHS, the path term
+// pg_coef[k,b] (softmax - onehot(pg_paths[k,t,b])) --, then the tails of ctc_grad_multi_wide_kernel (TAIL: 0 none, 1 entropy,
+// 2 entropy (nullable) and KL).  PATHS = false (the N-best form, MWER): pg_paths is not read and a pair over the cap adds nothing.
+// One wave per (t,b), one pass, one write; rows t >= T_b are written as zeros.  With NV = 1 every sum is ctc_grad_seq_kernel's, in
+// its order.
+template <int NV, bool PATHS, int TAIL>
+__global__ __launch_bounds__(64 * CTC_WIDE_WPB) void ctc_grad_seq_wide_kernel(
+    const float* __restrict__ lp, const int32_t* __restrict__ in_len,
+    const int32_t* __restrict__ tg_len, int T, int B, int V, int vec, int Lmax, int Smax, int blank, CtcWs ws,
+    const float* __restrict__ utt_scale, int K, const float* __restrict__ pg_coef, const int32_t* __restrict__ pg_paths,
+    const int32_t* __restrict__ hyp_len, int Lh, int Smax_h, CtcWs hws,
+    const float* __restrict__ ent_scale, const float* __restrict__ ref_lp, const float* __restrict__ kl_scale,
+    float* __restrict__ grad) {
+    const int lane = threadIdx.x & 63;
+    const long long w = (long long)blockIdx.x * CTC_WIDE_WPB + (threadIdx.x >> 6);
+    if (w >= (long long)T * B) return;
+    const int t = (int)(w / B), b = (int)(w % B);
+    int Tb = in_len[b]; Tb = Tb < 0 ? 0 : (Tb > T ? T : Tb);
+    int Lb = tg_len[b]; Lb = Lb < 0 ? 0 : (Lb > Lmax ? Lmax : Lb);
+    const size_t o = ((size_t)t * B + b) * V;
+    const int v0 = lane * NV;
+    float g[NV];
+#pragma unroll
+    for (int i = 0; i < NV; ++i) g[i] = 0.f;
+    if (t >= Tb) {
+        wide_row_store<NV>(grad + o, V, lane, vec != 0, g);
+        return;
+    }
+    float lpv[NV], sm[NV];
+    wide_row_load<NV>(lp + o, V, lane, vec != 0, 0.f, lpv);
+#pragma unroll
+    for (int i = 0; i < NV; ++i) sm[i] = (v0 + i < V) ? __expf(lpv[i]) : 0.f;
+    const float lpb = lp[o + blank];
+
+    // (One copy of the walk for all K + 1 lattices, the workspace chosen per trip, was tried: the choice between the two CtcWs put
+    // them into 136 bytes of scratch and saved no register.  Two copies, none in scratch.)
+    ctc_grad_row_wide<NV>(lpv, sm, lpb, lane, t, b, T, V, Lb, Smax, blank, ws, utt_scale, g);
+    const size_t TB = (size_t)T * B;
+    for (int k = 0; k < K; ++k) {
+        const int p = k * B + b;
+        const int len = hyp_len[p];
+        if (len <= Lh) {              // uniform over the wave
+            float r[NV];
+            ctc_grad_row_wide<NV>(lpv, sm, lpb, lane, t, p, T, V, len < 0 ? 0 : len, Smax_h, blank, hws, pg_coef, r);
+#pragma unroll
+            for (int i = 0; i < NV; ++i) g[i] += r[i];
+        } else if constexpr (PATHS) {
+            const int pk = pg_paths[k * TB + (size_t)t * B + b];
+            const float c = pg_coef[p];
+#pragma unroll
+            for (int i = 0; i < NV; ++i) g[i] += c * (sm[i] - (v0 + i == pk ? 1.f : 0.f));
+        }
+    }
+    if constexpr (TAIL >= 1) {
+        if (TAIL == 1 || ent_scale != nullptr) {
+            float plp[NV], s = 0.f;
+#pragma unroll
+            for (int i = 0; i < NV; ++i) {
+                plp[i] = sm[i] > 0.f ? sm[i] * lpv[i] : 0.f;
+                s = (i == 0) ? plp[i] : s + plp[i];
+            }
+            const float H = -wave_sum(s);
+            const float es = ent_scale[b];
+#pragma unroll
+            for (int i = 0; i < NV; ++i) g[i] += sm[i] > 0.f ? es * fmaf(sm[i], H, plp[i]) : 0.f;
+        }
+    }
+    if constexpr (TAIL == 2) {
+        float d[NV];
+        wide_row_load<NV>(ref_lp + o, V, lane, vec != 0, 0.f, d);
+        float s = 0.f;
+#pragma unroll
+        for (int i = 0; i < NV; ++i) {
+            d[i] = sm[i] > 0.f ? sm[i] * (lpv[i] - fmaxf(d[i], KL_LOG_FLOOR)) : 0.f;
+            s = (i == 0) ? d[i] : s + d[i];
+        }
+        const float kl = wave_sum(s);
+        const float ks = kl_scale[b];
+#pragma unroll
+        for (int i = 0; i < NV; ++i) {
+            const float term = ks * fmaf(-sm[i], kl, d[i]);
+            g[i] = term != 0.f ? g[i] + term : g[i];
+        }
+    }
+    wide_row_store<NV>(grad + o, V, lane, vec != 0, g);
+}
+
+static int ctc_hyp_args_ok_wide(int T, int B, int V, int K, int Lh) {
+    if (T <= 0 || B <= 0 || V <= 0 || Lh < 0) return PGASR_ERR_INVALID_ARG;
+    if (K < 1 || K > PGASR_MAX_SAMPLES) return PGASR_ERR_INVALID_ARG;
+    if (2 * (long long)Lh + 1 > CTC_SMAX || V > PGASR_WIDE_VMAX) return PGASR_ERR_UNSUPPORTED;
+    if ((long long)K * B > 0x7fffffffLL / 4) return PGASR_ERR_UNSUPPORTED;
+    return PGASR_OK;
+}
+
+template <bool PATHS, int TAIL>
+static int ctc_launch_grad_seq_wide(const float* log_probs, const int32_t* input_lengths, const int32_t* target_lengths, int T, int B,
+                                    int V, int Lmax, int blank, const CtcWs& ws, const float* utt_scale, int K, const float* pg_coef,
+                                    const int32_t* pg_paths, const int32_t* hyp_len, int Lh, const CtcWs& hws, const float* ent_scale,
+                                    const float* ref_log_probs, const float* kl_scale, float* grad_logits, void* stream) {
+    const long long waves = (long long)T * B;
+    const unsigned blocks = (unsigned)((waves + CTC_WIDE_WPB - 1) / CTC_WIDE_WPB);
+    // one `vec` for the launch: the row loads of log_probs and ref_log_probs and the row store must all be aligned
+#define PGASR_CALL(NV) PGASR_LAUNCH_KERNEL((ctc_grad_seq_wide_kernel<NV, PATHS, TAIL>), dim3(blocks), dim3(64 * CTC_WIDE_WPB), 0,             \
+                                           (hipStream_t)stream, log_probs, input_lengths, target_lengths, T, B, V,                              \
+                                           (wide_vec_ok<NV>(log_probs, grad_logits, V) &&                                                       \
+                                            (TAIL < 2 || wide_vec_ok<NV>(ref_log_probs, ref_log_probs, V))) ? 1 : 0,                            \
+                                           Lmax > 0 ? Lmax : 1, 2 * Lmax + 1, blank, ws, utt_scale, K, pg_coef, pg_paths, hyp_len, Lh,          \
+                                           2 * Lh + 1, hws, ent_scale, ref_log_probs, kl_scale, grad_logits)
+    PGASR_WIDE_DISPATCH(V, PGASR_CALL);
+#undef PGASR_CALL
+    PGASR_CHECK_LAUNCH();
+    return PGASR_OK;
+}
+
 }  // namespace
 
 extern "C" size_t pgasr_ctc_workspace_bytes(int T, int B, int V, int Lmax) {
@@ -1328,4 +1555,67 @@ extern "C" int pgasr_ctc_grad_from_lattice_multi_wide(const float* log_probs, co
                                              pg_paths, ent_scale, nullptr, nullptr, grad_logits, stream);
     return ctc_launch_grad_multi_wide<0>(log_probs, input_lengths, target_lengths, T, B, V, Lmax, blank, ws, utt_scale, K, pg_coef,
                                          pg_paths, nullptr, nullptr, nullptr, grad_logits, stream);
+}
+
+// ---- A13-WIDE: the hypothesis lattices and the pass over K+1 lattices for 1 <= V <= 1024 (same workspaces, same sweep kernel) ----
+extern "C" size_t pgasr_ctc_hyp_workspace_bytes_wide(int T, int B, int V, int K, int Lh) {
+    if (ctc_hyp_args_ok_wide(T, B, V, K, Lh) != PGASR_OK) return 0;
+    return ctc_ws_layout(T, K * B, V, 2 * Lh + 1, nullptr, nullptr);
+}
+
+extern "C" int pgasr_ctc_hyp_lattice_wide(const float* log_probs, const int32_t* hyp_tokens, int hyp_stride, const int32_t* hyp_len,
+                                          const int32_t* input_lengths, int T, int B, int V, int K, int Lh, int blank,
+                                          float* hyp_nll, void* hyp_workspace, size_t hyp_workspace_bytes, void* stream) {
+    if (!log_probs || !hyp_tokens || !hyp_len || !input_lengths || !hyp_nll) return PGASR_ERR_INVALID_ARG;
+    if (blank < 0 || blank >= V || hyp_stride < 1 || hyp_stride < Lh) return PGASR_ERR_INVALID_ARG;
+    const int ok = ctc_hyp_args_ok_wide(T, B, V, K, Lh);
+    if (ok != PGASR_OK) return ok;
+    const int Smax = 2 * Lh + 1;
+    CtcWs ws;
+    if (!ctc_ws_bind(T, K * B, V, Smax, &ws, hyp_workspace, hyp_workspace_bytes)) return PGASR_ERR_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    PGASR_LAUNCH_KERNEL(ctc_hyp_labels_wide_kernel, dim3(K * B), dim3(256), 0, st, hyp_tokens, hyp_stride, hyp_len, V, Lh, Smax, blank, ws);
+    PGASR_CHECK_LAUNCH();
+    // the sweeps alone: grid rows 0 and 1 of the hypothesis lattice kernel, whose third row (the narrow label lists) is not launched
+#define PGASR_HYP_LATTICE(NMAX) PGASR_LAUNCH_KERNEL(ctc_hyp_lattice_kernel<NMAX>, dim3(K * B, 2), dim3(CTC_THREADS + 64), 0, st, \
+                        log_probs, hyp_tokens, hyp_stride, hyp_len, input_lengths, T, B, V, Lh, Smax, blank, ws, hyp_nll)
+    if (Smax <= CTC_THREADS) PGASR_HYP_LATTICE(1);
+    else if (Smax <= 2 * CTC_THREADS) PGASR_HYP_LATTICE(2);
+    else if (Smax <= 4 * CTC_THREADS) PGASR_HYP_LATTICE(4);
+    else PGASR_HYP_LATTICE(8);
+#undef PGASR_HYP_LATTICE
+    PGASR_CHECK_LAUNCH();
+    return PGASR_OK;
+}
+
+// pgasr_ctc_grad_from_lattices_seq, _seq_ent, _seq_kl and (pg_paths NULL) pgasr_ctc_grad_from_lattices_nbest in one entry.
+// ent_scale NULL and ref_log_probs / kl_scale NULL: the plain instantiation; ent_scale alone: the entropy one; ref_log_probs and
+// kl_scale (together): the one with both tails, ent_scale nullable there.  The N-best form has no tails.
+extern "C" int pgasr_ctc_grad_from_lattices_seq_wide(const float* log_probs, const int32_t* input_lengths, const int32_t* target_lengths,
+                                                     int T, int B, int V, int Lmax, int blank, const float* utt_scale,
+                                                     int K, const float* pg_coef, const int32_t* pg_paths, const int32_t* hyp_len, int Lh,
+                                                     const float* ent_scale, const float* ref_log_probs, const float* kl_scale,
+                                                     float* grad_logits, void* workspace, size_t workspace_bytes,
+                                                     void* hyp_workspace, size_t hyp_workspace_bytes, void* stream) {
+    if (!log_probs || !input_lengths || !target_lengths || !grad_logits || !pg_coef || !hyp_len) return PGASR_ERR_INVALID_ARG;
+    if ((ref_log_probs == nullptr) != (kl_scale == nullptr)) return PGASR_ERR_INVALID_ARG;
+    if (!pg_paths && (ent_scale || kl_scale)) return PGASR_ERR_INVALID_ARG;
+    if (Lmax < 0 || blank < 0 || blank >= V) return PGASR_ERR_INVALID_ARG;
+    int ok = ctc_hyp_args_ok_wide(T, B, V, K, Lh);
+    if (ok == PGASR_OK) ok = ctc_args_ok_wide(T, B, V, Lmax, blank);
+    if (ok != PGASR_OK) return ok;
+    CtcWs ws, hws;
+    if (!ctc_ws_bind(T, B, V, 2 * Lmax + 1, &ws, workspace, workspace_bytes)) return PGASR_ERR_WORKSPACE;
+    if (!ctc_ws_bind(T, K * B, V, 2 * Lh + 1, &hws, hyp_workspace, hyp_workspace_bytes)) return PGASR_ERR_WORKSPACE;
+    if (!pg_paths)
+        return ctc_launch_grad_seq_wide<false, 0>(log_probs, input_lengths, target_lengths, T, B, V, Lmax, blank, ws, utt_scale, K, pg_coef,
+                                                  nullptr, hyp_len, Lh, hws, nullptr, nullptr, nullptr, grad_logits, stream);
+    if (kl_scale)
+        return ctc_launch_grad_seq_wide<true, 2>(log_probs, input_lengths, target_lengths, T, B, V, Lmax, blank, ws, utt_scale, K, pg_coef,
+                                                 pg_paths, hyp_len, Lh, hws, ent_scale, ref_log_probs, kl_scale, grad_logits, stream);
+    if (ent_scale)
+        return ctc_launch_grad_seq_wide<true, 1>(log_probs, input_lengths, target_lengths, T, B, V, Lmax, blank, ws, utt_scale, K, pg_coef,
+                                                 pg_paths, hyp_len, Lh, hws, ent_scale, nullptr, nullptr, grad_logits, stream);
+    return ctc_launch_grad_seq_wide<true, 0>(log_probs, input_lengths, target_lengths, T, B, V, Lmax, blank, ws, utt_scale, K, pg_coef,
+                                             pg_paths, hyp_len, Lh, hws, nullptr, nullptr, nullptr, grad_logits, stream);
 }

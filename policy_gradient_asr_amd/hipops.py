@@ -124,7 +124,7 @@ def _workspace(nbytes, device, tag):
     return buf
 
 
-# ---- alphabets of 65 .. 1024 symbols (include/pgasr_hip.h, A5-WIDE / A9-WIDE / A12-WIDE) ----
+# ---- alphabets of 65 .. 1024 symbols (include/pgasr_hip.h, A5-WIDE / A9-WIDE / A12-WIDE / A13-WIDE) ----
 MAX_VOCAB_NARROW = 64            # one label per lane: every entry point without a _wide form
 MAX_VOCAB_WIDE = 1024            # PGASR_MAX_VOCAB_WIDE: log-softmax, arg-max / sample, CTC lattice and gradient pass; the K-draw
                                  # sampler, the entropy and KL statistics and the multi-sample gradient pass with their tails
@@ -419,16 +419,21 @@ def hyp_len_cap(T, max_hyp_len=None):
     return min(int(T), MAX_HYP_LEN) if max_hyp_len is None else min(int(T), MAX_HYP_LEN, int(max_hyp_len))
 
 
-def ctc_hyp_workspace_bytes(T, B, V, K, Lh):
-    """Bytes of the K*B hypothesis lattices: 2 * K*B*T * roundup64(2*Lh+1) * 4 plus the per-pair tables."""
+def ctc_hyp_workspace_bytes(T, B, V, K, Lh, wide=None):
+    """Bytes of the K*B hypothesis lattices: 2 * K*B*T * roundup64(2*Lh+1) * 4 plus the per-pair tables.
+    V > 64 (or wide=True): ``pgasr_ctc_hyp_workspace_bytes_wide``, the same layout for V <= 1024."""
+    if _wide(V, wide, "ctc_hyp_workspace_bytes"):
+        return int(_lib.load().pgasr_ctc_hyp_workspace_bytes_wide(T, B, V, K, Lh))
     return int(_lib.load().pgasr_ctc_hyp_workspace_bytes(T, B, V, K, Lh))
 
 
-def ctc_hyp_lattice(log_probs, hyp_tokens, hyp_len, input_lengths, Lh, blank=0):
+def ctc_hyp_lattice(log_probs, hyp_tokens, hyp_len, input_lengths, Lh, blank=0, wide=None):
     """The CTC lattices of the K sampled hypotheses of every utterance over the SAME log-prob rows: log_probs (T,B,V),
     hyp_tokens (K,B,stride) / hyp_len (K,B) int32 as ``ctc_collapse`` returns them.  Pairs with hyp_len > Lh are skipped.
     Returns (hyp_nll (K,B) fp32 -- 0 for a skipped pair --, handle); the handle goes to ``ctc_grad_from_lattices_seq``.
-    The lattices live in a cached workspace of ``ctc_hyp_workspace_bytes(T, B, V, K, Lh)`` bytes (tag "ctc_hyp")."""
+    The lattices live in a cached workspace of ``ctc_hyp_workspace_bytes(T, B, V, K, Lh)`` bytes (tag "ctc_hyp").
+    V > 64 (or wide=True): ``pgasr_ctc_hyp_lattice_wide`` (include/pgasr_hip.h, A13-WIDE) -- the same sweeps, arguments and
+    workspace, the label lists built for V <= 1024."""
     lib = _lib.load()
     _req(log_probs, torch.float32, "log_probs"); _req(hyp_tokens, torch.int32, "hyp_tokens")
     _req(hyp_len, torch.int32, "hyp_len"); _req(input_lengths, torch.int32, "input_lengths")
@@ -436,13 +441,14 @@ def ctc_hyp_lattice(log_probs, hyp_tokens, hyp_len, input_lengths, Lh, blank=0):
     if hyp_tokens.dim() != 3 or hyp_tokens.shape[1] != B or tuple(hyp_len.shape) != (hyp_tokens.shape[0], B):
         raise _lib.PgasrError(f"ctc_hyp_lattice wants hyp_tokens (K,{B},stride) and hyp_len (K,{B})")
     K, stride, Lh = hyp_tokens.shape[0], hyp_tokens.shape[2], int(Lh)
-    nbytes = lib.pgasr_ctc_hyp_workspace_bytes(T, B, V, K, Lh)
+    tail = "_wide" if _wide(V, wide, "ctc_hyp_lattice") else ""
+    nbytes = getattr(lib, "pgasr_ctc_hyp_workspace_bytes" + tail)(T, B, V, K, Lh)
     ws = _workspace(nbytes, log_probs.device, "ctc_hyp")
     hyp_nll = torch.empty(K, B, dtype=torch.float32, device=log_probs.device)
     with _timed("ctc_hyp_lattice_kernel"):
-        st = lib.pgasr_ctc_hyp_lattice(_p(log_probs), _p(hyp_tokens), stride, _p(hyp_len), _p(input_lengths), T, B, V, K, Lh, blank,
-                                       _p(hyp_nll), _p(ws), ws.numel(), _stream())
-    _lib.check(st, "pgasr_ctc_hyp_lattice")
+        st = getattr(lib, "pgasr_ctc_hyp_lattice" + tail)(_p(log_probs), _p(hyp_tokens), stride, _p(hyp_len), _p(input_lengths), T, B, V,
+                                                          K, Lh, blank, _p(hyp_nll), _p(ws), ws.numel(), _stream())
+    _lib.check(st, "pgasr_ctc_hyp_lattice" + tail)
     return hyp_nll, (ws, K, Lh)
 
 
@@ -470,16 +476,60 @@ def ctc_hyp_score(log_probs, hyp_tokens, hyp_len, input_lengths, Lh, count=None,
     return nll
 
 
+def _grad_pass_seq_wide(log_probs, input_lengths, target_lengths, handle, hyp_handle, utt_scale, pg_coef, pg_paths, hyp_len,
+                        ent_scale=None, ref_log_probs=None, kl_scale=None):
+    """``pgasr_ctc_grad_from_lattices_seq_wide`` with ``_grad_pass``'s checks of the optional terms; pg_paths None: the N-best form."""
+    lib = _lib.load()
+    ws, Lmax, blank = handle
+    hws, K, Lh = hyp_handle
+    T, B, V = log_probs.shape
+    _req(log_probs, torch.float32, "log_probs")
+    _req(input_lengths, torch.int32, "input_lengths"); _req(target_lengths, torch.int32, "target_lengths")
+    _req(utt_scale, torch.float32, "utt_scale"); _req(pg_coef, torch.float32, "pg_coef"); _req(pg_paths, torch.int32, "pg_paths")
+    _req(hyp_len, torch.int32, "hyp_len")
+    if input_lengths.numel() != B or target_lengths.numel() != B or (utt_scale is not None and utt_scale.numel() != B):
+        raise _lib.PgasrError(f"input_lengths, target_lengths and utt_scale must hold {B} utterances")
+    # the handles say nothing of T and B: the lattices must at least fit the workspaces they name
+    need, need_h = lib.pgasr_ctc_workspace_bytes(T, B, V, Lmax), lib.pgasr_ctc_hyp_workspace_bytes_wide(T, B, V, K, Lh)
+    if need_h == 0 or ws.numel() < need or hws.numel() < need_h:
+        raise _lib.PgasrError(f"the lattice handles were not made for log_probs {tuple(log_probs.shape)} with K = {K}, Lh = {Lh}: "
+                              f"workspaces of {ws.numel()} and {hws.numel()} bytes, {need} and {need_h} needed")
+    if ent_scale is not None:
+        _req(ent_scale, torch.float32, "ent_scale")
+        if tuple(ent_scale.shape) != (B,):
+            raise _lib.PgasrError(f"ent_scale must be ({B},); got {tuple(ent_scale.shape)}")
+    if ref_log_probs is not None or kl_scale is not None:
+        if ref_log_probs is None or kl_scale is None:
+            raise _lib.PgasrError("the KL term takes ref_log_probs and kl_scale together")
+        _req(ref_log_probs, torch.float32, "ref_log_probs"); _req(kl_scale, torch.float32, "kl_scale")
+        if ref_log_probs.shape != log_probs.shape or tuple(kl_scale.shape) != (B,):
+            raise _lib.PgasrError(f"ref_log_probs must be {tuple(log_probs.shape)} and kl_scale ({B},); got "
+                                  f"{tuple(ref_log_probs.shape)} and {tuple(kl_scale.shape)}")
+    grad = torch.empty_like(log_probs)
+    with _timed("ctc_grad_seq_wide_kernel"):
+        st = lib.pgasr_ctc_grad_from_lattices_seq_wide(_p(log_probs), _p(input_lengths), _p(target_lengths), T, B, V, Lmax, blank,
+                                                       _p(utt_scale), K, _p(pg_coef), _p(pg_paths), _p(hyp_len), Lh, _p(ent_scale),
+                                                       _p(ref_log_probs), _p(kl_scale), _p(grad), _p(ws), ws.numel(), _p(hws),
+                                                       hws.numel(), _stream())
+    _lib.check(st, "pgasr_ctc_grad_from_lattices_seq_wide")
+    return grad
+
+
 def ctc_grad_from_lattices_seq(log_probs, input_lengths, target_lengths, handle, hyp_handle, utt_scale, pg_coef, pg_paths, hyp_len,
-                               ent_scale=None, ref_log_probs=None, kl_scale=None):
+                               ent_scale=None, ref_log_probs=None, kl_scale=None, wide=None):
     """One gradient pass over the target lattice (``ctc_lattice``'s handle) and the K*B hypothesis lattices (``ctc_hyp_lattice``'s):
     utt_scale (softmax - occ_target) + sum_k pg_coef[k,b] * (hyp_len[k,b] <= Lh ? softmax - occ_hyp : softmax - onehot(pg_paths[k,t,b])),
-    the K terms in k order.  pg_paths (K,T,B) int32, pg_coef (K,B) fp32, hyp_len (K,B) int32."""
+    the K terms in k order.  pg_paths (K,T,B) int32, pg_coef (K,B) fp32, hyp_len (K,B) int32.
+    V > 64 (or wide=True): ``pgasr_ctc_grad_from_lattices_seq_wide``, ONE entry that takes ent_scale, ref_log_probs and kl_scale as
+    nullable pointers where the narrow family has three."""
     hws, K, Lh = hyp_handle
-    T, B, _ = log_probs.shape
+    T, B, V = log_probs.shape
     _req(hyp_len, torch.int32, "hyp_len")
     if tuple(pg_paths.shape) != (K, T, B) or tuple(pg_coef.shape) != (K, B) or tuple(hyp_len.shape) != (K, B):
         raise _lib.PgasrError(f"ctc_grad_from_lattices_seq wants pg_paths ({K},{T},{B}), pg_coef and hyp_len ({K},{B})")
+    if _wide(V, wide, "ctc_grad_from_lattices_seq"):
+        return _grad_pass_seq_wide(log_probs, input_lengths, target_lengths, handle, hyp_handle, utt_scale, pg_coef, pg_paths, hyp_len,
+                                   ent_scale, ref_log_probs, kl_scale)
     return _grad_pass("pgasr_ctc_grad_from_lattices_seq", log_probs, input_lengths, target_lengths, handle, utt_scale, pg_coef,
                       pg_paths, "pg_paths", (K, pg_coef, pg_paths, hyp_len, Lh), ws_tail=(_p(hws), hws.numel()),
                       label="ctc_grad_seq_kernel", ent_scale=ent_scale, ref_log_probs=ref_log_probs, kl_scale=kl_scale)
@@ -1703,15 +1753,18 @@ def mwer_weights(dist, risk_len, target_lengths, hyp_nll, hyp_len, count, nll, L
     return p, r, coef, rest[0], rest[1], rest[2]
 
 
-def ctc_grad_from_lattices_nbest(log_probs, input_lengths, target_lengths, handle, hyp_handle, utt_scale, coef, hyp_len):
+def ctc_grad_from_lattices_nbest(log_probs, input_lengths, target_lengths, handle, hyp_handle, utt_scale, coef, hyp_len, wide=None):
     """``ctc_grad_from_lattices_seq`` without sampled paths (pgasr_ctc_grad_from_lattices_nbest): utt_scale (softmax - occ_target) +
     sum_n coef[n,b] (softmax - occ_{y_n}) over the N*B hypothesis lattices of ``ctc_hyp_lattice``, the N terms in n order.  coef (N,B)
-    fp32; hyp_len (N,B) int32 is the tensor ``ctc_hyp_lattice`` was given."""
+    fp32; hyp_len (N,B) int32 is the tensor ``ctc_hyp_lattice`` was given.
+    V > 64 (or wide=True): ``pgasr_ctc_grad_from_lattices_seq_wide`` without a path tensor, its N-best form."""
     hws, N, Lh = hyp_handle
-    T, B, _ = log_probs.shape
+    T, B, V = log_probs.shape
     _req(hyp_len, torch.int32, "hyp_len")
     if tuple(coef.shape) != (N, B) or tuple(hyp_len.shape) != (N, B):
         raise _lib.PgasrError(f"ctc_grad_from_lattices_nbest wants coef and hyp_len ({N},{B})")
+    if _wide(V, wide, "ctc_grad_from_lattices_nbest"):
+        return _grad_pass_seq_wide(log_probs, input_lengths, target_lengths, handle, hyp_handle, utt_scale, coef, None, hyp_len)
     return _grad_pass("pgasr_ctc_grad_from_lattices_nbest", log_probs, input_lengths, target_lengths, handle, utt_scale, coef,
                       None, "paths", (N, coef, hyp_len, Lh), ws_tail=(_p(hws), hws.numel()), label="ctc_grad_nbest_kernel")
 

@@ -284,14 +284,16 @@ class PGOptions:
     kl_weight: float = 0.0
 
 
-def check_options(opt, vocab=None, frames=None, symbols=None, sample_ids=None, wide_check=True, wide_objectives=False):
+def check_options(opt, vocab=None, frames=None, symbols=None, sample_ids=None, wide_check=True, wide_objectives=False,
+                  wide_sequence=False):
     """The one check of a ``PGOptions`` -- by ``pg_ctc_loss`` per call, by ``PolicyGradientTrainer`` at construction and before
     every step --, made before any kernel runs and where the caller can read the reason.  vocab, frames (T) and symbols (the
     targets' row length) are checked against where they are known.  Returns the options with their integers as ints.
     An alphabet of 65 .. 1024 symbols (hipops.MAX_VOCAB_WIDE) takes the default objective alone -- CTC + single-sample REINFORCE
     against the greedy hypothesis (``_check_wide``); wide_check=False leaves that rule to the caller (a trainer without
     ``wide_alphabet`` refuses such a model itself).  wide_objectives=True (opt-in) admits the multi-sample, leave-one-out, entropy
-    and KL objectives for such an alphabet as well; at most 64 symbols it changes nothing."""
+    and KL objectives for such an alphabet as well; at most 64 symbols it changes nothing.  wide_sequence=True (opt-in) admits
+    score_function="sequence" there (A13-WIDE), alone or with what wide_objectives=True admits; at most 64 symbols it changes nothing."""
     _check_score(opt.score_function, opt.max_hyp_len, opt.per_step)
     if sample_ids is not None and opt.sample_base >= 0:
         raise ValueError("sample_ids and sample_base >= 0 are two addressings of the same draws: give one")
@@ -303,7 +305,7 @@ def check_options(opt, vocab=None, frames=None, symbols=None, sample_ids=None, w
         raise ValueError(f"the word-level reward takes at most {hipops.WORD_MAX_STRIDE} frames and target symbols per utterance "
                          f"(pgasr_word_ids); got T = {frames}")
     if wide_check and vocab is not None and vocab > hipops.MAX_VOCAB_NARROW:
-        _check_wide(opt, vocab, wide_objectives=bool(wide_objectives))
+        _check_wide(opt, vocab, wide_objectives=bool(wide_objectives), wide_sequence=bool(wide_sequence))
     return dataclasses.replace(opt, num_samples=int(opt.num_samples),
                                max_hyp_len=None if opt.max_hyp_len is None else int(opt.max_hyp_len),
                                entropy_weight=check_entropy_weight(opt.entropy_weight), kl_weight=check_kl_weight(opt.kl_weight))
@@ -312,12 +314,15 @@ def check_options(opt, vocab=None, frames=None, symbols=None, sample_ids=None, w
 WIDE_OBJECTIVES = ("num_samples", "baseline", "entropy_weight", "kl_weight")      # what wide_objectives=True opens above 64 symbols
 
 
-def _check_wide(opt, vocab, wide_objectives=False):
+def _check_wide(opt, vocab, wide_objectives=False, wide_sequence=False):
     """An alphabet of more than 64 symbols: the wide kernels cover log-softmax, arg-max / sample, the CTC lattice and its gradient
     pass with one sampled path -- the default objective.  Every other option runs kernels that hold one symbol per lane.
     wide_objectives=True (opt-in): the K-draw sampler, the entropy and KL statistics and the multi-sample gradient pass have wide
     forms too (include/pgasr_hip.h, A12-WIDE), so num_samples 1..16, either baseline, entropy_weight and kl_weight are admitted in
-    any combination; the beam reward search, the sequence score function, the word reward and per-step rewards stay refused."""
+    any combination; the beam reward search, the sequence score function, the word reward and per-step rewards stay refused.
+    wide_sequence=True (opt-in): the hypothesis lattices and the gradient pass over K+1 lattices have wide forms (A13-WIDE), so
+    score_function="sequence" (with max_hyp_len) is admitted -- with K = 1 against the greedy hypothesis, or with whatever
+    wide_objectives=True admits beside it; the beam reward search, the word reward and per-step rewards stay refused."""
     if vocab > hipops.MAX_VOCAB_WIDE:
         raise ValueError(f"alphabet of {vocab} symbols > {hipops.MAX_VOCAB_WIDE}: the wide kernels hold at most 16 symbols per lane")
     entropy, kl = check_entropy_weight(opt.entropy_weight), check_kl_weight(opt.kl_weight)
@@ -329,8 +334,15 @@ def _check_wide(opt, vocab, wide_objectives=False):
                             ("kl_weight", opt.kl_weight, kl == 0.0),
                             ("reward_unit", opt.reward_unit, opt.reward_unit == "char"),
                             ("per_step", opt.per_step, not opt.per_step)):
-        if ok or (wide_objectives and name in WIDE_OBJECTIVES):
+        if ok or (wide_objectives and name in WIDE_OBJECTIVES) or (wide_sequence and name == "score_function"):
             continue
+        if wide_sequence:
+            rest = (f"wide_objectives=True opens num_samples 1..{hipops.MAX_SAMPLES}, baseline='leave_one_out', entropy_weight and "
+                    f"kl_weight" if wide_objectives else
+                    "num_samples > 1, baseline='leave_one_out', entropy_weight and kl_weight need wide_objectives=True as well")
+            raise ValueError(f"{name}={given!r} takes an alphabet of at most {hipops.MAX_VOCAB_NARROW} symbols (got {vocab}): above the "
+                             f"64-symbol limit wide_sequence=True opens score_function='sequence' (with max_hyp_len); {rest}; "
+                             f"nothing else -- beam=0, reward_unit='char', no per-step rewards")
         if wide_objectives:
             raise ValueError(f"{name}={given!r} takes an alphabet of at most {hipops.MAX_VOCAB_NARROW} symbols (got {vocab}): above the "
                              f"64-symbol limit wide_objectives=True opens num_samples 1..{hipops.MAX_SAMPLES}, "
@@ -427,7 +439,7 @@ def _check_samples(num_samples, baseline, per_step=False):
 def pg_ctc_loss(logits, in_len, targets, tg_len, lam=1.0, seed=0, offset=0, global_batch=None, blank=0, beam=0, sample_base=-1,
                 per_step=False, log_probs=None, num_samples=1, baseline="hypothesis", reward_unit="char", word_delimiter=None,
                 sample_ids=None, score_function="path", max_hyp_len=None, entropy_weight=0.0, kl_weight=0.0, ref_log_probs=None,
-                wide_objectives=False):
+                wide_objectives=False, wide_sequence=False):
     """beam > 0: the baseline reward comes from the prefix-beam-search hypothesis of that width (see PGCTCLossFn).
     num_samples / baseline: multi-sample REINFORCE (see PGCTCLossFn); with num_samples > 1 the third returned tensor is R_s (K,B).
     reward_unit: "char" (default) or "word" -- the word-level reward R = -WED / W(y) with words split at the token
@@ -449,6 +461,10 @@ def pg_ctc_loss(logits, in_len, targets, tg_len, lam=1.0, seed=0, offset=0, glob
     wide_objectives: opt-in for an alphabet of 65 .. 1024 symbols -- num_samples 1..16, either baseline, entropy_weight and kl_weight
     then run there too, on the wide kernels of A12-WIDE (``_check_wide``); beam, score_function="sequence", reward_unit="word" and
     per_step stay refused.  False (default) and at most 64 symbols: every call as it was.
+    wide_sequence: opt-in for an alphabet of 65 .. 1024 symbols -- score_function="sequence" then runs there, on the wide kernels of
+    A13-WIDE: K = 1 against the greedy hypothesis, or together with whatever wide_objectives=True admits.  Set max_hyp_len for unit
+    models: the hypothesis lattices take 2 * K*B*T * roundup64(2*Lh+1) * 4 bytes (2.1 GB at K = 4, B = 32, T = 1000 with the
+    default cap).  beam, reward_unit="word" and per_step stay refused.  False (default) and at most 64 symbols: every call as it was.
     log_probs: log_softmax(logits) if the caller already has it (the head kernel's by-product, ``logits.log_probs`` of
     Seq2Seq.logits -- picked up from that attribute when not given)."""
     T, B, V = logits.shape
@@ -458,7 +474,7 @@ def pg_ctc_loss(logits, in_len, targets, tg_len, lam=1.0, seed=0, offset=0, glob
                                   score_function=score_function, max_hyp_len=max_hyp_len, entropy_weight=entropy_weight,
                                   kl_weight=kl_weight),
                         vocab=V, frames=T, symbols=targets.shape[1] if targets.dim() == 2 else 0, sample_ids=sample_ids,
-                        wide_objectives=wide_objectives)
+                        wide_objectives=wide_objectives, wide_sequence=wide_sequence)
     if log_probs is None:
         # the by-product is valid only for the tensor as the head kernel wrote it: any in-place edit since bumps _version
         log_probs = getattr(logits, "log_probs", None)

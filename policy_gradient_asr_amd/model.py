@@ -243,7 +243,8 @@ def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset
           accumulate_steps=1, score_function="path", max_hyp_len=None, entropy_weight=0.0, objective="reinforce", mwer_nbest=4,
           mwer_beam=16, init_from=None, kl_weight=0.0, kl_reference_path=None, mwer_lm_path=None, mwer_lm_alpha=0.0,
           mwer_lm_beta=0.0, target_rate=None, speed_perturb=None, noise_dir=None, rir_dir=None, snr_db=(5.0, 20.0), noise_prob=1.0,
-          rir_prob=0.5, units_path=None, wide_alphabet=None, wide_objectives=None):
+          rir_prob=0.5, units_path=None, wide_alphabet=None, wide_objectives=None, wide_sequence=None,
+          mwer_unit_lm_path=None):
     """Epoch loop of model.py:186-274 on the MI355X path: per-epoch train loss -> train_loss.npy,
     validation CTC loss -> val_losses.npy, model_best.pth / model_last.pth (state_dicts, reference
     names), plus checkpoint_last.pth (model + Adam moments + epoch) from which ``resume`` restarts
@@ -306,7 +307,13 @@ def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset
     wide_objectives: None / False (default: the line above) or True -- PolicyGradientTrainer(wide_objectives=True): with more than
     64 symbols num_samples 1..16, either reward_baseline, entropy_weight and kl_weight (with init_from / kl_reference_path) run on
     the wide kernels too; the word reward and score_function="sequence" stay refused there.  Needs wide_alphabet; kept in the
-    checkpoint beside it."""
+    checkpoint beside it.
+    wide_sequence: None (default: False, or what the checkpoint of a resumed run holds) or a bool -- with more than 64 symbols,
+    objective="mwer" (mwer_nbest <= 16, mwer_beam <= 128, reward_unit="char"; mwer.MWERTrainer(wide_sequence=True)) and
+    score_function="sequence" (PolicyGradientTrainer(wide_sequence=True)) run on the wide kernels too.  Set max_hyp_len for unit
+    models: the hypothesis lattices take 2 * K*B*T * roundup64(2*Lh+1) * 4 bytes.  Needs wide_alphabet; kept in the checkpoint beside it.
+    mwer_unit_lm_path: None or a ``lm.UnitNgramLM.save`` file: with objective="mwer" and wide_sequence the lists come from the wide
+    search fused with that unit LM at weights mwer_lm_alpha / mwer_lm_beta."""
     import os
     import numpy as np
     import torch.utils.data as tud
@@ -343,8 +350,20 @@ def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset
     if wide_alphabet is None:
         wide_alphabet = len(char2ind) > hipops.MAX_VOCAB_NARROW
     wide_alphabet = bool(wide_alphabet)
-    if wide_alphabet and objective == "mwer":
+    resume_state = None
+    if wide_sequence is None:
+        wide_sequence = False
+        last = os.path.join(model_path, "checkpoint_last.pth")
+        if wide_alphabet and resume and os.path.exists(last):           # a resumed run keeps the objective it was started with:
+            resume_state = torch.load(last, map_location="cpu")         # the one load of the checkpoint, used again below
+            wide_sequence = bool(resume_state.get("wide_sequence", False))
+    wide_sequence = bool(wide_sequence)
+    if wide_sequence and not wide_alphabet:
+        raise ValueError("wide_sequence=True opens the sequence-level objectives for alphabets of more than 64 symbols: it needs wide_alphabet")
+    if wide_alphabet and objective == "mwer" and not wide_sequence:
         raise ValueError("objective='mwer' takes an alphabet of at most 64 symbols (the beam search's limit): not with wide_alphabet")
+    if mwer_unit_lm_path is not None and not (objective == "mwer" and wide_sequence):
+        raise ValueError("mwer_unit_lm_path belongs to objective='mwer' with wide_sequence=True (the wide search fuses the unit LM)")
     wide_objectives = bool(wide_objectives)
     if wide_objectives and not wide_alphabet:
         raise ValueError("wide_objectives=True opens objectives for alphabets of more than 64 symbols: it needs wide_alphabet")
@@ -376,6 +395,11 @@ def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset
         if mwer_lm_path is not None:
             from .lm import CharNgramLM
             mwer_lm = {"lm": CharNgramLM.load(mwer_lm_path), "lm_alpha": mwer_lm_alpha, "lm_beta": mwer_lm_beta}
+        if wide_sequence:
+            mwer_lm["wide_sequence"] = True
+            if mwer_unit_lm_path is not None:
+                from .lm import UnitNgramLM
+                mwer_lm.update(unit_lm=UnitNgramLM.load(mwer_unit_lm_path), lm_alpha=mwer_lm_alpha, lm_beta=mwer_lm_beta)
         trainer = MWERTrainer(model, lr=lr, lam=lam, seed=seed, precision=precision, max_grad_norm=max_grad_norm,
                               beam_size=mwer_beam, nbest=mwer_nbest, risk_unit=reward_unit, word_delimiter=word_delimiter,
                               max_hyp_len=max_hyp_len, num_samples=num_samples, reward_baseline=reward_baseline,
@@ -391,7 +415,8 @@ def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset
                                         reward_baseline=reward_baseline, reward_unit=reward_unit, word_delimiter=word_delimiter,
                                         max_grad_norm=max_grad_norm, score_function=score_function, max_hyp_len=max_hyp_len,
                                         entropy_weight=entropy_weight, **kl, **({"wide_alphabet": True} if wide_alphabet else {}),
-                                        **({"wide_objectives": True} if wide_objectives else {}))
+                                        **({"wide_objectives": True} if wide_objectives else {}),
+                                        **({"wide_sequence": True} if wide_sequence else {}))
     losses, val_losses, best, start_epoch = [], [], 9999999.0, 1
     ckpt = os.path.join(model_path, "checkpoint_last.pth")
     resuming = resume and os.path.exists(ckpt)
@@ -399,7 +424,7 @@ def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset
         model.load_state_dict(torch.load(init_from, map_location=dev))      # in place: the trainer's flat buffer holds the parameters
         print("Initialised from", init_from)
     if resuming:
-        st = torch.load(ckpt, map_location=dev)
+        st = resume_state if resume_state is not None else torch.load(ckpt, map_location=dev)
         model.load_state_dict(st["model"])
         from .train_step import FLAG_PAD
         # the checkpoint holds the moments of the PARAMETERS (the flat buffers' leading flag words are not state)
@@ -415,6 +440,7 @@ def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset
                         ("max_hyp_len", max_hyp_len), ("entropy_weight", entropy_weight), ("kl_weight", kl_weight),
                         ("kl_reference_path", kl_reference_path), ("target_rate", target_rate),
                         ("units_path", units_path), ("wide_alphabet", wide_alphabet), ("wide_objectives", wide_objectives),
+                        ("wide_sequence", wide_sequence),
                         ("speed_perturb", None if speed_perturb is None else speed_perturb.state()),
                         ("wave_augment", None if wave_augment is None else wave_augment.state())):
             if k in st and st[k] != want:
@@ -503,7 +529,7 @@ def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset
                     "reward_unit": reward_unit, "max_grad_norm": max_grad_norm, "accumulate_steps": accumulate_steps,
                     "score_function": score_function, "max_hyp_len": max_hyp_len, "entropy_weight": trainer.entropy_weight,
                     "kl_weight": kl_weight, "kl_reference_path": kl_reference_path, "target_rate": target_rate,
-                    "units_path": units_path, "wide_alphabet": wide_alphabet, "wide_objectives": wide_objectives,
+                    "units_path": units_path, "wide_alphabet": wide_alphabet, "wide_objectives": wide_objectives, "wide_sequence": wide_sequence,
                     "speed_perturb": None if speed_perturb is None else speed_perturb.state(),
                     "wave_augment": None if wave_augment is None else wave_augment.state()}, ckpt)
     return losses, val_losses

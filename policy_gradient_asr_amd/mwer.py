@@ -36,8 +36,32 @@ class MWEROptions:
     lm_beta: float = 0.0
 
 
+@dataclasses.dataclass(frozen=True)
+class MWERWideOptions(MWEROptions):
+    """The options of a ``wide_sequence=True`` call: ``MWEROptions`` keeps its fields (a call without the keyword has the options it
+    always had), these two come with the keyword."""
+    wide: bool = True              # more than 64 symbols are taken (the wide search and the A13-WIDE kernels)
+    unit_lm: object = None         # a lm.UnitNgramLM: the list comes from the wide search fused with it (lm_alpha / lm_beta its weights)
+
+
+MAX_BEAM_WIDE = 128                  # pgasr_ctc_beam_search_wide
+
+
+def _wide_fields(opt):
+    """(wide, unit_lm) of either options class: ``MWEROptions`` has neither field and reads (False, None)."""
+    return (bool(opt.wide), opt.unit_lm) if isinstance(opt, MWERWideOptions) else (False, None)
+
+
+def _wide_list(opt, vocab):
+    """Does the list come from the wide search?  With wide_sequence=True, above 64 symbols or with a unit LM (which only that search
+    fuses); at most 64 symbols without one, the fast single-wave list as ever."""
+    wide, unit_lm = _wide_fields(opt)
+    return wide and (unit_lm is not None or (vocab is not None and int(vocab) > hipops.MAX_VOCAB_NARROW))
+
+
 def check_mwer_options(opt, vocab=None, frames=None, symbols=None):
     """Made before any kernel runs.  Returns the options with their integers as ints."""
+    wide, unit_lm = _wide_fields(opt)
     for name in ("beam", "nbest"):
         v = getattr(opt, name)
         if isinstance(v, bool) or int(v) != v:
@@ -47,12 +71,37 @@ def check_mwer_options(opt, vocab=None, frames=None, symbols=None):
     if opt.nbest > MAX_NBEST:
         raise ValueError(f"nbest {opt.nbest} > {MAX_NBEST}: the MWER kernels take at most {MAX_NBEST} hypotheses per utterance")
     if opt.lm is not None:
+        if wide and vocab is not None and int(vocab) > hipops.MAX_VOCAB_NARROW:
+            raise ValueError(f"lm= is a dense character LM over at most {hipops.MAX_VOCAB_NARROW} symbols (got {int(vocab)}): above that "
+                             f"give unit_lm=, a lm.UnitNgramLM, which the wide beam search fuses")
         if opt.lm.blank != int(opt.blank) or (vocab is not None and opt.lm.vocab != int(vocab)):
             raise ValueError(f"the LM is over {opt.lm.vocab} symbols with blank {opt.lm.blank}; the search has "
                              f"{'its own' if vocab is None else int(vocab)} symbols and blank {int(opt.blank)}")
         for name in ("lm_alpha", "lm_beta"):
             if not math.isfinite(float(getattr(opt, name))):
                 raise ValueError(f"{name} must be finite (got {getattr(opt, name)!r})")
+    if unit_lm is not None:
+        if not wide:
+            raise ValueError("unit_lm= is fused by the wide beam search: it needs wide_sequence=True")
+        if opt.lm is not None:
+            raise ValueError("lm= and unit_lm= are two language models for one search: give one")
+        if vocab is not None:
+            hipops._unit_lm_check(unit_lm, int(vocab), opt.blank)
+        for name in ("lm_alpha", "lm_beta"):
+            if not math.isfinite(float(getattr(opt, name))):
+                raise ValueError(f"{name} must be finite (got {getattr(opt, name)!r})")
+    if vocab is not None and int(vocab) > hipops.MAX_VOCAB_NARROW:
+        if not wide:
+            raise ValueError(f"MWER over an alphabet of {int(vocab)} symbols needs wide_sequence=True: without it the beam search and "
+                             f"the N-best kernels hold one symbol per lane, at most {hipops.MAX_VOCAB_NARROW}")
+        if int(vocab) > hipops.MAX_VOCAB_WIDE:
+            raise ValueError(f"alphabet of {int(vocab)} symbols > {hipops.MAX_VOCAB_WIDE}: the wide kernels hold at most 16 symbols per lane")
+        if opt.risk_unit == "word":
+            raise ValueError(f"risk_unit='word' takes an alphabet of at most {hipops.MAX_VOCAB_NARROW} symbols (got {int(vocab)}): a "
+                             f"subword unit may span a space, so a list of units has no word boundaries of its own "
+                             f"(hipops.nbest_pair_distance's reason); use risk_unit='char', the unit error rate")
+    if _wide_list(opt, vocab) and opt.beam > MAX_BEAM_WIDE:
+        raise ValueError(f"beam {opt.beam} > {MAX_BEAM_WIDE}: the wide beam search keeps at most {MAX_BEAM_WIDE} prefixes")
     _check_unit(opt.risk_unit, opt.word_delimiter, blank=opt.blank, vocab=vocab)
     _check_score("sequence", opt.max_hyp_len)
     if opt.risk_unit == "word" and frames is not None and max(frames, symbols or 0) > hipops.WORD_MAX_STRIDE:
@@ -67,6 +116,16 @@ def _lm_fields(lm, lm_alpha, lm_beta):
     return {} if lm is None else {"lm": lm, "lm_alpha": float(lm_alpha), "lm_beta": float(lm_beta)}
 
 
+def _options(wide_sequence, unit_lm, lm, lm_alpha, lm_beta, **fields):
+    """``MWEROptions`` as ever, or with the keyword ``MWERWideOptions`` (the unit LM and its weights among them)."""
+    if not wide_sequence:
+        if unit_lm is not None:
+            raise ValueError("unit_lm= is fused by the wide beam search: it needs wide_sequence=True")
+        return MWEROptions(**fields, **_lm_fields(lm, lm_alpha, lm_beta))
+    weights = {} if unit_lm is None else {"lm_alpha": float(lm_alpha), "lm_beta": float(lm_beta)}
+    return MWERWideOptions(**fields, unit_lm=unit_lm, **{**weights, **_lm_fields(lm, lm_alpha, lm_beta)})
+
+
 class MWERLossFn(torch.autograd.Function):
     """loss = sum_b [ nll_b / (Bg max(L_b,1))  +  lam / Bg * sum_n p[n,b] r[n,b] ]
 
@@ -77,6 +136,8 @@ class MWERLossFn(torch.autograd.Function):
         r[n,b]     =  ED(y_b, y_n) / max(L_b,1), or WED / W(y_b) with risk_unit = "word"
         d(logits)  =  utt_scale_b (softmax - occ_target) + sum_n coef[n,b] (softmax - occ_{y_n}),
         coef[n,b]  =  -lam / Bg * p[n,b] (r[n,b] - rbar_b)
+    ``MWERWideOptions`` (wide_sequence=True) with more than 64 symbols: the list is ``ctc_beam_search_wide``'s (beam <= 128; with ``opt.unit_lm``
+    the search fused with that back-off unit LM), the lattices and the gradient pass are the A13-WIDE entries; char risk only.
     With ``opt.lm`` the list is the final beam of the LM-FUSED search (every extension by s gets lm_alpha * ln p_lm(s | context) + lm_beta,
     ``ctc_beam_search_nbest(lm=, fast=True, fast_lm=True)``: the single-wave kernel with the LM term): the hypotheses the model is
     decoded to at test time.  The LM only chooses which hypotheses are in the list; p, r and the gradient are formed as above.
@@ -105,8 +166,14 @@ class MWERLossFn(torch.autograd.Function):
         PGCTCLossFn._lattice_streams[main.cuda_stream] = side
         side.wait_stream(main)
         with torch.cuda.stream(side):
-            fused = {} if opt.lm is None else {"lm": opt.lm, "lm_alpha": float(opt.lm_alpha), "lm_beta": float(opt.lm_beta), "fast_lm": True}
-            nb = hipops.ctc_beam_search_nbest(lp, in_len, beam=opt.beam, nbest=N, blank=blank, collapse=False, fast=True, **fused)
+            if _wide_list(opt, V):
+                # wide_sequence=True above 64 symbols (or with a unit LM): the exact wide search's list; everything behind it is the
+                # sequence of calls below, whose wrappers take the A13-WIDE entries by V
+                fused = {} if opt.unit_lm is None else {"unit_lm": opt.unit_lm, "lm_alpha": float(opt.lm_alpha), "lm_beta": float(opt.lm_beta)}
+                nb = hipops.ctc_beam_search_wide(lp, in_len, beam=opt.beam, nbest=N, blank=blank, collapse=False, **fused)
+            else:
+                fused = {} if opt.lm is None else {"lm": opt.lm, "lm_alpha": float(opt.lm_alpha), "lm_beta": float(opt.lm_beta), "fast_lm": True}
+                nb = hipops.ctc_beam_search_nbest(lp, in_len, beam=opt.beam, nbest=N, blank=blank, collapse=False, fast=True, **fused)
             # a hypothesis over the cap gets the EMPTY hypothesis' lattice (rows beyond count have length 0 already): every lattice
             # the gradient pass reads was really computed, and meets a coefficient of 0
             lat_len = torch.where(nb.lengths > Lh, torch.zeros_like(nb.lengths), nb.lengths)
@@ -153,24 +220,30 @@ def mwer_ctc_loss(logits, in_len, targets, tg_len, lam=1.0, beam=16, nbest=4, gl
     workspace, 2 * nbest*B*T * roundup64(2*Lh+1) * 4 bytes.
     log_probs: log_softmax(logits) if the caller already has it (picked up from ``logits.log_probs`` when not given).
     Returns (loss, nll (B), expected_reward (B) = -rbar, top_reward (B) = -r[0]).  The list is the acoustic search's;
-    ``mwer_ctc_loss_lm`` takes it from the search fused with a language model."""
+    ``mwer_ctc_loss_lm`` takes it from the search fused with a language model, and (``wide_sequence=True``) takes alphabets of 65 ..
+    1024 symbols: this function keeps its parameter list."""
     return mwer_ctc_loss_lm(logits, in_len, targets, tg_len, None, lam=lam, beam=beam, nbest=nbest, global_batch=global_batch, blank=blank,
                             risk_unit=risk_unit, word_delimiter=word_delimiter, max_hyp_len=max_hyp_len, log_probs=log_probs)
 
 
 def mwer_ctc_loss_lm(logits, in_len, targets, tg_len, lm=None, lm_alpha=0.0, lm_beta=0.0, lam=1.0, beam=16, nbest=4, global_batch=None,
-                     blank=0, risk_unit="char", word_delimiter=None, max_hyp_len=None, log_probs=None):
+                     blank=0, risk_unit="char", word_delimiter=None, max_hyp_len=None, log_probs=None, wide_sequence=False,
+                     unit_lm=None):
     """``mwer_ctc_loss`` over the N-best list of the LM-FUSED search: ``lm`` a ``lm.CharNgramLM`` over the same V symbols and blank, its
     weights lm_alpha / lm_beta as ``CTCDecoder`` takes them (``MWERLossFn``; the list comes from the single-wave kernel's LM
     instantiation where its limits allow).  The posterior over the list stays the exact CTC likelihood.  ``lm=None`` is
     ``mwer_ctc_loss``: the options and the calls it always made.  (A function of its own because ``mwer_ctc_loss`` keeps its
-    parameter list.)"""
+    parameter list.)
+    wide_sequence: opt-in for an alphabet of 65 .. 1024 symbols (V <= 64 without unit_lm: the call as it was, bit for bit) -- the list
+    is ``hipops.ctc_beam_search_wide``'s (beam <= 128, nbest <= 16), risk_unit "char" only; unit_lm: a ``lm.UnitNgramLM`` that search is
+    fused with, weighted by lm_alpha / lm_beta -- above 64 symbols ``lm`` (dense, character-level) is refused in its favour.  Set
+    max_hyp_len for unit models: the default cap takes 2.1 GB of lattices at nbest = 4, B = 32, T = 1000."""
     if logits.dim() != 3:
         raise ValueError("mwer_ctc_loss: logits (T,B,V)")
     T, B, V = logits.shape
-    opt = check_mwer_options(MWEROptions(lam=float(lam), beam=beam, nbest=nbest, global_batch=int(global_batch or B), blank=int(blank),
-                                         risk_unit=risk_unit, word_delimiter=word_delimiter, max_hyp_len=max_hyp_len,
-                                         **_lm_fields(lm, lm_alpha, lm_beta)),
+    opt = check_mwer_options(_options(wide_sequence, unit_lm, lm, lm_alpha, lm_beta, lam=float(lam), beam=beam, nbest=nbest,
+                                      global_batch=int(global_batch or B), blank=int(blank), risk_unit=risk_unit,
+                                      word_delimiter=word_delimiter, max_hyp_len=max_hyp_len),
                              vocab=V, frames=T, symbols=targets.shape[1] if targets.dim() == 2 else 0)
     for name, t_ in (("logits", logits), ("in_len", in_len), ("targets", targets), ("tg_len", tg_len)):
         if not t_.is_cuda:
@@ -189,15 +262,20 @@ class MWERTrainer(PolicyGradientTrainer):
     ``last_stats`` = (nll, expected reward -rbar, top-hypothesis reward -r[0]), each (B,); ``last_sample_rewards`` = -r, (nbest, B);
     ``last_posterior`` (nbest, B), 0 where an entry is not in the list's posterior.
     lm / lm_alpha / lm_beta: None (default) or a ``lm.CharNgramLM`` and its weights -- the N-best lists then come from the LM-fused search
-    (the standard MWER setting, arXiv:1712.01818 section 3: train on the lists the model is decoded to); ``mwer_options`` holds the checked options."""
+    (the standard MWER setting, arXiv:1712.01818 section 3: train on the lists the model is decoded to); ``mwer_options`` holds the checked options.
+    wide_sequence=True: an alphabet of 65 .. 1024 subword units -- MAX_VOCAB becomes 1024, the lists come from ``ctc_beam_search_wide``
+    (beam_size <= 128, nbest <= 16), with ``unit_lm`` (a ``lm.UnitNgramLM``, weights lm_alpha / lm_beta) from that search fused with it;
+    risk_unit="char" and no dense ``lm`` above 64 symbols.  Set max_hyp_len for unit models (2.1 GB of lattices at nbest = 4, B = 32,
+    T = 1000 with the default cap).  ``wide_alphabet=True`` without it keeps being refused."""
 
     _FIXED = {"num_samples": 1, "reward_baseline": "hypothesis", "score_function": "path", "reward_mode": "utterance",
               "reward_decoder": "greedy", "entropy_weight": 0.0}
 
     def __init__(self, model, lr=5e-4, lam=1.0, seed=0, blank=0, world_size=1, process_group=None, rank=0, precision=None,
                  max_grad_norm=None, beam_size=16, nbest=4, risk_unit="char", word_delimiter=None, max_hyp_len=None, lm=None, lm_alpha=0.0,
-                 lm_beta=0.0, **sampled):
-        if sampled.pop("wide_alphabet", False):
+                 lm_beta=0.0, wide_sequence=False, unit_lm=None, **sampled):
+        wide_sequence = bool(wide_sequence)
+        if sampled.pop("wide_alphabet", False) and not wide_sequence:
             raise ValueError("MWERTrainer takes an alphabet of at most 64 symbols: the beam search and the N-best kernels hold one "
                              "symbol per lane (wide_alphabet=True is PolicyGradientTrainer's default objective only)")
         for k, v in sampled.items():
@@ -206,17 +284,28 @@ class MWERTrainer(PolicyGradientTrainer):
             if isinstance(v, bool) or v != self._FIXED[k]:
                 raise ValueError(f"MWERTrainer samples nothing: {k}={v!r} has no meaning here (an entropy bonus for MWER is not built)")
         vocab = getattr(getattr(model, "head", None), "out_features", None)
-        opt = check_mwer_options(MWEROptions(blank=int(blank), beam=beam_size, nbest=nbest, risk_unit=risk_unit,
-                                             word_delimiter=word_delimiter, max_hyp_len=max_hyp_len,
-                                             **_lm_fields(lm, lm_alpha, lm_beta)), vocab=vocab)
+        opt = check_mwer_options(_options(wide_sequence, unit_lm, lm, lm_alpha, lm_beta, blank=int(blank), beam=beam_size, nbest=nbest,
+                                          risk_unit=risk_unit, word_delimiter=word_delimiter, max_hyp_len=max_hyp_len), vocab=vocab)
+        # wide_sequence=True lifts MAX_VOCAB to 1024 itself: the parent's wide_alphabet, whose default objective is not run here
         super().__init__(model, lr=lr, lam=lam, seed=seed, blank=blank, world_size=world_size, process_group=process_group, rank=rank,
-                         precision=precision, max_grad_norm=max_grad_norm)
+                         precision=precision, max_grad_norm=max_grad_norm,
+                         **({"wide_alphabet": True, "wide_sequence": True} if wide_sequence else {}))
         self.beam_size, self.nbest = opt.beam, opt.nbest
         self.risk_unit, self.mwer_max_hyp_len = risk_unit, opt.max_hyp_len
         self.risk_delimiter = None if word_delimiter is None else int(word_delimiter)
         self.mwer_lm, self.mwer_lm_alpha, self.mwer_lm_beta = opt.lm, opt.lm_alpha, opt.lm_beta
+        self.mwer_unit_lm = _wide_fields(opt)[1]
         self.mwer_options = opt
         self.last_posterior = None
+
+    def _list_fields(self):
+        """What ``mwer_ctc_loss_lm`` takes beyond the call it always got: nothing without an LM and without wide_sequence."""
+        if not self.wide_sequence:
+            return _lm_fields(self.mwer_lm, self.mwer_lm_alpha, self.mwer_lm_beta)
+        fields = {"wide_sequence": True, "unit_lm": self.mwer_unit_lm}
+        if self.mwer_lm is not None or self.mwer_unit_lm is not None:
+            fields.update(lm=self.mwer_lm, lm_alpha=self.mwer_lm_alpha, lm_beta=self.mwer_lm_beta)
+        return fields
 
     def forward_loss(self, batch, global_batch):
         x, targets, fmask, tmask = batch
@@ -235,7 +324,7 @@ class MWERTrainer(PolicyGradientTrainer):
         loss, nll, expected, top = mwer_ctc_loss_lm(logits, in_len, tg, tg_len, lam=self.lam, beam=self.beam_size, nbest=self.nbest,
                                                     global_batch=global_batch, blank=self.blank, risk_unit=self.risk_unit,
                                                     word_delimiter=self.risk_delimiter, max_hyp_len=self.mwer_max_hyp_len,
-                                                    **_lm_fields(self.mwer_lm, self.mwer_lm_alpha, self.mwer_lm_beta))
+                                                    **self._list_fields())
         post = MWERLossFn.last_posterior
         R_all = -MWERLossFn.last_risk                            # (N,B): every entry's reward
         self.last_posterior = post[:, :real_b] if padded else post

@@ -448,7 +448,7 @@ class PolicyGradientTrainer(DataParallelStep):
                  reward_decoder="greedy", beam_size=16, precision=None, reward_mode="utterance", num_samples=1,
                  reward_baseline="hypothesis", reward_unit="char", word_delimiter=None, max_grad_norm=None,
                  score_function="path", max_hyp_len=None, entropy_weight=0.0, kl_weight=0.0, kl_reference=None, wide_alphabet=False,
-                 wide_objectives=False):
+                 wide_objectives=False, wide_sequence=False):
         """wide_alphabet: opt in to alphabets of 65 .. 1024 symbols (subword units).  MAX_VOCAB becomes 1024, and such a model takes
         the default objective alone: reward_decoder="greedy", reward_mode="utterance", num_samples=1, reward_baseline="hypothesis",
         reward_unit="char", score_function="path", entropy_weight=0, kl_weight=0 -- anything else raises here and before every
@@ -457,6 +457,10 @@ class PolicyGradientTrainer(DataParallelStep):
         entropy_weight and kl_weight / kl_reference for such a model too, in any combination, on the wide kernels of A12-WIDE;
         reward_decoder="beam", reward_mode="per_step", reward_unit="word" and score_function="sequence" stay refused there.  The
         default objective keeps its launches and bits with or without it.
+        wide_sequence: with wide_alphabet=True (else ValueError), opt in to score_function="sequence" for such a model, on the wide
+        kernels of A13-WIDE: num_samples=1 against the greedy hypothesis, or together with whatever wide_objectives=True admits.  Set
+        max_hyp_len for unit models (the workspace formula below: 2.1 GB at K = 4, B = 32, T = 1000 with the default cap).
+        reward_decoder="beam", reward_mode="per_step" and reward_unit="word" stay refused there.
         reward_mode: "utterance" (default) -- one reward R = -ED / |y| per utterance, the sum of the reference's per-step rewards
         (policy_grad.py:10-15) up to a constant the baseline removes; "per_step" -- the per-step rewards themselves, as rewards-to-go
         per frame against the greedy path's reward-to-go at the same frame (loss.PGCTCLossFn; greedy baseline only).
@@ -507,6 +511,10 @@ class PolicyGradientTrainer(DataParallelStep):
         self.wide_objectives = bool(wide_objectives)
         if self.wide_objectives and not self.wide_alphabet:
             raise ValueError("wide_objectives=True opens objectives for alphabets of more than 64 symbols: it needs wide_alphabet=True")
+        self.wide_sequence = bool(wide_sequence)
+        if self.wide_sequence and not self.wide_alphabet:
+            raise ValueError("wide_sequence=True opens the sequence-level objectives for alphabets of more than 64 symbols: it needs "
+                             "wide_alphabet=True")
         if reward_decoder not in ("greedy", "beam"):
             raise ValueError("reward_decoder must be 'greedy' or 'beam'")
         if reward_mode not in ("utterance", "per_step"):
@@ -612,7 +620,8 @@ class PolicyGradientTrainer(DataParallelStep):
                         score_function=self.score_function, max_hyp_len=self.max_hyp_len, entropy_weight=self.entropy_weight,
                         kl_weight=self.kl_weight)
         return check_options(opt, vocab=vocab, frames=frames, symbols=symbols, wide_check=self.wide_alphabet,
-                             wide_objectives=getattr(self, "wide_objectives", False))
+                             wide_objectives=getattr(self, "wide_objectives", False),
+                             wide_sequence=getattr(self, "wide_sequence", False))
 
     def _check_limits(self, x, targets):
         """The kernels' compiled-in limits, stated where the caller can read them (otherwise the first symptom is a
@@ -723,7 +732,8 @@ class PolicyGradientTrainer(DataParallelStep):
                                           word_delimiter=self.word_delimiter, sample_ids=sample_ids,
                                           score_function=self.score_function, max_hyp_len=self.max_hyp_len,
                                           entropy_weight=self.entropy_weight, **kl,
-                                          **({"wide_objectives": True} if self.wide_objectives else {}))
+                                          **({"wide_objectives": True} if self.wide_objectives else {}),
+                                          **({"wide_sequence": True} if self.wide_sequence else {}))
         scored = PGCTCLossFn.last_sequence_scored                # (K,B) bool, None with score_function="path"
         self.last_sequence_scored = scored[:, :real_b] if (padded and scored is not None) else scored
         ent = PGCTCLossFn.last_entropy                           # (B,) mean frame entropy, None with entropy_weight = 0
