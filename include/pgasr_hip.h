@@ -53,7 +53,8 @@ typedef enum pgasr_status {
  * sample-rate conversion / speed perturbation (pgasr_resample), and minimum-Bayes-risk decoding over N-best lists
  * (pgasr_nbest_pair_dist, pgasr_mbr_select), and waveform augmentation (pgasr_reverb_limits, pgasr_reverb, pgasr_wave_power,
  * pgasr_wave_mix), and edit-operation alignment (pgasr_edit_ops_workspace_bytes, pgasr_edit_ops), and the wide-alphabet entries
- * (pgasr_log_softmax_rows_wide, pgasr_frame_argmax_sample_wide, pgasr_ctc_loss_grad_wide, pgasr_ctc_grad_from_lattice_wide). */
+ * (pgasr_log_softmax_rows_wide, pgasr_frame_argmax_sample_wide, pgasr_ctc_loss_grad_wide, pgasr_ctc_grad_from_lattice_wide), and
+ * spelling rows of subword units into characters (pgasr_unit_spell). */
 #define PGASR_ABI_VERSION 7
 
 int pgasr_abi_version(void);
@@ -333,6 +334,27 @@ int pgasr_word_ids(const int32_t* ref, const int32_t* ref_len, int ref_stride,
 int pgasr_pg_rewards_multi_ex(const int32_t* dist, const int32_t* reward_lengths, const int32_t* target_lengths, int B, int K,
                               int baseline, float lam, float inv_global_batch, float* R_baseline, float* R_sample,
                               float* pg_coef, float* utt_scale, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * A11-SPELL  spelling rows of subword units into rows of characters, opt-in: a unit of a 65 .. 1024-symbol alphabet may hold a
+ * space, so a unit row has no word boundaries of its own and its unit edit distance depends on the unit inventory.  The spelled row
+ * is a row over at most 64 character ids, which pgasr_word_ids, pgasr_edit_distance, pgasr_nbest_pair_dist and pgasr_edit_ops take
+ * as it is: WER and CER of the text for a subword model.
+ *   spell_off (V+1) int32, spell_chars int32: unit id v in [0, V) spells spell_chars[spell_off[v] .. spell_off[v+1]), at most
+ *     PGASR_SPELL_MAX_UNIT_CHARS characters (the host checks the table; a longer entry is read up to the cap); id 0, the blank /
+ *     pad, has an empty spelling.
+ *   Row n reads tokens[n, i] for i < clamp(lengths[n], 0, stride).  A token outside [0, V) and a token with an empty spelling
+ *     contribute nothing.  full_len[n] (may be NULL) = the length of the concatenated spellings, out_len[n] = min(full_len[n],
+ *     out_stride), out[n, :out_len[n]] = the concatenation cut at out_stride characters (the cut may fall inside a unit), and
+ *     out[n, out_len[n] : out_stride] is written as 0: the output need not be initialised.
+ *   One launch, one wave per row; no workspace, no atomics, no host synchronisation; deterministic.
+ *   N <= 0, stride < 0, out_stride < 0, V < 1, a missing required pointer: PGASR_ERR_INVALID_ARG; stride > 2^24:
+ *   PGASR_ERR_UNSUPPORTED (full_len stays an int32).
+ * ---------------------------------------------------------------------------------------- */
+#define PGASR_SPELL_MAX_UNIT_CHARS 64
+int pgasr_unit_spell(const int32_t* tokens, const int32_t* lengths, int stride, int N,
+                     const int32_t* spell_off, const int32_t* spell_chars, int V,
+                     int32_t* out, int out_stride, int32_t* out_len, int32_t* full_len /* may be NULL */, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * A4  the CTC head as one kernel (model.py:52-55 as the build's Seq2Seq uses it): logits = x W^T + bias, log_probs = log_softmax.

@@ -273,7 +273,8 @@ class CTCDecoder:
         res = NBestRescored(order, total, am, lm_logp, best[0], best[1], skipped)
         return res if unit_lm is None else NBestRescoredUnits(*res, unit_logp)
 
-    def mbr_from_list(self, nb, score, vocab=None, risk_unit="char", word_delimiter=None, posterior_scale=1.0, max_hyp_len=None):
+    def mbr_from_list(self, nb, score, vocab=None, risk_unit="char", word_delimiter=None, posterior_scale=1.0, max_hyp_len=None,
+                      unit_spelling=None):
         """Minimum-Bayes-risk choice over an N-best list the caller already holds: ``nb`` a ``hipops.CTCNBest`` (N <= 128), ``score``
         (N,B) float64 with lower better (``rescore(...).total``, ``nb.score``, ...), ``vocab`` the number of symbols (default: the
         alphabet's).  posterior = softmax(-posterior_scale * score) over the list's valid rows; the row of least expected edit
@@ -286,12 +287,24 @@ class CTCDecoder:
             avoids it, and a hypothesis longer than that takes no part (risk +inf, posterior 0).
         Returns ``MBRDecoded``: tokens (B,T) / lengths (B) int32 the chosen row of every utterance, best (B) int32 its rank in the
         list, risk (N,B) / posterior (N,B) float64, dist (B,N,N) int32 (-1 where a row takes no part), nbest = ``nb``.
-        risk[best[b], b] is the expected number of unit (word) errors of the returned hypothesis: a confidence."""
+        risk[best[b], b] is the expected number of unit (word) errors of the returned hypothesis: a confidence.
+        unit_spelling: None (default: everything above) or the ``units.UnitSpelling`` of a list of subword units: the distances come
+            from the spelled text of the list (``hipops.nbest_pair_distance_spelled``) -- risk_unit="char" its characters, "word" its
+            words, split at the spelling's " " (no word_delimiter), whatever the number of units; max_hyp_len then caps the spelled
+            rows.  The returned tokens stay the list's unit rows."""
         if risk_unit not in ("char", "word"):
             raise ValueError(f"risk_unit must be 'char' or 'word' (got {risk_unit!r})")
         V = len(self.alphabet) if vocab is None else int(vocab)
-        dist = hipops.nbest_pair_distance(nb.tokens, nb.lengths, nb.count, V, max_hyp_len=max_hyp_len, unit=risk_unit,
-                                          delimiter=word_delimiter)
+        if unit_spelling is not None:
+            if word_delimiter is not None:
+                raise ValueError("unit_spelling brings its own word delimiter, the id of ' ' in the spelled text: give no word_delimiter")
+            if unit_spelling.vocab != V:
+                raise ValueError(f"unit_spelling spells {unit_spelling.vocab} symbols (units and blank), the list is over {V}")
+            dist = hipops.nbest_pair_distance_spelled(nb.tokens, nb.lengths, nb.count, unit_spelling, max_hyp_len=max_hyp_len,
+                                                      unit=risk_unit)
+        else:
+            dist = hipops.nbest_pair_distance(nb.tokens, nb.lengths, nb.count, V, max_hyp_len=max_hyp_len, unit=risk_unit,
+                                              delimiter=word_delimiter)
         best, risk, posterior = hipops.mbr_select(dist, score.contiguous(), nb.count, scale=float(posterior_scale))
         first = best.long()
         cols = torch.arange(first.numel(), device=first.device)
@@ -299,20 +312,27 @@ class CTCDecoder:
 
     def mbr_decode(self, log_probs, lengths=None, beam_size=16, nbest=16, risk_unit="char", word_delimiter=None, acoustic="ctc",
                    posterior_scale=1.0, lm=_UNSET, lm_alpha=None, lm_beta=None, am_weight=1.0, max_hyp_len=None, blank=0,
-                   word_lm=None, word_lm_alpha=0.0, word_lm_beta=0.0, unit_lm=None, unit_lm_alpha=0.0, unit_lm_beta=0.0):
+                   word_lm=None, word_lm_alpha=0.0, word_lm_beta=0.0, unit_lm=None, unit_lm_alpha=0.0, unit_lm_beta=0.0,
+                   unit_spelling=None):
         """Minimum-Bayes-risk decoding: the N-best search (``decode_batch(nbest=)``, with the decoder's first-pass LM if it has
         one), the score of every hypothesis (``rescore(...).total`` with ``acoustic`` / ``lm`` / ``lm_alpha`` / ``lm_beta`` /
         ``am_weight`` as ``rescore`` takes them: without an LM the exact CTC -log p, or the first-pass score), the distances inside
         each list and the selection (``mbr_from_list``), in that order.  log_probs (T,B,V) GPU tensor, nbest <= beam_size, nbest <= 128.
         word_lm / word_lm_alpha / word_lm_beta go to ``rescore`` (words split at ``word_delimiter``, as the word risk): the
         posterior then comes from the totals with the word LM in them; unit_lm / unit_lm_alpha / unit_lm_beta likewise (a
-        ``lm.UnitNgramLM`` in the second pass, wide lists included).  Returns ``MBRDecoded``."""
+        ``lm.UnitNgramLM`` in the second pass, wide lists included).  unit_spelling: the risk over the spelled text of a list of
+        subword units (``mbr_from_list``; max_hyp_len keeps capping the unit rows, the spelled rows by that many units' longest
+        spelling).  Returns ``MBRDecoded``."""
         T, B, V = log_probs.shape
         nb = self.decode_batch(log_probs, lengths, beam_size=beam_size, blank=blank, nbest=int(nbest))
         rs = self.rescore(log_probs, lengths, nb, lm=lm, lm_alpha=lm_alpha, lm_beta=lm_beta, acoustic=acoustic, am_weight=am_weight,
                           max_hyp_len=max_hyp_len, blank=blank, word_lm=word_lm, word_lm_alpha=word_lm_alpha,
                           word_lm_beta=word_lm_beta, word_delimiter=word_delimiter, unit_lm=unit_lm, unit_lm_alpha=unit_lm_alpha,
                           unit_lm_beta=unit_lm_beta)
+        if unit_spelling is not None:
+            cap = None if max_hyp_len is None else int(max_hyp_len) * unit_spelling.max_unit_chars
+            return self.mbr_from_list(nb, rs.total, vocab=V, risk_unit=risk_unit, word_delimiter=word_delimiter,
+                                      posterior_scale=posterior_scale, max_hyp_len=cap, unit_spelling=unit_spelling)
         return self.mbr_from_list(nb, rs.total, vocab=V, risk_unit=risk_unit, word_delimiter=word_delimiter,
                                   posterior_scale=posterior_scale, max_hyp_len=max_hyp_len)
 

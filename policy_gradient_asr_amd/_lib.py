@@ -83,6 +83,7 @@ SIGNATURES = {
                                  c_ptr]),
     "pgasr_pg_rewards_multi_ex": (C.c_int, [c_i32p, c_i32p, c_i32p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, c_f32p, c_f32p,
                                             c_f32p, c_f32p, c_ptr]),
+    "pgasr_unit_spell": (C.c_int, [c_i32p, c_i32p, C.c_int, C.c_int, c_i32p, c_i32p, C.c_int, c_i32p, C.c_int, c_i32p, c_i32p, c_ptr]),
     "pgasr_batch_prep": (C.c_int, [c_f32p, C.c_int, C.c_int, c_ptr, c_ptr, C.c_int, c_i32p, c_i32p, c_i32p, c_ptr]),
     "pgasr_ctc_collapse": (C.c_int, [c_i32p, c_i32p, C.c_int, C.c_int, C.c_int, C.c_int, c_i32p, c_i32p, c_ptr]),
     "pgasr_edit_distance": (C.c_int, [c_i32p, c_i32p, C.c_int, c_i32p, c_i32p, C.c_int, C.c_int,

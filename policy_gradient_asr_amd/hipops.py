@@ -986,6 +986,57 @@ def word_edit_distance(ref, ref_len, hyp, hyp_len, delimiter):
     return edit_distance(ref_ids, ref_words, hyp_ids, hyp_words), ref_words, hyp_words
 
 
+SPELL_MAX_UNIT_CHARS = 64        # PGASR_SPELL_MAX_UNIT_CHARS
+
+
+def unit_spell(tokens, lengths, spelling, out_stride=None, want_full=False):
+    """Rows of subword units -> rows of character ids (pgasr_unit_spell; include/pgasr_hip.h, A11-SPELL): tokens (N,stride) or
+    (P,B,T) int32 with lengths (N,) or (P,B), ``spelling`` a ``units.UnitSpelling``.  Returns (chars, char_len[, full_len]) int32 with
+    the rows' leading shape: chars (.., out_stride) is the concatenation of the units' spellings cut at out_stride and zero behind
+    char_len = min(full_len, out_stride).  out_stride: None = min(stride * spelling.max_unit_chars, WORD_MAX_STRIDE), which keeps every
+    spelled row within pgasr_word_ids' and pgasr_edit_distance's limits.  One launch, no host synchronisation."""
+    lib = _lib.load()
+    _req(tokens, torch.int32, "tokens"); _req(lengths, torch.int32, "lengths")
+    if tokens.dim() < 2 or tuple(lengths.shape) != tuple(tokens.shape[:-1]):
+        raise _lib.PgasrError("unit_spell wants tokens (.., stride) and lengths of the leading shape")
+    if spelling.max_unit_chars > SPELL_MAX_UNIT_CHARS:
+        raise ValueError(f"a unit of {spelling.max_unit_chars} characters: pgasr_unit_spell takes at most {SPELL_MAX_UNIT_CHARS}")
+    lead, stride = tuple(tokens.shape[:-1]), tokens.shape[-1]
+    N = lengths.numel()
+    if out_stride is None:
+        out_stride = min(stride * spelling.max_unit_chars, WORD_MAX_STRIDE)
+    out_stride = int(out_stride)
+    if out_stride < 0:
+        raise ValueError(f"out_stride must be >= 0 (got {out_stride})")
+    dev = tokens.device
+    off, pool = spelling.to(dev)
+    out = torch.empty(lead + (out_stride,), dtype=torch.int32, device=dev)
+    lens = torch.empty((2 if want_full else 1,) + lead, dtype=torch.int32, device=dev)
+    with _timed("unit_spell"):
+        st = lib.pgasr_unit_spell(_p(tokens) if stride else 0, _p(lengths), stride, N, _p(off), _p(pool), spelling.vocab,
+                                  _p(out) if out_stride else 0, out_stride, lens[0].data_ptr(),
+                                  lens[1].data_ptr() if want_full else 0, _stream())
+    _lib.check(st, "pgasr_unit_spell")
+    return (out, lens[0], lens[1]) if want_full else (out, lens[0])
+
+
+def spelled_edit_distance(ref, ref_len, hyp, hyp_len, spelling, unit="char"):
+    """The edit distance of N pairs of unit rows over their SPELLED text: both sides through ``unit_spell``, then ``edit_distance``
+    (unit="char") or ``word_edit_distance`` at the spelling's " " (unit="word").  Returns (dist (N,), ref_count (N,), truncated)
+    int32 on the device: ref_count the reference's spelled length or word count, truncated the number of rows, of either side, whose
+    spelling was cut at the output stride (a 0-d tensor; nothing synchronises on it)."""
+    if unit not in ("char", "word"):
+        raise ValueError(f"unit must be 'char' or 'word' (got {unit!r})")
+    delim = spelling.word_delimiter() if unit == "word" else None
+    rc, rl, rf = unit_spell(ref, ref_len, spelling, want_full=True)
+    hc, hl, hf = unit_spell(hyp, hyp_len, spelling, want_full=True)
+    truncated = ((rf > rl).sum() + (hf > hl).sum()).to(torch.int32)
+    if unit == "char":
+        return edit_distance(rc, rl, hc, hl), rl, truncated
+    dist, ref_words, _ = word_edit_distance(rc, rl, hc, hl, delim)
+    return dist, ref_words, truncated
+
+
 EditOps = collections.namedtuple("EditOps", "counts ops n_ops")
 WordEditOps = collections.namedtuple("WordEditOps", "counts ops n_ops ref_words hyp_words")
 EDIT_OPS_MAX_VOCAB = 64          # csrc/editops.hip: the confusion matrix
@@ -1923,7 +1974,8 @@ def nbest_pair_distance(tokens, lengths, count, vocab, max_hyp_len=None, unit="c
     unit="word": words split at the token ``delimiter`` as str.split(" ") cuts them (``word_edit_distance`` on the composed path);
         vocab <= 64 only (ValueError above: a subword unit may span a space).
     max_hyp_len: the cap.  None: the longest hypothesis of the lists, read from the device (ONE host synchronisation, as in
-        ``CTCDecoder.rescore``; unit="word" needs none) -- nothing is over it.  A number avoids the synchronisation."""
+        ``CTCDecoder.rescore``; unit="word" needs none) -- nothing is over it.  A number avoids the synchronisation.
+    A list of subword units is counted in characters or words of its text by ``nbest_pair_distance_spelled``."""
     _lib.load()
     _req(tokens, torch.int32, "tokens"); _req(lengths, torch.int32, "lengths"); _req(count, torch.int32, "count")
     if tokens.dim() != 3 or tuple(lengths.shape) != tuple(tokens.shape[:2]) or count.numel() != tokens.shape[1]:
@@ -1953,6 +2005,22 @@ def nbest_pair_distance(tokens, lengths, count, vocab, max_hyp_len=None, unit="c
         with _timed("nbest_pair_dist_composed"):
             return _pair_distance_composed(tokens, lengths, count, vocab, cap, unit, delimiter)
     return _pair_distance_kernel(tokens, lengths, count, vocab, cap)
+
+
+def nbest_pair_distance_spelled(tokens, lengths, count, spelling, max_hyp_len=None, unit="char"):
+    """``nbest_pair_distance`` over the SPELLED text of a list of subword units (``nbest_pair_distance``'s own parameter list is
+    fixed, so the spelling has an entry of its own): the list is spelled first (``unit_spell``, one launch) and is then a list over
+    at most 64 character ids that takes the paths there by its rules -- unit="char" counts the characters of the text (the
+    bit-vector kernel or the composed path, by the length rule), unit="word" its words, split at the spelling's " " (the composed
+    word path).  max_hyp_len caps the spelled rows."""
+    if unit not in ("char", "word"):
+        raise ValueError(f"unit must be 'char' or 'word' (got {unit!r})")
+    delimiter = spelling.word_delimiter() if unit == "word" else None
+    _req(tokens, torch.int32, "tokens"); _req(lengths, torch.int32, "lengths")
+    if tokens.dim() != 3 or tuple(lengths.shape) != tuple(tokens.shape[:2]):
+        raise _lib.PgasrError("nbest_pair_distance_spelled wants tokens (N,B,stride), lengths (N,B) and count (B)")
+    chars, char_len = unit_spell(tokens, lengths, spelling)
+    return nbest_pair_distance(chars, char_len, count, spelling.n_symbols, max_hyp_len=max_hyp_len, unit=unit, delimiter=delimiter)
 
 
 def _pair_distance_kernel(tokens, lengths, count, vocab, cap):

@@ -107,6 +107,12 @@ class PGCTCLossFn(torch.autograd.Function):
     term after the entropy term in the pass that writes d(logits) (their ``_kl`` entries).  ``PGCTCLossFn.last_kl``: (B,) mean frame KL
     per utterance of the last call, detached, on the device (None after a call with weight 0; not clamped at 0, it can read -1e-7
     where the policies agree); ``metrics.frame_kl`` is the same kernel for monitoring.
+    ``unit_spelling`` (opt-in; None, the default, is every objective above launch for launch): for a model of subword units, whose
+    units may hold spaces, every reward above is counted on the spelled TEXT -- targets (once) and collapsed paths go through
+    ``pgasr_unit_spell`` on the side stream between collapse and the distance, and R = -ED(chars) / max(C(y),1) for reward_unit="char",
+    -WED / W(y) for "word" with words split at the spelling's " ".  utt_scale stays on the unit counts, the unit rows still feed the
+    hypothesis lattices of score_function="sequence".  Not with per_step.  ``PGCTCLossFn.last_spell_truncated``: how many rows were
+    cut at the 4094-character row limit, a 0-d int32 on the device that nothing synchronises on (None after a call without).
     Returns (loss, stats) where stats = (nll (B), R_s (B), R_g (B)) detached; with K > 1, (nll (B), R_s (K,B), R_b (B)) where
     R_b is the baseline averaged over k (R_g for "hypothesis")."""
 
@@ -120,16 +126,18 @@ class PGCTCLossFn(torch.autograd.Function):
     last_sequence_scored = None    # (K,B) bool: the samples of the last score_function="sequence" call that were sequence-scored
     last_entropy = None            # (B,) fp32: mean frame entropy per utterance of the last entropy_weight > 0 call
     last_kl = None                 # (B,) fp32: mean frame KL(p || reference) per utterance of the last kl_weight > 0 call
+    last_spell_truncated = None    # 0-d int32: rows of the last unit_spelling call whose spelling was cut at the row limit
     @staticmethod
     def forward(ctx, logits, in_len, targets, tg_len, log_probs, sample_ids, opt, ref_log_probs=None):
         """opt: the ``PGOptions`` of the call, checked by ``pg_ctc_loss``; ref_log_probs: read only when opt.kl_weight > 0."""
         T, B, V = logits.shape
-        PGCTCLossFn.last_sequence_scored = PGCTCLossFn.last_entropy = PGCTCLossFn.last_kl = None
+        PGCTCLossFn.last_sequence_scored = PGCTCLossFn.last_entropy = PGCTCLossFn.last_kl = PGCTCLossFn.last_spell_truncated = None
         K, beam, blank = opt.num_samples, opt.beam, opt.blank
         beta, gamma = opt.entropy_weight, opt.kl_weight
         ent_mean = ent_scale = kl_mean = kl_scale = None
         loo = opt.baseline == "leave_one_out"
         wd = opt.word_delimiter if opt.reward_unit == "word" else None
+        sp = opt.unit_spelling
         Lh = hipops.hyp_len_cap(T, opt.max_hyp_len) if opt.score_function == "sequence" else None     # the hypothesis-length cap
         # Kernel family: the single-path kernels (per_step's (T,B) coefficients included) for the one configuration they were
         # written for, the multi-sample kernels -- K = 1 included -- for every other, their _seq pair when Lh is set.
@@ -195,7 +203,11 @@ class PGCTCLossFn(torch.autograd.Function):
                 hyp_nll, hyp_lattice = hipops.ctc_hyp_lattice(lp, tokens[P - K:], hyp_len, in_len, Lh, blank=blank)
                 PGCTCLossFn.last_sequence_scored = scored = hyp_len <= Lh
             n_words = prefix = None
-            if wd is not None:
+            if sp is not None:
+                # reward over the spelled text: R = -ED / C(y) or -WED / W(y); the CTC term's utt_scale stays on the unit counts
+                dist, n_words, PGCTCLossFn.last_spell_truncated = _spelled_distances(targets, tg_len, tokens, tok_len, P, sp,
+                                                                                     opt.reward_unit)
+            elif wd is not None:
                 # word-level reward: R = -WED / W(y), the CTC term's utt_scale stays on the character counts
                 dist, n_words = _word_distances(targets, tg_len, tokens, tok_len, P, wd)
             else:
@@ -203,7 +215,7 @@ class PGCTCLossFn(torch.autograd.Function):
                                             want_prefix=opt.per_step)
                 if opt.per_step:
                     dist, prefix = dist
-            if single and wd is None:
+            if single and wd is None and sp is None:
                 R_b, R_s, coef, utt_scale = hipops.pg_rewards(dist, tg_len, opt.lam, inv_gb)
             else:
                 R_b, R_s, coef, utt_scale = hipops.pg_rewards_multi(dist, tg_len, K, opt.lam, inv_gb, baseline=opt.baseline,
@@ -215,7 +227,8 @@ class PGCTCLossFn(torch.autograd.Function):
         nll, lattice = hipops.ctc_lattice(lp, targets, in_len, tg_len, blank=blank)
         main.wait_stream(side)
         for t_ in ((samples, R_b, R_s, coef, utt_scale) + ((tok_len, hyp_nll, scored) if Lh is not None else ())
-                   + ((ent_mean, ent_scale) if beta > 0 else ()) + ((kl_mean, kl_scale, ref_log_probs) if gamma > 0 else ())):
+                   + ((ent_mean, ent_scale) if beta > 0 else ()) + ((kl_mean, kl_scale, ref_log_probs) if gamma > 0 else ())
+                   + ((PGCTCLossFn.last_spell_truncated,) if sp is not None else ())):
             streams.hold(t_, main)
         ent = {"ent_scale": ent_scale} if beta > 0 else {}        # weight 0: the calls as they were
         if gamma > 0:
@@ -263,6 +276,21 @@ def _word_distances(targets, tg_len, tokens, tok_len, P, delimiter):
     return dist, ref_words[:B]
 
 
+def _spelled_distances(targets, tg_len, tokens, tok_len, P, spelling, unit):
+    """Distances of the P x B (target, collapsed path) pairs over their spelled text -- characters, or words split at the spelling's
+    " " --, the targets' spelled lengths or word counts (B,), and the number of rows cut at the row limit (0-d), all int32.  The
+    targets are spelled once, not P times."""
+    B, T = tokens.shape[1], tokens.shape[2]
+    tc, tl, tf = hipops.unit_spell(targets, tg_len, spelling, want_full=True)
+    hc, hl, hf = hipops.unit_spell(tokens, tok_len, spelling, want_full=True)
+    truncated = ((tf > tl).sum() + (hf > hl).sum()).to(torch.int32)
+    ref, ref_len, hyp, hyp_len = tc.repeat(P, 1), tl.repeat(P), hc.view(P * B, hc.shape[2]), hl.view(P * B)
+    if unit == "word":
+        dist, ref_words, _ = hipops.word_edit_distance(ref, ref_len, hyp, hyp_len, spelling.word_delimiter("reward_unit='word'"))
+        return dist, ref_words[:B], truncated
+    return hipops.edit_distance(ref, ref_len, hyp, hyp_len), tl, truncated
+
+
 @dataclasses.dataclass(frozen=True)
 class PGOptions:
     """Everything of a ``pg_ctc_loss`` call that is not a tensor: ONE input of ``PGCTCLossFn`` beside the tensors."""
@@ -282,6 +310,7 @@ class PGOptions:
     max_hyp_len: object = None
     entropy_weight: float = 0.0
     kl_weight: float = 0.0
+    unit_spelling: object = None
 
 
 def check_options(opt, vocab=None, frames=None, symbols=None, sample_ids=None, wide_check=True, wide_objectives=False,
@@ -300,8 +329,11 @@ def check_options(opt, vocab=None, frames=None, symbols=None, sample_ids=None, w
     if opt.per_step and opt.beam > 0:
         raise ValueError("per-step rewards need the frame-aligned greedy baseline (beam = 0)")
     _check_samples(opt.num_samples, opt.baseline, opt.per_step)
-    _check_unit(opt.reward_unit, opt.word_delimiter, opt.per_step, blank=opt.blank, vocab=vocab)
-    if opt.reward_unit == "word" and frames is not None and max(frames, symbols or 0) > hipops.WORD_MAX_STRIDE:
+    if opt.unit_spelling is not None:
+        _check_spelling(opt.unit_spelling, opt.reward_unit, opt.word_delimiter, opt.per_step, vocab=vocab)
+    else:
+        _check_unit(opt.reward_unit, opt.word_delimiter, opt.per_step, blank=opt.blank, vocab=vocab)
+    if opt.unit_spelling is None and opt.reward_unit == "word" and frames is not None and max(frames, symbols or 0) > hipops.WORD_MAX_STRIDE:
         raise ValueError(f"the word-level reward takes at most {hipops.WORD_MAX_STRIDE} frames and target symbols per utterance "
                          f"(pgasr_word_ids); got T = {frames}")
     if wide_check and vocab is not None and vocab > hipops.MAX_VOCAB_NARROW:
@@ -332,7 +364,7 @@ def _check_wide(opt, vocab, wide_objectives=False, wide_sequence=False):
                             ("score_function", opt.score_function, opt.score_function == "path"),
                             ("entropy_weight", opt.entropy_weight, entropy == 0.0),
                             ("kl_weight", opt.kl_weight, kl == 0.0),
-                            ("reward_unit", opt.reward_unit, opt.reward_unit == "char"),
+                            ("reward_unit", opt.reward_unit, opt.reward_unit == "char" or opt.unit_spelling is not None),
                             ("per_step", opt.per_step, not opt.per_step)):
         if ok or (wide_objectives and name in WIDE_OBJECTIVES) or (wide_sequence and name == "score_function"):
             continue
@@ -409,6 +441,25 @@ def _check_unit(reward_unit, word_delimiter, per_step=False, blank=None, vocab=N
         raise ValueError("per-step rewards are character-level: reward_mode='per_step' does not take reward_unit='word'")
 
 
+def _check_spelling(unit_spelling, reward_unit, word_delimiter, per_step=False, vocab=None):
+    """A reward over the spelled text of subword units (``units.UnitSpelling``): "char" counts its characters, "word" its words."""
+    if reward_unit not in REWARD_UNITS:
+        raise ValueError(f"reward_unit must be one of {REWARD_UNITS} (got {reward_unit!r})")
+    if not all(hasattr(unit_spelling, a) for a in ("offsets", "chars", "max_unit_chars", "delimiter", "to")):
+        raise ValueError(f"unit_spelling must be a units.UnitSpelling (got {type(unit_spelling).__name__})")
+    if word_delimiter is not None:
+        raise ValueError("unit_spelling brings its own word delimiter, the id of ' ' in the spelled text: give no word_delimiter")
+    if per_step:
+        raise ValueError("per-step rewards are counted on the frame-aligned units: per_step does not take unit_spelling")
+    if vocab is not None and unit_spelling.vocab != vocab:
+        raise ValueError(f"unit_spelling spells {unit_spelling.vocab} symbols (units and blank), the output layer has {vocab}")
+    if unit_spelling.max_unit_chars > hipops.SPELL_MAX_UNIT_CHARS:
+        raise ValueError(f"unit_spelling has a unit of {unit_spelling.max_unit_chars} characters: pgasr_unit_spell takes at most "
+                         f"{hipops.SPELL_MAX_UNIT_CHARS}")
+    if reward_unit == "word":
+        unit_spelling.word_delimiter("reward_unit='word'")
+
+
 def _check_score(score_function, max_hyp_len, per_step=False):
     if score_function not in hipops.SCORE_FUNCTIONS:
         raise ValueError(f"score_function must be one of {hipops.SCORE_FUNCTIONS} (got {score_function!r})")
@@ -439,7 +490,7 @@ def _check_samples(num_samples, baseline, per_step=False):
 def pg_ctc_loss(logits, in_len, targets, tg_len, lam=1.0, seed=0, offset=0, global_batch=None, blank=0, beam=0, sample_base=-1,
                 per_step=False, log_probs=None, num_samples=1, baseline="hypothesis", reward_unit="char", word_delimiter=None,
                 sample_ids=None, score_function="path", max_hyp_len=None, entropy_weight=0.0, kl_weight=0.0, ref_log_probs=None,
-                wide_objectives=False, wide_sequence=False):
+                wide_objectives=False, wide_sequence=False, unit_spelling=None):
     """beam > 0: the baseline reward comes from the prefix-beam-search hypothesis of that width (see PGCTCLossFn).
     num_samples / baseline: multi-sample REINFORCE (see PGCTCLossFn); with num_samples > 1 the third returned tensor is R_s (K,B).
     reward_unit: "char" (default) or "word" -- the word-level reward R = -WED / W(y) with words split at the token
@@ -465,6 +516,12 @@ def pg_ctc_loss(logits, in_len, targets, tg_len, lam=1.0, seed=0, offset=0, glob
     A13-WIDE: K = 1 against the greedy hypothesis, or together with whatever wide_objectives=True admits.  Set max_hyp_len for unit
     models: the hypothesis lattices take 2 * K*B*T * roundup64(2*Lh+1) * 4 bytes (2.1 GB at K = 4, B = 32, T = 1000 with the
     default cap).  beam, reward_unit="word" and per_step stay refused.  False (default) and at most 64 symbols: every call as it was.
+    unit_spelling: None (default: every call as it was) or the ``units.UnitSpelling`` of a subword alphabet -- the rewards are then
+    counted on the spelled TEXT of targets and hypotheses (``pgasr_unit_spell`` on the side stream, between collapse and the distance):
+    reward_unit="char" is R = -ED(chars) / max(C(y),1), "word" is R = -WED / W(y) with words split at the spelling's " " (no
+    word_delimiter); utt_scale stays on the unit counts.  With every option the alphabet's size admits except per_step; above 64
+    symbols it is what admits reward_unit="word".  Spelled rows are cut at 4094 characters; ``PGCTCLossFn.last_spell_truncated`` counts
+    the rows cut (0-d int32 on the device, None after a call without a spelling).
     log_probs: log_softmax(logits) if the caller already has it (the head kernel's by-product, ``logits.log_probs`` of
     Seq2Seq.logits -- picked up from that attribute when not given)."""
     T, B, V = logits.shape
@@ -472,7 +529,7 @@ def pg_ctc_loss(logits, in_len, targets, tg_len, lam=1.0, seed=0, offset=0, glob
                                   blank=int(blank), beam=int(beam), sample_base=int(sample_base), per_step=bool(per_step),
                                   num_samples=num_samples, baseline=baseline, reward_unit=reward_unit, word_delimiter=word_delimiter,
                                   score_function=score_function, max_hyp_len=max_hyp_len, entropy_weight=entropy_weight,
-                                  kl_weight=kl_weight),
+                                  kl_weight=kl_weight, unit_spelling=unit_spelling),
                         vocab=V, frames=T, symbols=targets.shape[1] if targets.dim() == 2 else 0, sample_ids=sample_ids,
                         wide_objectives=wide_objectives, wide_sequence=wide_sequence)
     if log_probs is None:

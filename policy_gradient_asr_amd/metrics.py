@@ -75,6 +75,19 @@ def error_counts(targets, tg_len, tokens, tok_len, delimiter):
     return cc, wc
 
 
+def unit_error_counts(targets, tg_len, tokens, tok_len, spelling):
+    """``edit_counts`` for rows of SUBWORD UNITS, counted on their spelled text: targets (B,L) / tokens (B,T) int32 unit rows on the GPU
+    with their lengths, ``spelling`` the alphabet's ``units.UnitSpelling`` (with a " ").  Both sides go through ``hipops.unit_spell``;
+    returns (character distance, character length, word distance, word count), each (B,) int32 on the device -- CER = cd / cl and
+    WER = wd / wc as ``evaluate`` gives them on the decoded strings.  No host round trip."""
+    delim = spelling.word_delimiter("unit_error_counts")
+    rc, rl = hipops.unit_spell(targets, tg_len, spelling)
+    hc, hl = hipops.unit_spell(tokens, tok_len, spelling)
+    cd = hipops.edit_distance(rc, rl, hc, hl)
+    wd, wc, _ = hipops.word_edit_distance(rc, rl, hc, hl, delim)
+    return cd, rl, wd, wc
+
+
 def _pad_rows(seqs, device):
     n = len(seqs)
     width = max(max((len(s) for s in seqs), default=0), 1)
@@ -254,21 +267,40 @@ class ErrorReport:
                 fo.write("{}\t{}\t{}\t{}\n".format(kind, r, h, c))
 
 
-def nbest_oracle(targets, tg_len, nb):
+def nbest_oracle(targets, tg_len, nb, spelling=None, unit="char"):
     """The best the list could have done: targets (B,L) / tg_len (B) int32 on the GPU, ``nb`` a ``hipops.CTCNBest``.
     Returns (min character edit distance over the utterance's count hypotheses (B) int32, the first rank that reaches it (B) int32),
     on the device without a host round trip: one ``hipops.edit_distance`` launch over the N * B (target, hypothesis) pairs.
-    Oracle CER = distance / tg_len; a rank > 0 says the search had a better hypothesis than the one it ranked first."""
+    Oracle CER = distance / tg_len; a rank > 0 says the search had a better hypothesis than the one it ranked first.
+    spelling: None (default: the distance over the rows' own symbols, the unit error rate of a subword list) or the alphabet's
+    ``units.UnitSpelling``: targets and list are spelled first and the distance is over the characters of the text (unit="char") or
+    its words (unit="word"); a third value is then returned, the references' spelled lengths or word counts (B) int32, the
+    denominator of the oracle CER / WER."""
     N, B, T = nb.tokens.shape
     L = targets.shape[1]
-    ref = targets.unsqueeze(0).expand(N, B, L).reshape(N * B, L).contiguous()
-    ref_len = tg_len.unsqueeze(0).expand(N, B).reshape(N * B).contiguous()
-    dist = hipops.edit_distance(ref, ref_len, nb.tokens.reshape(N * B, T), nb.lengths.reshape(N * B)).view(N, B)
+    ref_count = None
+    if spelling is not None:
+        if unit not in ("char", "word"):
+            raise ValueError(f"unit must be 'char' or 'word' (got {unit!r})")
+        delim = spelling.word_delimiter() if unit == "word" else None
+        tc, tl = hipops.unit_spell(targets, tg_len, spelling)
+        hc, hl = hipops.unit_spell(nb.tokens, nb.lengths, spelling)
+        ref, ref_len = tc.repeat(N, 1), tl.repeat(N)
+        hyp, hyp_len = hc.view(N * B, hc.shape[2]), hl.view(N * B)
+        if unit == "word":
+            dist, words, _ = hipops.word_edit_distance(ref, ref_len, hyp, hyp_len, delim)
+            dist, ref_count = dist.view(N, B), words[:B]
+        else:
+            dist, ref_count = hipops.edit_distance(ref, ref_len, hyp, hyp_len).view(N, B), tl
+    else:
+        ref = targets.unsqueeze(0).expand(N, B, L).reshape(N * B, L).contiguous()
+        ref_len = tg_len.unsqueeze(0).expand(N, B).reshape(N * B).contiguous()
+        dist = hipops.edit_distance(ref, ref_len, nb.tokens.reshape(N * B, T), nb.lengths.reshape(N * B)).view(N, B)
     rows = torch.arange(N, dtype=torch.int32, device=dist.device).unsqueeze(1)
     dist = torch.where(rows < nb.count.unsqueeze(0), dist, torch.full_like(dist, torch.iinfo(torch.int32).max))
     best = dist.min(0).values
     rank = torch.where(dist == best.unsqueeze(0), rows.expand(N, B), torch.full_like(dist, N)).min(0).values
-    return best, rank
+    return (best, rank) if spelling is None else (best, rank, ref_count)
 
 
 def frame_entropy(log_probs, in_len):

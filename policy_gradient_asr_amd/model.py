@@ -244,7 +244,7 @@ def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset
           mwer_beam=16, init_from=None, kl_weight=0.0, kl_reference_path=None, mwer_lm_path=None, mwer_lm_alpha=0.0,
           mwer_lm_beta=0.0, target_rate=None, speed_perturb=None, noise_dir=None, rir_dir=None, snr_db=(5.0, 20.0), noise_prob=1.0,
           rir_prob=0.5, units_path=None, wide_alphabet=None, wide_objectives=None, wide_sequence=None,
-          mwer_unit_lm_path=None):
+          mwer_unit_lm_path=None, spelled_reward=False):
     """Epoch loop of model.py:186-274 on the MI355X path: per-epoch train loss -> train_loss.npy,
     validation CTC loss -> val_losses.npy, model_best.pth / model_last.pth (state_dicts, reference
     names), plus checkpoint_last.pth (model + Adam moments + epoch) from which ``resume`` restarts
@@ -313,7 +313,12 @@ def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset
     score_function="sequence" (PolicyGradientTrainer(wide_sequence=True)) run on the wide kernels too.  Set max_hyp_len for unit
     models: the hypothesis lattices take 2 * K*B*T * roundup64(2*Lh+1) * 4 bytes.  Needs wide_alphabet; kept in the checkpoint beside it.
     mwer_unit_lm_path: None or a ``lm.UnitNgramLM.save`` file: with objective="mwer" and wide_sequence the lists come from the wide
-    search fused with that unit LM at weights mwer_lm_alpha / mwer_lm_beta."""
+    search fused with that unit LM at weights mwer_lm_alpha / mwer_lm_beta.
+    spelled_reward: False (default: the line under units_path -- the reward is the edit distance over units) or True, with
+    units_path: the rewards (the risk of objective="mwer") are counted on the SPELLED text of targets and hypotheses -- reward_unit=
+    "char" its characters, "word" its words, the metrics that are reported -- through a ``units.UnitSpelling`` built from the units
+    file and <corpus_path>/alphabet.txt (PolicyGradientTrainer(unit_spelling=), mwer.MWERTrainer(unit_spelling=)); above 64 symbols it
+    is what admits reward_unit="word".  Kept in the checkpoint beside wide_alphabet."""
     import os
     import numpy as np
     import torch.utils.data as tud
@@ -368,7 +373,15 @@ def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset
     if wide_objectives and not wide_alphabet:
         raise ValueError("wide_objectives=True opens objectives for alphabets of more than 64 symbols: it needs wide_alphabet")
     word_delimiter = None
-    if reward_unit == "word":
+    spelling = {}
+    if spelled_reward:
+        if units is None:
+            raise ValueError("spelled_reward=True spells subword units into characters: it needs units_path")
+        from .units import UnitSpelling
+        spelling = {"unit_spelling": UnitSpelling.load(units_path, os.path.join(corpus_path, "alphabet.txt"))}
+        if reward_unit == "word":
+            spelling["unit_spelling"].word_delimiter("reward_unit='word'")
+    elif reward_unit == "word":
         if " " not in char2ind:
             raise ValueError(f"reward_unit='word' splits words at the alphabet's ' ' symbol, and {alphabet_path} has none")
         word_delimiter = char2ind[" "]
@@ -403,7 +416,7 @@ def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset
         trainer = MWERTrainer(model, lr=lr, lam=lam, seed=seed, precision=precision, max_grad_norm=max_grad_norm,
                               beam_size=mwer_beam, nbest=mwer_nbest, risk_unit=reward_unit, word_delimiter=word_delimiter,
                               max_hyp_len=max_hyp_len, num_samples=num_samples, reward_baseline=reward_baseline,
-                              score_function=score_function, entropy_weight=entropy_weight, **mwer_lm)
+                              score_function=score_function, entropy_weight=entropy_weight, **mwer_lm, **spelling)
     else:
         kl = {}
         if kl_weight > 0:
@@ -416,7 +429,7 @@ def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset
                                         max_grad_norm=max_grad_norm, score_function=score_function, max_hyp_len=max_hyp_len,
                                         entropy_weight=entropy_weight, **kl, **({"wide_alphabet": True} if wide_alphabet else {}),
                                         **({"wide_objectives": True} if wide_objectives else {}),
-                                        **({"wide_sequence": True} if wide_sequence else {}))
+                                        **({"wide_sequence": True} if wide_sequence else {}), **spelling)
     losses, val_losses, best, start_epoch = [], [], 9999999.0, 1
     ckpt = os.path.join(model_path, "checkpoint_last.pth")
     resuming = resume and os.path.exists(ckpt)
@@ -440,7 +453,7 @@ def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset
                         ("max_hyp_len", max_hyp_len), ("entropy_weight", entropy_weight), ("kl_weight", kl_weight),
                         ("kl_reference_path", kl_reference_path), ("target_rate", target_rate),
                         ("units_path", units_path), ("wide_alphabet", wide_alphabet), ("wide_objectives", wide_objectives),
-                        ("wide_sequence", wide_sequence),
+                        ("wide_sequence", wide_sequence), ("spelled_reward", bool(spelled_reward)),
                         ("speed_perturb", None if speed_perturb is None else speed_perturb.state()),
                         ("wave_augment", None if wave_augment is None else wave_augment.state())):
             if k in st and st[k] != want:
@@ -530,6 +543,7 @@ def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset
                     "score_function": score_function, "max_hyp_len": max_hyp_len, "entropy_weight": trainer.entropy_weight,
                     "kl_weight": kl_weight, "kl_reference_path": kl_reference_path, "target_rate": target_rate,
                     "units_path": units_path, "wide_alphabet": wide_alphabet, "wide_objectives": wide_objectives, "wide_sequence": wide_sequence,
+                    "spelled_reward": bool(spelled_reward),
                     "speed_perturb": None if speed_perturb is None else speed_perturb.state(),
                     "wave_augment": None if wave_augment is None else wave_augment.state()}, ckpt)
     return losses, val_losses
@@ -540,7 +554,7 @@ def predict(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=N
             nbest=1, rescore_lm_path=None, rescore_alpha=0.0, rescore_beta=0.0, lm_fast=False, target_rate=None,
             mbr=False, mbr_unit="char", mbr_scale=1.0, rescore_word_lm_path=None, rescore_word_alpha=0.0, rescore_word_beta=0.0,
             error_report=False, units_path=None, wide_beam=False, wide_second_pass=False, unit_lm_path=None, unit_lm_alpha=0.0,
-            unit_lm_beta=0.0, rescore_unit_lm_path=None, rescore_unit_alpha=0.0, rescore_unit_beta=0.0):
+            unit_lm_beta=0.0, rescore_unit_lm_path=None, rescore_unit_alpha=0.0, rescore_unit_beta=0.0, spelled=False):
     """model.py:277-339: load model_best.pth, forward, beam=5 prefix search (device side, batched),
     collapse_fn, CER/WER, predicted.txt.  Frames are cut by the FEATURE mask (the reference cuts the
     time axis by the target mask, model.py:322 -- a listed defect).  Returns (CER, WER).
@@ -602,7 +616,13 @@ def predict(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=N
     rescore_unit_lm_path: None (default: everything above, nothing else) or such a file, with nbest >= 2 (and wide_second_pass=True
     for an alphabet of more than 64 symbols): the second pass also scores every hypothesis under the unit LM, total -=
     rescore_unit_alpha * ln p_unit + rescore_unit_beta * length (``CTCDecoder.rescore(unit_lm=)``); with mbr=True the posterior comes
-    from these totals.  ``nbest.tsv`` then has one more column at its end: unit_logp."""
+    from these totals.  ``nbest.tsv`` then has one more column at its end: unit_logp.
+    spelled: False (default: everything above, nothing else -- every refusal above stands) or True, with units_path: the lists of a
+    subword model are counted on their SPELLED text (``units.UnitSpelling`` from the units file and ``alphabet_path``, the corpus'
+    alphabet.txt, where that file exists; else the characters of the units).  error_report=True is then allowed with greedy decoding
+    and with the wide search (``ErrorReport`` over the spelling's characters), mbr_unit="word" with wide_second_pass=True (and
+    mbr_unit="char" counts characters, not units: ``CTCDecoder.mbr_from_list(unit_spelling=)``), and the oracle of a wide list is
+    printed as the CER over spelled text (``metrics.nbest_oracle(spelling=)``)."""
     import os
     import functools
     import torch.utils.data as tud
@@ -633,6 +653,7 @@ def predict(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=N
         raise ValueError("minimum-Bayes-risk decoding needs a list: give nbest >= 2 with mbr=True")
     if mbr and mbr_unit not in ("char", "word"):
         raise ValueError(f"mbr_unit must be 'char' or 'word' (got {mbr_unit!r})")
+    char_alphabet_path = alphabet_path
     if units_path is not None:
         alphabet_path = units_path
     alphabet, char2ind = _read_alphabet(alphabet_path)
@@ -641,24 +662,35 @@ def predict(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=N
     if units_path is not None:
         from .units import SubwordUnits
         unit_args = {"units": SubwordUnits.load(units_path)}
+    spelling = None
+    if spelled:
+        if units_path is None:
+            raise ValueError("spelled=True spells subword units into characters: it needs units_path")
+        from .units import UnitSpelling
+        have = char_alphabet_path is not None and char_alphabet_path != units_path and os.path.isfile(str(char_alphabet_path))
+        spelling = UnitSpelling.load(units_path, char_alphabet_path if have else None)
+        if (mbr and mbr_unit == "word") or error_report:
+            spelling.word_delimiter("mbr_unit='word'" if mbr and mbr_unit == "word" else "error_report")
     wide = len(alphabet) > hipops.MAX_VOCAB_NARROW and not greedy and bool(wide_beam)
     second = wide and bool(wide_second_pass)
     if second:
         if nbest < 2:
             raise ValueError("wide_second_pass re-ranks a list: give nbest >= 2 with it")
         for name, given in (("lm_path", lm_path is not None), ("rescore_lm_path", rescore_lm_path is not None),
-                            ("rescore_word_lm_path", rescore_word_lm_path is not None), ("error_report", bool(error_report))):
+                            ("rescore_word_lm_path", rescore_word_lm_path is not None),
+                            ("error_report", bool(error_report) and spelling is None)):
             if given:
                 raise ValueError(f"{name}: not with the wide beam search ({len(alphabet)} > {hipops.MAX_VOCAB_NARROW} symbols): its "
                                  f"second pass is the exact CTC likelihood and minimum-Bayes-risk decoding over units, without "
                                  f"language models or an error report")
-        if mbr and mbr_unit == "word":
+        if mbr and mbr_unit == "word" and spelling is None:
             raise ValueError(f"mbr_unit='word': not over {len(alphabet)} > {hipops.MAX_VOCAB_NARROW} symbols -- a subword unit may span "
                              f"a space; take mbr_unit='char', which counts units")
     elif wide:
         for name, given in (("lm_path", lm_path is not None), ("rescore_lm_path", rescore_lm_path is not None),
                             ("rescore_word_lm_path", rescore_word_lm_path is not None), ("mbr", bool(mbr)),
-                            ("error_report", bool(error_report)), ("rescore_unit_lm_path", rescore_unit_lm_path is not None)):
+                            ("error_report", bool(error_report) and spelling is None),
+                            ("rescore_unit_lm_path", rescore_unit_lm_path is not None)):
             if given:
                 raise ValueError(f"{name}: not with the wide beam search ({len(alphabet)} > {hipops.MAX_VOCAB_NARROW} symbols), which "
                                  f"has no LM fusion, no second pass over its lists and no error report yet")
@@ -693,7 +725,7 @@ def predict(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=N
     else:
         decoder = CTCDecoder(alphabet, lm=lm, lm_alpha=lm_alpha, lm_beta=lm_beta, fast_lm=bool(lm_fast), wide_search=wide)
     list_text = to_text if wide else collapse_fn      # a wide list holds units: their concatenation is the text
-    if mbr and mbr_unit == "word" and " " not in char2ind:
+    if mbr and mbr_unit == "word" and spelling is None and " " not in char2ind:
         raise ValueError("mbr_unit='word' needs an alphabet with the ' ' symbol")
     rescore_lm = CharNgramLM.load(rescore_lm_path) if rescore_lm_path is not None else None
     if rescore_word_lm_path is not None and " " not in char2ind:
@@ -706,7 +738,8 @@ def predict(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=N
     report = None
     if error_report:
         from .metrics import ErrorReport
-        report = ErrorReport([a.replace("\n", "") for a in alphabet], " ", device=dev)
+        report = (ErrorReport([a.replace("\n", "") for a in alphabet], " ", device=dev) if spelling is None else
+                  ErrorReport(spelling.char_alphabet, " ", device=dev))
     targets, predicted, tot_cer, tot_wer, n = [], [], 0.0, 0.0, 0
     nbest_lines, tot_oracle = [], 0.0
     mbr_lines, map_cer, map_wer = [], 0.0, 0.0
@@ -730,8 +763,12 @@ def predict(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=N
                         units_lp = rs.unit_logp.cpu()
                 if mbr:
                     score = rs.total if total is not None else decoder.rescore(lp, in_len, nb, lm=None).total
-                    md = decoder.mbr_from_list(nb, score, vocab=lp.shape[2], risk_unit=mbr_unit, posterior_scale=mbr_scale,
-                                               word_delimiter=char2ind[" "] if mbr_unit == "word" else None)
+                    if spelling is not None:
+                        md = decoder.mbr_from_list(nb, score, vocab=lp.shape[2], risk_unit=mbr_unit, posterior_scale=mbr_scale,
+                                                   unit_spelling=spelling)
+                    else:
+                        md = decoder.mbr_from_list(nb, score, vocab=lp.shape[2], risk_unit=mbr_unit, posterior_scale=mbr_scale,
+                                                   word_delimiter=char2ind[" "] if mbr_unit == "word" else None)
                     map_tok, map_tl, tok, tl = tok.cpu(), tl.cpu(), md.tokens, md.lengths
                     mbest, mrisk = md.best.cpu(), md.risk.cpu()
                     for i in range(mbest.shape[0]):
@@ -756,8 +793,13 @@ def predict(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=N
                                                                             text, extra))
                 if wide:      # over units: the lists against the encoded references, on the device
                     from .metrics import nbest_oracle
-                    od, _ = nbest_oracle(t.to(torch.int32).contiguous(), tmask.sum(1).to(torch.int32).contiguous(), nb)
-                    tot_oracle += sum(int(d) / max(int(tlen_h[i]), 1) for i, d in enumerate(od.cpu().tolist()))
+                    if spelling is not None:      # .. or, spelled, over the characters of the text
+                        od, _, oc = nbest_oracle(t.to(torch.int32).contiguous(), tmask.sum(1).to(torch.int32).contiguous(), nb,
+                                                 spelling=spelling)
+                        tot_oracle += sum(int(d) / max(int(c), 1) for d, c in zip(od.cpu().tolist(), oc.cpu().tolist()))
+                    else:
+                        od, _ = nbest_oracle(t.to(torch.int32).contiguous(), tmask.sum(1).to(torch.int32).contiguous(), nb)
+                        tot_oracle += sum(int(d) / max(int(tlen_h[i]), 1) for i, d in enumerate(od.cpu().tolist()))
                 else:
                     best = {}
                     for i, d in zip(owner, edit_dist_batch(refs, hyps, device=dev)):
@@ -788,9 +830,9 @@ def predict(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=N
             with open(os.path.join(model_path, "mbr.tsv"), "w") as fo:
                 fo.writelines(mbr_lines)
             print("MBR ({}) CER: {:>4f} WER: {:>4f} MAP CER: {:>4f} WER: {:>4f} Oracle {} ({}-best): {:>4f}".format(
-                "unit" if wide else mbr_unit, cer, wer, map_cer / max(n, 1), map_wer / max(n, 1),
-                "unit error rate" if wide else "CER", nbest, tot_oracle / max(n, 1)))
-        elif wide:
+                "unit" if wide and spelling is None else mbr_unit, cer, wer, map_cer / max(n, 1), map_wer / max(n, 1),
+                "unit error rate" if wide and spelling is None else "CER", nbest, tot_oracle / max(n, 1)))
+        elif wide and spelling is None:
             print("CER: {:>4f} WER: {:>4f} Oracle unit error rate ({}-best): {:>4f}".format(cer, wer, nbest, tot_oracle / max(n, 1)))
         else:
             print("CER: {:>4f} WER: {:>4f} Oracle CER ({}-best): {:>4f}".format(cer, wer, nbest, tot_oracle / max(n, 1)))

@@ -14,7 +14,7 @@ import torch
 
 from . import hipops
 from . import streams
-from .loss import PGCTCLossFn, _check_score, _check_unit, _word_distances
+from .loss import PGCTCLossFn, _check_score, _check_spelling, _check_unit, _spelled_distances, _word_distances
 from .train_step import PolicyGradientTrainer
 
 MAX_NBEST = hipops.MAX_SAMPLES       # PGASR_MAX_SAMPLES: entries per utterance the weights and gradient kernels take
@@ -44,6 +44,13 @@ class MWERWideOptions(MWEROptions):
     unit_lm: object = None         # a lm.UnitNgramLM: the list comes from the wide search fused with it (lm_alpha / lm_beta its weights)
 
 
+@dataclasses.dataclass(frozen=True)
+class MWERSpelledOptions(MWERWideOptions):
+    """The options of a ``unit_spelling=`` call: the risk is counted on the spelled text of the units (``wide`` says whether
+    wide_sequence=True came with it)."""
+    unit_spelling: object = None   # a units.UnitSpelling
+
+
 MAX_BEAM_WIDE = 128                  # pgasr_ctc_beam_search_wide
 
 
@@ -60,8 +67,10 @@ def _wide_list(opt, vocab):
 
 
 def check_mwer_options(opt, vocab=None, frames=None, symbols=None):
-    """Made before any kernel runs.  Returns the options with their integers as ints."""
+    """Made before any kernel runs.  Returns the options with their integers as ints.  With a spelling (``MWERSpelledOptions``) the
+    risk is counted on the spelled text, so risk_unit="word" is admitted above 64 symbols too and takes no word_delimiter."""
     wide, unit_lm = _wide_fields(opt)
+    spelling = getattr(opt, "unit_spelling", None)
     for name in ("beam", "nbest"):
         v = getattr(opt, name)
         if isinstance(v, bool) or int(v) != v:
@@ -96,15 +105,18 @@ def check_mwer_options(opt, vocab=None, frames=None, symbols=None):
                              f"the N-best kernels hold one symbol per lane, at most {hipops.MAX_VOCAB_NARROW}")
         if int(vocab) > hipops.MAX_VOCAB_WIDE:
             raise ValueError(f"alphabet of {int(vocab)} symbols > {hipops.MAX_VOCAB_WIDE}: the wide kernels hold at most 16 symbols per lane")
-        if opt.risk_unit == "word":
+        if opt.risk_unit == "word" and spelling is None:
             raise ValueError(f"risk_unit='word' takes an alphabet of at most {hipops.MAX_VOCAB_NARROW} symbols (got {int(vocab)}): a "
                              f"subword unit may span a space, so a list of units has no word boundaries of its own "
                              f"(hipops.nbest_pair_distance's reason); use risk_unit='char', the unit error rate")
     if _wide_list(opt, vocab) and opt.beam > MAX_BEAM_WIDE:
         raise ValueError(f"beam {opt.beam} > {MAX_BEAM_WIDE}: the wide beam search keeps at most {MAX_BEAM_WIDE} prefixes")
-    _check_unit(opt.risk_unit, opt.word_delimiter, blank=opt.blank, vocab=vocab)
+    if spelling is not None:
+        _check_spelling(spelling, opt.risk_unit, opt.word_delimiter, vocab=vocab)
+    else:
+        _check_unit(opt.risk_unit, opt.word_delimiter, blank=opt.blank, vocab=vocab)
     _check_score("sequence", opt.max_hyp_len)
-    if opt.risk_unit == "word" and frames is not None and max(frames, symbols or 0) > hipops.WORD_MAX_STRIDE:
+    if spelling is None and opt.risk_unit == "word" and frames is not None and max(frames, symbols or 0) > hipops.WORD_MAX_STRIDE:
         raise ValueError(f"the word-level risk takes at most {hipops.WORD_MAX_STRIDE} frames and target symbols per utterance "
                          f"(pgasr_word_ids); got T = {frames}")
     return dataclasses.replace(opt, beam=int(opt.beam), nbest=int(opt.nbest),
@@ -116,8 +128,15 @@ def _lm_fields(lm, lm_alpha, lm_beta):
     return {} if lm is None else {"lm": lm, "lm_alpha": float(lm_alpha), "lm_beta": float(lm_beta)}
 
 
-def _options(wide_sequence, unit_lm, lm, lm_alpha, lm_beta, **fields):
-    """``MWEROptions`` as ever, or with the keyword ``MWERWideOptions`` (the unit LM and its weights among them)."""
+def _options(wide_sequence, unit_lm, lm, lm_alpha, lm_beta, unit_spelling=None, **fields):
+    """``MWEROptions`` as ever, or with the keyword ``MWERWideOptions`` (the unit LM and its weights among them); with a spelling
+    ``MWERSpelledOptions``."""
+    if unit_spelling is not None:
+        if unit_lm is not None and not wide_sequence:
+            raise ValueError("unit_lm= is fused by the wide beam search: it needs wide_sequence=True")
+        weights = {} if unit_lm is None else {"lm_alpha": float(lm_alpha), "lm_beta": float(lm_beta)}
+        return MWERSpelledOptions(**fields, wide=bool(wide_sequence), unit_lm=unit_lm, unit_spelling=unit_spelling,
+                                  **{**weights, **_lm_fields(lm, lm_alpha, lm_beta)})
     if not wide_sequence:
         if unit_lm is not None:
             raise ValueError("unit_lm= is fused by the wide beam search: it needs wide_sequence=True")
@@ -150,12 +169,15 @@ class MWERLossFn(torch.autograd.Function):
     last_nbest = None
     last_posterior = None
     last_risk = None           # r (N,B) fp32 of the last call
+    last_spell_truncated = None    # 0-d int32: rows of the last unit_spelling call whose spelling was cut at the row limit
 
     @staticmethod
     def forward(ctx, logits, in_len, targets, tg_len, log_probs, opt):
         T, B, V = logits.shape
         N, blank = opt.nbest, opt.blank
         wd = opt.word_delimiter if opt.risk_unit == "word" else None
+        sp = getattr(opt, "unit_spelling", None)
+        MWERLossFn.last_spell_truncated = None
         Lh = hipops.hyp_len_cap(T, opt.max_hyp_len)
         inv_gb = 1.0 / float(opt.global_batch)
         lp = log_probs
@@ -178,7 +200,11 @@ class MWERLossFn(torch.autograd.Function):
             # the gradient pass reads was really computed, and meets a coefficient of 0
             lat_len = torch.where(nb.lengths > Lh, torch.zeros_like(nb.lengths), nb.lengths)
             hyp_nll, hyp_lattice = hipops.ctc_hyp_lattice(lp, nb.tokens, lat_len, in_len, Lh, blank=blank)
-            if wd is not None:
+            if sp is not None:
+                # the risk over the spelled text: r = ED(chars) / C(y) or WED / W(y)
+                dist, risk_len, MWERLossFn.last_spell_truncated = _spelled_distances(targets, tg_len, nb.tokens, nb.lengths, N, sp,
+                                                                                    opt.risk_unit)
+            elif wd is not None:
                 dist, risk_len = _word_distances(targets, tg_len, nb.tokens, nb.lengths, N, wd)
             else:
                 dist = hipops.edit_distance(targets.repeat(N, 1), tg_len.repeat(N), nb.tokens.view(N * B, T), nb.lengths.view(N * B))
@@ -189,7 +215,8 @@ class MWERLossFn(torch.autograd.Function):
             p, r, coef, utt_scale, rbar, terms = hipops.mwer_weights(dist, risk_len, tg_len, hyp_nll, nb.lengths, nb.count, nll, Lh,
                                                                      opt.lam, inv_gb)
         main.wait_stream(side)
-        for t_ in (nb.tokens, nb.lengths, nb.score, nb.count, lat_len, hyp_nll, dist, p, r, coef, utt_scale, rbar, terms):
+        for t_ in ((nb.tokens, nb.lengths, nb.score, nb.count, lat_len, hyp_nll, dist, p, r, coef, utt_scale, rbar, terms)
+                   + ((MWERLossFn.last_spell_truncated,) if sp is not None else ())):
             streams.hold(t_, main)
         MWERLossFn.last_nbest, MWERLossFn.last_posterior, MWERLossFn.last_risk = nb, p, r
         grad = hipops.ctc_grad_from_lattices_nbest(lp, in_len, tg_len, lattice, hyp_lattice, utt_scale, coef, lat_len)
@@ -228,7 +255,7 @@ def mwer_ctc_loss(logits, in_len, targets, tg_len, lam=1.0, beam=16, nbest=4, gl
 
 def mwer_ctc_loss_lm(logits, in_len, targets, tg_len, lm=None, lm_alpha=0.0, lm_beta=0.0, lam=1.0, beam=16, nbest=4, global_batch=None,
                      blank=0, risk_unit="char", word_delimiter=None, max_hyp_len=None, log_probs=None, wide_sequence=False,
-                     unit_lm=None):
+                     unit_lm=None, unit_spelling=None):
     """``mwer_ctc_loss`` over the N-best list of the LM-FUSED search: ``lm`` a ``lm.CharNgramLM`` over the same V symbols and blank, its
     weights lm_alpha / lm_beta as ``CTCDecoder`` takes them (``MWERLossFn``; the list comes from the single-wave kernel's LM
     instantiation where its limits allow).  The posterior over the list stays the exact CTC likelihood.  ``lm=None`` is
@@ -237,11 +264,15 @@ def mwer_ctc_loss_lm(logits, in_len, targets, tg_len, lm=None, lm_alpha=0.0, lm_
     wide_sequence: opt-in for an alphabet of 65 .. 1024 symbols (V <= 64 without unit_lm: the call as it was, bit for bit) -- the list
     is ``hipops.ctc_beam_search_wide``'s (beam <= 128, nbest <= 16), risk_unit "char" only; unit_lm: a ``lm.UnitNgramLM`` that search is
     fused with, weighted by lm_alpha / lm_beta -- above 64 symbols ``lm`` (dense, character-level) is refused in its favour.  Set
-    max_hyp_len for unit models: the default cap takes 2.1 GB of lattices at nbest = 4, B = 32, T = 1000."""
+    max_hyp_len for unit models: the default cap takes 2.1 GB of lattices at nbest = 4, B = 32, T = 1000.
+    unit_spelling: None (default: the call as it was) or the ``units.UnitSpelling`` of the alphabet's subword units -- the distances
+    and the risk normaliser come from the spelled text of targets and hypotheses (``pgasr_unit_spell``): risk_unit="char" is
+    r = ED(chars) / max(C(y),1), "word" r = WED / W(y) with words split at the spelling's " " (no word_delimiter), admitted above 64
+    symbols too.  ``MWERLossFn.last_spell_truncated``: the rows cut at the 4094-character row limit (0-d int32 on the device)."""
     if logits.dim() != 3:
         raise ValueError("mwer_ctc_loss: logits (T,B,V)")
     T, B, V = logits.shape
-    opt = check_mwer_options(_options(wide_sequence, unit_lm, lm, lm_alpha, lm_beta, lam=float(lam), beam=beam, nbest=nbest,
+    opt = check_mwer_options(_options(wide_sequence, unit_lm, lm, lm_alpha, lm_beta, unit_spelling, lam=float(lam), beam=beam, nbest=nbest,
                                       global_batch=int(global_batch or B), blank=int(blank), risk_unit=risk_unit,
                                       word_delimiter=word_delimiter, max_hyp_len=max_hyp_len),
                              vocab=V, frames=T, symbols=targets.shape[1] if targets.dim() == 2 else 0)
@@ -266,14 +297,16 @@ class MWERTrainer(PolicyGradientTrainer):
     wide_sequence=True: an alphabet of 65 .. 1024 subword units -- MAX_VOCAB becomes 1024, the lists come from ``ctc_beam_search_wide``
     (beam_size <= 128, nbest <= 16), with ``unit_lm`` (a ``lm.UnitNgramLM``, weights lm_alpha / lm_beta) from that search fused with it;
     risk_unit="char" and no dense ``lm`` above 64 symbols.  Set max_hyp_len for unit models (2.1 GB of lattices at nbest = 4, B = 32,
-    T = 1000 with the default cap).  ``wide_alphabet=True`` without it keeps being refused."""
+    T = 1000 with the default cap).  ``wide_alphabet=True`` without it keeps being refused.
+    unit_spelling: a ``units.UnitSpelling`` -- the risk is counted on the spelled text (characters, or words with risk_unit="word", which
+    this admits above 64 symbols; no word_delimiter); ``last_spell_truncated`` as in the parent."""
 
     _FIXED = {"num_samples": 1, "reward_baseline": "hypothesis", "score_function": "path", "reward_mode": "utterance",
               "reward_decoder": "greedy", "entropy_weight": 0.0}
 
     def __init__(self, model, lr=5e-4, lam=1.0, seed=0, blank=0, world_size=1, process_group=None, rank=0, precision=None,
                  max_grad_norm=None, beam_size=16, nbest=4, risk_unit="char", word_delimiter=None, max_hyp_len=None, lm=None, lm_alpha=0.0,
-                 lm_beta=0.0, wide_sequence=False, unit_lm=None, **sampled):
+                 lm_beta=0.0, wide_sequence=False, unit_lm=None, unit_spelling=None, **sampled):
         wide_sequence = bool(wide_sequence)
         if sampled.pop("wide_alphabet", False) and not wide_sequence:
             raise ValueError("MWERTrainer takes an alphabet of at most 64 symbols: the beam search and the N-best kernels hold one "
@@ -284,7 +317,7 @@ class MWERTrainer(PolicyGradientTrainer):
             if isinstance(v, bool) or v != self._FIXED[k]:
                 raise ValueError(f"MWERTrainer samples nothing: {k}={v!r} has no meaning here (an entropy bonus for MWER is not built)")
         vocab = getattr(getattr(model, "head", None), "out_features", None)
-        opt = check_mwer_options(_options(wide_sequence, unit_lm, lm, lm_alpha, lm_beta, blank=int(blank), beam=beam_size, nbest=nbest,
+        opt = check_mwer_options(_options(wide_sequence, unit_lm, lm, lm_alpha, lm_beta, unit_spelling, blank=int(blank), beam=beam_size, nbest=nbest,
                                           risk_unit=risk_unit, word_delimiter=word_delimiter, max_hyp_len=max_hyp_len), vocab=vocab)
         # wide_sequence=True lifts MAX_VOCAB to 1024 itself: the parent's wide_alphabet, whose default objective is not run here
         super().__init__(model, lr=lr, lam=lam, seed=seed, blank=blank, world_size=world_size, process_group=process_group, rank=rank,
@@ -296,6 +329,7 @@ class MWERTrainer(PolicyGradientTrainer):
         self.mwer_lm, self.mwer_lm_alpha, self.mwer_lm_beta = opt.lm, opt.lm_alpha, opt.lm_beta
         self.mwer_unit_lm = _wide_fields(opt)[1]
         self.mwer_options = opt
+        self.mwer_unit_spelling = unit_spelling
         self.last_posterior = None
 
     def _list_fields(self):
@@ -324,7 +358,9 @@ class MWERTrainer(PolicyGradientTrainer):
         loss, nll, expected, top = mwer_ctc_loss_lm(logits, in_len, tg, tg_len, lam=self.lam, beam=self.beam_size, nbest=self.nbest,
                                                     global_batch=global_batch, blank=self.blank, risk_unit=self.risk_unit,
                                                     word_delimiter=self.risk_delimiter, max_hyp_len=self.mwer_max_hyp_len,
-                                                    **self._list_fields())
+                                                    **self._list_fields(),
+                                                    **({} if self.mwer_unit_spelling is None else {"unit_spelling": self.mwer_unit_spelling}))
+        self.last_spell_truncated = MWERLossFn.last_spell_truncated
         post = MWERLossFn.last_posterior
         R_all = -MWERLossFn.last_risk                            # (N,B): every entry's reward
         self.last_posterior = post[:, :real_b] if padded else post

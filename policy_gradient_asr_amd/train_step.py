@@ -448,7 +448,7 @@ class PolicyGradientTrainer(DataParallelStep):
                  reward_decoder="greedy", beam_size=16, precision=None, reward_mode="utterance", num_samples=1,
                  reward_baseline="hypothesis", reward_unit="char", word_delimiter=None, max_grad_norm=None,
                  score_function="path", max_hyp_len=None, entropy_weight=0.0, kl_weight=0.0, kl_reference=None, wide_alphabet=False,
-                 wide_objectives=False, wide_sequence=False):
+                 wide_objectives=False, wide_sequence=False, unit_spelling=None):
         """wide_alphabet: opt in to alphabets of 65 .. 1024 symbols (subword units).  MAX_VOCAB becomes 1024, and such a model takes
         the default objective alone: reward_decoder="greedy", reward_mode="utterance", num_samples=1, reward_baseline="hypothesis",
         reward_unit="char", score_function="path", entropy_weight=0, kl_weight=0 -- anything else raises here and before every
@@ -496,7 +496,12 @@ class PolicyGradientTrainer(DataParallelStep):
         The trainer puts it in eval() with requires_grad_(False) and never updates it.  Every step its logits are computed on the
         padded batch under no_grad, in the trainer's precision, on the calling stream and BEFORE the policy's forward (the two
         models' sweeps never run beside each other), which costs one eval forward per step.  ``last_kl``: (B,) mean frame KL of the
-        last step's real utterances, on the device (None with weight 0)."""
+        last step's real utterances, on the device (None with weight 0).
+        unit_spelling: None (default: the step as it was) or the ``units.UnitSpelling`` of the model's subword units: the rewards are
+        counted on the spelled TEXT -- reward_unit="char" its characters, "word" its words, split at the spelling's " " (give no
+        word_delimiter) -- with every setting the alphabet's size admits except reward_mode="per_step"; above 64 symbols it is what
+        admits reward_unit="word" (loss.PGCTCLossFn).  ``last_spell_truncated``: how many rows of the last step were cut at the
+        4094-character row limit, a 0-d int32 on the device (None without a spelling); nothing synchronises until it is read."""
         from .loss import check_kl_weight
         kl_weight = check_kl_weight(kl_weight)
         if isinstance(kl_reference, str):
@@ -525,6 +530,7 @@ class PolicyGradientTrainer(DataParallelStep):
         self.blank = blank
         self.num_samples, self.reward_baseline = num_samples, reward_baseline
         self.reward_unit, self.word_delimiter = reward_unit, word_delimiter
+        self.unit_spelling, self.last_spell_truncated = unit_spelling, None
         self.score_function, self.max_hyp_len = score_function, max_hyp_len
         self.entropy_weight = entropy_weight
         self.kl_weight, self.kl_reference = kl_weight, None
@@ -618,7 +624,7 @@ class PolicyGradientTrainer(DataParallelStep):
         opt = PGOptions(blank=self.blank, per_step=self.reward_mode == "per_step", num_samples=self.num_samples,
                         beam=self.beam_size if self.reward_decoder == "beam" else 0, baseline=self.reward_baseline, reward_unit=self.reward_unit, word_delimiter=self.word_delimiter,
                         score_function=self.score_function, max_hyp_len=self.max_hyp_len, entropy_weight=self.entropy_weight,
-                        kl_weight=self.kl_weight)
+                        kl_weight=self.kl_weight, unit_spelling=getattr(self, "unit_spelling", None))
         return check_options(opt, vocab=vocab, frames=frames, symbols=symbols, wide_check=self.wide_alphabet,
                              wide_objectives=getattr(self, "wide_objectives", False),
                              wide_sequence=getattr(self, "wide_sequence", False))
@@ -733,7 +739,9 @@ class PolicyGradientTrainer(DataParallelStep):
                                           score_function=self.score_function, max_hyp_len=self.max_hyp_len,
                                           entropy_weight=self.entropy_weight, **kl,
                                           **({"wide_objectives": True} if self.wide_objectives else {}),
-                                          **({"wide_sequence": True} if self.wide_sequence else {}))
+                                          **({"wide_sequence": True} if self.wide_sequence else {}),
+                                          **({"unit_spelling": self.unit_spelling} if self.unit_spelling is not None else {}))
+        self.last_spell_truncated = PGCTCLossFn.last_spell_truncated      # 0-d int32, None without a spelling
         scored = PGCTCLossFn.last_sequence_scored                # (K,B) bool, None with score_function="path"
         self.last_sequence_scored = scored[:, :real_b] if (padded and scored is not None) else scored
         ent = PGCTCLossFn.last_entropy                           # (B,) mean frame entropy, None with entropy_weight = 0
@@ -747,7 +755,7 @@ class PolicyGradientTrainer(DataParallelStep):
         self.last_stats = (nll[:real_b], R_s[:real_b], R_g[:real_b]) if padded else (nll, R_s, R_g)
         if self._micro is not None and self._micro.count > 1:
             self._micro_stats.append((self.last_stats, self.last_sample_rewards, self.last_sequence_scored, self.last_entropy,
-                                      self.last_kl))
+                                      self.last_kl, self.last_spell_truncated))
         return loss
 
     def _sample_addressing(self, real_b, padded_b, device):
@@ -788,6 +796,8 @@ class PolicyGradientTrainer(DataParallelStep):
                     self.last_entropy = torch.cat([m[3] for m in self._micro_stats])
                 if self.kl_weight > 0:
                     self.last_kl = torch.cat([m[4] for m in self._micro_stats])
+                if self.unit_spelling is not None:
+                    self.last_spell_truncated = torch.stack([m[5] for m in self._micro_stats]).sum().to(torch.int32)
         finally:
             self._micro_stats = []
         return loss

@@ -116,3 +116,94 @@ class SubwordUnits:
     def load(cls, path):
         with open(path, "r") as fo:
             return cls([line.rstrip("\n") for line in fo.readlines() if line.rstrip("\n") != ""])
+
+
+SPELL_MAX_UNIT_CHARS = 64        # PGASR_SPELL_MAX_UNIT_CHARS
+SPELL_MAX_SYMBOLS = 64           # the spelled rows feed the kernels that hold one symbol per lane (hipops.MAX_VOCAB_NARROW)
+
+
+class UnitSpelling:
+    """UnitSpelling(units, alphabet=None): the character spelling of every unit of a ``SubwordUnits``, as the tables
+    ``pgasr_unit_spell`` reads.  A unit may hold a space (``learn_bpe`` merges across spaces), so unit rows have no word boundaries of
+    their own; the spelled row is the text itself (``decode(encode(text)) == text``), a row over at most 64 character ids.
+
+    alphabet: the characters in the order of the corpus' ``alphabet.txt``; default: the sorted characters that occur in the units.
+    Character ids are 1 .. C in that order, id 0 is never produced, and C + 1 <= 64 is required (ValueError).
+    offsets (V + 1 ints, V = len(units)): token id v spells chars[offsets[v] : offsets[v + 1]]; id 0, the blank / pad, spells nothing.
+    max_unit_chars <= SPELL_MAX_UNIT_CHARS (ValueError).  delimiter: the id of " ", or None -- every word-level use then raises.
+    char_alphabet: the characters, for ``metrics.ErrorReport(spelling.char_alphabet, " ")``."""
+
+    def __init__(self, units, alphabet=None):
+        if not isinstance(units, SubwordUnits):
+            units = SubwordUnits(units)
+        if alphabet is None:
+            alphabet = sorted({ch for u in units.units for ch in u})
+        alphabet = list(alphabet)
+        for ch in alphabet:
+            if not isinstance(ch, str) or len(ch) != 1:
+                raise ValueError(f"the spelling alphabet holds single characters (got {ch!r})")
+        if len(set(alphabet)) != len(alphabet):
+            raise ValueError("a character is listed twice in the spelling alphabet")
+        if len(alphabet) + 1 > SPELL_MAX_SYMBOLS:
+            raise ValueError(f"{len(alphabet)} characters and the pad are more than {SPELL_MAX_SYMBOLS} symbols: the spelled rows must "
+                             f"fit the kernels that hold one symbol per lane")
+        self.units = units
+        self.char_alphabet = alphabet
+        self.char2ind = {ch: i + 1 for i, ch in enumerate(alphabet)}
+        offsets, chars = [0, 0], []
+        for u in units.units:
+            if len(u) > SPELL_MAX_UNIT_CHARS:
+                raise ValueError(f"unit {u!r} has {len(u)} characters, more than the {SPELL_MAX_UNIT_CHARS} that pgasr_unit_spell takes")
+            for ch in u:
+                if ch not in self.char2ind:
+                    raise ValueError(f"character {ch!r} of unit {u!r} is not in the spelling alphabet")
+                chars.append(self.char2ind[ch])
+            offsets.append(len(chars))
+        self.offsets = offsets                      # V + 1 entries
+        self.chars = chars
+        self.vocab = len(units)                     # V: the units and the blank
+        self.n_symbols = len(alphabet) + 1          # the spelled rows' alphabet: the characters and the pad
+        self.max_unit_chars = max(len(u) for u in units.units)
+        self.delimiter = self.char2ind.get(" ")
+        self._device = {}
+
+    def word_delimiter(self, what="unit='word'"):
+        """The id of ' ' for a word-level use, named in the error when the alphabet has none."""
+        if self.delimiter is None:
+            raise ValueError(f"{what} needs words, and the spelling alphabet has no ' ' character to split them at")
+        return self.delimiter
+
+    def spell(self, ids):
+        """token ids -> list of character ids: the contract of pgasr_unit_spell on the host.  An id outside [0, V) adds nothing."""
+        out = []
+        for i in ids:
+            i = int(i)
+            if 0 <= i < self.vocab:
+                out.extend(self.chars[self.offsets[i]:self.offsets[i + 1]])
+        return out
+
+    def text(self, char_ids):
+        """character ids -> text; id 0 adds nothing."""
+        return "".join(self.char_alphabet[int(c) - 1] for c in char_ids if int(c) != 0)
+
+    def to(self, device):
+        """(offsets, chars) as int32 tensors on ``device``, made once per device."""
+        import torch
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        got = self._device.get(device)
+        if got is None:
+            got = (torch.tensor(self.offsets, dtype=torch.int32, device=device),
+                   torch.tensor(self.chars if self.chars else [0], dtype=torch.int32, device=device))
+            self._device[device] = got
+        return got
+
+    @classmethod
+    def load(cls, units_path, alphabet_path=None):
+        """From a units file and, where given, the corpus' alphabet file (one character per line, the line's text as it stands)."""
+        alphabet = None
+        if alphabet_path is not None:
+            with open(alphabet_path, "r") as fo:
+                alphabet = [line.rstrip("\n") for line in fo.readlines() if line.rstrip("\n") != ""]
+        return cls(SubwordUnits.load(units_path), alphabet)
