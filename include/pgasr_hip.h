@@ -370,6 +370,11 @@ int pgasr_head_logsoftmax(const float* x, long long rows, int K, int ldx, const 
  *   greedy_path[t,b] = argmax_v scores[t,b,v], first max wins  (oracle: numpy argmax)
  *   sample_path[t,b] ~ softmax(scores[t,b,:]) by inverse CDF with
  *        u = (philox4x32_10(ctr=(t*ctr_stride+ctr_base+b, offset,0,0), key=(seed_lo,seed_hi)).x >> 8) * 2^-24
+ *        k = min(#{v : cdf_v <= u * total}, V - 1), cdf the inclusive fp32 lane scan of e_v = exp(score_v - max).  A draw never
+ *        returns a label with e_v == 0 (score -inf, or more than about 87 under the maximum): such a k moves to the nearest label
+ *        above it with e > 0, or to the last label with e > 0 if there is none above; a k with e_k > 0 is returned as counted.
+ *        (The scan adds each lane's prefix in its own order, so a flat stretch of the cdf is flat to an ulp only.)  The same
+ *        rule holds for every draw of pgasr_frame_sample_multi and for the wide samplers (A9-WIDE, A12-WIDE).
  *   ctr_stride = 0 means B (counter t*B+b, the single-process layout); a data-parallel rank passes the GLOBAL batch as
  *   ctr_stride and its first utterance's global index as ctr_base (0 <= ctr_base < ctr_stride), so that N ranks with one
  *   seed draw what one process holding the whole batch draws.  Utterances with ctr_base + b >= ctr_stride lie BEYOND the global batch
@@ -1332,7 +1337,8 @@ int pgasr_feat_stack(const float* x, const int32_t* n_frames, int B, int Tmax, i
  *     then ignored, ctr_stride >= 1 is required and T * ctr_stride must fit counter word 0, else PGASR_ERR_UNSUPPORTED).  The
  *     arg-max takes the first maximum.  The sample uses the same Philox counter, key and u, the domain for rows beyond the global
  *     batch included: k = min(#{v : cdf_v <= u * total}, V - 1) with the inclusive cdf of exp(score - max) in label order (a
- *     sequential prefix over the lane's labels on top of the wave scan of the lane totals; with V <= 64 the narrow kernel's cdf).
+ *     sequential prefix over the lane's labels on top of the wave scan of the lane totals; with V <= 64 the narrow kernel's cdf),
+ *     moved off a label whose exp(score - max) is 0 by the rule of A9 / A12.
  *   pgasr_ctc_loss_grad_wide, pgasr_ctc_grad_from_lattice_wide: pgasr_ctc_loss_grad and pgasr_ctc_grad_from_lattice, argument for
  *     argument, on the same workspace (pgasr_ctc_workspace_bytes, same format: either pair may run the gradient pass over the
  *     other's lattice).  The alpha / beta sweeps are the same kernel, so nll has the same bits; the label lists and the gradient
@@ -1369,8 +1375,9 @@ int pgasr_ctc_grad_from_lattice_wide(const float* log_probs, const int32_t* inpu
  *   pgasr_frame_sample_multi_wide: pgasr_frame_sample_multi and, with utt_ids != NULL, pgasr_frame_sample_multi_ids (ctr_base is
  *     then ignored, ctr_stride >= 1 is required and T * ctr_stride must fit counter word 0, else PGASR_ERR_UNSUPPORTED).  The
  *     row's maximum, cdf and total are pgasr_frame_argmax_sample_wide's and are formed once; draw k uses Philox word 0 of counter
- *     (t*ctr_stride + id, offset, 0 or 1, k), the same u and the same min(#{v : cdf_v <= u * total}, V - 1).  Draw 0 is
- *     pgasr_frame_argmax_sample_wide's sample and greedy_path its arg-max, bit for bit.
+ *     (t*ctr_stride + id, offset, 0 or 1, k), the same u and the same min(#{v : cdf_v <= u * total}, V - 1), moved off a label
+ *     of probability 0 by the same rule.  Draw 0 is pgasr_frame_argmax_sample_wide's sample and greedy_path its arg-max, bit for
+ *     bit.
  *   pgasr_frame_entropy_wide, pgasr_frame_kl_wide: pgasr_frame_entropy and pgasr_frame_kl, argument for argument: one workgroup of
  *     16 waves per utterance, frames added in t order with fp64 carries.  p = 0 adds exactly 0; the reference's log-probability is
  *     floored at PGASR_KL_LOG_FLOOR; q = p gives exactly 0.

@@ -6,6 +6,14 @@
 
 namespace {
 
+// A draw never returns a label whose e = exp(score - max) is 0 (the fp32 scan adds each lane's prefix in its own order, so the cdf
+// of such a label can lie one ulp under the threshold that its neighbour's does not).  pos: ballot of e > 0 in label order.  A k
+// with e_k > 0 stays as it is; otherwise the nearest label above it with e > 0, or the last such label if there is none above.
+__device__ __forceinline__ int sample_skip_zero(int k, unsigned long long pos) {
+    const unsigned long long above = pos & (~0ull << k);
+    if (above) return __ffsll((long long)above) - 1;
+    return pos ? 63 - __clzll((long long)pos) : k;
+}
 
 // one wave per (t,b) row
 __global__ __launch_bounds__(256) void frame_argmax_sample_kernel(
@@ -48,17 +56,19 @@ __global__ __launch_bounds__(256) void frame_argmax_sample_kernel(
         philox4x32_10((uint32_t)ctr, offset, outside ? 1u : 0u, 0u, k0, k1, rnd);
         const float u = (float)(rnd[0] >> 8) * (1.0f / 16777216.0f);
         const float thr = u * total;
-        // k = number of labels whose inclusive cdf <= u  (oracle: (cdf <= u).sum())
+        // k = number of labels whose inclusive cdf <= u  (oracle: (cdf <= u).sum()), moved off a label of probability 0
         const unsigned long long m = __ballot(lane < V && c <= thr);
         int k = __popcll(m);
         if (k > V - 1) k = V - 1;
+        k = sample_skip_zero(k, __ballot(e > 0.f));
         if (lane == 0) sample[r] = k;
     }
 }
 
 // K draws per (t,b) row from ONE exp + prefix sum (multi-sample REINFORCE, pgasr_frame_sample_multi).  One wave per row as above;
 // lane j < K runs the Philox block of draw j (counter word 3 = j), so the K blocks cost one; each draw is then resolved by a ballot
-// against the same cdf.  Draw 0's counter, u, threshold and ballot are those of frame_argmax_sample_kernel: its sample bit for bit.
+// against the same cdf and moved off a label of probability 0 by the same rule.  Draw 0's counter, u, threshold and ballot are those
+// of frame_argmax_sample_kernel: its sample bit for bit.
 __global__ __launch_bounds__(256) void frame_sample_multi_kernel(
     const float* __restrict__ scores, long long rows, int B, int V, int K, uint32_t k0, uint32_t k1,
     uint32_t offset, int ctr_stride, int ctr_base, const int32_t* __restrict__ utt_ids, int32_t* __restrict__ greedy,
@@ -89,12 +99,14 @@ __global__ __launch_bounds__(256) void frame_sample_multi_kernel(
     uint32_t rnd[4];
     philox4x32_10((uint32_t)ctr, offset, outside ? 1u : 0u, (uint32_t)lane, k0, k1, rnd);
     const float u = (float)(rnd[0] >> 8) * (1.0f / 16777216.0f);
+    const unsigned long long pos = __ballot(e > 0.f);
     int mine = 0;
     for (int j = 0; j < K; ++j) {
         const float thr = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(u), j)) * total;
         const unsigned long long m = __ballot(lane < V && c <= thr);
         int k = __popcll(m);
         if (k > V - 1) k = V - 1;
+        k = sample_skip_zero(k, pos);
         if (lane == j) mine = k;
     }
     if (lane < K) samples[(size_t)lane * rows + r] = mine;

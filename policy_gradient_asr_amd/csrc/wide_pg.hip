@@ -37,11 +37,13 @@ __global__ __launch_bounds__(256) void frame_sample_multi_wide_kernel(
     if (greedy && lane == 0) greedy[r] = bi;
     float c[NV];          // inclusive prefix within the lane
     float run = 0.f;
+    unsigned pm = 0;      // the lane's labels with e > 0
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
         const float e = (v0 + i < V) ? __expf(x[i] - bv) : 0.f;
         run = (i == 0) ? e : run + e;
         c[i] = run;
+        pm |= (e > 0.f ? 1u : 0u) << i;
     }
     float scan = run;     // inclusive scan of the lane totals, in lane order
 #pragma unroll
@@ -67,6 +69,7 @@ __global__ __launch_bounds__(256) void frame_sample_multi_wide_kernel(
 #pragma unroll
         for (int i = 0; i < NV; ++i) n += __popcll(__ballot(v0 + i < V && c[i] <= thr));
         if (n > V - 1) n = V - 1;
+        n = wide_sample_skip_zero<NV>(n, pm, lane);
         if (lane == j) mine = n;
     }
     if (lane < K) samples[(size_t)lane * rows + r] = mine;

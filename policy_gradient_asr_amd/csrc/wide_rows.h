@@ -52,6 +52,25 @@ __device__ __forceinline__ void wide_row_load(const float* __restrict__ row, int
     for (int i = 0; i < NV; ++i) v[i] = (v0 + i < V) ? row[v0 + i] : fill;
 }
 
+// The wide samplers' rule for a draw n that fell on a label whose e = exp(score - max) is 0 (frame_ops.hip: sample_skip_zero): n
+// stays where e_n > 0; otherwise the nearest label above it with e > 0, or the last such label if there is none above.  pm: bit i
+// set where the lane's label lane*NV + i has e > 0; n is uniform over the wave.  The usual case costs one ballot; the rest (about
+// one draw in 2^24) two butterflies behind a wave-uniform branch.
+template <int NV>
+__device__ __forceinline__ int wide_sample_skip_zero(int n, unsigned pm, int lane) {
+    const int own = n / NV, sub = n % NV;
+    if (__ballot(lane == own && ((pm >> sub) & 1u))) return n;
+    const unsigned above = lane > own ? pm : (lane == own ? pm & (~0u << sub) : 0u);
+    int lo = above ? lane * NV + __ffs((int)above) - 1 : 0x7fffffff;
+    int hi = pm ? lane * NV + 31 - __clz((int)pm) : -1;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        lo = min(lo, __shfl_xor(lo, o, 64));
+        hi = max(hi, __shfl_xor(hi, o, 64));
+    }
+    return lo != 0x7fffffff ? lo : (hi >= 0 ? hi : n);
+}
+
 // row[lane*NV + i] = v[i] for the labels inside the row
 template <int NV>
 __device__ __forceinline__ void wide_row_store(float* __restrict__ row, int V, int lane, bool vec, const float (&v)[NV]) {

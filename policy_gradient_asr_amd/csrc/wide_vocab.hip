@@ -59,11 +59,13 @@ __global__ __launch_bounds__(256) void frame_argmax_sample_wide_kernel(
     if (sample) {
         float c[NV];          // inclusive prefix within the lane
         float run = 0.f;
+        unsigned pm = 0;      // the lane's labels with e > 0
 #pragma unroll
         for (int i = 0; i < NV; ++i) {
             const float e = (v0 + i < V) ? __expf(x[i] - bv) : 0.f;
             run = (i == 0) ? e : run + e;
             c[i] = run;
+            pm |= (e > 0.f ? 1u : 0u) << i;
         }
         float scan = run;     // inclusive scan of the lane totals, in lane order
 #pragma unroll
@@ -92,6 +94,7 @@ __global__ __launch_bounds__(256) void frame_argmax_sample_wide_kernel(
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o, 64);
         if (n > V - 1) n = V - 1;
+        n = wide_sample_skip_zero<NV>(n, pm, lane);
         if (lane == 0) sample[r] = n;
     }
 }

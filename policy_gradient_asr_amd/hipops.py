@@ -610,18 +610,21 @@ def frame_argmax_sample(scores, seed=0, offset=0, want_greedy=True, want_sample=
     g = torch.empty(T, B, dtype=torch.int32, device=scores.device) if want_greedy else None
     s = torch.empty(T, B, dtype=torch.int32, device=scores.device) if want_sample else None
     if _wide(V, wide, "frame_argmax_sample"):
-        st = lib.pgasr_frame_argmax_sample_wide(_p(scores), T, B, V, int(seed) & (2 ** 64 - 1), int(offset) & 0xFFFFFFFF,
-                                                int(batch_stride), 0 if utt_ids is not None else int(batch_offset), _p(utt_ids),
-                                                _p(g), _p(s), _stream())
+        with _timed("frame_argmax_sample_wide"):
+            st = lib.pgasr_frame_argmax_sample_wide(_p(scores), T, B, V, int(seed) & (2 ** 64 - 1), int(offset) & 0xFFFFFFFF,
+                                                    int(batch_stride), 0 if utt_ids is not None else int(batch_offset), _p(utt_ids),
+                                                    _p(g), _p(s), _stream())
         _lib.check(st, "pgasr_frame_argmax_sample_wide")
         return g, s
     if utt_ids is not None:
-        st = lib.pgasr_frame_argmax_sample_ids(_p(scores), T, B, V, int(seed) & (2 ** 64 - 1), int(offset) & 0xFFFFFFFF,
-                                               int(batch_stride), _p(utt_ids), _p(g), _p(s), _stream())
+        with _timed("frame_argmax_sample"):
+            st = lib.pgasr_frame_argmax_sample_ids(_p(scores), T, B, V, int(seed) & (2 ** 64 - 1), int(offset) & 0xFFFFFFFF,
+                                                   int(batch_stride), _p(utt_ids), _p(g), _p(s), _stream())
         _lib.check(st, "pgasr_frame_argmax_sample_ids")
         return g, s
-    st = lib.pgasr_frame_argmax_sample(_p(scores), T, B, V, int(seed) & (2 ** 64 - 1), int(offset) & 0xFFFFFFFF,
-                                       int(batch_stride), int(batch_offset), _p(g), _p(s), _stream())
+    with _timed("frame_argmax_sample"):
+        st = lib.pgasr_frame_argmax_sample(_p(scores), T, B, V, int(seed) & (2 ** 64 - 1), int(offset) & 0xFFFFFFFF,
+                                           int(batch_stride), int(batch_offset), _p(g), _p(s), _stream())
     _lib.check(st, "pgasr_frame_argmax_sample")
     return g, s
 
@@ -647,18 +650,21 @@ def frame_sample_multi(scores, num_samples, seed=0, offset=0, want_greedy=False,
         g = torch.empty(T, B, dtype=torch.int32, device=scores.device) if want_greedy else None
         s = torch.empty(K, T, B, dtype=torch.int32, device=scores.device)
     if _wide(V, wide, "frame_sample_multi"):
-        st = lib.pgasr_frame_sample_multi_wide(_p(scores), T, B, V, K, int(seed) & (2 ** 64 - 1), int(offset) & 0xFFFFFFFF,
-                                               int(batch_stride), 0 if utt_ids is not None else int(batch_offset), _p(utt_ids),
-                                               _p(g), _p(s), _stream())
+        with _timed("frame_sample_multi_wide"):
+            st = lib.pgasr_frame_sample_multi_wide(_p(scores), T, B, V, K, int(seed) & (2 ** 64 - 1), int(offset) & 0xFFFFFFFF,
+                                                   int(batch_stride), 0 if utt_ids is not None else int(batch_offset), _p(utt_ids),
+                                                   _p(g), _p(s), _stream())
         _lib.check(st, "pgasr_frame_sample_multi_wide")
         return g, s
     if utt_ids is not None:
-        st = lib.pgasr_frame_sample_multi_ids(_p(scores), T, B, V, K, int(seed) & (2 ** 64 - 1), int(offset) & 0xFFFFFFFF,
-                                              int(batch_stride), _p(utt_ids), _p(g), _p(s), _stream())
+        with _timed("frame_sample_multi"):
+            st = lib.pgasr_frame_sample_multi_ids(_p(scores), T, B, V, K, int(seed) & (2 ** 64 - 1), int(offset) & 0xFFFFFFFF,
+                                                  int(batch_stride), _p(utt_ids), _p(g), _p(s), _stream())
         _lib.check(st, "pgasr_frame_sample_multi_ids")
         return g, s
-    st = lib.pgasr_frame_sample_multi(_p(scores), T, B, V, K, int(seed) & (2 ** 64 - 1), int(offset) & 0xFFFFFFFF,
-                                      int(batch_stride), int(batch_offset), _p(g), _p(s), _stream())
+    with _timed("frame_sample_multi"):
+        st = lib.pgasr_frame_sample_multi(_p(scores), T, B, V, K, int(seed) & (2 ** 64 - 1), int(offset) & 0xFFFFFFFF,
+                                          int(batch_stride), int(batch_offset), _p(g), _p(s), _stream())
     _lib.check(st, "pgasr_frame_sample_multi")
     return g, s
 

@@ -21,6 +21,7 @@ import pytest
 import torch
 
 import ctc_cases as cc
+from frame_rows_ref import lsm_check as _lsm_check
 from oracle import ctc_ref, decode_ref, model_ref, pg_ref
 from pg_harness import DEV, load_params, make_batch, param_errs, rel_err
 
@@ -38,18 +39,7 @@ def ops():
 
 
 # ---- log-softmax ----
-def _lsm_check(ops, x, label):
-    got = ops.log_softmax_rows(x.to(DEV)).cpu().double()
-    want = torch.log_softmax(x.double(), -1)
-    finite = torch.isfinite(want)
-    assert torch.equal(torch.isneginf(got), torch.isneginf(want)) and torch.isfinite(got[finite]).all()
-    lse = torch.logsumexp(x.double(), -1, keepdim=True)
-    mag = torch.maximum(x.double().masked_fill(~torch.isfinite(x), 0).abs().amax(-1, keepdim=True), lse.abs())
-    bound = (4 * EPS32 * mag + 2e-6).expand_as(want)
-    err = (got - want).abs()
-    worst = float((err[finite] / bound[finite]).max())
-    print(f"[wide log-softmax] {label}: worst err / bound {worst:.2f}, max err {float(err[finite].max()):.2e}")
-    assert worst <= 1.0
+# the check and its bound live in tests/frame_rows_ref.py, which holds the narrow kernel to the same
 
 
 @pytest.mark.parametrize("V", WIDE_V)
@@ -62,14 +52,14 @@ def test_log_softmax_vs_fp64(ops, V):
         if T > 1:
             x[1, 0, ::3] = -float("inf")            # p = 0 entries, the last partial group included
             x[1, 0, V - 1] = -float("inf")
-        _lsm_check(ops, x, f"V={V} T={T} B={B}")
+        _lsm_check(ops, x, f"V={V} T={T} B={B}", DEV)
 
 
 def test_log_softmax_maximum_in_the_last_column(ops):
     g = torch.Generator().manual_seed(1)
     x = torch.randn(17, 3, 65, generator=g)
     x[:, :, 64] += 12.0                             # the one label of lane 32's group, alone in the ragged tail
-    _lsm_check(ops, x, "V=65 max last")
+    _lsm_check(ops, x, "V=65 max last", DEV)
     # misaligned tensors take the scalar loads: a view that starts 4 bytes into the allocation
     base = torch.randn(5 * 128 + 1, generator=g).to(DEV)
     x = base[1:].view(5, 1, 128)
