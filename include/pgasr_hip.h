@@ -668,8 +668,10 @@ int pgasr_log_softmax_rows(const float* logits, long long rows, int V, float* lo
  *     sweeps (flags bit 1 below; the reference's nn.LSTM is fp32, model.py:39-44): six products, every term down to
  *     2^-24 of the product.
  * pgasr_lstm_layer_fwd: gates (T,B,2,H,4) holds xproj = X * wih_perm^T + bias_perm on entry and
- *   the activations (i,f,g,o) on exit; out (T,B,2H) = h; cbuf (T,B,2,H) = c.
- * pgasr_lstm_layer_bwd: dout (T,B,2H) -> gates overwritten in place by d(pre-activation gates);
+ *   the activations (i,f,g,o) on exit; out (T,B,2H) = h; cbuf (T,B,2,H) = c.  Every row t < T, b < B is written, none
+ *   beyond; past an utterance's length out and the activations are 0 and cbuf is the state as it stands there: the last
+ *   frame's in the forward direction, 0 in the reverse one (tests/test_lstm_geometry_gpu.py).
+ * pgasr_lstm_layer_bwd: dout (T,B,2H) -> gates overwritten in place by d(pre-activation gates), 0 past each length;
  *   the caller forms dX = dgates * wih_perm, dW_ih = dgates^T X, dW_hh = dgates^T h_prev with
  *   pgasr_gemm_f32 and maps them back with pgasr_lstm_unpack_grads.  dbias_part (optional, 16-byte aligned,
  *   ceil(B/16) x 2*4H floats): per 16-utterance group, the sum over t of dgates in gates' column order -- the bias

@@ -664,7 +664,9 @@ bool pgasr_internal_tn256_ok(const PgasrTn256Args& a, int tk) {
     // PGASR_TN_TILE=128 (read at every call) keeps gemm.hip's 128 x 128 kernel (A/B measurements)
     const char* e = getenv("PGASR_TN_TILE");
     if (e && e[0] == '1' && e[1] == '2' && e[2] == '8') return false;
-    if (!a.A || !a.B || !a.partial || a.M <= 0 || a.N <= 0 || a.K < 32 || a.batch <= 0 || a.splitk <= 0) return false;
+    // at least ONE k-step of the kernel that will run: 16 rows for t6 -- dW_hh of a two-frame sweep over 16 utterances (hipops.lstm_wgrads_ok
+    // has always promised that shape; `K < 32` here refused it)
+    if (!a.A || !a.B || !a.partial || a.M <= 0 || a.N <= 0 || a.K < tk || a.batch <= 0 || a.splitk <= 0) return false;
     if ((a.M % t256::TM) || (a.N % t256::TN) || (a.K % tk) || (!a.tslabs && (a.kper % 32)) || (a.lda & 3) || (a.ldb & 3)) return false;
     if ((a.sA & 3) || (a.sB & 3) || (((size_t)a.A) & 15) || (((size_t)a.B) & 15)) return false;
     if (!a.tslabs && (long long)(a.splitk - 1) * a.kper >= a.K) return false;        // no empty slab
