@@ -1471,6 +1471,52 @@ int pgasr_ctc_grad_from_lattices_seq_wide(const float* log_probs, const int32_t*
                                           float* grad_logits, void* workspace, size_t workspace_bytes,
                                           void* hyp_workspace, size_t hyp_workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * A12-STEP  Per-step rewards (pgasr_pg_step_coefs) with K sampled paths, either baseline, both tails and rows of 1 <= V <= 1024
+ * symbols: the reward-to-go of every frame goes into the multi-sample REINFORCE term in place of one coefficient per utterance.
+ * Path rows of utterance b: the hypothesis baseline has P = K + 1 rows, the greedy path first, then the K samples; leave one out
+ * has P = K rows.  For row w with collapsed length n_w and D_w[i] = ED(y_b, yhat_w[:i]) (pgasr_edit_distance's prefix row):
+ *   a character starts at frame t when t < T_b, the label is not blank, and t = 0 or the label differs from the label at t - 1;
+ *   c_w(t) = characters started at frames < t, clipped to n_w;      G_w(t) = D_w[c_w(t)] - D_w[n_w]      an integer
+ *   kf_b   = ((lam * inv_global_batch) / K) / max(L_b,1)            fp32, in this order
+ *   PGASR_BASELINE_HYPOTHESIS:     coef[k,t,b] = kf_b * (G_k(t) - G_greedy(t))
+ *   PGASR_BASELINE_LEAVE_ONE_OUT:  coef[k,t,b] = kf_b * (G_k(t) - (S(t) - G_k(t)) / (K-1)),  S(t) = sum_j G_j(t) an exact integer
+ *   coef[k,t,b] = 0 for t >= T_b.  In exact arithmetic coef[k,0,b] is pgasr_pg_rewards_multi's pg_coef[k,b]; the leave-one-out
+ *   coefficients of a frame sum to 0 over k.  Either baseline is a function of the OTHER rows at the same frame, so the estimator
+ *   stays unbiased.
+ *   objective  = sum_b nll_b utt_scale_b - sum_k sum_b sum_{t<T_b} coef[k,t,b] log p(pi_k[t,b])      (+ the entropy and KL terms)
+ *   d(logits)[t,b,:] = utt_scale_b (softmax - occupancy) + sum_k coef[k,t,b] (softmax - onehot(pi_k[t,b])) in k order, then the
+ *   entropy tail, then the KL tail.  R_sample, R_baseline and utt_scale come from pgasr_pg_rewards_multi as in any multi-sample call;
+ *   its (K,B) coefficients are not used.
+ *
+ * pgasr_pg_step_coefs_multi: paths (P,T,B) int32 frame labels; prefix_dist (P*B, prefix_stride) and token_lengths (P*B) int32 of
+ *   their collapsed forms, row w*B + b; coef (K,T,B) fp32, every word written.  One workgroup of 16 waves per utterance, each wave a
+ *   64-frame chunk of a 1024-frame pass: per (row, chunk) start counts by ballot, one scan per row for the carries, then each lane
+ *   forms all K coefficients of its frame from the P integers it holds.  Deterministic.  With K = 1 and the hypothesis baseline
+ *   the output is pgasr_pg_step_coefs' (T,B) words bit for bit.  Checked before any launch: a NULL pointer, T or B <= 0,
+ *   prefix_stride < 1, blank < 0, K outside 1..PGASR_MAX_SAMPLES, an unknown baseline, leave one out with K < 2 ->
+ *   PGASR_ERR_INVALID_ARG.
+ * pgasr_ctc_grad_from_lattice_multi_steps: pgasr_ctc_grad_from_lattice_multi[_ent,_kl] and _multi_wide with pg_coef (K,T,B), read
+ *   at k*T*B + t*B + b: ONE entry for 1 <= V <= 1024 with nullable tails, on the workspace of pgasr_ctc_loss_grad or
+ *   pgasr_ctc_loss_grad_wide.  V <= 64 runs the narrow kernels' body, V > 64 the wide kernels' -- a compile-time switch of each,
+ *   so coefficients that are constant over t give the per-utterance entries' bits, and K = 1 without tails at V <= 64 gives
+ *   pgasr_ctc_grad_from_lattice's with pg_coef_per_frame.  Argument checks and codes of pgasr_ctc_grad_from_lattice_multi_wide.
+ * pgasr_pg_loss_value_multi_steps: terms[b] = nll[b]*utt_scale[b] - sum_k sum_{t<input_lengths[b]} pg_coef[k,t,b] *
+ *   log_probs[t,b,paths[k,t,b]]; each path's sum in pgasr_pg_loss_value's fixed per-frame order, the K sums added in k order.  Any V.
+ * ---------------------------------------------------------------------------------------- */
+int pgasr_pg_step_coefs_multi(const int32_t* paths, const int32_t* input_lengths, const int32_t* prefix_dist, int prefix_stride,
+                              const int32_t* token_lengths, const int32_t* target_lengths, int T, int B, int K, int baseline,
+                              int blank, float lam, float inv_global_batch, float* coef, void* stream);
+int pgasr_ctc_grad_from_lattice_multi_steps(const float* log_probs, const int32_t* input_lengths,
+                                            const int32_t* target_lengths, int T, int B, int V, int Lmax, int blank,
+                                            const float* utt_scale, int K, const float* pg_coef /* (K,T,B) */,
+                                            const int32_t* pg_paths, const float* ent_scale /* may be NULL */,
+                                            const float* ref_log_probs /* may be NULL */, const float* kl_scale /* may be NULL */,
+                                            float* grad_logits, void* workspace, size_t workspace_bytes, void* stream);
+int pgasr_pg_loss_value_multi_steps(const float* log_probs, const int32_t* paths, int K, const int32_t* input_lengths,
+                                    const float* nll, const float* utt_scale, const float* pg_coef /* (K,T,B) */,
+                                    int T, int B, int V, float* terms, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -188,6 +188,13 @@ SIGNATURES = {
     "pgasr_ctc_grad_from_lattices_seq_wide": (C.c_int, [c_f32p, c_i32p, c_i32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_f32p,
                                                         C.c_int, c_f32p, c_i32p, c_i32p, C.c_int, c_f32p, c_f32p, c_f32p, c_f32p,
                                                         c_ptr, C.c_size_t, c_ptr, C.c_size_t, c_ptr]),
+    "pgasr_pg_step_coefs_multi": (C.c_int, [c_i32p, c_i32p, c_i32p, C.c_int, c_i32p, c_i32p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                            C.c_int, C.c_float, C.c_float, c_f32p, c_ptr]),
+    "pgasr_ctc_grad_from_lattice_multi_steps": (C.c_int, [c_f32p, c_i32p, c_i32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                          c_f32p, C.c_int, c_f32p, c_i32p, c_f32p, c_f32p, c_f32p, c_f32p, c_ptr,
+                                                          C.c_size_t, c_ptr]),
+    "pgasr_pg_loss_value_multi_steps": (C.c_int, [c_f32p, c_i32p, C.c_int, c_i32p, c_f32p, c_f32p, c_f32p, C.c_int, C.c_int,
+                                                  C.c_int, c_f32p, c_ptr]),
     "pgasr_lstm_pack_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "pgasr_lstm_pack_weights": (C.c_int, [c_f32p] * 8 + [C.c_int, c_f32p, c_f32p, c_ptr, c_ptr, C.c_int, c_ptr]),
     "pgasr_lstm_unpack_grads": (C.c_int, [c_f32p, c_f32p, c_f32p, C.c_int] + [c_f32p] * 8 + [C.c_int, c_ptr]),

@@ -526,7 +526,11 @@ __global__ __launch_bounds__(256) void ctc_grad_kernel(
 // Multi-sample REINFORCE (pgasr_ctc_grad_from_lattice_multi): the CTC part above, then the K terms
 // pg_coef[k,b] * (softmax - onehot(pg_paths[k,t,b])) added in k order.  One wave per (t,b), one pass over the gradient;
 // K = 1 is ctc_grad_kernel's per-utterance expression.
-template <bool ENT, class... Ent>
+// STEPS (pgasr_ctc_grad_from_lattice_multi_steps, A12-STEP): pg_coef is (K,T,B), one coefficient per sample and FRAME, read at
+// k*T*B + t*B + b; everything else is the same line.  A compile-time switch, so the STEPS = false instantiations keep the instruction
+// text they had before it existed (their symbols gained the parameter; per-kernel disassembly compared, NOTES.md 0.37).  One
+// __device__ body called by two kernels did not keep it: the registers came out differently.
+template <bool ENT, bool STEPS, class... Ent>
 __global__ __launch_bounds__(256) void ctc_grad_multi_kernel(
     const float* __restrict__ lp, const int32_t* __restrict__ in_len, const int32_t* __restrict__ tg_len,
     int T, int B, int V, int Lmax, int Smax, int blank, CtcWs ws,
@@ -547,7 +551,7 @@ __global__ __launch_bounds__(256) void ctc_grad_multi_kernel(
     const size_t TB = (size_t)T * B;
     for (int k = 0; k < K; ++k) {
         const int pk = pg_paths[k * TB + (size_t)t * B + b];
-        g += pg_coef[(size_t)k * B + b] * (sm - (lane == pk ? 1.f : 0.f));
+        g += pg_coef[STEPS ? k * TB + (size_t)t * B + b : (size_t)k * B + b] * (sm - (lane == pk ? 1.f : 0.f));
     }
     g = ctc_grad_tail<ENT>(g, lpv, sm, lane, V, b, o, ent_scale...);
     if (lane < V) grad[o + lane] = g;
@@ -868,7 +872,8 @@ static int ctc_launch_grad_wide(const float* log_probs, const int32_t* input_len
 // of ALL its labels, and reads the NV - 1 offsets between them only when the two differ.  A lane none of whose labels occurs in the
 // target -- with L labels over V / NV groups, most lanes at V >= 256 -- does two loads where ctc_grad_wide_kernel does NV + 1, and
 // every label's (empty) sum is the 0 the walk would have given: the summation order is unchanged.
-template <int NV, int TAIL>
+// STEPS: pg_coef (K,T,B) as in ctc_grad_multi_kernel, the same compile-time switch.
+template <int NV, int TAIL, bool STEPS>
 __global__ __launch_bounds__(64 * CTC_WIDE_WPB) void ctc_grad_multi_wide_kernel(
     const float* __restrict__ lp, const int32_t* __restrict__ in_len,
     const int32_t* __restrict__ tg_len, int T, int B, int V, int vec, int Lmax, int Smax, int blank, CtcWs ws,
@@ -942,7 +947,7 @@ __global__ __launch_bounds__(64 * CTC_WIDE_WPB) void ctc_grad_multi_wide_kernel(
     const size_t TB = (size_t)T * B;
     for (int k = 0; k < K; ++k) {
         const int pk = pg_paths[k * TB + (size_t)t * B + b];
-        const float c = pg_coef[(size_t)k * B + b];
+        const float c = pg_coef[STEPS ? k * TB + (size_t)t * B + b : (size_t)k * B + b];
 #pragma unroll
         for (int i = 0; i < NV; ++i) g[i] += c * (sm[i] - (v0 + i == pk ? 1.f : 0.f));
     }
@@ -980,7 +985,7 @@ __global__ __launch_bounds__(64 * CTC_WIDE_WPB) void ctc_grad_multi_wide_kernel(
     wide_row_store<NV>(grad + o, V, lane, vec != 0, g);
 }
 
-template <int TAIL>
+template <int TAIL, bool STEPS = false>
 static int ctc_launch_grad_multi_wide(const float* log_probs, const int32_t* input_lengths, const int32_t* target_lengths, int T, int B,
                                       int V, int Lmax, int blank, const CtcWs& ws, const float* utt_scale, int K, const float* pg_coef,
                                       const int32_t* pg_paths, const float* ent_scale, const float* ref_log_probs,
@@ -988,7 +993,7 @@ static int ctc_launch_grad_multi_wide(const float* log_probs, const int32_t* inp
     const long long waves = (long long)T * B;
     const unsigned blocks = (unsigned)((waves + CTC_WIDE_WPB - 1) / CTC_WIDE_WPB);
     // one `vec` for the launch: the row loads of log_probs and ref_log_probs and the row store must all be aligned
-#define PGASR_CALL(NV) PGASR_LAUNCH_KERNEL((ctc_grad_multi_wide_kernel<NV, TAIL>), dim3(blocks), dim3(64 * CTC_WIDE_WPB), 0,                  \
+#define PGASR_CALL(NV) PGASR_LAUNCH_KERNEL((ctc_grad_multi_wide_kernel<NV, TAIL, STEPS>), dim3(blocks), dim3(64 * CTC_WIDE_WPB), 0,           \
                                            (hipStream_t)stream, log_probs, input_lengths, target_lengths, T, B, V,                              \
                                            (wide_vec_ok<NV>(log_probs, grad_logits, V) &&                                                       \
                                             (TAIL < 2 || wide_vec_ok<NV>(ref_log_probs, ref_log_probs, V))) ? 1 : 0,                            \
@@ -1343,12 +1348,12 @@ extern "C" int pgasr_ctc_grad_from_lattice_multi_kl(const float* log_probs, cons
     CtcWs ws;
     if (!ctc_ws_bind(T, B, V, 2 * Lmax + 1, &ws, workspace, workspace_bytes)) return PGASR_ERR_WORKSPACE;
     if (kl_scale)
-        return ctc_launch_grad(ctc_grad_multi_kernel<true, const float*, const float*, const float*>, log_probs, input_lengths, target_lengths, T, B, V,
+        return ctc_launch_grad(ctc_grad_multi_kernel<true, false, const float*, const float*, const float*>, log_probs, input_lengths, target_lengths, T, B, V,
                                Lmax, blank, ws, utt_scale, stream, K, pg_coef, pg_paths, grad_logits, ent_scale, ref_log_probs, kl_scale);
     if (ent_scale)
-        return ctc_launch_grad(ctc_grad_multi_kernel<true, const float*>, log_probs, input_lengths, target_lengths, T, B, V, Lmax, blank, ws, utt_scale,
+        return ctc_launch_grad(ctc_grad_multi_kernel<true, false, const float*>, log_probs, input_lengths, target_lengths, T, B, V, Lmax, blank, ws, utt_scale,
                                stream, K, pg_coef, pg_paths, grad_logits, ent_scale);
-    return ctc_launch_grad(ctc_grad_multi_kernel<false>, log_probs, input_lengths, target_lengths, T, B, V, Lmax, blank, ws, utt_scale,
+    return ctc_launch_grad(ctc_grad_multi_kernel<false, false>, log_probs, input_lengths, target_lengths, T, B, V, Lmax, blank, ws, utt_scale,
                            stream, K, pg_coef, pg_paths, grad_logits);
 }
 
@@ -1555,6 +1560,43 @@ extern "C" int pgasr_ctc_grad_from_lattice_multi_wide(const float* log_probs, co
                                              pg_paths, ent_scale, nullptr, nullptr, grad_logits, stream);
     return ctc_launch_grad_multi_wide<0>(log_probs, input_lengths, target_lengths, T, B, V, Lmax, blank, ws, utt_scale, K, pg_coef,
                                          pg_paths, nullptr, nullptr, nullptr, grad_logits, stream);
+}
+
+// ---- A12-STEP: the multi-sample gradient pass with per-frame coefficients pg_coef (K,T,B), ONE entry for 1 <= V <= 1024 ----
+// The tails are nullable as in the entry above.  V <= 64 runs ctc_grad_multi_kernel (one label per lane) over the lattice
+// pgasr_ctc_loss_grad left, V > 64 ctc_grad_multi_wide_kernel's over pgasr_ctc_loss_grad_wide's -- the workspace layout is the same --,
+// so coefficients that are constant over t give the bits of the per-utterance entries a caller would have taken for that V.
+extern "C" int pgasr_ctc_grad_from_lattice_multi_steps(const float* log_probs, const int32_t* input_lengths,
+                                                       const int32_t* target_lengths, int T, int B, int V, int Lmax, int blank,
+                                                       const float* utt_scale, int K, const float* pg_coef, const int32_t* pg_paths,
+                                                       const float* ent_scale, const float* ref_log_probs, const float* kl_scale,
+                                                       float* grad_logits, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!log_probs || !input_lengths || !target_lengths || !grad_logits || !pg_coef || !pg_paths) return PGASR_ERR_INVALID_ARG;
+    if ((ref_log_probs == nullptr) != (kl_scale == nullptr)) return PGASR_ERR_INVALID_ARG;
+    if (K < 1 || K > PGASR_MAX_SAMPLES) return PGASR_ERR_INVALID_ARG;
+    const int ok = ctc_args_ok_wide(T, B, V, Lmax, blank);
+    if (ok != PGASR_OK) return ok;
+    CtcWs ws;
+    if (!ctc_ws_bind(T, B, V, 2 * Lmax + 1, &ws, workspace, workspace_bytes)) return PGASR_ERR_WORKSPACE;
+    if (V <= CTC_VMAX) {
+        if (kl_scale)
+            return ctc_launch_grad(ctc_grad_multi_kernel<true, true, const float*, const float*, const float*>, log_probs, input_lengths,
+                                   target_lengths, T, B, V, Lmax, blank, ws, utt_scale, stream, K, pg_coef, pg_paths, grad_logits, ent_scale,
+                                   ref_log_probs, kl_scale);
+        if (ent_scale)
+            return ctc_launch_grad(ctc_grad_multi_kernel<true, true, const float*>, log_probs, input_lengths, target_lengths, T, B, V, Lmax,
+                                   blank, ws, utt_scale, stream, K, pg_coef, pg_paths, grad_logits, ent_scale);
+        return ctc_launch_grad(ctc_grad_multi_kernel<false, true>, log_probs, input_lengths, target_lengths, T, B, V, Lmax, blank, ws,
+                               utt_scale, stream, K, pg_coef, pg_paths, grad_logits);
+    }
+    if (kl_scale)
+        return ctc_launch_grad_multi_wide<2, true>(log_probs, input_lengths, target_lengths, T, B, V, Lmax, blank, ws, utt_scale, K, pg_coef,
+                                                   pg_paths, ent_scale, ref_log_probs, kl_scale, grad_logits, stream);
+    if (ent_scale)
+        return ctc_launch_grad_multi_wide<1, true>(log_probs, input_lengths, target_lengths, T, B, V, Lmax, blank, ws, utt_scale, K, pg_coef,
+                                                   pg_paths, ent_scale, nullptr, nullptr, grad_logits, stream);
+    return ctc_launch_grad_multi_wide<0, true>(log_probs, input_lengths, target_lengths, T, B, V, Lmax, blank, ws, utt_scale, K, pg_coef,
+                                               pg_paths, nullptr, nullptr, nullptr, grad_logits, stream);
 }
 
 // ---- A13-WIDE: the hypothesis lattices and the pass over K+1 lattices for 1 <= V <= 1024 (same workspaces, same sweep kernel) ----

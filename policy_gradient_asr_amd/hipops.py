@@ -226,8 +226,9 @@ def _grad_pass(entry, log_probs, input_lengths, target_lengths, handle, utt_scal
 
 
 def _grad_pass_multi_wide(log_probs, input_lengths, target_lengths, handle, utt_scale, pg_coef, pg_paths, ent_scale, ref_log_probs,
-                          kl_scale):
-    """``pgasr_ctc_grad_from_lattice_multi_wide`` with ``_grad_pass``'s checks of the optional terms."""
+                          kl_scale, entry="pgasr_ctc_grad_from_lattice_multi_wide"):
+    """``pgasr_ctc_grad_from_lattice_multi_wide`` with ``_grad_pass``'s checks of the optional terms; entry: that one, or
+    ``pgasr_ctc_grad_from_lattice_multi_steps``, which takes the same arguments with pg_coef (K,T,B)."""
     lib = _lib.load()
     ws, Lmax, blank = handle
     T, B, V = log_probs.shape
@@ -246,10 +247,10 @@ def _grad_pass_multi_wide(log_probs, input_lengths, target_lengths, handle, utt_
             raise _lib.PgasrError(f"ref_log_probs must be {tuple(log_probs.shape)} and kl_scale ({B},); got "
                                   f"{tuple(ref_log_probs.shape)} and {tuple(kl_scale.shape)}")
     grad = torch.empty_like(log_probs)
-    st = lib.pgasr_ctc_grad_from_lattice_multi_wide(_p(log_probs), _p(input_lengths), _p(target_lengths), T, B, V, Lmax, blank,
-                                                    _p(utt_scale), K, _p(pg_coef), _p(pg_paths), _p(ent_scale), _p(ref_log_probs),
-                                                    _p(kl_scale), _p(grad), _p(ws), ws.numel(), _stream())
-    _lib.check(st, "pgasr_ctc_grad_from_lattice_multi_wide")
+    st = getattr(lib, entry)(_p(log_probs), _p(input_lengths), _p(target_lengths), T, B, V, Lmax, blank,
+                             _p(utt_scale), K, _p(pg_coef), _p(pg_paths), _p(ent_scale), _p(ref_log_probs),
+                             _p(kl_scale), _p(grad), _p(ws), ws.numel(), _stream())
+    _lib.check(st, entry)
     return grad
 
 
@@ -357,11 +358,18 @@ def ctc_grad_from_lattice_multi(log_probs, input_lengths, target_lengths, handle
     """``ctc_grad_from_lattice`` with K sampled paths: pg_paths (K,T,B) int32, pg_coef (K,B) fp32; the K REINFORCE terms are
     added in k order after the CTC part, in the same pass.
     V > 64 (or wide=True): ``pgasr_ctc_grad_from_lattice_multi_wide``, ONE entry that takes ent_scale, ref_log_probs and kl_scale as
-    nullable pointers where the narrow family has three."""
+    nullable pointers where the narrow family has three.
+    pg_coef (K,T,B), one coefficient per sample and frame (``pg_step_coefs_multi``): ``pgasr_ctc_grad_from_lattice_multi_steps``, one
+    entry for every V <= 1024 with nullable tails (the form is chosen by the shape, as ``_coef_per_frame`` does for one path)."""
     T, B, V = log_probs.shape
     K = pg_paths.shape[0]
+    if pg_paths.dim() == 3 and tuple(pg_paths.shape[1:]) == (T, B) and tuple(pg_coef.shape) == (K, T, B):
+        # one coefficient per sample and frame (pg_step_coefs_multi): ONE entry for every V, which picks the kernel family by V
+        _wide(V, wide, "ctc_grad_from_lattice_multi")
+        return _grad_pass_multi_wide(log_probs, input_lengths, target_lengths, handle, utt_scale, pg_coef, pg_paths, ent_scale,
+                                     ref_log_probs, kl_scale, entry="pgasr_ctc_grad_from_lattice_multi_steps")
     if pg_paths.dim() != 3 or tuple(pg_paths.shape[1:]) != (T, B) or tuple(pg_coef.shape) != (K, B):
-        raise _lib.PgasrError(f"ctc_grad_from_lattice_multi wants pg_paths (K,{T},{B}) and pg_coef (K,{B})")
+        raise _lib.PgasrError(f"ctc_grad_from_lattice_multi wants pg_paths (K,{T},{B}) and pg_coef (K,{B}) or (K,{T},{B})")
     if _wide(V, wide, "ctc_grad_from_lattice_multi"):
         return _grad_pass_multi_wide(log_probs, input_lengths, target_lengths, handle, utt_scale, pg_coef, pg_paths, ent_scale,
                                      ref_log_probs, kl_scale)
@@ -401,11 +409,15 @@ def pg_rewards_multi(dist, target_lengths, num_samples, lam, inv_global_batch, b
 
 
 def pg_loss_value_multi(log_probs, paths, input_lengths, nll, utt_scale, pg_coef):
-    """Per-utterance value of the multi-sample objective, paths (K,T,B), pg_coef (K,B); sum() it for the loss."""
+    """Per-utterance value of the multi-sample objective, paths (K,T,B), pg_coef (K,B) -- or (K,T,B), one coefficient per sample and
+    frame (``pgasr_pg_loss_value_multi_steps``); sum() it for the loss."""
     T, B, _ = log_probs.shape
     K = paths.shape[0]
+    if paths.dim() == 3 and tuple(paths.shape[1:]) == (T, B) and tuple(pg_coef.shape) == (K, T, B):
+        # one coefficient per sample and frame (pg_step_coefs_multi)
+        return _loss_value("pgasr_pg_loss_value_multi_steps", log_probs, paths, "paths", input_lengths, nll, utt_scale, pg_coef, K=(K,))
     if paths.dim() != 3 or tuple(paths.shape[1:]) != (T, B) or tuple(pg_coef.shape) != (K, B):
-        raise _lib.PgasrError(f"pg_loss_value_multi wants paths (K,{T},{B}) and pg_coef (K,{B})")
+        raise _lib.PgasrError(f"pg_loss_value_multi wants paths (K,{T},{B}) and pg_coef (K,{B}) or (K,{T},{B})")
     return _loss_value("pgasr_pg_loss_value_multi", log_probs, paths, "paths", input_lengths, nll, utt_scale, pg_coef, K=(K,))
 
 
@@ -581,6 +593,33 @@ def pg_step_coefs(paths, input_lengths, prefix_dist, token_lengths, target_lengt
     st = lib.pgasr_pg_step_coefs(_p(paths), _p(input_lengths), _p(prefix_dist), prefix_dist.shape[1], _p(token_lengths),
                                  _p(target_lengths), T, B, int(blank), float(lam), float(inv_global_batch), _p(coef), _stream())
     _lib.check(st, "pgasr_pg_step_coefs")
+    return coef
+
+
+def pg_step_coefs_multi(paths, input_lengths, prefix_dist, token_lengths, target_lengths, num_samples, lam, inv_global_batch,
+                        baseline="hypothesis", blank=0):
+    """Per-frame REINFORCE coefficients (K,T,B) of K sampled paths (``pgasr_pg_step_coefs_multi``; include/pgasr_hip.h, A12-STEP):
+    paths (P,T,B) frame labels -- the greedy path then the K samples (baseline "hypothesis", P = K + 1), or the K samples
+    ("leave_one_out", P = K) --, prefix_dist (P*B, stride) / token_lengths (P*B) of their collapsed forms.  K = 1 with the hypothesis
+    baseline gives ``pg_step_coefs``' words as (1,T,B)."""
+    lib = _lib.load()
+    _req(paths, torch.int32, "paths"); _req(prefix_dist, torch.int32, "prefix_dist"); _req(token_lengths, torch.int32, "token_lengths")
+    _req(input_lengths, torch.int32, "input_lengths"); _req(target_lengths, torch.int32, "target_lengths")
+    if baseline not in BASELINES:
+        raise ValueError(f"baseline must be one of {sorted(BASELINES)}")
+    K = int(num_samples)
+    P = K + (1 if baseline == "hypothesis" else 0)
+    if (paths.dim() != 3 or paths.shape[0] != P or prefix_dist.dim() != 2 or prefix_dist.shape[0] != P * paths.shape[2]
+            or token_lengths.numel() != P * paths.shape[2] or target_lengths.numel() != paths.shape[2]
+            or input_lengths.numel() != paths.shape[2]):
+        raise _lib.PgasrError(f"pg_step_coefs_multi wants paths ({P},T,B), prefix_dist ({P}*B,stride), token_lengths ({P}*B,), "
+                              f"input_lengths and target_lengths (B,)")
+    _, T, B = paths.shape
+    coef = torch.empty(K, T, B, dtype=torch.float32, device=paths.device)
+    st = lib.pgasr_pg_step_coefs_multi(_p(paths), _p(input_lengths), _p(prefix_dist), prefix_dist.shape[1], _p(token_lengths),
+                                       _p(target_lengths), T, B, K, BASELINES[baseline], int(blank), float(lam),
+                                       float(inv_global_batch), _p(coef), _stream())
+    _lib.check(st, "pgasr_pg_step_coefs_multi")
     return coef
 
 

@@ -54,8 +54,26 @@ class PGCTCLossFn(torch.autograd.Function):
       "leave_one_out": (S - R_k) / (K-1) with S = sum_j R_j in j order, fp32 (K >= 2; the greedy argmax and the beam search are skipped).
         loss = sum_b [ nll_b / (Bg max(L_b,1))  -  sum_k lam / (Bg K) (R_k - b_k) sum_{t<T_b} log p(pi_k,t,b) ]
     and d(logits) adds the K REINFORCE terms in k order after the CTC part.  K = 1 with the hypothesis baseline is the objective
-    above, on the single-path kernels.  per_step takes K = 1 only.  The baseline of an utterance uses that utterance's samples alone, so
-    data-parallel ranks exchange nothing for it.
+    above, on the single-path kernels.  per_step takes K = 1 only, unless step_objectives is set (below).  The baseline of an
+    utterance uses that utterance's samples alone, so data-parallel ranks exchange nothing for it.
+    ``step_objectives = True`` (opt-in; False, the default, is every call, refusal and bit above): per_step with num_samples 1..16,
+    either baseline, entropy_weight, kl_weight and the shard addressings, and with alphabets of 65 .. 1024 symbols
+    (include/pgasr_hip.h, A12-STEP).  Path rows of utterance b: P = K + 1 with the hypothesis baseline -- the greedy path, then the K
+    samples --, P = K with leave one out.  For row w with collapsed length n_w, D_w[i] = ED(y_b, yhat_w[:i]) and c_w(t) the characters
+    started at frames < t (a character starts at t < T_b where the label is not blank and t = 0 or the label differs from that at
+    t - 1), clipped to n_w, the reward-to-go is the integer G_w(t) = D_w[c_w(t)] - D_w[n_w], and in fp32
+        kf_b         = ((lam / Bg) / K) / max(L_b,1)
+        coef[k,t,b]  = kf_b (G_k(t) - G_greedy(t))                                          "hypothesis"
+                     = kf_b (G_k(t) - (S(t) - G_k(t)) / (K-1)),  S(t) = sum_j G_j(t)        "leave_one_out"     0 for t >= T_b
+        loss         = sum_b nll_b utt_scale_b - sum_k sum_b sum_{t<T_b} coef[k,t,b] log p(pi_k[t,b])    + the entropy and KL terms
+        d(logits)    = utt_scale_b (softmax - occ) + sum_k coef[k,t,b] (softmax - onehot(pi_k[t,b]))  in k order, then the two tails
+    Frame 0 carries the utterance-level pg_coef[k,b] in exact arithmetic; either baseline of a frame depends on the other rows alone, so
+    the estimator is unbiased.  R_s (K,B), R_b (B) and utt_scale are the multi-sample call's (``pgasr_pg_rewards_multi``, whose (K,B)
+    coefficients are not used).  K = 1 with the hypothesis baseline and no entropy or KL term above 64 symbols keeps the per_step
+    launches and bits above; every other call samples, collapses and scores as a multi-sample call and takes
+    ``pgasr_pg_step_coefs_multi`` (side stream, after the edit distance), ``pgasr_ctc_grad_from_lattice_multi_steps`` and
+    ``pgasr_pg_loss_value_multi_steps``; with leave one out no greedy arg-max runs.  Above 64 symbols K > 1, leave one out, entropy and
+    KL need wide_objectives=True as well.  beam > 0, score_function="sequence", reward_unit="word" and unit_spelling stay refused.
     ``reward_unit = "word"`` (opt-in): every reward above -- sample, hypothesis and the leave-one-out baselines -- is the word-level
     R = -WED(y, yhat) / W(y), words being the runs between ``word_delimiter`` tokens exactly as str.split(" ") cuts the decoded string
     (n delimiters give n + 1 words, empty ones included), WED the Levenshtein distance over the word lists and W(y) >= 1 the target's
@@ -145,6 +163,10 @@ class PGCTCLossFn(torch.autograd.Function):
         # Above 64 symbols the single-path gradient pass has no entropy or KL form: such a call samples, collapses and scores as a
         # single-path call does and takes the multi-sample pass and loss value with K = 1 (samples = sample[None], coef[None]).
         single_pass = single and not (V > hipops.MAX_VOCAB_NARROW and (beta > 0 or gamma > 0))
+        # step_objectives: per-step rewards of every configuration but the one the single-path per-step kernels were written for
+        # take the multi-sample family with (K,T,B) coefficients, K = 1 included
+        steps = opt.per_step and opt.step_objectives and not single_pass
+        single = single and not steps
         greedy_row = not loo and beam == 0      # the greedy path is sampled along and collapsed as row 0
         P = K + (0 if loo else 1)               # path sets that are collapsed and scored: [hypothesis,] sample 0 .. K-1
         inv_gb = 1.0 / float(opt.global_batch)
@@ -222,7 +244,12 @@ class PGCTCLossFn(torch.autograd.Function):
                                                                     reward_lengths=n_words)
                 if single:
                     R_s, coef = R_s[0], coef[0]
-            if opt.per_step:
+                elif steps and K == 1:
+                    R_s = R_s[0]
+            if steps:
+                coef = hipops.pg_step_coefs_multi(paths, in_len, prefix, tok_len.view(P * B), tg_len, K, opt.lam, inv_gb,
+                                                  baseline=opt.baseline, blank=blank)
+            elif opt.per_step:
                 coef = hipops.pg_step_coefs(paths, in_len, prefix, tok_len.view(2 * B), tg_len, opt.lam, inv_gb, blank=blank)
         nll, lattice = hipops.ctc_lattice(lp, targets, in_len, tg_len, blank=blank)
         main.wait_stream(side)
@@ -311,10 +338,11 @@ class PGOptions:
     entropy_weight: float = 0.0
     kl_weight: float = 0.0
     unit_spelling: object = None
+    step_objectives: bool = False
 
 
 def check_options(opt, vocab=None, frames=None, symbols=None, sample_ids=None, wide_check=True, wide_objectives=False,
-                  wide_sequence=False):
+                  wide_sequence=False, step_objectives=False):
     """The one check of a ``PGOptions`` -- by ``pg_ctc_loss`` per call, by ``PolicyGradientTrainer`` at construction and before
     every step --, made before any kernel runs and where the caller can read the reason.  vocab, frames (T) and symbols (the
     targets' row length) are checked against where they are known.  Returns the options with their integers as ints.
@@ -322,13 +350,18 @@ def check_options(opt, vocab=None, frames=None, symbols=None, sample_ids=None, w
     against the greedy hypothesis (``_check_wide``); wide_check=False leaves that rule to the caller (a trainer without
     ``wide_alphabet`` refuses such a model itself).  wide_objectives=True (opt-in) admits the multi-sample, leave-one-out, entropy
     and KL objectives for such an alphabet as well; at most 64 symbols it changes nothing.  wide_sequence=True (opt-in) admits
-    score_function="sequence" there (A13-WIDE), alone or with what wide_objectives=True admits; at most 64 symbols it changes nothing."""
+    score_function="sequence" there (A13-WIDE), alone or with what wide_objectives=True admits; at most 64 symbols it changes nothing.
+    step_objectives=True (opt-in, here or in ``opt``) admits per_step with num_samples 1..16, either baseline, entropy_weight, kl_weight
+    and the shard addressings (A12-STEP), and above 64 symbols per_step with K = 1, the greedy baseline and no tails -- K > 1, leave one
+    out, entropy and KL there need wide_objectives=True as well; beam, score_function="sequence", reward_unit="word" and unit_spelling
+    stay refused with per_step.  Without per_step it changes nothing."""
+    steps = bool(step_objectives) or bool(opt.step_objectives)
     _check_score(opt.score_function, opt.max_hyp_len, opt.per_step)
     if sample_ids is not None and opt.sample_base >= 0:
         raise ValueError("sample_ids and sample_base >= 0 are two addressings of the same draws: give one")
     if opt.per_step and opt.beam > 0:
         raise ValueError("per-step rewards need the frame-aligned greedy baseline (beam = 0)")
-    _check_samples(opt.num_samples, opt.baseline, opt.per_step)
+    _check_samples(opt.num_samples, opt.baseline, opt.per_step and not steps)
     if opt.unit_spelling is not None:
         _check_spelling(opt.unit_spelling, opt.reward_unit, opt.word_delimiter, opt.per_step, vocab=vocab)
     else:
@@ -337,8 +370,13 @@ def check_options(opt, vocab=None, frames=None, symbols=None, sample_ids=None, w
         raise ValueError(f"the word-level reward takes at most {hipops.WORD_MAX_STRIDE} frames and target symbols per utterance "
                          f"(pgasr_word_ids); got T = {frames}")
     if wide_check and vocab is not None and vocab > hipops.MAX_VOCAB_NARROW:
-        _check_wide(opt, vocab, wide_objectives=bool(wide_objectives), wide_sequence=bool(wide_sequence))
-    return dataclasses.replace(opt, num_samples=int(opt.num_samples),
+        try:
+            _check_wide(opt, vocab, wide_objectives=bool(wide_objectives), wide_sequence=bool(wide_sequence), step_objectives=steps)
+        except ValueError as e:
+            if not steps:
+                raise
+            raise ValueError(str(e).replace(", no per-step rewards", "")) from None      # they are what the keyword opens
+    return dataclasses.replace(opt, num_samples=int(opt.num_samples), step_objectives=steps,
                                max_hyp_len=None if opt.max_hyp_len is None else int(opt.max_hyp_len),
                                entropy_weight=check_entropy_weight(opt.entropy_weight), kl_weight=check_kl_weight(opt.kl_weight))
 
@@ -346,7 +384,7 @@ def check_options(opt, vocab=None, frames=None, symbols=None, sample_ids=None, w
 WIDE_OBJECTIVES = ("num_samples", "baseline", "entropy_weight", "kl_weight")      # what wide_objectives=True opens above 64 symbols
 
 
-def _check_wide(opt, vocab, wide_objectives=False, wide_sequence=False):
+def _check_wide(opt, vocab, wide_objectives=False, wide_sequence=False, step_objectives=False):
     """An alphabet of more than 64 symbols: the wide kernels cover log-softmax, arg-max / sample, the CTC lattice and its gradient
     pass with one sampled path -- the default objective.  Every other option runs kernels that hold one symbol per lane.
     wide_objectives=True (opt-in): the K-draw sampler, the entropy and KL statistics and the multi-sample gradient pass have wide
@@ -354,7 +392,9 @@ def _check_wide(opt, vocab, wide_objectives=False, wide_sequence=False):
     any combination; the beam reward search, the sequence score function, the word reward and per-step rewards stay refused.
     wide_sequence=True (opt-in): the hypothesis lattices and the gradient pass over K+1 lattices have wide forms (A13-WIDE), so
     score_function="sequence" (with max_hyp_len) is admitted -- with K = 1 against the greedy hypothesis, or with whatever
-    wide_objectives=True admits beside it; the beam reward search, the word reward and per-step rewards stay refused."""
+    wide_objectives=True admits beside it; the beam reward search, the word reward and per-step rewards stay refused.
+    step_objectives=True (opt-in): per-step rewards are admitted (A12-STEP) -- alone with K = 1, the greedy baseline and no tails, on
+    the single-path wide kernels; K > 1, leave one out, entropy and KL beside them need wide_objectives=True as well."""
     if vocab > hipops.MAX_VOCAB_WIDE:
         raise ValueError(f"alphabet of {vocab} symbols > {hipops.MAX_VOCAB_WIDE}: the wide kernels hold at most 16 symbols per lane")
     entropy, kl = check_entropy_weight(opt.entropy_weight), check_kl_weight(opt.kl_weight)
@@ -365,9 +405,14 @@ def _check_wide(opt, vocab, wide_objectives=False, wide_sequence=False):
                             ("entropy_weight", opt.entropy_weight, entropy == 0.0),
                             ("kl_weight", opt.kl_weight, kl == 0.0),
                             ("reward_unit", opt.reward_unit, opt.reward_unit == "char" or opt.unit_spelling is not None),
-                            ("per_step", opt.per_step, not opt.per_step)):
+                            ("per_step", opt.per_step, not opt.per_step or step_objectives)):
         if ok or (wide_objectives and name in WIDE_OBJECTIVES) or (wide_sequence and name == "score_function"):
             continue
+        if step_objectives and opt.per_step and name in WIDE_OBJECTIVES:
+            raise ValueError(f"{name}={given!r} with per-step rewards takes an alphabet of at most {hipops.MAX_VOCAB_NARROW} symbols (got "
+                             f"{vocab}): above the 64-symbol limit step_objectives=True alone opens per_step with num_samples=1, "
+                             f"baseline='hypothesis', entropy_weight=0 and kl_weight=0; num_samples 1..{hipops.MAX_SAMPLES}, "
+                             f"baseline='leave_one_out', entropy_weight and kl_weight need wide_objectives=True as well")
         if wide_sequence:
             rest = (f"wide_objectives=True opens num_samples 1..{hipops.MAX_SAMPLES}, baseline='leave_one_out', entropy_weight and "
                     f"kl_weight" if wide_objectives else
@@ -490,7 +535,7 @@ def _check_samples(num_samples, baseline, per_step=False):
 def pg_ctc_loss(logits, in_len, targets, tg_len, lam=1.0, seed=0, offset=0, global_batch=None, blank=0, beam=0, sample_base=-1,
                 per_step=False, log_probs=None, num_samples=1, baseline="hypothesis", reward_unit="char", word_delimiter=None,
                 sample_ids=None, score_function="path", max_hyp_len=None, entropy_weight=0.0, kl_weight=0.0, ref_log_probs=None,
-                wide_objectives=False, wide_sequence=False, unit_spelling=None):
+                wide_objectives=False, wide_sequence=False, unit_spelling=None, step_objectives=False):
     """beam > 0: the baseline reward comes from the prefix-beam-search hypothesis of that width (see PGCTCLossFn).
     num_samples / baseline: multi-sample REINFORCE (see PGCTCLossFn); with num_samples > 1 the third returned tensor is R_s (K,B).
     reward_unit: "char" (default) or "word" -- the word-level reward R = -WED / W(y) with words split at the token
@@ -511,17 +556,23 @@ def pg_ctc_loss(logits, in_len, targets, tg_len, lam=1.0, seed=0, offset=0, glob
     (default): off, the tensor is ignored and the call is as it was, so a schedule may anneal gamma to 0.  With every other option.
     wide_objectives: opt-in for an alphabet of 65 .. 1024 symbols -- num_samples 1..16, either baseline, entropy_weight and kl_weight
     then run there too, on the wide kernels of A12-WIDE (``_check_wide``); beam, score_function="sequence", reward_unit="word" and
-    per_step stay refused.  False (default) and at most 64 symbols: every call as it was.
+    per_step (without step_objectives) stay refused.  False (default) and at most 64 symbols: every call as it was.
     wide_sequence: opt-in for an alphabet of 65 .. 1024 symbols -- score_function="sequence" then runs there, on the wide kernels of
     A13-WIDE: K = 1 against the greedy hypothesis, or together with whatever wide_objectives=True admits.  Set max_hyp_len for unit
     models: the hypothesis lattices take 2 * K*B*T * roundup64(2*Lh+1) * 4 bytes (2.1 GB at K = 4, B = 32, T = 1000 with the
-    default cap).  beam, reward_unit="word" and per_step stay refused.  False (default) and at most 64 symbols: every call as it was.
+    default cap).  beam, reward_unit="word" and per_step (without step_objectives) stay refused.  False (default) and at most 64
+    symbols: every call as it was.
     unit_spelling: None (default: every call as it was) or the ``units.UnitSpelling`` of a subword alphabet -- the rewards are then
     counted on the spelled TEXT of targets and hypotheses (``pgasr_unit_spell`` on the side stream, between collapse and the distance):
     reward_unit="char" is R = -ED(chars) / max(C(y),1), "word" is R = -WED / W(y) with words split at the spelling's " " (no
     word_delimiter); utt_scale stays on the unit counts.  With every option the alphabet's size admits except per_step; above 64
     symbols it is what admits reward_unit="word".  Spelled rows are cut at 4094 characters; ``PGCTCLossFn.last_spell_truncated`` counts
     the rows cut (0-d int32 on the device, None after a call without a spelling).
+    step_objectives: opt-in for per_step beyond one sampled path -- num_samples 1..16, either baseline, entropy_weight, kl_weight,
+    sample_ids / sample_base / global_batch, and alphabets of 65 .. 1024 symbols (K = 1, the greedy baseline and no tails there; the
+    rest with wide_objectives=True as well): per-FRAME coefficients from the rewards-to-go of all K paths (see PGCTCLossFn, A12-STEP).
+    beam, score_function="sequence", reward_unit="word" and unit_spelling stay refused with per_step.  False (default), or without
+    per_step: every call, refusal and bit as it was.
     log_probs: log_softmax(logits) if the caller already has it (the head kernel's by-product, ``logits.log_probs`` of
     Seq2Seq.logits -- picked up from that attribute when not given)."""
     T, B, V = logits.shape
@@ -529,7 +580,7 @@ def pg_ctc_loss(logits, in_len, targets, tg_len, lam=1.0, seed=0, offset=0, glob
                                   blank=int(blank), beam=int(beam), sample_base=int(sample_base), per_step=bool(per_step),
                                   num_samples=num_samples, baseline=baseline, reward_unit=reward_unit, word_delimiter=word_delimiter,
                                   score_function=score_function, max_hyp_len=max_hyp_len, entropy_weight=entropy_weight,
-                                  kl_weight=kl_weight, unit_spelling=unit_spelling),
+                                  kl_weight=kl_weight, unit_spelling=unit_spelling, step_objectives=bool(step_objectives)),
                         vocab=V, frames=T, symbols=targets.shape[1] if targets.dim() == 2 else 0, sample_ids=sample_ids,
                         wide_objectives=wide_objectives, wide_sequence=wide_sequence)
     if log_probs is None:

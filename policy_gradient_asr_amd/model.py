@@ -244,7 +244,7 @@ def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset
           mwer_beam=16, init_from=None, kl_weight=0.0, kl_reference_path=None, mwer_lm_path=None, mwer_lm_alpha=0.0,
           mwer_lm_beta=0.0, target_rate=None, speed_perturb=None, noise_dir=None, rir_dir=None, snr_db=(5.0, 20.0), noise_prob=1.0,
           rir_prob=0.5, units_path=None, wide_alphabet=None, wide_objectives=None, wide_sequence=None,
-          mwer_unit_lm_path=None, spelled_reward=False):
+          mwer_unit_lm_path=None, spelled_reward=False, reward_mode="utterance", step_objectives=None):
     """Epoch loop of model.py:186-274 on the MI355X path: per-epoch train loss -> train_loss.npy,
     validation CTC loss -> val_losses.npy, model_best.pth / model_last.pth (state_dicts, reference
     names), plus checkpoint_last.pth (model + Adam moments + epoch) from which ``resume`` restarts
@@ -308,6 +308,12 @@ def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset
     64 symbols num_samples 1..16, either reward_baseline, entropy_weight and kl_weight (with init_from / kl_reference_path) run on
     the wide kernels too; the word reward and score_function="sequence" stay refused there.  Needs wide_alphabet; kept in the
     checkpoint beside it.
+    reward_mode: "utterance" (default: one reward per utterance) or "per_step" -- the reward-to-go of every frame in the REINFORCE
+    term (PolicyGradientTrainer(reward_mode=)); alone it takes num_samples=1 with the hypothesis baseline and at most 64 symbols;
+    objective="mwer" does not take it.
+    step_objectives: None / False (default) or True -- PolicyGradientTrainer(step_objectives=True): reward_mode="per_step" then runs
+    with num_samples 1..16, either reward_baseline, entropy_weight and kl_weight, and with wide_alphabet (above 64 symbols K > 1, leave
+    one out, entropy and KL need wide_objectives as well).  Kept in the checkpoint beside wide_objectives and checked on resume.
     wide_sequence: None (default: False, or what the checkpoint of a resumed run holds) or a bool -- with more than 64 symbols,
     objective="mwer" (mwer_nbest <= 16, mwer_beam <= 128, reward_unit="char"; mwer.MWERTrainer(wide_sequence=True)) and
     score_function="sequence" (PolicyGradientTrainer(wide_sequence=True)) run on the wide kernels too.  Set max_hyp_len for unit
@@ -372,6 +378,9 @@ def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset
     wide_objectives = bool(wide_objectives)
     if wide_objectives and not wide_alphabet:
         raise ValueError("wide_objectives=True opens objectives for alphabets of more than 64 symbols: it needs wide_alphabet")
+    step_objectives = bool(step_objectives)
+    if reward_mode not in ("utterance", "per_step"):
+        raise ValueError("reward_mode must be 'utterance' or 'per_step'")
     word_delimiter = None
     spelling = {}
     if spelled_reward:
@@ -416,7 +425,8 @@ def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset
         trainer = MWERTrainer(model, lr=lr, lam=lam, seed=seed, precision=precision, max_grad_norm=max_grad_norm,
                               beam_size=mwer_beam, nbest=mwer_nbest, risk_unit=reward_unit, word_delimiter=word_delimiter,
                               max_hyp_len=max_hyp_len, num_samples=num_samples, reward_baseline=reward_baseline,
-                              score_function=score_function, entropy_weight=entropy_weight, **mwer_lm, **spelling)
+                              score_function=score_function, entropy_weight=entropy_weight,
+                              **({"reward_mode": reward_mode} if reward_mode != "utterance" else {}), **mwer_lm, **spelling)
     else:
         kl = {}
         if kl_weight > 0:
@@ -429,7 +439,9 @@ def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset
                                         max_grad_norm=max_grad_norm, score_function=score_function, max_hyp_len=max_hyp_len,
                                         entropy_weight=entropy_weight, **kl, **({"wide_alphabet": True} if wide_alphabet else {}),
                                         **({"wide_objectives": True} if wide_objectives else {}),
-                                        **({"wide_sequence": True} if wide_sequence else {}), **spelling)
+                                        **({"wide_sequence": True} if wide_sequence else {}),
+                                        **({"reward_mode": reward_mode} if reward_mode != "utterance" else {}),
+                                        **({"step_objectives": True} if step_objectives else {}), **spelling)
     losses, val_losses, best, start_epoch = [], [], 9999999.0, 1
     ckpt = os.path.join(model_path, "checkpoint_last.pth")
     resuming = resume and os.path.exists(ckpt)
@@ -453,6 +465,7 @@ def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset
                         ("max_hyp_len", max_hyp_len), ("entropy_weight", entropy_weight), ("kl_weight", kl_weight),
                         ("kl_reference_path", kl_reference_path), ("target_rate", target_rate),
                         ("units_path", units_path), ("wide_alphabet", wide_alphabet), ("wide_objectives", wide_objectives),
+                        ("reward_mode", reward_mode), ("step_objectives", step_objectives),
                         ("wide_sequence", wide_sequence), ("spelled_reward", bool(spelled_reward)),
                         ("speed_perturb", None if speed_perturb is None else speed_perturb.state()),
                         ("wave_augment", None if wave_augment is None else wave_augment.state())):
@@ -543,6 +556,7 @@ def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset
                     "score_function": score_function, "max_hyp_len": max_hyp_len, "entropy_weight": trainer.entropy_weight,
                     "kl_weight": kl_weight, "kl_reference_path": kl_reference_path, "target_rate": target_rate,
                     "units_path": units_path, "wide_alphabet": wide_alphabet, "wide_objectives": wide_objectives, "wide_sequence": wide_sequence,
+                    "reward_mode": reward_mode, "step_objectives": step_objectives,
                     "spelled_reward": bool(spelled_reward),
                     "speed_perturb": None if speed_perturb is None else speed_perturb.state(),
                     "wave_augment": None if wave_augment is None else wave_augment.state()}, ckpt)

@@ -448,19 +448,19 @@ class PolicyGradientTrainer(DataParallelStep):
                  reward_decoder="greedy", beam_size=16, precision=None, reward_mode="utterance", num_samples=1,
                  reward_baseline="hypothesis", reward_unit="char", word_delimiter=None, max_grad_norm=None,
                  score_function="path", max_hyp_len=None, entropy_weight=0.0, kl_weight=0.0, kl_reference=None, wide_alphabet=False,
-                 wide_objectives=False, wide_sequence=False, unit_spelling=None):
+                 wide_objectives=False, wide_sequence=False, unit_spelling=None, step_objectives=False):
         """wide_alphabet: opt in to alphabets of 65 .. 1024 symbols (subword units).  MAX_VOCAB becomes 1024, and such a model takes
         the default objective alone: reward_decoder="greedy", reward_mode="utterance", num_samples=1, reward_baseline="hypothesis",
         reward_unit="char", score_function="path", entropy_weight=0, kl_weight=0 -- anything else raises here and before every
         step (loss.check_options).  False (default): a model of more than 64 symbols is refused by ``step`` as ever.
         wide_objectives: with wide_alphabet=True (else ValueError), opt in to num_samples 1 .. MAX_SAMPLES, either reward_baseline,
         entropy_weight and kl_weight / kl_reference for such a model too, in any combination, on the wide kernels of A12-WIDE;
-        reward_decoder="beam", reward_mode="per_step", reward_unit="word" and score_function="sequence" stay refused there.  The
-        default objective keeps its launches and bits with or without it.
+        reward_decoder="beam", reward_mode="per_step" (without step_objectives), reward_unit="word" and score_function="sequence" stay
+        refused there.  The default objective keeps its launches and bits with or without it.
         wide_sequence: with wide_alphabet=True (else ValueError), opt in to score_function="sequence" for such a model, on the wide
         kernels of A13-WIDE: num_samples=1 against the greedy hypothesis, or together with whatever wide_objectives=True admits.  Set
         max_hyp_len for unit models (the workspace formula below: 2.1 GB at K = 4, B = 32, T = 1000 with the default cap).
-        reward_decoder="beam", reward_mode="per_step" and reward_unit="word" stay refused there.
+        reward_decoder="beam", reward_mode="per_step" (without step_objectives) and reward_unit="word" stay refused there.
         reward_mode: "utterance" (default) -- one reward R = -ED / |y| per utterance, the sum of the reference's per-step rewards
         (policy_grad.py:10-15) up to a constant the baseline removes; "per_step" -- the per-step rewards themselves, as rewards-to-go
         per frame against the greedy path's reward-to-go at the same frame (loss.PGCTCLossFn; greedy baseline only).
@@ -501,7 +501,14 @@ class PolicyGradientTrainer(DataParallelStep):
         counted on the spelled TEXT -- reward_unit="char" its characters, "word" its words, split at the spelling's " " (give no
         word_delimiter) -- with every setting the alphabet's size admits except reward_mode="per_step"; above 64 symbols it is what
         admits reward_unit="word" (loss.PGCTCLossFn).  ``last_spell_truncated``: how many rows of the last step were cut at the
-        4094-character row limit, a 0-d int32 on the device (None without a spelling); nothing synchronises until it is read."""
+        4094-character row limit, a 0-d int32 on the device (None without a spelling); nothing synchronises until it is read.
+        step_objectives: False (default: the step, and every refusal, as it was) or True -- reward_mode="per_step" then takes
+        num_samples 1 .. MAX_SAMPLES, either reward_baseline, entropy_weight, kl_weight, shards and micro-batches: per-FRAME
+        coefficients from the rewards-to-go of all K sampled paths against the greedy path's or the other samples' at the same frame
+        (loss.PGCTCLossFn, A12-STEP).  With wide_alphabet=True it admits per_step above 64 symbols with num_samples=1, the hypothesis
+        baseline and no entropy or KL term; the rest there needs wide_objectives=True as well.  reward_decoder="beam",
+        score_function="sequence", reward_unit="word" and unit_spelling stay refused with reward_mode="per_step"; with
+        reward_mode="utterance" the keyword changes nothing."""
         from .loss import check_kl_weight
         kl_weight = check_kl_weight(kl_weight)
         if isinstance(kl_reference, str):
@@ -516,6 +523,7 @@ class PolicyGradientTrainer(DataParallelStep):
         self.wide_objectives = bool(wide_objectives)
         if self.wide_objectives and not self.wide_alphabet:
             raise ValueError("wide_objectives=True opens objectives for alphabets of more than 64 symbols: it needs wide_alphabet=True")
+        self.step_objectives = bool(step_objectives)
         self.wide_sequence = bool(wide_sequence)
         if self.wide_sequence and not self.wide_alphabet:
             raise ValueError("wide_sequence=True opens the sequence-level objectives for alphabets of more than 64 symbols: it needs "
@@ -627,7 +635,8 @@ class PolicyGradientTrainer(DataParallelStep):
                         kl_weight=self.kl_weight, unit_spelling=getattr(self, "unit_spelling", None))
         return check_options(opt, vocab=vocab, frames=frames, symbols=symbols, wide_check=self.wide_alphabet,
                              wide_objectives=getattr(self, "wide_objectives", False),
-                             wide_sequence=getattr(self, "wide_sequence", False))
+                             wide_sequence=getattr(self, "wide_sequence", False),
+                             step_objectives=getattr(self, "step_objectives", False))
 
     def _check_limits(self, x, targets):
         """The kernels' compiled-in limits, stated where the caller can read them (otherwise the first symptom is a
@@ -740,6 +749,7 @@ class PolicyGradientTrainer(DataParallelStep):
                                           entropy_weight=self.entropy_weight, **kl,
                                           **({"wide_objectives": True} if self.wide_objectives else {}),
                                           **({"wide_sequence": True} if self.wide_sequence else {}),
+                                          **({"step_objectives": True} if self.step_objectives else {}),
                                           **({"unit_spelling": self.unit_spelling} if self.unit_spelling is not None else {}))
         self.last_spell_truncated = PGCTCLossFn.last_spell_truncated      # 0-d int32, None without a spelling
         scored = PGCTCLossFn.last_sequence_scored                # (K,B) bool, None with score_function="path"
