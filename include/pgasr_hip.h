@@ -977,6 +977,60 @@ int pgasr_nbest_unit_lm_score(const int32_t* tokens, int tok_stride, const int32
                               void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * A7-BIAS  Hotword (contextual phrase) biasing: the A7 / A7-LM / A7-NBEST search with a weighted automaton over the token rows, and the
+ * automaton's score of every hypothesis of an N-best list (csrc/beam.hip BIAS = true, csrc/hotword.hip; the builder and the host
+ * statement of the query: lm.HotwordBias).
+ * The meaning.  For a list of phrases p (token-id rows without the blank) with weights w(p), the bias of a token row y is
+ *     B(y) = sum_p (occurrences of p in y, overlapping ones included) * w(p)
+ *            + partial * boost * (length of the longest suffix of y that is a PROPER prefix of some phrase);
+ *   the second term is pending credit: it rewards a hypothesis for being on the way into a phrase and is taken back by the transition
+ *   that leaves the phrase.
+ * bias_table: S * V 8-byte little-endian words {int32 next; float32 bonus} on the device, word (q, s) at q * V + s: the Aho-Corasick
+ *   machine of the phrase trie (state 0 the root, states in breadth-first order, children in symbol order; dense goto with the failure
+ *   links resolved), bonus[q, s] = out(next) + pend(next) - pend(q) formed in fp64 and rounded once to fp32, so that the sum of the
+ *   bonuses along y is B(y).  The blank's column is next = q, bonus = 0.  bias_states = S >= 1; S * V <= 2^24 words (128 MiB).  A next
+ *   outside [0, S) read from the table is taken as state 0: no table content gives an address outside the S * V words.
+ * pgasr_ctc_beam_search_bias / pgasr_ctc_beam_search_nbest_bias: the arguments of pgasr_ctc_beam_search_lm / _nbest, then the table,
+ *   S and bias_weight.  A7-LM's algebra line for line.  An entry carries bst = the state of its prefix (a stay inherits it, an
+ *   extension by s takes next[bst_j V + s]) and bwi = bst(parent prefix) V + last, the word of its own last emission, which is the
+ *   merged term of its stay candidate (parent i extended by last(j)).  Every term that enters a prefix by an extension with a
+ *   non-blank s gets w added, with these roundings, for fp32 and fp64 log_probs alike:
+ *       wb = __dmul_rn(bias_weight, (double)bonus);
+ *       with a language model  w = __dadd_rn(__dadd_rn(__dmul_rn(lm_alpha, (double)lm_word), lm_beta), wb);   without  w = wb;
+ *       then (p_b + p) + w and (p_nb + p) + w.
+ *   The blank update and the repeat branch that keeps the prefix are unchanged; candidate order, first-touch ties and the sort are
+ *   A7's; out_score is a FUSED score.  bias_weight = 0 returns the words of the same kernel without a table bit for bit.
+ *   With a table every call takes the workgroup-per-utterance kernel (fp64 input: exact math; fp32: fp32 exp/log on differences),
+ *   and every (beam, V) that kernel accepts without a table it accepts with one.  flags bits 3 and 4 (the single-wave kernel) with a
+ *   table -> PGASR_ERR_UNSUPPORTED: the call is refused, never run differently.
+ *   bias_table == NULL and bias_states == 0: exactly pgasr_ctc_beam_search_lm / pgasr_ctc_beam_search_nbest, every dispatch included.
+ *   Checked before any HIP call, behind the language model's checks: a NULL table with bias_states != 0, a table with bias_states < 1,
+ *   bias_states * V > 2^24, a bias_weight that is not finite -> PGASR_ERR_INVALID_ARG; then the flag refusal above.
+ * pgasr_nbest_bias_score: tokens (N, B, tok_stride) int32, len (N, B), count (B): a list as pgasr_ctc_beam_search_nbest or
+ *   pgasr_ctc_beam_search_wide writes it (len is clamped to [0, tok_stride], count to [0, N]).  For n < count[b]:
+ *     out[n, b] fp64 = sum_i (double)bonus[q_i, y_i], q_0 = 0, q_{i+1} = next[q_i, y_i], one addition per token in index order;
+ *   a token outside [0, V) leaves state and sum unchanged (and so does the blank, by its column).  Rows n >= count[b]: 0.
+ *   N <= 128, V <= 1024, else PGASR_ERR_UNSUPPORTED; a NULL pointer, B < 1, tok_stride < 1, V < 1, bias_states < 1, bias_states * V >
+ *   2^24 -> PGASR_ERR_INVALID_ARG; all before any HIP call.  One launch, one lane per hypothesis with its tokens staged ahead of the
+ *   state chain, no workspace, no host synchronisation.  Totals and ranks: pgasr_nbest_combine_rank with word_logp = out,
+ *   word_alpha = bias_weight, word_beta = 0.
+ * ---------------------------------------------------------------------------------------- */
+int pgasr_ctc_beam_search_bias(const void* log_probs, int is_f64, long long stride_t, long long stride_b,
+                               const int32_t* lengths, int T, int B, int V, int beam, int blank, int flags,
+                               int32_t* out_tokens, int32_t* out_len, double* out_score,
+                               void* workspace, size_t workspace_bytes, void* stream,
+                               const float* lm_table, int lm_order, double lm_alpha, double lm_beta,
+                               const void* bias_table, int bias_states, double bias_weight);
+int pgasr_ctc_beam_search_nbest_bias(const void* log_probs, int is_f64, long long stride_t, long long stride_b,
+                                     const int32_t* lengths, int T, int B, int V, int beam, int blank, int flags,
+                                     int nbest, int32_t* out_tokens, int tok_stride, int32_t* out_len, double* out_score,
+                                     int32_t* out_count, void* workspace, size_t workspace_bytes, void* stream,
+                                     const float* lm_table, int lm_order, double lm_alpha, double lm_beta,
+                                     const void* bias_table, int bias_states, double bias_weight);
+int pgasr_nbest_bias_score(const int32_t* tokens, const int32_t* len, const int32_t* count, int N, int B, int tok_stride, int V,
+                           const void* bias_table, int bias_states, double* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * A7-RESCORE Second pass over N-best lists: an n-gram LM score of every hypothesis, a weighted total and its rank.
  *   tokens (N, B, tok_stride) int32, len (N, B), count (B): a list as pgasr_ctc_beam_search_nbest writes it (len is clamped to
  *   [0, tok_stride], count to [0, N]); am (N, B) fp64: the caller's acoustic score, lower is better.

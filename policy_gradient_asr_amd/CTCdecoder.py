@@ -6,7 +6,9 @@ as a HIP kernel (csrc/beam.hip).  ``greedy_decode`` is the best-path decoder the
 likelihood of lists of more than 16 rows or more than 64 symbols from the lattice-free scorer, csrc/hyp_score.hip; with
 ``word_lm=`` a word n-gram LM on top, csrc/word_lm.hip; with ``unit_lm=`` a back-off LM over the units themselves, csrc/unit_lm.hip);
 ``CTCDecoder.mbr_decode`` returns the hypothesis of least expected edit distance under the list's posterior instead of the best-scored
-one (minimum-Bayes-risk decoding, csrc/mbr.hip)."""
+one (minimum-Bayes-risk decoding, csrc/mbr.hip); ``CTCDecoder(hotwords=...)`` biases the search towards a list of phrases (contextual
+biasing with a weighted automaton, ``lm.HotwordBias``; csrc/beam.hip BIAS = true) and ``rescore(bias=...)`` applies the same bias to a list
+in the second pass (csrc/hotword.hip), which is how lists of subword units get it."""
 import collections
 
 import numpy as np
@@ -40,11 +42,18 @@ NBestRescored = collections.namedtuple("NBestRescored", "order total am lm_logp 
 NBestRescoredWords = collections.namedtuple("NBestRescoredWords", NBestRescored._fields + ("word_logp", "n_words", "n_oov"))
 NBestRescoredUnits = collections.namedtuple("NBestRescoredUnits", NBestRescored._fields + ("unit_logp",))
 NBestRescoredWordsUnits = collections.namedtuple("NBestRescoredWordsUnits", NBestRescoredWords._fields + ("unit_logp",))
+
+
+def _with_bias(res, bias_score):
+    """``res`` with one more field at its end: bias (N,B) float64, B(y) of every hypothesis."""
+    cls = collections.namedtuple(type(res).__name__ + "Bias", type(res)._fields + ("bias",))
+    return cls(*res, bias_score)
 MBRDecoded = collections.namedtuple("MBRDecoded", "tokens lengths best risk posterior dist nbest")
 
 
 class CTCDecoder:
-    def __init__(self, alphabet, device=None, lm=None, lm_alpha=0.0, lm_beta=0.0, fast_lm=False, wide_search=False, unit_lm=None):
+    def __init__(self, alphabet, device=None, lm=None, lm_alpha=0.0, lm_beta=0.0, fast_lm=False, wide_search=False, unit_lm=None,
+                 hotwords=None, hotword_weight=1.0):
         """lm: None (default: the acoustic search of the reference) or a ``lm.CharNgramLM``; every extension of a prefix by a
         non-blank symbol s then gets ``lm_alpha * ln p_lm(s | last order-1 symbols) + lm_beta`` added (Hannun/Maas,
         arXiv:1408.2873 -- the place CTCdecoder.py:90-96 marks for an LM score).  ``decode`` / ``decode_batch`` use these values
@@ -59,7 +68,14 @@ class CTCDecoder:
         unit_lm: None or a ``lm.UnitNgramLM`` (a sparse back-off model over the units themselves, up to 1024 symbols), fused into the
         wide search with ``lm_alpha`` / ``lm_beta`` as ``lm`` is into the narrow one (``hipops.ctc_beam_search_wide(unit_lm=)``).  It
         needs ``wide_search=True`` and excludes ``lm``; rows of at most 64 symbols then take the wide entry too.  A model whose
-        vocabulary or blank differs from a call's raises."""
+        vocabulary or blank differs from a call's raises.
+        hotwords: None (default: every call is the call it was) or a ``lm.HotwordBias``, or a list of strings compiled with this
+        decoder's alphabet and blank 0 (``HotwordBias.from_strings``): ``decode`` / ``decode_batch`` and their ``nbest=`` forms then add
+        ``hotword_weight * bonus`` to every extension on the way into or through a phrase (``hipops.ctc_beam_search(bias=)``), with or
+        without ``lm``, and their scores are FUSED scores.  ``set_hotwords(hotwords, weight)`` changes the list later.  The biased
+        search is the workgroup kernel's: fast_lm=True with hotwords raises, and so do rows of more than 64 symbols and ``unit_lm`` --
+        the wide search has no bias; bias its lists in the second pass, ``rescore(bias=)``.  A bias whose vocabulary or blank differs
+        from a call's raises."""
         if unit_lm is not None and lm is not None:
             raise ValueError("unit_lm: not together with lm -- one first-pass language model")
         if unit_lm is not None and not wide_search:
@@ -71,6 +87,40 @@ class CTCDecoder:
         self.lm, self.lm_alpha, self.lm_beta = lm, float(lm_alpha), float(lm_beta)
         self.fast_lm = bool(fast_lm)
         self.wide_search = bool(wide_search)
+        self.hotwords, self.hotword_weight = None, 1.0
+        self.set_hotwords(hotwords, hotword_weight)
+
+    def set_hotwords(self, hotwords, weight=1.0):
+        """The decoder's hotword list from now on: None, a ``lm.HotwordBias`` or a list of strings (see the constructor)."""
+        from .lm import HotwordBias
+        if hotwords is not None:
+            if self.fast_lm:
+                raise ValueError("fast_lm: the single-wave kernel has no hotword bias; give fast_lm=False with hotwords")
+            if self.unit_lm is not None:
+                raise ValueError("hotwords: the wide search has no hotword bias (unit_lm is fused into it); bias its lists in the "
+                                 "second pass, rescore(bias=)")
+            if not isinstance(hotwords, HotwordBias):
+                if isinstance(hotwords, str):
+                    raise ValueError("hotwords: a list of strings or a lm.HotwordBias, not one string")
+                hotwords = HotwordBias.from_strings(list(hotwords), self.alphabet, blank=0)
+        weight = float(weight)
+        if weight != weight or weight in (float("inf"), -float("inf")):
+            raise ValueError("hotword_weight must be finite")
+        self.hotwords, self.hotword_weight = hotwords, weight
+
+    def _bias_args(self, V, blank, wide, fast_lm=False):
+        """The bias keywords of the narrow entries; refuses what no kernel does.  Touches no device."""
+        if self.hotwords is None:
+            return {}
+        if wide:
+            raise ValueError(f"hotwords: the wide beam search ({V} symbols) has no hotword bias; bias its lists in the second pass, "
+                             f"rescore(bias=)")
+        if fast_lm:
+            raise ValueError("fast_lm: the single-wave kernel has no hotword bias; give fast_lm=False with hotwords")
+        if self.hotwords.vocab != V or self.hotwords.blank != int(blank):
+            raise ValueError(f"hotwords: the bias is over {self.hotwords.vocab} symbols with blank {self.hotwords.blank}; the call has "
+                             f"{V} symbols and blank {int(blank)}")
+        return {"bias": self.hotwords, "bias_weight": self.hotword_weight}
 
     def _takes_wide(self, V, args, blank=0):
         """Whether rows of V symbols go to the wide search; refuses what neither search takes.  Touches no device."""
@@ -117,10 +167,14 @@ class CTCDecoder:
         args = self._lm_args(lm, lm_alpha, lm_beta)
         if self.wide_search:                                 # refused before a device is asked for
             self._takes_wide(np.shape(probs)[-1], args, blank)
+        if self.hotwords is not None:                        # likewise
+            V0 = np.shape(probs)[-1]
+            self._bias_args(V0, blank, self._takes_wide(V0, args, blank))
         dev = _device(self.device)
         probs = np.asarray(probs)
         T, V = probs.shape
         wide = self._takes_wide(V, args, blank)
+        args.update(self._bias_args(V, blank, wide))
         if T == 0:
             return (tuple(), -0.0) if nbest is None else [(tuple(), -0.0)]
         with np.errstate(divide="ignore"):
@@ -152,6 +206,9 @@ class CTCDecoder:
         fast_lm: None (default: the decoder's own) or a bool -- with an LM, take the single-wave kernel where its limits allow."""
         fast_lm = self.fast_lm if fast_lm is None else bool(fast_lm)
         args = self._lm_args(lm, lm_alpha, lm_beta)
+        if self.hotwords is not None:
+            bias_args = self._bias_args(log_probs.shape[-1], blank, self._takes_wide(log_probs.shape[-1], args, blank), fast_lm)
+            args.update(bias_args)
         if self._takes_wide(log_probs.shape[-1], args, blank):
             return hipops.ctc_beam_search_wide(log_probs, lengths, beam=int(beam_size), blank=int(blank),
                                                nbest=None if nbest is None else int(nbest), **self._wide_lm(args))
@@ -170,7 +227,7 @@ class CTCDecoder:
 
     def rescore(self, log_probs, lengths, nb, lm=_UNSET, lm_alpha=None, lm_beta=None, acoustic="ctc", am_weight=1.0, max_hyp_len=None,
                 blank=0, word_lm=None, word_lm_alpha=0.0, word_lm_beta=0.0, word_delimiter=None, scorer=None, unit_lm=None,
-                unit_lm_alpha=0.0, unit_lm_beta=0.0):
+                unit_lm_alpha=0.0, unit_lm_beta=0.0, bias=None, bias_weight=0.0):
         """Second pass over an N-best list ``nb`` (``hipops.CTCNBest`` of ``decode_batch(..., nbest=N)`` on the same log_probs
         (T,B,V) / lengths), N <= 128:  total = am_weight * am - lm_alpha * lm_logp - lm_beta * length, lower is better, with
         lm_logp the hypothesis' log-probability under ``lm`` (the decoder's own unless given; None: no LM term).
@@ -205,9 +262,22 @@ class CTCDecoder:
             launch pair: total = base - unit_lm_alpha * unit_logp - unit_lm_beta * length, with unit_logp the hypothesis'
             ``logp_sequence`` (``hipops.nbest_unit_lm_score``) and the roundings of the formula above
             (``hipops.nbest_combine_rank``); a word LM, if any, comes on top of that.  The result carries one more field, unit_logp
-            (N,B) float64 (``NBestRescoredUnits`` / ``NBestRescoredWordsUnits``).  No further host synchronisation."""
+            (N,B) float64 (``NBestRescoredUnits`` / ``NBestRescoredWordsUnits``).  No further host synchronisation.
+        bias: None (default: everything above, nothing else) or a ``lm.HotwordBias`` over the list's V symbols and ``blank`` -- narrow
+            and wide lists alike, which is how lists of subword units are biased.  It comes last: total = total - bias_weight * B(y),
+            with B(y) the hypothesis' ``score_sequence`` (``hipops.nbest_bias_score``) and the roundings of
+            ``hipops.nbest_combine_rank`` on the earlier total.  The result carries one more field at its end, bias (N,B) float64
+            (the result's type with "Bias" behind its name).  No further host synchronisation.  With acoustic="first_pass" after a
+            search that was itself biased, am already holds the first pass' bonuses: the bias is then added on top of them."""
         if unit_lm is not None:
             hipops._unit_lm_check(unit_lm, log_probs.shape[-1], blank)
+        if bias is not None:
+            from .lm import HotwordBias
+            if not isinstance(bias, HotwordBias):
+                raise ValueError("bias: a lm.HotwordBias is wanted (never raw tensors)")
+            if bias.vocab != log_probs.shape[-1] or bias.blank != int(blank):
+                raise ValueError(f"bias: the hotwords are over {bias.vocab} symbols with blank {bias.blank}; the list has "
+                                 f"{log_probs.shape[-1]} symbols and blank {int(blank)}")
         if acoustic not in ("ctc", "first_pass"):
             raise ValueError(f"acoustic must be 'ctc' or 'first_pass' (got {acoustic!r})")
         if scorer not in (None, "lattice", "forward"):
@@ -264,14 +334,20 @@ class CTCDecoder:
             word_logp, n_words, n_oov = hipops.nbest_word_lm_score(nb.tokens, nb.lengths, nb.count, word_lm, delim)
             order, total = hipops.nbest_combine_rank(total, word_logp, n_words, nb.count, word_alpha=float(word_lm_alpha),
                                                      word_beta=float(word_lm_beta))
+        if bias is not None:
+            bias_score = hipops.nbest_bias_score(nb.tokens, nb.lengths, nb.count, bias)
+            order, total = hipops.nbest_combine_rank(total, bias_score, torch.zeros_like(nb.lengths), nb.count,
+                                                     word_alpha=float(bias_weight), word_beta=0.0)
         first = order[:, 0].long()
         cols = torch.arange(B, device=order.device)
         best = (nb.tokens[first, cols].contiguous(), nb.lengths[first, cols].contiguous())
         if word_lm is not None:
             res = NBestRescoredWords(order, total, am, lm_logp, best[0], best[1], skipped, word_logp, n_words, n_oov)
-            return res if unit_lm is None else NBestRescoredWordsUnits(*res, unit_logp)
-        res = NBestRescored(order, total, am, lm_logp, best[0], best[1], skipped)
-        return res if unit_lm is None else NBestRescoredUnits(*res, unit_logp)
+            res = res if unit_lm is None else NBestRescoredWordsUnits(*res, unit_logp)
+        else:
+            res = NBestRescored(order, total, am, lm_logp, best[0], best[1], skipped)
+            res = res if unit_lm is None else NBestRescoredUnits(*res, unit_logp)
+        return res if bias is None else _with_bias(res, bias_score)
 
     def mbr_from_list(self, nb, score, vocab=None, risk_unit="char", word_delimiter=None, posterior_scale=1.0, max_hyp_len=None,
                       unit_spelling=None):
@@ -313,7 +389,7 @@ class CTCDecoder:
     def mbr_decode(self, log_probs, lengths=None, beam_size=16, nbest=16, risk_unit="char", word_delimiter=None, acoustic="ctc",
                    posterior_scale=1.0, lm=_UNSET, lm_alpha=None, lm_beta=None, am_weight=1.0, max_hyp_len=None, blank=0,
                    word_lm=None, word_lm_alpha=0.0, word_lm_beta=0.0, unit_lm=None, unit_lm_alpha=0.0, unit_lm_beta=0.0,
-                   unit_spelling=None):
+                   unit_spelling=None, bias=None, bias_weight=0.0):
         """Minimum-Bayes-risk decoding: the N-best search (``decode_batch(nbest=)``, with the decoder's first-pass LM if it has
         one), the score of every hypothesis (``rescore(...).total`` with ``acoustic`` / ``lm`` / ``lm_alpha`` / ``lm_beta`` /
         ``am_weight`` as ``rescore`` takes them: without an LM the exact CTC -log p, or the first-pass score), the distances inside
@@ -322,13 +398,13 @@ class CTCDecoder:
         posterior then comes from the totals with the word LM in them; unit_lm / unit_lm_alpha / unit_lm_beta likewise (a
         ``lm.UnitNgramLM`` in the second pass, wide lists included).  unit_spelling: the risk over the spelled text of a list of
         subword units (``mbr_from_list``; max_hyp_len keeps capping the unit rows, the spelled rows by that many units' longest
-        spelling).  Returns ``MBRDecoded``."""
+        spelling).  bias / bias_weight go to ``rescore`` (a ``lm.HotwordBias`` in the second pass).  Returns ``MBRDecoded``."""
         T, B, V = log_probs.shape
         nb = self.decode_batch(log_probs, lengths, beam_size=beam_size, blank=blank, nbest=int(nbest))
         rs = self.rescore(log_probs, lengths, nb, lm=lm, lm_alpha=lm_alpha, lm_beta=lm_beta, acoustic=acoustic, am_weight=am_weight,
                           max_hyp_len=max_hyp_len, blank=blank, word_lm=word_lm, word_lm_alpha=word_lm_alpha,
                           word_lm_beta=word_lm_beta, word_delimiter=word_delimiter, unit_lm=unit_lm, unit_lm_alpha=unit_lm_alpha,
-                          unit_lm_beta=unit_lm_beta)
+                          unit_lm_beta=unit_lm_beta, **({} if bias is None else {"bias": bias, "bias_weight": bias_weight}))
         if unit_spelling is not None:
             cap = None if max_hyp_len is None else int(max_hyp_len) * unit_spelling.max_unit_chars
             return self.mbr_from_list(nb, rs.total, vocab=V, risk_unit=risk_unit, word_delimiter=word_delimiter,

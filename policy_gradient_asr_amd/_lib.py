@@ -103,6 +103,14 @@ SIGNATURES = {
     "pgasr_ctc_beam_search_nbest": (C.c_int, [c_ptr, C.c_int, C.c_longlong, C.c_longlong, c_i32p, C.c_int, C.c_int, C.c_int,
                                               C.c_int, C.c_int, C.c_int, C.c_int, c_i32p, C.c_int, c_i32p, c_ptr, c_i32p,
                                               c_ptr, C.c_size_t, c_ptr, c_f32p, C.c_int, C.c_double, C.c_double]),
+    "pgasr_ctc_beam_search_bias": (C.c_int, [c_ptr, C.c_int, C.c_longlong, C.c_longlong, c_i32p, C.c_int, C.c_int, C.c_int,
+                                             C.c_int, C.c_int, C.c_int, c_i32p, c_i32p, c_ptr, c_ptr, C.c_size_t, c_ptr,
+                                             c_f32p, C.c_int, C.c_double, C.c_double, c_ptr, C.c_int, C.c_double]),
+    "pgasr_ctc_beam_search_nbest_bias": (C.c_int, [c_ptr, C.c_int, C.c_longlong, C.c_longlong, c_i32p, C.c_int, C.c_int, C.c_int,
+                                                   C.c_int, C.c_int, C.c_int, C.c_int, c_i32p, C.c_int, c_i32p, c_ptr, c_i32p,
+                                                   c_ptr, C.c_size_t, c_ptr, c_f32p, C.c_int, C.c_double, C.c_double,
+                                                   c_ptr, C.c_int, C.c_double]),
+    "pgasr_nbest_bias_score": (C.c_int, [c_i32p, c_i32p, c_i32p, C.c_int, C.c_int, C.c_int, C.c_int, c_ptr, C.c_int, c_ptr, c_ptr]),
     "pgasr_beam_wide_workspace_bytes": (C.c_size_t, [C.c_int] * 4),
     "pgasr_ctc_beam_search_wide": (C.c_int, [c_ptr, C.c_int, C.c_longlong, C.c_longlong, c_i32p, C.c_int, C.c_int, C.c_int,
                                              C.c_int, C.c_int, C.c_int, C.c_int, c_i32p, C.c_int, c_i32p, c_ptr, c_i32p, c_i32p,

@@ -63,11 +63,35 @@ template <bool LM> struct BeamNbest : BeamLm<LM> {
     int32_t* out_count;      // (B) min(nbest, entries of the final beam)
 };
 
-template <typename TIn, bool FAST, bool LM, bool NBEST = false>
+// Hotword (contextual phrase) biasing (BIAS = true, pgasr_ctc_beam_search_bias / _nbest_bias; include/pgasr_hip.h, A7-BIAS; the host
+// builder: lm.HotwordBias).  An n-gram context is the special case next = (ctx V + s) mod V^(n-1) of a deterministic automaton; a phrase
+// list compiles to such an automaton too (Aho-Corasick with weighted transitions), and the algebra is A7-LM's line for line:
+//   * the table holds S * V 8-byte words {int32 next; float bonus}, word (q, s) at q V + s: consecutive candidates of one entry read
+//     consecutive words;
+//   * an entry carries bst = the automaton state of its prefix (stay: inherited; extension by s: next[bst V + s]) and bwi = bst(parent
+//     prefix) V + last, the word of its own last emission -- the merged term of its stay candidate, known without pidx;
+//   * every term that enters a prefix by a non-blank extension gets w added: wb = __dmul_rn(weight, (double)bonus), w = wb without a
+//     language model and __dadd_rn(__dadd_rn(__dmul_rn(alpha, tv), beta), wb) with one; the blank update and the repeat branch are unchanged;
+//   * the bonuses of a thread's first BEAM_LM_PRE candidates and of the entries' own words are gathered at the top of the frame, beside
+//     the language model's, and parked in the `time` word of the thread's own, not yet written sort items;
+//   * the thread that writes entry r of the new beam re-reads its winner's word for `next` -- one independent 8-byte load beside
+//     trie_find_or_create, instead of 4 K V bytes of LDS --; a next outside [0, S) is taken as state 0, so every index stays below S V.
+// The arguments ride behind the others in the last parameter: the BIAS = false instantiations keep their argument list and their code.
+struct BiasWord { int32_t next; float bonus; };
+static_assert(sizeof(BiasWord) == 8, "a table word is 8 bytes");
+constexpr long long BEAM_BIAS_MAX_WORDS = 1ll << 24;      // S * V words (128 MiB)
+template <bool LM, bool NBEST> using BeamTail = typename std::conditional<NBEST, BeamNbest<LM>, BeamLm<LM>>::type;
+template <bool LM, bool NBEST> struct BeamBiased : BeamTail<LM, NBEST> {
+    const BiasWord* btable;  // S * V words
+    int bstates;             // S
+    double bweight;
+};
+
+template <typename TIn, bool FAST, bool LM, bool NBEST = false, bool BIAS = false>
 __global__ __launch_bounds__(BEAM_THREADS) void beam_search_kernel(
     const TIn* __restrict__ lp, long long stride_t, long long stride_b, const int32_t* __restrict__ lengths,
     int T, int V, int K, int blank, int collapse, BeamWs ws, int32_t* __restrict__ out_tokens, int32_t* __restrict__ out_len,
-    double* __restrict__ out_score, const typename std::conditional<NBEST, BeamNbest<LM>, BeamLm<LM>>::type lm) {
+    double* __restrict__ out_score, const typename std::conditional<BIAS, BeamBiased<LM, NBEST>, BeamTail<LM, NBEST>>::type lm) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int b = blockIdx.x, tid = threadIdx.x;
     int Tb = lengths ? lengths[b] : T; Tb = Tb < 0 ? 0 : (Tb > T ? T : Tb);
@@ -88,7 +112,10 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_search_kernel(
     int* ctx = s_ctl + 4;                      // LM only: [2][K] context index
     int* lmi = ctx + 2 * K;                    // LM only: [2][K] table index of the entry's own last emission
     float* ptv = reinterpret_cast<float*>(lmi + 2 * K);    // LM only: [K] table[lmi] of the current beam
-    short* cb = reinterpret_cast<short*>(LM ? s_ctl + 4 + 5 * K : s_ctl + 4);       // [K][V] child-in-beam table
+    int* bst = s_ctl + 4 + (LM ? 5 * K : 0);   // BIAS only: [2][K] automaton state of the entry's prefix
+    int* bwi = bst + 2 * K;                    // BIAS only: [2][K] table index of the entry's own last emission
+    float* pbv = reinterpret_cast<float*>(bwi + 2 * K);    // BIAS only: [K] bonus of table[bwi] of the current beam
+    short* cb = reinterpret_cast<short*>(BIAS ? bst + 5 * K : (LM ? s_ctl + 4 + 5 * K : s_ctl + 4));       // [K][V] child-in-beam table
 #define s_nb s_ctl[0]
 #define s_nodes s_ctl[1]
 
@@ -100,6 +127,7 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_search_kernel(
         id[0] = 0; last[0] = -1; par[0] = -1; pb[0] = 0.0; pnb[0] = -INFINITY;
         nodes[0] = 0xFFFFFFFFu;
         if constexpr (LM) { ctx[0] = lm.ctx0; lmi[0] = 0; }      // the root has no emission of its own: lmi is never used (last < 0)
+        if constexpr (BIAS) { bst[0] = 0; bwi[0] = 0; }          // state 0 is the automaton's root; bwi likewise unused while last < 0
     }
     __syncthreads();
     int cur = 0;
@@ -118,6 +146,17 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_search_kernel(
             }
             if (tid < nb && last[cur * K + tid] >= 0) lmp = lm.table[lmi[cur * K + tid]];
         }
+        [[maybe_unused]] const int* cbst = bst + cur * K;
+        [[maybe_unused]] float bv[BEAM_LM_PRE], bvp = 0.0f;
+        if constexpr (BIAS) {    // the bonuses likewise
+#pragma unroll
+            for (int k = 0; k < BEAM_LM_PRE; ++k) {
+                const int c = tid + k * BEAM_THREADS;
+                bv[k] = 0.0f;
+                if (c < nb * V) { const int j = c / V, s = c % V; if (s != blank) bv[k] = lm.btable[cbst[j] * V + s].bonus; }
+            }
+            if (tid < nb && last[cur * K + tid] >= 0) bvp = lm.btable[bwi[cur * K + tid]].bonus;
+        }
         if (tid < V) frame[tid] = (double)lp[(long long)t * stride_t + (long long)b * stride_b + tid];
         for (int i = tid; i < nb * V; i += BEAM_THREADS) cb[i] = -1;
         if (tid < nb) {
@@ -132,6 +171,14 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_search_kernel(
                 if (c < P) items[c].cand = __float_as_uint(lmv[k]);
             }
             if (tid < nb) ptv[tid] = lmp;
+        }
+        if constexpr (BIAS) {
+#pragma unroll
+            for (int k = 0; k < BEAM_LM_PRE; ++k) {
+                const int c = tid + k * BEAM_THREADS;
+                if (c < P) items[c].time = __float_as_uint(bv[k]);
+            }
+            if (tid < nb) pbv[tid] = bvp;
         }
         __syncthreads();
         if (tid < nb && pidx[tid] >= 0) cb[pidx[tid] * V + clast[tid]] = (short)tid;
@@ -157,6 +204,12 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_search_kernel(
                         const double own = cpnb[j] + pl;                              // repeat branch (:103-106)
                         if (i >= 0) {
                             double e1 = cpb[i] + pl, e2 = cpnb[i] + pl;               // extension of parent i by lj (:90-96)
+                            if constexpr (BIAS) {
+                                const double wb = __dmul_rn(lm.bweight, (double)pbv[j]);
+                                double w = wb;
+                                if constexpr (LM) w = __dadd_rn(__dadd_rn(__dmul_rn(lm.alpha, (double)ptv[j]), lm.beta), wb);
+                                e1 += w; e2 += w;
+                            } else
                             if constexpr (LM) {
                                 const double w = __dadd_rn(__dmul_rn(lm.alpha, (double)ptv[j]), lm.beta);
                                 e1 += w; e2 += w;
@@ -181,6 +234,18 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_search_kernel(
                     alive = false;          // merged into an existing entry's stay candidate
                 } else {
                     const double ps = frame[s];
+                    if constexpr (BIAS) {
+                        const bool pre = c < BEAM_LM_PRE * BEAM_THREADS;
+                        const float bon = pre ? __uint_as_float(items[c].time) : lm.btable[cbst[j] * V + s].bonus;
+                        const double wb = __dmul_rn(lm.bweight, (double)bon);
+                        double w = wb;
+                        if constexpr (LM) {
+                            const float tv = pre ? __uint_as_float(items[c].cand) : lm.table[cctx[j] * V + s];
+                            w = __dadd_rn(__dadd_rn(__dmul_rn(lm.alpha, (double)tv), lm.beta), wb);
+                        }
+                        const double eb = (cpb[j] + ps) + w, en = (cpnb[j] + ps) + w;
+                        npnb = (s != clast[j]) ? lse3x<FAST>(-INFINITY, eb, en) : lse2x<FAST>(-INFINITY, eb);
+                    } else
                     if constexpr (LM) {
                         const float tv = (c < BEAM_LM_PRE * BEAM_THREADS) ? __uint_as_float(items[c].cand) : lm.table[cctx[j] * V + s];
                         const double w = __dadd_rn(__dmul_rn(lm.alpha, (double)tv), lm.beta);
@@ -213,6 +278,13 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_search_kernel(
                     const int e = cctx[j] * V + s;
                     ctx[nxt * K + tid] = (s == blank) ? cctx[j] : e % lm.ctx_mod;
                     lmi[nxt * K + tid] = (s == blank) ? lmi[cur * K + j] : e;
+                }
+                if constexpr (BIAS) {
+                    const int e = cbst[j] * V + s;                          // cbst[j] < S: below S V words
+                    int nx = cbst[j];
+                    if (s != blank) { nx = lm.btable[e].next; nx = ((unsigned)nx < (unsigned)lm.bstates) ? nx : 0; }
+                    bst[nxt * K + tid] = nx;
+                    bwi[nxt * K + tid] = (s == blank) ? bwi[cur * K + j] : e;
                 }
                 if (s == blank) { nid[tid] = cid[j]; nlast[tid] = clast[j]; npar[tid] = cpar[j]; }
                 else {
@@ -258,7 +330,7 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_search_kernel(
 #undef s_nb
 #undef s_nodes
 
-inline size_t beam_lds_bytes(int K, int V, bool lm) {
+inline size_t beam_lds_bytes(int K, int V, bool lm, bool bias = false) {
     int P = 1; while (P < K * V) P <<= 1;
     size_t n = (size_t)P * sizeof(SortItem);
     n += (size_t)2 * K * V * sizeof(double);          // c_pb, c_pnb
@@ -266,6 +338,7 @@ inline size_t beam_lds_bytes(int K, int V, bool lm) {
     n += (size_t)BEAM_VMAX * sizeof(double);          // frame
     n += (size_t)(6 * K + K + 4) * sizeof(int);       // id,last,par (x2), pidx, control words
     if (lm) n += (size_t)(5 * K) * sizeof(int);       // ctx, lmi (x2), ptv
+    if (bias) n += (size_t)(5 * K) * sizeof(int);     // bst, bwi (x2), pbv: at most 2560 bytes, and the largest shape without them is 150032
     n += (size_t)K * V * sizeof(short);               // cb
     return (n + 15) / 16 * 16;
 }
@@ -887,18 +960,57 @@ int beam_lm_args(int V, int blank, const float* lm_table, int lm_order, double l
     return PGASR_OK;
 }
 
+// the bias table's arguments (no HIP call; include/pgasr_hip.h, A7-BIAS): a NULL table with no states is "no bias"
+int beam_bias_args(int V, int flags, const void* bias_table, int bias_states, double bias_weight) {
+    if (!bias_table && bias_states == 0) return PGASR_OK;
+    if (!bias_table || bias_states < 1 || (long long)bias_states * V > BEAM_BIAS_MAX_WORDS || !std::isfinite(bias_weight)) return PGASR_ERR_INVALID_ARG;
+    if (flags & (8 | 16)) return PGASR_ERR_UNSUPPORTED;      // the single-wave kernel has no bias: refused, never run differently
+    return PGASR_OK;
+}
+
 int beam_search_impl(const void* log_probs, int is_f64, long long stride_t, long long stride_b,
                      const int32_t* lengths, int T, int B, int V, int beam, int blank, int flags,
                      int32_t* out_tokens, int32_t* out_len, double* out_score,
                      void* workspace, size_t workspace_bytes, void* stream,
-                     const float* lm_table, int lm_order, double lm_alpha, double lm_beta) {
+                     const float* lm_table, int lm_order, double lm_alpha, double lm_beta,
+                     const void* bias_table = nullptr, int bias_states = 0, double bias_weight = 0.0) {
     // the shared checks with the language model's arguments in their place, before any HIP call
     BeamLm<true> lm{};
     BeamWs ws;
     if (const int st = beam_check_args(log_probs, out_tokens, out_len, out_score, T, B, V, beam, blank, BEAM_VMAX, BEAM_KMAX,
-                                       [&] { return beam_lm_args(V, blank, lm_table, lm_order, lm_alpha, lm_beta, &lm); },
+                                       [&] {
+                                           if (const int s = beam_lm_args(V, blank, lm_table, lm_order, lm_alpha, lm_beta, &lm)) return s;
+                                           return beam_bias_args(V, flags, bias_table, bias_states, bias_weight);
+                                       },
                                        workspace, workspace_bytes, &ws)) return st;
     const bool with_lm = lm_order > 0;
+    if (bias_table) {      // always the workgroup-per-utterance kernel, BIAS = true
+        const size_t lds = beam_lds_bytes(beam, V, with_lm, true);
+        if (lds > 160 * 1024) return PGASR_ERR_UNSUPPORTED;
+        hipStream_t st = (hipStream_t)stream;
+        if (hipMemsetAsync(ws.table, 0, (size_t)B * ws.H * sizeof(unsigned long long), st) != hipSuccess) return PGASR_ERR_LAUNCH;
+        BeamBiased<true, false> bl{};
+        static_cast<BeamLm<true>&>(bl) = lm;
+        bl.btable = (const BiasWord*)bias_table; bl.bstates = bias_states; bl.bweight = bias_weight;
+        BeamBiased<false, false> bn{};
+        bn.btable = bl.btable; bn.bstates = bias_states; bn.bweight = bias_weight;
+#define BEAM_BIAS_LAUNCH(TIN, FAST, LMB, ARG)                                                                                     \
+    {                                                                                                                             \
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&beam_search_kernel<TIN, FAST, LMB, false, true>),                \
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                          \
+        PGASR_LAUNCH_KERNEL((beam_search_kernel<TIN, FAST, LMB, false, true>), dim3(B), dim3(BEAM_THREADS), lds, st,              \
+                           (const TIN*)log_probs, stride_t, stride_b, lengths, T, V, beam, blank, flags & 1, ws, out_tokens,      \
+                           out_len, out_score, ARG);                                                                              \
+    }
+        if (with_lm) {
+            if (is_f64) BEAM_BIAS_LAUNCH(double, false, true, bl) else BEAM_BIAS_LAUNCH(float, true, true, bl)
+        } else {
+            if (is_f64) BEAM_BIAS_LAUNCH(double, false, false, bn) else BEAM_BIAS_LAUNCH(float, true, false, bn)
+        }
+#undef BEAM_BIAS_LAUNCH
+        PGASR_CHECK_LAUNCH();
+        return PGASR_OK;
+    }
     hipStream_t st = (hipStream_t)stream;
 #ifdef PGASR_BEAM_DIAG
     const int collapse = (flags & 1) | ((flags & 4) ? 2 : 0);
@@ -968,25 +1080,54 @@ extern "C" int pgasr_ctc_beam_search_lm(const void* log_probs, int is_f64, long 
 
 // The N-best list of the final beam (include/pgasr_hip.h, A7-NBEST): the workgroup-per-utterance kernel, NBEST = true; with flags bit 3
 // ("fast") the single-wave kernel's NBEST instantiation wherever the 1-best dispatch of beam_search_impl takes that kernel.
-extern "C" int pgasr_ctc_beam_search_nbest(const void* log_probs, int is_f64, long long stride_t, long long stride_b,
-                                           const int32_t* lengths, int T, int B, int V, int beam, int blank, int flags,
-                                           int nbest, int32_t* out_tokens, int tok_stride, int32_t* out_len, double* out_score,
-                                           int32_t* out_count, void* workspace, size_t workspace_bytes, void* stream,
-                                           const float* lm_table, int lm_order, double lm_alpha, double lm_beta) {
+namespace {
+int beam_search_nbest_impl(const void* log_probs, int is_f64, long long stride_t, long long stride_b,
+                           const int32_t* lengths, int T, int B, int V, int beam, int blank, int flags,
+                           int nbest, int32_t* out_tokens, int tok_stride, int32_t* out_len, double* out_score,
+                           int32_t* out_count, void* workspace, size_t workspace_bytes, void* stream,
+                           const float* lm_table, int lm_order, double lm_alpha, double lm_beta,
+                           const void* bias_table, int bias_states, double bias_weight) {
     // the shared checks, in the order of pgasr_ctc_beam_search_lm, with the language model's and then the list's in their place
     BeamLm<true> lmb{};
     BeamWs ws;
     if (const int st = beam_check_args(log_probs, out_tokens, out_len, out_score, T, B, V, beam, blank, BEAM_VMAX, BEAM_KMAX,
                                        [&] {
                                            if (const int s = beam_lm_args(V, blank, lm_table, lm_order, lm_alpha, lm_beta, &lmb)) return s;
+                                           if (const int s = beam_bias_args(V, flags, bias_table, bias_states, bias_weight)) return s;
                                            return (nbest < 1 || nbest > beam || tok_stride < T || !out_count) ? (int)PGASR_ERR_INVALID_ARG : (int)PGASR_OK;
                                        },
                                        workspace, workspace_bytes, &ws)) return st;
     const bool with_lm = lm_order > 0;
-    const size_t lds = beam_lds_bytes(beam, V, with_lm);
+    const size_t lds = beam_lds_bytes(beam, V, with_lm, bias_table != nullptr);
     if (lds > 160 * 1024) return PGASR_ERR_UNSUPPORTED;
     hipStream_t st = (hipStream_t)stream;
     const int collapse = flags & 1;
+    if (bias_table) {      // always the workgroup-per-utterance kernel, BIAS = true
+        if (hipMemsetAsync(ws.table, 0, (size_t)B * ws.H * sizeof(unsigned long long), st) != hipSuccess) return PGASR_ERR_LAUNCH;
+        BeamBiased<true, true> bl{};
+        static_cast<BeamLm<true>&>(bl) = lmb;
+        bl.nbest = nbest; bl.tok_stride = tok_stride; bl.out_count = out_count;
+        bl.btable = (const BiasWord*)bias_table; bl.bstates = bias_states; bl.bweight = bias_weight;
+        BeamBiased<false, true> bn{};
+        bn.nbest = nbest; bn.tok_stride = tok_stride; bn.out_count = out_count;
+        bn.btable = bl.btable; bn.bstates = bias_states; bn.bweight = bias_weight;
+#define BEAM_NBEST_BIAS_LAUNCH(TIN, FAST, LMB, ARG)                                                                               \
+    {                                                                                                                             \
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&beam_search_kernel<TIN, FAST, LMB, true, true>),                 \
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                          \
+        PGASR_LAUNCH_KERNEL((beam_search_kernel<TIN, FAST, LMB, true, true>), dim3(B), dim3(BEAM_THREADS), lds, st,               \
+                           (const TIN*)log_probs, stride_t, stride_b, lengths, T, V, beam, blank, collapse, ws, out_tokens,       \
+                           out_len, out_score, ARG);                                                                              \
+    }
+        if (with_lm) {
+            if (is_f64) BEAM_NBEST_BIAS_LAUNCH(double, false, true, bl) else BEAM_NBEST_BIAS_LAUNCH(float, true, true, bl)
+        } else {
+            if (is_f64) BEAM_NBEST_BIAS_LAUNCH(double, false, false, bn) else BEAM_NBEST_BIAS_LAUNCH(float, true, false, bn)
+        }
+#undef BEAM_NBEST_BIAS_LAUNCH
+        PGASR_CHECK_LAUNCH();
+        return PGASR_OK;
+    }
     if (with_lm && (flags & 16) && pgasr_beam_lm_single_wave_ok(T, V, beam, is_f64, lm_order)) {      // flags bit 4, as in the 1-best dispatch
         auto kern = V <= 32 ? &sb::beam_small_kernel<8, true, true> : &sb::beam_small_kernel<16, true, true>;
         const size_t lds_small = sb::lds_bytes_lm(V <= 32 ? 8 : 16);
@@ -1029,4 +1170,37 @@ extern "C" int pgasr_ctc_beam_search_nbest(const void* log_probs, int is_f64, lo
 #undef BEAM_NBEST_LAUNCH
     PGASR_CHECK_LAUNCH();
     return PGASR_OK;
+}
+}  // namespace
+
+extern "C" int pgasr_ctc_beam_search_nbest(const void* log_probs, int is_f64, long long stride_t, long long stride_b,
+                                           const int32_t* lengths, int T, int B, int V, int beam, int blank, int flags,
+                                           int nbest, int32_t* out_tokens, int tok_stride, int32_t* out_len, double* out_score,
+                                           int32_t* out_count, void* workspace, size_t workspace_bytes, void* stream,
+                                           const float* lm_table, int lm_order, double lm_alpha, double lm_beta) {
+    return beam_search_nbest_impl(log_probs, is_f64, stride_t, stride_b, lengths, T, B, V, beam, blank, flags, nbest, out_tokens, tok_stride,
+                                  out_len, out_score, out_count, workspace, workspace_bytes, stream, lm_table, lm_order, lm_alpha, lm_beta,
+                                  nullptr, 0, 0.0);
+}
+
+// Hotword biasing (include/pgasr_hip.h, A7-BIAS): the two searches with a bias automaton; a NULL table with no states is the call without.
+extern "C" int pgasr_ctc_beam_search_bias(const void* log_probs, int is_f64, long long stride_t, long long stride_b,
+                                          const int32_t* lengths, int T, int B, int V, int beam, int blank, int flags,
+                                          int32_t* out_tokens, int32_t* out_len, double* out_score,
+                                          void* workspace, size_t workspace_bytes, void* stream,
+                                          const float* lm_table, int lm_order, double lm_alpha, double lm_beta,
+                                          const void* bias_table, int bias_states, double bias_weight) {
+    return beam_search_impl(log_probs, is_f64, stride_t, stride_b, lengths, T, B, V, beam, blank, flags, out_tokens, out_len, out_score,
+                            workspace, workspace_bytes, stream, lm_table, lm_order, lm_alpha, lm_beta, bias_table, bias_states, bias_weight);
+}
+
+extern "C" int pgasr_ctc_beam_search_nbest_bias(const void* log_probs, int is_f64, long long stride_t, long long stride_b,
+                                                const int32_t* lengths, int T, int B, int V, int beam, int blank, int flags,
+                                                int nbest, int32_t* out_tokens, int tok_stride, int32_t* out_len, double* out_score,
+                                                int32_t* out_count, void* workspace, size_t workspace_bytes, void* stream,
+                                                const float* lm_table, int lm_order, double lm_alpha, double lm_beta,
+                                                const void* bias_table, int bias_states, double bias_weight) {
+    return beam_search_nbest_impl(log_probs, is_f64, stride_t, stride_b, lengths, T, B, V, beam, blank, flags, nbest, out_tokens, tok_stride,
+                                  out_len, out_score, out_count, workspace, workspace_bytes, stream, lm_table, lm_order, lm_alpha, lm_beta,
+                                  bias_table, bias_states, bias_weight);
 }

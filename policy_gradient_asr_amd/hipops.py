@@ -1700,8 +1700,23 @@ def _lm_table(lm, V, blank, device):
     return lm.device_table(device), lm.order
 
 
+def _bias_table(bias, V, blank, device, fast_lm=False, fast=False):
+    """The bias keywords of the search wrappers: (table tensor, states) of a ``lm.HotwordBias``.  Refusals need no device."""
+    from .lm import HotwordBias
+    if not isinstance(bias, HotwordBias):
+        raise ValueError("bias: a lm.HotwordBias is wanted (never raw tensors)")
+    if bias.vocab != V or bias.blank != int(blank):
+        raise ValueError(f"bias: the hotwords are over {bias.vocab} symbols with blank {bias.blank}; the call has {V} symbols and "
+                         f"blank {int(blank)}")
+    if fast_lm:
+        raise ValueError("fast_lm: the single-wave kernel has no hotword bias; search with fast_lm=False")
+    if fast:
+        raise ValueError("fast: the single-wave kernel has no hotword bias; search with fast=False")
+    return bias.device_table(device), bias.n_states
+
+
 def ctc_beam_search(log_probs, lengths=None, beam=5, blank=0, collapse=False, out=None, generic=False,
-                    lm=None, lm_alpha=0.0, lm_beta=0.0, fast_lm=False):
+                    lm=None, lm_alpha=0.0, lm_beta=0.0, fast_lm=False, bias=None, bias_weight=0.0):
     """log_probs (T,B,V) fp32 or fp64 natural-log probabilities on the GPU.
     Returns (tokens (B,T) int32, token_lengths (B) int32, score (B) float64 = -log p).
     collapse: the returned tokens have gone through collapse_fn (adjacent duplicates removed, CTCdecoder.py:119-131),
@@ -1714,7 +1729,13 @@ def ctc_beam_search(log_probs, lengths=None, beam=5, blank=0, collapse=False, ou
     fast_lm: the call takes the single-wave kernel with the LM term where ``beam_lm_single_wave_ok`` says so (an LM, fp32, beam <= 16,
     V <= 64, T * beam <= 24576, T <= 4096): the same algebra, several times faster; its scores agree with the workgroup kernel's to
     ~1e-7 relative, its hypotheses wherever no two candidates are closer than that.  Without an LM or outside those limits the flag
-    changes nothing."""
+    changes nothing.
+    bias: None (default: the calls above, launch for launch) or a ``lm.HotwordBias`` over the same V symbols and blank: every
+    extension by a non-blank s also gets ``bias_weight * bonus(state of the prefix, s)`` added (pgasr_ctc_beam_search_bias;
+    include/pgasr_hip.h, A7-BIAS), with or without ``lm``.  Such a call always takes the workgroup-per-utterance kernel -- fast_lm=True
+    with it raises --, and bias_weight = 0 returns the words of that kernel without a bias (``generic=True`` without an LM)."""
+    if bias is not None:
+        bias_table, bias_states = _bias_table(bias, log_probs.shape[-1], blank, log_probs.device, fast_lm=fast_lm)
     lib = _lib.load()
     T, B, V = _search_inputs(log_probs, lengths)
     lm_table, lm_order = _lm_table(lm, V, blank, log_probs.device)
@@ -1729,6 +1750,16 @@ def ctc_beam_search(log_probs, lengths=None, beam=5, blank=0, collapse=False, ou
         tokens = torch.zeros(B, T, dtype=torch.int32, device=log_probs.device)
         tl = torch.empty(B, dtype=torch.int32, device=log_probs.device)
     score = torch.empty(B, dtype=torch.float64, device=log_probs.device)
+    if bias is not None:
+        with _timed("beam_search_bias"):
+            st = lib.pgasr_ctc_beam_search_bias(_p(log_probs), int(log_probs.dtype == torch.float64), log_probs.stride(0),
+                                                log_probs.stride(1), _p(lengths), T, B, V, int(beam), int(blank),
+                                                int(bool(collapse)) | (2 if generic else 0),
+                                                _p(tokens), _p(tl), _p(score), _p(ws), ws.numel(), _stream(),
+                                                _p(lm_table), lm_order, float(lm_alpha), float(lm_beta),
+                                                _p(bias_table), bias_states, float(bias_weight))
+        _lib.check(st, "pgasr_ctc_beam_search_bias")
+        return tokens, tl, score
     with _timed("beam_search"):
         # one entry point for both: without a table it IS pgasr_ctc_beam_search
         st = lib.pgasr_ctc_beam_search_lm(_p(log_probs), int(log_probs.dtype == torch.float64), log_probs.stride(0),
@@ -1745,7 +1776,7 @@ NBEST_RESCORE_MAX = 128          # csrc/nbest.hip: hypotheses per utterance
 
 
 def ctc_beam_search_nbest(log_probs, lengths=None, beam=5, nbest=1, blank=0, collapse=False, lm=None, lm_alpha=0.0, lm_beta=0.0,
-                          fast=False, fast_lm=False):
+                          fast=False, fast_lm=False, bias=None, bias_weight=0.0):
     """The first ``nbest`` entries of the search's final beam (pgasr_ctc_beam_search_nbest): log_probs (T,B,V) fp32 or fp64 as
     ``ctc_beam_search`` takes them, 1 <= nbest <= beam.  Returns ``CTCNBest`` of device tensors, no host synchronisation:
     tokens (N,B,T) int32 (zero behind each hypothesis), lengths (N,B) int32, score (N,B) float64 = -logsumexp(p_blank, p_nonblank)
@@ -1761,13 +1792,26 @@ def ctc_beam_search_nbest(log_probs, lengths=None, beam=5, nbest=1, blank=0, col
     the flag changes nothing.
     fast_lm: with ``lm``, the call takes the single-wave kernel's LM instantiations where ``beam_lm_single_wave_ok`` says so (the
     limits of ``fast`` with a table); row 0 is then bit for bit ``ctc_beam_search(lm=..., fast_lm=True)``.  Without an LM or outside
-    the limits the flag changes nothing; ``fast`` without it keeps a call with an LM on the workgroup kernel."""
+    the limits the flag changes nothing; ``fast`` without it keeps a call with an LM on the workgroup kernel.
+    bias / bias_weight: a ``lm.HotwordBias`` as ``ctc_beam_search`` takes it (pgasr_ctc_beam_search_nbest_bias); row 0 is then bit
+    for bit ``ctc_beam_search(bias=...)``.  Not with ``fast`` or ``fast_lm`` (ValueError)."""
+    if bias is not None:
+        bias_table, bias_states = _bias_table(bias, log_probs.shape[-1], blank, log_probs.device, fast_lm=fast_lm, fast=fast)
     lib = _lib.load()
     T, B, V = _search_inputs(log_probs, lengths)
     lm_table, lm_order = _lm_table(lm, V, blank, log_probs.device)
     N, dev = int(nbest), log_probs.device
     ws = _workspace(lib.pgasr_beam_workspace_bytes(T, B, V, int(beam)), dev, "beam")
     tokens, tl, score, count = _nbest_outputs(N, B, T, dev)
+    if bias is not None:
+        with _timed("beam_search_nbest_bias"):
+            st = lib.pgasr_ctc_beam_search_nbest_bias(_p(log_probs), int(log_probs.dtype == torch.float64), log_probs.stride(0),
+                                                      log_probs.stride(1), _p(lengths), T, B, V, int(beam), int(blank),
+                                                      int(bool(collapse)), N, _p(tokens), T, _p(tl), _p(score), _p(count), _p(ws),
+                                                      ws.numel(), _stream(), _p(lm_table), lm_order, float(lm_alpha), float(lm_beta),
+                                                      _p(bias_table), bias_states, float(bias_weight))
+        _lib.check(st, "pgasr_ctc_beam_search_nbest_bias")
+        return CTCNBest(tokens, tl, score, count)
     with _timed("beam_search_nbest"):
         st = lib.pgasr_ctc_beam_search_nbest(_p(log_probs), int(log_probs.dtype == torch.float64), log_probs.stride(0),
                                              log_probs.stride(1), _p(lengths), T, B, V, int(beam), int(blank),
@@ -1778,6 +1822,31 @@ def ctc_beam_search_nbest(log_probs, lengths=None, beam=5, nbest=1, blank=0, col
 
 
 MAX_VOCAB_SEARCH_WIDE = 1024     # csrc/beam_wide.hip: the exact prefix beam search over rows of up to 1024 symbols
+
+
+BIAS_SCORE_MAX_VOCAB = 1024      # csrc/hotword.hip
+
+
+def nbest_bias_score(tokens, lengths, count, bias):
+    """A hotword bias over N-best lists (pgasr_nbest_bias_score; include/pgasr_hip.h, A7-BIAS): tokens (N,B,stride) / lengths (N,B) /
+    count (B) int32 as the searches return them (narrow or wide), ``bias`` a ``lm.HotwordBias``.  Returns bias_score (N,B) float64, no
+    host synchronisation: per hypothesis what ``bias.score_sequence`` returns, bit for bit -- the fp64 sum of the fp32 bonuses in token
+    order; 0 in the rows beyond count.  A blank or an id outside the vocabulary adds nothing.  N <= 128, at most 1024 symbols."""
+    from .lm import HotwordBias
+    if not isinstance(bias, HotwordBias):
+        raise ValueError("bias: a lm.HotwordBias is wanted (never raw tensors)")
+    lib = _lib.load()
+    _req(tokens, torch.int32, "tokens"); _req(lengths, torch.int32, "lengths"); _req(count, torch.int32, "count")
+    if tokens.dim() != 3 or tuple(lengths.shape) != tuple(tokens.shape[:2]) or count.numel() != tokens.shape[1]:
+        raise _lib.PgasrError("nbest_bias_score wants tokens (N,B,stride), lengths (N,B) and count (B)")
+    N, B, stride = tokens.shape
+    table = bias.device_table(tokens.device)
+    out = torch.empty(N, B, dtype=torch.float64, device=tokens.device)
+    with _timed("nbest_bias_score"):
+        st = lib.pgasr_nbest_bias_score(_p(tokens), _p(lengths), _p(count), N, B, stride, bias.vocab, _p(table), bias.n_states,
+                                        _p(out), _stream())
+    _lib.check(st, "pgasr_nbest_bias_score")
+    return out
 
 
 def _unit_lm_check(unit_lm, V, blank):

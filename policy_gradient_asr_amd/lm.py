@@ -987,3 +987,195 @@ class UnitNgramLM(_BackoffNgramLM):
                                    p["states"].shape[0], p["succ"].shape[0], p["start"])
             return UnitLMDeviceTables(st, tensors)
         return _on_device(self._device_tables, device, make)
+
+
+# ------------------------------------------------------------------------------------------
+# Hotword (contextual phrase) biasing (csrc/beam.hip BIAS = true, csrc/hotword.hip; include/pgasr_hip.h, section A7-BIAS)
+# ------------------------------------------------------------------------------------------
+MAX_BIAS_WORDS = 1 << 24   # S * V table words of 8 bytes (128 MiB): the entry points refuse more
+
+
+class HotwordBias:
+    """A list of phrases to bias the CTC beam search towards, compiled to a weighted automaton.
+
+    ``phrases`` is a list of token-id sequences (no blank, ids in [0, vocab), no empty phrase; duplicates are merged, the first
+    one's weight kept).  The weight of phrase p is ``weights[p]`` if given, else ``boost * len(p)``.  The bias of a token row y is
+
+        B(y) = sum over phrases p of (occurrences of p in y, overlapping ones included) * w(p)
+               + partial * boost * (length of the longest suffix of y that is a PROPER prefix of some phrase).
+
+    The second term is pending credit: it rewards a hypothesis for being on the way into a phrase and is taken back by the
+    transition that leaves the phrase.  The automaton is the Aho-Corasick machine of the phrase trie: state 0 is the root, states are
+    numbered in breadth-first order with children in symbol order; ``next`` (S, V) int32 is the dense goto with the failure links
+    resolved, ``bonus`` (S, V) float32 the increment of B on that transition, out(next) + pend(next) - pend(q) with out the summed
+    weights over the dictionary links, formed in float64 and rounded once.  The blank's column is next = q, bonus = 0.
+    ``transition`` / ``score_sequence`` are the host statements of the query the device makes; ``device_table`` is what the kernels
+    read: S * V 8-byte little-endian words {int32 next; float32 bonus}, at most 2**24 of them (ValueError beyond, never truncated)."""
+
+    def __init__(self, phrases, vocab, blank=0, boost=1.0, weights=None, partial=1.0):
+        V, blank = int(vocab), int(blank)
+        if V < 2:
+            raise ValueError("a bias needs at least one symbol beside the blank")
+        if not 0 <= blank < V:
+            raise ValueError("blank must be a symbol of the vocabulary")
+        boost, partial = float(boost), float(partial)
+        if not (math.isfinite(boost) and math.isfinite(partial)):
+            raise ValueError("boost and partial must be finite")
+        rows = [tuple(int(t) for t in p) for p in phrases]
+        if weights is not None:
+            weights = [float(w) for w in weights]
+            if len(weights) != len(rows):
+                raise ValueError("weights: one per phrase")
+            if not all(math.isfinite(w) for w in weights):
+                raise ValueError("weights must be finite")
+        merged = {}
+        for i, p in enumerate(rows):
+            if not p:
+                raise ValueError("an empty phrase cannot be a hotword")
+            if any(t < 0 or t >= V or t == blank for t in p):
+                raise ValueError(f"phrase {i} holds the blank or a symbol outside [0, {V})")
+            merged.setdefault(p, weights[i] if weights is not None else boost * len(p))
+        self.phrases = list(merged)
+        self.weights = np.asarray([merged[p] for p in self.phrases], dtype=np.float64).reshape(-1)
+        self.vocab, self.blank, self.boost, self.partial = V, blank, boost, partial
+        self._build()
+        self._device_tables = {}
+
+    def _build(self):
+        V, blank = self.vocab, self.blank
+        # the trie, in insertion order ...
+        kids, own = [{}], [0.0]
+        for p, w in zip(self.phrases, self.weights):
+            q = 0
+            for t in p:
+                nx = kids[q].get(t)
+                if nx is None:
+                    nx = len(kids)
+                    kids[q][t] = nx
+                    kids.append({})
+                    own.append(0.0)
+                q = nx
+            own[q] += float(w)
+        S = len(kids)
+        if S * V > MAX_BIAS_WORDS:
+            raise ValueError(f"the bias automaton has {S} states over {V} symbols: {S * V} table words, the limit is 2**24")
+        # ... renumbered breadth first, children in symbol order
+        order, new_of = [0], {0: 0}
+        parent, sym, depth = [0], [-1], [0]
+        head = 0
+        while head < len(order):
+            old = order[head]
+            for t in sorted(kids[old]):
+                c = kids[old][t]
+                new_of[c] = len(order)
+                order.append(c)
+                parent.append(head); sym.append(t); depth.append(depth[head] + 1)
+            head += 1
+        nxt = np.zeros((S, V), dtype=np.int32)
+        out = np.zeros(S, dtype=np.float64)
+        plen = np.zeros(S, dtype=np.int64)        # length of the longest suffix that is a proper prefix of some phrase
+        fail = np.zeros(S, dtype=np.int64)
+        has_kids = np.array([bool(kids[o]) for o in order])
+        for q in range(S):                        # breadth-first order: a state's failure state comes before it
+            if q:
+                f = int(nxt[fail[parent[q]], sym[q]]) if parent[q] else 0
+                fail[q] = f
+                nxt[q] = nxt[f]
+                out[q] = own[order[q]] + out[f]
+                plen[q] = depth[q] if has_kids[q] else plen[f]
+            for t, c in kids[order[q]].items():
+                nxt[q, t] = new_of[c]
+        pend = (self.partial * self.boost) * plen.astype(np.float64)
+        bonus64 = out[nxt] + pend[nxt] - pend[:, None]
+        nxt[:, blank] = np.arange(S, dtype=np.int32)
+        bonus64[:, blank] = 0.0
+        bonus = bonus64.astype(np.float32)
+        assert nxt.min() >= 0 and nxt.max() < S, "a transition leaves the automaton"
+        assert np.isfinite(bonus).all(), "a bonus is not finite"
+        self.next, self.bonus, self.n_states = np.ascontiguousarray(nxt), np.ascontiguousarray(bonus), S
+        self.depth = np.asarray(depth, dtype=np.int64)
+
+    # ---------------------------------------------------------------- construction
+    @classmethod
+    def from_strings(cls, lines, alphabet, blank=0, boost=1.0, weights=None, partial=1.0):
+        """One phrase per line, encoded character by character.  ``alphabet``: the list of symbols in index order (the decoder's;
+        entries may carry their line break) or a ``char2ind`` dict.  Empty lines are skipped (then give no ``weights``); a
+        character outside the alphabet raises."""
+        if hasattr(alphabet, "items"):
+            char2ind = dict(alphabet)
+            vocab = max(char2ind.values()) + 1
+        else:
+            char2ind = {str(a).replace("\n", ""): i for i, a in enumerate(alphabet)}
+            vocab = len(alphabet)
+        phrases = []
+        for ln in lines:
+            ln = ln.rstrip("\n").rstrip("\r")
+            if not ln:
+                if weights is not None:
+                    raise ValueError("an empty line cannot carry a weight")
+                continue
+            try:
+                phrases.append([char2ind[c] for c in ln])
+            except KeyError as e:
+                raise ValueError(f"character {e.args[0]!r} of hotword {ln!r} is not in the alphabet") from None
+        return cls(phrases, vocab, blank=blank, boost=boost, weights=weights, partial=partial)
+
+    @classmethod
+    def from_units(cls, lines, units, blank=0, boost=1.0, weights=None, partial=1.0):
+        """One phrase per line, encoded with ``units.encode`` (``units.SubwordUnits``, greedy longest match).  A phrase is
+        segmented IN ISOLATION: inside a sentence the same characters can be cut into other units (a unit may span the phrase's
+        boundary), and such an occurrence is not matched.  Empty lines are skipped (then give no ``weights``)."""
+        phrases = []
+        for ln in lines:
+            ln = ln.rstrip("\n").rstrip("\r")
+            if not ln:
+                if weights is not None:
+                    raise ValueError("an empty line cannot carry a weight")
+                continue
+            phrases.append(units.encode(ln))
+        return cls(phrases, len(units), blank=blank, boost=boost, weights=weights, partial=partial)
+
+    # ---------------------------------------------------------------- persistence
+    def save(self, path):
+        """The phrases and their weights (.npz); ``load`` compiles them again, to the same bits."""
+        flat = np.asarray([t for p in self.phrases for t in p], dtype=np.int32)
+        off = np.cumsum([0] + [len(p) for p in self.phrases]).astype(np.int64)
+        with open(path, "wb") as fo:
+            np.savez(fo, tokens=flat, offsets=off, weights=self.weights, vocab=np.int64(self.vocab), blank=np.int64(self.blank),
+                     boost=np.float64(self.boost), partial=np.float64(self.partial))
+
+    @classmethod
+    def load(cls, path):
+        with np.load(path, allow_pickle=False) as z:
+            flat, off = z["tokens"], z["offsets"]
+            phrases = [flat[int(off[i]):int(off[i + 1])].tolist() for i in range(len(off) - 1)]
+            return cls(phrases, int(z["vocab"]), blank=int(z["blank"]), boost=float(z["boost"]), weights=z["weights"].tolist(),
+                       partial=float(z["partial"]))
+
+    # ---------------------------------------------------------------- queries
+    def transition(self, q, s):
+        """(next state, bonus as a Python float) of token ``s`` in state ``q``; a token outside [0, vocab) or equal to the blank
+        leaves the state unchanged and adds nothing."""
+        q, s = int(q), int(s)
+        if s < 0 or s >= self.vocab or s == self.blank:
+            return q, 0.0
+        return int(self.next[q, s]), float(self.bonus[q, s])
+
+    def score_sequence(self, tokens):
+        """The Python-float sum of float(bonus) along ``tokens`` from state 0, in token order: B(tokens) up to the table's fp32."""
+        q, total = 0, 0.0
+        for s in tokens:
+            q, w = self.transition(q, s)
+            total = total + w
+        return total
+
+    def device_table(self, device):
+        """The table as an (S * V, 2) int32 tensor on ``device`` -- word (q, s) = {next, the bonus' bits} -- made once per device."""
+        import torch
+
+        def make(dev):
+            words = np.empty((self.n_states * self.vocab, 2), dtype="<i4")
+            words[:, 0] = self.next.reshape(-1)
+            words[:, 1] = self.bonus.reshape(-1).view(np.int32)
+            return torch.from_numpy(words).to(dev).contiguous()
+        return _on_device(self._device_tables, device, make)

@@ -568,7 +568,8 @@ def predict(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=N
             nbest=1, rescore_lm_path=None, rescore_alpha=0.0, rescore_beta=0.0, lm_fast=False, target_rate=None,
             mbr=False, mbr_unit="char", mbr_scale=1.0, rescore_word_lm_path=None, rescore_word_alpha=0.0, rescore_word_beta=0.0,
             error_report=False, units_path=None, wide_beam=False, wide_second_pass=False, unit_lm_path=None, unit_lm_alpha=0.0,
-            unit_lm_beta=0.0, rescore_unit_lm_path=None, rescore_unit_alpha=0.0, rescore_unit_beta=0.0, spelled=False):
+            unit_lm_beta=0.0, rescore_unit_lm_path=None, rescore_unit_alpha=0.0, rescore_unit_beta=0.0, spelled=False,
+            hotwords_path=None, hotword_weight=1.0, hotword_boost=1.0):
     """model.py:277-339: load model_best.pth, forward, beam=5 prefix search (device side, batched),
     collapse_fn, CER/WER, predicted.txt.  Frames are cut by the FEATURE mask (the reference cuts the
     time axis by the target mask, model.py:322 -- a listed defect).  Returns (CER, WER).
@@ -636,7 +637,14 @@ def predict(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=N
     alphabet.txt, where that file exists; else the characters of the units).  error_report=True is then allowed with greedy decoding
     and with the wide search (``ErrorReport`` over the spelling's characters), mbr_unit="word" with wide_second_pass=True (and
     mbr_unit="char" counts characters, not units: ``CTCDecoder.mbr_from_list(unit_spelling=)``), and the oracle of a wide list is
-    printed as the CER over spelled text (``metrics.nbest_oracle(spelling=)``)."""
+    printed as the CER over spelled text (``metrics.nbest_oracle(spelling=)``).
+    hotwords_path: None (default: everything above, nothing else) or a text file with one phrase per line (empty lines are skipped):
+    the decoder is biased towards these phrases (``lm.HotwordBias`` with boost = hotword_boost per token, applied with weight
+    hotword_weight).  An alphabet of at most 64 symbols: the bias is fused into the beam search (``CTCDecoder(hotwords=)``, beam_size
+    >= 1; the first-pass scores are then fused scores) -- not with lm_fast=True or unit_lm_path, whose kernels have no bias.  A wider
+    alphabet: with units_path, wide_beam=True and wide_second_pass=True (nbest >= 2) the phrases are encoded with the units, each
+    in isolation, and the bias goes into the second pass over the wide lists (``CTCDecoder.rescore(bias=)``); the wide search itself
+    has no bias, so any other combination raises a ValueError that names the missing option."""
     import os
     import functools
     import torch.utils.data as tud
@@ -667,6 +675,13 @@ def predict(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=N
         raise ValueError("minimum-Bayes-risk decoding needs a list: give nbest >= 2 with mbr=True")
     if mbr and mbr_unit not in ("char", "word"):
         raise ValueError(f"mbr_unit must be 'char' or 'word' (got {mbr_unit!r})")
+    if hotwords_path is not None:
+        if greedy:
+            raise ValueError("hotwords_path: greedy decoding (beam_size=0) has no hotword bias; give beam_size >= 1")
+        if lm_fast:
+            raise ValueError("lm_fast: the single-wave kernel has no hotword bias; give lm_fast=False with hotwords_path")
+        if unit_lm_path is not None:
+            raise ValueError("unit_lm_path: the wide search it is fused into has no hotword bias; not together with hotwords_path")
     char_alphabet_path = alphabet_path
     if units_path is not None:
         alphabet_path = units_path
@@ -708,6 +723,27 @@ def predict(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=N
             if given:
                 raise ValueError(f"{name}: not with the wide beam search ({len(alphabet)} > {hipops.MAX_VOCAB_NARROW} symbols), which "
                                  f"has no LM fusion, no second pass over its lists and no error report yet")
+    hotwords = rescore_bias = None
+    if hotwords_path is not None:
+        from .lm import HotwordBias
+        if len(alphabet) > hipops.MAX_VOCAB_NARROW:
+            for name, given in (("units_path", units_path is not None), ("wide_beam", wide), ("wide_second_pass", second)):
+                if not given:
+                    raise ValueError(f"{name}: hotwords over {len(alphabet)} > {hipops.MAX_VOCAB_NARROW} symbols go into the second pass "
+                                     f"over the wide lists (the wide search has no bias); give units_path, wide_beam=True and "
+                                     f"wide_second_pass=True with hotwords_path")
+        with open(hotwords_path, "r") as fo:
+            lines = fo.readlines()
+        if units_path is not None:
+            bias = HotwordBias.from_units(lines, unit_args["units"], boost=hotword_boost)
+        else:
+            bias = HotwordBias.from_strings(lines, alphabet, boost=hotword_boost)
+        if bias.vocab != len(alphabet):
+            raise ValueError(f"hotwords_path: the phrases compile to {bias.vocab} symbols; {alphabet_path} has {len(alphabet)}")
+        if len(alphabet) > hipops.MAX_VOCAB_NARROW:
+            rescore_bias = bias
+        else:
+            hotwords = bias
     if len(alphabet) > hipops.MAX_VOCAB_NARROW and not greedy and not wide:
         raise ValueError(f"the beam search takes at most {hipops.MAX_VOCAB_NARROW} symbols and {alphabet_path} has {len(alphabet)}: "
                          f"decode greedily with beam_size=0 (up to {hipops.MAX_VOCAB_WIDE} symbols)")
@@ -737,7 +773,8 @@ def predict(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=N
     if unit_lm is not None:
         decoder = CTCDecoder(alphabet, lm_alpha=unit_lm_alpha, lm_beta=unit_lm_beta, wide_search=True, unit_lm=unit_lm)
     else:
-        decoder = CTCDecoder(alphabet, lm=lm, lm_alpha=lm_alpha, lm_beta=lm_beta, fast_lm=bool(lm_fast), wide_search=wide)
+        decoder = CTCDecoder(alphabet, lm=lm, lm_alpha=lm_alpha, lm_beta=lm_beta, fast_lm=bool(lm_fast), wide_search=wide,
+                             **({} if hotwords is None else {"hotwords": hotwords, "hotword_weight": hotword_weight}))
     list_text = to_text if wide else collapse_fn      # a wide list holds units: their concatenation is the text
     if mbr and mbr_unit == "word" and spelling is None and " " not in char2ind:
         raise ValueError("mbr_unit='word' needs an alphabet with the ' ' symbol")
@@ -749,6 +786,8 @@ def predict(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=N
                                             "word_delimiter": char2ind[" "]}
     if rescore_unit_lm is not None:
         word_args = dict(word_args, unit_lm=rescore_unit_lm, unit_lm_alpha=rescore_unit_alpha, unit_lm_beta=rescore_unit_beta)
+    if rescore_bias is not None:
+        word_args = dict(word_args, bias=rescore_bias, bias_weight=float(hotword_weight))
     report = None
     if error_report:
         from .metrics import ErrorReport

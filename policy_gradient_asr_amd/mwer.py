@@ -308,6 +308,9 @@ class MWERTrainer(PolicyGradientTrainer):
                  max_grad_norm=None, beam_size=16, nbest=4, risk_unit="char", word_delimiter=None, max_hyp_len=None, lm=None, lm_alpha=0.0,
                  lm_beta=0.0, wide_sequence=False, unit_lm=None, unit_spelling=None, **sampled):
         wide_sequence = bool(wide_sequence)
+        if sampled.pop("hotwords", None) is not None:
+            raise ValueError("hotwords: MWERTrainer trains on unbiased N-best lists -- there is no hotword bias during training; bias "
+                             "the decoder (CTCDecoder(hotwords=))")
         if sampled.pop("wide_alphabet", False) and not wide_sequence:
             raise ValueError("MWERTrainer takes an alphabet of at most 64 symbols: the beam search and the N-best kernels hold one "
                              "symbol per lane (wide_alphabet=True is PolicyGradientTrainer's default objective only)")

@@ -448,7 +448,7 @@ class PolicyGradientTrainer(DataParallelStep):
                  reward_decoder="greedy", beam_size=16, precision=None, reward_mode="utterance", num_samples=1,
                  reward_baseline="hypothesis", reward_unit="char", word_delimiter=None, max_grad_norm=None,
                  score_function="path", max_hyp_len=None, entropy_weight=0.0, kl_weight=0.0, kl_reference=None, wide_alphabet=False,
-                 wide_objectives=False, wide_sequence=False, unit_spelling=None, step_objectives=False):
+                 wide_objectives=False, wide_sequence=False, unit_spelling=None, step_objectives=False, hotwords=None):
         """wide_alphabet: opt in to alphabets of 65 .. 1024 symbols (subword units).  MAX_VOCAB becomes 1024, and such a model takes
         the default objective alone: reward_decoder="greedy", reward_mode="utterance", num_samples=1, reward_baseline="hypothesis",
         reward_unit="char", score_function="path", entropy_weight=0, kl_weight=0 -- anything else raises here and before every
@@ -508,9 +508,14 @@ class PolicyGradientTrainer(DataParallelStep):
         (loss.PGCTCLossFn, A12-STEP).  With wide_alphabet=True it admits per_step above 64 symbols with num_samples=1, the hypothesis
         baseline and no entropy or KL term; the rest there needs wide_objectives=True as well.  reward_decoder="beam",
         score_function="sequence", reward_unit="word" and unit_spelling stay refused with reward_mode="per_step"; with
-        reward_mode="utterance" the keyword changes nothing."""
+        reward_mode="utterance" the keyword changes nothing.
+        hotwords: must stay None -- there is no hotword bias during training (the in-step search of reward_decoder="beam" is the
+        single-wave kernel); anything else raises a ValueError that says so.  Bias the decoder: CTCDecoder(hotwords=)."""
         from .loss import check_kl_weight
         kl_weight = check_kl_weight(kl_weight)
+        if hotwords is not None:
+            raise ValueError("hotwords: there is no hotword bias during training -- the in-step search of reward_decoder='beam' is the "
+                             "single-wave kernel, which has none; bias the decoder (CTCDecoder(hotwords=))")
         if isinstance(kl_reference, str):
             if kl_reference != "initial":
                 raise ValueError(f"kl_reference must be a module with Seq2Seq.logits or 'initial' (got {kl_reference!r})")
