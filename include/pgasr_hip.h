@@ -1031,6 +1031,43 @@ int pgasr_nbest_bias_score(const int32_t* tokens, const int32_t* len, const int3
                            const void* bias_table, int bias_states, double* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * A7-WIDE-BIAS  Hotword biasing inside the A7-WIDE search: rows of up to 1024 symbols, with or without the unit model of A7-WIDE-LM
+ * (csrc/beam_wide.hip, the WideBias argument of beam_wide_kernel).  The first pass itself is biased, so a rare phrase the acoustic
+ * search would drop from the beam stays in it; a second pass (pgasr_nbest_bias_score) can only re-rank rows that are in the list.
+ *   The arguments of pgasr_ctc_beam_search_wide_lm up to and including stream; then tables (NULL: no model), lm_alpha, lm_beta as
+ *   there; then bias_table, bias_states, bias_weight: the automaton of A7-BIAS in its one layout -- S * V words {int32 next; float32
+ *   bonus}, word (q, s) at q * V + s, what lm.HotwordBias.device_table holds and the A7-BIAS entries read.
+ *   The meaning is A7-BIAS's, line for line, on A7-WIDE's candidates.  An entry carries the state of its prefix (the root, 0, for the
+ *   empty prefix; a stay inherits it, an extension by s takes next[state_j V + s]) and the bonus of its own last emission,
+ *   bonus[state(parent prefix), last], which is the bias part of the merged term of its stay candidate.  Every term that enters a
+ *   prefix by an extension with a non-blank s gets w added, with these roundings, for fp32 and fp64 log_probs alike:
+ *       wb = __dmul_rn(bias_weight, (double)bonus);
+ *       with a model  w = __dadd_rn(__dadd_rn(__dmul_rn(lm_alpha, (double)lp32(ctx(prefix), s)), lm_beta), wb);   without  w = wb;
+ *       then (p_b + p) + w and (p_nb + p) + w.
+ *   The blank update and the repeat branch that keeps the prefix are unchanged.  Candidates, touch times, both selections, the trie
+ *   and the result tail are A7-WIDE's; bonuses can be negative, so the threshold's extension candidate of an entry is the symbol of
+ *   largest log-prob + w with its own w in its image, as in A7-WIDE-LM.  out_score is a FUSED score.  A next outside [0, S) read from
+ *   the table is taken as state 0 and every index is formed from the clamped state: no table content gives an address outside the
+ *   S * V words.  No loop is added: everything is bounded as in A7-WIDE.  For V <= 64 (and a model with a dense form) every output
+ *   word equals pgasr_ctc_beam_search_nbest_bias's wherever no two candidates tie.
+ *   Dispatch: tables == NULL, bias_table == NULL and bias_states == 0 is exactly pgasr_ctc_beam_search_wide; tables != NULL without a
+ *   bias is exactly pgasr_ctc_beam_search_wide_lm; bias_weight = 0 with a table returns the words of the same call without a table
+ *   bit for bit.
+ *   Workspace: pgasr_beam_wide_workspace_bytes without a model, pgasr_beam_wide_lm_workspace_bytes with one; the bias needs none.
+ *   Checked before any HIP call, in this order: A7-WIDE's checks up to and including the flags / nbest / tok_stride / out_count group;
+ *   the model's checks as in A7-WIDE-LM when tables != NULL; then the bias -- a NULL table with bias_states != 0, a table with
+ *   bias_states < 1, bias_states * V > 2^24, a bias_weight that is not finite -> PGASR_ERR_INVALID_ARG --; then the workspace and the
+ *   node-id width as in A7-WIDE / A7-WIDE-LM.  No host synchronisation.
+ * ---------------------------------------------------------------------------------------- */
+int pgasr_ctc_beam_search_wide_bias(const void* log_probs, int is_f64, long long stride_t, long long stride_b,
+                                    const int32_t* lengths, int T, int B, int V, int beam, int blank, int flags,
+                                    int nbest, int32_t* out_tokens, int tok_stride, int32_t* out_len, double* out_score,
+                                    int32_t* out_count, int32_t* out_counting_frames,
+                                    void* workspace, size_t workspace_bytes, void* stream,
+                                    const pgasr_unit_lm_tables* tables, double lm_alpha, double lm_beta,
+                                    const void* bias_table, int bias_states, double bias_weight);
+
+/* ------------------------------------------------------------------------------------------
  * A7-RESCORE Second pass over N-best lists: an n-gram LM score of every hypothesis, a weighted total and its rank.
  *   tokens (N, B, tok_stride) int32, len (N, B), count (B): a list as pgasr_ctc_beam_search_nbest writes it (len is clamped to
  *   [0, tok_stride], count to [0, N]); am (N, B) fp64: the caller's acoustic score, lower is better.

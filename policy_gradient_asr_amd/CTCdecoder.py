@@ -8,7 +8,8 @@ likelihood of lists of more than 16 rows or more than 64 symbols from the lattic
 ``CTCDecoder.mbr_decode`` returns the hypothesis of least expected edit distance under the list's posterior instead of the best-scored
 one (minimum-Bayes-risk decoding, csrc/mbr.hip); ``CTCDecoder(hotwords=...)`` biases the search towards a list of phrases (contextual
 biasing with a weighted automaton, ``lm.HotwordBias``; csrc/beam.hip BIAS = true) and ``rescore(bias=...)`` applies the same bias to a list
-in the second pass (csrc/hotword.hip), which is how lists of subword units get it."""
+in the second pass (csrc/hotword.hip), which is how lists of subword units get it unless ``wide_hotwords=True`` puts the bias into
+the wide search itself (csrc/beam_wide.hip with a WideBias)."""
 import collections
 
 import numpy as np
@@ -53,7 +54,7 @@ MBRDecoded = collections.namedtuple("MBRDecoded", "tokens lengths best risk post
 
 class CTCDecoder:
     def __init__(self, alphabet, device=None, lm=None, lm_alpha=0.0, lm_beta=0.0, fast_lm=False, wide_search=False, unit_lm=None,
-                 hotwords=None, hotword_weight=1.0):
+                 wide_hotwords=False, hotwords=None, hotword_weight=1.0):
         """lm: None (default: the acoustic search of the reference) or a ``lm.CharNgramLM``; every extension of a prefix by a
         non-blank symbol s then gets ``lm_alpha * ln p_lm(s | last order-1 symbols) + lm_beta`` added (Hannun/Maas,
         arXiv:1408.2873 -- the place CTCdecoder.py:90-96 marks for an LM score).  ``decode`` / ``decode_batch`` use these values
@@ -74,8 +75,16 @@ class CTCDecoder:
         ``hotword_weight * bonus`` to every extension on the way into or through a phrase (``hipops.ctc_beam_search(bias=)``), with or
         without ``lm``, and their scores are FUSED scores.  ``set_hotwords(hotwords, weight)`` changes the list later.  The biased
         search is the workgroup kernel's: fast_lm=True with hotwords raises, and so do rows of more than 64 symbols and ``unit_lm`` --
-        the wide search has no bias; bias its lists in the second pass, ``rescore(bias=)``.  A bias whose vocabulary or blank differs
-        from a call's raises."""
+        the wide search takes no bias unless ``wide_hotwords`` is given; without it bias its lists in the second pass,
+        ``rescore(bias=)``.  A bias whose vocabulary or blank differs from a call's raises.
+        wide_hotwords: with ``wide_search=True`` (ValueError without it), the calls that take the wide entry -- rows of more than 64
+        symbols, or any rows once ``unit_lm`` is given; ``decode``, ``decode_batch`` and their ``nbest=`` forms -- pass the hotwords
+        there (``hipops.ctc_beam_search_wide(bias=)``, csrc/beam_wide.hip): the first pass itself is biased, with or without
+        ``unit_lm``, so a rare phrase stays in the beam instead of having to be in the list already when a second pass looks for it.
+        Rows of at most 64 symbols without ``unit_lm`` keep taking the narrow biased kernel."""
+        if wide_hotwords and not wide_search:
+            raise ValueError("wide_hotwords: the bias is fused into the wide search; give wide_search=True")
+        self.wide_hotwords = bool(wide_hotwords)
         if unit_lm is not None and lm is not None:
             raise ValueError("unit_lm: not together with lm -- one first-pass language model")
         if unit_lm is not None and not wide_search:
@@ -96,7 +105,7 @@ class CTCDecoder:
         if hotwords is not None:
             if self.fast_lm:
                 raise ValueError("fast_lm: the single-wave kernel has no hotword bias; give fast_lm=False with hotwords")
-            if self.unit_lm is not None:
+            if self.unit_lm is not None and not self.wide_hotwords:
                 raise ValueError("hotwords: the wide search has no hotword bias (unit_lm is fused into it); bias its lists in the "
                                  "second pass, rescore(bias=)")
             if not isinstance(hotwords, HotwordBias):
@@ -109,13 +118,14 @@ class CTCDecoder:
         self.hotwords, self.hotword_weight = hotwords, weight
 
     def _bias_args(self, V, blank, wide, fast_lm=False):
-        """The bias keywords of the narrow entries; refuses what no kernel does.  Touches no device."""
+        """The bias keywords of the narrow entries, and of the wide one with ``wide_hotwords``; refuses what no kernel does.
+        Touches no device."""
         if self.hotwords is None:
             return {}
-        if wide:
+        if wide and not self.wide_hotwords:
             raise ValueError(f"hotwords: the wide beam search ({V} symbols) has no hotword bias; bias its lists in the second pass, "
                              f"rescore(bias=)")
-        if fast_lm:
+        if fast_lm and not wide:
             raise ValueError("fast_lm: the single-wave kernel has no hotword bias; give fast_lm=False with hotwords")
         if self.hotwords.vocab != V or self.hotwords.blank != int(blank):
             raise ValueError(f"hotwords: the bias is over {self.hotwords.vocab} symbols with blank {self.hotwords.blank}; the call has "
@@ -143,10 +153,11 @@ class CTCDecoder:
         return True
 
     def _wide_lm(self, args):
-        """The language-model keywords of the wide entry."""
+        """The language-model and bias keywords of the wide entry."""
+        bias = {k: args[k] for k in ("bias", "bias_weight") if k in args}
         if self.unit_lm is None:
-            return {}
-        return {"unit_lm": self.unit_lm, "lm_alpha": args["lm_alpha"], "lm_beta": args["lm_beta"]}
+            return bias
+        return {"unit_lm": self.unit_lm, "lm_alpha": args["lm_alpha"], "lm_beta": args["lm_beta"], **bias}
 
     def _lm_args(self, lm, lm_alpha, lm_beta):
         return {"lm": self.lm if lm is _UNSET else lm,
@@ -268,7 +279,9 @@ class CTCDecoder:
             with B(y) the hypothesis' ``score_sequence`` (``hipops.nbest_bias_score``) and the roundings of
             ``hipops.nbest_combine_rank`` on the earlier total.  The result carries one more field at its end, bias (N,B) float64
             (the result's type with "Bias" behind its name).  No further host synchronisation.  With acoustic="first_pass" after a
-            search that was itself biased, am already holds the first pass' bonuses: the bias is then added on top of them."""
+            search that was itself biased -- the narrow one, or the wide one of ``CTCDecoder(wide_hotwords=True)`` --, am already
+            holds the first pass' bonuses: the bias is then added on top of them.  acoustic="ctc" drops them: am is the exact
+            likelihood of every row, and the biased first pass has only decided which rows are in the list."""
         if unit_lm is not None:
             hipops._unit_lm_check(unit_lm, log_probs.shape[-1], blank)
         if bias is not None:
@@ -398,7 +411,9 @@ class CTCDecoder:
         posterior then comes from the totals with the word LM in them; unit_lm / unit_lm_alpha / unit_lm_beta likewise (a
         ``lm.UnitNgramLM`` in the second pass, wide lists included).  unit_spelling: the risk over the spelled text of a list of
         subword units (``mbr_from_list``; max_hyp_len keeps capping the unit rows, the spelled rows by that many units' longest
-        spelling).  bias / bias_weight go to ``rescore`` (a ``lm.HotwordBias`` in the second pass).  Returns ``MBRDecoded``."""
+        spelling).  bias / bias_weight go to ``rescore`` (a ``lm.HotwordBias`` in the second pass); the decoder's own hotwords bias the
+        N-best search itself, the wide one with ``wide_hotwords=True``, and acoustic="first_pass" keeps their bonuses in the scores.
+        Returns ``MBRDecoded``."""
         T, B, V = log_probs.shape
         nb = self.decode_batch(log_probs, lengths, beam_size=beam_size, blank=blank, nbest=int(nbest))
         rs = self.rescore(log_probs, lengths, nb, lm=lm, lm_alpha=lm_alpha, lm_beta=lm_beta, acoustic=acoustic, am_weight=am_weight,

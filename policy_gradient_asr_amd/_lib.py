@@ -119,6 +119,10 @@ SIGNATURES = {
     "pgasr_ctc_beam_search_wide_lm": (C.c_int, [c_ptr, C.c_int, C.c_longlong, C.c_longlong, c_i32p, C.c_int, C.c_int, C.c_int,
                                                 C.c_int, C.c_int, C.c_int, C.c_int, c_i32p, C.c_int, c_i32p, c_ptr, c_i32p, c_i32p,
                                                 c_ptr, C.c_size_t, c_ptr, c_ptr, C.c_double, C.c_double]),
+    "pgasr_ctc_beam_search_wide_bias": (C.c_int, [c_ptr, C.c_int, C.c_longlong, C.c_longlong, c_i32p, C.c_int, C.c_int, C.c_int,
+                                                  C.c_int, C.c_int, C.c_int, C.c_int, c_i32p, C.c_int, c_i32p, c_ptr, c_i32p, c_i32p,
+                                                  c_ptr, C.c_size_t, c_ptr, c_ptr, C.c_double, C.c_double,
+                                                  c_ptr, C.c_int, C.c_double]),
     "pgasr_nbest_unit_lm_score": (C.c_int, [c_i32p, C.c_int, c_i32p, c_i32p, C.c_int, C.c_int, C.c_int, C.c_int, c_ptr, c_ptr,
                                             c_ptr]),
     "pgasr_nbest_rescore": (C.c_int, [c_i32p, C.c_int, c_i32p, c_i32p, c_ptr, C.c_int, C.c_int, C.c_int, C.c_int, c_f32p, C.c_int,

@@ -25,11 +25,13 @@
 //     at or above that cut -- exactly min(beam, all) by uniqueness of the key -- are then listed and sorted.  Both paths rank by the
 //     same key, so both are exact and equal.
 // Every loop is bounded by construction: hash probes by the table size, ancestor walks by lengths[b], radix passes by the key width.
-// With a back-off unit n-gram model (pgasr_ctc_beam_search_wide_lm) the same kernel fuses its scores in; see WideLm below.
+// With a back-off unit n-gram model (pgasr_ctc_beam_search_wide_lm) the same kernel fuses its scores in; see WideLm below.  With a
+// hotword automaton (pgasr_ctc_beam_search_wide_bias) it adds the phrase bonuses, with or without the model; see WideBias.
 #include "common.h"
 #include "beam_core.h"
 #include "unit_lm.h"
 #include <cmath>
+#include <type_traits>
 
 namespace {
 
@@ -106,14 +108,58 @@ struct WideLmLds {
 };
 constexpr size_t WIDE_LM_LDS_OFFSET = (sizeof(WideLds) + 15) / 16 * 16;
 
+// Hotword (contextual phrase) biasing (pgasr_ctc_beam_search_wide_bias; include/pgasr_hip.h, A7-WIDE-BIAS): A7-BIAS's algebra on this
+// kernel's candidates, over the dense automaton of lm.HotwordBias -- S * V 8-byte words {int32 next; float bonus}, word (q, s) at
+// q V + s, the layout beam.hip and hotword.hip read.  The table IS the row of every state, so nothing is cached or filled:
+//   * an entry carries st = the automaton state of its prefix (the root, 0, for the empty one; always inside [0, S): a next outside
+//     is taken as 0 where it is read) and own = the bonus of its own last emission, bonus[st(parent prefix), last];
+//   * every term that enters a prefix by an extension with a non-blank s gets w added: wb = __dmul_rn(weight, (double)bonus), w = wb
+//     without a model and __dadd_rn(__dadd_rn(__dmul_rn(alpha, (double)lp32), beta), wb) with one; the merged term of a stay candidate
+//     gets the entry's own w, from `own`;
+//   * a candidate (entry j, symbol s) reads word st_j V + s, consecutive lanes consecutive words, entry j + 1's while entry j's are
+//     scored; bonuses can be negative (leaving a phrase takes the pending credit back), so the threshold's extension candidate is the
+//     symbol of largest frame[s] + w, as with the model;
+//   * the thread that writes an extension winner re-reads its word -- one independent 8-byte load in front of trie_find_or_create --
+//     for the new state and the new own bonus.
+struct BiasWord { int32_t next; float bonus; };
+static_assert(sizeof(BiasWord) == 8, "a table word is 8 bytes");
+constexpr long long WIDE_BIAS_MAX_WORDS = 1ll << 24;      // S * V words (128 MiB), as A7-BIAS
+struct WideBias {
+    const BiasWord* table;   // S * V words
+    int n_states;            // S
+    double weight;
+};
+struct WideNoBias {};
+struct WideBiasLds {
+    int st[2][WIDE_KMAX];                       // the automaton state of the entry's prefix
+    float own[2][WIDE_KMAX];                    // bonus[st(parent prefix), last]: the bonus of the entry's own last emission
+};
+constexpr size_t WIDE_LM_BIAS_LDS_OFFSET = (WIDE_LM_LDS_OFFSET + sizeof(WideLmLds) + 15) / 16 * 16;
+
 template <bool FAST> __device__ __forceinline__ double wide_ext_w(double pbj, double pnbj, double ps, bool rep, double w) {
     const double eb = (pbj + ps) + w, en = (pnbj + ps) + w;
     return rep ? lse2x<FAST>(-INFINITY, eb) : lse3x<FAST>(-INFINITY, eb, en);
 }
 
-// LmArg: nothing (the search of A7-WIDE: its argument list, and with it its code, is what it was without the model) or WideLm<true>
+// LmArg: nothing (the search of A7-WIDE: its argument list, and with it its code, is what it was without a model), WideLm<true>,
+// WideBias, or WideLm<true> and WideBias in that order
+template <typename X, typename... A> constexpr bool wide_has = (std::is_same<X, A>::value || ...);
 __device__ __forceinline__ WideLm<false> wide_lm_of() { return {}; }
-__device__ __forceinline__ const WideLm<true>& wide_lm_of(const WideLm<true>& lm) { return lm; }
+__device__ __forceinline__ WideLm<false> wide_lm_of(const WideBias&) { return {}; }
+template <typename... R> __device__ __forceinline__ const WideLm<true>& wide_lm_of(const WideLm<true>& lm, const R&...) { return lm; }
+__device__ __forceinline__ WideNoBias wide_bias_of() { return {}; }
+__device__ __forceinline__ WideNoBias wide_bias_of(const WideLm<true>&) { return {}; }
+__device__ __forceinline__ const WideBias& wide_bias_of(const WideBias& bias) { return bias; }
+__device__ __forceinline__ const WideBias& wide_bias_of(const WideLm<true>&, const WideBias& bias) { return bias; }
+
+// w of a term: the model's word and the automaton's bonus, each where there is one (A7-LM / A7-BIAS: the roundings are contractual)
+template <typename Lm, typename Bs> __device__ __forceinline__ double wide_w(const Lm& lm, const Bs& bias, float word, float bonus) {
+    constexpr bool LM = std::is_same<Lm, WideLm<true>>::value, BIAS = std::is_same<Bs, WideBias>::value;
+    static_assert(LM || BIAS, "a term without a model has no w");
+    if constexpr (LM && BIAS) return __dadd_rn(__dadd_rn(__dmul_rn(lm.alpha, (double)word), lm.beta), __dmul_rn(bias.weight, (double)bonus));
+    else if constexpr (LM) return __dadd_rn(__dmul_rn(lm.alpha, (double)word), lm.beta);
+    else return __dmul_rn(bias.weight, (double)bonus);
+}
 
 template <typename TIn, bool FAST, typename... LmArg>
 __global__ __launch_bounds__(WIDE_THREADS) void beam_wide_kernel(
@@ -121,11 +167,13 @@ __global__ __launch_bounds__(WIDE_THREADS) void beam_wide_kernel(
     int T, int V, int K, int blank, int collapse, int force_counting, WideWs ws, int nbest, int tok_stride,
     int32_t* __restrict__ out_tokens, int32_t* __restrict__ out_len, double* __restrict__ out_score,
     int32_t* __restrict__ out_count, int32_t* __restrict__ out_counting, const LmArg... lmarg) {
-    constexpr bool LM = sizeof...(LmArg) != 0;
+    constexpr bool LM = wide_has<WideLm<true>, LmArg...>, BIAS = wide_has<WideBias, LmArg...>;
     [[maybe_unused]] const auto& lm = wide_lm_of(lmarg...);
+    [[maybe_unused]] const auto& bias = wide_bias_of(lmarg...);
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     WideLds& L = *reinterpret_cast<WideLds*>(smem);
     [[maybe_unused]] WideLmLds& M = *reinterpret_cast<WideLmLds*>(smem + WIDE_LM_LDS_OFFSET);
+    [[maybe_unused]] WideBiasLds& H = *reinterpret_cast<WideBiasLds*>(smem + (LM ? WIDE_LM_BIAS_LDS_OFFSET : WIDE_LM_LDS_OFFSET));
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     int Tb = lengths ? lengths[b] : T; Tb = Tb < 0 ? 0 : (Tb > T ? T : Tb);
     const int W = (V + 31) >> 5;                          // bitmap words per entry
@@ -138,6 +186,7 @@ __global__ __launch_bounds__(WIDE_THREADS) void beam_wide_kernel(
         L.id[0][0] = 0; L.last[0][0] = -1; L.par[0][0] = -1; L.pb[0][0] = 0.0; L.pnb[0][0] = -INFINITY;
         nodes[0] = 0xFFFFFFFFu;
         if constexpr (LM) { M.st[0][0] = lm.start; M.own[0][0] = 0.0f; M.isext[0] = 1; }
+        if constexpr (BIAS) { H.st[0][0] = 0; H.own[0][0] = 0.0f; }               // state 0 is the automaton's root
     }
     __syncthreads();
     [[maybe_unused]] float* lmrows = nullptr;
@@ -254,8 +303,11 @@ __global__ __launch_bounds__(WIDE_THREADS) void beam_wide_kernel(
                 time = t_own < time ? t_own : time;
                 if (i >= 0) {
                     double e1 = cpb[i] + pl, e2 = cpnb[i] + pl;                   // extension of parent i by lj (:90-96): touched first in iteration (lj, i)
-                    if constexpr (LM) {                                           // with the parent's context: the entry's own word
-                        const double w = __dadd_rn(__dmul_rn(lm.alpha, (double)M.own[cur][j]), lm.beta);
+                    if constexpr (LM || BIAS) {                                   // with the parent's context / state: the entry's own word
+                        float word = 0.0f, bonus = 0.0f;
+                        if constexpr (LM) word = M.own[cur][j];
+                        if constexpr (BIAS) bonus = H.own[cur][j];
+                        const double w = wide_w(lm, bias, word, bonus);
                         e1 += w; e2 += w;
                     }
                     const bool rep = (clast[i] == lj);
@@ -281,12 +333,21 @@ __global__ __launch_bounds__(WIDE_THREADS) void beam_wide_kernel(
             double best = -INFINITY;
             bool found = false;
             const int lj = clast[j];
-            if constexpr (LM) {      // the symbol of largest frame[s] + w (the lowest such s): that candidate's image, its w included
-                const float* rl = lmrows + (size_t)M.row[cur][j] * 2 * V;
+            if constexpr (LM || BIAS) {  // the symbol of largest frame[s] + w (the lowest such s): that candidate's image, its w included
+                [[maybe_unused]] const float* rl = nullptr;
+                [[maybe_unused]] const BiasWord* bt = nullptr;
+                if constexpr (LM) rl = lmrows + (size_t)M.row[cur][j] * 2 * V;
+                if constexpr (BIAS) bt = bias.table + (size_t)H.st[cur][j] * V;      // st < S: below S V words
+                auto w_of = [&](int s) {
+                    float word = 0.0f, bonus = 0.0f;
+                    if constexpr (LM) word = rl[s];
+                    if constexpr (BIAS) bonus = bt[s].bonus;
+                    return wide_w(lm, bias, word, bonus);
+                };
                 int bs = -1;
                 for (int s = lane; s < V; s += 64) {
                     if (s == blank || s == lj || ((L.bitmap[j * W + (s >> 5)] >> (s & 31)) & 1u)) continue;
-                    const double v = L.frame[s] + __dadd_rn(__dmul_rn(lm.alpha, (double)rl[s]), lm.beta);
+                    const double v = L.frame[s] + w_of(s);
                     if (bs < 0 || v > best) { best = v; bs = s; }
                 }
                 if (bs < 0) best = -INFINITY;
@@ -298,7 +359,7 @@ __global__ __launch_bounds__(WIDE_THREADS) void beam_wide_kernel(
                 if (lane == 0) {
                     unsigned long long img = 0ull;
                     if (any && s1 >= 0) {                                         // s1 < 0: every sum is NaN or none compares equal -- no bound from this entry
-                        const double w = __dadd_rn(__dmul_rn(lm.alpha, (double)rl[s1]), lm.beta);
+                        const double w = w_of(s1);
                         img = ordered_key(lse2x<FAST>(-INFINITY, wide_ext_w<FAST>(cpb[j], cpnb[j], L.frame[s1], false, w)));
                     }
                     L.tkeys[nb + j] = img;
@@ -333,21 +394,31 @@ __global__ __launch_bounds__(WIDE_THREADS) void beam_wide_kernel(
 
         // every candidate of the frame, visited by all threads in step (the appends are wave-aggregated): f(valid, image, time, cand)
         auto for_each_candidate = [&](auto&& f) {
-            if constexpr (LM) {      // the same visits; entry j + 1's words are loaded while entry j's candidates are scored
+            if constexpr (LM || BIAS) {  // the same visits; entry j + 1's words are loaded while entry j's candidates are scored
                 constexpr int NV = WIDE_VMAX / WIDE_THREADS;
-                float wn[NV];
+                [[maybe_unused]] float wn[NV], bn[NV];
                 auto load_words = [&](int j) {
-                    const float* rl = lmrows + (size_t)M.row[cur][j] * 2 * V;
+                    if constexpr (LM) {
+                        const float* rl = lmrows + (size_t)M.row[cur][j] * 2 * V;
 #pragma unroll
-                    for (int k = 0; k < NV; ++k) { const int s = k * WIDE_THREADS + tid; wn[k] = s < V ? rl[s] : 0.0f; }
+                        for (int k = 0; k < NV; ++k) { const int s = k * WIDE_THREADS + tid; wn[k] = s < V ? rl[s] : 0.0f; }
+                    }
+                    if constexpr (BIAS) {
+                        const BiasWord* bt = bias.table + (size_t)H.st[cur][j] * V;
+#pragma unroll
+                        for (int k = 0; k < NV; ++k) { const int s = k * WIDE_THREADS + tid; bn[k] = s < V ? bt[s].bonus : 0.0f; }
+                    }
                 };
                 if (nb > 0) load_words(0);
                 for (int j = 0; j < nb; ++j) {
                     const double pbj = cpb[j], pnbj = cpnb[j];
                     const int lj = clast[j];
-                    float wc[NV];
+                    [[maybe_unused]] float wc[NV], bc[NV];
 #pragma unroll
-                    for (int k = 0; k < NV; ++k) wc[k] = wn[k];
+                    for (int k = 0; k < NV; ++k) {
+                        if constexpr (LM) wc[k] = wn[k];
+                        if constexpr (BIAS) bc[k] = bn[k];
+                    }
                     if (j + 1 < nb) load_words(j + 1);
 #pragma unroll
                     for (int k = 0; k < NV; ++k) {
@@ -357,7 +428,10 @@ __global__ __launch_bounds__(WIDE_THREADS) void beam_wide_kernel(
                         if (valid) valid = !((L.bitmap[j * W + (s >> 5)] >> (s & 31)) & 1u);
                         unsigned long long img = 0ull;
                         if (valid) {
-                            const double w = __dadd_rn(__dmul_rn(lm.alpha, (double)wc[k]), lm.beta);
+                            float word = 0.0f, bonus = 0.0f;
+                            if constexpr (LM) word = wc[k];
+                            if constexpr (BIAS) bonus = bc[k];
+                            const double w = wide_w(lm, bias, word, bonus);
                             img = ordered_key(lse2x<FAST>(-INFINITY, wide_ext_w<FAST>(pbj, pnbj, L.frame[s], s == lj, w)));
                         }
                         f(valid, img, 2u * (unsigned)(s * nb + j), (unsigned)(j * V + s));
@@ -466,15 +540,23 @@ __global__ __launch_bounds__(WIDE_THREADS) void beam_wide_kernel(
                 L.pb[nxt][tid] = L.st_pb[j]; L.pnb[nxt][tid] = L.st_pnb[j];
                 L.id[nxt][tid] = cid[j]; L.last[nxt][tid] = clast[j]; L.par[nxt][tid] = cpar[j];
                 if constexpr (LM) { M.st[nxt][tid] = M.st[cur][j]; M.row[nxt][tid] = M.row[cur][j]; M.own[nxt][tid] = M.own[cur][j]; M.isext[tid] = 0; }
+                if constexpr (BIAS) { H.st[nxt][tid] = H.st[cur][j]; H.own[nxt][tid] = H.own[cur][j]; }
             } else {
                 const int j = (int)it.cand / V, s = (int)it.cand - j * V;
                 L.pb[nxt][tid] = -INFINITY;
-                if constexpr (LM) {      // the candidate's score as its key had it; its word becomes the entry's own, next[s] its state
-                    const float* rl = lmrows + (size_t)M.row[cur][j] * 2 * V;
-                    const float word = rl[s];
-                    const double w = __dadd_rn(__dmul_rn(lm.alpha, (double)word), lm.beta);
+                if constexpr (LM || BIAS) {  // the candidate's score as its key had it; its word becomes the entry's own, next[s] its state
+                    [[maybe_unused]] const float* rl = nullptr;
+                    [[maybe_unused]] BiasWord bw = {0, 0.0f};
+                    float word = 0.0f;
+                    if constexpr (BIAS) bw = bias.table[(size_t)H.st[cur][j] * V + s];      // st < S: below S V words
+                    if constexpr (LM) { rl = lmrows + (size_t)M.row[cur][j] * 2 * V; word = rl[s]; }
+                    const double w = wide_w(lm, bias, word, bw.bonus);
                     L.pnb[nxt][tid] = wide_ext_w<FAST>(cpb[j], cpnb[j], L.frame[s], s == clast[j], w);
-                    M.st[nxt][tid] = reinterpret_cast<const int*>(rl + V)[s]; M.own[nxt][tid] = word; M.isext[tid] = 1;
+                    if constexpr (LM) { M.st[nxt][tid] = reinterpret_cast<const int*>(rl + V)[s]; M.own[nxt][tid] = word; M.isext[tid] = 1; }
+                    if constexpr (BIAS) {
+                        H.st[nxt][tid] = ((unsigned)bw.next < (unsigned)bias.n_states) ? bw.next : 0;
+                        H.own[nxt][tid] = bw.bonus;
+                    }
                 } else
                 L.pnb[nxt][tid] = wide_ext<FAST>(cpb[j], cpnb[j], L.frame[s], s == clast[j]);
                 // canonical node for (id[j], s): look up, else create
@@ -502,18 +584,31 @@ inline size_t wide_lm_ws_layout(int T, int B, int V, int beam, WideWs* ws, float
 }
 
 static_assert(2 * WIDE_KMAX == WIDE_THREADS, "one threshold slot and one histogram bin per thread");
-static_assert(WIDE_LM_LDS_OFFSET + sizeof(WideLmLds) <= 160 * 1024, "LDS");
+static_assert(WIDE_LM_BIAS_LDS_OFFSET + sizeof(WideBiasLds) <= 160 * 1024, "LDS");
 
-// The host side of both entries.  The checks are pgasr_ctc_beam_search_nbest's in its order and with its status codes, lm_check()
-// (the model's) where that entry checks its flags, then the room for a model's row cache behind the trie; nothing touches HIP until
-// every check has passed.  Then the hash table is cleared and beam_wide_kernel<TIn, FAST, LmArg...> launched.  LmArg: nothing, or
-// the WideLm<true> that lm_check() fills in; its rows are set here.
+// the model's checks (A7-WIDE-LM), then its kernel arguments but for the rows
+inline int wide_lm_check(WideLm<true>* lm, const pgasr_unit_lm_tables* tables, int V, int blank, double lm_alpha, double lm_beta) {
+    if (const int st = unit_lm::check_tables(tables, V, blank, lm_alpha, lm_beta)) return st;
+    lm->states = (const int4*)tables->states; lm->succ = (const int4*)tables->succ;
+    lm->n_states = tables->n_states; lm->n_succ = tables->n_succ; lm->start = tables->start; lm->order = tables->order;
+    lm->alpha = lm_alpha; lm->beta = lm_beta;
+    return PGASR_OK;
+}
+
+inline float** wide_rows_of() { return nullptr; }
+inline float** wide_rows_of(WideBias&) { return nullptr; }
+template <typename... R> inline float** wide_rows_of(WideLm<true>& lm, R&...) { return &lm.rows; }
+
+// The host side of all entries.  The checks are pgasr_ctc_beam_search_nbest's in its order and with its status codes, lm_check()
+// (the models') where that entry checks its flags, then the room for a model's row cache behind the trie; nothing touches HIP until
+// every check has passed.  Then the hash table is cleared and beam_wide_kernel<TIn, FAST, LmArg...> launched.  LmArg: nothing, the
+// WideLm<true> and / or the WideBias that lm_check() fills in; the model's rows are set here.
 template <typename LmCheck, typename... LmArg>
 int wide_search(const void* log_probs, int is_f64, long long stride_t, long long stride_b, const int32_t* lengths, int T, int B, int V,
                 int beam, int blank, int flags, int nbest, int32_t* out_tokens, int tok_stride, int32_t* out_len, double* out_score,
                 int32_t* out_count, int32_t* out_counting_frames, void* workspace, size_t workspace_bytes, void* stream,
                 LmCheck&& lm_check, LmArg&... lm) {
-    constexpr bool LM = sizeof...(LmArg) != 0;
+    constexpr bool LM = wide_has<WideLm<true>, LmArg...>, BIAS = wide_has<WideBias, LmArg...>;
     WideWs ws;
     if (const int st = beam_check_args(log_probs, out_tokens, out_len, out_score, T, B, V, beam, blank, WIDE_VMAX, WIDE_KMAX,
                                        [&] {
@@ -522,10 +617,11 @@ int wide_search(const void* log_probs, int is_f64, long long stride_t, long long
                                        },
                                        workspace, workspace_bytes, &ws)) return st;
     if constexpr (LM)
-        if (workspace_bytes < wide_lm_ws_layout(T, B, V, beam, &ws, &lm.rows..., (char*)workspace)) return PGASR_ERR_WORKSPACE;
+        if (workspace_bytes < wide_lm_ws_layout(T, B, V, beam, &ws, wide_rows_of(lm...), (char*)workspace)) return PGASR_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     if (hipMemsetAsync(ws.table, 0, (size_t)B * ws.H * sizeof(unsigned long long), st) != hipSuccess) return PGASR_ERR_LAUNCH;
-    constexpr size_t lds = ((LM ? WIDE_LM_LDS_OFFSET + sizeof(WideLmLds) : sizeof(WideLds)) + 15) / 16 * 16;
+    constexpr size_t lds_lm = LM ? WIDE_LM_LDS_OFFSET + sizeof(WideLmLds) : sizeof(WideLds);
+    constexpr size_t lds = ((BIAS ? (LM ? WIDE_LM_BIAS_LDS_OFFSET : WIDE_LM_LDS_OFFSET) + sizeof(WideBiasLds) : lds_lm) + 15) / 16 * 16;
 #define WIDE_LAUNCH(TIN, FAST)                                                                                                    \
     {                                                                                                                             \
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&beam_wide_kernel<TIN, FAST, LmArg...>),                          \
@@ -573,12 +669,41 @@ extern "C" int pgasr_ctc_beam_search_wide_lm(const void* log_probs, int is_f64, 
     return wide_search(log_probs, is_f64, stride_t, stride_b, lengths, T, B, V, beam, blank, flags, nbest, out_tokens, tok_stride,
                        out_len, out_score, out_count, out_counting_frames, workspace, workspace_bytes, stream,
                        [&] {
-                           if (const int st = unit_lm::check_tables(tables, V, blank, lm_alpha, lm_beta)) return st;
-                           lm.states = (const int4*)tables->states; lm.succ = (const int4*)tables->succ;
-                           lm.n_states = tables->n_states; lm.n_succ = tables->n_succ; lm.start = tables->start; lm.order = tables->order;
-                           lm.alpha = lm_alpha; lm.beta = lm_beta;
-                           return (int)PGASR_OK;
+                           return wide_lm_check(&lm, tables, V, blank, lm_alpha, lm_beta);
                        },
                        lm);
 }
 
+
+// A7-WIDE-BIAS: the search with a hotword automaton, with or without the unit model; without a table it is one of the two entries above
+extern "C" int pgasr_ctc_beam_search_wide_bias(const void* log_probs, int is_f64, long long stride_t, long long stride_b,
+                                               const int32_t* lengths, int T, int B, int V, int beam, int blank, int flags,
+                                               int nbest, int32_t* out_tokens, int tok_stride, int32_t* out_len, double* out_score,
+                                               int32_t* out_count, int32_t* out_counting_frames,
+                                               void* workspace, size_t workspace_bytes, void* stream,
+                                               const pgasr_unit_lm_tables* tables, double lm_alpha, double lm_beta,
+                                               const void* bias_table, int bias_states, double bias_weight) {
+    if (!bias_table && bias_states == 0) {
+        if (!tables)
+            return pgasr_ctc_beam_search_wide(log_probs, is_f64, stride_t, stride_b, lengths, T, B, V, beam, blank, flags, nbest, out_tokens,
+                                              tok_stride, out_len, out_score, out_count, out_counting_frames, workspace, workspace_bytes, stream);
+        return pgasr_ctc_beam_search_wide_lm(log_probs, is_f64, stride_t, stride_b, lengths, T, B, V, beam, blank, flags, nbest, out_tokens,
+                                             tok_stride, out_len, out_score, out_count, out_counting_frames, workspace, workspace_bytes,
+                                             stream, tables, lm_alpha, lm_beta);
+    }
+    WideLm<true> lm;
+    WideBias bias;
+    const auto check = [&] {
+        if (tables)
+            if (const int st = wide_lm_check(&lm, tables, V, blank, lm_alpha, lm_beta)) return st;
+        if (!bias_table || bias_states < 1 || (long long)bias_states * V > WIDE_BIAS_MAX_WORDS || !std::isfinite(bias_weight))
+            return (int)PGASR_ERR_INVALID_ARG;
+        bias.table = (const BiasWord*)bias_table; bias.n_states = bias_states; bias.weight = bias_weight;
+        return (int)PGASR_OK;
+    };
+    if (tables)
+        return wide_search(log_probs, is_f64, stride_t, stride_b, lengths, T, B, V, beam, blank, flags, nbest, out_tokens, tok_stride,
+                           out_len, out_score, out_count, out_counting_frames, workspace, workspace_bytes, stream, check, lm, bias);
+    return wide_search(log_probs, is_f64, stride_t, stride_b, lengths, T, B, V, beam, blank, flags, nbest, out_tokens, tok_stride,
+                       out_len, out_score, out_count, out_counting_frames, workspace, workspace_bytes, stream, check, bias);
+}

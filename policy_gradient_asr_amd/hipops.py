@@ -1859,7 +1859,7 @@ def _unit_lm_check(unit_lm, V, blank):
 
 
 def ctc_beam_search_wide(log_probs, lengths=None, beam=5, nbest=None, blank=0, collapse=False, counting=False, stats=False,
-                         unit_lm=None, lm_alpha=0.0, lm_beta=0.0):
+                         unit_lm=None, lm_alpha=0.0, lm_beta=0.0, bias=None, bias_weight=0.0):
     """The exact prefix beam search over rows of up to MAX_VOCAB_SEARCH_WIDE = 1024 symbols (pgasr_ctc_beam_search_wide; narrower
     rows are taken too): log_probs (T,B,V) fp32 or fp64 as ``ctc_beam_search`` takes them, beam <= 128, no language model.
     nbest=None (default): the triple of ``ctc_beam_search`` -- tokens (B,T) int32, token_lengths (B) int32, score (B) float64.
@@ -1872,9 +1872,15 @@ def ctc_beam_search_wide(log_probs, lengths=None, beam=5, nbest=None, blank=0, c
     unit_lm: None (default: the acoustic search, the kernels and bits it always had) or a ``lm.UnitNgramLM`` over the same V symbols
     and blank: every extension by a non-blank s gets ``lm_alpha * ln p_lm(s | context) + lm_beta`` added (pgasr_ctc_beam_search_wide_lm;
     include/pgasr_hip.h, A7-WIDE-LM) and the returned score is a FUSED score.  lm_alpha = lm_beta = 0 returns the words of the call
-    without a model."""
+    without a model.
+    bias: None (default: the calls above, launch for launch) or a ``lm.HotwordBias`` over the same V symbols and blank: every
+    extension by a non-blank s also gets ``bias_weight * bonus(state of the prefix, s)`` added inside the search
+    (pgasr_ctc_beam_search_wide_bias; include/pgasr_hip.h, A7-WIDE-BIAS), with or without ``unit_lm``; the returned score is a FUSED
+    score.  bias_weight = 0 returns the words of the call without a bias."""
     if unit_lm is not None:
         _unit_lm_check(unit_lm, log_probs.shape[-1], blank)
+    if bias is not None:
+        bias_table, bias_states = _bias_table(bias, log_probs.shape[-1], blank, log_probs.device)
     lib = _lib.load()
     T, B, V = _search_inputs(log_probs, lengths)
     N, dev = (1 if nbest is None else int(nbest)), log_probs.device
@@ -1883,6 +1889,9 @@ def ctc_beam_search_wide(log_probs, lengths=None, beam=5, nbest=None, blank=0, c
     else:
         entry, label, ws_bytes = "pgasr_ctc_beam_search_wide_lm", "beam_search_wide_lm", lib.pgasr_beam_wide_lm_workspace_bytes
         lm_args = (ctypes.byref(unit_lm.device_tables(dev).struct), float(lm_alpha), float(lm_beta))
+    if bias is not None:     # one entry for both: the model's arguments (NULL tables without one), then the automaton's
+        entry, label = "pgasr_ctc_beam_search_wide_bias", "beam_search_wide_bias"
+        lm_args = (lm_args or (None, 0.0, 0.0)) + (_p(bias_table), bias_states, float(bias_weight))
     ws = _workspace(ws_bytes(T, B, V, int(beam)), dev, "beam_wide")
     tokens, tl, score, count = _nbest_outputs(N, B, T, dev)
     frames = torch.empty(B, dtype=torch.int32, device=dev) if stats else None

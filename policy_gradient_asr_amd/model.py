@@ -569,7 +569,7 @@ def predict(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=N
             mbr=False, mbr_unit="char", mbr_scale=1.0, rescore_word_lm_path=None, rescore_word_alpha=0.0, rescore_word_beta=0.0,
             error_report=False, units_path=None, wide_beam=False, wide_second_pass=False, unit_lm_path=None, unit_lm_alpha=0.0,
             unit_lm_beta=0.0, rescore_unit_lm_path=None, rescore_unit_alpha=0.0, rescore_unit_beta=0.0, spelled=False,
-            hotwords_path=None, hotword_weight=1.0, hotword_boost=1.0):
+            wide_hotwords=False, hotwords_path=None, hotword_weight=1.0, hotword_boost=1.0):
     """model.py:277-339: load model_best.pth, forward, beam=5 prefix search (device side, batched),
     collapse_fn, CER/WER, predicted.txt.  Frames are cut by the FEATURE mask (the reference cuts the
     time axis by the target mask, model.py:322 -- a listed defect).  Returns (CER, WER).
@@ -644,7 +644,13 @@ def predict(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=N
     >= 1; the first-pass scores are then fused scores) -- not with lm_fast=True or unit_lm_path, whose kernels have no bias.  A wider
     alphabet: with units_path, wide_beam=True and wide_second_pass=True (nbest >= 2) the phrases are encoded with the units, each
     in isolation, and the bias goes into the second pass over the wide lists (``CTCDecoder.rescore(bias=)``); the wide search itself
-    has no bias, so any other combination raises a ValueError that names the missing option."""
+    takes no bias unless ``wide_hotwords`` is given, so any other combination raises a ValueError that names the missing option.
+    wide_hotwords: False (default: everything above, nothing else -- every refusal above stands) or True, with units_path,
+    wide_beam=True and hotwords_path (ValueError naming the missing one): the phrases, compiled with the units, are fused into the
+    wide search itself (``CTCDecoder(wide_search=True, wide_hotwords=True, hotwords=)``, csrc/beam_wide.hip), together with
+    unit_lm_path if given and without needing wide_second_pass; the first-pass scores are then fused scores.  With
+    wide_second_pass=True as well the second pass applies ``rescore(bias=)`` as above: the first pass gets the phrase into the list,
+    the exact-likelihood second pass ranks it, and ``nbest.tsv`` carries B(y) of every hypothesis as its last column."""
     import os
     import functools
     import torch.utils.data as tud
@@ -675,12 +681,18 @@ def predict(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=N
         raise ValueError("minimum-Bayes-risk decoding needs a list: give nbest >= 2 with mbr=True")
     if mbr and mbr_unit not in ("char", "word"):
         raise ValueError(f"mbr_unit must be 'char' or 'word' (got {mbr_unit!r})")
+    if wide_hotwords:
+        for name, given in (("wide_beam", bool(wide_beam)), ("units_path", units_path is not None),
+                            ("hotwords_path", hotwords_path is not None)):
+            if not given:
+                raise ValueError(f"{name}: wide_hotwords fuses the phrases of hotwords_path into the wide search over units; give "
+                                 f"units_path, wide_beam=True and hotwords_path with it")
     if hotwords_path is not None:
         if greedy:
             raise ValueError("hotwords_path: greedy decoding (beam_size=0) has no hotword bias; give beam_size >= 1")
         if lm_fast:
             raise ValueError("lm_fast: the single-wave kernel has no hotword bias; give lm_fast=False with hotwords_path")
-        if unit_lm_path is not None:
+        if unit_lm_path is not None and not wide_hotwords:
             raise ValueError("unit_lm_path: the wide search it is fused into has no hotword bias; not together with hotwords_path")
     char_alphabet_path = alphabet_path
     if units_path is not None:
@@ -726,7 +738,7 @@ def predict(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=N
     hotwords = rescore_bias = None
     if hotwords_path is not None:
         from .lm import HotwordBias
-        if len(alphabet) > hipops.MAX_VOCAB_NARROW:
+        if len(alphabet) > hipops.MAX_VOCAB_NARROW and not wide_hotwords:
             for name, given in (("units_path", units_path is not None), ("wide_beam", wide), ("wide_second_pass", second)):
                 if not given:
                     raise ValueError(f"{name}: hotwords over {len(alphabet)} > {hipops.MAX_VOCAB_NARROW} symbols go into the second pass "
@@ -740,8 +752,9 @@ def predict(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=N
             bias = HotwordBias.from_strings(lines, alphabet, boost=hotword_boost)
         if bias.vocab != len(alphabet):
             raise ValueError(f"hotwords_path: the phrases compile to {bias.vocab} symbols; {alphabet_path} has {len(alphabet)}")
-        if len(alphabet) > hipops.MAX_VOCAB_NARROW:
-            rescore_bias = bias
+        if len(alphabet) > hipops.MAX_VOCAB_NARROW:      # the second pass over the wide lists, and / or the wide search itself
+            rescore_bias = bias if second else None
+            hotwords = bias if wide_hotwords else None
         else:
             hotwords = bias
     if len(alphabet) > hipops.MAX_VOCAB_NARROW and not greedy and not wide:
@@ -770,11 +783,13 @@ def predict(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=N
                 unit_lm = m
             else:
                 rescore_unit_lm = m
+    hotword_args = {} if hotwords is None else {"hotwords": hotwords, "hotword_weight": hotword_weight}
     if unit_lm is not None:
-        decoder = CTCDecoder(alphabet, lm_alpha=unit_lm_alpha, lm_beta=unit_lm_beta, wide_search=True, unit_lm=unit_lm)
+        decoder = CTCDecoder(alphabet, lm_alpha=unit_lm_alpha, lm_beta=unit_lm_beta, wide_search=True, unit_lm=unit_lm,
+                             wide_hotwords=bool(wide_hotwords), **hotword_args)
     else:
         decoder = CTCDecoder(alphabet, lm=lm, lm_alpha=lm_alpha, lm_beta=lm_beta, fast_lm=bool(lm_fast), wide_search=wide,
-                             **({} if hotwords is None else {"hotwords": hotwords, "hotword_weight": hotword_weight}))
+                             wide_hotwords=bool(wide_hotwords) and wide, **hotword_args)
     list_text = to_text if wide else collapse_fn      # a wide list holds units: their concatenation is the text
     if mbr and mbr_unit == "word" and spelling is None and " " not in char2ind:
         raise ValueError("mbr_unit='word' needs an alphabet with the ' ' symbol")
@@ -805,7 +820,7 @@ def predict(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=N
             lp = Fh.LogSoftmaxFn.apply(logits)
             if nbest > 1:
                 nb = decoder.decode_batch(lp, in_len, beam_size=beam_size, nbest=nbest)
-                tok, tl, total, words, units_lp = nb.tokens[0], nb.lengths[0], None, None, None
+                tok, tl, total, words, units_lp, bias_col = nb.tokens[0], nb.lengths[0], None, None, None, None
                 if rescore_lm is not None or word_lm is not None or second or rescore_unit_lm is not None:
                     rs = decoder.rescore(lp, in_len, nb, lm=rescore_lm, lm_alpha=rescore_alpha if rescore_lm is not None else 0.0,
                                          lm_beta=rescore_beta if rescore_lm is not None else 0.0, **word_args)
@@ -814,6 +829,8 @@ def predict(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=N
                         words = (rs.word_logp.cpu(), rs.n_words.cpu(), rs.n_oov.cpu())
                     if rescore_unit_lm is not None:
                         units_lp = rs.unit_logp.cpu()
+                    if wide_hotwords and rescore_bias is not None:
+                        bias_col = rs.bias.cpu()
                 if mbr:
                     score = rs.total if total is not None else decoder.rescore(lp, in_len, nb, lm=None).total
                     if spelling is not None:
@@ -841,6 +858,8 @@ def predict(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=N
                                                                                   int(words[2][r, i]))
                         if units_lp is not None:
                             extra += "\t{:.6f}".format(float(units_lp[r, i]))
+                        if bias_col is not None:
+                            extra += "\t{:.6f}".format(float(bias_col[r, i]))
                         nbest_lines.append("{}\t{}\t{:.6f}\t{}\t{}{}\n".format(n + i, r, float(nscore[r, i]),
                                                                             "" if total is None else "{:.6f}".format(float(total[r, i])),
                                                                             text, extra))
