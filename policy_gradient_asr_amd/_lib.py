@@ -19,6 +19,16 @@ c_f32p = C.c_void_p   # device pointers travel as integers (tensor.data_ptr())
 c_i32p = C.c_void_p
 c_ptr = C.c_void_p
 
+# The eight beam-search entries share their argument list piece by piece (include/pgasr_hip.h, A7-*)
+_S_HEAD = [c_ptr, C.c_int, C.c_longlong, C.c_longlong, c_i32p] + [C.c_int] * 6   # log_probs, is_f64, strides, lengths, T, B, V, beam, blank, flags
+_S_BEST = [c_i32p, c_i32p, c_ptr]                                    # out_tokens, out_len, out_score
+_S_LIST = [C.c_int, c_i32p, C.c_int, c_i32p, c_ptr, c_i32p]          # nbest, out_tokens, tok_stride, out_len, out_score, out_count
+_S_WS = [c_ptr, C.c_size_t, c_ptr]                                   # workspace, workspace_bytes, stream
+_S_LM = [c_f32p, C.c_int, C.c_double, C.c_double]                    # lm_table, lm_order, lm_alpha, lm_beta
+_S_UNIT_LM = [c_ptr, C.c_double, C.c_double]                         # tables, lm_alpha, lm_beta
+_S_BIAS = [c_ptr, C.c_int, C.c_double]                               # bias_table, bias_states, bias_weight
+_S_WIDE = _S_HEAD + _S_LIST + [c_i32p] + _S_WS                       # ... out_counting_frames
+
 # name -> (restype, argtypes).  Mirrors include/pgasr_hip.h one to one.
 SIGNATURES = {
     "pgasr_abi_version": (C.c_int, []),
@@ -94,35 +104,18 @@ SIGNATURES = {
     "pgasr_reinforce_grad": (C.c_int, [c_f32p, c_i32p, c_f32p, c_i32p, C.c_int, C.c_int, C.c_int, C.c_int,
                                        c_f32p, c_ptr]),
     "pgasr_beam_workspace_bytes": (C.c_size_t, [C.c_int] * 4),
-    "pgasr_ctc_beam_search": (C.c_int, [c_ptr, C.c_int, C.c_longlong, C.c_longlong, c_i32p, C.c_int, C.c_int, C.c_int,
-                                        C.c_int, C.c_int, C.c_int, c_i32p, c_i32p, c_ptr, c_ptr, C.c_size_t, c_ptr]),
-    "pgasr_ctc_beam_search_lm": (C.c_int, [c_ptr, C.c_int, C.c_longlong, C.c_longlong, c_i32p, C.c_int, C.c_int, C.c_int,
-                                           C.c_int, C.c_int, C.c_int, c_i32p, c_i32p, c_ptr, c_ptr, C.c_size_t, c_ptr,
-                                           c_f32p, C.c_int, C.c_double, C.c_double]),
+    "pgasr_ctc_beam_search": (C.c_int, _S_HEAD + _S_BEST + _S_WS),
+    "pgasr_ctc_beam_search_lm": (C.c_int, _S_HEAD + _S_BEST + _S_WS + _S_LM),
     "pgasr_beam_lm_single_wave_ok": (C.c_int, [C.c_int] * 5),
-    "pgasr_ctc_beam_search_nbest": (C.c_int, [c_ptr, C.c_int, C.c_longlong, C.c_longlong, c_i32p, C.c_int, C.c_int, C.c_int,
-                                              C.c_int, C.c_int, C.c_int, C.c_int, c_i32p, C.c_int, c_i32p, c_ptr, c_i32p,
-                                              c_ptr, C.c_size_t, c_ptr, c_f32p, C.c_int, C.c_double, C.c_double]),
-    "pgasr_ctc_beam_search_bias": (C.c_int, [c_ptr, C.c_int, C.c_longlong, C.c_longlong, c_i32p, C.c_int, C.c_int, C.c_int,
-                                             C.c_int, C.c_int, C.c_int, c_i32p, c_i32p, c_ptr, c_ptr, C.c_size_t, c_ptr,
-                                             c_f32p, C.c_int, C.c_double, C.c_double, c_ptr, C.c_int, C.c_double]),
-    "pgasr_ctc_beam_search_nbest_bias": (C.c_int, [c_ptr, C.c_int, C.c_longlong, C.c_longlong, c_i32p, C.c_int, C.c_int, C.c_int,
-                                                   C.c_int, C.c_int, C.c_int, C.c_int, c_i32p, C.c_int, c_i32p, c_ptr, c_i32p,
-                                                   c_ptr, C.c_size_t, c_ptr, c_f32p, C.c_int, C.c_double, C.c_double,
-                                                   c_ptr, C.c_int, C.c_double]),
+    "pgasr_ctc_beam_search_nbest": (C.c_int, _S_HEAD + _S_LIST + _S_WS + _S_LM),
+    "pgasr_ctc_beam_search_bias": (C.c_int, _S_HEAD + _S_BEST + _S_WS + _S_LM + _S_BIAS),
+    "pgasr_ctc_beam_search_nbest_bias": (C.c_int, _S_HEAD + _S_LIST + _S_WS + _S_LM + _S_BIAS),
     "pgasr_nbest_bias_score": (C.c_int, [c_i32p, c_i32p, c_i32p, C.c_int, C.c_int, C.c_int, C.c_int, c_ptr, C.c_int, c_ptr, c_ptr]),
     "pgasr_beam_wide_workspace_bytes": (C.c_size_t, [C.c_int] * 4),
-    "pgasr_ctc_beam_search_wide": (C.c_int, [c_ptr, C.c_int, C.c_longlong, C.c_longlong, c_i32p, C.c_int, C.c_int, C.c_int,
-                                             C.c_int, C.c_int, C.c_int, C.c_int, c_i32p, C.c_int, c_i32p, c_ptr, c_i32p, c_i32p,
-                                             c_ptr, C.c_size_t, c_ptr]),
+    "pgasr_ctc_beam_search_wide": (C.c_int, _S_WIDE),
     "pgasr_beam_wide_lm_workspace_bytes": (C.c_size_t, [C.c_int] * 4),
-    "pgasr_ctc_beam_search_wide_lm": (C.c_int, [c_ptr, C.c_int, C.c_longlong, C.c_longlong, c_i32p, C.c_int, C.c_int, C.c_int,
-                                                C.c_int, C.c_int, C.c_int, C.c_int, c_i32p, C.c_int, c_i32p, c_ptr, c_i32p, c_i32p,
-                                                c_ptr, C.c_size_t, c_ptr, c_ptr, C.c_double, C.c_double]),
-    "pgasr_ctc_beam_search_wide_bias": (C.c_int, [c_ptr, C.c_int, C.c_longlong, C.c_longlong, c_i32p, C.c_int, C.c_int, C.c_int,
-                                                  C.c_int, C.c_int, C.c_int, C.c_int, c_i32p, C.c_int, c_i32p, c_ptr, c_i32p, c_i32p,
-                                                  c_ptr, C.c_size_t, c_ptr, c_ptr, C.c_double, C.c_double,
-                                                  c_ptr, C.c_int, C.c_double]),
+    "pgasr_ctc_beam_search_wide_lm": (C.c_int, _S_WIDE + _S_UNIT_LM),
+    "pgasr_ctc_beam_search_wide_bias": (C.c_int, _S_WIDE + _S_UNIT_LM + _S_BIAS),
     "pgasr_nbest_unit_lm_score": (C.c_int, [c_i32p, C.c_int, c_i32p, c_i32p, C.c_int, C.c_int, C.c_int, C.c_int, c_ptr, c_ptr,
                                             c_ptr]),
     "pgasr_nbest_rescore": (C.c_int, [c_i32p, C.c_int, c_i32p, c_i32p, c_ptr, C.c_int, C.c_int, C.c_int, C.c_int, c_f32p, C.c_int,

@@ -17,6 +17,7 @@
 // with the wide search (beam_wide.hip) and live in beam_core.h; the single-wave kernel further down (namespace sb) uses none of them.
 #include "common.h"
 #include "beam_core.h"
+#include "bias_table.h"
 #include <cmath>
 #include <type_traits>
 
@@ -77,9 +78,7 @@ template <bool LM> struct BeamNbest : BeamLm<LM> {
 //   * the thread that writes entry r of the new beam re-reads its winner's word for `next` -- one independent 8-byte load beside
 //     trie_find_or_create, instead of 4 K V bytes of LDS --; a next outside [0, S) is taken as state 0, so every index stays below S V.
 // The arguments ride behind the others in the last parameter: the BIAS = false instantiations keep their argument list and their code.
-struct BiasWord { int32_t next; float bonus; };
-static_assert(sizeof(BiasWord) == 8, "a table word is 8 bytes");
-constexpr long long BEAM_BIAS_MAX_WORDS = 1ll << 24;      // S * V words (128 MiB)
+using bias_table::BiasWord;
 template <bool LM, bool NBEST> using BeamTail = typename std::conditional<NBEST, BeamNbest<LM>, BeamLm<LM>>::type;
 template <bool LM, bool NBEST> struct BeamBiased : BeamTail<LM, NBEST> {
     const BiasWord* btable;  // S * V words
@@ -933,131 +932,146 @@ extern "C" size_t pgasr_beam_workspace_bytes(int T, int B, int V, int beam) {
     return trie_ws_layout<BEAM_SYM_BITS>(T, B, beam, nullptr, nullptr);
 }
 
+namespace {
+// the single-wave kernel's limits (namespace sb)
+inline bool beam_single_wave_fits(int T, int V, int beam) {
+    return beam <= sb::K_MAX && V <= sb::V_MAX && (long long)T * beam <= sb::MAX_NODES && T <= sb::MAX_TOKENS;
+}
+}  // namespace
+
 // Which kernel flags bit 4 picks (include/pgasr_hip.h, A7-LM): 1 = the single-wave kernel's LM instantiations.  Host only, no HIP call.
 extern "C" int pgasr_beam_lm_single_wave_ok(int T, int V, int beam, int is_f64, int lm_order) {
     if (T <= 0 || V <= 0 || beam <= 0 || lm_order <= 0 || is_f64) return 0;
-    if (beam > sb::K_MAX || V > sb::V_MAX || (long long)T * beam > sb::MAX_NODES || T > sb::MAX_TOKENS) return 0;
+    if (!beam_single_wave_fits(T, V, beam)) return 0;
     long long entries = 1;
     for (int k = 0; k < lm_order; ++k) { entries *= V; if (entries > BEAM_LM_MAX_ENTRIES) return 0; }      // such a table is refused by the search itself
     return 1;
 }
 
 namespace {
+// One call of the narrow search, as the five entries below fill it in: the common arguments, the list's (list = false: the 1-best
+// result), the language model's (lm_order = 0: none) and the bias automaton's (a NULL table with no states: none).
+struct BeamCall {
+    const void* log_probs; int is_f64; long long stride_t, stride_b; const int32_t* lengths; int T, B, V, beam, blank, flags;
+    int32_t* out_tokens; int32_t* out_len; double* out_score; void* workspace; size_t workspace_bytes; void* stream;
+    bool list = false; int nbest = 0, tok_stride = 0; int32_t* out_count = nullptr;
+    const float* lm_table = nullptr; int lm_order = 0; double lm_alpha = 0.0, lm_beta = 0.0;
+    const void* bias_table = nullptr; int bias_states = 0; double bias_weight = 0.0;
+
+    BeamCall& with_list(int n, int stride, int32_t* count) { list = true; nbest = n; tok_stride = stride; out_count = count; return *this; }
+    BeamCall& with_lm(const float* table, int order, double alpha, double beta) {
+        lm_table = table; lm_order = order; lm_alpha = alpha; lm_beta = beta; return *this;
+    }
+    BeamCall& with_bias(const void* table, int states, double weight) { bias_table = table; bias_states = states; bias_weight = weight; return *this; }
+};
+
 // the language model's arguments (no HIP call): PGASR_OK with *lm filled where lm_order > 0
-int beam_lm_args(int V, int blank, const float* lm_table, int lm_order, double lm_alpha, double lm_beta, BeamLm<true>* lm) {
-    if (lm_order < 0 || (lm_order > 0) != (lm_table != nullptr)) return PGASR_ERR_INVALID_ARG;
-    if (lm_order > 0) {
-        if (!std::isfinite(lm_alpha) || !std::isfinite(lm_beta)) return PGASR_ERR_INVALID_ARG;
+int beam_lm_args(const BeamCall& c, BeamLm<true>* lm) {
+    if (c.lm_order < 0 || (c.lm_order > 0) != (c.lm_table != nullptr)) return PGASR_ERR_INVALID_ARG;
+    if (c.lm_order > 0) {
+        if (!std::isfinite(c.lm_alpha) || !std::isfinite(c.lm_beta)) return PGASR_ERR_INVALID_ARG;
         long long entries = 1, ctx_mod = 1, ctx0 = 0;
-        for (int k = 0; k < lm_order; ++k) {
-            if (k == lm_order - 1) ctx_mod = entries;
-            entries *= V;
+        for (int k = 0; k < c.lm_order; ++k) {
+            if (k == c.lm_order - 1) ctx_mod = entries;
+            entries *= c.V;
             if (entries > BEAM_LM_MAX_ENTRIES) return PGASR_ERR_UNSUPPORTED;      // refused, never truncated
         }
-        for (int k = 0; k < lm_order - 1; ++k) ctx0 = ctx0 * V + blank;
-        lm->table = lm_table; lm->ctx_mod = (int)ctx_mod; lm->ctx0 = (int)ctx0; lm->alpha = lm_alpha; lm->beta = lm_beta;
+        for (int k = 0; k < c.lm_order - 1; ++k) ctx0 = ctx0 * c.V + c.blank;
+        *lm = {c.lm_table, (int)ctx_mod, (int)ctx0, c.lm_alpha, c.lm_beta};
     }
     return PGASR_OK;
 }
 
 // the bias table's arguments (no HIP call; include/pgasr_hip.h, A7-BIAS): a NULL table with no states is "no bias"
-int beam_bias_args(int V, int flags, const void* bias_table, int bias_states, double bias_weight) {
-    if (!bias_table && bias_states == 0) return PGASR_OK;
-    if (!bias_table || bias_states < 1 || (long long)bias_states * V > BEAM_BIAS_MAX_WORDS || !std::isfinite(bias_weight)) return PGASR_ERR_INVALID_ARG;
-    if (flags & (8 | 16)) return PGASR_ERR_UNSUPPORTED;      // the single-wave kernel has no bias: refused, never run differently
+int beam_bias_args(const BeamCall& c) {
+    if (!c.bias_table && c.bias_states == 0) return PGASR_OK;
+    if (!bias_table::usable(c.bias_table, c.bias_states, c.V) || !std::isfinite(c.bias_weight)) return PGASR_ERR_INVALID_ARG;
+    if (c.flags & (8 | 16)) return PGASR_ERR_UNSUPPORTED;      // the single-wave kernel has no bias: refused, never run differently
     return PGASR_OK;
 }
 
-int beam_search_impl(const void* log_probs, int is_f64, long long stride_t, long long stride_b,
-                     const int32_t* lengths, int T, int B, int V, int beam, int blank, int flags,
-                     int32_t* out_tokens, int32_t* out_len, double* out_score,
-                     void* workspace, size_t workspace_bytes, void* stream,
-                     const float* lm_table, int lm_order, double lm_alpha, double lm_beta,
-                     const void* bias_table = nullptr, int bias_states = 0, double bias_weight = 0.0) {
-    // the shared checks with the language model's arguments in their place, before any HIP call
-    BeamLm<true> lm{};
-    BeamWs ws;
-    if (const int st = beam_check_args(log_probs, out_tokens, out_len, out_score, T, B, V, beam, blank, BEAM_VMAX, BEAM_KMAX,
-                                       [&] {
-                                           if (const int s = beam_lm_args(V, blank, lm_table, lm_order, lm_alpha, lm_beta, &lm)) return s;
-                                           return beam_bias_args(V, flags, bias_table, bias_states, bias_weight);
-                                       },
-                                       workspace, workspace_bytes, &ws)) return st;
-    const bool with_lm = lm_order > 0;
-    if (bias_table) {      // always the workgroup-per-utterance kernel, BIAS = true
-        const size_t lds = beam_lds_bytes(beam, V, with_lm, true);
-        if (lds > 160 * 1024) return PGASR_ERR_UNSUPPORTED;
-        hipStream_t st = (hipStream_t)stream;
-        if (hipMemsetAsync(ws.table, 0, (size_t)B * ws.H * sizeof(unsigned long long), st) != hipSuccess) return PGASR_ERR_LAUNCH;
-        BeamBiased<true, false> bl{};
-        static_cast<BeamLm<true>&>(bl) = lm;
-        bl.btable = (const BiasWord*)bias_table; bl.bstates = bias_states; bl.bweight = bias_weight;
-        BeamBiased<false, false> bn{};
-        bn.btable = bl.btable; bn.bstates = bias_states; bn.bweight = bias_weight;
-#define BEAM_BIAS_LAUNCH(TIN, FAST, LMB, ARG)                                                                                     \
-    {                                                                                                                             \
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&beam_search_kernel<TIN, FAST, LMB, false, true>),                \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                          \
-        PGASR_LAUNCH_KERNEL((beam_search_kernel<TIN, FAST, LMB, false, true>), dim3(B), dim3(BEAM_THREADS), lds, st,              \
-                           (const TIN*)log_probs, stride_t, stride_b, lengths, T, V, beam, blank, flags & 1, ws, out_tokens,      \
-                           out_len, out_score, ARG);                                                                              \
-    }
-        if (with_lm) {
-            if (is_f64) BEAM_BIAS_LAUNCH(double, false, true, bl) else BEAM_BIAS_LAUNCH(float, true, true, bl)
-        } else {
-            if (is_f64) BEAM_BIAS_LAUNCH(double, false, false, bn) else BEAM_BIAS_LAUNCH(float, true, false, bn)
-        }
-#undef BEAM_BIAS_LAUNCH
-        PGASR_CHECK_LAUNCH();
-        return PGASR_OK;
-    }
-    hipStream_t st = (hipStream_t)stream;
+// the kernels' collapse argument: flags bit 0 and, in the diagnostic build, flags bit 2 as bit 1 (1-best without bias only)
+inline int beam_collapse(const BeamCall& c) {
 #ifdef PGASR_BEAM_DIAG
-    const int collapse = (flags & 1) | ((flags & 4) ? 2 : 0);
-#else
-    const int collapse = flags & 1;
+    if (!c.list && !c.bias_table && (c.flags & 4)) return (c.flags & 1) | 2;
 #endif
-    if (with_lm && (flags & 16) && pgasr_beam_lm_single_wave_ok(T, V, beam, is_f64, lm_order)) {
-        // flags bit 4: the single-wave kernel's LM instantiations (the same limits as below; the bit is the caller's explicit choice, so bit 1 is not consulted)
-        auto kern = V <= 32 ? &sb::beam_small_kernel<8, false, true> : &sb::beam_small_kernel<16, false, true>;
-        const size_t lds_small = sb::lds_bytes_lm(V <= 32 ? 8 : 16);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_small);
-        const sb::SmallLmScore sl{out_score, lm};
-        PGASR_LAUNCH_KERNEL(kern, dim3(B), dim3(64), lds_small, st, (const float*)log_probs, stride_t, stride_b,
-                           lengths, T, V, beam, blank, collapse, out_tokens, out_len, sl);
-        PGASR_CHECK_LAUNCH();
-        return PGASR_OK;
-    }
-    if (!with_lm && !is_f64 && !(flags & 2) && beam <= sb::K_MAX && V <= sb::V_MAX && (long long)T * beam <= sb::MAX_NODES && T <= sb::MAX_TOKENS) {
-        // training path: one wave per utterance, trie and candidate lists in LDS, no workspace traffic; 8 symbols per lane up to V = 32
-        // (the English alphabet of the headline), 16 up to V = 64 (round 5: CommonVoice's larger alphabets stay on this kernel)
-        auto kern = V <= 32 ? &sb::beam_small_kernel<8> : &sb::beam_small_kernel<16>;
-        const size_t lds_small = sb::lds_bytes(V <= 32 ? 8 : 16);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_small);
-        PGASR_LAUNCH_KERNEL(kern, dim3(B), dim3(64), lds_small, st, (const float*)log_probs, stride_t, stride_b,
-                           lengths, T, V, beam, blank, collapse, out_tokens, out_len, out_score);
-        PGASR_CHECK_LAUNCH();
-        return PGASR_OK;
-    }
-    if (hipMemsetAsync(ws.table, 0, (size_t)B * ws.H * sizeof(unsigned long long), st) != hipSuccess) return PGASR_ERR_LAUNCH;
-    const size_t lds = beam_lds_bytes(beam, V, with_lm);
-    if (lds > 160 * 1024) return PGASR_ERR_UNSUPPORTED;
-    // is_f64: exact path, fp64 transcendentals (drop-in CTCDecoder.decode); fp32 device log-probs: fast transcendentals
-#define BEAM_LAUNCH(TIN, FAST, LMB, LMARG)                                                                                        \
-    {                                                                                                                             \
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&beam_search_kernel<TIN, FAST, LMB>),                             \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                          \
-        PGASR_LAUNCH_KERNEL((beam_search_kernel<TIN, FAST, LMB>), dim3(B), dim3(BEAM_THREADS), lds, st, (const TIN*)log_probs,    \
-                           stride_t, stride_b, lengths, T, V, beam, blank, collapse, ws, out_tokens, out_len, out_score, LMARG);  \
-    }
-    if (with_lm) {      // with a language model every call without flags bit 4 takes this kernel
-        if (is_f64) BEAM_LAUNCH(double, false, true, lm) else BEAM_LAUNCH(float, true, true, lm)
-    } else {
-        if (is_f64) BEAM_LAUNCH(double, false, false, BeamLm<false>{}) else BEAM_LAUNCH(float, true, false, BeamLm<false>{})
-    }
-#undef BEAM_LAUNCH
+    return c.flags & 1;
+}
+
+// f(std::bool_constant<b>...) for runtime b...: the launchers' template arguments
+template <bool... Bs, typename F> int beam_with_bools(F&& f) { return f(std::bool_constant<Bs>{}...); }
+template <bool... Bs, typename F, typename... R> int beam_with_bools(F&& f, bool b, R... r) {
+    return b ? beam_with_bools<Bs..., true>(f, r...) : beam_with_bools<Bs..., false>(f, r...);
+}
+
+// The workgroup-per-utterance kernel.  Its last argument is exactly the type the instantiation declares (the tails ride behind one another).
+// is_f64: exact path, fp64 transcendentals (drop-in CTCDecoder.decode); fp32 device log-probs: fast transcendentals
+template <bool LM, bool NBEST, bool BIAS>
+int launch_workgroup(const BeamCall& c, const BeamLm<true>& lm, const BeamWs& ws, size_t lds) {
+    typename std::conditional<BIAS, BeamBiased<LM, NBEST>, BeamTail<LM, NBEST>>::type tail{};
+    if constexpr (LM) static_cast<BeamLm<true>&>(tail) = lm;
+    if constexpr (NBEST) { tail.nbest = c.nbest; tail.tok_stride = c.tok_stride; tail.out_count = c.out_count; }
+    if constexpr (BIAS) { tail.btable = (const BiasWord*)c.bias_table; tail.bstates = c.bias_states; tail.bweight = c.bias_weight; }
+    const auto launch = [&](auto kern, auto* lp) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        PGASR_LAUNCH_KERNEL(kern, dim3(c.B), dim3(BEAM_THREADS), lds, (hipStream_t)c.stream, lp, c.stride_t, c.stride_b, c.lengths, c.T, c.V,
+                            c.beam, c.blank, beam_collapse(c), ws, c.out_tokens, c.out_len, c.out_score, tail);
+    };
+    if (c.is_f64) launch(&beam_search_kernel<double, false, LM, NBEST, BIAS>, (const double*)c.log_probs);
+    else launch(&beam_search_kernel<float, true, LM, NBEST, BIAS>, (const float*)c.log_probs);
     PGASR_CHECK_LAUNCH();
     return PGASR_OK;
+}
+
+// The single-wave kernel: one wave per utterance, trie and candidate lists in LDS, no workspace traffic; 8 symbols per lane up to V = 32
+// (the English alphabet of the headline), 16 up to V = 64 (round 5: CommonVoice's larger alphabets stay on this kernel)
+template <bool LM, bool NBEST>
+int launch_single_wave(const BeamCall& c, const BeamLm<true>& lm) {
+    const auto tail = [&] {
+        if constexpr (NBEST && LM) return sb::SmallLmNbest{{c.out_score, c.out_count, c.nbest, c.tok_stride}, lm};
+        else if constexpr (NBEST) return sb::SmallNbest{c.out_score, c.out_count, c.nbest, c.tok_stride};
+        else if constexpr (LM) return sb::SmallLmScore{c.out_score, lm};
+        else return c.out_score;
+    }();
+    const int spl = c.V <= 32 ? 8 : 16;
+    const auto kern = spl == 8 ? &sb::beam_small_kernel<8, NBEST, LM> : &sb::beam_small_kernel<16, NBEST, LM>;
+    const size_t lds = LM ? sb::lds_bytes_lm(spl) : sb::lds_bytes(spl);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    PGASR_LAUNCH_KERNEL(kern, dim3(c.B), dim3(64), lds, (hipStream_t)c.stream, (const float*)c.log_probs, c.stride_t, c.stride_b, c.lengths,
+                        c.T, c.V, c.beam, c.blank, beam_collapse(c), c.out_tokens, c.out_len, tail);
+    PGASR_CHECK_LAUNCH();
+    return PGASR_OK;
+}
+
+// The host side of all five entries.  The shared checks with the language model's, the bias table's and the list's in their place;
+// nothing touches HIP until every check has passed.  Then one kernel family:
+//   * a bias table: the workgroup kernel, BIAS = true (the single-wave kernel has none);
+//   * a language model, flags bit 4 and pgasr_beam_lm_single_wave_ok: the single-wave kernel's LM instantiations (the bit is the caller's
+//     explicit choice, so bits 1 and 3 are not consulted);
+//   * no model, fp32 log-probs inside the single-wave limits: the single-wave kernel -- the training path -- unless flags bit 1 opts a
+//     1-best call out; a list has to opt in with flags bit 3 ("fast");
+//   * everything else: the workgroup kernel, whose hash table is cleared first.
+int beam_search_run(const BeamCall& c) {
+    BeamLm<true> lm{};
+    BeamWs ws;
+    if (const int st = beam_check_args(c.log_probs, c.out_tokens, c.out_len, c.out_score, c.T, c.B, c.V, c.beam, c.blank, BEAM_VMAX, BEAM_KMAX,
+                                       [&] {
+                                           if (const int s = beam_lm_args(c, &lm)) return s;
+                                           if (const int s = beam_bias_args(c)) return s;
+                                           const bool bad = c.list && (c.nbest < 1 || c.nbest > c.beam || c.tok_stride < c.T || !c.out_count);
+                                           return bad ? (int)PGASR_ERR_INVALID_ARG : (int)PGASR_OK;
+                                       },
+                                       c.workspace, c.workspace_bytes, &ws)) return st;
+    const bool with_lm = c.lm_order > 0, bias = c.bias_table != nullptr;
+    const bool single_wave = with_lm ? (c.flags & 16) && pgasr_beam_lm_single_wave_ok(c.T, c.V, c.beam, c.is_f64, c.lm_order)
+                                     : !c.is_f64 && (c.list ? (c.flags & 8) != 0 : !(c.flags & 2)) && beam_single_wave_fits(c.T, c.V, c.beam);
+    if (!bias && single_wave)
+        return beam_with_bools([&](auto l, auto nb) { return launch_single_wave<decltype(l)::value, decltype(nb)::value>(c, lm); }, with_lm, c.list);
+    const size_t lds = beam_lds_bytes(c.beam, c.V, with_lm, bias);
+    if (lds > 160 * 1024) return PGASR_ERR_UNSUPPORTED;
+    if (hipMemsetAsync(ws.table, 0, (size_t)c.B * ws.H * sizeof(unsigned long long), (hipStream_t)c.stream) != hipSuccess) return PGASR_ERR_LAUNCH;
+    return beam_with_bools([&](auto l, auto nb, auto bi) { return launch_workgroup<decltype(l)::value, decltype(nb)::value, decltype(bi)::value>(c, lm, ws, lds); },
+                           with_lm, c.list, bias);
 }
 }  // namespace
 
@@ -1065,8 +1079,8 @@ extern "C" int pgasr_ctc_beam_search(const void* log_probs, int is_f64, long lon
                                      const int32_t* lengths, int T, int B, int V, int beam, int blank, int flags,
                                      int32_t* out_tokens, int32_t* out_len, double* out_score,
                                      void* workspace, size_t workspace_bytes, void* stream) {
-    return beam_search_impl(log_probs, is_f64, stride_t, stride_b, lengths, T, B, V, beam, blank, flags, out_tokens, out_len, out_score,
-                            workspace, workspace_bytes, stream, nullptr, 0, 0.0, 0.0);
+    return beam_search_run(BeamCall{log_probs, is_f64, stride_t, stride_b, lengths, T, B, V, beam, blank, flags, out_tokens, out_len, out_score,
+                                     workspace, workspace_bytes, stream});
 }
 
 extern "C" int pgasr_ctc_beam_search_lm(const void* log_probs, int is_f64, long long stride_t, long long stride_b,
@@ -1074,113 +1088,20 @@ extern "C" int pgasr_ctc_beam_search_lm(const void* log_probs, int is_f64, long 
                                         int32_t* out_tokens, int32_t* out_len, double* out_score,
                                         void* workspace, size_t workspace_bytes, void* stream,
                                         const float* lm_table, int lm_order, double lm_alpha, double lm_beta) {
-    return beam_search_impl(log_probs, is_f64, stride_t, stride_b, lengths, T, B, V, beam, blank, flags, out_tokens, out_len, out_score,
-                            workspace, workspace_bytes, stream, lm_table, lm_order, lm_alpha, lm_beta);
+    return beam_search_run(BeamCall{log_probs, is_f64, stride_t, stride_b, lengths, T, B, V, beam, blank, flags, out_tokens, out_len, out_score,
+                                     workspace, workspace_bytes, stream}
+                               .with_lm(lm_table, lm_order, lm_alpha, lm_beta));
 }
 
-// The N-best list of the final beam (include/pgasr_hip.h, A7-NBEST): the workgroup-per-utterance kernel, NBEST = true; with flags bit 3
-// ("fast") the single-wave kernel's NBEST instantiation wherever the 1-best dispatch of beam_search_impl takes that kernel.
-namespace {
-int beam_search_nbest_impl(const void* log_probs, int is_f64, long long stride_t, long long stride_b,
-                           const int32_t* lengths, int T, int B, int V, int beam, int blank, int flags,
-                           int nbest, int32_t* out_tokens, int tok_stride, int32_t* out_len, double* out_score,
-                           int32_t* out_count, void* workspace, size_t workspace_bytes, void* stream,
-                           const float* lm_table, int lm_order, double lm_alpha, double lm_beta,
-                           const void* bias_table, int bias_states, double bias_weight) {
-    // the shared checks, in the order of pgasr_ctc_beam_search_lm, with the language model's and then the list's in their place
-    BeamLm<true> lmb{};
-    BeamWs ws;
-    if (const int st = beam_check_args(log_probs, out_tokens, out_len, out_score, T, B, V, beam, blank, BEAM_VMAX, BEAM_KMAX,
-                                       [&] {
-                                           if (const int s = beam_lm_args(V, blank, lm_table, lm_order, lm_alpha, lm_beta, &lmb)) return s;
-                                           if (const int s = beam_bias_args(V, flags, bias_table, bias_states, bias_weight)) return s;
-                                           return (nbest < 1 || nbest > beam || tok_stride < T || !out_count) ? (int)PGASR_ERR_INVALID_ARG : (int)PGASR_OK;
-                                       },
-                                       workspace, workspace_bytes, &ws)) return st;
-    const bool with_lm = lm_order > 0;
-    const size_t lds = beam_lds_bytes(beam, V, with_lm, bias_table != nullptr);
-    if (lds > 160 * 1024) return PGASR_ERR_UNSUPPORTED;
-    hipStream_t st = (hipStream_t)stream;
-    const int collapse = flags & 1;
-    if (bias_table) {      // always the workgroup-per-utterance kernel, BIAS = true
-        if (hipMemsetAsync(ws.table, 0, (size_t)B * ws.H * sizeof(unsigned long long), st) != hipSuccess) return PGASR_ERR_LAUNCH;
-        BeamBiased<true, true> bl{};
-        static_cast<BeamLm<true>&>(bl) = lmb;
-        bl.nbest = nbest; bl.tok_stride = tok_stride; bl.out_count = out_count;
-        bl.btable = (const BiasWord*)bias_table; bl.bstates = bias_states; bl.bweight = bias_weight;
-        BeamBiased<false, true> bn{};
-        bn.nbest = nbest; bn.tok_stride = tok_stride; bn.out_count = out_count;
-        bn.btable = bl.btable; bn.bstates = bias_states; bn.bweight = bias_weight;
-#define BEAM_NBEST_BIAS_LAUNCH(TIN, FAST, LMB, ARG)                                                                               \
-    {                                                                                                                             \
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&beam_search_kernel<TIN, FAST, LMB, true, true>),                 \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                          \
-        PGASR_LAUNCH_KERNEL((beam_search_kernel<TIN, FAST, LMB, true, true>), dim3(B), dim3(BEAM_THREADS), lds, st,               \
-                           (const TIN*)log_probs, stride_t, stride_b, lengths, T, V, beam, blank, collapse, ws, out_tokens,       \
-                           out_len, out_score, ARG);                                                                              \
-    }
-        if (with_lm) {
-            if (is_f64) BEAM_NBEST_BIAS_LAUNCH(double, false, true, bl) else BEAM_NBEST_BIAS_LAUNCH(float, true, true, bl)
-        } else {
-            if (is_f64) BEAM_NBEST_BIAS_LAUNCH(double, false, false, bn) else BEAM_NBEST_BIAS_LAUNCH(float, true, false, bn)
-        }
-#undef BEAM_NBEST_BIAS_LAUNCH
-        PGASR_CHECK_LAUNCH();
-        return PGASR_OK;
-    }
-    if (with_lm && (flags & 16) && pgasr_beam_lm_single_wave_ok(T, V, beam, is_f64, lm_order)) {      // flags bit 4, as in the 1-best dispatch
-        auto kern = V <= 32 ? &sb::beam_small_kernel<8, true, true> : &sb::beam_small_kernel<16, true, true>;
-        const size_t lds_small = sb::lds_bytes_lm(V <= 32 ? 8 : 16);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_small);
-        const sb::SmallLmNbest sn{{out_score, out_count, nbest, tok_stride}, lmb};
-        PGASR_LAUNCH_KERNEL(kern, dim3(B), dim3(64), lds_small, st, (const float*)log_probs, stride_t, stride_b,
-                           lengths, T, V, beam, blank, collapse, out_tokens, out_len, sn);
-        PGASR_CHECK_LAUNCH();
-        return PGASR_OK;
-    }
-    if ((flags & 8) && !with_lm && !is_f64 && beam <= sb::K_MAX && V <= sb::V_MAX && (long long)T * beam <= sb::MAX_NODES && T <= sb::MAX_TOKENS) {
-        auto kern = V <= 32 ? &sb::beam_small_kernel<8, true> : &sb::beam_small_kernel<16, true>;
-        const size_t lds_small = sb::lds_bytes(V <= 32 ? 8 : 16);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_small);
-        const sb::SmallNbest sn{out_score, out_count, nbest, tok_stride};
-        PGASR_LAUNCH_KERNEL(kern, dim3(B), dim3(64), lds_small, st, (const float*)log_probs, stride_t, stride_b,
-                           lengths, T, V, beam, blank, collapse, out_tokens, out_len, sn);
-        PGASR_CHECK_LAUNCH();
-        return PGASR_OK;
-    }
-    if (hipMemsetAsync(ws.table, 0, (size_t)B * ws.H * sizeof(unsigned long long), st) != hipSuccess) return PGASR_ERR_LAUNCH;
-    BeamNbest<true> nl{};
-    static_cast<BeamLm<true>&>(nl) = lmb;
-    nl.nbest = nbest; nl.tok_stride = tok_stride; nl.out_count = out_count;
-    BeamNbest<false> nn{};
-    nn.nbest = nbest; nn.tok_stride = tok_stride; nn.out_count = out_count;
-#define BEAM_NBEST_LAUNCH(TIN, FAST, LMB, ARG)                                                                                    \
-    {                                                                                                                             \
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&beam_search_kernel<TIN, FAST, LMB, true>),                       \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                          \
-        PGASR_LAUNCH_KERNEL((beam_search_kernel<TIN, FAST, LMB, true>), dim3(B), dim3(BEAM_THREADS), lds, st,                     \
-                           (const TIN*)log_probs, stride_t, stride_b, lengths, T, V, beam, blank, collapse, ws, out_tokens,       \
-                           out_len, out_score, ARG);                                                                              \
-    }
-    if (with_lm) {
-        if (is_f64) BEAM_NBEST_LAUNCH(double, false, true, nl) else BEAM_NBEST_LAUNCH(float, true, true, nl)
-    } else {
-        if (is_f64) BEAM_NBEST_LAUNCH(double, false, false, nn) else BEAM_NBEST_LAUNCH(float, true, false, nn)
-    }
-#undef BEAM_NBEST_LAUNCH
-    PGASR_CHECK_LAUNCH();
-    return PGASR_OK;
-}
-}  // namespace
-
+// The N-best list of the final beam (include/pgasr_hip.h, A7-NBEST): the same search, NBEST = true
 extern "C" int pgasr_ctc_beam_search_nbest(const void* log_probs, int is_f64, long long stride_t, long long stride_b,
                                            const int32_t* lengths, int T, int B, int V, int beam, int blank, int flags,
                                            int nbest, int32_t* out_tokens, int tok_stride, int32_t* out_len, double* out_score,
                                            int32_t* out_count, void* workspace, size_t workspace_bytes, void* stream,
                                            const float* lm_table, int lm_order, double lm_alpha, double lm_beta) {
-    return beam_search_nbest_impl(log_probs, is_f64, stride_t, stride_b, lengths, T, B, V, beam, blank, flags, nbest, out_tokens, tok_stride,
-                                  out_len, out_score, out_count, workspace, workspace_bytes, stream, lm_table, lm_order, lm_alpha, lm_beta,
-                                  nullptr, 0, 0.0);
+    return beam_search_run(BeamCall{log_probs, is_f64, stride_t, stride_b, lengths, T, B, V, beam, blank, flags, out_tokens, out_len, out_score,
+                                     workspace, workspace_bytes, stream}
+                               .with_list(nbest, tok_stride, out_count).with_lm(lm_table, lm_order, lm_alpha, lm_beta));
 }
 
 // Hotword biasing (include/pgasr_hip.h, A7-BIAS): the two searches with a bias automaton; a NULL table with no states is the call without.
@@ -1190,8 +1111,9 @@ extern "C" int pgasr_ctc_beam_search_bias(const void* log_probs, int is_f64, lon
                                           void* workspace, size_t workspace_bytes, void* stream,
                                           const float* lm_table, int lm_order, double lm_alpha, double lm_beta,
                                           const void* bias_table, int bias_states, double bias_weight) {
-    return beam_search_impl(log_probs, is_f64, stride_t, stride_b, lengths, T, B, V, beam, blank, flags, out_tokens, out_len, out_score,
-                            workspace, workspace_bytes, stream, lm_table, lm_order, lm_alpha, lm_beta, bias_table, bias_states, bias_weight);
+    return beam_search_run(BeamCall{log_probs, is_f64, stride_t, stride_b, lengths, T, B, V, beam, blank, flags, out_tokens, out_len, out_score,
+                                     workspace, workspace_bytes, stream}
+                               .with_lm(lm_table, lm_order, lm_alpha, lm_beta).with_bias(bias_table, bias_states, bias_weight));
 }
 
 extern "C" int pgasr_ctc_beam_search_nbest_bias(const void* log_probs, int is_f64, long long stride_t, long long stride_b,
@@ -1200,7 +1122,8 @@ extern "C" int pgasr_ctc_beam_search_nbest_bias(const void* log_probs, int is_f6
                                                 int32_t* out_count, void* workspace, size_t workspace_bytes, void* stream,
                                                 const float* lm_table, int lm_order, double lm_alpha, double lm_beta,
                                                 const void* bias_table, int bias_states, double bias_weight) {
-    return beam_search_nbest_impl(log_probs, is_f64, stride_t, stride_b, lengths, T, B, V, beam, blank, flags, nbest, out_tokens, tok_stride,
-                                  out_len, out_score, out_count, workspace, workspace_bytes, stream, lm_table, lm_order, lm_alpha, lm_beta,
-                                  bias_table, bias_states, bias_weight);
+    return beam_search_run(BeamCall{log_probs, is_f64, stride_t, stride_b, lengths, T, B, V, beam, blank, flags, out_tokens, out_len, out_score,
+                                     workspace, workspace_bytes, stream}
+                               .with_list(nbest, tok_stride, out_count).with_lm(lm_table, lm_order, lm_alpha, lm_beta)
+                               .with_bias(bias_table, bias_states, bias_weight));
 }

@@ -29,6 +29,7 @@
 // hotword automaton (pgasr_ctc_beam_search_wide_bias) it adds the phrase bonuses, with or without the model; see WideBias.
 #include "common.h"
 #include "beam_core.h"
+#include "bias_table.h"
 #include "unit_lm.h"
 #include <cmath>
 #include <type_traits>
@@ -121,9 +122,7 @@ constexpr size_t WIDE_LM_LDS_OFFSET = (sizeof(WideLds) + 15) / 16 * 16;
 //     symbol of largest frame[s] + w, as with the model;
 //   * the thread that writes an extension winner re-reads its word -- one independent 8-byte load in front of trie_find_or_create --
 //     for the new state and the new own bonus.
-struct BiasWord { int32_t next; float bonus; };
-static_assert(sizeof(BiasWord) == 8, "a table word is 8 bytes");
-constexpr long long WIDE_BIAS_MAX_WORDS = 1ll << 24;      // S * V words (128 MiB), as A7-BIAS
+using bias_table::BiasWord;
 struct WideBias {
     const BiasWord* table;   // S * V words
     int n_states;            // S
@@ -696,8 +695,7 @@ extern "C" int pgasr_ctc_beam_search_wide_bias(const void* log_probs, int is_f64
     const auto check = [&] {
         if (tables)
             if (const int st = wide_lm_check(&lm, tables, V, blank, lm_alpha, lm_beta)) return st;
-        if (!bias_table || bias_states < 1 || (long long)bias_states * V > WIDE_BIAS_MAX_WORDS || !std::isfinite(bias_weight))
-            return (int)PGASR_ERR_INVALID_ARG;
+        if (!bias_table::usable(bias_table, bias_states, V) || !std::isfinite(bias_weight)) return (int)PGASR_ERR_INVALID_ARG;
         bias.table = (const BiasWord*)bias_table; bias.n_states = bias_states; bias.weight = bias_weight;
         return (int)PGASR_OK;
     };

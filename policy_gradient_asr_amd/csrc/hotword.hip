@@ -6,6 +6,7 @@
 // staged HW_CHUNK at a time, one chunk ahead of the chain, so that the table gather is the only dependent load.  Every loop is bounded
 // by the clamped length; a next outside [0, S) is taken as state 0, so every index stays below S V whatever the table holds.
 #include "common.h"
+#include "bias_table.h"
 #include <cmath>
 
 namespace {
@@ -14,10 +15,7 @@ constexpr int HW_THREADS = 64;
 constexpr int HW_NMAX = 128;
 constexpr int HW_VMAX = 1024;
 constexpr int HW_CHUNK = 8;
-constexpr long long HW_MAX_WORDS = 1ll << 24;      // S * V words (128 MiB)
-
-struct BiasWord { int32_t next; float bonus; };
-static_assert(sizeof(BiasWord) == 8, "a table word is 8 bytes");
+using bias_table::BiasWord;
 
 __global__ __launch_bounds__(HW_THREADS) void nbest_bias_kernel(
     const int32_t* __restrict__ tokens, int tok_stride, const int32_t* __restrict__ len, const int32_t* __restrict__ count,
@@ -59,8 +57,7 @@ extern "C" int pgasr_nbest_bias_score(const int32_t* tokens, const int32_t* len,
                                       const void* bias_table, int bias_states, double* out, void* stream) {
     // nothing below touches HIP until every check has passed
     if (N < 1 || N > HW_NMAX || V > HW_VMAX) return PGASR_ERR_UNSUPPORTED;
-    if (!tokens || !len || !count || !out || !bias_table || B < 1 || tok_stride < 1 || V < 1 || bias_states < 1) return PGASR_ERR_INVALID_ARG;
-    if ((long long)bias_states * V > HW_MAX_WORDS) return PGASR_ERR_INVALID_ARG;
+    if (!tokens || !len || !count || !out || B < 1 || tok_stride < 1 || V < 1 || !bias_table::usable(bias_table, bias_states, V)) return PGASR_ERR_INVALID_ARG;
     if ((long long)N * B > 0x7FFFFFFFll) return PGASR_ERR_UNSUPPORTED;
     const int blocks = (N * B + HW_THREADS - 1) / HW_THREADS;
     PGASR_LAUNCH_KERNEL(nbest_bias_kernel, dim3(blocks), dim3(HW_THREADS), 0, (hipStream_t)stream, tokens, tok_stride, len, count, N, B, V,

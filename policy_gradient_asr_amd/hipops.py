@@ -1715,6 +1715,12 @@ def _bias_table(bias, V, blank, device, fast_lm=False, fast=False):
     return bias.device_table(device), bias.n_states
 
 
+def _search_head(log_probs, lengths, T, B, V, beam, blank):
+    """The leading C arguments of every search entry, up to the flags."""
+    return (_p(log_probs), int(log_probs.dtype == torch.float64), log_probs.stride(0), log_probs.stride(1), _p(lengths), T, B, V,
+            int(beam), int(blank))
+
+
 def ctc_beam_search(log_probs, lengths=None, beam=5, blank=0, collapse=False, out=None, generic=False,
                     lm=None, lm_alpha=0.0, lm_beta=0.0, fast_lm=False, bias=None, bias_weight=0.0):
     """log_probs (T,B,V) fp32 or fp64 natural-log probabilities on the GPU.
@@ -1750,24 +1756,17 @@ def ctc_beam_search(log_probs, lengths=None, beam=5, blank=0, collapse=False, ou
         tokens = torch.zeros(B, T, dtype=torch.int32, device=log_probs.device)
         tl = torch.empty(B, dtype=torch.int32, device=log_probs.device)
     score = torch.empty(B, dtype=torch.float64, device=log_probs.device)
+    # one entry point with and without a language model: without a table it IS pgasr_ctc_beam_search
+    entry, label, extra = "pgasr_ctc_beam_search_lm", "beam_search", ()
     if bias is not None:
-        with _timed("beam_search_bias"):
-            st = lib.pgasr_ctc_beam_search_bias(_p(log_probs), int(log_probs.dtype == torch.float64), log_probs.stride(0),
-                                                log_probs.stride(1), _p(lengths), T, B, V, int(beam), int(blank),
-                                                int(bool(collapse)) | (2 if generic else 0),
-                                                _p(tokens), _p(tl), _p(score), _p(ws), ws.numel(), _stream(),
-                                                _p(lm_table), lm_order, float(lm_alpha), float(lm_beta),
-                                                _p(bias_table), bias_states, float(bias_weight))
-        _lib.check(st, "pgasr_ctc_beam_search_bias")
-        return tokens, tl, score
-    with _timed("beam_search"):
-        # one entry point for both: without a table it IS pgasr_ctc_beam_search
-        st = lib.pgasr_ctc_beam_search_lm(_p(log_probs), int(log_probs.dtype == torch.float64), log_probs.stride(0),
-                                          log_probs.stride(1), _p(lengths), T, B, V, int(beam), int(blank),
-                                          int(bool(collapse)) | (2 if generic else 0) | (16 if fast_lm else 0),
-                                          _p(tokens), _p(tl), _p(score), _p(ws), ws.numel(), _stream(),
-                                          _p(lm_table), lm_order, float(lm_alpha), float(lm_beta))
-    _lib.check(st, "pgasr_ctc_beam_search_lm")
+        entry, label, extra = "pgasr_ctc_beam_search_bias", "beam_search_bias", (_p(bias_table), bias_states, float(bias_weight))
+    # fast_lm with a bias has raised by name in _bias_table: the bias entry never sees bit 4 (it would refuse it as unsupported)
+    with _timed(label):
+        st = getattr(lib, entry)(*_search_head(log_probs, lengths, T, B, V, beam, blank),
+                                 int(bool(collapse)) | (2 if generic else 0) | (16 if fast_lm else 0),
+                                 _p(tokens), _p(tl), _p(score), _p(ws), ws.numel(), _stream(),
+                                 _p(lm_table), lm_order, float(lm_alpha), float(lm_beta), *extra)
+    _lib.check(st, entry)
     return tokens, tl, score
 
 
@@ -1803,21 +1802,16 @@ def ctc_beam_search_nbest(log_probs, lengths=None, beam=5, nbest=1, blank=0, col
     N, dev = int(nbest), log_probs.device
     ws = _workspace(lib.pgasr_beam_workspace_bytes(T, B, V, int(beam)), dev, "beam")
     tokens, tl, score, count = _nbest_outputs(N, B, T, dev)
+    entry, label, extra = "pgasr_ctc_beam_search_nbest", "beam_search_nbest", ()
     if bias is not None:
-        with _timed("beam_search_nbest_bias"):
-            st = lib.pgasr_ctc_beam_search_nbest_bias(_p(log_probs), int(log_probs.dtype == torch.float64), log_probs.stride(0),
-                                                      log_probs.stride(1), _p(lengths), T, B, V, int(beam), int(blank),
-                                                      int(bool(collapse)), N, _p(tokens), T, _p(tl), _p(score), _p(count), _p(ws),
-                                                      ws.numel(), _stream(), _p(lm_table), lm_order, float(lm_alpha), float(lm_beta),
-                                                      _p(bias_table), bias_states, float(bias_weight))
-        _lib.check(st, "pgasr_ctc_beam_search_nbest_bias")
-        return CTCNBest(tokens, tl, score, count)
-    with _timed("beam_search_nbest"):
-        st = lib.pgasr_ctc_beam_search_nbest(_p(log_probs), int(log_probs.dtype == torch.float64), log_probs.stride(0),
-                                             log_probs.stride(1), _p(lengths), T, B, V, int(beam), int(blank),
-                                             int(bool(collapse)) | (8 if fast else 0) | (16 if fast_lm else 0), N, _p(tokens), T, _p(tl), _p(score), _p(count), _p(ws), ws.numel(), _stream(),
-                                             _p(lm_table), lm_order, float(lm_alpha), float(lm_beta))
-    _lib.check(st, "pgasr_ctc_beam_search_nbest")
+        entry, label = "pgasr_ctc_beam_search_nbest_bias", "beam_search_nbest_bias"
+        extra = (_p(bias_table), bias_states, float(bias_weight))
+    # fast / fast_lm with a bias have raised by name in _bias_table: the bias entry never sees bits 3 and 4
+    with _timed(label):
+        st = getattr(lib, entry)(*_search_head(log_probs, lengths, T, B, V, beam, blank),
+                                 int(bool(collapse)) | (8 if fast else 0) | (16 if fast_lm else 0), N, _p(tokens), T, _p(tl), _p(score),
+                                 _p(count), _p(ws), ws.numel(), _stream(), _p(lm_table), lm_order, float(lm_alpha), float(lm_beta), *extra)
+    _lib.check(st, entry)
     return CTCNBest(tokens, tl, score, count)
 
 
@@ -1896,8 +1890,7 @@ def ctc_beam_search_wide(log_probs, lengths=None, beam=5, nbest=None, blank=0, c
     tokens, tl, score, count = _nbest_outputs(N, B, T, dev)
     frames = torch.empty(B, dtype=torch.int32, device=dev) if stats else None
     with _timed(label):
-        st = getattr(lib, entry)(_p(log_probs), int(log_probs.dtype == torch.float64), log_probs.stride(0), log_probs.stride(1),
-                                 _p(lengths), T, B, V, int(beam), int(blank), int(bool(collapse)) | (32 if counting else 0), N,
+        st = getattr(lib, entry)(*_search_head(log_probs, lengths, T, B, V, beam, blank), int(bool(collapse)) | (32 if counting else 0), N,
                                  _p(tokens), T, _p(tl), _p(score), _p(count), _p(frames), _p(ws), ws.numel(), _stream(), *lm_args)
     _lib.check(st, entry)
     res = (tokens[0], tl[0], score[0]) if nbest is None else CTCNBest(tokens, tl, score, count)
