@@ -1256,6 +1256,26 @@ int pgasr_spec_augment(const float* x, const int32_t* lengths, const int32_t* ut
                        void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * A0-LFR  Low-frame-rate input (Sak et al., Interspeech 2015; Pundak & Sainath, Interspeech 2016): stack `stack` neighbouring frames
+ *   of a feature batch and keep every `skip`-th one, on the device (csrc/frame_stack.hip; in numpy: tests/frame_stack_ref.py).
+ *   x (B,F,T) fp32 contiguous; n_frames (B) int32 on the device, clamped to [0,T]; out (B, stack*F, Tout) fp32, not x.
+ *   With n = n_frames[b], n' = ceil(n / skip) and Tout = ceil(T / skip):
+ *        out[b, j*F + f, t'] = x[b, f, clamp(t'*skip + j - left, 0, n-1)]     for t' < n',  j = 0 .. stack-1
+ *        out[b, j*F + f, t'] = 0.0f                                            for n' <= t' < Tout
+ *   The rows are offset-major (j), feature-minor (f), as in Kaldi's splice; `left` of the stack's frames lie in front of the anchor
+ *   frame t'*skip.  The edges replicate the first / last real frame; an utterance of 0 frames gives all zeros and n' = 0.
+ *   fmask_out: NULL, or (B,1,Tout) fp32 = (t' < n');  n_out: NULL, or (B) int32 = n'.
+ *   Pure data movement: the result equals the statement above bit for bit, whatever x holds (NaN and inf included); a frame at or
+ *   beyond n is never read, so x need not be zero (or even finite) there.
+ *   One launch, no workspace, no atomics, no host synchronisation; any T and any alignment (16-byte loads where T % 4 == 0 and x is
+ *   16-byte aligned).  Checked before any pointer is touched or anything is launched, PGASR_ERR_INVALID_ARG: x, n_frames or out
+ *   NULL, out == x, B / F / T < 1, stack or skip outside [1, 16], left outside [0, stack), stack * F > 65535, B > 65535,
+ *   Tout != ceil(T / skip).
+ * ---------------------------------------------------------------------------------------- */
+int pgasr_frame_stack(const float* x, const int32_t* n_frames, int B, int F, int T, int stack, int skip, int left, int Tout,
+                      float* out, float* fmask_out /* NULL or (B,1,Tout) */, int32_t* n_out /* NULL or (B) */, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * A0-RS  Sample-rate conversion and speed perturbation (Ko et al., Interspeech 2015) of a waveform batch on the device: one
  *   polyphase Hann-windowed sinc filter (the function of torchaudio's default "sinc_interp_hann" resampler, 6 zero crossings,
  *   rolloff 0.99).  A conversion is a reduced ratio L / M = output rate / input rate; speed factor f = p / q is the ratio q / p.

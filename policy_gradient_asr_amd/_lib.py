@@ -134,6 +134,7 @@ SIGNATURES = {
     "pgasr_dropout": (C.c_int, [c_f32p, c_f32p, C.c_ulonglong, C.c_float, C.c_uint64, C.c_uint32, c_f32p, C.c_float, c_ptr]),
     "pgasr_spec_augment": (C.c_int, [c_f32p, c_i32p, c_i32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                      C.c_float, C.c_int, C.c_ulonglong, C.c_uint, c_f32p, c_i32p, c_ptr]),
+    "pgasr_frame_stack": (C.c_int, [c_f32p, c_i32p] + [C.c_int] * 7 + [c_f32p, c_f32p, c_i32p, c_ptr]),
     "pgasr_resample": (C.c_int, [c_f32p, C.c_int, c_i32p, C.c_int, c_i32p, C.c_int, c_ptr, c_f32p, c_i32p, c_f32p, C.c_int, c_i32p,
                                  c_ptr]),
     "pgasr_reverb_limits": (C.c_int, [C.POINTER(C.c_int)] * 3),

@@ -105,15 +105,28 @@ def encode_trans(batch, units=None):
 
 
 def collate_custom(batch, device=None, features="mfcc", target_rate=None, speed_perturb=None, seed=0, offset=0, wave_augment=None,
-                   units=None):
+                   units=None, frame_stack=None):
     """data.py:107-116.  device = None: the reference's contract -- everything on the CPU.  device = a GPU: "feat" / "fmask" stay
     where the front end computed them and "trans" / "tmask" are put beside them, so ``PolicyGradientTrainer.step`` consumes the
     batch without the features ever visiting the host (use ``functools.partial(collate_custom, device=...)`` as collate_fn).
     target_rate / speed_perturb / wave_augment / seed / offset: sample-rate conversion, speed perturbation, noise and reverberation of
-    waveform items (``extract_feats``).  units: subword units for the transcripts (``encode_trans``)."""
+    waveform items (``extract_feats``).  units: subword units for the transcripts (``encode_trans``).
+    frame_stack: None (default) or a features.FrameStack (or (stack, skip[, left])): low-frame-rate input -- the batch is stacked and
+    subsampled on the device LAST, behind the front end and whatever augments it, for waveform items and for items with a
+    precomputed "feat" alike: "feat" is (B, stack*F, ceil(Tmax/skip)), "fmask" (B,1,ceil(Tmax/skip)).  It needs a GPU ``device``: with
+    device = None it raises, there is no CPU path."""
     aug = {"target_rate": target_rate, "speed_perturb": speed_perturb, "seed": seed, "offset": offset}
     if wave_augment is not None:
         aug["wave_augment"] = wave_augment
+    if frame_stack is not None:
+        from .features import FrameStack
+        frame_stack = FrameStack.coerce(frame_stack)
+        if device is None:
+            raise ValueError("frame_stack stacks on the MI355X only: collate_custom needs a GPU device with it (there is no CPU path)")
+        feats, fmasks = extract_feats(batch, device=device, features=features, keep_on_device=True, **aug)
+        feats, fmasks = frame_stack(feats.to(torch.float32).contiguous(), fmasks)
+        trans, tmasks = (t.to(device) for t in encode_trans(batch, units))
+        return {"feat": feats, "fmask": fmasks, "trans": trans, "tmask": tmasks}
     if device is None:
         feats, fmasks = extract_feats(batch, features=features, **aug)
         trans, tmasks = encode_trans(batch, units)

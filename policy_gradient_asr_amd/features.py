@@ -232,6 +232,100 @@ class SpecAugment:
         return hipops.spec_augment(feat, lengths, self, seed, offset, utt_ids=utt_ids)
 
 
+class FrameStack:
+    """The low-frame-rate input policy (Sak et al., Interspeech 2015; Pundak & Sainath, Interspeech 2016): ``stack`` neighbouring
+    frames are stacked into one and every ``skip``-th one is kept, so the encoder, the lattice, the sampler and every decoder see
+    n' = ceil(n / skip) frames of stack * F features (include/pgasr_hip.h, A0-LFR):
+        feat'[b, j*F + f, t'] = feat[b, f, clamp(t'*skip + j - left, 0, n-1)],   j = 0 .. stack-1   (offset-major, as Kaldi's splice)
+    ``left`` of the stacked frames lie in front of the anchor frame t'*skip; the edges replicate the first / last real frame.
+    Limits: 1 <= stack, skip <= 16, 0 <= left < stack.  Parameter-free, so there is no backward pass: it sits in front of the train
+    step.  ORDER: SpecAugment masks the UNSTACKED (B,F,T) tensor first -- a band mask then is one band of rows and a time mask a run
+    of input frames -- and stacking comes last, directly in front of the model.
+    Immutable; ``state()`` / ``from_state()`` for checkpoints.  ``fs(feat, fmask)`` -> (feat' (B, stack*F, T'), fmask' (B,1,T')) on the
+    device, T' = ceil(T / skip); fmask (B,1,T) / (B,T), or lengths (B) int32.  No CPU path."""
+    FIELDS = ("stack", "skip", "left")
+    __slots__ = FIELDS
+
+    def __init__(self, stack=3, skip=3, left=0):
+        stack, skip, left = hipops.frame_stack_check(stack, skip, left, "FrameStack")
+        for k, v in zip(self.FIELDS, (stack, skip, left)):
+            object.__setattr__(self, k, v)
+
+    def __setattr__(self, k, v):
+        raise AttributeError("FrameStack is immutable")
+
+    def __delattr__(self, k):
+        raise AttributeError("FrameStack is immutable")
+
+    def state(self):
+        return {k: getattr(self, k) for k in self.FIELDS}
+
+    @classmethod
+    def from_state(cls, state):
+        unknown = sorted(set(state) - set(cls.FIELDS))
+        if unknown:
+            raise ValueError(f"FrameStack: unknown fields {unknown}")
+        return cls(**state)
+
+    @classmethod
+    def coerce(cls, value, what="frame_stack"):
+        """None, a FrameStack, a dict of its fields or (stack, skip[, left]) -> None or a FrameStack; anything else: TypeError."""
+        if value is None or isinstance(value, cls):
+            return value
+        if isinstance(value, dict):
+            return cls.from_state(value)
+        if isinstance(value, (tuple, list)) and len(value) in (2, 3):
+            return cls(*value)
+        raise TypeError(f"{what} must be None, a features.FrameStack, a dict of its fields or (stack, skip[, left]) (got {value!r})")
+
+    def __eq__(self, other):
+        return isinstance(other, FrameStack) and self.state() == other.state()
+
+    def __hash__(self):
+        return hash(tuple(self.state().values()))
+
+    def __repr__(self):
+        return "FrameStack({})".format(", ".join(f"{k}={getattr(self, k)!r}" for k in self.FIELDS))
+
+    def out_feats(self, F):
+        """Features per stacked frame."""
+        return self.stack * int(F)
+
+    def out_frames(self, n):
+        """Frames that n input frames leave: ceil(n / skip) (a python int, or elementwise on an integer tensor / array)."""
+        return (n + (self.skip - 1)) // self.skip
+
+    def input_span(self, start, end, n):
+        """The input frames [start*skip, min(end*skip, n)) that the stacked frames [start, end) of an utterance of n input frames are
+        anchored at: stacked frame t' stands at input frame t'*skip."""
+        return int(start) * self.skip, min(int(end) * self.skip, int(n))
+
+    def fits(self, trans, tg_len, n_out, blank=0):
+        """(B) bool: the transcript still has a CTC alignment over the stacked frames, L + repeats <= n' (repeats: positions whose
+        symbol equals the one in front of it, which need a blank between them).  trans (B,Lmax) integer ids; tg_len (B), or None:
+        the count of ids != blank; n_out (B).  Tensor operations on the tensors' device only: no host synchronisation."""
+        trans = torch.as_tensor(trans)
+        n_out = torch.as_tensor(n_out, device=trans.device)
+        if tg_len is None:
+            tg_len = (trans != blank).sum(dim=1)
+        tg_len = torch.as_tensor(tg_len, device=trans.device).to(torch.int64)
+        pos = torch.arange(1, trans.shape[1], device=trans.device)[None, :]
+        repeats = ((trans[:, 1:] == trans[:, :-1]) & (pos < tg_len[:, None])).sum(dim=1)
+        return tg_len + repeats <= n_out.to(torch.int64)
+
+    def __call__(self, feat, fmask):
+        if not isinstance(feat, torch.Tensor) or not feat.is_cuda:
+            raise _lib.PgasrError("FrameStack stacks on the MI355X only; there is no CPU path")
+        if isinstance(fmask, torch.Tensor) and fmask.is_floating_point():
+            out, fmask_out, _ = hipops.frame_stack(feat, fmask=fmask, **self.state())
+        else:
+            if not isinstance(fmask, torch.Tensor):
+                fmask = torch.tensor(list(fmask), dtype=torch.int32)
+            out, fmask_out, _ = hipops.frame_stack(feat, lengths=fmask.to(device=feat.device, dtype=torch.int32).contiguous(),
+                                                   **self.state())
+        return out, fmask_out
+
+
 RESAMPLE_ZEROS, RESAMPLE_ROLLOFF = 6, 0.99              # torchaudio's default sinc_interp_hann resampler
 RESAMPLE_MAX_LM, RESAMPLE_MAX_FACTOR, RESAMPLE_MAX_RATIOS = hipops.RESAMPLE_MAX_LM, hipops.RESAMPLE_MAX_FACTOR, hipops.RESAMPLE_MAX_RATIOS
 

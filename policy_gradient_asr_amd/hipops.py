@@ -758,6 +758,71 @@ def spec_augment(x, lengths, policy, seed, offset, utt_ids=None, batch_offset=0,
     return (out, masks) if want_masks else out
 
 
+FRAME_STACK_MAX, FRAME_STACK_MAX_ROWS, FRAME_STACK_MAX_BATCH = 16, 65535, 65535      # csrc/frame_stack.hip: stack and skip; stack * F; B
+
+
+def frame_stack_check(stack, skip, left, what="frame_stack"):
+    """(stack, skip, left) as python ints; TypeError / ValueError with the reason unless they lie within the kernel's limits
+    (include/pgasr_hip.h, A0-LFR): 1 <= stack, skip <= 16, 0 <= left < stack."""
+    import numbers
+    for k, v in (("stack", stack), ("skip", skip), ("left", left)):
+        if isinstance(v, bool) or not isinstance(v, numbers.Integral):
+            raise TypeError(f"{what}: {k} must be an integer (got {v!r})")
+    stack, skip, left = int(stack), int(skip), int(left)
+    if not 1 <= stack <= FRAME_STACK_MAX:
+        raise ValueError(f"{what}: stack must lie in [1, {FRAME_STACK_MAX}] (got {stack})")
+    if not 1 <= skip <= FRAME_STACK_MAX:
+        raise ValueError(f"{what}: skip must lie in [1, {FRAME_STACK_MAX}] (got {skip})")
+    if not 0 <= left < stack:
+        raise ValueError(f"{what}: left must lie in [0, stack = {stack}) (got {left})")
+    return stack, skip, left
+
+
+def frame_stack(x, lengths=None, fmask=None, stack=3, skip=3, left=0):
+    """Low-frame-rate input (include/pgasr_hip.h, A0-LFR): x (B,F,T) fp32 -> (out (B, stack*F, Tout) fp32, fmask_out (B,1,Tout) fp32,
+    n_out (B) int32) with Tout = ceil(T / skip), n_out = ceil(n / skip) and
+        out[b, j*F + f, t'] = x[b, f, clamp(t'*skip + j - left, 0, n-1)]  for t' < n_out[b],  0 beyond.
+    The frame counts n are ``lengths`` (B) int32 on the device, or the sum of ``fmask`` (B,1,T) / (B,T) (1 / 0; taken on the device),
+    or T for every row where both are None.  One launch, no host synchronisation.  A wrong dtype, device, layout or a value beyond
+    the limits (1 <= stack, skip <= 16, 0 <= left < stack, stack * F <= 65535, B <= 65535) raises a ValueError that says which."""
+    stack, skip, left = frame_stack_check(stack, skip, left)
+    if not isinstance(x, torch.Tensor) or x.dim() != 3:
+        raise ValueError("frame_stack: x must be a (B,F,T) tensor")
+    if not x.is_cuda:
+        raise ValueError(f"frame_stack: x must live on the GPU (got {x.device}); there is no CPU path")
+    if x.dtype != torch.float32:
+        raise ValueError(f"frame_stack: x must be torch.float32 (got {x.dtype})")
+    if not x.is_contiguous():
+        raise ValueError("frame_stack: x must be contiguous")
+    B, F, T = x.shape
+    if B < 1 or F < 1 or T < 1:
+        raise ValueError(f"frame_stack: x must not be empty (got {tuple(x.shape)})")
+    if stack * F > FRAME_STACK_MAX_ROWS:
+        raise ValueError(f"frame_stack: stack * F = {stack * F} output rows; at most {FRAME_STACK_MAX_ROWS}")
+    if B > FRAME_STACK_MAX_BATCH:
+        raise ValueError(f"frame_stack: B = {B}; at most {FRAME_STACK_MAX_BATCH} utterances per call")
+    if lengths is not None and fmask is not None:
+        raise ValueError("frame_stack: give lengths or fmask, not both")
+    if fmask is not None:
+        if not isinstance(fmask, torch.Tensor) or fmask.device != x.device or fmask.shape[0] != B or fmask.numel() != B * T:
+            raise ValueError(f"frame_stack: fmask must be ({B},1,{T}) or ({B},{T}) on {x.device}")
+        lengths = fmask.reshape(B, T).sum(dim=1).to(torch.int32)          # on the device: no host synchronisation
+    elif lengths is None:
+        lengths = torch.full((B,), T, dtype=torch.int32, device=x.device)
+    elif not isinstance(lengths, torch.Tensor) or lengths.dtype != torch.int32 or lengths.device != x.device \
+            or lengths.dim() != 1 or lengths.numel() != B or not lengths.is_contiguous():
+        raise ValueError(f"frame_stack: lengths must be a contiguous ({B},) torch.int32 tensor on {x.device}")
+    Tout = (T + skip - 1) // skip
+    out = torch.empty(B, stack * F, Tout, dtype=torch.float32, device=x.device)
+    fmask_out = torch.empty(B, 1, Tout, dtype=torch.float32, device=x.device)
+    n_out = torch.empty(B, dtype=torch.int32, device=x.device)
+    lib = _lib.load()
+    with _timed("frame_stack"):
+        st = lib.pgasr_frame_stack(_p(x), _p(lengths), B, F, T, stack, skip, left, Tout, _p(out), _p(fmask_out), _p(n_out), _stream())
+    _lib.check(st, "pgasr_frame_stack")
+    return out, fmask_out, n_out
+
+
 RESAMPLE_MAX_LM, RESAMPLE_MAX_FACTOR, RESAMPLE_MAX_RATIOS = 1024, 16, 8      # csrc/resample.hip
 
 _resample_tables = {}

@@ -193,9 +193,10 @@ def _to_device(batch, device):
 FEATURE_DIMS = {"mfcc": 120, "logmel80": 80}      # what data.collate_custom(features=...) produces from a waveform
 
 
-def _check_features(features, n_feats, dataset):
+def _check_features(features, n_feats, dataset, stack=1):
     """A waveform-carrying dataset meets the model through the front end: its width must be the model's n_feats (a mismatch
-    used to surface as a shape error at the instance norm of the first step)."""
+    used to surface as a shape error at the instance norm of the first step).  stack: the frames a ``FrameStack`` policy stacks
+    between the two -- the model's width is then FEATURE_DIMS[features] * stack."""
     if features not in FEATURE_DIMS:
         raise ValueError(f"features must be one of {sorted(FEATURE_DIMS)}")
     try:
@@ -203,8 +204,28 @@ def _check_features(features, n_feats, dataset):
     except Exception:
         item = None
     if isinstance(item, dict) and ("wave" in item or "aud" in item) and "feat" not in item:
-        if n_feats != FEATURE_DIMS[features]:
-            raise ValueError(f"features='{features}' gives {FEATURE_DIMS[features]} features per frame but n_feats={n_feats}")
+        if n_feats != FEATURE_DIMS[features] * stack:
+            raise ValueError(f"features='{features}' gives {FEATURE_DIMS[features]} features per frame but n_feats={n_feats}" if stack == 1 else
+                             f"features='{features}' stacked {stack} times gives {FEATURE_DIMS[features] * stack} features per frame "
+                             f"but the model takes {n_feats}")
+
+
+def _frame_stack_of(model_path, frame_stack, who):
+    """The low-frame-rate policy ``predict`` / ``align`` run with: the one <model_path>/checkpoint_last.pth was trained with, which a
+    given ``frame_stack`` must agree with (ValueError); without a checkpoint, or with one that has no such field, the argument."""
+    import os
+    from .features import FrameStack
+    frame_stack = FrameStack.coerce(frame_stack)
+    ckpt = os.path.join(model_path, "checkpoint_last.pth")
+    if not os.path.exists(ckpt):
+        return frame_stack
+    st = torch.load(ckpt, map_location="cpu")
+    if "frame_stack" not in st:
+        return frame_stack
+    saved = FrameStack.coerce(st["frame_stack"])
+    if frame_stack is not None and frame_stack != saved:
+        raise ValueError(f"{who}: frame_stack={frame_stack!r} but the model in {model_path} was trained with frame_stack={saved!r}")
+    return saved
 
 
 def _read_wav_dir(path):
@@ -244,7 +265,7 @@ def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset
           mwer_beam=16, init_from=None, kl_weight=0.0, kl_reference_path=None, mwer_lm_path=None, mwer_lm_alpha=0.0,
           mwer_lm_beta=0.0, target_rate=None, speed_perturb=None, noise_dir=None, rir_dir=None, snr_db=(5.0, 20.0), noise_prob=1.0,
           rir_prob=0.5, units_path=None, wide_alphabet=None, wide_objectives=None, wide_sequence=None,
-          mwer_unit_lm_path=None, spelled_reward=False, reward_mode="utterance", step_objectives=None):
+          mwer_unit_lm_path=None, spelled_reward=False, reward_mode="utterance", step_objectives=None, frame_stack=None):
     """Epoch loop of model.py:186-274 on the MI355X path: per-epoch train loss -> train_loss.npy,
     validation CTC loss -> val_losses.npy, model_best.pth / model_last.pth (state_dicts, reference
     names), plus checkpoint_last.pth (model + Adam moments + epoch) from which ``resume`` restarts
@@ -324,7 +345,14 @@ def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset
     units_path: the rewards (the risk of objective="mwer") are counted on the SPELLED text of targets and hypotheses -- reward_unit=
     "char" its characters, "word" its words, the metrics that are reported -- through a ``units.UnitSpelling`` built from the units
     file and <corpus_path>/alphabet.txt (PolicyGradientTrainer(unit_spelling=), mwer.MWERTrainer(unit_spelling=)); above 64 symbols it
-    is what admits reward_unit="word".  Kept in the checkpoint beside wide_alphabet."""
+    is what admits reward_unit="word".  Kept in the checkpoint beside wide_alphabet.
+    frame_stack: None (default: every frame of the front end is one step of the sweeps) or (stack, skip[, left]) / a
+    features.FrameStack -- low-frame-rate input: every batch, training and validation, is stacked and subsampled on the device behind
+    the front end and its augmentation (data.collate_custom(frame_stack=)), the model is built with n_feats * stack inputs (n_feats
+    stays the front end's width) and sees ceil(n / skip) frames per utterance.  An utterance whose transcript no longer fits its
+    frames (features.FrameStack.fits) gets zero weight from the loss as ever; they are counted on the device and printed once per
+    epoch.  Kept in the checkpoint beside wide_alphabet, where ``predict`` and ``align`` find it; a resume with another policy is
+    refused."""
     import os
     import numpy as np
     import torch.utils.data as tud
@@ -398,19 +426,29 @@ def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset
     os.makedirs(model_path, exist_ok=True)
     from .features import SpeedPerturb
     speed_perturb = SpeedPerturb.coerce(speed_perturb)
+    n_in = n_feats                                              # the model's input width
+    if frame_stack is not None:
+        from .features import FrameStack
+        frame_stack = FrameStack.coerce(frame_stack)
+        n_in = frame_stack.out_feats(n_feats)
     wave_augment = _wave_augment(noise_dir, rir_dir, snr_db, noise_prob, rir_prob, dev)
     unit_args = {} if units is None else {"units": units}       # without a units file: the calls as they were
-    collate_custom = functools.partial(_collate, device=dev, features=features, target_rate=target_rate, **unit_args)
+    # the collate function stacks last, validation batches too
+    collate_args = unit_args if frame_stack is None else dict(unit_args, frame_stack=frame_stack)
+    collate_custom = functools.partial(_collate, device=dev, features=features, target_rate=target_rate, **collate_args)
     if train_dataset is None:
         train_dataset = Data(os.path.join(corpus_path, "train.tsv"), os.path.join(corpus_path, "clips"), char2ind, **unit_args)
     if dev_dataset is None and os.path.exists(os.path.join(corpus_path, "dev.tsv")):
         dev_dataset = Data(os.path.join(corpus_path, "dev.tsv"), os.path.join(corpus_path, "clips"), char2ind, **unit_args)
 
     torch.manual_seed(seed)
-    model = Seq2Seq(alphabet_size=len(char2ind), n_feats=n_feats)
+    model = Seq2Seq(alphabet_size=len(char2ind), n_feats=n_in)
     model.apply(weights)                                            # model.py:202
     model = model.to(dev)
-    _check_features(features, n_feats, train_dataset)
+    if frame_stack is None:
+        _check_features(features, n_feats, train_dataset)
+    else:
+        _check_features(features, n_in, train_dataset, stack=frame_stack.stack)
     if objective == "mwer":
         from .mwer import MWERTrainer
         mwer_lm = {}
@@ -431,7 +469,7 @@ def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset
         kl = {}
         if kl_weight > 0:
             # the frozen reference is a model of its own, loaded from its path -- in a resumed run too
-            reference = Seq2Seq(alphabet_size=len(char2ind), n_feats=n_feats)
+            reference = Seq2Seq(alphabet_size=len(char2ind), n_feats=n_in)
             reference.load_state_dict(torch.load(kl_reference_path, map_location="cpu"))
             kl = {"kl_weight": kl_weight, "kl_reference": reference.to(dev)}
         trainer = PolicyGradientTrainer(model, lr=lr, lam=lam, seed=seed, precision=precision, num_samples=num_samples,
@@ -450,6 +488,10 @@ def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset
         print("Initialised from", init_from)
     if resuming:
         st = resume_state if resume_state is not None else torch.load(ckpt, map_location=dev)
+        if frame_stack is not None or st.get("frame_stack") is not None:      # the policy decides the model's width: no warning, a refusal
+            if st.get("frame_stack") != (None if frame_stack is None else frame_stack.state()):
+                raise ValueError("frame_stack: resuming with frame_stack={} but the checkpoint was written with frame_stack={}".format(
+                    None if frame_stack is None else frame_stack.state(), st.get("frame_stack")))
         model.load_state_dict(st["model"])
         from .train_step import FLAG_PAD
         # the checkpoint holds the moments of the PARAMETERS (the flat buffers' leading flag words are not state)
@@ -485,7 +527,7 @@ def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset
             draws = {"speed_perturb": speed_perturb, "seed": seed, "offset": epoch}
             if wave_augment is not None:
                 draws["wave_augment"] = wave_augment
-            train_collate = functools.partial(_collate, device=dev, features=features, target_rate=target_rate, **draws, **unit_args)
+            train_collate = functools.partial(_collate, device=dev, features=features, target_rate=target_rate, **draws, **collate_args)
         if lens is not None:      # similar lengths per batch instead of model.py:221's shuffle=True
             sampler = LengthBucketSampler(lens, batch_size, seed=seed)
             sampler.set_epoch(epoch)
@@ -493,9 +535,12 @@ def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset
         else:
             loader = tud.DataLoader(epoch_dataset, batch_size=batch_size, shuffle=True, collate_fn=train_collate)
         acc = torch.zeros((), device=dev)
+        unfit = torch.zeros((), dtype=torch.int64, device=dev) if frame_stack is not None else None
         n_steps = -(-len(loader) // accumulate_steps)          # optimizer steps of this epoch
         step, group = 0, []
         for n_batch, batch in enumerate(loader, 1):
+            if unfit is not None:      # counted on the device: read once, at the end of the epoch
+                unfit += (~frame_stack.fits(batch["trans"], batch["tmask"].sum(1), batch["fmask"].sum((1, 2)))).sum()
             if accumulate_steps == 1:
                 loss = trainer.step(*_to_device(batch, dev))
             else:
@@ -522,6 +567,9 @@ def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset
         streams.release()                         # the host has synchronised: nothing of the last step needs keeping alive
         np.save(os.path.join(model_path, "train_loss.npy"), np.array(losses))
         print("Epoch:{}/{} Training loss:{:>4f}".format(epoch, num_epochs, losses[-1]))
+        if unfit is not None:
+            print("Epoch:{}/{} Utterances whose transcript does not fit their stacked frames (zero weight): {}".format(
+                epoch, num_epochs, int(unfit)))
         if max_grad_norm is not None:
             print("Epoch:{}/{} Clipped steps: {} Skipped (non-finite gradient): {}".format(epoch, num_epochs, *trainer.clip_counts()))
 
@@ -558,6 +606,7 @@ def train(corpus_path, model_path, num_epochs, batch_size, device, train_dataset
                     "units_path": units_path, "wide_alphabet": wide_alphabet, "wide_objectives": wide_objectives, "wide_sequence": wide_sequence,
                     "reward_mode": reward_mode, "step_objectives": step_objectives,
                     "spelled_reward": bool(spelled_reward),
+                    **({} if frame_stack is None else {"frame_stack": frame_stack.state()}),
                     "speed_perturb": None if speed_perturb is None else speed_perturb.state(),
                     "wave_augment": None if wave_augment is None else wave_augment.state()}, ckpt)
     return losses, val_losses
@@ -569,7 +618,7 @@ def predict(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=N
             mbr=False, mbr_unit="char", mbr_scale=1.0, rescore_word_lm_path=None, rescore_word_alpha=0.0, rescore_word_beta=0.0,
             error_report=False, units_path=None, wide_beam=False, wide_second_pass=False, unit_lm_path=None, unit_lm_alpha=0.0,
             unit_lm_beta=0.0, rescore_unit_lm_path=None, rescore_unit_alpha=0.0, rescore_unit_beta=0.0, spelled=False,
-            wide_hotwords=False, hotwords_path=None, hotword_weight=1.0, hotword_boost=1.0):
+            frame_stack=None, wide_hotwords=False, hotwords_path=None, hotword_weight=1.0, hotword_boost=1.0):
     """model.py:277-339: load model_best.pth, forward, beam=5 prefix search (device side, batched),
     collapse_fn, CER/WER, predicted.txt.  Frames are cut by the FEATURE mask (the reference cuts the
     time axis by the target mask, model.py:322 -- a listed defect).  Returns (CER, WER).
@@ -650,7 +699,11 @@ def predict(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=N
     wide search itself (``CTCDecoder(wide_search=True, wide_hotwords=True, hotwords=)``, csrc/beam_wide.hip), together with
     unit_lm_path if given and without needing wide_second_pass; the first-pass scores are then fused scores.  With
     wide_second_pass=True as well the second pass applies ``rescore(bias=)`` as above: the first pass gets the phrase into the list,
-    the exact-likelihood second pass ranks it, and ``nbest.tsv`` carries B(y) of every hypothesis as its last column."""
+    the exact-likelihood second pass ranks it, and ``nbest.tsv`` carries B(y) of every hypothesis as its last column.
+    frame_stack: None (default) or (stack, skip[, left]) / a features.FrameStack, as in ``train``.  None takes the policy the model
+    was trained with from <model_path>/checkpoint_last.pth, where there is one -- a model trained without a policy, or a directory
+    without that file, decodes as ever --; a policy that differs from the checkpoint's raises.  The model then has n_feats * stack
+    inputs and every decoder sees ceil(n / skip) frames."""
     import os
     import functools
     import torch.utils.data as tud
@@ -761,12 +814,18 @@ def predict(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=N
         raise ValueError(f"the beam search takes at most {hipops.MAX_VOCAB_NARROW} symbols and {alphabet_path} has {len(alphabet)}: "
                          f"decode greedily with beam_size=0 (up to {hipops.MAX_VOCAB_WIDE} symbols)")
     dev = torch.device("cuda", device_id)
-    model = Seq2Seq(alphabet_size=len(alphabet), n_feats=n_feats)
+    frame_stack = _frame_stack_of(model_path, frame_stack, "predict")
+    n_in = n_feats if frame_stack is None else frame_stack.out_feats(n_feats)
+    model = Seq2Seq(alphabet_size=len(alphabet), n_feats=n_in)
     model.load_state_dict(torch.load(os.path.join(model_path, "model_best.pth"), map_location="cpu"))
     model = model.to(dev).eval()
     if test_dataset is None:
         test_dataset = Data(test_path, aud_path, char2ind, **unit_args)
-    _check_features(features, n_feats, test_dataset)
+    if frame_stack is None:
+        _check_features(features, n_feats, test_dataset)
+    else:
+        _check_features(features, n_in, test_dataset, stack=frame_stack.stack)
+        unit_args = dict(unit_args, frame_stack=frame_stack)
     collate_custom = functools.partial(_collate, device=dev, features=features, target_rate=target_rate, **unit_args)
     # a units file: the device's collapse is the whole collapse -- collapse_fn would merge a unit's last character with the next unit's first
     to_text = collapse_fn if units_path is None else (lambda text: text)
@@ -917,13 +976,17 @@ def predict(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=N
 
 
 def align(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=None, maxlent=None, device_id=0,
-          test_dataset=None, n_feats=120, features="mfcc", out_path=None, target_rate=None):
+          test_dataset=None, n_feats=120, features="mfcc", out_path=None, target_rate=None, frame_stack=None):
     """Forced alignment of the REFERENCE transcripts: ``predict``'s loading and batching, then per batch forward, log-softmax and
     ``CTCDecoder.align_batch`` (Viterbi on the device).  Writes ``out_path`` (default <model_path>/alignments.tsv), one line per
     reference character: utterance index, character index, symbol, start frame, end frame (one past the last), mean log-prob of
     its frames.  An utterance whose transcript does not fit its frames is written with spans -1 -1 and mean -inf, not dropped.
     Returns the per-utterance scores (negative log-probability of the best alignment, +inf where there is none).
-    target_rate: as in ``predict``."""
+    target_rate: as in ``predict``.
+    frame_stack: as in ``predict`` (None: the policy in <model_path>/checkpoint_last.pth, where there is one).  The alignment then
+    runs over the stacked frames, and a token's span [s', e') is written in INPUT frames, ``FrameStack.input_span``: start s' * skip,
+    end min(e' * skip, n) -- stacked frame t' is anchored at input frame t' * skip (its stack covers t'*skip - left .. t'*skip - left
+    + stack - 1) --, so the columns of ``alignments.tsv`` keep their meaning of 10 ms frames and consecutive tokens still tile."""
     import os
     import functools
     import torch.utils.data as tud
@@ -934,12 +997,17 @@ def align(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=Non
     alphabet, char2ind = _read_alphabet(alphabet_path)
     ind2char = {char2ind[k]: k for k in char2ind}
     dev = torch.device("cuda", device_id)
-    model = Seq2Seq(alphabet_size=len(alphabet), n_feats=n_feats)
+    frame_stack = _frame_stack_of(model_path, frame_stack, "align")
+    n_in = n_feats if frame_stack is None else frame_stack.out_feats(n_feats)
+    model = Seq2Seq(alphabet_size=len(alphabet), n_feats=n_in)
     model.load_state_dict(torch.load(os.path.join(model_path, "model_best.pth"), map_location="cpu"))
     model = model.to(dev).eval()
     if test_dataset is None:
         test_dataset = Data(test_path, aud_path, char2ind)
-    _check_features(features, n_feats, test_dataset)
+    if frame_stack is None:
+        _check_features(features, n_feats, test_dataset)
+    else:
+        _check_features(features, n_in, test_dataset, stack=frame_stack.stack)
     collate_custom = functools.partial(_collate, device=dev, features=features, target_rate=target_rate)
     loader = tud.DataLoader(test_dataset, batch_size=batch_size, shuffle=False, collate_fn=collate_custom)
     decoder = CTCDecoder(alphabet)
@@ -947,6 +1015,10 @@ def align(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=Non
     with torch.no_grad():
         for batch in loader:
             x, t, fmask, tmask = _to_device(batch, dev)
+            if frame_stack is not None:      # stacked here, not in the collate function: the spans need the input frame counts
+                n_frames = fmask.sum(1).to(torch.int64).cpu()
+                x, fmask = frame_stack(x.to(torch.float32).contiguous(), fmask)
+                fmask = fmask.squeeze(1)
             logits, in_len = model.logits(x, fmask)
             lp = Fh.LogSoftmaxFn.apply(logits).contiguous()
             tl = tmask.sum(1).to(torch.int32).contiguous()
@@ -959,6 +1031,8 @@ def align(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=Non
                 for j in range(int(tl[i])):
                     s0, s1 = int(st[i, j]), int(en[i, j])
                     mean = float(sm[i, j]) / (s1 - s0) if s0 >= 0 else -float("inf")
+                    if frame_stack is not None and s0 >= 0:
+                        s0, s1 = frame_stack.input_span(s0, s1, n_frames[i])
                     lines.append("{}\t{}\t{}\t{}\t{}\t{:.6f}\n".format(u, j, ind2char[int(t[i, j])], s0, s1, mean))
     if out_path is None:
         out_path = os.path.join(model_path, "alignments.tsv")
