@@ -29,15 +29,28 @@ _S_UNIT_LM = [c_ptr, C.c_double, C.c_double]                         # tables, l
 _S_BIAS = [c_ptr, C.c_int, C.c_double]                               # bias_table, bias_states, bias_weight
 _S_WIDE = _S_HEAD + _S_LIST + [c_i32p] + _S_WS                       # ... out_counting_frames
 
+# The CTC loss section's gradient, loss and hypothesis-lattice entries likewise (include/pgasr_hip.h, A5 / A12 / A13 and their -WIDE forms):
+# head, one policy-gradient group, [the hypothesis group,] [the tails,] output + workspace(s) + stream
+_G_HEAD = [c_f32p, c_i32p, c_i32p] + [C.c_int] * 5 + [c_f32p]        # log_probs, input_lengths, target_lengths, T, B, V, Lmax, blank, utt_scale
+_G_ONE = [c_f32p, c_i32p, C.c_int]                                   # pg_coef, pg_path, pg_coef_per_frame
+_G_MULTI = [C.c_int, c_f32p, c_i32p]                                 # K, pg_coef, pg_paths
+_G_NBEST = [C.c_int, c_f32p]                                         # N, coef
+_G_HYP = [c_i32p, C.c_int]                                           # hyp_len, Lh
+_G_ENT = [c_f32p]                                                    # ent_scale
+_G_KL = [c_f32p, c_f32p, c_f32p]                                     # ent_scale (nullable), ref_log_probs, kl_scale
+_G_OUT = [c_f32p] + _S_WS                                            # grad_logits, workspace, workspace_bytes, stream
+_G_OUT2 = [c_f32p, c_ptr, C.c_size_t] + _S_WS                        # grad_logits, workspace, its bytes, hyp_workspace, its bytes, stream
+_G_LOSS = [c_f32p, c_i32p] + _G_HEAD[1:] + [c_f32p, c_i32p, c_f32p] + _G_OUT       # log_probs, targets, <head>, pg_coef, pg_path, nll, <out>
+_G_HYP_LATTICE = [c_f32p, c_i32p, C.c_int, c_i32p, c_i32p] + [C.c_int] * 6 + [c_f32p] + _S_WS   # log_probs, hyp_tokens, hyp_stride, hyp_len,
+                                                                     # input_lengths, T, B, V, K, Lh, blank, hyp_nll, hyp_workspace, bytes, stream
+
 # name -> (restype, argtypes).  Mirrors include/pgasr_hip.h one to one.
 SIGNATURES = {
     "pgasr_abi_version": (C.c_int, []),
     "pgasr_status_string": (C.c_char_p, [C.c_int]),
     "pgasr_ctc_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
-    "pgasr_ctc_loss_grad": (C.c_int, [c_f32p, c_i32p, c_i32p, c_i32p, C.c_int, C.c_int, C.c_int, C.c_int,
-                                      C.c_int, c_f32p, c_f32p, c_i32p, c_f32p, c_f32p, c_ptr, C.c_size_t, c_ptr]),
-    "pgasr_ctc_grad_from_lattice": (C.c_int, [c_f32p, c_i32p, c_i32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                              c_f32p, c_f32p, c_i32p, C.c_int, c_f32p, c_ptr, C.c_size_t, c_ptr]),
+    "pgasr_ctc_loss_grad": (C.c_int, _G_LOSS),
+    "pgasr_ctc_grad_from_lattice": (C.c_int, _G_HEAD + _G_ONE + _G_OUT),
     "pgasr_pg_rewards": (C.c_int, [c_i32p, c_i32p, C.c_int, C.c_float, C.c_float, c_f32p, c_f32p, c_f32p, c_f32p, c_ptr]),
     "pgasr_pg_loss_value": (C.c_int, [c_f32p, c_i32p, c_i32p, c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int,
                                       c_f32p, c_ptr]),
@@ -52,43 +65,29 @@ SIGNATURES = {
                                                 c_i32p, c_i32p, c_ptr]),
     "pgasr_frame_sample_multi_ids": (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint32, C.c_int, c_i32p,
                                                c_i32p, c_i32p, c_ptr]),
-    "pgasr_ctc_grad_from_lattice_multi": (C.c_int, [c_f32p, c_i32p, c_i32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                                    c_f32p, C.c_int, c_f32p, c_i32p, c_f32p, c_ptr, C.c_size_t, c_ptr]),
+    "pgasr_ctc_grad_from_lattice_multi": (C.c_int, _G_HEAD + _G_MULTI + _G_OUT),
     "pgasr_pg_rewards_multi": (C.c_int, [c_i32p, c_i32p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, c_f32p, c_f32p, c_f32p,
                                          c_f32p, c_ptr]),
     "pgasr_pg_loss_value_multi": (C.c_int, [c_f32p, c_i32p, C.c_int, c_i32p, c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int,
                                             c_f32p, c_ptr]),
     "pgasr_ctc_hyp_workspace_bytes": (C.c_size_t, [C.c_int] * 5),
-    "pgasr_ctc_hyp_lattice": (C.c_int, [c_f32p, c_i32p, C.c_int, c_i32p, c_i32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                        c_f32p, c_ptr, C.c_size_t, c_ptr]),
+    "pgasr_ctc_hyp_lattice": (C.c_int, _G_HYP_LATTICE),
     "pgasr_ctc_hyp_score": (C.c_int, [c_f32p, c_i32p, C.c_int, c_i32p, c_i32p, c_i32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                       C.c_int, c_ptr, c_ptr]),
-    "pgasr_ctc_grad_from_lattices_seq": (C.c_int, [c_f32p, c_i32p, c_i32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_f32p,
-                                                   C.c_int, c_f32p, c_i32p, c_i32p, C.c_int, c_f32p, c_ptr, C.c_size_t,
-                                                   c_ptr, C.c_size_t, c_ptr]),
+    "pgasr_ctc_grad_from_lattices_seq": (C.c_int, _G_HEAD + _G_MULTI + _G_HYP + _G_OUT2),
     "pgasr_pg_loss_value_seq": (C.c_int, [c_f32p, c_i32p, C.c_int, c_i32p, c_f32p, c_f32p, c_f32p, c_f32p, c_i32p, C.c_int,
                                           C.c_int, C.c_int, C.c_int, c_f32p, c_ptr]),
     "pgasr_frame_entropy": (C.c_int, [c_f32p, c_i32p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, c_f32p, c_f32p, c_ptr]),
-    "pgasr_ctc_grad_from_lattice_ent": (C.c_int, [c_f32p, c_i32p, c_i32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                                  c_f32p, c_f32p, c_i32p, C.c_int, c_f32p, c_f32p, c_ptr, C.c_size_t, c_ptr]),
-    "pgasr_ctc_grad_from_lattice_multi_ent": (C.c_int, [c_f32p, c_i32p, c_i32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                                        c_f32p, C.c_int, c_f32p, c_i32p, c_f32p, c_f32p, c_ptr, C.c_size_t, c_ptr]),
-    "pgasr_ctc_grad_from_lattices_seq_ent": (C.c_int, [c_f32p, c_i32p, c_i32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_f32p,
-                                                       C.c_int, c_f32p, c_i32p, c_i32p, C.c_int, c_f32p, c_f32p, c_ptr, C.c_size_t,
-                                                       c_ptr, C.c_size_t, c_ptr]),
+    "pgasr_ctc_grad_from_lattice_ent": (C.c_int, _G_HEAD + _G_ONE + _G_ENT + _G_OUT),
+    "pgasr_ctc_grad_from_lattice_multi_ent": (C.c_int, _G_HEAD + _G_MULTI + _G_ENT + _G_OUT),
+    "pgasr_ctc_grad_from_lattices_seq_ent": (C.c_int, _G_HEAD + _G_MULTI + _G_HYP + _G_ENT + _G_OUT2),
     "pgasr_ctc_align_workspace_bytes": (C.c_size_t, [C.c_int] * 3),
     "pgasr_ctc_forced_align": (C.c_int, [c_f32p, c_i32p, c_i32p, c_i32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                          c_ptr, c_i32p, c_i32p, c_i32p, c_i32p, c_ptr, c_ptr, C.c_size_t, c_ptr]),
     "pgasr_frame_kl": (C.c_int, [c_f32p, c_f32p, c_i32p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, c_f32p, c_f32p, c_ptr]),
-    "pgasr_ctc_grad_from_lattice_kl": (C.c_int, [c_f32p, c_i32p, c_i32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                                 c_f32p, c_f32p, c_i32p, C.c_int, c_f32p, c_f32p, c_f32p, c_f32p, c_ptr, C.c_size_t,
-                                                 c_ptr]),
-    "pgasr_ctc_grad_from_lattice_multi_kl": (C.c_int, [c_f32p, c_i32p, c_i32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                                       c_f32p, C.c_int, c_f32p, c_i32p, c_f32p, c_f32p, c_f32p, c_f32p, c_ptr,
-                                                       C.c_size_t, c_ptr]),
-    "pgasr_ctc_grad_from_lattices_seq_kl": (C.c_int, [c_f32p, c_i32p, c_i32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_f32p,
-                                                      C.c_int, c_f32p, c_i32p, c_i32p, C.c_int, c_f32p, c_f32p, c_f32p, c_f32p, c_ptr,
-                                                      C.c_size_t, c_ptr, C.c_size_t, c_ptr]),
+    "pgasr_ctc_grad_from_lattice_kl": (C.c_int, _G_HEAD + _G_ONE + _G_KL + _G_OUT),
+    "pgasr_ctc_grad_from_lattice_multi_kl": (C.c_int, _G_HEAD + _G_MULTI + _G_KL + _G_OUT),
+    "pgasr_ctc_grad_from_lattices_seq_kl": (C.c_int, _G_HEAD + _G_MULTI + _G_HYP + _G_KL + _G_OUT2),
     "pgasr_word_ids": (C.c_int, [c_i32p, c_i32p, C.c_int, c_i32p, c_i32p, C.c_int, C.c_int, C.c_int, c_i32p, c_i32p, c_i32p, c_i32p,
                                  c_ptr]),
     "pgasr_pg_rewards_multi_ex": (C.c_int, [c_i32p, c_i32p, c_i32p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, c_f32p, c_f32p,
@@ -128,9 +127,7 @@ SIGNATURES = {
                                            c_ptr]),
     "pgasr_mwer_weights": (C.c_int, [c_i32p, c_i32p, c_i32p, c_f32p, c_i32p, c_i32p, c_f32p, C.c_int, C.c_int, C.c_int,
                                      C.c_float, C.c_float, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_ptr]),
-    "pgasr_ctc_grad_from_lattices_nbest": (C.c_int, [c_f32p, c_i32p, c_i32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_f32p,
-                                                     C.c_int, c_f32p, c_i32p, C.c_int, c_f32p, c_ptr, C.c_size_t,
-                                                     c_ptr, C.c_size_t, c_ptr]),
+    "pgasr_ctc_grad_from_lattices_nbest": (C.c_int, _G_HEAD + _G_NBEST + _G_HYP + _G_OUT2),
     "pgasr_dropout": (C.c_int, [c_f32p, c_f32p, C.c_ulonglong, C.c_float, C.c_uint64, C.c_uint32, c_f32p, C.c_float, c_ptr]),
     "pgasr_spec_augment": (C.c_int, [c_f32p, c_i32p, c_i32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                      C.c_float, C.c_int, C.c_ulonglong, C.c_uint, c_f32p, c_i32p, c_ptr]),
@@ -176,29 +173,20 @@ SIGNATURES = {
     "pgasr_log_softmax_rows_wide": (C.c_int, [c_f32p, C.c_longlong, C.c_int, c_f32p, c_ptr]),
     "pgasr_frame_argmax_sample_wide": (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint32, C.c_int, C.c_int,
                                                  c_i32p, c_i32p, c_i32p, c_ptr]),
-    "pgasr_ctc_loss_grad_wide": (C.c_int, [c_f32p, c_i32p, c_i32p, c_i32p, C.c_int, C.c_int, C.c_int, C.c_int,
-                                           C.c_int, c_f32p, c_f32p, c_i32p, c_f32p, c_f32p, c_ptr, C.c_size_t, c_ptr]),
-    "pgasr_ctc_grad_from_lattice_wide": (C.c_int, [c_f32p, c_i32p, c_i32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                                   c_f32p, c_f32p, c_i32p, C.c_int, c_f32p, c_ptr, C.c_size_t, c_ptr]),
+    "pgasr_ctc_loss_grad_wide": (C.c_int, _G_LOSS),
+    "pgasr_ctc_grad_from_lattice_wide": (C.c_int, _G_HEAD + _G_ONE + _G_OUT),
     "pgasr_frame_sample_multi_wide": (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint32, C.c_int, C.c_int,
                                                 c_i32p, c_i32p, c_i32p, c_ptr]),
     "pgasr_frame_entropy_wide": (C.c_int, [c_f32p, c_i32p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, c_f32p, c_f32p, c_ptr]),
     "pgasr_frame_kl_wide": (C.c_int, [c_f32p, c_f32p, c_i32p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, c_f32p, c_f32p,
                                       c_ptr]),
-    "pgasr_ctc_grad_from_lattice_multi_wide": (C.c_int, [c_f32p, c_i32p, c_i32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                                         c_f32p, C.c_int, c_f32p, c_i32p, c_f32p, c_f32p, c_f32p, c_f32p, c_ptr,
-                                                         C.c_size_t, c_ptr]),
+    "pgasr_ctc_grad_from_lattice_multi_wide": (C.c_int, _G_HEAD + _G_MULTI + _G_KL + _G_OUT),
     "pgasr_ctc_hyp_workspace_bytes_wide": (C.c_size_t, [C.c_int] * 5),
-    "pgasr_ctc_hyp_lattice_wide": (C.c_int, [c_f32p, c_i32p, C.c_int, c_i32p, c_i32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                             C.c_int, c_f32p, c_ptr, C.c_size_t, c_ptr]),
-    "pgasr_ctc_grad_from_lattices_seq_wide": (C.c_int, [c_f32p, c_i32p, c_i32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_f32p,
-                                                        C.c_int, c_f32p, c_i32p, c_i32p, C.c_int, c_f32p, c_f32p, c_f32p, c_f32p,
-                                                        c_ptr, C.c_size_t, c_ptr, C.c_size_t, c_ptr]),
+    "pgasr_ctc_hyp_lattice_wide": (C.c_int, _G_HYP_LATTICE),
+    "pgasr_ctc_grad_from_lattices_seq_wide": (C.c_int, _G_HEAD + _G_MULTI + _G_HYP + _G_KL + _G_OUT2),
     "pgasr_pg_step_coefs_multi": (C.c_int, [c_i32p, c_i32p, c_i32p, C.c_int, c_i32p, c_i32p, C.c_int, C.c_int, C.c_int, C.c_int,
                                             C.c_int, C.c_float, C.c_float, c_f32p, c_ptr]),
-    "pgasr_ctc_grad_from_lattice_multi_steps": (C.c_int, [c_f32p, c_i32p, c_i32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                                          c_f32p, C.c_int, c_f32p, c_i32p, c_f32p, c_f32p, c_f32p, c_f32p, c_ptr,
-                                                          C.c_size_t, c_ptr]),
+    "pgasr_ctc_grad_from_lattice_multi_steps": (C.c_int, _G_HEAD + _G_MULTI + _G_KL + _G_OUT),
     "pgasr_pg_loss_value_multi_steps": (C.c_int, [c_f32p, c_i32p, C.c_int, c_i32p, c_f32p, c_f32p, c_f32p, C.c_int, C.c_int,
                                                   C.c_int, c_f32p, c_ptr]),
     "pgasr_lstm_pack_bytes": (C.c_size_t, [C.c_int, C.c_int]),

@@ -34,6 +34,8 @@
 // per step ~1e-7 instead of the ~2e-4 ulp an fp32 log-space value of magnitude 3000 has at
 // T=1000.  Sums over states are taken in a fixed order (wave butterfly, then list order), so
 // results are run-to-run reproducible.
+#include <type_traits>
+
 #include "common.h"
 #include "wide_rows.h"
 
@@ -673,17 +675,18 @@ __global__ __launch_bounds__(256) void pg_loss_value_seq_kernel(const float* __r
     if (threadIdx.x == 0) terms[b] = nll[b] * utt_scale[b] - acc;
 }
 
-// ---- what the entry points below share: argument checks, workspace binding, the gradient passes' launch ----
-static int ctc_args_ok(int T, int B, int V, int Lmax, int blank) {
+// ---- what the entry points below share: argument checks, workspace binding, the description of a gradient call ----
+// vmax: CTC_VMAX for the one-label-per-lane kernels, PGASR_WIDE_VMAX for the wide ones
+static int ctc_args_ok(int T, int B, int V, int Lmax, int blank, int vmax) {
     if (T <= 0 || B <= 0 || V <= 0 || Lmax < 0 || blank < 0 || blank >= V) return PGASR_ERR_INVALID_ARG;
-    if (2 * (long long)Lmax + 1 > CTC_SMAX || V > CTC_VMAX) return PGASR_ERR_UNSUPPORTED;
+    if (2 * (long long)Lmax + 1 > CTC_SMAX || V > vmax) return PGASR_ERR_UNSUPPORTED;
     return PGASR_OK;
 }
 
-static int ctc_hyp_args_ok(int T, int B, int V, int K, int Lh) {
+static int ctc_hyp_args_ok(int T, int B, int V, int K, int Lh, int vmax) {
     if (T <= 0 || B <= 0 || V <= 0 || Lh < 0) return PGASR_ERR_INVALID_ARG;
     if (K < 1 || K > PGASR_MAX_SAMPLES) return PGASR_ERR_INVALID_ARG;
-    if (2 * (long long)Lh + 1 > CTC_SMAX || V > CTC_VMAX) return PGASR_ERR_UNSUPPORTED;
+    if (2 * (long long)Lh + 1 > CTC_SMAX || V > vmax) return PGASR_ERR_UNSUPPORTED;
     if ((long long)K * B > 0x7fffffffLL / 4) return PGASR_ERR_UNSUPPORTED;
     return PGASR_OK;
 }
@@ -694,18 +697,58 @@ static bool ctc_ws_bind(int T, int N, int V, int Smax, CtcWs* ws, void* workspac
     return workspace && workspace_bytes >= need;
 }
 
-// A gradient pass: one wave per (t,b) row, four rows per workgroup.  Every gradient kernel starts with the same arguments up to
-// utt_scale; `tail` is what follows them.
-template <class Kernel, class... Tail>
-static int ctc_launch_grad(Kernel kernel, const float* log_probs, const int32_t* input_lengths, const int32_t* target_lengths,
-                           int T, int B, int V, int Lmax, int blank, const CtcWs& ws, const float* utt_scale, void* stream, Tail... tail) {
-    const long long waves = (long long)T * B;
+// Everything a gradient pass can take, group by group: an entry point fills the groups its signature has and leaves the rest zero.
+struct GradHead { const float* log_probs; const int32_t *input_lengths, *target_lengths; int T, B, V, Lmax, blank; const float* utt_scale; };
+struct GradPg   { int K; const float* pg_coef; const int32_t* pg_paths; int coef_per_frame; };   // one path: K = 1, the flag 0 or 1
+struct GradHyp  { const int32_t* hyp_len; int Lh; void* hyp_workspace; size_t hyp_workspace_bytes; };
+struct GradTail { const float *ent_scale, *ref_log_probs, *kl_scale; };     // the tail rule of include/pgasr_hip.h
+struct GradCall : GradHead, GradPg, GradHyp, GradTail { float* grad_logits; void* workspace; size_t workspace_bytes; void* stream; };
+
+// What follows the target part: one sampled path (optional; its coefficient per utterance or per frame), K paths, K paths with
+// per-frame coefficients (K,T,B), K hypothesis lattices with the path fallback, N hypothesis lattices alone.
+enum GradForm { GRAD_ONE, GRAD_MULTI, GRAD_STEPS, GRAD_SEQ, GRAD_NBEST };
+
+// TAIL as the kernels number it: 0 = none, 1 = entropy, 2 = entropy (nullable) and KL.  f(integral_constant<int, TAIL>) for the call's.
+template <int N> using Int = std::integral_constant<int, N>;
+template <class F>
+static int ctc_with_tail(const GradTail& t, F f) { return t.kl_scale ? f(Int<2>{}) : t.ent_scale ? f(Int<1>{}) : f(Int<0>{}); }
+
+// A gradient pass of the one-label-per-lane kernels: one wave per (t,b) row, four rows per workgroup.  Every gradient kernel starts
+// with the same arguments up to utt_scale; `rest` is what follows them.
+template <class Kernel, class... Rest>
+static int ctc_launch_grad(Kernel kernel, const GradCall& c, const CtcWs& ws, Rest... rest) {
+    const long long waves = (long long)c.T * c.B;
     const int wpb = 4;
     const unsigned blocks = (unsigned)((waves + wpb - 1) / wpb);
-    PGASR_LAUNCH_KERNEL(kernel, dim3(blocks), dim3(64 * wpb), 0, (hipStream_t)stream,
-                       log_probs, input_lengths, target_lengths, T, B, V, Lmax > 0 ? Lmax : 1, 2 * Lmax + 1, blank, ws, utt_scale, tail...);
+    PGASR_LAUNCH_KERNEL(kernel, dim3(blocks), dim3(64 * wpb), 0, (hipStream_t)c.stream, c.log_probs, c.input_lengths, c.target_lengths,
+                       c.T, c.B, c.V, c.Lmax > 0 ? c.Lmax : 1, 2 * c.Lmax + 1, c.blank, ws, c.utt_scale, rest...);
     PGASR_CHECK_LAUNCH();
     return PGASR_OK;
+}
+
+// ... with the tail the kernels take as a pack of pointers: none, (ent_scale), or (ent_scale, ref_log_probs, kl_scale).  The one
+// place that names the narrow instantiations; the N-best form exists without a tail only.
+template <int TAIL, class... Ent>
+static int ctc_grad_narrow(const GradCall& c, GradForm form, const CtcWs& ws, const CtcWs& hws, Ent... ent) {
+    static_assert(sizeof...(Ent) == (TAIL == 2 ? 3 : TAIL), "the pack is the tail");
+    constexpr bool ENT = TAIL != 0;
+    const int Smax_h = 2 * c.Lh + 1;
+    switch (form) {
+    case GRAD_ONE:
+        return ctc_launch_grad(ctc_grad_kernel<ENT, Ent...>, c, ws, c.pg_coef, c.pg_paths, c.coef_per_frame, c.grad_logits, ent...);
+    case GRAD_MULTI:
+        return ctc_launch_grad(ctc_grad_multi_kernel<ENT, false, Ent...>, c, ws, c.K, c.pg_coef, c.pg_paths, c.grad_logits, ent...);
+    case GRAD_STEPS:
+        return ctc_launch_grad(ctc_grad_multi_kernel<ENT, true, Ent...>, c, ws, c.K, c.pg_coef, c.pg_paths, c.grad_logits, ent...);
+    case GRAD_SEQ:
+        return ctc_launch_grad(ctc_grad_seq_kernel<ENT, true, Ent...>, c, ws, c.K, c.pg_coef, c.pg_paths, c.hyp_len, c.Lh, Smax_h, hws,
+                               c.grad_logits, ent...);
+    case GRAD_NBEST:
+        if constexpr (TAIL == 0)
+            return ctc_launch_grad(ctc_grad_seq_kernel<false, false>, c, ws, c.K, c.pg_coef, c.pg_paths, c.hyp_len, c.Lh, Smax_h, hws,
+                                   c.grad_logits);
+    }
+    return PGASR_ERR_INVALID_ARG;
 }
 
 // ---- alphabets of up to 1024 symbols (pgasr_ctc_loss_grad_wide, pgasr_ctc_grad_from_lattice_wide; header section A5-WIDE) ----
@@ -840,28 +883,6 @@ __global__ __launch_bounds__(64 * CTC_WIDE_WPB) void ctc_grad_wide_kernel(
     wide_row_store<NV>(grad + o, V, lane, vec != 0, g);
 }
 
-static int ctc_args_ok_wide(int T, int B, int V, int Lmax, int blank) {
-    if (T <= 0 || B <= 0 || V <= 0 || Lmax < 0 || blank < 0 || blank >= V) return PGASR_ERR_INVALID_ARG;
-    if (2 * (long long)Lmax + 1 > CTC_SMAX || V > PGASR_WIDE_VMAX) return PGASR_ERR_UNSUPPORTED;
-    return PGASR_OK;
-}
-
-static int ctc_launch_grad_wide(const float* log_probs, const int32_t* input_lengths,
-                                const int32_t* target_lengths, int T, int B, int V, int Lmax, int blank, const CtcWs& ws,
-                                const float* utt_scale, const float* pg_coef, const int32_t* pg_path, int coef_per_frame,
-                                float* grad_logits, void* stream) {
-    const long long waves = (long long)T * B;
-    const unsigned blocks = (unsigned)((waves + CTC_WIDE_WPB - 1) / CTC_WIDE_WPB);
-#define PGASR_CALL(NV) PGASR_LAUNCH_KERNEL(ctc_grad_wide_kernel<NV>, dim3(blocks), dim3(64 * CTC_WIDE_WPB), 0, (hipStream_t)stream,           \
-                                           log_probs, input_lengths, target_lengths, T, B, V,                                                  \
-                                           wide_vec_ok<NV>(log_probs, grad_logits, V) ? 1 : 0, Lmax > 0 ? Lmax : 1, 2 * Lmax + 1, blank, ws, \
-                                           utt_scale, pg_coef, pg_path, coef_per_frame, grad_logits)
-    PGASR_WIDE_DISPATCH(V, PGASR_CALL);
-#undef PGASR_CALL
-    PGASR_CHECK_LAUNCH();
-    return PGASR_OK;
-}
-
 // ---- the multi-sample gradient pass for wide rows, with the entropy and KL tails (pgasr_ctc_grad_from_lattice_multi_wide; A12-WIDE) ----
 // ctc_grad_multi_kernel with NV labels per lane: the CTC part of ctc_grad_wide_kernel, then the K terms
 // pg_coef[k,b] (softmax - onehot(pg_paths[k,t,b])) in k order, then ent_scale_b p (ln p + H), then kl_scale_b p (ln p - lnq - KL)
@@ -983,26 +1004,6 @@ __global__ __launch_bounds__(64 * CTC_WIDE_WPB) void ctc_grad_multi_wide_kernel(
         }
     }
     wide_row_store<NV>(grad + o, V, lane, vec != 0, g);
-}
-
-template <int TAIL, bool STEPS = false>
-static int ctc_launch_grad_multi_wide(const float* log_probs, const int32_t* input_lengths, const int32_t* target_lengths, int T, int B,
-                                      int V, int Lmax, int blank, const CtcWs& ws, const float* utt_scale, int K, const float* pg_coef,
-                                      const int32_t* pg_paths, const float* ent_scale, const float* ref_log_probs,
-                                      const float* kl_scale, float* grad_logits, void* stream) {
-    const long long waves = (long long)T * B;
-    const unsigned blocks = (unsigned)((waves + CTC_WIDE_WPB - 1) / CTC_WIDE_WPB);
-    // one `vec` for the launch: the row loads of log_probs and ref_log_probs and the row store must all be aligned
-#define PGASR_CALL(NV) PGASR_LAUNCH_KERNEL((ctc_grad_multi_wide_kernel<NV, TAIL, STEPS>), dim3(blocks), dim3(64 * CTC_WIDE_WPB), 0,           \
-                                           (hipStream_t)stream, log_probs, input_lengths, target_lengths, T, B, V,                              \
-                                           (wide_vec_ok<NV>(log_probs, grad_logits, V) &&                                                       \
-                                            (TAIL < 2 || wide_vec_ok<NV>(ref_log_probs, ref_log_probs, V))) ? 1 : 0,                            \
-                                           Lmax > 0 ? Lmax : 1, 2 * Lmax + 1, blank, ws, utt_scale, K, pg_coef, pg_paths, ent_scale,            \
-                                           ref_log_probs, kl_scale, grad_logits)
-    PGASR_WIDE_DISPATCH(V, PGASR_CALL);
-#undef PGASR_CALL
-    PGASR_CHECK_LAUNCH();
-    return PGASR_OK;
 }
 
 // ---- sequence-level REINFORCE and N-best MWER for wide rows (pgasr_ctc_hyp_lattice_wide, pgasr_ctc_grad_from_lattices_seq_wide; A13-WIDE) ----
@@ -1204,36 +1205,159 @@ __global__ __launch_bounds__(64 * CTC_WIDE_WPB) void ctc_grad_seq_wide_kernel(
     wide_row_store<NV>(grad + o, V, lane, vec != 0, g);
 }
 
-static int ctc_hyp_args_ok_wide(int T, int B, int V, int K, int Lh) {
-    if (T <= 0 || B <= 0 || V <= 0 || Lh < 0) return PGASR_ERR_INVALID_ARG;
-    if (K < 1 || K > PGASR_MAX_SAMPLES) return PGASR_ERR_INVALID_ARG;
-    if (2 * (long long)Lh + 1 > CTC_SMAX || V > PGASR_WIDE_VMAX) return PGASR_ERR_UNSUPPORTED;
-    if ((long long)K * B > 0x7fffffffLL / 4) return PGASR_ERR_UNSUPPORTED;
+// ---- the host side of every gradient pass ----
+// A gradient pass of the wide kernels: CTC_WIDE_WPB rows per workgroup, the kernel's NV by V, and ONE `vec` for the launch -- the row
+// loads of log_probs and (KL tail only) ref_log_probs and the row store must all be aligned.  pick(Int<NV>) is the kernel; they all
+// start with the same arguments up to utt_scale, `rest` is what follows them.
+template <int TAIL, class Pick, class... Rest>
+static int ctc_launch_grad_wide(const GradCall& c, const CtcWs& ws, Pick pick, Rest... rest) {
+    const long long waves = (long long)c.T * c.B;
+    const unsigned blocks = (unsigned)((waves + CTC_WIDE_WPB - 1) / CTC_WIDE_WPB);
+#define PGASR_CALL(NV) do {                                                                                                            \
+        const bool vec = wide_vec_ok<NV>(c.log_probs, c.grad_logits, c.V) &&                                                            \
+                         (TAIL < 2 || wide_vec_ok<NV>(c.ref_log_probs, c.ref_log_probs, c.V));                                          \
+        auto kernel = pick(Int<NV>{});                                                                                                  \
+        PGASR_LAUNCH_KERNEL(kernel, dim3(blocks), dim3(64 * CTC_WIDE_WPB), 0, (hipStream_t)c.stream, c.log_probs, c.input_lengths,      \
+                           c.target_lengths, c.T, c.B, c.V, vec ? 1 : 0, c.Lmax > 0 ? c.Lmax : 1, 2 * c.Lmax + 1, c.blank, ws,          \
+                           c.utt_scale, rest...);                                                                                       \
+    } while (0)
+    PGASR_WIDE_DISPATCH(c.V, PGASR_CALL);
+#undef PGASR_CALL
+    PGASR_CHECK_LAUNCH();
     return PGASR_OK;
 }
 
-template <bool PATHS, int TAIL>
-static int ctc_launch_grad_seq_wide(const float* log_probs, const int32_t* input_lengths, const int32_t* target_lengths, int T, int B,
-                                    int V, int Lmax, int blank, const CtcWs& ws, const float* utt_scale, int K, const float* pg_coef,
-                                    const int32_t* pg_paths, const int32_t* hyp_len, int Lh, const CtcWs& hws, const float* ent_scale,
-                                    const float* ref_log_probs, const float* kl_scale, float* grad_logits, void* stream) {
-    const long long waves = (long long)T * B;
-    const unsigned blocks = (unsigned)((waves + CTC_WIDE_WPB - 1) / CTC_WIDE_WPB);
-    // one `vec` for the launch: the row loads of log_probs and ref_log_probs and the row store must all be aligned
-#define PGASR_CALL(NV) PGASR_LAUNCH_KERNEL((ctc_grad_seq_wide_kernel<NV, PATHS, TAIL>), dim3(blocks), dim3(64 * CTC_WIDE_WPB), 0,             \
-                                           (hipStream_t)stream, log_probs, input_lengths, target_lengths, T, B, V,                              \
-                                           (wide_vec_ok<NV>(log_probs, grad_logits, V) &&                                                       \
-                                            (TAIL < 2 || wide_vec_ok<NV>(ref_log_probs, ref_log_probs, V))) ? 1 : 0,                            \
-                                           Lmax > 0 ? Lmax : 1, 2 * Lmax + 1, blank, ws, utt_scale, K, pg_coef, pg_paths, hyp_len, Lh,          \
-                                           2 * Lh + 1, hws, ent_scale, ref_log_probs, kl_scale, grad_logits)
-    PGASR_WIDE_DISPATCH(V, PGASR_CALL);
-#undef PGASR_CALL
+// The one place that names the wide instantiations.  The single-path pass and the N-best form exist without a tail only; the tail
+// pointers a TAIL does not use are NULL in the call (ctc_grad_run), and reach the kernel so.
+template <int TAIL>
+static int ctc_grad_wide(const GradCall& c, GradForm form, const CtcWs& ws, const CtcWs& hws) {
+    const int Smax_h = 2 * c.Lh + 1;
+    switch (form) {
+    case GRAD_ONE:
+        if constexpr (TAIL == 0)
+            return ctc_launch_grad_wide<0>(c, ws, [](auto nv) { return ctc_grad_wide_kernel<decltype(nv)::value>; },
+                                           c.pg_coef, c.pg_paths, c.coef_per_frame, c.grad_logits);
+        break;
+    case GRAD_MULTI:
+        return ctc_launch_grad_wide<TAIL>(c, ws, [](auto nv) { return ctc_grad_multi_wide_kernel<decltype(nv)::value, TAIL, false>; },
+                                          c.K, c.pg_coef, c.pg_paths, c.ent_scale, c.ref_log_probs, c.kl_scale, c.grad_logits);
+    case GRAD_STEPS:
+        return ctc_launch_grad_wide<TAIL>(c, ws, [](auto nv) { return ctc_grad_multi_wide_kernel<decltype(nv)::value, TAIL, true>; },
+                                          c.K, c.pg_coef, c.pg_paths, c.ent_scale, c.ref_log_probs, c.kl_scale, c.grad_logits);
+    case GRAD_SEQ:
+        return ctc_launch_grad_wide<TAIL>(c, ws, [](auto nv) { return ctc_grad_seq_wide_kernel<decltype(nv)::value, true, TAIL>; },
+                                          c.K, c.pg_coef, c.pg_paths, c.hyp_len, c.Lh, Smax_h, hws, c.ent_scale, c.ref_log_probs,
+                                          c.kl_scale, c.grad_logits);
+    case GRAD_NBEST:
+        if constexpr (TAIL == 0)
+            return ctc_launch_grad_wide<0>(c, ws, [](auto nv) { return ctc_grad_seq_wide_kernel<decltype(nv)::value, false, 0>; },
+                                           c.K, c.pg_coef, c.pg_paths, c.hyp_len, c.Lh, Smax_h, hws, c.ent_scale, c.ref_log_probs,
+                                           c.kl_scale, c.grad_logits);
+        break;
+    }
+    return PGASR_ERR_INVALID_ARG;
+}
+
+// Every exported gradient pass: the checks, the workspace(s), the tail, the launch.  vmax is the limit the entry promises
+// (CTC_VMAX or PGASR_WIDE_VMAX); rows of at most CTC_VMAX symbols of the per-frame multi-sample entry, which promises the wide limit,
+// run the one-label-per-lane kernel.  All refusals for bad values come before those for unsupported sizes.
+static int ctc_grad_run(const GradCall& c, GradForm form, int vmax) {
+    const bool hyp = form == GRAD_SEQ || form == GRAD_NBEST;
+    if (!c.log_probs || !c.input_lengths || !c.target_lengths || !c.grad_logits) return PGASR_ERR_INVALID_ARG;
+    if ((c.ref_log_probs == nullptr) != (c.kl_scale == nullptr)) return PGASR_ERR_INVALID_ARG;
+    if (form == GRAD_ONE ? (c.pg_coef == nullptr) != (c.pg_paths == nullptr) : !c.pg_coef || (form != GRAD_NBEST && !c.pg_paths))
+        return PGASR_ERR_INVALID_ARG;
+    if (hyp && !c.hyp_len) return PGASR_ERR_INVALID_ARG;
+    if (form == GRAD_NBEST && (c.ent_scale || c.kl_scale)) return PGASR_ERR_INVALID_ARG;      // the N-best form has no tails
+    int ok = PGASR_OK;
+    if (hyp) {
+        if (c.Lmax < 0 || c.blank < 0 || c.blank >= c.V) return PGASR_ERR_INVALID_ARG;
+        ok = ctc_hyp_args_ok(c.T, c.B, c.V, c.K, c.Lh, vmax);
+    } else if (form != GRAD_ONE && (c.K < 1 || c.K > PGASR_MAX_SAMPLES)) {
+        return PGASR_ERR_INVALID_ARG;
+    }
+    if (ok == PGASR_OK) ok = ctc_args_ok(c.T, c.B, c.V, c.Lmax, c.blank, vmax);
+    if (ok != PGASR_OK) return ok;
+    CtcWs ws, hws{};
+    if (!ctc_ws_bind(c.T, c.B, c.V, 2 * c.Lmax + 1, &ws, c.workspace, c.workspace_bytes)) return PGASR_ERR_WORKSPACE;
+    if (hyp && !ctc_ws_bind(c.T, c.K * c.B, c.V, 2 * c.Lh + 1, &hws, c.hyp_workspace, c.hyp_workspace_bytes)) return PGASR_ERR_WORKSPACE;
+    const bool narrow = vmax <= CTC_VMAX || (form == GRAD_STEPS && c.V <= CTC_VMAX);
+    return ctc_with_tail(c, [&](auto tail) {
+        constexpr int TAIL = decltype(tail)::value;
+        if (!narrow) return ctc_grad_wide<TAIL>(c, form, ws, hws);
+        if constexpr (TAIL == 2) return ctc_grad_narrow<2>(c, form, ws, hws, c.ent_scale, c.ref_log_probs, c.kl_scale);
+        else if constexpr (TAIL == 1) return ctc_grad_narrow<1>(c, form, ws, hws, c.ent_scale);
+        else return ctc_grad_narrow<0>(c, form, ws, hws);
+    });
+}
+
+// The target lattice into ws: the sweeps with the states-per-thread variant that holds Smax.  Narrow: grid (B,3), whose third row
+// builds the label lists.  Wide: ctc_labels_wide_kernel first, then the sweeps alone, grid (B,2).
+static int ctc_launch_lattice(const GradCall& c, const int32_t* targets, float* nll, const CtcWs& ws, bool wide) {
+    const int Lmax1 = c.Lmax > 0 ? c.Lmax : 1, Smax = 2 * c.Lmax + 1;
+    hipStream_t st = (hipStream_t)c.stream;
+    if (wide) {
+        PGASR_LAUNCH_KERNEL(ctc_labels_wide_kernel, dim3(c.B), dim3(256), 0, st, targets, c.target_lengths, c.V, Lmax1, Smax, c.blank, ws);
+        PGASR_CHECK_LAUNCH();
+    }
+    // Lmax == 0 still needs a valid targets row pointer; Lmax>=1 is the caller's job.
+    // (a single-wave register-resident variant was measured SLOWER: 850 us vs 492 us at S=201 --
+    // one wave's fp64 VALU issue rate, not the barrier, is then the limit)
+#define PGASR_LATTICE(NSPT) PGASR_LAUNCH_KERNEL(ctc_lattice_kernel<NSPT>, dim3(c.B, wide ? 2 : 3), dim3(CTC_THREADS + 64), 0, st, c.log_probs, \
+                        targets, c.input_lengths, c.target_lengths, c.T, c.B, c.V, Lmax1, Smax, c.blank, ws, nll, 0)
+    if (Smax <= CTC_THREADS) PGASR_LATTICE(1);
+    else if (Smax <= 2 * CTC_THREADS) PGASR_LATTICE(2);
+    else if (Smax <= 4 * CTC_THREADS) PGASR_LATTICE(4);
+    else PGASR_LATTICE(8);
+#undef PGASR_LATTICE
+    PGASR_CHECK_LAUNCH();
+    return PGASR_OK;
+}
+
+// pgasr_ctc_loss_grad and _wide: the lattice, then (grad_logits given) the single-path pass with a per-utterance coefficient
+static int ctc_loss_grad_run(const GradCall& c, const int32_t* targets, float* nll, int vmax) {
+    if (!c.log_probs || !targets || !c.input_lengths || !c.target_lengths || !nll) return PGASR_ERR_INVALID_ARG;
+    if ((c.pg_coef == nullptr) != (c.pg_paths == nullptr)) return PGASR_ERR_INVALID_ARG;
+    int ok = ctc_args_ok(c.T, c.B, c.V, c.Lmax, c.blank, vmax);
+    if (ok != PGASR_OK) return ok;
+    CtcWs ws;
+    if (!ctc_ws_bind(c.T, c.B, c.V, 2 * c.Lmax + 1, &ws, c.workspace, c.workspace_bytes)) return PGASR_ERR_WORKSPACE;
+    ok = ctc_launch_lattice(c, targets, nll, ws, vmax > CTC_VMAX);
+    return ok != PGASR_OK || !c.grad_logits ? ok : ctc_grad_run(c, GRAD_ONE, vmax);
+}
+
+// pgasr_ctc_hyp_lattice and _wide: the K*B hypothesis lattices, the ladder and the two families as in ctc_launch_lattice
+static int ctc_hyp_lattice_run(const float* log_probs, const int32_t* hyp_tokens, int hyp_stride, const int32_t* hyp_len,
+                               const int32_t* input_lengths, int T, int B, int V, int K, int Lh, int blank, float* hyp_nll,
+                               void* hyp_workspace, size_t hyp_workspace_bytes, void* stream, int vmax) {
+    if (!log_probs || !hyp_tokens || !hyp_len || !input_lengths || !hyp_nll) return PGASR_ERR_INVALID_ARG;
+    if (blank < 0 || blank >= V || hyp_stride < 1 || hyp_stride < Lh) return PGASR_ERR_INVALID_ARG;
+    const int ok = ctc_hyp_args_ok(T, B, V, K, Lh, vmax);
+    if (ok != PGASR_OK) return ok;
+    const int Smax = 2 * Lh + 1;
+    const bool wide = vmax > CTC_VMAX;
+    CtcWs ws;
+    if (!ctc_ws_bind(T, K * B, V, Smax, &ws, hyp_workspace, hyp_workspace_bytes)) return PGASR_ERR_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    if (wide) {
+        PGASR_LAUNCH_KERNEL(ctc_hyp_labels_wide_kernel, dim3(K * B), dim3(256), 0, st, hyp_tokens, hyp_stride, hyp_len, V, Lh, Smax, blank, ws);
+        PGASR_CHECK_LAUNCH();
+    }
+#define PGASR_HYP_LATTICE(NMAX) PGASR_LAUNCH_KERNEL(ctc_hyp_lattice_kernel<NMAX>, dim3(K * B, wide ? 2 : 3), dim3(CTC_THREADS + 64), 0, st, \
+                        log_probs, hyp_tokens, hyp_stride, hyp_len, input_lengths, T, B, V, Lh, Smax, blank, ws, hyp_nll)
+    if (Smax <= CTC_THREADS) PGASR_HYP_LATTICE(1);
+    else if (Smax <= 2 * CTC_THREADS) PGASR_HYP_LATTICE(2);
+    else if (Smax <= 4 * CTC_THREADS) PGASR_HYP_LATTICE(4);
+    else PGASR_HYP_LATTICE(8);
+#undef PGASR_HYP_LATTICE
     PGASR_CHECK_LAUNCH();
     return PGASR_OK;
 }
 
 }  // namespace
 
+// ---- the exported entries: each fills a GradCall group by group ({head}, {policy gradient}, {hypotheses}, {tail}, output,
+// workspace, stream) and names its form and V limit.  The narrow X -> X_ent -> X_kl chains forward with NULL tails. ----
 extern "C" size_t pgasr_ctc_workspace_bytes(int T, int B, int V, int Lmax) {
     if (T <= 0 || B <= 0 || V <= 0 || Lmax < 0) return 0;
     return ctc_ws_layout(T, B, V, 2 * Lmax + 1, nullptr, nullptr);
@@ -1245,28 +1369,8 @@ extern "C" int pgasr_ctc_loss_grad(const float* log_probs, const int32_t* target
                                    const float* utt_scale, const float* pg_coef, const int32_t* pg_path,
                                    float* nll, float* grad_logits,
                                    void* workspace, size_t workspace_bytes, void* stream) {
-    if (!log_probs || !targets || !input_lengths || !target_lengths || !nll) return PGASR_ERR_INVALID_ARG;
-    if ((pg_coef == nullptr) != (pg_path == nullptr)) return PGASR_ERR_INVALID_ARG;
-    const int ok = ctc_args_ok(T, B, V, Lmax, blank);
-    if (ok != PGASR_OK) return ok;
-    const int Smax = 2 * Lmax + 1;
-    CtcWs ws;
-    if (!ctc_ws_bind(T, B, V, Smax, &ws, workspace, workspace_bytes)) return PGASR_ERR_WORKSPACE;
-    hipStream_t st = (hipStream_t)stream;
-    // Lmax == 0 still needs a valid targets row pointer; Lmax>=1 is the caller's job.
-    // (a single-wave register-resident variant was measured SLOWER: 850 us vs 492 us at S=201 --
-    // one wave's fp64 VALU issue rate, not the barrier, is then the limit)
-#define PGASR_LATTICE(NSPT) PGASR_LAUNCH_KERNEL(ctc_lattice_kernel<NSPT>, dim3(B, 3), dim3(CTC_THREADS + 64), 0, st, \
-                        log_probs, targets, input_lengths, target_lengths, T, B, V, Lmax > 0 ? Lmax : 1, Smax, blank, ws, nll, 0)
-    if (Smax <= CTC_THREADS) PGASR_LATTICE(1);
-    else if (Smax <= 2 * CTC_THREADS) PGASR_LATTICE(2);
-    else if (Smax <= 4 * CTC_THREADS) PGASR_LATTICE(4);
-    else PGASR_LATTICE(8);
-#undef PGASR_LATTICE
-    PGASR_CHECK_LAUNCH();
-    if (!grad_logits) return PGASR_OK;
-    return ctc_launch_grad(ctc_grad_kernel<false>, log_probs, input_lengths, target_lengths, T, B, V, Lmax, blank, ws, utt_scale, stream,
-                           pg_coef, pg_path, 0, grad_logits);
+    return ctc_loss_grad_run({{log_probs, input_lengths, target_lengths, T, B, V, Lmax, blank, utt_scale}, {1, pg_coef, pg_path, 0}, {}, {},
+                              grad_logits, workspace, workspace_bytes, stream}, targets, nll, CTC_VMAX);
 }
 
 // Second half of pgasr_ctc_loss_grad on its own: the gradient pass over a lattice that an earlier
@@ -1282,7 +1386,6 @@ extern "C" int pgasr_ctc_grad_from_lattice(const float* log_probs, const int32_t
                                            pg_coef_per_frame, nullptr, grad_logits, workspace, workspace_bytes, stream);
 }
 
-// ... with the entropy term: ent_scale NULL launches the kernel of the entry above, else its ENT instantiation
 extern "C" int pgasr_ctc_grad_from_lattice_ent(const float* log_probs, const int32_t* input_lengths,
                                                const int32_t* target_lengths, int T, int B, int V, int Lmax, int blank,
                                                const float* utt_scale, const float* pg_coef, const int32_t* pg_path,
@@ -1292,29 +1395,15 @@ extern "C" int pgasr_ctc_grad_from_lattice_ent(const float* log_probs, const int
                                           pg_coef_per_frame, ent_scale, nullptr, nullptr, grad_logits, workspace, workspace_bytes, stream);
 }
 
-// ... and with the KL term: ref_log_probs and kl_scale both NULL launch what the entry above launched, else the three-pointer
-// instantiation (ent_scale may be NULL there)
 extern "C" int pgasr_ctc_grad_from_lattice_kl(const float* log_probs, const int32_t* input_lengths,
                                               const int32_t* target_lengths, int T, int B, int V, int Lmax, int blank,
                                               const float* utt_scale, const float* pg_coef, const int32_t* pg_path,
                                               int pg_coef_per_frame, const float* ent_scale, const float* ref_log_probs,
                                               const float* kl_scale, float* grad_logits,
                                               void* workspace, size_t workspace_bytes, void* stream) {
-    if (!log_probs || !input_lengths || !target_lengths || !grad_logits) return PGASR_ERR_INVALID_ARG;
-    if ((ref_log_probs == nullptr) != (kl_scale == nullptr)) return PGASR_ERR_INVALID_ARG;
-    if ((pg_coef == nullptr) != (pg_path == nullptr)) return PGASR_ERR_INVALID_ARG;
-    const int ok = ctc_args_ok(T, B, V, Lmax, blank);
-    if (ok != PGASR_OK) return ok;
-    CtcWs ws;
-    if (!ctc_ws_bind(T, B, V, 2 * Lmax + 1, &ws, workspace, workspace_bytes)) return PGASR_ERR_WORKSPACE;
-    if (kl_scale)
-        return ctc_launch_grad(ctc_grad_kernel<true, const float*, const float*, const float*>, log_probs, input_lengths, target_lengths, T, B, V, Lmax,
-                               blank, ws, utt_scale, stream, pg_coef, pg_path, pg_coef_per_frame ? 1 : 0, grad_logits, ent_scale, ref_log_probs, kl_scale);
-    if (ent_scale)
-        return ctc_launch_grad(ctc_grad_kernel<true, const float*>, log_probs, input_lengths, target_lengths, T, B, V, Lmax, blank, ws, utt_scale, stream,
-                               pg_coef, pg_path, pg_coef_per_frame ? 1 : 0, grad_logits, ent_scale);
-    return ctc_launch_grad(ctc_grad_kernel<false>, log_probs, input_lengths, target_lengths, T, B, V, Lmax, blank, ws, utt_scale, stream,
-                           pg_coef, pg_path, pg_coef_per_frame ? 1 : 0, grad_logits);
+    return ctc_grad_run({{log_probs, input_lengths, target_lengths, T, B, V, Lmax, blank, utt_scale},
+                         {1, pg_coef, pg_path, pg_coef_per_frame ? 1 : 0}, {}, {ent_scale, ref_log_probs, kl_scale},
+                         grad_logits, workspace, workspace_bytes, stream}, GRAD_ONE, CTC_VMAX);
 }
 
 // pgasr_ctc_grad_from_lattice with K sampled paths per utterance (multi-sample REINFORCE): pg_paths (K,T,B), pg_coef (K,B).
@@ -1340,21 +1429,8 @@ extern "C" int pgasr_ctc_grad_from_lattice_multi_kl(const float* log_probs, cons
                                                     const float* utt_scale, int K, const float* pg_coef, const int32_t* pg_paths,
                                                     const float* ent_scale, const float* ref_log_probs, const float* kl_scale,
                                                     float* grad_logits, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!log_probs || !input_lengths || !target_lengths || !grad_logits || !pg_coef || !pg_paths) return PGASR_ERR_INVALID_ARG;
-    if ((ref_log_probs == nullptr) != (kl_scale == nullptr)) return PGASR_ERR_INVALID_ARG;
-    if (K < 1 || K > PGASR_MAX_SAMPLES) return PGASR_ERR_INVALID_ARG;
-    const int ok = ctc_args_ok(T, B, V, Lmax, blank);
-    if (ok != PGASR_OK) return ok;
-    CtcWs ws;
-    if (!ctc_ws_bind(T, B, V, 2 * Lmax + 1, &ws, workspace, workspace_bytes)) return PGASR_ERR_WORKSPACE;
-    if (kl_scale)
-        return ctc_launch_grad(ctc_grad_multi_kernel<true, false, const float*, const float*, const float*>, log_probs, input_lengths, target_lengths, T, B, V,
-                               Lmax, blank, ws, utt_scale, stream, K, pg_coef, pg_paths, grad_logits, ent_scale, ref_log_probs, kl_scale);
-    if (ent_scale)
-        return ctc_launch_grad(ctc_grad_multi_kernel<true, false, const float*>, log_probs, input_lengths, target_lengths, T, B, V, Lmax, blank, ws, utt_scale,
-                               stream, K, pg_coef, pg_paths, grad_logits, ent_scale);
-    return ctc_launch_grad(ctc_grad_multi_kernel<false, false>, log_probs, input_lengths, target_lengths, T, B, V, Lmax, blank, ws, utt_scale,
-                           stream, K, pg_coef, pg_paths, grad_logits);
+    return ctc_grad_run({{log_probs, input_lengths, target_lengths, T, B, V, Lmax, blank, utt_scale}, {K, pg_coef, pg_paths, 0}, {},
+                         {ent_scale, ref_log_probs, kl_scale}, grad_logits, workspace, workspace_bytes, stream}, GRAD_MULTI, CTC_VMAX);
 }
 
 // ---- the frame policy's entropy: ent_mean (B) for monitoring and the loss value, ent_scale (B) for the *_ent gradient passes ----
@@ -1383,30 +1459,15 @@ extern "C" int pgasr_frame_kl(const float* log_probs, const float* ref_log_probs
 
 // ---- sequence-level REINFORCE: the K*B hypothesis lattices and the passes over K+1 lattices (see the kernels' comment) ----
 extern "C" size_t pgasr_ctc_hyp_workspace_bytes(int T, int B, int V, int K, int Lh) {
-    if (ctc_hyp_args_ok(T, B, V, K, Lh) != PGASR_OK) return 0;
+    if (ctc_hyp_args_ok(T, B, V, K, Lh, CTC_VMAX) != PGASR_OK) return 0;
     return ctc_ws_layout(T, K * B, V, 2 * Lh + 1, nullptr, nullptr);
 }
 
 extern "C" int pgasr_ctc_hyp_lattice(const float* log_probs, const int32_t* hyp_tokens, int hyp_stride, const int32_t* hyp_len,
                                      const int32_t* input_lengths, int T, int B, int V, int K, int Lh, int blank,
                                      float* hyp_nll, void* hyp_workspace, size_t hyp_workspace_bytes, void* stream) {
-    if (!log_probs || !hyp_tokens || !hyp_len || !input_lengths || !hyp_nll) return PGASR_ERR_INVALID_ARG;
-    if (blank < 0 || blank >= V || hyp_stride < 1 || hyp_stride < Lh) return PGASR_ERR_INVALID_ARG;
-    const int ok = ctc_hyp_args_ok(T, B, V, K, Lh);
-    if (ok != PGASR_OK) return ok;
-    const int Smax = 2 * Lh + 1;
-    CtcWs ws;
-    if (!ctc_ws_bind(T, K * B, V, Smax, &ws, hyp_workspace, hyp_workspace_bytes)) return PGASR_ERR_WORKSPACE;
-    hipStream_t st = (hipStream_t)stream;
-#define PGASR_HYP_LATTICE(NMAX) PGASR_LAUNCH_KERNEL(ctc_hyp_lattice_kernel<NMAX>, dim3(K * B, 3), dim3(CTC_THREADS + 64), 0, st, \
-                        log_probs, hyp_tokens, hyp_stride, hyp_len, input_lengths, T, B, V, Lh, Smax, blank, ws, hyp_nll)
-    if (Smax <= CTC_THREADS) PGASR_HYP_LATTICE(1);
-    else if (Smax <= 2 * CTC_THREADS) PGASR_HYP_LATTICE(2);
-    else if (Smax <= 4 * CTC_THREADS) PGASR_HYP_LATTICE(4);
-    else PGASR_HYP_LATTICE(8);
-#undef PGASR_HYP_LATTICE
-    PGASR_CHECK_LAUNCH();
-    return PGASR_OK;
+    return ctc_hyp_lattice_run(log_probs, hyp_tokens, hyp_stride, hyp_len, input_lengths, T, B, V, K, Lh, blank, hyp_nll, hyp_workspace,
+                               hyp_workspace_bytes, stream, CTC_VMAX);
 }
 
 extern "C" int pgasr_ctc_grad_from_lattices_seq(const float* log_probs, const int32_t* input_lengths, const int32_t* target_lengths,
@@ -1435,25 +1496,9 @@ extern "C" int pgasr_ctc_grad_from_lattices_seq_kl(const float* log_probs, const
                                                    const float* ent_scale, const float* ref_log_probs, const float* kl_scale,
                                                    float* grad_logits, void* workspace, size_t workspace_bytes,
                                                    void* hyp_workspace, size_t hyp_workspace_bytes, void* stream) {
-    if (!log_probs || !input_lengths || !target_lengths || !grad_logits || !pg_coef || !pg_paths || !hyp_len) return PGASR_ERR_INVALID_ARG;
-    if ((ref_log_probs == nullptr) != (kl_scale == nullptr)) return PGASR_ERR_INVALID_ARG;
-    if (Lmax < 0 || blank < 0 || blank >= V) return PGASR_ERR_INVALID_ARG;
-    int ok = ctc_hyp_args_ok(T, B, V, K, Lh);
-    if (ok == PGASR_OK) ok = ctc_args_ok(T, B, V, Lmax, blank);
-    if (ok != PGASR_OK) return ok;
-    const int Smax_h = 2 * Lh + 1;
-    CtcWs ws, hws;
-    if (!ctc_ws_bind(T, B, V, 2 * Lmax + 1, &ws, workspace, workspace_bytes)) return PGASR_ERR_WORKSPACE;
-    if (!ctc_ws_bind(T, K * B, V, Smax_h, &hws, hyp_workspace, hyp_workspace_bytes)) return PGASR_ERR_WORKSPACE;
-    if (kl_scale)
-        return ctc_launch_grad(ctc_grad_seq_kernel<true, true, const float*, const float*, const float*>, log_probs, input_lengths, target_lengths, T, B,
-                               V, Lmax, blank, ws, utt_scale, stream, K, pg_coef, pg_paths, hyp_len, Lh, Smax_h, hws, grad_logits, ent_scale,
-                               ref_log_probs, kl_scale);
-    if (ent_scale)
-        return ctc_launch_grad(ctc_grad_seq_kernel<true, true, const float*>, log_probs, input_lengths, target_lengths, T, B, V, Lmax, blank, ws, utt_scale,
-                               stream, K, pg_coef, pg_paths, hyp_len, Lh, Smax_h, hws, grad_logits, ent_scale);
-    return ctc_launch_grad(ctc_grad_seq_kernel<false, true>, log_probs, input_lengths, target_lengths, T, B, V, Lmax, blank, ws, utt_scale,
-                           stream, K, pg_coef, pg_paths, hyp_len, Lh, Smax_h, hws, grad_logits);
+    return ctc_grad_run({{log_probs, input_lengths, target_lengths, T, B, V, Lmax, blank, utt_scale}, {K, pg_coef, pg_paths, 0},
+                         {hyp_len, Lh, hyp_workspace, hyp_workspace_bytes}, {ent_scale, ref_log_probs, kl_scale},
+                         grad_logits, workspace, workspace_bytes, stream}, GRAD_SEQ, CTC_VMAX);
 }
 
 // MWER over N-best lists: the sequence pass without a path tensor.  Every pair (n,b) adds coef[n,b] (softmax - occ_{y_n}) from its
@@ -1464,17 +1509,9 @@ extern "C" int pgasr_ctc_grad_from_lattices_nbest(const float* log_probs, const 
                                                   int N, const float* coef, const int32_t* hyp_len, int Lh,
                                                   float* grad_logits, void* workspace, size_t workspace_bytes,
                                                   void* hyp_workspace, size_t hyp_workspace_bytes, void* stream) {
-    if (!log_probs || !input_lengths || !target_lengths || !grad_logits || !coef || !hyp_len) return PGASR_ERR_INVALID_ARG;
-    if (Lmax < 0 || blank < 0 || blank >= V) return PGASR_ERR_INVALID_ARG;
-    int ok = ctc_hyp_args_ok(T, B, V, N, Lh);
-    if (ok == PGASR_OK) ok = ctc_args_ok(T, B, V, Lmax, blank);
-    if (ok != PGASR_OK) return ok;
-    const int Smax_h = 2 * Lh + 1;
-    CtcWs ws, hws;
-    if (!ctc_ws_bind(T, B, V, 2 * Lmax + 1, &ws, workspace, workspace_bytes)) return PGASR_ERR_WORKSPACE;
-    if (!ctc_ws_bind(T, N * B, V, Smax_h, &hws, hyp_workspace, hyp_workspace_bytes)) return PGASR_ERR_WORKSPACE;
-    return ctc_launch_grad(ctc_grad_seq_kernel<false, false>, log_probs, input_lengths, target_lengths, T, B, V, Lmax, blank, ws, utt_scale,
-                           stream, N, coef, (const int32_t*)nullptr, hyp_len, Lh, Smax_h, hws, grad_logits);
+    return ctc_grad_run({{log_probs, input_lengths, target_lengths, T, B, V, Lmax, blank, utt_scale}, {N, coef, nullptr, 0},
+                         {hyp_len, Lh, hyp_workspace, hyp_workspace_bytes}, {}, grad_logits, workspace, workspace_bytes, stream},
+                        GRAD_NBEST, CTC_VMAX);
 }
 
 extern "C" int pgasr_pg_loss_value_seq(const float* log_probs, const int32_t* paths, int K, const int32_t* input_lengths,
@@ -1498,28 +1535,8 @@ extern "C" int pgasr_ctc_loss_grad_wide(const float* log_probs, const int32_t* t
                                         const float* utt_scale, const float* pg_coef, const int32_t* pg_path,
                                         float* nll, float* grad_logits,
                                         void* workspace, size_t workspace_bytes, void* stream) {
-    if (!log_probs || !targets || !input_lengths || !target_lengths || !nll) return PGASR_ERR_INVALID_ARG;
-    if ((pg_coef == nullptr) != (pg_path == nullptr)) return PGASR_ERR_INVALID_ARG;
-    const int ok = ctc_args_ok_wide(T, B, V, Lmax, blank);
-    if (ok != PGASR_OK) return ok;
-    const int Smax = 2 * Lmax + 1;
-    CtcWs ws;
-    if (!ctc_ws_bind(T, B, V, Smax, &ws, workspace, workspace_bytes)) return PGASR_ERR_WORKSPACE;
-    hipStream_t st = (hipStream_t)stream;
-    PGASR_LAUNCH_KERNEL(ctc_labels_wide_kernel, dim3(B), dim3(256), 0, st, targets, target_lengths, V, Lmax > 0 ? Lmax : 1, Smax, blank, ws);
-    PGASR_CHECK_LAUNCH();
-    // the sweeps alone: grid rows 0 and 1 of the lattice kernel, whose third row (the narrow label lists) is not launched
-#define PGASR_LATTICE(NSPT) PGASR_LAUNCH_KERNEL(ctc_lattice_kernel<NSPT>, dim3(B, 2), dim3(CTC_THREADS + 64), 0, st, \
-                        log_probs, targets, input_lengths, target_lengths, T, B, V, Lmax > 0 ? Lmax : 1, Smax, blank, ws, nll, 0)
-    if (Smax <= CTC_THREADS) PGASR_LATTICE(1);
-    else if (Smax <= 2 * CTC_THREADS) PGASR_LATTICE(2);
-    else if (Smax <= 4 * CTC_THREADS) PGASR_LATTICE(4);
-    else PGASR_LATTICE(8);
-#undef PGASR_LATTICE
-    PGASR_CHECK_LAUNCH();
-    if (!grad_logits) return PGASR_OK;
-    return ctc_launch_grad_wide(log_probs, input_lengths, target_lengths, T, B, V, Lmax, blank, ws, utt_scale, pg_coef, pg_path,
-                                0, grad_logits, stream);
+    return ctc_loss_grad_run({{log_probs, input_lengths, target_lengths, T, B, V, Lmax, blank, utt_scale}, {1, pg_coef, pg_path, 0}, {}, {},
+                              grad_logits, workspace, workspace_bytes, stream}, targets, nll, PGASR_WIDE_VMAX);
 }
 
 extern "C" int pgasr_ctc_grad_from_lattice_wide(const float* log_probs, const int32_t* input_lengths,
@@ -1527,137 +1544,55 @@ extern "C" int pgasr_ctc_grad_from_lattice_wide(const float* log_probs, const in
                                                 const float* utt_scale, const float* pg_coef, const int32_t* pg_path,
                                                 int pg_coef_per_frame, float* grad_logits, void* workspace, size_t workspace_bytes,
                                                 void* stream) {
-    if (!log_probs || !input_lengths || !target_lengths || !grad_logits) return PGASR_ERR_INVALID_ARG;
-    if ((pg_coef == nullptr) != (pg_path == nullptr)) return PGASR_ERR_INVALID_ARG;
-    const int ok = ctc_args_ok_wide(T, B, V, Lmax, blank);
-    if (ok != PGASR_OK) return ok;
-    CtcWs ws;
-    if (!ctc_ws_bind(T, B, V, 2 * Lmax + 1, &ws, workspace, workspace_bytes)) return PGASR_ERR_WORKSPACE;
-    return ctc_launch_grad_wide(log_probs, input_lengths, target_lengths, T, B, V, Lmax, blank, ws, utt_scale, pg_coef, pg_path,
-                                pg_coef_per_frame ? 1 : 0, grad_logits, stream);
+    return ctc_grad_run({{log_probs, input_lengths, target_lengths, T, B, V, Lmax, blank, utt_scale},
+                         {1, pg_coef, pg_path, pg_coef_per_frame ? 1 : 0}, {}, {}, grad_logits, workspace, workspace_bytes, stream},
+                        GRAD_ONE, PGASR_WIDE_VMAX);
 }
 
 // ---- A12-WIDE: pgasr_ctc_grad_from_lattice_multi with its entropy and KL forms in one entry, for 1 <= V <= 1024 ----
-// ent_scale NULL and ref_log_probs / kl_scale NULL: the plain instantiation; ent_scale alone: the entropy one; ref_log_probs and
-// kl_scale (together): the one with both tails, ent_scale nullable there.
 extern "C" int pgasr_ctc_grad_from_lattice_multi_wide(const float* log_probs, const int32_t* input_lengths,
                                                       const int32_t* target_lengths, int T, int B, int V, int Lmax, int blank,
                                                       const float* utt_scale, int K, const float* pg_coef, const int32_t* pg_paths,
                                                       const float* ent_scale, const float* ref_log_probs, const float* kl_scale,
                                                       float* grad_logits, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!log_probs || !input_lengths || !target_lengths || !grad_logits || !pg_coef || !pg_paths) return PGASR_ERR_INVALID_ARG;
-    if ((ref_log_probs == nullptr) != (kl_scale == nullptr)) return PGASR_ERR_INVALID_ARG;
-    if (K < 1 || K > PGASR_MAX_SAMPLES) return PGASR_ERR_INVALID_ARG;
-    const int ok = ctc_args_ok_wide(T, B, V, Lmax, blank);
-    if (ok != PGASR_OK) return ok;
-    CtcWs ws;
-    if (!ctc_ws_bind(T, B, V, 2 * Lmax + 1, &ws, workspace, workspace_bytes)) return PGASR_ERR_WORKSPACE;
-    if (kl_scale)
-        return ctc_launch_grad_multi_wide<2>(log_probs, input_lengths, target_lengths, T, B, V, Lmax, blank, ws, utt_scale, K, pg_coef,
-                                             pg_paths, ent_scale, ref_log_probs, kl_scale, grad_logits, stream);
-    if (ent_scale)
-        return ctc_launch_grad_multi_wide<1>(log_probs, input_lengths, target_lengths, T, B, V, Lmax, blank, ws, utt_scale, K, pg_coef,
-                                             pg_paths, ent_scale, nullptr, nullptr, grad_logits, stream);
-    return ctc_launch_grad_multi_wide<0>(log_probs, input_lengths, target_lengths, T, B, V, Lmax, blank, ws, utt_scale, K, pg_coef,
-                                         pg_paths, nullptr, nullptr, nullptr, grad_logits, stream);
+    return ctc_grad_run({{log_probs, input_lengths, target_lengths, T, B, V, Lmax, blank, utt_scale}, {K, pg_coef, pg_paths, 0}, {},
+                         {ent_scale, ref_log_probs, kl_scale}, grad_logits, workspace, workspace_bytes, stream}, GRAD_MULTI, PGASR_WIDE_VMAX);
 }
 
 // ---- A12-STEP: the multi-sample gradient pass with per-frame coefficients pg_coef (K,T,B), ONE entry for 1 <= V <= 1024 ----
-// The tails are nullable as in the entry above.  V <= 64 runs ctc_grad_multi_kernel (one label per lane) over the lattice
-// pgasr_ctc_loss_grad left, V > 64 ctc_grad_multi_wide_kernel's over pgasr_ctc_loss_grad_wide's -- the workspace layout is the same --,
-// so coefficients that are constant over t give the bits of the per-utterance entries a caller would have taken for that V.
+// V <= 64 runs ctc_grad_multi_kernel (one label per lane) over the lattice pgasr_ctc_loss_grad left, V > 64
+// ctc_grad_multi_wide_kernel's over pgasr_ctc_loss_grad_wide's -- the workspace layout is the same --, so coefficients that are
+// constant over t give the bits of the per-utterance entries a caller would have taken for that V.
 extern "C" int pgasr_ctc_grad_from_lattice_multi_steps(const float* log_probs, const int32_t* input_lengths,
                                                        const int32_t* target_lengths, int T, int B, int V, int Lmax, int blank,
                                                        const float* utt_scale, int K, const float* pg_coef, const int32_t* pg_paths,
                                                        const float* ent_scale, const float* ref_log_probs, const float* kl_scale,
                                                        float* grad_logits, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!log_probs || !input_lengths || !target_lengths || !grad_logits || !pg_coef || !pg_paths) return PGASR_ERR_INVALID_ARG;
-    if ((ref_log_probs == nullptr) != (kl_scale == nullptr)) return PGASR_ERR_INVALID_ARG;
-    if (K < 1 || K > PGASR_MAX_SAMPLES) return PGASR_ERR_INVALID_ARG;
-    const int ok = ctc_args_ok_wide(T, B, V, Lmax, blank);
-    if (ok != PGASR_OK) return ok;
-    CtcWs ws;
-    if (!ctc_ws_bind(T, B, V, 2 * Lmax + 1, &ws, workspace, workspace_bytes)) return PGASR_ERR_WORKSPACE;
-    if (V <= CTC_VMAX) {
-        if (kl_scale)
-            return ctc_launch_grad(ctc_grad_multi_kernel<true, true, const float*, const float*, const float*>, log_probs, input_lengths,
-                                   target_lengths, T, B, V, Lmax, blank, ws, utt_scale, stream, K, pg_coef, pg_paths, grad_logits, ent_scale,
-                                   ref_log_probs, kl_scale);
-        if (ent_scale)
-            return ctc_launch_grad(ctc_grad_multi_kernel<true, true, const float*>, log_probs, input_lengths, target_lengths, T, B, V, Lmax,
-                                   blank, ws, utt_scale, stream, K, pg_coef, pg_paths, grad_logits, ent_scale);
-        return ctc_launch_grad(ctc_grad_multi_kernel<false, true>, log_probs, input_lengths, target_lengths, T, B, V, Lmax, blank, ws,
-                               utt_scale, stream, K, pg_coef, pg_paths, grad_logits);
-    }
-    if (kl_scale)
-        return ctc_launch_grad_multi_wide<2, true>(log_probs, input_lengths, target_lengths, T, B, V, Lmax, blank, ws, utt_scale, K, pg_coef,
-                                                   pg_paths, ent_scale, ref_log_probs, kl_scale, grad_logits, stream);
-    if (ent_scale)
-        return ctc_launch_grad_multi_wide<1, true>(log_probs, input_lengths, target_lengths, T, B, V, Lmax, blank, ws, utt_scale, K, pg_coef,
-                                                   pg_paths, ent_scale, nullptr, nullptr, grad_logits, stream);
-    return ctc_launch_grad_multi_wide<0, true>(log_probs, input_lengths, target_lengths, T, B, V, Lmax, blank, ws, utt_scale, K, pg_coef,
-                                               pg_paths, nullptr, nullptr, nullptr, grad_logits, stream);
+    return ctc_grad_run({{log_probs, input_lengths, target_lengths, T, B, V, Lmax, blank, utt_scale}, {K, pg_coef, pg_paths, 1}, {},
+                         {ent_scale, ref_log_probs, kl_scale}, grad_logits, workspace, workspace_bytes, stream}, GRAD_STEPS, PGASR_WIDE_VMAX);
 }
 
 // ---- A13-WIDE: the hypothesis lattices and the pass over K+1 lattices for 1 <= V <= 1024 (same workspaces, same sweep kernel) ----
 extern "C" size_t pgasr_ctc_hyp_workspace_bytes_wide(int T, int B, int V, int K, int Lh) {
-    if (ctc_hyp_args_ok_wide(T, B, V, K, Lh) != PGASR_OK) return 0;
+    if (ctc_hyp_args_ok(T, B, V, K, Lh, PGASR_WIDE_VMAX) != PGASR_OK) return 0;
     return ctc_ws_layout(T, K * B, V, 2 * Lh + 1, nullptr, nullptr);
 }
 
 extern "C" int pgasr_ctc_hyp_lattice_wide(const float* log_probs, const int32_t* hyp_tokens, int hyp_stride, const int32_t* hyp_len,
                                           const int32_t* input_lengths, int T, int B, int V, int K, int Lh, int blank,
                                           float* hyp_nll, void* hyp_workspace, size_t hyp_workspace_bytes, void* stream) {
-    if (!log_probs || !hyp_tokens || !hyp_len || !input_lengths || !hyp_nll) return PGASR_ERR_INVALID_ARG;
-    if (blank < 0 || blank >= V || hyp_stride < 1 || hyp_stride < Lh) return PGASR_ERR_INVALID_ARG;
-    const int ok = ctc_hyp_args_ok_wide(T, B, V, K, Lh);
-    if (ok != PGASR_OK) return ok;
-    const int Smax = 2 * Lh + 1;
-    CtcWs ws;
-    if (!ctc_ws_bind(T, K * B, V, Smax, &ws, hyp_workspace, hyp_workspace_bytes)) return PGASR_ERR_WORKSPACE;
-    hipStream_t st = (hipStream_t)stream;
-    PGASR_LAUNCH_KERNEL(ctc_hyp_labels_wide_kernel, dim3(K * B), dim3(256), 0, st, hyp_tokens, hyp_stride, hyp_len, V, Lh, Smax, blank, ws);
-    PGASR_CHECK_LAUNCH();
-    // the sweeps alone: grid rows 0 and 1 of the hypothesis lattice kernel, whose third row (the narrow label lists) is not launched
-#define PGASR_HYP_LATTICE(NMAX) PGASR_LAUNCH_KERNEL(ctc_hyp_lattice_kernel<NMAX>, dim3(K * B, 2), dim3(CTC_THREADS + 64), 0, st, \
-                        log_probs, hyp_tokens, hyp_stride, hyp_len, input_lengths, T, B, V, Lh, Smax, blank, ws, hyp_nll)
-    if (Smax <= CTC_THREADS) PGASR_HYP_LATTICE(1);
-    else if (Smax <= 2 * CTC_THREADS) PGASR_HYP_LATTICE(2);
-    else if (Smax <= 4 * CTC_THREADS) PGASR_HYP_LATTICE(4);
-    else PGASR_HYP_LATTICE(8);
-#undef PGASR_HYP_LATTICE
-    PGASR_CHECK_LAUNCH();
-    return PGASR_OK;
+    return ctc_hyp_lattice_run(log_probs, hyp_tokens, hyp_stride, hyp_len, input_lengths, T, B, V, K, Lh, blank, hyp_nll, hyp_workspace,
+                               hyp_workspace_bytes, stream, PGASR_WIDE_VMAX);
 }
 
-// pgasr_ctc_grad_from_lattices_seq, _seq_ent, _seq_kl and (pg_paths NULL) pgasr_ctc_grad_from_lattices_nbest in one entry.
-// ent_scale NULL and ref_log_probs / kl_scale NULL: the plain instantiation; ent_scale alone: the entropy one; ref_log_probs and
-// kl_scale (together): the one with both tails, ent_scale nullable there.  The N-best form has no tails.
+// pgasr_ctc_grad_from_lattices_seq, _seq_ent, _seq_kl and (pg_paths NULL) pgasr_ctc_grad_from_lattices_nbest in one entry
 extern "C" int pgasr_ctc_grad_from_lattices_seq_wide(const float* log_probs, const int32_t* input_lengths, const int32_t* target_lengths,
                                                      int T, int B, int V, int Lmax, int blank, const float* utt_scale,
                                                      int K, const float* pg_coef, const int32_t* pg_paths, const int32_t* hyp_len, int Lh,
                                                      const float* ent_scale, const float* ref_log_probs, const float* kl_scale,
                                                      float* grad_logits, void* workspace, size_t workspace_bytes,
                                                      void* hyp_workspace, size_t hyp_workspace_bytes, void* stream) {
-    if (!log_probs || !input_lengths || !target_lengths || !grad_logits || !pg_coef || !hyp_len) return PGASR_ERR_INVALID_ARG;
-    if ((ref_log_probs == nullptr) != (kl_scale == nullptr)) return PGASR_ERR_INVALID_ARG;
-    if (!pg_paths && (ent_scale || kl_scale)) return PGASR_ERR_INVALID_ARG;
-    if (Lmax < 0 || blank < 0 || blank >= V) return PGASR_ERR_INVALID_ARG;
-    int ok = ctc_hyp_args_ok_wide(T, B, V, K, Lh);
-    if (ok == PGASR_OK) ok = ctc_args_ok_wide(T, B, V, Lmax, blank);
-    if (ok != PGASR_OK) return ok;
-    CtcWs ws, hws;
-    if (!ctc_ws_bind(T, B, V, 2 * Lmax + 1, &ws, workspace, workspace_bytes)) return PGASR_ERR_WORKSPACE;
-    if (!ctc_ws_bind(T, K * B, V, 2 * Lh + 1, &hws, hyp_workspace, hyp_workspace_bytes)) return PGASR_ERR_WORKSPACE;
-    if (!pg_paths)
-        return ctc_launch_grad_seq_wide<false, 0>(log_probs, input_lengths, target_lengths, T, B, V, Lmax, blank, ws, utt_scale, K, pg_coef,
-                                                  nullptr, hyp_len, Lh, hws, nullptr, nullptr, nullptr, grad_logits, stream);
-    if (kl_scale)
-        return ctc_launch_grad_seq_wide<true, 2>(log_probs, input_lengths, target_lengths, T, B, V, Lmax, blank, ws, utt_scale, K, pg_coef,
-                                                 pg_paths, hyp_len, Lh, hws, ent_scale, ref_log_probs, kl_scale, grad_logits, stream);
-    if (ent_scale)
-        return ctc_launch_grad_seq_wide<true, 1>(log_probs, input_lengths, target_lengths, T, B, V, Lmax, blank, ws, utt_scale, K, pg_coef,
-                                                 pg_paths, hyp_len, Lh, hws, ent_scale, nullptr, nullptr, grad_logits, stream);
-    return ctc_launch_grad_seq_wide<true, 0>(log_probs, input_lengths, target_lengths, T, B, V, Lmax, blank, ws, utt_scale, K, pg_coef,
-                                             pg_paths, hyp_len, Lh, hws, nullptr, nullptr, nullptr, grad_logits, stream);
+    return ctc_grad_run({{log_probs, input_lengths, target_lengths, T, B, V, Lmax, blank, utt_scale}, {K, pg_coef, pg_paths, 0},
+                         {hyp_len, Lh, hyp_workspace, hyp_workspace_bytes}, {ent_scale, ref_log_probs, kl_scale},
+                         grad_logits, workspace, workspace_bytes, stream}, pg_paths ? GRAD_SEQ : GRAD_NBEST, PGASR_WIDE_VMAX);
 }

@@ -158,7 +158,7 @@ def _ctc_call(log_probs, targets, input_lengths, target_lengths, blank, utt_scal
     ws = _workspace(nbytes, log_probs.device, "ctc")
     nll = torch.empty(B, dtype=torch.float32, device=log_probs.device)
     grad = torch.empty_like(log_probs) if need_grad else None
-    entry = "pgasr_ctc_loss_grad_wide" if _wide(V, wide, "ctc_loss_grad") else "pgasr_ctc_loss_grad"
+    entry = "pgasr_ctc_loss_grad" + ("_wide" if _wide(V, wide, "ctc_loss_grad") else "")
     st = getattr(lib, entry)(_p(log_probs), _p(targets), _p(input_lengths), _p(target_lengths),
                              T, B, V, Lmax, blank, _p(utt_scale), _p(pg_coef), _p(pg_path),
                              _p(nll), _p(grad), _p(ws), ws.numel(), _stream())
@@ -189,68 +189,67 @@ def _coef_per_frame(pg_coef, T, B):
     return 1
 
 
-def _grad_pass(entry, log_probs, input_lengths, target_lengths, handle, utt_scale, pg_coef, paths, paths_name, mid, ws_tail=(),
-               label=None, ent_scale=None, ref_log_probs=None, kl_scale=None):
-    """The three ``ctc_grad_from_lattice*`` wrappers: entry(log-probs, lengths, shapes, blank, utt_scale, *mid, grad, workspace,
-    *ws_tail, stream) into a fresh (T,B,V) gradient.  mid: what the entry point takes between utt_scale and grad_logits, tensors
-    as tensors; label: the launch's ``_timed`` name.
-    ent_scale (B) fp32 (``frame_entropy``): the entry's ``_ent`` form, which takes it as the last of ``mid`` and adds the entropy
-    term ent_scale_b p (ln p + H) in the same pass.  None: the entry itself -- the same call as before the term existed.
-    ref_log_probs (T,B,V), kl_scale (B) fp32 (``frame_kl``), both or neither: the entry's ``_kl`` form, which takes them after
-    ent_scale (NULL when that is None) and adds kl_scale_b p (ln p - lnq - KL) after the entropy term.  Neither: the calls above."""
-    lib = _lib.load()
-    ws, Lmax, blank = handle
-    T, B, V = log_probs.shape
-    _req(utt_scale, torch.float32, "utt_scale"); _req(pg_coef, torch.float32, "pg_coef"); _req(paths, torch.int32, paths_name)
+def _tail(log_probs, ent_scale, ref_log_probs, kl_scale):
+    """The optional terms of a gradient pass, checked: 0 = none, 1 = the entropy term, 2 = the KL term (with or without entropy).
+    ent_scale (B) fp32 (``frame_entropy``): adds ent_scale_b p (ln p + H) in the same pass.
+    ref_log_probs (T,B,V), kl_scale (B) fp32 (``frame_kl``), both or neither: adds kl_scale_b p (ln p - lnq - KL) after it."""
+    B = log_probs.shape[1]
     if ent_scale is not None:
         _req(ent_scale, torch.float32, "ent_scale")
         if tuple(ent_scale.shape) != (B,):
             raise _lib.PgasrError(f"ent_scale must be ({B},); got {tuple(ent_scale.shape)}")
-        entry, mid = entry + "_ent", tuple(mid) + (ent_scale,)
-    if ref_log_probs is not None or kl_scale is not None:
-        if ref_log_probs is None or kl_scale is None:
-            raise _lib.PgasrError("the KL term takes ref_log_probs and kl_scale together")
-        _req(ref_log_probs, torch.float32, "ref_log_probs"); _req(kl_scale, torch.float32, "kl_scale")
-        if ref_log_probs.shape != log_probs.shape or tuple(kl_scale.shape) != (B,):
-            raise _lib.PgasrError(f"ref_log_probs must be {tuple(log_probs.shape)} and kl_scale ({B},); got "
-                                  f"{tuple(ref_log_probs.shape)} and {tuple(kl_scale.shape)}")
-        # the _kl form takes (ent_scale or NULL, ref_log_probs, kl_scale) where the _ent form takes ent_scale
-        entry = (entry[:-4] if ent_scale is not None else entry) + "_kl"
-        mid = (tuple(mid) if ent_scale is not None else tuple(mid) + (None,)) + (ref_log_probs, kl_scale)
+    if ref_log_probs is None and kl_scale is None:
+        return 0 if ent_scale is None else 1
+    if ref_log_probs is None or kl_scale is None:
+        raise _lib.PgasrError("the KL term takes ref_log_probs and kl_scale together")
+    _req(ref_log_probs, torch.float32, "ref_log_probs"); _req(kl_scale, torch.float32, "kl_scale")
+    if ref_log_probs.shape != log_probs.shape or tuple(kl_scale.shape) != (B,):
+        raise _lib.PgasrError(f"ref_log_probs must be {tuple(log_probs.shape)} and kl_scale ({B},); got "
+                              f"{tuple(ref_log_probs.shape)} and {tuple(kl_scale.shape)}")
+    return 2
+
+
+# how many of (ent_scale, ref_log_probs, kl_scale) a narrow family's entry takes, by ``_tail``'s number: X, X_ent, X_kl (ent_scale
+# NULL there when it is None).  A wide entry takes all three as nullable pointers.
+_TAIL_ENTRY = (("", 0), ("_ent", 1), ("_kl", 3))
+
+
+def _grad_pass(entry, log_probs, input_lengths, target_lengths, handle, utt_scale, mid, hyp_handle=None, label=None,
+               nullable_tails=False, ent_scale=None, ref_log_probs=None, kl_scale=None):
+    """Every ``ctc_grad_from_lattice*`` wrapper: entry(log-probs, lengths, shapes, blank, utt_scale, *mid, *tails, grad, workspace,
+    [hypothesis workspace,] stream) into a fresh (T,B,V) gradient.  mid: what the entry point takes between utt_scale and the tails,
+    by name, tensors as tensors (``*coef`` fp32, the others int32); label: the launch's ``_timed`` name; nullable_tails: the entry
+    takes ent_scale, ref_log_probs and kl_scale as three nullable pointers, else it is the first of a narrow family whose ``_ent`` /
+    ``_kl`` form the terms select (``_TAIL_ENTRY``).  hyp_handle: ``ctc_hyp_lattice``'s, for the entries with two workspaces."""
+    lib = _lib.load()
+    ws, Lmax, blank = handle
+    T, B, V = log_probs.shape
+    _req(log_probs, torch.float32, "log_probs"); _req(utt_scale, torch.float32, "utt_scale")
+    for name, a in mid.items():
+        if not isinstance(a, int):
+            _req(a, torch.float32 if name.endswith("coef") else torch.int32, name)
+    ws_tail = ()
+    if hyp_handle is not None:
+        hws, K, Lh = hyp_handle
+        _req(input_lengths, torch.int32, "input_lengths"); _req(target_lengths, torch.int32, "target_lengths")
+        if input_lengths.numel() != B or target_lengths.numel() != B or (utt_scale is not None and utt_scale.numel() != B):
+            raise _lib.PgasrError(f"input_lengths, target_lengths and utt_scale must hold {B} utterances")
+        # the handles say nothing of T and B: the lattices must at least fit the workspaces they name
+        need = lib.pgasr_ctc_workspace_bytes(T, B, V, Lmax)
+        need_h = getattr(lib, "pgasr_ctc_hyp_workspace_bytes" + ("_wide" if entry.endswith("_wide") else ""))(T, B, V, K, Lh)
+        if need_h == 0 or ws.numel() < need or hws.numel() < need_h:
+            raise _lib.PgasrError(f"the lattice handles were not made for log_probs {tuple(log_probs.shape)} with K = {K}, Lh = {Lh}: "
+                                  f"workspaces of {ws.numel()} and {hws.numel()} bytes, {need} and {need_h} needed")
+        ws_tail = (_p(hws), hws.numel())
+    tail = _tail(log_probs, ent_scale, ref_log_probs, kl_scale)
+    suffix, ntail = ("", 3) if nullable_tails else _TAIL_ENTRY[tail]
     grad = torch.empty_like(log_probs)
     with _timed(label):
-        st = getattr(lib, entry)(_p(log_probs), _p(input_lengths), _p(target_lengths), T, B, V, Lmax, blank, _p(utt_scale),
-                                 *(a if isinstance(a, int) else _p(a) for a in mid), _p(grad), _p(ws), ws.numel(), *ws_tail, _stream())
-    _lib.check(st, entry)
-    return grad
-
-
-def _grad_pass_multi_wide(log_probs, input_lengths, target_lengths, handle, utt_scale, pg_coef, pg_paths, ent_scale, ref_log_probs,
-                          kl_scale, entry="pgasr_ctc_grad_from_lattice_multi_wide"):
-    """``pgasr_ctc_grad_from_lattice_multi_wide`` with ``_grad_pass``'s checks of the optional terms; entry: that one, or
-    ``pgasr_ctc_grad_from_lattice_multi_steps``, which takes the same arguments with pg_coef (K,T,B)."""
-    lib = _lib.load()
-    ws, Lmax, blank = handle
-    T, B, V = log_probs.shape
-    K = pg_paths.shape[0]
-    _req(log_probs, torch.float32, "log_probs")
-    _req(utt_scale, torch.float32, "utt_scale"); _req(pg_coef, torch.float32, "pg_coef"); _req(pg_paths, torch.int32, "pg_paths")
-    if ent_scale is not None:
-        _req(ent_scale, torch.float32, "ent_scale")
-        if tuple(ent_scale.shape) != (B,):
-            raise _lib.PgasrError(f"ent_scale must be ({B},); got {tuple(ent_scale.shape)}")
-    if ref_log_probs is not None or kl_scale is not None:
-        if ref_log_probs is None or kl_scale is None:
-            raise _lib.PgasrError("the KL term takes ref_log_probs and kl_scale together")
-        _req(ref_log_probs, torch.float32, "ref_log_probs"); _req(kl_scale, torch.float32, "kl_scale")
-        if ref_log_probs.shape != log_probs.shape or tuple(kl_scale.shape) != (B,):
-            raise _lib.PgasrError(f"ref_log_probs must be {tuple(log_probs.shape)} and kl_scale ({B},); got "
-                                  f"{tuple(ref_log_probs.shape)} and {tuple(kl_scale.shape)}")
-    grad = torch.empty_like(log_probs)
-    st = getattr(lib, entry)(_p(log_probs), _p(input_lengths), _p(target_lengths), T, B, V, Lmax, blank,
-                             _p(utt_scale), K, _p(pg_coef), _p(pg_paths), _p(ent_scale), _p(ref_log_probs),
-                             _p(kl_scale), _p(grad), _p(ws), ws.numel(), _stream())
-    _lib.check(st, entry)
+        st = getattr(lib, entry + suffix)(_p(log_probs), _p(input_lengths), _p(target_lengths), T, B, V, Lmax, blank, _p(utt_scale),
+                                          *(a if isinstance(a, int) else _p(a) for a in mid.values()),
+                                          *(_p(a) for a in (ent_scale, ref_log_probs, kl_scale)[:ntail]),
+                                          _p(grad), _p(ws), ws.numel(), *ws_tail, _stream())
+    _lib.check(st, entry + suffix)
     return grad
 
 
@@ -274,14 +273,12 @@ def ctc_grad_from_lattice(log_probs, input_lengths, target_lengths, handle, utt_
     ref_log_probs (T,B,V), kl_scale (B): add the KL term of ``frame_kl`` after it, likewise.
     V > 64 (or wide=True): ``pgasr_ctc_grad_from_lattice_wide``, which has no entropy or KL form."""
     T, B, V = log_probs.shape
-    if _wide(V, wide, "ctc_grad_from_lattice"):
-        if ent_scale is not None or ref_log_probs is not None or kl_scale is not None:
-            raise _lib.PgasrError(f"ctc_grad_from_lattice: the entropy and KL terms take at most {MAX_VOCAB_NARROW} symbols (V = {V}); "
-                                  f"ctc_grad_from_lattice_multi has them for wide rows")
-        return _grad_pass("pgasr_ctc_grad_from_lattice_wide", log_probs, input_lengths, target_lengths, handle, utt_scale, pg_coef,
-                          pg_path, "pg_path", (pg_coef, pg_path, _coef_per_frame(pg_coef, T, B)))
-    return _grad_pass("pgasr_ctc_grad_from_lattice", log_probs, input_lengths, target_lengths, handle, utt_scale, pg_coef, pg_path,
-                      "pg_path", (pg_coef, pg_path, _coef_per_frame(pg_coef, T, B)), ent_scale=ent_scale,
+    tail = "_wide" if _wide(V, wide, "ctc_grad_from_lattice") else ""
+    if tail and (ent_scale is not None or ref_log_probs is not None or kl_scale is not None):
+        raise _lib.PgasrError(f"ctc_grad_from_lattice: the entropy and KL terms take at most {MAX_VOCAB_NARROW} symbols (V = {V}); "
+                              f"ctc_grad_from_lattice_multi has them for wide rows")
+    return _grad_pass("pgasr_ctc_grad_from_lattice" + tail, log_probs, input_lengths, target_lengths, handle, utt_scale,
+                      dict(pg_coef=pg_coef, pg_path=pg_path, per_frame=_coef_per_frame(pg_coef, T, B)), ent_scale=ent_scale,
                       ref_log_probs=ref_log_probs, kl_scale=kl_scale)
 
 
@@ -363,19 +360,14 @@ def ctc_grad_from_lattice_multi(log_probs, input_lengths, target_lengths, handle
     entry for every V <= 1024 with nullable tails (the form is chosen by the shape, as ``_coef_per_frame`` does for one path)."""
     T, B, V = log_probs.shape
     K = pg_paths.shape[0]
-    if pg_paths.dim() == 3 and tuple(pg_paths.shape[1:]) == (T, B) and tuple(pg_coef.shape) == (K, T, B):
-        # one coefficient per sample and frame (pg_step_coefs_multi): ONE entry for every V, which picks the kernel family by V
-        _wide(V, wide, "ctc_grad_from_lattice_multi")
-        return _grad_pass_multi_wide(log_probs, input_lengths, target_lengths, handle, utt_scale, pg_coef, pg_paths, ent_scale,
-                                     ref_log_probs, kl_scale, entry="pgasr_ctc_grad_from_lattice_multi_steps")
-    if pg_paths.dim() != 3 or tuple(pg_paths.shape[1:]) != (T, B) or tuple(pg_coef.shape) != (K, B):
+    # one coefficient per sample and frame (pg_step_coefs_multi): ONE entry for every V, which picks the kernel family by V
+    steps = pg_paths.dim() == 3 and tuple(pg_paths.shape[1:]) == (T, B) and tuple(pg_coef.shape) == (K, T, B)
+    if not steps and (pg_paths.dim() != 3 or tuple(pg_paths.shape[1:]) != (T, B) or tuple(pg_coef.shape) != (K, B)):
         raise _lib.PgasrError(f"ctc_grad_from_lattice_multi wants pg_paths (K,{T},{B}) and pg_coef (K,{B}) or (K,{T},{B})")
-    if _wide(V, wide, "ctc_grad_from_lattice_multi"):
-        return _grad_pass_multi_wide(log_probs, input_lengths, target_lengths, handle, utt_scale, pg_coef, pg_paths, ent_scale,
-                                     ref_log_probs, kl_scale)
-    return _grad_pass("pgasr_ctc_grad_from_lattice_multi", log_probs, input_lengths, target_lengths, handle, utt_scale, pg_coef,
-                      pg_paths, "pg_paths", (K, pg_coef, pg_paths), ent_scale=ent_scale, ref_log_probs=ref_log_probs,
-                      kl_scale=kl_scale)
+    tail = "_wide" if _wide(V, wide, "ctc_grad_from_lattice_multi") else ""
+    return _grad_pass("pgasr_ctc_grad_from_lattice_multi" + ("_steps" if steps else tail), log_probs, input_lengths, target_lengths,
+                      handle, utt_scale, dict(K=K, pg_coef=pg_coef, pg_paths=pg_paths), nullable_tails=steps or bool(tail),
+                      ent_scale=ent_scale, ref_log_probs=ref_log_probs, kl_scale=kl_scale)
 
 
 def pg_rewards_multi(dist, target_lengths, num_samples, lam, inv_global_batch, baseline="hypothesis", reward_lengths=None):
@@ -434,9 +426,8 @@ def hyp_len_cap(T, max_hyp_len=None):
 def ctc_hyp_workspace_bytes(T, B, V, K, Lh, wide=None):
     """Bytes of the K*B hypothesis lattices: 2 * K*B*T * roundup64(2*Lh+1) * 4 plus the per-pair tables.
     V > 64 (or wide=True): ``pgasr_ctc_hyp_workspace_bytes_wide``, the same layout for V <= 1024."""
-    if _wide(V, wide, "ctc_hyp_workspace_bytes"):
-        return int(_lib.load().pgasr_ctc_hyp_workspace_bytes_wide(T, B, V, K, Lh))
-    return int(_lib.load().pgasr_ctc_hyp_workspace_bytes(T, B, V, K, Lh))
+    tail = "_wide" if _wide(V, wide, "ctc_hyp_workspace_bytes") else ""
+    return int(getattr(_lib.load(), "pgasr_ctc_hyp_workspace_bytes" + tail)(T, B, V, K, Lh))
 
 
 def ctc_hyp_lattice(log_probs, hyp_tokens, hyp_len, input_lengths, Lh, blank=0, wide=None):
@@ -488,45 +479,6 @@ def ctc_hyp_score(log_probs, hyp_tokens, hyp_len, input_lengths, Lh, count=None,
     return nll
 
 
-def _grad_pass_seq_wide(log_probs, input_lengths, target_lengths, handle, hyp_handle, utt_scale, pg_coef, pg_paths, hyp_len,
-                        ent_scale=None, ref_log_probs=None, kl_scale=None):
-    """``pgasr_ctc_grad_from_lattices_seq_wide`` with ``_grad_pass``'s checks of the optional terms; pg_paths None: the N-best form."""
-    lib = _lib.load()
-    ws, Lmax, blank = handle
-    hws, K, Lh = hyp_handle
-    T, B, V = log_probs.shape
-    _req(log_probs, torch.float32, "log_probs")
-    _req(input_lengths, torch.int32, "input_lengths"); _req(target_lengths, torch.int32, "target_lengths")
-    _req(utt_scale, torch.float32, "utt_scale"); _req(pg_coef, torch.float32, "pg_coef"); _req(pg_paths, torch.int32, "pg_paths")
-    _req(hyp_len, torch.int32, "hyp_len")
-    if input_lengths.numel() != B or target_lengths.numel() != B or (utt_scale is not None and utt_scale.numel() != B):
-        raise _lib.PgasrError(f"input_lengths, target_lengths and utt_scale must hold {B} utterances")
-    # the handles say nothing of T and B: the lattices must at least fit the workspaces they name
-    need, need_h = lib.pgasr_ctc_workspace_bytes(T, B, V, Lmax), lib.pgasr_ctc_hyp_workspace_bytes_wide(T, B, V, K, Lh)
-    if need_h == 0 or ws.numel() < need or hws.numel() < need_h:
-        raise _lib.PgasrError(f"the lattice handles were not made for log_probs {tuple(log_probs.shape)} with K = {K}, Lh = {Lh}: "
-                              f"workspaces of {ws.numel()} and {hws.numel()} bytes, {need} and {need_h} needed")
-    if ent_scale is not None:
-        _req(ent_scale, torch.float32, "ent_scale")
-        if tuple(ent_scale.shape) != (B,):
-            raise _lib.PgasrError(f"ent_scale must be ({B},); got {tuple(ent_scale.shape)}")
-    if ref_log_probs is not None or kl_scale is not None:
-        if ref_log_probs is None or kl_scale is None:
-            raise _lib.PgasrError("the KL term takes ref_log_probs and kl_scale together")
-        _req(ref_log_probs, torch.float32, "ref_log_probs"); _req(kl_scale, torch.float32, "kl_scale")
-        if ref_log_probs.shape != log_probs.shape or tuple(kl_scale.shape) != (B,):
-            raise _lib.PgasrError(f"ref_log_probs must be {tuple(log_probs.shape)} and kl_scale ({B},); got "
-                                  f"{tuple(ref_log_probs.shape)} and {tuple(kl_scale.shape)}")
-    grad = torch.empty_like(log_probs)
-    with _timed("ctc_grad_seq_wide_kernel"):
-        st = lib.pgasr_ctc_grad_from_lattices_seq_wide(_p(log_probs), _p(input_lengths), _p(target_lengths), T, B, V, Lmax, blank,
-                                                       _p(utt_scale), K, _p(pg_coef), _p(pg_paths), _p(hyp_len), Lh, _p(ent_scale),
-                                                       _p(ref_log_probs), _p(kl_scale), _p(grad), _p(ws), ws.numel(), _p(hws),
-                                                       hws.numel(), _stream())
-    _lib.check(st, "pgasr_ctc_grad_from_lattices_seq_wide")
-    return grad
-
-
 def ctc_grad_from_lattices_seq(log_probs, input_lengths, target_lengths, handle, hyp_handle, utt_scale, pg_coef, pg_paths, hyp_len,
                                ent_scale=None, ref_log_probs=None, kl_scale=None, wide=None):
     """One gradient pass over the target lattice (``ctc_lattice``'s handle) and the K*B hypothesis lattices (``ctc_hyp_lattice``'s):
@@ -539,12 +491,11 @@ def ctc_grad_from_lattices_seq(log_probs, input_lengths, target_lengths, handle,
     _req(hyp_len, torch.int32, "hyp_len")
     if tuple(pg_paths.shape) != (K, T, B) or tuple(pg_coef.shape) != (K, B) or tuple(hyp_len.shape) != (K, B):
         raise _lib.PgasrError(f"ctc_grad_from_lattices_seq wants pg_paths ({K},{T},{B}), pg_coef and hyp_len ({K},{B})")
-    if _wide(V, wide, "ctc_grad_from_lattices_seq"):
-        return _grad_pass_seq_wide(log_probs, input_lengths, target_lengths, handle, hyp_handle, utt_scale, pg_coef, pg_paths, hyp_len,
-                                   ent_scale, ref_log_probs, kl_scale)
-    return _grad_pass("pgasr_ctc_grad_from_lattices_seq", log_probs, input_lengths, target_lengths, handle, utt_scale, pg_coef,
-                      pg_paths, "pg_paths", (K, pg_coef, pg_paths, hyp_len, Lh), ws_tail=(_p(hws), hws.numel()),
-                      label="ctc_grad_seq_kernel", ent_scale=ent_scale, ref_log_probs=ref_log_probs, kl_scale=kl_scale)
+    tail = "_wide" if _wide(V, wide, "ctc_grad_from_lattices_seq") else ""
+    return _grad_pass("pgasr_ctc_grad_from_lattices_seq" + tail, log_probs, input_lengths, target_lengths, handle, utt_scale,
+                      dict(K=K, pg_coef=pg_coef, pg_paths=pg_paths, hyp_len=hyp_len, Lh=Lh), hyp_handle=hyp_handle,
+                      label=f"ctc_grad_seq{tail}_kernel", nullable_tails=bool(tail), ent_scale=ent_scale, ref_log_probs=ref_log_probs,
+                      kl_scale=kl_scale)
 
 
 def pg_loss_value_seq(log_probs, paths, input_lengths, nll, utt_scale, pg_coef, hyp_nll, hyp_len, Lh):
@@ -1996,9 +1947,11 @@ def ctc_grad_from_lattices_nbest(log_probs, input_lengths, target_lengths, handl
     if tuple(coef.shape) != (N, B) or tuple(hyp_len.shape) != (N, B):
         raise _lib.PgasrError(f"ctc_grad_from_lattices_nbest wants coef and hyp_len ({N},{B})")
     if _wide(V, wide, "ctc_grad_from_lattices_nbest"):
-        return _grad_pass_seq_wide(log_probs, input_lengths, target_lengths, handle, hyp_handle, utt_scale, coef, None, hyp_len)
-    return _grad_pass("pgasr_ctc_grad_from_lattices_nbest", log_probs, input_lengths, target_lengths, handle, utt_scale, coef,
-                      None, "paths", (N, coef, hyp_len, Lh), ws_tail=(_p(hws), hws.numel()), label="ctc_grad_nbest_kernel")
+        return _grad_pass("pgasr_ctc_grad_from_lattices_seq_wide", log_probs, input_lengths, target_lengths, handle, utt_scale,
+                          dict(K=N, pg_coef=coef, pg_paths=None, hyp_len=hyp_len, Lh=Lh), hyp_handle=hyp_handle,
+                          label="ctc_grad_seq_wide_kernel", nullable_tails=True)
+    return _grad_pass("pgasr_ctc_grad_from_lattices_nbest", log_probs, input_lengths, target_lengths, handle, utt_scale,
+                      dict(N=N, coef=coef, hyp_len=hyp_len, Lh=Lh), hyp_handle=hyp_handle, label="ctc_grad_nbest_kernel")
 
 
 def nbest_rescore(tokens, lengths, count, am, vocab, blank=0, lm=None, am_weight=1.0, lm_alpha=0.0, lm_beta=0.0):
