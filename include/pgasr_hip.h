@@ -1185,6 +1185,55 @@ int pgasr_nbest_combine_rank(const double* base, const double* word_logp, const 
                              void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * A7-WORDFUSE  The word n-gram model of A7-WORDLM and its lexicon inside the first pass: the A7 / A7-NBEST search with a per-extension
+ * bonus from a lexicon trie and, at every word end, from the word model (csrc/beam.hip WORDS = true; the builder and the host statement
+ * of every term: lm.WordFusion).  A second pass (pgasr_nbest_word_lm_score) can only re-rank rows that survived a search that knew
+ * nothing about words; here the hypothesis the word model prefers stays in the beam.
+ * The meaning.  d = `delimiter`, a token other than the blank.  The lexicon is the model's vocabulary (word ids 3 and up, 1 .. 32 tokens
+ *   each, no d, no blank) as a trie: state 0 the root, the nodes in breadth-first order with children in symbol order, and ONE sink for
+ *   everything outside the lexicon, the LAST state (trie_states - 1).  For a prefix y: u(y) = the tokens behind its last d (the pending
+ *   word, maybe empty), hist(y) = the ids of its completed words, cut as str.split() cuts them (no empty words), a word outside the
+ *   lexicon being <unk>.  Every term that enters a prefix by an extension with a non-blank s gets w = bonus(y, s) added exactly where
+ *   A7-LM adds its term, (p_b + p) + w and (p_nb + p) + w; the blank update and the repeat branch are unchanged.
+ *     s != d:  w = (double)trie[q V + s].bonus and the state becomes trie[q V + s].next: 0.0 into a child node; oov_penalty (fp32, <= 0,
+ *              may be -inf: the hard lexicon constraint) from a trie node into the sink; 0.0 inside the sink.
+ *     s == d:  u empty (q = 0): w = 0.0, nothing changes.  Otherwise word = node_word[q] (the word's id at a terminal node, <unk> = 2
+ *              elsewhere) and  w = __dadd_rn(__dmul_rn(alpha, score(hist, word)), beta), score the fp64 back-off query of A7-WORDLM;
+ *              for a node that is neither terminal nor the sink, w = __dadd_rn(w, (double)trie[q V + d].bonus) -- that word holds
+ *              oov_penalty there and 0 elsewhere; the sink was charged on the way in.  The state becomes 0, the word joins hist.
+ *   Finalisation (flags2 bit 0).  After the last frame every entry of the final beam gets fin(y): 0.0, or the d-bonus of its pending
+ *   word where u is not empty; with flags2 bit 1 (eos) fin = __dadd_rn(fin, __dmul_rn(alpha, score(hist', </s>))), hist' with the pending
+ *   word in it.  The final beam is ranked again by lse(p_b, p_nb) + fin, descending, equal totals in the search's order, and the rows and
+ *   out_score = -(lse + fin) come from that ranking.  Without bit 0 the list is the search's own and no fin is added.  The bonuses
+ *   along a row y plus fin(y) with eos equal alpha * word_logp + beta * n_words + oov_penalty * n_oov of pgasr_nbest_word_lm_score.
+ *   alpha = beta = oov_penalty = 0 without eos: every output word of pgasr_ctc_beam_search_nbest's workgroup kernel, bit for bit.
+ * pgasr_ctc_beam_search_words: the arguments of pgasr_ctc_beam_search_nbest, all of them (a dense character table beside the word model
+ *   is out of scope: lm_table must be NULL and lm_order 0, anything else -> PGASR_ERR_UNSUPPORTED), then
+ *   trie: trie_states * V words {int32 next; float32 bonus}, word (q, s) at q * V + s, the layout of A7-BIAS; the columns of the blank
+ *     and of d hold next = q / 0 and are read for the bonus of d only.  A next outside [0, trie_states) is taken as state 0.
+ *   node_word (trie_states) int32; an id outside [0, n_words) is taken as <unk>.   tables: the model, as A7-WORDLM passes it (the
+ *     unigram arrays and ngram_slots are read; the spellings are in the trie).   delimiter, alpha, beta, flags2.
+ *   An entry carries its trie state, the entry indices of its last 1 .. order-1 words as contexts, own = the w of its own last emission
+ *   (the merged term of its stay candidate) and dlm = the bonus d would get; the thread that writes an extension winner makes the one
+ *   back-off query (at most order-1 independent probes), so the model costs O(beam) probes per frame.
+ *   fp32 and fp64 log_probs, the workgroup-per-utterance kernel, N-best form (the 1-best is row 0 at nbest = 1).  Accepted (beam, V):
+ *   beam <= 128, V <= 64 and a power-of-two sort of beam * V candidates within 160 KB of LDS with 72 bytes of word state per entry --
+ *   beam * V <= 4096 (128 x 32, 64 x 64) is accepted, beyond that PGASR_ERR_UNSUPPORTED before any HIP call, as without a model.
+ *   Checked before any HIP call, behind the checks of pgasr_ctc_beam_search_nbest (V > 64 or beam > 128 -> PGASR_ERR_UNSUPPORTED):
+ *   trie, node_word, tables or one of the tables' unigram / n-gram pointers NULL, trie_states < 1, trie_states * V > 2^24, an alpha or
+ *   beta that is not finite, n_words < 3, an ngram_cap that is no power of two, delimiter outside [0, V) or equal to blank, unknown
+ *   flags2 bits -> PGASR_ERR_INVALID_ARG; order outside 1 .. 5, n_words > 2^22, ngram_cap > 2^25, a character table, flags bits 3 and 4 (the
+ *   single-wave kernel has no word model) -> PGASR_ERR_UNSUPPORTED; then the workspace (pgasr_beam_workspace_bytes).  No host synchronisation.
+ * ---------------------------------------------------------------------------------------- */
+int pgasr_ctc_beam_search_words(const void* log_probs, int is_f64, long long stride_t, long long stride_b,
+                                const int32_t* lengths, int T, int B, int V, int beam, int blank, int flags,
+                                int nbest, int32_t* out_tokens, int tok_stride, int32_t* out_len, double* out_score,
+                                int32_t* out_count, void* workspace, size_t workspace_bytes, void* stream,
+                                const float* lm_table, int lm_order, double lm_alpha, double lm_beta,
+                                const void* trie, int trie_states, const int32_t* node_word, const pgasr_word_lm_tables* tables,
+                                int delimiter, double alpha, double beta, int flags2);
+
+/* ------------------------------------------------------------------------------------------
  * A13-MWER  Minimum word error rate training over the N-best list of the beam search (Prabhavalkar et al., arXiv:1712.01818): the
  * model's probability renormalised over the N hypotheses the decoder returns, and the expected risk under that distribution.
  * Nothing is sampled.  With a list as pgasr_ctc_beam_search_nbest writes it WITHOUT collapse (raw prefixes are distinct label

@@ -54,6 +54,7 @@ MBRDecoded = collections.namedtuple("MBRDecoded", "tokens lengths best risk post
 
 class CTCDecoder:
     def __init__(self, alphabet, device=None, lm=None, lm_alpha=0.0, lm_beta=0.0, fast_lm=False, wide_search=False, unit_lm=None,
+                 fused_word_lm=None, fused_word_alpha=0.0, fused_word_beta=0.0, word_delimiter=None, oov_penalty=0.0,
                  wide_hotwords=False, hotwords=None, hotword_weight=1.0):
         """lm: None (default: the acoustic search of the reference) or a ``lm.CharNgramLM``; every extension of a prefix by a
         non-blank symbol s then gets ``lm_alpha * ln p_lm(s | last order-1 symbols) + lm_beta`` added (Hannun/Maas,
@@ -81,7 +82,37 @@ class CTCDecoder:
         symbols, or any rows once ``unit_lm`` is given; ``decode``, ``decode_batch`` and their ``nbest=`` forms -- pass the hotwords
         there (``hipops.ctc_beam_search_wide(bias=)``, csrc/beam_wide.hip): the first pass itself is biased, with or without
         ``unit_lm``, so a rare phrase stays in the beam instead of having to be in the list already when a second pass looks for it.
-        Rows of at most 64 symbols without ``unit_lm`` keep taking the narrow biased kernel."""
+        Rows of at most 64 symbols without ``unit_lm`` keep taking the narrow biased kernel.
+        fused_word_lm: None (default: every call is the call it was) or a ``lm.WordNgramLM`` -- made a ``lm.WordFusion`` over this
+        alphabet with blank 0, ``word_delimiter`` (default the alphabet's " ") and ``oov_penalty`` (<= 0; -inf: only lexicon words) --
+        or a ready ``lm.WordFusion`` (``word_delimiter`` and ``oov_penalty`` are then its own).  ``decode`` / ``decode_batch`` and their
+        ``nbest=`` forms then take ``hipops.ctc_beam_search_words`` (csrc/beam.hip WORDS = true): the word model and its lexicon act
+        inside the first pass -- every word end adds ``fused_word_alpha * ln p(word | history) + fused_word_beta``, the final beam is
+        ranked with the pending word and </s> scored -- and the scores are FUSED scores.  Not together with ``lm``, ``hotwords``,
+        ``fast_lm``, ``wide_search`` / ``unit_lm`` or more than 64 symbols (ValueError naming the option).  ``rescore(word_lm=)`` stays
+        the second pass it is."""
+        self.fused_word_lm = None
+        self.fused_word_alpha, self.fused_word_beta = float(fused_word_alpha), float(fused_word_beta)
+        if fused_word_lm is not None:
+            from .lm import WordFusion, WordNgramLM
+            for name, given in (("lm", lm is not None), ("hotwords", hotwords is not None), ("fast_lm", bool(fast_lm)),
+                                ("wide_search", bool(wide_search)), ("unit_lm", unit_lm is not None)):
+                if given:
+                    raise ValueError(f"{name}: not together with fused_word_lm -- the word LM is fused into the workgroup kernel's "
+                                     f"search, alone")
+            if len(alphabet) > hipops.MAX_VOCAB_NARROW:
+                raise ValueError(f"fused_word_lm: the fused search takes at most {hipops.MAX_VOCAB_NARROW} symbols (got "
+                                 f"{len(alphabet)})")
+            if isinstance(fused_word_lm, WordNgramLM):
+                self.alphabet = alphabet
+                fused_word_lm = WordFusion(fused_word_lm, len(alphabet), self._word_delimiter(word_delimiter), blank=0,
+                                           oov_penalty=oov_penalty)
+            elif not isinstance(fused_word_lm, WordFusion):
+                raise ValueError("fused_word_lm: a lm.WordFusion or a lm.WordNgramLM is wanted")
+            for name, x in (("fused_word_alpha", self.fused_word_alpha), ("fused_word_beta", self.fused_word_beta)):
+                if x != x or x in (float("inf"), -float("inf")):
+                    raise ValueError(f"{name} must be finite")
+            self.fused_word_lm = fused_word_lm
         if wide_hotwords and not wide_search:
             raise ValueError("wide_hotwords: the bias is fused into the wide search; give wide_search=True")
         self.wide_hotwords = bool(wide_hotwords)
@@ -103,6 +134,8 @@ class CTCDecoder:
         """The decoder's hotword list from now on: None, a ``lm.HotwordBias`` or a list of strings (see the constructor)."""
         from .lm import HotwordBias
         if hotwords is not None:
+            if self.fused_word_lm is not None:
+                raise ValueError("hotwords: not together with fused_word_lm -- the word LM is fused into the search alone")
             if self.fast_lm:
                 raise ValueError("fast_lm: the single-wave kernel has no hotword bias; give fast_lm=False with hotwords")
             if self.unit_lm is not None and not self.wide_hotwords:
@@ -159,6 +192,26 @@ class CTCDecoder:
             return bias
         return {"unit_lm": self.unit_lm, "lm_alpha": args["lm_alpha"], "lm_beta": args["lm_beta"], **bias}
 
+    def _fused_check(self, V, blank, args, fast_lm=False):
+        """The refusals of a call with ``fused_word_lm``, by option name; no device is touched."""
+        f = self.fused_word_lm
+        if args["lm"] is not None:
+            raise ValueError("lm: not together with fused_word_lm -- the word LM is fused into the search alone; call with lm=None")
+        if fast_lm:
+            raise ValueError("fast_lm: the single-wave kernel has no word LM fusion; give fast_lm=False with fused_word_lm")
+        if V > hipops.MAX_VOCAB_NARROW:
+            raise ValueError(f"fused_word_lm: the fused search takes at most {hipops.MAX_VOCAB_NARROW} symbols (got {V})")
+        if f.vocab != V or f.blank != int(blank):
+            raise ValueError(f"fused_word_lm: the lexicon is over {f.vocab} symbols with blank {f.blank}; the call has {V} symbols and "
+                             f"blank {int(blank)}")
+
+    def _fused_search(self, log_probs, lengths, beam_size, blank, args, nbest, fast_lm=False):
+        """The call with ``fused_word_lm``: ``hipops.ctc_beam_search_words`` behind ``_fused_check``."""
+        self._fused_check(log_probs.shape[-1], blank, args, fast_lm)
+        return hipops.ctc_beam_search_words(log_probs, lengths, beam=int(beam_size), nbest=1 if nbest is None else int(nbest),
+                                            blank=int(blank), fusion=self.fused_word_lm, alpha=self.fused_word_alpha,
+                                            beta=self.fused_word_beta)
+
     def _lm_args(self, lm, lm_alpha, lm_beta):
         return {"lm": self.lm if lm is _UNSET else lm,
                 "lm_alpha": self.lm_alpha if lm_alpha is None else float(lm_alpha),
@@ -176,6 +229,21 @@ class CTCDecoder:
         min(N, size of the final beam) entries of the final beam in the search's rank order (best first; equal scores in first-touch
         order, like the reference's sorted(...)[:N])."""
         args = self._lm_args(lm, lm_alpha, lm_beta)
+        if self.fused_word_lm is not None:
+            T, V = np.shape(probs)
+            self._fused_check(V, blank, args)
+            if int(beam_size) > BEAM_KMAX:
+                raise ValueError(f"beam_size {beam_size} exceeds the device search's limit of {BEAM_KMAX}")
+            if T == 0:                                       # the empty prefix, finalised on the host: no device needed
+                row = (tuple(), -(0.0 + self.fused_word_lm.final((), self.fused_word_alpha, self.fused_word_beta, True)))
+                return row if nbest is None else [row]
+            with np.errstate(divide="ignore"):
+                logp = np.log(np.asarray(probs).astype(np.float64)).reshape(T, 1, V)
+            lp = torch.from_numpy(np.ascontiguousarray(logp)).to(_device(self.device))
+            nb = self._fused_search(lp, None, beam_size, blank, args, nbest)
+            tok, tl, sc = nb.tokens[:, 0].cpu(), nb.lengths[:, 0].tolist(), nb.score[:, 0].tolist()
+            rows = [(tuple(int(x) for x in tok[r, :tl[r]].tolist()), float(sc[r])) for r in range(int(nb.count[0].item()))]
+            return rows[0] if nbest is None else rows
         if self.wide_search:                                 # refused before a device is asked for
             self._takes_wide(np.shape(probs)[-1], args, blank)
         if self.hotwords is not None:                        # likewise
@@ -217,6 +285,9 @@ class CTCDecoder:
         fast_lm: None (default: the decoder's own) or a bool -- with an LM, take the single-wave kernel where its limits allow."""
         fast_lm = self.fast_lm if fast_lm is None else bool(fast_lm)
         args = self._lm_args(lm, lm_alpha, lm_beta)
+        if self.fused_word_lm is not None:
+            nb = self._fused_search(log_probs, lengths, beam_size, blank, args, nbest, fast_lm)
+            return (nb.tokens[0], nb.lengths[0], nb.score[0]) if nbest is None else nb
         if self.hotwords is not None:
             bias_args = self._bias_args(log_probs.shape[-1], blank, self._takes_wide(log_probs.shape[-1], args, blank), fast_lm)
             args.update(bias_args)

@@ -19,7 +19,7 @@ c_f32p = C.c_void_p   # device pointers travel as integers (tensor.data_ptr())
 c_i32p = C.c_void_p
 c_ptr = C.c_void_p
 
-# The eight beam-search entries share their argument list piece by piece (include/pgasr_hip.h, A7-*)
+# The nine beam-search entries share their argument list piece by piece (include/pgasr_hip.h, A7-*)
 _S_HEAD = [c_ptr, C.c_int, C.c_longlong, C.c_longlong, c_i32p] + [C.c_int] * 6   # log_probs, is_f64, strides, lengths, T, B, V, beam, blank, flags
 _S_BEST = [c_i32p, c_i32p, c_ptr]                                    # out_tokens, out_len, out_score
 _S_LIST = [C.c_int, c_i32p, C.c_int, c_i32p, c_ptr, c_i32p]          # nbest, out_tokens, tok_stride, out_len, out_score, out_count
@@ -27,6 +27,7 @@ _S_WS = [c_ptr, C.c_size_t, c_ptr]                                   # workspace
 _S_LM = [c_f32p, C.c_int, C.c_double, C.c_double]                    # lm_table, lm_order, lm_alpha, lm_beta
 _S_UNIT_LM = [c_ptr, C.c_double, C.c_double]                         # tables, lm_alpha, lm_beta
 _S_BIAS = [c_ptr, C.c_int, C.c_double]                               # bias_table, bias_states, bias_weight
+_S_WORDS = [c_ptr, C.c_int, c_i32p, c_ptr, C.c_int, C.c_double, C.c_double, C.c_int]   # trie, trie_states, node_word, tables, delimiter, alpha, beta, flags2
 _S_WIDE = _S_HEAD + _S_LIST + [c_i32p] + _S_WS                       # ... out_counting_frames
 
 # The CTC loss section's gradient, loss and hypothesis-lattice entries likewise (include/pgasr_hip.h, A5 / A12 / A13 and their -WIDE forms):
@@ -109,6 +110,7 @@ SIGNATURES = {
     "pgasr_ctc_beam_search_nbest": (C.c_int, _S_HEAD + _S_LIST + _S_WS + _S_LM),
     "pgasr_ctc_beam_search_bias": (C.c_int, _S_HEAD + _S_BEST + _S_WS + _S_LM + _S_BIAS),
     "pgasr_ctc_beam_search_nbest_bias": (C.c_int, _S_HEAD + _S_LIST + _S_WS + _S_LM + _S_BIAS),
+    "pgasr_ctc_beam_search_words": (C.c_int, _S_HEAD + _S_LIST + _S_WS + _S_LM + _S_WORDS),
     "pgasr_nbest_bias_score": (C.c_int, [c_i32p, c_i32p, c_i32p, C.c_int, C.c_int, C.c_int, C.c_int, c_ptr, C.c_int, c_ptr, c_ptr]),
     "pgasr_beam_wide_workspace_bytes": (C.c_size_t, [C.c_int] * 4),
     "pgasr_ctc_beam_search_wide": (C.c_int, _S_WIDE),

@@ -18,6 +18,7 @@
 #include "common.h"
 #include "beam_core.h"
 #include "bias_table.h"
+#include "word_ngram.h"
 #include <cmath>
 #include <type_traits>
 
@@ -86,11 +87,83 @@ template <bool LM, bool NBEST> struct BeamBiased : BeamTail<LM, NBEST> {
     double bweight;
 };
 
-template <typename TIn, bool FAST, bool LM, bool NBEST = false, bool BIAS = false>
+// Word fusion (WORDS = true, pgasr_ctc_beam_search_words; include/pgasr_hip.h, A7-WORDFUSE states every term; the host model:
+// lm.WordFusion): the lexicon of a word n-gram model as a trie in the bias table's layout, and the model itself at every word end.
+//   * an entry carries wst = the trie state of its pending word, wcx = the entry indices of its last 1 .. order-1 completed words as
+//     contexts (a unigram's is its word id, an n-gram's n_words + slot, -1 where the model does not store it; word_lm.hip's step 4),
+//     own = the w of its own last emission -- inherited on a stay; the merged term of its stay candidate, known without pidx -- and
+//     dlm = the bonus the delimiter would get, alpha score(hist, word of wst) + beta (+ oov_penalty at a non-terminal node);
+//   * candidate (j, s) reads dlm[j] for the delimiter and one trie word otherwise (consecutive candidates of one entry read consecutive
+//     words; the first BEAM_LM_PRE per thread are gathered at the top of the frame and parked like the bias' bonuses);
+//   * the thread that writes an extension winner does the model's work: one trie word and, for a symbol, the back-off query of the
+//     new node's word under the inherited contexts -- at most order-1 probes that do not depend on each other (word_lm.hip's step 5) --
+//     or, for the delimiter, the same probes to advance the contexts.  O(beam) probes per frame, never O(beam V);
+//   * finalisation: every final entry gets fin = its dlm (and alpha score(hist', </s>) with eos); a bitonic sort of the at most 128
+//     entries on (lse + fin, search rank) puts the beam in its final order in front of nbest_tail.
+// N-best form only, no dense table and no bias beside it; the arguments ride in the last parameter.
+using word_ngram::NgramSlot;
+constexpr int BEAM_WCTX = word_ngram::WL_MAX_ORDER - 1;      // contexts per entry
+constexpr size_t BEAM_WORDS_ENTRY_BYTES = 2 * (2 * sizeof(double) + (1 + BEAM_WCTX) * sizeof(int));      // own, dlm, wst, wcx, double-buffered: 72
+struct BeamWords : BeamNbest<false> {
+    const BiasWord* trie;    // S * V words
+    const int32_t* node_word;      // S
+    const NgramSlot* slots; const float* uni_logp; const float* uni_bow;
+    int tstates, order, n_words, ngram_cap, delim, finalize, eos;
+    double alpha, beta;
+};
+
+// the slots of (wcx[m], word), m < order-1, as independent probes: hit[m] the slot's content, at[m] its index or -1
+__device__ __forceinline__ void words_probe(const BeamWords& a, const int (&cx)[BEAM_WCTX], int word, int (&at)[BEAM_WCTX], NgramSlot (&hit)[BEAM_WCTX]) {
+#pragma unroll
+    for (int m = 0; m < BEAM_WCTX; ++m) {
+        at[m] = -1;
+        hit[m] = NgramSlot{-1, 0, 0.0f, 0.0f};
+        if (m < a.order - 1 && cx[m] >= 0) at[m] = word_ngram::ngram_find(a.slots, a.ngram_cap, cx[m], word, hit[m]);
+    }
+}
+// score(hist, word): from 0.0 the back-off weights of the stored contexts, longest first, until one holds the word; then its logp
+__device__ __forceinline__ double words_score(const BeamWords& a, const int (&cx)[BEAM_WCTX], int word) {
+    int at[BEAM_WCTX]; NgramSlot hit[BEAM_WCTX];
+    words_probe(a, cx, word, at, hit);
+    double acc = 0.0;
+    bool found = false;
+#pragma unroll
+    for (int m = BEAM_WCTX - 1; m >= 0; --m) {
+        if (m < a.order - 1 && cx[m] >= 0 && !found) {
+            if (at[m] >= 0) { acc += (double)hit[m].logp; found = true; }
+            else acc += (double)(cx[m] < a.n_words ? a.uni_bow[cx[m]] : a.slots[cx[m] - a.n_words].bow);
+        }
+    }
+    if (!found) acc += (double)a.uni_logp[word];
+    return acc;
+}
+// hist + word: the context of m + 1 words is the n-gram (context of m words, word)
+__device__ __forceinline__ void words_advance(const BeamWords& a, int (&cx)[BEAM_WCTX], int word) {
+    int at[BEAM_WCTX]; NgramSlot hit[BEAM_WCTX];
+    words_probe(a, cx, word, at, hit);
+#pragma unroll
+    for (int m = BEAM_WCTX - 1; m >= 1; --m) cx[m] = (m < a.order - 1 && at[m - 1] >= 0) ? a.n_words + at[m - 1] : -1;
+    cx[0] = a.order > 1 ? word : -1;
+}
+__device__ __forceinline__ int words_word(const BeamWords& a, int q) {
+    const int w = a.node_word[q];
+    return ((unsigned)w < (unsigned)a.n_words) ? w : word_ngram::WL_UNK;
+}
+// the bonus of the delimiter behind trie state q != 0
+__device__ __forceinline__ double words_dbonus(const BeamWords& a, int V, const int (&cx)[BEAM_WCTX], int q) {
+    const int word = words_word(a, q);
+    double w = __dadd_rn(__dmul_rn(a.alpha, words_score(a, cx, word)), a.beta);
+    if (word == word_ngram::WL_UNK && q != a.tstates - 1) w = __dadd_rn(w, (double)a.trie[q * V + a.delim].bonus);
+    return w;
+}
+
+template <typename TIn, bool FAST, bool LM, bool NBEST = false, bool BIAS = false, bool WORDS = false>
 __global__ __launch_bounds__(BEAM_THREADS) void beam_search_kernel(
     const TIn* __restrict__ lp, long long stride_t, long long stride_b, const int32_t* __restrict__ lengths,
     int T, int V, int K, int blank, int collapse, BeamWs ws, int32_t* __restrict__ out_tokens, int32_t* __restrict__ out_len,
-    double* __restrict__ out_score, const typename std::conditional<BIAS, BeamBiased<LM, NBEST>, BeamTail<LM, NBEST>>::type lm) {
+    double* __restrict__ out_score,
+    const typename std::conditional<WORDS, BeamWords, typename std::conditional<BIAS, BeamBiased<LM, NBEST>, BeamTail<LM, NBEST>>::type>::type lm) {
+    static_assert(!WORDS || (NBEST && !LM && !BIAS), "word fusion: the N-best form, no dense table, no bias");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int b = blockIdx.x, tid = threadIdx.x;
     int Tb = lengths ? lengths[b] : T; Tb = Tb < 0 ? 0 : (Tb > T ? T : Tb);
@@ -114,7 +187,12 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_search_kernel(
     int* bst = s_ctl + 4 + (LM ? 5 * K : 0);   // BIAS only: [2][K] automaton state of the entry's prefix
     int* bwi = bst + 2 * K;                    // BIAS only: [2][K] table index of the entry's own last emission
     float* pbv = reinterpret_cast<float*>(bwi + 2 * K);    // BIAS only: [K] bonus of table[bwi] of the current beam
-    short* cb = reinterpret_cast<short*>(BIAS ? bst + 5 * K : (LM ? s_ctl + 4 + 5 * K : s_ctl + 4));       // [K][V] child-in-beam table
+    // WORDS only, from the next multiple of 8 bytes on: own, dlm [2][K] fp64; wst [2][K]; wcx [2][K][BEAM_WCTX]
+    double* wown = reinterpret_cast<double*>(smem + ((reinterpret_cast<unsigned char*>(s_ctl + 4) - smem + 7) & ~(ptrdiff_t)7));
+    double* wdlm = wown + 2 * K;
+    int* wst = reinterpret_cast<int*>(wdlm + 2 * K);
+    int* wcx = wst + 2 * K;
+    short* cb = reinterpret_cast<short*>(WORDS ? wcx + 2 * K * BEAM_WCTX : (BIAS ? bst + 5 * K : (LM ? s_ctl + 4 + 5 * K : s_ctl + 4)));       // [K][V] child-in-beam table
 #define s_nb s_ctl[0]
 #define s_nodes s_ctl[1]
 
@@ -127,6 +205,14 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_search_kernel(
         nodes[0] = 0xFFFFFFFFu;
         if constexpr (LM) { ctx[0] = lm.ctx0; lmi[0] = 0; }      // the root has no emission of its own: lmi is never used (last < 0)
         if constexpr (BIAS) { bst[0] = 0; bwi[0] = 0; }          // state 0 is the automaton's root; bwi likewise unused while last < 0
+        if constexpr (WORDS) {                                   // the empty prefix: the trie's root, a history of <s>
+            wst[0] = 0; wown[0] = 0.0; wdlm[0] = 0.0;
+            int e = word_ngram::WL_BOS;
+            for (int m = 0; m < BEAM_WCTX; ++m) {
+                if (m > 0 && e >= 0) { NgramSlot hit; const int at = word_ngram::ngram_find(lm.slots, lm.ngram_cap, e, word_ngram::WL_BOS, hit); e = at < 0 ? -1 : lm.n_words + at; }
+                wcx[m] = m < lm.order - 1 ? e : -1;
+            }
+        }
     }
     __syncthreads();
     int cur = 0;
@@ -156,6 +242,16 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_search_kernel(
             }
             if (tid < nb && last[cur * K + tid] >= 0) bvp = lm.btable[bwi[cur * K + tid]].bonus;
         }
+        [[maybe_unused]] const int* cwst = wst + cur * K;
+        [[maybe_unused]] float wv[BEAM_LM_PRE];
+        if constexpr (WORDS) {   // the trie words likewise; the delimiter's term is dlm, already in LDS
+#pragma unroll
+            for (int k = 0; k < BEAM_LM_PRE; ++k) {
+                const int c = tid + k * BEAM_THREADS;
+                wv[k] = 0.0f;
+                if (c < nb * V) { const int j = c / V, s = c % V; if (s != blank && s != lm.delim) wv[k] = lm.trie[cwst[j] * V + s].bonus; }
+            }
+        }
         if (tid < V) frame[tid] = (double)lp[(long long)t * stride_t + (long long)b * stride_b + tid];
         for (int i = tid; i < nb * V; i += BEAM_THREADS) cb[i] = -1;
         if (tid < nb) {
@@ -178,6 +274,13 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_search_kernel(
                 if (c < P) items[c].time = __float_as_uint(bv[k]);
             }
             if (tid < nb) pbv[tid] = bvp;
+        }
+        if constexpr (WORDS) {
+#pragma unroll
+            for (int k = 0; k < BEAM_LM_PRE; ++k) {
+                const int c = tid + k * BEAM_THREADS;
+                if (c < P) items[c].time = __float_as_uint(wv[k]);
+            }
         }
         __syncthreads();
         if (tid < nb && pidx[tid] >= 0) cb[pidx[tid] * V + clast[tid]] = (short)tid;
@@ -203,6 +306,10 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_search_kernel(
                         const double own = cpnb[j] + pl;                              // repeat branch (:103-106)
                         if (i >= 0) {
                             double e1 = cpb[i] + pl, e2 = cpnb[i] + pl;               // extension of parent i by lj (:90-96)
+                            if constexpr (WORDS) {
+                                const double w = wown[cur * K + j];
+                                e1 += w; e2 += w;
+                            } else
                             if constexpr (BIAS) {
                                 const double wb = __dmul_rn(lm.bweight, (double)pbv[j]);
                                 double w = wb;
@@ -233,6 +340,13 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_search_kernel(
                     alive = false;          // merged into an existing entry's stay candidate
                 } else {
                     const double ps = frame[s];
+                    if constexpr (WORDS) {
+                        double w;
+                        if (s == lm.delim) w = wdlm[cur * K + j];
+                        else w = (double)((c < BEAM_LM_PRE * BEAM_THREADS) ? __uint_as_float(items[c].time) : lm.trie[cwst[j] * V + s].bonus);
+                        const double eb = (cpb[j] + ps) + w, en = (cpnb[j] + ps) + w;
+                        npnb = (s != clast[j]) ? lse3x<FAST>(-INFINITY, eb, en) : lse2x<FAST>(-INFINITY, eb);
+                    } else
                     if constexpr (BIAS) {
                         const bool pre = c < BEAM_LM_PRE * BEAM_THREADS;
                         const float bon = pre ? __uint_as_float(items[c].time) : lm.btable[cbst[j] * V + s].bonus;
@@ -285,6 +399,28 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_search_kernel(
                     bst[nxt * K + tid] = nx;
                     bwi[nxt * K + tid] = (s == blank) ? bwi[cur * K + j] : e;
                 }
+                if constexpr (WORDS) {
+                    const int q = cwst[j];                                  // < S: below S V words
+                    int nq = q;
+                    double nown = wown[cur * K + j], ndlm = wdlm[cur * K + j];
+                    int cx[BEAM_WCTX];
+#pragma unroll
+                    for (int m = 0; m < BEAM_WCTX; ++m) cx[m] = wcx[(cur * K + j) * BEAM_WCTX + m];
+                    if (s != blank) {
+                        if (s == lm.delim) {                                // a word end (q != 0), or a delimiter behind none
+                            nown = ndlm;                                    // dlm is 0.0 at the root
+                            if (q != 0) { words_advance(lm, cx, words_word(lm, q)); nq = 0; ndlm = 0.0; }
+                        } else {
+                            const BiasWord tw = lm.trie[q * V + s];
+                            nq = ((unsigned)tw.next < (unsigned)lm.tstates) ? tw.next : 0;
+                            nown = (double)tw.bonus;
+                            ndlm = nq != 0 ? words_dbonus(lm, V, cx, nq) : 0.0;
+                        }
+                    }
+                    wst[nxt * K + tid] = nq; wown[nxt * K + tid] = nown; wdlm[nxt * K + tid] = ndlm;
+#pragma unroll
+                    for (int m = 0; m < BEAM_WCTX; ++m) wcx[(nxt * K + tid) * BEAM_WCTX + m] = cx[m];
+                }
                 if (s == blank) { nid[tid] = cid[j]; nlast[tid] = clast[j]; npar[tid] = cpar[j]; }
                 else {
                     // canonical node for (id[j], s): look up, else create
@@ -300,6 +436,46 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_search_kernel(
         }
         __syncthreads();
         cur = nxt;
+    }
+    if constexpr (WORDS) {
+        if (lm.finalize) {
+            // ---- finalisation: total = lse + fin per final entry, the beam ranked again on (total, search rank); items, c_pb, c_pnb are free ----
+            const int nb = s_nb, nxt = cur ^ 1;
+            double* tot = c_pb;            // [nb] by search rank
+            double* stot = c_pnb;          // [nb] by final rank
+            if (tid < nb) {
+                const int e = cur * K + tid, q = wst[e];
+                int cx[BEAM_WCTX];
+#pragma unroll
+                for (int m = 0; m < BEAM_WCTX; ++m) cx[m] = wcx[e * BEAM_WCTX + m];
+                double fin = 0.0;
+                if (q != 0) fin = wdlm[e];
+                if (lm.eos) {
+                    if (q != 0) words_advance(lm, cx, words_word(lm, q));
+                    fin = __dadd_rn(fin, __dmul_rn(lm.alpha, words_score(lm, cx, word_ngram::WL_EOS)));
+                }
+                tot[tid] = lse2x<FAST>(pb[e], pnb[e]) + fin;
+            }
+            __syncthreads();
+            int Pf = 1; while (Pf < nb) Pf <<= 1;          // <= the frame loop's P: inside items
+            for (int i = tid; i < Pf; i += BEAM_THREADS) {
+                SortItem it; it.key = ~0ull; it.time = 0xFFFFFFFFu; it.cand = 0xFFFFFFFFu;
+                if (i < nb) { it.key = ~ordered_key(tot[i]); it.time = (unsigned)i; it.cand = (unsigned)i; }
+                items[i] = it;
+            }
+            __syncthreads();
+            bitonic_sort<BEAM_THREADS>(items, Pf, tid);
+            if (tid < nb) {
+                const int r = cur * K + (int)items[tid].cand;
+                id[nxt * K + tid] = id[r]; pb[nxt * K + tid] = pb[r]; pnb[nxt * K + tid] = pnb[r];
+                stot[tid] = tot[items[tid].cand];
+            }
+            __syncthreads();
+            nbest_tail<BEAM_SYM_BITS, BEAM_THREADS, FAST>(nodes, ws.NN, Tb, b, tid, lm.nbest, lm.tok_stride, collapse, nb, id + nxt * K, pb + nxt * K,
+                                                          pnb + nxt * K, pidx, out_tokens, out_len, out_score, lm.out_count);
+            if (tid < lm.nbest && tid < nb) out_score[(size_t)tid * gridDim.x + b] = -stot[tid];      // the thread that wrote -lse there
+            return;
+        }
     }
     if constexpr (NBEST) {
         // ---- N-best result: row r is entry r of the final, ranked beam; pidx is free after the frame loop ----
@@ -329,7 +505,7 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_search_kernel(
 #undef s_nb
 #undef s_nodes
 
-inline size_t beam_lds_bytes(int K, int V, bool lm, bool bias = false) {
+inline size_t beam_lds_bytes(int K, int V, bool lm, bool bias = false, bool words = false) {
     int P = 1; while (P < K * V) P <<= 1;
     size_t n = (size_t)P * sizeof(SortItem);
     n += (size_t)2 * K * V * sizeof(double);          // c_pb, c_pnb
@@ -338,6 +514,7 @@ inline size_t beam_lds_bytes(int K, int V, bool lm, bool bias = false) {
     n += (size_t)(6 * K + K + 4) * sizeof(int);       // id,last,par (x2), pidx, control words
     if (lm) n += (size_t)(5 * K) * sizeof(int);       // ctx, lmi (x2), ptv
     if (bias) n += (size_t)(5 * K) * sizeof(int);     // bst, bwi (x2), pbv: at most 2560 bytes, and the largest shape without them is 150032
+    if (words) n += (size_t)K * BEAM_WORDS_ENTRY_BYTES + 8;       // own, dlm, wst, wcx (x2) behind an 8-byte boundary: 9224 bytes at beam 128, 159256 in all at 128 x 32
     n += (size_t)K * V * sizeof(short);               // cb
     return (n + 15) / 16 * 16;
 }
@@ -957,12 +1134,18 @@ struct BeamCall {
     bool list = false; int nbest = 0, tok_stride = 0; int32_t* out_count = nullptr;
     const float* lm_table = nullptr; int lm_order = 0; double lm_alpha = 0.0, lm_beta = 0.0;
     const void* bias_table = nullptr; int bias_states = 0; double bias_weight = 0.0;
+    bool words = false; const void* trie = nullptr; int trie_states = 0; const int32_t* node_word = nullptr;
+    const pgasr_word_lm_tables* word_tables = nullptr; int delimiter = 0; double word_alpha = 0.0, word_beta = 0.0; int flags2 = 0;
 
     BeamCall& with_list(int n, int stride, int32_t* count) { list = true; nbest = n; tok_stride = stride; out_count = count; return *this; }
     BeamCall& with_lm(const float* table, int order, double alpha, double beta) {
         lm_table = table; lm_order = order; lm_alpha = alpha; lm_beta = beta; return *this;
     }
     BeamCall& with_bias(const void* table, int states, double weight) { bias_table = table; bias_states = states; bias_weight = weight; return *this; }
+    BeamCall& with_words(const void* t, int states, const int32_t* nw, const pgasr_word_lm_tables* tb, int d, double alpha, double beta, int f2) {
+        words = true; trie = t; trie_states = states; node_word = nw; word_tables = tb; delimiter = d; word_alpha = alpha; word_beta = beta; flags2 = f2;
+        return *this;
+    }
 };
 
 // the language model's arguments (no HIP call): PGASR_OK with *lm filled where lm_order > 0
@@ -987,6 +1170,21 @@ int beam_bias_args(const BeamCall& c) {
     if (!c.bias_table && c.bias_states == 0) return PGASR_OK;
     if (!bias_table::usable(c.bias_table, c.bias_states, c.V) || !std::isfinite(c.bias_weight)) return PGASR_ERR_INVALID_ARG;
     if (c.flags & (8 | 16)) return PGASR_ERR_UNSUPPORTED;      // the single-wave kernel has no bias: refused, never run differently
+    return PGASR_OK;
+}
+
+// the word fusion's arguments (no HIP call; include/pgasr_hip.h, A7-WORDFUSE)
+int beam_words_args(const BeamCall& c) {
+    if (!c.words) return PGASR_OK;
+    if (!c.trie || !c.node_word || !c.word_tables) return PGASR_ERR_INVALID_ARG;
+    const pgasr_word_lm_tables& tb = *c.word_tables;          // host memory
+    if (!bias_table::usable(c.trie, c.trie_states, c.V) || !std::isfinite(c.word_alpha) || !std::isfinite(c.word_beta)) return PGASR_ERR_INVALID_ARG;
+    if (tb.order < 1 || tb.order > word_ngram::WL_MAX_ORDER || tb.n_words > (1 << 22) || tb.ngram_cap > (1 << 25)) return PGASR_ERR_UNSUPPORTED;
+    if (!tb.uni_logp || !tb.uni_bow || !tb.ngram_slots || tb.n_words < word_ngram::WL_RESERVED) return PGASR_ERR_INVALID_ARG;
+    if (tb.ngram_cap < 1 || (tb.ngram_cap & (tb.ngram_cap - 1)) != 0) return PGASR_ERR_INVALID_ARG;
+    if (c.delimiter < 0 || c.delimiter >= c.V || c.delimiter == c.blank || (c.flags2 & ~3)) return PGASR_ERR_INVALID_ARG;
+    if (c.lm_table || c.lm_order != 0 || c.bias_table) return PGASR_ERR_UNSUPPORTED;      // no dense table and no bias beside the word model
+    if (c.flags & (8 | 16)) return PGASR_ERR_UNSUPPORTED;      // the single-wave kernel has no word model: refused, never run differently
     return PGASR_OK;
 }
 
@@ -1019,6 +1217,27 @@ int launch_workgroup(const BeamCall& c, const BeamLm<true>& lm, const BeamWs& ws
     };
     if (c.is_f64) launch(&beam_search_kernel<double, false, LM, NBEST, BIAS>, (const double*)c.log_probs);
     else launch(&beam_search_kernel<float, true, LM, NBEST, BIAS>, (const float*)c.log_probs);
+    PGASR_CHECK_LAUNCH();
+    return PGASR_OK;
+}
+
+// The same kernel with the word fusion (WORDS = true): the N-best form, no dense table, no bias
+int launch_words(const BeamCall& c, const BeamWs& ws, size_t lds) {
+    const pgasr_word_lm_tables& tb = *c.word_tables;
+    BeamWords tail{};
+    tail.nbest = c.nbest; tail.tok_stride = c.tok_stride; tail.out_count = c.out_count;
+    tail.trie = (const BiasWord*)c.trie; tail.node_word = c.node_word;
+    tail.slots = (const NgramSlot*)tb.ngram_slots; tail.uni_logp = tb.uni_logp; tail.uni_bow = tb.uni_bow;
+    tail.tstates = c.trie_states; tail.order = tb.order; tail.n_words = tb.n_words; tail.ngram_cap = tb.ngram_cap; tail.delim = c.delimiter;
+    tail.finalize = c.flags2 & 1; tail.eos = (c.flags2 >> 1) & 1;
+    tail.alpha = c.word_alpha; tail.beta = c.word_beta;
+    const auto launch = [&](auto kern, auto* lp) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        PGASR_LAUNCH_KERNEL(kern, dim3(c.B), dim3(BEAM_THREADS), lds, (hipStream_t)c.stream, lp, c.stride_t, c.stride_b, c.lengths, c.T, c.V,
+                            c.beam, c.blank, c.flags & 1, ws, c.out_tokens, c.out_len, c.out_score, tail);
+    };
+    if (c.is_f64) launch(&beam_search_kernel<double, false, false, true, false, true>, (const double*)c.log_probs);
+    else launch(&beam_search_kernel<float, true, false, true, false, true>, (const float*)c.log_probs);
     PGASR_CHECK_LAUNCH();
     return PGASR_OK;
 }
@@ -1058,6 +1277,7 @@ int beam_search_run(const BeamCall& c) {
                                        [&] {
                                            if (const int s = beam_lm_args(c, &lm)) return s;
                                            if (const int s = beam_bias_args(c)) return s;
+                                           if (const int s = beam_words_args(c)) return s;
                                            const bool bad = c.list && (c.nbest < 1 || c.nbest > c.beam || c.tok_stride < c.T || !c.out_count);
                                            return bad ? (int)PGASR_ERR_INVALID_ARG : (int)PGASR_OK;
                                        },
@@ -1065,11 +1285,12 @@ int beam_search_run(const BeamCall& c) {
     const bool with_lm = c.lm_order > 0, bias = c.bias_table != nullptr;
     const bool single_wave = with_lm ? (c.flags & 16) && pgasr_beam_lm_single_wave_ok(c.T, c.V, c.beam, c.is_f64, c.lm_order)
                                      : !c.is_f64 && (c.list ? (c.flags & 8) != 0 : !(c.flags & 2)) && beam_single_wave_fits(c.T, c.V, c.beam);
-    if (!bias && single_wave)
+    if (!bias && !c.words && single_wave)
         return beam_with_bools([&](auto l, auto nb) { return launch_single_wave<decltype(l)::value, decltype(nb)::value>(c, lm); }, with_lm, c.list);
-    const size_t lds = beam_lds_bytes(c.beam, c.V, with_lm, bias);
+    const size_t lds = beam_lds_bytes(c.beam, c.V, with_lm, bias, c.words);
     if (lds > 160 * 1024) return PGASR_ERR_UNSUPPORTED;
     if (hipMemsetAsync(ws.table, 0, (size_t)c.B * ws.H * sizeof(unsigned long long), (hipStream_t)c.stream) != hipSuccess) return PGASR_ERR_LAUNCH;
+    if (c.words) return launch_words(c, ws, lds);
     return beam_with_bools([&](auto l, auto nb, auto bi) { return launch_workgroup<decltype(l)::value, decltype(nb)::value, decltype(bi)::value>(c, lm, ws, lds); },
                            with_lm, c.list, bias);
 }
@@ -1126,4 +1347,19 @@ extern "C" int pgasr_ctc_beam_search_nbest_bias(const void* log_probs, int is_f6
                                      workspace, workspace_bytes, stream}
                                .with_list(nbest, tok_stride, out_count).with_lm(lm_table, lm_order, lm_alpha, lm_beta)
                                .with_bias(bias_table, bias_states, bias_weight));
+}
+
+// The word n-gram model and its lexicon inside the search (include/pgasr_hip.h, A7-WORDFUSE): the N-best search, WORDS = true
+extern "C" int pgasr_ctc_beam_search_words(const void* log_probs, int is_f64, long long stride_t, long long stride_b,
+                                           const int32_t* lengths, int T, int B, int V, int beam, int blank, int flags,
+                                           int nbest, int32_t* out_tokens, int tok_stride, int32_t* out_len, double* out_score,
+                                           int32_t* out_count, void* workspace, size_t workspace_bytes, void* stream,
+                                           const float* lm_table, int lm_order, double lm_alpha, double lm_beta,
+                                           const void* trie, int trie_states, const int32_t* node_word, const pgasr_word_lm_tables* tables,
+                                           int delimiter, double alpha, double beta, int flags2) {
+    BeamCall c{log_probs, is_f64, stride_t, stride_b, lengths, T, B, V, beam, blank, flags, out_tokens, out_len, out_score,
+               workspace, workspace_bytes, stream};
+    c.with_list(nbest, tok_stride, out_count).with_words(trie, trie_states, node_word, tables, delimiter, alpha, beta, flags2);
+    c.lm_table = lm_table; c.lm_order = lm_order; c.lm_alpha = lm_alpha; c.lm_beta = lm_beta;      // refused by beam_words_args, never by beam_lm_args' own rules
+    return beam_search_run(c);
 }

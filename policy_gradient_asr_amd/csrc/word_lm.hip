@@ -8,7 +8,9 @@
 //      the candidate byte by byte on the packed pool -- a hash match alone never decides; the id (or <unk>) goes to LDS behind
 //      order-1 ids of <s>, with </s> after the last word;
 //   4. one thread per start position walks the chain of contexts that start there: entry(w_p), entry(w_p w_p+1), .. up to
-//      order-1 words, each a probe keyed by (entry index of the context, word id) and confirmed on that pair (lm.hash_ngram);
+//      order-1 words, each a probe keyed by (entry index of the context, word id) and confirmed on that pair (lm.hash_ngram:
+//      splitmix64's finaliser, multipliers 0xBF58476D1CE4E5B9ull and 0x94D049BB133111EBull; the probe itself, ngram_find, is in
+//      word_ngram.h, shared with the beam search's word fusion);
 //   5. one thread per scored position (every word and </s>) walks the back-off rule from the longest context to the unigram
 //      on those entry indices: its probes do not depend on each other, its fp64 sum is in the contractual order;
 //   6. thread 0 adds the per-word scores in word order.
@@ -17,43 +19,23 @@
 //
 // pgasr_nbest_combine_rank: one launch, one workgroup of 128 threads per utterance; the rank is that of csrc/nbest.hip.
 #include "common.h"
+#include "word_ngram.h"
 #include <cmath>
 
 namespace {
 
+using namespace word_ngram;      // NgramSlot, ngram_find and the reserved ids: shared with the beam search's word fusion
+
 constexpr int WL_THREADS = 256;
 constexpr int WL_NMAX = 128;
-constexpr int WL_MAX_ORDER = 5;
 constexpr int WL_MAX_WORD_LEN = 32;
 constexpr int WL_MAX_STRIDE = PGASR_WORD_LM_MAX_STRIDE;   // 4096: 61 KB of LDS
-constexpr int WL_BOS = 0, WL_EOS = 1, WL_UNK = 2, WL_RESERVED = 3;
 constexpr unsigned short WL_DELIM = 0xFFFFu, WL_BAD = 0xFFFEu;      // LDS marks: a delimiter; a token outside [0, 255]
-
-struct NgramSlot { int32_t ctx, word; float logp, bow; };             // 16 bytes, one load per probe
 
 __device__ __forceinline__ uint32_t word_hash_step(uint32_t h, uint32_t c) { return (h ^ c) * 16777619u; }
 __device__ __forceinline__ uint32_t word_hash_final(uint32_t h) {
     h ^= h >> 16; h *= 0x85EBCA6Bu; h ^= h >> 13; h *= 0xC2B2AE35u; h ^= h >> 16;
     return h;
-}
-__device__ __forceinline__ uint64_t ngram_hash(uint32_t ctx, uint32_t word) {
-    uint64_t x = ((uint64_t)ctx << 32) | (uint64_t)word;
-    x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull; x ^= x >> 27; x *= 0x94D049BB133111EBull; x ^= x >> 31;
-    return x;
-}
-
-// The slot of the n-gram (ctx, word), or -1.  At most half the slots are taken, so an empty one ends every probe; the bound on the
-// steps only keeps a damaged table from holding the thread.
-__device__ __forceinline__ int ngram_find(const NgramSlot* __restrict__ slots, int cap, int ctx, int word, NgramSlot& out) {
-    const uint32_t mask = (uint32_t)cap - 1u;
-    uint32_t s = (uint32_t)ngram_hash((uint32_t)ctx, (uint32_t)word) & mask;
-    for (int step = 0; step < cap; ++step) {
-        const NgramSlot e = slots[s];
-        if (e.ctx < 0) return -1;
-        if (e.ctx == ctx && e.word == word) { out = e; return (int)s; }
-        s = (s + 1u) & mask;
-    }
-    return -1;
 }
 
 // The carve of the dynamic LDS, for the kernel and for the launch alike (every offset a multiple of 16 bytes).

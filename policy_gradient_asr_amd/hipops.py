@@ -1831,6 +1831,44 @@ def ctc_beam_search_nbest(log_probs, lengths=None, beam=5, nbest=1, blank=0, col
     return CTCNBest(tokens, tl, score, count)
 
 
+def ctc_beam_search_words(log_probs, lengths=None, beam=5, nbest=1, blank=0, collapse=False, fusion=None, alpha=0.0, beta=0.0,
+                          finalize=True, eos=True):
+    """The N-best search with a word n-gram model and its lexicon fused into it (pgasr_ctc_beam_search_words; include/pgasr_hip.h,
+    A7-WORDFUSE): log_probs (T,B,V) fp32 or fp64 as ``ctc_beam_search_nbest`` takes them, 1 <= nbest <= beam, ``fusion`` a
+    ``lm.WordFusion`` over the same V <= 64 symbols and blank.  Every extension by a non-blank s gets ``fusion.bonus(prefix, s, alpha,
+    beta)`` added: the lexicon's ``oov_penalty`` on the way out of the lexicon, and ``alpha * ln p(word | history) + beta`` at every
+    word end.  Returns ``CTCNBest`` of device tensors, no host synchronisation; the scores are FUSED scores.
+    finalize (default): every entry of the final beam also gets ``fusion.final(prefix, alpha, beta, eos)`` -- the bonus of its pending
+    word and, with ``eos``, ``alpha * ln p(</s> | history)`` --, and the list is the final beam ranked again with it (equal totals in
+    the search's order).  finalize=False: the search's own list, nothing added (``eos`` is then not consulted).
+    Always the workgroup-per-utterance kernel; the 1-best is row 0 at nbest = 1.  alpha = beta = 0 with a fusion of oov_penalty 0 and
+    eos=False returns every word of ``ctc_beam_search_nbest`` bit for bit."""
+    from .lm import WordFusion
+    if not isinstance(fusion, WordFusion):
+        raise ValueError("fusion: a lm.WordFusion is wanted (never raw tensors)")
+    V = log_probs.shape[-1]
+    if fusion.vocab != V or fusion.blank != int(blank):
+        raise ValueError(f"fusion: the lexicon is over {fusion.vocab} symbols with blank {fusion.blank}; the call has {V} symbols and "
+                         f"blank {int(blank)}")
+    alpha, beta = float(alpha), float(beta)
+    for name, x in (("alpha", alpha), ("beta", beta)):
+        if x != x or x in (float("inf"), -float("inf")):
+            raise ValueError(f"{name}: a finite weight is wanted (got {x!r})")
+    lib = _lib.load()
+    T, B, V = _search_inputs(log_probs, lengths)
+    N, dev = int(nbest), log_probs.device
+    tabs = fusion.device_tables(dev)
+    ws = _workspace(lib.pgasr_beam_workspace_bytes(T, B, V, int(beam)), dev, "beam")
+    tokens, tl, score, count = _nbest_outputs(N, B, T, dev)
+    with _timed("beam_search_words"):
+        st = lib.pgasr_ctc_beam_search_words(*_search_head(log_probs, lengths, T, B, V, beam, blank), int(bool(collapse)), N, _p(tokens), T,
+                                             _p(tl), _p(score), _p(count), _p(ws), ws.numel(), _stream(), None, 0, 0.0, 0.0,
+                                             _p(tabs.trie), fusion.n_states, _p(tabs.node_word), ctypes.byref(tabs.word_lm.struct),
+                                             fusion.delimiter, alpha, beta, (1 if finalize else 0) | (2 if eos else 0))
+    _lib.check(st, "pgasr_ctc_beam_search_words")
+    return CTCNBest(tokens, tl, score, count)
+
+
 MAX_VOCAB_SEARCH_WIDE = 1024     # csrc/beam_wide.hip: the exact prefix beam search over rows of up to 1024 symbols
 
 

@@ -9,6 +9,9 @@ search reads the table on the device (``device_table``).
 ``WordNgramLM`` is the word-level model of the second pass: a back-off n-gram model (ARPA form, order <= 5) over words spelled in
 the acoustic alphabet, queried on the host by ``logp_sentence`` and on the device by csrc/word_lm.hip through ``device_tables``.
 
+``WordFusion`` puts that word model and its vocabulary, as a lexicon trie, into the first pass itself (csrc/beam.hip WORDS = true,
+``pgasr_ctc_beam_search_words``): it builds the trie the search reads and states every term the search adds (``bonus``, ``final``).
+
 ``UnitNgramLM`` is the sparse model over the acoustic units themselves, for alphabets the dense table cannot hold (up to 1024
 symbols at order <= 5): a back-off n-gram model fused into the wide search (csrc/beam_wide.hip) and applied to N-best lists
 (csrc/unit_lm.hip) through ``device_tables``, queried on the host by ``logp`` / ``logp_sequence``.
@@ -1178,4 +1181,199 @@ class HotwordBias:
             words[:, 0] = self.next.reshape(-1)
             words[:, 1] = self.bonus.reshape(-1).view(np.int32)
             return torch.from_numpy(words).to(dev).contiguous()
+        return _on_device(self._device_tables, device, make)
+
+
+# ------------------------------------------------------------------------------------------
+# The word model and its lexicon inside the first pass (csrc/beam.hip WORDS = true; include/pgasr_hip.h, section A7-WORDFUSE)
+# ------------------------------------------------------------------------------------------
+MAX_FUSION_VOCAB = 64      # the workgroup-per-utterance search: one symbol per lane
+WordFusionDeviceTables = collections.namedtuple("WordFusionDeviceTables", "trie node_word word_lm")
+
+
+class WordFusion:
+    """A ``WordNgramLM`` and its vocabulary as a lexicon, in the form the fused CTC prefix beam search reads
+    (``hipops.ctc_beam_search_words``), and the host's own statement of every term that search adds.
+
+    ``delimiter`` d is the token that ends a word, ``blank`` the CTC blank.  The lexicon is the vocabulary of ``word_lm`` (ids 3 and
+    up) as a trie over the spellings: state 0 is the root, the nodes follow in breadth-first order with children in symbol order, and
+    the LAST state is the one sink for everything outside the lexicon.  For a prefix y, u(y) is the pending word (the tokens behind the
+    last d) and hist(y) the ids of the completed words, cut as ``WordNgramLM.split`` cuts them, a word outside the lexicon being <unk>.
+    ``bonus(y, s)`` is what an extension of y by the non-blank s adds:
+        s != d: 0.0 into a child node; ``oov_penalty`` from a trie node into the sink; 0.0 inside the sink
+        s == d: 0.0 behind an empty u; else alpha * score(hist, word) + beta with word = the id at a terminal node and <unk>
+                elsewhere, plus ``oov_penalty`` (one more addition) at a node that is neither terminal nor the sink -- the sink was
+                charged on the way in.
+    ``final(y)`` is the d-bonus of a pending word (0.0 without one) and, with ``eos``, alpha * score(hist', </s>) added to it.  The
+    bonuses along y plus final(y, eos=True) are alpha * word_logp + beta * n_words + oov_penalty * n_oov of
+    ``word_lm.logp_sentence(y)``.  ``oov_penalty`` is an fp32 value <= 0; -inf is the hard lexicon constraint.
+
+    Arrays: ``next`` (S, V) int32 and ``trie_bonus`` (S, V) float32 -- the blank's column is next = q, the delimiter's next = 0 with
+    ``oov_penalty`` in the bonus where a delimiter behind state q is charged it -- and ``node_word`` (S,) int32: the word id at a
+    terminal node, <unk> elsewhere, -1 at the root."""
+
+    def __init__(self, word_lm, vocab, delimiter, blank=0, oov_penalty=0.0):
+        if not isinstance(word_lm, WordNgramLM):
+            raise ValueError("word_lm: a lm.WordNgramLM is wanted")
+        V, d, blank = int(vocab), int(delimiter), int(blank)
+        if not 2 <= V <= MAX_FUSION_VOCAB:
+            raise ValueError(f"vocab: the fused search takes 2 .. {MAX_FUSION_VOCAB} symbols (got {V})")
+        if not 0 <= blank < V:
+            raise ValueError(f"blank: {blank} is no symbol of the {V}")
+        if not 0 <= d < V:
+            raise ValueError(f"delimiter: {d} is no symbol of the {V}")
+        if d == blank:
+            raise ValueError("delimiter: the word delimiter cannot be the blank")
+        pen = float(oov_penalty)
+        if pen != pen or pen > 0.0:
+            raise ValueError(f"oov_penalty: a value <= 0 is wanted, -inf for the hard lexicon constraint (got {oov_penalty!r})")
+        pool = word_lm.word_pool
+        if pool.size and int(pool.max()) >= V:
+            raise ValueError(f"vocab: a word's spelling holds token {int(pool.max())}, outside the {V} symbols")
+        if (pool == d).any():
+            raise ValueError(f"delimiter: token {d} stands inside a word's spelling")
+        if (pool == blank).any():
+            raise ValueError(f"blank: token {blank} stands inside a word's spelling")
+        self.word_lm, self.vocab, self.delimiter, self.blank = word_lm, V, d, blank
+        self.oov_penalty = float(np.float32(pen))
+        self._build()
+        self._states = {(): (0, ())}
+        self._device_tables = {}
+
+    def _build(self):
+        V, d, blank, lm = self.vocab, self.delimiter, self.blank, self.word_lm
+        kids, word = [{}], [-1]                               # the trie in insertion order ...
+        for wid in range(N_RESERVED, lm.n_words):
+            q = 0
+            for t in lm.spellings[wid]:
+                nx = kids[q].get(t)
+                if nx is None:
+                    nx = len(kids)
+                    kids[q][t] = nx
+                    kids.append({})
+                    word.append(UNK)
+                q = nx
+            word[q] = wid
+        S = len(kids) + 1
+        if S * V > MAX_BIAS_WORDS:
+            raise ValueError(f"word_lm: the lexicon trie has {S} states over {V} symbols: {S * V} table words, the limit is 2**24")
+        order, new_of, head = [0], {0: 0}, 0                  # ... renumbered breadth first, children in symbol order
+        while head < len(order):
+            old = order[head]
+            for t in sorted(kids[old]):
+                new_of[kids[old][t]] = len(order)
+                order.append(kids[old][t])
+            head += 1
+        sink = S - 1
+        nxt = np.full((S, V), sink, dtype=np.int32)
+        bonus = np.zeros((S, V), dtype=np.float32)
+        bonus[:sink] = np.float32(self.oov_penalty)           # out of the lexicon, unless a child says otherwise
+        node_word = np.full(S, UNK, dtype=np.int32)
+        for q, old in enumerate(order):
+            node_word[q] = word[old]
+            for t, c in kids[old].items():
+                nxt[q, t] = new_of[c]
+                bonus[q, t] = 0.0
+        nxt[:, blank] = np.arange(S, dtype=np.int32)
+        bonus[:, blank] = 0.0
+        nxt[:, d] = 0
+        bonus[:, d] = np.where(node_word == UNK, np.float32(self.oov_penalty), np.float32(0.0))      # a non-terminal node closed by d
+        bonus[0, d] = bonus[sink, d] = 0.0
+        self.next, self.trie_bonus, self.node_word = np.ascontiguousarray(nxt), np.ascontiguousarray(bonus), node_word
+        self.n_states, self.sink = S, sink
+
+    # ---------------------------------------------------------------- persistence
+    def save(self, path):
+        """The word model's arrays and the fusion's own arguments (.npz); ``load`` builds the same trie again."""
+        lm = self.word_lm
+        lm._save(path, word_pool=lm.word_pool, word_off=lm.word_off, order=np.int64(lm.order), blank=np.int64(lm.blank),
+                 delimiter=np.int64(lm.delimiter), fusion_vocab=np.int64(self.vocab), fusion_delimiter=np.int64(self.delimiter),
+                 fusion_blank=np.int64(self.blank), oov_penalty=np.float32(self.oov_penalty))
+
+    @classmethod
+    def load(cls, path):
+        with np.load(path, allow_pickle=False) as z:
+            lm = WordNgramLM(z["word_pool"], z["word_off"], *WordNgramLM._saved_arrays(z), blank=int(z["blank"]),
+                             delimiter=int(z["delimiter"]))
+            return cls(lm, int(z["fusion_vocab"]), int(z["fusion_delimiter"]), blank=int(z["fusion_blank"]),
+                       oov_penalty=float(z["oov_penalty"]))
+
+    # ---------------------------------------------------------------- queries (the host's own statement)
+    def transition(self, q, s):
+        """(next state, the trie's bonus as a Python float) of token ``s`` in state ``q``: for the delimiter the root and the
+        ``oov_penalty`` a delimiter behind ``q`` is charged (the word model's term is ``bonus``'s); a token outside [0, vocab) or
+        equal to the blank leaves the state unchanged and adds nothing."""
+        q, s = int(q), int(s)
+        if s < 0 or s >= self.vocab or s == self.blank:
+            return q, 0.0
+        return int(self.next[q, s]), float(self.trie_bonus[q, s])
+
+    def _state(self, prefix):
+        """(trie state, the last order-1 completed word ids) of a prefix, remembered per prefix."""
+        prefix = tuple(int(t) for t in prefix)
+        st = self._states.get(prefix)
+        if st is not None:
+            return st
+        if len(self._states) > (1 << 20):
+            self._states = {(): (0, ())}
+        k = len(prefix)
+        while prefix[:k] not in self._states:
+            k -= 1
+        st = self._states[prefix[:k]]
+        keep = self.word_lm.order - 1
+        for i in range(k, len(prefix)):
+            q, hist = st
+            s = prefix[i]
+            if s == self.delimiter:
+                if q != 0:
+                    hist = (hist + (int(self.node_word[q]),))[-keep:] if keep else ()
+                st = (0, hist)
+            else:
+                st = (self.transition(q, s)[0], hist)
+            self._states[prefix[:i + 1]] = st
+        return st
+
+    def _dbonus(self, q, hist, alpha, beta):
+        word = int(self.node_word[q])
+        w = alpha * self.word_lm.score(hist, word) + beta
+        if word == UNK and q != self.sink:
+            w = w + float(self.trie_bonus[q, self.delimiter])
+        return w
+
+    def bonus(self, prefix, s, alpha, beta):
+        """What the extension of ``prefix`` by the non-blank token ``s`` adds, in Python floats with the device's rounding order."""
+        q, hist = self._state(prefix)
+        s = int(s)
+        if s != self.delimiter:
+            return self.transition(q, s)[1]
+        if q == 0:
+            return 0.0
+        return self._dbonus(q, hist, float(alpha), float(beta))
+
+    def final(self, prefix, alpha, beta, eos=True):
+        """fin(prefix): the delimiter's bonus of a pending word, and with ``eos`` alpha * score(hist', </s>) added to it."""
+        q, hist = self._state(prefix)
+        alpha, beta = float(alpha), float(beta)
+        fin = 0.0
+        if q != 0:
+            fin = self._dbonus(q, hist, alpha, beta)
+        if eos:
+            if q != 0:
+                hist = hist + (int(self.node_word[q]),)
+            fin = fin + alpha * self.word_lm.score(hist, EOS)
+        return fin
+
+    # ---------------------------------------------------------------- the device's tables
+    def device_tables(self, device):
+        """(trie, node_word, word_lm) on ``device``, made once per device: the trie as an (S * V, 2) int32 tensor -- word (q, s) =
+        {next, the bonus' bits}, the layout of ``HotwordBias.device_table`` --, node_word (S,) int32, and the word model's own
+        ``device_tables``."""
+        import torch
+
+        def make(dev):
+            words = np.empty((self.n_states * self.vocab, 2), dtype="<i4")
+            words[:, 0] = self.next.reshape(-1)
+            words[:, 1] = self.trie_bonus.reshape(-1).view(np.int32)
+            return WordFusionDeviceTables(torch.from_numpy(words).to(dev).contiguous(),
+                                          torch.from_numpy(self.node_word).to(dev).contiguous(), self.word_lm.device_tables(dev))
         return _on_device(self._device_tables, device, make)

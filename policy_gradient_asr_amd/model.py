@@ -618,7 +618,8 @@ def predict(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=N
             mbr=False, mbr_unit="char", mbr_scale=1.0, rescore_word_lm_path=None, rescore_word_alpha=0.0, rescore_word_beta=0.0,
             error_report=False, units_path=None, wide_beam=False, wide_second_pass=False, unit_lm_path=None, unit_lm_alpha=0.0,
             unit_lm_beta=0.0, rescore_unit_lm_path=None, rescore_unit_alpha=0.0, rescore_unit_beta=0.0, spelled=False,
-            frame_stack=None, wide_hotwords=False, hotwords_path=None, hotword_weight=1.0, hotword_boost=1.0):
+            frame_stack=None, fused_word_lm_path=None, fused_word_alpha=0.0, fused_word_beta=0.0, oov_penalty=0.0,
+            wide_hotwords=False, hotwords_path=None, hotword_weight=1.0, hotword_boost=1.0):
     """model.py:277-339: load model_best.pth, forward, beam=5 prefix search (device side, batched),
     collapse_fn, CER/WER, predicted.txt.  Frames are cut by the FEATURE mask (the reference cuts the
     time axis by the target mask, model.py:322 -- a listed defect).  Returns (CER, WER).
@@ -703,7 +704,14 @@ def predict(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=N
     frame_stack: None (default) or (stack, skip[, left]) / a features.FrameStack, as in ``train``.  None takes the policy the model
     was trained with from <model_path>/checkpoint_last.pth, where there is one -- a model trained without a policy, or a directory
     without that file, decodes as ever --; a policy that differs from the checkpoint's raises.  The model then has n_feats * stack
-    inputs and every decoder sees ceil(n / skip) frames."""
+    inputs and every decoder sees ceil(n / skip) frames.
+    fused_word_lm_path: None (default: everything above, nothing else) or a word LM's .npz (``lm.WordNgramLM.save``, or a
+    ``lm.WordFusion.save`` with its own delimiter and oov_penalty): the model and its vocabulary as a lexicon are fused into the
+    first pass itself (``CTCDecoder(fused_word_lm=)``, csrc/beam.hip WORDS = true) -- every word end adds fused_word_alpha * ln p(word |
+    history) + fused_word_beta, the way out of the lexicon ``oov_penalty`` (<= 0; -inf: only lexicon words), and the final beam is
+    ranked with the pending word and </s> scored; the first-pass scores are then fused scores.  beam_size >= 1, an alphabet of at most
+    64 symbols with the ' ' symbol; not together with lm_path, hotwords_path, lm_fast, wide_beam or unit_lm_path (ValueError naming
+    the option).  ``rescore_word_lm_path`` stays the second pass it is."""
     import os
     import functools
     import torch.utils.data as tud
@@ -747,10 +755,25 @@ def predict(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=N
             raise ValueError("lm_fast: the single-wave kernel has no hotword bias; give lm_fast=False with hotwords_path")
         if unit_lm_path is not None and not wide_hotwords:
             raise ValueError("unit_lm_path: the wide search it is fused into has no hotword bias; not together with hotwords_path")
+    if fused_word_lm_path is not None:
+        if greedy:
+            raise ValueError("fused_word_lm_path: greedy decoding (beam_size=0) has no word LM fusion; give beam_size >= 1")
+        for name, given in (("lm_path", lm_path is not None), ("hotwords_path", hotwords_path is not None), ("lm_fast", bool(lm_fast)),
+                            ("unit_lm_path", unit_lm_path is not None), ("wide_beam", bool(wide_beam)),
+                            ("units_path", units_path is not None)):
+            if given:
+                raise ValueError(f"{name}: not together with fused_word_lm_path -- the word LM is fused into the workgroup kernel's "
+                                 f"search over characters, alone")
     char_alphabet_path = alphabet_path
     if units_path is not None:
         alphabet_path = units_path
     alphabet, char2ind = _read_alphabet(alphabet_path)
+    if fused_word_lm_path is not None:
+        if len(alphabet) > hipops.MAX_VOCAB_NARROW:
+            raise ValueError(f"fused_word_lm_path: the fused search takes at most {hipops.MAX_VOCAB_NARROW} symbols and "
+                             f"{alphabet_path} has {len(alphabet)}")
+        if " " not in char2ind:
+            raise ValueError("fused_word_lm_path needs an alphabet with the ' ' symbol")
     ind2char = {char2ind[k]: k for k in char2ind}
     unit_args = {}
     if units_path is not None:
@@ -843,6 +866,14 @@ def predict(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=N
             else:
                 rescore_unit_lm = m
     hotword_args = {} if hotwords is None else {"hotwords": hotwords, "hotword_weight": hotword_weight}
+    if fused_word_lm_path is not None:
+        import numpy as np
+        from .lm import WordFusion
+        with np.load(fused_word_lm_path, allow_pickle=False) as z:
+            is_fusion = "fusion_vocab" in z.files
+        fused = WordFusion.load(fused_word_lm_path) if is_fusion else WordNgramLM.load(fused_word_lm_path)
+        hotword_args = dict(fused_word_lm=fused, fused_word_alpha=fused_word_alpha, fused_word_beta=fused_word_beta,
+                            **({} if is_fusion else {"word_delimiter": char2ind[" "], "oov_penalty": oov_penalty}))
     if unit_lm is not None:
         decoder = CTCDecoder(alphabet, lm_alpha=unit_lm_alpha, lm_beta=unit_lm_beta, wide_search=True, unit_lm=unit_lm,
                              wide_hotwords=bool(wide_hotwords), **hotword_args)
