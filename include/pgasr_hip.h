@@ -54,7 +54,8 @@ typedef enum pgasr_status {
  * (pgasr_nbest_pair_dist, pgasr_mbr_select), and waveform augmentation (pgasr_reverb_limits, pgasr_reverb, pgasr_wave_power,
  * pgasr_wave_mix), and edit-operation alignment (pgasr_edit_ops_workspace_bytes, pgasr_edit_ops), and the wide-alphabet entries
  * (pgasr_log_softmax_rows_wide, pgasr_frame_argmax_sample_wide, pgasr_ctc_loss_grad_wide, pgasr_ctc_grad_from_lattice_wide), and
- * spelling rows of subword units into characters (pgasr_unit_spell). */
+ * spelling rows of subword units into characters (pgasr_unit_spell), and the slot masses behind N-best confidences
+ * (pgasr_edit_ops_slot_mass). */
 #define PGASR_ABI_VERSION 7
 
 int pgasr_abi_version(void);
@@ -456,6 +457,37 @@ int pgasr_edit_ops(const int32_t* ref, const int32_t* ref_len, int ref_stride,
                    const int32_t* hyp, const int32_t* hyp_len, int hyp_stride, int N,
                    int32_t* counts, int8_t* ops, int32_t* n_ops, long long* confusion, int vocab,
                    void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * A10-CONF  slot masses of operation strings (csrc/confidence.hip): the reduction behind N-best confidences (Wessel et al.,
+ * IEEE Trans. SAP 9(3), 2001).  Align every hypothesis of a list to the chosen one with pgasr_edit_ops; the confidence of a
+ * position of the chosen row is the posterior mass of the hypotheses whose alignment has a hit there.  Because the alignment
+ * is the contractual one of A10-OPS, the result is a pure function of operation strings and weights.
+ *   ops (groups * per_group, ops_stride) int8, n_ops (groups * per_group) int32: what pgasr_edit_ops writes (0 hit, 1 substitution,
+ *     2 deletion, 3 insertion, left to right; entries from n_ops on are not read).  Pair p = g * per_group + n belongs to group g.
+ *     A byte outside 0 .. 3 in front of n_ops is skipped.
+ *   side = 0: slots are reference positions; operations 0, 1, 2 consume a slot, 2 is the side's own gap operation, 3 the "other"
+ *     one.  side = 1: slots are hypothesis positions; 0, 1, 3 consume a slot, 3 is the own gap operation, 2 the other one.
+ *     The slot of a slot-consuming operation is the number of slot-consuming operations in front of it; the gap of an "other"
+ *     operation is the number of slot-consuming operations in front of it, 0 .. the slot count.
+ *   weight (groups * per_group) fp64.  A pair takes part iff its weight is finite and > 0 and 0 <= n_ops <= ops_stride.
+ *   n_slots[g]: the slot count of the group's first participating pair (the pivot's length), -1 if none takes part.  A
+ *     participating pair whose slot count differs from n_slots[g] or exceeds `slots` is left out and counted in left_out[g].
+ *   mass (groups, 4, slots + 1) fp64, every word written (nothing needs initialising):
+ *     [g][0][i] = sum over the participating pairs n that are not left out, ascending, of w_n where the operation on slot i is a hit,
+ *     [g][1][i] the same for substitutions, [g][2][i] for the own gap operation;
+ *     [g][3][j] = sum over those n, ascending, of w_n * (double)k_n(j), k_n(j) the number of "other" operations of pair n in gap j:
+ *       one product and one addition per pair and gap, and only where k_n(j) > 0;
+ *     every cell at or behind n_slots[g] is exactly 0, except [g][3][n_slots[g]], the last gap.
+ *   fp64, every product and sum rounded once, in the stated order; no floating-point atomics.  One launch, one workgroup per
+ *   group, (slots + 1) * 36 bytes of LDS; no workspace, no host synchronisation.
+ *   Checked before any HIP call: a null n_ops / weight / mass / n_slots / left_out, ops null with ops_stride > 0, groups or
+ *   per_group < 1, ops_stride or slots < 0, side outside {0, 1} -> PGASR_ERR_INVALID_ARG; ops_stride > 8190, slots > 4095,
+ *   per_group > 128, groups * per_group >= 2^31 -> PGASR_ERR_UNSUPPORTED.
+ * ---------------------------------------------------------------------------------------- */
+int pgasr_edit_ops_slot_mass(const int8_t* ops, const int32_t* n_ops, int ops_stride,
+                             const double* weight, int groups, int per_group, int side, int slots,
+                             double* mass, int32_t* n_slots, int32_t* left_out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * A12  REINFORCE gradient on the logits:

@@ -498,6 +498,85 @@ class CTCDecoder:
         return self.mbr_from_list(nb, rs.total, vocab=V, risk_unit=risk_unit, word_delimiter=word_delimiter,
                                   posterior_scale=posterior_scale, max_hyp_len=max_hyp_len)
 
+    def confidence(self, md, pivot="mbr", unit="char", word_delimiter=None, max_hyp_len=None):
+        """N-best confidences of a decoded hypothesis (``hipops.nbest_confidence``; Wessel et al. 2001): ``md`` an ``MBRDecoded``
+        (``mbr_decode`` / ``mbr_from_list``), whose list is aligned to the pivot row and weighted with ``md.posterior``.
+        pivot: "mbr" (default: ``md.best``, the row ``md.tokens`` holds), "map" (row 0, the best-scored one) or a (B) int tensor of
+        ranks.  unit: "char" (the list's own units) or "word" (words split at ``word_delimiter``, default the alphabet's " "; at
+        most 64 symbols, ValueError above: a subword unit may hold a space).
+        Returns ``hipops.NBestConfidence``: per position of the pivot row the posterior mass of the hypotheses whose canonical
+        alignment (diagonal, then deletion, then insertion on the walk back) has a hit there, the masses that substitute or drop
+        it, and per gap the expected number of extra symbols.  No host synchronisation."""
+        nb = md.nbest
+        B = nb.tokens.shape[1]
+        if isinstance(pivot, str):
+            if pivot not in ("mbr", "map"):
+                raise ValueError(f"pivot must be 'mbr', 'map' or a tensor of ranks (got {pivot!r})")
+            piv = md.best if pivot == "mbr" else torch.zeros(B, dtype=torch.int32, device=nb.tokens.device)
+        else:
+            piv = torch.as_tensor(pivot, device=nb.tokens.device).to(torch.int32).reshape(-1)
+            if piv.numel() != B:
+                raise ValueError(f"pivot: one rank per utterance is wanted ({B}), got {piv.numel()}")
+        if unit not in ("char", "word"):
+            raise ValueError(f"unit must be 'char' or 'word' (got {unit!r})")
+        delim = None
+        if unit == "word":
+            if len(self.alphabet) > hipops.MAX_VOCAB_NARROW:
+                raise ValueError(f"unit='word': not over {len(self.alphabet)} > {hipops.MAX_VOCAB_NARROW} symbols -- a subword unit may "
+                                 f"hold a space; take unit='char' (the units are the symbols)")
+            delim = self._word_delimiter(word_delimiter)
+        return hipops.nbest_confidence(nb.tokens, nb.lengths, nb.count, md.posterior.contiguous(), piv.contiguous(), unit=unit,
+                                       delimiter=delim, max_hyp_len=max_hyp_len, vocab=len(self.alphabet))
+
+    def decode_words(self, log_probs, lengths=None, beam_size=16, nbest=16, pivot="map", posterior_scale=1.0, word_delimiter=None,
+                     **scoring):
+        """Words with time stamps and confidences: ``mbr_decode`` (``scoring``: its scoring keywords -- acoustic, lm, lm_alpha,
+        lm_beta, am_weight, word_lm, ..., max_hyp_len, blank), ``confidence`` at character and at word level against the pivot row
+        ("map": row 0, "mbr": the row of least risk), and ``align_batch`` of the pivot rows.  Alphabets of at most 64 symbols
+        with a " " (or ``word_delimiter``).  Returns, per utterance, a list of
+        ``(word, start_frame, end_frame, confidence, [character confidences])`` -- words as str.split(" ") cuts the row, an empty
+        word included with span (-1, -1) and its own confidence; spans from ``word_spans`` (first frame of the first character,
+        one past the last frame of the last; (-1, -1) where the row does not fit the frames).  Copies the results to the host."""
+        if pivot not in ("map", "mbr"):
+            raise ValueError(f"pivot must be 'map' or 'mbr' (got {pivot!r})")
+        for name in ("risk_unit", "unit_spelling"):
+            if name in scoring:
+                raise ValueError(f"{name}: decode_words scores characters and words of the list itself; not a keyword here")
+        delim = self._word_delimiter(word_delimiter)
+        blank = int(scoring.get("blank", 0))
+        md = self.mbr_decode(log_probs, lengths, beam_size=beam_size, nbest=nbest, posterior_scale=posterior_scale,
+                             word_delimiter=delim, **scoring)
+        return self.words_of_list(md, log_probs, lengths, pivot=pivot, word_delimiter=delim, blank=blank,
+                                  max_hyp_len=scoring.get("max_hyp_len"))[0]
+
+    def words_of_list(self, md, log_probs, lengths=None, pivot="map", word_delimiter=None, blank=0, max_hyp_len=None):
+        """``decode_words`` behind the search, for a list the caller already holds: ``md`` an ``MBRDecoded`` over ``log_probs``
+        (T,B,V) / ``lengths``, ``pivot`` as ``confidence`` takes it.  Returns (words, character confidences, word confidences):
+        the per-utterance word lists of ``decode_words`` and the two ``hipops.NBestConfidence`` they were read from."""
+        delim = self._word_delimiter(word_delimiter)
+        cc = self.confidence(md, pivot=pivot, unit="char", max_hyp_len=max_hyp_len)
+        wc = self.confidence(md, pivot=pivot, unit="word", word_delimiter=delim, max_hyp_len=max_hyp_len)
+        Lmax = min(cc.tokens.shape[1], hipops.ALIGN_MAX_TOKENS)
+        al = self.align_batch(log_probs, cc.tokens[:, :Lmax].contiguous(), cc.lengths.clamp(max=Lmax), lengths, blank=blank)
+        tok, tl = cc.tokens.cpu(), cc.lengths.cpu().tolist()
+        cconf, wconf = cc.conf.cpu(), wc.conf.cpu()
+        st, en = al.token_start.cpu(), al.token_end.cpu()
+        out = []
+        for b in range(tok.shape[0]):
+            n = min(int(tl[b]), Lmax)
+            row = [int(k) for k in tok[b, :n]]
+            spans = word_spans(st[b, :n].tolist(), en[b, :n].tolist(), row, delim)
+            words, first = [], 0
+            for w, (s0, s1) in enumerate(spans):
+                last = first
+                while last < n and row[last] != delim:
+                    last += 1
+                text = "".join(self.alphabet[k].replace("\n", "") for k in row[first:last])
+                words.append((text, s0, s1, float(wconf[b, w]), [float(x) for x in cconf[b, first:last]]))
+                first = last + 1
+            out.append(words)
+        return out, cc, wc
+
     def align_batch(self, log_probs, tokens, token_lengths, lengths=None, blank=0):
         """Forced alignment on the device: log_probs (T,B,V) fp32 GPU tensor of natural-log probabilities, tokens (B,Lmax) /
         token_lengths (B) int32 the transcripts (Lmax <= 1023).  Returns ``hipops.CTCAlignment`` (score, frame_label, frame_token,

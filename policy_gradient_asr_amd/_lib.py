@@ -101,6 +101,8 @@ SIGNATURES = {
     "pgasr_edit_ops_workspace_bytes": (C.c_size_t, [C.c_int] * 3),
     "pgasr_edit_ops": (C.c_int, [c_i32p, c_i32p, C.c_int, c_i32p, c_i32p, C.c_int, C.c_int,
                                  c_i32p, c_ptr, c_i32p, c_ptr, C.c_int, c_ptr, C.c_size_t, c_ptr]),
+    "pgasr_edit_ops_slot_mass": (C.c_int, [c_ptr, c_i32p, C.c_int, c_ptr, C.c_int, C.c_int, C.c_int, C.c_int,
+                                           c_ptr, c_i32p, c_i32p, c_ptr]),
     "pgasr_reinforce_grad": (C.c_int, [c_f32p, c_i32p, c_f32p, c_i32p, C.c_int, C.c_int, C.c_int, C.c_int,
                                        c_f32p, c_ptr]),
     "pgasr_beam_workspace_bytes": (C.c_size_t, [C.c_int] * 4),

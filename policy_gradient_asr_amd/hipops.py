@@ -1162,6 +1162,128 @@ def word_edit_ops(ref, ref_len, hyp, hyp_len, delimiter, want_ops=True, max_work
     return WordEditOps(eo.counts, eo.ops, eo.n_ops, ref_words, hyp_words)
 
 
+SlotMass = collections.namedtuple("SlotMass", "hit sub gap other n_slots left_out")
+NBestConfidence = collections.namedtuple("NBestConfidence", "tokens lengths conf substituted deleted inserted left_out")
+SLOT_MASS_MAX_SLOTS = 4095       # csrc/confidence.hip (and ops_stride <= 8190)
+SLOT_MASS_MAX_PER_GROUP = 128
+_SLOT_SIDES = {"ref": 0, "hyp": 1}
+
+
+def _slot_mass_launch(ops, n_ops, ops_stride, weight, groups, per_group, side, slots, mass, n_slots, left_out):
+    with _timed("edit_ops_slot_mass"):
+        st = _lib.load().pgasr_edit_ops_slot_mass(_p(ops) if ops_stride else 0, _p(n_ops), ops_stride, _p(weight), groups, per_group,
+                                                  side, slots, _p(mass), _p(n_slots), _p(left_out), _stream())
+    _lib.check(st, "pgasr_edit_ops_slot_mass")
+
+
+def edit_ops_slot_mass(ops, n_ops, weight, per_group, side="ref", slots=None):
+    """Per-position masses of groups of operation strings (pgasr_edit_ops_slot_mass; include/pgasr_hip.h, A10-CONF): ops (P,stride)
+    int8 / n_ops (P) int32 as ``edit_ops(want_ops=True)`` returns them, weight (P) float64, pair p = g * per_group + n in group g,
+    per_group <= 128.  side="ref" indexes slots by reference position (own gap operation: the deletion, other: the insertion),
+    side="hyp" by hypothesis position (own: insertion, other: deletion).  Returns ``SlotMass``: hit / sub / gap / other
+    (groups, slots+1) float64 views of one tensor -- per slot the weight of the participating pairs (weight finite and > 0) with a
+    hit / a substitution / the own gap operation there, in ascending pair order, and per gap the weighted count of other operations
+    --, n_slots (groups) int32 the slot count of the group's first participating pair (-1: none) and left_out (groups) int32 the
+    participating pairs with another slot count or more than ``slots``.  slots: None reads the largest possible count from the
+    device (ONE host synchronisation); a number avoids it.  One launch."""
+    _req(ops, torch.int8, "ops"); _req(n_ops, torch.int32, "n_ops"); _req(weight, torch.float64, "weight")
+    if side not in _SLOT_SIDES:
+        raise ValueError(f"side must be 'ref' or 'hyp' (got {side!r})")
+    per_group = int(per_group)
+    if ops.dim() != 2 or per_group < 1 or ops.shape[0] % per_group or n_ops.numel() != ops.shape[0] or weight.numel() != ops.shape[0]:
+        raise _lib.PgasrError("edit_ops_slot_mass wants ops (P,stride), n_ops (P) and weight (P) with P a multiple of per_group")
+    P, stride = ops.shape
+    if P == 0:
+        raise _lib.PgasrError("edit_ops_slot_mass: no pairs")
+    if slots is None:
+        slots = min(int(n_ops.clamp(0, stride).max().item()), SLOT_MASS_MAX_SLOTS)
+    slots = int(slots)
+    if slots < 0:
+        raise ValueError(f"slots must be >= 0 (got {slots})")
+    groups = P // per_group
+    dev = ops.device
+    mass = torch.empty(groups, 4, slots + 1, dtype=torch.float64, device=dev)
+    meta = torch.empty(2, groups, dtype=torch.int32, device=dev)
+    _slot_mass_launch(ops, n_ops, stride, weight, groups, per_group, _SLOT_SIDES[side], slots, mass, meta[0], meta[1])
+    return SlotMass(mass[:, 0], mass[:, 1], mass[:, 2], mass[:, 3], meta[0], meta[1])
+
+
+def nbest_confidence(tokens, lengths, count, posterior, pivot, unit="char", delimiter=None, max_hyp_len=None,
+                     max_workspace_bytes=256 << 20, vocab=None):
+    """N-best confidences (Wessel et al. 2001): every hypothesis of a list aligned to the chosen one, the confidence of a position
+    being the posterior mass of the hypotheses that agree with it there.  tokens (N,B,stride) / lengths (N,B) / count (B) int32 as
+    the N-best searches return them (narrow or wide), posterior (N,B) float64 as ``mbr_select`` returns it (rows with 0 take no
+    part), pivot (B) int32 the chosen row of every utterance.  The B * N pairs (pivot row of b, row n of b) are expanded in bounded
+    chunks of whole utterances through ``edit_ops(want_ops=True)`` -- the canonical alignment, pivot as the reference -- and
+    ``pgasr_edit_ops_slot_mass`` with side="ref"; unit="word" runs ``word_ids`` first and aligns the id rows (words split at the
+    token ``delimiter`` as str.split(" ") cuts them).  vocab: the number of symbols, if the caller knows it: unit="word" over more
+    than 64 raises ValueError, because a subword unit may hold a space.
+    max_hyp_len: None, or a cap on the rows' length: a longer row takes no part, and neither does a list whose pivot is longer.
+    Returns ``NBestConfidence``: tokens (B,L) / lengths (B) int32 the pivot rows (unit="word": tokens None, lengths the pivots'
+    word counts), and (B,L+1) float64 conf (hit mass), substituted, deleted (the mass of hypotheses
+    without a partner for the position) and inserted (per gap j, in front of position j, the expected number of extra symbols);
+    left_out (B) int32 as ``edit_ops_slot_mass`` counts it.  conf + substituted + deleted is the participating mass at every
+    position.  No host synchronisation."""
+    lib = _lib.load()
+    _req(tokens, torch.int32, "tokens"); _req(lengths, torch.int32, "lengths"); _req(count, torch.int32, "count")
+    _req(posterior, torch.float64, "posterior"); _req(pivot, torch.int32, "pivot")
+    if tokens.dim() != 3 or tuple(lengths.shape) != tuple(tokens.shape[:2]) or count.numel() != tokens.shape[1] \
+            or tuple(posterior.shape) != tuple(lengths.shape) or pivot.numel() != tokens.shape[1]:
+        raise _lib.PgasrError("nbest_confidence wants tokens (N,B,stride), lengths (N,B), count (B), posterior (N,B) and pivot (B)")
+    if unit not in ("char", "word"):
+        raise ValueError(f"unit must be 'char' or 'word' (got {unit!r})")
+    if unit == "word" and (delimiter is None or int(delimiter) < 0):
+        raise ValueError("unit='word' needs delimiter, the token id of the alphabet's ' ' symbol")
+    if unit == "word" and vocab is not None and int(vocab) > MAX_VOCAB_NARROW:
+        raise ValueError(f"unit='word': not over {int(vocab)} > {MAX_VOCAB_NARROW} symbols -- a subword unit may hold a space, so words "
+                         f"cannot be split at a delimiter token; take unit='char' (the units are the symbols)")
+    N, B, stride = tokens.shape
+    if N < 1 or N > SLOT_MASS_MAX_PER_GROUP:
+        raise _lib.PgasrError(f"nbest_confidence takes 1 <= N <= {SLOT_MASS_MAX_PER_GROUP} hypotheses per utterance (got {N})")
+    if max_hyp_len is not None and int(max_hyp_len) < 0:
+        raise ValueError(f"max_hyp_len must be >= 0 (got {max_hyp_len})")
+    cap = stride if max_hyp_len is None else min(stride, int(max_hyp_len))
+    S = max(1, cap)
+    dev = tokens.device
+    piv = pivot.long().clamp(0, N - 1)
+    cols = torch.arange(B, device=dev)
+    ln = lengths.clamp(0, stride)
+    rows = torch.arange(N, device=dev).view(N, 1) < count.clamp(0, N).view(1, B)
+    valid = rows & (ln <= cap)
+    valid = valid & valid[piv, cols].view(1, B)
+    ln = torch.where(valid, ln, torch.zeros_like(ln))
+    weight = torch.where(valid, posterior, torch.zeros_like(posterior)).t().contiguous()            # (B,N): pair b * N + n
+    piv_tok = tokens[piv, cols, :S].contiguous()                                                     # (B,S)
+    piv_len = ln[piv, cols].contiguous()
+    L = S + 1 if unit == "word" else S                      # word rows: a row of S tokens has at most S + 1 words
+    ops_stride = 2 * L
+    if L > SLOT_MASS_MAX_SLOTS:
+        raise _lib.PgasrError(f"nbest_confidence: rows of {S} tokens exceed the limit of {SLOT_MASS_MAX_SLOTS} positions")
+    mass = torch.empty(B, 4, L + 1, dtype=torch.float64, device=dev)
+    meta = torch.empty(2, B, dtype=torch.int32, device=dev)
+    n_words = torch.empty(B, dtype=torch.int32, device=dev) if unit == "word" else None
+    per_pair = int(lib.pgasr_edit_ops_workspace_bytes(L, L, 1))
+    by_ws = int(max_workspace_bytes) // max(per_pair * N, 1)
+    by_rows = PAIR_DIST_CHUNK_ELEMS // ((2 if unit == "char" else 4) * (S + 1) * N)
+    step = max(1, min(B, by_ws, by_rows))                   # utterances per chunk
+    with _timed("nbest_confidence"):
+        for b0 in range(0, B, step):
+            b1 = min(B, b0 + step)
+            G = b1 - b0
+            ref = piv_tok[b0:b1].unsqueeze(1).expand(G, N, S).reshape(G * N, S)
+            rl = piv_len[b0:b1].unsqueeze(1).expand(G, N).reshape(G * N).contiguous()
+            hyp = tokens[:, b0:b1, :S].permute(1, 0, 2).reshape(G * N, S)
+            hl = ln[:, b0:b1].t().reshape(G * N).contiguous()
+            if unit == "word":
+                ref, rl, hyp, hl = word_ids(ref.contiguous(), rl, hyp.contiguous(), hl, int(delimiter))
+                n_words[b0:b1] = rl.view(G, N)[:, 0]
+            eo = edit_ops(ref.contiguous(), rl, hyp.contiguous(), hl, want_ops=True, max_workspace_bytes=max_workspace_bytes)
+            _slot_mass_launch(eo.ops, eo.n_ops, ops_stride, weight[b0:b1], G, N, 0, L, mass[b0:b1], meta[0, b0:b1], meta[1, b0:b1])
+    if unit == "word":
+        return NBestConfidence(None, n_words, mass[:, 0], mass[:, 1], mass[:, 2], mass[:, 3], meta[1])
+    return NBestConfidence(piv_tok, piv_len, mass[:, 0], mass[:, 1], mass[:, 2], mass[:, 3], meta[1])
+
+
 def reinforce_grad(scores, path, coef, lengths, out=None, accumulate=False):
     lib = _lib.load()
     _req(scores, torch.float32, "scores"); _req(path, torch.int32, "path")

@@ -75,6 +75,45 @@ def error_counts(targets, tg_len, tokens, tok_len, delimiter):
     return cc, wc
 
 
+def hyp_correct(targets, tg_len, hyp, hyp_len, unit="char", delimiter=None):
+    """Which positions of a hypothesis are right: targets (B,L) / hyp (B,T) int32 on the GPU with their lengths (B).  Returns
+    (correct (B,T+1) float64, n (B) int32) on the device: correct[b, j] = 1.0 where the canonical alignment of hypothesis b to its
+    transcript (``hipops.edit_ops``) has a hit on hypothesis position j, 0.0 elsewhere and from n[b] on, n the hypothesis' length.
+    unit="word": positions are words, split at the token ``delimiter`` as str.split(" ") cuts them (correct is (B,T+2), n the
+    word counts).  The slot-mass kernel with side="hyp", one pair per group and weight 1 (include/pgasr_hip.h, A10-CONF): the
+    labels ``confidence_nce`` scores confidences against.  No host round trip."""
+    if unit not in ("char", "word"):
+        raise ValueError(f"unit must be 'char' or 'word' (got {unit!r})")
+    if unit == "word":
+        if delimiter is None or int(delimiter) < 0:
+            raise ValueError("unit='word' needs delimiter, the token id of the alphabet's ' ' symbol")
+        targets, tg_len, hyp, hyp_len = hipops.word_ids(targets, tg_len, hyp, hyp_len, int(delimiter))
+    eo = hipops.edit_ops(targets, tg_len, hyp, hyp_len, want_ops=True)
+    one = torch.ones(hyp.shape[0], dtype=torch.float64, device=hyp.device)
+    sm = hipops.edit_ops_slot_mass(eo.ops, eo.n_ops, one, 1, side="hyp", slots=hyp.shape[1])
+    return sm.hit, sm.n_slots
+
+
+def confidence_nce(conf, correct, eps=1e-12):
+    """NIST's normalised cross entropy of confidences, (H_max - H_conf) / H_max in bits: conf and correct equally shaped tensors
+    (or sequences) over the scored positions, correct > 0.5 meaning right.  H_max = -(n_c log2 p_c + (n - n_c) log2(1 - p_c))
+    with p_c = n_c / n the base rate, H_conf = -(sum over the right positions of log2 c + sum over the wrong ones of
+    log2(1 - c)), c clipped to [eps, 1 - eps]; computed in fp64.  1 for perfect confidences, 0 for the base rate everywhere,
+    negative for worse; NaN when all or none (or no) positions are right.  Returns a Python float (synchronises)."""
+    conf = torch.as_tensor(conf).to(torch.float64).reshape(-1)
+    right = torch.as_tensor(correct).to(conf.device).to(torch.float64).reshape(-1) > 0.5
+    if conf.numel() != right.numel():
+        raise ValueError("confidence_nce: conf and correct must have as many elements")
+    n, nc = int(right.numel()), int(right.sum())
+    if n == 0 or nc == 0 or nc == n:
+        return float("nan")
+    c = conf.clamp(float(eps), 1.0 - float(eps))
+    pc = torch.tensor(nc / n, dtype=torch.float64)
+    h_max = -(nc * torch.log2(pc) + (n - nc) * torch.log2(1.0 - pc))
+    h_conf = -(torch.log2(c[right]).sum() + torch.log2(1.0 - c[~right]).sum())
+    return float((h_max - h_conf.cpu()) / h_max)
+
+
 def unit_error_counts(targets, tg_len, tokens, tok_len, spelling):
     """``edit_counts`` for rows of SUBWORD UNITS, counted on their spelled text: targets (B,L) / tokens (B,T) int32 unit rows on the GPU
     with their lengths, ``spelling`` the alphabet's ``units.UnitSpelling`` (with a " ").  Both sides go through ``hipops.unit_spell``;

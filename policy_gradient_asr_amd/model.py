@@ -619,6 +619,7 @@ def predict(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=N
             error_report=False, units_path=None, wide_beam=False, wide_second_pass=False, unit_lm_path=None, unit_lm_alpha=0.0,
             unit_lm_beta=0.0, rescore_unit_lm_path=None, rescore_unit_alpha=0.0, rescore_unit_beta=0.0, spelled=False,
             frame_stack=None, fused_word_lm_path=None, fused_word_alpha=0.0, fused_word_beta=0.0, oov_penalty=0.0,
+            word_confidence=False, confidence_pivot="map",
             wide_hotwords=False, hotwords_path=None, hotword_weight=1.0, hotword_boost=1.0):
     """model.py:277-339: load model_best.pth, forward, beam=5 prefix search (device side, batched),
     collapse_fn, CER/WER, predicted.txt.  Frames are cut by the FEATURE mask (the reference cuts the
@@ -711,7 +712,19 @@ def predict(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=N
     history) + fused_word_beta, the way out of the lexicon ``oov_penalty`` (<= 0; -inf: only lexicon words), and the final beam is
     ranked with the pending word and </s> scored; the first-pass scores are then fused scores.  beam_size >= 1, an alphabet of at most
     64 symbols with the ' ' symbol; not together with lm_path, hotwords_path, lm_fast, wide_beam or unit_lm_path (ValueError naming
-    the option).  ``rescore_word_lm_path`` stays the second pass it is."""
+    the option).  ``rescore_word_lm_path`` stays the second pass it is.
+    word_confidence: False (default: everything above, nothing else) or True, with nbest >= 2 and an alphabet of at most 64 symbols
+    with the ' ' symbol (ValueError naming what is missing; not for subword models -- units_path --, whose units may hold a space):
+    every word of a decoded hypothesis gets its N-best confidence and its time span.  The posterior over each list is
+    softmax(-mbr_scale * score) as for ``mbr`` (the rescored totals where there is a second pass, the exact CTC likelihood
+    without); the list is aligned to the pivot row -- confidence_pivot="map": the best-scored row, what is written to predicted.txt
+    unless mbr=True chooses another; "mbr": the row of least expected character errors -- and a word's confidence is the posterior
+    mass of the hypotheses that have the word there (``CTCDecoder.confidence``; csrc/confidence.hip); the pivot rows are force-aligned
+    for the spans (``CTCDecoder.align_batch``, ``word_spans``).  ``words.tsv`` in model_path gets one line per word: utterance, word
+    index, word, start frame, end frame (one past the last; -1 -1 for an empty word or a row that does not fit its frames),
+    confidence -- in INPUT frames under a frame_stack policy, as ``align`` writes them.  The word and character normalised cross
+    entropies of the confidences against the transcripts (``metrics.confidence_nce``) are printed.  predicted.txt, the rates and
+    every other output stay what they are."""
     import os
     import functools
     import torch.utils.data as tud
@@ -742,6 +755,14 @@ def predict(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=N
         raise ValueError("minimum-Bayes-risk decoding needs a list: give nbest >= 2 with mbr=True")
     if mbr and mbr_unit not in ("char", "word"):
         raise ValueError(f"mbr_unit must be 'char' or 'word' (got {mbr_unit!r})")
+    if word_confidence:
+        if nbest < 2:
+            raise ValueError("word_confidence: the confidences come from an N-best list; give nbest >= 2 with it")
+        if units_path is not None:
+            raise ValueError("word_confidence: not for subword models (units_path) -- a unit may hold a space, so the list has no "
+                             "word boundaries of its own")
+        if confidence_pivot not in ("map", "mbr"):
+            raise ValueError(f"confidence_pivot must be 'map' or 'mbr' (got {confidence_pivot!r})")
     if wide_hotwords:
         for name, given in (("wide_beam", bool(wide_beam)), ("units_path", units_path is not None),
                             ("hotwords_path", hotwords_path is not None)):
@@ -775,6 +796,12 @@ def predict(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=N
         if " " not in char2ind:
             raise ValueError("fused_word_lm_path needs an alphabet with the ' ' symbol")
     ind2char = {char2ind[k]: k for k in char2ind}
+    if word_confidence:
+        if len(alphabet) > hipops.MAX_VOCAB_NARROW:
+            raise ValueError(f"word_confidence: not over {len(alphabet)} > {hipops.MAX_VOCAB_NARROW} symbols -- a subword unit may hold "
+                             f"a space")
+        if " " not in char2ind:
+            raise ValueError("word_confidence needs an alphabet with the ' ' symbol")
     unit_args = {}
     if units_path is not None:
         from .units import SubwordUnits
@@ -848,7 +875,8 @@ def predict(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=N
         _check_features(features, n_feats, test_dataset)
     else:
         _check_features(features, n_in, test_dataset, stack=frame_stack.stack)
-        unit_args = dict(unit_args, frame_stack=frame_stack)
+        if not word_confidence:      # word spans need the input frame counts: the batch is then stacked in the loop, as align does
+            unit_args = dict(unit_args, frame_stack=frame_stack)
     collate_custom = functools.partial(_collate, device=dev, features=features, target_rate=target_rate, **unit_args)
     # a units file: the device's collapse is the whole collapse -- collapse_fn would merge a unit's last character with the next unit's first
     to_text = collapse_fn if units_path is None else (lambda text: text)
@@ -901,11 +929,16 @@ def predict(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=N
     targets, predicted, tot_cer, tot_wer, n = [], [], 0.0, 0.0, 0
     nbest_lines, tot_oracle = [], 0.0
     mbr_lines, map_cer, map_wer = [], 0.0, 0.0
+    word_lines, conf_pairs = [], {"word": ([], []), "char": ([], [])}
     print("Total number of examples: ", len(test_dataset))
     with torch.no_grad():
         for step, batch in enumerate(loader, 1):
             print("Decoding step {}/{}...".format(step, len(loader)))
             x, t, fmask, tmask = _to_device(batch, dev)
+            if word_confidence and frame_stack is not None:
+                n_frames = fmask.sum(1).to(torch.int64).cpu()
+                x, fmask = frame_stack(x.to(torch.float32).contiguous(), fmask)
+                fmask = fmask.squeeze(1)
             logits, in_len = model.logits(x, fmask)
             lp = Fh.LogSoftmaxFn.apply(logits)
             if nbest > 1:
@@ -934,6 +967,29 @@ def predict(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=N
                     for i in range(mbest.shape[0]):
                         mbr_lines.append("{}\t{}\t{:.6f}\t{:.6f}\n".format(n + i, int(mbest[i]), float(mrisk[int(mbest[i]), i]),
                                                                           float(mrisk[0, i])))
+                if word_confidence:
+                    from .metrics import hyp_correct
+                    if mbr and mbr_unit == "char":
+                        cmd = md
+                    else:
+                        score = rs.total if total is not None else decoder.rescore(lp, in_len, nb, lm=None).total
+                        cmd = decoder.mbr_from_list(nb, score, vocab=lp.shape[2], risk_unit="char", posterior_scale=mbr_scale)
+                    if confidence_pivot == "mbr":
+                        piv = cmd.best
+                    else:      # the best-scored row: the second pass' first where there is one, the search's otherwise
+                        piv = rs.order[:, 0].to(torch.int32) if total is not None else torch.zeros_like(cmd.best)
+                    wlists, cc, wc = decoder.words_of_list(cmd, lp.contiguous(), in_len, pivot=piv, word_delimiter=char2ind[" "])
+                    t32, tl32 = t.to(torch.int32).contiguous(), tmask.sum(1).to(torch.int32).contiguous()
+                    for kind, c, delim in (("char", cc, None), ("word", wc, char2ind[" "])):
+                        right, n_pos = hyp_correct(t32, tl32, cc.tokens, cc.lengths, unit=kind, delimiter=delim)
+                        keep = torch.arange(right.shape[1], device=dev).view(1, -1) < n_pos.view(-1, 1)
+                        conf_pairs[kind][0].append(c.conf[:, :right.shape[1]][keep].cpu())
+                        conf_pairs[kind][1].append(right[keep].cpu())
+                    for i, wl in enumerate(wlists):
+                        for j, (word, s0, s1, wconf, _) in enumerate(wl):
+                            if frame_stack is not None and s0 >= 0:
+                                s0, s1 = frame_stack.input_span(s0, s1, n_frames[i])
+                            word_lines.append("{}\t{}\t{}\t{}\t{}\t{:.6f}\n".format(n + i, j, word, s0, s1, wconf))
                 # every hypothesis through collapse_fn on the host (the list is copied once); the oracle is over these strings,
                 # one edit-distance launch per batch
                 ntok, nlen, nscore, ncount = nb.tokens.cpu(), nb.lengths.cpu(), nb.score.cpu(), nb.count.cpu()
@@ -1003,6 +1059,13 @@ def predict(test_path, aud_path, alphabet_path, model_path, batch_size, maxlen=N
     if report is not None:
         report.write(model_path)
         print("Corpus " + "  ".join(report.totals_lines()))
+    if word_confidence:
+        from .metrics import confidence_nce
+        with open(os.path.join(model_path, "words.tsv"), "w") as fo:
+            fo.writelines(word_lines)
+        nce = {k: confidence_nce(torch.cat(v[0]), torch.cat(v[1])) if v[0] else float("nan") for k, v in conf_pairs.items()}
+        print("Confidence ({}-best, pivot {}) word NCE: {:>4f} character NCE: {:>4f}".format(nbest, confidence_pivot, nce["word"],
+                                                                                           nce["char"]))
     return cer, wer
 
 
